@@ -8,8 +8,18 @@ iSTFT x2  (inference.py:147-176 of the reference) on CascadedNet(n_fft=2048, hop
 weights (no baseline.pth is shipped), 30 s stereo 44.1 kHz synthetic audio -> 1292 frames, 11
 crops.  With N GPUs every rank separates its own song (songs shard with no collective): weak scaling.
 
-The same JSON line carries the other two single-GPU configurations as sub-objects, each timed over its own K steps
-between barriers after the headline region:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, runs W
+warm-up steps, times K steps, writes the outputs of the last timed step when `--dump-outputs DIR` is given, and prints
+one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the config).  Everything below --
+the other configurations, `roofline`, `cpu_baseline` and the detail file -- is measured with `--full` only.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy: inference (and
+--tta) the two stems `instruments` / `vocals` [2, L'] float32 as Separator.separate_wave returns them; train the step's
+`loss` (float64) and `state_sample`, a fixed seeded sample of 4 M elements of the updated state_dict (float32).  The
+inputs (audio, weights, training batch) are seeded, so two builds can be compared output for output.
+
+With `--full` the same JSON line carries the other two single-GPU configurations as sub-objects, each timed over its
+own K steps between barriers after the headline region:
     "tta"    configs[2]: the same song through Separator.separate_tta (23 crops)
     "train"  configs[3]: the train.py step (fwd + L1 + bwd [+ RCCL all-reduce of the flat gradient bucket over the N
              ranks] + Adam), batch 16 x [2,1025,256] per GPU
@@ -36,7 +46,7 @@ everywhere (mfma_mode 0).
 
 `python bench.py --gpus N` without a torch.distributed environment launches its own N ranks
 (python -m torch.distributed.run); under the driver's launcher it just reads RANK / WORLD_SIZE.
-`--mode infer|tta|train` times one configuration only (profiling runs).
+`--mode infer|tta|train` times one configuration only (profiling runs; with `--full` its `roofline` steps follow).
 """
 import argparse
 import ctypes
@@ -311,7 +321,7 @@ def compact_roofline(r, nclasses=6):
     return o
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE stdout line: the contract's keys, `roofline` (scalars + <= 6 class rows), `cpu_baseline`, and the other configurations as
     {value, ms_per_step, frac}.  Everything else (classes in full, per-kernel rows, notes) goes to gpurun_out/bench_detail.json."""
     line = {k: out[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
@@ -320,7 +330,8 @@ def compact_line(out):
     line['ms_per_step_per_rank'] = out.get('ms_per_step_per_rank')          # unrounded: ms_per_step is their MAX
     line['allreduce_ms'] = _r(out.get('allreduce_ms'), 4)
     line['config'] = {k: _r(v) for k, v in out['config'].items()}
-    line['roofline'] = compact_roofline(out.get('roofline'))
+    if 'roofline' in out:
+        line['roofline'] = compact_roofline(out['roofline'])
     for key in ('tta', 'train', 'train_bf16'):
         if key in out:
             sub = out[key]
@@ -345,7 +356,8 @@ def compact_line(out):
         cb = dict(out['cpu_baseline'])
         cb['sample'] = cb.get('sample', '')[:160]
         line['cpu_baseline'] = {k: _r(v) for k, v in cb.items()}
-    line['detail'] = os.path.relpath(DETAIL_PATH, ROOT) if DETAIL_PATH.startswith(ROOT) else DETAIL_PATH
+    if detail:
+        line['detail'] = os.path.relpath(DETAIL_PATH, ROOT) if DETAIL_PATH.startswith(ROOT) else DETAIL_PATH
     text = json.dumps(line, separators=(',', ':'))
     # belt and braces: shed optional parts rather than ever print a line a tail buffer would cut
     for drop in (('split_bf16',), ('fp32_mfma',), ('train_bf16',), ('tta', 'classes'), ('train', 'classes'), ('roofline', 'classes')):
@@ -367,6 +379,30 @@ def write_detail(out):
             json.dump(out, f, indent=1)
     except OSError as e:                      # a read-only checkout must not cost the run its line
         print('bench.py: could not write %s: %s' % (DETAIL_PATH, e), file=sys.stderr)
+
+
+# ---- --dump-outputs: what the timed path returned in its last timed step, as DIR/<name>.npy ------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+STATE_SAMPLE = 1 << 22             # elements of the updated state_dict a train dump keeps (a fixed seeded sample: 16 MB)
+
+
+def seeded_sample(flat, n, seed=0):
+    """A fixed, seeded, sorted sample of n indices of a 1-D array (all of it when it is not larger)."""
+    if flat.shape[0] <= n:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(flat.shape[0], n, replace=False))
+    return flat[idx]
+
+
+def dump_outputs(path, arrays):
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
 
 
 # ---- runtimes: the real one (HIP library + RCCL) and a stub that keeps ONLY the multi-rank control flow -----------------------
@@ -508,6 +544,16 @@ class NativeWorkloads(object):
     def cpu_baseline(self, which):
         return cpu_baseline_infer(self.sd) if which == 'infer' else cpu_baseline_train(self.sd, self.args.train_batch)
 
+    def step_outputs(self, kind, ret):
+        """What a caller of the timed path receives from one step, as float32 / float64 numpy arrays."""
+        if kind == 'infer':
+            y, v = ret
+            return {'instruments': y.float().cpu().numpy(), 'vocals': v.float().cpu().numpy()}
+        # train: Trainer.step returns the loss and updates the model in place
+        sd = self.net.state_dict()
+        flat = torch.cat([t.reshape(-1).float().cpu() for t in sd.values() if t.is_floating_point()]).numpy()
+        return {'loss': np.array([float(ret)], dtype=np.float64), 'state_sample': seeded_sample(flat, STATE_SAMPLE)}
+
 
 class StubWorkloads(object):
     """VR_BENCH_STUB=1: no GPU, no library -- sleeps stand for kernels, a gloo all-reduce of a bucket-sized CPU tensor for the gradient
@@ -550,6 +596,12 @@ class StubWorkloads(object):
     def cpu_baseline(self, which):
         return {'value': 1.0, 'unit': 'spectrogram-frames/sec', 'cores': 1, 'kind': 'port', 'sample': 'stub'}
 
+    def step_outputs(self, kind, ret):
+        rng = np.random.default_rng(0)
+        if kind == 'infer':
+            return {'instruments': rng.standard_normal((2, 4096)).astype(np.float32), 'vocals': rng.standard_normal((2, 4096)).astype(np.float32)}
+        return {'loss': np.array([0.5]), 'state_sample': seeded_sample(rng.standard_normal(1 << 12).astype(np.float32), 1 << 10)}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -564,6 +616,9 @@ def main():
     ap.add_argument('--wire', choices=['fp32', 'bf16'], default='fp32', help='gradient bucket format on xGMI (N > 1)')
     ap.add_argument('--bf16', action='store_true', help='--mode train: bf16 MFMA operands + bf16 bucket (an experiment, not configs[4])')
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure roofline, the other configurations and precisions and the CPU baseline, and write the detail file')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy')
     args = ap.parse_args()
     if args.tta:
         args.mode = 'tta'
@@ -598,17 +653,33 @@ def main():
         conv_totals, rows = min((wl.profile(step) for _ in range(3)), key=lambda r: sum(x[2] for x in r[1]))
         return roofline_from_rows(rows, pmc_name, conv_totals)
 
-    def run_infer(tta):
+    def recorded(step, kind):
+        """The step as timed when its outputs are to be dumped: it keeps what the step returned, and after the timed region
+        rank 0 writes the last timed step's outputs (before any further step runs)."""
+        last = {}
+
+        def timed_step():
+            last['out'] = step()
+
+        def dump():
+            if rank == 0:
+                dump_outputs(args.dump_outputs, wl.step_outputs(kind, last.get('out')))
+        return timed_step, dump
+
+    def run_infer(tta, record=False):
         pet()
         step = wl.infer_step(tta)
-        dt = rt.timed(step, args.steps, args.warmup)
+        timed_step, dump = recorded(step, 'infer') if record else (step, None)
+        dt = rt.timed(timed_step, args.steps, args.warmup)
+        if dump:
+            dump()
         crops = wl.crops_tta if tta else wl.crops_plain
         res = {'frames_per_sec': world * T * args.steps / dt, 'ms_per_step': dt / args.steps * 1e3,
                'computed_frames_per_sec': world * crops * CROP * args.steps / dt, 'crops_per_step_per_gpu': crops,
                'frames_per_step_per_gpu': T, 'ms_per_step_per_rank': [t / args.steps * 1e3 for t in rt.per_rank]}
         return res, step
 
-    def run_train(bf16=False, mfma_mode=None, configs4=False):
+    def run_train(bf16=False, mfma_mode=None, configs4=False, record=False):
         pet()
         wl.set_mode(bf16=bf16)
         if mfma_mode is not None:
@@ -616,7 +687,10 @@ def main():
         wire = 'bf16' if (configs4 or (bf16 and world > 1)) else args.wire
         step, reduce, zero_grad = wl.trainer(wire, exchange_at_world1=configs4)
         B = args.train_batch
-        dt = rt.timed(step, args.steps, args.warmup)
+        timed_step, dump = recorded(step, 'train') if record else (step, None)
+        dt = rt.timed(timed_step, args.steps, args.warmup)
+        if dump:
+            dump()
         per_rank = [t / args.steps * 1e3 for t in rt.per_rank]
         allreduce_ms = None
         if world > 1:
@@ -645,18 +719,18 @@ def main():
     primary_mode = 'infer' if args.mode == 'all' else args.mode
     out, extra = None, {}
     if primary_mode in ('infer', 'tta'):
-        res, step = run_infer(primary_mode == 'tta')
+        res, step = run_infer(primary_mode == 'tta', record=bool(args.dump_outputs))
         workload = ('configs[%d]: 30 s stereo 44.1 kHz synthetic song, STFT -> %d crops of 256 frames in one device batch -> '
                     'predict_mask -> stitch -> mask apply -> iSTFT x2%s' % (2 if primary_mode == 'tta' else 1, res['crops_per_step_per_gpu'],
                                                                              ' (--tta)' if primary_mode == 'tta' else '')) \
             if args.seconds == 30.0 else '%.0f s synthetic song, %d crops' % (args.seconds, res['crops_per_step_per_gpu'])
         metric = 'spectrogram-frames/sec (inference, CascadedNet n_fft=2048)'
         parallelism = 'replicas x%d (songs shard, no collective)' % world
-        roof = roofline(step, pmc(primary_mode))
+        roof = roofline(step, pmc(primary_mode)) if args.full else None
     else:
-        res, step = run_train(args.bf16)
+        res, step = run_train(args.bf16, record=bool(args.dump_outputs))
         workload, metric, parallelism = res['workload'], 'spectrogram-frames/sec (train-step, CascadedNet n_fft=2048)', res['parallelism']
-        roof = roofline(step, pmc('train'))
+        roof = roofline(step, pmc('train')) if args.full else None
         wl.end_train()
     if rank == 0:
         out = {
@@ -669,13 +743,14 @@ def main():
             'config': {'workload': workload, 'n_fft': N_FFT, 'hop': HOP, 'cropsize': CROP,
                        'frames_per_step_per_gpu': res['frames_per_step_per_gpu'], 'parallelism': parallelism,
                        'input_residency': 'inputs resident in HBM when the timed region starts'},
-            'roofline': roof,
         }
+        if args.full:
+            out['roofline'] = roof
         if 'computed_frames_per_sec' in res:
             out['config']['crops_per_step_per_gpu'] = res['crops_per_step_per_gpu']
             out['config']['computed_frames_per_sec'] = res['computed_frames_per_sec']
 
-    if args.mode == 'all':
+    if args.full and args.mode == 'all':
         # PCIe-inclusive rate of the headline workload: host numpy in, host numpy out (2 x 10.6 MB + 2 x 10.6 MB per step)
         if world == 1:
             dt = rt.timed(wl.infer_step(False, host=True), max(3, args.steps // 2), 1)
@@ -739,15 +814,16 @@ def main():
                 'train': {'value': b16_trn['frames_per_sec'], 'ms_per_step': b16_trn['ms_per_step']}}
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             pet()
             out['cpu_baseline'] = wl.cpu_baseline('infer' if primary_mode in ('infer', 'tta') else 'train')
             if args.mode == 'all':
                 out['train']['cpu_baseline'] = wl.cpu_baseline('train')
-        write_detail(out)
+        if args.full:
+            write_detail(out)
         sys.stdout.flush()
         sys.stderr.flush()
-        os.write(json_fd, (compact_line(out) + '\n').encode())
+        os.write(json_fd, (compact_line(out, detail=args.full) + '\n').encode())
     rt.finish()
 
 

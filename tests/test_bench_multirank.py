@@ -12,6 +12,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,10 @@ def _port():
 DETAIL = None          # set per test: the stub run's detail file goes to the test's tmp dir (a real gpurun_out/bench_detail.json stays untouched)
 
 
-def _run(cmd):
+LINE_KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype', 'config')
+
+
+def _run(cmd, keys=LINE_KEYS + ('roofline',)):
     env = dict(os.environ, VR_BENCH_STUB='1', OMP_NUM_THREADS='1', VR_BENCH_DETAIL=DETAIL)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
@@ -42,7 +46,7 @@ def _run(cmd):
     assert len(lines[0]) < 4096, len(lines[0])
     tail = (r.stderr + r.stdout)[-8000:]
     last = json.loads(tail.splitlines()[-1])
-    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'config', 'roofline'):
+    for key in keys:
         assert key in last, key
     return json.loads(lines[0])
 
@@ -80,10 +84,10 @@ def test_bench_control_flow_under_the_drivers_launcher(world, tmp_path):
     DETAIL = str(tmp_path / 'bench_detail.json')
     steps, warmup = 3, 1
     if world == 1:
-        cmd = [sys.executable, BENCH, '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup)]
+        cmd = [sys.executable, BENCH, '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--full']
     else:
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',
-               '--master-port', str(_port()), BENCH, '--gpus', str(world), '--steps', str(steps), '--warmup', str(warmup)]
+               '--master-port', str(_port()), BENCH, '--gpus', str(world), '--steps', str(steps), '--warmup', str(warmup), '--full']
     _check(_run(cmd), world, steps, warmup)
 
 
@@ -91,7 +95,30 @@ def test_bench_self_launch_two_ranks(tmp_path):
     """`python bench.py --gpus 2` without a launcher environment starts its own ranks (torch.distributed.run, 127.0.0.1)."""
     global DETAIL
     DETAIL = str(tmp_path / 'bench_detail.json')
-    _check(_run([sys.executable, BENCH, '--gpus', '2', '--steps', '2', '--warmup', '1']), 2, 2, 1)
+    _check(_run([sys.executable, BENCH, '--gpus', '2', '--steps', '2', '--warmup', '1', '--full']), 2, 2, 1)
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline's K timed steps and its line, nothing else (no roofline, other configurations, CPU baseline or
+    detail file); --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files, identical from run to run."""
+    global DETAIL
+    DETAIL = str(tmp_path / 'bench_detail.json')
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ('dump%d' % i)
+        out = _run([sys.executable, BENCH, '--gpus', '1', '--steps', '4', '--warmup', '1', '--dump-outputs', str(d)], keys=LINE_KEYS)
+        assert out['steps'] == 4 and out['warmup'] == 1 and out['higher_is_better'] is True and out['dtype'] == 'f32'
+        assert out['ms_per_step'] >= 1.0 * 0.95                                 # the stub's inference step sleeps 1 ms
+        assert abs(out['value'] - 1292 / (out['ms_per_step'] * 1e-3)) < 1e-6 * out['value']
+        for key in ('roofline', 'tta', 'train', 'train_bf16', 'fp32_mfma', 'split_bf16', 'cpu_baseline', 'detail'):
+            assert key not in out, key
+        assert not os.path.exists(DETAIL)
+        files = sorted(os.listdir(str(d)))
+        assert files == ['instruments.npy', 'vocals.npy'], files
+        dumps.append({f: np.load(str(d / f)) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        assert np.array_equal(a, dumps[1][f]), f
 
 
 def test_roofline_classes_price_each_kernel_against_its_own_roof():

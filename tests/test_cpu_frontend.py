@@ -1,5 +1,5 @@
 """CPU tests of the host-side front end: WAV codec, librosa.effects.trim restatement,
-dataset preparation pinned to the REFERENCE's own lib/dataset.py where it is importable (build container)."""
+dataset preparation pinned to the REFERENCE's own lib/dataset.py (its results are stored in tests/golden/reference_cpu.npz)."""
 import os
 import random
 import struct
@@ -95,30 +95,39 @@ def _fake_cache(tmp_path, sr, hop, n_fft, names=('s0', 's1', 's2'), lengths=(300
     return str(tmp_path / 'data')
 
 
-def test_dataset_preparation_matches_the_reference(vr, reference_lib, tmp_path, monkeypatch):
-    """make_pair / train_val_split / make_training_set / make_validation_set against lib/dataset.py on the same cache."""
-    import lib.dataset as ref_ds          # reference (librosa stubbed by the fixture; the cache exists, so it is never called)
+def _patch_digest(a):
+    """Exact identity of a validation patch (dtype, shape and bytes) without storing its megabytes."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return '%s %s %s' % (a.dtype.str, 'x'.join(map(str, a.shape)), hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def test_dataset_preparation_matches_the_reference(vr, tmp_path, monkeypatch):
+    """make_pair / train_val_split / make_training_set / make_validation_set against lib/dataset.py on the same cache (the
+    reference's results, with paths relative to the cache root and each validation patch as dtype, shape and SHA-256, are in
+    tests/golden/reference_cpu.npz: tests/golden/make_golden_cpu.py)."""
+    import json
+    ref = json.loads(str(np.load(os.path.join(os.path.dirname(__file__), 'golden', 'reference_cpu.npz'))['prep_json']))
     sr, hop, n_fft = 44100, 256, 512
     root = _fake_cache(tmp_path, sr, hop, n_fft)
+    full = lambda rows: [tuple(os.path.join(root, p) for p in row) for row in rows]        # noqa: E731
     monkeypatch.chdir(tmp_path)
-    assert vr.dataset.make_pair(root + '/mixtures', root + '/instruments') == ref_ds.make_pair(root + '/mixtures', root + '/instruments')
-    random.seed(3)
-    want_split = ref_ds.train_val_split(root, 'random', 0.34, [])
+    assert vr.dataset.make_pair(root + '/mixtures', root + '/instruments') == full(ref['pairs'])
+    want_split = (full(ref['train']), full(ref['val']))
     random.seed(3)
     got_split = vr.dataset.train_val_split(root, 'random', 0.34, [])
-    assert got_split == want_split
-    want_ts = ref_ds.make_training_set(want_split[0], sr, hop, n_fft)
+    assert [list(map(tuple, s)) for s in got_split] == [list(s) for s in want_split]
+    want_ts = [(os.path.join(root, a), os.path.join(root, b), c) for a, b, c in ref['training_set']]
     got_ts = vr.dataset.make_training_set(got_split[0], sr, hop, n_fft)
     assert [(a, b) for a, b, _ in got_ts] == [(a, b) for a, b, _ in want_ts]
     assert all(abs(float(g[2]) - float(w[2])) == 0.0 for g, w in zip(got_ts, want_ts))
-    os.makedirs('ref'); os.makedirs('got')
-    monkeypatch.chdir(tmp_path / 'ref')
-    want_p = ref_ds.make_validation_set(want_split[1] + want_split[0][:1], 160, sr, hop, n_fft, 64)
+    os.makedirs('got')
     monkeypatch.chdir(tmp_path / 'got')
+    want_p = ref['patches']
     got_p = vr.dataset.make_validation_set(got_split[1] + got_split[0][:1], 160, sr, hop, n_fft, 64)
     assert got_p == want_p and len(got_p) >= 3
-    for p in got_p:
-        a, b = np.load(str(tmp_path / 'got' / p)), np.load(str(tmp_path / 'ref' / p))
-        assert np.array_equal(a['X'], b['X']) and np.array_equal(a['y'], b['y'])
+    for p, (want_X, want_y) in zip(got_p, ref['patch_digests']):
+        a = np.load(str(tmp_path / 'got' / p))
+        assert _patch_digest(a['X']) == want_X and _patch_digest(a['y']) == want_y
     with pytest.raises(ValueError):
         vr.dataset.train_val_split(root, 'subdirs', 0.2, [['a', 'b']])

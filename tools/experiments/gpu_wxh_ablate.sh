@@ -2,7 +2,7 @@
 # wgrad_x3h_kernel phase ablation (VR_WXH_DBG bits: 1 no loads, 4 no split pass, 8 no tile maxima); results are wrong on purpose
 O=gpurun_out/wxh; mkdir -p $O
 for d in 0 1 4 8 5 13; do
-  VR_WXH_DBG=$d timeout 90 python bench.py --mode train --steps 3 --warmup 1 --no-cpu-baseline > $O/t$d.json 2> $O/t$d.err
+  VR_WXH_DBG=$d timeout 90 python bench.py --full --mode train --steps 3 --warmup 1 --no-cpu-baseline > $O/t$d.json 2> $O/t$d.err
 done
 python - <<'PY'
 import json

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/call1; rm -rf $O; mkdir -p $O
 timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=8 -s > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
 grep -n "passed\|failed\|error" $O/pytest.log | tail -4
-timeout 900 python bench.py > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
 python - <<'PY'
 import json
 t=open('gpurun_out/call1/bench_stdout.txt').read()

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/call10; rm -rf $O; mkdir -p $O
 run() { name=$1; mode=$2; shift; shift
-  env "$@" timeout 300 python bench.py --mode $mode --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
+  env "$@" timeout 300 python bench.py --full --mode $mode --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
   python - "$O/bench_$name.json" "$name" <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[1]).read().splitlines()[-1])

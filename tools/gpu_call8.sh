@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/call8; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_configs.py tests/test_golden.py tests/test_gpu_frontend.py tests/test_dropin_launcher.py -m gpu -q -p no:cacheprovider -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log
 for i in 1 2 3; do
-timeout 300 python bench.py --mode infer --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_infer$i.json 2> $O/bench_infer$i.err
+timeout 300 python bench.py --full --mode infer --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_infer$i.json 2> $O/bench_infer$i.err
 python - "$O/bench_infer$i.json" <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[1]).read().splitlines()[-1])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/evidence; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=6 -s > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 grep -n "passed\|failed\|error\|rc=" $O/pytest.log | tail -4
-timeout 900 python bench.py > $O/bench_all.json 2> $O/bench_all.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_all.json 2> $O/bench_all.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 j=json.load(open('gpurun_out/evidence/bench_all.json'))
@@ -19,10 +19,10 @@ print('cpu', j['cpu_baseline']['value'], j['train']['cpu_baseline']['value'])
 PY
 export VR_NO_SIDE_STREAM=1 VR_NO_SPLIT_BATCH=1
 for m in train infer tta; do
-  timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt_$m -o r -- python bench.py --mode $m --steps 2 --warmup 1 --no-cpu-baseline > $O/kt_$m.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt_$m -o r -- python bench.py --full --mode $m --steps 2 --warmup 1 --no-cpu-baseline > $O/kt_$m.log 2>&1
   python tools/rocpd_summary.py $(ls $O/kt_$m/*.db | head -1) $O/${m}_kernel_trace.md > /dev/null
-  timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_f_$m -o r -- python bench.py --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_f_$m.log 2>&1
-  timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_w_$m -o r -- python bench.py --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_w_$m.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_f_$m -o r -- python bench.py --full --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_f_$m.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_w_$m -o r -- python bench.py --full --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_w_$m.log 2>&1
   python tools/pmc_summary.py $(ls $O/pmc_f_$m/*.db | head -1) $(ls $O/pmc_w_$m/*.db | head -1) 2 $O/${m}_pmc.json $m > $O/${m}_pmc.md
 done
 # MFMA-pipe utilisation and wave states from the SQ counters, calibrated on tools/mfma_peak.hip (tools/pmc_sq_summary.py)
@@ -30,7 +30,7 @@ C="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT
 hipcc --offload-arch=gfx950 -O3 tools/mfma_peak.hip -o /tmp/mfma_peak 2>/dev/null
 timeout 300 rocprofv3 --kernel-trace --pmc $C -d $O/sq_cal -o r -- /tmp/mfma_peak > $O/sq_cal.log 2>&1
 for m in infer train; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $C -d $O/sq_$m -o r -- python bench.py --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/sq_$m.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $C -d $O/sq_$m -o r -- python bench.py --full --mode $m --steps 1 --warmup 0 --no-cpu-baseline > $O/sq_$m.log 2>&1
   python tools/pmc_sq_summary.py $(ls $O/sq_$m/*.db | head -1) $(ls $O/sq_cal/*.db | head -1) $O/${m}_sq_pmc.json > $O/${m}_sq_pmc.md
 done
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6call12; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_x3d.py tests/test_gpu_train.py tests/test_gpu_b16.py -m gpu -q -p no:cacheprovider -s -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|largest|loss:|  stg" $O/pytest.log | tail -12
 run() { name=$1; shift
-  env "$@" timeout 300 python bench.py --mode train --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
+  env "$@" timeout 300 python bench.py --full --mode train --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
   python - "$O/bench_$name.json" "$name" <<'PY'
 import json,sys
 try:

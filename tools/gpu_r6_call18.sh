@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r6call18; rm -rf $O; mkdir -p $O
 for pt in 512 768 1024 2048; do
-VR_WW_PTARGET=$pt VR_PROFILE_DUMP=1 timeout 300 python bench.py --mode train --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_$pt.json 2> $O/dump_$pt.txt
+VR_WW_PTARGET=$pt VR_PROFILE_DUMP=1 timeout 300 python bench.py --full --mode train --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_$pt.json 2> $O/dump_$pt.txt
 python - $O/dump_$pt.txt $pt $O/bench_$pt.json <<'PY'
 import re,sys,json
 rows=[ln for ln in open(sys.argv[1]) if '[vr-prof]' in ln and 'wgrad_wino' in ln]

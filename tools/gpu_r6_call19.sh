@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6call19; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_b16.py -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 for pt in 512 0 512 0; do
-VR_WW_PTARGET=$pt VR_PROFILE_DUMP=1 timeout 300 python bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$pt.json 2> $O/dump_$pt.txt
+VR_WW_PTARGET=$pt VR_PROFILE_DUMP=1 timeout 300 python bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$pt.json 2> $O/dump_$pt.txt
 python - $O/dump_$pt.txt $pt $O/bench_$pt.json <<'PY'
 import re,sys,json
 rows=[ln for ln in open(sys.argv[1]) if '[vr-prof]' in ln and ('wgrad_wino' in ln or 'wgrad_reduce' in ln)]

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6call20; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_b16.py -m gpu -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
 for pt in 512 0 512 0; do
-VR_WG_PTARGET=$pt timeout 300 python bench.py --mode train --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$pt.json 2> $O/bench_$pt.err
+VR_WG_PTARGET=$pt timeout 300 python bench.py --full --mode train --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$pt.json 2> $O/bench_$pt.err
 python - $O/bench_$pt.json $pt <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[1]).read().splitlines()[-1])

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6call27; rm -rf $O; mkdir -p $O
 for v in new old new old; do
   if [ $v = old ]; then export VR_LIB_PATH=$PWD/tools/_build/libvr_old_epilogue.so; else unset VR_LIB_PATH; fi
-  VR_PROFILE_DUMP=1 timeout 300 python bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$v.json 2> $O/dump_$v.txt
+  VR_PROFILE_DUMP=1 timeout 300 python bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$v.json 2> $O/dump_$v.txt
   python - $O/dump_$v.txt $v $O/bench_$v.json <<'PY'
 import re,sys,json
 rows=[ln for ln in open(sys.argv[1]) if '[vr-prof]' in ln]

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6call9; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_x3d.py -m gpu -q -p no:cacheprovider -s > $O/pytest_x3d.log 2>&1; echo "pytest x3d rc=$?"; grep -E "passed|failed|error" $O/pytest_x3d.log | tail -3; grep -E "^FAILED|^ERROR|Error|assert " $O/pytest_x3d.log | head -20
 run() { name=$1; mode=$2; shift; shift
-  env "$@" timeout 300 python bench.py --mode $mode --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
+  env "$@" timeout 300 python bench.py --full --mode $mode --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err
   python - "$O/bench_$name.json" "$name" <<'PY'
 import json,sys
 try:
