@@ -340,7 +340,7 @@ void ws_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, int TH, hipSt
 void conv_fill_tiling(ConvArgs& a, const ConvShape& s) {
     int wmt, wth;
     int wino_mt, thin_th;
-    if (thin16_pick(a, s, &thin_th)) { thin16_fill_tiling(a, thin_th); return; }
+    if (a.w_hi == 0 && thin16_pick(a, s, &thin_th)) { thin16_fill_tiling(a, thin_th); return; }
     X3Tile x3t;
     if (x3_pick(a, s, &x3t)) { x3_fill_tiling(a, x3t); return; }
     int x3d_mt;
@@ -397,10 +397,16 @@ double launch_conv(const ConvArgs& a_in, const ConvShape& s, hipStream_t st) {
     ConvArgs a = a_in;
     static const int dbg = getenv("VR_CONV_DBG") ? atoi(getenv("VR_CONV_DBG")) : 0;
     a.dbg = dbg;
+    if (a.w_hi > 0) {
+        // a column window is honoured by conv_x3h.hip alone: the launch must take it (mfma_mode 3, x3_pick), nothing falls back to full width
+        X3Tile x3t;
+        VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && a.w_lo >= 0 && a.w_lo < a.w_hi && !a.part && x3_pick(a, s, &x3t), -2,
+                 "conv column window: only conv_x3h (mfma_mode 3, eval) takes one");
+    }
     {
         int wmt, wth;
         int wino_mt, thin_th;
-        if (a.nsrc >= 1 && a.nsrc <= 3 && thin16_pick(a, s, &thin_th)) {
+        if (a.w_hi == 0 && a.nsrc >= 1 && a.nsrc <= 3 && thin16_pick(a, s, &thin_th)) {
             thin16_fill_tiling(a, thin_th);
             thin16_launch_conv(a, s, thin_th, st);
             return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;

@@ -517,6 +517,12 @@ bool x3_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
 
 void x3_fill_tiling(ConvArgs& a, const X3Tile& t) {
     a.tiles_w = (a.Wout + 31) / 32;
+    a.wt0 = 0;
+    if (a.w_hi > 0) {                                                    // column window (conv_x3h.hip): the tiles that meet [w_lo, w_hi)
+        const int hi = a.w_hi < a.Wout ? a.w_hi : a.Wout;
+        a.wt0 = a.w_lo / 32;
+        a.tiles_w = (hi + 31) / 32 - a.wt0;
+    }
     a.tiles_h = (a.Hout + t.TH - 1) / t.TH;
     a.npt = a.N * a.tiles_h * a.tiles_w;
     a.nct = a.CoutPad / t.MT;

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256, (X3hCfg<MT, TH>::OCC + (HI ? 1 : 0))) void con
     const int n = pt / tiles_per_img;
     const int trem = pt - n * tiles_per_img;
     const int h0 = (trem / a.tiles_w) * TH;
-    const int w0 = (trem % a.tiles_w) * TW;
+    const int w0 = (a.wt0 + trem % a.tiles_w) * TW;                // (absolute column: wt0 > 0 under a column window, ConvArgs::w_lo)
     const int co0 = ct * MT;
     const int tid = threadIdx.x;
     const int lane = tid & 63;

@@ -167,6 +167,11 @@ public:
     bool x3_mode() const { return mfma_mode == 2 || mfma_mode == 3; }
     int default_mfma_mode = 3;                           // (VR_MFMA_MODE overrides; "mfma_mode" -1 / "mfma_bf16" 0 return to it)
     bool serial = false;                                 // vr_set_option("serial_exec"): no lanes / side streams (tests: race detector)
+    // vr_set_option("crop_window") (default 1): eval, mfma_mode 3, no taps -- a caller that keeps only the columns [w_lo, w_hi) of
+    // the mask (predict_mask's offset crop, lib/nets.py:124-128) has the stage-3 dec1 conv compute only the 32-column tiles meeting
+    // them (ConvArgs::w_lo / w_hi) and the head read only those; 0 = every column, as before
+    bool crop_window = true;
+    int net_w_lo = 0, net_w_hi = 0;                      // run_net: the columns of the mask the caller keeps (0, 0: all)
     void set_option(const std::string& name, int value);
     void reset_adam_state();
     void profile_end(double* conv_ms, double* conv_flops, double* conv_bytes, int* launches);
@@ -201,6 +206,7 @@ private:
     struct PendingConv { ConvArgs a; ConvShape shp; double flops, bytes; bool stats; BNFinalizeArgs fin; BN* bn; };
     std::vector<PendingConv>* conv_sink = nullptr;       // set: run_conv hands the launch to its caller instead of launching (ASPP branch group)
     int x3d_mode = 2;                                    // option "conv_x3d": 0 off, 1 single launches, 2 + the ASPP branch group
+    int conv_w_lo = 0, conv_w_hi = 0;                    // set: the next run_conv stores only these output columns if conv_x3h takes it
     std::vector<Conv*> x3d_list;                         // the ASPP branch convs conv_x3d.hip takes in mfma_mode 3: dilated 3x3, conv2 (1x1)
     float* wino_arena = nullptr;
     float* winot_arena = nullptr;                        // training: Winograd copies of the flipped/transposed weights
@@ -334,6 +340,7 @@ private:
                     bool batch_as_h);
     template <class F> void for_each_conv(F&& f);
     Tensor run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view);
+    Tensor run_net_window(const Tensor& x, int w_lo, int w_hi);
     Tensor run_lstm(LSTMMod& M, const Tensor& h);
     SrcSpec upsampled(const Tensor& t);
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)

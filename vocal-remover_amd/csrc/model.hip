@@ -360,6 +360,7 @@ void Model::set_option(const std::string& name, int value) {
         if (value < -1 || value > 2) throw Error(-2, "conv_x3d: 0, 1, 2 or -1 (default)");     // 1 one launch per conv, 2 (default) + the four ASPP branches in one launch
         x3d_mode = value < 0 ? 2 : value;
     }
+    else if (name == "crop_window") crop_window = value != 0;
     else if (name == "adam_reset") reset_adam_state();      // a freshly constructed torch.optim.Adam has no moments
     else if (name == "hip_graph" || name == "conv_x3p" || name == "wgrad_x3h" || name == "conv_x3b") {
         // options of round 4 whose kernels moved to tools/experiments in round 5: accepted and ignored, so that an older caller keeps
@@ -788,6 +789,16 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
     a.x3w = (x3_mode() && !(training && !train_wino)) ? L.x3w : nullptr;
     if (!x3d_mode && a.Win == 16) a.x3w = nullptr;          // (16-column layers: only conv_x3d.hip reads the planes)
     a.bf16 = mfma_mode;
+    int wcols = a.Wout;                                      // output columns the launch computes
+    if (conv_w_hi > 0 && !training && mfma_mode == 3 && !batch_as_h && !conv_sink) {
+        X3Tile xt;
+        int tth;
+        const ConvShape cs{L.KS, L.stride, L.dh, L.dw};
+        if (!thin16_pick(a, cs, &tth) && x3_pick(a, cs, &xt)) {             // (the launch takes conv_x3h: launch_conv's order)
+            a.w_lo = conv_w_lo; a.w_hi = conv_w_hi;
+            wcols = std::min(a.Wout, (conv_w_hi + 31) / 32 * 32) - conv_w_lo / 32 * 32;
+        }
+    }
     Tensor o;
     if (batch_as_h) {
         o.N = N; o.C = L.Cout; o.H = 1; o.W = a.Wout;
@@ -834,14 +845,21 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         }
         conv_sink->push_back(pc);
     } else if (!dry) {
-        const double flops = 2.0 * N * (double)(batch_as_h ? 1 : a.Hout) * a.Wout * (double)L.Cout * L.Cin * L.KS * L.KS;
+        const double flops = 2.0 * N * (double)(batch_as_h ? 1 : a.Hout) * wcols * (double)L.Cout * L.Cin * L.KS * L.KS;
         record_begin(0, flops);
         if (profiling) {
             // algorithmic HBM bytes of the launch: the virtual input, the 3x3/1x1 weights and the output, once each
             char tag[160];
             snprintf(tag, sizeof tag, "%s k%d s%d d%d ci%d co%d %dx%dx%d", L.name.c_str(), L.KS, L.stride, L.dh, L.Cin,
                      L.Cout, a.N, a.Hout, a.Wout);
-            record_note(conv_alg_bytes(L, a, N, batch_as_h), tag);
+            double bytes = conv_alg_bytes(L, a, N, batch_as_h);
+            if (wcols < a.Wout) {                            // column window: the output and the full-resolution input over those columns (+ halo)
+                const double fi = std::min(1.0, (wcols + 2.0) / a.Win), fo = (double)wcols / a.Wout;
+                bytes = 4.0 * ((double)a.N * L.Cin * a.Hin * a.Win * fi + (double)N * L.Cout * a.Hout * a.Wout * fo +
+                               (double)L.Cin * L.KS * L.KS * L.Cout);
+                snprintf(tag + strlen(tag), sizeof tag - strlen(tag), " cols %d-%d", a.w_lo / 32 * 32, a.w_lo / 32 * 32 + wcols);
+            }
+            record_note(bytes, tag);
         }
         launch_conv(a, shp, stream);
         record_end();
@@ -1106,7 +1124,12 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
     if (fk) VR_HIP(hipStreamWaitEvent(stream, lstm_join, 0));
     else uh = upsampled(h);
     SrcSpec ul = upsampled(l);
-    Tensor o = run_conv(B.dec[3], {uh, ul, SrcSpec{e[0]}}, N, out_view, nullptr, false);
+    // (stage 3 under a caller's column window: only the head reads this output, and only those columns)
+    const bool win = &B == &nets_[4] && net_w_hi > 0;
+    if (win) { conv_w_lo = net_w_lo; conv_w_hi = net_w_hi; }
+    Tensor o;
+    try { o = run_conv(B.dec[3], {uh, ul, SrcSpec{e[0]}}, N, out_view, nullptr, false); } catch (...) { conv_w_lo = conv_w_hi = 0; throw; }
+    conv_w_lo = conv_w_hi = 0;
     tap(p + ".dec1", o);
     return o;
 }
@@ -1176,6 +1199,17 @@ Tensor Model::run_net(const Tensor& x) {
     return f3;
 }
 
+// run_net for a caller that keeps only the mask columns [w_lo, w_hi) (w_hi == 0: all): with "crop_window" on, in eval and mfma_mode 3
+// and while no taps are recorded (the parity tests compare every dec1 tap at full width), stage 3's dec1 computes only those columns
+Tensor Model::run_net_window(const Tensor& x, int w_lo, int w_hi) {
+    if (!(crop_window && !training && mfma_mode == 3 && !record_taps && w_hi > 0 && w_lo > 0)) return run_net(x);
+    net_w_lo = w_lo; net_w_hi = w_hi;
+    Tensor f3;
+    try { f3 = run_net(x); } catch (...) { net_w_lo = net_w_hi = 0; throw; }
+    net_w_lo = net_w_hi = 0;
+    return f3;
+}
+
 void Model::plan_and_reserve(int B, int T, size_t extra_bytes) {
     graph_valid = false;                         // the workspace is about to be rewound: a kept training graph dies here
     // the dry run is pure host work (~0.3 ms for the full net): remember its result per (B, T, mode)
@@ -1235,7 +1269,7 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
     xt.p = xd; xt.N = B; xt.C = 2; xt.H = max_bin; xt.W = T;
     xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
     if (record_taps) taps.clear();
-    Tensor f3 = run_net(xt);
+    Tensor f3 = run_net_window(xt, mode == 0 ? 0 : offset, mode == 0 ? 0 : T - offset);
     HeadDst d{};
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
@@ -1296,7 +1330,7 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     Tensor xt;
     xt.p = xd; xt.N = B; xt.C = 2; xt.H = max_bin; xt.W = T;
     xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
-    Tensor f3 = run_net(xt);
+    Tensor f3 = run_net_window(xt, offset, T - offset);
     HeadDst d{};
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
@@ -1478,7 +1512,7 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
             x.p = mag + (size_t)first * roi; x.N = count; x.C = 2; x.H = max_bin; x.W = cropsize;
             x.sN = roi; x.sC = (long long)bins * Wpad; x.sH = Wpad;
             x.slope = 1.f;
-            Tensor f3 = run_net(x);
+            Tensor f3 = run_net_window(x, offset, cropsize - offset);
             HeadDst d{};
             d.p = mask[ps] + (size_t)first * roi; d.dN = roi; d.dC = (long long)bins * Wm[ps]; d.dH = Wm[ps];
             d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;

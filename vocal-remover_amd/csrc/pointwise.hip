@@ -104,8 +104,17 @@ static void check_vec4(const Tensor& x) {
              -2, "thin conv needs 16-byte aligned rows (frames % 4 == 0)");
 }
 
-void launch_head_sigmoid(const Tensor& x, const float* w, const HeadDst& d, hipStream_t st) {
-    check_vec4(x);
+void launch_head_sigmoid(const Tensor& x_in, const float* w, const HeadDst& d_in, hipStream_t st) {
+    check_vec4(x_in);
+    // only the 4-column groups that meet the kept window [w_lo, w_hi) are read (the others would be computed and dropped; under
+    // Model::crop_window the stage-3 dec1 does not even compute them)
+    const int q0 = (d_in.w_lo > 0 ? d_in.w_lo : 0) / 4;
+    const int q1 = ((d_in.w_hi < x_in.W ? d_in.w_hi : x_in.W) + 3) / 4;
+    VR_CHECK(q1 > q0, -2, "mask head: empty column window");
+    Tensor x = x_in;
+    x.p += (long long)q0 * 4; x.W = (q1 - q0) * 4;
+    HeadDst d = d_in;
+    d.w_lo -= q0 * 4; d.w_hi -= q0 * 4;
     const long long total = (long long)x.N * x.H * (x.W / 4);
     const int grid = (int)((total + 255) / 256);
     prof_note(2.0 * 2 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + 2.0 * x.N * x.H * x.W));   // C -> 2 head

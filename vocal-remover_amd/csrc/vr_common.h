@@ -167,6 +167,10 @@ struct ConvArgs {
                                // stride-2 conv is four stride-1 convs over dz, one per output parity (ph, pw), with
                                // 1 / 2 / 2 / 4 live taps and outputs interleaved (dst.wshift, doubled row stride):
                                // 9 tap evaluations instead of the 36 of the zero-insertion form (conv_dma.hip only)
+    int w_lo, w_hi;            // output-column window (conv_x3h.hip only; w_hi == 0: every column).  Only the 32-column tiles that meet
+                               // [w_lo, w_hi) run; the input geometry stays full width (halo columns are real data) and the columns
+                               // outside those tiles are not written.  Eval: the consumer keeps only the window (predict_mask's crop)
+    int wt0;                   // first 32-column tile of the window (x3_fill_tiling); tiles_w counts the window's tiles
 };
 
 struct ConvShape {             // static description used by the launcher
