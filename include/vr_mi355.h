@@ -44,6 +44,18 @@ const char* vr_last_error(void);
 /* nets.CascadedNet(n_fft, hop_length, nout=32, nout_lstm=128)        lib/nets.py:46-80
  * (is_complex=False, the only configuration any reference caller uses).                           */
 int vr_create(int device, int n_fft, int hop_length, int nout, int nout_lstm, vr_handle* out);
+/* The same with flags.  VR_CREATE_COMPLEX: nets.CascadedNet(..., is_complex=True) -- nin = 4 input channels
+ * [re L, re R, im L, im R], so the first layers and out / aux_out take their nin = 4 shapes (vr_param_info), and a
+ * complex mask bounded by tanh(|m|) (lib/nets.py:104-107,119-122).  Such a handle runs eval-mode inference only:
+ *   vr_forward      x and out are complex64 (interleaved re, im): x [B,2,bins,T], out [B,2,bins,Wm] in every mode;
+ *                   in training mode it returns VR_ERR_BAD_ARGUMENT
+ *   vr_separate / vr_separate_wave   same signatures; the network sees the complex crops (X_pad / c, with c = max|X|,
+ *                   or for tta numpy's lexicographic complex maximum as a complex divisor), TTA averages the complex masks,
+ *                   --postprocess blends |mask| and keeps its phase, y = mask X and v = (1 - mask) X are complex products
+ *   vr_train_step, vr_forward_train, vr_backward, vr_validate_step   VR_ERR_BAD_ARGUMENT (training is not supported)
+ *   vr_set_mode(h, 1) is accepted (model.train()).                                                  */
+#define VR_CREATE_COMPLEX 1
+int vr_create_ex(int device, int n_fft, int hop_length, int nout, int nout_lstm, int flags, vr_handle* out);
 int vr_destroy(vr_handle h);
 
 /* nn.Module.state_dict() / load_state_dict()                  inference.py:131, train.py:209,290
@@ -87,7 +99,7 @@ int vr_set_mode(vr_handle h, int training);
 int vr_set_option(vr_handle h, const char* name, int value);
 
 /* CascadedNet.forward (mode 0) / predict_mask (mode 1) / predict (mode 2)   lib/nets.py:82-141
- * x:   [B, 2, n_fft/2+1, T] fp32 magnitudes
+ * x:   [B, 2, n_fft/2+1, T] fp32 magnitudes (a VR_CREATE_COMPLEX handle: complex64, and out complex64)
  * out: mode 0 [B,2,bins,T];  modes 1,2 [B,2,bins,T-128]                                          */
 int vr_forward(vr_handle h, const float* x, int x_on_device, int B, int T, int mode, float* out,
                int out_on_device);

@@ -13,7 +13,7 @@ void xcorr_argmax_api(int device, const float* a, long long na, const float* b, 
 
 struct vr_model {
     vr::Model m;
-    vr_model(int d, int n, int h, int o, int l) : m(d, n, h, o, l) {}
+    vr_model(int d, int n, int h, int o, int l, bool cplx) : m(d, n, h, o, l, cplx) {}
 };
 
 static thread_local std::string g_err;
@@ -49,14 +49,19 @@ extern "C" {
 const char* vr_last_error(void) { return g_err.c_str(); }
 
 int vr_create(int device, int n_fft, int hop_length, int nout, int nout_lstm, vr_handle* out) {
+    return vr_create_ex(device, n_fft, hop_length, nout, nout_lstm, 0, out);
+}
+
+int vr_create_ex(int device, int n_fft, int hop_length, int nout, int nout_lstm, int flags, vr_handle* out) {
     if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
     *out = nullptr;
     return guard([&] {
+        if (flags & ~VR_CREATE_COMPLEX) throw vr::Error(VR_ERR_BAD_ARGUMENT, "unknown vr_create_ex flag");
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
             throw vr::Error(VR_ERR_HIP, "no HIP device visible: libvr_mi355 has no CPU fallback");
         if (device < 0 || device >= count) throw vr::Error(VR_ERR_BAD_ARGUMENT, "device index out of range");
-        *out = new vr_model(device, n_fft, hop_length, nout, nout_lstm);
+        *out = new vr_model(device, n_fft, hop_length, nout, nout_lstm, (flags & VR_CREATE_COMPLEX) != 0);
     });
 }
 
@@ -165,6 +170,7 @@ int vr_train_step(vr_handle h, const float* X, const float* y, int on_device, in
     NEED(h);
     return guard([&] {
         VR_CHECK(X && y, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.need_real_mask("vr_train_step");
         h->m.train_fwd_bwd_api(X, y, on_device != 0, B, T, accumulation_steps, loss_out, mask_out, mask_on_device != 0);
     });
 }
@@ -173,13 +179,17 @@ int vr_forward_train(vr_handle h, const float* X, int on_device, int B, int T, f
     NEED(h);
     return guard([&] {
         VR_CHECK(X && mask_out, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.need_real_mask("vr_forward_train");
         h->m.forward_train_api(X, on_device != 0, B, T, mask_out, mask_on_device != 0);
     });
 }
 
 int vr_backward(vr_handle h, const float* dmask, int on_device) {
     NEED(h);
-    return guard([&] { h->m.backward_api(dmask, on_device != 0); });
+    return guard([&] {
+        h->m.need_real_mask("vr_backward");
+        h->m.backward_api(dmask, on_device != 0);
+    });
 }
 
 int vr_graph_generation(vr_handle h, int64_t* generation, int* valid) {

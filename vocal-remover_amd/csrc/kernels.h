@@ -15,6 +15,9 @@ struct HeadDst {
     int pad_rows;             // replicate the last input row this many extra times (1025 - 1024)
 };
 void launch_head_sigmoid(const Tensor& x, const float* w /*[2][C]*/, const HeadDst& d, hipStream_t st);
+// complex-mask head (is_complex, lib/nets.py:104-107,119-122): 4 outputs, m = complex(out[o], out[o+2]) for o = 0, 1, bounded as
+// tanh(|m|) * m / (|m| + 1e-8); d.p holds complex64 and its strides count complex elements
+void launch_head_complex(const Tensor& x, const float* w /*[4][C]*/, const HeadDst& d, hipStream_t st);
 // out[n][0][h][w] = sum_c w[c] * act(x);  part: [nblocks][2] (sum, sumsq) or null; returns nblocks
 // epi (eval): device [2] = folded (scale, shift) of the single-channel BatchNorm, applied with the ReLU before the store
 int launch_squeeze_conv(const Tensor& x, const float* w /*[C]*/, float* out, float* part, bool dry, hipStream_t st,
@@ -161,6 +164,12 @@ void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpa
                     unsigned* stats, hipStream_t st);
 // aff[0..3] = (1/coef, 0, 1/coef, 0), coef = max|X| (mode 0) or |lexicographic max| (mode 1)
 void launch_coef_affine(const unsigned* stats, int rows, int mode, float* aff, hipStream_t st);   // rows = 2 * bins partials
+// complex handle: 1/c as a complex number, c = max|X| (mode 0) or the lexicographic complex max itself (mode 1)
+void launch_coef_complex(const unsigned* stats, int rows, int mode, float2* inv, hipStream_t st);
+// spec [N][2][bins][T] complex64 -> dst [N][4][bins][Wdst] planar (re ch0, re ch1, im ch0, im ch1), frame t at column pad_l + t,
+// every other column zero; times *scale (complex, may be null)
+void launch_pack_complex(const float2* spec, int N, int bins, int T, float* dst, int Wdst, int pad_l, const float2* scale,
+                         hipStream_t st);
 // y = m*X, v = (1-m)*X with m = mask_a[.., t] (tta=0) or 0.5*(mask_a[.., t] + mask_b[.., t + shift])
 // wgt [T] (or null): per-frame merge_artifacts weight, m += wgt[t] * (1 - m)
 void launch_apply_mask(const float2* spec, int bins, int T, const float* mask_a, int Wa,
@@ -168,5 +177,13 @@ void launch_apply_mask(const float2* spec, int bins, int T, const float* mask_a,
 // fmin[t] = min over (channel, bin) of the final mask at frame t
 void launch_frame_min(int bins, int T, const float* mask_a, int Wa, const float* mask_b, int Wb, int shift, float* fmin,
                       hipStream_t st);
+// the same three for a complex64 mask: complex products; the TTA average is complex; merge_artifacts blends |m| and keeps the
+// phase, m' = (|m| + wgt (1 - |m|)) m / |m| (m = 0: m' = wgt); the frame minimum is taken over |m|
+void launch_apply_mask_complex(const float2* spec, int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb,
+                               int shift, const float* wgt, float2* y, float2* v, hipStream_t st);
+void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop, int T, const float2* mask_a, int Wa,
+                                 const float2* mask_b, int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st);
+void launch_frame_min_complex(int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb, int shift, float* fmin,
+                              hipStream_t st);
 
 }  // namespace vr

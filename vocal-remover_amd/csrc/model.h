@@ -98,10 +98,17 @@ void merge_artifacts_weight(const std::vector<float>& fmin, std::vector<float>& 
 
 class Model {
 public:
-    Model(int device, int n_fft, int hop, int nout, int nout_lstm);
+    Model(int device, int n_fft, int hop, int nout, int nout_lstm, bool is_complex = false);
     ~Model();
 
     int device, n_fft, hop, nout, nout_lstm, max_bin, output_bin, offset = 64;
+    // CascadedNet(is_complex=True) (lib/nets.py:46-141): the input is the complex spectrogram as nin = 4 planar channels
+    // [re L, re R, im L, im R], the head predicts a complex mask bounded by tanh(|m|), every mask buffer is complex64.
+    // Eval-mode inference only: the training entry points refuse such a handle (need_real_mask).
+    bool is_complex = false;
+    int nin = 2;
+    void need_real_mask(const char* what) const;          // refuse a complex handle (training entry points)
+    void need_real_mask_train(const char* what) const;    // ... only while it is in training mode
 
     // ---- parameters ----
     std::deque<Param> params;
@@ -114,9 +121,10 @@ public:
     bool taping() const { return training && !fwd_only; }
 
     // ---- forward over host or device input ----
-    // x: [B,2,output_bin,T] fp32 magnitudes.  mode 0: forward (full width), 1: predict_mask
-    // (offset crop), 2: predict (x*mask, offset crop).  out sized accordingly.
+    // x: [B,2,output_bin,T] fp32 magnitudes (complex handle: complex64, and out complex64 too).  mode 0: forward (full
+    // width), 1: predict_mask (offset crop), 2: predict (x*mask, offset crop).  out sized accordingly.
     void forward_api(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device);
+    void forward_complex(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device);
 
     // train.validate_epoch body for one batch (train.py:117-127): predict + crop_center(y) + L1, on the device
     void validate_api(const float* X, const float* Y, bool on_dev, int B, int T, float* loss_out);

@@ -120,8 +120,8 @@ void Model::build_basenet(BaseNetL& B, const std::string& p, int nin, int c, int
     build_cba(B.dec[3], p + ".dec1.conv1", 3 * c + 1, c, 3, 1, 1, 1, 1, 1, RELU);
 }
 
-Model::Model(int device_, int n_fft_, int hop_, int nout_, int nout_lstm_)
-    : device(device_), n_fft(n_fft_), hop(hop_), nout(nout_), nout_lstm(nout_lstm_) {
+Model::Model(int device_, int n_fft_, int hop_, int nout_, int nout_lstm_, bool is_complex_)
+    : device(device_), n_fft(n_fft_), hop(hop_), nout(nout_), nout_lstm(nout_lstm_), is_complex(is_complex_), nin(is_complex_ ? 4 : 2) {
     VR_CHECK(n_fft >= 64 && (n_fft & (n_fft - 1)) == 0 && n_fft <= 8192, -2, "n_fft must be a power of two in [64, 8192]");
     VR_CHECK(hop > 0, -2, "hop_length must be positive");
     VR_CHECK(nout % 4 == 0 && nout >= 4 && nout_lstm % 4 == 0 && nout_lstm >= 4, -2, "nout / nout_lstm must be multiples of 4");
@@ -150,7 +150,6 @@ Model::Model(int device_, int n_fft_, int hop_, int nout_, int nout_lstm_)
             }
         }
     }
-    const int nin = 2;
     const int nin_lstm = max_bin / 2;
     // lib/nets.py:59-80
     build_basenet(nets_[0], "stg1_low_band_net.0", nin, nout / 2, nin_lstm / 2, nout_lstm);
@@ -323,6 +322,16 @@ void Model::get_param(const std::string& key, void* host, int64_t cap_bytes) {
     } else {
         VR_HIP(hipMemcpy(dst, p.dev, p.numel * sizeof(float), hipMemcpyDeviceToHost));
     }
+}
+
+void Model::need_real_mask(const char* what) const {
+    VR_CHECK(!is_complex, -2, std::string(what) + ": this handle predicts a complex mask (is_complex=True); only eval-mode inference "
+                              "is supported for it, training is not");
+}
+
+void Model::need_real_mask_train(const char* what) const {
+    VR_CHECK(!(is_complex && training), -2, std::string(what) + " in training mode: this handle predicts a complex mask "
+                                            "(is_complex=True); only eval-mode inference is supported for it, training is not");
 }
 
 void Model::set_training(bool t) {
@@ -1223,7 +1232,7 @@ void Model::plan_and_reserve(int B, int T, size_t extra_bytes) {
     dry = true;
     Tensor x;
     x.p = reinterpret_cast<float*>(uintptr_t(256));
-    x.N = B; x.C = 2; x.H = max_bin; x.W = T; x.sH = T; x.sC = (long long)output_bin * T; x.sN = 2 * x.sC;
+    x.N = B; x.C = nin; x.H = max_bin; x.W = T; x.sH = T; x.sC = (long long)output_bin * T; x.sN = nin * x.sC;
     try { run_net(x); } catch (...) { dry = false; ws = saved; throw; }
     dry = false;
     const size_t need = ws.peak + extra_bytes + 4096;
@@ -1238,18 +1247,61 @@ static void check_T(int T, int offset, int mode) {
     if (mode != 0) VR_CHECK(T - 2 * offset > 0, -6, "assert mask.size()[3] > 0 (frames must exceed 2*offset)");
 }
 
+// m *= x[.., off + w]; CPLX: complex64 x and m, the complex product (predict of a complex handle); `total` counts elements
+template <bool CPLX>
 __global__ void mul_crop_kernel(const float* __restrict__ x, float* __restrict__ m, int T, int Wm, int off, long long total) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
     const int w = (int)(gid % Wm);
     const long long row = gid / Wm;
-    m[gid] *= x[row * T + off + w];
+    if constexpr (CPLX) {
+        const float2 a = reinterpret_cast<const float2*>(x)[row * T + off + w];
+        float2* mc = reinterpret_cast<float2*>(m) + gid;
+        const float2 b = *mc;
+        *mc = make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+    } else {
+        m[gid] *= x[row * T + off + w];
+    }
+}
+
+// forward_api of a complex handle: x [B][2][bins][T] complex64 -> planar [B][4][bins][T] (the reference's cat([x.real, x.imag])),
+// out [B][2][bins][Wm] complex64
+void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
+    need_real_mask_train("vr_forward");
+    const size_t in_floats = (size_t)B * 2 * output_bin * T * 2;
+    const size_t pack_floats = (size_t)B * 4 * output_bin * T;
+    const int Wm = mode == 0 ? T : T - 2 * offset;
+    const size_t out_floats = (size_t)B * 2 * output_bin * Wm * 2;
+    fold_eval_affines();
+    plan_and_reserve(B, T, (in_floats + pack_floats + out_floats) * sizeof(float) + 2048);
+    float* xd = ws.allocf(in_floats);
+    float* xp = ws.allocf(pack_floats);
+    float* od = out_on_device ? out : ws.allocf(out_floats);
+    VR_HIP(hipMemcpyAsync(xd, x, in_floats * sizeof(float), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
+    Tensor xt;
+    xt.p = xp; xt.N = B; xt.C = 4; xt.H = max_bin; xt.W = T;
+    xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 4 * xt.sC; xt.slope = 1.f;
+    if (record_taps) taps.clear();
+    Tensor f3 = run_net_window(xt, mode == 0 ? 0 : offset, mode == 0 ? 0 : T - offset);
+    HeadDst d{};
+    d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;       // (complex elements)
+    d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
+    launch_head_complex(f3, out_w->dev, d, stream);
+    if (mode == 2) {
+        const long long total = (long long)B * 2 * output_bin * Wm;
+        VR_LAUNCH((mul_crop_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm, offset, total);
+        VR_HIP(hipGetLastError());
+    }
+    if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipStreamSynchronize(stream));
 }
 
 void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
     DeviceGuard dev_guard(device);
     VR_CHECK(B > 0, -2, "batch must be positive");
     check_T(T, offset, mode);
+    if (is_complex) { forward_complex(x, x_on_device, B, T, mode, out, out_on_device); return; }
     const size_t in_floats = (size_t)B * 2 * output_bin * T;
     const int Wm = mode == 0 ? T : T - 2 * offset;
     const size_t out_floats = (size_t)B * 2 * output_bin * Wm;
@@ -1276,7 +1328,7 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
     launch_head_sigmoid(f3, out_w->dev, d, stream);
     if (mode == 2) {
         const long long total = (long long)out_floats;
-        VR_LAUNCH(mul_crop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm,
+        VR_LAUNCH((mul_crop_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm,
                            offset, total);
         VR_HIP(hipGetLastError());
     }
@@ -1306,6 +1358,7 @@ __global__ __launch_bounds__(256) void l1_crop_kernel(const float* __restrict__ 
 // loss = L1Loss()(y_pred, y) -- forward, crop and the mean-absolute-error reduction all on the device.
 void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int T, float* loss_out) {
     DeviceGuard dev_guard(device);
+    need_real_mask("vr_validate_step (its L1 loss is defined on magnitudes)");
     VR_CHECK(!training, -2, "validate step runs in eval mode (train.py:109 model.eval()); call vr_set_mode(h, 0) first");
     VR_CHECK(B > 0, -2, "batch must be positive");
     check_T(T, offset, 2);
@@ -1336,7 +1389,7 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
     launch_head_sigmoid(f3, out_w->dev, d, stream);
     const long long total = (long long)out_floats;
-    VR_LAUNCH(mul_crop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm, offset, total);
+    VR_LAUNCH((mul_crop_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm, offset, total);
     VR_HIP(hipGetLastError());
     VR_LAUNCH(l1_crop_kernel, dim3(nblk), dim3(256), 0, stream, od, yd, T, Wm, offset, total, part);
     VR_HIP(hipGetLastError());
@@ -1441,11 +1494,12 @@ static void make_padding(int width, int cropsize, int offset, int& left, int& ri
 
 // Separator.separate / separate_tta (inference.py:70-102) on device-resident spectrograms.
 // spec_d, y_d, v_d: device [2][bins][T] complex64.  scratch comes from `io` (caller reserved).
-static size_t separate_scratch_floats(int bins, int T, int cropsize, int offset, int tta) {
+// (planes 2 for a complex handle: its crop source has 4 channels and its mask is complex64)
+static size_t separate_scratch_floats(int bins, int T, int cropsize, int offset, int tta, int planes) {
     int l, r, roi;
     make_padding(T, cropsize, offset, l, r, roi);
     const size_t Wpad2 = (size_t)T + l + r + roi;
-    return 2 * (size_t)2 * bins * Wpad2 * (tta ? 2 : 1) + 2 * (size_t)T + (size_t)8 * bins + 4096;
+    return planes * 2 * (size_t)2 * bins * Wpad2 * (tta ? 2 : 1) + 2 * (size_t)T + (size_t)8 * bins + 4096;
 }
 
 void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize, float* y_spec,
@@ -1461,7 +1515,7 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
     const size_t spec_f = (size_t)2 * bins * T * 2;
     int pad_l, pad_r, roi;
     make_padding(T, cropsize, offset, pad_l, pad_r, roi);
-    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta);
+    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta, is_complex ? 2 : 1);
     if (!io_reserved) {
         // direct call (host or device pointers): size and rewind the staging arena here; only the wave-level entry
         // point, which has already carved its own buffers out of `io`, passes io_reserved
@@ -1493,13 +1547,22 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
         const int pl = pad_l + (ps ? roi / 2 : 0), pr = pad_r + (ps ? roi / 2 : 0);
         const int Wpad = T + pl + pr;
         const int patches = (Wpad - 2 * offset) / roi;
-        float* mag = io.allocf((size_t)2 * bins * Wpad);
+        float* mag = io.allocf((size_t)nin * bins * Wpad);
         Wm[ps] = patches * roi;
-        mask[ps] = io.allocf((size_t)2 * bins * Wm[ps]);
-        prof_memset_async(mag, 0, (size_t)2 * bins * Wpad * sizeof(float), stream);
-        launch_mag_pad(reinterpret_cast<const float2*>(sd), bins, T, mag, Wpad, pl, stats, stream);
-        launch_coef_affine(stats, 2 * bins, tta ? 1 : 0, in_aff, stream);
-        {   // X_mag / coef once, so that the first conv of every BaseNet reads a plain tensor (LDS-DMA path)
+        mask[ps] = io.allocf((size_t)(is_complex ? 4 : 2) * bins * Wm[ps]);
+        if (is_complex) {
+            // X_pad / c as [re L, re R, im L, im R] planes, zero padding included.  The stats pass is the magnitude path's: it
+            // also stores |X| into the first two planes, which the pack then overwrites.  c is real (max |X|, inference.py:74) or
+            // numpy's lexicographic complex maximum (inference.py:87,94), applied as a complex product with 1/c.
+            launch_mag_pad(reinterpret_cast<const float2*>(sd), bins, T, mag, Wpad, pl, stats, stream);
+            launch_coef_complex(stats, 2 * bins, tta ? 1 : 0, reinterpret_cast<float2*>(in_aff), stream);
+            launch_pack_complex(reinterpret_cast<const float2*>(sd), 1, bins, T, mag, Wpad, pl, reinterpret_cast<const float2*>(in_aff),
+                                stream);
+        } else {
+            prof_memset_async(mag, 0, (size_t)2 * bins * Wpad * sizeof(float), stream);
+            launch_mag_pad(reinterpret_cast<const float2*>(sd), bins, T, mag, Wpad, pl, stats, stream);
+            launch_coef_affine(stats, 2 * bins, tta ? 1 : 0, in_aff, stream);
+            // X_mag / coef once, so that the first conv of every BaseNet reads a plain tensor (LDS-DMA path)
             Tensor m;
             m.p = mag; m.N = 1; m.C = 2; m.H = bins; m.W = Wpad;
             m.sH = Wpad; m.sC = (long long)bins * Wpad; m.sN = 2 * m.sC;
@@ -1509,14 +1572,15 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
         auto run_crops = [&](int first, int count) {
             ws.reset();
             Tensor x;
-            x.p = mag + (size_t)first * roi; x.N = count; x.C = 2; x.H = max_bin; x.W = cropsize;
+            x.p = mag + (size_t)first * roi; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
             x.sN = roi; x.sC = (long long)bins * Wpad; x.sH = Wpad;
             x.slope = 1.f;
             Tensor f3 = run_net_window(x, offset, cropsize - offset);
             HeadDst d{};
-            d.p = mask[ps] + (size_t)first * roi; d.dN = roi; d.dC = (long long)bins * Wm[ps]; d.dH = Wm[ps];
+            d.p = mask[ps] + (size_t)(is_complex ? 2 : 1) * first * roi; d.dN = roi; d.dC = (long long)bins * Wm[ps]; d.dH = Wm[ps];
             d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
-            launch_head_sigmoid(f3, out_w->dev, d, stream);
+            if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
+            else launch_head_sigmoid(f3, out_w->dev, d, stream);
         };
         for (int i = 0; i < patches; i += bs) {
             const int nb = std::min(bs, patches - i);
@@ -1568,7 +1632,11 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
         // minimum is reduced on the GPU, the O(T) run logic runs on the host, the blend in apply_mask.
         float* fmin_d = io.allocf((size_t)T);
         float* wgt_d = io.allocf((size_t)T);
-        launch_frame_min(bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2, fmin_d, stream);
+        if (is_complex)      // (the minimum of |mask|, inference.py:28-29)
+            launch_frame_min_complex(bins, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
+                                     tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, fmin_d, stream);
+        else
+            launch_frame_min(bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2, fmin_d, stream);
         std::vector<float> fmin((size_t)T), w;
         VR_HIP(hipMemcpyAsync(fmin.data(), fmin_d, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream));
         VR_HIP(hipStreamSynchronize(stream));
@@ -1580,15 +1648,26 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
     if (y_wave_d && v_wave_d) {
         // wave-level caller: mask application, inverse FFT, window and overlap-add in one pass per stem -- the y / v
         // spectrograms (inference.py:32-38) are never materialised
-        for (int which = 0; which < 2; ++which)
-            launch_istft_masked(plan, reinterpret_cast<const float2*>(sd), hop, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1],
-                                roi / 2, wgt, which, which ? v_wave_d : y_wave_d, stream);
+        for (int which = 0; which < 2; ++which) {
+            if (is_complex)
+                launch_istft_masked_complex(plan, reinterpret_cast<const float2*>(sd), hop, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
+                                            tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, wgt, which,
+                                            which ? v_wave_d : y_wave_d, stream);
+            else
+                launch_istft_masked(plan, reinterpret_cast<const float2*>(sd), hop, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1],
+                                    roi / 2, wgt, which, which ? v_wave_d : y_wave_d, stream);
+        }
         enq_t1 = std::chrono::steady_clock::now(); enq_have = true;       // (VR_ENQ_TIMING: everything is enqueued at this point)
         VR_HIP(hipStreamSynchronize(stream));
         return;
     }
-    launch_apply_mask(reinterpret_cast<const float2*>(sd), bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2,
-                      wgt, reinterpret_cast<float2*>(yd), reinterpret_cast<float2*>(vd), stream);
+    if (is_complex)
+        launch_apply_mask_complex(reinterpret_cast<const float2*>(sd), bins, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
+                                  tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, wgt,
+                                  reinterpret_cast<float2*>(yd), reinterpret_cast<float2*>(vd), stream);
+    else
+        launch_apply_mask(reinterpret_cast<const float2*>(sd), bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2,
+                          wgt, reinterpret_cast<float2*>(yd), reinterpret_cast<float2*>(vd), stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(y_spec, yd, spec_f * sizeof(float), hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(v_spec, vd, spec_f * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -1623,7 +1702,7 @@ void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int 
     const size_t spec_f = (size_t)2 * bins * T * 2;
     const size_t out_f = (size_t)2 * hop * (T - 1);
     const size_t frames_f = (size_t)2 * T * n_fft;
-    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta);
+    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta, is_complex ? 2 : 1);
     ensure_io(((size_t)2 * L + 3 * spec_f + 2 * out_f + frames_f + scratch) * sizeof(float) + 65536);
     io.reset();
     float* stage_in = io.allocf((size_t)2 * L);

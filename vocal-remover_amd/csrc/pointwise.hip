@@ -22,7 +22,8 @@ __device__ __forceinline__ void load_aff(const Tensor& x, int h, int c, float& s
 
 // ---------------------------------------------------------------------------------------------------
 // Thin 1x1 conv over channels, CO outputs, 4 consecutive frames per thread.
-//   FINAL: sigmoid + window/crop + replicate rows (mask head, lib/nets.py:109-115,127-128)
+//   FINAL: sigmoid + window/crop + replicate rows (mask head, lib/nets.py:109-115,127-128); CO = 4: the complex-mask head
+//          (lib/nets.py:104-107,119-122), complex64 stores
 //   else : raw store to out[n][h][w] (+ per-block sum/sumsq partials for BatchNorm batch stats)
 // ---------------------------------------------------------------------------------------------------
 template <int CO, bool FINAL>
@@ -56,7 +57,25 @@ __global__ __launch_bounds__(256) void thin_conv_kernel(Tensor x, const float* _
                 for (int j = 0; j < 4; ++j) acc[o][j] = fmaf(wc, v[j], acc[o][j]);
             }
         }
-        if constexpr (FINAL) {
+        if constexpr (FINAL && CO == 4) {
+            float2* dp = reinterpret_cast<float2*>(d.p);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int wcol = w4 * 4 + j;
+                    if (wcol < d.w_lo || wcol >= d.w_hi) continue;
+                    const float re = acc[o][j], im = acc[o + 2][j];
+                    const float mag = hypotf(re, im);                         // torch.abs of a complex tensor
+                    const float th = tanhf(mag), den = mag + 1e-8f;
+                    const float2 m = make_float2(th * re / den, th * im / den);
+                    float2* dst = dp + (long long)n * d.dN + (long long)o * d.dC + (wcol - d.w_lo);
+                    dst[(long long)h * d.dH] = m;
+                    if (h == x.H - 1)
+                        for (int e = 1; e <= d.pad_rows; ++e) dst[(long long)(h + e) * d.dH] = m;
+                }
+            }
+        } else if constexpr (FINAL) {
 #pragma unroll
             for (int o = 0; o < CO; ++o) {
 #pragma unroll
@@ -104,7 +123,8 @@ static void check_vec4(const Tensor& x) {
              -2, "thin conv needs 16-byte aligned rows (frames % 4 == 0)");
 }
 
-void launch_head_sigmoid(const Tensor& x_in, const float* w, const HeadDst& d_in, hipStream_t st) {
+template <int CO>
+static void launch_head(const Tensor& x_in, const float* w, const HeadDst& d_in, hipStream_t st) {
     check_vec4(x_in);
     // only the 4-column groups that meet the kept window [w_lo, w_hi) are read (the others would be computed and dropped; under
     // Model::crop_window the stage-3 dec1 does not even compute them)
@@ -117,10 +137,13 @@ void launch_head_sigmoid(const Tensor& x_in, const float* w, const HeadDst& d_in
     d.w_lo -= q0 * 4; d.w_hi -= q0 * 4;
     const long long total = (long long)x.N * x.H * (x.W / 4);
     const int grid = (int)((total + 255) / 256);
-    prof_note(2.0 * 2 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + 2.0 * x.N * x.H * x.W));   // C -> 2 head
-    VR_LAUNCH((thin_conv_kernel<2, true>), dim3(grid), dim3(256), 0, st, x, w, d, nullptr, nullptr, nullptr);
+    prof_note(2.0 * CO * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + CO * (double)x.N * x.H * x.W));   // C -> CO head
+    VR_LAUNCH((thin_conv_kernel<CO, true>), dim3(grid), dim3(256), 0, st, x, w, d, nullptr, nullptr, nullptr);
     VR_HIP(hipGetLastError());
 }
+
+void launch_head_sigmoid(const Tensor& x, const float* w, const HeadDst& d, hipStream_t st) { launch_head<2>(x, w, d, st); }
+void launch_head_complex(const Tensor& x, const float* w, const HeadDst& d, hipStream_t st) { launch_head<4>(x, w, d, st); }
 
 int launch_squeeze_conv(const Tensor& x, const float* w, float* out, float* part, bool dry, hipStream_t st, const float* epi) {
     const long long total = (long long)x.N * x.H * (x.W / 4);

@@ -8,6 +8,8 @@
 //  K14 istft        : librosa.istft at lib/spec_utils.py:157-165 (irfft * window, overlap-add,
 //                     / window-sum-square where > tiny, trim n_fft/2) -> hop*(T-1) samples.
 //      apply_mask   : inference.py:26-40 (y = mask*X, v = (1-mask)*X; TTA average :97-98).
+//      <true> forms : the complex-mask model (CascadedNet(is_complex=True)): the complex input pack
+//                     (mag_pad), the complex normaliser (coef_affine) and the consumers of a complex64 mask.
 // One workgroup per frame; radix-2 FFT in LDS.  These stages are HBM-bound streaming work that is
 // <1 % of the pipeline, kept simple and exact-ordered.
 #include "kernels.h"
@@ -147,7 +149,25 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, const float
     }
 }
 
+// The final mask at (row, t): mask_a, or the TTA average with mask_b shifted by `shift`, then the merge_artifacts blend wgt[t].
+__device__ __forceinline__ float2 final_mask(const float2* __restrict__ ma, int Wa, const float2* __restrict__ mb, int Wb, int shift,
+                                             const float* __restrict__ wgt, long long row, int t) {
+    float2 m = ma[row * Wa + t];
+    if (mb) {
+        const float2 b = mb[row * Wb + t + shift];
+        m = make_float2((m.x + b.x) * 0.5f, (m.y + b.y) * 0.5f);
+    }
+    if (wgt) {        // inference.py:27-30: |m| through merge_artifacts, the phase kept (np.angle(0) = 0: m' = w where m = 0)
+        const float mag = hypotf(m.x, m.y), w = wgt[t];
+        const float nm = mag + w * (1.f - mag);
+        m = mag > 0.f ? make_float2(nm * (m.x / mag), nm * (m.y / mag)) : make_float2(nm, 0.f);
+    }
+    return m;
+}
+
 // which: 0 = plain spectrogram (mask_a null) / instruments y = m X, 1 = vocals v = (1 - m) X
+// CPLX: the mask is complex64 (is_complex handles), y = m X and v = (1 - m) X as complex products
+template <bool CPLX>
 __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, const float2* __restrict__ spec, int T, int S,
                                                           const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb,
                                                           int shift, const float* __restrict__ wgt, int which,
@@ -167,7 +187,14 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, const floa
             const long long row = (long long)ch * bins + k;
             const int t = t0 + f;
             v = spec[row * T + t];
-            if (ma) {
+            if constexpr (CPLX) {
+                if (ma) {
+                    const float2 m = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift,
+                                                wgt, row, t);
+                    const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
+                    v = cmul(gm, v);
+                }
+            } else if (ma) {
                 float m = ma[row * Wa + t];
                 if (mb) m = (m + mb[row * Wb + t + shift]) * 0.5f;
                 if (wgt) m += wgt[t] * (1.f - m);
@@ -243,8 +270,9 @@ static bool tiled_signal_path(const FFTPlan& pl, int hop) {
     return on && hop * 2 == pl.n_fft && pl.n_fft >= 128 && tile_frames(pl, pl.n_fft / 2) >= 3;
 }
 
-void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
-                         int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
+template <bool CPLX>
+static void launch_istft_tile(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
+                              int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
     const int M = pl.n_fft / 2, bins = M + 1;
     const long long out_len = (long long)hop * (T - 1);
     if (out_len <= 0) return;
@@ -252,12 +280,23 @@ void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, 
     const int S = F - 1;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel), 160 * 1024);
-    // per stem: the complex spectrogram (8 B per bin-frame), the mask(s) (4 B), hop samples written per frame, two channels
-    prof_note(0.0, 2.0 * ((double)bins * T * (8.0 + 4.0 * (mask_b ? 2 : 1)) + 4.0 * (double)out_len));
-    VR_LAUNCH(istft_tile_kernel, dim3((unsigned)((T - 1 + S - 1) / S), 2), dim3(1024), lds, st, pl, spec, T, S, mask_a, Wa,
-                       mask_b, Wb, shift, wgt, which, wave, out_len);
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<CPLX>), 160 * 1024);
+    // per stem: the complex spectrogram (8 B per bin-frame), the mask(s) (4 B, complex 8 B), hop samples written per frame, two channels
+    prof_note(0.0, 2.0 * ((double)bins * T * (8.0 + (CPLX ? 8.0 : 4.0) * (mask_b ? 2 : 1)) + 4.0 * (double)out_len));
+    VR_LAUNCH((istft_tile_kernel<CPLX>), dim3((unsigned)((T - 1 + S - 1) / S), 2), dim3(1024), lds, st, pl, spec, T, S, mask_a, Wa,
+              mask_b, Wb, shift, wgt, which, wave, out_len);
     VR_HIP(hipGetLastError());
+}
+
+void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
+                         int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
+    launch_istft_tile<false>(pl, spec, hop, T, mask_a, Wa, mask_b, Wb, shift, wgt, which, wave, st);
+}
+
+void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop, int T, const float2* mask_a, int Wa,
+                                 const float2* mask_b, int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
+    launch_istft_tile<true>(pl, spec, hop, T, reinterpret_cast<const float*>(mask_a), Wa, reinterpret_cast<const float*>(mask_b), Wb,
+                            shift, wgt, which, wave, st);
 }
 
 // irfft(spec[:, t]) * window -> frames[ch][t][0..n)
@@ -354,8 +393,29 @@ __device__ __forceinline__ float unord32(unsigned o) {
 // One workgroup per (channel, bin) row: |X| into the padded crop source (row-contiguous loads and stores, no 64-bit
 // division per element) and the row's two maxima into part[row] -- no atomics; coef_affine_kernel reduces the 2 x bins
 // partials.  (Round 1: 16 k same-address atomics and a flat 64-bit index made this 190 us for 34 MB.)
+// PACK (complex handles): the same row pass stores the complex row as a real row in plane c and an imaginary row in plane c + 2
+// ([re L, re R, im L, im R], lib/nets.py:84 cat([x.real, x.imag], dim=1)), times the complex *scale when given, zero outside
+// [pad_l, pad_l + T) (the whole row is written: no pre-zeroing), for blockIdx.y = batch item n; no statistics.
+template <bool PACK>
 __global__ __launch_bounds__(256) void mag_pad_kernel(const float2* __restrict__ spec, int T, float* __restrict__ mag_pad,
-                                                      int Wpad, int pad_l, unsigned long long* __restrict__ part) {
+                                                      int Wpad, int pad_l, unsigned long long* __restrict__ part, int bins,
+                                                      const float2* __restrict__ scale) {
+    if constexpr (PACK) {
+        const int row = blockIdx.x, n = blockIdx.y;                  // row = c * bins + k
+        const int c = row / bins, k = row - c * bins;
+        const float2* sp = spec + ((long long)n * 2 * bins + row) * T;
+        float* re = mag_pad + (((long long)n * 4 + c) * bins + k) * Wpad;
+        float* im = mag_pad + (((long long)n * 4 + c + 2) * bins + k) * Wpad;
+        const float2 s = scale ? *scale : make_float2(1.f, 0.f);
+        for (int col = threadIdx.x; col < Wpad; col += 256) {
+            const int t = col - pad_l;
+            float2 z = (t >= 0 && t < T) ? sp[t] : make_float2(0.f, 0.f);
+            if (scale) z = cmul(z, s);
+            re[col] = z.x;
+            im[col] = z.y;
+        }
+        return;
+    }
     const int row = blockIdx.x;
     const float2* sp = spec + (long long)row * T;
     float* dst = mag_pad + (long long)row * Wpad + pad_l;
@@ -389,12 +449,16 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(const float2* __restrict__
 void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpad, int pad_l, unsigned* stats,
                     hipStream_t st) {
     prof_note(0.0, 2.0 * (double)bins * (8.0 * T + 4.0 * Wpad));
-    VR_LAUNCH(mag_pad_kernel, dim3(2 * bins), dim3(256), 0, st, spec, T, mag_pad, Wpad, pad_l,
-                       reinterpret_cast<unsigned long long*>(stats) + 2);
+    VR_LAUNCH((mag_pad_kernel<false>), dim3(2 * bins), dim3(256), 0, st, spec, T, mag_pad, Wpad, pad_l,
+                       reinterpret_cast<unsigned long long*>(stats) + 2, bins, nullptr);
     VR_HIP(hipGetLastError());
 }
 
 // stats layout: [0..1] legacy words, then 2 x bins rows of (max |X| bits, lexicographic complex key) partials
+// CPLX (complex handles): aff[0..1] = 1 / c as a complex number, formed in double and rounded once -- c = max|X| (mode 0,
+// inference.py:74) or the lexicographic complex maximum itself (mode 1, inference.py:87,94: numpy divides by the complex number,
+// which also rotates the phase)
+template <bool CPLX>
 __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats, int rows, int mode, float* aff) {
     const unsigned long long* part = reinterpret_cast<const unsigned long long*>(stats) + 2;
     unsigned mxb = 0u;
@@ -415,6 +479,18 @@ __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats,
         }
         __syncthreads();
     }
+    if constexpr (CPLX) {
+        if (threadIdx.x == 0) {
+            double re = (double)__uint_as_float(rm[0]), im = 0.0;
+            if (mode != 0) {
+                re = (double)unord32((unsigned)(rk[0] >> 32));
+                im = (double)unord32((unsigned)(rk[0] & 0xffffffffu));
+            }
+            const double n2 = re * re + im * im;
+            aff[0] = (float)(re / n2); aff[1] = (float)(-im / n2);
+        }
+        return;
+    }
     if (threadIdx.x == 0) {
         float coef;
         if (mode == 0) {
@@ -428,12 +504,26 @@ __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats,
     }
 }
 void launch_coef_affine(const unsigned* stats, int rows, int mode, float* aff, hipStream_t st) {
-    VR_LAUNCH(coef_affine_kernel, dim3(1), dim3(256), 0, st, stats, rows, mode, aff);
+    VR_LAUNCH((coef_affine_kernel<false>), dim3(1), dim3(256), 0, st, stats, rows, mode, aff);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_coef_complex(const unsigned* stats, int rows, int mode, float2* inv, hipStream_t st) {
+    VR_LAUNCH((coef_affine_kernel<true>), dim3(1), dim3(256), 0, st, stats, rows, mode, reinterpret_cast<float*>(inv));
+    VR_HIP(hipGetLastError());
+}
+
+void launch_pack_complex(const float2* spec, int N, int bins, int T, float* dst, int Wdst, int pad_l, const float2* scale,
+                         hipStream_t st) {
+    prof_note(0.0, (double)N * 2 * bins * (8.0 * T + 8.0 * Wdst));
+    VR_LAUNCH((mag_pad_kernel<true>), dim3(2 * bins, N), dim3(256), 0, st, spec, T, dst, Wdst, pad_l, nullptr, bins, scale);
     VR_HIP(hipGetLastError());
 }
 
 // per-frame minimum of the final mask over (channel, bin): input of spec_utils.merge_artifacts
 // (lib/spec_utils.py:64).  One workgroup per 64 frames; lanes along time (coalesced rows).
+// CPLX: complex64 masks, the minimum of |mask| (inference.py:28-29)
+template <bool CPLX>
 __global__ __launch_bounds__(256) void frame_min_kernel(int rows, int T, const float* __restrict__ ma, int Wa,
                                                         const float* __restrict__ mb, int Wb, int shift,
                                                         float* __restrict__ fmin) {
@@ -443,9 +533,15 @@ __global__ __launch_bounds__(256) void frame_min_kernel(int rows, int T, const f
     float m = 3.4e38f;
     if (t < T) {
         for (int r = part; r < rows; r += 4) {
-            float v = ma[(long long)r * Wa + t];
-            if (mb) v = (v + mb[(long long)r * Wb + t + shift]) * 0.5f;
-            m = fminf(m, v);
+            if constexpr (CPLX) {
+                const float2 v = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift,
+                                            nullptr, r, t);
+                m = fminf(m, hypotf(v.x, v.y));
+            } else {
+                float v = ma[(long long)r * Wa + t];
+                if (mb) v = (v + mb[(long long)r * Wb + t + shift]) * 0.5f;
+                m = fminf(m, v);
+            }
         }
     }
     red[part][threadIdx.x & 63] = m;
@@ -455,10 +551,12 @@ __global__ __launch_bounds__(256) void frame_min_kernel(int rows, int T, const f
 
 void launch_frame_min(int bins, int T, const float* mask_a, int Wa, const float* mask_b, int Wb, int shift, float* fmin,
                       hipStream_t st) {
-    VR_LAUNCH(frame_min_kernel, dim3((T + 63) / 64), dim3(256), 0, st, 2 * bins, T, mask_a, Wa, mask_b, Wb, shift, fmin);
+    VR_LAUNCH((frame_min_kernel<false>), dim3((T + 63) / 64), dim3(256), 0, st, 2 * bins, T, mask_a, Wa, mask_b, Wb, shift, fmin);
     VR_HIP(hipGetLastError());
 }
 
+// CPLX: complex64 masks, complex products (final_mask: TTA average and merge_artifacts blend of a complex mask)
+template <bool CPLX>
 __global__ void apply_mask_kernel(const float2* __restrict__ spec, int bins, int T, const float* __restrict__ ma,
                                   int Wa, const float* __restrict__ mb, int Wb, int shift, const float* __restrict__ wgt,
                                   float2* __restrict__ y, float2* __restrict__ v) {
@@ -467,6 +565,14 @@ __global__ void apply_mask_kernel(const float2* __restrict__ spec, int bins, int
     if (gid >= total) return;
     const int t = (int)(gid % T);
     const long long row = gid / T;
+    if constexpr (CPLX) {
+        const float2 mc = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift, wgt,
+                                     row, t);
+        const float2 zc = spec[gid];
+        y[gid] = cmul(mc, zc);
+        v[gid] = cmul(make_float2(1.f - mc.x, -mc.y), zc);
+        return;
+    }
     float m = ma[row * Wa + t];
     if (mb) m = (m + mb[row * Wb + t + shift]) * 0.5f;
     if (wgt) m += wgt[t] * (1.f - m);            // merge_artifacts: y_mask += weight * (1 - y_mask)
@@ -479,8 +585,24 @@ __global__ void apply_mask_kernel(const float2* __restrict__ spec, int bins, int
 void launch_apply_mask(const float2* spec, int bins, int T, const float* mask_a, int Wa, const float* mask_b, int Wb,
                        int shift, const float* wgt, float2* y, float2* v, hipStream_t st) {
     const long long total = 2LL * bins * T;
-    VR_LAUNCH(apply_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, spec, bins, T, mask_a,
+    VR_LAUNCH((apply_mask_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, spec, bins, T, mask_a,
                        Wa, mask_b, Wb, shift, wgt, y, v);
+    VR_HIP(hipGetLastError());
+}
+
+// ---- complex64 masks (is_complex handles) ------------------------------------------------------------
+void launch_frame_min_complex(int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb, int shift, float* fmin,
+                              hipStream_t st) {
+    VR_LAUNCH((frame_min_kernel<true>), dim3((T + 63) / 64), dim3(256), 0, st, 2 * bins, T, reinterpret_cast<const float*>(mask_a), Wa,
+              reinterpret_cast<const float*>(mask_b), Wb, shift, fmin);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_apply_mask_complex(const float2* spec, int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb,
+                               int shift, const float* wgt, float2* y, float2* v, hipStream_t st) {
+    const long long total = 2LL * bins * T;
+    VR_LAUNCH((apply_mask_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, spec, bins, T,
+              reinterpret_cast<const float*>(mask_a), Wa, reinterpret_cast<const float*>(mask_b), Wb, shift, wgt, y, v);
     VR_HIP(hipGetLastError());
 }
 

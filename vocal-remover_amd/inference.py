@@ -1,5 +1,7 @@
 """inference.Separator look-alike (inference.py:16-102): same constructor, same methods, same
-numpy-in / numpy-out contract; the crop loop, stitching and mask application run on the GPU."""
+numpy-in / numpy-out contract; the crop loop, stitching and mask application run on the GPU.  A complex-mask model
+(CascadedNet(is_complex=True)) sees the complex crops instead of torch.abs(...) and its complex mask is applied as written in
+_postprocess (inference.py:26-40): complex TTA average, merge_artifacts on |mask| with the phase kept, complex products."""
 import numpy as np
 
 from . import native
@@ -93,6 +95,7 @@ def main(argv=None):
     p.add_argument('--cropsize', '-c', type=int, default=256)
     p.add_argument('--tta', '-t', action='store_true')
     p.add_argument('--postprocess', '-p', action='store_true')
+    p.add_argument('--is_complex', action='store_true')              # a checkpoint of CascadedNet(..., is_complex=True)
     p.add_argument('--output_image', '-I', action='store_true')      # accepted for command-line compatibility; no image is written
     p.add_argument('--output_dir', '-o', type=str, default="")
     args = p.parse_args(argv)
@@ -101,7 +104,7 @@ def main(argv=None):
         print('--output_image: not written by this entry point (spectrogram_to_image + cv2 are outside the MI355X path); run the '
               "reference's inference.py through vocal-remover_amd/run.py to get the image dumps")
     device = torch.device('cuda:{}'.format(max(args.gpu, 0)))
-    model = nets.CascadedNet(args.n_fft, args.hop_length, 32, 128)
+    model = nets.CascadedNet(args.n_fft, args.hop_length, 32, 128, is_complex=args.is_complex)
     model.load_state_dict(torch.load(args.pretrained_model, map_location='cpu'))
     model.to(device)
     X, sr = audio.load(args.input, sr=args.sr, mono=False, dtype=np.float32, res_type='kaiser_fast')

@@ -10,11 +10,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VR_LIB_PATH') or os.path.join(_HERE, 'libvr_mi355.so')
 
 c_f32p = ctypes.c_void_p
+VR_CREATE_COMPLEX = 1         # include/vr_mi355.h
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 
 _SIGNATURES = {
     'vr_last_error': (ctypes.c_char_p, []),
     'vr_create': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_create_ex': (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_void_p)]),
     'vr_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'vr_num_params': (ctypes.c_int, [ctypes.c_void_p]),
     'vr_param_info': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, c_i64p,
@@ -140,10 +142,14 @@ def np_ptr(a):
 class Handle:
     """Owns one vr_handle (one GPU, one stream)."""
 
-    def __init__(self, device, n_fft, hop_length, nout, nout_lstm):
+    def __init__(self, device, n_fft, hop_length, nout, nout_lstm, is_complex=False):
         self._h = ctypes.c_void_p()
-        check(lib().vr_create(int(device), int(n_fft), int(hop_length), int(nout), int(nout_lstm),
-                              ctypes.byref(self._h)))
+        if is_complex:
+            check(lib().vr_create_ex(int(device), int(n_fft), int(hop_length), int(nout), int(nout_lstm), VR_CREATE_COMPLEX,
+                                     ctypes.byref(self._h)))
+        else:
+            check(lib().vr_create(int(device), int(n_fft), int(hop_length), int(nout), int(nout_lstm),
+                                  ctypes.byref(self._h)))
         self.device = int(device)
 
     def close(self):

@@ -2,7 +2,8 @@
 
 What callers touch and what happens here:
 
-    nets.CascadedNet(n_fft, hop_length, nout=32, nout_lstm=128)  -> host-side state (689 tensors)
+    nets.CascadedNet(n_fft, hop_length, nout=32, nout_lstm=128,
+                     is_complex=False)                           -> host-side state (689 tensors)
     .load_state_dict(dict) / .state_dict()                      -> reference keys / torch layouts
     .to(device)                                                 -> creates the native handle on that GPU
     .eval() / .train()                                          -> vr_set_mode
@@ -11,6 +12,9 @@ What callers touch and what happens here:
 
 Inputs and outputs are torch tensors; a tensor already on the handle's GPU is passed by device
 pointer (no host round trip), a CPU tensor is copied in by the library.
+
+is_complex=True (lib/nets.py:82-122): inputs are complex spectrograms, masks and predictions are complex64; eval-mode
+inference only -- a forward under model.train() and the training entry points raise NotImplementedError.
 """
 import math
 from collections import OrderedDict
@@ -62,9 +66,9 @@ def _base_net(spec, p, nin, c, nin_lstm, nout_lstm):
     _cba(spec, p + '.dec1.conv1', 3 * c + 1, c, 3)
 
 
-def state_spec(n_fft, nout, nout_lstm):
+def state_spec(n_fft, nout, nout_lstm, is_complex=False):
     """(key, shape, init) in the reference's registration order (lib/nets.py:59-80)."""
-    nin = 2
+    nin = 4 if is_complex else 2
     nin_lstm = (n_fft // 2) // 2
     spec = []
     _base_net(spec, 'stg1_low_band_net.0', nin, nout // 2, nin_lstm // 2, nout_lstm)
@@ -139,12 +143,9 @@ class _ForwardTrain(torch.autograd.Function):
 class CascadedNet(object):
 
     def __init__(self, n_fft, hop_length, nout=32, nout_lstm=128, is_complex=False):
-        if is_complex:
-            raise NotImplementedError('is_complex=True is unreachable from every reference caller '
-                                      '(lib/nets.py:83-84,104-107) and is not part of the MI355X hot path')
         self.n_fft = n_fft
         self.hop_length = hop_length
-        self.is_complex = False
+        self.is_complex = bool(is_complex)
         self.nout = nout
         self.nout_lstm = nout_lstm
         self.max_bin = n_fft // 2
@@ -152,7 +153,7 @@ class CascadedNet(object):
         self.nin_lstm = self.max_bin // 2
         self.offset = 64
         self.training = True
-        self._spec = state_spec(n_fft, nout, nout_lstm)
+        self._spec = state_spec(n_fft, nout, nout_lstm, self.is_complex)
         self._state = OrderedDict((k, _init_tensor(shape, init)) for k, shape, init in self._spec)
         self._handle = None
         self._handle_gen = 0          # bumped whenever a native handle is created or closed
@@ -190,7 +191,7 @@ class CascadedNet(object):
             if self._handle is None or self._handle.device != index:
                 self._pull()
                 self._drop_handle()
-                self._handle = native.Handle(index, self.n_fft, self.hop_length, self.nout, self.nout_lstm)
+                self._handle = native.Handle(index, self.n_fft, self.hop_length, self.nout, self.nout_lstm, self.is_complex)
                 self._handle_gen += 1
                 self._device = torch.device('cuda', index)
                 self._push()
@@ -253,12 +254,19 @@ class CascadedNet(object):
                                '(this package has no CPU fallback)')
         return self._handle
 
+    def _no_complex_training(self, what):
+        if self.is_complex:
+            raise NotImplementedError('%s: training a complex-mask CascadedNet (is_complex=True) is not supported; only eval-mode '
+                                      'inference is (call model.eval())' % what)
+
     def _run(self, x, mode):
         h = self._need_handle()
         if not torch.is_tensor(x):
             x = torch.as_tensor(x)
+        if self.is_complex:
+            return self._run_complex(h, x, mode)
         if x.is_complex():
-            raise NotImplementedError('is_complex inputs are not supported (pass torch.abs(X))')
+            raise NotImplementedError('complex inputs need a complex-mask model; this one predicts a magnitude mask (pass torch.abs(X))')
         if x.dim() != 4 or x.shape[1] != 2 or x.shape[2] != self.output_bin:
             raise ValueError('expected input [B, 2, %d, T], got %s' % (self.output_bin, tuple(x.shape)))
         B, T = int(x.shape[0]), int(x.shape[3])
@@ -274,12 +282,34 @@ class CascadedNet(object):
         native.check(native.lib().vr_forward(h.h, x.data_ptr(), int(on_dev), B, T, mode, out.data_ptr(), int(on_dev)))
         return out
 
+    def _run_complex(self, h, x, mode):
+        """is_complex=True: x complex [B, 2, bins, T] -> complex64 mask (modes 0 / 1) or x * mask (mode 2)."""
+        if self.training:
+            self._no_complex_training('forward under model.train()')
+        if not x.is_complex():
+            raise RuntimeError('imag is not implemented for tensors with non-complex dtypes')     # the reference's x.imag
+        if x.dim() != 4 or x.shape[1] != 2 or x.shape[2] != self.output_bin:
+            raise ValueError('expected input [B, 2, %d, T], got %s' % (self.output_bin, tuple(x.shape)))
+        B, T = int(x.shape[0]), int(x.shape[3])
+        Wm = T if mode == 0 else T - 2 * self.offset
+        on_dev = x.is_cuda
+        if on_dev and x.device.index != h.device:
+            raise RuntimeError('input is on %s but the model is on cuda:%d' % (x.device, h.device))
+        x = x.detach().to(torch.complex64).resolve_conj().contiguous()       # interleaved (re, im) float pairs
+        out = torch.empty((B, 2, self.output_bin, max(Wm, 1)), dtype=torch.complex64, device=x.device if on_dev else 'cpu')
+        if on_dev:
+            torch.cuda.current_stream(x.device).synchronize()
+        native.check(native.lib().vr_forward(h.h, x.data_ptr(), int(on_dev), B, T, mode, out.data_ptr(), int(on_dev)))
+        return out
+
     def forward(self, x):
         """CascadedNet.forward (lib/nets.py:82-117): mask [B,2,n_fft/2+1,T].
 
         Under model.train() with autograd enabled (the reference's train_epoch, train.py:81) the returned mask is
         differentiable: `loss.backward()` reaches the native backward pass through _ForwardTrain and the gradients
         accumulate in the library's gradient arena = `.grad` of the flat parameter `parameters()` hands to the optimizer."""
+        if self.training:
+            self._no_complex_training('forward under model.train()')
         if self.training and torch.is_grad_enabled() and self._handle is not None:
             if not torch.is_tensor(x):
                 x = torch.as_tensor(x)
@@ -340,6 +370,7 @@ class CascadedNet(object):
         """mask = model(X); loss = L1Loss()(mask * X, y); (loss / accumulation_steps).backward()
         in one native call.  Returns loss.item() (and the mask if asked)."""
         import ctypes
+        self._no_complex_training('train_step')
         h = self._need_handle()
         X = torch.as_tensor(X)
         y = torch.as_tensor(y)
@@ -364,6 +395,7 @@ class CascadedNet(object):
     def validate_step(self, X, y):
         """One batch of train.validate_epoch (train.py:117-127): L1(predict(X), crop_center(y)) -> float."""
         import ctypes
+        self._no_complex_training('validate_step (an L1 loss on magnitudes, part of training)')
         h = self._need_handle()
         X = torch.as_tensor(X)
         y = torch.as_tensor(y)

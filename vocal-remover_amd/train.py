@@ -109,6 +109,8 @@ class Trainer(object):
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, world_size=1, rank=0, dropout_seed=None,
                  dropout=True, backend='auto', wire='fp32', broadcast=True):
+        if getattr(model, 'is_complex', False):
+            model._no_complex_training('Trainer')
         self.model = model
         self.world_size = world_size
         self.rank = rank
