@@ -125,6 +125,24 @@ int vr_separate(vr_handle h, const float* spec, int spec_on_device, int T, int t
 int vr_separate_wave(vr_handle h, const float* wave, int wave_on_device, int64_t L, int tta, int batchsize,
                      int cropsize, float* y_wave, float* v_wave, int out_on_device);
 
+/* ---- many songs in one call: what pseudo.py:40-74 (a dataset) and a folder of inputs do one file at a time ------------
+ * Separator.separate[_tta] for n_songs spectrograms of different lengths in ONE call.
+ * specs[s]: [2,bins,T[s]] complex64; y_specs[s], v_specs[s]: same shape.  tta (flag word) / cropsize as vr_separate.
+ * The result for song s is what vr_separate returns for that song alone: its own normaliser, its own make_padding, its own
+ * merge_artifacts runs.  What the songs share is the device batches: the crops of all songs, and of both --tta passes, form one list
+ * and batchsize counts crops of that list (<= 0: every crop of the call in one batch), so a short clip no longer pays the
+ * network's launch-bound tails for two crops of its own.  Front end and back end are one launch each for all songs.
+ * Magnitude and VR_CREATE_COMPLEX handles.  n_songs == 1 is valid.  One stream drain per call (one more with --postprocess).
+ * Errors: n_songs <= 0, a null table (both reported before the handle is looked at), a null entry, T[s] <= 0, L[s] < hop_length,
+ * training mode -> VR_ERR_BAD_ARGUMENT before the device is touched; a --postprocess failure of one song (VR_ERR_INDEX, the
+ * reference's IndexError) fails the call, vr_last_error() starts with "song <s>: ", no output is defined, the handle stays usable. */
+int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int specs_on_device, const int* T, int tta, int batchsize,
+                     int cropsize, float* const* y_specs, float* const* v_specs, int out_on_device);
+/* inference.py:147-176 for n_songs waves: waves[s] [2,L[s]] -> y_waves[s], v_waves[s] [2, hop*(L[s]/hop)], as vr_separate_wave
+ * gives them for each song alone.  The pointer tables themselves are host memory; `*_on_device` describe what they point to. */
+int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
+                          int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device);
+
 /* ---- training: the body of train.train_epoch (train.py:77-96) ------------------------------------ */
 /* mask = model(X); loss = L1Loss()(mask * X, y); (loss / accumulation_steps).backward()
  * X, y: [B, 2, bins, T] fp32.  Gradients ACCUMULATE in the library's gradient arena until vr_zero_grad

@@ -165,6 +165,34 @@ int vr_separate_wave(vr_handle h, const float* wave, int wave_on_device, int64_t
     });
 }
 
+// The many-song forms check their tables before the handle, so that a caller's argument error is reported without a device.
+static bool many_args_ok(int n_songs, const void* in, const void* len, const void* y, const void* v) {
+    if (n_songs <= 0) { g_err = "n_songs must be positive"; return false; }
+    if (!in || !len || !y || !v) { g_err = "null table"; return false; }
+    return true;
+}
+
+int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int specs_on_device, const int* T, int tta, int batchsize,
+                     int cropsize, float* const* y_specs, float* const* v_specs, int out_on_device) {
+    if (!many_args_ok(n_songs, specs, T, y_specs, v_specs)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        h->m.separate_many_api(n_songs, specs, specs_on_device != 0, T, nullptr, tta, batchsize, cropsize, y_specs, v_specs,
+                               out_on_device != 0);
+    });
+}
+
+int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
+                          int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device) {
+    if (!many_args_ok(n_songs, waves, L, y_waves, v_waves)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n_songs);
+        h->m.separate_many_api(n_songs, waves, waves_on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, y_waves, v_waves,
+                               out_on_device != 0);
+    });
+}
+
 int vr_train_step(vr_handle h, const float* X, const float* y, int on_device, int B, int T, int accumulation_steps,
                   float* loss_out, float* mask_out, int mask_on_device) {
     NEED(h);

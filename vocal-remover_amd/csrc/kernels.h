@@ -186,4 +186,37 @@ void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop,
 void launch_frame_min_complex(int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb, int shift, float* fmin,
                               hipStream_t st);
 
+// ---- many songs in one call (vr_separate_many / vr_separate_wave_many) ----------------------------------------------------------
+// One entry of the call's song table (built on the host, one copy to the device).  The crops of all songs, and of both TTA passes, form
+// ONE crop list (pass-major, song-major inside a pass): crop n's mask lands at column n * roi of one concatenated mask
+// [2][bins][W] (complex64 for a complex handle), so a device batch may hold crops of several songs and of both passes.
+struct SongSeg {
+    const float* wave;        // [2][L]           (wave-level calls)
+    long long L;
+    float2* spec;             // [2][bins][T]     (read; written by the STFT of a wave-level call)
+    float2* y;                // [2][bins][T]     instruments, vocals (spectrogram-level calls)
+    float2* v;
+    float* y_wave;            // [2][hop * (T-1)] (wave-level calls)
+    float* v_wave;
+    int T;
+    int mcol_a, mcol_b;       // column of the song's frame 0 in the concatenated mask: pass 0, TTA pass 1
+    int frame0;               // the song's first slot in the call's per-frame merge_artifacts weights
+    float* fmin;              // [T] the song's per-frame mask minima (--postprocess)
+};
+bool many_tiled_available(const FFTPlan& pl, int hop);       // hop == n_fft / 2: the tile kernels below exist
+void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st);
+// part [song][2 * bins][2]: per-row partial maxima (max |X| bits, lexicographic complex key); aff [song][4]: 1 / c as launch_coef_affine
+// (cplx: launch_coef_complex) gives it
+void launch_song_stats(const SongSeg* songs, int n_songs, int bins, double sum_T, unsigned long long* part, hipStream_t st);
+void launch_song_coef(const unsigned long long* part, int n_songs, int rows, int mode, bool cplx, float* aff, hipStream_t st);
+// crops[n] = (song, first frame; may be negative): dst [count][nin][max_bin][cropsize] = the normalised network input, zero outside the song
+void launch_crop_gather(const SongSeg* songs, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
+                        float* dst, hipStream_t st);
+void launch_frame_min_many(const SongSeg* songs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                           hipStream_t st);
+void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                            const float* wgt, hipStream_t st);
+void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
+                              bool cplx, const float* wgt, int which, hipStream_t st);
+
 }  // namespace vr

@@ -3,6 +3,7 @@
 #pragma once
 #include <chrono>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -142,6 +143,10 @@ public:
     // wave [2,L] -> y_wave, v_wave [2, hop*(T-1)]: whole inference.py pipeline, device resident
     void separate_wave_api(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
                            float* y_wave, float* v_wave, bool out_on_dev);
+    // n_songs spectrograms (L null: specs [2,bins,T[s]] -> y / v spectrograms) or waves (L given: [2,L[s]] -> y / v waves) in one call
+    void separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta,
+                           int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev);
+    void run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops);
     void separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
                             float* y_wave, float* v_wave, bool out_on_dev);
 

@@ -1502,6 +1502,53 @@ static size_t separate_scratch_floats(int bins, int T, int cropsize, int offset,
     return planes * 2 * (size_t)2 * bins * Wpad2 * (tta ? 2 : 1) + 2 * (size_t)T + (size_t)8 * bins + 4096;
 }
 
+// The crops [0, patches) of a separate call in device batches of `bs`; run_crops(first, count) enqueues the network and the mask
+// head for one contiguous part on the current streams.  A batch is split over the lanes unless profiling / serial_exec.
+void Model::run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops) {
+    for (int i = 0; i < patches; i += bs) {
+        const int nb = std::min(bs, patches - i);
+        const int K = std::min((int)lanes.size() + 1, nb);
+        if (K < 2 || profiling || serial) {
+            run_crops(i, nb);
+            continue;
+        }
+        // crops [i, i+nb) in K contiguous parts; part 0 on the handle's own streams, part j on lane j-1
+        for (Lane& l : lanes) {
+            if (l.ws.cap >= ws.cap) continue;            // every lane plans for the same (bs, cropsize)
+            VR_HIP(hipDeviceSynchronize());
+            if (l.ws.base) VR_HIP(hipFree(l.ws.base));
+            l.ws.base = nullptr; l.ws.cap = 0;
+            VR_HIP(hipMalloc(reinterpret_cast<void**>(&l.ws.base), ws.cap));
+            l.ws.cap = ws.cap;
+        }
+        // The host enqueues part 0 completely before part 1 (~0.5 ms of launches: profiles/README.md), so the later lanes start late:
+        // VR_LANE0_EXTRA = n gives part 0 n crops more than an even share.  Measured in round 6 (tools/gpu_r6_call7.sh, S30, two lanes):
+        // 6 + 5 crops 8.63 - 8.78 ms, 7 + 4 8.69 - 8.73, 8 + 3 8.90; three lanes 10.4, one lane 9.24 -- the even split stays.
+        static const int extra_env = getenv("VR_LANE0_EXTRA") ? atoi(getenv("VR_LANE0_EXTRA")) : -1;
+        const int even = (nb + K - 1) / K;
+        int head = extra_env >= 0 ? extra_env : 0;
+        if (even + head > nb - (K - 1)) head = std::max(0, nb - (K - 1) - even);      // every part keeps at least one crop
+        const int per0 = even + head;
+        const int per = K > 1 ? (nb - per0 + K - 2) / (K - 1) : nb;
+        for (int j = 1; j < K; ++j) {                    // `mag` is ready at this point of the main stream
+            hipEvent_t es = lanes[j - 1].start;
+            VR_HIP(hipEventRecord(es, stream));
+            VR_HIP(hipStreamWaitEvent(lanes[j - 1].main, es, 0));
+        }
+        run_crops(i, std::min(per0, nb));
+        for (int j = 1; j < K; ++j) {
+            const int first = per0 + (j - 1) * per, count = std::min(per, nb - first);
+            if (count <= 0) break;
+            swap_lane(j - 1);
+            try { run_crops(i + first, count); } catch (...) { swap_lane(j - 1); throw; }
+            hipEvent_t done = lanes[j - 1].done;
+            VR_HIP(hipEventRecord(done, stream));
+            swap_lane(j - 1);
+            VR_HIP(hipStreamWaitEvent(stream, done, 0));
+        }
+    }
+}
+
 void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize, float* y_spec,
                          float* v_spec, bool out_on_dev, bool io_reserved, float* y_wave_d, float* v_wave_d) {
     DeviceGuard dev_guard(device);
@@ -1582,48 +1629,7 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
             if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
             else launch_head_sigmoid(f3, out_w->dev, d, stream);
         };
-        for (int i = 0; i < patches; i += bs) {
-            const int nb = std::min(bs, patches - i);
-            const int K = std::min((int)lanes.size() + 1, nb);
-            if (K < 2 || profiling || serial) {
-                run_crops(i, nb);
-                continue;
-            }
-            // crops [i, i+nb) in K contiguous parts; part 0 on the handle's own streams, part j on lane j-1
-            for (Lane& l : lanes) {
-                if (l.ws.cap >= ws.cap) continue;            // every lane plans for the same (bs, cropsize)
-                VR_HIP(hipDeviceSynchronize());
-                if (l.ws.base) VR_HIP(hipFree(l.ws.base));
-                l.ws.base = nullptr; l.ws.cap = 0;
-                VR_HIP(hipMalloc(reinterpret_cast<void**>(&l.ws.base), ws.cap));
-                l.ws.cap = ws.cap;
-            }
-            // The host enqueues part 0 completely before part 1 (~0.5 ms of launches: profiles/README.md), so the later lanes start late:
-            // VR_LANE0_EXTRA = n gives part 0 n crops more than an even share.  Measured in round 6 (tools/gpu_r6_call7.sh, S30, two lanes):
-            // 6 + 5 crops 8.63 - 8.78 ms, 7 + 4 8.69 - 8.73, 8 + 3 8.90; three lanes 10.4, one lane 9.24 -- the even split stays.
-            static const int extra_env = getenv("VR_LANE0_EXTRA") ? atoi(getenv("VR_LANE0_EXTRA")) : -1;
-            const int even = (nb + K - 1) / K;
-            int head = extra_env >= 0 ? extra_env : 0;
-            if (even + head > nb - (K - 1)) head = std::max(0, nb - (K - 1) - even);      // every part keeps at least one crop
-            const int per0 = even + head;
-            const int per = K > 1 ? (nb - per0 + K - 2) / (K - 1) : nb;
-            for (int j = 1; j < K; ++j) {                    // `mag` is ready at this point of the main stream
-                hipEvent_t es = lanes[j - 1].start;
-                VR_HIP(hipEventRecord(es, stream));
-                VR_HIP(hipStreamWaitEvent(lanes[j - 1].main, es, 0));
-            }
-            run_crops(i, std::min(per0, nb));
-            for (int j = 1; j < K; ++j) {
-                const int first = per0 + (j - 1) * per, count = std::min(per, nb - first);
-                if (count <= 0) break;
-                swap_lane(j - 1);
-                try { run_crops(i + first, count); } catch (...) { swap_lane(j - 1); throw; }
-                hipEvent_t done = lanes[j - 1].done;
-                VR_HIP(hipEventRecord(done, stream));
-                swap_lane(j - 1);
-                VR_HIP(hipStreamWaitEvent(stream, done, 0));
-            }
-        }
+        run_crop_chunks(patches, bs, run_crops);
     }
     const float* wgt = nullptr;
     if (post) {
@@ -1731,6 +1737,188 @@ void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int 
         VR_HIP(hipMemcpyAsync(y_wave, yw, out_f * sizeof(float), hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(v_wave, vw, out_f * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
+// Separator.separate[_tta] / the inference.py:147-176 pipeline for n_songs inputs in ONE call (vr_separate_many /
+// vr_separate_wave_many).  Each song keeps its own normaliser, padding and merge_artifacts runs; what the songs share is the device
+// batches.  All crops of the call -- pass 0 of every song, then for tta pass 1 of every song -- form one list; a gather kernel writes
+// the crops of a batch part as one dense tensor [n][nin][max_bin][cropsize] straight from the complex spectrograms (normalised,
+// zero outside the song), and crop n's mask lands at column n * roi of one concatenated mask [2][bins][W].  Front end and back end
+// are one launch each for all songs (song = a grid dimension, kernels.h SongSeg), so the launch count does not depend on n_songs.
+void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta,
+                              int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev) {
+    const bool post = (tta & 2) != 0;       // flags: bit 0 = --tta, bit 1 = --postprocess
+    tta &= 1;
+    const bool waves = L != nullptr;
+    // ---- arguments and the host-side plan: nothing here touches the device
+    VR_CHECK(n_songs > 0, -2, "n_songs must be positive");
+    VR_CHECK(in && y && v && (waves || T_in), -2, "null table");
+    VR_CHECK(!training, -2, "separate() runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    check_T(cropsize, offset, 1);
+    VR_CHECK(cropsize - 2 * offset > 0, -6, "cropsize must exceed 2*offset");
+    const int bins = output_bin, E = is_complex ? 2 : 1;
+    struct Song { int T, pad_l, patches[2], crop0[2]; size_t spec_f, out_f; };
+    std::vector<Song> sg((size_t)n_songs);
+    int roi = 0, max_T = 0;
+    long long n_crops[2] = {0, 0}, sum_T = 0, sum_L = 0;
+    for (int s = 0; s < n_songs; ++s) {
+        const std::string who = "song " + std::to_string(s) + ": ";
+        VR_CHECK(in[s] && y[s] && v[s], -2, who + "null pointer");
+        if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
+        else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
+        if (waves) VR_CHECK(L[s] / hop < (1LL << 30), -2, who + "wave too long");
+        Song& g = sg[s];
+        g.T = waves ? 1 + (int)(L[s] / hop) : T_in[s];
+        int pad_r;
+        make_padding(g.T, cropsize, offset, g.pad_l, pad_r, roi);
+        g.patches[0] = (g.T + g.pad_l + pad_r - 2 * offset) / roi;
+        g.patches[1] = tta ? (g.T + g.pad_l + pad_r + roi - 2 * offset) / roi : 0;
+        g.spec_f = (size_t)2 * bins * g.T * 2;
+        g.out_f = (size_t)2 * hop * (g.T - 1);
+        max_T = std::max(max_T, g.T);
+        sum_T += g.T;
+        if (waves) sum_L += L[s];
+    }
+    for (int ps = 0; ps < 2; ++ps)
+        for (int s = 0; s < n_songs; ++s) { sg[s].crop0[ps] = (int)(n_crops[0] + n_crops[1]); n_crops[ps] += sg[s].patches[ps]; }
+    const long long total_crops = n_crops[0] + n_crops[1];
+    VR_CHECK(total_crops * roi < (1LL << 31) && sum_T < (1LL << 31), -2, "too many frames for one call: split the songs over several calls");
+    const int crops_n = (int)total_crops, W = crops_n * roi;
+    const int bs = (batchsize <= 0) ? crops_n : std::min(batchsize, crops_n);
+    const bool tiled = many_tiled_available(plan, hop);
+
+    DeviceGuard dev_guard(device);
+    // ---- the staging arena: carved twice, first dry for its size
+    std::vector<SongSeg> tab((size_t)n_songs);
+    std::vector<float*> stage_in((size_t)n_songs), stage_y((size_t)n_songs), stage_v((size_t)n_songs);
+    SongSeg* tab_d = nullptr; int2* crops_d = nullptr;
+    unsigned long long* part = nullptr;
+    float *aff = nullptr, *mask = nullptr, *gather = nullptr, *fmin_d = nullptr, *wgt_d = nullptr, *frames = nullptr;
+    const size_t crop_f = (size_t)nin * max_bin * cropsize;
+    auto carve = [&](Arena& A) {
+        tab_d = static_cast<SongSeg*>(A.alloc(sizeof(SongSeg) * n_songs));
+        crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * crops_n));
+        part = static_cast<unsigned long long*>(A.alloc((size_t)n_songs * 2 * bins * 16));
+        aff = A.allocf((size_t)n_songs * 4);
+        mask = A.allocf((size_t)E * 2 * bins * W);
+        gather = A.allocf((size_t)bs * crop_f + 4096);
+        if (post) { fmin_d = A.allocf((size_t)sum_T); wgt_d = A.allocf((size_t)sum_T); }
+        if (waves && !tiled) frames = A.allocf((size_t)2 * max_T * n_fft);
+        for (int s = 0; s < n_songs; ++s) {
+            const Song& g = sg[s];
+            SongSeg& t = tab[s];
+            t = SongSeg{};
+            t.T = g.T;
+            t.mcol_a = g.crop0[0] * roi;
+            t.mcol_b = tta ? g.crop0[1] * roi + roi / 2 : 0;
+            stage_in[s] = in_on_dev ? nullptr : A.allocf(waves ? (size_t)2 * L[s] : g.spec_f);
+            const float* src = in_on_dev ? in[s] : stage_in[s];
+            if (waves) {
+                t.wave = src; t.L = L[s];
+                t.spec = reinterpret_cast<float2*>(A.allocf(g.spec_f));
+                stage_y[s] = out_on_dev ? y[s] : A.allocf(g.out_f + 4);
+                stage_v[s] = out_on_dev ? v[s] : A.allocf(g.out_f + 4);
+                t.y_wave = stage_y[s]; t.v_wave = stage_v[s];
+                if (!tiled) {                         // general hop: masked spectrograms, then the per-frame inverse per song
+                    t.y = reinterpret_cast<float2*>(A.allocf(g.spec_f));
+                    t.v = reinterpret_cast<float2*>(A.allocf(g.spec_f));
+                }
+            } else {
+                t.spec = reinterpret_cast<float2*>(const_cast<float*>(src));
+                stage_y[s] = out_on_dev ? y[s] : A.allocf(g.spec_f);
+                stage_v[s] = out_on_dev ? v[s] : A.allocf(g.spec_f);
+                t.y = reinterpret_cast<float2*>(stage_y[s]); t.v = reinterpret_cast<float2*>(stage_v[s]);
+            }
+        }
+    };
+    Arena dry;
+    dry.dry = true;
+    carve(dry);
+    ensure_io(dry.peak + 65536);
+    io.reset();
+    carve(io);
+    std::vector<int2> crops((size_t)crops_n);
+    int frame0 = 0;
+    for (int s = 0; s < n_songs; ++s) {
+        tab[s].frame0 = frame0;
+        if (post) tab[s].fmin = fmin_d + frame0;
+        frame0 += sg[s].T;
+        for (int ps = 0; ps < (tta ? 2 : 1); ++ps)
+            for (int i = 0; i < sg[s].patches[ps]; ++i)
+                crops[(size_t)sg[s].crop0[ps] + i] = make_int2(s, i * roi - sg[s].pad_l - (ps ? roi / 2 : 0));
+    }
+    VR_HIP(hipMemcpyAsync(tab_d, tab.data(), sizeof(SongSeg) * n_songs, hipMemcpyHostToDevice, stream));
+    VR_HIP(hipMemcpyAsync(crops_d, crops.data(), sizeof(int2) * crops_n, hipMemcpyHostToDevice, stream));
+    if (!in_on_dev)
+        for (int s = 0; s < n_songs; ++s)
+            VR_HIP(hipMemcpyAsync(stage_in[s], in[s], (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float), hipMemcpyHostToDevice, stream));
+    // ---- front end
+    if (waves) {
+        if (tiled) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
+        else for (int s = 0; s < n_songs; ++s) launch_stft(plan, tab[s].wave, L[s], hop, sg[s].T, tab[s].spec, stream);
+    }
+    launch_song_stats(tab_d, n_songs, bins, (double)sum_T, part, stream);
+    launch_song_coef(part, n_songs, 2 * bins, tta ? 1 : 0, is_complex, aff, stream);
+    // ---- the network over the crop list
+    fold_eval_affines();                    // before planning, as in forward_api
+    plan_and_reserve(bs, cropsize, 0);
+    auto run_crops = [&](int first, int count) {
+        ws.reset();
+        float* dense = gather + (size_t)(first % bs) * crop_f;          // (batches start at multiples of bs: the part's slot in its batch)
+        launch_crop_gather(tab_d, crops_d + first, count, is_complex, bins, max_bin, cropsize, aff, dense, stream);
+        Tensor x;
+        x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
+        x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
+        x.slope = 1.f;
+        Tensor f3 = run_net_window(x, offset, cropsize - offset);
+        HeadDst d{};
+        d.p = mask + (size_t)E * first * roi; d.dN = roi; d.dC = (long long)bins * W; d.dH = W;
+        d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
+        if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
+        else launch_head_sigmoid(f3, out_w->dev, d, stream);
+    };
+    run_crop_chunks(crops_n, bs, run_crops);
+    // ---- back end
+    const float* wgt = nullptr;
+    std::vector<float> fmin_h, wgt_h;
+    if (post) {
+        launch_frame_min_many(tab_d, n_songs, max_T, bins, mask, W, tta, is_complex, stream);
+        fmin_h.resize((size_t)sum_T);
+        wgt_h.resize((size_t)sum_T);
+        VR_HIP(hipMemcpyAsync(fmin_h.data(), fmin_d, (size_t)sum_T * sizeof(float), hipMemcpyDeviceToHost, stream));
+        VR_HIP(hipStreamSynchronize(stream));
+        std::vector<float> f1, w1;
+        for (int s = 0; s < n_songs; ++s) {
+            f1.assign(fmin_h.begin() + tab[s].frame0, fmin_h.begin() + tab[s].frame0 + sg[s].T);
+            try {
+                merge_artifacts_weight(f1, w1, 0.05f, 64, 32);
+            } catch (const Error& e) {
+                throw Error(e.code, "song " + std::to_string(s) + ": " + e.what());
+            }
+            std::copy(w1.begin(), w1.end(), wgt_h.begin() + tab[s].frame0);
+        }
+        VR_HIP(hipMemcpyAsync(wgt_d, wgt_h.data(), (size_t)sum_T * sizeof(float), hipMemcpyHostToDevice, stream));
+        wgt = wgt_d;
+    }
+    if (waves && tiled) {
+        for (int which = 0; which < 2; ++which)
+            launch_istft_masked_many(plan, tab_d, n_songs, max_T, (double)sum_T, mask, W, tta, is_complex, wgt, which, stream);
+    } else {
+        launch_apply_mask_many(tab_d, n_songs, max_T, bins, mask, W, tta, is_complex, wgt, stream);
+        if (waves)
+            for (int s = 0; s < n_songs; ++s) {
+                launch_istft(plan, tab[s].y, hop, sg[s].T, frames, tab[s].y_wave, stream);
+                launch_istft(plan, tab[s].v, hop, sg[s].T, frames, tab[s].v_wave, stream);
+            }
+    }
+    if (!out_on_dev)
+        for (int s = 0; s < n_songs; ++s) {
+            const size_t nf = waves ? sg[s].out_f : sg[s].spec_f;
+            if (!nf) continue;
+            VR_HIP(hipMemcpyAsync(y[s], stage_y[s], nf * sizeof(float), hipMemcpyDeviceToHost, stream));
+            VR_HIP(hipMemcpyAsync(v[s], stage_v[s], nf * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
     VR_HIP(hipStreamSynchronize(stream));
 }
 

@@ -16,8 +16,16 @@
 
 #include <cfloat>
 #include <cstdlib>
+#include <type_traits>
 
 namespace vr {
+
+// The kernels of the spectrogram side exist in two forms under one name.  SRC = const float2 (the default): one song, every
+// argument as documented at the kernel.  SRC = const SongSeg (vr_separate_many / vr_separate_wave_many): `src` is the call's song
+// table and one more grid dimension picks the song; the kernel takes that song's pointers, length and mask columns from its entry
+// and then runs the same code.  `mask_a` is then the call's concatenated mask (row pitch Wa), `mask_b` the same pointer when the TTA
+// pass is to be averaged in (else null), `wgt` the weights of all songs; the arguments an entry replaces are passed as 0.
+template <class SRC> constexpr bool kSongTable = std::is_same<SRC, const SongSeg>::value;
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -108,7 +116,8 @@ __device__ __forceinline__ void fft_lds_sub(float2* x, const float2* __restrict_
 
 constexpr int TG = 4;                        // frames in flight per workgroup (1024 threads = 4 groups of 256)
 
-__global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, const float* __restrict__ wave, long long L, int T, int F,
+template <class SRC = const float>
+__global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
                                                          float2* __restrict__ spec) {
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
@@ -116,7 +125,15 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, const float
     float2* zs = lds2 + (size_t)g * M;       // this group's FFT buffer
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
     const int t0 = blockIdx.x * F, ch = blockIdx.y;
-    const float* wv = wave + (long long)ch * L;
+    const float* wv;
+    if constexpr (kSongTable<SRC>) {                 // blockIdx.z = song; the grid is sized for the longest one
+        const SongSeg sg = wave[blockIdx.z];
+        if (t0 >= sg.T) return;
+        L = sg.L; T = sg.T; spec = sg.spec;
+        wv = sg.wave + (long long)ch * L;
+    } else {
+        wv = wave + (long long)ch * L;
+    }
     const int nf = (T - t0) < F ? (T - t0) : F;
     for (int f0 = 0; f0 < nf; f0 += TG) {
         const int f = f0 + g;
@@ -167,8 +184,8 @@ __device__ __forceinline__ float2 final_mask(const float2* __restrict__ ma, int 
 
 // which: 0 = plain spectrogram (mask_a null) / instruments y = m X, 1 = vocals v = (1 - m) X
 // CPLX: the mask is complex64 (is_complex handles), y = m X and v = (1 - m) X as complex products
-template <bool CPLX>
-__global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, const float2* __restrict__ spec, int T, int S,
+template <bool CPLX, class SRC = const float2>
+__global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __restrict__ src, int T, int S,
                                                           const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb,
                                                           int shift, const float* __restrict__ wgt, int which,
                                                           float* __restrict__ wave, long long out_len) {
@@ -179,6 +196,19 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, const floa
     float2* tile = lds2 + (size_t)TG * M;                           // [bins][F]
     float* prev = reinterpret_cast<float*>(tile + (size_t)bins * F);   // [M] windowed second half of the last frame of the previous round
     const int t0 = blockIdx.x * S, ch = blockIdx.y;
+    const float2* __restrict__ spec;
+    if constexpr (kSongTable<SRC>) {                 // blockIdx.z = song; writes that song's y_wave (which 0) or v_wave (which 1)
+        const SongSeg sg = src[blockIdx.z];
+        if (t0 >= sg.T - 1) return;
+        spec = sg.spec; T = sg.T;
+        ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
+        if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
+        if (wgt) wgt += sg.frame0;
+        wave = which ? sg.v_wave : sg.y_wave;
+        out_len = (long long)M * (sg.T - 1);
+    } else {
+        spec = src;
+    }
     const int nf = (T - t0) < F ? (T - t0) : F;
     for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
         const int k = idx / F, f = idx - k * F;
@@ -356,9 +386,9 @@ void launch_stft_tiled(const FFTPlan& pl, const float* wave, long long L, int T,
     F = F / TG * TG;                                     // whole rounds of TG frames
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel), 160 * 1024);
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<>), 160 * 1024);
     prof_note(0.0, 2.0 * (4.0 * (double)L + 8.0 * (double)bins * T));              // unique audio read once, complex64 spectrogram written
-    VR_LAUNCH(stft_tile_kernel, dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, wave, L, T, F, spec);
+    VR_LAUNCH((stft_tile_kernel<>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, wave, L, T, F, spec);
     VR_HIP(hipGetLastError());
 }
 
@@ -396,11 +426,38 @@ __device__ __forceinline__ float unord32(unsigned o) {
 // PACK (complex handles): the same row pass stores the complex row as a real row in plane c and an imaginary row in plane c + 2
 // ([re L, re R, im L, im R], lib/nets.py:84 cat([x.real, x.imag], dim=1)), times the complex *scale when given, zero outside
 // [pad_l, pad_l + T) (the whole row is written: no pre-zeroing), for blockIdx.y = batch item n; no statistics.
-template <bool PACK>
-__global__ __launch_bounds__(256) void mag_pad_kernel(const float2* __restrict__ spec, int T, float* __restrict__ mag_pad,
+// SRC = const SongSeg, PACK false: the statistics pass per song, blockIdx = (row, song), the row's maxima into part[song][row] and
+// no |X| store.  GATHER (song table only; T = cropsize, Wpad = max_bin, part = the crop list as (song, first frame) pairs, scale =
+// aff [song][4] holding 1 / c): blockIdx = (row of [2][max_bin], crop n); the crop's frames [first, first + cropsize) of its song become
+// item n of the dense network input mag_pad [n][nin][max_bin][cropsize] -- |X| / c (PACK false) or the planes [re L, re R, im L, im R]
+// of X / c (PACK true), zero outside [0, T_song).  It stands for memset + mag_pad + materialize (+ pack) of the one-song path and for
+// its strided crop view, so that a device batch can hold crops of several songs and of both TTA passes.
+template <bool PACK, class SRC = const float2, bool GATHER = false>
+__global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, int T, float* __restrict__ mag_pad,
                                                       int Wpad, int pad_l, unsigned long long* __restrict__ part, int bins,
                                                       const float2* __restrict__ scale) {
-    if constexpr (PACK) {
+    if constexpr (GATHER) {
+        const int max_bin = Wpad, cropsize = T;
+        const int c = blockIdx.x / max_bin, k = blockIdx.x - c * max_bin, n = blockIdx.y;
+        const int2 cr = reinterpret_cast<const int2*>(part)[n];
+        const SongSeg sg = spec[cr.x];
+        const float2* sp = sg.spec + ((long long)c * bins + k) * sg.T;
+        float* d0 = mag_pad + (((long long)n * (PACK ? 4 : 2) + c) * max_bin + k) * cropsize;
+        float* d1 = d0 + 2LL * max_bin * cropsize;                  // (PACK: the imaginary plane)
+        const float2 s = scale[2 * cr.x];
+        for (int col = threadIdx.x; col < cropsize; col += 256) {
+            const int t = cr.y + col;
+            const float2 z = (t >= 0 && t < sg.T) ? sp[t] : make_float2(0.f, 0.f);
+            if constexpr (PACK) {
+                const float2 q = cmul(z, s);
+                d0[col] = q.x;
+                d1[col] = q.y;
+            } else {
+                d0[col] = sqrtf(z.x * z.x + z.y * z.y) * s.x;
+            }
+        }
+        return;
+    } else if constexpr (PACK) {
         const int row = blockIdx.x, n = blockIdx.y;                  // row = c * bins + k
         const int c = row / bins, k = row - c * bins;
         const float2* sp = spec + ((long long)n * 2 * bins + row) * T;
@@ -416,15 +473,24 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(const float2* __restrict__
         }
         return;
     }
-    const int row = blockIdx.x;
-    const float2* sp = spec + (long long)row * T;
-    float* dst = mag_pad + (long long)row * Wpad + pad_l;
+    int row = blockIdx.x;
+    const float2* sp;
+    float* dst = nullptr;
+    if constexpr (kSongTable<SRC>) {
+        const SongSeg sg = spec[blockIdx.y];
+        T = sg.T;
+        sp = sg.spec + (long long)row * T;
+        row += blockIdx.y * 2 * bins;
+    } else {
+        sp = spec + (long long)row * T;
+        dst = mag_pad + (long long)row * Wpad + pad_l;
+    }
     float mx = 0.f;
     unsigned long long key = ((unsigned long long)ord32(0.f) << 32) | ord32(0.f);   // the zero padding is part of the reduced array
     for (int t = threadIdx.x; t < T; t += 256) {
         const float2 z = sp[t];
         const float m = sqrtf(z.x * z.x + z.y * z.y);
-        dst[t] = m;
+        if constexpr (!kSongTable<SRC>) dst[t] = m;
         mx = fmaxf(mx, m);
         const unsigned long long k = ((unsigned long long)ord32(z.x) << 32) | ord32(z.y);
         key = k > key ? k : key;
@@ -458,9 +524,14 @@ void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpa
 // CPLX (complex handles): aff[0..1] = 1 / c as a complex number, formed in double and rounded once -- c = max|X| (mode 0,
 // inference.py:74) or the lexicographic complex maximum itself (mode 1, inference.py:87,94: numpy divides by the complex number,
 // which also rotates the phase)
-template <bool CPLX>
+// PER_SONG: blockIdx.x = song, stats = that layout without the header for every song ([song][rows] partials), aff [song][4]
+template <bool CPLX, bool PER_SONG = false>
 __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats, int rows, int mode, float* aff) {
     const unsigned long long* part = reinterpret_cast<const unsigned long long*>(stats) + 2;
+    if constexpr (PER_SONG) {
+        part = reinterpret_cast<const unsigned long long*>(stats) + (long long)blockIdx.x * rows * 2;
+        aff += 4 * blockIdx.x;
+    }
     unsigned mxb = 0u;
     unsigned long long key = ((unsigned long long)ord32(0.f) << 32) | ord32(0.f);
     for (int r = threadIdx.x; r < rows; r += 256) {
@@ -523,11 +594,22 @@ void launch_pack_complex(const float2* spec, int N, int bins, int T, float* dst,
 // per-frame minimum of the final mask over (channel, bin): input of spec_utils.merge_artifacts
 // (lib/spec_utils.py:64).  One workgroup per 64 frames; lanes along time (coalesced rows).
 // CPLX: complex64 masks, the minimum of |mask| (inference.py:28-29)
-template <bool CPLX>
+// DST = const SongSeg: `dst` is the song table, blockIdx.y = song, the minima go to that song's own fmin
+template <bool CPLX, class DST = float>
 __global__ __launch_bounds__(256) void frame_min_kernel(int rows, int T, const float* __restrict__ ma, int Wa,
                                                         const float* __restrict__ mb, int Wb, int shift,
-                                                        float* __restrict__ fmin) {
+                                                        DST* __restrict__ dst) {
     __shared__ float red[4][64];
+    float* __restrict__ fmin;
+    if constexpr (kSongTable<DST>) {
+        const SongSeg sg = dst[blockIdx.y];
+        T = sg.T;
+        ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
+        if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
+        fmin = sg.fmin;
+    } else {
+        fmin = dst;
+    }
     const int t = blockIdx.x * 64 + (threadIdx.x & 63);
     const int part = threadIdx.x >> 6;
     float m = 3.4e38f;
@@ -556,10 +638,20 @@ void launch_frame_min(int bins, int T, const float* mask_a, int Wa, const float*
 }
 
 // CPLX: complex64 masks, complex products (final_mask: TTA average and merge_artifacts blend of a complex mask)
-template <bool CPLX>
-__global__ void apply_mask_kernel(const float2* __restrict__ spec, int bins, int T, const float* __restrict__ ma,
+template <bool CPLX, class SRC = const float2>
+__global__ void apply_mask_kernel(SRC* __restrict__ src, int bins, int T, const float* __restrict__ ma,
                                   int Wa, const float* __restrict__ mb, int Wb, int shift, const float* __restrict__ wgt,
                                   float2* __restrict__ y, float2* __restrict__ v) {
+    const float2* __restrict__ spec;
+    if constexpr (kSongTable<SRC>) {                 // blockIdx.y = song, its own y / v
+        const SongSeg sg = src[blockIdx.y];
+        spec = sg.spec; T = sg.T; y = sg.y; v = sg.v;
+        ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
+        if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
+        if (wgt) wgt += sg.frame0;
+    } else {
+        spec = src;
+    }
     const long long total = 2LL * bins * T;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total) return;
@@ -603,6 +695,88 @@ void launch_apply_mask_complex(const float2* spec, int bins, int T, const float2
     const long long total = 2LL * bins * T;
     VR_LAUNCH((apply_mask_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, spec, bins, T,
               reinterpret_cast<const float*>(mask_a), Wa, reinterpret_cast<const float*>(mask_b), Wb, shift, wgt, y, v);
+    VR_HIP(hipGetLastError());
+}
+
+// ---- many songs in one call (vr_separate_many / vr_separate_wave_many): the SEG instantiations --------------------------------
+// Every launch covers all songs of the call: the song is a grid dimension sized for the longest one.
+bool many_tiled_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
+
+void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const SongSeg>), 160 * 1024);
+    prof_note(0.0, 2.0 * (4.0 * sum_L + 8.0 * (double)bins * sum_T));
+    VR_LAUNCH((stft_tile_kernel<const SongSeg>), dim3((unsigned)((max_T + F - 1) / F), 2, n_songs), dim3(1024), lds, st, pl, songs, 0LL, 0, F, nullptr);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_song_stats(const SongSeg* songs, int n_songs, int bins, double sum_T, unsigned long long* part, hipStream_t st) {
+    prof_note(0.0, 2.0 * (double)bins * 8.0 * sum_T);
+    VR_LAUNCH((mag_pad_kernel<false, const SongSeg>), dim3(2 * bins, n_songs), dim3(256), 0, st, songs, 0, nullptr, 0, 0, part, bins, nullptr);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_song_coef(const unsigned long long* part, int n_songs, int rows, int mode, bool cplx, float* aff, hipStream_t st) {
+    const unsigned* stats = reinterpret_cast<const unsigned*>(part);
+    if (cplx) VR_LAUNCH((coef_affine_kernel<true, true>), dim3(n_songs), dim3(256), 0, st, stats, rows, mode, aff);
+    else VR_LAUNCH((coef_affine_kernel<false, true>), dim3(n_songs), dim3(256), 0, st, stats, rows, mode, aff);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_crop_gather(const SongSeg* songs, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
+                        float* dst, hipStream_t st) {
+    prof_note(0.0, (double)count * 2 * max_bin * cropsize * (8.0 + (cplx ? 8.0 : 4.0)));
+    // (the kernel's T / Wpad / part / scale slots carry cropsize / max_bin / the crop list / aff: see mag_pad_kernel)
+    unsigned long long* list = reinterpret_cast<unsigned long long*>(const_cast<int2*>(crops));
+    const float2* inv = reinterpret_cast<const float2*>(aff);
+    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const SongSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, songs, cropsize, dst, max_bin, 0, list, bins, inv);
+    else VR_LAUNCH((mag_pad_kernel<false, const SongSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, songs, cropsize, dst, max_bin, 0, list, bins, inv);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_frame_min_many(const SongSeg* songs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                           hipStream_t st) {
+    const dim3 grid((max_T + 63) / 64, n_songs);
+    const float* mb = tta ? mask : nullptr;
+    if (cplx) VR_LAUNCH((frame_min_kernel<true, const SongSeg>), grid, dim3(256), 0, st, 2 * bins, 0, mask, W, mb, W, 0, songs);
+    else VR_LAUNCH((frame_min_kernel<false, const SongSeg>), grid, dim3(256), 0, st, 2 * bins, 0, mask, W, mb, W, 0, songs);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                            const float* wgt, hipStream_t st) {
+    const long long total = 2LL * bins * max_T;
+    const dim3 grid((unsigned)((total + 255) / 256), n_songs);
+    const float* mb = tta ? mask : nullptr;
+    if (cplx) VR_LAUNCH((apply_mask_kernel<true, const SongSeg>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr);
+    else VR_LAUNCH((apply_mask_kernel<false, const SongSeg>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
+                              bool cplx, const float* wgt, int which, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    if (max_T < 2) return;
+    const int F = tile_frames(pl, M);
+    const int S = F - 1;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
+    const dim3 grid((unsigned)((max_T - 1 + S - 1) / S), 2, n_songs);
+    prof_note(0.0, 2.0 * ((double)bins * sum_T * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * sum_T));
+    const float* mb = tta ? mask : nullptr;
+    if (cplx) {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const SongSeg>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<true, const SongSeg>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+    } else {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<false, const SongSeg>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+    }
     VR_HIP(hipGetLastError());
 }
 

@@ -74,6 +74,78 @@ class Separator(object):
         return y, v
 
 
+    def separate_many(self, X_specs, tta=False):
+        """separate / separate_tta for a list of spectrograms [2, bins, T_s] in ONE library call: returns [(y_spec, v_spec), ...],
+        each pair what separate(X_s) / separate_tta(X_s) returns for that song alone.  The crops of all songs (and of both TTA
+        passes) share device batches of `self.batchsize` crops."""
+        h = self.model._need_handle()
+        specs = [np.ascontiguousarray(np.asarray(X).astype(np.complex64)) for X in X_specs]
+        if not specs:
+            raise ValueError('separate_many needs at least one spectrogram')
+        for X in specs:
+            if X.ndim != 3 or X.shape[0] != 2 or X.shape[1] != self.model.output_bin:
+                raise ValueError('every X_spec must be [2, %d, T]' % self.model.output_bin)
+        self.model.eval()
+        ys = [np.empty_like(X) for X in specs]
+        vs = [np.empty_like(X) for X in specs]
+        T = (native.ctypes.c_int * len(specs))(*[X.shape[2] for X in specs])
+        native.check(native.lib().vr_separate_many(
+            h.h, len(specs), native.ptr_table([X.ctypes.data for X in specs]), 0, T, self._flags(tta), int(self.batchsize),
+            int(self.cropsize), native.ptr_table([a.ctypes.data for a in ys]), native.ptr_table([a.ctypes.data for a in vs]), 0))
+        return list(zip(ys, vs))
+
+    def separate_wave_many(self, waves, tta=False):
+        """separate_wave for a list of waves [2, L_s] in ONE library call: returns [(y_wave, v_wave), ...].  A list of numpy arrays
+        gives numpy arrays; a list of torch cuda tensors (all on the model's GPU) stays on the device, as in separate_wave."""
+        h = self.model._need_handle()
+        hop = self.model.hop_length
+        waves = list(waves)
+        if not waves:
+            raise ValueError('separate_wave_many needs at least one wave')
+        self.model.eval()
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        on_dev = torch is not None and all(torch.is_tensor(w) and w.is_cuda for w in waves)
+        if on_dev:
+            waves = [w.detach().to(torch.float32).contiguous() for w in waves]
+        else:
+            if torch is not None and any(torch.is_tensor(w) and w.is_cuda for w in waves):
+                raise ValueError('separate_wave_many: either every wave is a cuda tensor or none is')
+            waves = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w in waves]
+        for w in waves:
+            if w.ndim != 2 or w.shape[0] != 2:
+                raise ValueError('every wave must be [2, L]')
+        lens = [int(w.shape[1]) for w in waves]
+        L = (native.ctypes.c_int64 * len(waves))(*lens)
+        if on_dev:
+            ys = [torch.empty((2, hop * (n // hop)), dtype=torch.float32, device=w.device) for w, n in zip(waves, lens)]
+            vs = [torch.empty_like(a) for a in ys]
+            torch.cuda.current_stream(waves[0].device).synchronize()
+            addr = lambda seq: native.ptr_table([a.data_ptr() for a in seq])
+        else:
+            ys = [np.empty((2, hop * (n // hop)), dtype=np.float32) for n in lens]
+            vs = [np.empty_like(a) for a in ys]
+            addr = lambda seq: native.ptr_table([a.ctypes.data for a in seq])
+        # (an empty torch tensor has a null data_ptr; the library reports waves shorter than one hop before it reads any pointer table entry)
+        native.check(native.lib().vr_separate_wave_many(h.h, len(waves), addr(waves), 1 if on_dev else 0, L, self._flags(tta),
+                                                        int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0))
+        return list(zip(ys, vs))
+
+
+def expand_inputs(path, songs_per_call):
+    """--input: a file is one group of one song; a directory is every .wav in it, sorted by name, in groups of songs_per_call."""
+    import os
+    if not os.path.isdir(path):
+        return [[path]]
+    if songs_per_call < 1:
+        raise ValueError('--songs_per_call must be at least 1')
+    files = sorted(os.path.join(path, f) for f in os.listdir(path)
+                   if f.lower().endswith('.wav') and os.path.isfile(os.path.join(path, f)))
+    return [files[i:i + songs_per_call] for i in range(0, len(files), songs_per_call)]
+
+
 def main(argv=None):
     """inference.py main() (inference.py:107-185) with the same flags; decoding / resampling / WAV writing come from
     vocal_remover_amd.audio (no librosa / soundfile), everything numeric from the library.  --output_image is the only
@@ -98,6 +170,7 @@ def main(argv=None):
     p.add_argument('--is_complex', action='store_true')              # a checkpoint of CascadedNet(..., is_complex=True)
     p.add_argument('--output_image', '-I', action='store_true')      # accepted for command-line compatibility; no image is written
     p.add_argument('--output_dir', '-o', type=str, default="")
+    p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call
     args = p.parse_args(argv)
 
     if args.output_image:
@@ -107,18 +180,33 @@ def main(argv=None):
     model = nets.CascadedNet(args.n_fft, args.hop_length, 32, 128, is_complex=args.is_complex)
     model.load_state_dict(torch.load(args.pretrained_model, map_location='cpu'))
     model.to(device)
-    X, sr = audio.load(args.input, sr=args.sr, mono=False, dtype=np.float32, res_type='kaiser_fast')
-    basename = os.path.splitext(os.path.basename(args.input))[0]
-    if X.ndim == 1:
-        X = np.asarray([X, X])                   # mono to stereo (inference.py:143-145)
     sp = Separator(model=model, device=device, batchsize=args.batchsize, cropsize=args.cropsize, postprocess=args.postprocess)
-    y_wave, v_wave = sp.separate_wave(X, tta=args.tta)      # STFT -> separate -> iSTFT x2 in one device-resident call
     output_dir = args.output_dir
     if output_dir != "":
         output_dir = output_dir.rstrip('/') + '/'
         os.makedirs(output_dir, exist_ok=True)
-    audio.write('{}{}_Instruments.wav'.format(output_dir, basename), y_wave.T, sr)
-    audio.write('{}{}_Vocals.wav'.format(output_dir, basename), v_wave.T, sr)
+
+    def load(path):
+        X, sr = audio.load(path, sr=args.sr, mono=False, dtype=np.float32, res_type='kaiser_fast')
+        if X.ndim == 1:
+            X = np.asarray([X, X])               # mono to stereo (inference.py:143-145)
+        return X, sr
+
+    def write(path, y_wave, v_wave, sr):
+        basename = os.path.splitext(os.path.basename(path))[0]
+        audio.write('{}{}_Instruments.wav'.format(output_dir, basename), y_wave.T, sr)
+        audio.write('{}{}_Vocals.wav'.format(output_dir, basename), v_wave.T, sr)
+
+    if not os.path.isdir(args.input):
+        X, sr = load(args.input)
+        y_wave, v_wave = sp.separate_wave(X, tta=args.tta)  # STFT -> separate -> iSTFT x2 in one device-resident call
+        write(args.input, y_wave, v_wave, sr)
+        return 0
+    for group in expand_inputs(args.input, args.songs_per_call):
+        loaded = [load(path) for path in group]
+        stems = sp.separate_wave_many([X for X, _ in loaded], tta=args.tta)      # the crops of the group's songs share device batches
+        for path, (_, sr), (y_wave, v_wave) in zip(group, loaded, stems):
+            write(path, y_wave, v_wave, sr)
     return 0
 
 

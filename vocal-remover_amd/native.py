@@ -33,6 +33,12 @@ _SIGNATURES = {
                                    ctypes.c_int, c_f32p, c_f32p, ctypes.c_int]),
     'vr_separate_wave': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_int]),
+    'vr_separate_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_separate_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     'vr_train_step': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.POINTER(ctypes.c_float), c_f32p, ctypes.c_int]),
     'vr_forward_train': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int]),
@@ -137,6 +143,11 @@ def debug_kernel(handle, name, dims, fparams, inputs, outputs):
 def np_ptr(a):
     assert a.flags['C_CONTIGUOUS']
     return ctypes.c_void_p(a.ctypes.data)
+
+
+def ptr_table(addresses):
+    """A host table of data pointers (vr_separate_many / vr_separate_wave_many) from integer addresses."""
+    return (ctypes.c_void_p * len(addresses))(*[int(a) for a in addresses])
 
 
 class Handle:
