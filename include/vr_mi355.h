@@ -143,6 +143,58 @@ int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int sp
 int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
                           int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device);
 
+/* ---- streaming separation: push audio in blocks, get the stems back with bounded state -----------------------------------
+ * The offline call's crops sit at multiples of roi = cropsize - 2 * offset whatever the song's length (make_padding: pad_l = offset),
+ * the --tta pass is the same list shifted by roi / 2, and with hop == n_fft / 2 frame t needs the samples below (t + 1) * hop.  The
+ * only whole-song quantity is the normaliser c.  GIVEN c, a stream therefore runs the crops vr_separate_wave runs, on the same numbers:
+ * for any split of a wave [2][L] into pushes of any sizes >= 1 followed by vr_stream_flush, the concatenated y / v have hop * (L / hop)
+ * samples and are what vr_separate_wave(tta = flags & VR_STREAM_TTA) returns for the whole wave on this handle (the batches are
+ * composed differently, which moves the result by rounding only: tests hold 2e-4 * scale, the bar between the offline entry points),
+ * provided (coef_re, coef_im) is that call's normaliser: max|X| (plain; coef_im 0) or numpy's lexicographic complex maximum (tta).
+ * A magnitude handle uses |coef|, a VR_CREATE_COMPLEX handle the complex number (both kinds of handle are supported).  A
+ * VR_STREAM_MEASURE stream runs no network and returns no samples; after its flush vr_stream_coef gives exactly that normaliser
+ * (the lexicographic maximum with VR_STREAM_TTA, else max|X| and 0), from the statistics pass of the offline path.
+ * coef_re == coef_im == 0 (plain streams only; with VR_STREAM_TTA it is VR_ERR_BAD_ARGUMENT): a RUNNING normaliser -- crop i is
+ * divided by max|X| over the frames below (i + 1) * roi + offset, the end of its own window.  That is NOT the offline result (it is,
+ * when the loudest frame lies inside crop 0's window); like every mode it does not depend on how the input was split into pushes.
+ * Zero padding in front of the first and behind the last frame, the right zero padding of the last crops and the window-sum division
+ * are the offline kernels'.  A frame whose window reaches past the samples received waits for more data or for the flush.
+ *
+ * vr_stream_push runs every crop that has become ready -- the crops of both passes share device batches of `batchsize` (<= 0: 8) --
+ * and returns every output sample that is final: *n_out per channel, possibly 0, at y / v [2][capacity] (channel pitch = capacity).
+ * A capacity below what the call returns is VR_ERR_BAD_ARGUMENT, reported before anything is consumed; vr_last_error() names the size
+ * needed (vr_stream_plan computes it: samples_out after minus before).  wave: planar [2][n].
+ * vr_stream_info: lookahead_samples = (roi + offset) * hop, the samples that must have arrived before the first output sample;
+ * block_samples = roi * hop, the step in which crops become ready; state_bytes = the device memory the stream holds: an input tail,
+ * a ring of spectrogram frames, a mask ring per pass, one hop of overlap-add carry per stem and channel, the normaliser.  It depends
+ * on (n_fft, cropsize, batchsize, flags) and not on how much audio has passed; the handle's staging arena holds one push (see
+ * vr_arena_bytes).  A push larger than batchsize * roi frames is worked through in steps of that size.
+ * Errors (VR_ERR_BAD_ARGUMENT, before the device is touched): training mode (at open and at every push), hop_length != n_fft / 2,
+ * VR_STREAM_POSTPROCESS (merge_artifacts needs whole-song runs), an unknown flag, push or flush after flush, fewer than hop_length
+ * samples in all at flush ("wave shorter than one hop", as vr_separate_wave).  Other calls on the handle between two pushes are
+ * allowed (the stream keeps nothing in the handle's arenas); a stream must be closed before its handle is destroyed.  A push that
+ * fails half way (a HIP error) leaves the stream unusable: close it. */
+typedef struct vr_stream_s* vr_stream;
+#define VR_STREAM_TTA         1   /* second pass shifted by roi/2, masks averaged (separate_tta)                  */
+#define VR_STREAM_MEASURE     2   /* no network, no output: only accumulate the normaliser                        */
+#define VR_STREAM_POSTPROCESS 4   /* refused: see above                                                           */
+int vr_stream_open(vr_handle h, int cropsize, int batchsize, int flags, double coef_re, double coef_im, vr_stream* out);
+int vr_stream_push(vr_stream s, const float* wave, int on_device, int64_t n, float* y, float* v, int out_on_device, int64_t capacity,
+                   int64_t* n_out);
+int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t capacity, int64_t* n_out);
+int vr_stream_coef(vr_stream s, double* coef_re_im /*[2]*/);
+int vr_stream_info(vr_stream s, int64_t* lookahead_samples, int64_t* block_samples, int64_t* state_bytes);
+int vr_stream_close(vr_stream s);
+/* Host only, no handle, no GPU: the schedule the executor follows.  After samples_in samples (flushed: and the flush):
+ * frames_ready = samples_in / hop (flushed: + 1, the offline frame count); crops_ready[2] = crops run so far per pass (flushed: the
+ * offline `patches` of make_padding, T / roi + 1 and, tta, T / roi + 2; crops_ready[1] = 0 without tta); samples_out = output
+ * samples final so far per channel (flushed: hop * (samples_in / hop)).  Any out pointer may be NULL.
+ * VR_ERR_BAD_ARGUMENT: hop * 2 != n_fft, cropsize <= 2 * offset, samples_in < 0, flushed with samples_in < hop. */
+int vr_stream_plan(int n_fft, int hop, int cropsize, int offset, int tta, int64_t samples_in, int flushed, int64_t* frames_ready,
+                   int64_t* crops_ready /*[2]*/, int64_t* samples_out);
+/* Device bytes the handle holds for staging (inputs, outputs, masks of one call) and for the network's workspace. */
+int vr_arena_bytes(vr_handle h, int64_t* staging_bytes, int64_t* workspace_bytes);
+
 /* ---- training: the body of train.train_epoch (train.py:77-96) ------------------------------------ */
 /* mask = model(X); loss = L1Loss()(mask * X, y); (loss / accumulation_steps).backward()
  * X, y: [B, 2, bins, T] fp32.  Gradients ACCUMULATE in the library's gradient arena until vr_zero_grad

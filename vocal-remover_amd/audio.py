@@ -42,7 +42,11 @@ def read_wav(path):
         raise ValueError('%s: missing fmt or data chunk' % path)
     tag, ch, rate, align, bits = fmt
     n = len(body) // align
-    body = body[:n * align]
+    return _decode(path, body[:n * align], tag, ch, bits), int(rate)
+
+
+def _decode(path, body, tag, ch, bits):
+    """Interleaved sample bytes of whole frames -> float32 [channels, samples]."""
     if tag == _PCM and bits == 16:
         x = np.frombuffer(body, '<i2').astype(np.float32) / 32768.0
     elif tag == _PCM and bits == 8:
@@ -60,7 +64,94 @@ def read_wav(path):
         x = np.frombuffer(body, '<f8').astype(np.float32)
     else:
         raise ValueError('%s: unsupported WAV encoding (format tag %d, %d bits)' % (path, tag, bits))
-    return np.ascontiguousarray(x.reshape(n, ch).T), int(rate)
+    return np.ascontiguousarray(x.reshape(-1, ch).T)
+
+
+class WavBlockReader(object):
+    """A RIFF/WAVE file read block by block (streaming separation): the file is never held whole.  `blocks(n)` yields float32 arrays
+    [channels, <= n] in file order and may be called again for another pass; the decoding is read_wav's."""
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, 'rb') as f:
+            head = f.read(12)
+            if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+                raise ValueError('%s: not a RIFF/WAVE file' % path)
+            fmt = None
+            self._data_pos = None
+            while True:
+                hdr = f.read(8)
+                if len(hdr) < 8:
+                    break
+                cid, size = hdr[:4], struct.unpack('<I', hdr[4:])[0]
+                if cid == b'fmt ':
+                    chunk = f.read(size)
+                    tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', chunk[:16])
+                    if tag == _EXT and len(chunk) >= 26:
+                        tag = struct.unpack('<H', chunk[24:26])[0]
+                    fmt = (tag, ch, rate, align, bits)
+                    f.seek(size & 1, 1)
+                elif cid == b'data':
+                    self._data_pos = f.tell()
+                    left = os.path.getsize(path) - self._data_pos
+                    self._data_bytes = min(size, left)          # (a writer that never patched its sizes leaves 0xFFFFFFFF here)
+                    break
+                else:
+                    f.seek(size + (size & 1), 1)
+        if fmt is None or self._data_pos is None:
+            raise ValueError('%s: missing fmt or data chunk' % path)
+        self._tag, self.channels, self.sr, self._align, self._bits = fmt
+        self.samples = self._data_bytes // self._align
+
+    def blocks(self, block_samples):
+        with open(self.path, 'rb') as f:
+            f.seek(self._data_pos)
+            left = self.samples
+            while left > 0:
+                n = min(int(block_samples), left)
+                body = f.read(n * self._align)
+                n = len(body) // self._align
+                if n == 0:
+                    break
+                yield _decode(self.path, body[:n * self._align], self._tag, self.channels, self._bits)
+                left -= n
+
+
+class WavAppendWriter(object):
+    """write()'s 16-bit PCM file, grown block by block: append(data [samples, channels]); close() patches the two sizes."""
+
+    def __init__(self, path, sr, channels):
+        self._f = open(path, 'wb')
+        self._ch, self._bytes = int(channels), 0
+        self._f.write(b'RIFF' + struct.pack('<I', 36) + b'WAVE')
+        self._f.write(b'fmt ' + struct.pack('<IHHIIHH', 16, _PCM, self._ch, int(sr), int(sr) * self._ch * 2, self._ch * 2, 16))
+        self._f.write(b'data' + struct.pack('<I', 0))
+
+    def append(self, data):
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim == 1:
+            data = data[:, None]
+        if data.shape[1] != self._ch:
+            raise ValueError('append: expected [samples, %d]' % self._ch)
+        body = np.clip(np.rint(data * 32767.0), -32768, 32767).astype('<i2').tobytes()
+        self._f.write(body)
+        self._bytes += len(body)
+
+    def close(self):
+        if self._f is None:
+            return
+        self._f.seek(4)
+        self._f.write(struct.pack('<I', 36 + self._bytes))
+        self._f.seek(40)
+        self._f.write(struct.pack('<I', self._bytes))
+        self._f.close()
+        self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def write(path, data, sr):

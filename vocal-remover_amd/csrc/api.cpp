@@ -193,6 +193,95 @@ int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, i
     });
 }
 
+// ---- streaming separation ----------------------------------------------------------------------------------------------------
+struct vr_stream_s {
+    vr_model* h;
+    vr::StreamState* st;
+};
+
+#define NEED_STREAM(s)                                           \
+    if (!(s) || !(s)->st) {                                      \
+        g_err = "null stream";                                   \
+        return VR_ERR_BAD_ARGUMENT;                              \
+    }
+
+int vr_stream_plan(int n_fft, int hop, int cropsize, int offset, int tta, int64_t samples_in, int flushed, int64_t* frames_ready,
+                   int64_t* crops_ready, int64_t* samples_out) {
+    return guard([&] {
+        const vr::StreamSchedule p = vr::stream_schedule(n_fft, hop, cropsize, offset, tta != 0, samples_in, flushed != 0);
+        if (frames_ready) *frames_ready = p.frames;
+        if (crops_ready) { crops_ready[0] = p.crops[0]; crops_ready[1] = p.crops[1]; }
+        if (samples_out) *samples_out = p.samples_out;
+    });
+}
+
+int vr_stream_open(vr_handle h, int cropsize, int batchsize, int flags, double coef_re, double coef_im, vr_stream* out) {
+    if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
+    *out = nullptr;
+    NEED(h);
+    return guard([&] {
+        vr::StreamState* st = h->m.stream_open(cropsize, batchsize, flags, coef_re, coef_im);
+        *out = new vr_stream_s{h, st};
+    });
+}
+
+int vr_stream_push(vr_stream s, const float* wave, int on_device, int64_t n, float* y, float* v, int out_on_device, int64_t capacity,
+                   int64_t* n_out) {
+    NEED_STREAM(s);
+    return guard([&] {
+        long long got = 0;
+        s->h->m.stream_push(*s->st, wave, on_device != 0, n, false, y, v, out_on_device != 0, capacity, &got);
+        if (n_out) *n_out = got;
+    });
+}
+
+int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t capacity, int64_t* n_out) {
+    NEED_STREAM(s);
+    return guard([&] {
+        long long got = 0;
+        s->h->m.stream_push(*s->st, nullptr, false, 0, true, y, v, out_on_device != 0, capacity, &got);
+        if (n_out) *n_out = got;
+    });
+}
+
+int vr_stream_coef(vr_stream s, double* coef_re_im) {
+    NEED_STREAM(s);
+    return guard([&] {
+        VR_CHECK(coef_re_im, VR_ERR_BAD_ARGUMENT, "null argument");
+        VR_CHECK(s->st->measure && s->st->flushed, VR_ERR_BAD_ARGUMENT, "vr_stream_coef: the normaliser exists after the flush of a VR_STREAM_MEASURE stream");
+        coef_re_im[0] = s->st->coef[0];
+        coef_re_im[1] = s->st->coef[1];
+    });
+}
+
+int vr_stream_info(vr_stream s, int64_t* lookahead_samples, int64_t* block_samples, int64_t* state_bytes) {
+    NEED_STREAM(s);
+    return guard([&] {
+        const vr::Model& m = s->h->m;
+        if (lookahead_samples) *lookahead_samples = (int64_t)(s->st->roi + m.offset) * m.hop;
+        if (block_samples) *block_samples = (int64_t)s->st->roi * m.hop;
+        if (state_bytes) *state_bytes = (int64_t)s->st->state_bytes;
+    });
+}
+
+int vr_stream_close(vr_stream s) {
+    if (!s) { g_err = "null stream"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        s->h->m.stream_close(s->st);
+        delete s;
+    });
+}
+
+int vr_arena_bytes(vr_handle h, int64_t* staging_bytes, int64_t* workspace_bytes) {
+    NEED(h);
+    return guard([&] {
+        long long a = 0, b = 0;
+        h->m.arena_bytes(&a, &b);
+        if (staging_bytes) *staging_bytes = a;
+        if (workspace_bytes) *workspace_bytes = b;
+    });
+}
+
 int vr_train_step(vr_handle h, const float* X, const float* y, int on_device, int B, int T, int accumulation_steps,
                   float* loss_out, float* mask_out, int mask_on_device) {
     NEED(h);

@@ -219,4 +219,46 @@ void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bi
 void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
                               bool cplx, const float* wgt, int which, hipStream_t st);
 
+// ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
+// The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
+// step).  Samples and frames carry their ABSOLUTE index in the stream; the device keeps rings: frame t of the complex spectrogram at
+// column t % R of ring [2][bins][R], the mask of frame t at column t % RM of mask_a [2][bins][RM] (complex64 for a complex handle) and,
+// for the TTA pass, at column (t + shift) % RM of mask_b (the offline layout: crop j of a pass at column j * roi).
+struct StreamSeg {
+    // samples: p < blk_base lives in tail[ch * tail_pitch + p - tail_base], p >= blk_base in blk[ch * blk_pitch + p - blk_base];
+    // outside [0, L) a sample is zero (centre padding in front; behind the data only the flush step's last frame reaches there)
+    const float* tail;
+    const float* blk;
+    float* tail_out;          // the STFT step leaves the samples [tail_out_base, L) here for the next step (never the buffer it reads)
+    long long tail_base, blk_base, blk_pitch, tail_out_base;
+    long long L;              // samples received so far, this step's block included
+    int tail_pitch;
+    // frames
+    float2* ring;
+    int R;
+    int t_new;                // the STFT writes the frames [t_new, T); the statistics pass reads the same ones
+    int T;                    // frames valid so far; the true frame count once flushed (the crop gather writes zero outside [0, T))
+    // masks
+    const float* mask_a;
+    const float* mask_b;      // null without TTA
+    int RM, shift;
+    // masked iSTFT of the frames [t_out, t_done): segment s = second half of frame s + first half of frame s + 1 lands at
+    // wave[ch * out_pitch + (s - t_out) * hop]; `carried`: frame t_out was transformed by the previous step, its windowed second half
+    // comes from carry_in; the second half of frame t_done - 1 goes to carry_out ([stem][ch][hop], never the buffer read)
+    int t_out, t_done, carried;
+    const float* carry_in;
+    float* carry_out;
+    float* y_wave;
+    float* v_wave;
+    long long out_pitch;
+};
+bool stream_tiled_available(const FFTPlan& pl, int hop);
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int new_frames, double new_samples, hipStream_t st);
+// part: per-row partial maxima as launch_mag_pad leaves them (stats + 16 bytes); the new frames are reduced INTO them
+void launch_stream_stats(const StreamSeg* seg, int bins, int new_frames, unsigned long long* part, hipStream_t st);
+// crops[n] = (0, first frame; may be negative): as launch_crop_gather, from the ring, aff = 1 / c of the stream
+void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
+                          float* dst, hipStream_t st);
+void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int segments, bool cplx, bool tta, int which, hipStream_t st);
+
 }  // namespace vr

@@ -97,6 +97,36 @@ void merge_artifacts_weight(const std::vector<float>& fmin, std::vector<float>& 
                             int fade);
 
 
+// The schedule of a streaming session (vr_stream_plan: the one statement of it, the executor follows it).  hop == n_fft / 2: frame t
+// reads the samples [(t-1) hop, (t+1) hop), so it is ready once (t+1) hop samples have arrived, or -- zeros behind the data -- at flush,
+// when the frame count becomes the offline 1 + L / hop.  Crop i of pass 0 covers the frames [i roi - offset, (i+1) roi + offset) and
+// gives the mask of [i roi, (i+1) roi); pass 1 (tta) is the same list shifted by -roi/2.  A crop runs once every frame of its window
+// is ready, at flush the offline count of make_padding.  Frame t is final when the crops of both passes that hold its mask have run;
+// with `done` final frames, hop * (done - 1) output samples are final.
+struct StreamSchedule { long long frames, crops[2], done, samples_out; };
+StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed);
+
+// One streaming session of a handle (vr_stream_*): everything that outlives a push.  Device state is one slab whose size depends on
+// (n_fft, cropsize, batchsize, tta) only.
+struct StreamState {
+    int cropsize = 0, bs = 0, roi = 0, R = 0, RM = 0, chunk_frames = 0;
+    bool tta = false, measure = false, running = false;
+    bool flushed = false, broken = false;
+    long long samples = 0, tail_base = 0;
+    long long frames = 0, crops[2] = {0, 0}, done = 0;
+    char* slab = nullptr; size_t state_bytes = 0;
+    float* tail[2] = {nullptr, nullptr}; int tail_cur = 0;
+    float2* ring = nullptr;
+    float* mask[2] = {nullptr, nullptr};
+    float* carry[2] = {nullptr, nullptr}; int carry_cur = 0;
+    unsigned* stats = nullptr;                           // launch_mag_pad's layout: 16-byte header + 2 * bins rows of partial maxima
+    float* aff = nullptr;                                // 1 / c as the crop gather reads it
+    double coef[2] = {0.0, 0.0};                         // MEASURE: the normaliser, valid after flush
+    // host copies of what a push sends to the device, alive until the push has drained
+    std::deque<StreamSeg> segs_h;
+    std::deque<std::vector<int2>> crops_h;
+};
+
 class Model {
 public:
     Model(int device, int n_fft, int hop, int nout, int nout_lstm, bool is_complex = false);
@@ -147,6 +177,13 @@ public:
     void separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta,
                            int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev);
     void run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops);
+    // ---- streaming separation (vr_stream_*) ----
+    StreamState* stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im);
+    // n samples more (flush: none, the end of the input); y / v [2][capacity] receive *n_out final samples per channel
+    void stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
+                     long long capacity, long long* n_out);
+    void stream_close(StreamState* S);
+    void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
     void separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
                             float* y_wave, float* v_wave, bool out_on_dev);
 
@@ -357,6 +394,9 @@ private:
     Tensor run_lstm(LSTMMod& M, const Tensor& h);
     SrcSpec upsampled(const Tensor& t);
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)
+    struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off;
+                          StreamSeg* seg_d; int2* crops_d; float* gather; };
+    void stream_step(StreamState& S, StreamStepIO& io_, bool final);
     void tap(const std::string& name, const Tensor& t);
     bool dry = false;
     const float* dropout_dev = nullptr;                  // [5][N][Cmax] keep-masks (training), or null

@@ -1923,6 +1923,314 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
 }
 
 // =====================================================================================================
+// Streaming separation (vr_stream_*): audio is pushed in blocks, stems come back as soon as they are final.
+// The offline call's crops sit at multiples of roi whatever the song's length, and the only whole-song quantity is the normaliser:
+// given it, a stream runs the same crops on the same numbers.  Per stream the device keeps an input tail, a ring of spectrogram
+// frames, a mask ring per pass, one hop of overlap-add carry per stem and channel, and the normaliser (StreamState); the staging
+// arena holds one push.  A push is cut into steps of at most `chunk_frames` new frames, so the rings have a fixed size; a step is
+// one STFT of the new frames, one statistics launch (running normaliser / MEASURE), the ready crops through run_crop_chunks, and one
+// masked iSTFT per stem over the frames that became final.
+// =====================================================================================================
+StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed) {
+    VR_CHECK(n_fft >= 2 && hop > 0 && hop * 2 == n_fft, -2, "streaming needs hop_length == n_fft / 2 (the frame-tiled STFT / iSTFT kernels exist only there)");
+    VR_CHECK(offset >= 0 && cropsize - 2 * offset > 0, -2, "cropsize must exceed 2*offset");
+    VR_CHECK(samples_in >= 0, -2, "negative sample count");
+    VR_CHECK(!flushed || samples_in >= hop, -2, "wave shorter than one hop");
+    const long long roi = cropsize - 2 * offset, half = roi / 2;
+    StreamSchedule p{};
+    p.frames = samples_in / hop + (flushed ? 1 : 0);
+    if (flushed) {
+        p.crops[0] = p.frames / roi + 1;
+        p.crops[1] = tta ? p.frames / roi + 2 : 0;
+        p.done = p.frames;
+    } else {
+        p.crops[0] = p.frames >= offset ? (p.frames - offset) / roi : 0;
+        p.crops[1] = (tta && p.frames + half >= offset) ? (p.frames - offset + half) / roi : 0;
+        p.done = tta ? std::max(0LL, std::min(p.crops[0] * roi, p.crops[1] * roi - half)) : p.crops[0] * roi;
+    }
+    p.samples_out = (long long)hop * std::max(0LL, p.done - 1);
+    return p;
+}
+
+static unsigned host_ord32(float f) {
+    unsigned u;
+    memcpy(&u, &f, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+static float host_unord32(unsigned o) {
+    const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im) {
+    // ---- arguments: nothing here touches the device
+    VR_CHECK(!(flags & ~7), -2, "unknown vr_stream_open flag");
+    VR_CHECK(!(flags & 4), -2, "a stream cannot run --postprocess: merge_artifacts looks at runs of frames over the whole song; use vr_separate_wave");
+    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    VR_CHECK(hop * 2 == n_fft && stream_tiled_available(plan, hop), -2,
+             "streaming needs hop_length == n_fft / 2 (the frame-tiled STFT / iSTFT kernels exist only there)");
+    check_T(cropsize, offset, 1);
+    VR_CHECK(cropsize - 2 * offset > 0, -6, "cropsize must exceed 2*offset");
+    const bool tta = flags & 1, measure = (flags & 2) != 0;
+    const bool running = !measure && coef_re == 0.0 && coef_im == 0.0;
+    VR_CHECK(!(running && tta), -2, "a tta stream needs the normaliser (coef): the running normaliser exists for plain streams only");
+    VR_CHECK(measure || (std::isfinite(coef_re) && std::isfinite(coef_im)), -2, "coef must be finite");
+    std::unique_ptr<StreamState> S(new StreamState);
+    S->cropsize = cropsize; S->tta = tta; S->measure = measure; S->running = running;
+    S->bs = batchsize > 0 ? batchsize : 8;               // (a stream never sees "all crops": <= 0 means 8)
+    const int roi = cropsize - 2 * offset, bins = output_bin, E = is_complex ? 2 : 1;
+    S->roi = roi;
+    S->chunk_frames = S->bs * roi;
+    // frames still needed before a step reach back less than cropsize + roi / 2, a step adds at most chunk_frames (+ 1 at flush)
+    S->R = cropsize + roi / 2 + S->chunk_frames + 4;
+    // mask columns not yet final before a step: at most roi / 2; a step adds at most bs + 1 crops per pass, the flush offset / roi + 3
+    S->RM = roi * (std::max(S->bs + 1, offset / roi + 3) + 2);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t a = (off + 255) & ~size_t(255); off = a + bytes; return a; };
+    const size_t tail_b = (size_t)2 * 2 * hop * 4, ring_b = (size_t)2 * bins * S->R * 8, mask_b = (size_t)E * 2 * bins * S->RM * 4;
+    const size_t carry_b = (size_t)2 * 2 * hop * 4, stats_b = 16 + (size_t)2 * bins * 16;
+    const size_t o_tail0 = take(tail_b), o_tail1 = take(tail_b), o_ring = take(ring_b);
+    const size_t o_stats = take(stats_b), o_aff = take(64);
+    size_t o_mask[2] = {0, 0}, o_carry[2] = {0, 0};
+    if (!measure) {
+        o_mask[0] = take(mask_b);
+        if (tta) o_mask[1] = take(mask_b);
+        o_carry[0] = take(carry_b); o_carry[1] = take(carry_b);
+    }
+    S->state_bytes = off;
+
+    DeviceGuard dev_guard(device);
+    VR_HIP(hipMalloc(reinterpret_cast<void**>(&S->slab), off));
+    try {
+        char* b = S->slab;
+        S->tail[0] = reinterpret_cast<float*>(b + o_tail0); S->tail[1] = reinterpret_cast<float*>(b + o_tail1);
+        S->ring = reinterpret_cast<float2*>(b + o_ring);
+        S->stats = reinterpret_cast<unsigned*>(b + o_stats); S->aff = reinterpret_cast<float*>(b + o_aff);
+        if (!measure) {
+            S->mask[0] = reinterpret_cast<float*>(b + o_mask[0]);
+            S->mask[1] = tta ? reinterpret_cast<float*>(b + o_mask[1]) : nullptr;
+            S->carry[0] = reinterpret_cast<float*>(b + o_carry[0]); S->carry[1] = reinterpret_cast<float*>(b + o_carry[1]);
+        }
+        VR_HIP(hipMemsetAsync(S->slab, 0, off, stream));
+        // the statistics rows as an empty reduction leaves them (the zero padding is part of the reduced array); a given normaliser
+        // enters as row 0, so that 1 / c comes from the same coef_affine arithmetic as offline
+        std::vector<unsigned long long> st((size_t)2 + 2 * 2 * bins);
+        const unsigned long long zero_key = ((unsigned long long)host_ord32(0.f) << 32) | host_ord32(0.f);
+        st[0] = st[1] = 0;
+        for (int r = 0; r < 2 * bins; ++r) { st[2 + 2 * r] = 0; st[2 + 2 * r + 1] = zero_key; }
+        if (!measure && !running) {
+            const float re = (float)coef_re, im = (float)coef_im;
+            float mag = (float)std::hypot(coef_re, coef_im);
+            if (coef_im == 0.0) mag = std::fabs(re);
+            unsigned mb;
+            memcpy(&mb, &mag, 4);
+            st[2] = mb;
+            const unsigned long long key = ((unsigned long long)host_ord32(re) << 32) | host_ord32(im);
+            st[3] = key > zero_key ? key : zero_key;
+            VR_CHECK(mag > 0.f, -2, "coef must not be zero");
+        }
+        VR_HIP(hipMemcpyAsync(S->stats, st.data(), st.size() * 8, hipMemcpyHostToDevice, stream));
+        if (!measure && !running) {
+            if (is_complex) launch_coef_complex(S->stats, 2 * bins, tta ? 1 : 0, reinterpret_cast<float2*>(S->aff), stream);
+            else launch_coef_affine(S->stats, 2 * bins, tta ? 1 : 0, S->aff, stream);
+        }
+        VR_HIP(hipStreamSynchronize(stream));
+    } catch (...) {
+        hipFree(S->slab);
+        throw;
+    }
+    return S.release();
+}
+
+void Model::stream_close(StreamState* S) {
+    if (!S) return;
+    DeviceGuard dev_guard(device);
+    hipStreamSynchronize(stream);
+    if (S->slab) hipFree(S->slab);
+    delete S;
+}
+
+void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
+    const int bins = output_bin, E = is_complex ? 2 : 1, roi = S.roi, cropsize = S.cropsize;
+    const long long prev_frames = S.frames;
+    S.samples += o.blk_n;
+    const StreamSchedule p = stream_schedule(n_fft, hop, cropsize, offset, S.tta, S.samples, final);
+    VR_CHECK(p.frames < (1LL << 31) - 2 * cropsize, -2, "stream too long");
+    // what the rings must still hold: the oldest frame a coming crop or the iSTFT reads, the oldest mask column not yet final
+    long long oldest = std::min(S.done, S.crops[0] * roi - offset);
+    if (S.tta) oldest = std::min(oldest, S.crops[1] * roi - offset - roi / 2);
+    if (S.measure) oldest = prev_frames;        // (only the statistics pass reads the new frames)
+    VR_CHECK(p.frames - std::max(0LL, oldest) <= S.R, -4, "stream frame ring overflow (planning bug)");
+    if (!S.measure) {
+        VR_CHECK(p.crops[0] * roi - S.done / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+        if (S.tta) VR_CHECK(p.crops[1] * roi - (S.done + roi / 2) / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+    }
+    S.segs_h.emplace_back();
+    StreamSeg& g = S.segs_h.back();
+    g = StreamSeg{};
+    g.tail = S.tail[S.tail_cur]; g.tail_out = S.tail[S.tail_cur ^ 1];
+    g.blk = o.blk; g.blk_pitch = o.blk_pitch;
+    g.tail_base = S.tail_base; g.blk_base = S.samples - o.blk_n;
+    g.tail_out_base = std::max(0LL, (S.samples / hop - 1) * hop);
+    g.L = S.samples; g.tail_pitch = 2 * hop;
+    g.ring = S.ring; g.R = S.R; g.t_new = (int)prev_frames; g.T = (int)p.frames;
+    g.mask_a = S.mask[0]; g.mask_b = S.tta ? S.mask[1] : nullptr; g.RM = S.RM; g.shift = roi / 2;
+    const bool emit = !S.measure && p.done > S.done;
+    g.carried = S.done > 0;
+    g.t_out = S.done > 0 ? (int)S.done - 1 : 0; g.t_done = (int)p.done;
+    g.carry_in = S.carry[S.carry_cur]; g.carry_out = S.carry[S.carry_cur ^ 1];
+    g.y_wave = o.y ? o.y + o.out_off : nullptr; g.v_wave = o.v ? o.v + o.out_off : nullptr; g.out_pitch = o.out_pitch;
+    VR_HIP(hipMemcpyAsync(o.seg_d, &g, sizeof(StreamSeg), hipMemcpyHostToDevice, stream));
+    const int new_frames = (int)(p.frames - prev_frames);
+    launch_stft_stream(plan, o.seg_d, new_frames, (double)o.blk_n, stream);
+    if (new_frames > 0 && (S.measure || S.running))
+        launch_stream_stats(o.seg_d, bins, new_frames, reinterpret_cast<unsigned long long*>(S.stats) + 2, stream);
+    // ---- the crops that became ready: pass 0, then pass 1, as one list in device batches of bs
+    struct Crop { int pass; long long idx; };
+    std::vector<Crop> list;
+    if (!S.measure)
+        for (int ps = 0; ps < (S.tta ? 2 : 1); ++ps)
+            for (long long i = S.crops[ps]; i < p.crops[ps]; ++i) list.push_back(Crop{ps, i});
+    if (!list.empty()) {
+        if (S.running) {
+            if (is_complex) launch_coef_complex(S.stats, 2 * bins, 0, reinterpret_cast<float2*>(S.aff), stream);
+            else launch_coef_affine(S.stats, 2 * bins, 0, S.aff, stream);
+        }
+        const int n = (int)list.size();
+        VR_CHECK(n <= 2 * (S.RM / roi), -4, "stream crop list overflow (planning bug)");
+        S.crops_h.emplace_back((size_t)n);
+        std::vector<int2>& cl = S.crops_h.back();
+        for (int k = 0; k < n; ++k) cl[k] = make_int2(0, (int)(list[k].idx * roi - offset - (list[k].pass ? roi / 2 : 0)));
+        VR_HIP(hipMemcpyAsync(o.crops_d, cl.data(), sizeof(int2) * n, hipMemcpyHostToDevice, stream));
+        fold_eval_affines();                    // before planning, as in forward_api
+        plan_and_reserve(S.bs, cropsize, 0);
+        const size_t crop_f = (size_t)nin * max_bin * cropsize;
+        auto run_crops = [&](int first, int count) {
+            ws.reset();
+            float* dense = o.gather + (size_t)(first % S.bs) * crop_f;
+            launch_stream_gather(o.seg_d, o.crops_d + first, count, is_complex, bins, max_bin, cropsize, S.aff, dense, stream);
+            Tensor x;
+            x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
+            x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
+            x.slope = 1.f;
+            Tensor f3 = run_net_window(x, offset, cropsize - offset);
+            // one head launch per run of crops that are neighbours in one mask ring
+            for (int k = 0; k < count;) {
+                const Crop c0 = list[(size_t)first + k];
+                const long long col = c0.idx * roi % S.RM;
+                int run = 1;
+                while (k + run < count && list[(size_t)first + k + run].pass == c0.pass && col + (long long)(run + 1) * roi <= S.RM) ++run;
+                Tensor part = f3;
+                part.p = f3.p + (long long)k * f3.sN; part.N = run;
+                HeadDst d{};
+                d.p = S.mask[c0.pass] + (size_t)E * col; d.dN = roi; d.dC = (long long)bins * S.RM; d.dH = S.RM;
+                d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
+                if (is_complex) launch_head_complex(part, out_w->dev, d, stream);
+                else launch_head_sigmoid(part, out_w->dev, d, stream);
+                k += run;
+            }
+        };
+        run_crop_chunks(n, S.bs, run_crops);
+    }
+    if (emit) {
+        const int segments = g.t_done - 1 - g.t_out;
+        for (int which = 0; which < 2; ++which) launch_istft_stream(plan, o.seg_d, segments, is_complex, S.tta, which, stream);
+        S.carry_cur ^= 1;
+        o.out_off += (long long)hop * segments;
+        S.done = p.done;
+    }
+    S.tail_cur ^= 1;
+    S.tail_base = g.tail_out_base;
+    S.frames = p.frames; S.crops[0] = p.crops[0]; S.crops[1] = p.crops[1];
+}
+
+void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
+                        long long capacity, long long* n_out) {
+    // ---- arguments and the schedule of this call: nothing here touches the device
+    VR_CHECK(!S.broken, -2, "this stream failed in an earlier call: close it");
+    VR_CHECK(!S.flushed, -2, flush ? "the stream is already flushed" : "push after flush");
+    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    VR_CHECK(n >= 0 && (n == 0 || wave), -2, "null or negative input");
+    const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
+    const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, flush);
+    const long long need = S.measure ? 0 : after.samples_out - before.samples_out;
+    if (need > 0)
+        VR_CHECK(y && v && capacity >= need, -2, "output capacity " + std::to_string(capacity) + " is too small: this call returns " +
+                                                     std::to_string(need) + " samples per channel");
+    if (n_out) *n_out = 0;
+    if (n == 0 && !flush) return;
+
+    DeviceGuard dev_guard(device);
+    const size_t crop_f = (size_t)nin * max_bin * S.cropsize;
+    float *stage_in = nullptr, *stage_y = nullptr, *stage_v = nullptr;
+    StreamStepIO o{};
+    auto carve = [&](Arena& A) {
+        o.seg_d = static_cast<StreamSeg*>(A.alloc(sizeof(StreamSeg)));
+        o.crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * 2 * (S.RM / S.roi)));
+        if (!S.measure) o.gather = A.allocf((size_t)S.bs * crop_f + 4096);
+        if (!on_dev && n > 0) stage_in = A.allocf((size_t)2 * n);
+        if (!out_on_dev && need > 0) { stage_y = A.allocf((size_t)2 * need + 4); stage_v = A.allocf((size_t)2 * need + 4); }
+    };
+    Arena dry_a;
+    dry_a.dry = true;
+    carve(dry_a);
+    ensure_io(dry_a.peak + 65536);
+    io.reset();
+    carve(io);
+    S.broken = true;                            // until the call has gone through: a failure half way leaves the rings undefined
+    if (stage_in) VR_HIP(hipMemcpyAsync(stage_in, wave, (size_t)2 * n * sizeof(float), hipMemcpyHostToDevice, stream));
+    const float* src = on_dev ? wave : stage_in;
+    o.y = out_on_dev ? y : stage_y; o.v = out_on_dev ? v : stage_v;
+    o.out_pitch = out_on_dev ? capacity : need;
+    o.blk_pitch = n;
+    const long long chunk = (long long)S.chunk_frames * hop;
+    for (long long at = 0; at < n;) {
+        long long take = std::min(chunk, n - at);
+        if (S.running)                          // the running normaliser of crop i covers exactly the frames below its window's end
+            take = std::min(take, ((S.crops[0] + 1) * S.roi + offset) * (long long)hop - S.samples);
+        o.blk = src + at; o.blk_n = take;
+        stream_step(S, o, false);
+        at += take;
+    }
+    if (flush) {
+        o.blk = src; o.blk_n = 0;
+        stream_step(S, o, true);
+        S.flushed = true;
+    }
+    VR_CHECK(S.measure || o.out_off == need, -4, "stream schedule mismatch (planning bug)");
+    std::vector<unsigned long long> st;
+    if (flush && S.measure) {
+        st.resize((size_t)2 * 2 * output_bin);
+        VR_HIP(hipMemcpyAsync(st.data(), reinterpret_cast<unsigned long long*>(S.stats) + 2, st.size() * 8, hipMemcpyDeviceToHost, stream));
+    }
+    if (!out_on_dev && need > 0) {
+        VR_HIP(hipMemcpy2DAsync(y, (size_t)capacity * 4, stage_y, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
+        VR_HIP(hipMemcpy2DAsync(v, (size_t)capacity * 4, stage_v, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+    S.segs_h.clear(); S.crops_h.clear();
+    if (flush && S.measure) {
+        unsigned mxb = 0;
+        unsigned long long key = ((unsigned long long)host_ord32(0.f) << 32) | host_ord32(0.f);
+        for (int r = 0; r < 2 * output_bin; ++r) {
+            mxb = std::max(mxb, (unsigned)st[2 * r]);           // non-negative floats order like their bit patterns
+            key = std::max(key, st[2 * r + 1]);
+        }
+        if (S.tta) {
+            S.coef[0] = host_unord32((unsigned)(key >> 32)); S.coef[1] = host_unord32((unsigned)(key & 0xffffffffu));
+        } else {
+            float m;
+            memcpy(&m, &mxb, 4);
+            S.coef[0] = m; S.coef[1] = 0.0;
+        }
+    }
+    S.broken = false;
+    if (n_out) *n_out = need;
+}
+
+// =====================================================================================================
 // unit-test hook: one conv through the MFMA kernel with a single dense source
 // =====================================================================================================
 void Model::debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,

@@ -26,6 +26,16 @@ namespace vr {
 // and then runs the same code.  `mask_a` is then the call's concatenated mask (row pitch Wa), `mask_b` the same pointer when the TTA
 // pass is to be averaged in (else null), `wgt` the weights of all songs; the arguments an entry replaces are passed as 0.
 template <class SRC> constexpr bool kSongTable = std::is_same<SRC, const SongSeg>::value;
+// SRC = const StreamSeg (vr_stream_*): `src` points at the one StreamSeg of the stream's current step.  Frames and samples are addressed
+// by their absolute index in the stream and live in rings (kernels.h); each kernel handles only what the step added.
+template <class SRC> constexpr bool kStream = std::is_same<SRC, const StreamSeg>::value;
+template <class SRC> using StreamLocal = typename std::conditional<kStream<SRC>, StreamSeg, int>::type;
+
+// sample p of channel ch of a stream: the tail kept from earlier steps, then the step's block; zero outside [0, L)
+__device__ __forceinline__ float stream_sample(const StreamSeg& sg, int ch, long long p) {
+    if (p < 0 || p >= sg.L) return 0.f;
+    return p < sg.blk_base ? sg.tail[(long long)ch * sg.tail_pitch + (p - sg.tail_base)] : sg.blk[(long long)ch * sg.blk_pitch + (p - sg.blk_base)];
+}
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -124,9 +134,15 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
     float2* zs = lds2 + (size_t)g * M;       // this group's FFT buffer
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
-    const int t0 = blockIdx.x * F, ch = blockIdx.y;
+    int t0 = blockIdx.x * F;
+    const int ch = blockIdx.y;
     const float* wv;
-    if constexpr (kSongTable<SRC>) {                 // blockIdx.z = song; the grid is sized for the longest one
+    StreamLocal<SRC> ss{};
+    if constexpr (kStream<SRC>) {                    // the frames [t_new, T) of the stream, written into the ring
+        ss = wave[0];
+        t0 += ss.t_new; T = ss.T;
+        wv = nullptr;
+    } else if constexpr (kSongTable<SRC>) {          // blockIdx.z = song; the grid is sized for the longest one
         const SongSeg sg = wave[blockIdx.z];
         if (t0 >= sg.T) return;
         L = sg.L; T = sg.T; spec = sg.spec;
@@ -142,8 +158,14 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
             const long long start = (long long)(t0 + f) * hop - M;      // centre = True: n_fft/2 zeros in front
             for (int m = tid; m < M; m += 256) {
                 const long long p = start + 2 * m;
-                const float v0 = (p >= 0 && p < L) ? wv[p] * pl.window[2 * m] : 0.f;
-                const float v1 = (p + 1 >= 0 && p + 1 < L) ? wv[p + 1] * pl.window[2 * m + 1] : 0.f;
+                float v0, v1;
+                if constexpr (kStream<SRC>) {
+                    v0 = stream_sample(ss, ch, p) * pl.window[2 * m];
+                    v1 = stream_sample(ss, ch, p + 1) * pl.window[2 * m + 1];
+                } else {
+                    v0 = (p >= 0 && p < L) ? wv[p] * pl.window[2 * m] : 0.f;
+                    v1 = (p + 1 >= 0 && p + 1 < L) ? wv[p + 1] * pl.window[2 * m + 1] : 0.f;
+                }
                 zs[__brev((unsigned)m) >> (32 - logM)] = make_float2(v0, v1);
             }
         }
@@ -162,7 +184,18 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     }
     for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
         const int k = idx / F, f = idx - k * F;
-        if (f < nf) spec[((long long)ch * bins + k) * T + t0 + f] = tile[idx];
+        if constexpr (kStream<SRC>) {
+            if (f < nf) ss.ring[((long long)ch * bins + k) * ss.R + (t0 + f) % ss.R] = tile[idx];
+        } else {
+            if (f < nf) spec[((long long)ch * bins + k) * T + t0 + f] = tile[idx];
+        }
+    }
+    if constexpr (kStream<SRC>) {                    // the samples the next step's first frames reach back to
+        if (blockIdx.x == 0) {
+            const int keep = (int)(ss.L - ss.tail_out_base);
+            for (int i = threadIdx.x; i < keep; i += 1024)
+                ss.tail_out[(long long)ch * ss.tail_pitch + i] = stream_sample(ss, ch, ss.tail_out_base + i);
+        }
     }
 }
 
@@ -195,9 +228,18 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     float2* zs = lds2 + (size_t)g * M;                              // this group's FFT buffer = its time-domain frame afterwards
     float2* tile = lds2 + (size_t)TG * M;                           // [bins][F]
     float* prev = reinterpret_cast<float*>(tile + (size_t)bins * F);   // [M] windowed second half of the last frame of the previous round
-    const int t0 = blockIdx.x * S, ch = blockIdx.y;
+    int t0 = blockIdx.x * S;
+    const int ch = blockIdx.y;
     const float2* __restrict__ spec;
-    if constexpr (kSongTable<SRC>) {                 // blockIdx.z = song; writes that song's y_wave (which 0) or v_wave (which 1)
+    StreamLocal<SRC> ss{};
+    bool carried = false;                            // (stream) frame t0 of this workgroup comes from the carry, not from the ring
+    if constexpr (kStream<SRC>) {                    // the frames [t_out, t_done) of the stream, spectrogram and masks from their rings
+        ss = src[0];
+        t0 += ss.t_out; T = ss.t_done;
+        spec = ss.ring; ma = ss.mask_a; mb = ss.mask_b; shift = ss.shift;
+        wave = which ? ss.v_wave : ss.y_wave;
+        carried = ss.carried && blockIdx.x == 0;
+    } else if constexpr (kSongTable<SRC>) {          // blockIdx.z = song; writes that song's y_wave (which 0) or v_wave (which 1)
         const SongSeg sg = src[blockIdx.z];
         if (t0 >= sg.T - 1) return;
         spec = sg.spec; T = sg.T;
@@ -213,7 +255,28 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
         const int k = idx / F, f = idx - k * F;
         float2 v = make_float2(0.f, 0.f);
-        if (f < nf) {
+        if constexpr (kStream<SRC>) {
+            if (f < nf && !(carried && f == 0)) {
+                const long long row = (long long)ch * bins + k;
+                const int t = t0 + f;
+                v = spec[row * ss.R + t % ss.R];
+                const long long ca = row * ss.RM + t % ss.RM, cb = row * ss.RM + (t + shift) % ss.RM;
+                if constexpr (CPLX) {
+                    float2 m = reinterpret_cast<const float2*>(ma)[ca];
+                    if (mb) {
+                        const float2 b = reinterpret_cast<const float2*>(mb)[cb];
+                        m = make_float2((m.x + b.x) * 0.5f, (m.y + b.y) * 0.5f);
+                    }
+                    const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
+                    v = cmul(gm, v);
+                } else {
+                    float m = ma[ca];
+                    if (mb) m = (m + mb[cb]) * 0.5f;
+                    const float gm = which ? 1.f - m : m;
+                    v = make_float2(gm * v.x, gm * v.y);
+                }
+            }
+        } else if (f < nf) {
             const long long row = (long long)ch * bins + k;
             const int t = t0 + f;
             v = spec[row * T + t];
@@ -255,9 +318,19 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
         fft_lds_sub(zs, pl.twiddle, M, logM, 1, tid, 256);
         // in place: zs[m] = (x[2m], x[2m+1]) windowed -> the group's buffer is the windowed frame, as floats [n_fft]
         if (live) {
-            for (int m = tid; m < M; m += 256) {
-                const float2 r = zs[m];
-                zs[m] = make_float2(r.x * invM * pl.window[2 * m], -r.y * invM * pl.window[2 * m + 1]);
+            bool from_carry = false;
+            if constexpr (kStream<SRC>) from_carry = carried && f == 0;
+            if (from_carry) {                        // only the windowed second half of that frame is used: floats [M, 2M) of the buffer
+                if constexpr (kStream<SRC>) {
+                    const float* cin = ss.carry_in + (long long)(which * 2 + ch) * M;
+                    for (int m = tid; m < M; m += 256)
+                        zs[m] = 2 * m >= M ? make_float2(cin[2 * m - M], cin[2 * m + 1 - M]) : make_float2(0.f, 0.f);
+                }
+            } else {
+                for (int m = tid; m < M; m += 256) {
+                    const float2 r = zs[m];
+                    zs[m] = make_float2(r.x * invM * pl.window[2 * m], -r.y * invM * pl.window[2 * m + 1]);
+                }
             }
         }
         __syncthreads();
@@ -270,8 +343,12 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                 const float w0 = pl.window[i], w2 = pl.window[i + M];
                 const float ws = fmaf(w0, w0, w2 * w2);
                 const float a = before[i] + cur[i];
-                const long long p = (long long)s * M + i;
-                if (p < out_len) wave[(long long)ch * out_len + p] = ws > FLT_MIN ? a / ws : a;
+                if constexpr (kStream<SRC>) {
+                    wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
+                } else {
+                    const long long p = (long long)s * M + i;
+                    if (p < out_len) wave[(long long)ch * out_len + p] = ws > FLT_MIN ? a / ws : a;
+                }
             }
         }
         __syncthreads();
@@ -284,6 +361,12 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
             }
         }
         __syncthreads();
+    }
+    if constexpr (kStream<SRC>) {                    // the workgroup that ends the step hands its last half frame to the next step
+        if (t0 + nf == ss.t_done) {
+            float* cout = ss.carry_out + (long long)(which * 2 + ch) * M;
+            for (int i = threadIdx.x; i < M; i += 1024) cout[i] = prev[i];
+        }
     }
 }
 
@@ -440,14 +523,18 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
         const int max_bin = Wpad, cropsize = T;
         const int c = blockIdx.x / max_bin, k = blockIdx.x - c * max_bin, n = blockIdx.y;
         const int2 cr = reinterpret_cast<const int2*>(part)[n];
-        const SongSeg sg = spec[cr.x];
-        const float2* sp = sg.spec + ((long long)c * bins + k) * sg.T;
+        const auto sg = spec[cr.x];                                 // (a stream has one entry: its crops name entry 0)
+        const float2* sp;
+        if constexpr (kStream<SRC>) sp = sg.ring + ((long long)c * bins + k) * sg.R;
+        else sp = sg.spec + ((long long)c * bins + k) * sg.T;
         float* d0 = mag_pad + (((long long)n * (PACK ? 4 : 2) + c) * max_bin + k) * cropsize;
         float* d1 = d0 + 2LL * max_bin * cropsize;                  // (PACK: the imaginary plane)
         const float2 s = scale[2 * cr.x];
         for (int col = threadIdx.x; col < cropsize; col += 256) {
             const int t = cr.y + col;
-            const float2 z = (t >= 0 && t < sg.T) ? sp[t] : make_float2(0.f, 0.f);
+            float2 z;
+            if constexpr (kStream<SRC>) z = (t >= 0 && t < sg.T) ? sp[t % sg.R] : make_float2(0.f, 0.f);
+            else z = (t >= 0 && t < sg.T) ? sp[t] : make_float2(0.f, 0.f);
             if constexpr (PACK) {
                 const float2 q = cmul(z, s);
                 d0[col] = q.x;
@@ -476,7 +563,12 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
     int row = blockIdx.x;
     const float2* sp;
     float* dst = nullptr;
-    if constexpr (kSongTable<SRC>) {
+    int t_first = 0, ring = 0;                       // (stream) the new frames [t_new, T) at column t % R; the maxima join part[row]
+    if constexpr (kStream<SRC>) {
+        const StreamSeg sg = spec[0];
+        T = sg.T; t_first = sg.t_new; ring = sg.R;
+        sp = sg.ring + (long long)row * ring;
+    } else if constexpr (kSongTable<SRC>) {
         const SongSeg sg = spec[blockIdx.y];
         T = sg.T;
         sp = sg.spec + (long long)row * T;
@@ -487,10 +579,12 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
     }
     float mx = 0.f;
     unsigned long long key = ((unsigned long long)ord32(0.f) << 32) | ord32(0.f);   // the zero padding is part of the reduced array
-    for (int t = threadIdx.x; t < T; t += 256) {
-        const float2 z = sp[t];
+    for (int t = t_first + threadIdx.x; t < T; t += 256) {
+        float2 z;
+        if constexpr (kStream<SRC>) z = sp[t % ring];
+        else z = sp[t];
         const float m = sqrtf(z.x * z.x + z.y * z.y);
-        if constexpr (!kSongTable<SRC>) dst[t] = m;
+        if constexpr (!kSongTable<SRC> && !kStream<SRC>) dst[t] = m;
         mx = fmaxf(mx, m);
         const unsigned long long k = ((unsigned long long)ord32(z.x) << 32) | ord32(z.y);
         key = k > key ? k : key;
@@ -507,6 +601,10 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < 4; ++i) { mx = fmaxf(mx, rmx[i]); key = rkey[i] > key ? rkey[i] : key; }
+        if constexpr (kStream<SRC>) {
+            mx = fmaxf(mx, __uint_as_float((unsigned)part[2 * row]));
+            key = part[2 * row + 1] > key ? part[2 * row + 1] : key;
+        }
         part[2 * row] = (unsigned long long)__float_as_uint(mx);
         part[2 * row + 1] = key;
     }
@@ -776,6 +874,61 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
         static std::atomic<unsigned long long> attr_done{0};
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg>), 160 * 1024);
         VR_LAUNCH((istft_tile_kernel<false, const SongSeg>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+    }
+    VR_HIP(hipGetLastError());
+}
+
+// ---- streaming separation (vr_stream_*): the STREAM instantiations -----------------------------------------------------------------
+// Every launch covers what one step of the stream added: new frames, newly ready crops, newly final output segments.
+bool stream_tiled_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
+
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int new_frames, double new_samples, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const StreamSeg>), 160 * 1024);
+    prof_note(0.0, 2.0 * (4.0 * new_samples + 8.0 * (double)bins * new_frames));
+    // (a step without a new frame still launches one workgroup per channel: it moves the input tail on)
+    const int blocks = new_frames > 0 ? (new_frames + F - 1) / F : 1;
+    VR_LAUNCH((stft_tile_kernel<const StreamSeg>), dim3((unsigned)blocks, 2), dim3(1024), lds, st, pl, seg, 0LL, 0, F, nullptr);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stream_stats(const StreamSeg* seg, int bins, int new_frames, unsigned long long* part, hipStream_t st) {
+    prof_note(0.0, 2.0 * (double)bins * 8.0 * new_frames);
+    VR_LAUNCH((mag_pad_kernel<false, const StreamSeg>), dim3(2 * bins), dim3(256), 0, st, seg, 0, nullptr, 0, 0, part, bins, nullptr);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
+                          float* dst, hipStream_t st) {
+    prof_note(0.0, (double)count * 2 * max_bin * cropsize * (8.0 + (cplx ? 8.0 : 4.0)));
+    unsigned long long* list = reinterpret_cast<unsigned long long*>(const_cast<int2*>(crops));
+    const float2* inv = reinterpret_cast<const float2*>(aff);
+    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, inv);
+    else VR_LAUNCH((mag_pad_kernel<false, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, inv);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int segments, bool cplx, bool tta, int which, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    if (segments < 1) return;
+    const int F = tile_frames(pl, M);
+    const int S = F - 1;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
+    const dim3 grid((unsigned)((segments + S - 1) / S), 2);
+    prof_note(0.0, 2.0 * ((double)bins * segments * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * segments));
+    if (cplx) {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const StreamSeg>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<true, const StreamSeg>), grid, dim3(1024), lds, st, pl, seg, 0, S, nullptr, 0, nullptr, 0, 0, nullptr, which, nullptr, 0LL);
+    } else {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const StreamSeg>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<false, const StreamSeg>), grid, dim3(1024), lds, st, pl, seg, 0, S, nullptr, 0, nullptr, 0, 0, nullptr, which, nullptr, 0LL);
     }
     VR_HIP(hipGetLastError());
 }

@@ -133,6 +133,145 @@ class Separator(object):
                                                         int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0))
         return list(zip(ys, vs))
 
+    def stream(self, coef=None, tta=False):
+        """A streaming session on this model: see Stream.  coef: the normaliser of the whole input (measure_coef); None (plain only)
+        = a running normaliser over the audio received so far, which is NOT the offline result."""
+        return Stream(self, coef, tta)
+
+    def measure_coef(self, blocks, tta=False):
+        """The normaliser separate_wave(tta=tta) would use for the concatenation of `blocks` (an iterable of waves [2, n]), without
+        running the network or holding the input."""
+        with Stream(self, None, tta, measure=True) as s:
+            for b in blocks:
+                s.push(b)
+            s.flush()
+            return s.coef()
+
+
+class Stream(object):
+    """One streaming session (vr_stream_*): push(wave [2, n]) -> (y, v) [2, n_out] with every sample that has become final (n_out may be
+    0), flush() -> the rest; the concatenation is what separate_wave returns for the whole input when `coef` is that call's normaliser
+    (Separator.measure_coef).  numpy in, numpy out; a torch cuda tensor in, cuda tensors out.  Use as a context manager or close()."""
+
+    def __init__(self, sep, coef, tta, measure=False):
+        m = sep.model
+        self._handle = m._need_handle()
+        self._geom = (m.n_fft, m.hop_length, int(sep.cropsize), m.offset, bool(tta))
+        self.measure = measure
+        m.eval()
+        flags = (native.VR_STREAM_TTA if tta else 0) | (native.VR_STREAM_MEASURE if measure else 0)
+        flags |= native.VR_STREAM_POSTPROCESS if sep.postprocess else 0          # (the library refuses it with its reason)
+        c = complex(coef) if coef is not None else 0j
+        self._s = native.ctypes.c_void_p()
+        native.check(native.lib().vr_stream_open(self._handle.h, int(sep.cropsize), int(sep.batchsize), flags, c.real, c.imag,
+                                                 native.ctypes.byref(self._s)))
+        self._samples = 0
+        info = [native.ctypes.c_int64() for _ in range(3)]
+        native.check(native.lib().vr_stream_info(self._s, *[native.ctypes.byref(i) for i in info]))
+        self.lookahead_samples, self.block_samples, self.state_bytes = [int(i.value) for i in info]
+
+    def _need(self, n, flushed):
+        before = native.stream_plan(*self._geom, self._samples, False)[2]
+        return 0 if self.measure else native.stream_plan(*self._geom, self._samples + n, flushed)[2] - before
+
+    def _call(self, wave, flush):
+        if not self._s.value:
+            raise native.VRError('stream is closed')
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        got = native.ctypes.c_int64()
+        on_dev = torch is not None and wave is not None and torch.is_tensor(wave) and wave.is_cuda
+        if flush:
+            on_dev, n = self._dev_out, 0
+        elif on_dev:
+            wave = wave.detach().to(torch.float32).contiguous()
+            n = int(wave.shape[1])
+        else:
+            if torch is not None and torch.is_tensor(wave):
+                wave = wave.detach().cpu().numpy()
+            wave = np.ascontiguousarray(np.asarray(wave, dtype=np.float32))
+            n = int(wave.shape[1])
+        if not flush and (wave.ndim != 2 or wave.shape[0] != 2):
+            raise ValueError('wave must be [2, n]')
+        self._dev_out = on_dev
+        need = self._need(n, flush)              # (a flush below one hop of input raises here, with separate_wave's message)
+        cap = max(need, 1)
+        if on_dev:
+            dev = wave.device if not flush else self._device
+            self._device = dev
+            y = torch.empty((2, cap), dtype=torch.float32, device=dev)
+            v = torch.empty_like(y)
+            torch.cuda.current_stream(dev).synchronize()
+            yp, vp, wp = y.data_ptr(), v.data_ptr(), (wave.data_ptr() if not flush and n else None)
+        else:
+            y = np.empty((2, cap), dtype=np.float32)
+            v = np.empty_like(y)
+            yp, vp, wp = native.np_ptr(y), native.np_ptr(v), (native.np_ptr(wave) if not flush and n else None)
+        if flush:
+            native.check(native.lib().vr_stream_flush(self._s, yp, vp, 1 if on_dev else 0, cap, native.ctypes.byref(got)))
+        else:
+            native.check(native.lib().vr_stream_push(self._s, wp, 1 if on_dev else 0, n, yp, vp, 1 if on_dev else 0, cap,
+                                                     native.ctypes.byref(got)))
+        self._samples += n
+        return y[:, :int(got.value)], v[:, :int(got.value)]
+
+    _dev_out, _device = False, None
+
+    def push(self, wave):
+        return self._call(wave, False)
+
+    def flush(self):
+        return self._call(None, True)
+
+    def coef(self):
+        """After the flush of a measuring stream: max|X| (plain) or numpy's lexicographic complex maximum (tta) of the whole input."""
+        c = (native.ctypes.c_double * 2)()
+        native.check(native.lib().vr_stream_coef(self._s, c))
+        return complex(c[0], c[1]) if self._geom[4] else float(c[0])
+
+    def close(self):
+        if getattr(self, '_s', None) is not None and self._s.value:
+            native.lib().vr_stream_close(self._s)
+            self._s = native.ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self._handle._h.value:        # (the handle may already be gone at interpreter exit: its memory went with it)
+                self.close()
+        except Exception:
+            pass
+
+
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
+    """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
+    written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed."""
+    from . import audio
+    rd = audio.WavBlockReader(path)
+    if rd.sr != sr:
+        raise ValueError('%s has sample rate %d, not --sr %d: the resampler is not streamed, run without --stream' % (path, rd.sr, sr))
+    n = max(1, int(round(block_seconds * sr)))
+
+    def blocks():
+        for b in rd.blocks(n):
+            yield np.ascontiguousarray(np.vstack([b, b]) if b.shape[0] == 1 else b[:2])      # mono to stereo (inference.py:143-145)
+    coef = sp.measure_coef(blocks(), tta=tta)
+    with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, sp.stream(coef=coef, tta=tta) as s:
+        for b in blocks():
+            y, v = s.push(b)
+            wy.append(y.T)
+            wv.append(v.T)
+        y, v = s.flush()
+        wy.append(y.T)
+        wv.append(v.T)
+
 
 def expand_inputs(path, songs_per_call):
     """--input: a file is one group of one song; a directory is every .wav in it, sorted by name, in groups of songs_per_call."""
@@ -171,6 +310,8 @@ def main(argv=None):
     p.add_argument('--output_image', '-I', action='store_true')      # accepted for command-line compatibility; no image is written
     p.add_argument('--output_dir', '-o', type=str, default="")
     p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call
+    p.add_argument('--stream', action='store_true')                  # read, separate and write block by block (Separator.stream)
+    p.add_argument('--block_seconds', type=float, default=1.0)
     args = p.parse_args(argv)
 
     if args.output_image:
@@ -197,6 +338,13 @@ def main(argv=None):
         audio.write('{}{}_Instruments.wav'.format(output_dir, basename), y_wave.T, sr)
         audio.write('{}{}_Vocals.wav'.format(output_dir, basename), v_wave.T, sr)
 
+    if args.stream:
+        if os.path.isdir(args.input):
+            raise SystemExit('--stream takes one file')
+        basename = os.path.splitext(os.path.basename(args.input))[0]
+        stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
+                    args.sr, tta=args.tta, block_seconds=args.block_seconds)
+        return 0
     if not os.path.isdir(args.input):
         X, sr = load(args.input)
         y_wave, v_wave = sp.separate_wave(X, tta=args.tta)  # STFT -> separate -> iSTFT x2 in one device-resident call

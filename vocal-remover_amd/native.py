@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('VR_LIB_PATH') or os.path.join(_HERE, 'libvr_mi355.so'
 
 c_f32p = ctypes.c_void_p
 VR_CREATE_COMPLEX = 1         # include/vr_mi355.h
+VR_STREAM_TTA, VR_STREAM_MEASURE, VR_STREAM_POSTPROCESS = 1, 2, 4
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 
 _SIGNATURES = {
@@ -39,6 +40,16 @@ _SIGNATURES = {
     'vr_separate_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_stream_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                      ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_stream_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int,
+                                      ctypes.c_int64, c_i64p]),
+    'vr_stream_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_stream_coef': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    'vr_stream_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i64p]),
+    'vr_stream_close': (ctypes.c_int, [ctypes.c_void_p]),
+    'vr_stream_plan': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_int64, ctypes.c_int, c_i64p, c_i64p, c_i64p]),
+    'vr_arena_bytes': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p]),
     'vr_train_step': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.POINTER(ctypes.c_float), c_f32p, ctypes.c_int]),
     'vr_forward_train': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int]),
@@ -148,6 +159,15 @@ def np_ptr(a):
 def ptr_table(addresses):
     """A host table of data pointers (vr_separate_many / vr_separate_wave_many) from integer addresses."""
     return (ctypes.c_void_p * len(addresses))(*[int(a) for a in addresses])
+
+
+def stream_plan(n_fft, hop, cropsize, offset, tta, samples_in, flushed):
+    """vr_stream_plan (host only): -> (frames_ready, (crops_ready pass 0, pass 1), samples_out)."""
+    fr, out = ctypes.c_int64(), ctypes.c_int64()
+    crops = (ctypes.c_int64 * 2)()
+    check(lib().vr_stream_plan(int(n_fft), int(hop), int(cropsize), int(offset), 1 if tta else 0, int(samples_in), 1 if flushed else 0,
+                               ctypes.byref(fr), crops, ctypes.byref(out)))
+    return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
 
 
 class Handle:
