@@ -324,8 +324,9 @@ int vr_debug_conv2d_backward(vr_handle h, const float* x, int N, int Cin, int H,
  * weight [T] (lib/spec_utils.py:64-87), incl. the reference's IndexError / ValueError cases.        */
 int vr_debug_merge_artifacts_weight(const float* frame_min, int T, float thres, int min_range, int fade_size,
                                     float* weight_out);
-/* One kernel of the training path in isolation, host pointers in and out (csrc/debug.hip lists the names, their
- * dims / float parameters / inputs / outputs): bn_backward, lstm, upsample, pool, thin, head_loss, rows, adam.      */
+/* One kernel of the training path or of the signal front end in isolation, host pointers in and out (csrc/debug.hip lists
+ * the names, their dims / float parameters / inputs / outputs): bn_backward, lstm, upsample, pool, thin, head_loss, rows,
+ * adam, wire, signal_norm, signal_mask.                                                                             */
 int vr_debug_kernel(vr_handle h, const char* name, const int64_t* dims, int ndims, const float* fparams, int nfparams,
                     const float* const* inputs, int ninputs, float* const* outputs, int noutputs);
 /* Record intermediate activations of the next vr_forward and read them back (post-activation). */

@@ -127,8 +127,11 @@ def test_every_kernel_of_the_library_is_reached_by_a_documented_shape_or_option(
         try:
             trb = vtrain.Trainer(small, lr=1e-3, backend='rccl', wire='bf16', world_size=1, rank=0)
             col.run('Trainer(backend=rccl, wire=bf16).step at world 1', h, lambda: trb.step(X.to('cuda:0'), y.to('cuda:0')))
-        except Exception as e:                           # no RCCL on the box: the wire kernels stay on the allow-list below
+        except Exception as e:                           # no RCCL on the box: the wire kernels run through their hook below
             print('Trainer(backend=rccl) unavailable: %r' % (e,))
+        # the bf16 wire conversion on its own (debug.hip 'wire'; values: tests/test_gpu_signal.py)
+        wx, wy = np.linspace(-3, 3, 1000, dtype=np.float32), np.empty(1000, np.float32)
+        col.run('vr_debug_kernel wire', h, lambda: nat.debug_kernel(h, 'wire', [1000], [], [wx], [wy]))
         # Separator: STFT -> crops -> mask -> stitch -> iSTFT, plain / tta / postprocess
         rng = np.random.default_rng(0)
         wave = (0.1 * rng.standard_normal((2, 256 * 300))).astype(np.float32)
@@ -185,7 +188,7 @@ def test_every_kernel_of_the_library_is_reached_by_a_documented_shape_or_option(
     for n in ('bilstm_kernel', 'bilstm_bwd_kernel', 'upsample2x_kernel', 'upsample_bwd_kernel', 'materialize_kernel', 'bn_bwd_apply_kernel',
               'wgrad_wino_kernel', 'conv_mfma_kernel', 'conv_ws_kernel', 'stft_kernel', 'istft_frame_kernel', 'istft_ola_kernel', 'adam_kernel'):
         assert n in col.seen, (n, missing)
-    # vr_augment_batch: tests/test_golden.py; rows form of the upsample: widths % 4 == 2 only; wire conversion: needs RCCL (test_gpu_dp.py)
+    # vr_augment_batch: tests/test_golden.py; rows form of the upsample: widths % 4 == 2 only
     # head_bwd (backward from dLoss / dmask) runs on torch's autograd thread, outside this thread's profiler: tests/test_gpu_frontend.py
-    allowed = {'augment_kernel', 'upsample2x_rows_kernel', 'f32_to_bf16_kernel', 'bf16_to_f32_kernel', 'head_bwd_kernel'}
+    allowed = {'augment_kernel', 'upsample2x_rows_kernel', 'head_bwd_kernel'}
     assert not [n for n in missing if n not in allowed], missing

@@ -1,5 +1,7 @@
 // Test hooks (tests/ only): single kernels of the training path behind vr_debug_kernel, host pointers in and out,
-// so that every backward kernel has an isolated parity test against torch autograd (tests/test_gpu_kernels.py).
+// so that every backward kernel has an isolated parity test against torch autograd (tests/test_gpu_kernels.py), and the
+// spectrogram-side glue of stft.hip against float64 numpy (tests/test_gpu_signal.py).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -52,6 +54,17 @@ Tensor dense(float* p, int N, int C, int H, int W) {
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
 // rows            N,R,W                 -                x[N,R,W], aff[R][2], d[N,R,W]                       relu(x*a+b), channel sums of d [R]
 // adam            n                     lr,b1,b2,eps,gscale,step   p, g, m, v                                p, m, v
+// wire            n                     -                x[n]                                                bf16_to_f32(f32_to_bf16(x)) [n]
+// signal_norm     bins,T,Wpad,pad_l,mode,cplx   -        spec[2][bins][T] complex64                          mag_pad[2][bins][Wpad] (cplx: the packed planes
+//                                                                                                            [4][bins][Wpad] of X / c), aff[4] (cplx: 1 / c in
+//                                                                                                            aff[0..1]), sel[4] = the stats header as words:
+//                                                                                                            max |X| bits, 0, key imag, key real (ord32 keys)
+//                 mag_pad + coef_affine (cplx: mag_pad + coef_complex + pack_complex) as Model::separate runs them; mode 0 = max |X|,
+//                 1 = numpy's lexicographic complex maximum of the zero-padded array
+// signal_mask     T,Wa,Wb,shift,has_b,has_wgt,cplx   -   spec[2][bins][T] complex64, mask_a[2 bins][Wa],     fmin[T], y, v [2][bins][T] complex64,
+//                                                        mask_b[2 bins][Wb]|null, wgt[T]|null                y_wave, v_wave [2][hop (T-1)] (fused masked
+//                                                        (cplx: complex64 masks)                             iSTFT; hop == n_fft / 2 handles only)
+//                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
 void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims, const float* fp, int nfp,
                          const float* const* in, int nin, float* const* out, int nout) {
     DeviceGuard dev_guard(device);
@@ -187,6 +200,67 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         launch_adam(p.p, g.p, m.p, v.p, (long long)n, dp[0], dp[1], dp[2], dp[3], (long long)dp[5], dp[4], st);
         VR_HIP(hipStreamSynchronize(st));
         p.download(out[0]); m.download(out[1]); v.download(out[2]);
+    } else if (name == "wire") {
+        need(1, 0, 1, 1);
+        const size_t n = (size_t)dims[0];
+        DevBuf x(in[0], n), half((n + 1) / 2), y(n);
+        launch_f32_to_bf16(x.p, reinterpret_cast<unsigned short*>(half.p), (long long)n, st);
+        launch_bf16_to_f32(reinterpret_cast<const unsigned short*>(half.p), y.p, (long long)n, st);
+        VR_HIP(hipStreamSynchronize(st));
+        y.download(out[0]);
+    } else if (name == "signal_norm") {
+        need(6, 0, 1, 2);
+        const int bins = (int)dims[0], T = (int)dims[1], Wpad = (int)dims[2], pad_l = (int)dims[3], mode = (int)dims[4];
+        const bool cplx = dims[5] != 0;
+        VR_CHECK(bins > 0 && T > 0 && pad_l >= 0 && Wpad >= pad_l + T, -2, "signal_norm: need bins, T > 0 and Wpad >= pad_l + T");
+        const size_t nmag = (size_t)(cplx ? 4 : 2) * bins * Wpad;
+        // the magnitude path zeroes its crop source first; the complex pack writes every column itself, so it starts from NaN here
+        std::vector<float> fill(nmag, cplx ? std::nanf("") : 0.f);
+        DevBuf spec(in[0], (size_t)2 * bins * T * 2), mag(fill.data(), nmag), stats(4 + (size_t)2 * bins * 4), aff(4);
+        unsigned* sp = reinterpret_cast<unsigned*>(stats.p);
+        launch_mag_pad(reinterpret_cast<const float2*>(spec.p), bins, T, mag.p, Wpad, pad_l, sp, st);
+        if (cplx) {
+            launch_coef_complex(sp, 2 * bins, mode, reinterpret_cast<float2*>(aff.p), st);
+            launch_pack_complex(reinterpret_cast<const float2*>(spec.p), 1, bins, T, mag.p, Wpad, pad_l, reinterpret_cast<const float2*>(aff.p), st);
+        } else {
+            launch_coef_affine(sp, 2 * bins, mode, aff.p, st);
+        }
+        VR_HIP(hipStreamSynchronize(st));
+        mag.download(out[0]); aff.download(out[1]);
+        if (nout >= 3 && out[2]) VR_HIP(hipMemcpy(out[2], stats.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
+    } else if (name == "signal_mask") {
+        need(7, 0, 4, 3);
+        const int T = (int)dims[0], Wa = (int)dims[1], Wb = (int)dims[2], shift = (int)dims[3];
+        const bool has_b = dims[4] != 0, has_wgt = dims[5] != 0, cplx = dims[6] != 0;
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(T > 0 && Wa >= T && (!has_b || (shift >= 0 && Wb >= T + shift)), -2, "signal_mask: the masks must cover T (+ shift) frames");
+        VR_CHECK(in[0] && in[1] && (!has_b || in[2]) && (!has_wgt || in[3]), -2, "signal_mask: missing input");
+        const size_t rows = (size_t)2 * bins, mc = cplx ? 2 : 1, nspec = rows * T * 2, nwave = (size_t)2 * hop * (T - 1);
+        DevBuf spec(in[0], nspec), ma(in[1], rows * Wa * mc), mb(has_b ? in[2] : nullptr, has_b ? rows * Wb * mc : 0);
+        DevBuf wgt(has_wgt ? in[3] : nullptr, has_wgt ? (size_t)T : 0);
+        DevBuf fmin((size_t)T), y(nspec), v(nspec), yw(nwave), vw(nwave);
+        const float2* sd = reinterpret_cast<const float2*>(spec.p);
+        const float* mbp = has_b ? mb.p : nullptr;
+        const float* wp = has_wgt ? wgt.p : nullptr;
+        const bool waves = nout >= 5 && out[3] && out[4];
+        VR_CHECK(!waves || istft_masked_available(plan, hop), -2, "signal_mask: the fused masked iSTFT needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        if (cplx) {
+            const float2 *a2 = reinterpret_cast<const float2*>(ma.p), *b2 = reinterpret_cast<const float2*>(mbp);
+            launch_frame_min_complex(bins, T, a2, Wa, b2, Wb, shift, fmin.p, st);
+            launch_apply_mask_complex(sd, bins, T, a2, Wa, b2, Wb, shift, wp, reinterpret_cast<float2*>(y.p), reinterpret_cast<float2*>(v.p), st);
+            if (waves)
+                for (int which = 0; which < 2; ++which)
+                    launch_istft_masked_complex(plan, sd, hop, T, a2, Wa, b2, Wb, shift, wp, which, which ? vw.p : yw.p, st);
+        } else {
+            launch_frame_min(bins, T, ma.p, Wa, mbp, Wb, shift, fmin.p, st);
+            launch_apply_mask(sd, bins, T, ma.p, Wa, mbp, Wb, shift, wp, reinterpret_cast<float2*>(y.p), reinterpret_cast<float2*>(v.p), st);
+            if (waves)
+                for (int which = 0; which < 2; ++which)
+                    launch_istft_masked(plan, sd, hop, T, ma.p, Wa, mbp, Wb, shift, wp, which, which ? vw.p : yw.p, st);
+        }
+        VR_HIP(hipStreamSynchronize(st));
+        fmin.download(out[0]); y.download(out[1]); v.download(out[2]);
+        if (waves) { yw.download(out[3]); vw.download(out[4]); }
     } else {
         throw Error(-2, "vr_debug_kernel: unknown kernel name: " + name);
     }

@@ -163,9 +163,9 @@ void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, 
 void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpad, int pad_l,
                     unsigned* stats, hipStream_t st);
 // aff[0..3] = (1/coef, 0, 1/coef, 0), coef = max|X| (mode 0) or |lexicographic max| (mode 1)
-void launch_coef_affine(const unsigned* stats, int rows, int mode, float* aff, hipStream_t st);   // rows = 2 * bins partials
+void launch_coef_affine(unsigned* stats, int rows, int mode, float* aff, hipStream_t st);   // rows = 2 * bins partials
 // complex handle: 1/c as a complex number, c = max|X| (mode 0) or the lexicographic complex max itself (mode 1)
-void launch_coef_complex(const unsigned* stats, int rows, int mode, float2* inv, hipStream_t st);
+void launch_coef_complex(unsigned* stats, int rows, int mode, float2* inv, hipStream_t st);
 // spec [N][2][bins][T] complex64 -> dst [N][4][bins][Wdst] planar (re ch0, re ch1, im ch0, im ch1), frame t at column pad_l + t,
 // every other column zero; times *scale (complex, may be null)
 void launch_pack_complex(const float2* spec, int N, int bins, int T, float* dst, int Wdst, int pad_l, const float2* scale,

@@ -586,7 +586,8 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
         const float m = sqrtf(z.x * z.x + z.y * z.y);
         if constexpr (!kSongTable<SRC> && !kStream<SRC>) dst[t] = m;
         mx = fmaxf(mx, m);
-        const unsigned long long k = ((unsigned long long)ord32(z.x) << 32) | ord32(z.y);
+        // numpy compares -0.0 == +0.0 and goes on to the imaginary part; as bit patterns -0.0 would sort below the padding's +0.0
+        const unsigned long long k = ((unsigned long long)ord32(z.x + 0.f) << 32) | ord32(z.y + 0.f);
         key = k > key ? k : key;
     }
     __shared__ float rmx[4];
@@ -618,16 +619,17 @@ void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpa
     VR_HIP(hipGetLastError());
 }
 
-// stats layout: [0..1] legacy words, then 2 x bins rows of (max |X| bits, lexicographic complex key) partials
+// stats layout: a 16-byte header, then 2 x bins rows of (max |X| bits, lexicographic complex key) partials
 // CPLX (complex handles): aff[0..1] = 1 / c as a complex number, formed in double and rounded once -- c = max|X| (mode 0,
 // inference.py:74) or the lexicographic complex maximum itself (mode 1, inference.py:87,94: numpy divides by the complex number,
 // which also rotates the phase)
 // PER_SONG: blockIdx.x = song, stats = that layout without the header for every song ([song][rows] partials), aff [song][4]
+// The one-song forms also leave what they reduced in the 16-byte header: (max |X| bits, the selected key) -- read by the tests only.
 template <bool CPLX, bool PER_SONG = false>
-__global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats, int rows, int mode, float* aff) {
-    const unsigned long long* part = reinterpret_cast<const unsigned long long*>(stats) + 2;
+__global__ __launch_bounds__(256) void coef_affine_kernel(unsigned* stats, int rows, int mode, float* aff) {
+    const unsigned long long* part = reinterpret_cast<unsigned long long*>(stats) + 2;
     if constexpr (PER_SONG) {
-        part = reinterpret_cast<const unsigned long long*>(stats) + (long long)blockIdx.x * rows * 2;
+        part = reinterpret_cast<unsigned long long*>(stats) + (long long)blockIdx.x * rows * 2;
         aff += 4 * blockIdx.x;
     }
     unsigned mxb = 0u;
@@ -647,6 +649,12 @@ __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats,
             rk[threadIdx.x] = rk[threadIdx.x + off] > rk[threadIdx.x] ? rk[threadIdx.x + off] : rk[threadIdx.x];
         }
         __syncthreads();
+    }
+    if constexpr (!PER_SONG) {
+        if (threadIdx.x == 0) {
+            reinterpret_cast<unsigned long long*>(stats)[0] = rm[0];
+            reinterpret_cast<unsigned long long*>(stats)[1] = rk[0];
+        }
     }
     if constexpr (CPLX) {
         if (threadIdx.x == 0) {
@@ -672,12 +680,12 @@ __global__ __launch_bounds__(256) void coef_affine_kernel(const unsigned* stats,
         aff[0] = s; aff[1] = 0.f; aff[2] = s; aff[3] = 0.f;
     }
 }
-void launch_coef_affine(const unsigned* stats, int rows, int mode, float* aff, hipStream_t st) {
+void launch_coef_affine(unsigned* stats, int rows, int mode, float* aff, hipStream_t st) {
     VR_LAUNCH((coef_affine_kernel<false>), dim3(1), dim3(256), 0, st, stats, rows, mode, aff);
     VR_HIP(hipGetLastError());
 }
 
-void launch_coef_complex(const unsigned* stats, int rows, int mode, float2* inv, hipStream_t st) {
+void launch_coef_complex(unsigned* stats, int rows, int mode, float2* inv, hipStream_t st) {
     VR_LAUNCH((coef_affine_kernel<true>), dim3(1), dim3(256), 0, st, stats, rows, mode, reinterpret_cast<float*>(inv));
     VR_HIP(hipGetLastError());
 }
@@ -820,7 +828,7 @@ void launch_song_stats(const SongSeg* songs, int n_songs, int bins, double sum_T
 }
 
 void launch_song_coef(const unsigned long long* part, int n_songs, int rows, int mode, bool cplx, float* aff, hipStream_t st) {
-    const unsigned* stats = reinterpret_cast<const unsigned*>(part);
+    unsigned* stats = reinterpret_cast<unsigned*>(const_cast<unsigned long long*>(part));      // (read only in the per-song form)
     if (cplx) VR_LAUNCH((coef_affine_kernel<true, true>), dim3(n_songs), dim3(256), 0, st, stats, rows, mode, aff);
     else VR_LAUNCH((coef_affine_kernel<false, true>), dim3(n_songs), dim3(256), 0, st, stats, rows, mode, aff);
     VR_HIP(hipGetLastError());
