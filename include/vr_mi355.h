@@ -182,6 +182,24 @@ int vr_stream_open(vr_handle h, int cropsize, int batchsize, int flags, double c
 int vr_stream_push(vr_stream s, const float* wave, int on_device, int64_t n, float* y, float* v, int out_on_device, int64_t capacity,
                    int64_t* n_out);
 int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t capacity, int64_t* n_out);
+/* Many streams of ONE handle in one call: stream k receives n[k] >= 0 more samples (wave[k], planar [2][n[k]]) and, where flush[k] != 0,
+ * its input ends there (a push followed by a flush; flush == NULL: no stream ends).  n[k] == 0 without flush leaves stream k untouched.
+ * y[k] / v[k]: [2][capacity[k]]; n_out[k] = the final samples returned, exactly vr_stream_plan's samples_out after minus before.
+ * CONTRACT: the samples stream k returns and its state afterwards are what vr_stream_push (then vr_stream_flush) on that stream alone
+ * would have produced -- the same steps, the same crops; the bar is 2e-4 * scale as between the other entry points (a device batch
+ * composed differently may change a conv's tile choice).  Afterwards any stream may go on through either entry point, and other calls
+ * on the handle may come between.  What the streams share is the launches: the call goes in rounds, round r = step r of every stream
+ * that still has input; per round one STFT over all streams, the ready crops of all streams and both passes in shared device batches
+ * of `batchsize` (independent of the batchsize a stream was opened with, which sizes its rings and its step; <= 0: the largest among
+ * the streams), one masked iSTFT per stem; per call one drain.  Plain and VR_STREAM_TTA streams may be mixed; VR_CREATE_COMPLEX
+ * handles are supported.  VR_STREAM_MEASURE streams and running-normaliser streams (coef 0) are REFUSED here: the running normaliser
+ * cuts its steps per crop, which stays on vr_stream_push.
+ * Checked before the device is touched, every stream left as it was (VR_ERR_BAD_ARGUMENT, vr_last_error() starts "stream <k>: "):
+ * n_streams >= 1; all streams of one handle; no stream twice; equal cropsize; no stream closed (NULL), flushed or broken; eval mode;
+ * capacity[k] large enough.  While the call runs its streams are marked broken, as in vr_stream_push; a call that fails half way
+ * leaves them so. */
+int vr_stream_push_many(int n_streams, const vr_stream* s, const float* const* wave, int on_device, const int64_t* n, const int* flush,
+                        int batchsize, float* const* y, float* const* v, int out_on_device, const int64_t* capacity, int64_t* n_out);
 int vr_stream_coef(vr_stream s, double* coef_re_im /*[2]*/);
 int vr_stream_info(vr_stream s, int64_t* lookahead_samples, int64_t* block_samples, int64_t* state_bytes);
 int vr_stream_close(vr_stream s);

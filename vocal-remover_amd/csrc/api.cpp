@@ -244,6 +244,26 @@ int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t 
     });
 }
 
+int vr_stream_push_many(int n_streams, const vr_stream* s, const float* const* wave, int on_device, const int64_t* n, const int* flush,
+                        int batchsize, float* const* y, float* const* v, int out_on_device, const int64_t* capacity, int64_t* n_out) {
+    if (n_streams <= 0) { g_err = "n_streams must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!s || !n) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        std::vector<vr::StreamState*> st((size_t)n_streams);
+        std::vector<long long> len(n, n + n_streams), cap, got((size_t)n_streams, 0);
+        if (capacity) cap.assign(capacity, capacity + n_streams);
+        for (int k = 0; k < n_streams; ++k) {
+            const std::string who = "stream " + std::to_string(k) + ": ";
+            VR_CHECK(s[k] && s[k]->st, VR_ERR_BAD_ARGUMENT, who + "null stream (closed?)");
+            VR_CHECK(s[k]->h == s[0]->h, VR_ERR_BAD_ARGUMENT, who + "belongs to another handle than stream 0: the streams of one call share a handle");
+            st[k] = s[k]->st;
+        }
+        s[0]->h->m.stream_push_many(n_streams, st.data(), wave, on_device != 0, len.data(), flush, batchsize, y, v, out_on_device != 0,
+                                    capacity ? cap.data() : nullptr, got.data());
+        if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = got[k];
+    });
+}
+
 int vr_stream_coef(vr_stream s, double* coef_re_im) {
     NEED_STREAM(s);
     return guard([&] {

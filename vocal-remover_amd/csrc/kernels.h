@@ -13,6 +13,11 @@ struct HeadDst {
     long long dN, dC, dH;     // strides of the destination (elements)
     int w_lo, w_hi;           // keep input columns [w_lo, w_hi); column w lands at w - w_lo
     int pad_rows;             // replicate the last input row this many extra times (1025 - 1024)
+    // optional (mask heads only): a device table with one destination per batch item, used in place of p + n * dN -- the items of a
+    // batch may then land in different buffers (vr_stream_push_many: one mask ring per stream and pass).  item_pitch[n] is then the
+    // row pitch of item n's buffer, in place of dH, and rows * item_pitch[n] its plane pitch, in place of dC.
+    float* const* items;
+    const int* item_pitch;
 };
 void launch_head_sigmoid(const Tensor& x, const float* w /*[2][C]*/, const HeadDst& d, hipStream_t st);
 // complex-mask head (is_complex, lib/nets.py:104-107,119-122): 4 outputs, m = complex(out[o], out[o+2]) for o = 0, 1, bounded as
@@ -221,7 +226,8 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
 
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
-// step).  Samples and frames carry their ABSOLUTE index in the stream; the device keeps rings: frame t of the complex spectrogram at
+// step).  The kernels take a TABLE of them: one grid dimension is the table entry, sized for the largest entry, and a workgroup past
+// its own entry's frame or segment count leaves at once (vr_stream_push has one entry, vr_stream_push_many one per stream of a round).  Samples and frames carry their ABSOLUTE index in the stream; the device keeps rings: frame t of the complex spectrogram at
 // column t % R of ring [2][bins][R], the mask of frame t at column t % RM of mask_a [2][bins][RM] (complex64 for a complex handle) and,
 // for the TTA pass, at column (t + shift) % RM of mask_b (the offline layout: crop j of a pass at column j * roi).
 struct StreamSeg {
@@ -242,6 +248,7 @@ struct StreamSeg {
     const float* mask_a;
     const float* mask_b;      // null without TTA
     int RM, shift;
+    const float* aff;         // 1 / c of this stream as the crop gather reads it (launch_coef_affine / launch_coef_complex)
     // masked iSTFT of the frames [t_out, t_done): segment s = second half of frame s + first half of frame s + 1 lands at
     // wave[ch * out_pitch + (s - t_out) * hop]; `carried`: frame t_out was transformed by the previous step, its windowed second half
     // comes from carry_in; the second half of frame t_done - 1 goes to carry_out ([stem][ch][hop], never the buffer read)
@@ -253,12 +260,15 @@ struct StreamSeg {
     long long out_pitch;
 };
 bool stream_tiled_available(const FFTPlan& pl, int hop);
-void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int new_frames, double new_samples, hipStream_t st);
+// seg: a device table of n_seg entries; new_frames = the largest count of new frames among them, new_samples / sum_* only size the profiler's note
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st);
 // part: per-row partial maxima as launch_mag_pad leaves them (stats + 16 bytes); the new frames are reduced INTO them
 void launch_stream_stats(const StreamSeg* seg, int bins, int new_frames, unsigned long long* part, hipStream_t st);
-// crops[n] = (0, first frame; may be negative): as launch_crop_gather, from the ring, aff = 1 / c of the stream
-void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
-                          float* dst, hipStream_t st);
-void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int segments, bool cplx, bool tta, int which, hipStream_t st);
+// crops[n] = (table entry, first frame; may be negative): as launch_crop_gather, from the entry's ring, times the entry's 1 / c
+void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, float* dst,
+                          hipStream_t st);
+// segments = the largest count of output segments among the n_seg entries (an entry with none is skipped); sum_segments, tta: profiler's note
+void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int segments, double sum_segments, bool cplx, bool tta, int which,
+                         hipStream_t st);
 
 }  // namespace vr

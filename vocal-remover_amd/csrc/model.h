@@ -182,6 +182,9 @@ public:
     // n samples more (flush: none, the end of the input); y / v [2][capacity] receive *n_out final samples per channel
     void stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
                      long long capacity, long long* n_out);
+    // vr_stream_push_many: stream k gets n[k] more samples and, flush[k], its end; the crops of all streams share device batches
+    void stream_push_many(int n_streams, StreamState* const* S, const float* const* wave, bool on_dev, const long long* n, const int* flush,
+                          int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out);
     void stream_close(StreamState* S);
     void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
     void separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
@@ -396,6 +399,14 @@ private:
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)
     struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off;
                           StreamSeg* seg_d; int2* crops_d; float* gather; };
+    // One step of one stream in three parts, shared by stream_push (one stream) and stream_push_many (a round of streams):
+    // stream_step_plan takes the block in, asks stream_schedule what is ready, checks the rings and fills the StreamSeg; the caller
+    // launches; stream_step_commit flips the tail / carry buffers and moves the stream's counters on.
+    struct StreamStepPlan { StreamSeg seg; StreamSchedule p; int new_frames, segments; bool emit; };
+    struct StreamCrop { int entry, pass; long long idx; };          // crop idx of a pass of the stream at table entry `entry`
+    StreamStepPlan stream_step_plan(StreamState& S, const StreamStepIO& io_, bool final);
+    void stream_step_crops(const StreamState& S, const StreamStepPlan& sp, int entry, std::vector<StreamCrop>& list) const;
+    void stream_step_commit(StreamState& S, StreamStepIO& io_, const StreamStepPlan& sp);
     void stream_step(StreamState& S, StreamStepIO& io_, bool final);
     void tap(const std::string& name, const Tensor& t);
     bool dry = false;

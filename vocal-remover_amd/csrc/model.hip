@@ -2052,11 +2052,13 @@ void Model::stream_close(StreamState* S) {
     delete S;
 }
 
-void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
-    const int bins = output_bin, E = is_complex ? 2 : 1, roi = S.roi, cropsize = S.cropsize;
+Model::StreamStepPlan Model::stream_step_plan(StreamState& S, const StreamStepIO& o, bool final) {
+    const int roi = S.roi, cropsize = S.cropsize;
     const long long prev_frames = S.frames;
     S.samples += o.blk_n;
+    StreamStepPlan sp{};
     const StreamSchedule p = stream_schedule(n_fft, hop, cropsize, offset, S.tta, S.samples, final);
+    sp.p = p;
     VR_CHECK(p.frames < (1LL << 31) - 2 * cropsize, -2, "stream too long");
     // what the rings must still hold: the oldest frame a coming crop or the iSTFT reads, the oldest mask column not yet final
     long long oldest = std::min(S.done, S.crops[0] * roi - offset);
@@ -2066,10 +2068,9 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
     if (!S.measure) {
         VR_CHECK(p.crops[0] * roi - S.done / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
         if (S.tta) VR_CHECK(p.crops[1] * roi - (S.done + roi / 2) / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+        VR_CHECK((p.crops[0] - S.crops[0]) + (p.crops[1] - S.crops[1]) <= 2 * (S.RM / roi), -4, "stream crop list overflow (planning bug)");
     }
-    S.segs_h.emplace_back();
-    StreamSeg& g = S.segs_h.back();
-    g = StreamSeg{};
+    StreamSeg& g = sp.seg;
     g.tail = S.tail[S.tail_cur]; g.tail_out = S.tail[S.tail_cur ^ 1];
     g.blk = o.blk; g.blk_pitch = o.blk_pitch;
     g.tail_base = S.tail_base; g.blk_base = S.samples - o.blk_n;
@@ -2077,29 +2078,52 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
     g.L = S.samples; g.tail_pitch = 2 * hop;
     g.ring = S.ring; g.R = S.R; g.t_new = (int)prev_frames; g.T = (int)p.frames;
     g.mask_a = S.mask[0]; g.mask_b = S.tta ? S.mask[1] : nullptr; g.RM = S.RM; g.shift = roi / 2;
-    const bool emit = !S.measure && p.done > S.done;
+    g.aff = S.aff;
+    sp.emit = !S.measure && p.done > S.done;
     g.carried = S.done > 0;
     g.t_out = S.done > 0 ? (int)S.done - 1 : 0; g.t_done = (int)p.done;
     g.carry_in = S.carry[S.carry_cur]; g.carry_out = S.carry[S.carry_cur ^ 1];
     g.y_wave = o.y ? o.y + o.out_off : nullptr; g.v_wave = o.v ? o.v + o.out_off : nullptr; g.out_pitch = o.out_pitch;
-    VR_HIP(hipMemcpyAsync(o.seg_d, &g, sizeof(StreamSeg), hipMemcpyHostToDevice, stream));
-    const int new_frames = (int)(p.frames - prev_frames);
-    launch_stft_stream(plan, o.seg_d, new_frames, (double)o.blk_n, stream);
-    if (new_frames > 0 && (S.measure || S.running))
-        launch_stream_stats(o.seg_d, bins, new_frames, reinterpret_cast<unsigned long long*>(S.stats) + 2, stream);
+    sp.new_frames = (int)(p.frames - prev_frames);
+    sp.segments = sp.emit ? g.t_done - 1 - g.t_out : 0;
+    return sp;
+}
+
+// the crops that became ready in this step: pass 0, then pass 1
+void Model::stream_step_crops(const StreamState& S, const StreamStepPlan& sp, int entry, std::vector<StreamCrop>& list) const {
+    if (S.measure) return;
+    for (int ps = 0; ps < (S.tta ? 2 : 1); ++ps)
+        for (long long i = S.crops[ps]; i < sp.p.crops[ps]; ++i) list.push_back(StreamCrop{entry, ps, i});
+}
+
+void Model::stream_step_commit(StreamState& S, StreamStepIO& o, const StreamStepPlan& sp) {
+    if (sp.emit) {
+        S.carry_cur ^= 1;
+        o.out_off += (long long)hop * sp.segments;
+        S.done = sp.p.done;
+    }
+    S.tail_cur ^= 1;
+    S.tail_base = sp.seg.tail_out_base;
+    S.frames = sp.p.frames; S.crops[0] = sp.p.crops[0]; S.crops[1] = sp.p.crops[1];
+}
+
+void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
+    const int bins = output_bin, E = is_complex ? 2 : 1, roi = S.roi, cropsize = S.cropsize;
+    const StreamStepPlan sp = stream_step_plan(S, o, final);
+    S.segs_h.push_back(sp.seg);
+    VR_HIP(hipMemcpyAsync(o.seg_d, &S.segs_h.back(), sizeof(StreamSeg), hipMemcpyHostToDevice, stream));
+    launch_stft_stream(plan, o.seg_d, 1, sp.new_frames, (double)o.blk_n, (double)sp.new_frames, stream);
+    if (sp.new_frames > 0 && (S.measure || S.running))
+        launch_stream_stats(o.seg_d, bins, sp.new_frames, reinterpret_cast<unsigned long long*>(S.stats) + 2, stream);
     // ---- the crops that became ready: pass 0, then pass 1, as one list in device batches of bs
-    struct Crop { int pass; long long idx; };
-    std::vector<Crop> list;
-    if (!S.measure)
-        for (int ps = 0; ps < (S.tta ? 2 : 1); ++ps)
-            for (long long i = S.crops[ps]; i < p.crops[ps]; ++i) list.push_back(Crop{ps, i});
+    std::vector<StreamCrop> list;
+    stream_step_crops(S, sp, 0, list);
     if (!list.empty()) {
         if (S.running) {
             if (is_complex) launch_coef_complex(S.stats, 2 * bins, 0, reinterpret_cast<float2*>(S.aff), stream);
             else launch_coef_affine(S.stats, 2 * bins, 0, S.aff, stream);
         }
         const int n = (int)list.size();
-        VR_CHECK(n <= 2 * (S.RM / roi), -4, "stream crop list overflow (planning bug)");
         S.crops_h.emplace_back((size_t)n);
         std::vector<int2>& cl = S.crops_h.back();
         for (int k = 0; k < n; ++k) cl[k] = make_int2(0, (int)(list[k].idx * roi - offset - (list[k].pass ? roi / 2 : 0)));
@@ -2110,7 +2134,7 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
         auto run_crops = [&](int first, int count) {
             ws.reset();
             float* dense = o.gather + (size_t)(first % S.bs) * crop_f;
-            launch_stream_gather(o.seg_d, o.crops_d + first, count, is_complex, bins, max_bin, cropsize, S.aff, dense, stream);
+            launch_stream_gather(o.seg_d, o.crops_d + first, count, is_complex, bins, max_bin, cropsize, dense, stream);
             Tensor x;
             x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
             x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
@@ -2118,7 +2142,7 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
             Tensor f3 = run_net_window(x, offset, cropsize - offset);
             // one head launch per run of crops that are neighbours in one mask ring
             for (int k = 0; k < count;) {
-                const Crop c0 = list[(size_t)first + k];
+                const StreamCrop c0 = list[(size_t)first + k];
                 const long long col = c0.idx * roi % S.RM;
                 int run = 1;
                 while (k + run < count && list[(size_t)first + k + run].pass == c0.pass && col + (long long)(run + 1) * roi <= S.RM) ++run;
@@ -2134,16 +2158,10 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
         };
         run_crop_chunks(n, S.bs, run_crops);
     }
-    if (emit) {
-        const int segments = g.t_done - 1 - g.t_out;
-        for (int which = 0; which < 2; ++which) launch_istft_stream(plan, o.seg_d, segments, is_complex, S.tta, which, stream);
-        S.carry_cur ^= 1;
-        o.out_off += (long long)hop * segments;
-        S.done = p.done;
-    }
-    S.tail_cur ^= 1;
-    S.tail_base = g.tail_out_base;
-    S.frames = p.frames; S.crops[0] = p.crops[0]; S.crops[1] = p.crops[1];
+    if (sp.emit)
+        for (int which = 0; which < 2; ++which)
+            launch_istft_stream(plan, o.seg_d, 1, sp.segments, (double)sp.segments, is_complex, S.tta, which, stream);
+    stream_step_commit(S, o, sp);
 }
 
 void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
@@ -2228,6 +2246,198 @@ void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long lon
     }
     S.broken = false;
     if (n_out) *n_out = need;
+}
+
+// vr_stream_push_many: the steps of several streams of this handle, taken together in rounds.  Round r holds step r of every stream that
+// still has one -- the cut of stream_push, the flush step last -- so a stream's steps, and with them its crops and its numbers, are the
+// ones it would take alone; what the streams share is the launches: one StreamSeg table and one crop list per round, one STFT over the
+// table, the ready crops of all streams and both passes as ONE list through run_crop_chunks in parts of `batchsize` (one gather, one
+// network pass and one head launch per part: the head scatters every item into its own stream's mask ring through a pointer table),
+// one masked iSTFT per stem over the table.  Per call: inputs in, outputs out, one drain.
+void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float* const* wave, bool on_dev, const long long* n_in, const int* flush,
+                             int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out) {
+    // ---- arguments and the schedule of this call: nothing here touches the device or a stream
+    VR_CHECK(n_streams >= 1, -2, "n_streams must be positive");
+    VR_CHECK(Sv && n_in, -2, "null table");
+    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    struct Part { StreamState* S; int k; bool fl; long long n, need, at; float *stage_in, *stage_y, *stage_v; StreamStepIO o; bool last_done; };
+    std::vector<Part> parts;
+    int bs = batchsize;
+    for (int k = 0; k < n_streams; ++k) {
+        const std::string who = "stream " + std::to_string(k) + ": ";
+        VR_CHECK(Sv[k], -2, who + "null stream (closed?)");
+        StreamState& S = *Sv[k];
+        for (int j = 0; j < k; ++j) VR_CHECK(Sv[j] != Sv[k], -2, who + "the same stream as stream " + std::to_string(j));
+        VR_CHECK(S.cropsize == Sv[0]->cropsize, -2, who + "cropsize " + std::to_string(S.cropsize) + " differs from stream 0's " +
+                                                        std::to_string(Sv[0]->cropsize) + ": the streams of one call share device batches");
+        VR_CHECK(!S.measure, -2, who + "a VR_STREAM_MEASURE stream is not taken by vr_stream_push_many: use vr_stream_push");
+        VR_CHECK(!S.running, -2, who + "a running-normaliser stream (coef 0) is not taken by vr_stream_push_many: its steps are cut per crop, "
+                                       "use vr_stream_push");
+        VR_CHECK(!S.broken, -2, who + "this stream failed in an earlier call: close it");
+        const bool fl = flush && flush[k];
+        VR_CHECK(!S.flushed, -2, who + (fl ? "the stream is already flushed" : "push after flush"));
+        const long long n = n_in[k];
+        VR_CHECK(n >= 0 && (n == 0 || (wave && wave[k])), -2, who + "null or negative input");
+        long long need = 0;
+        try {
+            const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
+            const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, fl);
+            need = after.samples_out - before.samples_out;
+        } catch (const Error& e) {
+            throw Error(e.code, who + e.what());
+        }
+        if (need > 0)
+            VR_CHECK(y && v && capacity && y[k] && v[k] && capacity[k] >= need, -2,
+                     who + "output capacity " + std::to_string(capacity ? capacity[k] : 0) + " is too small: this call returns " +
+                         std::to_string(need) + " samples per channel");
+        if (batchsize <= 0) bs = std::max(bs, S.bs);
+        if (n == 0 && !fl) continue;                 // untouched
+        Part p{};
+        p.S = &S; p.k = k; p.fl = fl; p.n = n; p.need = need;
+        parts.push_back(p);
+    }
+    if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = 0;
+    if (parts.empty()) return;
+    const int np = (int)parts.size();
+    const int cropsize = Sv[0]->cropsize, roi = Sv[0]->roi, bins = output_bin, E = is_complex ? 2 : 1;
+    size_t list_cap = 0;
+    for (const Part& p : parts) list_cap += (size_t)2 * (p.S->RM / roi);
+
+    DeviceGuard dev_guard(device);
+    // ---- the staging arena: carved twice, first dry for its size
+    const size_t crop_f = (size_t)nin * max_bin * cropsize;
+    StreamSeg* seg_d = nullptr;
+    unsigned long long* list_d = nullptr;            // per round: the crop list (int2 per crop), one mask destination per crop, its row pitch
+    float* gather = nullptr;
+    auto carve = [&](Arena& A) {
+        seg_d = static_cast<StreamSeg*>(A.alloc(sizeof(StreamSeg) * np));
+        list_d = static_cast<unsigned long long*>(A.alloc(24 * list_cap));
+        gather = A.allocf((size_t)bs * crop_f + 4096);
+        for (Part& p : parts) {
+            p.stage_in = (!on_dev && p.n > 0) ? A.allocf((size_t)2 * p.n) : nullptr;
+            p.stage_y = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
+            p.stage_v = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
+        }
+    };
+    Arena dry_a;
+    dry_a.dry = true;
+    carve(dry_a);
+    ensure_io(dry_a.peak + 65536);
+    io.reset();
+    carve(io);
+    for (Part& p : parts) p.S->broken = true;       // until the call has gone through: a failure half way leaves the rings undefined
+    // host copies of what the rounds send to the device, alive until the call has drained
+    std::deque<std::vector<StreamSeg>> segs_h;
+    std::deque<std::vector<unsigned long long>> lists_h;
+    try {
+        for (Part& p : parts) {
+            if (p.stage_in) VR_HIP(hipMemcpyAsync(p.stage_in, wave[p.k], (size_t)2 * p.n * sizeof(float), hipMemcpyHostToDevice, stream));
+            p.o = StreamStepIO{};
+            p.o.blk = on_dev ? (p.n > 0 ? wave[p.k] : nullptr) : p.stage_in;
+            p.o.blk_pitch = p.n;
+            p.o.y = out_on_dev ? (y ? y[p.k] : nullptr) : p.stage_y; p.o.v = out_on_dev ? (v ? v[p.k] : nullptr) : p.stage_v;
+            p.o.out_pitch = out_on_dev ? (capacity ? capacity[p.k] : 0) : p.need;
+        }
+        std::vector<int> live;                       // the parts that take a step in this round
+        std::vector<StreamStepPlan> plans;
+        std::vector<StreamCrop> list;
+        for (;;) {
+            live.clear(); plans.clear(); list.clear();
+            for (int i = 0; i < np; ++i) {
+                Part& p = parts[i];
+                if (p.at >= p.n && !(p.fl && !p.last_done)) continue;
+                StreamState& S = *p.S;
+                const float* src = p.o.blk_pitch > 0 ? (on_dev ? wave[p.k] : p.stage_in) : nullptr;
+                bool final = false;
+                if (p.at < p.n) {
+                    const long long take = std::min((long long)S.chunk_frames * hop, p.n - p.at);
+                    p.o.blk = src + p.at; p.o.blk_n = take;
+                    p.at += take;
+                } else {
+                    p.o.blk = src; p.o.blk_n = 0;
+                    final = true;
+                    p.last_done = true;
+                }
+                const int entry = (int)live.size();
+                plans.push_back(stream_step_plan(S, p.o, final));
+                stream_step_crops(S, plans.back(), entry, list);
+                live.push_back(i);
+                if (final) S.flushed = true;
+            }
+            if (live.empty()) break;
+            const int ne = (int)live.size();
+            segs_h.emplace_back((size_t)ne);
+            int max_new = 0, max_seg = 0;
+            double sum_new = 0, sum_seg = 0, sum_blk = 0;
+            bool any_tta = false;
+            for (int e = 0; e < ne; ++e) {
+                segs_h.back()[e] = plans[e].seg;
+                max_new = std::max(max_new, plans[e].new_frames); sum_new += plans[e].new_frames;
+                max_seg = std::max(max_seg, plans[e].segments); sum_seg += plans[e].segments;
+                sum_blk += (double)parts[live[e]].o.blk_n;
+                any_tta = any_tta || parts[live[e]].S->tta;
+            }
+            VR_HIP(hipMemcpyAsync(seg_d, segs_h.back().data(), sizeof(StreamSeg) * ne, hipMemcpyHostToDevice, stream));
+            launch_stft_stream(plan, seg_d, ne, max_new, sum_blk, sum_new, stream);
+            // ---- the crops of all streams that became ready: stream-major, pass 0 then pass 1 inside a stream, in device batches of bs
+            if (!list.empty()) {
+                const int nc = (int)list.size();
+                VR_CHECK((size_t)nc <= list_cap, -4, "stream crop list overflow (planning bug)");
+                lists_h.emplace_back((size_t)2 * nc + ((size_t)nc + 1) / 2);
+                std::vector<unsigned long long>& lh = lists_h.back();
+                for (int c = 0; c < nc; ++c) {
+                    const StreamCrop& cr = list[c];
+                    const StreamState& S = *parts[live[cr.entry]].S;
+                    const int2 at = make_int2(cr.entry, (int)(cr.idx * roi - offset - (cr.pass ? roi / 2 : 0)));
+                    memcpy(&lh[c], &at, 8);
+                    // (RM is a multiple of roi: the roi columns of a crop never wrap inside the ring)
+                    lh[(size_t)nc + c] = (unsigned long long)reinterpret_cast<uintptr_t>(S.mask[cr.pass] + (size_t)E * (cr.idx * roi % S.RM));
+                    reinterpret_cast<int*>(&lh[(size_t)2 * nc])[c] = S.RM;
+                }
+                VR_HIP(hipMemcpyAsync(list_d, lh.data(), lh.size() * 8, hipMemcpyHostToDevice, stream));
+                const int2* crops_d = reinterpret_cast<const int2*>(list_d);
+                float* const* items_d = reinterpret_cast<float* const*>(list_d + nc);
+                fold_eval_affines();                // before planning, as in forward_api
+                plan_and_reserve(bs, cropsize, 0);
+                const int* pitch_d = reinterpret_cast<const int*>(list_d + 2 * (size_t)nc);
+                auto run_crops = [&](int first, int count) {
+                    ws.reset();
+                    float* dense = gather + (size_t)(first % bs) * crop_f;
+                    launch_stream_gather(seg_d, crops_d + first, count, is_complex, bins, max_bin, cropsize, dense, stream);
+                    Tensor x;
+                    x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
+                    x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
+                    x.slope = 1.f;
+                    Tensor f3 = run_net_window(x, offset, cropsize - offset);
+                    HeadDst d{};
+                    d.items = items_d + first; d.item_pitch = pitch_d + first;
+                    d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
+                    if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
+                    else launch_head_sigmoid(f3, out_w->dev, d, stream);
+                };
+                run_crop_chunks(nc, bs, run_crops);
+            }
+            if (max_seg > 0)
+                for (int which = 0; which < 2; ++which)
+                    launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream);
+            for (int e = 0; e < ne; ++e) stream_step_commit(*parts[live[e]].S, parts[live[e]].o, plans[e]);
+        }
+        for (Part& p : parts) {
+            VR_CHECK(p.o.out_off == p.need, -4, "stream schedule mismatch (planning bug)");
+            if (!out_on_dev && p.need > 0) {
+                VR_HIP(hipMemcpy2DAsync(y[p.k], (size_t)capacity[p.k] * 4, p.stage_y, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpy2DAsync(v[p.k], (size_t)capacity[p.k] * 4, p.stage_v, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
+            }
+        }
+        VR_HIP(hipStreamSynchronize(stream));
+    } catch (...) {
+        hipStreamSynchronize(stream);               // the host copies above must outlive every copy that is still in flight
+        throw;
+    }
+    for (Part& p : parts) {
+        p.S->broken = false;
+        if (n_out) n_out[p.k] = p.need;
+    }
 }
 
 // =====================================================================================================

@@ -23,7 +23,7 @@ __device__ __forceinline__ void load_aff(const Tensor& x, int h, int c, float& s
 // ---------------------------------------------------------------------------------------------------
 // Thin 1x1 conv over channels, CO outputs, 4 consecutive frames per thread.
 //   FINAL: sigmoid + window/crop + replicate rows (mask head, lib/nets.py:109-115,127-128); CO = 4: the complex-mask head
-//          (lib/nets.py:104-107,119-122), complex64 stores
+//          (lib/nets.py:104-107,119-122), complex64 stores; item n goes to d.items[n] when that table is given, else to d.p + n * d.dN
 //   else : raw store to out[n][h][w] (+ per-block sum/sumsq partials for BatchNorm batch stats)
 // ---------------------------------------------------------------------------------------------------
 template <int CO, bool FINAL>
@@ -58,7 +58,9 @@ __global__ __launch_bounds__(256) void thin_conv_kernel(Tensor x, const float* _
             }
         }
         if constexpr (FINAL && CO == 4) {
-            float2* dp = reinterpret_cast<float2*>(d.p);
+            float2* dp = reinterpret_cast<float2*>(d.p) + (long long)n * d.dN;
+            long long dC = d.dC, dH = d.dH;
+            if (d.items) { dp = reinterpret_cast<float2*>(d.items[n]); dH = d.item_pitch[n]; dC = (long long)(x.H + d.pad_rows) * dH; }
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
 #pragma unroll
@@ -69,13 +71,16 @@ __global__ __launch_bounds__(256) void thin_conv_kernel(Tensor x, const float* _
                     const float mag = hypotf(re, im);                         // torch.abs of a complex tensor
                     const float th = tanhf(mag), den = mag + 1e-8f;
                     const float2 m = make_float2(th * re / den, th * im / den);
-                    float2* dst = dp + (long long)n * d.dN + (long long)o * d.dC + (wcol - d.w_lo);
-                    dst[(long long)h * d.dH] = m;
+                    float2* dst = dp + (long long)o * dC + (wcol - d.w_lo);
+                    dst[(long long)h * dH] = m;
                     if (h == x.H - 1)
-                        for (int e = 1; e <= d.pad_rows; ++e) dst[(long long)(h + e) * d.dH] = m;
+                        for (int e = 1; e <= d.pad_rows; ++e) dst[(long long)(h + e) * dH] = m;
                 }
             }
         } else if constexpr (FINAL) {
+            float* dp = d.p + (long long)n * d.dN;
+            long long dC = d.dC, dH = d.dH;
+            if (d.items) { dp = d.items[n]; dH = d.item_pitch[n]; dC = (long long)(x.H + d.pad_rows) * dH; }
 #pragma unroll
             for (int o = 0; o < CO; ++o) {
 #pragma unroll
@@ -83,10 +88,10 @@ __global__ __launch_bounds__(256) void thin_conv_kernel(Tensor x, const float* _
                     const int wcol = w4 * 4 + j;
                     if (wcol < d.w_lo || wcol >= d.w_hi) continue;
                     const float m = 1.f / (1.f + __expf(-acc[o][j]));
-                    float* dst = d.p + (long long)n * d.dN + (long long)o * d.dC + (wcol - d.w_lo);
-                    dst[(long long)h * d.dH] = m;
+                    float* dst = dp + (long long)o * dC + (wcol - d.w_lo);
+                    dst[(long long)h * dH] = m;
                     if (h == x.H - 1)
-                        for (int e = 1; e <= d.pad_rows; ++e) dst[(long long)(h + e) * d.dH] = m;
+                        for (int e = 1; e <= d.pad_rows; ++e) dst[(long long)(h + e) * dH] = m;
                 }
             }
         } else {
@@ -131,6 +136,7 @@ static void launch_head(const Tensor& x_in, const float* w, const HeadDst& d_in,
     const int q0 = (d_in.w_lo > 0 ? d_in.w_lo : 0) / 4;
     const int q1 = ((d_in.w_hi < x_in.W ? d_in.w_hi : x_in.W) + 3) / 4;
     VR_CHECK(q1 > q0, -2, "mask head: empty column window");
+    VR_CHECK(!d_in.items || d_in.item_pitch, -2, "mask head: a destination table needs its pitch table");
     Tensor x = x_in;
     x.p += (long long)q0 * 4; x.W = (q1 - q0) * 4;
     HeadDst d = d_in;

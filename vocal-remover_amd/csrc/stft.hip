@@ -26,8 +26,9 @@ namespace vr {
 // and then runs the same code.  `mask_a` is then the call's concatenated mask (row pitch Wa), `mask_b` the same pointer when the TTA
 // pass is to be averaged in (else null), `wgt` the weights of all songs; the arguments an entry replaces are passed as 0.
 template <class SRC> constexpr bool kSongTable = std::is_same<SRC, const SongSeg>::value;
-// SRC = const StreamSeg (vr_stream_*): `src` points at the one StreamSeg of the stream's current step.  Frames and samples are addressed
-// by their absolute index in the stream and live in rings (kernels.h); each kernel handles only what the step added.
+// SRC = const StreamSeg (vr_stream_*): `src` is a table of StreamSeg, one entry per stream taking a step (vr_stream_push: one entry), and
+// one more grid dimension picks the entry, as for the song table.  Frames and samples are addressed by their absolute index in the
+// stream and live in rings (kernels.h); each kernel handles only what the step added to its entry's stream.
 template <class SRC> constexpr bool kStream = std::is_same<SRC, const StreamSeg>::value;
 template <class SRC> using StreamLocal = typename std::conditional<kStream<SRC>, StreamSeg, int>::type;
 
@@ -138,8 +139,9 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     const int ch = blockIdx.y;
     const float* wv;
     StreamLocal<SRC> ss{};
-    if constexpr (kStream<SRC>) {                    // the frames [t_new, T) of the stream, written into the ring
-        ss = wave[0];
+    if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_new, T) of its stream, written into the ring
+        ss = wave[blockIdx.z];
+        if (blockIdx.x > 0 && t0 >= ss.T - ss.t_new) return;        // (workgroup 0 always runs: it moves the input tail on)
         t0 += ss.t_new; T = ss.T;
         wv = nullptr;
     } else if constexpr (kSongTable<SRC>) {          // blockIdx.z = song; the grid is sized for the longest one
@@ -233,8 +235,9 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     const float2* __restrict__ spec;
     StreamLocal<SRC> ss{};
     bool carried = false;                            // (stream) frame t0 of this workgroup comes from the carry, not from the ring
-    if constexpr (kStream<SRC>) {                    // the frames [t_out, t_done) of the stream, spectrogram and masks from their rings
-        ss = src[0];
+    if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_out, t_done) of its stream, from its rings
+        ss = src[blockIdx.z];
+        if (t0 >= ss.t_done - 1 - ss.t_out) return;                 // (an entry with nothing turning final has no segment at all)
         t0 += ss.t_out; T = ss.t_done;
         spec = ss.ring; ma = ss.mask_a; mb = ss.mask_b; shift = ss.shift;
         wave = which ? ss.v_wave : ss.y_wave;
@@ -511,7 +514,7 @@ __device__ __forceinline__ float unord32(unsigned o) {
 // [pad_l, pad_l + T) (the whole row is written: no pre-zeroing), for blockIdx.y = batch item n; no statistics.
 // SRC = const SongSeg, PACK false: the statistics pass per song, blockIdx = (row, song), the row's maxima into part[song][row] and
 // no |X| store.  GATHER (song table only; T = cropsize, Wpad = max_bin, part = the crop list as (song, first frame) pairs, scale =
-// aff [song][4] holding 1 / c): blockIdx = (row of [2][max_bin], crop n); the crop's frames [first, first + cropsize) of its song become
+// aff [song][4] holding 1 / c; a StreamSeg entry brings its own): blockIdx = (row of [2][max_bin], crop n); the crop's frames [first, first + cropsize) of its song become
 // item n of the dense network input mag_pad [n][nin][max_bin][cropsize] -- |X| / c (PACK false) or the planes [re L, re R, im L, im R]
 // of X / c (PACK true), zero outside [0, T_song).  It stands for memset + mag_pad + materialize (+ pack) of the one-song path and for
 // its strided crop view, so that a device batch can hold crops of several songs and of both TTA passes.
@@ -523,13 +526,15 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
         const int max_bin = Wpad, cropsize = T;
         const int c = blockIdx.x / max_bin, k = blockIdx.x - c * max_bin, n = blockIdx.y;
         const int2 cr = reinterpret_cast<const int2*>(part)[n];
-        const auto sg = spec[cr.x];                                 // (a stream has one entry: its crops name entry 0)
+        const auto sg = spec[cr.x];                                 // (streams: the table entry of the crop's stream)
         const float2* sp;
         if constexpr (kStream<SRC>) sp = sg.ring + ((long long)c * bins + k) * sg.R;
         else sp = sg.spec + ((long long)c * bins + k) * sg.T;
         float* d0 = mag_pad + (((long long)n * (PACK ? 4 : 2) + c) * max_bin + k) * cropsize;
         float* d1 = d0 + 2LL * max_bin * cropsize;                  // (PACK: the imaginary plane)
-        const float2 s = scale[2 * cr.x];
+        float2 s;
+        if constexpr (kStream<SRC>) s = *reinterpret_cast<const float2*>(sg.aff);        // 1 / c travels with the entry
+        else s = scale[2 * cr.x];
         for (int col = threadIdx.x; col < cropsize; col += 256) {
             const int t = cr.y + col;
             float2 z;
@@ -890,7 +895,7 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
 // Every launch covers what one step of the stream added: new frames, newly ready crops, newly final output segments.
 bool stream_tiled_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
 
-void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int new_frames, double new_samples, hipStream_t st) {
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st) {
     const int M = pl.n_fft / 2, bins = M + 1;
     int F = tile_frames(pl, 0);
     if (F > 16) F = 16;
@@ -898,10 +903,10 @@ void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int new_frames,
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
     static std::atomic<unsigned long long> attr_done{0};
     ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const StreamSeg>), 160 * 1024);
-    prof_note(0.0, 2.0 * (4.0 * new_samples + 8.0 * (double)bins * new_frames));
+    prof_note(0.0, 2.0 * (4.0 * new_samples + 8.0 * (double)bins * sum_frames));
     // (a step without a new frame still launches one workgroup per channel: it moves the input tail on)
     const int blocks = new_frames > 0 ? (new_frames + F - 1) / F : 1;
-    VR_LAUNCH((stft_tile_kernel<const StreamSeg>), dim3((unsigned)blocks, 2), dim3(1024), lds, st, pl, seg, 0LL, 0, F, nullptr);
+    VR_LAUNCH((stft_tile_kernel<const StreamSeg>), dim3((unsigned)blocks, 2, (unsigned)n_seg), dim3(1024), lds, st, pl, seg, 0LL, 0, F, nullptr);
     VR_HIP(hipGetLastError());
 }
 
@@ -911,24 +916,24 @@ void launch_stream_stats(const StreamSeg* seg, int bins, int new_frames, unsigne
     VR_HIP(hipGetLastError());
 }
 
-void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, const float* aff,
-                          float* dst, hipStream_t st) {
+void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bool cplx, int bins, int max_bin, int cropsize, float* dst,
+                          hipStream_t st) {
     prof_note(0.0, (double)count * 2 * max_bin * cropsize * (8.0 + (cplx ? 8.0 : 4.0)));
     unsigned long long* list = reinterpret_cast<unsigned long long*>(const_cast<int2*>(crops));
-    const float2* inv = reinterpret_cast<const float2*>(aff);
-    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, inv);
-    else VR_LAUNCH((mag_pad_kernel<false, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, inv);
+    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, nullptr);
+    else VR_LAUNCH((mag_pad_kernel<false, const StreamSeg, true>), dim3(2 * max_bin, count), dim3(256), 0, st, seg, cropsize, dst, max_bin, 0, list, bins, nullptr);
     VR_HIP(hipGetLastError());
 }
 
-void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int segments, bool cplx, bool tta, int which, hipStream_t st) {
+void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int segments, double sum_segments, bool cplx, bool tta, int which,
+                         hipStream_t st) {
     const int M = pl.n_fft / 2, bins = M + 1;
     if (segments < 1) return;
     const int F = tile_frames(pl, M);
     const int S = F - 1;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
-    const dim3 grid((unsigned)((segments + S - 1) / S), 2);
-    prof_note(0.0, 2.0 * ((double)bins * segments * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * segments));
+    const dim3 grid((unsigned)((segments + S - 1) / S), 2, (unsigned)n_seg);
+    prof_note(0.0, 2.0 * ((double)bins * sum_segments * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * sum_segments));
     if (cplx) {
         static std::atomic<unsigned long long> attr_done{0};
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const StreamSeg>), 160 * 1024);

@@ -138,6 +138,72 @@ class Separator(object):
         = a running normaliser over the audio received so far, which is NOT the offline result."""
         return Stream(self, coef, tta)
 
+    def push_many(self, streams, waves, flush=False, batchsize=None):
+        """One vr_stream_push_many call: streams[k] (opened by self.stream) receives waves[k] ([2, n], or None for nothing) and, where
+        flush (a bool, or one per stream) says so, its input ends there.  Returns [(y, v), ...] as Stream.push / Stream.flush return
+        them for each stream alone; the crops of all streams share device batches of `batchsize` (default self.batchsize).  Either
+        every wave is a numpy array (numpy out) or every wave is a cuda tensor on one device (cuda out)."""
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        ct = native.ctypes
+        streams, waves = list(streams), list(waves)
+        N = len(streams)
+        if not N:
+            raise ValueError('push_many needs at least one stream')
+        if len(waves) != N:
+            raise ValueError('push_many: %d streams but %d waves' % (N, len(waves)))
+        fl = [bool(flush)] * N if isinstance(flush, (bool, np.bool_)) else [bool(f) for f in flush]
+        if len(fl) != N:
+            raise ValueError('push_many: %d streams but %d flush flags' % (N, len(fl)))
+        given = [w for w in waves if w is not None]
+        cuda = [torch is not None and torch.is_tensor(w) and w.is_cuda for w in given]
+        if any(cuda) and not all(cuda):
+            raise ValueError('push_many: either every wave is a cuda tensor or none is')
+        on_dev = all(cuda) if given else bool(streams[0]._dev_out)
+        if on_dev:
+            waves = [None if w is None else w.detach().to(torch.float32).contiguous() for w in waves]
+            devs = set(w.device for w in waves if w is not None)
+            if len(devs) > 1:
+                raise ValueError('push_many: the waves are on different devices')
+            dev = devs.pop() if devs else next(st._device for st in streams if st._device is not None)
+        else:
+            waves = [None if w is None else np.ascontiguousarray(np.asarray(w.detach().cpu().numpy() if torch is not None and torch.is_tensor(w)
+                                                                             else w, dtype=np.float32)) for w in waves]
+        for k, w in enumerate(waves):
+            if w is not None and (w.ndim != 2 or w.shape[0] != 2):
+                raise ValueError('stream %d: wave must be [2, n]' % k)
+        lens = [0 if w is None else int(w.shape[1]) for w in waves]
+        caps = [max(st._need(n, f), 1) for st, n, f in zip(streams, lens, fl)]       # (a flush below one hop of input raises here)
+        if on_dev:
+            ys = [torch.empty((2, c), dtype=torch.float32, device=dev) for c in caps]
+            vs = [torch.empty_like(a) for a in ys]
+            torch.cuda.current_stream(dev).synchronize()
+            addr = lambda a: a.data_ptr()
+        else:
+            ys = [np.empty((2, c), dtype=np.float32) for c in caps]
+            vs = [np.empty_like(a) for a in ys]
+            addr = lambda a: a.ctypes.data
+        table = lambda seq: (ct.c_void_p * N)(*[(addr(a) if a is not None and a.shape[1] else 0) or None for a in seq])
+        got = (ct.c_int64 * N)()
+        self.model.eval()
+        native.check(native.lib().vr_stream_push_many(
+            N, (ct.c_void_p * N)(*[st._s.value for st in streams]), table(waves), 1 if on_dev else 0, (ct.c_int64 * N)(*lens),
+            (ct.c_int * N)(*[1 if f else 0 for f in fl]), int(self.batchsize if batchsize is None else batchsize), table(ys), table(vs),
+            1 if on_dev else 0, (ct.c_int64 * N)(*caps), got))
+        for st, n, f in zip(streams, lens, fl):
+            if n or f:
+                st._samples += n
+                st._dev_out = on_dev
+                st._device = dev if on_dev else st._device
+        return [(a[:, :int(g)], b[:, :int(g)]) for a, b, g in zip(ys, vs, got)]
+
+    def flush_many(self, streams):
+        """Stream.flush for every stream of the list in one call."""
+        streams = list(streams)
+        return self.push_many(streams, [None] * len(streams), flush=True)
+
     def measure_coef(self, blocks, tta=False):
         """The normaliser separate_wave(tta=tta) would use for the concatenation of `blocks` (an iterable of waves [2, n]), without
         running the network or holding the input."""
@@ -250,9 +316,8 @@ class Stream(object):
             pass
 
 
-def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
-    """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
-    written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed."""
+def _stream_reader(path, sr, block_seconds):
+    """-> blocks(): a fresh iterator over the WAV at `path` as stereo blocks [2, n] of block_seconds.  The file's rate must be `sr`."""
     from . import audio
     rd = audio.WavBlockReader(path)
     if rd.sr != sr:
@@ -262,6 +327,14 @@ def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
     def blocks():
         for b in rd.blocks(n):
             yield np.ascontiguousarray(np.vstack([b, b]) if b.shape[0] == 1 else b[:2])      # mono to stereo (inference.py:143-145)
+    return blocks
+
+
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
+    """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
+    written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed."""
+    from . import audio
+    blocks = _stream_reader(path, sr, block_seconds)
     coef = sp.measure_coef(blocks(), tta=tta)
     with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, sp.stream(coef=coef, tta=tta) as s:
         for b in blocks():
@@ -271,6 +344,33 @@ def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
         y, v = s.flush()
         wy.append(y.T)
         wv.append(v.T)
+
+
+def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0):
+    """--stream on a directory: stream_file for a group of WAVs at once.  Every file's normaliser is measured first; then the files
+    advance together, one block each per Separator.push_many call, so their crops share device batches; a file that ends is flushed
+    in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k]."""
+    import contextlib
+
+    from . import audio
+    readers = [_stream_reader(p, sr, block_seconds) for p in paths]
+    coefs = [sp.measure_coef(blocks(), tta=tta) for blocks in readers]
+    with contextlib.ExitStack() as stack:
+        wy = [stack.enter_context(audio.WavAppendWriter(oy, sr, 2)) for oy, _ in outs]
+        wv = [stack.enter_context(audio.WavAppendWriter(ov, sr, 2)) for _, ov in outs]
+        streams = [stack.enter_context(sp.stream(coef=c, tta=tta)) for c in coefs]
+        its = [blocks() for blocks in readers]
+        ahead = [next(it, None) for it in its]
+        live = list(range(len(paths)))                  # the files still streaming; a flushed stream takes no further part
+        while live:
+            cur = [ahead[k] for k in live]
+            for k in live:
+                ahead[k] = next(its[k], None) if ahead[k] is not None else None
+            ends = [ahead[k] is None for k in live]
+            for k, (y, v) in zip(live, sp.push_many([streams[k] for k in live], cur, ends)):
+                wy[k].append(y.T)
+                wv[k].append(v.T)
+            live = [k for k, end in zip(live, ends) if not end]
 
 
 def expand_inputs(path, songs_per_call):
@@ -309,7 +409,7 @@ def main(argv=None):
     p.add_argument('--is_complex', action='store_true')              # a checkpoint of CascadedNet(..., is_complex=True)
     p.add_argument('--output_image', '-I', action='store_true')      # accepted for command-line compatibility; no image is written
     p.add_argument('--output_dir', '-o', type=str, default="")
-    p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call
+    p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call (--stream: files streamed together)
     p.add_argument('--stream', action='store_true')                  # read, separate and write block by block (Separator.stream)
     p.add_argument('--block_seconds', type=float, default=1.0)
     args = p.parse_args(argv)
@@ -338,9 +438,13 @@ def main(argv=None):
         audio.write('{}{}_Instruments.wav'.format(output_dir, basename), y_wave.T, sr)
         audio.write('{}{}_Vocals.wav'.format(output_dir, basename), v_wave.T, sr)
 
+    if args.stream and os.path.isdir(args.input):
+        for group in expand_inputs(args.input, args.songs_per_call):      # the group's files advance together, block by block
+            names = [os.path.splitext(os.path.basename(path))[0] for path in group]
+            stream_files(sp, group, [('{}{}_Instruments.wav'.format(output_dir, b), '{}{}_Vocals.wav'.format(output_dir, b)) for b in names],
+                         args.sr, tta=args.tta, block_seconds=args.block_seconds)
+        return 0
     if args.stream:
-        if os.path.isdir(args.input):
-            raise SystemExit('--stream takes one file')
         basename = os.path.splitext(os.path.basename(args.input))[0]
         stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
                     args.sr, tta=args.tta, block_seconds=args.block_seconds)

@@ -45,6 +45,9 @@ _SIGNATURES = {
     'vr_stream_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int,
                                       ctypes.c_int64, c_i64p]),
     'vr_stream_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_stream_push_many': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p, c_i64p]),
     'vr_stream_coef': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     'vr_stream_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i64p]),
     'vr_stream_close': (ctypes.c_int, [ctypes.c_void_p]),
