@@ -252,6 +252,34 @@ int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X
                      const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
                      int out_on_device);
 
+/* The training set resident in HBM: load every song's cached spectrogram pair once, then each batch is one vr_dataset_batch -- the
+ * kernel of vr_augment_batch reading the crops where they lie, no file read and no host-to-device copy of spectrogram rows.
+ *   vr_dataset_create   an empty store on `device` for spectrograms of `bins` bins.  It owns its own device allocations and nothing
+ *                       of any handle: it may outlive handles and serve several handles on its device.
+ *   vr_dataset_add      one song: X, y host [rows][2][bins] complex64 (re,im interleaved), the on-disk layout of the cache
+ *                       (spec_utils.SpectrogramCache), copied once into one device slab each.  The pointers may be memory maps of
+ *                       the .npy files: the copy runs in bounded pieces through the store's own pinned staging.  *song_out (may be
+ *                       NULL) is the song's index, counting from 0 in the order added.  A failed device allocation is VR_ERR_OOM,
+ *                       vr_last_error() gives the bytes asked for and the bytes the store already holds; the store stays usable.
+ *   vr_dataset_info     songs held, and the device bytes of their slabs.   vr_dataset_rows: the rows of one song.
+ *   vr_dataset_batch    B samples of T rows: sample b is rows [start, start + T) of song crops[b].song, mixed -- when desc[b].flags has
+ *                       bit 3 -- with rows [mix_start, mix_start + T) of song mix_song (both ignored otherwise).  desc,
+ *                       reduction_weight and the outputs X_mag, y_mag [B][2][bins][T] are those of vr_augment_batch, and so is every
+ *                       value computed.  Runs on the handle's stream and returns when the outputs are complete.
+ * Errors of vr_dataset_batch, all VR_ERR_BAD_ARGUMENT and all before anything is launched (the kernel is never given a row it cannot
+ * read): B <= 0 or a null table (reported before the handle and the store are looked at); a handle on another device than the store;
+ * and, with vr_last_error() naming the sample: a song index out of range, start < 0, start + T > rows, the same for the partner when
+ * bit 3 is set, bit 3 with mix_song < 0, bit 0 or 4 without reduction_weight. */
+typedef struct vr_dataset_s* vr_dataset;
+typedef struct vr_crop { int song; int mix_song; int64_t start; int64_t mix_start; } vr_crop;
+int vr_dataset_create(int device, int bins, vr_dataset* out);
+int vr_dataset_destroy(vr_dataset d);
+int vr_dataset_add(vr_dataset d, const float* X, const float* y, int64_t rows, int* song_out);
+int vr_dataset_info(vr_dataset d, int* n_songs, int64_t* bytes);
+int vr_dataset_rows(vr_dataset d, int song, int64_t* rows);
+int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                     float* X_mag, float* y_mag, int out_on_device);
+
 /* torch.optim.Adam(lr, betas=(b1,b2), eps, weight_decay=0).step()   train.py:215-218,95
  * grad_scale multiplies every gradient first (1/world_size after a SUM all-reduce).  Hyper-parameters are doubles
  * like torch's python floats: 1 - beta, the bias corrections and lr / bias_correction1 are formed in double and only

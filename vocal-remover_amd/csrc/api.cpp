@@ -364,6 +364,76 @@ int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X
     });
 }
 
+// ---- the resident training set ---------------------------------------------------------------------------------------------
+static void need_device(int device);
+
+struct vr_dataset_s {
+    vr::ResidentSet set;
+    vr_dataset_s(int device, int bins) : set(device, bins) {}
+};
+
+#define NEED_DATASET(d)                                          \
+    if (!(d)) {                                                  \
+        g_err = "null dataset";                                  \
+        return VR_ERR_BAD_ARGUMENT;                              \
+    }
+
+int vr_dataset_create(int device, int bins, vr_dataset* out) {
+    if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
+    *out = nullptr;
+    if (bins <= 0) { g_err = "vr_dataset_create: bins must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        need_device(device);
+        *out = new vr_dataset_s(device, bins);
+    });
+}
+
+int vr_dataset_destroy(vr_dataset d) {
+    NEED_DATASET(d);
+    return guard([&] { delete d; });
+}
+
+int vr_dataset_add(vr_dataset d, const float* X, const float* y, int64_t rows, int* song_out) {
+    NEED_DATASET(d);
+    return guard([&] {
+        VR_CHECK(X && y, VR_ERR_BAD_ARGUMENT, "null argument");
+        const int song = d->set.add(X, y, rows);
+        if (song_out) *song_out = song;
+    });
+}
+
+int vr_dataset_info(vr_dataset d, int* n_songs, int64_t* bytes) {
+    NEED_DATASET(d);
+    if (n_songs) *n_songs = (int)d->set.songs.size();
+    if (bytes) *bytes = d->set.bytes;
+    return VR_OK;
+}
+
+int vr_dataset_rows(vr_dataset d, int song, int64_t* rows) {
+    NEED_DATASET(d);
+    return guard([&] {
+        VR_CHECK(rows, VR_ERR_BAD_ARGUMENT, "null argument");
+        VR_CHECK(song >= 0 && song < (int)d->set.songs.size(), VR_ERR_BAD_ARGUMENT,
+                 "vr_dataset_rows: song " + std::to_string(song) + " out of range (the dataset holds " + std::to_string(d->set.songs.size()) + ")");
+        *rows = d->set.songs[song].rows;
+    });
+}
+
+// The tables and the batch size are checked before the handle and the store, so that a caller's argument error is reported without a
+// device (as vr_separate_many does).
+int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                     float* X_mag, float* y_mag, int out_on_device) {
+    if (B <= 0) { g_err = "B must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!crops || !desc || !X_mag || !y_mag) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    NEED_DATASET(d);
+    static_assert(sizeof(vr_crop) == sizeof(vr::ResidentCrop) && sizeof(vr_aug) == sizeof(vr::AugDesc), "C ABI structs and their kernels.h twins");
+    return guard([&] {
+        h->m.dataset_batch_api(d->set, reinterpret_cast<const vr::ResidentCrop*>(crops), desc, reduction_weight, B, T, X_mag, y_mag,
+                               out_on_device != 0);
+    });
+}
+
 int vr_adam_step(vr_handle h, double lr, double b1, double b2, double eps, double grad_scale) {
     NEED(h);
     return guard([&] { h->m.adam_step_api(lr, b1, b2, eps, grad_scale); });

@@ -7,6 +7,8 @@
 //   np.abs, and the [T,2,bins] -> [2,bins,T] transpose      (dataset.py:63-64,116-117)
 // -- as ONE HBM-bound kernel over a whole batch.  The host keeps what is inherently host work: drawing
 // the numpy random numbers in the reference's order and seek-reading cropsize rows of the cached .npy.
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace vr {
@@ -35,15 +37,30 @@ __device__ __forceinline__ void aug_element(const float2* __restrict__ X, const 
 
 // grid: (ceil(T/32), ceil(bins/32), B*2); block (32, 8).  32x32 tile transposed through LDS so that both the
 // reads (bin-contiguous) and the writes (frame-contiguous) are coalesced.
-__global__ __launch_bounds__(256) void augment_kernel(const float2* __restrict__ X, const float2* __restrict__ Y,
-                                                      const float2* __restrict__ Xi, const float2* __restrict__ Yi,
-                                                      const AugDesc* __restrict__ desc, const float* __restrict__ rw, int T,
-                                                      int bins, float* __restrict__ Xmag, float* __restrict__ Ymag) {
+// Two forms, which differ only in where the four crops of sample b lie.  Dense (vr_augment_batch): X, Y, Xi, Yi are staged batches,
+// sample b at b * T * 2 * bins of each.  Resident (vr_dataset_batch): the first argument is a table with one AugCrops per sample,
+// every pointer already advanced to the sample's start row inside the [rows][2][bins] slab of its song (the mixup pair repeats the
+// first two when the sample has no partner); the other three pointer arguments are unused.
+template <bool kResident>
+__global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kResident, const AugCrops*, const float2*> __restrict__ X,
+                                                      const float2* __restrict__ Y, const float2* __restrict__ Xi,
+                                                      const float2* __restrict__ Yi, const AugDesc* __restrict__ desc,
+                                                      const float* __restrict__ rw, int T, int bins, float* __restrict__ Xmag,
+                                                      float* __restrict__ Ymag) {
     __shared__ float tx[32][33], ty[32][33];
     const int b = blockIdx.z >> 1, c = blockIdx.z & 1;
     const int t0 = blockIdx.x * 32, bin0 = blockIdx.y * 32;
     const AugDesc d = desc[b];
-    const long long base = (long long)b * T * 2 * bins;
+    const float2* __restrict__ Xc;
+    long long base;
+    if constexpr (kResident) {
+        const AugCrops s = X[b];                   // (b is uniform over the block: scalar loads)
+        Xc = s.X; Y = s.y; Xi = s.X_mix; Yi = s.y_mix;
+        base = 0;
+    } else {
+        Xc = X;
+        base = (long long)b * T * 2 * bins;
+    }
     const int bin = bin0 + threadIdx.x;
     for (int r = threadIdx.y; r < 32; r += 8) {
         const int t = t0 + r;
@@ -51,7 +68,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const float2* __restrict__
         if (t < T && bin < bins) {
             const float w = rw ? rw[bin] : 0.f;
             float2 x, y;
-            aug_element(X, Y, base, bins, t, c, bin, d.coef, d.flags & 1, d.flags & 2, d.flags & 4, w, x, y);
+            aug_element(Xc, Y, base, bins, t, c, bin, d.coef, d.flags & 1, d.flags & 2, d.flags & 4, w, x, y);
             if (d.flags & 8) {
                 float2 xi, yi;
                 aug_element(Xi, Yi, base, bins, t, c, bin, d.coef_mix, d.flags & 16, d.flags & 32, d.flags & 64, w, xi, yi);
@@ -80,7 +97,15 @@ __global__ __launch_bounds__(256) void augment_kernel(const float2* __restrict__
 void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDesc* desc, const float* rw,
                     int B, int T, int bins, float* Xmag, float* Ymag, hipStream_t st) {
     const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
-    VR_LAUNCH(augment_kernel, grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    VR_LAUNCH(augment_kernel<false>, grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
+                             float* Ymag, hipStream_t st) {
+    const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
+    const float2* const unused = nullptr;
+    VR_LAUNCH(augment_kernel<true>, grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
     VR_HIP(hipGetLastError());
 }
 

@@ -57,6 +57,11 @@ void launch_materialize(const Tensor& x, float* out, hipStream_t st);
 struct AugDesc { float coef, coef_mix, lam; int flags; };
 void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDesc* desc, const float* rw,
                     int B, int T, int bins, float* Xmag, float* Ymag, hipStream_t st);
+// the same kernel reading the crops where they lie in a resident store: one entry per sample, every pointer at the sample's
+// first row of its song's [rows][2][bins] slab (the mixup pair repeats the first two when the sample has no partner)
+struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
+void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
+                             float* Ymag, hipStream_t st);
 bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32
 void thin16_fill_tiling(ConvArgs& a, int TH);
 void thin16_launch_conv(const ConvArgs& a, const ConvShape& s, int TH, hipStream_t st);

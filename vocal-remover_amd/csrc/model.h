@@ -127,6 +127,28 @@ struct StreamState {
     std::deque<std::vector<int2>> crops_h;
 };
 
+// The resident training set (vr_dataset_*): every song's cached spectrogram pair copied once into two device slabs of
+// [rows][2][bins] complex64, the on-disk layout of spec_utils.SpectrogramCache.  The store owns its allocations and nothing of any
+// handle: it may outlive handles, and every handle on its device may cut batches from it (Model::dataset_batch_api).
+struct ResidentCrop { int song, mix_song; long long start, mix_start; };        // layout-compatible with vr_crop
+struct ResidentSet {
+    struct Song { float2* X; float2* y; long long rows; };
+    int device, bins;
+    std::vector<Song> songs;
+    long long bytes = 0;
+    ResidentSet(int device, int bins);
+    ~ResidentSet();
+    ResidentSet(const ResidentSet&) = delete;
+    ResidentSet& operator=(const ResidentSet&) = delete;
+    int add(const float* X, const float* y, long long rows);                    // -> song index
+private:
+    static constexpr size_t kPiece = size_t(8) << 20;                           // upload staging: two pinned pieces, never a whole song
+    hipStream_t up = nullptr;
+    char* stage[2] = {nullptr, nullptr};
+    hipEvent_t drained[2] = {nullptr, nullptr};
+    void upload(float2* dst, const float* src, size_t n_bytes);
+};
+
 class Model {
 public:
     Model(int device, int n_fft, int hop, int nout, int nout_lstm, bool is_complex = false);
@@ -205,7 +227,10 @@ public:
     void profile_begin();
     void augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
                      int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev);
+    void dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
+                           float* Xmag, float* ymag, bool out_on_dev);
     char* aug_buf = nullptr; size_t aug_cap = 0;         // staging of the training input pipeline
+    void aug_reserve(size_t need);
     bool train_wino = true;                              // vr_set_option("train_winograd"): Winograd kernels in train mode
     // vr_set_option("mfma_mode"): how the 3x3 stride-1 convs multiply.
     //   2 (round-3 default) = fp32 products as six bf16 products of three-way split operands on v_mfma_f32_32x32x16_bf16, fp32 accumulation

@@ -631,6 +631,15 @@ void Model::backward_api(const float* dmask, bool on_dev) {
     dropout_dev = nullptr;
 }
 
+void Model::aug_reserve(size_t need) {
+    if (need <= aug_cap) return;
+    VR_HIP(hipStreamSynchronize(stream));
+    if (aug_buf) VR_HIP(hipFree(aug_buf));
+    aug_buf = nullptr; aug_cap = 0;
+    VR_HIP(hipMalloc(reinterpret_cast<void**>(&aug_buf), need + (need >> 3)));
+    aug_cap = need + (need >> 3);
+}
+
 // Training input pipeline (lib/dataset.py:105-120 after the random draws and the file reads), see augment.hip.
 void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
                         int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev) {
@@ -642,13 +651,7 @@ void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const
     size_t need = up256(desc_b) + up256(rw_b);
     if (!in_on_dev) need += 4 * up256(crop_b);
     if (!out_on_dev) need += 2 * up256(out_b);
-    if (need > aug_cap) {
-        VR_HIP(hipStreamSynchronize(stream));
-        if (aug_buf) VR_HIP(hipFree(aug_buf));
-        aug_buf = nullptr; aug_cap = 0;
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&aug_buf), need + (need >> 3)));
-        aug_cap = need + (need >> 3);
-    }
+    aug_reserve(need);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = aug_buf + off; off += up256(bytes); return p; };
     AugDesc* dd = reinterpret_cast<AugDesc*>(take(desc_b));
@@ -668,6 +671,135 @@ void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(take(out_b));
     launch_augment(dev[0], dev[1], dev[2] ? dev[2] : dev[0], dev[3] ? dev[3] : dev[1], dd, rw ? drw : nullptr, B, T, bins, ox, oy,
                    stream);
+    if (!out_on_dev) {
+        VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
+        VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
+// ---- the resident training set (vr_dataset_*) ---------------------------------------------------------------------------------
+ResidentSet::ResidentSet(int device_, int bins_) : device(device_), bins(bins_) {
+    DeviceGuard dev_guard(device);
+    VR_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+}
+
+ResidentSet::~ResidentSet() {
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(device);
+    if (up) (void)hipStreamSynchronize(up);
+    for (Song& s : songs) { (void)hipFree(s.X); (void)hipFree(s.y); }
+    for (int i = 0; i < 2; ++i) {
+        if (stage[i]) (void)hipHostFree(stage[i]);
+        if (drained[i]) (void)hipEventDestroy(drained[i]);
+    }
+    if (up) (void)hipStreamDestroy(up);
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+// Host -> slab in pieces through two pinned buffers: the source may be a memory map of the cache file, so its pages are touched by a
+// plain memcpy (never pinned), and the copy of piece k overlaps the device transfer of piece k - 1.
+void ResidentSet::upload(float2* dst, const float* src, size_t n_bytes) {
+    for (int i = 0; i < 2; ++i) {
+        if (!stage[i]) VR_HIP(hipHostMalloc(reinterpret_cast<void**>(&stage[i]), kPiece, hipHostMallocDefault));
+        if (!drained[i]) VR_HIP(hipEventCreateWithFlags(&drained[i], hipEventDisableTiming));
+    }
+    const char* from = reinterpret_cast<const char*>(src);
+    char* to = reinterpret_cast<char*>(dst);
+    int k = 0;
+    for (size_t off = 0; off < n_bytes; off += kPiece, ++k) {
+        const size_t n = n_bytes - off < kPiece ? n_bytes - off : kPiece;
+        const int i = k & 1;
+        if (k >= 2) VR_HIP(hipEventSynchronize(drained[i]));
+        std::memcpy(stage[i], from + off, n);
+        VR_HIP(hipMemcpyAsync(to + off, stage[i], n, hipMemcpyHostToDevice, up));
+        VR_HIP(hipEventRecord(drained[i], up));
+    }
+    VR_HIP(hipStreamSynchronize(up));
+}
+
+int ResidentSet::add(const float* X, const float* y, long long rows) {
+    DeviceGuard dev_guard(device);
+    VR_CHECK(rows > 0, -2, "vr_dataset_add: rows must be positive");
+    const size_t slab = (size_t)rows * 2 * bins * sizeof(float2);
+    const float* src[2] = {X, y};
+    float2* dev[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (hipMalloc(reinterpret_cast<void**>(&dev[i]), slab) != hipSuccess) {
+            (void)hipGetLastError();                     // the failed allocation is reported here, not by the next launch
+            if (dev[0]) (void)hipFree(dev[0]);
+            throw Error(-4, "vr_dataset_add: hipMalloc of " + std::to_string(slab) + " bytes failed (song of " + std::to_string(rows) +
+                                " rows needs two of them; the store already holds " + std::to_string(bytes) + " bytes in " +
+                                std::to_string(songs.size()) + " songs)");
+        }
+    }
+    try {
+        for (int i = 0; i < 2; ++i) upload(dev[i], src[i], slab);
+    } catch (...) {
+        (void)hipFree(dev[0]); (void)hipFree(dev[1]);
+        throw;
+    }
+    songs.push_back(Song{dev[0], dev[1], rows});
+    bytes += 2 * (long long)slab;
+    return (int)songs.size() - 1;
+}
+
+// One batch cut from the store: the host checks every crop against its song (the kernel is never given a row it cannot read), then
+// pointer table, descriptors and reduction weight go to the handle's aug_buf in ONE copy and augment_kernel<true> reads the crops
+// where they lie.
+void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
+                              float* Xmag, float* ymag, bool out_on_dev) {
+    VR_CHECK(set.device == device, -2, "vr_dataset_batch: the handle is on device " + std::to_string(device) + ", the dataset on device " +
+                                           std::to_string(set.device));
+    VR_CHECK(T > 0, -2, "vr_dataset_batch: T must be positive");
+    const AugDesc* dh = static_cast<const AugDesc*>(desc);
+    const int bins = set.bins, n_songs = (int)set.songs.size();
+    std::vector<char> host;
+    auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t tab_b = (size_t)B * sizeof(AugCrops), desc_b = (size_t)B * sizeof(AugDesc), rw_b = (size_t)bins * sizeof(float);
+    const size_t out_b = (size_t)B * 2 * bins * T * sizeof(float);
+    const size_t head = up256(tab_b) + up256(desc_b) + (rw ? up256(rw_b) : 0);
+    host.resize(head);
+    AugCrops* tab = reinterpret_cast<AugCrops*>(host.data());
+    auto rows_at = [&](int b, const char* which, int song, long long start) -> size_t {
+        const std::string who = "vr_dataset_batch: sample " + std::to_string(b) + ": " + which;
+        VR_CHECK(song >= 0 && song < n_songs, -2, who + "song " + std::to_string(song) + " out of range (the dataset holds " +
+                                                     std::to_string(n_songs) + ")");
+        const long long rows = set.songs[song].rows;
+        VR_CHECK(start >= 0, -2, who + "start " + std::to_string(start) + " is negative");
+        VR_CHECK(T <= rows && start <= rows - T, -2, who + "rows [" + std::to_string(start) + ", " + std::to_string(start + T) + ") end past the " +
+                                                        std::to_string(rows) + " rows of song " + std::to_string(song));
+        return (size_t)start * 2 * bins;
+    };
+    for (int b = 0; b < B; ++b) {
+        const int flags = dh[b].flags;
+        VR_CHECK(!(flags & (1 | 16)) || rw, -2, "vr_dataset_batch: sample " + std::to_string(b) +
+                                                   ": vocal reduction flagged but no reduction_weight given");
+        const size_t o = rows_at(b, "", crops[b].song, crops[b].start);
+        const ResidentSet::Song& s = set.songs[crops[b].song];
+        tab[b] = AugCrops{s.X + o, s.y + o, s.X + o, s.y + o};
+        if (flags & 8) {
+            VR_CHECK(crops[b].mix_song >= 0, -2, "vr_dataset_batch: sample " + std::to_string(b) + ": mixup flagged but mix_song is " +
+                                                     std::to_string(crops[b].mix_song));
+            const size_t om = rows_at(b, "mixup partner: ", crops[b].mix_song, crops[b].mix_start);
+            const ResidentSet::Song& m = set.songs[crops[b].mix_song];
+            tab[b].X_mix = m.X + om;
+            tab[b].y_mix = m.y + om;
+        }
+    }
+    std::memcpy(host.data() + up256(tab_b), dh, desc_b);
+    if (rw) std::memcpy(host.data() + up256(tab_b) + up256(desc_b), rw, rw_b);
+
+    DeviceGuard dev_guard(device);
+    aug_reserve(head + (out_on_dev ? 0 : 2 * up256(out_b)));
+    VR_HIP(hipMemcpyAsync(aug_buf, host.data(), head, hipMemcpyHostToDevice, stream));
+    const AugCrops* dtab = reinterpret_cast<const AugCrops*>(aug_buf);
+    const AugDesc* dd = reinterpret_cast<const AugDesc*>(aug_buf + up256(tab_b));
+    const float* drw = rw ? reinterpret_cast<const float*>(aug_buf + up256(tab_b) + up256(desc_b)) : nullptr;
+    float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(aug_buf + head);
+    float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(aug_buf + head + up256(out_b));
+    launch_augment_resident(dtab, dd, drw, B, T, bins, ox, oy, stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));

@@ -183,6 +183,209 @@ class VocalRemoverValidationSet(object):
         return X_mag[0], y_mag[0]
 
 
+# ---- the same two sets resident in HBM --------------------------------------------------------------------------------
+# A training set of a few hundred songs fits an MI355X's 288 GB several times over: upload every cached spectrogram once
+# (native.Dataset, vr_dataset_add) and each batch is one vr_dataset_batch -- the kernel of vr_augment_batch reading the crops
+# where they lie.  Same random draws, same arithmetic: the batches are bit-identical to the file-backed classes'.
+def _check_capacity(what, need, max_bytes):
+    if max_bytes is not None and need > max_bytes:
+        raise MemoryError('%s needs %d bytes resident on the device (%.1f MiB), max_bytes allows %d'
+                          % (what, need, need / 2.0 ** 20, max_bytes))
+
+
+class _Resident(object):
+    """What the two resident sets share: the store on the model's device, filled at the first batch, and its lifetime."""
+    model = None
+    _store = None
+
+    def _handle(self):
+        if self.model is None:
+            raise RuntimeError('%s needs the model (its device holds the set and cuts the batches); no CPU fallback'
+                               % type(self).__name__)
+        return self.model._need_handle()
+
+    def _batch(self, h, crops, desc, rw, T):
+        store = self._store
+        B = len(desc)
+        dev = torch.device('cuda', h.device)
+        X_mag = torch.empty((B, 2, store.bins, T), dtype=torch.float32, device=dev)
+        y_mag = torch.empty((B, 2, store.bins, T), dtype=torch.float32, device=dev)
+        native.check(native.lib().vr_dataset_batch(
+            h.h, store.d, ctypes.cast(crops, ctypes.c_void_p), ctypes.cast(desc, ctypes.c_void_p),
+            native.np_ptr(rw) if rw is not None else None, B, T,
+            ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
+        return X_mag, y_mag
+
+    @property
+    def nbytes(self):
+        """Bytes of the set on the device: what the upload will take before the first batch, what the store holds after it."""
+        return self._store.info()[1] if self._store is not None else self._need
+
+    def close(self):
+        """Free the device copy (the next batch uploads again)."""
+        if self._store is not None:
+            self._store.close()
+            self._store = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __getitem__(self, idx):
+        X_mag, y_mag = self.batch([idx])
+        return X_mag[0], y_mag[0]
+
+
+class ResidentTrainingSet(_Resident):
+    """VocalRemoverTrainingSet with the cached spectrograms resident on the model's device.  Same constructor plus `max_bytes`
+    (MemoryError at construction when the distinct songs of the list need more); same numpy draws in the same order, so from one
+    numpy seed `batch(indices)` returns what VocalRemoverTrainingSet.batch returns, bit for bit, and leaves numpy's generator
+    where that leaves it.  The first batch uploads every distinct (X, y) pair of the list once, through a memory map of the .npy
+    files; `model` may be swapped for another model on the same device at any time (the store belongs to the set, not to a handle)."""
+
+    def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None):
+        self.training_set = training_set
+        self.cropsize = cropsize
+        self.reduction_rate = reduction_rate
+        self.reduction_weight = None if reduction_weight is None else \
+            np.ascontiguousarray(np.asarray(reduction_weight, np.float32).reshape(-1))
+        self.mixup_rate = mixup_rate
+        self.mixup_alpha = mixup_alpha
+        self.model = model
+        self.max_bytes = max_bytes
+        self._shape = {}                       # path -> shape in the .npy header (the file-backed class reads it at every draw)
+        self._song = {}                        # (X path, y path) -> index in the store, in first-seen order
+        need = 0
+        for X_path, y_path, _ in training_set:
+            if (X_path, y_path) in self._song:
+                continue
+            self._song[(X_path, y_path)] = len(self._song)
+            for path in (X_path, y_path):
+                shape, dtype, _ = _npy_header(path)
+                self._shape[path] = tuple(int(n) for n in shape)
+                need += int(np.prod(shape)) * dtype.itemsize
+        self._need = need
+        _check_capacity('ResidentTrainingSet: %d songs' % len(self._song), need, max_bytes)
+
+    __len__ = VocalRemoverTrainingSet.__len__
+    _draw_aug = VocalRemoverTrainingSet._draw_aug
+    plan = VocalRemoverTrainingSet.plan          # the draws themselves: one statement of them for both classes
+
+    def read_npy_shape(self, path):
+        return self._shape[path]
+
+    def _upload(self, device):
+        bins = self._shape[self.training_set[0][0]][2]
+        store = native.Dataset(device, bins)
+        try:
+            for (X_path, y_path), song in self._song.items():
+                pair = []
+                for path in (X_path, y_path):
+                    a = np.load(path, mmap_mode='r')
+                    if a.dtype != np.complex64 or tuple(a.shape[1:]) != (2, bins):
+                        raise ValueError('%s: expected complex64 rows of shape %s, found %s %s' % (path, (2, bins), a.dtype, a.shape[1:]))
+                    pair.append(a)
+                if pair[0].shape[0] != pair[1].shape[0]:
+                    raise ValueError('%s, %s: %d and %d rows, a resident pair has as many of both'
+                                     % (X_path, y_path, pair[0].shape[0], pair[1].shape[0]))
+                assert store.add(pair[0], pair[1]) == song
+        except Exception:
+            store.close()
+            raise
+        self._store = store
+
+    def batch(self, indices):
+        h = self._handle()
+        if self._store is None:
+            self._upload(h.device)
+        plans = [self.plan(i) for i in indices]
+        B = len(plans)
+        crops, desc = (native.Crop * B)(), (_Aug * B)()
+        need_rw = False
+        for b, p in enumerate(plans):
+            flags, coef_mix, lam, mix_song, mix_start = p['flags'], 1.0, 1.0, -1, 0
+            if p['mix'] is not None:
+                m = p['mix']
+                flags |= 8 | (m['flags'] << 4)
+                coef_mix, lam, mix_song, mix_start = m['coef'], m['lam'], self._song[m['paths']], m['start']
+            need_rw = need_rw or bool(flags & (1 | 16))
+            crops[b] = native.Crop(self._song[p['paths']], mix_song, p['start'], mix_start)
+            desc[b] = _Aug(p['coef'], coef_mix, lam, flags)
+        if need_rw and self.reduction_weight is None:
+            raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
+        return self._batch(h, crops, desc, self.reduction_weight, self.cropsize)
+
+
+def _npz_member_shape(path, key):
+    import zipfile
+    with zipfile.ZipFile(path) as z, z.open(key + '.npy') as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        return tuple(int(n) for n in read(f)[0])
+
+
+class ResidentValidationSet(_Resident):
+    """VocalRemoverValidationSet with the patches resident on the model's device: each distinct .npz of make_validation_set is
+    uploaded once as a song of [T, 2, bins] rows, and a batch is the device call of ResidentTrainingSet with start 0 and no
+    augmentation flags -- bit-identical to VocalRemoverValidationSet.batch."""
+
+    def __init__(self, patch_list, model=None, max_bytes=None):
+        self.patch_list = patch_list
+        self.model = model
+        self.max_bytes = max_bytes
+        self._song = {}
+        self._T = None
+        need = 0
+        for path in patch_list:
+            if path in self._song:
+                continue
+            self._song[path] = len(self._song)
+            for key in ('X', 'y'):
+                shape = _npz_member_shape(path, key)          # [2, bins, T]
+                need += int(np.prod(shape)) * np.dtype(np.complex64).itemsize
+        self._need = need
+        _check_capacity('ResidentValidationSet: %d patches' % len(self._song), need, max_bytes)
+
+    def __len__(self):
+        return len(self.patch_list)
+
+    def _upload(self, device):
+        store = None
+        try:
+            for path, song in self._song.items():
+                with np.load(path) as data:
+                    X = np.ascontiguousarray(data['X'].astype(np.complex64, copy=False).transpose(2, 0, 1))   # -> [T, 2, bins]
+                    y = np.ascontiguousarray(data['y'].astype(np.complex64, copy=False).transpose(2, 0, 1))
+                if store is None:
+                    store, self._T = native.Dataset(device, X.shape[2]), X.shape[0]
+                if X.shape != (self._T, 2, store.bins) or y.shape != X.shape:
+                    raise ValueError('%s: patches of one set have one shape, found X %s and y %s after %s'
+                                     % (path, X.shape, y.shape, (self._T, 2, store.bins)))
+                assert store.add(X, y) == song
+        except Exception:
+            if store is not None:
+                store.close()
+            raise
+        self._store = store
+
+    def batch(self, indices):
+        h = self._handle()
+        if self._store is None:
+            self._upload(h.device)
+        B = len(indices)
+        crops = (native.Crop * B)(*[native.Crop(self._song[self.patch_list[i]], -1, 0, 0) for i in indices])
+        desc = (_Aug * B)(*[_Aug(1.0, 1.0, 1.0, 0) for _ in range(B)])
+        return self._batch(h, crops, desc, None, self._T)
+
+
 class DeviceLoader(object):
     """Iterable stand-in for torch.utils.data.DataLoader(dataset, batch_size, shuffle) (train.py:242-247):
     yields (X_batch, y_batch) device tensors produced by one vr_augment_batch call per batch."""

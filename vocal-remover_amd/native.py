@@ -70,6 +70,13 @@ _SIGNATURES = {
     'vr_augment_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    'vr_dataset_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_dataset_destroy': (ctypes.c_int, [ctypes.c_void_p]),
+    'vr_dataset_add': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]),
+    'vr_dataset_info': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), c_i64p]),
+    'vr_dataset_rows': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64p]),
+    'vr_dataset_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'vr_validate_step': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_float)]),
     'vr_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
@@ -171,6 +178,52 @@ def stream_plan(n_fft, hop, cropsize, offset, tta, samples_in, flushed):
     check(lib().vr_stream_plan(int(n_fft), int(hop), int(cropsize), int(offset), 1 if tta else 0, int(samples_in), 1 if flushed else 0,
                                ctypes.byref(fr), crops, ctypes.byref(out)))
     return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
+
+
+class Crop(ctypes.Structure):               # include/vr_mi355.h: vr_crop
+    _fields_ = [('song', ctypes.c_int), ('mix_song', ctypes.c_int), ('start', ctypes.c_int64), ('mix_start', ctypes.c_int64)]
+
+
+class Dataset:
+    """Owns one vr_dataset: songs resident on one GPU, independent of any Handle."""
+
+    def __init__(self, device, bins):
+        self._d = ctypes.c_void_p()
+        check(lib().vr_dataset_create(int(device), int(bins), ctypes.byref(self._d)))
+        self.device, self.bins = int(device), int(bins)
+
+    def close(self):
+        if getattr(self, '_d', None) and self._d.value:
+            lib().vr_dataset_destroy(self._d)
+            self._d = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def d(self):
+        if not self._d.value:
+            raise VRError('dataset is closed')
+        return self._d
+
+    def add(self, X, y):
+        """One song: X, y complex64 [rows, 2, bins], C-contiguous (a np.memmap of the cache file will do) -> its index."""
+        song = ctypes.c_int()
+        check(lib().vr_dataset_add(self.d, np_ptr(X), np_ptr(y), int(X.shape[0]), ctypes.byref(song)))
+        return int(song.value)
+
+    def info(self):
+        n, b = ctypes.c_int(), ctypes.c_int64()
+        check(lib().vr_dataset_info(self.d, ctypes.byref(n), ctypes.byref(b)))
+        return int(n.value), int(b.value)
+
+    def rows(self, song):
+        r = ctypes.c_int64()
+        check(lib().vr_dataset_rows(self.d, int(song), ctypes.byref(r)))
+        return int(r.value)
 
 
 class Handle:
