@@ -334,6 +334,48 @@ int vr_broadcast_params(vr_handle h, int root, int with_optimizer);
 int vr_resample(int device, const float* x, int channels, int64_t n_in, int sr_in, int sr_out, float* y, int64_t n_out);
 int vr_xcorr_argmax(int device, const float* a, int64_t na, const float* b, int64_t nb, int64_t* argmax_out);
 
+/* ---- the streamed resampler: vr_resample on blocks, with bounded state ----------------------------------------------
+ * A session takes audio x [channels][n] at sr_in in pushes of any sizes >= 1 followed by one flush.  CONTRACT: the concatenation of
+ * everything it returned IS what vr_resample returns for the whole input -- bit for bit, the same length ceil(n_in * sr_out / sr_in),
+ * the same zero samples behind resampy's int(n_in * ratio) -- however the input was split.  It is exact because output sample t of the
+ * kernel depends on t alone, reads at most K = 8193 / index_step inputs on either side of n(t) = floor(t / ratio) and sums them in a
+ * fixed order: the session runs the same kernel source on global t and n.  A sample is FINAL, and returned, once input n(t) + K has
+ * arrived (from then on the right-hand clamp n_in - n - 1 is inactive whatever n_in turns out to be); the flush computes the rest with
+ * the clamp active and appends the zero tail.
+ * vr_resampler_push returns every sample that is final: *n_out per channel, possibly 0, at y [channels][capacity] (channel pitch =
+ * capacity).  A capacity below what the call returns is VR_ERR_BAD_ARGUMENT, reported before anything is consumed; vr_last_error()
+ * names the size needed (vr_resampler_plan computes it: samples_out after minus before).  x, y: host or device pointers, as flagged.
+ * vr_resampler_flush ends the session.  sr_in == sr_out is a pass-through session: it returns its input, on the same schedule as any
+ * other pair (K = 16), so that a caller's capacity arithmetic has no special case.
+ * vr_resampler_push_many: session k receives n_in[k] >= 0 samples and, where flush[k] != 0, its input ends there (flush == NULL: none
+ * ends); n_in[k] == 0 without flush leaves session k untouched.  ONE kernel launch serves all sessions -- the launch table carries each
+ * session's ratio and filter table, so the sessions may have different rate pairs -- and session k returns exactly what
+ * vr_resampler_push (then vr_resampler_flush) on it alone would return.
+ * vr_resampler_info: lookahead_samples = K + 1, the input that must have arrived before the first output sample; state_bytes = what a
+ * session carries from push to push: the last 2K + 2 input samples per channel, the filter table and its differences (2 x 8193
+ * doubles, computed once at open), two 64-bit counters.  It depends on (channels, sr_in, sr_out) and not on how much audio has passed.
+ * Besides that a session holds staging for one push: two window buffers of history + the largest push seen (used in turn) and, for
+ * host destinations, one output buffer; they grow when a larger push arrives and are otherwise reused.  A session owns its HIP stream
+ * and its device memory; every call returns when its outputs are complete.
+ * vr_resampler_plan (host only, no session, no GPU) is the schedule the executor follows, from the very expressions of vr_resample:
+ * ratio = (double)sr_out / sr_in; n(t) = (long long)((double)t * (1.0 / ratio)); samples_out = the number of t with n(t) + K <
+ * samples_in, or, flushed, ceil(samples_in * ratio).
+ * Errors (VR_ERR_BAD_ARGUMENT, before the device is touched): non-positive rates or channels, more than 65535 channels or sessions
+ * in one call, sr_out / sr_in below 1 / 512, n < 0,
+ * push or flush after a flush, a flush with no sample received (vr_resample refuses n_in <= 0 too); in vr_resampler_push_many also a
+ * session listed twice, sessions on different devices or with different channel counts, vr_last_error() starting "resampler <k>: ".
+ * A call that fails half way (a HIP error) leaves its sessions unusable: close them. */
+typedef struct vr_resampler_s* vr_resampler;
+int vr_resampler_open(int device, int channels, int sr_in, int sr_out, vr_resampler* out);
+int vr_resampler_push(vr_resampler r, const float* x, int x_on_device, int64_t n, float* y, int y_on_device, int64_t capacity,
+                      int64_t* n_out);
+int vr_resampler_flush(vr_resampler r, float* y, int y_on_device, int64_t capacity, int64_t* n_out);
+int vr_resampler_push_many(int n, const vr_resampler* r, const float* const* x, int on_device, const int64_t* n_in, const int* flush,
+                           float* const* y, int y_on_device, const int64_t* capacity, int64_t* n_out);
+int vr_resampler_info(vr_resampler r, int64_t* lookahead_samples, int64_t* state_bytes);
+int vr_resampler_close(vr_resampler r);
+int vr_resampler_plan(int sr_in, int sr_out, int64_t samples_in, int flushed, int64_t* samples_out);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------------------------- */
 /* Bracket subsequent calls: every kernel launch is timed with HIP events on the stream it is launched on (the executor runs
  * every kernel on ONE stream while profiling); conv_* aggregate the convolution launches.

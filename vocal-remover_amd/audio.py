@@ -7,7 +7,8 @@
 Decoding covers RIFF/WAVE (PCM 8/16/24/32 bit, IEEE float 32/64, WAVE_FORMAT_EXTENSIBLE); the reference also accepts
 .m4a/.mp3/.mp4/.flac through audioread/ffmpeg, which is outside this package: those raise.  Resampling runs on the GPU
 (vr_resample: resampy's 'kaiser_fast' band-limited interpolation restated -- resampy is not vendored in the reference,
-parity unpinned).  `write` produces 16-bit PCM, soundfile's default subtype for .wav.
+parity unpinned); `StreamResampler` / `resample_push_many` (vr_resampler_*) are the same resampler on blocks, with bounded state and
+the same bits.  `write` produces 16-bit PCM, soundfile's default subtype for .wav.
 """
 import os
 import struct
@@ -187,6 +188,159 @@ def resample(y, orig_sr, target_sr, res_type='kaiser_fast'):
     native.check(native.lib().vr_resample(_device(), native.np_ptr(x), x.shape[0], x.shape[1], int(orig_sr), int(target_sr),
                                           native.np_ptr(out), n_out))
     return out[0] if mono else out
+
+
+class StreamResampler(object):
+    """resample() on blocks with bounded state (vr_resampler_*): push(x [channels, n]) -> every output sample that has become final
+    (possibly none), flush() -> the rest; the concatenation IS resample(whole input, orig_sr, target_sr), bit for bit, however the input
+    was split.  numpy in, numpy out; a torch cuda tensor in, a cuda tensor out (it can go into inference.Stream.push as it is).  A
+    one-channel session also takes and returns 1-D blocks.  Use as a context manager or close()."""
+
+    def __init__(self, orig_sr, target_sr, channels=2, device=None):
+        self._r = native.ctypes.c_void_p()
+        self._rates = (int(orig_sr), int(target_sr))
+        self.channels = int(channels)
+        dev = _device() if device is None else getattr(device, 'index', device)
+        self.device = int(0 if dev is None else dev)
+        native.check(native.lib().vr_resampler_open(self.device, self.channels, self._rates[0], self._rates[1], native.ctypes.byref(self._r)))
+        self._samples = 0
+        self._dev_out = False
+        info = [native.ctypes.c_int64() for _ in range(2)]
+        native.check(native.lib().vr_resampler_info(self._r, *[native.ctypes.byref(i) for i in info]))
+        self.lookahead_samples, self.state_bytes = [int(i.value) for i in info]
+
+    def _handle(self):
+        if not self._r.value:
+            raise native.VRError('resampler is closed')
+        return self._r
+
+    def _need(self, n, flushed):
+        return native.resampler_plan(self._rates[0], self._rates[1], self._samples + n, flushed) - \
+            native.resampler_plan(self._rates[0], self._rates[1], self._samples, False)
+
+    def _block(self, x, who=''):
+        """-> (block [channels, n] as a contiguous float32 array or cuda tensor, or None; on the device; given as 1-D)"""
+        torch = _torch()
+        if x is None:
+            return None, self._dev_out, False
+        on_dev = torch is not None and torch.is_tensor(x) and x.is_cuda
+        if on_dev:
+            x = x.detach().to(torch.float32)
+        else:
+            x = np.asarray(x.detach().cpu().numpy() if torch is not None and torch.is_tensor(x) else x, dtype=np.float32)
+        flat = x.ndim == 1
+        if flat:
+            x = x[None]
+        if x.ndim != 2 or x.shape[0] != self.channels or (flat and self.channels != 1):
+            raise ValueError('%sblock must be [%d, n]' % (who, self.channels))
+        return (x.contiguous() if on_dev else np.ascontiguousarray(x)), on_dev, flat
+
+    def _out(self, cap, on_dev):
+        if on_dev:
+            torch = _torch()
+            dev = torch.device('cuda', self.device)
+            y = torch.empty((self.channels, cap), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            return y, y.data_ptr()
+        y = np.empty((self.channels, cap), dtype=np.float32)
+        return y, y.ctypes.data
+
+    def _call(self, x, flush):
+        r = self._handle()
+        x, on_dev, flat = self._block(x)
+        if on_dev and x is not None and x.device.index != self.device:
+            raise ValueError('block is on %s, the resampler on cuda:%d' % (x.device, self.device))
+        n = 0 if x is None else int(x.shape[1])
+        y, yp = self._out(max(self._need(n, flush), 1), on_dev)     # (a flush with no sample received raises here)
+        got = native.ctypes.c_int64()
+        dev = 1 if on_dev else 0
+        if flush:
+            native.check(native.lib().vr_resampler_flush(r, yp, dev, y.shape[1], native.ctypes.byref(got)))
+        else:
+            xp = (x.data_ptr() if on_dev else x.ctypes.data) if n else None
+            native.check(native.lib().vr_resampler_push(r, xp, dev, n, yp, dev, y.shape[1], native.ctypes.byref(got)))
+        self._samples += n
+        self._dev_out = on_dev
+        self._flat = flat if x is not None else getattr(self, '_flat', False)
+        y = y[:, :int(got.value)]
+        return y[0] if self._flat else y
+
+    def push(self, x):
+        return self._call(x, False)
+
+    def flush(self):
+        return self._call(None, True)
+
+    def close(self):
+        if getattr(self, '_r', None) is not None and self._r.value:
+            native.lib().vr_resampler_close(self._r)
+            self._r = native.ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _torch():
+    try:
+        import torch
+        return torch
+    except ImportError:              # pragma: no cover
+        return None
+
+
+def resample_push_many(resamplers, blocks, flush=False):
+    """One vr_resampler_push_many call -- one kernel launch for all sessions: resamplers[k] receives blocks[k] ([channels, n], or None
+    for nothing) and, where flush (a bool, or one per session) says so, its input ends there.  Returns what push (then flush) returns
+    for each session alone.  The sessions may have different rate pairs; they share a device and a channel count.  Either every block
+    is a numpy array (numpy out) or every block is a cuda tensor (cuda out)."""
+    ct = native.ctypes
+    rs, blocks = list(resamplers), list(blocks)
+    N = len(rs)
+    if not N:
+        raise ValueError('resample_push_many needs at least one resampler')
+    if len(blocks) != N:
+        raise ValueError('resample_push_many: %d resamplers but %d blocks' % (N, len(blocks)))
+    fl = [bool(flush)] * N if isinstance(flush, (bool, np.bool_)) else [bool(f) for f in flush]
+    if len(fl) != N:
+        raise ValueError('resample_push_many: %d resamplers but %d flush flags' % (N, len(fl)))
+    prepared = [r._block(b, 'resampler %d: ' % k) for k, (r, b) in enumerate(zip(rs, blocks))]
+    given = [on for (x, on, _) in prepared if x is not None]
+    if any(given) and not all(given):
+        raise ValueError('resample_push_many: either every block is a cuda tensor or none is')
+    on_dev = all(given) if given else bool(rs[0]._dev_out)
+    xs = [x for x, _, _ in prepared]
+    for k, (r, x) in enumerate(zip(rs, xs)):
+        if on_dev and x is not None and x.device.index != r.device:
+            raise ValueError('resampler %d: block is on %s, the resampler on cuda:%d' % (k, x.device, r.device))
+    lens = [0 if x is None else int(x.shape[1]) for x in xs]
+    handles = [r._handle().value for r in rs]
+    caps = [max(r._need(n, f), 1) for r, n, f in zip(rs, lens, fl)]
+    outs = [r._out(c, on_dev) for r, c in zip(rs, caps)]
+    addr = lambda x: (x.data_ptr() if on_dev else x.ctypes.data)
+    got = (ct.c_int64 * N)()
+    native.check(native.lib().vr_resampler_push_many(
+        N, (ct.c_void_p * N)(*handles), (ct.c_void_p * N)(*[addr(x) if n else None for x, n in zip(xs, lens)]), 1 if on_dev else 0,
+        (ct.c_int64 * N)(*lens), (ct.c_int * N)(*[1 if f else 0 for f in fl]), (ct.c_void_p * N)(*[p for _, p in outs]),
+        1 if on_dev else 0, (ct.c_int64 * N)(*caps), got))
+    res = []
+    for r, (x, _, flat), n, f, (y, _), g in zip(rs, prepared, lens, fl, outs, got):
+        if n or f:
+            r._samples += n
+            r._dev_out = on_dev
+            if x is not None:
+                r._flat = flat
+        y = y[:, :int(g)]
+        res.append(y[0] if getattr(r, '_flat', False) else y)
+    return res
 
 
 def load(path, sr=22050, mono=True, dtype=np.float32, res_type='kaiser_fast'):

@@ -9,6 +9,13 @@
 namespace vr {
 void resample_api(int device, const float* x, int channels, long long n_in, int sr_in, int sr_out, float* y, long long n_out);
 void xcorr_argmax_api(int device, const float* a, long long na, const float* b, long long nb, long long* argmax_out);
+struct Resampler;
+long long resampler_plan(int sr_in, int sr_out, long long samples_in, bool flushed);
+Resampler* resampler_open(int device, int channels, int sr_in, int sr_out);
+void resampler_close(Resampler* r);
+void resampler_info(const Resampler* r, long long* lookahead, long long* state_bytes);
+void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool x_on_dev, const long long* n, const int* flush,
+                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many);
 }  // namespace vr
 
 struct vr_model {
@@ -538,6 +545,88 @@ int vr_resample(int device, const float* x, int channels, int64_t n_in, int sr_i
         VR_CHECK(x && y, VR_ERR_BAD_ARGUMENT, "null argument");
         need_device(device);
         vr::resample_api(device, x, channels, n_in, sr_in, sr_out, y, n_out);
+    });
+}
+
+// ---- the streamed resampler --------------------------------------------------------------------------------------------------
+struct vr_resampler_s {
+    vr::Resampler* r;
+};
+
+#define NEED_RESAMPLER(r)                                        \
+    if (!(r) || !(r)->r) {                                       \
+        g_err = "null resampler";                                \
+        return VR_ERR_BAD_ARGUMENT;                              \
+    }
+
+int vr_resampler_plan(int sr_in, int sr_out, int64_t samples_in, int flushed, int64_t* samples_out) {
+    return guard([&] {
+        const long long out = vr::resampler_plan(sr_in, sr_out, samples_in, flushed != 0);
+        if (samples_out) *samples_out = out;
+    });
+}
+
+int vr_resampler_open(int device, int channels, int sr_in, int sr_out, vr_resampler* out) {
+    if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
+    *out = nullptr;
+    return guard([&] {
+        VR_CHECK(channels > 0 && channels <= 65535, VR_ERR_BAD_ARGUMENT, "resampler: channels must be positive (and at most 65535, one grid row each)");
+        vr::resampler_plan(sr_in, sr_out, 0, false);                  // the rate checks, before the device is looked at
+        need_device(device);
+        *out = new vr_resampler_s{vr::resampler_open(device, channels, sr_in, sr_out)};
+    });
+}
+
+static int resampler_push_one(vr_resampler r, const float* x, int x_on_device, int64_t n, int flush, float* y, int y_on_device,
+                              int64_t capacity, int64_t* n_out) {
+    NEED_RESAMPLER(r);
+    return guard([&] {
+        const long long len = n, cap = capacity;
+        long long got = 0;
+        vr::resampler_push_many(1, &r->r, &x, x_on_device != 0, &len, &flush, &y, y_on_device != 0, &cap, &got, false);
+        if (n_out) *n_out = got;
+    });
+}
+
+int vr_resampler_push(vr_resampler r, const float* x, int x_on_device, int64_t n, float* y, int y_on_device, int64_t capacity,
+                      int64_t* n_out) {
+    return resampler_push_one(r, x, x_on_device, n, 0, y, y_on_device, capacity, n_out);
+}
+
+int vr_resampler_flush(vr_resampler r, float* y, int y_on_device, int64_t capacity, int64_t* n_out) {
+    return resampler_push_one(r, nullptr, 0, 0, 1, y, y_on_device, capacity, n_out);
+}
+
+int vr_resampler_push_many(int n, const vr_resampler* r, const float* const* x, int on_device, const int64_t* n_in, const int* flush,
+                           float* const* y, int y_on_device, const int64_t* capacity, int64_t* n_out) {
+    if (n <= 0) { g_err = "n must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!r || !n_in) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        std::vector<vr::Resampler*> rs((size_t)n);
+        std::vector<long long> len(n_in, n_in + n), cap, got((size_t)n, 0);
+        if (capacity) cap.assign(capacity, capacity + n);
+        for (int k = 0; k < n; ++k) rs[k] = r[k] ? r[k]->r : nullptr;
+        vr::resampler_push_many(n, rs.data(), x, on_device != 0, len.data(), flush, y, y_on_device != 0, capacity ? cap.data() : nullptr,
+                                got.data(), true);
+        if (n_out) for (int k = 0; k < n; ++k) n_out[k] = got[k];
+    });
+}
+
+int vr_resampler_info(vr_resampler r, int64_t* lookahead_samples, int64_t* state_bytes) {
+    NEED_RESAMPLER(r);
+    return guard([&] {
+        long long a = 0, b = 0;
+        vr::resampler_info(r->r, &a, &b);
+        if (lookahead_samples) *lookahead_samples = a;
+        if (state_bytes) *state_bytes = b;
+    });
+}
+
+int vr_resampler_close(vr_resampler r) {
+    if (!r) { g_err = "null resampler"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        if (r->r) vr::resampler_close(r->r);
+        delete r;
     });
 }
 

@@ -6,30 +6,83 @@
 //                     sinc interpolation with a Kaiser-windowed filter table -- 'kaiser_fast' = 16 zero crossings,
 //                     2^9 table samples per crossing, roll-off 0.85, Kaiser beta 8.555504641634386 -- linear interpolation
 //                     between table entries, left wing + right wing per output sample (resampy/interpn.py).
+//   vr_resampler_*    the same resampler on blocks: a session with bounded state whose output, concatenated, is vr_resample's bit
+//                     for bit; one launch serves any number of sessions.
 //   vr_xcorr_argmax   argmax of np.correlate(a, b, 'full') in spec_utils.align_wave_head_and_tail
 //                     (lib/spec_utils.py:107-108): one workgroup per lag.
-// Both are tiny next to the network; they exist so that the whole of inference.py / cache_or_load stays on the device
+// All are tiny next to the network; they exist so that the whole of inference.py / cache_or_load stays on the device
 // path and needs neither librosa nor resampy.
+#include <climits>
+#include <algorithm>
 #include <cmath>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.h"
 
 namespace vr {
 
-// y[c][t] = sum over both filter wings (resampy.interpn._resample_loop), fp32 accumulator like the float32 output array
-__global__ void resample_kernel(const float* __restrict__ x, long long n_in, float* __restrict__ y, long long n_out,
-                                const double* __restrict__ win, const double* __restrict__ delta, int nwin, int precision,
-                                double sample_ratio) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+// One session's share of a streamed launch (resample_kernel<true>, blockIdx.z selects the entry).  Every position is a global one: input
+// sample g of the session lies at x[c * x_pitch + (g - g0)], output sample t0 + j goes to y[c * y_pitch + j].
+struct ResampleSeg {
+    const float* x;          // the window: [channels][x_pitch]
+    long long x_pitch;
+    long long g0;            // global index of the window's first sample
+    long long n_in;          // samples received so far: the right-hand clamp.  Before the flush it is inactive for every sample launched
+                             // (the host launches t only once input n(t) + K has arrived), at the flush it is the offline call's n_in
+    long long t0;            // first output index of this launch
+    long long count;         // output samples of this launch; a workgroup past it leaves at once
+    long long t_core;        // outputs at or beyond it are librosa's zero tail (fix_length); LLONG_MAX before the flush
+    float* y;
+    long long y_pitch;
+    const double* win;       // the session's filter table and its first differences
+    const double* delta;
+    double ratio;
+    int nwin, precision;
+};
+
+// y[c][t] = sum over both filter wings (resampy.interpn._resample_loop), fp32 accumulator like the float32 output array.
+// resample_kernel<false> is the offline kernel of vr_resample, argument for argument.  resample_kernel<true> takes a table of ResampleSeg
+// in place of the first pointer (the other arguments are unused) and computes the same taps from global positions: output sample t
+// depends on t alone, so a sample whose right wing lies inside the samples received is already the offline call's sample.
+template <bool kStream>
+__global__ void resample_kernel(std::conditional_t<kStream, const ResampleSeg*, const float*> __restrict__ x, long long n_in,
+                                float* __restrict__ y, long long n_out, const double* __restrict__ win, const double* __restrict__ delta,
+                                int nwin, int precision, double sample_ratio) {
+    long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int c = blockIdx.y;
-    if (t >= n_out) return;
-    const float* xc = x + (long long)c * n_in;
+    const float* xc;
+    float* yo;
+    long long g0 = 0;
+    if constexpr (kStream) {
+        const ResampleSeg& s = x[blockIdx.z];
+        if (t >= s.count) return;
+        yo = s.y + (long long)c * s.y_pitch + t;
+        t += s.t0;
+        if (t >= s.t_core) {
+            *yo = 0.f;
+            return;
+        }
+        xc = s.x + (long long)c * s.x_pitch;
+        g0 = s.g0;
+        n_in = s.n_in;
+        win = s.win;
+        delta = s.delta;
+        nwin = s.nwin;
+        precision = s.precision;
+        sample_ratio = s.ratio;
+    } else {
+        if (t >= n_out) return;
+        xc = x + (long long)c * n_in;
+        yo = y + (long long)c * n_out + t;
+    }
     const double scale = sample_ratio < 1.0 ? sample_ratio : 1.0;
     const double time_increment = 1.0 / sample_ratio;
     const int index_step = (int)(scale * precision);
     const double time_register = (double)t * time_increment;
     const long long n = (long long)time_register;
+    const long long nw = n - g0;                        // n inside the window
     double frac = scale * (time_register - (double)n);
     double index_frac = frac * precision;
     int offset = (int)index_frac;
@@ -40,7 +93,7 @@ __global__ void resample_kernel(const float* __restrict__ x, long long n_in, flo
     for (long long i = 0; i < i_max; ++i) {
         const int k = offset + (int)i * index_step;
         const double w = win[k] + eta * delta[k];
-        acc = (float)((double)acc + w * (double)xc[n - i]);
+        acc = (float)((double)acc + w * (double)xc[nw - i]);
     }
     frac = scale - frac;
     index_frac = frac * precision;
@@ -51,9 +104,9 @@ __global__ void resample_kernel(const float* __restrict__ x, long long n_in, flo
     for (long long k2 = 0; k2 < k_max; ++k2) {
         const int k = offset + (int)k2 * index_step;
         const double w = win[k] + eta * delta[k];
-        acc = (float)((double)acc + w * (double)xc[n + k2 + 1]);
+        acc = (float)((double)acc + w * (double)xc[nw + k2 + 1]);
     }
-    y[(long long)c * n_out + t] = acc;
+    *yo = acc;
 }
 
 // resampy.filters.sinc_window(num_zeros, precision, kaiser(beta), rolloff): the right half of the windowed sinc
@@ -100,7 +153,7 @@ void resample_api(int device, const float* x, int channels, long long n_in, int 
     if (n_run > 0) {
         float* ytmp = dy;
         // rows of dy are n_out long; the kernel writes the first n_run samples of each
-        hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_run + 255) / 256), channels), dim3(256), 0, 0, dx, n_in, ytmp, n_out,
+        hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)((n_run + 255) / 256), channels), dim3(256), 0, 0, dx, n_in, ytmp, n_out,
                            dw, dd, (int)win.size(), 1 << 9, ratio);
         VR_HIP(hipGetLastError());
     }
@@ -110,6 +163,228 @@ void resample_api(int device, const float* x, int channels, long long n_in, int 
         for (int c = 0; c < channels; ++c)
             VR_HIP(hipMemset(dy + (size_t)c * n_out + n_run, 0, (size_t)(n_out - n_run) * sizeof(float)));
     VR_HIP(hipMemcpy(y, dy, (size_t)channels * n_out * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+// ---- the streamed resampler (vr_resampler_*) -------------------------------------------------------------------------------------
+// The schedule, from the very expressions of resample_api and the kernel: ratio = (double)sr_out / sr_in, n(t) = (long long)((double)t *
+// (1.0 / ratio)), K = nwin / index_step (no wing reaches further: a wing has (nwin - offset) / index_step <= K taps).  Output sample t
+// reads the inputs n(t) - K + 1 .. n(t) + K at most, so it is final once input n(t) + K has arrived: from then on the right-hand clamp
+// n_in - n - 1 is inactive whatever n_in turns out to be.  At the flush n_in is known: the rest is computed with the clamp active, up to
+// resampy's int(n_in * ratio), and zeros follow up to librosa's ceil(n_in * ratio).
+struct ResampleGeom {
+    double ratio, inc;
+    int index_step, K;
+};
+
+static ResampleGeom resample_geom(int sr_in, int sr_out) {
+    VR_CHECK(sr_in > 0 && sr_out > 0, -2, "resampler: the sample rates must be positive");
+    ResampleGeom g;
+    g.ratio = (double)sr_out / (double)sr_in;
+    g.inc = 1.0 / g.ratio;
+    const double scale = g.ratio < 1.0 ? g.ratio : 1.0;
+    g.index_step = (int)(scale * (1 << 9));
+    VR_CHECK(g.index_step >= 1, -2, "resampler: sr_out / sr_in is below the filter table's resolution (1 / 512)");
+    g.K = ((16 << 9) + 1) / g.index_step;
+    return g;
+}
+
+static long long resample_ready(const ResampleGeom& g, long long samples_in, bool flushed) {
+    VR_CHECK(samples_in >= 0, -2, "resampler: negative sample count");
+    if (flushed) {
+        VR_CHECK(samples_in > 0, -2, "resampler: flush with no sample received");
+        return (long long)std::ceil((double)samples_in * g.ratio);
+    }
+    const long long m = samples_in - g.K - 1;                 // the last n(t) whose right wing has arrived whole
+    if (m < 0) return 0;
+    long long t = (long long)((double)(m + 1) * g.ratio);      // an estimate of the first t with n(t) > m, then the exact expression
+    while ((long long)((double)t * g.inc) <= m) ++t;
+    while (t > 0 && (long long)((double)(t - 1) * g.inc) > m) --t;
+    return t;
+}
+
+long long resampler_plan(int sr_in, int sr_out, long long samples_in, bool flushed) {
+    return resample_ready(resample_geom(sr_in, sr_out), samples_in, flushed);
+}
+
+// One session: its own stream, its filter table, two window buffers [channels][pitch] used in turn (the carried samples are copied
+// from the front of one to the front of the other, so no copy overlaps itself), an output staging buffer for host destinations and a
+// launch table.  The window buffers grow to history + the largest push seen; nothing else is allocated after the first pushes.
+struct Resampler {
+    int device, channels, sr_in, sr_out;
+    ResampleGeom g;
+    hipStream_t st = nullptr;
+    double *d_win = nullptr, *d_delta = nullptr;
+    int nwin = 0;
+    float* buf[2] = {nullptr, nullptr};
+    long long pitch = 0, hist = 0, g0 = 0;       // samples per row; samples held at the front of buf[cur]; global index of the first
+    int cur = 0;
+    long long n_recv = 0, n_emit = 0;            // the two counters: input samples received, output samples returned
+    bool flushed = false, broken = false;
+    float* d_out = nullptr;
+    long long out_cap = 0;
+    ResampleSeg *d_tab = nullptr, *h_tab = nullptr;
+    int tab_cap = 0;
+    long long history_cap() const { return 2LL * g.K + 2; }
+    ~Resampler() {
+        hipFree(d_win); hipFree(d_delta); hipFree(buf[0]); hipFree(buf[1]); hipFree(d_out); hipFree(d_tab);
+        if (h_tab) hipHostFree(h_tab);
+        if (st) hipStreamDestroy(st);
+    }
+};
+
+Resampler* resampler_open(int device, int channels, int sr_in, int sr_out) {
+    DeviceGuard dev_guard(device);
+    Resampler* r = new Resampler();
+    try {
+        r->device = device; r->channels = channels; r->sr_in = sr_in; r->sr_out = sr_out;
+        r->g = resample_geom(sr_in, sr_out);
+        VR_HIP(hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking));
+        std::vector<double> win, delta;
+        kaiser_sinc_table(16, 9, 0.85, 8.555504641634386, win);                       // 'kaiser_fast', as resample_api builds it
+        if (r->g.ratio < 1.0) for (double& v : win) v *= r->g.ratio;
+        delta.resize(win.size());
+        for (size_t i = 0; i + 1 < win.size(); ++i) delta[i] = win[i + 1] - win[i];
+        delta.back() = 0.0;
+        r->nwin = (int)win.size();
+        VR_HIP(hipMalloc(&r->d_win, win.size() * sizeof(double)));
+        VR_HIP(hipMalloc(&r->d_delta, win.size() * sizeof(double)));
+        VR_HIP(hipMemcpy(r->d_win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
+        VR_HIP(hipMemcpy(r->d_delta, delta.data(), win.size() * sizeof(double), hipMemcpyHostToDevice));
+        r->pitch = r->history_cap();
+        for (float*& b : r->buf) VR_HIP(hipMalloc(&b, (size_t)channels * r->pitch * sizeof(float)));
+    } catch (...) {
+        delete r;
+        throw;
+    }
+    return r;
+}
+
+void resampler_close(Resampler* r) {
+    DeviceGuard dev_guard(r->device);
+    delete r;
+}
+
+void resampler_info(const Resampler* r, long long* lookahead, long long* state_bytes) {
+    if (lookahead) *lookahead = r->g.K + 1;
+    if (state_bytes)
+        *state_bytes = (long long)r->channels * r->history_cap() * (long long)sizeof(float) + 2LL * r->nwin * (long long)sizeof(double) +
+                       2LL * (long long)sizeof(long long);
+}
+
+static void copy_rows(void* dst, long long dpitch, const void* src, long long spitch, long long width, int rows, hipMemcpyKind kind,
+                      hipStream_t st) {
+    if (width > 0)
+        VR_HIP(hipMemcpy2DAsync(dst, (size_t)dpitch * sizeof(float), src, (size_t)spitch * sizeof(float), (size_t)width * sizeof(float),
+                                (size_t)rows, kind, st));
+}
+
+// Session k receives n[k] >= 0 samples and, where flush[k], its input ends.  Everything is checked first; then the copies of all sessions,
+// ONE launch with one table entry per session, the copies out and the carry run on session 0's stream, and the call waits for it (every
+// session's memory is idle between calls, so no other stream has to be waited for).
+void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool x_on_dev, const long long* n, const int* flush,
+                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many) {
+    VR_CHECK(N <= 65535, -2, "resampler: at most 65535 sessions in one call (one grid plane each)");
+    std::vector<long long> need((size_t)N, 0), total((size_t)N, 0);
+    for (int k = 0; k < N; ++k) {
+        const std::string who = many ? "resampler " + std::to_string(k) + ": " : std::string("resampler: ");
+        VR_CHECK(r[k], -2, who + "null session (closed?)");
+        for (int j = 0; j < k; ++j) VR_CHECK(r[j] != r[k], -2, who + "the same session as resampler " + std::to_string(j));
+        VR_CHECK(r[k]->device == r[0]->device, -2, who + "on another device than resampler 0: the sessions of one call share a device");
+        VR_CHECK(r[k]->channels == r[0]->channels, -2, who + "another channel count than resampler 0");
+        const bool fl = flush && flush[k];
+        VR_CHECK(!r[k]->flushed, -2, who + (fl && n[k] == 0 ? "already flushed" : "push after flush"));
+        VR_CHECK(!r[k]->broken, -2, who + "an earlier call failed half way: close the session");
+        VR_CHECK(n[k] >= 0, -2, who + "negative sample count");
+        VR_CHECK(n[k] == 0 || (x && x[k]), -2, who + "null input");
+        total[k] = r[k]->n_recv + n[k];
+        VR_CHECK(!fl || total[k] > 0, -2, who + "flush with no sample received");
+        need[k] = resample_ready(r[k]->g, total[k], fl) - r[k]->n_emit;
+        const long long cap = capacity ? capacity[k] : 0;
+        VR_CHECK(cap >= need[k], -2, who + "capacity " + std::to_string(cap) + " but the call returns " + std::to_string(need[k]) + " samples");
+        VR_CHECK(need[k] == 0 || (y && y[k]), -2, who + "null output");
+    }
+    Resampler* lead = r[0];
+    const int C = lead->channels;
+    DeviceGuard dev_guard(lead->device);
+    hipStream_t st = lead->st;
+    for (int k = 0; k < N; ++k) r[k]->broken = true;
+    if (lead->tab_cap < N) {
+        hipFree(lead->d_tab);
+        if (lead->h_tab) hipHostFree(lead->h_tab);
+        lead->d_tab = nullptr; lead->h_tab = nullptr; lead->tab_cap = 0;
+        VR_HIP(hipMalloc(&lead->d_tab, (size_t)N * sizeof(ResampleSeg)));
+        VR_HIP(hipHostMalloc(&lead->h_tab, (size_t)N * sizeof(ResampleSeg)));
+        lead->tab_cap = N;
+    }
+    const hipMemcpyKind in_kind = x_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = y_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    long long max_count = 0;
+    for (int k = 0; k < N; ++k) {
+        Resampler& s = *r[k];
+        if (s.hist + n[k] > s.pitch) {                      // a larger push than any before: both windows grow, the history moves over
+            const long long pitch = s.history_cap() + n[k];
+            struct Pair { float* p[2]; ~Pair() { hipFree(p[0]); hipFree(p[1]); } } nb{{nullptr, nullptr}};      // freed unless taken over
+            for (float*& b : nb.p) VR_HIP(hipMalloc(&b, (size_t)C * pitch * sizeof(float)));
+            copy_rows(nb.p[0], pitch, s.buf[s.cur], s.pitch, s.hist, C, hipMemcpyDeviceToDevice, st);
+            VR_HIP(hipStreamSynchronize(st));
+            std::swap(s.buf[0], nb.p[0]);                    // the old pair goes with the guard
+            std::swap(s.buf[1], nb.p[1]);
+            s.cur = 0; s.pitch = pitch;
+        }
+        copy_rows(s.buf[s.cur] + s.hist, s.pitch, n[k] ? x[k] : nullptr, n[k], n[k], C, in_kind, st);
+        const bool fl = flush && flush[k];
+        const bool same = s.sr_in == s.sr_out;               // pass-through: the schedule is the filter's, the samples are the input's
+        ResampleSeg& e = lead->h_tab[k];
+        e.x = s.buf[s.cur]; e.x_pitch = s.pitch; e.g0 = s.g0; e.n_in = total[k];
+        e.t0 = s.n_emit; e.count = same ? 0 : need[k];
+        e.t_core = fl ? (long long)((double)total[k] * s.g.ratio) : LLONG_MAX;
+        VR_CHECK(s.n_emit <= e.t_core, -3, "resampler: the schedule ran past int(n_in * ratio)");
+        e.win = s.d_win; e.delta = s.d_delta; e.ratio = s.g.ratio; e.nwin = s.nwin; e.precision = 1 << 9;
+        if (y_on_dev) { e.y = y[k]; e.y_pitch = capacity ? capacity[k] : 0; }
+        else if (!same) {
+            if (s.out_cap < need[k]) {
+                hipFree(s.d_out); s.d_out = nullptr; s.out_cap = 0;
+                VR_HIP(hipMalloc(&s.d_out, (size_t)C * need[k] * sizeof(float)));
+                s.out_cap = need[k];
+            }
+            e.y = s.d_out; e.y_pitch = need[k];
+        } else { e.y = nullptr; e.y_pitch = 0; }              // pass-through to the host: copied from the window, no staging
+        // the first sample of the launch reads from n(t0) - K + 1 on: the carry rule below keeps it inside the window
+        VR_CHECK(e.count == 0 || s.g0 <= std::max(0LL, (long long)((double)e.t0 * s.g.inc) - s.g.K + 1), -3, "resampler: window lost its history");
+        max_count = std::max(max_count, e.count);
+    }
+    if (max_count > 0) {
+        VR_HIP(hipMemcpyAsync(lead->d_tab, lead->h_tab, (size_t)N * sizeof(ResampleSeg), hipMemcpyHostToDevice, st));
+        float* const unused_out = nullptr;
+        const double* const unused_tab = nullptr;
+        VR_LAUNCH(resample_kernel<true>, dim3((unsigned)((max_count + 255) / 256), C, N), dim3(256), 0, st, lead->d_tab, 0LL, unused_out, 0LL,
+                  unused_tab, unused_tab, 0, 0, 0.0);
+        VR_HIP(hipGetLastError());
+    }
+    for (int k = 0; k < N; ++k) {
+        Resampler& s = *r[k];
+        const ResampleSeg& e = lead->h_tab[k];
+        const long long cap = capacity ? capacity[k] : 0;
+        if (s.sr_in == s.sr_out) copy_rows(y ? y[k] : nullptr, cap, s.buf[s.cur] + (s.n_emit - s.g0), s.pitch, need[k], C, out_kind, st);
+        else if (!y_on_dev) copy_rows(y ? y[k] : nullptr, cap, s.d_out, e.y_pitch, need[k], C, hipMemcpyDeviceToHost, st);
+        const bool fl = flush && flush[k];
+        const long long emit = s.n_emit + need[k];
+        if (!fl && n[k] > 0) {
+            // the next sample to come, t = emit, reads from n(t) - K + 1 on; n(t) + K >= total (it is not final), so at most 2K are kept
+            long long keep = std::max(s.g0, std::max(0LL, (long long)((double)emit * s.g.inc) - s.g.K));
+            keep = std::min(keep, total[k]);
+            copy_rows(s.buf[1 - s.cur], s.pitch, s.buf[s.cur] + (keep - s.g0), s.pitch, total[k] - keep, C, hipMemcpyDeviceToDevice, st);
+            s.cur = 1 - s.cur; s.g0 = keep; s.hist = total[k] - keep;
+        }
+    }
+    VR_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < N; ++k) {
+        Resampler& s = *r[k];
+        s.n_recv = total[k]; s.n_emit += need[k];
+        if (flush && flush[k]) s.flushed = true;
+        s.broken = false;
+        if (n_out) n_out[k] = need[k];
+    }
 }
 
 // full[k] = sum_n a[n + k - (nb - 1)] * b[n],  k = 0 .. na + nb - 2   (np.correlate(a, b, 'full'), real input)

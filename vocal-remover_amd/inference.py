@@ -316,50 +316,105 @@ class Stream(object):
             pass
 
 
-def _stream_reader(path, sr, block_seconds):
-    """-> blocks(): a fresh iterator over the WAV at `path` as stereo blocks [2, n] of block_seconds.  The file's rate must be `sr`."""
-    from . import audio
-    rd = audio.WavBlockReader(path)
-    if rd.sr != sr:
-        raise ValueError('%s has sample rate %d, not --sr %d: the resampler is not streamed, run without --stream' % (path, rd.sr, sr))
-    n = max(1, int(round(block_seconds * sr)))
-
-    def blocks():
-        for b in rd.blocks(n):
-            yield np.ascontiguousarray(np.vstack([b, b]) if b.shape[0] == 1 else b[:2])      # mono to stereo (inference.py:143-145)
-    return blocks
+def _stereo(b):
+    return np.ascontiguousarray(np.vstack([b, b]) if b.shape[0] == 1 else b[:2])          # mono to stereo (inference.py:143-145)
 
 
-def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0):
+def _host(a):
+    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+
+
+class _StreamSource(object):
+    """The WAV at `path` as stereo blocks [2, n] at `sr`, block_seconds of the file each.  The file's rate must be `sr` unless
+    resample is set: then every pass reads the file at its own rate and puts it through an audio.StreamResampler, whose output for the
+    whole file is audio.load(path, sr)'s, so the blocks vary in length by a sample and the last one carries the resampler's flush.
+    A mono file is up-mixed BEFORE the resampler (the channels are independent, so the bits are those of resampling it mono): every
+    session has two channels, and the sessions of a group fit one resample_push_many call.  on_device: the blocks are uploaded once, as
+    cuda tensors, so that the resampler's output goes into Stream.push where it lies (set for a source that resamples)."""
+
+    def __init__(self, path, sr, block_seconds, resample=False, device=None):
+        from . import audio
+        self.device = device
+        self.rd = rd = audio.WavBlockReader(path)
+        if rd.sr != sr and not resample:
+            raise ValueError('%s has sample rate %d, not --sr %d: the resampler is not streamed, run without --stream '
+                             '(or pass resample=True to stream_file / stream_files)' % (path, rd.sr, sr))
+        self.sr, self.resamples = sr, rd.sr != sr
+        self.on_device = self.resamples
+        self.n = max(1, int(round(block_seconds * rd.sr)))
+
+    def raw(self):
+        """the file's own blocks, stereo [2, n], at its own rate"""
+        if self.on_device:
+            import torch
+            dev = torch.device('cuda', int(self.device or 0))
+        for b in self.rd.blocks(self.n):
+            b = _stereo(b)
+            yield torch.from_numpy(b).to(dev) if self.on_device else b
+
+    def resampler(self):
+        from . import audio
+        return audio.StreamResampler(self.rd.sr, self.sr, channels=2, device=self.device)
+
+    def blocks(self):
+        if not self.resamples:
+            for b in self.raw():
+                yield b
+            return
+        with self.resampler() as rs:
+            for b in self.raw():
+                y = rs.push(b)
+                if y.shape[1]:
+                    yield y
+            yield rs.flush()
+
+
+def _stream_reader(path, sr, block_seconds, resample=False, device=None):
+    """-> blocks(): a fresh iterator over the WAV at `path` as stereo blocks [2, n] at `sr` (see _StreamSource)."""
+    return _StreamSource(path, sr, block_seconds, resample, device).blocks
+
+
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False):
     """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
-    written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed."""
+    written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed -- unless
+    resample=True, which reads both passes at the file's own rate through an audio.StreamResampler (bounded state; the blocks stay on
+    the device from the upload to the stems); the stems are written at `sr`, as the offline path writes them."""
     from . import audio
-    blocks = _stream_reader(path, sr, block_seconds)
+    blocks = _stream_reader(path, sr, block_seconds, resample, sp.model._need_handle().device)
     coef = sp.measure_coef(blocks(), tta=tta)
     with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, sp.stream(coef=coef, tta=tta) as s:
         for b in blocks():
             y, v = s.push(b)
-            wy.append(y.T)
-            wv.append(v.T)
+            wy.append(_host(y).T)
+            wv.append(_host(v).T)
         y, v = s.flush()
-        wy.append(y.T)
-        wv.append(v.T)
+        wy.append(_host(y).T)
+        wv.append(_host(v).T)
 
 
-def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0):
+def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False):
     """--stream on a directory: stream_file for a group of WAVs at once.  Every file's normaliser is measured first; then the files
     advance together, one block each per Separator.push_many call, so their crops share device batches; a file that ends is flushed
-    in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k]."""
+    in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k].
+    resample=True: files whose rate is not `sr` go through one audio.StreamResampler each, and a round resamples the blocks of all of
+    them in ONE audio.resample_push_many launch in front of push_many.  The files may have different rates: the launch table carries
+    each session's ratio and filter, so they are not grouped by rate.  Mono files are up-mixed first, so every session has two
+    channels.  When any file of the group resamples, the blocks of all its files are uploaded as cuda tensors (push_many takes one
+    kind), and nothing comes back to the host before the stems."""
     import contextlib
 
     from . import audio
-    readers = [_stream_reader(p, sr, block_seconds) for p in paths]
-    coefs = [sp.measure_coef(blocks(), tta=tta) for blocks in readers]
+    sources = [_StreamSource(p, sr, block_seconds, resample, sp.model._need_handle().device) for p in paths]
+    coefs = [sp.measure_coef(src.blocks(), tta=tta) for src in sources]
+    on_device = any(src.resamples for src in sources)
+    for src in sources:
+        src.on_device = on_device
     with contextlib.ExitStack() as stack:
         wy = [stack.enter_context(audio.WavAppendWriter(oy, sr, 2)) for oy, _ in outs]
         wv = [stack.enter_context(audio.WavAppendWriter(ov, sr, 2)) for _, ov in outs]
         streams = [stack.enter_context(sp.stream(coef=c, tta=tta)) for c in coefs]
-        its = [blocks() for blocks in readers]
+        rs = [stack.enter_context(src.resampler()) if src.resamples else None for src in sources]
+        its = [src.raw() for src in sources]
         ahead = [next(it, None) for it in its]
         live = list(range(len(paths)))                  # the files still streaming; a flushed stream takes no further part
         while live:
@@ -367,9 +422,14 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0):
             for k in live:
                 ahead[k] = next(its[k], None) if ahead[k] is not None else None
             ends = [ahead[k] is None for k in live]
+            sel = [i for i, k in enumerate(live) if rs[k] is not None]
+            if sel:                                     # one resampling launch for the round, whatever the files' rates
+                done = audio.resample_push_many([rs[live[i]] for i in sel], [cur[i] for i in sel], [ends[i] for i in sel])
+                for i, y in zip(sel, done):
+                    cur[i] = y
             for k, (y, v) in zip(live, sp.push_many([streams[k] for k in live], cur, ends)):
-                wy[k].append(y.T)
-                wv[k].append(v.T)
+                wy[k].append(_host(y).T)
+                wv[k].append(_host(v).T)
             live = [k for k, end in zip(live, ends) if not end]
 
 
@@ -442,12 +502,12 @@ def main(argv=None):
         for group in expand_inputs(args.input, args.songs_per_call):      # the group's files advance together, block by block
             names = [os.path.splitext(os.path.basename(path))[0] for path in group]
             stream_files(sp, group, [('{}{}_Instruments.wav'.format(output_dir, b), '{}{}_Vocals.wav'.format(output_dir, b)) for b in names],
-                         args.sr, tta=args.tta, block_seconds=args.block_seconds)
+                         args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True)
         return 0
     if args.stream:
         basename = os.path.splitext(os.path.basename(args.input))[0]
         stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
-                    args.sr, tta=args.tta, block_seconds=args.block_seconds)
+                    args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True)
         return 0
     if not os.path.isdir(args.input):
         X, sr = load(args.input)

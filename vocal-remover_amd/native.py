@@ -89,6 +89,14 @@ _SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     'vr_resample': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int64]),
     'vr_xcorr_argmax': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64, c_i64p]),
+    'vr_resampler_open': (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_resampler_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_resampler_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_resampler_push_many': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p, c_i64p]),
+    'vr_resampler_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p]),
+    'vr_resampler_close': (ctypes.c_int, [ctypes.c_void_p]),
+    'vr_resampler_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i64p]),
     'vr_profile_begin': (ctypes.c_int, [ctypes.c_void_p]),
     'vr_profile_end': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
@@ -178,6 +186,13 @@ def stream_plan(n_fft, hop, cropsize, offset, tta, samples_in, flushed):
     check(lib().vr_stream_plan(int(n_fft), int(hop), int(cropsize), int(offset), 1 if tta else 0, int(samples_in), 1 if flushed else 0,
                                ctypes.byref(fr), crops, ctypes.byref(out)))
     return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
+
+
+def resampler_plan(sr_in, sr_out, samples_in, flushed):
+    """vr_resampler_plan (host only): output samples per channel that are final after samples_in input samples (flushed: in all)."""
+    out = ctypes.c_int64()
+    check(lib().vr_resampler_plan(int(sr_in), int(sr_out), int(samples_in), 1 if flushed else 0, ctypes.byref(out)))
+    return int(out.value)
 
 
 class Crop(ctypes.Structure):               # include/vr_mi355.h: vr_crop
