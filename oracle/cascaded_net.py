@@ -170,6 +170,23 @@ BASE_NETS = ('stg1_low_band_net.0', 'stg1_high_band_net', 'stg2_low_band_net.0',
              'stg2_high_band_net', 'stg3_full_band_net')
 
 
+def mask_head(f3, out_weight, output_bin):
+    """The mask head of CascadedNet.forward, lib/nets.py:109-115: sigmoid(out(f3)), replicate-padded to output_bin rows."""
+    mask = torch.sigmoid(F.conv2d(f3, out_weight))
+    return F.pad(mask, (0, 0, 0, output_bin - mask.shape[2]), mode='replicate')
+
+
+def complex_mask_head(f3, out_weight, output_bin, eps=1e-8):
+    """The same for is_complex=True, lib/nets.py:104-107,111-115,119-122: out has four channels, (real ch0, real ch1, imag ch0,
+    imag ch1); the complex mask is bounded to the unit disc as tanh(|m|) m / (|m| + eps)."""
+    o = F.conv2d(f3, out_weight)
+    mask = torch.complex(o[:, :2], o[:, 2:])
+    mag = torch.abs(mask)
+    mask = torch.tanh(mag) * mask / (mag + eps)
+    pad = mask[:, :, -1:].expand(-1, -1, output_bin - mask.shape[2], -1)         # (replicate rows)
+    return torch.cat([mask, pad], dim=2)
+
+
 def forward(x, sd, n_fft=2048, training=False, update_running=True, dropout=None):
     """CascadedNet.forward, lib/nets.py:82-117 (is_complex=False). x [B,2,n_fft/2+1,T]."""
     kw = dict(training=training, update_running=update_running)
@@ -187,8 +204,7 @@ def forward(x, sd, n_fft=2048, training=False, update_running=True, dropout=None
     h2 = base_net(torch.cat([h1_in, h1], dim=1), sd, 'stg2_high_band_net', dropout, **kw)
     aux2 = torch.cat([l2, h2], dim=2)
     f3 = base_net(torch.cat([x, aux1, aux2], dim=1), sd, 'stg3_full_band_net', dropout, **kw)
-    mask = torch.sigmoid(F.conv2d(f3, sd['out.weight']))
-    return F.pad(mask, (0, 0, 0, output_bin - mask.shape[2]), mode='replicate')
+    return mask_head(f3, sd['out.weight'], output_bin)
 
 
 def predict_mask(x, sd, n_fft=2048, offset=64):

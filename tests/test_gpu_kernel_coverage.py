@@ -6,7 +6,8 @@ fallbacks behind the fast forms -- odd widths (frames / 16 odd), hidden sizes th
 0 / 1 / 2, `train_winograd` off, a general STFT hop.  This test drives each of those through the public Python surface under the library's
 own launch profiler (`vr_profile_begin / _end / _report`: every VR_LAUNCH of the thread) and asserts that the union of what ran covers
 every kernel the built library exports, minus a short list that is launched outside the profiler and has its own tests.
-The numerics of these paths are checked elsewhere (test_gpu_parity / _kernels / _train / _configs); here only reachability."""
+The numerics of these paths are checked by test_gpu_parity / _kernels / _train / _configs, and those of the LSTM fallbacks, the eval mask
+heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py; here only reachability."""
 import ctypes
 import os
 import shutil
@@ -165,6 +166,11 @@ def test_every_kernel_of_the_library_is_reached_by_a_documented_shape_or_option(
         col.run('vr_debug_conv2d, mfma_mode %d' % mode, h, lambda: nat.check(nat.lib().vr_debug_conv2d(
             h.h, nat.np_ptr(xn), 1, 16, 16, 32, nat.np_ptr(wn), 32, 3, 1, 1, 1, 2, None, ctypes.c_float(1.0), None, nat.np_ptr(out), None)))
     small.set_option('mfma_mode', -1)
+    # the backward of the mask head alone: in training it runs on torch's autograd thread, outside this thread's profiler; here through its hook
+    # (debug.hip 'head_bwd'; values: tests/test_gpu_heads_lstm.py)
+    hb = np.random.default_rng(6).random((2, 1, 2, 5, 8)).astype(np.float32)
+    hbo = np.empty((1, 2, 4, 8), np.float32)
+    col.run('vr_debug_kernel head_bwd', h, lambda: nat.debug_kernel(h, 'head_bwd', [1, 4, 8, 5], [], [hb[0], hb[1]], [hbo]))
     # the single-layer backward hook sums its weight-gradient slabs at once (wgrad_reduce_kernel); Model::backward defers them into one launch
     dzn = np.random.default_rng(5).standard_normal((1, 32, 16, 32)).astype(np.float32)
     dxo, dwo = np.empty_like(xn), np.empty_like(wn)
@@ -189,6 +195,5 @@ def test_every_kernel_of_the_library_is_reached_by_a_documented_shape_or_option(
               'wgrad_wino_kernel', 'conv_mfma_kernel', 'conv_ws_kernel', 'stft_kernel', 'istft_frame_kernel', 'istft_ola_kernel', 'adam_kernel'):
         assert n in col.seen, (n, missing)
     # vr_augment_batch: tests/test_golden.py; rows form of the upsample: widths % 4 == 2 only
-    # head_bwd (backward from dLoss / dmask) runs on torch's autograd thread, outside this thread's profiler: tests/test_gpu_frontend.py
-    allowed = {'augment_kernel', 'upsample2x_rows_kernel', 'head_bwd_kernel'}
+    allowed = {'augment_kernel', 'upsample2x_rows_kernel'}
     assert not [n for n in missing if n not in allowed], missing

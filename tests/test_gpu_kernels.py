@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle import kernel_refs
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -85,34 +87,17 @@ def test_batchnorm_train_forward_stats_and_backward(handle, shape, slope, use_po
 @pytest.mark.parametrize('N,T,H', [(2, 128, 64), (3, 128, 32), (1, 40, 16), (11, 72, 64), (16, 256, 32)])
 def test_bilstm_forward_bptt_and_whh_gradient(handle, N, T, H):
     nat, h = handle
-    g = torch.Generator().manual_seed(T + H)
     G4 = 4 * H
-    gx = (torch.randn(N, 2 * G4, T, generator=g) * 0.8).float()
-    whh = [(torch.rand(G4, H, generator=g) * 2 - 1).float() / H ** 0.5 for _ in range(2)]
-    dh = torch.randn(N, 2 * H, T, generator=g).float()
-    gxd = gx.double().requires_grad_(True)
-    wd = [w.double().requires_grad_(True) for w in whh]
-    outs = [None] * 2
-    for d in range(2):                      # torch.nn.LSTM cell, gate order i, f, g, o (lib/layers.py:113-117)
-        hcur = torch.zeros(N, H, dtype=torch.float64)
-        c = torch.zeros(N, H, dtype=torch.float64)
-        seq = [None] * T
-        for t in (range(T) if d == 0 else range(T - 1, -1, -1)):
-            gates = gxd[:, d * G4:(d + 1) * G4, t] + hcur @ wd[d].t()
-            i, f, gg, o = gates.chunk(4, dim=1)
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-            hcur = torch.sigmoid(o) * torch.tanh(c)
-            seq[t] = hcur
-        outs[d] = torch.stack(seq, dim=2)
-    hout = torch.cat(outs, dim=1)
-    hout.backward(dh.double())
+    gx, whh_f, whh_r, dh = kernel_refs.lstm_inputs(N, T, H, seed=T + H)
+    # torch.nn.LSTM cell, gate order i, f, g, o (lib/layers.py:113-117), in fp64: oracle/kernel_refs.py, pinned against nn.LSTM itself
+    hout, dgx, dwf, dwr = kernel_refs.bilstm_grads(gx, whh_f, whh_r, dh)
     out = [np.empty((N, 2 * H, T), np.float32), np.empty((N, 2 * G4, T), np.float32), np.empty((G4, H), np.float32),
            np.empty((G4, H), np.float32)]
-    nat.debug_kernel(h, 'lstm', [N, T, H], [], [f32(gx), f32(whh[0]), f32(whh[1]), f32(dh)], out)
+    nat.debug_kernel(h, 'lstm', [N, T, H], [], [f32(gx), f32(whh_f), f32(whh_r), f32(dh)], out)
     close(out[0], hout, 'h')
-    close(out[1], gxd.grad, 'dgx (BPTT)')
-    close(out[2], wd[0].grad, 'dW_hh forward')
-    close(out[3], wd[1].grad, 'dW_hh reverse')
+    close(out[1], dgx, 'dgx (BPTT)')
+    close(out[2], dwf, 'dW_hh forward')
+    close(out[3], dwr, 'dW_hh reverse')
 
 
 # forward (launch_upsample2x): W even and >= 8 -> four columns per thread, 2^qp threads per row (qp = 3 at W 16): upsample2x_rows_kernel, or

@@ -1,6 +1,7 @@
 // Test hooks (tests/ only): single kernels of the training path behind vr_debug_kernel, host pointers in and out,
-// so that every backward kernel has an isolated parity test against torch autograd (tests/test_gpu_kernels.py), and the
-// spectrogram-side glue of stft.hip against float64 numpy (tests/test_gpu_signal.py).
+// so that every backward kernel has an isolated parity test against torch autograd (tests/test_gpu_kernels.py), the
+// spectrogram-side glue of stft.hip against float64 numpy (tests/test_gpu_signal.py), and the LSTM fallbacks, the eval mask heads,
+// the squeeze conv and the small kernels around them against oracle/kernel_refs.py (tests/test_gpu_heads_lstm.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -47,11 +48,26 @@ Tensor dense(float* p, int N, int C, int H, int W) {
 
 // name            dims                  fparams          inputs                                              outputs
 // bn_backward     N,C,H,W               slope,eps,mom    z, G, gamma, beta, post[N][C]|null, rm[C], rv[C]    dz, dgamma, dbeta, affine[C][2], rm, rv
-// lstm            N,T,H                 -                gx[N][8H][T], whh_f[4H][H], whh_r, dh[N][2H][T]     h[N][2H][T], dgx[N][8H][T], dwhh_f, dwhh_r
+// lstm            N,T,H[,flags]         -                gx[N][8H][T], whh_f[4H][H], whh_r, dh[N][2H][T]     h[N][2H][T], dgx[N][8H][T], dwhh_f, dwhh_r
+//                                                        [, dwhh_f0[4H][H]|null, dwhh_r0|null]
+//                 the W_hh gradient is ACCUMULATED onto dwhh_f0 / dwhh_r0 (zeros when absent).  flags bit 0: the inference form,
+//                 launch_bilstm without a save buffer -- only h is produced, dh and the other outputs may be null; bit 1: only
+//                 launch_bilstm_bwd, on a zeroed save buffer (its own size check, which the forward's would otherwise pre-empt)
 // upsample        N,C,H,W               -                x[N,C,H,W], dhi[N,C,2H,2W]                          up[N,C,2H,2W], glo[N,C,H,W]
 // pool            N,C,H,W               -                x, gp[N,C,W], d[N,C,H,W]                            pooled[N,C,W], g[N,C,H,W], sumh[N,C,W]
 // thin            N,C,H,W,CO            slope            x, aff[C][2]|null, w[CO][C], dz[N,CO,H,W]           g[N,C,H,W], dw[CO][C], z[N,H,W] (CO=1: forward)
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
+// head            N,C,H,W,w_lo,w_hi,pad_rows,cplx,hsplit,use_items,pitch_extra
+//                                       slope            x[N,C,H,W], aff0[C][2]|null, aff1[C][2]|null,       the destination(s), whole: dense [N][2][H+pad_rows][Wm +
+//                                                        w[CO][C] (CO = 2; cplx: 4)                          pitch_extra], or with use_items one buffer per item n,
+//                                                                                                            [2][H+pad_rows][Wm + pitch_extra + n] (cplx: complex64)
+//                 launch_head_sigmoid / launch_head_complex; Wm = w_hi - w_lo; rows < hsplit take aff0, the others aff1; every
+//                 destination is filled with NaN before the launch
+// squeeze         N,C,H,W,use_part      slope            x, aff[C][2]|null, w[C], epi[2]|null                z[N,H,W], part[nblk][2]|null, nblk[1]|null
+//                 launch_squeeze_conv; nblk = what its dry run returns
+// head_bwd        N,H,W,bins            -                dmask[N,2,bins,W], mask[N,2,bins,W]                 dlogit[N,2,H,W]
+// crop            rows,T,Wm,off,cplx    -                m[rows][Wm], x[rows][T], y[rows][T]|null            m * x[.., off + w] [rows][Wm], mean |that - y[.., off + w]|
+//                 launch_mul_crop, launch_l1_crop (real only); cplx: m and x complex64, the complex product     [1]|null
 // rows            N,R,W                 -                x[N,R,W], aff[R][2], d[N,R,W]                       relu(x*a+b), channel sums of d [R]
 // adam            n                     lr,b1,b2,eps,gscale,step   p, g, m, v                                p, m, v
 // wire            n                     -                x[n]                                                bf16_to_f32(f32_to_bf16(x)) [n]
@@ -117,11 +133,25 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_HIP(hipStreamSynchronize(st));
         g.download(out[0]); dgamma.download(out[1]); dbeta.download(out[2]); aff.download(out[3]); rm.download(out[4]); rv.download(out[5]);
     } else if (name == "lstm") {
-        need(3, 0, 4, 4);
+        const int flags = ndims >= 4 ? (int)dims[3] : 0;
+        const bool infer = flags & 1, bwd_only = flags & 2;
+        need(3, 0, infer ? 3 : 4, infer ? 1 : 4);
         const int N = (int)dims[0], T = (int)dims[1], H = (int)dims[2], G = 4 * H;
-        DevBuf gx(in[0], (size_t)N * 2 * G * T), wf(in[1], (size_t)G * H), wr(in[2], (size_t)G * H), dh(in[3], (size_t)N * 2 * H * T);
-        DevBuf h((size_t)N * 2 * H * T), save((size_t)N * 2 * T * 5 * H), dgx((size_t)N * 2 * G * T), dwf((size_t)G * H), dwr((size_t)G * H);
-        launch_bilstm_train(gx.p, wf.p, wr.p, h.p, save.p, N, T, H, st);
+        VR_CHECK(N > 0 && T > 0 && H > 0, -2, "lstm: N, T, H must be positive");
+        DevBuf gx(in[0], (size_t)N * 2 * G * T), wf(in[1], (size_t)G * H), wr(in[2], (size_t)G * H), h((size_t)N * 2 * H * T);
+        if (infer) {
+            launch_bilstm(gx.p, wf.p, wr.p, h.p, N, T, H, st);
+            VR_HIP(hipStreamSynchronize(st));
+            h.download(out[0]);
+            return;
+        }
+        DevBuf dh(in[3], (size_t)N * 2 * H * T), save((size_t)N * 2 * T * 5 * H), dgx((size_t)N * 2 * G * T);
+        // launch_lstm_whh_grad below accumulates: onto the caller's initial gradients, or onto zeros
+        const float* f0 = nin >= 5 ? in[4] : nullptr;
+        const float* r0 = nin >= 6 ? in[5] : nullptr;
+        std::vector<float> zeros(f0 && r0 ? 0 : (size_t)G * H, 0.f);
+        DevBuf dwf(f0 ? f0 : zeros.data(), (size_t)G * H), dwr(r0 ? r0 : zeros.data(), (size_t)G * H);
+        if (!bwd_only) launch_bilstm_train(gx.p, wf.p, wr.p, h.p, save.p, N, T, H, st);
         launch_bilstm_bwd(dh.p, save.p, wf.p, wr.p, dgx.p, N, T, H, st);
         DevBuf wpart(lstm_whh_grad_scratch_floats(N, H));
         launch_lstm_whh_grad(dgx.p, h.p, dwf.p, dwr.p, N, T, H, 1, wpart.p, st);
@@ -177,6 +207,91 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_HIP(hipStreamSynchronize(st));
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, sizeof(float), hipMemcpyDeviceToHost));
+    } else if (name == "head") {
+        need(11, 1, 4, 1);
+        const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], w_lo = (int)dims[4], w_hi = (int)dims[5];
+        const int pad_rows = (int)dims[6], hsplit = (int)dims[8], pitch_extra = (int)dims[10];
+        const bool cplx = dims[7] != 0, use_items = dims[9] != 0;
+        VR_CHECK(N > 0 && C > 0 && H > 0 && W > 0 && pad_rows >= 0 && pitch_extra >= 0 && w_lo >= 0 && w_hi <= W && w_lo <= w_hi, -2,
+                 "head: need positive sizes and 0 <= w_lo <= w_hi <= W");
+        VR_CHECK(!use_items || nout >= N, -2, "head: use_items needs one output per item");
+        const int CO = cplx ? 4 : 2, E = cplx ? 2 : 1, Wm = w_hi - w_lo, rows = H + pad_rows;
+        const size_t n = (size_t)N * C * H * W;
+        DevBuf x(in[0], n), aff0(in[1], in[1] ? (size_t)C * 2 : 0), aff1(in[2], in[2] ? (size_t)C * 2 : 0), w(in[3], (size_t)CO * C);
+        Tensor t = dense(x.p, N, C, H, W);
+        t.slope = fp[0]; t.hsplit = hsplit;
+        if (in[1]) t.aff0 = aff0.p;
+        if (in[2]) t.aff1 = aff1.p;
+        // one destination per item (use_items; item n has its own pitch) or one dense destination, all NaN before the launch
+        const int nbuf = use_items ? N : 1;
+        std::vector<std::unique_ptr<DevBuf>> dst;
+        std::vector<float*> items_h;
+        std::vector<int> pitch_h;
+        for (int b = 0; b < nbuf; ++b) {
+            const int pitch = Wm + pitch_extra + (use_items ? b : 0);
+            const size_t words = (size_t)(use_items ? 1 : N) * 2 * rows * pitch * E;
+            const std::vector<float> fill(words, std::nanf(""));
+            dst.emplace_back(new DevBuf(fill.data(), words));
+            items_h.push_back(dst.back()->p);
+            pitch_h.push_back(pitch);
+        }
+        DevBuf items_d((size_t)N * 2), pitch_d((size_t)N);         // device tables: N pointers, N ints
+        HeadDst d{};
+        d.w_lo = w_lo; d.w_hi = w_hi; d.pad_rows = pad_rows;
+        if (use_items) {
+            VR_HIP(hipMemcpy(items_d.p, items_h.data(), (size_t)N * sizeof(float*), hipMemcpyHostToDevice));
+            VR_HIP(hipMemcpy(pitch_d.p, pitch_h.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+            d.items = reinterpret_cast<float* const*>(items_d.p);
+            d.item_pitch = reinterpret_cast<const int*>(pitch_d.p);
+        } else {
+            d.p = dst[0]->p; d.dH = pitch_h[0]; d.dC = (long long)rows * d.dH; d.dN = 2 * d.dC;
+        }
+        if (cplx) launch_head_complex(t, w.p, d, st);
+        else launch_head_sigmoid(t, w.p, d, st);
+        VR_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < nbuf; ++b) dst[b]->download(out[b]);
+    } else if (name == "squeeze") {
+        need(5, 1, 4, 1);
+        const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];
+        const bool use_part = dims[4] != 0;
+        VR_CHECK(N > 0 && C > 0 && H > 0 && W > 0, -2, "squeeze: sizes must be positive");
+        VR_CHECK(!use_part || (nout >= 2 && out[1]), -2, "squeeze: use_part needs the partials output");
+        const size_t n = (size_t)N * C * H * W;
+        DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)C), epi(in[3], in[3] ? 2 : 0), z((size_t)N * H * W);
+        Tensor t = dense(x.p, N, C, H, W);
+        t.slope = fp[0];
+        if (in[1]) t.aff0 = aff.p;
+        const int nblk = launch_squeeze_conv(t, w.p, z.p, nullptr, true, st);
+        DevBuf part((size_t)nblk * 2);
+        launch_squeeze_conv(t, w.p, z.p, use_part ? part.p : nullptr, false, st, in[3] ? epi.p : nullptr);
+        VR_HIP(hipStreamSynchronize(st));
+        z.download(out[0]);
+        if (use_part) part.download(out[1]);
+        if (nout >= 3 && out[2]) out[2][0] = (float)nblk;
+    } else if (name == "head_bwd") {
+        need(4, 0, 2, 1);
+        const int N = (int)dims[0], H = (int)dims[1], W = (int)dims[2], bins = (int)dims[3];
+        VR_CHECK(N > 0 && H > 0 && W > 0 && bins >= H, -2, "head_bwd: need positive sizes and bins >= H");
+        const size_t nm = (size_t)N * 2 * bins * W;
+        DevBuf dmask(in[0], nm), mask(in[1], nm), dlogit((size_t)N * 2 * H * W);
+        launch_head_bwd(dmask.p, mask.p, N, H, W, bins, dlogit.p, st);
+        VR_HIP(hipStreamSynchronize(st));
+        dlogit.download(out[0]);
+    } else if (name == "crop") {
+        need(5, 0, 2, 1);
+        const long long rows = dims[0];
+        const int T = (int)dims[1], Wm = (int)dims[2], off = (int)dims[3];
+        const bool cplx = dims[4] != 0;
+        VR_CHECK(rows > 0 && Wm > 0 && off >= 0 && off + Wm <= T, -2, "crop: need rows, Wm > 0 and 0 <= off, off + Wm <= T");
+        const bool loss = !cplx && nin >= 3 && in[2] && nout >= 2 && out[1];
+        const size_t E = cplx ? 2 : 1;
+        DevBuf m(in[0], (size_t)rows * Wm * E), x(in[1], (size_t)rows * T * E), y(loss ? in[2] : nullptr, loss ? (size_t)rows * T : 0);
+        DevBuf part((size_t)l1_crop_blocks()), lossd(4);
+        launch_mul_crop(x.p, m.p, cplx, rows, T, Wm, off, st);
+        if (loss) launch_l1_crop(m.p, y.p, rows, T, Wm, off, part.p, lossd.p, st);
+        VR_HIP(hipStreamSynchronize(st));
+        m.download(out[0]);
+        if (loss) VR_HIP(hipMemcpy(out[1], lossd.p, sizeof(float), hipMemcpyDeviceToHost));
     } else if (name == "rows") {
         need(3, 0, 3, 2);
         const int N = (int)dims[0], R = (int)dims[1], W = (int)dims[2];

@@ -157,6 +157,13 @@ void launch_channel_sum(const float* d, int N, int C, int W, float* out, int acc
 void launch_f32_to_bf16(const float* x, unsigned short* y, long long n, hipStream_t st);
 void launch_bf16_to_f32(const unsigned short* x, float* y, long long n, hipStream_t st);
 
+// ---- model.hip (the product and the loss behind predict / validate_step) -------------------------
+// m [rows][Wm] *= x [rows][T] at columns off .. off + Wm; cplx: both complex64, the complex product
+void launch_mul_crop(const float* x, float* m, bool cplx, long long rows, int T, int Wm, int off, hipStream_t st);
+// loss[0] = mean |pred [rows][Wm] - y [rows][T] at columns off .. off + Wm|; part: scratch of l1_crop_blocks() floats
+int l1_crop_blocks();
+void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
+
 // ---- stft.hip -----------------------------------------------------------------------------------
 struct FFTPlan { int n_fft; int log2n; float2* twiddle; float* window; };
 // wave [2][L] -> spec [2][bins][T] complex64

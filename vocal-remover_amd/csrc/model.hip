@@ -1264,6 +1264,13 @@ __global__ void mul_crop_kernel(const float* __restrict__ x, float* __restrict__
     }
 }
 
+void launch_mul_crop(const float* x, float* m, bool cplx, long long rows, int T, int Wm, int off, hipStream_t st) {
+    const long long total = rows * Wm;
+    if (cplx) VR_LAUNCH((mul_crop_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, m, T, Wm, off, total);
+    else VR_LAUNCH((mul_crop_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, m, T, Wm, off, total);
+    VR_HIP(hipGetLastError());
+}
+
 // forward_api of a complex handle: x [B][2][bins][T] complex64 -> planar [B][4][bins][T] (the reference's cat([x.real, x.imag])),
 // out [B][2][bins][Wm] complex64
 void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
@@ -1288,11 +1295,7 @@ void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int 
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;       // (complex elements)
     d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
     launch_head_complex(f3, out_w->dev, d, stream);
-    if (mode == 2) {
-        const long long total = (long long)B * 2 * output_bin * Wm;
-        VR_LAUNCH((mul_crop_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm, offset, total);
-        VR_HIP(hipGetLastError());
-    }
+    if (mode == 2) launch_mul_crop(xd, od, true, (long long)B * 2 * output_bin, T, Wm, offset, stream);
     if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
 }
@@ -1326,12 +1329,7 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
     launch_head_sigmoid(f3, out_w->dev, d, stream);
-    if (mode == 2) {
-        const long long total = (long long)out_floats;
-        VR_LAUNCH((mul_crop_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm,
-                           offset, total);
-        VR_HIP(hipGetLastError());
-    }
+    if (mode == 2) launch_mul_crop(xd, od, false, (long long)B * 2 * output_bin, T, Wm, offset, stream);
     if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
     if (training) affine_dirty = true;
@@ -1354,6 +1352,16 @@ __global__ __launch_bounds__(256) void l1_crop_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+int l1_crop_blocks() { return 1024; }
+
+void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
+    const long long total = rows * Wm;
+    const int nblk = l1_crop_blocks();
+    VR_LAUNCH(l1_crop_kernel, dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    VR_HIP(hipGetLastError());
+    launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
+}
+
 // One batch of train.validate_epoch (train.py:117-127): y_pred = model.predict(X); y = crop_center(y, y_pred);
 // loss = L1Loss()(y_pred, y) -- forward, crop and the mean-absolute-error reduction all on the device.
 void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int T, float* loss_out) {
@@ -1365,7 +1373,7 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     const size_t in_floats = (size_t)B * 2 * output_bin * T;
     const int Wm = T - 2 * offset;
     const size_t out_floats = (size_t)B * 2 * output_bin * Wm;
-    const int nblk = 1024;
+    const int nblk = l1_crop_blocks();
     fold_eval_affines();                    // before planning, as in forward_api
     plan_and_reserve(B, T, (2 * in_floats + out_floats + nblk + 64) * sizeof(float) + 8192);
     float* xd = ws.allocf(in_floats);
@@ -1388,12 +1396,9 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
     launch_head_sigmoid(f3, out_w->dev, d, stream);
-    const long long total = (long long)out_floats;
-    VR_LAUNCH((mul_crop_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, xd, od, T, Wm, offset, total);
-    VR_HIP(hipGetLastError());
-    VR_LAUNCH(l1_crop_kernel, dim3(nblk), dim3(256), 0, stream, od, yd, T, Wm, offset, total, part);
-    VR_HIP(hipGetLastError());
-    launch_reduce_rows(part, 1, nblk, lossd, 1, 0, (float)(1.0 / (double)total), stream);
+    const long long rows = (long long)B * 2 * output_bin;
+    launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
+    launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
     float loss_h = 0.f;
     VR_HIP(hipMemcpyAsync(&loss_h, lossd, sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));

@@ -135,7 +135,8 @@ static void launch_head(const Tensor& x_in, const float* w, const HeadDst& d_in,
     // Model::crop_window the stage-3 dec1 does not even compute them)
     const int q0 = (d_in.w_lo > 0 ? d_in.w_lo : 0) / 4;
     const int q1 = ((d_in.w_hi < x_in.W ? d_in.w_hi : x_in.W) + 3) / 4;
-    VR_CHECK(q1 > q0, -2, "mask head: empty column window");
+    // (q1 > q0 alone lets an empty window inside one group through, (5, 5): a launch that writes nothing)
+    VR_CHECK(q1 > q0 && d_in.w_hi > d_in.w_lo, -2, "mask head: empty column window");
     VR_CHECK(!d_in.items || d_in.item_pitch, -2, "mask head: a destination table needs its pitch table");
     Tensor x = x_in;
     x.p += (long long)q0 * 4; x.W = (q1 - q0) * 4;
