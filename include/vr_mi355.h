@@ -125,6 +125,42 @@ int vr_separate(vr_handle h, const float* spec, int spec_on_device, int T, int t
 int vr_separate_wave(vr_handle h, const float* wave, int wave_on_device, int64_t L, int tta, int batchsize,
                      int cropsize, float* y_wave, float* v_wave, int out_on_device);
 
+/* ---- WAV sample bytes in, PCM16 stems out: the file's encoding handled by the first and the last kernel -----------------
+ * What python -m vocal_remover_amd.inference did on the host around vr_separate_wave -- audio._decode (interleaved PCM -> planar
+ * float32) in front, audio.write's clip(rint(x * 32767)) behind -- done where the samples pass through registers anyway: the STFT
+ * reads the file's bytes, the masked iSTFT writes the file's bytes.  No extra pass, no extra launch, and the transfers carry the
+ * file's sample size instead of float32.  The arithmetic is csrc/pcm.h, compiled for both sides:
+ *   in   `bytes`: `frames` interleaved frames of `channels` (1 or 2) samples in format `fmt`:
+ *          VR_PCM_S16  v / 32768            VR_PCM_S24  little-endian, sign-extended, / 2^23
+ *          VR_PCM_S32  (float)((double)v / 2^31)       VR_PCM_F32  IEEE float32 as stored
+ *        -- bit for bit the float32 audio._decode produces.  One channel: both network channels read the one sample
+ *        (inference.py:143-145).  8-bit PCM and float64 files stay on the host path.
+ *   out  int16 [samples][2] interleaved: clip(rint(x * 32767), -32768, 32767), round-half-even, of the very float the float entry
+ *        point would have stored; +-inf clip, NaN gives 0.
+ * Alignment: a VR_PCM_S24 buffer may start at any byte (the kernel reads aligned 32-bit words and assembles straddling samples in
+ * registers); DEVICE buffers of VR_PCM_S16 / S32 / F32 need their natural alignment and device int16 outputs 2 bytes, else
+ * VR_ERR_BAD_ARGUMENT (host buffers are copied through the staging arena and may lie anywhere).
+ * Only the frame-tiled kernels have these forms.  vr_pcm_available says whether the handle has them: hop_length == n_fft / 2 (every
+ * reference call site), n_fft >= 128 and small enough for the tile to fit the LDS budget, VR_NO_TILED_STFT unset.  Without them
+ * every call below is VR_ERR_BAD_ARGUMENT with the reason, and the caller converts on the host as before.  Host buffers are staged in the handle's
+ * staging arena (vr_arena_bytes): no allocation per call once it has grown.
+ *   vr_stft_pcm          vr_stft of the decoded bytes: spec [2, bins, 1 + frames / hop]
+ *   vr_istft_pcm16       vr_istft, encoded: out [hop * (T - 1)][2]
+ *   vr_separate_pcm      vr_separate_wave with bytes at both ends: y, v int16 [hop * (frames / hop)][2]
+ *   vr_separate_pcm_many vr_separate_wave_many likewise, format and channel count per song
+ *   vr_pcm_convert_host / vr_pcm16_from_float_host   the same header compiled for the host, no handle, no GPU: planar_out
+ *        [channels][frames] float32 (any alignment of `bytes`); out[i] = the encoding of x[i]                                   */
+enum vr_pcm_format { VR_PCM_S16 = 1, VR_PCM_S24 = 2, VR_PCM_S32 = 3, VR_PCM_F32 = 4 };
+int vr_pcm_available(vr_handle h, int* available);
+int vr_stft_pcm(vr_handle h, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* spec, int spec_on_device);
+int vr_istft_pcm16(vr_handle h, const float* spec, int on_device, int T, int16_t* out, int out_on_device);
+int vr_separate_pcm(vr_handle h, const void* bytes, int on_device, int64_t frames, int channels, int fmt, int tta, int batchsize,
+                    int cropsize, int16_t* y, int16_t* v, int out_on_device);
+int vr_separate_pcm_many(vr_handle h, int n_songs, const void* const* bytes, int on_device, const int64_t* frames, const int* channels,
+                         const int* fmt, int tta, int batchsize, int cropsize, int16_t* const* y, int16_t* const* v, int out_on_device);
+int vr_pcm_convert_host(int fmt, const void* bytes, int64_t frames, int channels, float* planar_out);
+int vr_pcm16_from_float_host(const float* x, int64_t n, int16_t* out);
+
 /* ---- many songs in one call: what pseudo.py:40-74 (a dataset) and a folder of inputs do one file at a time ------------
  * Separator.separate[_tta] for n_songs spectrograms of different lengths in ONE call.
  * specs[s]: [2,bins,T[s]] complex64; y_specs[s], v_specs[s]: same shape.  tta (flag word) / cropsize as vr_separate.
@@ -178,6 +214,10 @@ typedef struct vr_stream_s* vr_stream;
 #define VR_STREAM_TTA         1   /* second pass shifted by roi/2, masks averaged (separate_tta)                  */
 #define VR_STREAM_MEASURE     2   /* no network, no output: only accumulate the normaliser                        */
 #define VR_STREAM_POSTPROCESS 4   /* refused: see above                                                           */
+/* y / v of vr_stream_push, vr_stream_flush and vr_stream_push_many are int16 [capacity][2] interleaved (pass them cast to float*):
+ * the encoding of vr_separate_pcm of the very floats the stream would have returned.  capacity and n_out still count samples per
+ * channel; the input stays planar float.  All streams of one vr_stream_push_many call must agree on it (VR_ERR_BAD_ARGUMENT).   */
+#define VR_STREAM_PCM16_OUT   8
 int vr_stream_open(vr_handle h, int cropsize, int batchsize, int flags, double coef_re, double coef_im, vr_stream* out);
 int vr_stream_push(vr_stream s, const float* wave, int on_device, int64_t n, float* y, float* v, int out_on_device, int64_t capacity,
                    int64_t* n_out);

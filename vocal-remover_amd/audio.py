@@ -20,8 +20,44 @@ from . import native
 _PCM, _FLOAT, _EXT = 1, 3, 0xFFFE
 
 
+class RawPcm(object):
+    """Sample bytes as a WAV file holds them, for the entry points that decode on the device (Separator.separate_pcm,
+    spec_utils.pcm_to_spectrogram): `bytes` = whole interleaved frames as a uint8 array (numpy, or a torch cuda tensor), `fmt` =
+    native.VR_PCM_S16 / S24 / S32 / F32, `channels` 1 or 2, `sr`, `frames`."""
+
+    def __init__(self, data, fmt, channels, sr, frames=None):
+        self.bytes, self.fmt, self.channels, self.sr = data, int(fmt), int(channels), int(sr)
+        self.frames = int(data.shape[0]) // (native.PCM_SAMPLE_BYTES[self.fmt] * self.channels) if frames is None else int(frames)
+
+
+def _device_format(tag, ch, bits):
+    """the vr_pcm_format the device decodes for this encoding, or None (8-bit PCM, float64, more than two channels: host path)"""
+    if ch not in (1, 2):
+        return None
+    return {(_PCM, 16): native.VR_PCM_S16, (_PCM, 24): native.VR_PCM_S24, (_PCM, 32): native.VR_PCM_S32,
+            (_FLOAT, 32): native.VR_PCM_F32}.get((tag, bits))
+
+
+def read_wav_raw(path):
+    """The data chunk of a RIFF/WAVE file as it is -> RawPcm, or None for an encoding the device does not take (read_wav decodes
+    those).  Nothing is converted: `.bytes` is a view of the file's bytes, whole frames only."""
+    tag, ch, rate, align, bits, body = _read_chunks(path)
+    fmt = _device_format(tag, ch, bits)
+    if fmt is None or align != ch * native.PCM_SAMPLE_BYTES[fmt]:
+        return None
+    n = len(body) // align
+    return RawPcm(np.frombuffer(body, np.uint8, n * align), fmt, ch, rate, n)
+
+
 def read_wav(path):
     """-> (float32 array [channels, samples] in [-1, 1), sample rate); soundfile.read(..., dtype='float32').T"""
+    tag, ch, rate, align, bits, body = _read_chunks(path)
+    n = len(body) // align
+    return _decode(path, body[:n * align], tag, ch, bits), int(rate)
+
+
+def _read_chunks(path):
+    """-> (format tag, channels, rate, block align, bits, the data chunk's bytes)"""
     with open(path, 'rb') as f:
         data = f.read()
     if len(data) < 12 or data[:4] != b'RIFF' or data[8:12] != b'WAVE':
@@ -42,8 +78,7 @@ def read_wav(path):
     if fmt is None or body is None:
         raise ValueError('%s: missing fmt or data chunk' % path)
     tag, ch, rate, align, bits = fmt
-    n = len(body) // align
-    return _decode(path, body[:n * align], tag, ch, bits), int(rate)
+    return tag, ch, int(rate), align, bits, body
 
 
 def _decode(path, body, tag, ch, bits):
@@ -117,6 +152,26 @@ class WavBlockReader(object):
                 yield _decode(self.path, body[:n * self._align], self._tag, self.channels, self._bits)
                 left -= n
 
+    def raw_blocks(self, block_samples):
+        """blocks() without the decoding: an iterator of RawPcm, <= block_samples frames each, or None for an encoding the device
+        does not take."""
+        fmt = _device_format(self._tag, self.channels, self._bits)
+        if fmt is None or self._align != self.channels * native.PCM_SAMPLE_BYTES[fmt]:
+            return None
+
+        def gen():
+            with open(self.path, 'rb') as f:
+                f.seek(self._data_pos)
+                left = self.samples
+                while left > 0:
+                    body = f.read(min(int(block_samples), left) * self._align)
+                    n = len(body) // self._align
+                    if n == 0:
+                        break
+                    yield RawPcm(np.frombuffer(body, np.uint8, n * self._align), fmt, self.channels, self.sr, n)
+                    left -= n
+        return gen()
+
 
 class WavAppendWriter(object):
     """write()'s 16-bit PCM file, grown block by block: append(data [samples, channels]); close() patches the two sizes."""
@@ -129,12 +184,16 @@ class WavAppendWriter(object):
         self._f.write(b'data' + struct.pack('<I', 0))
 
     def append(self, data):
-        data = np.asarray(data, dtype=np.float32)
+        """data [samples, channels]: float32 is encoded as write() encodes it; an int16 array (Stream(pcm16=True)) is written as it is."""
+        data = np.asarray(data)
+        pcm = data.dtype == np.int16
+        if not pcm:
+            data = np.asarray(data, dtype=np.float32)
         if data.ndim == 1:
             data = data[:, None]
         if data.shape[1] != self._ch:
             raise ValueError('append: expected [samples, %d]' % self._ch)
-        body = np.clip(np.rint(data * 32767.0), -32768, 32767).astype('<i2').tobytes()
+        body = data.astype('<i2', copy=False).tobytes() if pcm else np.clip(np.rint(data * 32767.0), -32768, 32767).astype('<i2').tobytes()
         self._f.write(body)
         self._bytes += len(body)
 
@@ -164,6 +223,22 @@ def write(path, data, sr):
     n, ch = data.shape
     pcm = np.clip(np.rint(data * 32767.0), -32768, 32767).astype('<i2')
     body = pcm.tobytes()
+    with open(path, 'wb') as f:
+        f.write(b'RIFF' + struct.pack('<I', 36 + len(body)) + b'WAVE')
+        f.write(b'fmt ' + struct.pack('<IHHIIHH', 16, _PCM, ch, int(sr), int(sr) * ch * 2, ch * 2, 16))
+        f.write(b'data' + struct.pack('<I', len(body)) + body)
+
+
+def write_pcm16(path, pcm, sr):
+    """write() for samples that are already encoded: pcm int16 [samples, channels] (Separator.separate_pcm) -> the same file bytes
+    write() produces for the floats they came from."""
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16:
+        raise ValueError('write_pcm16 takes int16 samples (write() encodes float32)')
+    if pcm.ndim == 1:
+        pcm = pcm[:, None]
+    n, ch = pcm.shape
+    body = pcm.astype('<i2', copy=False).tobytes()
     with open(path, 'wb') as f:
         f.write(b'RIFF' + struct.pack('<I', 36 + len(body)) + b'WAVE')
         f.write(b'fmt ' + struct.pack('<IHHIIHH', 16, _PCM, ch, int(sr), int(sr) * ch * 2, ch * 2, 16))

@@ -200,6 +200,53 @@ int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, i
     });
 }
 
+// ---- WAV sample bytes in, PCM16 out (csrc/pcm.h; the host converters are pcm_host.cpp) ------------------------------------------
+int vr_pcm_available(vr_handle h, int* available) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(available, VR_ERR_BAD_ARGUMENT, "null argument");
+        *available = h->m.pcm_available() ? 1 : 0;
+    });
+}
+
+int vr_stft_pcm(vr_handle h, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* spec, int spec_on_device) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(bytes && spec, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.stft_pcm_api(bytes, on_device != 0, frames, channels, fmt, spec, spec_on_device != 0);
+    });
+}
+
+int vr_istft_pcm16(vr_handle h, const float* spec, int on_device, int T, int16_t* out, int out_on_device) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(spec && out, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.istft_pcm16_api(spec, on_device != 0, T, out, out_on_device != 0);
+    });
+}
+
+int vr_separate_pcm(vr_handle h, const void* bytes, int on_device, int64_t frames, int channels, int fmt, int tta, int batchsize,
+                    int cropsize, int16_t* y, int16_t* v, int out_on_device) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(bytes && y && v, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.separate_pcm_api(bytes, on_device != 0, frames, channels, fmt, tta, batchsize, cropsize, y, v, out_on_device != 0);
+    });
+}
+
+int vr_separate_pcm_many(vr_handle h, int n_songs, const void* const* bytes, int on_device, const int64_t* frames, const int* channels,
+                         const int* fmt, int tta, int batchsize, int cropsize, int16_t* const* y, int16_t* const* v, int out_on_device) {
+    if (!many_args_ok(n_songs, bytes, frames, y, v)) return VR_ERR_BAD_ARGUMENT;
+    if (!channels || !fmt) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(frames, frames + n_songs);
+        h->m.separate_many_api(n_songs, reinterpret_cast<const float* const*>(bytes), on_device != 0, nullptr, len.data(), tta, batchsize,
+                               cropsize, reinterpret_cast<float* const*>(y), reinterpret_cast<float* const*>(v), out_on_device != 0, channels,
+                               fmt);
+    });
+}
+
 // ---- streaming separation ----------------------------------------------------------------------------------------------------
 struct vr_stream_s {
     vr_model* h;

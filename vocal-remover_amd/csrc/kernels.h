@@ -175,6 +175,12 @@ void launch_istft(const FFTPlan& pl, const float2* spec, int hop, int T, float* 
 bool istft_masked_available(const FFTPlan& pl, int hop);
 void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
                          int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st);
+// The sample-format forms of the two tile kernels (hop == n_fft / 2 only; csrc/pcm.h): the STFT reads interleaved WAV sample bytes, the
+// masked iSTFT (mask_a null: plain) writes interleaved int16 [hop * (T-1)][2] = pcm16_from_float of the float it would have stored.
+struct PcmIn { const uint8_t* bytes; int channels; int fmt; };   // frames of `channels` (1: up-mixed) samples, fmt = vr_pcm_format
+void launch_stft_pcm(const FFTPlan& pl, const PcmIn& in, long long L, int T, float2* spec, hipStream_t st);
+void launch_istft_masked_pcm16(const FFTPlan& pl, const float2* spec, int hop, int T, bool cplx, const float* mask_a, int Wa,
+                               const float* mask_b, int Wb, int shift, const float* wgt, int which, int16_t* out, hipStream_t st);
 // mag_pad [2][bins][Wpad] (pre-zeroed) <- |spec| at column pad_l + t; maxima into stats:
 // per-row partial maxima into stats (16 B header + 2 x bins rows of (max |X| bits, 64-bit lexicographic complex key))
 void launch_mag_pad(const float2* spec, int bins, int T, float* mag_pad, int Wpad, int pad_l,
@@ -221,7 +227,9 @@ struct SongSeg {
     float* fmin;              // [T] the song's per-frame mask minima (--postprocess)
 };
 bool many_tiled_available(const FFTPlan& pl, int hop);       // hop == n_fft / 2: the tile kernels below exist
-void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st);
+// pcm (device, one per song): the songs' sample bytes are read in place of the table's `wave` (pcm_bytes: the profiler's note)
+void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st,
+                      const PcmIn* pcm = nullptr, double pcm_bytes = 0.0);
 // part [song][2 * bins][2]: per-row partial maxima (max |X| bits, lexicographic complex key); aff [song][4]: 1 / c as launch_coef_affine
 // (cplx: launch_coef_complex) gives it
 void launch_song_stats(const SongSeg* songs, int n_songs, int bins, double sum_T, unsigned long long* part, hipStream_t st);
@@ -234,7 +242,7 @@ void launch_frame_min_many(const SongSeg* songs, int n_songs, int max_T, int bin
 void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
                             const float* wgt, hipStream_t st);
 void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
-                              bool cplx, const float* wgt, int which, hipStream_t st);
+                              bool cplx, const float* wgt, int which, hipStream_t st, bool pcm16 = false);   // pcm16: y_wave / v_wave are int16 [samples][2]
 
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
@@ -281,6 +289,6 @@ void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bo
                           hipStream_t st);
 // segments = the largest count of output segments among the n_seg entries (an entry with none is skipped); sum_segments, tta: profiler's note
 void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int segments, double sum_segments, bool cplx, bool tta, int which,
-                         hipStream_t st);
+                         hipStream_t st, bool pcm16 = false);         // pcm16: y_wave / v_wave are int16 [capacity][2]
 
 }  // namespace vr

@@ -110,7 +110,7 @@ StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int
 // (n_fft, cropsize, batchsize, tta) only.
 struct StreamState {
     int cropsize = 0, bs = 0, roi = 0, R = 0, RM = 0, chunk_frames = 0;
-    bool tta = false, measure = false, running = false;
+    bool tta = false, measure = false, running = false, pcm16 = false;
     bool flushed = false, broken = false;
     long long samples = 0, tail_base = 0;
     long long frames = 0, crops[2] = {0, 0}, done = 0;
@@ -191,13 +191,21 @@ public:
     // spec [2,bins,T] complex64 -> y_spec, v_spec (same shape)
     void separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize,
                       float* y_spec, float* v_spec, bool out_on_dev, bool io_reserved = false,
-                      float* y_wave_d = nullptr, float* v_wave_d = nullptr);
+                      float* y_wave_d = nullptr, float* v_wave_d = nullptr, bool pcm16_out = false);
     // wave [2,L] -> y_wave, v_wave [2, hop*(T-1)]: whole inference.py pipeline, device resident
     void separate_wave_api(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
                            float* y_wave, float* v_wave, bool out_on_dev);
     // n_songs spectrograms (L null: specs [2,bins,T[s]] -> y / v spectrograms) or waves (L given: [2,L[s]] -> y / v waves) in one call
     void separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta,
-                           int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev);
+                           int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
+                           const int* pcm_fmt = nullptr);
+    // ---- WAV sample bytes in, PCM16 out (vr_*_pcm*; csrc/pcm.h): the sample-format forms of the frame-tiled STFT / iSTFT ----
+    bool pcm_available() const;                           // the frame-tiled kernels, whose forms these are, exist on this handle
+    void check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const;      // availability, format, channels, a device pointer's alignment
+    void stft_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, float* spec, bool spec_on_dev);
+    void istft_pcm16_api(const float* spec, bool on_dev, int T, int16_t* out, bool out_on_dev);
+    void separate_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, int tta, int batchsize, int cropsize,
+                          int16_t* y, int16_t* v, bool out_on_dev);
     void run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops);
     // ---- streaming separation (vr_stream_*) ----
     StreamState* stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im);
@@ -210,7 +218,7 @@ public:
     void stream_close(StreamState* S);
     void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
     void separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                            float* y_wave, float* v_wave, bool out_on_dev);
+                            float* y_wave, float* v_wave, bool out_on_dev, const PcmIn* pcm = nullptr);
 
     // ---- debug / test hooks ----
     void debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,

@@ -1,5 +1,6 @@
 // Host side of libvr_mi355.so: see model.h.  Topology follows lib/nets.py:8-141 and
 // lib/layers.py:8-133 of the reference; parameter keys are the reference's state_dict keys.
+#include "pcm.h"
 #include "model.h"
 
 #include <algorithm>
@@ -1448,6 +1449,64 @@ void Model::istft_api(const float* spec, bool on_dev, int T, float* wave, bool w
     VR_HIP(hipStreamSynchronize(stream));
 }
 
+// ---- WAV sample bytes in, PCM16 out (vr_*_pcm*): the format forms of the two tile kernels, csrc/pcm.h --------------------------------
+bool Model::pcm_available() const { return istft_masked_available(plan, hop); }
+
+// bytes: a DEVICE pointer to check for its samples' natural alignment, or null (host buffers are copied into the aligned staging arena)
+void Model::check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const {
+    VR_CHECK(pcm_available(), -2, who + "the sample-format kernels are forms of the frame-tiled STFT / iSTFT, which this handle does not have "
+                                        "(they need hop_length == n_fft / 2, n_fft >= 128, the tile inside the LDS budget, VR_NO_TILED_STFT "
+                                        "unset: vr_pcm_available); convert on the host and use the float entry point");
+    VR_CHECK(pcm_fmt_ok(fmt), -2, who + "unknown sample format " + std::to_string(fmt) + " (VR_PCM_S16 / S24 / S32 / F32)");
+    VR_CHECK(channels == 1 || channels == 2, -2, who + "1 or 2 channels, not " + std::to_string(channels));
+    if (bytes && fmt != VR_PCM_S24)
+        VR_CHECK(reinterpret_cast<uintptr_t>(bytes) % (uintptr_t)pcm_sample_bytes(fmt) == 0, -2,
+                 who + "the sample buffer is not aligned to its " + std::to_string(pcm_sample_bytes(fmt)) + "-byte samples (only VR_PCM_S24 may start at any byte)");
+}
+
+void Model::stft_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, float* spec, bool spec_on_dev) {
+    check_pcm(on_dev ? bytes : nullptr, channels, fmt, "");
+    DeviceGuard dev_guard(device);
+    VR_CHECK(L > 0, -2, "empty wave");
+    VR_CHECK(L / hop < (1LL << 30), -2, "wave too long");
+    const int T = 1 + (int)(L / hop);
+    const size_t spec_f = (size_t)2 * output_bin * T * 2;
+    const size_t in_b = (size_t)L * channels * pcm_sample_bytes(fmt);
+    ensure_io(in_b + spec_f * sizeof(float) + 4096);
+    io.reset();
+    PcmIn in{static_cast<const uint8_t*>(bytes), channels, fmt};
+    if (!on_dev) {
+        void* tmp = io.alloc(in_b + 4);
+        VR_HIP(hipMemcpyAsync(tmp, bytes, in_b, hipMemcpyHostToDevice, stream));
+        in.bytes = static_cast<const uint8_t*>(tmp);
+    }
+    float* sd = spec_on_dev ? spec : io.allocf(spec_f);
+    launch_stft_pcm(plan, in, L, T, reinterpret_cast<float2*>(sd), stream);
+    if (!spec_on_dev) VR_HIP(hipMemcpyAsync(spec, sd, spec_f * sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
+void Model::istft_pcm16_api(const float* spec, bool on_dev, int T, int16_t* out, bool out_on_dev) {
+    check_pcm(nullptr, 2, VR_PCM_S16, "");
+    if (out_on_dev) VR_CHECK(reinterpret_cast<uintptr_t>(out) % 2 == 0, -2, "the int16 output is not 2-byte aligned");
+    DeviceGuard dev_guard(device);
+    VR_CHECK(T > 0, -2, "empty spectrogram");
+    const size_t spec_f = (size_t)2 * output_bin * T * 2;
+    const size_t out_n = (size_t)2 * hop * (T - 1);
+    ensure_io(spec_f * sizeof(float) + out_n * 2 + 8192);
+    io.reset();
+    const float* sd = spec;
+    if (!on_dev) {
+        float* tmp = io.allocf(spec_f);
+        VR_HIP(hipMemcpyAsync(tmp, spec, spec_f * sizeof(float), hipMemcpyHostToDevice, stream));
+        sd = tmp;
+    }
+    int16_t* od = out_on_dev ? out : static_cast<int16_t*>(io.alloc(out_n * 2 + 16));
+    launch_istft_masked_pcm16(plan, reinterpret_cast<const float2*>(sd), hop, T, false, nullptr, 0, nullptr, 0, 0, nullptr, 0, od, stream);
+    if (!out_on_dev && out_n) VR_HIP(hipMemcpyAsync(out, od, out_n * 2, hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipStreamSynchronize(stream));
+}
+
 // spec_utils.merge_artifacts (lib/spec_utils.py:60-93) reduced to its per-frame weight vector
 // (the reference builds a [2, bins, T] weight that is constant over channel and bin).  numpy slice
 // semantics are kept: negative starts wrap, a slice/linspace length mismatch is numpy's ValueError,
@@ -1555,7 +1614,7 @@ void Model::run_crop_chunks(int patches, int bs, const std::function<void(int, i
 }
 
 void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize, float* y_spec,
-                         float* v_spec, bool out_on_dev, bool io_reserved, float* y_wave_d, float* v_wave_d) {
+                         float* v_spec, bool out_on_dev, bool io_reserved, float* y_wave_d, float* v_wave_d, bool pcm16_out) {
     DeviceGuard dev_guard(device);
     const bool post = (tta & 2) != 0;       // flags: bit 0 = --tta, bit 1 = --postprocess
     tta &= 1;
@@ -1660,7 +1719,10 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
         // wave-level caller: mask application, inverse FFT, window and overlap-add in one pass per stem -- the y / v
         // spectrograms (inference.py:32-38) are never materialised
         for (int which = 0; which < 2; ++which) {
-            if (is_complex)
+            if (pcm16_out)       // (y_wave_d / v_wave_d are int16 [samples][2]: the encode is the kernel's store)
+                launch_istft_masked_pcm16(plan, reinterpret_cast<const float2*>(sd), hop, T, is_complex, mask[0], Wm[0], tta ? mask[1] : nullptr,
+                                          Wm[1], roi / 2, wgt, which, reinterpret_cast<int16_t*>(which ? v_wave_d : y_wave_d), stream);
+            else if (is_complex)
                 launch_istft_masked_complex(plan, reinterpret_cast<const float2*>(sd), hop, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
                                             tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, wgt, which,
                                             which ? v_wave_d : y_wave_d, stream);
@@ -1693,8 +1755,21 @@ void Model::separate_wave_api(const float* wave, bool on_dev, long long L, int t
     separate_wave_body(wave, on_dev, L, tta, batchsize, cropsize, y_wave, v_wave, out_on_dev);
 }
 
+void Model::separate_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, int tta, int batchsize, int cropsize,
+                             int16_t* y, int16_t* v, bool out_on_dev) {
+    check_pcm(on_dev ? bytes : nullptr, channels, fmt, "");
+    if (out_on_dev)
+        VR_CHECK(reinterpret_cast<uintptr_t>(y) % 2 == 0 && reinterpret_cast<uintptr_t>(v) % 2 == 0, -2, "the int16 outputs are not 2-byte aligned");
+    DeviceGuard dev_guard(device);
+    VR_CHECK(L >= hop, -2, "wave shorter than one hop");
+    VR_CHECK(L / hop < (1LL << 30), -2, "wave too long");
+    const PcmIn in{static_cast<const uint8_t*>(bytes), channels, fmt};
+    separate_wave_body(nullptr, on_dev, L, tta, batchsize, cropsize, reinterpret_cast<float*>(y), reinterpret_cast<float*>(v), out_on_dev, &in);
+}
+
+// pcm: the input is pcm->bytes (interleaved sample bytes, `wave` unused) and y_wave / v_wave are int16 [samples][2]
 void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                               float* y_wave, float* v_wave, bool out_on_dev) {
+                               float* y_wave, float* v_wave, bool out_on_dev, const PcmIn* pcm) {
     // VR_ENQ_TIMING=1 (diagnostics): host time to ENQUEUE the whole call vs the time until the device has drained it
     static const bool enq_timing = getenv("VR_ENQ_TIMING") != nullptr;
     const auto enq_t0 = std::chrono::steady_clock::now();
@@ -1714,22 +1789,37 @@ void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int 
     const size_t out_f = (size_t)2 * hop * (T - 1);
     const size_t frames_f = (size_t)2 * T * n_fft;
     const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta, is_complex ? 2 : 1);
-    ensure_io(((size_t)2 * L + 3 * spec_f + 2 * out_f + frames_f + scratch) * sizeof(float) + 65536);
+    // (pcm: the staged input holds the file's sample bytes, the staged stems int16 -- half the floats)
+    const size_t in_b = pcm ? (size_t)L * pcm->channels * pcm_sample_bytes(pcm->fmt) : (size_t)2 * L * sizeof(float);
+    const size_t in_f = pcm ? in_b / 4 + 1 : (size_t)2 * L, stage_f = pcm ? out_f / 2 : out_f;
+    ensure_io((in_f + 3 * spec_f + 2 * out_f + frames_f + scratch) * sizeof(float) + 65536);
     io.reset();
-    float* stage_in = io.allocf((size_t)2 * L);
+    float* stage_in = io.allocf(in_f);
+    const void* src = pcm ? static_cast<const void*>(pcm->bytes) : wave;
     const float* wd = wave;
     if (!on_dev) {
-        VR_HIP(hipMemcpyAsync(stage_in, wave, (size_t)2 * L * sizeof(float), hipMemcpyHostToDevice, stream));
+        VR_HIP(hipMemcpyAsync(stage_in, src, in_b, hipMemcpyHostToDevice, stream));
         wd = stage_in;
+        src = stage_in;
     }
     float* spec = io.allocf(spec_f);
     float* ys = io.allocf(spec_f);
     float* vs = io.allocf(spec_f);
     float* frames = io.allocf(frames_f);
-    float* stage_y = io.allocf(out_f + 4);
-    float* stage_v = io.allocf(out_f + 4);
+    float* stage_y = io.allocf(stage_f + 4);
+    float* stage_v = io.allocf(stage_f + 4);
     float* yw = out_on_dev ? y_wave : stage_y;
     float* vw = out_on_dev ? v_wave : stage_v;
+    if (pcm) {                                  // (check_pcm: the tiled kernels exist; L >= hop: out_f > 0)
+        launch_stft_pcm(plan, PcmIn{static_cast<const uint8_t*>(src), pcm->channels, pcm->fmt}, L, T, reinterpret_cast<float2*>(spec), stream);
+        separate_api(spec, true, T, tta, batchsize, cropsize, ys, vs, true, /*io_reserved=*/true, yw, vw, /*pcm16_out=*/true);
+        if (!out_on_dev) {
+            VR_HIP(hipMemcpyAsync(y_wave, yw, out_f * 2, hipMemcpyDeviceToHost, stream));
+            VR_HIP(hipMemcpyAsync(v_wave, vw, out_f * 2, hipMemcpyDeviceToHost, stream));
+        }
+        VR_HIP(hipStreamSynchronize(stream));
+        return;
+    }
     launch_stft(plan, wd, L, hop, T, reinterpret_cast<float2*>(spec), stream);
     if (istft_masked_available(plan, hop) && out_f) {
         separate_api(spec, true, T, tta, batchsize, cropsize, ys, vs, true, /*io_reserved=*/true, yw, vw);
@@ -1752,10 +1842,13 @@ void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int 
 // zero outside the song), and crop n's mask lands at column n * roi of one concatenated mask [2][bins][W].  Front end and back end
 // are one launch each for all songs (song = a grid dimension, kernels.h SongSeg), so the launch count does not depend on n_songs.
 void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta,
-                              int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev) {
+                              int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels,
+                              const int* pcm_fmt) {
     const bool post = (tta & 2) != 0;       // flags: bit 0 = --tta, bit 1 = --postprocess
     tta &= 1;
     const bool waves = L != nullptr;
+    // vr_separate_pcm_many: in[s] are interleaved sample bytes (format and channel count per song), y[s] / v[s] int16 [samples][2]
+    const bool pcm = pcm_fmt != nullptr;
     // ---- arguments and the host-side plan: nothing here touches the device
     VR_CHECK(n_songs > 0, -2, "n_songs must be positive");
     VR_CHECK(in && y && v && (waves || T_in), -2, "null table");
@@ -1773,6 +1866,10 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
         if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
         else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
         if (waves) VR_CHECK(L[s] / hop < (1LL << 30), -2, who + "wave too long");
+        if (pcm) {
+            check_pcm(in_on_dev ? in[s] : nullptr, pcm_channels[s], pcm_fmt[s], who);
+            if (out_on_dev) VR_CHECK(reinterpret_cast<uintptr_t>(y[s]) % 2 == 0 && reinterpret_cast<uintptr_t>(v[s]) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
+        }
         Song& g = sg[s];
         g.T = waves ? 1 + (int)(L[s] / hop) : T_in[s];
         int pad_r;
@@ -1798,12 +1895,19 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     std::vector<SongSeg> tab((size_t)n_songs);
     std::vector<float*> stage_in((size_t)n_songs), stage_y((size_t)n_songs), stage_v((size_t)n_songs);
     SongSeg* tab_d = nullptr; int2* crops_d = nullptr;
+    std::vector<PcmIn> pin(pcm ? (size_t)n_songs : 0);
+    PcmIn* pin_d = nullptr;
+    double pcm_bytes = 0.0;
+    auto in_bytes = [&](int s) {
+        return pcm ? (size_t)L[s] * pcm_channels[s] * pcm_sample_bytes(pcm_fmt[s]) : (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float);
+    };
     unsigned long long* part = nullptr;
     float *aff = nullptr, *mask = nullptr, *gather = nullptr, *fmin_d = nullptr, *wgt_d = nullptr, *frames = nullptr;
     const size_t crop_f = (size_t)nin * max_bin * cropsize;
     auto carve = [&](Arena& A) {
         tab_d = static_cast<SongSeg*>(A.alloc(sizeof(SongSeg) * n_songs));
         crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * crops_n));
+        if (pcm) pin_d = static_cast<PcmIn*>(A.alloc(sizeof(PcmIn) * n_songs));
         part = static_cast<unsigned long long*>(A.alloc((size_t)n_songs * 2 * bins * 16));
         aff = A.allocf((size_t)n_songs * 4);
         mask = A.allocf((size_t)E * 2 * bins * W);
@@ -1817,13 +1921,17 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
             t.T = g.T;
             t.mcol_a = g.crop0[0] * roi;
             t.mcol_b = tta ? g.crop0[1] * roi + roi / 2 : 0;
-            stage_in[s] = in_on_dev ? nullptr : A.allocf(waves ? (size_t)2 * L[s] : g.spec_f);
+            stage_in[s] = in_on_dev ? nullptr : A.allocf(in_bytes(s) / 4 + (pcm ? 1 : 0));
             const float* src = in_on_dev ? in[s] : stage_in[s];
             if (waves) {
                 t.wave = src; t.L = L[s];
+                if (pcm) {                            // the STFT reads the bytes through the PcmIn table; the stems are int16
+                    t.wave = nullptr;
+                    pin[s] = PcmIn{reinterpret_cast<const uint8_t*>(src), pcm_channels[s], pcm_fmt[s]};
+                }
                 t.spec = reinterpret_cast<float2*>(A.allocf(g.spec_f));
-                stage_y[s] = out_on_dev ? y[s] : A.allocf(g.out_f + 4);
-                stage_v[s] = out_on_dev ? v[s] : A.allocf(g.out_f + 4);
+                stage_y[s] = out_on_dev ? y[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
+                stage_v[s] = out_on_dev ? v[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
                 t.y_wave = stage_y[s]; t.v_wave = stage_v[s];
                 if (!tiled) {                         // general hop: masked spectrograms, then the per-frame inverse per song
                     t.y = reinterpret_cast<float2*>(A.allocf(g.spec_f));
@@ -1855,12 +1963,17 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     }
     VR_HIP(hipMemcpyAsync(tab_d, tab.data(), sizeof(SongSeg) * n_songs, hipMemcpyHostToDevice, stream));
     VR_HIP(hipMemcpyAsync(crops_d, crops.data(), sizeof(int2) * crops_n, hipMemcpyHostToDevice, stream));
+    if (pcm) {
+        VR_HIP(hipMemcpyAsync(pin_d, pin.data(), sizeof(PcmIn) * n_songs, hipMemcpyHostToDevice, stream));
+        for (int s = 0; s < n_songs; ++s) pcm_bytes += (double)in_bytes(s);
+    }
     if (!in_on_dev)
         for (int s = 0; s < n_songs; ++s)
-            VR_HIP(hipMemcpyAsync(stage_in[s], in[s], (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float), hipMemcpyHostToDevice, stream));
+            VR_HIP(hipMemcpyAsync(stage_in[s], in[s], in_bytes(s), hipMemcpyHostToDevice, stream));
     // ---- front end
     if (waves) {
-        if (tiled) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
+        if (pcm) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream, pin_d, pcm_bytes);   // (check_pcm: tiled)
+        else if (tiled) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
         else for (int s = 0; s < n_songs; ++s) launch_stft(plan, tab[s].wave, L[s], hop, sg[s].T, tab[s].spec, stream);
     }
     launch_song_stats(tab_d, n_songs, bins, (double)sum_T, part, stream);
@@ -1908,7 +2021,7 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     }
     if (waves && tiled) {
         for (int which = 0; which < 2; ++which)
-            launch_istft_masked_many(plan, tab_d, n_songs, max_T, (double)sum_T, mask, W, tta, is_complex, wgt, which, stream);
+            launch_istft_masked_many(plan, tab_d, n_songs, max_T, (double)sum_T, mask, W, tta, is_complex, wgt, which, stream, pcm);
     } else {
         launch_apply_mask_many(tab_d, n_songs, max_T, bins, mask, W, tta, is_complex, wgt, stream);
         if (waves)
@@ -1921,8 +2034,8 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
         for (int s = 0; s < n_songs; ++s) {
             const size_t nf = waves ? sg[s].out_f : sg[s].spec_f;
             if (!nf) continue;
-            VR_HIP(hipMemcpyAsync(y[s], stage_y[s], nf * sizeof(float), hipMemcpyDeviceToHost, stream));
-            VR_HIP(hipMemcpyAsync(v[s], stage_v[s], nf * sizeof(float), hipMemcpyDeviceToHost, stream));
+            VR_HIP(hipMemcpyAsync(y[s], stage_y[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
+            VR_HIP(hipMemcpyAsync(v[s], stage_v[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
         }
     VR_HIP(hipStreamSynchronize(stream));
 }
@@ -1971,7 +2084,8 @@ static float host_unord32(unsigned o) {
 
 StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im) {
     // ---- arguments: nothing here touches the device
-    VR_CHECK(!(flags & ~7), -2, "unknown vr_stream_open flag");
+    VR_CHECK(!(flags & ~15), -2, "unknown vr_stream_open flag");
+    VR_CHECK(!((flags & 8) && (flags & 2)), -2, "VR_STREAM_PCM16_OUT on a VR_STREAM_MEASURE stream: it returns no samples");
     VR_CHECK(!(flags & 4), -2, "a stream cannot run --postprocess: merge_artifacts looks at runs of frames over the whole song; use vr_separate_wave");
     VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
     VR_CHECK(hop * 2 == n_fft && stream_tiled_available(plan, hop), -2,
@@ -1984,6 +2098,7 @@ StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double c
     VR_CHECK(measure || (std::isfinite(coef_re) && std::isfinite(coef_im)), -2, "coef must be finite");
     std::unique_ptr<StreamState> S(new StreamState);
     S->cropsize = cropsize; S->tta = tta; S->measure = measure; S->running = running;
+    S->pcm16 = (flags & 8) != 0;                // y / v are int16 [capacity][2]: the last kernel's store encodes
     S->bs = batchsize > 0 ? batchsize : 8;               // (a stream never sees "all crops": <= 0 means 8)
     const int roi = cropsize - 2 * offset, bins = output_bin, E = is_complex ? 2 : 1;
     S->roi = roi;
@@ -2165,7 +2280,7 @@ void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
     }
     if (sp.emit)
         for (int which = 0; which < 2; ++which)
-            launch_istft_stream(plan, o.seg_d, 1, sp.segments, (double)sp.segments, is_complex, S.tta, which, stream);
+            launch_istft_stream(plan, o.seg_d, 1, sp.segments, (double)sp.segments, is_complex, S.tta, which, stream, S.pcm16);
     stream_step_commit(S, o, sp);
 }
 
@@ -2182,6 +2297,8 @@ void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long lon
     if (need > 0)
         VR_CHECK(y && v && capacity >= need, -2, "output capacity " + std::to_string(capacity) + " is too small: this call returns " +
                                                      std::to_string(need) + " samples per channel");
+    if (S.pcm16 && need > 0 && out_on_dev)
+        VR_CHECK(reinterpret_cast<uintptr_t>(y) % 2 == 0 && reinterpret_cast<uintptr_t>(v) % 2 == 0, -2, "the int16 outputs are not 2-byte aligned");
     if (n_out) *n_out = 0;
     if (n == 0 && !flush) return;
 
@@ -2228,7 +2345,10 @@ void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long lon
         st.resize((size_t)2 * 2 * output_bin);
         VR_HIP(hipMemcpyAsync(st.data(), reinterpret_cast<unsigned long long*>(S.stats) + 2, st.size() * 8, hipMemcpyDeviceToHost, stream));
     }
-    if (!out_on_dev && need > 0) {
+    if (!out_on_dev && need > 0 && S.pcm16) {       // interleaved int16: `need` frames of 4 bytes, one piece
+        VR_HIP(hipMemcpyAsync(y, stage_y, (size_t)need * 4, hipMemcpyDeviceToHost, stream));
+        VR_HIP(hipMemcpyAsync(v, stage_v, (size_t)need * 4, hipMemcpyDeviceToHost, stream));
+    } else if (!out_on_dev && need > 0) {
         VR_HIP(hipMemcpy2DAsync(y, (size_t)capacity * 4, stage_y, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpy2DAsync(v, (size_t)capacity * 4, stage_v, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
     }
@@ -2279,6 +2399,8 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
         VR_CHECK(!S.running, -2, who + "a running-normaliser stream (coef 0) is not taken by vr_stream_push_many: its steps are cut per crop, "
                                        "use vr_stream_push");
         VR_CHECK(!S.broken, -2, who + "this stream failed in an earlier call: close it");
+        VR_CHECK(S.pcm16 == Sv[0]->pcm16, -2, who + "VR_STREAM_PCM16_OUT differs from stream 0's: the streams of one call share the masked iSTFT "
+                                                   "launch, which stores one sample format");
         const bool fl = flush && flush[k];
         VR_CHECK(!S.flushed, -2, who + (fl ? "the stream is already flushed" : "push after flush"));
         const long long n = n_in[k];
@@ -2295,6 +2417,8 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
             VR_CHECK(y && v && capacity && y[k] && v[k] && capacity[k] >= need, -2,
                      who + "output capacity " + std::to_string(capacity ? capacity[k] : 0) + " is too small: this call returns " +
                          std::to_string(need) + " samples per channel");
+        if (S.pcm16 && need > 0 && out_on_dev)
+            VR_CHECK(reinterpret_cast<uintptr_t>(y[k]) % 2 == 0 && reinterpret_cast<uintptr_t>(v[k]) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
         if (batchsize <= 0) bs = std::max(bs, S.bs);
         if (n == 0 && !fl) continue;                 // untouched
         Part p{};
@@ -2424,12 +2548,15 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
             }
             if (max_seg > 0)
                 for (int which = 0; which < 2; ++which)
-                    launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream);
+                    launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream, Sv[0]->pcm16);
             for (int e = 0; e < ne; ++e) stream_step_commit(*parts[live[e]].S, parts[live[e]].o, plans[e]);
         }
         for (Part& p : parts) {
             VR_CHECK(p.o.out_off == p.need, -4, "stream schedule mismatch (planning bug)");
-            if (!out_on_dev && p.need > 0) {
+            if (!out_on_dev && p.need > 0 && p.S->pcm16) {
+                VR_HIP(hipMemcpyAsync(y[p.k], p.stage_y, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpyAsync(v[p.k], p.stage_v, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
+            } else if (!out_on_dev && p.need > 0) {
                 VR_HIP(hipMemcpy2DAsync(y[p.k], (size_t)capacity[p.k] * 4, p.stage_y, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
                 VR_HIP(hipMemcpy2DAsync(v[p.k], (size_t)capacity[p.k] * 4, p.stage_v, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
             }

@@ -13,6 +13,7 @@
 // One workgroup per frame; radix-2 FFT in LDS.  These stages are HBM-bound streaming work that is
 // <1 % of the pipeline, kept simple and exact-ordered.
 #include "kernels.h"
+#include "pcm.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -127,9 +128,42 @@ __device__ __forceinline__ void fft_lds_sub(float2* x, const float2* __restrict_
 
 constexpr int TG = 4;                        // frames in flight per workgroup (1024 threads = 4 groups of 256)
 
-template <class SRC = const float>
+template <class A> __device__ __forceinline__ A pcm_first(A a) { return a; }
+// the first type of a pack, or D for an empty one: the format arguments of the tile kernels are trailing packs, so that an instantiation
+// without one keeps its signature and its name (the launch profiler's report and the tests that read it know the kernels by name)
+template <class D, class... T> struct FirstOr { using type = D; };
+template <class D, class A, class... T> struct FirstOr<D, A, T...> { using type = A; };
+
+// Where the STFT fetches sample p of its channel, and where the iSTFT stores sample p + i of channel ch: the file's sample format is a
+// template argument of the two tile kernels, not a pass of its own (csrc/pcm.h holds the arithmetic).
+struct WaveF32In {                           // planar float32 [2][L]: the channel's row
+    const float* wv;
+    __device__ __forceinline__ float at(long long p) const { return wv[p]; }
+};
+struct WavePcmIn {                           // interleaved frames of 1 or 2 channels in a WAV sample format; a mono file is up-mixed
+    PcmIn in;
+    int ch;
+    __device__ __forceinline__ float at(long long p) const { return pcm_decode(in.bytes, in.fmt, in.channels, p, ch); }
+};
+struct WaveF32Out {                          // planar float32 [2][pitch]
+    static constexpr bool kInterleaved = false;
+    static __device__ __forceinline__ void put(float* w, long long pitch, int ch, long long p, int i, float v) { w[(long long)ch * pitch + p + i] = v; }
+};
+struct WavePcm16Out {                        // interleaved int16 [samples][2] behind the kernel's float pointer
+    static constexpr bool kInterleaved = true;
+    static __device__ __forceinline__ void put(float* w, long long, int ch, long long p, int i, float v) {
+        reinterpret_cast<int16_t*>(w)[(p + i) * 2 + ch] = pcm16_from_float(v);
+    }
+};
+
+// PCM (at most one type): none = `wave` / the song table's `wave` are planar float32, as documented above.  PcmIn (SRC = const float, `wave`
+// unused) = the call's interleaved sample bytes; const PcmIn* (SRC = const SongSeg) = one entry per song beside the song table, whose
+// `wave` pointers are then unused.  The stream form keeps float input.
+template <class SRC = const float, class... PCM>
 __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
-                                                         float2* __restrict__ spec) {
+                                                         float2* __restrict__ spec, PCM... pcm) {
+    constexpr bool kPcm = sizeof...(PCM) == 1;
+    static_assert(sizeof...(PCM) <= 1 && !(kPcm && kStream<SRC>), "one PCM source at most, none for streams");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -137,21 +171,24 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
     int t0 = blockIdx.x * F;
     const int ch = blockIdx.y;
-    const float* wv;
+    typename std::conditional<kPcm, WavePcmIn, WaveF32In>::type in;
     StreamLocal<SRC> ss{};
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_new, T) of its stream, written into the ring
         ss = wave[blockIdx.z];
         if (blockIdx.x > 0 && t0 >= ss.T - ss.t_new) return;        // (workgroup 0 always runs: it moves the input tail on)
         t0 += ss.t_new; T = ss.T;
-        wv = nullptr;
+        in.wv = nullptr;
     } else if constexpr (kSongTable<SRC>) {          // blockIdx.z = song; the grid is sized for the longest one
         const SongSeg sg = wave[blockIdx.z];
         if (t0 >= sg.T) return;
         L = sg.L; T = sg.T; spec = sg.spec;
-        wv = sg.wave + (long long)ch * L;
+        if constexpr (kPcm) in.in = pcm_first(pcm...)[blockIdx.z];
+        else in.wv = sg.wave + (long long)ch * L;
     } else {
-        wv = wave + (long long)ch * L;
+        if constexpr (kPcm) in.in = pcm_first(pcm...);
+        else in.wv = wave + (long long)ch * L;
     }
+    if constexpr (kPcm) in.ch = ch < in.in.channels ? ch : in.in.channels - 1;
     const int nf = (T - t0) < F ? (T - t0) : F;
     for (int f0 = 0; f0 < nf; f0 += TG) {
         const int f = f0 + g;
@@ -165,8 +202,8 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
                     v0 = stream_sample(ss, ch, p) * pl.window[2 * m];
                     v1 = stream_sample(ss, ch, p + 1) * pl.window[2 * m + 1];
                 } else {
-                    v0 = (p >= 0 && p < L) ? wv[p] * pl.window[2 * m] : 0.f;
-                    v1 = (p + 1 >= 0 && p + 1 < L) ? wv[p + 1] * pl.window[2 * m + 1] : 0.f;
+                    v0 = (p >= 0 && p < L) ? in.at(p) * pl.window[2 * m] : 0.f;
+                    v1 = (p + 1 >= 0 && p + 1 < L) ? in.at(p + 1) * pl.window[2 * m + 1] : 0.f;
                 }
                 zs[__brev((unsigned)m) >> (32 - logM)] = make_float2(v0, v1);
             }
@@ -219,11 +256,16 @@ __device__ __forceinline__ float2 final_mask(const float2* __restrict__ ma, int 
 
 // which: 0 = plain spectrogram (mask_a null) / instruments y = m X, 1 = vocals v = (1 - m) X
 // CPLX: the mask is complex64 (is_complex handles), y = m X and v = (1 - m) X as complex products
-template <bool CPLX, class SRC = const float2>
+// OUT (at most one type): where the samples go -- none = WaveF32Out (planar float32, as documented); WavePcm16Out: `wave` / the table's
+// y_wave, v_wave then point to interleaved int16 [samples][2] (streams: [capacity][2], segment s at sample (s - t_out) * M); the carry
+// and `prev` stay float.
+template <bool CPLX, class SRC = const float2, class... OUT>
 __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __restrict__ src, int T, int S,
                                                           const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb,
                                                           int shift, const float* __restrict__ wgt, int which,
                                                           float* __restrict__ wave, long long out_len) {
+    static_assert(sizeof...(OUT) <= 1, "one destination type at most");
+    using DST = typename FirstOr<WaveF32Out, OUT...>::type;
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, logM = pl.log2n - 1, F = S + 1;
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -347,10 +389,12 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                 const float ws = fmaf(w0, w0, w2 * w2);
                 const float a = before[i] + cur[i];
                 if constexpr (kStream<SRC>) {
-                    wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
+                    // (the float store written out: through put() hipcc allocates this instantiation's registers differently)
+                    if constexpr (DST::kInterleaved) DST::put(wave, 0, ch, (long long)(s - ss.t_out) * M, i, ws > FLT_MIN ? a / ws : a);
+                    else wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
                 } else {
                     const long long p = (long long)s * M + i;
-                    if (p < out_len) wave[(long long)ch * out_len + p] = ws > FLT_MIN ? a / ws : a;
+                    if (p < out_len) DST::put(wave, out_len, ch, p, 0, ws > FLT_MIN ? a / ws : a);
                 }
             }
         }
@@ -386,7 +430,7 @@ static bool tiled_signal_path(const FFTPlan& pl, int hop) {
     return on && hop * 2 == pl.n_fft && pl.n_fft >= 128 && tile_frames(pl, pl.n_fft / 2) >= 3;
 }
 
-template <bool CPLX>
+template <bool CPLX, class... OUT>
 static void launch_istft_tile(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
                               int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
     const int M = pl.n_fft / 2, bins = M + 1;
@@ -396,10 +440,10 @@ static void launch_istft_tile(const FFTPlan& pl, const float2* spec, int hop, in
     const int S = F - 1;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<CPLX>), 160 * 1024);
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<CPLX, const float2, OUT...>), 160 * 1024);
     // per stem: the complex spectrogram (8 B per bin-frame), the mask(s) (4 B, complex 8 B), hop samples written per frame, two channels
-    prof_note(0.0, 2.0 * ((double)bins * T * (8.0 + (CPLX ? 8.0 : 4.0) * (mask_b ? 2 : 1)) + 4.0 * (double)out_len));
-    VR_LAUNCH((istft_tile_kernel<CPLX>), dim3((unsigned)((T - 1 + S - 1) / S), 2), dim3(1024), lds, st, pl, spec, T, S, mask_a, Wa,
+    prof_note(0.0, 2.0 * ((double)bins * T * (8.0 + (CPLX ? 8.0 : 4.0) * (mask_b ? 2 : 1)) + (sizeof...(OUT) ? 2.0 : 4.0) * (double)out_len));
+    VR_LAUNCH((istft_tile_kernel<CPLX, const float2, OUT...>), dim3((unsigned)((T - 1 + S - 1) / S), 2), dim3(1024), lds, st, pl, spec, T, S, mask_a, Wa,
               mask_b, Wb, shift, wgt, which, wave, out_len);
     VR_HIP(hipGetLastError());
 }
@@ -407,6 +451,13 @@ static void launch_istft_tile(const FFTPlan& pl, const float2* spec, int hop, in
 void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, const float* mask_a, int Wa, const float* mask_b,
                          int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
     launch_istft_tile<false>(pl, spec, hop, T, mask_a, Wa, mask_b, Wb, shift, wgt, which, wave, st);
+}
+
+void launch_istft_masked_pcm16(const FFTPlan& pl, const float2* spec, int hop, int T, bool cplx, const float* mask_a, int Wa,
+                               const float* mask_b, int Wb, int shift, const float* wgt, int which, int16_t* out, hipStream_t st) {
+    float* w = reinterpret_cast<float*>(out);
+    if (cplx) launch_istft_tile<true, WavePcm16Out>(pl, spec, hop, T, mask_a, Wa, mask_b, Wb, shift, wgt, which, w, st);
+    else launch_istft_tile<false, WavePcm16Out>(pl, spec, hop, T, mask_a, Wa, mask_b, Wb, shift, wgt, which, w, st);
 }
 
 void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop, int T, const float2* mask_a, int Wa,
@@ -475,6 +526,20 @@ void launch_stft_tiled(const FFTPlan& pl, const float* wave, long long L, int T,
     ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<>), 160 * 1024);
     prof_note(0.0, 2.0 * (4.0 * (double)L + 8.0 * (double)bins * T));              // unique audio read once, complex64 spectrogram written
     VR_LAUNCH((stft_tile_kernel<>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, wave, L, T, F, spec);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stft_pcm(const FFTPlan& pl, const PcmIn& in, long long L, int T, float2* spec, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, PcmIn>), 160 * 1024);
+    prof_note(0.0, (double)pcm_sample_bytes(in.fmt) * in.channels * (double)L + 2.0 * 8.0 * (double)bins * T);
+    VR_LAUNCH((stft_tile_kernel<const float, PcmIn>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, (const float*)nullptr, L, T, F,
+              spec, in);
     VR_HIP(hipGetLastError());
 }
 
@@ -813,12 +878,22 @@ void launch_apply_mask_complex(const float2* spec, int bins, int T, const float2
 // Every launch covers all songs of the call: the song is a grid dimension sized for the longest one.
 bool many_tiled_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
 
-void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st) {
+void launch_stft_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_L, double sum_T, hipStream_t st,
+                      const PcmIn* pcm, double pcm_bytes) {
     const int M = pl.n_fft / 2, bins = M + 1;
     int F = tile_frames(pl, 0);
     if (F > 16) F = 16;
     F = F / TG * TG;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    if (pcm) {                                           // the songs' sample bytes, one PcmIn per song beside the table
+        static std::atomic<unsigned long long> attr_pcm{0};
+        ensure_lds_attr(attr_pcm, reinterpret_cast<const void*>(stft_tile_kernel<const SongSeg, const PcmIn*>), 160 * 1024);
+        prof_note(0.0, pcm_bytes + 2.0 * 8.0 * (double)bins * sum_T);
+        VR_LAUNCH((stft_tile_kernel<const SongSeg, const PcmIn*>), dim3((unsigned)((max_T + F - 1) / F), 2, n_songs), dim3(1024), lds, st, pl, songs, 0LL,
+                  0, F, (float2*)nullptr, pcm);
+        VR_HIP(hipGetLastError());
+        return;
+    }
     static std::atomic<unsigned long long> attr_done{0};
     ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const SongSeg>), 160 * 1024);
     prof_note(0.0, 2.0 * (4.0 * sum_L + 8.0 * (double)bins * sum_T));
@@ -870,15 +945,28 @@ void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bi
 }
 
 void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
-                              bool cplx, const float* wgt, int which, hipStream_t st) {
+                              bool cplx, const float* wgt, int which, hipStream_t st, bool pcm16) {
     const int M = pl.n_fft / 2, bins = M + 1;
     if (max_T < 2) return;
     const int F = tile_frames(pl, M);
     const int S = F - 1;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
     const dim3 grid((unsigned)((max_T - 1 + S - 1) / S), 2, n_songs);
-    prof_note(0.0, 2.0 * ((double)bins * sum_T * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * sum_T));
+    prof_note(0.0, 2.0 * ((double)bins * sum_T * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + (pcm16 ? 2.0 : 4.0) * (double)M * sum_T));
     const float* mb = tta ? mask : nullptr;
+    if (pcm16) {                                         // y_wave / v_wave of the table point to interleaved int16
+        if (cplx) {
+            static std::atomic<unsigned long long> attr_done{0};
+            ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const SongSeg, WavePcm16Out>), 160 * 1024);
+            VR_LAUNCH((istft_tile_kernel<true, const SongSeg, WavePcm16Out>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+        } else {
+            static std::atomic<unsigned long long> attr_done{0};
+            ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg, WavePcm16Out>), 160 * 1024);
+            VR_LAUNCH((istft_tile_kernel<false, const SongSeg, WavePcm16Out>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+        }
+        VR_HIP(hipGetLastError());
+        return;
+    }
     if (cplx) {
         static std::atomic<unsigned long long> attr_done{0};
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const SongSeg>), 160 * 1024);
@@ -926,14 +1014,27 @@ void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bo
 }
 
 void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int segments, double sum_segments, bool cplx, bool tta, int which,
-                         hipStream_t st) {
+                         hipStream_t st, bool pcm16) {
     const int M = pl.n_fft / 2, bins = M + 1;
     if (segments < 1) return;
     const int F = tile_frames(pl, M);
     const int S = F - 1;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
     const dim3 grid((unsigned)((segments + S - 1) / S), 2, (unsigned)n_seg);
-    prof_note(0.0, 2.0 * ((double)bins * sum_segments * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + 4.0 * (double)M * sum_segments));
+    prof_note(0.0, 2.0 * ((double)bins * sum_segments * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)) + (pcm16 ? 2.0 : 4.0) * (double)M * sum_segments));
+    if (pcm16) {                                         // y_wave / v_wave of the entries point to interleaved int16
+        if (cplx) {
+            static std::atomic<unsigned long long> attr_done{0};
+            ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const StreamSeg, WavePcm16Out>), 160 * 1024);
+            VR_LAUNCH((istft_tile_kernel<true, const StreamSeg, WavePcm16Out>), grid, dim3(1024), lds, st, pl, seg, 0, S, nullptr, 0, nullptr, 0, 0, nullptr, which, nullptr, 0LL);
+        } else {
+            static std::atomic<unsigned long long> attr_done{0};
+            ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const StreamSeg, WavePcm16Out>), 160 * 1024);
+            VR_LAUNCH((istft_tile_kernel<false, const StreamSeg, WavePcm16Out>), grid, dim3(1024), lds, st, pl, seg, 0, S, nullptr, 0, nullptr, 0, 0, nullptr, which, nullptr, 0LL);
+        }
+        VR_HIP(hipGetLastError());
+        return;
+    }
     if (cplx) {
         static std::atomic<unsigned long long> attr_done{0};
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const StreamSeg>), 160 * 1024);

@@ -133,10 +133,68 @@ class Separator(object):
                                                         int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0))
         return list(zip(ys, vs))
 
-    def stream(self, coef=None, tta=False):
+    def separate_pcm(self, raw, tta=False):
+        """separate_wave with the file's bytes at both ends: raw = audio.RawPcm (audio.read_wav_raw: PCM16 / 24 / 32 or float32 frames of
+        1 or 2 channels) -> (instruments, vocals) as int16 [hop*(frames//hop), 2], ready for audio.write_pcm16 -- exactly
+        clip(rint(separate_wave(decoded).T * 32767)).  The STFT kernel decodes, the masked iSTFT encodes; no host pass over the
+        samples.  numpy bytes give numpy arrays; a cuda uint8 tensor gives cuda int16 tensors.  Needs pcm_available()."""
+        return self._separate_pcm([raw], tta, one=True)[0]
+
+    def separate_pcm_many(self, raws, tta=False):
+        """separate_pcm for a list of RawPcm in ONE library call (vr_separate_pcm_many): formats and channel counts may differ per song;
+        each result is what separate_pcm returns for that song alone up to the batching bar of separate_wave_many."""
+        return self._separate_pcm(raws, tta, one=False)
+
+    def pcm_available(self):
+        """Whether this model's handle has the sample-format kernels (vr_pcm_available): they are forms of the frame-tiled STFT / iSTFT,
+        which exist for hop_length == n_fft / 2 at the n_fft sizes whose tile fits the LDS budget.  Where it is False, separate_pcm
+        and stream(pcm16=True) are refused and callers convert on the host (inference.main does)."""
+        ok = native.ctypes.c_int()
+        native.check(native.lib().vr_pcm_available(self.model._need_handle().h, native.ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def _separate_pcm(self, raws, tta, one):
+        from .spec_utils import _pcm_bytes
+        h = self.model._need_handle()
+        hop = self.model.hop_length
+        raws = list(raws)
+        if not raws:
+            raise ValueError('separate_pcm_many needs at least one song')
+        self.model.eval()
+        prepared = [_pcm_bytes(r) for r in raws]
+        on_dev = all(p[2] for p in prepared)
+        if not on_dev and any(p[2] for p in prepared):
+            raise ValueError('separate_pcm_many: either every song is a cuda tensor or none is')
+        lens = [int(r.frames) for r in raws]
+        if on_dev:
+            import torch
+            dev = prepared[0][0].device
+            ys = [torch.empty((hop * (n // hop), 2), dtype=torch.int16, device=dev) for n in lens]
+            vs = [torch.empty_like(a) for a in ys]
+            torch.cuda.current_stream(dev).synchronize()
+            addr = lambda a: a.data_ptr()
+        else:
+            ys = [np.empty((hop * (n // hop), 2), dtype=np.int16) for n in lens]
+            vs = [np.empty_like(a) for a in ys]
+            addr = lambda a: a.ctypes.data
+        ct, N = native.ctypes, len(raws)
+        if one:
+            native.check(native.lib().vr_separate_pcm(h.h, prepared[0][1], 1 if on_dev else 0, lens[0], raws[0].channels, raws[0].fmt,
+                                                      self._flags(tta), int(self.batchsize), int(self.cropsize), addr(ys[0]), addr(vs[0]),
+                                                      1 if on_dev else 0), native.VRArgumentError)
+        else:
+            native.check(native.lib().vr_separate_pcm_many(
+                h.h, N, native.ptr_table([p[1] for p in prepared]), 1 if on_dev else 0, (ct.c_int64 * N)(*lens),
+                (ct.c_int * N)(*[r.channels for r in raws]), (ct.c_int * N)(*[r.fmt for r in raws]), self._flags(tta), int(self.batchsize),
+                int(self.cropsize), native.ptr_table([addr(a) for a in ys]), native.ptr_table([addr(a) for a in vs]), 1 if on_dev else 0),
+                native.VRArgumentError)
+        return list(zip(ys, vs))
+
+    def stream(self, coef=None, tta=False, pcm16=False):
         """A streaming session on this model: see Stream.  coef: the normaliser of the whole input (measure_coef); None (plain only)
-        = a running normaliser over the audio received so far, which is NOT the offline result."""
-        return Stream(self, coef, tta)
+        = a running normaliser over the audio received so far, which is NOT the offline result.  pcm16: the stems come back as int16
+        [n_out, 2], encoded by the last kernel as audio.write encodes them (VR_STREAM_PCM16_OUT); the input stays float."""
+        return Stream(self, coef, tta, pcm16=pcm16)
 
     def push_many(self, streams, waves, flush=False, batchsize=None):
         """One vr_stream_push_many call: streams[k] (opened by self.stream) receives waves[k] ([2, n], or None for nothing) and, where
@@ -176,13 +234,14 @@ class Separator(object):
                 raise ValueError('stream %d: wave must be [2, n]' % k)
         lens = [0 if w is None else int(w.shape[1]) for w in waves]
         caps = [max(st._need(n, f), 1) for st, n, f in zip(streams, lens, fl)]       # (a flush below one hop of input raises here)
+        pcm = [st.pcm16 for st in streams]           # (mixed: the library refuses the call; an int16 buffer is [capacity, 2])
         if on_dev:
-            ys = [torch.empty((2, c), dtype=torch.float32, device=dev) for c in caps]
+            ys = [torch.empty((c, 2) if q else (2, c), dtype=torch.int16 if q else torch.float32, device=dev) for c, q in zip(caps, pcm)]
             vs = [torch.empty_like(a) for a in ys]
             torch.cuda.current_stream(dev).synchronize()
             addr = lambda a: a.data_ptr()
         else:
-            ys = [np.empty((2, c), dtype=np.float32) for c in caps]
+            ys = [np.empty((c, 2) if q else (2, c), dtype=np.int16 if q else np.float32) for c, q in zip(caps, pcm)]
             vs = [np.empty_like(a) for a in ys]
             addr = lambda a: a.ctypes.data
         table = lambda seq: (ct.c_void_p * N)(*[(addr(a) if a is not None and a.shape[1] else 0) or None for a in seq])
@@ -191,13 +250,13 @@ class Separator(object):
         native.check(native.lib().vr_stream_push_many(
             N, (ct.c_void_p * N)(*[st._s.value for st in streams]), table(waves), 1 if on_dev else 0, (ct.c_int64 * N)(*lens),
             (ct.c_int * N)(*[1 if f else 0 for f in fl]), int(self.batchsize if batchsize is None else batchsize), table(ys), table(vs),
-            1 if on_dev else 0, (ct.c_int64 * N)(*caps), got))
+            1 if on_dev else 0, (ct.c_int64 * N)(*caps), got), native.VRArgumentError if any(pcm) else ValueError)
         for st, n, f in zip(streams, lens, fl):
             if n or f:
                 st._samples += n
                 st._dev_out = on_dev
                 st._device = dev if on_dev else st._device
-        return [(a[:, :int(g)], b[:, :int(g)]) for a, b, g in zip(ys, vs, got)]
+        return [(a[:int(g)], b[:int(g)]) if q else (a[:, :int(g)], b[:, :int(g)]) for a, b, g, q in zip(ys, vs, got, pcm)]
 
     def flush_many(self, streams):
         """Stream.flush for every stream of the list in one call."""
@@ -219,18 +278,22 @@ class Stream(object):
     0), flush() -> the rest; the concatenation is what separate_wave returns for the whole input when `coef` is that call's normaliser
     (Separator.measure_coef).  numpy in, numpy out; a torch cuda tensor in, cuda tensors out.  Use as a context manager or close()."""
 
-    def __init__(self, sep, coef, tta, measure=False):
+    def __init__(self, sep, coef, tta, measure=False, pcm16=False):
         m = sep.model
+        self.pcm16 = bool(pcm16)                 # push / flush return int16 [n_out, 2] instead of float32 [2, n_out]
         self._handle = m._need_handle()
         self._geom = (m.n_fft, m.hop_length, int(sep.cropsize), m.offset, bool(tta))
         self.measure = measure
         m.eval()
         flags = (native.VR_STREAM_TTA if tta else 0) | (native.VR_STREAM_MEASURE if measure else 0)
         flags |= native.VR_STREAM_POSTPROCESS if sep.postprocess else 0          # (the library refuses it with its reason)
+        flags |= native.VR_STREAM_PCM16_OUT if self.pcm16 else 0
         c = complex(coef) if coef is not None else 0j
         self._s = native.ctypes.c_void_p()
+        # (every refusal of a pcm16 stream -- open, push, flush, push_many -- is a VRArgumentError, as from the other sample-format calls)
+        self._arg_error = native.VRArgumentError if self.pcm16 else ValueError
         native.check(native.lib().vr_stream_open(self._handle.h, int(sep.cropsize), int(sep.batchsize), flags, c.real, c.imag,
-                                                 native.ctypes.byref(self._s)))
+                                                 native.ctypes.byref(self._s)), self._arg_error)
         self._samples = 0
         info = [native.ctypes.c_int64() for _ in range(3)]
         native.check(native.lib().vr_stream_info(self._s, *[native.ctypes.byref(i) for i in info]))
@@ -267,20 +330,22 @@ class Stream(object):
         if on_dev:
             dev = wave.device if not flush else self._device
             self._device = dev
-            y = torch.empty((2, cap), dtype=torch.float32, device=dev)
+            y = torch.empty((cap, 2) if self.pcm16 else (2, cap), dtype=torch.int16 if self.pcm16 else torch.float32, device=dev)
             v = torch.empty_like(y)
             torch.cuda.current_stream(dev).synchronize()
             yp, vp, wp = y.data_ptr(), v.data_ptr(), (wave.data_ptr() if not flush and n else None)
         else:
-            y = np.empty((2, cap), dtype=np.float32)
+            y = np.empty((cap, 2) if self.pcm16 else (2, cap), dtype=np.int16 if self.pcm16 else np.float32)
             v = np.empty_like(y)
             yp, vp, wp = native.np_ptr(y), native.np_ptr(v), (native.np_ptr(wave) if not flush and n else None)
         if flush:
-            native.check(native.lib().vr_stream_flush(self._s, yp, vp, 1 if on_dev else 0, cap, native.ctypes.byref(got)))
+            native.check(native.lib().vr_stream_flush(self._s, yp, vp, 1 if on_dev else 0, cap, native.ctypes.byref(got)), self._arg_error)
         else:
             native.check(native.lib().vr_stream_push(self._s, wp, 1 if on_dev else 0, n, yp, vp, 1 if on_dev else 0, cap,
-                                                     native.ctypes.byref(got)))
+                                                     native.ctypes.byref(got)), self._arg_error)
         self._samples += n
+        if self.pcm16:
+            return y[:int(got.value)], v[:int(got.value)]
         return y[:, :int(got.value)], v[:, :int(got.value)]
 
     _dev_out, _device = False, None
@@ -374,25 +439,33 @@ def _stream_reader(path, sr, block_seconds, resample=False, device=None):
     return _StreamSource(path, sr, block_seconds, resample, device).blocks
 
 
-def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False):
+def _rows(a, pcm16):
+    """a block of stems as WavAppendWriter.append takes it: [samples, 2] -- int16 as it is, float32 [2, n] transposed"""
+    a = _host(a)
+    return a if pcm16 else a.T
+
+
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False):
     """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
     written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed -- unless
     resample=True, which reads both passes at the file's own rate through an audio.StreamResampler (bounded state; the blocks stay on
-    the device from the upload to the stems); the stems are written at `sr`, as the offline path writes them."""
+    the device from the upload to the stems); the stems are written at `sr`, as the offline path writes them.  pcm16: the stream
+    returns the stems as the file's int16 samples (Separator.stream(pcm16=True)); the files are byte for byte the same."""
     from . import audio
     blocks = _stream_reader(path, sr, block_seconds, resample, sp.model._need_handle().device)
     coef = sp.measure_coef(blocks(), tta=tta)
-    with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, sp.stream(coef=coef, tta=tta) as s:
+    with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, \
+            sp.stream(coef=coef, tta=tta, pcm16=pcm16) as s:
         for b in blocks():
             y, v = s.push(b)
-            wy.append(_host(y).T)
-            wv.append(_host(v).T)
+            wy.append(_rows(y, pcm16))
+            wv.append(_rows(v, pcm16))
         y, v = s.flush()
-        wy.append(_host(y).T)
-        wv.append(_host(v).T)
+        wy.append(_rows(y, pcm16))
+        wv.append(_rows(v, pcm16))
 
 
-def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False):
+def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False):
     """--stream on a directory: stream_file for a group of WAVs at once.  Every file's normaliser is measured first; then the files
     advance together, one block each per Separator.push_many call, so their crops share device batches; a file that ends is flushed
     in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k].
@@ -412,7 +485,7 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
     with contextlib.ExitStack() as stack:
         wy = [stack.enter_context(audio.WavAppendWriter(oy, sr, 2)) for oy, _ in outs]
         wv = [stack.enter_context(audio.WavAppendWriter(ov, sr, 2)) for _, ov in outs]
-        streams = [stack.enter_context(sp.stream(coef=c, tta=tta)) for c in coefs]
+        streams = [stack.enter_context(sp.stream(coef=c, tta=tta, pcm16=pcm16)) for c in coefs]
         rs = [stack.enter_context(src.resampler()) if src.resamples else None for src in sources]
         its = [src.raw() for src in sources]
         ahead = [next(it, None) for it in its]
@@ -428,8 +501,8 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
                 for i, y in zip(sel, done):
                     cur[i] = y
             for k, (y, v) in zip(live, sp.push_many([streams[k] for k in live], cur, ends)):
-                wy[k].append(_host(y).T)
-                wv[k].append(_host(v).T)
+                wy[k].append(_rows(y, pcm16))
+                wv[k].append(_rows(v, pcm16))
             live = [k for k, end in zip(live, ends) if not end]
 
 
@@ -498,23 +571,50 @@ def main(argv=None):
         audio.write('{}{}_Instruments.wav'.format(output_dir, basename), y_wave.T, sr)
         audio.write('{}{}_Vocals.wav'.format(output_dir, basename), v_wave.T, sr)
 
+    # The file's own sample bytes in, the stems' int16 samples out (separate_pcm / Stream(pcm16=True)): the frame-tiled kernels decode
+    # and encode.  A file at another rate (the resampler works on floats), an 8-bit or float64 file and a handle without the tiled
+    # kernels (a general hop, n_fft below 128 or too large for the tile) take the old route.
+    tiled = sp.pcm_available()                   # (asked of the library: hop == n_fft / 2 alone does not give the tiled kernels at every n_fft)
+
+    def load_raw(path):
+        raw = audio.read_wav_raw(path) if tiled else None
+        return raw if raw is not None and raw.sr == args.sr else None
+
+    def write_pcm(path, y_pcm, v_pcm, sr):
+        basename = os.path.splitext(os.path.basename(path))[0]
+        audio.write_pcm16('{}{}_Instruments.wav'.format(output_dir, basename), _host(y_pcm), sr)
+        audio.write_pcm16('{}{}_Vocals.wav'.format(output_dir, basename), _host(v_pcm), sr)
+
     if args.stream and os.path.isdir(args.input):
         for group in expand_inputs(args.input, args.songs_per_call):      # the group's files advance together, block by block
             names = [os.path.splitext(os.path.basename(path))[0] for path in group]
             stream_files(sp, group, [('{}{}_Instruments.wav'.format(output_dir, b), '{}{}_Vocals.wav'.format(output_dir, b)) for b in names],
-                         args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True)
+                         args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled)
         return 0
     if args.stream:
         basename = os.path.splitext(os.path.basename(args.input))[0]
         stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
-                    args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True)
+                    args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled)
         return 0
     if not os.path.isdir(args.input):
+        raw = load_raw(args.input)
+        if raw is not None:
+            y_pcm, v_pcm = sp.separate_pcm(raw, tta=args.tta)
+            write_pcm(args.input, y_pcm, v_pcm, raw.sr)
+            return 0
         X, sr = load(args.input)
         y_wave, v_wave = sp.separate_wave(X, tta=args.tta)  # STFT -> separate -> iSTFT x2 in one device-resident call
         write(args.input, y_wave, v_wave, sr)
         return 0
     for group in expand_inputs(args.input, args.songs_per_call):
+        raws = [(path, load_raw(path)) for path in group]
+        fresh = [(path, raw) for path, raw in raws if raw is not None]
+        if fresh:                                # the group's files the device decodes share one call; the others the old one
+            for (path, raw), (y_pcm, v_pcm) in zip(fresh, sp.separate_pcm_many([raw for _, raw in fresh], tta=args.tta)):
+                write_pcm(path, y_pcm, v_pcm, raw.sr)
+        group = [path for path, raw in raws if raw is None]
+        if not group:
+            continue
         loaded = [load(path) for path in group]
         stems = sp.separate_wave_many([X for X, _ in loaded], tta=args.tta)      # the crops of the group's songs share device batches
         for path, (_, sr), (y_wave, v_wave) in zip(group, loaded, stems):

@@ -11,7 +11,9 @@ LIB_PATH = os.environ.get('VR_LIB_PATH') or os.path.join(_HERE, 'libvr_mi355.so'
 
 c_f32p = ctypes.c_void_p
 VR_CREATE_COMPLEX = 1         # include/vr_mi355.h
-VR_STREAM_TTA, VR_STREAM_MEASURE, VR_STREAM_POSTPROCESS = 1, 2, 4
+VR_STREAM_TTA, VR_STREAM_MEASURE, VR_STREAM_POSTPROCESS, VR_STREAM_PCM16_OUT = 1, 2, 4, 8
+VR_PCM_S16, VR_PCM_S24, VR_PCM_S32, VR_PCM_F32 = 1, 2, 3, 4          # enum vr_pcm_format
+PCM_SAMPLE_BYTES = {VR_PCM_S16: 2, VR_PCM_S24: 3, VR_PCM_S32: 4, VR_PCM_F32: 4}
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 
 _SIGNATURES = {
@@ -40,6 +42,16 @@ _SIGNATURES = {
     'vr_separate_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_pcm_available': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    'vr_stft_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int]),
+    'vr_istft_pcm16': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    'vr_separate_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5
+                        + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    'vr_separate_pcm_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
+                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_pcm_convert_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_f32p]),
+    'vr_pcm16_from_float_host': (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_void_p]),
     'vr_stream_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                       ctypes.POINTER(ctypes.c_void_p)]),
     'vr_stream_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, c_f32p, ctypes.c_int,
@@ -139,8 +151,14 @@ class VRError(RuntimeError):
     pass
 
 
-def check(rc):
-    """Map vr_status to the exception the reference would raise at the same spot."""
+class VRArgumentError(VRError, ValueError):
+    """VR_ERR_BAD_ARGUMENT of the sample-format entry points (vr_*_pcm*, VR_STREAM_PCM16_OUT): the ValueError every other entry point
+    raises for it, and a VRError like every other refusal of the library."""
+
+
+def check(rc, arg_error=ValueError):
+    """Map vr_status to the exception the reference would raise at the same spot.  arg_error: what VR_ERR_BAD_ARGUMENT raises (the
+    sample-format entry points pass VRArgumentError)."""
     if rc >= 0:
         return rc
     msg = lib().vr_last_error().decode('utf-8', 'replace')
@@ -151,7 +169,7 @@ def check(rc):
     if rc == -7:
         raise IndexError(msg)              # merge_artifacts on a mask with no frame above the threshold
     if rc == -2:
-        raise ValueError(msg)
+        raise arg_error(msg)
     if rc == -8:
         raise VRError('libvr_mi355 RCCL error: %s' % msg)
     raise VRError('libvr_mi355 error %d: %s' % (rc, msg))

@@ -74,6 +74,50 @@ def spectrogram_to_wave(spec, hop_length=1024):
     return wave[0] if mono else wave
 
 
+def _pcm_bytes(raw):
+    """-> (uint8 array or cuda tensor of raw's whole frames, its address, on the device)"""
+    n = raw.frames * raw.channels * native.PCM_SAMPLE_BYTES[raw.fmt]
+    b = raw.bytes
+    try:
+        import torch
+    except ImportError:              # pragma: no cover
+        torch = None
+    if torch is not None and torch.is_tensor(b) and b.is_cuda:
+        if b.dtype != torch.uint8 or b.ndim != 1 or b.numel() < n or not b.is_contiguous():
+            raise ValueError('raw.bytes must be a contiguous 1-D uint8 tensor of at least %d bytes' % n)
+        torch.cuda.current_stream(b.device).synchronize()
+        return b, b.data_ptr(), True
+    b = np.ascontiguousarray(np.asarray(b.cpu().numpy() if torch is not None and torch.is_tensor(b) else b, dtype=np.uint8).reshape(-1))
+    if b.shape[0] < n:
+        raise ValueError('raw.bytes holds %d bytes, %d frames need %d' % (b.shape[0], raw.frames, n))
+    return b, b.ctypes.data, False
+
+
+def pcm_to_spectrogram(raw, hop_length, n_fft):
+    """wave_to_spectrogram(audio._decode(...)) without the host decode: raw = audio.RawPcm (audio.read_wav_raw) -> the same
+    [2, n_fft/2+1, 1 + frames//hop] complex64, bit for bit; the STFT kernel reads the sample bytes (a mono file is up-mixed).
+    hop_length must be n_fft / 2; a misaligned PCM16 / PCM32 / float32 cuda buffer is refused (native.VRError)."""
+    b, addr, on_dev = _pcm_bytes(raw)
+    T = 1 + raw.frames // hop_length
+    spec = np.empty((2, n_fft // 2 + 1, T), dtype=np.complex64)
+    h = _signal_handle(n_fft, hop_length)
+    native.check(native.lib().vr_stft_pcm(h.h, addr, 1 if on_dev else 0, raw.frames, raw.channels, raw.fmt, native.np_ptr(spec), 0),
+                 native.VRArgumentError)
+    return spec
+
+
+def spectrogram_to_pcm16(spec, hop_length=1024):
+    """clip(rint(spectrogram_to_wave(spec).T * 32767)) as int16 [hop * (T - 1), 2], the encode done by the iSTFT kernel's store."""
+    spec = np.ascontiguousarray(np.asarray(spec).astype(np.complex64))
+    if spec.ndim != 3 or spec.shape[0] != 2:
+        raise ValueError('spec must be [2, bins, T]')
+    bins, T = spec.shape[1], spec.shape[2]
+    out = np.empty((hop_length * (T - 1), 2), dtype=np.int16)
+    h = _signal_handle(2 * (bins - 1), hop_length)
+    native.check(native.lib().vr_istft_pcm16(h.h, native.np_ptr(spec), 0, T, out.ctypes.data, 0), native.VRArgumentError)
+    return out
+
+
 def _head_lag(a, b, sr, seconds=4):
     """Lag (samples, positive = `a` starts late) at which the first `seconds` of the two stereo waves, summed to mono with the
     mean removed, correlate best -- argmax of the full cross-correlation, evaluated on the GPU (vr_xcorr_argmax)."""
