@@ -140,3 +140,239 @@ def l1_crop(pred, y, off):
     """mean |pred [rows][Wm] - y [rows][T] at columns off .. off + Wm|."""
     pred = np.asarray(pred, np.float64)
     return float(np.abs(pred - np.asarray(y, np.float64)[:, off:off + pred.shape[1]]).mean())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one conv launch in its general form: concatenated strided sources, split strided destinations, a column window
+# ---------------------------------------------------------------------------------------------------------------------------------
+CANARY_BITS = 0x7FC12345          # the quiet NaN every destination buffer is filled with outside its prior contents
+NO_SPLIT = 1 << 30                # hsplit / d1 / d2 of a launch that does not split
+
+
+def _src(C, H, W, up=0, layout='dense', aff0=False, aff1=False, hsplit=None, slope=1.0, post=False):
+    return dict(C=C, H=H, W=W, up=up, layout=layout, aff0=aff0, aff1=aff1, hsplit=hsplit, slope=slope, post=post)
+
+
+def _dst(layout='dense', accumulate=0, present=1):
+    return dict(layout=layout, accumulate=accumulate, present=present)
+
+
+_ALL6 = lambda a, b, c, d='conv_dma_kernel': {(3, 1): a, (2, 1): b, (0, 1): c, (3, 0): d, (2, 0): d, (0, 0): d}    # noqa: E731
+
+
+def _case(name, N, Cout, srcs, runs, dsts=None, d=(NO_SPLIT, NO_SPLIT), KS=3, dil=(1, 1), epi=True, bias=False, part=False, window=None,
+          data=None):
+    # data: what the random values are drawn by (cases that must share their values name the same one)
+    return dict(name=name, N=N, Cout=Cout, srcs=srcs, runs=runs, dsts=dsts or [_dst()], d=d, KS=KS, dil=dil, epi=epi, bias=bias,
+                part=part, window=window, data=data or name)
+
+
+def _pending_cases():
+    """b: the training form.  Source 0 arrives with two BatchNorms split at a row, LeakyReLU and a Dropout2d multiplier."""
+    out = []
+    for tag, N, H, W, kern in (('ws', 4, 64, 64, 'conv_ws_kernel'), ('mfma', 1, 16, 32, 'conv_mfma_kernel')):
+        runs = {(3, 1): kern, (0, 0): kern}
+        for hs in (5, 8, H):
+            out.append(_case('%s_hsplit%d' % (tag, hs), N, 64, [_src(8, H, W, aff0=True, aff1=True, hsplit=hs, slope=0.01, post=True),
+                                                               _src(8, H, W)], runs, epi=False, part=True))
+        out.append(_case('%s_up_affine' % tag, N, 64, [_src(8, H, W, aff0=True, aff1=True, hsplit=5, slope=0.01, post=True),
+                                                       _src(8, H // 2, W // 2, up=1, aff0=True, slope=0.01)], runs, epi=False, part=True))
+    return out
+
+
+WINDOWS = ((0, None), (32, 64), (40, 56), (31, 65), (64, None), (70, 200))      # None: the width
+
+
+def _window_cases():
+    """d: conv_x3h's output-column window; `window_W_full` is the full-width launch the others must equal bit for bit."""
+    out = []
+    for W in (96, 80):
+        srcs = [_src(10, 16, W), _src(12, 8, W // 2, up=1)]
+        runs = {(3, 1): 'conv_x3h_kernel'}
+        out.append(_case('window_%d_full' % W, 2, 32, srcs, runs, data='window_%d' % W))
+        for lo, hi in WINDOWS:
+            hi = W if hi is None else hi
+            out.append(_case('window_%d_%d_%d' % (W, lo, hi), 2, 32, srcs, runs, window=(lo, hi), data='window_%d' % W))
+    return out
+
+
+# The case table of tests/test_gpu_conv_launch.py and of the pin in tests/test_cpu_kernel_refs.py.  runs: (mfma_mode, transformed weights)
+# -> the kernel launch_conv must take.  Shapes are the smallest at which the form can still go wrong.
+CONV_LAUNCH_CASES = [
+    # a. plain concatenations, eval form (no pending arithmetic, epilogue on)
+    _case('cat2_5_12', 2, 32, [_src(5, 12, 32), _src(12, 12, 32)],             # the first 8-channel chunk straddles the boundary; Cin 17
+          _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_dma_kernel')),      # is below wino_pick's 24-channel floor
+    _case('cat2_13_20', 2, 32, [_src(13, 12, 32), _src(20, 12, 32)], _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_wino_kernel')),
+    _case('cat3_dec1', 2, 16, [_src(16, 24, 64), _src(16, 24, 64), _src(17, 24, 64)],
+          _ALL6('conv_thin_kernel', 'conv_thin_kernel', 'conv_thin_kernel', 'conv_thin_kernel')),
+    _case('cat2_13x48', 2, 64, [_src(9, 13, 48), _src(24, 13, 48)], _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_wino_kernel'),
+          bias=True),                                                          # odd H, partial 32-column tile
+    _case('decoder', 2, 32, [_src(16, 6, 16, up=1), _src(8, 6, 16, up=1), _src(9, 12, 32)],
+          _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_mfma_kernel', 'conv_mfma_kernel')),
+    _case('decoder_up_second', 2, 32, [_src(9, 12, 32), _src(16, 6, 16, up=1), _src(8, 6, 16, up=1)],
+          _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_mfma_kernel', 'conv_mfma_kernel')),
+    _case('strided', 3, 32, [_src(6, 12, 32, layout='band'), _src(10, 12, 32, layout='roll')],
+          _ALL6('conv_x3h_kernel', 'conv_x3_kernel', 'conv_dma_kernel')),
+    _case('strided_thin', 3, 16, [_src(6, 12, 32, layout='band'), _src(10, 12, 32, layout='roll')],
+          {(3, 1): 'conv_thin_kernel', (0, 0): 'conv_thin_kernel'}),
+    _case('cols16_dil42', 2, 32, [_src(24, 16, 16), _src(40, 16, 16)], {(3, 1): 'conv_x3d_kernel', (0, 0): 'conv_dma_kernel'}, dil=(4, 2)),
+    _case('cols16_1x1', 2, 64, [_src(40, 16, 16), _src(40, 16, 16), _src(48, 16, 16)],
+          {(3, 1): 'conv_x3d_kernel', (0, 0): 'conv_dma_kernel'}, KS=1, bias=True),
+] + _pending_cases() + [
+    # c. split destinations: the data-gradient form (one plain source, no epilogue)
+    _case('split_5_17', 2, 33, [_src(32, 12, 32)],
+          {(3, 1): 'conv_x3h_kernel', (2, 1): 'conv_x3_kernel', (0, 1): 'conv_wino_kernel', (0, 0): 'conv_dma_kernel'},
+          dsts=[_dst('pitch'), _dst(present=0), _dst(accumulate=1)], d=(5, 17), epi=False),
+    _case('split_5_17_all_store', 2, 33, [_src(32, 12, 32)],
+          {(3, 1): 'conv_x3h_kernel', (2, 1): 'conv_x3_kernel', (0, 1): 'conv_wino_kernel', (0, 0): 'conv_dma_kernel'},
+          dsts=[_dst('pitch'), _dst('pitch'), _dst()], d=(5, 17), epi=False),
+    _case('split_thin_3_4_5', 2, 12, [_src(32, 12, 32)], {(3, 1): 'conv_thin_kernel', (0, 0): 'conv_thin_kernel'},
+          dsts=[_dst('pitch'), _dst(accumulate=1), _dst()], d=(3, 7), epi=False),
+    _case('split_cols16_32', 2, 40, [_src(24, 16, 16)], {(3, 1): 'conv_x3d_kernel'}, dil=(4, 2),
+          dsts=[_dst(), _dst('pitch', accumulate=1)], d=(32, NO_SPLIT), epi=False),
+    _case('split_cols16_33', 2, 40, [_src(24, 16, 16)], {(3, 1): 'conv_x3d_kernel'}, dil=(4, 2),
+          dsts=[_dst('pitch'), _dst(accumulate=1)], d=(33, NO_SPLIT), epi=False),
+    _case('split_cols16_32_33', 2, 40, [_src(24, 16, 16)], {(3, 1): 'conv_x3d_kernel'}, dil=(4, 2),
+          dsts=[_dst(), _dst('pitch'), _dst(accumulate=1)], d=(32, 33), epi=False),
+] + _window_cases()
+
+
+def view_index(off, sN, sC, sH, N, C, H, W):
+    """Flat indices [N][C][H][W] of a strided view into its backing buffer."""
+    n, c, h, w = np.ogrid[:N, :C, :H, :W]
+    return off + n * sN + c * sC + h * sH + w
+
+
+def _strides(layout, N, C, H, W):
+    """(floats, off, sN, sC, sH) of a view in its backing buffer; every step a multiple of 4 floats, as the model's are."""
+    if layout == 'dense':
+        return N * C * H * W, 0, C * H * W, H * W, W
+    if layout == 'band':                  # rows [3, 3 + H) of a buffer 7 rows taller, a batch pitch above C * Hb * W
+        Hb = H + 7
+        sN = C * Hb * W + 8
+        return N * sN, 3 * W, sN, Hb * W, W
+    if layout == 'roll':                  # overlapping items cut from one [C][H][L = 64] roll, a new item every 16 columns
+        L = 64
+        assert W + (N - 1) * 16 <= L
+        return C * H * L, 0, 16, H * L, L
+    if layout == 'pitch':                 # a destination with a row, a plane and a batch pitch of its own, and an offset
+        sH = W + 4
+        sC = H * sH + 8
+        sN = C * sC + 16
+        return 12 + N * sN, 12, sN, sC, sH
+    raise ValueError(layout)
+
+
+def conv_launch_build(case):
+    """The float32 data of a case: every array the hook takes, the views as (off, sN, sC, sH).  Deterministic per case (its `data` name)."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(case['data'].encode()))
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)                          # noqa: E731
+    aff = lambda C: f32(np.stack([rng.random(C) + 0.5, rng.standard_normal(C) * 0.3], 1))    # noqa: E731
+    N, Cout, KS = case['N'], case['Cout'], case['KS']
+    srcs = []
+    for s in case['srcs']:
+        C, H, W = s['C'], s['H'], s['W']
+        floats, off, sN, sC, sH = _strides(s['layout'], N, C, H, W)
+        post = None
+        if s['post']:                       # Dropout2d: exact zeros and 1 / 0.9, both present
+            post = np.where(rng.random((N, C)) < 0.25, 0.0, 1 / 0.9)
+            post.flat[0], post.flat[1] = 0.0, 1 / 0.9
+        srcs.append(dict(C=C, H=H, W=W, up=s['up'], buf=f32(rng.standard_normal(floats)), off=off, sN=sN, sC=sC, sH=sH,
+                         aff0=aff(C) if s['aff0'] else None, aff1=aff(C) if s['aff1'] else None,
+                         hsplit=NO_SPLIT if s['hsplit'] is None else s['hsplit'], slope=s['slope'], post=None if post is None else f32(post)))
+    Cin = sum(s['C'] for s in srcs)
+    Hout, Wout = [(2 * s['H'], 2 * s['W']) if s['up'] else (s['H'], s['W']) for s in srcs][0]
+    d1, d2 = case['d']
+    edges = [0, min(d1, Cout), min(d2, Cout), Cout]
+    dsts = []
+    for i, t in enumerate(case['dsts']):
+        Cs = edges[i + 1] - edges[i]
+        if not t['present']:
+            dsts.append(None)
+            continue
+        floats, off, sN, sC, sH = _strides(t['layout'], N, Cs, Hout, Wout)
+        buf = np.full(floats, CANARY_BITS, np.uint32).view(np.float32)
+        if t['accumulate']:                 # prior, non-zero contents inside the view
+            buf[view_index(off, sN, sC, sH, N, Cs, Hout, Wout)] = f32(rng.standard_normal((N, Cs, Hout, Wout)))
+        dsts.append(dict(c0=edges[i], C=Cs, buf=buf, off=off, sN=sN, sC=sC, sH=sH, accumulate=t['accumulate']))
+    return dict(name=case['name'], N=N, Cin=Cin, Cout=Cout, KS=KS, dil=case['dil'], Hout=Hout, Wout=Wout, srcs=srcs, dsts=dsts, d=(d1, d2),
+                w=f32(rng.standard_normal((Cout, Cin, KS, KS)) / (Cin * KS * KS) ** 0.5),
+                bias=f32(rng.standard_normal(Cout)) if case['bias'] else None,
+                epi=aff(Cout) if case['epi'] else None, epi_slope=0.01 if case['epi'] else 1.0,
+                part=case['part'], window=case['window'])
+
+
+def upsample2x_align(v):
+    """Bilinear x2 with align_corners=True from its definition: output i reads the source at i (n - 1) / (2n - 1)."""
+    def taps(n):
+        x = np.arange(2 * n, dtype=np.float64) * (n - 1) / (2 * n - 1)
+        i0 = np.minimum(np.floor(x).astype(np.int64), n - 1)
+        return i0, np.minimum(i0 + 1, n - 1), x - i0
+    h0, h1, lh = taps(v.shape[2])
+    w0, w1, lw = taps(v.shape[3])
+    rows = v[:, :, h0] * (1 - lh)[None, None, :, None] + v[:, :, h1] * lh[None, None, :, None]
+    return rows[..., w0] * (1 - lw) + rows[..., w1] * lw
+
+
+def conv_launch_input(desc):
+    """The virtual input of the launch, float64 [N][Cin][Hin][Win]: per source act(raw * scale + shift) * post, then the upsample."""
+    N, parts = desc['N'], []
+    for s in desc['srcs']:
+        raw = np.asarray(s['buf'], np.float64)[view_index(s['off'], s['sN'], s['sC'], s['sH'], N, s['C'], s['H'], s['W'])]
+        v = activated(raw, s['slope'], s['aff0'], s['aff1'] if s['aff1'] is not None else s['aff0'], s['hsplit'])
+        if s['post'] is not None:
+            v = v * np.asarray(s['post'], np.float64)[:, :, None, None]
+        parts.append(upsample2x_align(v) if s['up'] else v)
+    return np.concatenate(parts, axis=1)
+
+
+def conv_launch_output(desc, x=None):
+    """(z, y): z = conv + bias [N][Cout][H][W] in float64 by direct summation over the taps, y = the epilogue affine + activation on z."""
+    x = conv_launch_input(desc) if x is None else x
+    KS, (dh, dw) = desc['KS'], desc['dil']
+    ph, pw = (dh, dw) if KS == 3 else (0, 0)
+    H, W = x.shape[2:]
+    xp = np.pad(x, ((0, 0), (0, 0), (ph, ph), (pw, pw)))
+    w = np.asarray(desc['w'], np.float64)
+    z = np.zeros((x.shape[0], w.shape[0], H, W))
+    for kh in range(KS):
+        for kw in range(KS):
+            z += np.einsum('oc,nchw->nohw', w[:, :, kh, kw], xp[:, :, kh * dh:kh * dh + H, kw * dw:kw * dw + W], optimize=True)
+    if desc['bias'] is not None:
+        z = z + np.asarray(desc['bias'], np.float64)[None, :, None, None]
+    y = z
+    if desc['epi'] is not None:
+        e = np.asarray(desc['epi'], np.float64)
+        y = z * e[None, :, 0, None, None] + e[None, :, 1, None, None]
+        y = np.where(y > 0, y, y * desc['epi_slope'])
+    return z, y
+
+
+def window_columns(desc):
+    """The output columns a launch writes: all, or those of the 32-column tiles that meet the window [w_lo, w_hi)."""
+    W = desc['Wout']
+    if desc['window'] is None:
+        return 0, W
+    lo, hi = desc['window']
+    return lo // 32 * 32, min((min(hi, W) + 31) // 32 * 32, W)
+
+
+def conv_launch_ref(desc):
+    """-> (the destinations' whole backing buffers in float64, None where absent; stats [Cout][2] = per-channel sum and sum of squares
+    of conv + bias, what the BatchNorm partials add up to).  Elements outside the views, and outside the window's tiles, keep what the
+    buffer held (the canary: NaN)."""
+    z, y = conv_launch_output(desc)
+    c_lo, c_hi = window_columns(desc)
+    bufs = []
+    for t in desc['dsts']:
+        if t is None:
+            bufs.append(None)
+            continue
+        b = np.asarray(t['buf'], np.float64).copy()
+        idx = view_index(t['off'], t['sN'], t['sC'], t['sH'], desc['N'], t['C'], desc['Hout'], desc['Wout'])[..., c_lo:c_hi]
+        val = y[:, t['c0']:t['c0'] + t['C'], :, c_lo:c_hi]
+        b[idx] = b[idx] + val if t['accumulate'] else val
+        bufs.append(b)
+    stats = np.stack([z.sum(axis=(0, 2, 3)), (z * z).sum(axis=(0, 2, 3))], 1)
+    return bufs, stats

@@ -1,7 +1,8 @@
 """Pins of oracle/kernel_refs.py, the float64 references of tests/test_gpu_heads_lstm.py and of the LSTM test of tests/test_gpu_kernels.py:
 the BiLSTM statement against torch.nn.LSTM(bidirectional=True) in float64, the two mask heads against the lines of oracle/cascaded_net.py
 (pinned in turn against the reference's own modules by tests/test_oracle_vs_reference.py), the small references against their formulas
-written a second way, and the conditions the saturated-gate LSTM cases are chosen by.  No GPU."""
+written a second way, and the conditions the saturated-gate LSTM cases are chosen by; the general conv launch of
+tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in float64, over that test's case table.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -119,3 +120,97 @@ def test_saturated_lstm_cases_meet_the_conditions_they_are_chosen_by(N, T, H):
     assert share >= 1.0 / 3
     assert max(errs) < TOL / 3
     assert all(bool(torch.isfinite(r).all()) for r in ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# conv_launch_ref: the reference of tests/test_gpu_conv_launch.py, over the same case table
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _torch_view(buf, v, N, C, H, W):
+    return torch.as_strided(buf, (N, C, H, W), (v['sN'], v['sC'], v['sH'], 1), v['off'])
+
+
+def _torch_conv_launch(desc):
+    """The launch stated with torch modules in float64: as_strided views, F.leaky_relu, F.interpolate(align_corners=True), torch.cat,
+    F.conv2d; the destinations are written through as_strided views of copies of their buffers."""
+    F = torch.nn.functional
+    N, parts = desc['N'], []
+    for s in desc['srcs']:
+        v = _torch_view(torch.from_numpy(s['buf']).double(), s, N, s['C'], s['H'], s['W']).clone()
+        hs = min(s['hsplit'], s['H'])
+        for aff, rows in ((s['aff0'], slice(0, hs)), (s['aff1'] if s['aff1'] is not None else s['aff0'], slice(hs, s['H']))):
+            if aff is not None:
+                a = torch.from_numpy(aff).double()
+                v[:, :, rows] = v[:, :, rows] * a[:, 0].view(1, -1, 1, 1) + a[:, 1].view(1, -1, 1, 1)
+        v = F.leaky_relu(v, s['slope'])
+        if s['post'] is not None:
+            v = v * torch.from_numpy(s['post']).double()[:, :, None, None]
+        if s['up']:
+            v = F.interpolate(v, scale_factor=2, mode='bilinear', align_corners=True)
+        parts.append(v)
+    x = torch.cat(parts, dim=1)
+    pad = desc['dil'] if desc['KS'] == 3 else (0, 0)
+    bias = None if desc['bias'] is None else torch.from_numpy(desc['bias']).double()
+    z = F.conv2d(x, torch.from_numpy(desc['w']).double(), bias, 1, pad, desc['dil'])
+    y = z
+    if desc['epi'] is not None:
+        e = torch.from_numpy(desc['epi']).double()
+        y = F.leaky_relu(z * e[:, 0].view(1, -1, 1, 1) + e[:, 1].view(1, -1, 1, 1), desc['epi_slope'])
+    cols = range(desc['Wout'])
+    if desc['window'] is not None:           # the 32-column tiles that meet [w_lo, w_hi)
+        lo, hi = desc['window']
+        cols = [c for c in cols if any(t * 32 <= c < t * 32 + 32 for t in range(desc['Wout'] // 32 + 1) if t * 32 < hi and t * 32 + 32 > lo)]
+    bufs = []
+    for t in desc['dsts']:
+        if t is None:
+            bufs.append(None)
+            continue
+        b = torch.from_numpy(t['buf']).double().clone()
+        view = _torch_view(b, t, N, t['C'], desc['Hout'], desc['Wout'])
+        val = y[:, t['c0']:t['c0'] + t['C']]
+        for c in cols:
+            view[..., c] = view[..., c] + val[..., c] if t['accumulate'] else val[..., c]
+        bufs.append(b.numpy())
+    return x.numpy(), bufs, torch.stack([z.sum(dim=(0, 2, 3)), (z * z).sum(dim=(0, 2, 3))], 1).numpy()
+
+
+@pytest.mark.parametrize('case', kr.CONV_LAUNCH_CASES, ids=lambda c: c['name'])
+def test_conv_launch_reference_equals_torch_modules_in_float64(case):
+    """Exact-arithmetic restatements: 1e-12 of the output scale, on the virtual input, on every element of every destination buffer
+    (the canary outside the views and the window's tiles must be NaN in both) and on the sums behind the BatchNorm partials."""
+    desc = kr.conv_launch_build(case)
+    x, bufs, stats = _torch_conv_launch(desc)
+    got_x = kr.conv_launch_input(desc)
+    got_bufs, got_stats = kr.conv_launch_ref(desc)
+    assert got_x.shape == x.shape and float(np.abs(got_x - x).max()) <= 1e-12 * float(np.abs(x).max())
+    scale = max(float(np.nanmax(np.abs(b))) for b in bufs if b is not None)
+    assert len(got_bufs) == len(bufs) and len(bufs) == len(case['dsts'])
+    written = 0
+    for got, want, t in zip(got_bufs, bufs, desc['dsts']):
+        assert (got is None) == (want is None) == (t is None)
+        if want is None:
+            continue
+        assert got.shape == want.shape and np.array_equal(np.isnan(got), np.isnan(want))
+        keep = np.isnan(want)
+        assert np.array_equal(np.asarray(t['buf'])[keep].view(np.uint32), np.full(int(keep.sum()), kr.CANARY_BITS, np.uint32))
+        assert float(np.abs(got[~keep] - want[~keep]).max()) <= 1e-12 * scale
+        written += int((~keep).sum())
+    c_lo, c_hi = kr.window_columns(desc)
+    assert written == desc['N'] * sum(t['C'] for t in desc['dsts'] if t is not None) * desc['Hout'] * (c_hi - c_lo)
+    assert float(np.abs(got_stats - stats).max()) <= 1e-12 * float(np.abs(stats).max())
+
+
+def test_conv_launch_case_table_holds_the_forms_it_is_meant_to():
+    """The properties the cases are chosen for, so an edit of the table cannot quietly lose one."""
+    by = {c['name']: kr.conv_launch_build(c) for c in kr.CONV_LAUNCH_CASES}
+    assert len(by) == len(kr.CONV_LAUNCH_CASES)
+    assert by['cat2_5_12']['srcs'][0]['C'] % 8 and by['cat2_5_12']['Cin'] < 24 <= by['cat2_13_20']['Cin']
+    s0, s1 = by['strided']['srcs']
+    assert s0['sN'] > s0['C'] * (s0['H'] + 7) * s0['W'] and s0['off'] == 3 * s0['W'] and s1['sN'] < s1['W']       # taller buffer; overlapping items
+    for d in by.values():
+        for v in d['srcs'] + [t for t in d['dsts'] if t is not None]:
+            assert all(v[k] % 4 == 0 for k in ('off', 'sN', 'sC', 'sH'))
+    p = by['ws_hsplit5']['srcs'][0]['post']
+    assert (p == 0).any() and (p == np.float32(1 / 0.9)).any() and set(np.unique(p)) == {np.float32(0), np.float32(1 / 0.9)}
+    assert by['split_5_17']['dsts'][1] is None and by['split_5_17']['dsts'][2]['accumulate'] == 1
+    assert [t['C'] for t in by['split_thin_3_4_5']['dsts']] == [3, 4, 5]
+    assert [t['C'] for t in by['split_cols16_32_33']['dsts']] == [32, 1, 7]

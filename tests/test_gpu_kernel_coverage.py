@@ -7,7 +7,8 @@ fallbacks behind the fast forms -- odd widths (frames / 16 odd), hidden sizes th
 own launch profiler (`vr_profile_begin / _end / _report`: every VR_LAUNCH of the thread) and asserts that the union of what ran covers
 every kernel the built library exports, minus a short list that is launched outside the profiler and has its own tests.
 The numerics of these paths are checked by test_gpu_parity / _kernels / _train / _configs, and those of the LSTM fallbacks, the eval mask
-heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py; here only reachability."""
+heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py; the forward conv kernels with concatenated, split and windowed
+launches, each asserting the kernel it ran, by test_gpu_conv_launch.py; here only reachability."""
 import ctypes
 import os
 import shutil

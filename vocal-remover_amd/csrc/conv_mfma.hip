@@ -403,6 +403,12 @@ double launch_conv(const ConvArgs& a_in, const ConvShape& s, hipStream_t st) {
         VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && a.w_lo >= 0 && a.w_lo < a.w_hi && !a.part && x3_pick(a, s, &x3t), -2,
                  "conv column window: only conv_x3h (mfma_mode 3, eval) takes one");
     }
+    for (int i = 0; i < a.nsrc && i < 3; ++i) {
+        // the loaders interpolate an upsampled source from ONE affine (aff0): no kernel splits its rows between two BatchNorms, and the
+        // network never asks for it (the band-stacked aux tensors are consumed at their own resolution) -- refuse it, do not compute it wrong
+        const ConvSrc& c = a.src[i];
+        VR_CHECK(!(c.up && c.aff1 && c.aff1 != c.aff0 && c.hsplit < c.H), -2, "conv: an upsampled source cannot carry a row-split affine (hsplit)");
+    }
     {
         int wmt, wth;
         int wino_mt, thin_th;

@@ -1,7 +1,9 @@
 // Test hooks (tests/ only): single kernels of the training path behind vr_debug_kernel, host pointers in and out,
 // so that every backward kernel has an isolated parity test against torch autograd (tests/test_gpu_kernels.py), the
 // spectrogram-side glue of stft.hip against float64 numpy (tests/test_gpu_signal.py), and the LSTM fallbacks, the eval mask heads,
-// the squeeze conv and the small kernels around them against oracle/kernel_refs.py (tests/test_gpu_heads_lstm.py).
+// the squeeze conv and the small kernels around them against oracle/kernel_refs.py (tests/test_gpu_heads_lstm.py), and ONE launch_conv in
+// its general form -- concatenated strided sources, split strided destinations, a column window -- against oracle/kernel_refs.py
+// (tests/test_gpu_conv_launch.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -44,7 +46,39 @@ Tensor dense(float* p, int N, int C, int H, int W) {
     return t;
 }
 
+// A host buffer uploaded as given between two guard bands, so that a store a little outside it lands in memory of the hook's own and is
+// reported (intact()) instead of corrupting a neighbour's.  The bands are GUARD floats wide: a store further out is neither caught nor seen.
+struct GuardedBuf {
+    static constexpr size_t GUARD = 64;                   // floats: keeps p() 256-byte aligned
+    static constexpr uint32_t PATTERN = 0x7fc5a5a5u;      // a quiet NaN no kernel produces
+    DevBuf d;
+    size_t n;
+    GuardedBuf(const float* host, size_t n_) : d(n_ + 2 * GUARD), n(n_) {
+        const std::vector<uint32_t> g(GUARD, PATTERN);
+        VR_HIP(hipMemcpy(d.p, g.data(), GUARD * 4, hipMemcpyHostToDevice));
+        VR_HIP(hipMemcpy(d.p + GUARD + n, g.data(), GUARD * 4, hipMemcpyHostToDevice));
+        if (host && n) VR_HIP(hipMemcpy(p(), host, n * 4, hipMemcpyHostToDevice));
+    }
+    float* p() const { return d.p + GUARD; }
+    void download(float* host) const { if (host && n) VR_HIP(hipMemcpy(host, p(), n * 4, hipMemcpyDeviceToHost)); }
+    bool intact() const {
+        std::vector<uint32_t> g(2 * GUARD);
+        VR_HIP(hipMemcpy(g.data(), d.p, GUARD * 4, hipMemcpyDeviceToHost));
+        VR_HIP(hipMemcpy(g.data() + GUARD, d.p + GUARD + n, GUARD * 4, hipMemcpyDeviceToHost));
+        for (uint32_t v : g) if (v != PATTERN) return false;
+        return true;
+    }
+};
+
+// the strided view [N][C][H][W] at `off` lies inside a buffer of n floats
+bool view_fits(long long off, long long sN, long long sC, long long sH, int N, int C, int H, int W, size_t n) {
+    if (off < 0 || sN < 0 || sC < 0 || sH < 0 || N < 1 || C < 1 || H < 1 || W < 1) return false;
+    return off + (N - 1) * sN + (C - 1) * sC + (H - 1) * sH + W <= (long long)n;
+}
+
 }  // namespace
+
+ConvSrc make_src(const Tensor& t, bool up, int bcastH);   // model.hip
 
 // name            dims                  fparams          inputs                                              outputs
 // bn_backward     N,C,H,W               slope,eps,mom    z, G, gamma, beta, post[N][C]|null, rm[C], rv[C]    dz, dgamma, dbeta, affine[C][2], rm, rv
@@ -81,6 +115,120 @@ Tensor dense(float* p, int N, int C, int H, int W) {
 //                                                        mask_b[2 bins][Wb]|null, wgt[T]|null                y_wave, v_wave [2][hop (T-1)] (fused masked
 //                                                        (cplx: complex64 masks)                             iSTFT; hop == n_fft / 2 handles only)
 //                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
+// conv_launch     nsrc,ndst,N,Cout,KS,  epi_slope,       w[Cout][Cin][KS][KS] (OIHW), bias[Cout]|null,       per destination its whole backing buffer (null where
+//                 dil_h,dil_w,flags,    slope of         epi[Cout][2]|null; per source: its backing buffer,  absent); then, with flags bit 1, stats[Cout][2] =
+//                 w_lo,w_hi,d1,d2;      source 0, 1, 2   aff0[C][2]|null, aff1[C][2]|null, post[N][C]|null;   the BatchNorm partials summed per channel
+//                 per source C,H,W,up,                   per destination its backing buffer, uploaded AS
+//                 hsplit,floats,off,                     GIVEN (null where absent)
+//                 sN,sC,sH; per
+//                 destination present,
+//                 accumulate,floats,
+//                 off,sN,sC,sH
+//                 ONE launch_conv (stride 1, 'same' padding) in its general form, on the handle's stream and in its mfma_mode.  A source is
+//                 the view (off, sN, sC, sH) of its backing buffer of `floats` floats (C, H, W before the x2 upsample `up`), a destination
+//                 the view of its own; output channels [0, d1) go to destination 0, [d1, d2) to 1, the others to 2.  flags bit 0: the
+//                 transformed weight forms of the mode (as vr_debug_conv2d's bit 1), bit 1: partials.  Error -2: a view that leaves its
+//                 buffer, and every refusal of launch_conv (message intact).  Error -3: a store found in the 64 floats in front of or
+//                 behind a destination's buffer (the guard bands; a store further out is not seen).
+void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin,
+                              float* const* out, int nout) {
+    const std::string who = "vr_debug_kernel(conv_launch): ";
+    VR_CHECK(ndims >= 12 && nfp >= 4, -2, who + "too few arguments");
+    const int nsrc = (int)dims[0], ndst = (int)dims[1], N = (int)dims[2], Cout = (int)dims[3], KS = (int)dims[4];
+    const int dh = (int)dims[5], dw = (int)dims[6], flags = (int)dims[7];
+    const bool transformed = flags & 1, want_part = flags & 2;
+    VR_CHECK(nsrc >= 1 && nsrc <= 3 && ndst >= 1 && ndst <= 3 && N >= 1 && Cout >= 1 && (KS == 1 || KS == 3) && dh >= 1 && dw >= 1, -2,
+             who + "1..3 sources and destinations, a 1x1 or 3x3 kernel");
+    VR_CHECK(ndims >= 12 + 10 * nsrc + 7 * ndst && nin >= 3 + 4 * nsrc + ndst && nout >= ndst + (want_part ? 1 : 0), -2,
+             who + "too few arguments");
+    VR_CHECK(in[0] && (!want_part || out[ndst]), -2, who + "missing weights or partials output");
+    ConvArgs a{};
+    a.nsrc = nsrc; a.N = N; a.Cout = Cout; a.CoutPad = (Cout + 31) / 32 * 32;
+    a.w_lo = (int)dims[8]; a.w_hi = (int)dims[9]; a.d1 = (int)dims[10]; a.d2 = (int)dims[11];
+    a.bf16 = mfma_mode;
+    a.pad_h = KS == 1 ? 0 : dh; a.pad_w = KS == 1 ? 0 : dw;
+    // sources
+    std::vector<std::unique_ptr<DevBuf>> keep;
+    auto upload = [&](const float* host, size_t n) { keep.emplace_back(new DevBuf(host, n)); return keep.back()->p; };
+    int Cin = 0;
+    const ConvSrc* ups = nullptr;
+    for (int i = 0; i < nsrc; ++i) {
+        const int64_t* d = dims + 12 + 10 * i;
+        const float* const* si = in + 3 + 4 * i;
+        Tensor t;
+        t.N = N; t.C = (int)d[0]; t.H = (int)d[1]; t.W = (int)d[2];
+        const bool up = d[3] != 0;
+        t.hsplit = (int)d[4];
+        const size_t floats = (size_t)d[5];
+        t.sN = d[7]; t.sC = d[8]; t.sH = d[9];
+        VR_CHECK(si[0] && view_fits(d[6], t.sN, t.sC, t.sH, N, t.C, t.H, t.W, floats), -2, who + "a source view leaves its buffer");
+        t.p = upload(si[0], floats) + d[6];
+        t.slope = fp[1 + i];
+        if (si[1]) t.aff0 = upload(si[1], (size_t)t.C * 2);
+        if (si[2]) t.aff1 = upload(si[2], (size_t)t.C * 2);
+        if (si[3]) t.post = upload(si[3], (size_t)N * t.C);
+        a.src[i] = make_src(t, up, 0);
+        const int vh = up ? 2 * t.H : t.H, vw = up ? 2 * t.W : t.W;
+        if (i == 0) { a.Hin = vh; a.Win = vw; }
+        VR_CHECK(vh == a.Hin && vw == a.Win, -2, who + "the sources must share the input size");
+        // (Model::build_fwd_args' rule: the loaders keep one interpolation table per workgroup)
+        if (up && ups) VR_CHECK(ups->H == t.H && ups->W == t.W && ups->sH == t.sH, -2, who + "upsampled sources must share H, W and row stride");
+        if (up) ups = &a.src[i];
+        Cin += t.C;
+        if (i == 0) a.c1 = Cin;
+        if (i <= 1) a.c2 = Cin;                           // (a missing source is an empty channel range at the end)
+    }
+    a.Cin = Cin;
+    a.Hout = a.Hin; a.Wout = a.Win;
+    // weights: K-major [Cin][KS*KS][CoutPad], then the forms of the mode
+    const int KK = KS * KS;
+    std::vector<float> wk((size_t)Cin * KK * a.CoutPad, 0.f);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int k = 0; k < KK; ++k) wk[((size_t)ci * KK + k) * a.CoutPad + co] = in[0][((size_t)co * Cin + ci) * KK + k];
+    DevBuf dwk(wk.data(), wk.size());
+    a.w = dwk.p;
+    if (in[1]) a.bias = upload(in[1], (size_t)Cout);
+    if (in[2]) { a.epi = upload(in[2], (size_t)Cout * 2); a.epi_slope = fp[0]; }
+    DebugWeightForms wf;
+    debug_weight_forms(dwk.p, Cin, KS, 1, dh, dw, a.CoutPad, a.Win, transformed, a, wf);
+    // destinations
+    std::vector<std::unique_ptr<GuardedBuf>> dst(3);
+    const int c1 = a.d1 < Cout ? a.d1 : Cout, c2 = a.d2 < Cout ? a.d2 : Cout;
+    VR_CHECK(0 <= c1 && c1 <= c2, -2, who + "need 0 <= d1 <= d2");
+    const int seg_c[3] = {c1, c2 - c1, Cout - c2};
+    for (int i = 0; i < ndst; ++i) {
+        const int64_t* d = dims + 12 + 10 * nsrc + 7 * i;
+        const float* host = in[3 + 4 * nsrc + i];
+        if (!d[0]) continue;                              // absent: p stays null
+        VR_CHECK(host && out[i], -2, who + "a present destination needs its buffer, in and out");
+        VR_CHECK(seg_c[i] == 0 || view_fits(d[3], d[4], d[5], d[6], N, seg_c[i], a.Hout, a.Wout, (size_t)d[2]), -2,
+                 who + "a destination view leaves its buffer");
+        dst[i].reset(new GuardedBuf(host, (size_t)d[2]));
+        a.dst[i] = ConvDst{dst[i]->p() + d[3], d[4], d[5], d[6], d[1] != 0 ? 1 : 0, 0};
+    }
+    const ConvShape shp{KS, 1, dh, dw};
+    size_t npt = 0;
+    std::unique_ptr<DevBuf> part;
+    if (want_part) { npt = conv_part_count(a, shp); part.reset(new DevBuf(npt * Cout * 2)); a.part = part->p; }
+    launch_conv(a, shp, stream);
+    VR_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < ndst; ++i)
+        if (dst[i]) {
+            VR_CHECK(dst[i]->intact(), -3, who + "the launch stored outside a destination's buffer");
+            dst[i]->download(out[i]);
+        }
+    if (want_part) {
+        std::vector<float> ph(npt * Cout * 2);
+        part->download(ph.data());
+        for (int c = 0; c < Cout; ++c) {
+            double s1 = 0, s2 = 0;
+            for (size_t i = 0; i < npt; ++i) { s1 += ph[(i * Cout + c) * 2]; s2 += ph[(i * Cout + c) * 2 + 1]; }
+            out[ndst][2 * c] = (float)s1; out[ndst][2 * c + 1] = (float)s2;
+        }
+    }
+}
+
 void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims, const float* fp, int nfp,
                          const float* const* in, int nin, float* const* out, int nout) {
     DeviceGuard dev_guard(device);
@@ -101,6 +249,7 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         for (int i = 0; i < 768; ++i) out[0][i] = raw[i] ? (float)(raw[i] - lo) : -1.f;
         return;
     }
+    if (name == "conv_launch") { debug_conv_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "bn_backward") {
         need(4, 3, 7, 6);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];

@@ -185,6 +185,8 @@ public:
     void debug_kernel(const std::string& name, const int64_t* dims, int ndims, const float* fp, int nfp,
                       const float* const* in, int nin, float* const* out, int nout);
 
+    void debug_conv_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                           int nout);                     // its "conv_launch" entry
     // ---- signal path ----
     void stft_api(const float* wave, bool on_dev, long long L, float* spec, bool spec_on_dev);
     void istft_api(const float* spec, bool on_dev, int T, float* wave, bool wave_on_dev);
@@ -224,6 +226,19 @@ public:
     void debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,
                     int dh, int dw, int up, const float* aff, float slope, const float* bias, float* out,
                     float* stats_out);
+    // The device forms of one layer's weights that `mfma_mode` multiplies with, made from the K-major copy dw_kmajor [Cin][KS*KS][CoutPad]
+    // and set in `a` (wino / wino6 / x3w); shared by debug_conv and the conv_launch hook of debug.hip.  Freed with the object.
+    struct DebugWeightForms {
+        float* wino = nullptr;
+        void* wino6 = nullptr;
+        void* x3w = nullptr;
+        DebugWeightForms() = default;
+        ~DebugWeightForms() { (void)hipFree(wino); (void)hipFree(wino6); (void)hipFree(x3w); }
+        DebugWeightForms(const DebugWeightForms&) = delete;
+        DebugWeightForms& operator=(const DebugWeightForms&) = delete;
+    };
+    void debug_weight_forms(const float* dw_kmajor, int Cin, int KS, int stride, int dh, int dw, int CoutPad, int Win, bool transformed,
+                            ConvArgs& a, DebugWeightForms& f);
     bool record_taps = false;
     std::map<std::string, Tensor> taps;
     int64_t get_tap(const std::string& name, float* host, int64_t cap_floats, int64_t* shape4);

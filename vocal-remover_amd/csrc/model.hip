@@ -2573,6 +2573,39 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
 }
 
 // =====================================================================================================
+// unit-test hooks: the weight forms of a single conv launch
+// =====================================================================================================
+void Model::debug_weight_forms(const float* dw_, int Cin, int KS, int stride, int dh, int dw, int CoutPad, int Win, bool want_wino,
+                               ConvArgs& a, DebugWeightForms& f) {
+    const int KK = KS * KS;
+    if (want_wino && mfma_mode == 3 && stride == 1 && (KS == 1 || dh > 1)) {
+        // conv_x3d.hip's layers (dilated 3x3, 1x1 at 16 columns): fp16-plane weights only
+        VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, KK, CoutPad)));
+        launch_x3h_weights(dw_, f.x3w, Cin, KK, CoutPad, stream);
+        a.x3w = f.x3w;
+    } else if (want_wino) {
+        VR_CHECK(KS == 3 && stride == 1 && dh == 1 && dw == 1, -2, "Winograd weights exist for 3x3 stride-1 convs only");
+        VR_HIP(hipMalloc(&f.wino, (size_t)Cin * 16 * CoutPad * 4));
+        launch_wino_weights(dw_, f.wino, Cin, CoutPad, stream);
+        a.wino = f.wino;
+        if (mfma_mode == 2) {
+            VR_HIP(hipMalloc(&f.wino6, wino_weights6_bytes(Cin, CoutPad)));
+            launch_wino_weights6(dw_, f.wino6, Cin, CoutPad, stream);
+            a.wino6 = f.wino6;
+            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
+            launch_x3_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
+            a.x3w = f.x3w;
+        }
+        if (mfma_mode == 3) {
+            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
+            launch_x3h_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
+            a.x3w = f.x3w;
+        }
+    }
+    if (!x3d_mode && Win == 16) a.x3w = nullptr;            // option conv_x3d 0: the fp32-pipe kernels for the 16-column layers
+}
+
+// =====================================================================================================
 // unit-test hook: one conv through the MFMA kernel with a single dense source
 // =====================================================================================================
 void Model::debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,
@@ -2608,34 +2641,8 @@ void Model::debug_conv(const float* x, int N, int Cin, int H, int W, const float
     a.w = dw_; a.bias = dbias; a.Cout = Cout; a.CoutPad = CoutPad;
     if (epi && daff) { a.epi = daff; a.epi_slope = slope; }
     a.bf16 = mfma_mode;
-    float* dwino = nullptr;
-    void* dwino6 = nullptr;
-    void* dx3w = nullptr;
-    if (want_wino && mfma_mode == 3 && stride == 1 && (KS == 1 || dh > 1)) {
-        // conv_x3d.hip's layers (dilated 3x3, 1x1 at 16 columns): fp16-plane weights only
-        VR_HIP(hipMalloc(&dx3w, x3_weights_bytes(Cin, KK, CoutPad)));
-        launch_x3h_weights(dw_, dx3w, Cin, KK, CoutPad, stream);
-        a.x3w = dx3w;
-    } else if (want_wino) {
-        VR_CHECK(KS == 3 && stride == 1 && dh == 1 && dw == 1, -2, "Winograd weights exist for 3x3 stride-1 convs only");
-        VR_HIP(hipMalloc(&dwino, (size_t)Cin * 16 * CoutPad * 4));
-        launch_wino_weights(dw_, dwino, Cin, CoutPad, stream);
-        a.wino = dwino;
-        if (mfma_mode == 2) {
-            VR_HIP(hipMalloc(&dwino6, wino_weights6_bytes(Cin, CoutPad)));
-            launch_wino_weights6(dw_, dwino6, Cin, CoutPad, stream);
-            a.wino6 = dwino6;
-            VR_HIP(hipMalloc(&dx3w, x3_weights_bytes(Cin, 9, CoutPad)));
-            launch_x3_weights(dw_, dx3w, Cin, 9, CoutPad, stream);
-            a.x3w = dx3w;
-        }
-        if (mfma_mode == 3) {
-            VR_HIP(hipMalloc(&dx3w, x3_weights_bytes(Cin, 9, CoutPad)));
-            launch_x3h_weights(dw_, dx3w, Cin, 9, CoutPad, stream);
-            a.x3w = dx3w;
-        }
-    }
-    if (!x3d_mode && Win == 16) a.x3w = nullptr;            // option conv_x3d 0: the fp32-pipe kernels for the 16-column layers
+    DebugWeightForms wf;
+    debug_weight_forms(dw_, Cin, KS, stride, dh, dw, CoutPad, Win, want_wino, a, wf);
     a.dst[0] = ConvDst{dout, (long long)Hout * Wout * Cout, (long long)Hout * Wout, (long long)Wout, 0};
     a.d1 = a.d2 = 1 << 30;
     a.N = N; a.Hout = Hout; a.Wout = Wout; a.Hin = Hin; a.Win = Win; a.pad_h = pad_h; a.pad_w = pad_w;
@@ -2654,7 +2661,7 @@ void Model::debug_conv(const float* x, int N, int Cin, int H, int W, const float
             stats_out[2 * c] = (float)s1; stats_out[2 * c + 1] = (float)s2;
         }
     }
-    hipFree(dx); hipFree(dw_); hipFree(dout); hipFree(daff); hipFree(dbias); hipFree(dpart); hipFree(dwino); hipFree(dwino6); hipFree(dx3w);
+    hipFree(dx); hipFree(dw_); hipFree(dout); hipFree(daff); hipFree(dbias); hipFree(dpart);
 }
 
 }  // namespace vr
