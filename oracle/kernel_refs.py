@@ -327,6 +327,47 @@ def conv_launch_input(desc):
     return np.concatenate(parts, axis=1)
 
 
+def conv_launch_materialised(desc):
+    """The virtual input as the device forms it, float32 [N][Cin][Hin][Win]: the pending affine, activation and multiplier in float32, the
+    bilinear x2 by torch's float32 kernel, whose float32 source coordinate i * (float)(n - 1) / (2n - 1) is the one the fused loaders
+    compute (ConvSrc::rh / rw).  It is what the isolated launch tests hand the dense single-source launch they compare with: the float64
+    input rounded once instead would leave that coordinate's rounding -- which grows with the column index, to 1e-6 of the scale at
+    column 90 -- on the multi-source side of the comparison alone."""
+    F = torch.nn.functional
+    parts = []
+    for s in desc['srcs']:
+        v = torch.from_numpy(s['buf'][view_index(s['off'], s['sN'], s['sC'], s['sH'], desc['N'], s['C'], s['H'], s['W'])])
+        hs = min(s['hsplit'], s['H'])
+        for aff, rows in ((s['aff0'], slice(0, hs)), (s['aff1'] if s['aff1'] is not None else s['aff0'], slice(hs, s['H']))):
+            if aff is not None:
+                a = torch.from_numpy(aff)
+                v[:, :, rows] = v[:, :, rows] * a[:, 0].view(1, -1, 1, 1) + a[:, 1].view(1, -1, 1, 1)
+        v = F.leaky_relu(v, s['slope'])
+        if s['post'] is not None:
+            v = v * torch.from_numpy(s['post'])[:, :, None, None]
+        parts.append(F.interpolate(v, scale_factor=2, mode='bilinear', align_corners=True) if s['up'] else v)
+    return np.ascontiguousarray(torch.cat(parts, dim=1).numpy(), np.float32)
+
+
+def profiled_kernels(nat, handle, fn):
+    """Run fn under the library's launch profiler (vr_profile_begin / _end / _report of the native handle) -> {kernel name with its
+    template arguments, 'vr::' and blanks removed: calls}.  How the isolated launch tests assert WHICH kernel a launch took."""
+    import ctypes
+    nat.check(nat.lib().vr_profile_begin(handle.h))
+    try:
+        fn()
+    finally:
+        z = [ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()]
+        nat.check(nat.lib().vr_profile_end(handle.h, ctypes.byref(z[0]), ctypes.byref(z[1]), ctypes.byref(z[2]), ctypes.byref(z[3])))
+    need = nat.lib().vr_profile_report(handle.h, None, 0)
+    rep = ctypes.create_string_buffer(int(need) + 1)
+    nat.lib().vr_profile_report(handle.h, rep, need)
+    ran = {}
+    for ln in rep.value.decode().splitlines():
+        ran[ln.split('\t')[0].replace('vr::', '').replace(' ', '')] = int(ln.split('\t')[1])
+    return ran
+
+
 def conv_launch_output(desc, x=None):
     """(z, y): z = conv + bias [N][Cout][H][W] in float64 by direct summation over the taps, y = the epilogue affine + activation on z."""
     x = conv_launch_input(desc) if x is None else x
@@ -376,3 +417,173 @@ def conv_launch_ref(desc):
         bufs.append(b)
     stats = np.stack([z.sum(axis=(0, 2, 3)), (z * z).sum(axis=(0, 2, 3))], 1)
     return bufs, stats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one weight-gradient launch in its general form: concatenated strided sources, a strided dz, batch-as-rows, K-major padded gradient
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _wcase(name, N, Cout, srcs, runs, KS=3, stride=1, dil=(1, 1), dz='dense', batch_as_h=False, matrix=False, data=None):
+    # runs: (mfma_mode, train_winograd) -> the weight-gradient kernel launch_wgrad must take, template arguments included (as the
+    # profiler demangles them, without blanks).  matrix: also run store / accumulate x immediate / deferred.  data: as in _case.
+    return dict(name=name, N=N, Cout=Cout, srcs=srcs, runs=runs, KS=KS, stride=stride, dil=dil, dz=dz, batch_as_h=batch_as_h,
+                matrix=matrix, data=data or name)
+
+
+_WR = 'wgrad_wino_r_kernel<%d,%d>'                                  # <CB, MT>: wgrad_wino_pick
+_WS = 'wgrad_ws_kernel<3,%d,%d,%d,%d,8>'                            # <KS, S, TH, TW, MB, NPW>: wg_pick
+_WM = 'wgrad_mfma_kernel<%d,1,%d,%d,%d,%d,%d>'                      # <KS, S, DH, DW, TH, TW, MB>
+_GEMM, _GEMM1, _GEMM_BF = 'wgrad_gemm_kernel<false,false>', 'wgrad_gemm_kernel<false,true>', 'wgrad_gemm_kernel<true,false>'
+_ws32 = lambda mb: _WS % (1, 4, 32, mb)                             # noqa: E731
+_ws16 = lambda mb: _WS % (1, 8, 16, mb)                             # noqa: E731
+_m1x1 = lambda tw, mb: _WM % (1, 1, 1, 4 if tw == 32 else 8, tw, mb)    # noqa: E731
+_PEND = dict(aff0=True, aff1=True, hsplit=5, slope=0.01, post=True)
+
+
+def _one_by_one_cases():
+    """1x1 launches wgrad_gemm_pick must refuse, each for ONE reason, on the 32- and on the 16-column tile of wgrad_mfma_kernel<1,...>:
+    c1 % 4 != 0, pixels per sample no multiple of 64, a dz row stride wider than Wout, a source with a pending affine."""
+    out = []
+    for tw in (32, 16):
+        k = {(3, 1): _m1x1(tw, 2)}
+        out += [_wcase('c1x1_c1_6_w%d' % tw, 2, 40, [_src(6, 4, tw), _src(26, 4, tw)], k, KS=1),
+                _wcase('c1x1_px_w%d' % tw, 2, 40, [_src(12, 3, tw), _src(20, 3, tw)], k, KS=1),          # 96 / 48 pixels per sample
+                _wcase('c1x1_dzwide_w%d' % tw, 2, 40, [_src(12, 4, tw), _src(20, 4, tw)], k, KS=1, dz='pitch'),
+                _wcase('c1x1_affine_w%d' % tw, 2, 40, [_src(12, 4, tw, aff0=True), _src(20, 4, tw)], k, KS=1)]
+    return out
+
+
+# The case table of tests/test_gpu_wgrad_launch.py and of the pin in tests/test_cpu_kernel_refs.py.  Every case keeps N * Hout * Wout
+# <= 2048 pixels: one dropped pixel then moves a gradient element by about 1 / sqrt(pixels) >= 2e-2 of its scale, a hundred times the bar.
+WGRAD_LAUNCH_CASES = [
+    # Winograd register-loader blocks (train_winograd 1, plain 16-byte aligned sources); with train_winograd 0 the same launches on the
+    # warp-specialised direct kernel, MB 1 (CoutPad 32, 96) and 2 (64, 128)
+    _wcase('wino_32x32', 2, 16, [_src(2, 8, 32), _src(1, 8, 32)], {(3, 1): _WR % (32, 32), (3, 0): _ws32(1)}),       # the stage-input form
+    _wcase('wino_32x64', 2, 64, [_src(8, 12, 16), _src(16, 12, 16)],
+           {(3, 1): _WR % (32, 64), (3, 0): _ws16(2), (1, 1): 'wgrad_wino_kernel<32,64,true>'}),
+    _wcase('wino_64x32', 2, 80, [_src(24, 8, 16), _src(24, 8, 16)], {(3, 1): _WR % (64, 32), (3, 0): _ws16(1)}),     # the 64-block straddles
+    _wcase('wino_64x64', 2, 128, [_src(16, 6, 32), _src(40, 6, 32), _src(9, 6, 32)],                                # one live channel in block 2
+           {(3, 1): _WR % (64, 64), (3, 0): _ws32(2)}, matrix=True),
+    # three plain sources on the 16-column tile: both boundaries (c1 = 8, c2 = 20) inside the one 32-channel chunk of the LDS-DMA loader
+    _wcase('wino_3src_w16', 2, 64, [_src(8, 10, 16), _src(12, 10, 16), _src(5, 10, 16)], {(3, 1): _WR % (32, 64), (3, 0): _ws16(2)}),
+    _wcase('wino_odd_h_w20', 2, 32, [_src(20, 9, 20), _src(13, 9, 20)], {(3, 1): _WR % (64, 32), (3, 0): _ws16(1)}),
+    _wcase('wino_n3', 3, 64, [_src(5, 6, 16), _src(12, 6, 16)], {(3, 1): _WR % (32, 64), (3, 0): _ws16(2)}),
+    _wcase('wino_slices', 2, 32, [_src(8, 8, 16, layout='slice24'), _src(16, 8, 16, layout='slice24')], {(3, 1): _WR % (32, 32)}),
+    # falling off Winograd by alignment: the same values, one misalignment each
+    _wcase('align_base', 2, 64, [_src(8, 12, 32), _src(16, 12, 32)], {(3, 1): _WR % (32, 64)}, data='align'),
+    _wcase('align_row33', 2, 64, [_src(8, 12, 32, layout='row_odd'), _src(16, 12, 32)], {(3, 1): _ws32(2)}, data='align', matrix=True),
+    _wcase('align_src_off1', 2, 64, [_src(8, 12, 32), _src(16, 12, 32, layout='off1')], {(3, 1): _ws32(2)}, data='align'),
+    _wcase('align_dz_off1', 2, 64, [_src(8, 12, 32), _src(16, 12, 32)], {(3, 1): _ws32(2)}, dz='off1', data='align'),
+    # pending sources: the fused loader (dma == 0)
+    _wcase('pending_w32', 2, 64, [_src(8, 12, 32, **_PEND), _src(8, 6, 16, up=1, aff0=True, slope=0.01), _src(9, 12, 32)], {(3, 1): _ws32(2)}),
+    _wcase('pending_w16', 2, 32, [_src(8, 16, 16, **_PEND), _src(12, 8, 8, up=1), _src(5, 16, 16)], {(3, 1): _ws16(1)}),
+    # stride 2: odd H, Wout 36
+    _wcase('stride2_plain', 2, 40, [_src(8, 15, 72), _src(9, 15, 72)], {(3, 1): _WS % (2, 4, 16, 2)}, stride=2),
+    _wcase('stride2_pending', 2, 32, [_src(8, 15, 72, **_PEND), _src(9, 15, 72)], {(3, 1): _WS % (2, 4, 16, 1)}, stride=2),
+    # dilated: MB 1, 2, 4
+    _wcase('dil_4_2', 2, 32, [_src(20, 16, 16), _src(13, 16, 16)], {(3, 1): _WM % (3, 4, 2, 4, 16, 1), (1, 1): _WM % (3, 4, 2, 4, 16, 1)}, dil=(4, 2)),
+    _wcase('dil_8_4', 2, 64, [_src(20, 16, 16), _src(13, 16, 16)], {(3, 1): _WM % (3, 8, 4, 4, 16, 2)}, dil=(8, 4), matrix=True),
+    _wcase('dil_12_6', 2, 128, [_src(20, 16, 16), _src(13, 16, 16)], {(3, 1): _WM % (3, 12, 6, 4, 16, 4)}, dil=(12, 6)),
+    # 1x1: the pixel-contiguous GEMM, and its one-tile form
+    _wcase('gemm_72', 2, 72, [_src(36, 4, 16), _src(28, 4, 16)], {(3, 1): _GEMM, (1, 1): _GEMM_BF}, KS=1, matrix=True),
+    _wcase('gemm_one_tile', 2, 8, [_src(12, 4, 16), _src(20, 4, 16)], {(3, 1): _GEMM1}, KS=1),
+] + _one_by_one_cases() + [
+    # batch_as_h (the LSTM's Linear): the batch as the rows of a 1x1 conv on H = 1.  In the net's layout [N][C][1][W] a row of the
+    # rewritten source is C * W floats away from the next: wgrad_gemm_pick needs rows back to back (c.sH == c.W) and refuses, whatever the
+    # pixel count.  'rows' lays source and dz out [C][N][W], the only layout in which the batch-as-rows form reaches the GEMM.
+    _wcase('batch_as_h_n4', 4, 40, [_src(24, 1, 16)], {(3, 1): _m1x1(16, 2)}, KS=1, batch_as_h=True),
+    _wcase('batch_as_h_n3', 3, 40, [_src(24, 1, 16)], {(3, 1): _m1x1(16, 2)}, KS=1, batch_as_h=True),
+    _wcase('batch_as_h_n4_rows', 4, 40, [_src(24, 1, 16, layout='rows')], {(3, 1): _GEMM}, KS=1, batch_as_h=True, dz='rows'),
+]
+
+
+def _wstrides(layout, N, C, H, W):
+    """(floats, off, sN, sC, sH) of the views only the weight-gradient table uses; the others are _strides'."""
+    if layout == 'slice24':               # channels [3, 3 + C) of a buffer 5 channels wider, rows 24 floats apart, columns from 4
+        sC = H * 24
+        sN = (C + 5) * sC
+        return N * sN, 3 * sC + 4, sN, sC, 24
+    if layout == 'row_odd':               # a row stride that is no multiple of 4 floats
+        return N * C * H * (W + 1), 0, C * H * (W + 1), H * (W + 1), W + 1
+    if layout == 'off1':                  # dense, one float into its buffer
+        return N * C * H * W + 1, 1, C * H * W, H * W, W
+    if layout == 'rows':                  # [C][N][W] (H == 1): the items of the batch are rows back to back under each channel
+        assert H == 1
+        return C * N * W, 0, W, N * W, W
+    return _strides(layout, N, C, H, W)
+
+
+def wgrad_launch_build(case):
+    """The float32 data of a case.  The VALUES of the views are drawn per `data` name and do not depend on the layouts, so cases that share
+    the name share them; what lies between the elements of a view is filled with values a thousand times larger, drawn separately."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(('wgrad ' + case['data']).encode()))
+    fill = np.random.default_rng(zlib.crc32(('wgrad fill ' + case['name']).encode()))
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)                          # noqa: E731
+    aff = lambda C: f32(np.stack([rng.random(C) + 0.5, rng.standard_normal(C) * 0.3], 1))    # noqa: E731
+    N, Cout, KS, stride, (dh, dw) = case['N'], case['Cout'], case['KS'], case['stride'], case['dil']
+
+    def strided(values, layout):
+        n, C, H, W = values.shape
+        floats, off, sN, sC, sH = _wstrides(layout, n, C, H, W)
+        buf = f32(fill.standard_normal(floats) * 1e3)
+        buf[view_index(off, sN, sC, sH, n, C, H, W)] = values
+        return dict(buf=buf, off=off, sN=sN, sC=sC, sH=sH)
+
+    srcs = []
+    for s in case['srcs']:
+        C, H, W = s['C'], s['H'], s['W']
+        v = strided(f32(rng.standard_normal((N, C, H, W))), s['layout'])
+        a0, a1 = aff(C) if s['aff0'] else None, aff(C) if s['aff1'] else None
+        post = None
+        if s['post']:
+            post = np.where(rng.random((N, C)) < 0.25, 0.0, 1 / 0.9)
+            post.flat[0], post.flat[1] = 0.0, 1 / 0.9
+        srcs.append(dict(v, C=C, H=H, W=W, up=s['up'], aff0=a0, aff1=a1, hsplit=NO_SPLIT if s['hsplit'] is None else s['hsplit'],
+                         slope=s['slope'], post=None if post is None else f32(post)))
+    Cin = sum(s['C'] for s in srcs)
+    Hin, Win = [(2 * s['H'], 2 * s['W']) if s['up'] else (s['H'], s['W']) for s in srcs][0]
+    ph, pw = (dh, dw) if KS == 3 else (0, 0)
+    Hout, Wout = (Hin + 2 * ph - dh * (KS - 1) - 1) // stride + 1, (Win + 2 * pw - dw * (KS - 1) - 1) // stride + 1
+    dz = strided(f32(rng.standard_normal((N, Cout, Hout, Wout))), case['dz'])
+    CoutPad = (Cout + 31) // 32 * 32
+    prior = f32(rng.standard_normal((Cin, KS * KS, CoutPad)))                   # the gradient buffer of an accumulating launch
+    return dict(name=case['name'], N=N, Cin=Cin, Cout=Cout, CoutPad=CoutPad, KS=KS, stride=stride, dil=case['dil'], Hin=Hin, Win=Win,
+                Hout=Hout, Wout=Wout, srcs=srcs, dz=dz, batch_as_h=case['batch_as_h'], prior=prior)
+
+
+def wgrad_launch_dz(desc):
+    """dz of the launch, float64 [N][Cout][Hout][Wout], read through its view."""
+    z = desc['dz']
+    return np.asarray(z['buf'], np.float64)[view_index(z['off'], z['sN'], z['sC'], z['sH'], desc['N'], desc['Cout'], desc['Hout'], desc['Wout'])]
+
+
+def wgrad_launch_grad(desc, x=None):
+    """dW [Cout][Cin][KS][KS] in float64: dW[co][ci][kh][kw] = sum over n, h, w of dz[n][co][h][w] x[n][ci][h s + kh dh - ph][w s + kw dw - pw],
+    x the virtual input of the launch (conv_launch_input).  batch_as_h only renames the batch as rows: the sum is the same."""
+    x = conv_launch_input(desc) if x is None else x
+    dz = wgrad_launch_dz(desc)
+    KS, s, (dh, dw) = desc['KS'], desc['stride'], desc['dil']
+    ph, pw = (dh, dw) if KS == 3 else (0, 0)
+    xp = np.pad(x, ((0, 0), (0, 0), (ph, ph), (pw, pw)))
+    Hout, Wout = dz.shape[2:]
+    g = np.zeros((desc['Cout'], desc['Cin'], KS, KS))
+    for kh in range(KS):
+        for kw in range(KS):
+            win = xp[:, :, kh * dh:kh * dh + (Hout - 1) * s + 1:s, kw * dw:kw * dw + (Wout - 1) * s + 1:s]
+            g[:, :, kh, kw] = np.einsum('nohw,nchw->oc', dz, win, optimize=True)
+    return g
+
+
+def wgrad_kmajor(g, CoutPad):
+    """[Cout][Cin][KS][KS] -> the device's K-major padded layout [Cin][KS*KS][CoutPad], zeros in the pad lanes."""
+    Cout, Cin, KS, _ = g.shape
+    out = np.zeros((Cin, KS * KS, CoutPad), g.dtype)
+    out[:, :, :Cout] = g.reshape(Cout, Cin, KS * KS).transpose(1, 2, 0)
+    return out
+
+
+def wgrad_launch_ref(desc, accumulate=False, times=1):
+    """The gradient buffer after the launch, float64 [Cin][KS*KS][CoutPad]: `times` x the gradient, zeros in the pad lanes
+    Cout <= co < CoutPad, on top of desc['prior'] where the launch accumulates."""
+    out = times * wgrad_kmajor(wgrad_launch_grad(desc), desc['CoutPad'])
+    return out + np.asarray(desc['prior'], np.float64) if accumulate else out

@@ -2,7 +2,9 @@
 the BiLSTM statement against torch.nn.LSTM(bidirectional=True) in float64, the two mask heads against the lines of oracle/cascaded_net.py
 (pinned in turn against the reference's own modules by tests/test_oracle_vs_reference.py), the small references against their formulas
 written a second way, and the conditions the saturated-gate LSTM cases are chosen by; the general conv launch of
-tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in float64, over that test's case table.  No GPU."""
+tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in float64, over that test's case table; the general
+weight-gradient launch of tests/test_gpu_wgrad_launch.py (`wgrad_launch_ref`) against torch autograd of F.conv2d in float64, over that
+test's case table.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -214,3 +216,84 @@ def test_conv_launch_case_table_holds_the_forms_it_is_meant_to():
     assert by['split_5_17']['dsts'][1] is None and by['split_5_17']['dsts'][2]['accumulate'] == 1
     assert [t['C'] for t in by['split_thin_3_4_5']['dsts']] == [3, 4, 5]
     assert [t['C'] for t in by['split_cols16_32_33']['dsts']] == [32, 1, 7]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# wgrad_launch_ref: the reference of tests/test_gpu_wgrad_launch.py, over the same case table
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', kr.WGRAD_LAUNCH_CASES, ids=lambda c: c['name'])
+def test_wgrad_launch_reference_equals_torch_autograd_in_float64(case):
+    """The virtual input and dz through torch's as_strided views and modules, the gradient by autograd of F.conv2d: 1e-12 of the gradient's
+    scale on every lane of the K-major padded buffer, exact zeros in the pad lanes, the prior contents added where the launch accumulates."""
+    F = torch.nn.functional
+    desc = kr.wgrad_launch_build(case)
+    conv_desc = dict(desc, dsts=[], epi=None, bias=None, window=None, w=np.zeros((desc['Cout'], desc['Cin'], desc['KS'], desc['KS']), np.float32))
+    x = torch.from_numpy(_torch_conv_launch(conv_desc)[0])
+    got_x = kr.conv_launch_input(desc)
+    assert got_x.shape == x.shape and float(np.abs(got_x - x.numpy()).max()) <= 1e-12 * float(x.abs().max())
+    z = desc['dz']
+    dz = _torch_view(torch.from_numpy(z['buf']).double(), z, desc['N'], desc['Cout'], desc['Hout'], desc['Wout'])
+    w = torch.zeros(desc['Cout'], desc['Cin'], desc['KS'], desc['KS'], dtype=torch.float64, requires_grad=True)
+    pad = desc['dil'] if desc['KS'] == 3 else (0, 0)
+    out = F.conv2d(x, w, None, desc['stride'], pad, desc['dil'])
+    assert tuple(out.shape) == (desc['N'], desc['Cout'], desc['Hout'], desc['Wout'])
+    out.backward(dz)
+    want = w.grad.numpy()                                                            # [Cout][Cin][KS][KS]
+    scale = float(np.abs(want).max())
+    prior = desc['prior'].astype(np.float64)
+    for accumulate, times in ((False, 1), (True, 1), (True, 2)):
+        got = kr.wgrad_launch_ref(desc, accumulate, times)
+        assert got.shape == (desc['Cin'], desc['KS'] ** 2, desc['CoutPad']) == prior.shape
+        pure = got - prior if accumulate else got
+        back = pure[:, :, :desc['Cout']].transpose(2, 0, 1).reshape(want.shape)
+        assert float(np.abs(back - times * want).max()) <= 1e-12 * scale * times
+        pads = got[:, :, desc['Cout']:]
+        assert np.array_equal(pads, prior[:, :, desc['Cout']:] if accumulate else np.zeros_like(pads))
+
+
+def test_wgrad_launch_case_table_holds_the_forms_it_is_meant_to():
+    """The properties the cases are chosen for, so an edit of the table cannot quietly lose one."""
+    by = {c['name']: kr.wgrad_launch_build(c) for c in kr.WGRAD_LAUNCH_CASES}
+    assert len(by) == len(kr.WGRAD_LAUNCH_CASES)
+    for name, d in by.items():
+        assert d['N'] * d['Hout'] * d['Wout'] <= 2048, name
+        assert d['batch_as_h'] or 2 <= d['Hin'] <= 24, name
+        assert all(not np.isnan(s['buf']).any() for s in d['srcs']), name
+    aligned = lambda v: all(v[k] % 4 == 0 for k in ('off', 'sN', 'sC', 'sH'))    # noqa: E731
+    for name in ('wino_32x32', 'wino_32x64', 'wino_64x32', 'wino_64x64', 'wino_3src_w16', 'wino_odd_h_w20', 'wino_n3', 'wino_slices', 'align_base'):
+        assert all(aligned(v) for v in by[name]['srcs'] + [by[name]['dz']]), name
+    assert [s['C'] for s in by['wino_32x32']['srcs']] == [2, 1] and by['wino_32x32']['CoutPad'] == 32
+    assert by['wino_64x32']['CoutPad'] == 96 and by['wino_64x32']['srcs'][0]['C'] % 32 and by['wino_64x32']['Cin'] > 32
+    assert by['wino_64x64']['Cin'] == 65 and len(by['wino_64x64']['srcs']) == 3
+    # train_winograd 0 on two AND three plain sources, on the 32- and on the 16-column tile; the three-source ones with both boundaries
+    # (c1, c2) inside one 32-channel chunk of the direct kernel's loader
+    cases = {c['name']: c for c in kr.WGRAD_LAUNCH_CASES}
+    plain = lambda d: all(s['aff0'] is None and s['aff1'] is None and s['post'] is None and not s['up'] and s['slope'] == 1.0 for s in d['srcs'])    # noqa: E731
+    direct = {(len(by[n]['srcs']), by[n]['Win'] >= 32) for n, c in cases.items() if (3, 0) in c['runs'] and plain(by[n])}
+    assert direct == {(2, True), (3, True), (2, False), (3, False)}
+    t = by['wino_3src_w16']
+    c1, c2 = t['srcs'][0]['C'], t['srcs'][0]['C'] + t['srcs'][1]['C']
+    assert t['Win'] == 16 and len(t['srcs']) == 3 and c1 // 32 == c2 // 32 == 0 and c1 % 32 and c2 % 32 and c2 < t['Cin'] and t['CoutPad'] == 64
+    assert cases['wino_3src_w16']['runs'][(3, 0)].startswith('wgrad_ws_kernel<3,1,8,16,') and (3, 1) in cases['wino_3src_w16']['runs']
+    assert by['wino_odd_h_w20']['Hin'] % 2 == 1 and by['wino_odd_h_w20']['Win'] == 20 and by['wino_n3']['N'] == 3
+    assert all(s['sH'] == 24 and s['W'] == 16 for s in by['wino_slices']['srcs'])
+    # one misalignment each, the values shared
+    base = by['align_base']
+    for name, bad in (('align_row33', lambda d: d['srcs'][0]['sH'] % 4), ('align_src_off1', lambda d: d['srcs'][1]['off'] == 1),
+                      ('align_dz_off1', lambda d: d['dz']['off'] == 1)):
+        d = by[name]
+        assert bad(d) and sum(not aligned(v) for v in d['srcs'] + [d['dz']]) == 1, name
+        assert np.array_equal(kr.conv_launch_input(d), kr.conv_launch_input(base)) and np.array_equal(kr.wgrad_launch_dz(d), kr.wgrad_launch_dz(base))
+    for name in ('pending_w32', 'pending_w16'):
+        s0, s1, s2 = by[name]['srcs']
+        assert s0['aff0'] is not None and s0['aff1'] is not None and 0 < s0['hsplit'] < 8 and s0['slope'] == 0.01 and (s0['post'] == 0).any()
+        assert s1['up'] and not s2['up'] and s2['aff0'] is None and s2['slope'] == 1.0
+    assert by['stride2_plain']['Hin'] == 15 and by['stride2_plain']['Wout'] == 36 and by['stride2_plain']['Hout'] == 8
+    assert [by[n]['CoutPad'] for n in ('dil_4_2', 'dil_8_4', 'dil_12_6')] == [32, 64, 128]
+    g = by['gemm_72']
+    assert g['Hout'] * g['Wout'] == 64 and g['srcs'][0]['C'] % 4 == 0 and g['CoutPad'] == 96
+    assert by['gemm_one_tile']['Cin'] == 32 and by['gemm_one_tile']['CoutPad'] == 32
+    assert by['c1x1_c1_6_w32']['srcs'][0]['C'] == 6 and by['c1x1_px_w16']['Hout'] * by['c1x1_px_w16']['Wout'] == 48
+    assert by['c1x1_px_w32']['Hout'] * by['c1x1_px_w32']['Wout'] % 64 and by['c1x1_dzwide_w16']['dz']['sH'] > 16
+    n4, rows = by['batch_as_h_n4'], by['batch_as_h_n4_rows']
+    assert n4['srcs'][0]['sN'] == 24 * 16 and rows['srcs'][0]['sN'] == 16 == rows['dz']['sN'] and rows['dz']['sC'] == 4 * 16

@@ -27,7 +27,7 @@ The six kernels that take plain sources reproduce the dense launch to the ratio 
 splits do not change their summation.  The two fused loaders do their pending arithmetic with an fma where the materialised input was
 rounded twice (1.23 .. 1.32; 0.52 and 0.91 with an upsampled source).  The worst, 1.32, is below 1.5: RMS_FACTOR stays at the 2 it was
 set to before anything was measured.  conv_x3h's 2e-06 is on the 96-column window cases: the fused upsample's float32 source coordinate
-loses a bit per doubling of the column index, as torch's own float32 upsample does (see `materialised`).
+loses a bit per doubling of the column index, as torch's own float32 upsample does (see kernel_refs.conv_launch_materialised).
 """
 import ctypes
 import functools
@@ -91,50 +91,16 @@ def launch(handle, desc, mode, transformed, window='case', part=None):
     if part:
         outs.append(stats)
     slopes = [s['slope'] for s in srcs] + [1.0] * (3 - len(srcs))
-    h = model._handle
-    nat.check(nat.lib().vr_profile_begin(h.h))
-    try:
-        nat.debug_kernel(h, 'conv_launch', dims, [desc['epi_slope']] + slopes, ins, outs)
-    finally:
-        z = [ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()]
-        nat.check(nat.lib().vr_profile_end(h.h, ctypes.byref(z[0]), ctypes.byref(z[1]), ctypes.byref(z[2]), ctypes.byref(z[3])))
-    need = nat.lib().vr_profile_report(h.h, None, 0)
-    rep = ctypes.create_string_buffer(int(need) + 1)
-    nat.lib().vr_profile_report(h.h, rep, need)
-    ran = []
-    for ln in rep.value.decode().splitlines():
-        full, calls = ln.split('\t')[0].replace('vr::', '').strip(), int(ln.split('\t')[1])
-        if full.split('<')[0] in CONV_KERNELS:
-            ran += [full] * calls
+    ran = kr.profiled_kernels(nat, model._handle, lambda: nat.debug_kernel(model._handle, 'conv_launch', dims, [desc['epi_slope']] + slopes, ins, outs))
+    ran = [k for k, calls in ran.items() if k.split('<')[0] in CONV_KERNELS for _ in range(calls)]
     return outs[:len(dsts)], stats, ran
-
-
-def materialised(desc):
-    """The virtual input as the device forms it, float32 [N][Cin][Hin][Win]: the pending affine, activation and multiplier in float32, the
-    bilinear x2 by torch's float32 kernel, whose float32 source coordinate i * (float)(n - 1) / (2n - 1) is the one the fused loaders
-    compute (ConvSrc::rh / rw).  Handing the dense launch the float64 input rounded once instead would leave that coordinate's rounding
-    -- which grows with the column index, to 1e-6 of the scale at column 90 -- on the multi-source side of the comparison alone."""
-    F = torch.nn.functional
-    parts = []
-    for s in desc['srcs']:
-        v = torch.from_numpy(s['buf'][kr.view_index(s['off'], s['sN'], s['sC'], s['sH'], desc['N'], s['C'], s['H'], s['W'])])
-        hs = min(s['hsplit'], s['H'])
-        for aff, rows in ((s['aff0'], slice(0, hs)), (s['aff1'] if s['aff1'] is not None else s['aff0'], slice(hs, s['H']))):
-            if aff is not None:
-                a = torch.from_numpy(aff)
-                v[:, :, rows] = v[:, :, rows] * a[:, 0].view(1, -1, 1, 1) + a[:, 1].view(1, -1, 1, 1)
-        v = F.leaky_relu(v, s['slope'])
-        if s['post'] is not None:
-            v = v * torch.from_numpy(s['post'])[:, :, None, None]
-        parts.append(F.interpolate(v, scale_factor=2, mode='bilinear', align_corners=True) if s['up'] else v)
-    return np.ascontiguousarray(torch.cat(parts, dim=1).numpy(), np.float32)
 
 
 def dense_launch(handle, desc, mode, transformed):
     """The same values as ONE dense materialised source through vr_debug_conv2d -> the full output [N][Cout][H][W] (epilogue applied)."""
     nat, model = handle
     model.set_option('mfma_mode', mode)
-    xs = materialised(desc)
+    xs = kr.conv_launch_materialised(desc)
     N, Cin, H, W = xs.shape
     out = np.empty((N, desc['Cout'], H, W), np.float32)
     epi = desc['epi']

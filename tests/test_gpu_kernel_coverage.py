@@ -8,7 +8,9 @@ own launch profiler (`vr_profile_begin / _end / _report`: every VR_LAUNCH of the
 every kernel the built library exports, minus a short list that is launched outside the profiler and has its own tests.
 The numerics of these paths are checked by test_gpu_parity / _kernels / _train / _configs, and those of the LSTM fallbacks, the eval mask
 heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py; the forward conv kernels with concatenated, split and windowed
-launches, each asserting the kernel it ran, by test_gpu_conv_launch.py; here only reachability."""
+launches, each asserting the kernel it ran, by test_gpu_conv_launch.py; the weight-gradient kernels and the two slab sums, with concatenated
+and strided sources, batch-as-rows, train_winograd 0 and mfma_mode 1, each asserting the instantiation it ran, by test_gpu_wgrad_launch.py;
+here only reachability."""
 import ctypes
 import os
 import shutil

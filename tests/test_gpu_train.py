@@ -32,7 +32,7 @@ def small_train(vr):
 
 BWD_CASES = [
     # N, Cin, H,  W,  Cout, ks, stride, dh, dw, up, aff, slope
-    (2, 8, 16, 32, 32, 3, 1, 1, 1, 0, 0, 1.0),
+    (2, 8, 16, 32, 32, 3, 1, 1, 1, 0, 0, 1.0),       # plain input: wgrad_wino_r_kernel<32,32> (the cases with an affine below: direct kernels)
     (1, 40, 24, 64, 64, 3, 1, 1, 1, 0, 1, 0.0),
     (2, 17, 20, 16, 48, 3, 1, 1, 1, 0, 1, 0.01),     # TW=16 tiles, odd Cin, Cout=48
     (2, 16, 32, 64, 32, 3, 2, 1, 1, 0, 1, 0.01),     # stride 2 (parity-class dgrad: 4 tap-masked convs over dz)
@@ -44,11 +44,12 @@ BWD_CASES = [
     (2, 40, 16, 32, 8, 1, 1, 1, 1, 0, 1, 0.0),       # 1x1
     (1, 320, 16, 16, 128, 1, 1, 1, 1, 0, 1, 0.0),
     (2, 12, 8, 16, 32, 3, 1, 1, 1, 1, 1, 0.0),       # through the fused bilinear x2 upsample
-    # plain inputs (no pending affine / activation): the weight gradient takes the Winograd F(3x3,2x2) kernel
-    (1, 40, 24, 64, 64, 3, 1, 1, 1, 0, 0, 1.0),      # 32 input channels x 64 couts per block
-    (2, 97, 12, 48, 32, 3, 1, 1, 1, 0, 0, 1.0),      # 64 x 32 blocks, Cin = 97 (one live channel in the last block)
+    # plain inputs (no pending affine / activation): the weight gradient takes the Winograd F(3x3,2x2) kernel, wgrad_wino_r_kernel<CB,MT>
+    # (tests/test_gpu_wgrad_launch.py asserts the instantiations on launches of these forms)
+    (1, 40, 24, 64, 64, 3, 1, 1, 1, 0, 0, 1.0),      # 64 x 64 blocks (register loader: Cin > 32; 32 x 64 only in mfma_mode 1)
+    (2, 97, 12, 48, 32, 3, 1, 1, 1, 0, 0, 1.0),      # 64 x 32 blocks, Cin = 97 (33 live channels in the second 64-channel block)
     (1, 70, 10, 16, 96, 3, 1, 1, 1, 0, 0, 1.0),      # CoutPad 96, H not a multiple of the 4-row chunk, 16 columns
-    (2, 33, 9, 20, 128, 3, 1, 1, 1, 0, 0, 1.0),      # odd H, W = 20 (partial 16-column chunk)
+    (2, 33, 9, 20, 128, 3, 1, 1, 1, 0, 0, 1.0),      # odd H, W = 20 (partial 16-column chunk); 64 x 64 blocks: one live channel in the second 32-channel half of the one 64-block
     (1, 16, 8, 32, 16, 3, 1, 1, 1, 0, 0, 1.0),       # 32 x 32 blocks, couts padded 16 -> 32
     # plain 1x1: pixel-contiguous GEMM weight gradient (wgrad_gemm.hip)
     (2, 40, 16, 32, 8, 1, 1, 1, 1, 0, 0, 1.0),

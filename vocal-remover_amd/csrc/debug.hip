@@ -3,7 +3,8 @@
 // spectrogram-side glue of stft.hip against float64 numpy (tests/test_gpu_signal.py), and the LSTM fallbacks, the eval mask heads,
 // the squeeze conv and the small kernels around them against oracle/kernel_refs.py (tests/test_gpu_heads_lstm.py), and ONE launch_conv in
 // its general form -- concatenated strided sources, split strided destinations, a column window -- against oracle/kernel_refs.py
-// (tests/test_gpu_conv_launch.py).
+// (tests/test_gpu_conv_launch.py), and ONE launch_wgrad in its general form plus the two slab sums on synthetic slabs
+// (tests/test_gpu_wgrad_launch.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -79,6 +80,7 @@ bool view_fits(long long off, long long sN, long long sC, long long sH, int N, i
 }  // namespace
 
 ConvSrc make_src(const Tensor& t, bool up, int bcastH);   // model.hip
+int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wgrad_mfma.hip: the plan launch_wgrad launches
 
 // name            dims                  fparams          inputs                                              outputs
 // bn_backward     N,C,H,W               slope,eps,mom    z, G, gamma, beta, post[N][C]|null, rm[C], rv[C]    dz, dgamma, dbeta, affine[C][2], rm, rv
@@ -130,6 +132,25 @@ ConvSrc make_src(const Tensor& t, bool up, int bcastH);   // model.hip
 //                 transformed weight forms of the mode (as vr_debug_conv2d's bit 1), bit 1: partials.  Error -2: a view that leaves its
 //                 buffer, and every refusal of launch_conv (message intact).  Error -3: a store found in the 64 floats in front of or
 //                 behind a destination's buffer (the guard bands; a store further out is not seen).
+// wgrad_launch    nsrc,N,Cout,KS,stride, slope of         dz's backing buffer, the gradient buffer            the gradient buffer, whole, as the device left it;
+//                 dil_h,dil_w,flags,    source 0, 1, 2   [Cin][KS*KS][CoutPad] uploaded AS GIVEN (prior       info = four int64 in eight floats: P (the plan's slab
+//                 dz floats,off,sN,sC,                   contents and canaries are the caller's); per        count), part_stride, the scratch floats, the
+//                 sH; per source C,H,W,                  source: its backing buffer, aff0[C][2]|null,        descriptors the deferred sum took
+//                 up,hsplit,floats,off,                  aff1[C][2]|null, post[N][C]|null
+//                 sN,sC,sH
+//                 ONE launch_wgrad in its general form, on the handle's stream, in its mfma_mode and train_winograd (allow_wino).  Sources
+//                 as conv_launch has them; dz is the view (off, sN, sC, sH) [N][Cout][Hout][Wout] of its buffer.  flags bit 0: batch_as_h
+//                 (1x1 on H = 1: build_fwd_args' rewrite of the sources and bwd_conv's of zN / zH), bit 1: accumulate, bit 2: defer (the
+//                 sink set as Model::backward sets it, then flush_wgrad_sums()), bit 3: the launch is issued a second time under the same
+//                 sink, into the same gradient from a scratch slab of its own, accumulating if bit 4 is set.  The scratch slab is sized
+//                 by wgrad_scratch_floats and filled with NaN; gradient and scratch sit between guard bands.  P and part_stride are those
+//                 of wgrad_choose, the function launch_wgrad itself takes its plan from, on the same arguments.  Error -2: a view that leaves
+//                 its buffer, and every refusal of launch_wgrad (message intact).  Error -3: a store found in a guard band.
+// wgrad_reduce    nd; per descriptor    -                per descriptor: its slabs [P][stride], its output   per descriptor: its output buffer after
+//                 P,n,stride,                            buffer (prior contents) of `floats` floats          wgrad_reduce_kernel, the same after the batched sum;
+//                 accumulate,floats,off                                                                      then vec[1] = what wgrad_reduce_vec chose
+//                 The two slab sums on synthetic slabs: every descriptor once through launch_wgrad_reduce, one by one, and all of them once
+//                 through wred_host + flush_wgrad_sums().  A descriptor sums into the n floats at `off` of its output buffer.
 void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin,
                               float* const* out, int nout) {
     const std::string who = "vr_debug_kernel(conv_launch): ";
@@ -229,6 +250,151 @@ void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, i
     }
 }
 
+void Model::debug_wgrad_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                               int nout) {
+    const std::string who = "vr_debug_kernel(wgrad_launch): ";
+    VR_CHECK(ndims >= 13 && nfp >= 3 && nin >= 2 && nout >= 2, -2, who + "too few arguments");
+    const int nsrc = (int)dims[0], N = (int)dims[1], Cout = (int)dims[2], KS = (int)dims[3], stride = (int)dims[4];
+    const int dh = (int)dims[5], dw = (int)dims[6], flags = (int)dims[7];
+    const bool batch_as_h = flags & 1, accumulate = flags & 2, defer = flags & 4, twice = flags & 8, accumulate2 = flags & 16;
+    VR_CHECK(nsrc >= 1 && nsrc <= 3 && N >= 1 && Cout >= 1 && (KS == 1 || KS == 3) && (stride == 1 || stride == 2) && dh >= 1 && dw >= 1, -2,
+             who + "1..3 sources, a 1x1 or 3x3 kernel, stride 1 or 2");
+    VR_CHECK(ndims >= 13 + 10 * nsrc && nin >= 2 + 4 * nsrc, -2, who + "too few arguments");
+    VR_CHECK(in[0] && in[1] && out[0] && out[1], -2, who + "missing dz, gradient or an output");
+    WgradArgs w{};
+    ConvArgs& a = w.in;
+    a.nsrc = nsrc; a.Cout = Cout; a.CoutPad = (Cout + 31) / 32 * 32;
+    a.d1 = a.d2 = 1 << 30;
+    a.pad_h = KS == 1 ? 0 : dh; a.pad_w = KS == 1 ? 0 : dw;
+    std::vector<std::unique_ptr<DevBuf>> keep;
+    auto upload = [&](const float* host, size_t n) { keep.emplace_back(new DevBuf(host, n)); return keep.back()->p; };
+    int Cin = 0, Hin = 0, Win = 0;
+    const ConvSrc* ups = nullptr;
+    for (int i = 0; i < nsrc; ++i) {
+        const int64_t* d = dims + 13 + 10 * i;
+        const float* const* si = in + 2 + 4 * i;
+        Tensor t;
+        t.N = N; t.C = (int)d[0]; t.H = (int)d[1]; t.W = (int)d[2];
+        const bool up = d[3] != 0;
+        t.hsplit = (int)d[4];
+        const size_t floats = (size_t)d[5];
+        t.sN = d[7]; t.sC = d[8]; t.sH = d[9];
+        VR_CHECK(si[0] && view_fits(d[6], t.sN, t.sC, t.sH, N, t.C, t.H, t.W, floats), -2, who + "a source view leaves its buffer");
+        t.p = upload(si[0], floats) + d[6];
+        t.slope = fp[i];
+        if (si[1]) t.aff0 = upload(si[1], (size_t)t.C * 2);
+        if (si[2]) t.aff1 = upload(si[2], (size_t)t.C * 2);
+        if (si[3]) t.post = upload(si[3], (size_t)N * t.C);
+        a.src[i] = make_src(t, up, 0);
+        const int vh = up ? 2 * t.H : t.H, vw = up ? 2 * t.W : t.W;
+        if (i == 0) { Hin = vh; Win = vw; }
+        VR_CHECK(vh == Hin && vw == Win, -2, who + "the sources must share the input size");
+        if (up && ups) VR_CHECK(ups->H == t.H && ups->W == t.W && ups->sH == t.sH, -2, who + "upsampled sources must share H, W and row stride");
+        if (up) ups = &a.src[i];
+        Cin += t.C;
+        if (i == 0) a.c1 = Cin;
+        if (i <= 1) a.c2 = Cin;
+    }
+    a.Cin = Cin;
+    if (nsrc < 2) a.c1 = Cin;                                 // (Model::build_fwd_args: a missing source is an empty range at the end)
+    if (nsrc < 3) a.c2 = Cin;
+    // the dz view, before the batch-as-rows rewrite: [N][Cout][Hout][Wout]
+    const int Hout0 = (Hin + 2 * a.pad_h - dh * (KS - 1) - 1) / stride + 1, Wout = (Win + 2 * a.pad_w - dw * (KS - 1) - 1) / stride + 1;
+    VR_CHECK(Hout0 >= 1 && Wout >= 1, -2, who + "empty output");
+    const size_t zfloats = (size_t)dims[8];
+    VR_CHECK(view_fits(dims[9], dims[10], dims[11], dims[12], N, Cout, Hout0, Wout, zfloats), -2, who + "the dz view leaves its buffer");
+    DevBuf dz(in[0], zfloats);
+    w.dz = dz.p + dims[9];
+    int Nk = N;
+    if (batch_as_h) {                                         // Model::build_fwd_args' and Model::bwd_conv's rewrites
+        VR_CHECK(KS == 1 && Hin == 1, -2, who + "batch-as-rows view needs a 1x1 conv on H=1 input");
+        for (int i = 0; i < nsrc; ++i) {
+            VR_CHECK(!a.src[i].post && !a.src[i].up, -2, who + "batch-as-rows: unsupported source flags");
+            a.src[i].sH = a.src[i].sN; a.src[i].sN = 0; a.src[i].H = N;
+        }
+        Hin = N; Nk = 1;
+        w.zN = 0; w.zC = dims[11]; w.zH = dims[10];
+    } else {
+        w.zN = dims[10]; w.zC = dims[11]; w.zH = dims[12];
+    }
+    a.N = Nk; a.Hin = Hin; a.Win = Win;
+    a.Hout = (Hin + 2 * a.pad_h - dh * (KS - 1) - 1) / stride + 1; a.Wout = Wout;
+    w.Cout = Cout; w.CoutPad = a.CoutPad;
+    w.allow_wino = train_wino ? 1 : 0;
+    w.bf16 = mfma_mode;
+    const ConvShape shp{KS, stride, dh, dw};
+    // the plan launch_wgrad launches (it calls the same wgrad_choose on the same arguments), for P and part_stride
+    WgradArgs pl = w;
+    {
+        int CB = 0, MT = 0;
+        wgrad_choose(pl, shp, &CB, &MT);
+    }
+    const size_t gfloats = (size_t)Cin * KS * KS * a.CoutPad, sfloats = wgrad_scratch_floats(w, shp);
+    VR_CHECK((size_t)pl.P * (size_t)pl.part_stride <= sfloats, -4, who + "the plan's slabs exceed wgrad_scratch_floats");
+    GuardedBuf grad(in[1], gfloats);
+    const std::vector<float> nans(sfloats, std::nanf(""));
+    GuardedBuf scratch(nans.data(), sfloats), scratch2(twice ? nans.data() : nullptr, twice ? sfloats : 0);
+    w.part = scratch.p();
+    long long ndesc = 0;
+    {
+        struct Unsink {                                   // (also when a launch throws: no descriptor of freed buffers stays behind)
+            std::vector<WgReduceDesc>& v;
+            ~Unsink() { wgrad_defer_to(nullptr); v.clear(); }
+        } unsink{wred_host};
+        wred_host.clear();
+        if (defer) wgrad_defer_to(&wred_host);
+        launch_wgrad(w, shp, grad.p(), accumulate ? 1 : 0, stream);
+        if (twice) {
+            w.part = scratch2.p();
+            launch_wgrad(w, shp, grad.p(), accumulate2 ? 1 : 0, stream);
+        }
+        wgrad_defer_to(nullptr);
+        ndesc = (long long)wred_host.size();
+        for (const WgReduceDesc& d : wred_host)
+            VR_CHECK(d.P == pl.P && d.stride == pl.part_stride && d.n == pl.part_stride, -4, who + "the deferred descriptor is not the plan's");
+        flush_wgrad_sums();
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+    VR_CHECK(grad.intact() && scratch.intact() && scratch2.intact(), -3, who + "the launch stored outside the gradient or the scratch slab");
+    grad.download(out[0]);
+    const int64_t info[4] = {pl.P, pl.part_stride, (int64_t)sfloats, ndesc};
+    std::memcpy(out[1], info, sizeof info);
+}
+
+void Model::debug_wgrad_reduce(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout) {
+    const std::string who = "vr_debug_kernel(wgrad_reduce): ";
+    VR_CHECK(ndims >= 1, -2, who + "too few arguments");
+    const int nd = (int)dims[0];
+    VR_CHECK(nd >= 1 && nd <= 128 && ndims >= 1 + 6 * nd && nin >= 2 * nd && nout >= 2 * nd + 1, -2, who + "1..128 descriptors, six dims each");
+    std::vector<std::unique_ptr<DevBuf>> slabs;
+    std::vector<std::unique_ptr<GuardedBuf>> o_imm, o_bat;
+    std::vector<WgReduceDesc> descs;
+    for (int j = 0; j < nd; ++j) {
+        const int64_t* d = dims + 1 + 6 * j;
+        const long long P = d[0], n = d[1], stride = d[2], floats = d[4], off = d[5];
+        VR_CHECK(P >= 1 && n >= 1 && stride >= n && off >= 0 && off + n <= floats, -2, who + "need P, n >= 1, stride >= n and the output inside its buffer");
+        VR_CHECK(in[2 * j] && in[2 * j + 1] && out[2 * j] && out[2 * j + 1] && out[2 * nd], -2, who + "missing buffer");
+        slabs.emplace_back(new DevBuf(in[2 * j], (size_t)(P * stride)));
+        o_imm.emplace_back(new GuardedBuf(in[2 * j + 1], (size_t)floats));
+        o_bat.emplace_back(new GuardedBuf(in[2 * j + 1], (size_t)floats));
+        descs.push_back(WgReduceDesc{slabs.back()->p, stride, o_bat.back()->p() + off, n, (int)P, d[3] != 0 ? 1 : 0, 0});
+    }
+    for (int j = 0; j < nd; ++j) {
+        const WgReduceDesc& d = descs[j];
+        launch_wgrad_reduce(d.part, d.stride, d.P, o_imm[j]->p() + dims[1 + 6 * j + 5], d.n, d.accumulate, stream);
+    }
+    const int vec = wgrad_reduce_vec(descs.data(), nd);
+    wred_host = descs;
+    flush_wgrad_sums();
+    VR_HIP(hipStreamSynchronize(stream));
+    for (int j = 0; j < nd; ++j) {
+        VR_CHECK(o_imm[j]->intact() && o_bat[j]->intact(), -3, who + "a slab sum stored outside its output buffer");
+        o_imm[j]->download(out[2 * j]);
+        o_bat[j]->download(out[2 * j + 1]);
+    }
+    out[2 * nd][0] = (float)vec;
+}
+
 void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims, const float* fp, int nfp,
                          const float* const* in, int nin, float* const* out, int nout) {
     DeviceGuard dev_guard(device);
@@ -250,6 +416,8 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         return;
     }
     if (name == "conv_launch") { debug_conv_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
+    if (name == "wgrad_launch") { debug_wgrad_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
+    if (name == "wgrad_reduce") { debug_wgrad_reduce(dims, ndims, in, nin, out, nout); return; }
     if (name == "bn_backward") {
         need(4, 3, 7, 6);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];

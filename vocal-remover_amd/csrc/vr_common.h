@@ -200,6 +200,8 @@ void wgrad_defer_to(std::vector<WgReduceDesc>* sink);          // nullptr: launc
 int wgrad_reduce_vec(const WgReduceDesc* host_descs, int n);    // 4: every slab / gradient is 16-byte aligned and sized (a block sums 256 elements), else 1 (64)
 void launch_wgrad_reduce_batched(const WgReduceDesc* d_descs, int n, long long total_blocks, int vec, hipStream_t st);
 size_t wgrad_scratch_floats(const WgradArgs& a, const ConvShape& s);
+// out[i] (+)= the sum over the P slabs part[p * stride + i], i < n: the immediate form of the slab sum (wgrad_reduce_kernel)
+void launch_wgrad_reduce(const float* part, long long stride, int P, float* out, long long n, int accumulate, hipStream_t st);
 
 // Returns the algorithmic FLOPs of the launch (2*MACs) for roofline accounting.
 double launch_conv(const ConvArgs& a, const ConvShape& s, hipStream_t st);

@@ -579,41 +579,63 @@ void launch_wgrad_reduce_batched(const WgReduceDesc* d_descs, int n, long long t
 static thread_local std::vector<WgReduceDesc>* g_wgrad_sink = nullptr;
 void wgrad_defer_to(std::vector<WgReduceDesc>* sink) { g_wgrad_sink = sink; }
 
+void launch_wgrad_reduce(const float* part, long long stride, int P, float* out, long long n, int accumulate, hipStream_t st) {
+    VR_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, part, stride, P, out, n, accumulate);
+    VR_HIP(hipGetLastError());
+}
+
+// A second sum into an `out` that already has a deferred descriptor runs immediately (wgrad_reduce below), i.e. BEFORE the deferred one.
+// The two commute only when both accumulate: a store on either side would drop or double a sum.  Model::backward always accumulates;
+// anything else is refused here, in front of the launch, instead of summing wrongly.
+static void wgrad_check_deferred(const float* grad_out, int accumulate) {
+    if (!g_wgrad_sink) return;
+    for (const WgReduceDesc& d : *g_wgrad_sink)
+        VR_CHECK(d.out != grad_out || (d.accumulate && accumulate), -2,
+                 "wgrad: a second sum into a gradient that has a deferred sum runs before it: both must accumulate");
+}
+
 static void wgrad_reduce(const WgradArgs& a, float* grad_out, int accumulate, hipStream_t st) {
     const long long n = a.part_stride;
     if (g_wgrad_sink) {
         // a later layer of the same step may add into the same gradient (shared weights do not exist in this net, but the debug hooks
         // accumulate on purpose): two deferred sums into one `out` would race inside the batched launch -- the second one runs now
+        // (both accumulate: wgrad_check_deferred)
         for (const WgReduceDesc& d : *g_wgrad_sink)
             if (d.out == grad_out) goto immediate;
         g_wgrad_sink->push_back(WgReduceDesc{a.part, a.part_stride, grad_out, n, a.P, accumulate, 0});
         return;
     }
 immediate:
-    VR_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, a.part, a.part_stride,
-                       a.P, grad_out, n, accumulate);
-    VR_HIP(hipGetLastError());
+    launch_wgrad_reduce(a.part, a.part_stride, a.P, grad_out, n, accumulate, st);
+}
+
+// The kernel family that takes a launch, chosen from the real pointers (alignment decides), and its slab partition filled into `a`
+// (P, part_stride, the grid's factors).  launch_wgrad launches what this returns and the debug hook of one launch (debug.hip) reports
+// it: one function, so the two cannot drift apart.  1: Winograd F(3x3,2x2), 2.25x fewer MFMAs (*CB x *MT blocks); 2: 1x1, the
+// pixel-contiguous GEMM on the LDS-DMA ring; 0: the direct kernels (wg_pick).
+int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT) {
+    if (wgrad_wino_pick(a, s, CB, MT)) { wgrad_wino_plan(a, *CB, *MT); return 1; }
+    if (wgrad_gemm_pick(a, s)) { wgrad_gemm_plan(a); return 2; }
+    wgrad_plan(a, s);
+    return 0;
 }
 
 double launch_wgrad(const WgradArgs& a_in, const ConvShape& s, float* grad_out, int accumulate, hipStream_t st) {
     WgradArgs a = a_in;
     VR_CHECK(a.part != nullptr, -2, "wgrad needs a scratch slab");
-    {
-        int CB = 0, MT = 0;
-        if (wgrad_wino_pick(a, s, &CB, &MT)) {             // Winograd F(3x3,2x2): 2.25x fewer MFMAs
-            wgrad_wino_plan(a, CB, MT);
-            wgrad_wino_launch(a, CB, MT, st);
-            wgrad_reduce(a, grad_out, accumulate, st);
-            return 2.0 * a.in.N * (double)a.in.Hout * a.in.Wout * (double)a.Cout * a.in.Cin * 9;
-        }
+    wgrad_check_deferred(grad_out, accumulate);
+    int CB = 0, MT = 0;
+    const int family = wgrad_choose(a, s, &CB, &MT);
+    if (family == 1) {
+        wgrad_wino_launch(a, CB, MT, st);
+        wgrad_reduce(a, grad_out, accumulate, st);
+        return 2.0 * a.in.N * (double)a.in.Hout * a.in.Wout * (double)a.Cout * a.in.Cin * 9;
     }
-    if (wgrad_gemm_pick(a, s)) {                           // 1x1: pixel-contiguous GEMM, LDS-DMA ring
-        wgrad_gemm_plan(a);
+    if (family == 2) {
         wgrad_gemm_launch(a, st);
         wgrad_reduce(a, grad_out, accumulate, st);
         return 2.0 * a.in.N * (double)a.in.Hout * a.in.Wout * (double)a.Cout * a.in.Cin;
     }
-    wgrad_plan(a, s);
     const WgTile t = wg_pick(a, s);
     {
         static const bool dma_on = !getenv("VR_NO_WGRAD_DMA");
