@@ -95,7 +95,10 @@ int vr_set_mode(vr_handle h, int training);
  * "params_dirty": the parameter arena was written from outside (vr_param_arena).
  * "conv_x3d" (round 6, "mfma_mode" 3 only): the 16-column layers of 256-frame crops -- the ASPP branch convs (lib/layers.py:74-85) and
  *   Encoder.conv2 of enc5 -- on the fp16 matrix pipe: 2 (default, also -1) with the four ASPP branches of a module in one launch,
- *   1 one launch per conv, 0 the fp32-pipe kernels.   */
+ *   1 one launch per conv, 0 the fp32-pipe kernels.
+ * "conv_x3s" ("mfma_mode" 3 only, eval): the encoders' 3x3 stride-2 convs (Encoder.conv1, lib/layers.py:33) with at least 32 output
+ *   columns and more than 16 input channels on the fp16 matrix pipe: 1 (default, also -1; VR_CONV_X3S=0 makes 0 the default),
+ *   0 the fp32-pipe kernel for them.   */
 int vr_set_option(vr_handle h, const char* name, int value);
 
 /* CascadedNet.forward (mode 0) / predict_mask (mode 1) / predict (mode 2)   lib/nets.py:82-141

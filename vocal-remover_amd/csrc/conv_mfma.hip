@@ -345,6 +345,8 @@ void conv_fill_tiling(ConvArgs& a, const ConvShape& s) {
     if (x3_pick(a, s, &x3t)) { x3_fill_tiling(a, x3t); return; }
     int x3d_mt;
     if (x3d_pick(a, s, &x3d_mt)) { x3d_fill_tiling(a, x3d_mt); return; }
+    X3Tile x3st;
+    if (x3s_pick(a, s, &x3st)) { x3s_fill_tiling(a, x3st); return; }
     if (wino_pick(a, s, &wino_mt)) { wino_fill_tiling(a, wino_mt); return; }
     DmaTile dt;
     if (dma_pick(a, s, &dt)) { dma_fill_tiling(a, dt); return; }
@@ -427,6 +429,12 @@ double launch_conv(const ConvArgs& a_in, const ConvShape& s, hipStream_t st) {
         if (a.nsrc >= 1 && a.nsrc <= 3 && x3d_pick(a, s, &x3d_mt)) {
             x3d_fill_tiling(a, x3d_mt);
             x3d_launch_conv(a, s, x3d_mt, st);
+            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
+        }
+        X3Tile x3st;
+        if (x3s_pick(a, s, &x3st)) {                              // 3x3 stride 2 on the fp16 pipe (conv_x3s.hip: eval, one plain source)
+            x3s_fill_tiling(a, x3st);
+            x3s_launch_conv(a, x3st, st);
             return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
         }
         if (a.nsrc >= 1 && a.nsrc <= 3 && wino_pick(a, s, &wino_mt)) {

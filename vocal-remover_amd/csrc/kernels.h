@@ -97,6 +97,11 @@ void x3d_fill_tiling(ConvArgs& a, int MT);
 void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, hipStream_t st);
 bool x3d_aspp_eligible(const ConvArgs* c4, const ConvShape* s4);   // c4 / s4 in concat order: 1x1, dilation (4,2), (8,4), (12,6)
 void x3d_launch_aspp(const ConvArgs* c4, hipStream_t st);          // the four branch convs of an ASPP module in ONE launch
+// conv_x3s.hip: conv_x3h's arithmetic for the 3x3 STRIDE-2 layers with >= 32 output columns (eval, one plain source), the stride taken in the
+// loader; weights in x3h format (KK = 9); mfma_mode 3 only
+bool x3s_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t);
+void x3s_fill_tiling(ConvArgs& a, const X3Tile& t);
+void x3s_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st);
 void launch_upsample2x(const Tensor& x, float* out, hipStream_t st);   // dense [N][C][2H][2W], activated
 
 // ---- lstm.hip -----------------------------------------------------------------------------------

@@ -312,6 +312,9 @@ private:
     int x3d_mode = 2;                                    // option "conv_x3d": 0 off, 1 single launches, 2 + the ASPP branch group
     int conv_w_lo = 0, conv_w_hi = 0;                    // set: the next run_conv stores only these output columns if conv_x3h takes it
     std::vector<Conv*> x3d_list;                         // the ASPP branch convs conv_x3d.hip takes in mfma_mode 3: dilated 3x3, conv2 (1x1)
+    int x3s_mode = x3s_default();                        // option "conv_x3s": the 3x3 stride-2 layers on the fp16 pipe in eval (conv_x3s.hip, mfma_mode 3); 0: conv_dma.hip
+    static int x3s_default() { const char* e = getenv("VR_CONV_X3S"); return (e && atoi(e) == 0) ? 0 : 1; }
+    std::vector<Conv*> x3s_list;                         // the 3x3 stride-2 convs (enc2..enc5.conv1): fp16 planes, filled in mfma_mode 3
     float* wino_arena = nullptr;
     float* winot_arena = nullptr;                        // training: Winograd copies of the flipped/transposed weights
     std::map<const Param*, float*> winot_of;

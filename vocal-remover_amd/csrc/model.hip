@@ -62,6 +62,7 @@ void Model::build_cba(Conv& L, const std::string& prefix, int nin, int nout_, in
     L.bn = add_bn(prefix + ".conv.1", nout_, 0);
     if (ks == 3 && stride == 1 && dh == 1 && dw == 1) wino_list.push_back(&L);
     if (ks == 3 && stride == 1 && dh > 1) x3d_list.push_back(&L);         // the dilated ASPP branches (conv_x3d.hip)
+    if (ks == 3 && stride == 2 && dh == 1 && dw == 1) x3s_list.push_back(&L);   // the encoder's stride-2 convs (conv_x3s.hip)
 }
 
 // nets.BaseNet (lib/nets.py:10-24)
@@ -370,6 +371,10 @@ void Model::set_option(const std::string& name, int value) {
         if (value < -1 || value > 2) throw Error(-2, "conv_x3d: 0, 1, 2 or -1 (default)");     // 1 one launch per conv, 2 (default) + the four ASPP branches in one launch
         x3d_mode = value < 0 ? 2 : value;
     }
+    else if (name == "conv_x3s") {                           // the 3x3 stride-2 layers on the fp16 pipe in eval (conv_x3s.hip, mfma_mode 3): 0 off (conv_dma.hip)
+        if (value < -1 || value > 1) throw Error(-2, "conv_x3s: 0, 1 or -1 (default)");
+        x3s_mode = value < 0 ? x3s_default() : value;
+    }
     else if (name == "crop_window") crop_window = value != 0;
     else if (name == "adam_reset") reset_adam_state();      // a freshly constructed torch.optim.Adam has no moments
     else if (name == "hip_graph" || name == "conv_x3p" || name == "wgrad_x3h" || name == "conv_x3b") {
@@ -408,16 +413,20 @@ void Model::refresh_wino(bool with_dgrad) {
             size_t total = 0;
             for (Conv* L : wino_list) total += x3_weights_bytes(L->Cin, 9, L->CoutPad);
             for (Conv* L : x3d_list) total += x3_weights_bytes(L->Cin, L->KS * L->KS, L->CoutPad);
+            for (Conv* L : x3s_list) total += x3_weights_bytes(L->Cin, 9, L->CoutPad);
             VR_HIP(hipMalloc(reinterpret_cast<void**>(&x3_arena), total ? total : 16));
             size_t off = 0;
             for (Conv* L : wino_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, 9, L->CoutPad); }
             for (Conv* L : x3d_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, L->KS * L->KS, L->CoutPad); }
+            for (Conv* L : x3s_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, 9, L->CoutPad); }
         }
         {
             std::vector<X3WDesc> d;
             for (Conv* L : wino_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, 9, L->CoutPad});
-            if (mfma_mode == 3)
+            if (mfma_mode == 3) {
                 for (Conv* L : x3d_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, L->KS * L->KS, L->CoutPad});
+                for (Conv* L : x3s_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, 9, L->CoutPad});
+            }
             run_x3_batch(xb_fwd, d);
         }
         if (with_dgrad) {
@@ -798,6 +807,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
     a.wino6 = (a.wino && mfma_mode == 2) ? L.wino6 : nullptr;
     a.x3w = (x3_mode() && !(training && !train_wino)) ? L.x3w : nullptr;
     if (!x3d_mode && a.Win == 16) a.x3w = nullptr;          // (16-column layers: only conv_x3d.hip reads the planes)
+    if (L.stride == 2 && (training || !x3s_mode)) a.x3w = nullptr;   // (stride-2 layers: conv_x3s.hip is eval only; option conv_x3s 0: conv_dma.hip)
     a.bf16 = mfma_mode;
     int wcols = a.Wout;                                      // output columns the launch computes
     if (conv_w_hi > 0 && !training && mfma_mode == 3 && !batch_as_h && !conv_sink) {
@@ -2578,7 +2588,14 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
 void Model::debug_weight_forms(const float* dw_, int Cin, int KS, int stride, int dh, int dw, int CoutPad, int Win, bool want_wino,
                                ConvArgs& a, DebugWeightForms& f) {
     const int KK = KS * KS;
-    if (want_wino && mfma_mode == 3 && stride == 1 && (KS == 1 || dh > 1)) {
+    if (mfma_mode == 3 && KS == 3 && stride == 2 && dh == 1 && dw == 1) {
+        // conv_x3s.hip's layers (3x3 stride 2): fp16-plane weights, with or without the flag -- no other weight form exists for them
+        if (x3s_mode) {
+            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
+            launch_x3h_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
+            a.x3w = f.x3w;
+        }
+    } else if (want_wino && mfma_mode == 3 && stride == 1 && (KS == 1 || dh > 1)) {
         // conv_x3d.hip's layers (dilated 3x3, 1x1 at 16 columns): fp16-plane weights only
         VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, KK, CoutPad)));
         launch_x3h_weights(dw_, f.x3w, Cin, KK, CoutPad, stream);
