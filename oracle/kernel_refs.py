@@ -587,3 +587,170 @@ def wgrad_launch_ref(desc, accumulate=False, times=1):
     Cout <= co < CoutPad, on top of desc['prior'] where the launch accumulates."""
     out = times * wgrad_kmajor(wgrad_launch_grad(desc), desc['CoutPad'])
     return out + np.asarray(desc['prior'], np.float64) if accumulate else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one data-gradient launch of a conv record (Model::bwd_conv_dgrad) in the network's forms: a strided dz, 1..3 sources with a strided
+# gradient view each (absent, stored into or accumulated into), upsampled and broadcast sources, batch-as-rows
+# ---------------------------------------------------------------------------------------------------------------------------------
+DGRAD_PATHS = {1: 'stride 1', 2: 'fused', 3: 'four classes', 4: 'zero insertion'}           # Model::DgradPath
+DGRAD_ALL_MODES = ((3, 1), (2, 1), (0, 1), (1, 1), (3, 0))                                  # (mfma_mode, train_winograd)
+
+
+def _gsrc(C, H, W, up=0, bcastH=0, absent=False):
+    return dict(C=C, H=H, W=W, up=up, bcastH=bcastH, absent=absent)
+
+
+def _dcase(name, N, Cout, srcs, runs, variants, KS=3, stride=1, dil=(1, 1), dz='band', batch_as_h=False, post=None):
+    # runs: (mfma_mode, train_winograd) -> (path, the conv kernel the data gradient must take, its launch count); a full name with template
+    # arguments where the case is about an instantiation, else the family.  variants: (layout of the gradient views, accumulate).
+    # post: the kernel that must follow the conv (upsample / broadcast backward).
+    return dict(name=name, N=N, Cout=Cout, srcs=srcs, runs=runs, variants=variants, KS=KS, stride=stride, dil=dil, dz=dz,
+                batch_as_h=batch_as_h, post=post)
+
+
+_STORE_ACC = (('dense', 0), ('dense', 1))
+_DST_MATRIX = tuple((lay, acc) for lay in ('dense', 'pitch', 'odd') for acc in (0, 1))
+_FUSED = {(3, 1): ('fused', 'conv_dma_s2d_kernel<4>', 1)}
+_CLASSES = {(3, 1): ('four classes', 'conv_dma_kernel<3,1,1,1,32,8,32,4,true>', 4)}
+_ZINS_MFMA = {(3, 1): ('zero insertion', 'conv_mfma_kernel', 1)}
+_X3D = {(3, 1): ('stride 1', 'conv_x3d_kernel', 1)}
+
+# The case table of tests/test_gpu_dgrad_launch.py and of the pin in tests/test_cpu_kernel_refs.py.  The kernels are filled in from
+# s2d_fused_eligible, dma_pick, ws_pick, x3_pick, x3d_pick, wino_pick and thin16_pick on the arguments bwd_conv_dgrad builds: the data
+# gradient is a conv with Cin = the layer's Cout (dz) and Cout = the layer's Cin, one plain source, split destinations.
+DGRAD_LAUNCH_CASES = [
+    # stride 2, 3x3.  Fused: dz channels % 4 == 0, dz width >= 16 and % 4 == 0
+    _dcase('s2_fused', 2, 32, [_gsrc(24, 18, 72)], _FUSED, _DST_MATRIX, stride=2),          # 2 x 2 tiles of 16 x 64: one interior, three edge
+    _dcase('s2_fused_odd', 1, 40, [_gsrc(20, 15, 71)], _FUSED, _STORE_ACC, stride=2),       # odd s2_H and s2_W; the dense pitch 71 is odd
+    _dcase('s2_fused_w16', 2, 64, [_gsrc(33, 16, 32)], _FUSED, _STORE_ACC, stride=2),
+    _dcase('s2_fused_cat3', 1, 32, [_gsrc(12, 16, 64), _gsrc(20, 16, 64), _gsrc(8, 16, 64, absent=True)], _FUSED, _STORE_ACC, stride=2),
+    # dz channels 30: not fused; class widths 32 / 32: four tap-masked launches
+    _dcase('s2_classes', 2, 30, [_gsrc(16, 16, 64)], _CLASSES, _DST_MATRIX, stride=2),
+    # forward width 63: class widths 32 / 31, the narrower refused by dma_pick -> zero insertion with nothing written before
+    _dcase('s2_classes_odd_w', 1, 30, [_gsrc(16, 16, 63)], _ZINS_MFMA, _STORE_ACC, stride=2),
+    _dcase('s2_zins_w12', 2, 32, [_gsrc(16, 16, 24)], _ZINS_MFMA, _STORE_ACC, stride=2),    # dz width 12 < 16
+    _dcase('s2_zins_w22', 1, 32, [_gsrc(24, 12, 44)], _ZINS_MFMA, _STORE_ACC, stride=2),    # dz width 22: the 176-frame form
+    # the same form on a grid ws_pick accepts (2 x 8 x 2 pixel tiles x 4 cout tiles = 128 workgroups)
+    _dcase('s2_zins_ws', 2, 16, [_gsrc(128, 64, 44)], {(3, 1): ('zero insertion', 'conv_ws_kernel', 1)}, (('dense', 0),), stride=2),
+    # stride 1
+    _dcase('dec_up_skip', 2, 16, [_gsrc(16, 8, 16, up=1), _gsrc(8, 16, 32)],
+           {(3, 1): ('stride 1', 'conv_x3h_kernel', 1), (2, 1): ('stride 1', 'conv_x3_kernel', 1), (0, 1): ('stride 1', 'conv_dma_kernel', 1),
+            (1, 1): ('stride 1', 'conv_dma_kernel', 1), (3, 0): ('stride 1', 'conv_dma_kernel', 1)},
+           (('pitch', 0), ('pitch', 1)), post='upsample_bwd_tiled_kernel<true>'),
+    _dcase('dec_up_small', 2, 16, [_gsrc(6, 3, 8, up=1), _gsrc(8, 6, 16)], _X3D, (('pitch', 0), ('pitch', 1)), post='upsample_bwd_kernel'),
+    _dcase('aspp_bcast', 2, 24, [_gsrc(8, 1, 16, bcastH=16), _gsrc(32, 16, 16)], _X3D, _STORE_ACC, KS=1, post='sum_h_kernel'),
+    _dcase('cat3_5_17_10', 2, 32, [_gsrc(5, 16, 32), _gsrc(17, 16, 32, absent=True), _gsrc(10, 16, 32)],
+           {(3, 1): ('stride 1', 'conv_x3h_kernel', 1), (2, 1): ('stride 1', 'conv_x3_kernel', 1), (0, 1): ('stride 1', 'conv_wino_kernel', 1),
+            (1, 1): ('stride 1', 'conv_wino_kernel', 1), (3, 0): ('stride 1', 'conv_dma_kernel', 1)},
+           (('pitch', 0), ('dense', 1))),
+    _dcase('dil_4_2_cols16', 2, 32, [_gsrc(32, 16, 16)], _X3D, _STORE_ACC, dil=(4, 2)),
+    # batch-as-rows (the LSTM's Linear): ConvDst{g, 0, sC, sN}, always accumulated into
+    _dcase('batch_as_h_n3', 3, 40, [_gsrc(24, 1, 16)], _X3D, (('dense', 1), ('pitch', 1)), KS=1, batch_as_h=True),
+    _dcase('batch_as_h_n4', 4, 40, [_gsrc(24, 1, 16)], _X3D, (('dense', 1), ('pitch', 1)), KS=1, batch_as_h=True),
+]
+
+
+def _gstrides(layout, N, C, H, W):
+    """(floats, off, sN, sC, sH) of a gradient view: dense, 'pitch' (every step even: 8-byte aligned rows) or 'odd' (an odd row pitch and
+    an odd offset: no 8-byte aligned pair of columns)."""
+    if layout == 'odd':
+        sH = W + 1 + W % 2
+        sC = H * sH + 2
+        sN = C * sC + 6
+        return 3 + N * sN, 3, sN, sC, sH
+    return _strides(layout, N, C, H, W)
+
+
+def dgrad_launch_build(case, layout='dense', accumulate=0):
+    """The float32 data of one run of a case: weights, dz as a strided view (what lies between its elements a thousand times larger), and per
+    source the backing buffer of its gradient: the canary everywhere, prior values inside the view where the run accumulates (a broadcast
+    source and a batch-as-rows record always do), the canary -- a NaN -- inside it too where the run stores.  The values depend on the
+    case's name alone, not on the layout or on store / accumulate."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(('dgrad ' + case['name']).encode()))
+    fill = np.random.default_rng(zlib.crc32(('dgrad fill ' + case['name']).encode()))
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)                          # noqa: E731
+    N, Cout, KS, stride, (dh, dw) = case['N'], case['Cout'], case['KS'], case['stride'], case['dil']
+    srcs_in = case['srcs']
+    Cin = sum(s['C'] for s in srcs_in)
+    s0 = srcs_in[0]
+    Hin, Win = (2 * s0['H'], 2 * s0['W']) if s0['up'] else ((s0['bcastH'] or s0['H']), s0['W'])
+    ph, pw = (dh, dw) if KS == 3 else (0, 0)
+    Hout, Wout = (Hin + 2 * ph - dh * (KS - 1) - 1) // stride + 1, (Win + 2 * pw - dw * (KS - 1) - 1) // stride + 1
+    w = f32(rng.standard_normal((Cout, Cin, KS, KS)) / (Cout * KS * KS) ** 0.5)
+    zv = f32(rng.standard_normal((N, Cout, Hout, Wout)))
+    floats, off, sN, sC, sH = _strides(case['dz'], N, Cout, Hout, Wout)
+    zbuf = f32(fill.standard_normal(floats) * 1e3)
+    zbuf[view_index(off, sN, sC, sH, N, Cout, Hout, Wout)] = zv
+    dz = dict(buf=zbuf, off=off, sN=sN, sC=sC, sH=sH)
+    srcs = []
+    for s in srcs_in:
+        C, H, W = s['C'], s['H'], s['W']
+        prior = f32(rng.standard_normal((N, C, H, W)))                          # drawn for every source: the values do not depend on the run
+        lay = 'dense' if (s['bcastH'] or s['absent']) else layout
+        floats, off, sN, sC, sH = _gstrides(lay, N, C, H, W)
+        mode = 0 if s['absent'] else (2 if (accumulate or s['bcastH'] or case['batch_as_h']) else 1)
+        buf = np.full(floats, CANARY_BITS, np.uint32).view(np.float32)
+        if mode == 2:
+            buf[view_index(off, sN, sC, sH, N, C, H, W)] = prior
+        srcs.append(dict(C=C, H=H, W=W, up=s['up'], bcastH=s['bcastH'], mode=mode, buf=buf, off=off, sN=sN, sC=sC, sH=sH))
+    return dict(name=case['name'], N=N, Cin=Cin, Cout=Cout, KS=KS, stride=stride, dil=case['dil'], Hin=Hin, Win=Win, Hout=Hout, Wout=Wout,
+                w=w, dz=dz, srcs=srcs, batch_as_h=case['batch_as_h'])
+
+
+def upsample2x_align_transpose(g):
+    """The transpose of upsample2x_align: [N][C][2H][2W] -> [N][C][H][W], G_lo = U_h^T G U_w with U the interpolation matrix."""
+    def matrix(n):
+        x = np.arange(2 * n, dtype=np.float64) * (n - 1) / (2 * n - 1)
+        i0 = np.minimum(np.floor(x).astype(np.int64), n - 1)
+        i1, lam = np.minimum(i0 + 1, n - 1), x - i0
+        U = np.zeros((2 * n, n))
+        np.add.at(U, (np.arange(2 * n), i0), 1 - lam)
+        np.add.at(U, (np.arange(2 * n), i1), lam)
+        return U
+    Uh, Uw = matrix(g.shape[2] // 2), matrix(g.shape[3] // 2)
+    return np.einsum('hi,nchw,wj->ncij', Uh, g, Uw, optimize=True)
+
+
+def dgrad_launch_grads(desc):
+    """Per source the float64 gradient [N][C][H][W] of the launch, without prior contents: the gradient of conv2d with respect to the virtual
+    concatenated input (dz scattered back through every tap), split by channel, an `up` source pulled back through the transpose of the
+    bilinear x2, a `bcastH` source summed over H."""
+    N, KS, s, (dh, dw) = desc['N'], desc['KS'], desc['stride'], desc['dil']
+    z = desc['dz']
+    dz = np.asarray(z['buf'], np.float64)[view_index(z['off'], z['sN'], z['sC'], z['sH'], N, desc['Cout'], desc['Hout'], desc['Wout'])]
+    w = np.asarray(desc['w'], np.float64)
+    ph, pw = (dh, dw) if KS == 3 else (0, 0)
+    Hin, Win, Hout, Wout = desc['Hin'], desc['Win'], desc['Hout'], desc['Wout']
+    gp = np.zeros((N, desc['Cin'], Hin + 2 * ph, Win + 2 * pw))
+    for kh in range(KS):
+        for kw in range(KS):
+            gp[:, :, kh * dh:kh * dh + (Hout - 1) * s + 1:s, kw * dw:kw * dw + (Wout - 1) * s + 1:s] += \
+                np.einsum('nohw,oc->nchw', dz, w[:, :, kh, kw], optimize=True)
+    gx = gp[:, :, ph:ph + Hin, pw:pw + Win]
+    out, c0 = [], 0
+    for t in desc['srcs']:
+        g = gx[:, c0:c0 + t['C']]
+        c0 += t['C']
+        if t['up']:
+            g = upsample2x_align_transpose(g)
+        elif t['bcastH']:
+            g = g.sum(axis=2, keepdims=True)
+        out.append(g)
+    return out
+
+
+def dgrad_launch_ref(desc):
+    """Per source its whole backing buffer after the launch, float64: the gradient stored into the view (mode 1) or added to its prior
+    contents (mode 2); everything outside the view, and the whole buffer of an absent source (mode 0), as given."""
+    bufs = []
+    for t, g in zip(desc['srcs'], dgrad_launch_grads(desc)):
+        b = np.asarray(t['buf'], np.float64).copy()
+        idx = view_index(t['off'], t['sN'], t['sC'], t['sH'], desc['N'], t['C'], t['H'], t['W'])
+        if t['mode'] == 1:
+            b[idx] = g
+        elif t['mode'] == 2:
+            b[idx] = b[idx] + g
+        bufs.append(b)
+    return bufs

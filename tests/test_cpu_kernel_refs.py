@@ -4,7 +4,8 @@ the BiLSTM statement against torch.nn.LSTM(bidirectional=True) in float64, the t
 written a second way, and the conditions the saturated-gate LSTM cases are chosen by; the general conv launch of
 tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in float64, over that test's case table; the general
 weight-gradient launch of tests/test_gpu_wgrad_launch.py (`wgrad_launch_ref`) against torch autograd of F.conv2d in float64, over that
-test's case table.  No GPU."""
+test's case table; the data-gradient launch of tests/test_gpu_dgrad_launch.py (`dgrad_launch_ref`) against torch autograd through
+torch.cat / F.interpolate / expand / F.conv2d in float64, over that test's.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -297,3 +298,103 @@ def test_wgrad_launch_case_table_holds_the_forms_it_is_meant_to():
     assert by['c1x1_px_w32']['Hout'] * by['c1x1_px_w32']['Wout'] % 64 and by['c1x1_dzwide_w16']['dz']['sH'] > 16
     n4, rows = by['batch_as_h_n4'], by['batch_as_h_n4_rows']
     assert n4['srcs'][0]['sN'] == 24 * 16 and rows['srcs'][0]['sN'] == 16 == rows['dz']['sN'] and rows['dz']['sC'] == 4 * 16
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# dgrad_launch_ref: the reference of tests/test_gpu_dgrad_launch.py, over the same case table
+# ---------------------------------------------------------------------------------------------------------------------------------
+DGRAD_RUNS = [(c, lay, acc) for c in kr.DGRAD_LAUNCH_CASES for lay, acc in c['variants']]
+
+
+@pytest.mark.parametrize('case,layout,accumulate', DGRAD_RUNS, ids=['%s-%s-%s' % (c['name'], lay, 'acc' if acc else 'store') for c, lay, acc in DGRAD_RUNS])
+def test_dgrad_launch_reference_equals_torch_autograd_in_float64(case, layout, accumulate):
+    """Leaves in float64, one per source at its own resolution; the virtual input by F.interpolate(align_corners=True) / expand over the rows
+    / torch.cat; F.conv2d; backward from dz read through its as_strided view.  Each leaf's gradient, written through the as_strided view of
+    a copy of its buffer (stored or added), equals dgrad_launch_ref's buffer to 1e-12 of the gradient's scale inside the view and bit for
+    bit outside it; an absent source's buffer comes back as given."""
+    F = torch.nn.functional
+    desc = kr.dgrad_launch_build(case, layout, accumulate)
+    N, KS, (dh, dw) = desc['N'], desc['KS'], desc['dil']
+    leaves, parts = [], []
+    for t in desc['srcs']:
+        x = torch.zeros(N, t['C'], t['H'], t['W'], dtype=torch.float64, requires_grad=True)
+        leaves.append(x)
+        if t['up']:
+            parts.append(F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True))
+        elif t['bcastH']:
+            parts.append(x.expand(N, t['C'], t['bcastH'], t['W']))
+        else:
+            parts.append(x)
+    y = F.conv2d(torch.cat(parts, dim=1), torch.from_numpy(desc['w']).double(), stride=desc['stride'],
+                 padding=(dh, dw) if KS == 3 else 0, dilation=(dh, dw))
+    assert tuple(y.shape) == (N, desc['Cout'], desc['Hout'], desc['Wout'])
+    z = desc['dz']
+    y.backward(_torch_view(torch.from_numpy(z['buf']).double(), z, N, desc['Cout'], desc['Hout'], desc['Wout']))
+    got = kr.dgrad_launch_ref(desc)
+    assert len(got) == len(desc['srcs'])
+    for t, x, b in zip(desc['srcs'], leaves, got):
+        given = t['buf'].astype(np.float64)
+        if t['mode'] == 0:
+            assert np.array_equal(b.view(np.uint64), given.view(np.uint64))
+            continue
+        want = torch.from_numpy(given.copy())
+        view = _torch_view(want, t, N, t['C'], t['H'], t['W'])
+        if t['mode'] == 1:
+            view.copy_(x.grad)
+        else:
+            view.add_(x.grad)
+        idx = kr.view_index(t['off'], t['sN'], t['sC'], t['sH'], N, t['C'], t['H'], t['W'])
+        scale = float(x.grad.abs().max())
+        assert scale > 0 and np.isfinite(b[idx]).all()
+        assert float(np.abs(b[idx] - want.numpy()[idx]).max()) <= 1e-12 * scale
+        outside = np.ones(b.size, bool)
+        outside[idx.ravel()] = False
+        assert np.array_equal(b[outside].view(np.uint64), given[outside].view(np.uint64))
+
+
+def test_dgrad_launch_case_table_holds_the_forms_it_is_meant_to():
+    """The properties the cases are chosen for, so an edit of the table cannot quietly lose one."""
+    cases = {c['name']: c for c in kr.DGRAD_LAUNCH_CASES}
+    assert len(cases) == len(kr.DGRAD_LAUNCH_CASES)
+    by = {n: kr.dgrad_launch_build(c) for n, c in cases.items()}
+    fused = lambda d: d['stride'] == 2 and d['Cout'] % 4 == 0 and d['Wout'] >= 16 and d['Wout'] % 4 == 0     # noqa: E731  (s2d_fused_eligible)
+    for n, d in by.items():
+        assert fused(d) == (cases[n]['runs'][(3, 1)][0] == 'fused'), n
+        assert d['N'] * d['Hin'] * d['Win'] <= 8192, n
+    t = by['s2_fused']                                         # 16 x 64 output tiles: (0, 0) inside, the other three cut by the image
+    assert (t['Hin'], t['Win']) == (18, 72) and 16 <= t['Hin'] < 32 and 64 <= t['Win'] < 128
+    t = by['s2_fused_odd']
+    assert t['Hin'] % 2 == 1 and t['Win'] % 2 == 1 and t['srcs'][0]['sH'] % 2 == 1
+    assert by['s2_fused_w16']['Wout'] == 16
+    t = by['s2_fused_cat3']
+    c1, c2 = t['srcs'][0]['C'], t['srcs'][0]['C'] + t['srcs'][1]['C']
+    assert c1 % 8 != 0 and c1 // 8 == (c1 + 3) // 8 and c2 == 32 and t['srcs'][2]['mode'] == 0      # a boundary inside an 8-channel group
+    # the four classes: widths (Win + 1) // 2 and Win // 2; dma_pick refuses a tap-masked launch below 32 columns
+    for n, both in (('s2_classes', True), ('s2_classes_odd_w', False)):
+        d = by[n]
+        assert not fused(d) and d['Wout'] % 4 == 0 and (d['Win'] + 1) // 2 >= 32 and ((d['Win'] // 2 >= 32) == both), n
+    assert by['s2_zins_w12']['Wout'] == 12 and by['s2_zins_w22']['Wout'] == 22
+    # the views of the destination matrix: 8-byte aligned or not
+    for n in ('s2_fused', 's2_classes'):
+        assert set(cases[n]['variants']) == {(lay, acc) for lay in ('dense', 'pitch', 'odd') for acc in (0, 1)}
+        for lay, al8 in (('dense', True), ('pitch', True), ('odd', False)):
+            s = kr.dgrad_launch_build(cases[n], lay, 0)['srcs'][0]
+            assert all(s[k] % 2 == 0 for k in ('off', 'sN', 'sC', 'sH')) == al8, (n, lay)
+            assert (lay == 'dense') == (s['sH'] == s['W'] and s['off'] == 0)
+    # stores run with a NaN canary as prior contents, accumulates with finite ones; a broadcast source and batch-as-rows always accumulate
+    for n, c in cases.items():
+        for lay, acc in c['variants']:
+            for s, t in zip(c['srcs'], kr.dgrad_launch_build(c, lay, acc)['srcs']):
+                idx = kr.view_index(t['off'], t['sN'], t['sC'], t['sH'], c['N'], t['C'], t['H'], t['W'])
+                inside = t['buf'][idx]
+                want_mode = 0 if s['absent'] else (2 if acc or s['bcastH'] or c['batch_as_h'] else 1)
+                assert t['mode'] == want_mode and (np.isfinite(inside).all() if want_mode == 2 else (inside.view(np.uint32) == kr.CANARY_BITS).all())
+                assert int((t['buf'].view(np.uint32) == kr.CANARY_BITS).sum()) == t['buf'].size - (idx.size if want_mode == 2 else 0)
+    up, small = by['dec_up_skip']['srcs'][0], by['dec_up_small']['srcs'][0]
+    assert up['up'] and up['W'] >= 16 and up['H'] >= 4 and up['W'] % 2 == 0 and small['up'] and small['H'] < 4      # launch_upsample_bwd's forms
+    assert by['aspp_bcast']['srcs'][0]['bcastH'] == 16 and by['aspp_bcast']['KS'] == 1
+    assert [s['mode'] for s in by['cat3_5_17_10']['srcs']] == [1, 0, 1]
+    assert by['dil_4_2_cols16']['dil'] == (4, 2) and by['dil_4_2_cols16']['Win'] == 16
+    assert set(cases['cat3_5_17_10']['runs']) == set(cases['dec_up_skip']['runs']) == set(kr.DGRAD_ALL_MODES)
+    assert all(set(c['runs']) == {(3, 1)} for n, c in cases.items() if n not in ('cat3_5_17_10', 'dec_up_skip'))
+    assert by['batch_as_h_n3']['N'] == 3 and by['batch_as_h_n4']['N'] == 4 and by['batch_as_h_n3']['Hin'] == 1

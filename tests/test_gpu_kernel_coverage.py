@@ -10,7 +10,8 @@ The numerics of these paths are checked by test_gpu_parity / _kernels / _train /
 heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py; the forward conv kernels with concatenated, split and windowed
 launches, each asserting the kernel it ran, by test_gpu_conv_launch.py; the weight-gradient kernels and the two slab sums, with concatenated
 and strided sources, batch-as-rows, train_winograd 0 and mfma_mode 1, each asserting the instantiation it ran, by test_gpu_wgrad_launch.py;
-here only reachability."""
+the data gradient of a conv record on its three stride-2 paths, with split, strided, stored and accumulated destinations, upsampled and broadcast
+sources and batch-as-rows, each asserting the path and the kernel it ran, by test_gpu_dgrad_launch.py; here only reachability."""
 import ctypes
 import os
 import shutil

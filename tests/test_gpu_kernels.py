@@ -82,6 +82,110 @@ def test_batchnorm_train_forward_stats_and_backward(handle, shape, slope, use_po
     close(out[5], rv, 'running_var (unbiased)', 1e-5)
 
 
+def _wide(shape, view, seed, prior=None):
+    """A backing buffer of canary bits holding the view (floats, off, sN, sC, sH) of `shape`, filled with `prior` (a tensor) or left as the
+    canary -- a NaN -- where prior is None -> (buffer, flat indices of the view)."""
+    floats, off, sN, sC, sH = view
+    idx = kernel_refs.view_index(off, sN, sC, sH, *shape)
+    buf = np.full(floats, kernel_refs.CANARY_BITS, np.uint32).view(np.float32)
+    if prior is not None:
+        buf[idx] = f32(prior)
+    return buf, idx
+
+
+def _untouched(got, given, idx, what):
+    outside = np.ones(got.size, bool)
+    outside[idx.ravel()] = False
+    assert np.array_equal(got.view(np.uint32)[outside], given.view(np.uint32)[outside]), '%s: floats outside the view changed' % what
+
+
+def _slice_view(N, C, H, W, Ctot, c0, extra=0):
+    """Channels [c0, c0 + C) of a dense [N][Ctot][H][W] buffer (an ASPP branch output inside the concatenation buffer), `extra` floats in."""
+    return N * Ctot * H * W + extra, c0 * H * W + extra, Ctot * H * W, H * W, W
+
+
+# conv outputs that are VIEWS (Model::run_conv's out_view: the ASPP branch outputs are channel slices of the concatenation buffer) and the
+# squeeze BatchNorm(1) with its broadcast affine table.  (2, 8, 16, 16): H * W / 4 = 64 quads per plane, the row-looped reduce and apply4;
+# (2, 8, 64, 64): 1024 quads, the flat reduce4p / apply4p; the same one float further into its buffer: no 16-byte alignment,
+# bn_bwd_reduce_kernel's scalar loop and bn_bwd_apply_kernel.
+@pytest.mark.parametrize('shape,view,aff_bcast,kernels', [
+    ((2, 8, 16, 16), _slice_view(2, 8, 16, 16, 40, 16), 0, ('bn_bwd_reduce_kernel', 'bn_bwd_apply4_kernel')),
+    ((2, 8, 64, 64), _slice_view(2, 8, 64, 64, 40, 16), 0, ('bn_bwd_reduce4p_kernel', 'bn_bwd_apply4p_kernel')),
+    ((2, 8, 64, 64), _slice_view(2, 8, 64, 64, 40, 16, extra=1), 0, ('bn_bwd_reduce_kernel', 'bn_bwd_apply_kernel')),
+    ((4, 1, 64, 32), _slice_view(4, 1, 64, 32, 1, 0), 1, ('bn_bwd_reduce4p_kernel', 'bn_bwd_apply4p_kernel')),
+], ids=['slice_8_of_40', 'slice_8_of_40_flat', 'slice_off_by_one_float', 'aff_bcast_c1'])
+def test_batchnorm_backward_on_a_view(handle, shape, view, aff_bcast, kernels):
+    nat, h = handle
+    N, C, H, W = shape
+    g = torch.Generator().manual_seed(N * 1000 + C + H)
+    z = (torch.randn(shape, generator=g) * 1.5 + torch.randn(1, C, 1, 1, generator=g)).float()
+    G = torch.randn(shape, generator=g).float()
+    gamma, beta = (torch.rand(C, generator=g) + 0.5).float(), (torch.randn(C, generator=g) * 0.3).float()
+    rm0, rv0 = (torch.randn(C, generator=g) * 0.1).float(), (torch.rand(C, generator=g) + 0.5).float()
+    post = (torch.rand(N, C, generator=g) > 0.2).float() / 0.9
+    slope = 0.01
+    zd = z.double().requires_grad_(True)
+    gd, bd = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    y = F.batch_norm(zd, rm0.double().clone(), rv0.double().clone(), gd, bd, True, 0.1, 1e-5)
+    (act(y, slope) * post.double()[:, :, None, None]).backward(G.double())
+    zbuf, idx = _wide(shape, view, 0, z)
+    gbuf, _ = _wide(shape, view, 0, G)
+    zbuf[np.isnan(zbuf)] = 1e30                        # what lies around the view in the wider buffer: large, finite, never to be read
+    out = [np.zeros_like(gbuf), np.empty(C, np.float32), np.empty(C, np.float32), np.empty((C, 2), np.float32),
+           np.empty(C, np.float32), np.empty(C, np.float32)]
+    ran = kernel_refs.profiled_kernels(nat, h, lambda: nat.debug_kernel(
+        h, 'bn_backward', list(shape) + list(view) + [aff_bcast], [slope, 1e-5, 0.1],
+        [zbuf, gbuf, f32(gamma), f32(beta), f32(post), f32(rm0), f32(rv0)], out))
+    assert sorted(k for k in ran if k.startswith('bn_bwd_') and 'finalize' not in k) == sorted(kernels), ran
+    _untouched(out[0], gbuf, idx, 'bn_backward')
+    close(out[0][idx], zd.grad, 'dz')
+    close(out[1], gd.grad, 'dgamma')
+    close(out[2], bd.grad, 'dbeta')
+
+
+# the low-resolution gradient as a strided view, stored into (the tensor's first backward writer) or accumulated into: (2, 3, 8, 16) the tiled
+# kernel with vector loads, (1, 2, 5, 17) with scalar ones, (1, 2, 5, 7) upsample_bwd_kernel
+@pytest.mark.parametrize('accumulate', [0, 1], ids=['store', 'acc'])
+@pytest.mark.parametrize('shape,kernel', [((2, 3, 8, 16), 'upsample_bwd_tiled_kernel<true>'), ((1, 2, 5, 17), 'upsample_bwd_tiled_kernel<false>'),
+                                          ((1, 2, 5, 7), 'upsample_bwd_kernel')])
+def test_upsample_transpose_into_a_strided_view(handle, shape, kernel, accumulate):
+    nat, h = handle
+    N, C, H, W = shape
+    g = torch.Generator().manual_seed(H * 100 + W + 7)
+    x = torch.randn(shape, generator=g).float()
+    dhi = torch.randn(N, C, 2 * H, 2 * W, generator=g).float()
+    prior = torch.randn(shape, generator=g).float()
+    xd = x.double().requires_grad_(True)
+    F.interpolate(xd, scale_factor=2, mode='bilinear', align_corners=True).backward(dhi.double())
+    view = kernel_refs._strides('pitch', N, C, H, W)
+    gbuf, idx = _wide(shape, view, 0, prior if accumulate else None)             # a store must not read the prior: the NaN canary
+    out = [np.empty((N, C, 2 * H, 2 * W), np.float32), np.zeros_like(gbuf)]
+    ran = kernel_refs.profiled_kernels(nat, h, lambda: nat.debug_kernel(h, 'upsample', list(shape) + list(view) + [accumulate], [],
+                                                                        [f32(x), f32(dhi), gbuf], out))
+    assert [k for k in ran if k.startswith('upsample_bwd')] == [kernel], ran
+    _untouched(out[1], gbuf, idx, 'upsample backward')
+    close(out[1][idx], xd.grad + prior.double() if accumulate else xd.grad, 'upsample backward into a view')
+
+
+@pytest.mark.parametrize('accumulate', [0, 1], ids=['store', 'acc'])
+def test_avgpool_backward_into_a_strided_view(handle, accumulate):
+    nat, h = handle
+    shape = N, C, H, W = (1, 5, 3, 9)
+    g = torch.Generator().manual_seed(C + 11)
+    x = torch.randn(shape, generator=g).float()
+    gp = torch.randn(N, C, W, generator=g).float()
+    d = torch.randn(shape, generator=g).float()
+    prior = torch.randn(shape, generator=g).float()
+    xd = x.double().requires_grad_(True)
+    F.adaptive_avg_pool2d(xd, (1, None))[:, :, 0].backward(gp.double())
+    view = kernel_refs._strides('pitch', N, C, H, W)
+    gbuf, idx = _wide(shape, view, 0, prior if accumulate else None)
+    out = [np.empty((N, C, W), np.float32), np.zeros_like(gbuf), np.empty((N, C, W), np.float32)]
+    nat.debug_kernel(h, 'pool', list(shape) + list(view) + [accumulate], [], [f32(x), f32(gp), f32(d), gbuf], out)
+    _untouched(out[1], gbuf, idx, 'avgpool backward')
+    close(out[1][idx], xd.grad + prior.double() if accumulate else xd.grad, 'avgpool backward into a view', 1e-5)
+
+
 # (11, 72, 64): eleven samples over the eight sample slices of lstm_whh_grad_kernel, a ragged last frame block; (16, 256, 32): the
 # benched batch
 @pytest.mark.parametrize('N,T,H', [(2, 128, 64), (3, 128, 32), (1, 40, 16), (11, 72, 64), (16, 256, 32)])

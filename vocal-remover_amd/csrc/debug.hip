@@ -4,7 +4,8 @@
 // the squeeze conv and the small kernels around them against oracle/kernel_refs.py (tests/test_gpu_heads_lstm.py), and ONE launch_conv in
 // its general form -- concatenated strided sources, split strided destinations, a column window -- against oracle/kernel_refs.py
 // (tests/test_gpu_conv_launch.py), and ONE launch_wgrad in its general form plus the two slab sums on synthetic slabs
-// (tests/test_gpu_wgrad_launch.py).
+// (tests/test_gpu_wgrad_launch.py), and ONE data gradient of a conv record (Model::bwd_conv_dgrad) in the network's forms
+// (tests/test_gpu_dgrad_launch.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -83,14 +84,24 @@ ConvSrc make_src(const Tensor& t, bool up, int bcastH);   // model.hip
 int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wgrad_mfma.hip: the plan launch_wgrad launches
 
 // name            dims                  fparams          inputs                                              outputs
-// bn_backward     N,C,H,W               slope,eps,mom    z, G, gamma, beta, post[N][C]|null, rm[C], rv[C]    dz, dgamma, dbeta, affine[C][2], rm, rv
+// bn_backward     N,C,H,W[,floats,off,  slope,eps,mom    z, G, gamma, beta, post[N][C]|null, rm[C], rv[C]    dz, dgamma, dbeta, affine[C][2], rm, rv
+//                 sN,sC,sH,aff_bcast]
+//                 with the six trailing dims z and G are the view (off, sN, sC, sH) of two backing buffers of `floats` floats each (a conv
+//                 output that is a channel slice of a wider buffer), given and returned whole, G between guard bands (error -3);
+//                 aff_bcast 1 (C == 1): the affine table is the broadcast copy of the squeeze BatchNorm(1), BnBwdArgs::aff_bcast
 // lstm            N,T,H[,flags]         -                gx[N][8H][T], whh_f[4H][H], whh_r, dh[N][2H][T]     h[N][2H][T], dgx[N][8H][T], dwhh_f, dwhh_r
 //                                                        [, dwhh_f0[4H][H]|null, dwhh_r0|null]
 //                 the W_hh gradient is ACCUMULATED onto dwhh_f0 / dwhh_r0 (zeros when absent).  flags bit 0: the inference form,
 //                 launch_bilstm without a save buffer -- only h is produced, dh and the other outputs may be null; bit 1: only
 //                 launch_bilstm_bwd, on a zeroed save buffer (its own size check, which the forward's would otherwise pre-empt)
-// upsample        N,C,H,W               -                x[N,C,H,W], dhi[N,C,2H,2W]                          up[N,C,2H,2W], glo[N,C,H,W]
-// pool            N,C,H,W               -                x, gp[N,C,W], d[N,C,H,W]                            pooled[N,C,W], g[N,C,H,W], sumh[N,C,W]
+// upsample        N,C,H,W[,floats,off,  -                x[N,C,H,W], dhi[N,C,2H,2W][, glo's backing buffer]  up[N,C,2H,2W], glo[N,C,H,W]
+//                 sN,sC,sH,accumulate]
+// pool            N,C,H,W[,floats,off,  -                x, gp[N,C,W], d[N,C,H,W][, g's backing buffer]      pooled[N,C,W], g[N,C,H,W], sumh[N,C,W]
+//                 sN,sC,sH,accumulate]
+//                 upsample / pool with the six trailing dims: the low-resolution gradient of launch_upsample_bwd / the gradient of
+//                 launch_avgpool_bwd is the view (off, sN, sC, sH) of a backing buffer of `floats` floats, uploaded AS GIVEN (prior
+//                 contents, canaries) between guard bands and returned whole in its output; accumulate 0 stores, 1 adds.  Without them:
+//                 dense, accumulated onto zeros
 // thin            N,C,H,W,CO            slope            x, aff[C][2]|null, w[CO][C], dz[N,CO,H,W]           g[N,C,H,W], dw[CO][C], z[N,H,W] (CO=1: forward)
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
 // head            N,C,H,W,w_lo,w_hi,pad_rows,cplx,hsplit,use_items,pitch_extra
@@ -146,6 +157,22 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 by wgrad_scratch_floats and filled with NaN; gradient and scratch sit between guard bands.  P and part_stride are those
 //                 of wgrad_choose, the function launch_wgrad itself takes its plan from, on the same arguments.  Error -2: a view that leaves
 //                 its buffer, and every refusal of launch_wgrad (message intact).  Error -3: a store found in a guard band.
+// dgrad_launch    nsrc,N,Cout,KS,stride, -               w[Cout][Cin][KS][KS] (OIHW), dz's backing buffer;   per source its gradient's backing buffer, whole, as
+//                 dil_h,dil_w,flags,                     per source the backing buffer of its gradient,      the device left it; info = four int64 in eight
+//                 dz floats,off,sN,sC,                   uploaded AS GIVEN (prior contents and canaries      floats: the path (Model::DgradPath: 1 stride 1,
+//                 sH; per source C,H,W,                  are the caller's)                                   2 fused parity classes, 3 four tap-masked launches,
+//                 up,bcastH,mode,floats,                                                                     4 zero insertion), the workspace floats, 0, 0
+//                 off,sN,sC,sH
+//                 ONE Model::bwd_conv_dgrad: the data gradient of a conv record and the passes after it (launch_upsample_bwd for an `up`
+//                 source, launch_sum_h for a `bcastH` one), on the handle's stream, in its mfma_mode and train_winograd, with the
+//                 transposed weight forms a train step would hold (Model::debug_dgrad_weight_forms).  dz is the view (off, sN, sC, sH)
+//                 [N][Cout][Hout][Wout] of its buffer; a source's gradient the view [N][C][H][W] of its own (C, H, W before the x2
+//                 upsample `up`; H = 1 with bcastH = the rows it is broadcast over, and then dense: launch_sum_h takes no strides).  mode 0:
+//                 the source takes no gradient (its buffer must come back untouched), 1: the first writer stores (the hook marks the
+//                 buffer fresh, Model::g_fresh), 2: accumulate.  flags bit 0: batch_as_h.  The workspace is sized by a dry pass, filled
+//                 with NaN, and like every gradient buffer sits between guard bands.  Error -2: a view that leaves its buffer and every
+//                 refusal of a launch (message intact; the outputs then hold the buffers as the refused call left them).  Error -3: a
+//                 store found in a guard band.
 // wgrad_reduce    nd; per descriptor    -                per descriptor: its slabs [P][stride], its output   per descriptor: its output buffer after
 //                 P,n,stride,                            buffer (prior contents) of `floats` floats          wgrad_reduce_kernel, the same after the batched sum;
 //                 accumulate,floats,off                                                                      then vec[1] = what wgrad_reduce_vec chose
@@ -361,6 +388,106 @@ void Model::debug_wgrad_launch(const int64_t* dims, int ndims, const float* fp, 
     std::memcpy(out[1], info, sizeof info);
 }
 
+void Model::debug_dgrad_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout) {
+    const std::string who = "vr_debug_kernel(dgrad_launch): ";
+    VR_CHECK(ndims >= 13 && nin >= 2, -2, who + "too few arguments");
+    const int nsrc = (int)dims[0], N = (int)dims[1], Cout = (int)dims[2], KS = (int)dims[3], stride = (int)dims[4];
+    const int dh = (int)dims[5], dw = (int)dims[6], flags = (int)dims[7];
+    const bool batch_as_h = flags & 1;
+    VR_CHECK(nsrc >= 1 && nsrc <= 3 && N >= 1 && Cout >= 1 && (KS == 1 || KS == 3) && (stride == 1 || stride == 2) && dh >= 1 && dw >= 1, -2,
+             who + "1..3 sources, a 1x1 or 3x3 kernel, stride 1 or 2");
+    VR_CHECK(stride == 1 || (KS == 3 && dh == 1 && dw == 1), -2, who + "stride 2 needs a 3x3 kernel without dilation");
+    VR_CHECK(ndims >= 13 + 11 * nsrc && nin >= 2 + nsrc && nout >= nsrc + 1, -2, who + "too few arguments");
+    VR_CHECK(in[0] && in[1] && out[nsrc], -2, who + "missing weights, dz or the info output");
+    Conv L;
+    L.name = "debug"; L.KS = KS; L.stride = stride; L.dh = dh; L.dw = dw;
+    L.pad_h = KS == 1 ? 0 : dh; L.pad_w = KS == 1 ? 0 : dw; L.bn = nullptr; L.slope = 1.f;
+    TapeRec r;
+    r.kind = TK_CONV; r.L = &L; r.N = N; r.batch_as_h = batch_as_h;
+    // sources: only their shapes and gradient views matter to a data gradient
+    std::vector<std::unique_ptr<GuardedBuf>> grads(nsrc);
+    struct Unfresh {                                      // (also when a launch throws: no entry of a freed buffer stays behind)
+        std::map<const float*, bool>& fresh;
+        std::vector<const float*> keys;
+        ~Unfresh() { for (const float* k : keys) fresh.erase(k); }
+    } unfresh{g_fresh, {}};
+    int Cin = 0, Hin = 0, Win = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        const int64_t* d = dims + 13 + 11 * i;
+        Tensor t;
+        t.N = N; t.C = (int)d[0]; t.H = (int)d[1]; t.W = (int)d[2];
+        const bool up = d[3] != 0;
+        const int bcastH = (int)d[4], mode = (int)d[5];
+        const size_t floats = (size_t)d[6];
+        t.sN = d[8]; t.sC = d[9]; t.sH = d[10];
+        VR_CHECK(mode >= 0 && mode <= 2 && bcastH >= 0 && !(up && bcastH), -2, who + "mode is 0, 1 or 2; a source is upsampled or broadcast, not both");
+        VR_CHECK(in[2 + i] && out[i], -2, who + "every source needs its gradient buffer, in and out");
+        VR_CHECK(view_fits(d[7], t.sN, t.sC, t.sH, N, t.C, t.H, t.W, floats), -2, who + "a gradient view leaves its buffer");
+        if (bcastH) VR_CHECK(t.H == 1 && t.sC == t.W && t.sN == (long long)t.C * t.W, -2, who + "a broadcast source has H = 1 and a dense gradient");
+        grads[i].reset(new GuardedBuf(in[2 + i], floats));
+        if (mode) t.g = grads[i]->p() + d[7];
+        if (mode == 1) { g_fresh[t.g] = true; unfresh.keys.push_back(t.g); }
+        SrcSpec sp{t};
+        sp.up = up; sp.bcastH = bcastH;
+        r.srcs.push_back(sp);
+        const int vh = up ? 2 * t.H : (bcastH ? bcastH : t.H), vw = up ? 2 * t.W : t.W;
+        if (i == 0) { Hin = vh; Win = vw; }
+        VR_CHECK(vh == Hin && vw == Win, -2, who + "the sources must share the input size");
+        Cin += t.C;
+    }
+    L.Cin = Cin; L.Cout = Cout; L.CoutPad = (Cout + 31) / 32 * 32;
+    const int KK = KS * KS;
+    Param P;
+    P.kind = PK_CONV; P.Cin = Cin; P.Cout = Cout; P.KK = KK; P.CoutPad = L.CoutPad;
+    L.w = &P;
+    std::vector<float> wk((size_t)Cin * KK * L.CoutPad, 0.f);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int k = 0; k < KK; ++k) wk[((size_t)ci * KK + k) * L.CoutPad + co] = in[0][((size_t)co * Cin + ci) * KK + k];
+    DevBuf dwk(wk.data(), wk.size());
+    P.dev = dwk.p;
+    // dz: the view [N][Cout][Hout][Wout] of its buffer
+    const int Hout = (Hin + 2 * L.pad_h - dh * (KS - 1) - 1) / stride + 1, Wout = (Win + 2 * L.pad_w - dw * (KS - 1) - 1) / stride + 1;
+    VR_CHECK(Hout >= 1 && Wout >= 1, -2, who + "empty output");
+    const size_t zfloats = (size_t)dims[8];
+    VR_CHECK(view_fits(dims[9], dims[10], dims[11], dims[12], N, Cout, Hout, Wout, zfloats), -2, who + "the dz view leaves its buffer");
+    DevBuf dz(in[1], zfloats);
+    r.out.p = nullptr; r.out.g = dz.p + dims[9]; r.out.N = N; r.out.C = Cout; r.out.H = Hout; r.out.W = Wout;
+    r.out.sN = dims[10]; r.out.sC = dims[11]; r.out.sH = dims[12]; r.out.slope = 1.f;
+    ConvArgs f;
+    build_fwd_args(L, r.srcs, N, batch_as_h, f);          // (refuses a batch-as-rows record that is no 1x1 conv on H = 1)
+    DebugDgradForms forms;
+    debug_dgrad_weight_forms(P, KS, stride, dh, dw, forms);
+    // the workspace: sized by a dry pass, then a guarded slab of exactly that size in place of the handle's arena
+    struct WsRestore {
+        Model* m; Arena saved;
+        ~WsRestore() { m->ws = saved; m->dry = false; }
+    } ws_restore{this, ws};
+    ws.dry = true; ws.base = nullptr; ws.off = 0; ws.peak = 0; dry = true;
+    bwd_conv_dgrad(r, f);
+    dry = false;
+    const size_t wfloats = (ws.peak + 3) / 4;
+    const std::vector<float> nans(wfloats, std::nanf(""));
+    GuardedBuf wsbuf(nans.data(), wfloats);
+    ws = Arena{};
+    ws.base = reinterpret_cast<char*>(wsbuf.p()); ws.cap = wfloats * 4;
+    int path = DG_NONE;
+    try {
+        path = bwd_conv_dgrad(r, f);
+    } catch (...) {                                       // a refusal: the caller still sees what the buffers hold (nothing may have been written)
+        (void)hipStreamSynchronize(stream);
+        for (int i = 0; i < nsrc; ++i) grads[i]->download(out[i]);
+        throw;
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+    bool intact = wsbuf.intact();
+    for (int i = 0; i < nsrc; ++i) intact = intact && grads[i]->intact();
+    VR_CHECK(intact, -3, who + "the launch stored outside a gradient buffer or the workspace");
+    for (int i = 0; i < nsrc; ++i) grads[i]->download(out[i]);
+    const int64_t info[4] = {path, (int64_t)wfloats, 0, 0};
+    std::memcpy(out[nsrc], info, sizeof info);
+}
+
 void Model::debug_wgrad_reduce(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout) {
     const std::string who = "vr_debug_kernel(wgrad_reduce): ";
     VR_CHECK(ndims >= 1, -2, who + "too few arguments");
@@ -418,37 +545,50 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
     if (name == "conv_launch") { debug_conv_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "wgrad_launch") { debug_wgrad_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "wgrad_reduce") { debug_wgrad_reduce(dims, ndims, in, nin, out, nout); return; }
+    if (name == "dgrad_launch") { debug_dgrad_launch(dims, ndims, in, nin, out, nout); return; }
     if (name == "bn_backward") {
         need(4, 3, 7, 6);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];
-        const size_t n = (size_t)N * C * H * W;
-        DevBuf z(in[0], n), g(in[1], n), gamma(in[2], C), beta(in[3], C), rm(in[5], C), rv(in[6], C);
+        // optional: z and G as a view of a wider buffer, and the broadcast affine table of BatchNorm(1)
+        const bool view = ndims >= 10;
+        const long long off = view ? dims[5] : 0, sH = view ? dims[8] : W, sC = view ? dims[7] : (long long)H * W, sN = view ? dims[6] : sC * C;
+        const size_t n = view ? (size_t)dims[4] : (size_t)N * C * H * W;
+        const int aff_bcast = view && dims[9] != 0 ? 1 : 0;
+        VR_CHECK(N >= 1 && C >= 1 && H >= 1 && W >= 1, -2, "bn_backward: empty tensor");
+        VR_CHECK(view_fits(off, sN, sC, sH, N, C, H, W, n), -2, "bn_backward: the view leaves its buffer");
+        VR_CHECK(!aff_bcast || C == 1, -2, "bn_backward: a broadcast affine table belongs to a single-channel BatchNorm");
+        DevBuf z(in[0], n), gamma(in[2], C), beta(in[3], C), rm(in[5], C), rv(in[6], C);
+        GuardedBuf g(in[1], n);
         DevBuf post(in[4], in[4] ? (size_t)N * C : 0);
         // forward statistics: one partial row of (sum, sumsq) per channel, then the library's own finalize
         std::vector<float> part((size_t)C * 2);
         for (int c = 0; c < C; ++c) {
             double s1 = 0, s2 = 0;
-            for (int b = 0; b < N; ++b) {
-                const float* q = in[0] + ((size_t)b * C + c) * H * W;
-                for (size_t i = 0; i < (size_t)H * W; ++i) { s1 += q[i]; s2 += (double)q[i] * q[i]; }
-            }
+            for (int b = 0; b < N; ++b)
+                for (int h = 0; h < H; ++h) {
+                    const float* q = in[0] + off + b * sN + c * sC + h * sH;
+                    for (int i = 0; i < W; ++i) { s1 += q[i]; s2 += (double)q[i] * q[i]; }
+                }
             part[2 * c] = (float)s1; part[2 * c + 1] = (float)s2;
         }
-        DevBuf dpart(part.data(), part.size()), aff((size_t)C * 2), smean(C), sinv(C), dgamma(C), dbeta(C);
+        const int bcast_rows = aff_bcast ? 8 : 0;             // (the squeeze BatchNorm's table is one row per frequency bin, all equal)
+        DevBuf dpart(part.data(), part.size()), aff((size_t)(aff_bcast ? bcast_rows : C) * 2), smean(C), sinv(C), dgamma(C), dbeta(C);
         BNFinalizeArgs f{};
         f.part = dpart.p; f.nparts = 1; f.pstride = C * 2; f.count = (double)N * H * W;
         f.w = gamma.p; f.b = beta.p; f.rm = rm.p; f.rv = rv.p; f.affine = aff.p; f.save_mean = smean.p; f.save_invstd = sinv.p;
-        f.C = C; f.eps = fp[1]; f.momentum = fp[2]; f.broadcast = 0;
+        f.C = C; f.eps = fp[1]; f.momentum = fp[2]; f.broadcast = bcast_rows;
         launch_bn_finalize(f, st);
         BnBwdArgs a{};
-        a.g = g.p; a.z = z.p; a.N = N; a.C = C; a.H = H; a.W = W; a.sH = W; a.sC = (long long)H * W; a.sN = a.sC * C;
-        a.aff = aff.p; a.aff_bcast = 0; a.slope = fp[0]; a.post = in[4] ? post.p : nullptr;
+        a.g = g.p() + off; a.z = z.p + off; a.N = N; a.C = C; a.H = H; a.W = W; a.sH = sH; a.sC = sC; a.sN = sN;
+        a.aff = aff.p; a.aff_bcast = aff_bcast; a.slope = fp[0]; a.post = in[4] ? post.p : nullptr;
         a.gamma = gamma.p; a.save_mean = smean.p; a.save_invstd = sinv.p; a.dgamma = dgamma.p; a.dbeta = dbeta.p; a.acc_grads = 1;
         DevBuf coef((size_t)C * 3), bpart((size_t)bn_bwd_chunks(a) * C * 2);
         a.coef = coef.p; a.part = bpart.p;
         launch_bn_bwd(a, st);
         VR_HIP(hipStreamSynchronize(st));
-        g.download(out[0]); dgamma.download(out[1]); dbeta.download(out[2]); aff.download(out[3]); rm.download(out[4]); rv.download(out[5]);
+        VR_CHECK(g.intact(), -3, "bn_backward: a store outside the gradient's buffer");
+        g.download(out[0]); dgamma.download(out[1]); dbeta.download(out[2]); rm.download(out[4]); rv.download(out[5]);
+        if (out[3]) VR_HIP(hipMemcpy(out[3], aff.p, (size_t)C * 2 * sizeof(float), hipMemcpyDeviceToHost));
     } else if (name == "lstm") {
         const int flags = ndims >= 4 ? (int)dims[3] : 0;
         const bool infer = flags & 1, bwd_only = flags & 2;
@@ -478,20 +618,39 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         need(4, 0, 2, 2);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];
         const size_t n = (size_t)N * C * H * W;
-        DevBuf x(in[0], n), dhi(in[1], 4 * n), up(4 * n), glo(n);
+        // optional: the low-resolution gradient as a view of its own buffer (prior contents in[2]), stored into or accumulated into
+        const bool view = ndims >= 10;
+        const long long off = view ? dims[5] : 0, gN = view ? dims[6] : (long long)C * H * W, gC = view ? dims[7] : (long long)H * W, gH = view ? dims[8] : W;
+        const size_t gfloats = view ? (size_t)dims[4] : n;
+        VR_CHECK(N >= 1 && C >= 1 && H >= 1 && W >= 1, -2, "upsample: empty tensor");
+        VR_CHECK(!view || (nin >= 3 && in[2]), -2, "upsample: a strided gradient needs its backing buffer");
+        VR_CHECK(view_fits(off, gN, gC, gH, N, C, H, W, gfloats), -2, "upsample: the gradient view leaves its buffer");
+        const std::vector<float> zeros(view ? 0 : n, 0.f);
+        DevBuf x(in[0], n), dhi(in[1], 4 * n), up(4 * n);
+        GuardedBuf glo(view ? in[2] : zeros.data(), gfloats);
         launch_upsample2x(dense(x.p, N, C, H, W), up.p, st);
-        launch_upsample_bwd(dhi.p, N, C, H, W, glo.p, (long long)C * H * W, (long long)H * W, W, 1, st);
+        launch_upsample_bwd(dhi.p, N, C, H, W, glo.p() + off, gN, gC, gH, view ? (dims[9] != 0 ? 1 : 0) : 1, st);
         VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(glo.intact(), -3, "upsample: a store outside the gradient's buffer");
         up.download(out[0]); glo.download(out[1]);
     } else if (name == "pool") {
         need(4, 0, 3, 3);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];
         const size_t n = (size_t)N * C * H * W, m = (size_t)N * C * W;
-        DevBuf x(in[0], n), gp(in[1], m), d(in[2], n), pooled(m), g(n), sumh(m);
+        const bool view = ndims >= 10;
+        const long long off = view ? dims[5] : 0, gN = view ? dims[6] : (long long)C * H * W, gC = view ? dims[7] : (long long)H * W, gH = view ? dims[8] : W;
+        const size_t gfloats = view ? (size_t)dims[4] : n;
+        VR_CHECK(N >= 1 && C >= 1 && H >= 1 && W >= 1, -2, "pool: empty tensor");
+        VR_CHECK(!view || (nin >= 4 && in[3]), -2, "pool: a strided gradient needs its backing buffer");
+        VR_CHECK(view_fits(off, gN, gC, gH, N, C, H, W, gfloats), -2, "pool: the gradient view leaves its buffer");
+        const std::vector<float> zeros(view ? 0 : n, 0.f);
+        DevBuf x(in[0], n), gp(in[1], m), d(in[2], n), pooled(m), sumh(m);
+        GuardedBuf g(view ? in[3] : zeros.data(), gfloats);
         launch_avgpool_h(dense(x.p, N, C, H, W), pooled.p, st);
-        launch_avgpool_bwd(gp.p, g.p, N, C, H, W, (long long)C * H * W, (long long)H * W, W, 1, st);
+        launch_avgpool_bwd(gp.p, g.p() + off, N, C, H, W, gN, gC, gH, view ? (dims[9] != 0 ? 1 : 0) : 1, st);
         launch_sum_h(d.p, N, C, H, W, sumh.p, st);
         VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(g.intact(), -3, "pool: a store outside the gradient's buffer");
         pooled.download(out[0]); g.download(out[1]); sumh.download(out[2]);
     } else if (name == "thin") {
         need(5, 1, 4, 3);

@@ -190,6 +190,7 @@ public:
     void debug_wgrad_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                             int nout);                    // "wgrad_launch": one launch_wgrad in its general form
     void debug_wgrad_reduce(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "wgrad_reduce"
+    void debug_dgrad_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "dgrad_launch"
     // ---- signal path ----
     void stft_api(const float* wave, bool on_dev, long long L, float* spec, bool spec_on_dev);
     void istft_api(const float* spec, bool on_dev, int T, float* wave, bool wave_on_dev);
@@ -410,6 +411,24 @@ private:
     void ensure_train_state();
     void backward();
     void bwd_conv(TapeRec& r);
+    // which launches the data gradient of a conv record took (bwd_conv_dgrad's return value)
+    enum DgradPath { DG_NONE = 0, DG_STRIDE1 = 1, DG_S2_FUSED = 2, DG_S2_CLASSES = 3, DG_S2_ZINS = 4 };
+    int bwd_conv_dgrad(TapeRec& r, const ConvArgs& f);   // step 4 of bwd_conv; f = the record's forward launch (build_fwd_args)
+    // The device forms of ONE layer's weights that its data gradient multiplies with, made from the K-major copy P.dev
+    // [Cin][KS*KS][CoutPad]: flipped / transposed, their Winograd, x3 / x3h and x3d forms in the handle's mfma_mode, the four parity-class
+    // arrays of a stride-2 3x3 -- registered under &P in wt_of / winot_of / x3t_of / x3dt_of / s2w_of as a train step registers a layer's.
+    // Shared by debug_conv_bwd and the dgrad_launch hook of debug.hip.  The object unregisters and frees them, also when a launch throws.
+    struct DebugDgradForms {
+        Model* m = nullptr;
+        const Param* P = nullptr;
+        float *wt = nullptr, *winot = nullptr, *s2w = nullptr;
+        void *x3t = nullptr, *flip_desc = nullptr, *s2_desc = nullptr;
+        DebugDgradForms() = default;
+        ~DebugDgradForms();
+        DebugDgradForms(const DebugDgradForms&) = delete;
+        DebugDgradForms& operator=(const DebugDgradForms&) = delete;
+    };
+    void debug_dgrad_weight_forms(const Param& P, int KS, int stride, int dh, int dw, DebugDgradForms& f);
     void bwd_bn_of(const Tensor& out, Conv& L);
     std::vector<float> dropout_host;                     // injected keep-masks [5][N][8*nout] or empty
     int dropout_mode = 1;                                // 0 off, 1 native RNG (default: nn.Dropout2d is active in train mode), 2 injected

@@ -197,9 +197,18 @@ void Model::bwd_conv(TapeRec& r) {
         }
     }
     // 4. data gradient, split back to the sources of the virtual concat
+    bwd_conv_dgrad(r, f);
+}
+
+// Step 4 of bwd_conv: the data gradient of one conv record, split back to the sources of the virtual concat (f: the record's forward
+// launch, build_fwd_args).  Returns the path it took (DgradPath; DG_NONE in a dry pass or when no source wants a gradient).
+int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
+    Conv& L = *r.L;
+    const Tensor& out = r.out;
+    const int N = r.N;
     bool any = false;
     for (auto& sp : r.srcs) any = any || sp.t.g != nullptr;
-    if (!any) return;
+    if (!any) return DG_NONE;
     ConvArgs d{};
     Tensor dzt = out;                       // dz as a plain source
     dzt.p = out.g; dzt.aff0 = dzt.aff1 = nullptr; dzt.slope = 1.f; dzt.post = nullptr; dzt.hsplit = 1 << 30;
@@ -253,7 +262,7 @@ void Model::bwd_conv(TapeRec& r) {
     }
     if (r.srcs.size() == 1) d.d1 = d.d2 = 1 << 30;
     if (r.srcs.size() == 2) d.d2 = 1 << 30;
-    if (dry) return;
+    if (dry) return DG_NONE;
     // Stride-2 3x3: four parity-class stride-1 convs over dz (9 tap evaluations) instead of one conv over the
     // zero-inserted gradient (36), when the LDS-DMA kernel covers the shape.
     {
@@ -277,13 +286,18 @@ void Model::bwd_conv(TapeRec& r) {
                     record_note(conv_alg_bytes(L, f, N, false), ("dgrad " + L.name).c_str());
                     launch_s2d_fused(k, stream);
                     record_end();
-                    return;
+                    return DG_S2_FUSED;
                 }
             }
+            // Eligibility is decided for ALL four classes before the first launch: with an odd width the pw = 1 classes are one column
+            // narrower than class 0 and may fall below the tap-masked kernel's 32 columns -- then nothing has been written yet and the
+            // zero-insertion launch below computes the whole gradient.
             const int masks[2] = {1 << 1, (1 << 1) | (1 << 2)};          // live taps along one axis: parity 0 / 1
+            ConvArgs cls_args[4];
             for (int cls = 0; cls < 4 && ok; ++cls) {
                 const int ph = cls >> 1, pw = cls & 1;
-                ConvArgs k = c;
+                ConvArgs& k = cls_args[cls];
+                k = c;
                 k.Hout = (f.Hin - ph + 1) / 2; k.Wout = (f.Win - pw + 1) / 2;
                 k.w = it->second + cls * cls_stride;
                 k.wino = nullptr; k.wino6 = nullptr; k.x3w = nullptr;
@@ -298,14 +312,15 @@ void Model::bwd_conv(TapeRec& r) {
                     k.dst[i].sH *= 2;
                     k.dst[i].wshift = 1;
                 }
-                if (cls == 0 && !conv_dma_eligible(k, cshp)) { ok = false; break; }
-                if (cls == 0) {
-                    record_begin(0, 2.0 * N * (double)f.Hout * f.Wout * (double)L.Cout * L.Cin * L.KS * L.KS);
-                    record_note(conv_alg_bytes(L, f, N, false), ("dgrad " + L.name).c_str());
-                }
-                launch_conv(k, cshp, stream);
+                if (k.Hout < 1 || k.Wout < 1 || !conv_dma_eligible(k, cshp)) ok = false;
             }
-            if (ok) { record_end(); return; }
+            if (ok) {
+                record_begin(0, 2.0 * N * (double)f.Hout * f.Wout * (double)L.Cout * L.Cin * L.KS * L.KS);
+                record_note(conv_alg_bytes(L, f, N, false), ("dgrad " + L.name).c_str());
+                for (int cls = 0; cls < 4; ++cls) launch_conv(cls_args[cls], cshp, stream);
+                record_end();
+                return DG_S2_CLASSES;
+            }
         }
     }
     const ConvShape dshp{L.KS, 1, L.dh, L.dw};
@@ -318,6 +333,7 @@ void Model::bwd_conv(TapeRec& r) {
         if (p.kind == 1) launch_upsample_bwd(p.tmp, N, t.C, t.H, t.W, t.g, t.sN, t.sC, t.sH, g_first(t.g) ? 0 : 1, stream);
         else launch_sum_h(p.tmp, N, t.C, f.Hin, f.Win, t.g, stream);
     }
+    return L.stride == 2 ? DG_S2_ZINS : DG_STRIDE1;
 }
 
 void Model::backward() {
@@ -877,12 +893,61 @@ void Model::get_grad(const std::string& key, float* host, int64_t cap_bytes) {
 // =====================================================================================================
 namespace vr {
 
+Model::DebugDgradForms::~DebugDgradForms() {
+    if (m && P) {
+        m->wt_of.erase(P); m->s2w_of.erase(P); m->winot_of.erase(P); m->x3t_of.erase(P); m->x3dt_of.erase(P);
+    }
+    (void)hipFree(wt); (void)hipFree(winot); (void)hipFree(s2w); (void)hipFree(x3t); (void)hipFree(flip_desc); (void)hipFree(s2_desc);
+}
+
+void Model::debug_dgrad_weight_forms(const Param& P, int KS, int stride, int dh, int dw, DebugDgradForms& f) {
+    const int Cin = P.Cin, Cout = P.Cout, KK = KS * KS, CoutPad = P.CoutPad, CinPad = round_up32(Cin);
+    f.m = this; f.P = &P;
+    VR_HIP(hipMalloc(&f.wt, (size_t)Cout * KK * CinPad * 4));
+    VR_HIP(hipMemset(f.wt, 0, (size_t)Cout * KK * CinPad * 4));
+    VR_HIP(hipStreamSynchronize(nullptr));                    // (the fill runs on the NULL stream, the transforms below on the handle's)
+    wt_of[&P] = f.wt;
+    const FlipDesc fd{P.dev, f.wt, Cin, Cout, KK, CinPad, CoutPad};
+    VR_HIP(hipMalloc(&f.flip_desc, sizeof(FlipDesc)));
+    VR_HIP(hipMemcpy(f.flip_desc, &fd, sizeof(FlipDesc), hipMemcpyHostToDevice));
+    launch_flip_transpose(static_cast<const FlipDesc*>(f.flip_desc), 1, stream);
+    // 3x3 stride-1: the data gradient takes the same kernels as in a train step (Winograd / split-bf16 direct over the flipped weights)
+    if (KS == 3 && stride == 1 && dh == 1 && dw == 1 && train_wino) {
+        VR_HIP(hipMalloc(&f.winot, (size_t)Cout * 16 * CinPad * sizeof(float)));
+        launch_wino_weights(f.wt, f.winot, Cout, CinPad, stream);
+        winot_of[&P] = f.winot;
+        if (mfma_mode == 2) {
+            VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, 9, CinPad)));
+            launch_x3_weights(f.wt, f.x3t, Cout, 9, CinPad, stream);
+            x3t_of[&P] = f.x3t;
+        }
+        if (mfma_mode == 3) {
+            VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, 9, CinPad)));
+            launch_x3h_weights(f.wt, f.x3t, Cout, 9, CinPad, stream);
+            x3t_of[&P] = f.x3t;
+        }
+    }
+    if (stride == 1 && (KS == 1 || dh > 1) && train_wino && mfma_mode == 3) {      // conv_x3d.hip's layers (16-column images)
+        VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, KK, CinPad)));
+        launch_x3h_weights(f.wt, f.x3t, Cout, KK, CinPad, stream);
+        x3dt_of[&P] = f.x3t;
+    }
+    if (KS == 3 && stride == 2 && dh == 1 && dw == 1) {       // stride-2 3x3: also exercise the parity-class data gradient
+        VR_HIP(hipMalloc(&f.s2w, (size_t)4 * Cout * 9 * CinPad * sizeof(float)));
+        const S2WDesc sd{P.dev, f.s2w, Cin, Cout, CoutPad, CinPad};
+        VR_HIP(hipMalloc(&f.s2_desc, sizeof(S2WDesc)));
+        VR_HIP(hipMemcpy(f.s2_desc, &sd, sizeof(S2WDesc), hipMemcpyHostToDevice));
+        launch_s2_class_weights(static_cast<const S2WDesc*>(f.s2_desc), 1, 4LL * Cout * 9 * CinPad, stream);
+        s2w_of[&P] = f.s2w;
+    }
+}
+
 void Model::debug_conv_bwd(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,
                            int dh, int dw, int up, const float* aff, float slope, const float* dz, float* dx_out,
                            float* dw_out) {
     DeviceGuard dev_guard(device);
     ensure_train_state();
-    const int KK = KS * KS, CoutPad = (Cout + 31) / 32 * 32, CinPad = round_up32(Cin);
+    const int KK = KS * KS, CoutPad = (Cout + 31) / 32 * 32;
     Conv L;
     L.name = "debug"; L.Cin = Cin; L.Cout = Cout; L.CoutPad = CoutPad; L.KS = KS; L.stride = stride; L.dh = dh; L.dw = dw;
     L.pad_h = KS == 1 ? 0 : dh; L.pad_w = KS == 1 ? 0 : dw; L.bn = nullptr; L.slope = 1.f;
@@ -896,54 +961,17 @@ void Model::debug_conv_bwd(const float* x, int N, int Cin, int H, int W, const f
         for (int ci = 0; ci < Cin; ++ci)
             for (int k = 0; k < KK; ++k) wk[((size_t)ci * KK + k) * CoutPad + co] = w_oihw[((size_t)co * Cin + ci) * KK + k];
     const size_t xin = (size_t)N * Cin * H * W, xout = (size_t)N * Cout * Hout * Wout;
-    float *dx, *dgx, *dwk, *dwt, *dgw, *dzd, *daff = nullptr;
+    float *dx, *dgx, *dwk, *dgw, *dzd, *daff = nullptr;
     VR_HIP(hipMalloc(&dx, xin * 4)); VR_HIP(hipMalloc(&dgx, xin * 4)); VR_HIP(hipMalloc(&dwk, wk.size() * 4));
-    VR_HIP(hipMalloc(&dwt, (size_t)Cout * KK * CinPad * 4)); VR_HIP(hipMalloc(&dgw, wk.size() * 4)); VR_HIP(hipMalloc(&dzd, xout * 4));
+    VR_HIP(hipMalloc(&dgw, wk.size() * 4)); VR_HIP(hipMalloc(&dzd, xout * 4));
     VR_HIP(hipMemcpy(dx, x, xin * 4, hipMemcpyHostToDevice));
-    VR_HIP(hipMemset(dgx, 0, xin * 4)); VR_HIP(hipMemset(dgw, 0, wk.size() * 4)); VR_HIP(hipMemset(dwt, 0, (size_t)Cout * KK * CinPad * 4));
+    VR_HIP(hipMemset(dgx, 0, xin * 4)); VR_HIP(hipMemset(dgw, 0, wk.size() * 4));
     VR_HIP(hipMemcpy(dwk, wk.data(), wk.size() * 4, hipMemcpyHostToDevice));
     VR_HIP(hipMemcpy(dzd, dz, xout * 4, hipMemcpyHostToDevice));
     if (aff) { VR_HIP(hipMalloc(&daff, (size_t)Cin * 8)); VR_HIP(hipMemcpy(daff, aff, (size_t)Cin * 8, hipMemcpyHostToDevice)); }
     P.dev = dwk; P.grad_override = dgw;
-    wt_of[&P] = dwt;
-    FlipDesc fd{dwk, dwt, Cin, Cout, KK, CinPad, CoutPad};
-    FlipDesc* dfd;
-    VR_HIP(hipMalloc(&dfd, sizeof(FlipDesc)));
-    VR_HIP(hipMemcpy(dfd, &fd, sizeof(FlipDesc), hipMemcpyHostToDevice));
-    launch_flip_transpose(dfd, 1, stream);
-    // 3x3 stride-1: the data gradient takes the same kernels as in a train step (Winograd / split-bf16 direct over the flipped weights)
-    float* dwinot = nullptr;
-    void* dx3t = nullptr;
-    if (KS == 3 && stride == 1 && dh == 1 && dw == 1 && train_wino) {
-        VR_HIP(hipMalloc(&dwinot, (size_t)Cout * 16 * CinPad * sizeof(float)));
-        launch_wino_weights(dwt, dwinot, Cout, CinPad, stream);
-        winot_of[&P] = dwinot;
-        if (mfma_mode == 2) {
-            VR_HIP(hipMalloc(&dx3t, x3_weights_bytes(Cout, 9, CinPad)));
-            launch_x3_weights(dwt, dx3t, Cout, 9, CinPad, stream);
-            x3t_of[&P] = dx3t;
-        }
-        if (mfma_mode == 3) {
-            VR_HIP(hipMalloc(&dx3t, x3_weights_bytes(Cout, 9, CinPad)));
-            launch_x3h_weights(dwt, dx3t, Cout, 9, CinPad, stream);
-            x3t_of[&P] = dx3t;
-        }
-    }
-    if (stride == 1 && (KS == 1 || dh > 1) && train_wino && mfma_mode == 3) {      // conv_x3d.hip's layers (16-column images)
-        VR_HIP(hipMalloc(&dx3t, x3_weights_bytes(Cout, KK, CinPad)));
-        launch_x3h_weights(dwt, dx3t, Cout, KK, CinPad, stream);
-        x3dt_of[&P] = dx3t;
-    }
-    float* ds2w = nullptr;                    // stride-2 3x3: also exercise the parity-class data gradient
-    S2WDesc* ds2d = nullptr;
-    if (KS == 3 && stride == 2 && dh == 1 && dw == 1) {
-        VR_HIP(hipMalloc(&ds2w, (size_t)4 * Cout * 9 * CinPad * sizeof(float)));
-        const S2WDesc sd{dwk, ds2w, Cin, Cout, CoutPad, CinPad};
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&ds2d), sizeof(S2WDesc)));
-        VR_HIP(hipMemcpy(ds2d, &sd, sizeof(S2WDesc), hipMemcpyHostToDevice));
-        launch_s2_class_weights(ds2d, 1, 4LL * Cout * 9 * CinPad, stream);
-        s2w_of[&P] = ds2w;
-    }
+    DebugDgradForms forms;
+    debug_dgrad_weight_forms(P, KS, stride, dh, dw, forms);
     Tensor t;
     t.p = dx; t.g = dgx; t.N = N; t.C = Cin; t.H = H; t.W = W; t.sH = W; t.sC = (long long)H * W; t.sN = t.sC * Cin;
     t.aff0 = daff; t.slope = slope;
@@ -972,13 +1000,7 @@ void Model::debug_conv_bwd(const float* x, int N, int Cin, int H, int W, const f
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci)
             for (int k = 0; k < KK; ++k) dw_out[((size_t)co * Cin + ci) * KK + k] = gk[((size_t)ci * KK + k) * CoutPad + co];
-    wt_of.erase(&P);
-    s2w_of.erase(&P);
-    winot_of.erase(&P);
-    x3t_of.erase(&P);
-    x3dt_of.erase(&P);
-    hipFree(ds2w); hipFree(ds2d); hipFree(dwinot); hipFree(dx3t);
-    hipFree(dx); hipFree(dgx); hipFree(dwk); hipFree(dwt); hipFree(dgw); hipFree(dzd); hipFree(daff); hipFree(dfd);
+    hipFree(dx); hipFree(dgx); hipFree(dwk); hipFree(dgw); hipFree(dzd); hipFree(daff);
 }
 
 }  // namespace vr
