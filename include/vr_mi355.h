@@ -46,14 +46,23 @@ const char* vr_last_error(void);
 int vr_create(int device, int n_fft, int hop_length, int nout, int nout_lstm, vr_handle* out);
 /* The same with flags.  VR_CREATE_COMPLEX: nets.CascadedNet(..., is_complex=True) -- nin = 4 input channels
  * [re L, re R, im L, im R], so the first layers and out / aux_out take their nin = 4 shapes (vr_param_info), and a
- * complex mask bounded by tanh(|m|) (lib/nets.py:104-107,119-122).  Such a handle runs eval-mode inference only:
+ * complex mask bounded by tanh(|m|) (lib/nets.py:104-107,119-122).  By default such a handle runs eval-mode inference only
+ * (training it is opt-in per handle: vr_set_option "complex_train" below):
  *   vr_forward      x and out are complex64 (interleaved re, im): x [B,2,bins,T], out [B,2,bins,Wm] in every mode;
  *                   in training mode it returns VR_ERR_BAD_ARGUMENT
  *   vr_separate / vr_separate_wave   same signatures; the network sees the complex crops (X_pad / c, with c = max|X|,
  *                   or for tta numpy's lexicographic complex maximum as a complex divisor), TTA averages the complex masks,
  *                   --postprocess blends |mask| and keeps its phase, y = mask X and v = (1 - mask) X are complex products
  *   vr_train_step, vr_forward_train, vr_backward, vr_validate_step   VR_ERR_BAD_ARGUMENT (training is not supported)
- *   vr_set_mode(h, 1) is accepted (model.train()).                                                  */
+ *   vr_set_mode(h, 1) is accepted (model.train()).
+ * With vr_set_option(h, "complex_train", 1) the same entry points train it (train.py:77-96 on complex tensors).  X, y, mask_out and
+ * dmask are then complex64 [B,2,bins,T] (interleaved re, im), as vr_forward takes them:
+ *   vr_train_step      loss = mean |mask X - y| over the B*2*bins*T complex elements (torch's L1Loss on complex tensors); the
+ *                      gradient of |d| at d = 0 is 0, and so is that of the bound at a zero logit pair
+ *   vr_forward_train / vr_backward   dmask in torch's convention for a real loss: dL/dRe(mask) + i dL/dIm(mask)
+ *   vr_forward         in training mode: batch statistics and the running update, live Dropout2d, as on a magnitude handle
+ *   vr_validate_step   eval mode only: mean |crop(X mask) - crop_center(y)| as a complex difference
+ * Tested in the default "mfma_mode" with "train_winograd" 0 and 1; the other modes run.                  */
 #define VR_CREATE_COMPLEX 1
 int vr_create_ex(int device, int n_fft, int hop_length, int nout, int nout_lstm, int flags, vr_handle* out);
 int vr_destroy(vr_handle h);
@@ -98,7 +107,9 @@ int vr_set_mode(vr_handle h, int training);
  *   1 one launch per conv, 0 the fp32-pipe kernels.
  * "conv_x3s" ("mfma_mode" 3 only, eval): the encoders' 3x3 stride-2 convs (Encoder.conv1, lib/layers.py:33) with at least 32 output
  *   columns and more than 16 input channels on the fp16 matrix pipe: 1 (default, also -1; VR_CONV_X3S=0 makes 0 the default),
- *   0 the fp32-pipe kernel for them.   */
+ *   0 the fp32-pipe kernel for them.
+ * "complex_train" (default 0; VR_CREATE_COMPLEX handles only, VR_ERR_BAD_ARGUMENT on a magnitude handle): 1 = the training entry points
+ *   take this complex-mask handle (see vr_create_ex); 0 = they refuse it again.  Eval-mode calls are the same either way.   */
 int vr_set_option(vr_handle h, const char* name, int value);
 
 /* CascadedNet.forward (mode 0) / predict_mask (mode 1) / predict (mode 2)   lib/nets.py:82-141
@@ -294,6 +305,11 @@ typedef struct vr_aug { float coef; float coef_mix; float lam; int flags; } vr_a
 int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
                      const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
                      int out_on_device);
+/* The same for a complex-mask model's batches (lib/dataset.py:120, the commented `return X, y`): everything before the final np.abs,
+ * X_out, y_out [B][2][bins][T] complex64 (re,im interleaved) = the augmented crops themselves.  Any handle may call it. */
+int vr_augment_batch_complex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
+                             const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_out, float* y_out,
+                             int out_on_device);
 
 /* The training set resident in HBM: load every song's cached spectrogram pair once, then each batch is one vr_dataset_batch -- the
  * kernel of vr_augment_batch reading the crops where they lie, no file read and no host-to-device copy of spectrogram rows.
@@ -322,6 +338,9 @@ int vr_dataset_info(vr_dataset d, int* n_songs, int64_t* bytes);
 int vr_dataset_rows(vr_dataset d, int song, int64_t* rows);
 int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
                      float* X_mag, float* y_mag, int out_on_device);
+/* vr_dataset_batch with the outputs of vr_augment_batch_complex: X_out, y_out [B][2][bins][T] complex64; same checks, same errors. */
+int vr_dataset_batch_complex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                             float* X_out, float* y_out, int out_on_device);
 
 /* torch.optim.Adam(lr, betas=(b1,b2), eps, weight_decay=0).step()   train.py:215-218,95
  * grad_scale multiplies every gradient first (1/world_size after a SUM all-reduce).  Hyper-parameters are doubles
@@ -347,7 +366,7 @@ int vr_grad_arena(vr_handle h, float** device_ptr, int64_t* numel);
 
 /* One batch of train.validate_epoch (train.py:117-127), eval mode:
  *   y_pred = model.predict(X); y = spec_utils.crop_center(y, y_pred); loss = nn.L1Loss()(y_pred, y)
- * X, y: [B, 2, bins, T] fp32.  *loss_out = loss.item().  Forward, crop and the L1 reduction run on the device. */
+ * X, y: [B, 2, bins, T] fp32 (a VR_CREATE_COMPLEX handle with "complex_train" on: complex64, the loss on the complex difference).  *loss_out = loss.item().  Forward, crop and the L1 reduction run on the device. */
 int vr_validate_step(vr_handle h, const float* X, const float* y, int on_device, int B, int T, float* loss_out);
 
 /* ---- data-parallel exchange.  The reference has none: train.py:211-213 takes one --gpu. ----

@@ -400,9 +400,9 @@ int vr_param_arena(vr_handle h, float** device_ptr, int64_t* numel) {
     });
 }
 
-int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
-                     const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
-                     int out_on_device) {
+static int augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
+                         const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
+                         int out_on_device, bool out_complex) {
     NEED(h);
     return guard([&] {
         VR_CHECK(X && y && desc && X_mag && y_mag, VR_ERR_BAD_ARGUMENT, "null argument");
@@ -414,7 +414,7 @@ int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X
         VR_CHECK(!mix || (X_mix && y_mix), VR_ERR_BAD_ARGUMENT, "mixup flagged but no partner crops given");
         VR_CHECK(!red || reduction_weight, VR_ERR_BAD_ARGUMENT, "vocal reduction flagged but no reduction_weight given");
         h->m.augment_api(X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device != 0, X_mag, y_mag,
-                         out_on_device != 0);
+                         out_on_device != 0, out_complex);
     });
 }
 
@@ -473,10 +473,22 @@ int vr_dataset_rows(vr_dataset d, int song, int64_t* rows) {
     });
 }
 
+int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
+                     const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
+                     int out_on_device) {
+    return augment_batch(h, X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device, X_mag, y_mag, out_on_device, false);
+}
+
+int vr_augment_batch_complex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
+                             const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_out, float* y_out,
+                             int out_on_device) {
+    return augment_batch(h, X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device, X_out, y_out, out_on_device, true);
+}
+
 // The tables and the batch size are checked before the handle and the store, so that a caller's argument error is reported without a
 // device (as vr_separate_many does).
-int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
-                     float* X_mag, float* y_mag, int out_on_device) {
+static int dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                         float* X_mag, float* y_mag, int out_on_device, bool out_complex) {
     if (B <= 0) { g_err = "B must be positive"; return VR_ERR_BAD_ARGUMENT; }
     if (!crops || !desc || !X_mag || !y_mag) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
     NEED(h);
@@ -484,8 +496,18 @@ int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_a
     static_assert(sizeof(vr_crop) == sizeof(vr::ResidentCrop) && sizeof(vr_aug) == sizeof(vr::AugDesc), "C ABI structs and their kernels.h twins");
     return guard([&] {
         h->m.dataset_batch_api(d->set, reinterpret_cast<const vr::ResidentCrop*>(crops), desc, reduction_weight, B, T, X_mag, y_mag,
-                               out_on_device != 0);
+                               out_on_device != 0, out_complex);
     });
+}
+
+int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                     float* X_mag, float* y_mag, int out_on_device) {
+    return dataset_batch(h, d, crops, desc, reduction_weight, B, T, X_mag, y_mag, out_on_device, false);
+}
+
+int vr_dataset_batch_complex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
+                             float* X_out, float* y_out, int out_on_device) {
+    return dataset_batch(h, d, crops, desc, reduction_weight, B, T, X_out, y_out, out_on_device, true);
 }
 
 int vr_adam_step(vr_handle h, double lr, double b1, double b2, double eps, double grad_scale) {

@@ -5,6 +5,7 @@
 //   channel swap / inst-only                                (dataset.py:68-83)
 //   mixup with a second, independently augmented crop       (dataset.py:85-103)
 //   np.abs, and the [T,2,bins] -> [2,bins,T] transpose      (dataset.py:63-64,116-117)
+//   (or, for a complex-mask model, the complex values themselves: dataset.py:120, the commented `return X, y`)
 // -- as ONE HBM-bound kernel over a whole batch.  The host keeps what is inherently host work: drawing
 // the numpy random numbers in the reference's order and seek-reading cropsize rows of the cached .npy.
 #include <type_traits>
@@ -41,13 +42,17 @@ __device__ __forceinline__ void aug_element(const float2* __restrict__ X, const 
 // sample b at b * T * 2 * bins of each.  Resident (vr_dataset_batch): the first argument is a table with one AugCrops per sample,
 // every pointer already advanced to the sample's start row inside the [rows][2][bins] slab of its song (the mixup pair repeats the
 // first two when the sample has no partner); the other three pointer arguments are unused.
-template <bool kResident>
+// kComplex (training a complex-mask model): everything before the final np.abs is the same; the augmented x, y themselves are stored,
+// complex64 [B][2][bins][T].  The real and imaginary parts cross the transpose in tiles of their own (four float tiles of 33-word rows,
+// the bank-conflict-free layout of the magnitude form; a float2 tile would put a 64-bit read at a 66-word stride).
+template <bool kResident, bool kComplex>
 __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kResident, const AugCrops*, const float2*> __restrict__ X,
                                                       const float2* __restrict__ Y, const float2* __restrict__ Xi,
                                                       const float2* __restrict__ Yi, const AugDesc* __restrict__ desc,
                                                       const float* __restrict__ rw, int T, int bins, float* __restrict__ Xmag,
                                                       float* __restrict__ Ymag) {
-    __shared__ float tx[32][33], ty[32][33];
+    constexpr int NT = kComplex ? 2 : 1;
+    __shared__ float tx[NT][32][33], ty[NT][32][33];
     const int b = blockIdx.z >> 1, c = blockIdx.z & 1;
     const int t0 = blockIdx.x * 32, bin0 = blockIdx.y * 32;
     const AugDesc d = desc[b];
@@ -64,10 +69,9 @@ __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kReside
     const int bin = bin0 + threadIdx.x;
     for (int r = threadIdx.y; r < 32; r += 8) {
         const int t = t0 + r;
-        float xm = 0.f, ym = 0.f;
+        float2 x = make_float2(0.f, 0.f), y = make_float2(0.f, 0.f);
         if (t < T && bin < bins) {
             const float w = rw ? rw[bin] : 0.f;
-            float2 x, y;
             aug_element(Xc, Y, base, bins, t, c, bin, d.coef, d.flags & 1, d.flags & 2, d.flags & 4, w, x, y);
             if (d.flags & 8) {
                 float2 xi, yi;
@@ -76,11 +80,14 @@ __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kReside
                 x = make_float2(l * x.x + m * xi.x, l * x.y + m * xi.y);
                 y = make_float2(l * y.x + m * yi.x, l * y.y + m * yi.y);
             }
-            xm = hypotf(x.x, x.y);
-            ym = hypotf(y.x, y.y);
         }
-        tx[r][threadIdx.x] = xm;
-        ty[r][threadIdx.x] = ym;
+        if constexpr (kComplex) {
+            tx[0][r][threadIdx.x] = x.x; tx[1][r][threadIdx.x] = x.y;
+            ty[0][r][threadIdx.x] = y.x; ty[1][r][threadIdx.x] = y.y;
+        } else {
+            tx[0][r][threadIdx.x] = hypotf(x.x, x.y);
+            ty[0][r][threadIdx.x] = hypotf(y.x, y.y);
+        }
     }
     __syncthreads();
     const int t = t0 + threadIdx.x;
@@ -88,24 +95,31 @@ __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kReside
         const int bo = bin0 + r;
         if (t < T && bo < bins) {
             const long long o = (((long long)b * 2 + c) * bins + bo) * T + t;
-            Xmag[o] = tx[threadIdx.x][r];
-            Ymag[o] = ty[threadIdx.x][r];
+            if constexpr (kComplex) {
+                reinterpret_cast<float2*>(Xmag)[o] = make_float2(tx[0][threadIdx.x][r], tx[1][threadIdx.x][r]);
+                reinterpret_cast<float2*>(Ymag)[o] = make_float2(ty[0][threadIdx.x][r], ty[1][threadIdx.x][r]);
+            } else {
+                Xmag[o] = tx[0][threadIdx.x][r];
+                Ymag[o] = ty[0][threadIdx.x][r];
+            }
         }
     }
 }
 
 void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDesc* desc, const float* rw,
-                    int B, int T, int bins, float* Xmag, float* Ymag, hipStream_t st) {
+                    int B, int T, int bins, float* Xmag, float* Ymag, bool out_complex, hipStream_t st) {
     const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
-    VR_LAUNCH(augment_kernel<false>, grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    if (out_complex) VR_LAUNCH((augment_kernel<false, true>), grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    else VR_LAUNCH((augment_kernel<false, false>), grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
     VR_HIP(hipGetLastError());
 }
 
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
-                             float* Ymag, hipStream_t st) {
+                             float* Ymag, bool out_complex, hipStream_t st) {
     const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
     const float2* const unused = nullptr;
-    VR_LAUNCH(augment_kernel<true>, grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
+    if (out_complex) VR_LAUNCH((augment_kernel<true, true>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
+    else VR_LAUNCH((augment_kernel<true, false>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
     VR_HIP(hipGetLastError());
 }
 

@@ -548,7 +548,7 @@ void launch_avgpool_bwd(const float* gp, float* g, int N, int C, int H, int W, l
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Thin convs (Cout = CO in {1,2}) backward.
+// Thin convs (Cout = CO in {1,2,4}; 4: the complex-mask head) backward.
 //   dgrad: G_x[n][c][h][w] (+)= post-chain is the producer's job; here  sum_o W[o][c] * dz[n][o][h][w]
 //   wgrad: dW[o][c] = sum_{n,h,w} dz[n][o][h][w] * act(x)[n][c][h][w]   (8 channels per blockIdx.y)
 // dz is dense [N][CO][H][W].
@@ -686,6 +686,7 @@ void launch_reduce_rows(const float* part, long long stride, int P, float* out, 
 }
 
 void launch_thin_dgrad(const Tensor& x, int CO, const float* w, const float* dz, float* g, int accumulate, hipStream_t st) {
+    VR_CHECK(CO == 1 || CO == 2 || CO == 4, -2, "thin conv data gradient: 1, 2 or 4 outputs");
     const long long total = (long long)x.N * x.C * x.H * x.W;
     // reads x (activation derivative), dz; writes (accumulating: read-modify-writes) g
     prof_note(2.0 * CO * (double)total, 4.0 * ((accumulate ? 3.0 : 2.0) * (double)total + (double)CO * x.N * x.H * x.W));
@@ -695,7 +696,8 @@ void launch_thin_dgrad(const Tensor& x, int CO, const float* w, const float* dz,
     if (vec) {
         const dim3 g4((unsigned)(((long long)x.N * x.H * (x.W >> 2) + 255) / 256), (unsigned)((x.C + 7) / 8));
         if (CO == 1) VR_LAUNCH((thin_dgrad4_kernel<1>), g4, dim3(256), 0, st, x, w, dz, g, accumulate);
-        else VR_LAUNCH((thin_dgrad4_kernel<2>), g4, dim3(256), 0, st, x, w, dz, g, accumulate);
+        else if (CO == 2) VR_LAUNCH((thin_dgrad4_kernel<2>), g4, dim3(256), 0, st, x, w, dz, g, accumulate);
+        else VR_LAUNCH((thin_dgrad4_kernel<4>), g4, dim3(256), 0, st, x, w, dz, g, accumulate);     // the complex-mask head
     } else {
         // (round 6: the scalar per-element form is gone -- frames % 16 == 0 (lib/nets.py:129 / spec_utils.crop_center) makes every width
         // the model can produce a multiple of 4, and nothing ever reached it)
@@ -712,6 +714,7 @@ int thin_wgrad_blocks(const Tensor& x) {
     return (int)b;
 }
 void launch_thin_wgrad(const Tensor& x, int CO, const float* dz, float* part, float* dw, int accumulate, hipStream_t st) {
+    VR_CHECK(CO == 1 || CO == 2 || CO == 4, -2, "thin conv weight gradient: 1, 2 or 4 outputs");
     const int nb = thin_wgrad_blocks(x);
     const dim3 grid(nb, (x.C + 7) / 8);
     prof_note(2.0 * CO * (double)x.N * x.C * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + (double)CO * x.N * x.H * x.W));
@@ -720,7 +723,8 @@ void launch_thin_wgrad(const Tensor& x, int CO, const float* dz, float* part, fl
                      (long long)x.N * x.H * x.W < 0x7FFFFFFFLL;
     if (vec) {
         if (CO == 1) VR_LAUNCH((thin_wgrad4_kernel<1>), grid, dim3(256), 0, st, x, dz, part);
-        else VR_LAUNCH((thin_wgrad4_kernel<2>), grid, dim3(256), 0, st, x, dz, part);
+        else if (CO == 2) VR_LAUNCH((thin_wgrad4_kernel<2>), grid, dim3(256), 0, st, x, dz, part);
+        else VR_LAUNCH((thin_wgrad4_kernel<4>), grid, dim3(256), 0, st, x, dz, part);               // the complex-mask head
     } else {
         throw Error(-2, "thin conv weight gradient: widths and strides must be multiples of 4 floats");
     }
@@ -733,6 +737,41 @@ void launch_thin_wgrad(const Tensor& x, int CO, const float* dz, float* part, fl
 // Writes dlogit [N][2][H][W] = dLoss/d(pre-sigmoid) * gscale and per-block |.| sums.
 // X, y: [N][2][bins][T] dense; bins = H + pad_rows.
 // ---------------------------------------------------------------------------------------------------
+// The bound of the complex-mask head (lib/nets.py:119-122), m = f(r) z with r = |z| and f = tanh(r) / (r + eps), and what its
+// backward needs: for an upstream gradient g (torch's convention for a real loss, dL/dRe + i dL/dIm)
+//     dz = f g + f'(r) (Re(conj(z) g) / r) z = f g + (f'(r) r) Re(conj(u) g) u,   u = z / r.
+// f'(r) = (sech^2(r) (r + eps) - tanh(r)) / (r + eps)^2 cancels for small r: r sech^2 r - tanh r = -(sinh 2r - 2r) / (2 cosh^2 r), and
+// sinh x - x comes from its series for r < 0.5, so f'(r) = sech^2(r) (eps - (sinh 2r - 2r) / 2) / (r + eps)^2 has no cancellation left
+// but the one between eps and r^3, which is the function's own.  r = 0: f = 0 and the second term is 0 (u is set to 0), dz = 0 exactly.
+struct CplxBound { float f, fpr, ux, uy; };           // f, f'(r) * r, u
+__device__ __forceinline__ CplxBound cplx_bound(float re, float im) {
+    const float eps = 1e-8f;
+    const float r = hypotf(re, im);                    // torch.abs of a complex tensor
+    const float th = tanhf(r), den = r + eps;
+    CplxBound b;
+    b.f = th / den;
+    if (!(r > 0.f)) { b.fpr = 0.f; b.ux = 0.f; b.uy = 0.f; return b; }
+    if (r < 0.5f) {
+        const float x = 2.f * r, x2 = x * x;
+        // sinh x - x = x^3/6 (1 + x^2/20 (1 + x^2/42 (1 + x^2/72 (1 + x^2/110))))  (the next term is below 1e-9 of the sum for x < 1)
+        const float S = x * x2 * (1.f / 6.f) * fmaf(x2 * (1.f / 20.f), fmaf(x2 * (1.f / 42.f), fmaf(x2 * (1.f / 72.f), fmaf(x2, 1.f / 110.f, 1.f), 1.f), 1.f), 1.f);
+        const float ch = coshf(r);
+        b.fpr = (eps - 0.5f * S) / (ch * ch) / den * (r / den);
+    } else {                                           // no cancellation worth the name: the numerator runs from -0.07 to -1
+        b.fpr = (fmaf(-th, th, 1.f) * den - th) / den * (r / den);
+    }
+    b.ux = re / r; b.uy = im / r;
+    return b;
+}
+__device__ __forceinline__ float2 cplx_bound_bwd(const CplxBound& b, float2 g) {
+    const float t = b.fpr * (b.ux * g.x + b.uy * g.y);
+    return make_float2(fmaf(b.f, g.x, t * b.ux), fmaf(b.f, g.y, t * b.uy));
+}
+
+// CPLX (the complex-mask head): w [4][C], logits (a0, a1, b0, b1), z_o = a_o + i b_o, m = the bound above;
+// X, Y, mask_out are complex64 [N][2][bins][W]; loss = sum |m X - y| over complex elements (torch's L1Loss on complex tensors);
+// dL/dm = sgn(m X - y) conj(X), sgn(0) = 0, summed over the rows that share the logit, then through the bound; dlogit [N][4][H][W].
+template <bool CPLX>
 __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* __restrict__ w, const float* __restrict__ X,
                                                         const float* __restrict__ Y, int bins, float gscale,
                                                         float* __restrict__ dlogit, float* __restrict__ mask_out,
@@ -745,31 +784,68 @@ __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* _
         const long long t = gid / x.W;
         const int h = (int)(t % x.H);
         const int n = (int)(t / x.H);
-        float a0 = 0.f, a1 = 0.f;
         const float* aff = (h < x.hsplit) ? x.aff0 : x.aff1;
-        for (int c = 0; c < x.C; ++c) {
-            float sc = 1.f, sh = 0.f;
-            if (aff) { sc = aff[2 * c]; sh = aff[2 * c + 1]; }
-            float v = fmaf(x.p[(long long)n * x.sN + (long long)c * x.sC + (long long)h * x.sH + wq], sc, sh);
-            v = v > 0.f ? v : v * x.slope;
-            a0 = fmaf(w[c], v, a0);
-            a1 = fmaf(w[x.C + c], v, a1);
-        }
-        const float lg[2] = {a0, a1};
+        const int reps = (h == x.H - 1) ? bins - x.H + 1 : 1;      // replicate-pad rows share the last logit
+        if constexpr (CPLX) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < x.C; ++c) {
+                float sc = 1.f, sh = 0.f;
+                if (aff) { sc = aff[2 * c]; sh = aff[2 * c + 1]; }
+                float v = fmaf(x.p[(long long)n * x.sN + (long long)c * x.sC + (long long)h * x.sH + wq], sc, sh);
+                v = v > 0.f ? v : v * x.slope;
 #pragma unroll
-        for (int o = 0; o < 2; ++o) {
-            const float m = 1.f / (1.f + expf(-lg[o]));
-            float dm = 0.f;
-            const int reps = (h == x.H - 1) ? bins - x.H + 1 : 1;      // replicate-pad rows share the last logit
-            for (int e = 0; e < reps; ++e) {
-                const long long off = (((long long)n * 2 + o) * bins + h + e) * x.W + wq;
-                const float xv = X[off];
-                const float diff = m * xv - Y[off];
-                lsum += fabsf(diff);
-                dm += (diff > 0.f ? xv : (diff < 0.f ? -xv : 0.f));
-                if (mask_out) mask_out[off] = m;
+                for (int o = 0; o < 4; ++o) a[o] = fmaf(w[o * x.C + c], v, a[o]);
             }
-            dlogit[(((long long)n * 2 + o) * x.H + h) * x.W + wq] = dm * gscale * m * (1.f - m);
+            const float2* Xc = reinterpret_cast<const float2*>(X);
+            const float2* Yc = reinterpret_cast<const float2*>(Y);
+            float2* Mc = reinterpret_cast<float2*>(mask_out);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                const CplxBound b = cplx_bound(a[o], a[o + 2]);
+                const float2 m = make_float2(b.f * a[o], b.f * a[o + 2]);
+                float2 g = make_float2(0.f, 0.f);
+                for (int e = 0; e < reps; ++e) {
+                    const long long off = (((long long)n * 2 + o) * bins + h + e) * x.W + wq;
+                    const float2 xv = Xc[off], yv = Yc[off];
+                    const float dr = m.x * xv.x - m.y * xv.y - yv.x, di = m.x * xv.y + m.y * xv.x - yv.y;
+                    const float ad = hypotf(dr, di);
+                    lsum += ad;
+                    if (ad > 0.f) {                                  // sgn(d) conj(X)
+                        const float sr = dr / ad, si = di / ad;
+                        g.x += sr * xv.x + si * xv.y;
+                        g.y += si * xv.x - sr * xv.y;
+                    }
+                    if (mask_out) Mc[off] = m;
+                }
+                const float2 dz = cplx_bound_bwd(b, g);
+                dlogit[(((long long)n * 4 + o) * x.H + h) * x.W + wq] = dz.x * gscale;
+                dlogit[(((long long)n * 4 + o + 2) * x.H + h) * x.W + wq] = dz.y * gscale;
+            }
+        } else {
+            float a0 = 0.f, a1 = 0.f;
+            for (int c = 0; c < x.C; ++c) {
+                float sc = 1.f, sh = 0.f;
+                if (aff) { sc = aff[2 * c]; sh = aff[2 * c + 1]; }
+                float v = fmaf(x.p[(long long)n * x.sN + (long long)c * x.sC + (long long)h * x.sH + wq], sc, sh);
+                v = v > 0.f ? v : v * x.slope;
+                a0 = fmaf(w[c], v, a0);
+                a1 = fmaf(w[x.C + c], v, a1);
+            }
+            const float lg[2] = {a0, a1};
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                const float m = 1.f / (1.f + expf(-lg[o]));
+                float dm = 0.f;
+                for (int e = 0; e < reps; ++e) {
+                    const long long off = (((long long)n * 2 + o) * bins + h + e) * x.W + wq;
+                    const float xv = X[off];
+                    const float diff = m * xv - Y[off];
+                    lsum += fabsf(diff);
+                    dm += (diff > 0.f ? xv : (diff < 0.f ? -xv : 0.f));
+                    if (mask_out) mask_out[off] = m;
+                }
+                dlogit[(((long long)n * 2 + o) * x.H + h) * x.W + wq] = dm * gscale * m * (1.f - m);
+            }
         }
     }
     __shared__ float red[4];
@@ -783,25 +859,72 @@ __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* _
 // Backward of the mask head alone (the autograd split of train.py:81,92): dmask [N][2][bins][W] = dLoss/d(mask), mask
 // [N][2][bins][W] = the forward's sigmoid output  ->  dlogit [N][2][H][W] = m (1 - m) * (sum over the replicate-padded
 // rows that share the logit of row H-1).
-__global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dmask, const float* __restrict__ mask, int N,
-                                                       int H, int W, int bins, float* __restrict__ dlogit) {
-    const long long total = (long long)N * 2 * H * W;
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= total) return;
-    const int w = (int)(gid % W);
-    long long t = gid / W;
-    const int h = (int)(t % H);
-    const long long no = t / H;                  // n * 2 + o
-    const long long off = (no * bins + h) * W + w;
-    const float m = mask[off];
-    float d = dmask[off];
-    if (h == H - 1)
-        for (int e = 1; e <= bins - H; ++e) d += dmask[off + (long long)e * W];
-    dlogit[gid] = d * m * (1.f - m);
+// CPLX (the complex-mask head): dmask complex64 [N][2][bins][W] in torch's convention for a real loss (dL/dRe + i dL/dIm), summed over
+// the rows that share row H-1's logits, then through the bound's Jacobian (cplx_bound_bwd) -> dlogit [N][4][H][W].  The logits are
+// formed again from the feature map x the graph keeps (C multiply-adds per output) instead of inverting |m| -> r from the stored mask,
+// which loses everything as |m| nears 1; `mask` is not read.  The magnitude form reads neither x nor w.
+template <bool CPLX>
+__global__ __launch_bounds__(256) void head_bwd_kernel(Tensor x, const float* __restrict__ w, const float* __restrict__ dmask,
+                                                       const float* __restrict__ mask, int N, int H, int W, int bins,
+                                                       float* __restrict__ dlogit) {
+    if constexpr (CPLX) {
+        const long long total = (long long)N * H * W;
+        const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (gid >= total) return;
+        const int wq = (int)(gid % W);
+        const long long t = gid / W;
+        const int h = (int)(t % H);
+        const int n = (int)(t / H);
+        const float* aff = (h < x.hsplit) ? x.aff0 : x.aff1;
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < x.C; ++c) {
+            float sc = 1.f, sh = 0.f;
+            if (aff) { sc = aff[2 * c]; sh = aff[2 * c + 1]; }
+            float v = fmaf(x.p[(long long)n * x.sN + (long long)c * x.sC + (long long)h * x.sH + wq], sc, sh);
+            v = v > 0.f ? v : v * x.slope;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) a[o] = fmaf(w[o * x.C + c], v, a[o]);
+        }
+        const float2* dm = reinterpret_cast<const float2*>(dmask);
+        const int reps = (h == H - 1) ? bins - H + 1 : 1;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const CplxBound b = cplx_bound(a[o], a[o + 2]);
+            float2 g = make_float2(0.f, 0.f);
+            for (int e = 0; e < reps; ++e) {
+                const float2 d = dm[(((long long)n * 2 + o) * bins + h + e) * W + wq];
+                g.x += d.x; g.y += d.y;
+            }
+            const float2 dz = cplx_bound_bwd(b, g);
+            dlogit[(((long long)n * 4 + o) * H + h) * W + wq] = dz.x;
+            dlogit[(((long long)n * 4 + o + 2) * H + h) * W + wq] = dz.y;
+        }
+    } else {
+        const long long total = (long long)N * 2 * H * W;
+        const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (gid >= total) return;
+        const int w = (int)(gid % W);
+        long long t = gid / W;
+        const int h = (int)(t % H);
+        const long long no = t / H;                  // n * 2 + o
+        const long long off = (no * bins + h) * W + w;
+        const float m = mask[off];
+        float d = dmask[off];
+        if (h == H - 1)
+            for (int e = 1; e <= bins - H; ++e) d += dmask[off + (long long)e * W];
+        dlogit[gid] = d * m * (1.f - m);
+    }
 }
 void launch_head_bwd(const float* dmask, const float* mask, int N, int H, int W, int bins, float* dlogit, hipStream_t st) {
     const long long total = (long long)N * 2 * H * W;
-    VR_LAUNCH(head_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dmask, mask, N, H, W, bins, dlogit);
+    VR_LAUNCH((head_bwd_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, Tensor{}, nullptr, dmask, mask, N, H, W, bins,
+              dlogit);
+    VR_HIP(hipGetLastError());
+}
+void launch_head_bwd_complex(const Tensor& x, const float* w, const float* dmask, int bins, float* dlogit, hipStream_t st) {
+    const long long total = (long long)x.N * x.H * x.W;
+    VR_LAUNCH((head_bwd_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, dmask, nullptr, x.N, x.H, x.W, bins,
+              dlogit);
     VR_HIP(hipGetLastError());
 }
 
@@ -812,7 +935,17 @@ void launch_head_loss(const Tensor& x, const float* w, const float* X, const flo
     const int nb = head_loss_blocks(x);
     // reads the C-channel feature map, X, Y; writes the 2-channel logit gradient (+ the mask when asked)
     prof_note(4.0 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + (mask_out ? 8.0 : 6.0) * x.N * x.H * x.W));
-    VR_LAUNCH(head_loss_kernel, dim3(nb), dim3(256), 0, st, x, w, X, Y, bins, gscale, dlogit, mask_out, loss_part);
+    VR_LAUNCH((head_loss_kernel<false>), dim3(nb), dim3(256), 0, st, x, w, X, Y, bins, gscale, dlogit, mask_out, loss_part);
+    VR_HIP(hipGetLastError());
+    launch_reduce_rows(loss_part, 1, nb, loss_out, 1, 0, loss_scale, st);
+}
+
+void launch_head_loss_complex(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float gscale,
+                              float* dlogit, float* mask_out, float* loss_part, float* loss_out, float loss_scale, hipStream_t st) {
+    const int nb = head_loss_blocks(x);
+    // reads the C-channel feature map and complex X, Y; writes the 4-channel logit gradient (+ the complex mask when asked)
+    prof_note(8.0 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + (mask_out ? 16.0 : 12.0) * x.N * x.H * x.W));
+    VR_LAUNCH((head_loss_kernel<true>), dim3(nb), dim3(256), 0, st, x, w, X, Y, bins, gscale, dlogit, mask_out, loss_part);
     VR_HIP(hipGetLastError());
     launch_reduce_rows(loss_part, 1, nb, loss_out, 1, 0, loss_scale, st);
 }

@@ -104,6 +104,11 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 dense, accumulated onto zeros
 // thin            N,C,H,W,CO            slope            x, aff[C][2]|null, w[CO][C], dz[N,CO,H,W]           g[N,C,H,W], dw[CO][C], z[N,H,W] (CO=1: forward)
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
+// head_loss_complex N,C,H,W,bins        slope,gscale     x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[1],
+//                                                        (complex64)                                         g[N,C,H,W], dw[4][C]
+//                 launch_head_loss_complex (loss = mean |m X - y| over the N*2*bins*W complex elements), then the CO = 4 thin data and
+//                 weight gradients of that dlogit (launch_thin_dgrad storing, launch_thin_wgrad storing), as Model::train_fwd_bwd_api
+//                 runs them on a complex handle
 // head            N,C,H,W,w_lo,w_hi,pad_rows,cplx,hsplit,use_items,pitch_extra
 //                                       slope            x[N,C,H,W], aff0[C][2]|null, aff1[C][2]|null,       the destination(s), whole: dense [N][2][H+pad_rows][Wm +
 //                                                        w[CO][C] (CO = 2; cplx: 4)                          pitch_extra], or with use_items one buffer per item n,
@@ -683,6 +688,24 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_HIP(hipStreamSynchronize(st));
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, sizeof(float), hipMemcpyDeviceToHost));
+    } else if (name == "head_loss_complex") {
+        need(5, 2, 5, 5);
+        const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], bins = (int)dims[4];
+        VR_CHECK(N > 0 && C > 0 && H > 0 && W > 0 && bins >= H && W % 4 == 0, -2, "head_loss_complex: need positive sizes, bins >= H, W % 4 == 0");
+        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W;       // (nx complex elements)
+        DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)4 * C), X(in[3], 2 * nx), Y(in[4], 2 * nx);
+        Tensor t = dense(x.p, N, C, H, W);
+        t.slope = fp[0];
+        if (in[1]) t.aff0 = aff.p;
+        DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), loss(4), g(n), dw((size_t)4 * C);
+        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C);
+        launch_head_loss_complex(t, w.p, X.p, Y.p, bins, fp[1], dlogit.p, mask.p, lpart.p, loss.p, (float)(1.0 / (double)nx), st);
+        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
+        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
+        VR_HIP(hipStreamSynchronize(st));
+        dlogit.download(out[0]); mask.download(out[1]);
+        VR_HIP(hipMemcpy(out[2], loss.p, sizeof(float), hipMemcpyDeviceToHost));
+        g.download(out[3]); dw.download(out[4]);
     } else if (name == "head") {
         need(11, 1, 4, 1);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], w_lo = (int)dims[4], w_hi = (int)dims[5];

@@ -56,12 +56,13 @@ void launch_materialize(const Tensor& x, float* out, hipStream_t st);
 // training input pipeline (augment.hip); layout-compatible with vr_aug in include/vr_mi355.h
 struct AugDesc { float coef, coef_mix, lam; int flags; };
 void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDesc* desc, const float* rw,
-                    int B, int T, int bins, float* Xmag, float* Ymag, hipStream_t st);
+                    int B, int T, int bins, float* Xmag, float* Ymag, bool out_complex, hipStream_t st);
+// (out_complex: the augmented x, y themselves as complex64 [B][2][bins][T] instead of their magnitudes -- a complex-mask model's batches)
 // the same kernel reading the crops where they lie in a resident store: one entry per sample, every pointer at the sample's
 // first row of its song's [rows][2][bins] slab (the mixup pair repeats the first two when the sample has no partner)
 struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
-                             float* Ymag, hipStream_t st);
+                             float* Ymag, bool out_complex, hipStream_t st);
 bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32
 void thin16_fill_tiling(ConvArgs& a, int TH);
 void thin16_launch_conv(const ConvArgs& a, const ConvShape& s, int TH, hipStream_t st);
@@ -154,6 +155,11 @@ int head_loss_blocks(const Tensor& x);
 void launch_head_loss(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float gscale,
                       float* dlogit, float* mask_out, float* loss_part, float* loss_out, float loss_scale, hipStream_t st);
 void launch_head_bwd(const float* dmask, const float* mask, int N, int H, int W, int bins, float* dlogit, hipStream_t st);
+// the complex-mask head (w [4][C]): X, Y, mask_out, dmask complex64 [N][2][bins][W], dlogit [N][4][H][W] (re ch0, re ch1, im ch0, im ch1);
+// loss = sum |m X - y| over complex elements times loss_scale; head_bwd forms the logits again from x
+void launch_head_loss_complex(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float gscale,
+                              float* dlogit, float* mask_out, float* loss_part, float* loss_out, float loss_scale, hipStream_t st);
+void launch_head_bwd_complex(const Tensor& x, const float* w, const float* dmask, int bins, float* dlogit, hipStream_t st);
 struct FlipDesc { const float* w; float* wt; int Cin, Cout, KK, CinPad, CoutPad; };
 void launch_flip_transpose(const FlipDesc* d_descs, int n, hipStream_t st);
 void launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2, double eps,
@@ -168,6 +174,8 @@ void launch_mul_crop(const float* x, float* m, bool cplx, long long rows, int T,
 // loss[0] = mean |pred [rows][Wm] - y [rows][T] at columns off .. off + Wm|; part: scratch of l1_crop_blocks() floats
 int l1_crop_blocks();
 void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
+// the same on complex64 pred and y: mean |pred - y| over complex elements (rows and columns count complex elements)
+void launch_l1_crop_complex(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
 
 // ---- stft.hip -----------------------------------------------------------------------------------
 struct FFTPlan { int n_fft; int log2n; float2* twiddle; float* window; };

@@ -157,8 +157,11 @@ public:
     int device, n_fft, hop, nout, nout_lstm, max_bin, output_bin, offset = 64;
     // CascadedNet(is_complex=True) (lib/nets.py:46-141): the input is the complex spectrogram as nin = 4 planar channels
     // [re L, re R, im L, im R], the head predicts a complex mask bounded by tanh(|m|), every mask buffer is complex64.
-    // Eval-mode inference only: the training entry points refuse such a handle (need_real_mask).
+    // Eval-mode inference only unless complex_train is set: the training entry points refuse such a handle (need_real_mask).
     bool is_complex = false;
+    // vr_set_option("complex_train") (default 0, complex handles only): the training entry points take such a handle -- interleaved
+    // complex64 X, y, mask, dmask; loss = mean |m X - y| over complex elements.  Off: they refuse it, as before.
+    bool complex_train = false;
     int nin = 2;
     void need_real_mask(const char* what) const;          // refuse a complex handle (training entry points)
     void need_real_mask_train(const char* what) const;    // ... only while it is in training mode
@@ -253,9 +256,9 @@ public:
     std::string profile_report;                          // per-kernel-name totals of the last profiled step (vr_profile_report)
     void profile_begin();
     void augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
-                     int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev);
+                     int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
     void dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
-                           float* Xmag, float* ymag, bool out_on_dev);
+                           float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
     char* aug_buf = nullptr; size_t aug_cap = 0;         // staging of the training input pipeline
     void aug_reserve(size_t need);
     bool train_wino = true;                              // vr_set_option("train_winograd"): Winograd kernels in train mode

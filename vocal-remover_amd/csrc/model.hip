@@ -327,12 +327,12 @@ void Model::get_param(const std::string& key, void* host, int64_t cap_bytes) {
 }
 
 void Model::need_real_mask(const char* what) const {
-    VR_CHECK(!is_complex, -2, std::string(what) + ": this handle predicts a complex mask (is_complex=True); only eval-mode inference "
+    VR_CHECK(!is_complex || complex_train, -2, std::string(what) + ": this handle predicts a complex mask (is_complex=True); only eval-mode inference "
                               "is supported for it, training is not");
 }
 
 void Model::need_real_mask_train(const char* what) const {
-    VR_CHECK(!(is_complex && training), -2, std::string(what) + " in training mode: this handle predicts a complex mask "
+    VR_CHECK(!(is_complex && training) || complex_train, -2, std::string(what) + " in training mode: this handle predicts a complex mask "
                                             "(is_complex=True); only eval-mode inference is supported for it, training is not");
 }
 
@@ -376,6 +376,11 @@ void Model::set_option(const std::string& name, int value) {
         x3s_mode = value < 0 ? x3s_default() : value;
     }
     else if (name == "crop_window") crop_window = value != 0;
+    else if (name == "complex_train") {                      // a complex handle under the training entry points (off by default: they refuse it)
+        if (!is_complex) throw Error(-2, "complex_train: this handle predicts a magnitude mask; the option belongs to complex-mask handles (VR_CREATE_COMPLEX)");
+        complex_train = value != 0;
+        graph_valid = false;
+    }
     else if (name == "adam_reset") reset_adam_state();      // a freshly constructed torch.optim.Adam has no moments
     else if (name == "hip_graph" || name == "conv_x3p" || name == "wgrad_x3h" || name == "conv_x3b") {
         // options of round 4 whose kernels moved to tools/experiments in round 5: accepted and ignored, so that an older caller keeps
@@ -1290,8 +1295,13 @@ void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int 
     const size_t pack_floats = (size_t)B * 4 * output_bin * T;
     const int Wm = mode == 0 ? T : T - 2 * offset;
     const size_t out_floats = (size_t)B * 2 * output_bin * Wm * 2;
-    fold_eval_affines();
+    // train mode ("complex_train"): batch statistics and their running update, live Dropout2d, no tape -- as forward_api
+    struct FwdOnly { Model* m; ~FwdOnly() { m->fwd_only = false; m->dropout_dev = nullptr; } } fwd_scope{this};
+    fwd_only = training;
+    if (training) refresh_wino(false);
+    if (!training) fold_eval_affines();
     plan_and_reserve(B, T, (in_floats + pack_floats + out_floats) * sizeof(float) + 2048);
+    if (training) prepare_dropout(B);
     float* xd = ws.allocf(in_floats);
     float* xp = ws.allocf(pack_floats);
     float* od = out_on_device ? out : ws.allocf(out_floats);
@@ -1309,6 +1319,7 @@ void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int 
     if (mode == 2) launch_mul_crop(xd, od, true, (long long)B * 2 * output_bin, T, Wm, offset, stream);
     if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
+    if (training) affine_dirty = true;
 }
 
 void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
@@ -1347,13 +1358,20 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
 }
 
 // sum |pred - crop_center(y)| per block; pred [rows][Wm] dense, y [rows][T] dense, columns [off, off+Wm) of y
+// CPLX: complex64 pred and y, |.| of the complex difference (torch's L1Loss on complex tensors); `total` counts elements
+template <bool CPLX>
 __global__ __launch_bounds__(256) void l1_crop_kernel(const float* __restrict__ pred, const float* __restrict__ y, int T, int Wm,
                                                       int off, long long total, float* __restrict__ part) {
     float s = 0.f;
     for (long long gid = (long long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long long)gridDim.x * 256) {
         const int w = (int)(gid % Wm);
         const long long row = gid / Wm;
-        s += fabsf(pred[gid] - y[row * T + off + w]);
+        if constexpr (CPLX) {
+            const float2 a = reinterpret_cast<const float2*>(pred)[gid], b = reinterpret_cast<const float2*>(y)[row * T + off + w];
+            s += hypotf(a.x - b.x, a.y - b.y);
+        } else {
+            s += fabsf(pred[gid] - y[row * T + off + w]);
+        }
     }
     __shared__ float red[4];
 #pragma unroll
@@ -1368,7 +1386,15 @@ int l1_crop_blocks() { return 1024; }
 void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
     const long long total = rows * Wm;
     const int nblk = l1_crop_blocks();
-    VR_LAUNCH(l1_crop_kernel, dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    VR_LAUNCH((l1_crop_kernel<false>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    VR_HIP(hipGetLastError());
+    launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
+}
+
+void launch_l1_crop_complex(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
+    const long long total = rows * Wm;
+    const int nblk = l1_crop_blocks();
+    VR_LAUNCH((l1_crop_kernel<true>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
     VR_HIP(hipGetLastError());
     launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
 }
@@ -1381,12 +1407,14 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     VR_CHECK(!training, -2, "validate step runs in eval mode (train.py:109 model.eval()); call vr_set_mode(h, 0) first");
     VR_CHECK(B > 0, -2, "batch must be positive");
     check_T(T, offset, 2);
-    const size_t in_floats = (size_t)B * 2 * output_bin * T;
+    const size_t E = is_complex ? 2 : 1;             // floats per element: a complex handle takes and predicts complex64
+    const size_t in_floats = (size_t)B * 2 * output_bin * T * E;
+    const size_t pack_floats = is_complex ? (size_t)B * 4 * output_bin * T : 0;
     const int Wm = T - 2 * offset;
-    const size_t out_floats = (size_t)B * 2 * output_bin * Wm;
+    const size_t out_floats = (size_t)B * 2 * output_bin * Wm * E;
     const int nblk = l1_crop_blocks();
     fold_eval_affines();                    // before planning, as in forward_api
-    plan_and_reserve(B, T, (2 * in_floats + out_floats + nblk + 64) * sizeof(float) + 8192);
+    plan_and_reserve(B, T, (2 * in_floats + pack_floats + out_floats + nblk + 64) * sizeof(float) + 8192);
     float* xd = ws.allocf(in_floats);
     const float* yd = Y;
     const hipMemcpyKind kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -1402,14 +1430,25 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     Tensor xt;
     xt.p = xd; xt.N = B; xt.C = 2; xt.H = max_bin; xt.W = T;
     xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
+    if (is_complex) {                       // the planar [re L, re R, im L, im R] input of forward_complex
+        float* xp = ws.allocf(pack_floats);
+        launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
+        xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
+    }
     Tensor f3 = run_net_window(xt, offset, T - offset);
     HeadDst d{};
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
-    launch_head_sigmoid(f3, out_w->dev, d, stream);
     const long long rows = (long long)B * 2 * output_bin;
-    launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
-    launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
+    if (is_complex) {
+        launch_head_complex(f3, out_w->dev, d, stream);
+        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
+        launch_l1_crop_complex(od, yd, rows, T, Wm, offset, part, lossd, stream);
+    } else {
+        launch_head_sigmoid(f3, out_w->dev, d, stream);
+        launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
+        launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
+    }
     float loss_h = 0.f;
     VR_HIP(hipMemcpyAsync(&loss_h, lossd, sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));

@@ -464,7 +464,10 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
     launch_flip_transpose(d_flip, n_flip, stream);
     launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
     refresh_wino(true);
-    const size_t io_floats = (size_t)B * 2 * output_bin * T;
+    // a complex handle ("complex_train"): X, y, mask are interleaved complex64, the network reads four planar channels, the head has four
+    // outputs -- every buffer below that holds complex or four-channel data doubles (cplx), in the dry run and the real one alike
+    const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;
+    const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
     const int Hm = max_bin;
     // ---- plan: dry run of forward + backward sizes both arenas ----------------------------------------
     auto run_all = [&](const float* xd, const float* yd, float* maskd, float* lossd) {
@@ -473,18 +476,27 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
         Tensor xt;
         xt.p = const_cast<float*>(xd); xt.N = B; xt.C = 2; xt.H = Hm; xt.W = T;
         xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
+        if (is_complex) {                            // [B][2][bins][T] complex64 -> planar [B][4][bins][T] (re L, re R, im L, im R), unscaled
+            float* xp = ws.allocf((size_t)B * 4 * output_bin * T);
+            if (!dry) launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
+            xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
+        }
         Tensor f3 = run_net(xt);
         // head + loss (train.py:81,89) and its backward into f3.g / out.weight
-        float* dlogit = ws.allocf((size_t)B * 2 * Hm * T);
+        float* dlogit = ws.allocf((size_t)B * CO * Hm * T);
         float* lpart = ws.allocf((size_t)head_loss_blocks(f3));
-        float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * 2 * f3.C);
+        float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
         if (!dry) {
             if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
-            const double ntot = (double)B * 2 * output_bin * T;
-            launch_head_loss(f3, out_w->dev, xd, yd, output_bin, (float)(1.0 / (ntot * accumulation_steps)), dlogit, maskd,
-                             lpart, lossd, (float)(1.0 / ntot), stream);
-            launch_thin_wgrad(f3, 2, dlogit, wpart, grad_of(out_w), 1, stream);
-            launch_thin_dgrad(f3, 2, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+            const double ntot = (double)B * 2 * output_bin * T;          // (complex handle: complex elements, as torch's L1Loss counts them)
+            if (is_complex)
+                launch_head_loss_complex(f3, out_w->dev, xd, yd, output_bin, (float)(1.0 / (ntot * accumulation_steps)), dlogit, maskd,
+                                         lpart, lossd, (float)(1.0 / ntot), stream);
+            else
+                launch_head_loss(f3, out_w->dev, xd, yd, output_bin, (float)(1.0 / (ntot * accumulation_steps)), dlogit, maskd,
+                                 lpart, lossd, (float)(1.0 / ntot), stream);
+            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
+            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
         }
         backward();
     };
@@ -557,7 +569,8 @@ void Model::forward_train_api(const float* X, bool on_dev, int B, int T, float* 
     launch_flip_transpose(d_flip, n_flip, stream);
     launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
     refresh_wino(true);
-    const size_t io_floats = (size_t)B * 2 * output_bin * T;
+    const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;          // as in train_fwd_bwd_api
+    const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
     const int Hm = max_bin;
     auto fwd = [&](const float* xd) {
         tape.clear();
@@ -565,11 +578,16 @@ void Model::forward_train_api(const float* X, bool on_dev, int B, int T, float* 
         Tensor xt;
         xt.p = const_cast<float*>(xd); xt.N = B; xt.C = 2; xt.H = Hm; xt.W = T;
         xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
+        if (is_complex) {
+            float* xp = ws.allocf((size_t)B * 4 * output_bin * T);
+            if (!dry) launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
+            xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
+        }
         return run_net(xt);
     };
     auto bwd_scratch = [&](const Tensor& f3) {       // the allocations backward_api makes, in its order
-        ws.allocf((size_t)B * 2 * Hm * T);
-        ws.allocf((size_t)thin_wgrad_blocks(f3) * 2 * f3.C);
+        ws.allocf((size_t)B * CO * Hm * T);
+        ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
     };
     {   // plan: dry run of forward + backward sizes both arenas
         Arena sws = ws, sgs = gs;
@@ -606,7 +624,8 @@ void Model::forward_train_api(const float* X, bool on_dev, int B, int T, float* 
     HeadDst d{};
     d.p = graph_mask; d.dH = T; d.dC = (long long)output_bin * T; d.dN = 2 * d.dC;
     d.w_lo = 0; d.w_hi = T; d.pad_rows = output_bin - max_bin;
-    launch_head_sigmoid(graph_f3, out_w->dev, d, stream);
+    if (is_complex) launch_head_complex(graph_f3, out_w->dev, d, stream);       // (d's strides count complex elements)
+    else launch_head_sigmoid(graph_f3, out_w->dev, d, stream);
     VR_HIP(hipMemcpyAsync(mask_out, graph_mask, io_floats * sizeof(float), mask_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
     graph_valid = true; graph_B = B; graph_T = T; ++graph_gen;
@@ -619,30 +638,25 @@ void Model::backward_api(const float* dmask, bool on_dev) {
     VR_CHECK(dmask != nullptr, -2, "null argument");
     graph_valid = false;
     const int B = graph_B, T = graph_T, Hm = max_bin;
-    const size_t io_floats = (size_t)B * 2 * output_bin * T;
+    const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;
+    const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
     const Tensor& f3 = graph_f3;
     const float* dm = dmask;
+    float* tmp = nullptr;
+    struct Free { float*& p; hipStream_t s; ~Free() { if (p) { hipStreamSynchronize(s); hipFree(p); } } } fr{tmp, stream};
     if (!on_dev) {                                                 // the input copy of the forward is dead by now: reuse nothing, stage after the tape
-        float* tmp = nullptr;
         VR_HIP(hipMalloc(&tmp, io_floats * sizeof(float)));
-        struct Free { float* p; hipStream_t s; ~Free() { hipStreamSynchronize(s); hipFree(p); } } fr{tmp, stream};
         VR_HIP(hipMemcpyAsync(tmp, dmask, io_floats * sizeof(float), hipMemcpyHostToDevice, stream));
-        float* dlogit = ws.allocf((size_t)B * 2 * Hm * T);
-        float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * 2 * f3.C);
-        launch_head_bwd(tmp, graph_mask, B, Hm, T, output_bin, dlogit, stream);
-        launch_thin_wgrad(f3, 2, dlogit, wpart, grad_of(out_w), 1, stream);
-        launch_thin_dgrad(f3, 2, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
-        backward();
-        VR_HIP(hipStreamSynchronize(stream));
-    } else {
-        float* dlogit = ws.allocf((size_t)B * 2 * Hm * T);
-        float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * 2 * f3.C);
-        launch_head_bwd(dm, graph_mask, B, Hm, T, output_bin, dlogit, stream);
-        launch_thin_wgrad(f3, 2, dlogit, wpart, grad_of(out_w), 1, stream);
-        launch_thin_dgrad(f3, 2, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
-        backward();
-        VR_HIP(hipStreamSynchronize(stream));
+        dm = tmp;
     }
+    float* dlogit = ws.allocf((size_t)B * CO * Hm * T);
+    float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
+    if (is_complex) launch_head_bwd_complex(f3, out_w->dev, dm, output_bin, dlogit, stream);
+    else launch_head_bwd(dm, graph_mask, B, Hm, T, output_bin, dlogit, stream);
+    launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
+    launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+    backward();
+    VR_HIP(hipStreamSynchronize(stream));
     tape.clear();
     dropout_dev = nullptr;
 }
@@ -658,10 +672,10 @@ void Model::aug_reserve(size_t need) {
 
 // Training input pipeline (lib/dataset.py:105-120 after the random draws and the file reads), see augment.hip.
 void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
-                        int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev) {
+                        int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex) {
     DeviceGuard dev_guard(device);
     VR_CHECK(B > 0 && T > 0 && bins > 0, -2, "augment: empty batch");
-    const size_t crop_b = (size_t)B * T * 2 * bins * sizeof(float2), out_b = (size_t)B * 2 * bins * T * sizeof(float);
+    const size_t crop_b = (size_t)B * T * 2 * bins * sizeof(float2), out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
     const size_t desc_b = (size_t)B * sizeof(AugDesc), rw_b = (size_t)bins * sizeof(float);
     auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
     size_t need = up256(desc_b) + up256(rw_b);
@@ -686,7 +700,7 @@ void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const
     float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(take(out_b));
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(take(out_b));
     launch_augment(dev[0], dev[1], dev[2] ? dev[2] : dev[0], dev[3] ? dev[3] : dev[1], dd, rw ? drw : nullptr, B, T, bins, ox, oy,
-                   stream);
+                   out_complex, stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));
@@ -765,7 +779,7 @@ int ResidentSet::add(const float* X, const float* y, long long rows) {
 // pointer table, descriptors and reduction weight go to the handle's aug_buf in ONE copy and augment_kernel<true> reads the crops
 // where they lie.
 void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
-                              float* Xmag, float* ymag, bool out_on_dev) {
+                              float* Xmag, float* ymag, bool out_on_dev, bool out_complex) {
     VR_CHECK(set.device == device, -2, "vr_dataset_batch: the handle is on device " + std::to_string(device) + ", the dataset on device " +
                                            std::to_string(set.device));
     VR_CHECK(T > 0, -2, "vr_dataset_batch: T must be positive");
@@ -774,7 +788,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
     std::vector<char> host;
     auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t tab_b = (size_t)B * sizeof(AugCrops), desc_b = (size_t)B * sizeof(AugDesc), rw_b = (size_t)bins * sizeof(float);
-    const size_t out_b = (size_t)B * 2 * bins * T * sizeof(float);
+    const size_t out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
     const size_t head = up256(tab_b) + up256(desc_b) + (rw ? up256(rw_b) : 0);
     host.resize(head);
     AugCrops* tab = reinterpret_cast<AugCrops*>(host.data());
@@ -815,7 +829,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
     const float* drw = rw ? reinterpret_cast<const float*>(aug_buf + up256(tab_b) + up256(desc_b)) : nullptr;
     float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(aug_buf + head);
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(aug_buf + head + up256(out_b));
-    launch_augment_resident(dtab, dd, drw, B, T, bins, ox, oy, stream);
+    launch_augment_resident(dtab, dd, drw, B, T, bins, ox, oy, out_complex, stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));

@@ -55,12 +55,24 @@ def _read_rows(path, start_row, n_rows, out):
         raise ValueError('%s: short read (%d of %d bytes)' % (path, got, n_rows * row_bytes))
 
 
+def _outputs(complex_output, shape, dev, entry):
+    """The two output tensors of a batch and the entry point that fills them: float32 magnitudes, or with complex_output the
+    augmented crops themselves as complex64 (the `_complex` variant of the entry point)."""
+    dtype = torch.complex64 if complex_output else torch.float32
+    call = getattr(native.lib(), entry + '_complex' if complex_output else entry)
+    return torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=dtype, device=dev), call
+
+
 class VocalRemoverTrainingSet(object):
     """lib/dataset.py:15-120 with the numeric part on the GPU.  `model` is the vocal_remover_amd CascadedNet
-    whose device (and HIP stream) the batches are produced on."""
+    whose device (and HIP stream) the batches are produced on.  complex_output=True (all four set classes): the batches are the
+    augmented complex crops (complex64), what a complex-mask model trains on -- lib/dataset.py:120, the commented `return X, y`;
+    the random draws are the same."""
 
-    def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None):
+    def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None,
+                 complex_output=False):
         self.training_set = training_set
+        self.complex_output = bool(complex_output)      # complex64 batches for a complex-mask model: no final np.abs
         self.cropsize = cropsize
         self.reduction_rate = reduction_rate
         self.reduction_weight = None if reduction_weight is None else \
@@ -132,10 +144,9 @@ class VocalRemoverTrainingSet(object):
         if need_rw and self.reduction_weight is None:
             raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
         dev = torch.device('cuda', h.device)
-        X_mag = torch.empty((B, 2, bins, T), dtype=torch.float32, device=dev)
-        y_mag = torch.empty((B, 2, bins, T), dtype=torch.float32, device=dev)
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, bins, T), dev, 'vr_augment_batch')
         rw = self.reduction_weight
-        native.check(native.lib().vr_augment_batch(
+        native.check(call(
             h.h, native.np_ptr(X), native.np_ptr(y), native.np_ptr(Xm) if any_mix else None,
             native.np_ptr(ym) if any_mix else None, ctypes.cast(desc, ctypes.c_void_p),
             native.np_ptr(rw) if rw is not None else None, B, T, bins, 0,
@@ -151,9 +162,10 @@ class VocalRemoverValidationSet(object):
     """lib/dataset.py:123-140: validation patches saved by make_validation_set as .npz with complex X, y of shape
     [2, bins, cropsize]; `abs` runs on the model's GPU (vr_augment_batch with no augmentation flags)."""
 
-    def __init__(self, patch_list, model=None):
+    def __init__(self, patch_list, model=None, complex_output=False):
         self.patch_list = patch_list
         self.model = model
+        self.complex_output = bool(complex_output)
 
     def __len__(self):
         return len(self.patch_list)
@@ -171,11 +183,10 @@ class VocalRemoverValidationSet(object):
         B, T, _, bins = X.shape
         desc = (_Aug * B)(*[_Aug(1.0, 1.0, 1.0, 0) for _ in range(B)])
         dev = torch.device('cuda', h.device)
-        X_mag = torch.empty((B, 2, bins, T), dtype=torch.float32, device=dev)
-        y_mag = torch.empty((B, 2, bins, T), dtype=torch.float32, device=dev)
-        native.check(native.lib().vr_augment_batch(h.h, native.np_ptr(X), native.np_ptr(y), None, None,
-                                                   ctypes.cast(desc, ctypes.c_void_p), None, B, T, bins, 0,
-                                                   ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, bins, T), dev, 'vr_augment_batch')
+        native.check(call(h.h, native.np_ptr(X), native.np_ptr(y), None, None,
+                          ctypes.cast(desc, ctypes.c_void_p), None, B, T, bins, 0,
+                          ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
         return X_mag, y_mag
 
     def __getitem__(self, idx):
@@ -196,6 +207,7 @@ def _check_capacity(what, need, max_bytes):
 class _Resident(object):
     """What the two resident sets share: the store on the model's device, filled at the first batch, and its lifetime."""
     model = None
+    complex_output = False
     _store = None
 
     def _handle(self):
@@ -208,9 +220,8 @@ class _Resident(object):
         store = self._store
         B = len(desc)
         dev = torch.device('cuda', h.device)
-        X_mag = torch.empty((B, 2, store.bins, T), dtype=torch.float32, device=dev)
-        y_mag = torch.empty((B, 2, store.bins, T), dtype=torch.float32, device=dev)
-        native.check(native.lib().vr_dataset_batch(
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, store.bins, T), dev, 'vr_dataset_batch')
+        native.check(call(
             h.h, store.d, ctypes.cast(crops, ctypes.c_void_p), ctypes.cast(desc, ctypes.c_void_p),
             native.np_ptr(rw) if rw is not None else None, B, T,
             ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
@@ -251,8 +262,10 @@ class ResidentTrainingSet(_Resident):
     where that leaves it.  The first batch uploads every distinct (X, y) pair of the list once, through a memory map of the .npy
     files; `model` may be swapped for another model on the same device at any time (the store belongs to the set, not to a handle)."""
 
-    def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None):
+    def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None,
+                 complex_output=False):
         self.training_set = training_set
+        self.complex_output = bool(complex_output)
         self.cropsize = cropsize
         self.reduction_rate = reduction_rate
         self.reduction_weight = None if reduction_weight is None else \
@@ -337,9 +350,10 @@ class ResidentValidationSet(_Resident):
     uploaded once as a song of [T, 2, bins] rows, and a batch is the device call of ResidentTrainingSet with start 0 and no
     augmentation flags -- bit-identical to VocalRemoverValidationSet.batch."""
 
-    def __init__(self, patch_list, model=None, max_bytes=None):
+    def __init__(self, patch_list, model=None, max_bytes=None, complex_output=False):
         self.patch_list = patch_list
         self.model = model
+        self.complex_output = bool(complex_output)
         self.max_bytes = max_bytes
         self._song = {}
         self._T = None

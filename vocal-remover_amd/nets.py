@@ -13,8 +13,11 @@ What callers touch and what happens here:
 Inputs and outputs are torch tensors; a tensor already on the handle's GPU is passed by device
 pointer (no host round trip), a CPU tensor is copied in by the library.
 
-is_complex=True (lib/nets.py:82-122): inputs are complex spectrograms, masks and predictions are complex64; eval-mode
-inference only -- a forward under model.train() and the training entry points raise NotImplementedError.
+is_complex=True (lib/nets.py:82-122): inputs are complex spectrograms, masks and predictions are complex64.  Training such a
+model is opt-in per handle: CascadedNet(..., is_complex=True, complex_train=True) or model.set_option('complex_train', 1) after
+.to(device); then forward under model.train(), train_step, validate_step and Trainer take complex64 tensors and the loss is
+L1Loss()(mask * X, y) on complex tensors (mean |.| of the complex difference).  Without the option -- the default -- a forward under
+model.train() and the training entry points raise NotImplementedError.
 """
 import math
 from collections import OrderedDict
@@ -105,12 +108,17 @@ class _ForwardTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat, x, model):
         h = model._need_handle()
+        if model.is_complex and not x.is_complex():
+            raise RuntimeError('imag is not implemented for tensors with non-complex dtypes')     # the reference's x.imag
         if x.dim() != 4 or x.shape[1] != 2 or x.shape[2] != model.output_bin:
             raise ValueError('expected input [B, 2, %d, T], got %s' % (model.output_bin, tuple(x.shape)))
         on_dev = x.is_cuda
         if on_dev and x.device.index != h.device:
             raise RuntimeError('input is on %s but the model is on cuda:%d' % (x.device, h.device))
-        xc = x.detach().to(torch.float32).contiguous()
+        if model.is_complex:                           # interleaved (re, im) float pairs in, a complex64 mask out
+            xc = x.detach().to(torch.complex64).resolve_conj().contiguous()
+        else:
+            xc = x.detach().to(torch.float32).contiguous()
         mask = torch.empty_like(xc)
         # a pending torch-side write to the parameter arena (torch.optim.Adam.step) must land before the library's own
         # stream reads it -- also when X itself comes from the host
@@ -133,7 +141,8 @@ class _ForwardTrain(torch.autograd.Function):
                                'the LAST model(X) only (another forward / predict / validate call, a second backward or a '
                                '.to(device) in between frees it)')
         on_dev = dmask.is_cuda
-        d = dmask.detach().to(torch.float32).contiguous()
+        # (a complex mask: torch hands dL/dRe + i dL/dIm for a real loss, which is what vr_backward takes)
+        d = dmask.detach().to(torch.complex64 if model.is_complex else torch.float32).resolve_conj().contiguous()
         torch.cuda.current_stream(torch.device('cuda', h.device)).synchronize()
         native.check(native.lib().vr_backward(h.h, d.data_ptr(), int(on_dev)))
         model._flat_parameter()                     # (re-)attach .grad to the arena view
@@ -142,10 +151,14 @@ class _ForwardTrain(torch.autograd.Function):
 
 class CascadedNet(object):
 
-    def __init__(self, n_fft, hop_length, nout=32, nout_lstm=128, is_complex=False):
+    def __init__(self, n_fft, hop_length, nout=32, nout_lstm=128, is_complex=False, complex_train=False):
         self.n_fft = n_fft
         self.hop_length = hop_length
         self.is_complex = bool(is_complex)
+        if complex_train and not is_complex:
+            raise ValueError('complex_train belongs to a complex-mask model (is_complex=True)')
+        self.complex_train = bool(complex_train)      # set on every handle .to(device) creates
+        self._complex_train_on = False                # the state of the CURRENT handle's "complex_train" option
         self.nout = nout
         self.nout_lstm = nout_lstm
         self.max_bin = n_fft // 2
@@ -195,6 +208,9 @@ class CascadedNet(object):
                 self._handle_gen += 1
                 self._device = torch.device('cuda', index)
                 self._push()
+                self._complex_train_on = False
+                if self.complex_train:
+                    self.set_option('complex_train', 1)
                 native.check(native.lib().vr_set_mode(self._handle.h, int(self.training)))
                 # nn.Dropout2d(0.1) on the ASPP outputs is live in train mode (lib/layers.py:90): the library's
                 # generator is seeded from torch's seed, so torch.manual_seed() makes runs repeatable
@@ -227,6 +243,7 @@ class CascadedNet(object):
         self._flat_key = None
         self._handle.close()
         self._handle = None
+        self._complex_train_on = False
         self._handle_gen += 1
 
     def _graph_generation(self):
@@ -255,9 +272,10 @@ class CascadedNet(object):
         return self._handle
 
     def _no_complex_training(self, what):
-        if self.is_complex:
+        if self.is_complex and not (self._handle is not None and self._complex_train_on):
             raise NotImplementedError('%s: training a complex-mask CascadedNet (is_complex=True) is not supported; only eval-mode '
-                                      'inference is (call model.eval())' % what)
+                                      'inference is (call model.eval()) -- unless the handle opts in: CascadedNet(..., complex_train=True) '
+                                      'or model.set_option("complex_train", 1) after .to(device)' % what)
 
     def _run(self, x, mode):
         h = self._need_handle()
@@ -366,6 +384,14 @@ class CascadedNet(object):
             if self._flat is not None:
                 self._flat.grad = self._flat_grad                     # stays the arena view (never None)
 
+    def _train_io(self, t):
+        """X / y of the training entry points as the library takes them: float32, or interleaved complex64 for a complex-mask model."""
+        if self.is_complex:
+            if not t.is_complex():
+                raise RuntimeError('imag is not implemented for tensors with non-complex dtypes')     # the reference's x.imag
+            return t.detach().to(torch.complex64).resolve_conj().contiguous()
+        return t.detach().to(torch.float32).contiguous()
+
     def train_step(self, X, y, accumulation_steps=1, return_mask=False):
         """mask = model(X); loss = L1Loss()(mask * X, y); (loss / accumulation_steps).backward()
         in one native call.  Returns loss.item() (and the mask if asked)."""
@@ -379,8 +405,7 @@ class CascadedNet(object):
         on_dev = X.is_cuda
         if on_dev != y.is_cuda:
             raise ValueError('X and y must live on the same device')
-        X = X.detach().to(torch.float32).contiguous()
-        y = y.detach().to(torch.float32).contiguous()
+        X, y = self._train_io(X), self._train_io(y)
         B, T = int(X.shape[0]), int(X.shape[3])
         mask = torch.empty_like(X) if return_mask else None
         if on_dev:
@@ -404,8 +429,7 @@ class CascadedNet(object):
         on_dev = X.is_cuda
         if on_dev != y.is_cuda:
             raise ValueError('X and y must live on the same device')
-        X = X.detach().to(torch.float32).contiguous()
-        y = y.detach().to(torch.float32).contiguous()
+        X, y = self._train_io(X), self._train_io(y)
         if on_dev:
             torch.cuda.current_stream(X.device).synchronize()
         loss = ctypes.c_float()
@@ -431,6 +455,8 @@ class CascadedNet(object):
         """Numerical options of the library (include/vr_mi355.h: vr_set_option), e.g. 'train_winograd'."""
         h = self._need_handle()
         native.check(native.lib().vr_set_option(h.h, name.encode(), int(value)))
+        if name == 'complex_train':
+            self._complex_train_on = bool(int(value))
 
     def set_dropout_masks(self, masks):
         """Inject Dropout2d keep-masks {'<net>.aspp': [B, 8c] tensor of 0 / (1/0.9)} (parity tests);
