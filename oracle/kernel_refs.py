@@ -754,3 +754,125 @@ def dgrad_launch_ref(desc):
             b[idx] = b[idx] + g
         bufs.append(b)
     return bufs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one pass over a pending, strided tensor: launch_materialize, launch_upsample2x, launch_avgpool_h (csrc/pointwise.hip)
+# ---------------------------------------------------------------------------------------------------------------------------------
+TENSOR_PASS_OPS = {'materialize': 0, 'upsample2x': 1, 'avgpool_h': 2}
+TENSOR_PASS_KERNELS = ('materialize_kernel', 'materialize4_kernel', 'materialize4p_kernel', 'upsample2x_kernel<2>', 'upsample2x_kernel<4>',
+                       'upsample2x_rows_kernel', 'upsample2x_lds_kernel', 'avgpool_h_kernel')
+
+
+def _tcase(name, op, shape, kernel, layout='dense', shift=0, aff0=False, aff1=False, hsplit=None, slope=1.0, post=False, bcastH=0,
+           inplace=False, refused=None, data=None):
+    # kernel: the kernel the launcher must take (None: the launch is refused, with `refused` in its message).  shift: the view lies that
+    # many floats further into a buffer that many floats longer.  data: as in _case.
+    return dict(name=name, op=TENSOR_PASS_OPS[op], shape=shape, kernel=kernel, layout=layout, shift=shift, aff0=aff0, aff1=aff1, hsplit=hsplit,
+                slope=slope, post=post, bcastH=bcastH, inplace=inplace, refused=refused, data=data or name)
+
+
+def _tpend(hsplit):
+    """Pending: two BatchNorm affines split at a row strictly inside the tensor, LeakyReLU, a Dropout2d multiplier."""
+    return dict(aff0=True, aff1=True, hsplit=hsplit, slope=0.01, post=True)
+
+
+# The case table of tests/test_gpu_tensor_pass.py and of the pin in tests/test_cpu_kernel_refs.py.  The kernel beside each case follows
+# from the dispatch of the launcher (Q = W / 4 quads per row, HQ = H * Q quads per plane):
+#   launch_materialize  W, sN, sC, sH all % 4 == 0 and source and result 16-byte aligned -> materialize4p_kernel when HQ >= 256 (the plane on
+#                       blockIdx.y), else materialize4_kernel; otherwise materialize_kernel
+#   launch_upsample2x   W even and >= 8 -> 2^qp threads per output row, qp the least of 2 .. 8 with 2^qp >= 2 W / 4, rpb = 256 >> qp rows
+#                       per block; upsample2x_lds_kernel when qp <= 7, W, sN, sC, sH % 4 == 0, the source 16-byte aligned, 2 H % rpb == 0
+#                       and (128 / 2^qp + 3) W <= 1024, else upsample2x_rows_kernel; W even below 8 -> upsample2x_kernel<4>; W odd -> <2>
+#   launch_avgpool_h    avgpool_h_kernel; a tensor with `post` is refused
+# Every layout of _strides keeps its steps multiples of 4 floats and the hook's buffers are 16-byte aligned, so only `shift` 1 misaligns.
+TENSOR_PASS_CASES = [
+    # materialize
+    _tcase('M1', 'materialize', (2, 5, 6, 12), 'materialize4_kernel', 'pitch', **_tpend(3)),       # HQ = 18; 180 quads: one partial block
+    _tcase('M2', 'materialize', (1, 3, 33, 32), 'materialize4p_kernel', 'band', **_tpend(20)),      # HQ = 264: a ragged second block; three
+                                                                                                    # planes on blockIdx.y
+    _tcase('M3', 'materialize', (2, 2, 32, 32), 'materialize4p_kernel', **_tpend(17)),              # HQ = 256 exactly, the switch point
+    _tcase('M4', 'materialize', (1, 3, 33, 32), 'materialize_kernel', 'band', shift=1, data='M2', **_tpend(20)),    # not 16-byte aligned
+    _tcase('M5', 'materialize', (2, 3, 7, 10), 'materialize_kernel', 'band', **_tpend(4)),          # W % 4 = 2
+    # the H-broadcast of the ASPP pooled branch (Model::run_conv: H = bcastH, sH = 0): aff0 + ReLU, no post, no hsplit
+    _tcase('M6', 'materialize', (2, 4, 1, 16), 'materialize4_kernel', aff0=True, slope=0.0, bcastH=6),      # HQ = 24
+    _tcase('M7', 'materialize', (1, 3, 1, 64), 'materialize4p_kernel', aff0=True, slope=0.0, bcastH=16),    # HQ = 256 with sH = 0
+    # in place, aff0 only, slope 1: Model::separate's magnitude planes
+    _tcase('M8', 'materialize', (1, 2, 9, 20), 'materialize4_kernel', aff0=True, inplace=True),             # HQ = 45
+    _tcase('M9', 'materialize', (1, 2, 16, 64), 'materialize4p_kernel', aff0=True, inplace=True),           # HQ = 256
+    _tcase('M9_out', 'materialize', (1, 2, 16, 64), 'materialize4p_kernel', aff0=True, data='M9'),          # the same, out of place
+    _tcase('M10', 'materialize', (2, 3, 5, 8), 'materialize4_kernel', post=True),                   # post only: no affine, slope 1; HQ = 10
+    _tcase('M11', 'materialize', (1, 2, 4, 6), 'materialize_kernel', slope=0.0),                    # ReLU only, no post; W % 4 = 2
+    # upsample2x
+    _tcase('U1', 'upsample2x', (1, 2, 16, 16), 'upsample2x_lds_kernel', 'pitch', **_tpend(9)),      # qp 3, 32 rows per block: one block per plane
+    _tcase('U2', 'upsample2x', (1, 2, 64, 16), 'upsample2x_lds_kernel', 'band', **_tpend(32)),      # four blocks per plane: hmin / hmax are not
+                                                                                                    # 0 / H - 1; row 32 is block 1's last (hmax)
+    _tcase('U3', 'upsample2x', (1, 2, 12, 40), 'upsample2x_lds_kernel', 'pitch', **_tpend(5)),      # 20 quads: qp 5, 8 rows per block
+    _tcase('U4', 'upsample2x', (1, 1, 4, 256), 'upsample2x_lds_kernel', **_tpend(2)),               # qp 7; (128 / 128 + 3) * 256 = 1024: at the
+                                                                                                    # capacity condition
+    _tcase('U5', 'upsample2x', (1, 2, 16, 16), 'upsample2x_rows_kernel', 'pitch', shift=1, data='U1', **_tpend(9)),     # source not 16-byte aligned
+    _tcase('U6', 'upsample2x', (2, 3, 8, 16), 'upsample2x_rows_kernel', 'pitch', **_tpend(3)),      # 2 H = 16 is no multiple of 32
+    _tcase('U7', 'upsample2x', (1, 2, 8, 10), 'upsample2x_rows_kernel', 'pitch', **_tpend(5)),      # W % 4 = 2; 5 quads on 8 threads: three idle
+    _tcase('U8', 'upsample2x', (1, 1, 2, 260), 'upsample2x_rows_kernel', **_tpend(1)),              # qp 8, the blockIdx.y form; 130 quads on 256 threads
+    _tcase('U9', 'upsample2x', (1, 2, 8, 6), 'upsample2x_kernel<4>', 'band', **_tpend(4)),          # W even below 8
+    _tcase('U10', 'upsample2x', (1, 2, 5, 7), 'upsample2x_kernel<2>', **_tpend(2)),                 # odd W; dense: 14 columns keep float2 stores aligned
+    _tcase('U11', 'upsample2x', (2, 8, 4, 12), 'upsample2x_rows_kernel', aff0=True, slope=0.0, post=True),      # the ASPP bottleneck's form, the
+                                                                                                    # only tensor with post; 2 H = 8 is no multiple of 32
+    # avgpool_h
+    _tcase('A1', 'avgpool_h', (2, 8, 32, 16), 'avgpool_h_kernel', 'pitch', aff0=True, aff1=True, hsplit=13, slope=0.01),
+    _tcase('A2', 'avgpool_h', (1, 5, 3, 9), 'avgpool_h_kernel', 'band', aff0=True, slope=0.0),
+    _tcase('A3', 'avgpool_h', (2, 3, 4, 8), 'avgpool_h_kernel'),
+    _tcase('A4', 'avgpool_h', (2, 3, 4, 8), None, aff0=True, slope=0.0, post=True, refused='avgpool_h: a tensor with a post multiplier'),
+]
+
+
+def tensor_pass_build(case):
+    """The float32 data of a case: the source's backing buffer -- the NaN canary everywhere outside the view, so that a read outside it that
+    reaches an output shows --, its view (off, sN, sC, sH), aff0 / aff1 [C][2] drawn as conv_launch_build draws them, post [N][C] of exact
+    zeros and 1 / 0.9, both present where there are two planes.  Deterministic per `data` name: cases that share it share every value, whatever their layout."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(('tensor_pass ' + case['data']).encode()))
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)                          # noqa: E731
+    aff = lambda C: f32(np.stack([rng.random(C) + 0.5, rng.standard_normal(C) * 0.3], 1))    # noqa: E731
+    N, C, H, W = case['shape']
+    values = f32(rng.standard_normal((N, C, H, W)))
+    a0, a1 = aff(C) if case['aff0'] else None, aff(C) if case['aff1'] else None
+    post = None
+    if case['post']:
+        post = np.where(rng.random((N, C)) < 0.25, 0.0, 1 / 0.9)
+        post.flat[0], post.flat[-1] = 0.0, 1 / 0.9         # (a single plane keeps 1 / 0.9: a zero there would leave nothing to compare)
+        post = f32(post)
+    floats, off, sN, sC, sH = _strides(case['layout'], N, C, H, W)
+    floats, off = floats + case['shift'], off + case['shift']
+    buf = np.full(floats, CANARY_BITS, np.uint32).view(np.float32)
+    buf[view_index(off, sN, sC, sH, N, C, H, W)] = values
+    return dict(name=case['name'], op=case['op'], N=N, C=C, H=H, W=W, buf=buf, off=off, sN=sN, sC=sC, sH=sH, aff0=a0, aff1=a1,
+                hsplit=NO_SPLIT if case['hsplit'] is None else case['hsplit'], slope=float(np.float32(case['slope'])), post=post,
+                bcastH=case['bcastH'], inplace=case['inplace'], kernel=case['kernel'], refused=case['refused'])
+
+
+def tensor_pass_raw(desc):
+    """The source read through its view, float64 [N][C][H][W]."""
+    return np.asarray(desc['buf'], np.float64)[view_index(desc['off'], desc['sN'], desc['sC'], desc['sH'], desc['N'], desc['C'], desc['H'], desc['W'])]
+
+
+def tensor_pass_values(desc):
+    """act(raw * scale + shift) * post in float64 [N][C][H][W], before the op.  The slope and the post values enter as the float32 values
+    the device is given.  Rows >= hsplit with aff1 None are the identity here, as in load_aff of pointwise.hip -- unlike the conv loaders,
+    which fall back to aff0 (conv_launch_input); TENSOR_PASS_CASES holds no such case."""
+    v = activated(tensor_pass_raw(desc), desc['slope'], desc['aff0'], desc['aff1'], desc['hsplit'])
+    if desc['post'] is not None:
+        v = v * np.asarray(desc['post'], np.float64)[:, :, None, None]
+    return v
+
+
+def tensor_pass_ref(desc):
+    """The dense result of the pass in float64: tensor_pass_values, then by op the identity (`bcastH`: the one row repeated over bcastH
+    rows) [N][C][Hv][W], the bilinear x2 with align_corners [N][C][2H][2W], or the mean over H [N][C][W].  See tensor_pass_values for
+    the rows >= hsplit of a tensor without aff1."""
+    v = tensor_pass_values(desc)
+    if desc['op'] == 0:
+        return np.repeat(v, desc['bcastH'], axis=2) if desc['bcastH'] else v
+    if desc['op'] == 1:
+        return upsample2x_align(v)
+    return v.mean(axis=2)

@@ -5,7 +5,8 @@ written a second way, and the conditions the saturated-gate LSTM cases are chose
 tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in float64, over that test's case table; the general
 weight-gradient launch of tests/test_gpu_wgrad_launch.py (`wgrad_launch_ref`) against torch autograd of F.conv2d in float64, over that
 test's case table; the data-gradient launch of tests/test_gpu_dgrad_launch.py (`dgrad_launch_ref`) against torch autograd through
-torch.cat / F.interpolate / expand / F.conv2d in float64, over that test's.  No GPU."""
+torch.cat / F.interpolate / expand / F.conv2d in float64, over that test's; the pass over a pending tensor of
+tests/test_gpu_tensor_pass.py (`tensor_pass_ref`) against the same statement in torch float64, over that test's.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -398,3 +399,121 @@ def test_dgrad_launch_case_table_holds_the_forms_it_is_meant_to():
     assert set(cases['cat3_5_17_10']['runs']) == set(cases['dec_up_skip']['runs']) == set(kr.DGRAD_ALL_MODES)
     assert all(set(c['runs']) == {(3, 1)} for n, c in cases.items() if n not in ('cat3_5_17_10', 'dec_up_skip'))
     assert by['batch_as_h_n3']['N'] == 3 and by['batch_as_h_n4']['N'] == 4 and by['batch_as_h_n3']['Hin'] == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tensor_pass_ref: the reference of tests/test_gpu_tensor_pass.py, over the same case table
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', kr.TENSOR_PASS_CASES, ids=lambda c: c['name'])
+def test_tensor_pass_reference_equals_the_torch_statement_in_float64(case):
+    """The source through an as_strided view, x * scale + shift per row band (rows >= hsplit without aff1: the identity, as load_aff has
+    it), F.leaky_relu, the channel mask, then expand over the broadcast rows, F.interpolate(align_corners=True) or mean(2): 1e-12 of
+    the scale."""
+    F = torch.nn.functional
+    d = kr.tensor_pass_build(case)
+    N, C, H, W = case['shape']
+    v = _torch_view(torch.from_numpy(d['buf']).double(), d, N, C, H, W).clone()
+    assert bool(torch.isfinite(v).all())
+    hs = min(d['hsplit'], H)
+    for aff, rows in ((d['aff0'], slice(0, hs)), (d['aff1'], slice(hs, H))):
+        if aff is not None:
+            a = torch.from_numpy(aff).double()
+            v[:, :, rows] = v[:, :, rows] * a[:, 0].view(1, -1, 1, 1) + a[:, 1].view(1, -1, 1, 1)
+    v = F.leaky_relu(v, float(np.float32(case['slope'])))
+    if d['post'] is not None:
+        v = v * torch.from_numpy(d['post']).double()[:, :, None, None]
+    if d['op'] == 0:
+        want = v.expand(N, C, d['bcastH'], W) if d['bcastH'] else v
+    elif d['op'] == 1:
+        want = F.interpolate(v, scale_factor=2, mode='bilinear', align_corners=True)
+    else:
+        want = v.mean(2)
+    want = want.numpy()
+    got = kr.tensor_pass_ref(d)
+    Hv = d['bcastH'] or H
+    assert got.shape == want.shape == {0: (N, C, Hv, W), 1: (N, C, 2 * H, 2 * W), 2: (N, C, W)}[d['op']]
+    scale = float(np.abs(want).max())
+    assert scale > 0 and float(np.abs(got - want).max()) <= 1e-12 * scale
+
+
+def _tensor_pass_kernel(d):
+    """The dispatch of launch_materialize / launch_upsample2x / launch_avgpool_h of csrc/pointwise.hip, restated on a built case; the hook's
+    buffers are 16-byte aligned, so the view's alignment is its offset's."""
+    W, H = d['W'], d['bcastH'] or d['H']
+    sH = 0 if d['bcastH'] else d['sH']
+    vec = W % 4 == 0 and all(v % 4 == 0 for v in (d['off'], d['sN'], d['sC'], sH))
+    if d['op'] == 0:
+        return ('materialize4p_kernel' if H * (W // 4) >= 256 else 'materialize4_kernel') if vec else 'materialize_kernel'
+    if d['op'] == 1:
+        if W % 2 == 0 and W >= 8:
+            qp = 2
+            while (1 << qp) < 2 * W // 4 and qp < 8:
+                qp += 1
+            lds = qp <= 7 and vec and (2 * H) % (256 >> qp) == 0 and (128 // (1 << qp) + 3) * W <= 1024
+            return 'upsample2x_lds_kernel' if lds else 'upsample2x_rows_kernel'
+        return 'upsample2x_kernel<4>' if W % 2 == 0 else 'upsample2x_kernel<2>'
+    return None if d['post'] is not None else 'avgpool_h_kernel'
+
+
+def test_tensor_pass_case_table_holds_the_forms_it_is_meant_to():
+    """The properties the cases are chosen for, so an edit of the table cannot quietly lose one."""
+    cases = {c['name']: c for c in kr.TENSOR_PASS_CASES}
+    assert len(cases) == len(kr.TENSOR_PASS_CASES)
+    by = {n: kr.tensor_pass_build(c) for n, c in cases.items()}
+    # every kernel of the three launchers is some case's, and each case names the one the dispatch rules give
+    assert {c['kernel'] for c in cases.values() if c['kernel']} == set(kr.TENSOR_PASS_KERNELS)
+    for n, d in by.items():
+        assert d['kernel'] == _tensor_pass_kernel(d), n
+        assert (d['kernel'] is None) == (d['refused'] is not None), n
+        # view_fits' condition; the floats outside the view hold the canary, those inside are finite
+        assert min(d['off'], d['sN'], d['sC'], d['sH']) >= 0 and min(d['N'], d['C'], d['H'], d['W']) >= 1, n
+        assert d['off'] + (d['N'] - 1) * d['sN'] + (d['C'] - 1) * d['sC'] + (d['H'] - 1) * d['sH'] + d['W'] <= d['buf'].size, n
+        assert np.isfinite(kr.tensor_pass_raw(d)).all(), n
+        assert int((d['buf'].view(np.uint32) == kr.CANARY_BITS).sum()) == d['buf'].size - d['N'] * d['C'] * d['H'] * d['W'], n
+        assert d['N'] * d['C'] * (d['bcastH'] or d['H']) * d['W'] <= 2 * 8 * 32 * 16, n
+        # no row band without an affine beside one with (load_aff's identity against the conv loaders' fall-back to aff0)
+        assert d['aff1'] is not None or d['hsplit'] >= d['H'], n
+        if d['post'] is not None:
+            assert set(np.unique(d['post'])) == ({np.float32(0), np.float32(1 / 0.9)} if d['post'].size > 1 else {np.float32(1 / 0.9)}), n
+    pending = lambda d: (d['aff0'] is not None and d['aff1'] is not None and 0 < d['hsplit'] < d['H'] and d['slope'] == float(np.float32(0.01))   # noqa: E731
+                         and d['post'] is not None)
+    for n in ('M1', 'M2', 'M3', 'M4', 'M5', 'U1', 'U2', 'U3', 'U4', 'U5', 'U6', 'U7', 'U8', 'U9', 'U10'):
+        assert pending(by[n]), n
+    hq = lambda d: (d['bcastH'] or d['H']) * (d['W'] // 4)                        # noqa: E731
+    assert [hq(by[n]) for n in ('M1', 'M2', 'M3', 'M7', 'M9')] == [18, 264, 256, 256, 256] and by['M2']['C'] == 3
+    assert by['M1']['N'] * by['M1']['C'] * hq(by['M1']) < 256 and hq(by['M2']) % 256 and by['M3']['hsplit'] == 17
+    # the shifted twins: the same values, the view one float further into a buffer one float longer, nothing else changed
+    for a, b in (('M4', 'M2'), ('U5', 'U1')):
+        assert by[a]['off'] == by[b]['off'] + 1 and by[a]['buf'].size == by[b]['buf'].size + 1 and by[b]['off'] % 4 == 0
+        assert all(by[a][k] == by[b][k] for k in ('sN', 'sC', 'sH', 'hsplit', 'slope'))
+        assert np.array_equal(kr.tensor_pass_ref(by[a]), kr.tensor_pass_ref(by[b]))
+    assert by['M5']['W'] % 4 == 2 and by['M11']['W'] % 4 == 2
+    for n, rows in (('M6', 6), ('M7', 16)):                                      # the ASPP pooled branch's form
+        d = by[n]
+        assert d['bcastH'] == rows and d['H'] == 1 and d['aff0'] is not None and d['aff1'] is None and d['post'] is None and d['slope'] == 0.0
+        assert d['hsplit'] == kr.NO_SPLIT
+    for n in ('M8', 'M9'):                                                       # Model::separate's form
+        d = by[n]
+        assert d['inplace'] and d['off'] == 0 and d['buf'].size == d['N'] * d['C'] * d['H'] * d['W'] and d['slope'] == 1.0
+        assert d['aff0'] is not None and d['aff1'] is None and d['post'] is None
+    assert not by['M9_out']['inplace'] and np.array_equal(by['M9_out']['buf'], by['M9']['buf']) and np.array_equal(by['M9_out']['aff0'], by['M9']['aff0'])
+    d = by['M10']
+    assert d['post'] is not None and d['aff0'] is None and d['aff1'] is None and d['slope'] == 1.0
+    d = by['M11']
+    assert d['post'] is None and d['slope'] == 0.0
+    # upsample: the block geometry of the LDS cases
+    assert (by['U1']['H'], by['U1']['W'], by['U1']['hsplit']) == (16, 16, 9)                     # 2 H = 32 rows = one block
+    assert 2 * by['U2']['H'] // 32 == 4 and by['U2']['W'] == 16
+    assert by['U3']['W'] == 40 and (2 * by['U3']['H']) % 8 == 0
+    assert by['U4']['W'] == 256 and (128 // 128 + 3) * by['U4']['W'] == 1024
+    assert (2 * by['U6']['H']) % 32 and by['U6']['W'] == 16 and by['U7']['W'] % 4 == 2 and by['U8']['W'] == 260
+    assert by['U9']['W'] == 6 and by['U10']['W'] % 2 == 1 and by['U10']['off'] == 0 and by['U10']['sH'] == by['U10']['W']
+    d = by['U11']
+    assert d['post'] is not None and d['aff0'] is not None and d['aff1'] is None and d['slope'] == 0.0 and (d['post'] == 0).any()
+    # avgpool
+    d = by['A1']
+    assert d['aff0'] is not None and d['aff1'] is not None and 0 < d['hsplit'] < d['H'] and d['post'] is None and d['sH'] > d['W']
+    assert by['A2']['aff0'] is not None and by['A2']['slope'] == 0.0 and by['A2']['W'] == 9
+    d = by['A3']
+    assert d['aff0'] is None and d['post'] is None and d['slope'] == 1.0 and d['off'] == 0
+    assert by['A4']['post'] is not None and cases['A4']['refused']

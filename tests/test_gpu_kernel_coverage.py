@@ -11,7 +11,9 @@ heads, the squeeze conv, head_bwd and the crop kernels by test_gpu_heads_lstm.py
 launches, each asserting the kernel it ran, by test_gpu_conv_launch.py; the weight-gradient kernels and the two slab sums, with concatenated
 and strided sources, batch-as-rows, train_winograd 0 and mfma_mode 1, each asserting the instantiation it ran, by test_gpu_wgrad_launch.py;
 the data gradient of a conv record on its three stride-2 paths, with split, strided, stored and accumulated destinations, upsampled and broadcast
-sources and batch-as-rows, each asserting the path and the kernel it ran, by test_gpu_dgrad_launch.py; here only reachability."""
+sources and batch-as-rows, each asserting the path and the kernel it ran, by test_gpu_dgrad_launch.py; the materialize, upsample and
+frequency-pool kernels on pending, strided, broadcast and in-place tensors, each asserting the kernel it ran, by test_gpu_tensor_pass.py;
+here only reachability."""
 import ctypes
 import os
 import shutil

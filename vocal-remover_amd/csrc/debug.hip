@@ -5,7 +5,8 @@
 // its general form -- concatenated strided sources, split strided destinations, a column window -- against oracle/kernel_refs.py
 // (tests/test_gpu_conv_launch.py), and ONE launch_wgrad in its general form plus the two slab sums on synthetic slabs
 // (tests/test_gpu_wgrad_launch.py), and ONE data gradient of a conv record (Model::bwd_conv_dgrad) in the network's forms
-// (tests/test_gpu_dgrad_launch.py).
+// (tests/test_gpu_dgrad_launch.py), and ONE launch_materialize, launch_upsample2x or launch_avgpool_h on a pending, strided tensor
+// (tests/test_gpu_tensor_pass.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -183,6 +184,63 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 accumulate,floats,off                                                                      then vec[1] = what wgrad_reduce_vec chose
 //                 The two slab sums on synthetic slabs: every descriptor once through launch_wgrad_reduce, one by one, and all of them once
 //                 through wred_host + flush_wgrad_sums().  A descriptor sums into the n floats at `off` of its output buffer.
+// tensor_pass     op,N,C,H,W,floats,off, slope            the source's backing buffer, aff0[C][2]|null,       the result, dense and whole (null with inplace); the
+//                 sN,sC,sH,hsplit,                       aff1[C][2]|null, post[N][C]|null                    source's backing buffer as the device left it
+//                 bcastH,inplace
+//                 ONE pass over a pending tensor, on the handle's stream: the view (off, sN, sC, sH) [N][C][H][W] of a backing buffer of
+//                 `floats` floats, uploaded AS GIVEN, with its affines (rows < hsplit take aff0, the others aff1), slope and multiplier.
+//                 op 0: launch_materialize -> [N][C][Hv][W]; with bcastH > 0 the source has H == 1 and the launch gets H = bcastH, sH = 0,
+//                 as Model::run_conv forms it (Hv = bcastH, else H).  op 1: launch_upsample2x -> [N][C][2H][2W].  op 2: launch_avgpool_h
+//                 -> [N][C][W].  The result buffer is 16-byte aligned, filled with the NaN canary 0x7FC12345 and, like the source's, sits
+//                 between guard bands.  inplace 1 (op 0, a dense view at off 0, no bcastH): the launch writes onto the source itself, as
+//                 Model::separate does; the result is then the returned source buffer.  Error -2: a view that leaves its buffer, and
+//                 every refusal of a launcher (message intact; the outputs then hold the buffers as the refused call left them).
+//                 Error -3: a store found in a guard band.
+void Model::debug_tensor_pass(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                              int nout) {
+    const std::string who = "vr_debug_kernel(tensor_pass): ";
+    VR_CHECK(ndims >= 13 && nfp >= 1 && nin >= 4 && nout >= 2, -2, who + "too few arguments");
+    const int op = (int)dims[0], N = (int)dims[1], C = (int)dims[2], H = (int)dims[3], W = (int)dims[4];
+    const long long floats = dims[5], off = dims[6], sN = dims[7], sC = dims[8], sH = dims[9];
+    const int bcastH = (int)dims[11];
+    const bool inplace = dims[12] != 0;
+    VR_CHECK(op >= 0 && op <= 2 && bcastH >= 0 && floats >= 1 && floats <= (1LL << 28), -2, who + "op is 0, 1 or 2; bcastH >= 0");
+    VR_CHECK(in[0] && out[1] && (inplace || out[0]), -2, who + "missing the source buffer or an output");
+    VR_CHECK(view_fits(off, sN, sC, sH, N, C, H, W, (size_t)floats), -2, who + "the source view leaves its buffer");
+    VR_CHECK(!bcastH || (op == 0 && H == 1), -2, who + "a broadcast source is materialised (op 0) and has H = 1");
+    VR_CHECK(!inplace || (op == 0 && !bcastH && off == 0 && sH == W && sC == (long long)H * W && sN == sC * C), -2,
+             who + "in place: op 0 on a dense view at off 0 without bcastH");
+    const int Hv = bcastH ? bcastH : H;
+    const size_t n = op == 0 ? (size_t)N * C * Hv * W : (op == 1 ? (size_t)4 * N * C * H * W : (size_t)N * C * W);
+    VR_CHECK(n <= ((size_t)1 << 28), -2, who + "the result is too large for a test hook");
+    GuardedBuf src(in[0], (size_t)floats);
+    const std::vector<uint32_t> canary(inplace ? 0 : n, 0x7fc12345u);
+    GuardedBuf res(inplace ? nullptr : reinterpret_cast<const float*>(canary.data()), inplace ? 0 : n);
+    DevBuf aff0(in[1], in[1] ? (size_t)C * 2 : 0), aff1(in[2], in[2] ? (size_t)C * 2 : 0), post(in[3], in[3] ? (size_t)N * C : 0);
+    Tensor t;
+    t.p = src.p() + off; t.N = N; t.C = C; t.H = Hv; t.W = W;
+    t.sN = sN; t.sC = sC; t.sH = bcastH ? 0 : sH;
+    t.hsplit = (int)dims[10]; t.slope = fp[0];
+    if (in[1]) t.aff0 = aff0.p;
+    if (in[2]) t.aff1 = aff1.p;
+    if (in[3]) t.post = post.p;
+    float* dst = inplace ? t.p : res.p();
+    try {
+        if (op == 0) launch_materialize(t, dst, stream);
+        else if (op == 1) launch_upsample2x(t, dst, stream);
+        else launch_avgpool_h(t, dst, stream);
+    } catch (...) {                                       // a refusal: the caller still sees what the buffers hold (nothing may have been written)
+        (void)hipStreamSynchronize(stream);
+        if (!inplace) res.download(out[0]);
+        src.download(out[1]);
+        throw;
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+    VR_CHECK(src.intact() && res.intact(), -3, who + "the launch stored outside the result or the source buffer");
+    if (!inplace) res.download(out[0]);
+    src.download(out[1]);
+}
+
 void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin,
                               float* const* out, int nout) {
     const std::string who = "vr_debug_kernel(conv_launch): ";
@@ -551,6 +609,7 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
     if (name == "wgrad_launch") { debug_wgrad_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "wgrad_reduce") { debug_wgrad_reduce(dims, ndims, in, nin, out, nout); return; }
     if (name == "dgrad_launch") { debug_dgrad_launch(dims, ndims, in, nin, out, nout); return; }
+    if (name == "tensor_pass") { debug_tensor_pass(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "bn_backward") {
         need(4, 3, 7, 6);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];

@@ -194,6 +194,8 @@ public:
                             int nout);                    // "wgrad_launch": one launch_wgrad in its general form
     void debug_wgrad_reduce(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "wgrad_reduce"
     void debug_dgrad_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "dgrad_launch"
+    void debug_tensor_pass(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                           int nout);                     // "tensor_pass": one materialize / upsample2x / avgpool_h on a pending tensor
     // ---- signal path ----
     void stft_api(const float* wave, bool on_dev, long long L, float* spec, bool spec_on_dev);
     void istft_api(const float* spec, bool on_dev, int T, float* wave, bool wave_on_dev);

@@ -183,6 +183,8 @@ __global__ void avgpool_h_kernel(Tensor x, float* out) {
 }
 
 void launch_avgpool_h(const Tensor& x, float* out, hipStream_t st) {
+    // (the kernel applies the affine and the activation only; no caller has a multiplier on x5)
+    VR_CHECK(!x.post, -2, "avgpool_h: a tensor with a post multiplier is not supported");
     const int total = x.N * x.C * x.W;
     VR_LAUNCH(avgpool_h_kernel, dim3((total + 255) / 256), dim3(256), 0, st, x, out);
     VR_HIP(hipGetLastError());
@@ -395,7 +397,10 @@ __global__ __launch_bounds__(256) void upsample2x_rows_kernel(Tensor x, float* _
 // LDS form of the row-tiled kernel (round 5): a workgroup makes 256 >> qp consecutive output rows of ONE plane; the source rows under
 // them (at most half as many + 2) are fetched once with aligned 16-byte loads, BatchNorm affine + activation applied on the way in, and
 // every thread then takes its eight source values from LDS -- one global load per thread at most instead of eight 4-byte ones.
-// Same arithmetic, same order as upsample2x_rows_kernel (bit-equal results).  Needs W % 4 == 0, 16-byte aligned rows, 2 H % rows == 0.
+// The same expressions in the same order as upsample2x_rows_kernel, but NOT bit-equal to it: the compiler contracts the interpolation's
+// products and sums into fmas differently in the two kernels (here two packed adds stay uncontracted), also when both inline one shared
+// function for it.  On the same pending 16 x 16 planes one element in six differs, by at most 9.5e-7 at values of a few units
+// (tests/test_gpu_tensor_pass.py holds both to the same float64 bound).  Needs W % 4 == 0, 16-byte aligned rows, 2 H % rows == 0.
 __global__ __launch_bounds__(256) void upsample2x_lds_kernel(Tensor x, float* __restrict__ out, float rh, float rw, int qp_log2) {
     __shared__ __attribute__((aligned(16))) float L[1024];                   // (128 >> qp + 2) rows x W <= 768 floats
     const int W2 = 2 * x.W, H2 = 2 * x.H;
