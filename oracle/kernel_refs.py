@@ -876,3 +876,196 @@ def tensor_pass_ref(desc):
     if desc['op'] == 1:
         return upsample2x_align(v)
     return v.mean(axis=2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The derived weight forms every fast-path launch reads instead of the weights (vr_debug_kernel 'weight_forms' / 'layer_forms'):
+# byte images in the device's layouts, from the K-major weight wk [Cin][KK][CoutPad] float32 (padded output channels zero).
+#   wino      U = G g G^T                      [Cin][16][CoutPad] fp32        conv_wino.hip   wino_weights_kernel
+#   wino6     U as three bf16 planes           [C8/8][16][3][CoutPad][8]      conv_wino.hip   wino_weights6_kernel
+#   x3        w as three bf16 planes           [C8/8][KK][3][CoutPad][8]      conv_x3.hip     x3_weights_kernel
+#   x3h       w as two fp16 planes, scaled per output channel, then winv [CoutPad], wscl [CoutPad] fp32
+#                                              [C8/8][KK][2][CoutPad][8]      conv_x3h.hip    x3h_wscale_kernel + x3h_weights_kernel
+#   flip      wt[co][KK-1-tap][ci] = w[ci][tap][co]                [Cout][KK][CinPad] fp32     backward.hip  flip_transpose_kernel
+#   s2_class  wc[2 ph + pw][co][3 th + tw][ci] = w[ci][3 kh + kw][co], parity 0: t = 1 <- k = 1; parity 1: t = 1 <- k = 2, t = 2 <- k = 0,
+#             every other tap 0                                    [4][Cout][9][CinPad] fp32  backward.hip  s2_class_weights_kernel
+# C8 = Cin rounded up to 8 (channels >= Cin are +0), CinPad / CoutPad = rounded up to 32.  Inf and NaN weights are out of scope.
+# ---------------------------------------------------------------------------------------------------------------------------------
+WEIGHT_FORMS = {'wino': 0, 'wino6': 1, 'x3': 2, 'x3h': 3, 'flip': 4, 's2_class': 5}
+WEIGHT_FORM_CIN = (1, 2, 7, 8, 9, 20, 33)
+WEIGHT_FORM_COUT = (1, 8, 33, 96)
+# one batched launch: five descriptors of different sizes, the smallest next to the largest and not first
+WEIGHT_FORM_BATCH = ((7, 8), (20, 33), (2, 1), (33, 96), (9, 33))
+WINO_G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def round_up(v, m):
+    return (v + m - 1) // m * m
+
+
+def weight_form_values(Cin, Cout, KK, seed):
+    """OIHW float32 weights whose output channel co plays the role co % 9 (a channel's scale matters to x3h, its values to every form):
+    0 unit normal times 2^k, k spread over [-20, 20];  1 all zero;  2 maximum exactly 2^k;  3 maximum the float just below 2^k;
+    4 one weight of 2^20 among weights of +-2^-20;  5 the maximum negative (a negative power of two for every other such channel);
+    6 subnormals only;  7 the largest finite float at (ci 0, tap 0) among unit normals;  8 magnitudes 2^-112 .. 2^-88, around the 2^-100
+    below which three bf16 planes no longer hold a float32."""
+    rng = np.random.default_rng(seed)
+    KS = 3 if KK == 9 else 1
+    n = Cin * KK
+    w = np.zeros((Cout, n), np.float32)
+    for co in range(Cout):
+        role, k = co % 9, (co // 9 * 7 + co) % 41 - 20
+        v = rng.standard_normal(n)
+        if role == 0:
+            v = np.ldexp(v, k)
+        elif role == 1:
+            v = np.zeros(n)
+        elif role in (2, 3, 5):
+            v = np.ldexp(rng.uniform(-0.9, 0.9, n), k)
+            top = np.float32(2.0 ** k)
+            if role == 3:
+                top = np.nextafter(top, np.float32(0))
+            if role == 5:
+                top = -top if co // 9 % 2 == 0 else -np.float32(1.37 * 2.0 ** k)
+            v[rng.integers(n)] = top
+        elif role == 4:
+            v = np.where(v < 0, -1.0, 1.0) * 2.0 ** -20
+            v[rng.integers(n)] = 2.0 ** 20
+        elif role == 6:
+            v = np.where(v < 0, -1.0, 1.0) * rng.integers(1, 2 ** 23, n) * 2.0 ** -149
+        elif role == 7:
+            v[0] = FLT_MAX
+        else:
+            v = np.ldexp(v, rng.integers(-112, -87, n))
+        w[co] = v.astype(np.float32)
+    return w.reshape(Cout, Cin, KS, KS)
+
+
+def weight_kmajor(w, CoutPad=None):
+    """OIHW -> the device's K-major [Cin][KK][CoutPad], padded output channels zero (Model::set_param)."""
+    Cout, Cin = w.shape[:2]
+    KK = w.shape[2] * w.shape[3]
+    wk = np.zeros((Cin, KK, CoutPad or round_up(Cout, 32)), np.float32)
+    wk[:, :, :Cout] = np.asarray(w, np.float32).reshape(Cout, Cin, KK).transpose(1, 2, 0)
+    return wk
+
+
+def wino_ref(wk):
+    """(U, A) float64 [Cin][16][CoutPad]: U = G g G^T and A = |G| |g| |G|^T, what the rounding bound of U is stated in."""
+    Cin, _, CP = wk.shape
+    g = np.asarray(wk, np.float64).reshape(Cin, 3, 3, CP)
+    U = np.einsum('ri,cijo,sj->crso', WINO_G, g, WINO_G).reshape(Cin, 16, CP)
+    A = np.einsum('ri,cijo,sj->crso', np.abs(WINO_G), np.abs(g), np.abs(WINO_G)).reshape(Cin, 16, CP)
+    return U, A
+
+
+def wino_f32(wk):
+    """U in float32 in the kernels' order of operations: 0.5 * ((a +- b) + c) down the rows, then along the columns."""
+    Cin, _, CP = wk.shape
+    g = np.asarray(wk, np.float32).reshape(Cin, 3, 3, CP)
+    h = np.float32(0.5)
+
+    def gmul(a, ax):
+        a0, a1, a2 = (np.take(a, i, axis=ax) for i in range(3))
+        return np.stack([a0, h * ((a0 + a1) + a2), h * ((a0 - a1) + a2), a2], axis=ax)
+    return gmul(gmul(g, 1), 2).reshape(Cin, 16, CP)
+
+
+def bf16_bits(v):
+    """float32 -> bfloat16 bits (uint16), round to nearest even on the uint32 bits.  A finite value that would round to infinity
+    (|v| > 2^128 - 2^119) takes the largest finite bfloat16 instead, so that the three planes of every finite float32 stay finite."""
+    b = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    r = ((b + np.uint32(0x7fff) + ((b >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    over = ((r & 0x7f80) == 0x7f80) & ((b & np.uint32(0x7f800000)) != np.uint32(0x7f800000))
+    return np.where(over, r - np.uint16(1), r).astype(np.uint16)
+
+
+def bf16_value(p):
+    return (np.ascontiguousarray(p, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def bf16_split3_ref(v):
+    """p1 = bf16(v), p2 = bf16(v - p1), p3 = bf16(v - p1 - p2) as uint16 bits; both float32 subtractions are exact."""
+    v = np.ascontiguousarray(v, np.float32)
+    p1 = bf16_bits(v)
+    r1 = v - bf16_value(p1)
+    p2 = bf16_bits(r1)
+    p3 = bf16_bits(r1 - bf16_value(p2))
+    return p1, p2, p3
+
+
+def _pad8(a):
+    """[C][K][CP] -> [C8][K][CP], the channels >= C +0"""
+    out = np.zeros((round_up(a.shape[0], 8),) + a.shape[1:], a.dtype)
+    out[:a.shape[0]] = a
+    return out
+
+
+def plane_image(planes):
+    """planes of [C8][K][CP] -> the device's [C8/8][K][plane][CP][8 channels]"""
+    a = np.stack(planes, 0)
+    P, C8, K, CP = a.shape
+    return np.ascontiguousarray(a.reshape(P, C8 // 8, 8, K, CP).transpose(1, 3, 0, 4, 2))
+
+
+def plane_unimage(img):
+    """the inverse of plane_image: [C8/8][K][P][CP][8] -> [P][C8][K][CP]"""
+    c, K, P, CP, _ = img.shape
+    return np.ascontiguousarray(img.transpose(2, 0, 4, 1, 3)).reshape(P, c * 8, K, CP)
+
+
+def x3_ref(wk):
+    """the x3 image (uint16): the three bf16 planes of w; wino6 is the same function of U [Cin][16][CoutPad] float32"""
+    return plane_image(bf16_split3_ref(_pad8(np.asarray(wk, np.float32))))
+
+
+def x3h_ref(wk):
+    """(planes float16 [C8/8][KK][2][CoutPad][8], winv [CoutPad], wscl [CoutPad] float32).  e = the biased exponent of the channel's
+    max |w|, clamped to [15, 254]; wscl = 2^(141 - e) puts that maximum into [2^14, 2^15); h1 = fp16(v wscl), h2 = fp16(v wscl - h1).
+    v wscl and the residual are exact in float64 and, unless they underflow float32 (and then both planes are zero), in float32."""
+    wk = np.asarray(wk, np.float32)
+    m = np.abs(wk).max(axis=(0, 1))
+    e = np.clip((m.view(np.uint32) >> np.uint32(23)).astype(np.int64), 15, 254)
+    wscl, winv = np.ldexp(1.0, 141 - e).astype(np.float32), np.ldexp(1.0, e - 141).astype(np.float32)
+    p = _pad8(wk).astype(np.float64) * wscl.astype(np.float64)
+    h1 = p.astype(np.float32).astype(np.float16)
+    h2 = (p - h1.astype(np.float64)).astype(np.float32).astype(np.float16)
+    return plane_image((h1, h2)), winv, wscl
+
+
+def x3h_unpack(words, Cin, KK, CoutPad):
+    """A device x3h buffer (float32 words, sized as the three-plane x3 buffer) -> (planes float16, winv, wscl, the unread rest as uint32)."""
+    c8 = round_up(Cin, 8) // 8
+    n = c8 * KK * 2 * CoutPad * 4                      # words of the two planes
+    words = np.ascontiguousarray(words, np.float32).reshape(-1)
+    planes = words[:n].view(np.float16).reshape(c8, KK, 2, CoutPad, 8)
+    return planes, words[n:n + CoutPad], words[n + CoutPad:n + 2 * CoutPad], words[n + 2 * CoutPad:].view(np.uint32)
+
+
+def flip_ref(wk, Cout, fill=0.0):
+    """wt [Cout][KK][CinPad] float32; the padding ci >= Cin, which the kernel does not write, holds `fill`."""
+    Cin, KK, _ = wk.shape
+    wt = np.full((Cout, KK, round_up(Cin, 32)), fill, np.float32)
+    wt[:, :, :Cin] = np.asarray(wk, np.float32)[:, ::-1, :Cout].transpose(2, 1, 0)
+    return wt
+
+
+def s2_class_ref(wk, Cout):
+    """wc [4][Cout][9][CinPad] float32: the stride-1 weights over dz of the four output parities of a 3x3 stride-2 conv's data gradient."""
+    Cin = wk.shape[0]
+    wc = np.zeros((4, Cout, 9, round_up(Cin, 32)), np.float32)
+    taps = ({1: 1}, {1: 2, 2: 0})                      # parity -> {tap of the class conv: tap of the forward conv}
+    for ph in range(2):
+        for pw in range(2):
+            for th, kh in taps[ph].items():
+                for tw, kw in taps[pw].items():
+                    wc[2 * ph + pw, :, 3 * th + tw, :Cin] = np.asarray(wk, np.float32)[:, 3 * kh + kw, :Cout].T
+    return wc
+
+
+def weight_form_words(form, Cin, Cout, KK):
+    """float32 words of a form's buffer, as the library sizes it (x3_weights_bytes, wino_weights6_bytes, ...)"""
+    CP, CinPad, c8 = round_up(Cout, 32), round_up(Cin, 32), round_up(Cin, 8) // 8
+    return {'wino': Cin * 16 * CP, 'wino6': c8 * 48 * CP * 4, 'x3': c8 * KK * 3 * CP * 4, 'x3h': c8 * KK * 3 * CP * 4,
+            'flip': Cout * KK * CinPad, 's2_class': 4 * Cout * 9 * CinPad}[form]

@@ -6,7 +6,9 @@ tests/test_gpu_conv_launch.py (`conv_launch_ref`) against torch's own modules in
 weight-gradient launch of tests/test_gpu_wgrad_launch.py (`wgrad_launch_ref`) against torch autograd of F.conv2d in float64, over that
 test's case table; the data-gradient launch of tests/test_gpu_dgrad_launch.py (`dgrad_launch_ref`) against torch autograd through
 torch.cat / F.interpolate / expand / F.conv2d in float64, over that test's; the pass over a pending tensor of
-tests/test_gpu_tensor_pass.py (`tensor_pass_ref`) against the same statement in torch float64, over that test's.  No GPU."""
+tests/test_gpu_tensor_pass.py (`tensor_pass_ref`) against the same statement in torch float64, over that test's; the derived weight forms of
+tests/test_gpu_weight_forms.py (`wino_ref`, `flip_ref`, `s2_class_ref`) against F.conv2d and torch autograd in float64, the split forms
+(`bf16_split3_ref`, `x3h_ref`) against the reconstruction they promise, over that test's value table.  No GPU."""
 import numpy as np
 import pytest
 import torch
@@ -517,3 +519,128 @@ def test_tensor_pass_case_table_holds_the_forms_it_is_meant_to():
     d = by['A3']
     assert d['aff0'] is None and d['post'] is None and d['slope'] == 1.0 and d['off'] == 0
     assert by['A4']['post'] is not None and cases['A4']['refused']
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the derived weight forms (tests/test_gpu_weight_forms.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _unit_weights(Cin, Cout, KS, seed):
+    return np.random.default_rng(seed).standard_normal((Cout, Cin, KS, KS)).astype(np.float32)
+
+
+def test_winograd_conv_with_wino_ref_equals_conv2d():
+    """F(2x2, 3x3): Y = A^T [sum_ci U . (B^T d B)] A over 4x4 tiles at stride 2 of the zero-padded input, U from wino_ref."""
+    Cin, Cout, H, W = 5, 7, 6, 8
+    w = _unit_weights(Cin, Cout, 3, 0)
+    U = kr.wino_ref(kr.weight_kmajor(w))[0][:, :, :Cout].reshape(Cin, 4, 4, Cout)
+    x = np.random.default_rng(1).standard_normal((2, Cin, H, W))
+    BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64)
+    AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)
+    xp = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)))
+    y = np.zeros((2, Cout, H, W))
+    for i in range(0, H, 2):
+        for j in range(0, W, 2):
+            V = np.einsum('ra,ncab,sb->ncrs', BT, xp[:, :, i:i + 4, j:j + 4], BT)
+            y[:, :, i:i + 2, j:j + 2] = np.einsum('pr,nors,qs->nopq', AT, np.einsum('ncrs,crso->nors', V, U), AT)
+    want = torch.nn.functional.conv2d(torch.from_numpy(x), torch.from_numpy(w).double(), padding=1).numpy()
+    assert np.abs(y - want).max() <= 1e-12 * np.abs(want).max()
+
+
+@pytest.mark.parametrize('KS', [3, 1])
+def test_conv_with_flip_ref_equals_the_autograd_data_gradient(KS):
+    Cin, Cout, H, W = 5, 7, 6, 9
+    w = _unit_weights(Cin, Cout, KS, 2)
+    x = torch.randn(2, Cin, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(3), requires_grad=True)
+    dz = torch.randn(2, Cout, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(4))
+    torch.nn.functional.conv2d(x, torch.from_numpy(w).double(), padding=KS // 2).backward(dz)
+    wt = kr.flip_ref(kr.weight_kmajor(w), Cout, fill=np.nan)                      # [Cout][KK][CinPad]
+    assert np.isnan(wt[:, :, Cin:]).all() and wt.shape == (Cout, KS * KS, 32)
+    wd = np.ascontiguousarray(wt[:, :, :Cin].transpose(2, 0, 1)).reshape(Cin, Cout, KS, KS)      # read as OIHW of the gradient conv
+    got = torch.nn.functional.conv2d(dz, torch.from_numpy(wd).double(), padding=KS // 2)
+    assert float((got - x.grad).abs().max()) <= 1e-12 * float(x.grad.abs().max())
+
+
+@pytest.mark.parametrize('H,W', [(8, 6), (7, 6), (8, 5), (7, 5)])
+def test_four_class_convs_with_s2_class_ref_equal_the_stride2_data_gradient(H, W):
+    """dx[.., 2 j + ph, 2 i + pw] = the stride-1 conv of dz with class 2 ph + pw.  Odd H and W are covered: the odd parity then has one row /
+    column fewer than dz, and the class conv's last one is dropped."""
+    Cin, Cout = 5, 7
+    w = _unit_weights(Cin, Cout, 3, 5)
+    x = torch.randn(2, Cin, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(6), requires_grad=True)
+    z = torch.nn.functional.conv2d(x, torch.from_numpy(w).double(), padding=1, stride=2)
+    dz = torch.randn(z.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(7))
+    z.backward(dz)
+    wc = kr.s2_class_ref(kr.weight_kmajor(w), Cout)                               # [4][Cout][9][CinPad]
+    assert wc.shape == (4, Cout, 9, 32) and not wc[:, :, :, Cin:].any()
+    got = torch.zeros_like(x.grad)
+    for cls in range(4):
+        wd = np.ascontiguousarray(wc[cls, :, :, :Cin].transpose(2, 0, 1)).reshape(Cin, Cout, 3, 3)
+        part = torch.nn.functional.conv2d(dz, torch.from_numpy(wd).double(), padding=1)
+        view = got[:, :, cls >> 1::2, cls & 1::2]
+        view.copy_(part[:, :, :view.shape[2], :view.shape[3]])
+    assert float((got - x.grad).abs().max()) <= 1e-12 * float(x.grad.abs().max())
+
+
+def _value_tables():
+    for Cin, Cout, KK in ((1, 33, 1), (9, 33, 9), (33, 96, 9), (20, 96, 1)):
+        yield Cin, Cout, KK, kr.weight_kmajor(kr.weight_form_values(Cin, Cout, KK, seed=Cin + Cout))
+
+
+def test_value_table_holds_every_role():
+    wk = kr.weight_kmajor(kr.weight_form_values(9, 33, 9, seed=0))
+    m = np.abs(wk).max(axis=(0, 1))
+    assert m[1] == 0 and m[33:].max() == 0                                        # an all-zero channel; the padded ones
+    assert np.log2(float(m[2])) % 1 == 0 and np.log2(float(np.nextafter(m[3], np.float32(np.inf)))) % 1 == 0
+    assert sorted(set(np.abs(wk[:, :, 4]).ravel())) == [np.float32(2.0 ** -20), np.float32(2.0 ** 20)]
+    assert wk[:, :, 5].ravel()[np.abs(wk[:, :, 5]).argmax()] < 0 and wk[:, :, 14].ravel()[np.abs(wk[:, :, 14]).argmax()] < 0
+    assert 0 < m[6] < 2.0 ** -126 and (wk[:, :, 6] != 0).all()
+    assert wk[0, 0, 7] == kr.FLT_MAX
+    assert 2.0 ** -113 < m[8] < 2.0 ** -87
+
+
+def test_bf16_split3_ref_reconstructs_every_table_value_exactly():
+    """p1 + p2 + p3 == v in float64 where |v| >= 2^-100 or v == 0 (below, the third plane's last bits fall under bfloat16's range); every
+    plane is finite, the largest finite float included (bf16_bits saturates where round-to-nearest would give infinity)."""
+    for Cin, Cout, KK, wk in _value_tables():
+        v = wk.astype(np.float64)
+        planes = [kr.bf16_value(p).astype(np.float64) for p in kr.bf16_split3_ref(wk)]
+        s = planes[0] + planes[1] + planes[2]
+        assert all(np.isfinite(p).all() for p in planes)
+        ok = (np.abs(v) >= 2.0 ** -100) | (v == 0)
+        assert ok.sum() > 0.8 * ok.size and (~ok).sum() > 0
+        assert np.array_equal(s[ok], v[ok])
+        assert (np.abs(s - v)[~ok] <= 2.0 ** -134).all()                          # half of bfloat16's smallest subnormal
+    # round to nearest EVEN on the bits, against torch's conversion, where no saturation is involved
+    x = np.random.default_rng(0).standard_normal(4096).astype(np.float32)
+    x[:4] = np.array([1.00390625, 1.01171875, -1.00390625, 0.0], np.float32)      # ties: to even down, to even up
+    want = torch.from_numpy(x).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    assert np.array_equal(kr.bf16_bits(x), want)
+    assert kr.bf16_bits(np.array([kr.FLT_MAX, -kr.FLT_MAX], np.float32)).tolist() == [0x7f7f, 0xff7f]
+
+
+def test_x3h_ref_meets_the_reconstruction_bound_on_the_value_table():
+    """|h1 + h2 - v wscl| <= 2^-22 |v wscl| + 2^-25 (11 significant bits per plane, half of fp16's smallest subnormal), |h1| <= 32768,
+    wscl winv == 1, and the scaled channel maximum lies in [2^14, 2^15) unless the exponent clamp holds it lower."""
+    for Cin, Cout, KK, wk in _value_tables():
+        planes, winv, wscl = kr.x3h_ref(wk)
+        h = kr.plane_unimage(planes).astype(np.float64)
+        t = kr._pad8(wk).astype(np.float64) * wscl.astype(np.float64)
+        assert np.isfinite(h).all() and np.abs(h[0]).max() <= 32768
+        assert (np.abs(h[0] + h[1] - t) <= 2.0 ** -22 * np.abs(t) + 2.0 ** -25).all()
+        assert np.array_equal(wscl.astype(np.float64) * winv.astype(np.float64), np.ones(wk.shape[2]))
+        m = np.abs(t).max(axis=(0, 1))
+        normal = np.abs(wk).max(axis=(0, 1)) >= 2.0 ** -112                        # biased exponent >= 15
+        assert ((m[normal] >= 2.0 ** 14) & (m[normal] < 2.0 ** 15)).all() and (m[~normal] < 2.0 ** 14).all()
+        assert not h[:, Cin:].any() and not np.signbit(h[:, Cin:]).any()            # padded channels: +0
+
+
+def test_wino_f32_stays_inside_the_bound_of_wino_ref():
+    """The float32 U in the kernels' order of operations against the float64 one: 8 u A with A = |G| |g| |G|^T; where A < 2^-100 float32
+    can underflow and 2^-148 is added (four roundings of at most half the smallest subnormal each, through coefficients <= 1)."""
+    for Cin, Cout, KK, wk in _value_tables():
+        if KK != 9:
+            continue
+        U, A = kr.wino_ref(wk)
+        err = np.abs(kr.wino_f32(wk).astype(np.float64) - U)
+        big = A >= 2.0 ** -100
+        assert (err <= 8 * 2.0 ** -24 * A + np.where(big, 0.0, 2.0 ** -148)).all() and big.any() and not big.all()

@@ -13,7 +13,9 @@ and strided sources, batch-as-rows, train_winograd 0 and mfma_mode 1, each asser
 the data gradient of a conv record on its three stride-2 paths, with split, strided, stored and accumulated destinations, upsampled and broadcast
 sources and batch-as-rows, each asserting the path and the kernel it ran, by test_gpu_dgrad_launch.py; the materialize, upsample and
 frequency-pool kernels on pending, strided, broadcast and in-place tensors, each asserting the kernel it ran, by test_gpu_tensor_pass.py;
-here only reachability."""
+the derived weight forms all of those launches read (wino_weights, wino_weights6, x3_weights, x3h_wscale / x3h_weights and their batched
+kernels, flip_transpose, s2_class_weights), bit for bit against numpy and through every route that refreshes them in a live handle, by
+test_gpu_weight_forms.py; here only reachability."""
 import ctypes
 import os
 import shutil

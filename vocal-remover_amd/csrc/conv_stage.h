@@ -58,6 +58,18 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, int& p1, int& p2
     v[1] -= __int_as_float(p2 & (int)0xffff0000);
     p3 = __builtin_bit_cast(int, __builtin_convertvector(v, vr_bf16x2));
 }
+// The split of one WEIGHT (the refresh kernels x3_weights_elem and wino_weights6_elem, not the loaders): as split3_pair's first value, but
+// a finite x that bf16 rounds to infinity (|x| > 2^128 - 2^119) takes the largest finite bf16 as its first plane.  The planes then stay
+// finite and still sum to x exactly; rounded, they are +Inf, -Inf and NaN (tests/test_gpu_weight_forms.py).
+__device__ __forceinline__ void split3_weight(float x, int& p1, int& p2, int& p3) {
+    split3_pair(x, 0.f, p1, p2, p3);
+    if ((p1 & 0x7f80) == 0x7f80 && (__float_as_int(x) & 0x7f800000) != 0x7f800000) {
+        int q2, q3;
+        p1 = (p1 & 0xffff) - 1;
+        split3_pair(x - __int_as_float(p1 << 16), 0.f, p2, q2, q3);
+        p3 = q2;                                              // (the rest after two planes: its first plane is the third of x)
+    }
+}
 __device__ __forceinline__ f32x16 mfma_bf16x16(vr_bf16x8 a, vr_bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }

@@ -441,7 +441,7 @@ __device__ __forceinline__ void wino_weights6_elem(const float* __restrict__ w, 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             int p1, p2, p3;
-            split3_pair(u[c], 0.f, p1, p2, p3);
+            split3_weight(u[c], p1, p2, p3);
             const long long f = r * 4 + c;
             o[(f * 3 + 0) * CoutPad * 8] = (unsigned short)(p1 & 0xffff);
             o[(f * 3 + 1) * CoutPad * 8] = (unsigned short)(p2 & 0xffff);

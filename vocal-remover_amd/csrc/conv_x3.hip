@@ -443,7 +443,7 @@ __device__ __forceinline__ void x3_weights_elem(const float* __restrict__ w, uns
     const int ci = (int)(gid / ((long long)CoutPad * KK));
     const float v = ci < Cin ? w[((long long)ci * KK + t) * CoutPad + co] : 0.f;
     int p1, p2, p3;
-    split3_pair(v, 0.f, p1, p2, p3);
+    split3_weight(v, p1, p2, p3);
     unsigned short* q = o + ((((long long)(ci >> 3) * KK + t) * 3) * CoutPad + co) * 8 + (ci & 7);
     q[0] = (unsigned short)(p1 & 0xffff);
     q[(long long)CoutPad * 8] = (unsigned short)(p2 & 0xffff);

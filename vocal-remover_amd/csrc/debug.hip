@@ -6,7 +6,8 @@
 // (tests/test_gpu_conv_launch.py), and ONE launch_wgrad in its general form plus the two slab sums on synthetic slabs
 // (tests/test_gpu_wgrad_launch.py), and ONE data gradient of a conv record (Model::bwd_conv_dgrad) in the network's forms
 // (tests/test_gpu_dgrad_launch.py), and ONE launch_materialize, launch_upsample2x or launch_avgpool_h on a pending, strided tensor
-// (tests/test_gpu_tensor_pass.py).
+// (tests/test_gpu_tensor_pass.py), and the derived weight forms those launches read -- one form of given weights through its single-layer and
+// its batched launcher, and what a live handle holds for a layer (tests/test_gpu_weight_forms.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -196,6 +197,168 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 Model::separate does; the result is then the returned source buffer.  Error -2: a view that leaves its buffer, and
 //                 every refusal of a launcher (message intact; the outputs then hold the buffers as the refused call left them).
 //                 Error -3: a store found in a guard band.
+// weight_forms    form,nd; per           -                per descriptor: w[Cout][Cin][KS][KS] (OIHW)         per descriptor: the form's buffer, whole, as float32
+//                 descriptor Cin,Cout,KK                                                                     words, after the single-layer launcher (null: skipped),
+//                                                                                                            then the same after the batched launch
+//                 ONE derived weight form (0 wino, 1 wino6, 2 x3, 3 x3h, 4 flip, 5 s2_class; oracle/kernel_refs.py states each) of nd
+//                 layers, from their K-major copies [Cin][KK][CoutPad] with zeroed padded couts, on the handle's stream: once per
+//                 descriptor through launch_wino_weights / launch_wino_weights6 / launch_x3_weights / launch_x3h_weights (flip and
+//                 s2_class exist only in batched form: a table of one descriptor), and once for all descriptors in ONE launch of the
+//                 batched launcher, its grid sized as Model::run_wino_batch / run_x3_batch / ensure_train_state size it.  Every buffer has
+//                 the size the library gives it (x3_weights_bytes, wino_weights6_bytes, Cin 16 CoutPad, Cout KK CinPad, 4 Cout 9
+//                 CinPad), is filled with the NaN canary 0x7FC12345 and sits between guard bands.  Error -3: a store found in a guard band.
+// layer_forms     i[,capacity]           -                -                                                   i = -1: out[0] = the layer count, then per conv in
+//                                                                                                            for_each_conv's order Cin, Cout, KS, stride, dh, dw,
+//                                                                                                            mask (`capacity` floats); else the K-major weights
+//                                                                                                            [Cin][KK][CoutPad], then the buffers of the mask
+//                 What the handle holds for conv i, read-only, after the handle's stream has drained.  Mask bits and outputs 1..9 in this
+//                 order: L.wino [Cin][16][CoutPad], L.wino6, L.x3w (x3_weights_bytes(Cin, KK, CoutPad)), wt_of [Cout][KK][CinPad], winot_of
+//                 [Cout][16][CinPad], winot6_of, x3t_of and x3dt_of (x3_weights_bytes(Cout, KK, CinPad)), s2w_of [4][Cout][9][CinPad].  A
+//                 null output is skipped; an output for a buffer the handle does not hold is error -2.  A set bit says that the buffer
+//                 exists, not that the current mfma_mode fills it.
+namespace {
+
+constexpr uint32_t FORM_CANARY = 0x7fc12345u;
+
+template <class D>
+struct DevTable {                                         // a descriptor table of a batched launch
+    D* p = nullptr;
+    explicit DevTable(const std::vector<D>& v) {
+        VR_HIP(hipMalloc(reinterpret_cast<void**>(&p), v.size() * sizeof(D)));
+        VR_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(D), hipMemcpyHostToDevice));
+    }
+    ~DevTable() { (void)hipFree(p); }
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+};
+
+int round32(int v) { return (v + 31) / 32 * 32; }
+
+}  // namespace
+
+void Model::debug_weight_form_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout) {
+    const std::string who = "vr_debug_kernel(weight_forms): ";
+    VR_CHECK(ndims >= 2, -2, who + "too few arguments");
+    const int form = (int)dims[0], nd = (int)dims[1];
+    VR_CHECK(form >= 0 && form <= 5 && nd >= 1 && nd <= 64 && ndims >= 2 + 3 * nd && nin >= nd && nout >= 2 * nd, -2,
+             who + "form 0..5, 1..64 descriptors of three dims each, two outputs per descriptor");
+    std::vector<std::unique_ptr<DevBuf>> wk;
+    std::vector<std::unique_ptr<GuardedBuf>> one, bat;
+    std::vector<WinoWDesc> wd;
+    std::vector<X3WDesc> xd;
+    std::vector<FlipDesc> fd;
+    std::vector<S2WDesc> sd;
+    for (int j = 0; j < nd; ++j) {
+        const int Cin = (int)dims[2 + 3 * j], Cout = (int)dims[3 + 3 * j], KK = (int)dims[4 + 3 * j];
+        VR_CHECK(Cin >= 1 && Cin <= 4096 && Cout >= 1 && Cout <= 4096 && (KK == 9 || (KK == 1 && (form == 2 || form == 3 || form == 4))), -2,
+                 who + "1..4096 channels; KK is 9, or 1 for x3, x3h and flip");
+        VR_CHECK(in[j] && out[nd + j], -2, who + "a descriptor needs its weights and its batched output");
+        const int CoutPad = round32(Cout), CinPad = round32(Cin);
+        std::vector<float> h((size_t)Cin * KK * CoutPad, 0.f);
+        for (int co = 0; co < Cout; ++co)
+            for (int ci = 0; ci < Cin; ++ci)
+                for (int k = 0; k < KK; ++k) h[((size_t)ci * KK + k) * CoutPad + co] = in[j][((size_t)co * Cin + ci) * KK + k];
+        wk.emplace_back(new DevBuf(h.data(), h.size()));
+        const float* w = wk.back()->p;
+        const size_t words = form == 0 ? (size_t)Cin * 16 * CoutPad
+                           : form == 1 ? wino_weights6_bytes(Cin, CoutPad) / 4
+                           : form <= 3 ? x3_weights_bytes(Cin, KK, CoutPad) / 4
+                           : form == 4 ? (size_t)Cout * KK * CinPad : (size_t)4 * Cout * 9 * CinPad;
+        const std::vector<uint32_t> canary(words, FORM_CANARY);
+        one.emplace_back(new GuardedBuf(reinterpret_cast<const float*>(canary.data()), words));
+        bat.emplace_back(new GuardedBuf(reinterpret_cast<const float*>(canary.data()), words));
+        float* o1 = one.back()->p();
+        float* ob = bat.back()->p();
+        switch (form) {
+        case 0: launch_wino_weights(w, o1, Cin, CoutPad, stream); wd.push_back(WinoWDesc{w, ob, Cin, CoutPad}); break;
+        case 1: launch_wino_weights6(w, o1, Cin, CoutPad, stream); wd.push_back(WinoWDesc{w, ob, Cin, CoutPad}); break;
+        case 2: launch_x3_weights(w, o1, Cin, KK, CoutPad, stream); xd.push_back(X3WDesc{w, ob, Cin, KK, CoutPad}); break;
+        case 3: launch_x3h_weights(w, o1, Cin, KK, CoutPad, stream); xd.push_back(X3WDesc{w, ob, Cin, KK, CoutPad}); break;
+        case 4: {
+            const std::vector<FlipDesc> t{FlipDesc{w, o1, Cin, Cout, KK, CinPad, CoutPad}};
+            DevTable<FlipDesc> dt(t);
+            launch_flip_transpose(dt.p, 1, stream);
+            VR_HIP(hipStreamSynchronize(stream));             // (the table is freed at the brace)
+            fd.push_back(FlipDesc{w, ob, Cin, Cout, KK, CinPad, CoutPad});
+            break;
+        }
+        default: {
+            const std::vector<S2WDesc> t{S2WDesc{w, o1, Cin, Cout, CoutPad, CinPad}};
+            DevTable<S2WDesc> dt(t);
+            launch_s2_class_weights(dt.p, 1, s2w_batch_max_elems(t), stream);
+            VR_HIP(hipStreamSynchronize(stream));
+            sd.push_back(S2WDesc{w, ob, Cin, Cout, CoutPad, CinPad});
+            break;
+        }
+        }
+    }
+    // all descriptors in ONE launch of the batched launcher
+    if (form <= 1) {
+        DevTable<WinoWDesc> dt(wd);
+        launch_wino_weights_batched(dt.p, nd, wino_batch_max_elems(wd, form == 1), form == 1, stream);
+        VR_HIP(hipStreamSynchronize(stream));
+    } else if (form <= 3) {
+        DevTable<X3WDesc> dt(xd);
+        if (form == 3) launch_x3h_weights_batched(dt.p, nd, x3_batch_max_elems(xd), x3_batch_max_cout_pad(xd), stream);
+        else launch_x3_weights_batched(dt.p, nd, x3_batch_max_elems(xd), stream);
+        VR_HIP(hipStreamSynchronize(stream));
+    } else if (form == 4) {
+        DevTable<FlipDesc> dt(fd);
+        launch_flip_transpose(dt.p, nd, stream);
+        VR_HIP(hipStreamSynchronize(stream));
+    } else {
+        DevTable<S2WDesc> dt(sd);
+        launch_s2_class_weights(dt.p, nd, s2w_batch_max_elems(sd), stream);
+        VR_HIP(hipStreamSynchronize(stream));
+    }
+    for (int j = 0; j < nd; ++j) VR_CHECK(one[j]->intact() && bat[j]->intact(), -3, who + "a launch stored outside its form's buffer");
+    for (int j = 0; j < nd; ++j) {
+        one[j]->download(out[j]);
+        bat[j]->download(out[nd + j]);
+    }
+}
+
+void Model::debug_layer_forms(const int64_t* dims, int ndims, float* const* out, int nout) {
+    const std::string who = "vr_debug_kernel(layer_forms): ";
+    VR_CHECK(ndims >= 1 && nout >= 1 && out[0], -2, who + "too few arguments");
+    VR_HIP(hipStreamSynchronize(stream));
+    const std::vector<Conv*> convs = conv_layers();
+    auto held = [&](const Conv& L, void* b[9]) {
+        auto at = [&](auto& map) { auto it = map.find(L.w); return it == map.end() ? nullptr : (void*)it->second; };
+        b[0] = L.wino; b[1] = L.wino6; b[2] = L.x3w; b[3] = at(wt_of); b[4] = at(winot_of); b[5] = at(winot6_of); b[6] = at(x3t_of);
+        b[7] = at(x3dt_of); b[8] = at(s2w_of);
+    };
+    const long long i = dims[0];
+    if (i < 0) {
+        VR_CHECK(ndims >= 2 && dims[1] >= (long long)(1 + 7 * convs.size()), -2, who + "the table needs 1 + 7 floats per conv");
+        out[0][0] = (float)convs.size();
+        for (size_t k = 0; k < convs.size(); ++k) {
+            const Conv& L = *convs[k];
+            void* b[9];
+            held(L, b);
+            int mask = 0;
+            for (int j = 0; j < 9; ++j) mask |= b[j] ? 1 << j : 0;
+            const int row[7] = {L.Cin, L.Cout, L.KS, L.stride, L.dh, L.dw, mask};
+            for (int j = 0; j < 7; ++j) out[0][1 + 7 * k + j] = (float)row[j];
+        }
+        return;
+    }
+    VR_CHECK(i < (long long)convs.size() && nout >= 10, -2, who + "no such conv, or fewer than ten outputs");
+    const Conv& L = *convs[(size_t)i];
+    const int KK = L.KS * L.KS, CinPad = round32(L.Cin);
+    void* b[9];
+    held(L, b);
+    const size_t words[9] = {(size_t)L.Cin * 16 * L.CoutPad, wino_weights6_bytes(L.Cin, L.CoutPad) / 4, x3_weights_bytes(L.Cin, KK, L.CoutPad) / 4,
+                             (size_t)L.Cout * KK * CinPad, (size_t)L.Cout * 16 * CinPad, wino_weights6_bytes(L.Cout, CinPad) / 4,
+                             x3_weights_bytes(L.Cout, KK, CinPad) / 4, x3_weights_bytes(L.Cout, KK, CinPad) / 4, (size_t)4 * L.Cout * 9 * CinPad};
+    VR_HIP(hipMemcpy(out[0], L.w->dev, (size_t)L.Cin * KK * L.CoutPad * 4, hipMemcpyDeviceToHost));
+    for (int j = 0; j < 9; ++j) {
+        if (!out[1 + j]) continue;
+        VR_CHECK(b[j], -2, who + "the handle holds no such buffer for this conv");
+        VR_HIP(hipMemcpy(out[1 + j], b[j], words[j] * 4, hipMemcpyDeviceToHost));
+    }
+}
+
 void Model::debug_tensor_pass(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                               int nout) {
     const std::string who = "vr_debug_kernel(tensor_pass): ";
@@ -610,6 +773,8 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
     if (name == "wgrad_reduce") { debug_wgrad_reduce(dims, ndims, in, nin, out, nout); return; }
     if (name == "dgrad_launch") { debug_dgrad_launch(dims, ndims, in, nin, out, nout); return; }
     if (name == "tensor_pass") { debug_tensor_pass(dims, ndims, fp, nfp, in, nin, out, nout); return; }
+    if (name == "weight_forms") { debug_weight_form_launch(dims, ndims, in, nin, out, nout); return; }
+    if (name == "layer_forms") { debug_layer_forms(dims, ndims, out, nout); return; }
     if (name == "bn_backward") {
         need(4, 3, 7, 6);
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3];

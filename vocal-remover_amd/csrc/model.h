@@ -196,6 +196,8 @@ public:
     void debug_dgrad_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "dgrad_launch"
     void debug_tensor_pass(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                            int nout);                     // "tensor_pass": one materialize / upsample2x / avgpool_h on a pending tensor
+    void debug_weight_form_launch(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "weight_forms"
+    void debug_layer_forms(const int64_t* dims, int ndims, float* const* out, int nout);   // "layer_forms": what the handle holds for one conv
     // ---- signal path ----
     void stft_api(const float* wave, bool on_dev, long long L, float* spec, bool spec_on_dev);
     void istft_api(const float* spec, bool on_dev, int T, float* wave, bool wave_on_dev);
@@ -339,6 +341,11 @@ private:
     struct X3Batch { std::vector<X3WDesc> host; X3WDesc* dev = nullptr; long long max_elems = 0; };
     X3Batch xb_fwd, xb_bwd;
     void run_x3_batch(X3Batch& b, std::vector<X3WDesc>& descs);
+    // the grid sizes of the batched refresh launches, from their descriptor tables (shared with the weight_forms hook of debug.hip)
+    static long long x3_batch_max_elems(const std::vector<X3WDesc>& descs);
+    static int x3_batch_max_cout_pad(const std::vector<X3WDesc>& descs);
+    static long long wino_batch_max_elems(const std::vector<WinoWDesc>& descs, bool split6);
+    static long long s2w_batch_max_elems(const std::vector<S2WDesc>& descs);
     void refresh_wino(bool with_dgrad);
     // batched refresh: descriptor tables (host copy + device copy, re-uploaded only when a pointer changed)
     struct WinoBatch { std::vector<WinoWDesc> host; WinoWDesc* dev = nullptr; long long max_elems = 0; };
@@ -470,6 +477,7 @@ private:
     Tensor run_conv(Conv& L, const std::vector<SrcSpec>& srcs, int N, const Tensor* out_view, const float* bias,
                     bool batch_as_h);
     template <class F> void for_each_conv(F&& f);
+    std::vector<Conv*> conv_layers();                    // every conv in for_each_conv's order (train.hip)
     Tensor run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view);
     Tensor run_net_window(const Tensor& x, int w_lo, int w_hi);
     Tensor run_lstm(LSTMMod& M, const Tensor& h);

@@ -505,6 +505,30 @@ void Model::refresh_wino(bool with_dgrad) {
     run_wino_batch(wb_bwd, d, false);
 }
 
+long long Model::x3_batch_max_elems(const std::vector<X3WDesc>& descs) {
+    long long m = 0;
+    for (const X3WDesc& e : descs) m = std::max(m, (long long)((e.Cin + 7) / 8 * 8) * e.KK * e.CoutPad);
+    return m;
+}
+int Model::x3_batch_max_cout_pad(const std::vector<X3WDesc>& descs) {
+    int mc = 0;
+    for (const X3WDesc& e : descs) mc = std::max(mc, e.CoutPad);
+    return mc;
+}
+long long Model::wino_batch_max_elems(const std::vector<WinoWDesc>& descs, bool split6) {
+    long long m = 0;
+    for (const WinoWDesc& e : descs) {
+        const long long cin = split6 ? (e.Cin + 7) / 8 * 8 : e.Cin;
+        m = std::max(m, cin * e.CoutPad);
+    }
+    return m;
+}
+long long Model::s2w_batch_max_elems(const std::vector<S2WDesc>& descs) {
+    long long m = 0;
+    for (const S2WDesc& e : descs) m = std::max(m, (long long)4 * e.Cout * 9 * e.CinPad);
+    return m;
+}
+
 void Model::run_x3_batch(X3Batch& b, std::vector<X3WDesc>& descs) {
     if (descs.empty()) return;
     bool same = b.dev && b.host.size() == descs.size();
@@ -516,13 +540,10 @@ void Model::run_x3_batch(X3Batch& b, std::vector<X3WDesc>& descs) {
         VR_HIP(hipMalloc(reinterpret_cast<void**>(&b.dev), descs.size() * sizeof(X3WDesc)));
         VR_HIP(hipMemcpy(b.dev, descs.data(), descs.size() * sizeof(X3WDesc), hipMemcpyHostToDevice));
         b.host = descs;
-        b.max_elems = 0;
-        for (const X3WDesc& e : descs) b.max_elems = std::max(b.max_elems, (long long)((e.Cin + 7) / 8 * 8) * e.KK * e.CoutPad);
+        b.max_elems = x3_batch_max_elems(descs);
     }
     if (mfma_mode == 3) {
-        int mc = 0;
-        for (const X3WDesc& e : descs) mc = std::max(mc, e.CoutPad);
-        launch_x3h_weights_batched(b.dev, (int)descs.size(), b.max_elems, mc, stream);
+        launch_x3h_weights_batched(b.dev, (int)descs.size(), b.max_elems, x3_batch_max_cout_pad(descs), stream);
     } else {
         launch_x3_weights_batched(b.dev, (int)descs.size(), b.max_elems, stream);
     }
@@ -540,11 +561,7 @@ void Model::run_wino_batch(WinoBatch& b, std::vector<WinoWDesc>& descs, bool spl
         VR_HIP(hipMalloc(reinterpret_cast<void**>(&b.dev), descs.size() * sizeof(WinoWDesc)));
         VR_HIP(hipMemcpy(b.dev, descs.data(), descs.size() * sizeof(WinoWDesc), hipMemcpyHostToDevice));
         b.host = descs;
-        b.max_elems = 0;
-        for (const WinoWDesc& e : descs) {
-            const long long cin = split6 ? (e.Cin + 7) / 8 * 8 : e.Cin;
-            b.max_elems = std::max(b.max_elems, cin * e.CoutPad);
-        }
+        b.max_elems = wino_batch_max_elems(descs, split6);
     }
     launch_wino_weights_batched(b.dev, (int)descs.size(), b.max_elems, split6, stream);
 }

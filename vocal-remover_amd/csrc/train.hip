@@ -26,6 +26,12 @@ void Model::for_each_conv(F&& f) {
     f(tail1); f(tail2);
 }
 
+std::vector<Conv*> Model::conv_layers() {
+    std::vector<Conv*> v;
+    for_each_conv([&](Conv& L) { v.push_back(&L); });
+    return v;
+}
+
 void Model::ensure_train_state() {
     if (g_arena) return;
     VR_HIP(hipMalloc(&g_arena, p_floats * sizeof(float)));
@@ -63,9 +69,9 @@ void Model::ensure_train_state() {
             for (Conv* L : s2_list) {
                 s2w_of[L->w] = s2w_arena + o;
                 sd.push_back(S2WDesc{L->w->dev, s2w_arena + o, L->Cin, L->Cout, L->CoutPad, round_up32(L->Cin)});
-                s2w_max = std::max(s2w_max, (long long)4 * L->Cout * 9 * round_up32(L->Cin));
                 o += (size_t)4 * L->Cout * 9 * round_up32(L->Cin);
             }
+            s2w_max = s2w_batch_max_elems(sd);
             VR_HIP(hipMalloc(reinterpret_cast<void**>(&d_s2w), sd.size() * sizeof(S2WDesc)));
             VR_HIP(hipMemcpy(d_s2w, sd.data(), sd.size() * sizeof(S2WDesc), hipMemcpyHostToDevice));
         }
