@@ -112,6 +112,26 @@ int vr_set_mode(vr_handle h, int training);
  *   take this complex-mask handle (see vr_create_ex); 0 = they refuse it again.  Eval-mode calls are the same either way.   */
 int vr_set_option(vr_handle h, const char* name, int value);
 
+/* The loss vr_train_step and vr_validate_step compute on this handle (vr_forward_train / vr_backward are unchanged: there the caller
+ * owns the loss).  VR_LOSS_L1 is the default and what every handle did before this function existed, bit for bit.
+ * VR_LOSS_MAG_L1_WAVE_SDR is the loss the reference keeps commented out in train.py:83-88 and 125-129, with p = mask * X:
+ *     loss = mean | |y| - |p| |  +  sdr_weight * sdr,     sdr = -<to_wave(y), to_wave(p)> / (||to_wave(y)|| ||to_wave(p)|| + 1e-8)
+ * to_wave = torch.istft with a periodic Hann window over all B*2 signals (train.py:37-43), inner product and norms over the whole
+ * batch (train.py:46-50); sdr_weight is 0.01 there.  In eval, vr_validate_step computes the same on p = predict(X) and
+ * crop_center(y).  Every gradient term carries 1 / accumulation_steps; the gradient of | |y| - |p| | is 0 where |p| = 0 and where
+ * the two magnitudes are equal.  Under data parallelism the sdr is per rank over that rank's batch (N ranks == gradient accumulation).
+ * Kind 1 is accepted only on a VR_CREATE_COMPLEX handle whose option "complex_train" is on (torch.istft rejects real input) and only
+ * where hop_length * 2 == n_fft (128 <= n_fft <= 4096: the tiled signal kernels); anything else returns VR_ERR_BAD_ARGUMENT before the
+ * device is touched, and vr_last_error says which condition failed.  vr_set_option(h, "complex_train", 0) puts the loss back to
+ * VR_LOSS_L1.  sdr_weight is ignored for kind 0 (vr_get_loss then reports 0.01).
+ * vr_loss_terms: the two terms of the last vr_train_step / vr_validate_step under kind 1 on this handle, unweighted: mean | |y| - |p| |
+ * and sdr (VR_ERR_BAD_ARGUMENT when there has been none since the loss was set).                                                    */
+#define VR_LOSS_L1               0   /* today's loss, the default */
+#define VR_LOSS_MAG_L1_WAVE_SDR  1
+int vr_set_loss(vr_handle h, int kind, double sdr_weight);
+int vr_get_loss(vr_handle h, int* kind, double* sdr_weight);
+int vr_loss_terms(vr_handle h, double* mag_l1, double* sdr);
+
 /* CascadedNet.forward (mode 0) / predict_mask (mode 1) / predict (mode 2)   lib/nets.py:82-141
  * x:   [B, 2, n_fft/2+1, T] fp32 magnitudes (a VR_CREATE_COMPLEX handle: complex64, and out complex64)
  * out: mode 0 [B,2,bins,T];  modes 1,2 [B,2,bins,T-128]                                          */

@@ -129,6 +129,29 @@ int vr_set_option(vr_handle h, const char* name, int value) {
     });
 }
 
+int vr_set_loss(vr_handle h, int kind, double sdr_weight) {
+    NEED(h);
+    return guard([&] { h->m.set_loss(kind, sdr_weight); });
+}
+
+int vr_get_loss(vr_handle h, int* kind, double* sdr_weight) {
+    NEED(h);
+    return guard([&] {
+        if (kind) *kind = h->m.loss_kind;
+        if (sdr_weight) *sdr_weight = h->m.sdr_weight;
+    });
+}
+
+int vr_loss_terms(vr_handle h, double* mag_l1, double* sdr) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(h->m.loss_terms_valid, VR_ERR_BAD_ARGUMENT, "vr_loss_terms: no vr_train_step / vr_validate_step under VR_LOSS_MAG_L1_WAVE_SDR "
+                                                             "on this handle since its loss was set");
+        if (mag_l1) *mag_l1 = h->m.last_mag_l1;
+        if (sdr) *sdr = h->m.last_sdr;
+    });
+}
+
 int vr_forward(vr_handle h, const float* x, int x_on_device, int B, int T, int mode, float* out, int out_on_device) {
     NEED(h);
     return guard([&] {

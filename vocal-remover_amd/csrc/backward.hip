@@ -771,11 +771,16 @@ __device__ __forceinline__ float2 cplx_bound_bwd(const CplxBound& b, float2 g) {
 // CPLX (the complex-mask head): w [4][C], logits (a0, a1, b0, b1), z_o = a_o + i b_o, m = the bound above;
 // X, Y, mask_out are complex64 [N][2][bins][W]; loss = sum |m X - y| over complex elements (torch's L1Loss on complex tensors);
 // dL/dm = sgn(m X - y) conj(X), sgn(0) = 0, summed over the rows that share the logit, then through the bound; dlogit [N][4][H][W].
-template <bool CPLX>
+// MODE (at most one type, a trailing pack so that the forms above keep their names): MagL1 (CPLX only) = the forward half of
+// VR_LOSS_MAG_L1_WAVE_SDR -- the mask, and per-block sums of | |y| - |m X| |; dlogit is not written (gscale unused): that loss's
+// gradient needs batch-wide sums and comes back through head_bwd_kernel<true>.
+template <bool CPLX, class... MODE>
 __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* __restrict__ w, const float* __restrict__ X,
                                                         const float* __restrict__ Y, int bins, float gscale,
                                                         float* __restrict__ dlogit, float* __restrict__ mask_out,
                                                         float* __restrict__ loss_part) {
+    constexpr bool kMag = sizeof...(MODE) == 1;
+    static_assert(sizeof...(MODE) <= 1 && (!kMag || CPLX), "one mode at most; the magnitude form belongs to the complex head");
     const long long total = (long long)x.N * x.H * x.W;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     float lsum = 0.f;
@@ -807,6 +812,11 @@ __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* _
                 for (int e = 0; e < reps; ++e) {
                     const long long off = (((long long)n * 2 + o) * bins + h + e) * x.W + wq;
                     const float2 xv = Xc[off], yv = Yc[off];
+                    if constexpr (kMag) {
+                        lsum += fabsf(hypotf(yv.x, yv.y) - hypotf(m.x * xv.x - m.y * xv.y, m.x * xv.y + m.y * xv.x));
+                        Mc[off] = m;
+                        continue;
+                    }
                     const float dr = m.x * xv.x - m.y * xv.y - yv.x, di = m.x * xv.y + m.y * xv.x - yv.y;
                     const float ad = hypotf(dr, di);
                     lsum += ad;
@@ -817,9 +827,11 @@ __global__ __launch_bounds__(256) void head_loss_kernel(Tensor x, const float* _
                     }
                     if (mask_out) Mc[off] = m;
                 }
-                const float2 dz = cplx_bound_bwd(b, g);
-                dlogit[(((long long)n * 4 + o) * x.H + h) * x.W + wq] = dz.x * gscale;
-                dlogit[(((long long)n * 4 + o + 2) * x.H + h) * x.W + wq] = dz.y * gscale;
+                if constexpr (!kMag) {
+                    const float2 dz = cplx_bound_bwd(b, g);
+                    dlogit[(((long long)n * 4 + o) * x.H + h) * x.W + wq] = dz.x * gscale;
+                    dlogit[(((long long)n * 4 + o + 2) * x.H + h) * x.W + wq] = dz.y * gscale;
+                }
             }
         } else {
             float a0 = 0.f, a1 = 0.f;
@@ -946,6 +958,16 @@ void launch_head_loss_complex(const Tensor& x, const float* w, const float* X, c
     // reads the C-channel feature map and complex X, Y; writes the 4-channel logit gradient (+ the complex mask when asked)
     prof_note(8.0 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + (mask_out ? 16.0 : 12.0) * x.N * x.H * x.W));
     VR_LAUNCH((head_loss_kernel<true>), dim3(nb), dim3(256), 0, st, x, w, X, Y, bins, gscale, dlogit, mask_out, loss_part);
+    VR_HIP(hipGetLastError());
+    launch_reduce_rows(loss_part, 1, nb, loss_out, 1, 0, loss_scale, st);
+}
+
+void launch_head_mag_l1(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float* mask_out, float* loss_part,
+                        float* loss_out, float loss_scale, hipStream_t st) {
+    const int nb = head_loss_blocks(x);
+    // reads the C-channel feature map and complex X, Y; writes the complex mask
+    prof_note(8.0 * x.C * (double)x.N * x.H * x.W, 4.0 * ((double)x.N * x.C * x.H * x.W + 12.0 * x.N * x.H * x.W));
+    VR_LAUNCH((head_loss_kernel<true, MagL1>), dim3(nb), dim3(256), 0, st, x, w, X, Y, bins, 0.f, (float*)nullptr, mask_out, loss_part);
     VR_HIP(hipGetLastError());
     launch_reduce_rows(loss_part, 1, nb, loss_out, 1, 0, loss_scale, st);
 }

@@ -135,6 +135,22 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                                                        mask_b[2 bins][Wb]|null, wgt[T]|null                y_wave, v_wave [2][hop (T-1)] (fused masked
 //                                                        (cplx: complex64 masks)                             iSTFT; hop == n_fft / 2 handles only)
 //                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
+// wave_pair       S,T,x_pitch,y_pitch,  -                x[S][bins][x_pitch] complex64, mask (same shape)    y_wave, p_wave [S][hop (T-1)], sums[3] = <y, p>,
+//                 y_off,has_mask                         |null, y[S][bins][y_pitch] complex64                <y, y>, <p, p> over all signals
+//                 launch_istft_pair + the launch_reduce_rows of its partials: the waves of the target y (frame t at column y_off + t) and
+//                 of the estimate p = mask * x (no mask: x itself); bins = n_fft / 2 + 1 of the handle (hop == n_fft / 2 only).  Waves
+//                 and partials sit between guard bands (error -3).
+// wave_grad       S,T,l1                sdr_scale,       y_wave, p_wave [S][hop (T-1)], sums[3], X[S][bins]  dmask[S][bins][T] complex64
+//                                       l1_scale         [T] complex64, mask|null, Y|null (same shape)
+//                 launch_stft_wave_grad (kernels.h: WaveGrad); l1 0 switches the magnitude-L1 part off (mask and Y are then not read);
+//                 dmask sits between guard bands (error -3)
+// head_wave_loss  N,C,H,W,bins[,       slope,sdr_scale, x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[4] =
+//                 head_only]            l1_scale                                                             (mean ||y|-|p||, <y,p>, <y,y>, <p,p>), g[N,C,H,W],
+//                                                                                                            dw[4][C], dmask[N,2,bins,W] complex64
+//                 the head of a VR_LOSS_MAG_L1_WAVE_SDR step as Model::train_fwd_bwd_api runs it: launch_head_mag_l1, launch_istft_pair
+//                 + reduce, launch_stft_wave_grad, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
+//                 of the handle, W = the frames.  A sixth dim head_only = 1: launch_head_mag_l1 alone at any bins >= H -- only mask and
+//                 loss[0] are produced
 // conv_launch     nsrc,ndst,N,Cout,KS,  epi_slope,       w[Cout][Cin][KS][KS] (OIHW), bias[Cout]|null,       per destination its whole backing buffer (null where
 //                 dil_h,dil_w,flags,    slope of         epi[Cout][2]|null; per source: its backing buffer,  absent); then, with flags bit 1, stats[Cout][2] =
 //                 w_lo,w_hi,d1,d2;      source 0, 1, 2   aff0[C][2]|null, aff1[C][2]|null, post[N][C]|null;   the BatchNorm partials summed per channel
@@ -1099,6 +1115,88 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_HIP(hipStreamSynchronize(st));
         fmin.download(out[0]); y.download(out[1]); v.download(out[2]);
         if (waves) { yw.download(out[3]); vw.download(out[4]); }
+    } else if (name == "wave_pair") {
+        need(6, 0, 3, 3);
+        const int S = (int)dims[0], T = (int)dims[1], xp = (int)dims[2], yp = (int)dims[3], yo = (int)dims[4];
+        const bool has_mask = dims[5] != 0;
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(wave_loss_available(plan, hop), -2, "wave_pair: the pair iSTFT needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(S > 0 && T >= 2 && xp >= T && yo >= 0 && yp >= yo + T && in[0] && in[2] && (!has_mask || in[1]), -2,
+                 "wave_pair: need signals > 0, T >= 2, x_pitch >= T, y_pitch >= y_off + T and the inputs");
+        const size_t rows = (size_t)S * bins, nw = (size_t)S * hop * (T - 1);
+        const int nb = wave_pair_blocks(plan, T);
+        DevBuf x(in[0], rows * xp * 2), m(has_mask ? in[1] : nullptr, has_mask ? rows * xp * 2 : 0), y(in[2], rows * yp * 2);
+        GuardedBuf yw(nullptr, nw), pw(nullptr, nw), part(nullptr, (size_t)S * nb * 3);
+        DevBuf sums(4), table(64);
+        WavePair pr{};
+        pr.x = reinterpret_cast<const float2*>(x.p); pr.mask = has_mask ? reinterpret_cast<const float2*>(m.p) : nullptr;
+        pr.y = reinterpret_cast<const float2*>(y.p); pr.x_pitch = xp; pr.y_pitch = yp; pr.y_off = yo;
+        pr.y_wave = yw.p(); pr.p_wave = pw.p(); pr.part = part.p();
+        VR_HIP(hipMemcpy(table.p, &pr, sizeof(WavePair), hipMemcpyHostToDevice));
+        launch_istft_pair(plan, reinterpret_cast<const WavePair*>(table.p), pr, S, T, st);
+        launch_reduce_rows(pr.part, 3, S * nb, sums.p, 3, 0, 1.f, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(yw.intact() && pw.intact() && part.intact(), -3, "wave_pair: a store outside a wave or the partial sums");
+        yw.download(out[0]); pw.download(out[1]);
+        VR_HIP(hipMemcpy(out[2], sums.p, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    } else if (name == "wave_grad") {
+        need(3, 2, 6, 1);
+        const int S = (int)dims[0], T = (int)dims[1];
+        const bool l1 = dims[2] != 0;
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(wave_loss_available(plan, hop), -2, "wave_grad: the gradient STFT needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(S > 0 && T >= 2 && in[0] && in[1] && in[2] && in[3] && (!l1 || (in[4] && in[5])), -2, "wave_grad: need signals > 0, T >= 2 and the inputs");
+        const size_t ns = (size_t)S * bins * T * 2, nw = (size_t)S * hop * (T - 1);
+        DevBuf yw(in[0], nw), pw(in[1], nw), sums(in[2], 3), X(in[3], ns), m(l1 ? in[4] : nullptr, l1 ? ns : 0), Y(l1 ? in[5] : nullptr, l1 ? ns : 0);
+        GuardedBuf dm(nullptr, ns);
+        WaveGrad g{};
+        g.y_wave = yw.p; g.p_wave = pw.p; g.sums = sums.p; g.X = reinterpret_cast<const float2*>(X.p);
+        g.mask = reinterpret_cast<const float2*>(m.p); g.Y = reinterpret_cast<const float2*>(Y.p);
+        g.dmask = reinterpret_cast<float2*>(dm.p()); g.sdr_scale = fp[0]; g.l1_scale = l1 ? fp[1] : 0.f;
+        launch_stft_wave_grad(plan, g, S, T, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(dm.intact(), -3, "wave_grad: a store outside dmask");
+        dm.download(out[0]);
+    } else if (name == "head_wave_loss") {
+        need(5, 3, 5, 6);
+        const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], bins = (int)dims[4];
+        const bool head_only = ndims >= 6 && dims[5] != 0;
+        VR_CHECK(head_only || (wave_loss_available(plan, hop) && bins == n_fft / 2 + 1), -2,
+                 "head_wave_loss: bins must be n_fft / 2 + 1 of a hop == n_fft / 2 handle (or head_only)");
+        VR_CHECK(N > 0 && C > 0 && H > 0 && W >= 2 && bins >= H && W % 4 == 0, -2, "head_wave_loss: need positive sizes, bins >= H, W % 4 == 0");
+        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W, nw = head_only ? 0 : (size_t)N * 2 * hop * (W - 1);
+        const int S = N * 2, nb = head_only ? 0 : wave_pair_blocks(plan, W);
+        DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)4 * C), X(in[3], 2 * nx), Y(in[4], 2 * nx);
+        Tensor t = dense(x.p, N, C, H, W);
+        t.slope = fp[0];
+        if (in[1]) t.aff0 = aff.p;
+        DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), loss(4), g(n), dw((size_t)4 * C);
+        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), yw(nw), pw(nw), pp((size_t)S * nb * 3), dm(2 * nx), table(64);
+        launch_head_mag_l1(t, w.p, X.p, Y.p, bins, mask.p, lpart.p, loss.p, (float)(1.0 / (double)nx), st);
+        if (head_only) {
+            VR_HIP(hipStreamSynchronize(st));
+            mask.download(out[1]);
+            VR_HIP(hipMemcpy(out[2], loss.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
+            return;
+        }
+        WavePair pr{};
+        pr.x = reinterpret_cast<const float2*>(X.p); pr.mask = reinterpret_cast<const float2*>(mask.p);
+        pr.y = reinterpret_cast<const float2*>(Y.p); pr.x_pitch = pr.y_pitch = W; pr.y_off = 0;
+        pr.y_wave = yw.p; pr.p_wave = pw.p; pr.part = pp.p;
+        VR_HIP(hipMemcpy(table.p, &pr, sizeof(WavePair), hipMemcpyHostToDevice));
+        launch_istft_pair(plan, reinterpret_cast<const WavePair*>(table.p), pr, S, W, st);
+        launch_reduce_rows(pr.part, 3, S * nb, loss.p + 1, 3, 0, 1.f, st);
+        WaveGrad wg{};
+        wg.y_wave = yw.p; wg.p_wave = pw.p; wg.sums = loss.p + 1; wg.X = pr.x; wg.mask = pr.mask; wg.Y = pr.y;
+        wg.dmask = reinterpret_cast<float2*>(dm.p); wg.sdr_scale = fp[1]; wg.l1_scale = fp[2];
+        launch_stft_wave_grad(plan, wg, S, W, st);
+        launch_head_bwd_complex(t, w.p, dm.p, bins, dlogit.p, st);
+        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
+        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
+        VR_HIP(hipStreamSynchronize(st));
+        dlogit.download(out[0]); mask.download(out[1]);
+        VR_HIP(hipMemcpy(out[2], loss.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
+        g.download(out[3]); dw.download(out[4]); dm.download(out[5]);
     } else {
         throw Error(-2, "vr_debug_kernel: unknown kernel name: " + name);
     }

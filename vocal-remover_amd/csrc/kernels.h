@@ -160,6 +160,11 @@ void launch_head_bwd(const float* dmask, const float* mask, int N, int H, int W,
 void launch_head_loss_complex(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float gscale,
                               float* dlogit, float* mask_out, float* loss_part, float* loss_out, float loss_scale, hipStream_t st);
 void launch_head_bwd_complex(const Tensor& x, const float* w, const float* dmask, int bins, float* dlogit, hipStream_t st);
+// The magnitude form of the complex head (VR_LOSS_MAG_L1_WAVE_SDR): the mask (always written) and
+// loss_out[0] = loss_scale * sum | |y| - |m X| |; no dlogit -- the gradient of that loss needs batch-wide sums (launch_stft_wave_grad)
+struct MagL1 {};                                      // the template tag of the magnitude forms (head_loss_kernel, l1_crop_kernel)
+void launch_head_mag_l1(const Tensor& x, const float* w, const float* X, const float* Y, int bins, float* mask_out, float* loss_part,
+                        float* loss_out, float loss_scale, hipStream_t st);
 struct FlipDesc { const float* w; float* wt; int Cin, Cout, KK, CinPad, CoutPad; };
 void launch_flip_transpose(const FlipDesc* d_descs, int n, hipStream_t st);
 void launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2, double eps,
@@ -176,6 +181,8 @@ int l1_crop_blocks();
 void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
 // the same on complex64 pred and y: mean |pred - y| over complex elements (rows and columns count complex elements)
 void launch_l1_crop_complex(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
+// the same on their magnitudes: mean | |pred| - |y| |
+void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
 
 // ---- stft.hip -----------------------------------------------------------------------------------
 struct FFTPlan { int n_fft; int log2n; float2* twiddle; float* window; };
@@ -221,6 +228,39 @@ void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop,
                                  const float2* mask_b, int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st);
 void launch_frame_min_complex(int bins, int T, const float2* mask_a, int Wa, const float2* mask_b, int Wb, int shift, float* fmin,
                               hipStream_t st);
+
+// ---- the wave-domain SDR term of a complex train / validate step (VR_LOSS_MAG_L1_WAVE_SDR; hop == n_fft / 2) --
+// The pair form of istft_tile_kernel takes this as its source (one entry in device memory): `signals` spectrograms [bins][T] each of the
+// target y and of the estimate p = mask * x (mask null: x is the estimate itself).  One workgroup runs the same frame tile of y and
+// of p, stores both waves [signals][hop (T-1)] and leaves its partial sums (<y, p>, <y, y>, <p, p>) in part [signals * blocks][3].
+struct WavePair {
+    const float2* x;          // [signals][bins][x_pitch]
+    const float2* mask;       // [signals][bins][x_pitch] or null
+    const float2* y;          // [signals][bins][y_pitch], frame t at column y_off + t
+    int x_pitch, y_pitch, y_off;
+    float* y_wave;            // [signals][hop (T-1)]
+    float* p_wave;
+    float* part;              // [signals * wave_pair_blocks()][3]
+};
+bool wave_loss_available(const FFTPlan& pl, int hop);        // the tile kernels take this n_fft and hop
+int wave_pair_blocks(const FFTPlan& pl, int T);              // workgroups per signal (0: T < 2, no samples)
+void launch_istft_pair(const FFTPlan& pl, const WavePair* pair_dev, const WavePair& pair, int signals, int T, hipStream_t st);
+// The adjoint: the gradient form of stft_tile_kernel.  Its wave source is (alpha y_wave + beta p_wave) / envelope with alpha, beta from
+// the three sums in device memory (d sdr / d p_wave = -y_wave / D + (a p / (q D^2)) p_wave, times sdr_scale); its store epilogue scales
+// by c_k / n_fft, zeroes the imaginary parts of DC and Nyquist, adds the magnitude-L1 gradient l1_scale sgn(|p| - |y|) p / |p|
+// (l1_scale 0: off, mask and Y are not read) and multiplies by conj(X): dmask [signals][bins][T] complex64, dL/dRe + i dL/dIm.
+struct WaveGrad {
+    const float* y_wave;      // [signals][hop (T-1)]
+    const float* p_wave;
+    const float* sums;        // [3]: <y, p>, <y, y>, <p, p>
+    const float2* X;          // [signals][bins][T]
+    const float2* mask;
+    const float2* Y;
+    float2* dmask;
+    float sdr_scale;          // sdr_weight / accumulation_steps
+    float l1_scale;           // 1 / (n_el accumulation_steps)
+};
+void launch_stft_wave_grad(const FFTPlan& pl, const WaveGrad& g, int signals, int T, hipStream_t st);
 
 // ---- many songs in one call (vr_separate_many / vr_separate_wave_many) ----------------------------------------------------------
 // One entry of the call's song table (built on the host, one copy to the device).  The crops of all songs, and of both TTA passes, form

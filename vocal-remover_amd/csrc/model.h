@@ -162,6 +162,15 @@ public:
     // vr_set_option("complex_train") (default 0, complex handles only): the training entry points take such a handle -- interleaved
     // complex64 X, y, mask, dmask; loss = mean |m X - y| over complex elements.  Off: they refuse it, as before.
     bool complex_train = false;
+    // vr_set_loss: 0 = L1 on mask * X - y (the default), 1 = VR_LOSS_MAG_L1_WAVE_SDR, mean | |y| - |mask X| | +
+    // sdr_weight * sdr(to_wave(y), to_wave(mask X)); complex_train handles on the tiled signal path only.  vr_train_step and
+    // vr_validate_step compute it; last_mag_l1 / last_sdr are the two terms of the last such call (vr_loss_terms).
+    int loss_kind = 0;
+    double sdr_weight = 0.01, last_mag_l1 = 0.0, last_sdr = 0.0;
+    bool loss_terms_valid = false;
+    WavePair pair_host{};                                 // the pair iSTFT's table entry, staged here for its copy to the device
+    void set_loss(int kind, double weight);
+    float finish_wave_loss(const float* l4);
     int nin = 2;
     void need_real_mask(const char* what) const;          // refuse a complex handle (training entry points)
     void need_real_mask_train(const char* what) const;    // ... only while it is in training mode

@@ -379,6 +379,7 @@ void Model::set_option(const std::string& name, int value) {
     else if (name == "complex_train") {                      // a complex handle under the training entry points (off by default: they refuse it)
         if (!is_complex) throw Error(-2, "complex_train: this handle predicts a magnitude mask; the option belongs to complex-mask handles (VR_CREATE_COMPLEX)");
         complex_train = value != 0;
+        if (!complex_train && loss_kind != 0) set_loss(0, 0.01);          // VR_LOSS_MAG_L1_WAVE_SDR lives on complex training only
         graph_valid = false;
     }
     else if (name == "adam_reset") reset_adam_state();      // a freshly constructed torch.optim.Adam has no moments
@@ -1376,16 +1377,21 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
 
 // sum |pred - crop_center(y)| per block; pred [rows][Wm] dense, y [rows][T] dense, columns [off, off+Wm) of y
 // CPLX: complex64 pred and y, |.| of the complex difference (torch's L1Loss on complex tensors); `total` counts elements
-template <bool CPLX>
+// MODE (at most one type; a trailing pack keeps the names of the forms above): MagL1 (CPLX only) = | |pred| - |y| |, the magnitude part of
+// VR_LOSS_MAG_L1_WAVE_SDR
+template <bool CPLX, class... MODE>
 __global__ __launch_bounds__(256) void l1_crop_kernel(const float* __restrict__ pred, const float* __restrict__ y, int T, int Wm,
                                                       int off, long long total, float* __restrict__ part) {
+    constexpr bool kMag = sizeof...(MODE) == 1;
+    static_assert(sizeof...(MODE) <= 1 && (!kMag || CPLX), "one mode at most; the magnitude form takes complex input");
     float s = 0.f;
     for (long long gid = (long long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long long)gridDim.x * 256) {
         const int w = (int)(gid % Wm);
         const long long row = gid / Wm;
         if constexpr (CPLX) {
             const float2 a = reinterpret_cast<const float2*>(pred)[gid], b = reinterpret_cast<const float2*>(y)[row * T + off + w];
-            s += hypotf(a.x - b.x, a.y - b.y);
+            if constexpr (kMag) s += fabsf(hypotf(b.x, b.y) - hypotf(a.x, a.y));
+            else s += hypotf(a.x - b.x, a.y - b.y);
         } else {
             s += fabsf(pred[gid] - y[row * T + off + w]);
         }
@@ -1416,6 +1422,43 @@ void launch_l1_crop_complex(const float* pred, const float* y, long long rows, i
     launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
 }
 
+void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
+    const long long total = rows * Wm;
+    const int nblk = l1_crop_blocks();
+    VR_LAUNCH((l1_crop_kernel<true, MagL1>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    VR_HIP(hipGetLastError());
+    launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
+}
+
+// vr_set_loss: which loss vr_train_step / vr_validate_step compute on this handle.  Every refusal comes before the
+// device is touched.
+void Model::set_loss(int kind, double weight) {
+    VR_CHECK(kind == 0 || kind == 1, -2, "vr_set_loss: kind must be VR_LOSS_L1 (0) or VR_LOSS_MAG_L1_WAVE_SDR (1)");
+    if (kind == 1) {
+        VR_CHECK(is_complex, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
+                                 "its wave term takes a complex spectrogram, and this handle predicts a magnitude mask");
+        VR_CHECK(complex_train, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs the option complex_train on (vr_set_option(h, \"complex_train\", 1)): "
+                                    "the training entry points refuse this complex handle without it");
+        VR_CHECK(wave_loss_available(plan, hop), -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs hop_length == n_fft / 2 (128 <= n_fft <= 4096), the "
+                                                     "tiled signal path; this handle has n_fft " + std::to_string(n_fft) + ", hop " + std::to_string(hop));
+        VR_CHECK(std::isfinite(weight), -2, "vr_set_loss: sdr_weight must be finite");
+    }
+    loss_kind = kind;
+    sdr_weight = kind == 1 ? weight : 0.01;
+    last_mag_l1 = last_sdr = 0.0;
+    loss_terms_valid = false;
+    graph_valid = false;
+}
+
+// lossd [4] = (mean | |y| - |p| |, <y, p>, <y, y>, <p, p>) -> the two terms and the loss, combined in double
+float Model::finish_wave_loss(const float* l4) {
+    const double D = std::sqrt((double)l4[2]) * std::sqrt((double)l4[3]) + 1e-8;
+    last_mag_l1 = (double)l4[0];
+    last_sdr = -(double)l4[1] / D;
+    loss_terms_valid = true;
+    return (float)(last_mag_l1 + sdr_weight * last_sdr);
+}
+
 // One batch of train.validate_epoch (train.py:117-127): y_pred = model.predict(X); y = crop_center(y, y_pred);
 // loss = L1Loss()(y_pred, y) -- forward, crop and the mean-absolute-error reduction all on the device.
 void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int T, float* loss_out) {
@@ -1430,8 +1473,13 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     const int Wm = T - 2 * offset;
     const size_t out_floats = (size_t)B * 2 * output_bin * Wm * E;
     const int nblk = l1_crop_blocks();
+    // VR_LOSS_MAG_L1_WAVE_SDR: both waves of the cropped pair and the pair kernel's partial sums
+    const bool wave_loss = loss_kind == 1;
+    const int signals = B * 2, pair_nb = wave_loss ? wave_pair_blocks(plan, Wm) : 0;
+    const size_t wave_floats = wave_loss ? (size_t)signals * hop * (Wm > 1 ? Wm - 1 : 0) : 0;
+    const size_t loss_extra = wave_loss ? 2 * wave_floats + (size_t)signals * pair_nb * 3 + 256 : 0;
     fold_eval_affines();                    // before planning, as in forward_api
-    plan_and_reserve(B, T, (2 * in_floats + pack_floats + out_floats + nblk + 64) * sizeof(float) + 8192);
+    plan_and_reserve(B, T, (2 * in_floats + pack_floats + out_floats + nblk + 64 + loss_extra) * sizeof(float) + 8192);
     float* xd = ws.allocf(in_floats);
     const float* yd = Y;
     const hipMemcpyKind kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -1457,7 +1505,25 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
     const long long rows = (long long)B * 2 * output_bin;
-    if (is_complex) {
+    float l4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (wave_loss) {                        // mean | |y| - |p| | and the three wave sums of the cropped pair, p = predict(X) as materialised
+        launch_head_complex(f3, out_w->dev, d, stream);
+        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
+        prof_memset_async(lossd, 0, 4 * sizeof(float), stream);
+        launch_mag_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
+        if (pair_nb > 0) {
+            WavePair pr{};
+            pr.x = reinterpret_cast<const float2*>(od); pr.mask = nullptr; pr.y = reinterpret_cast<const float2*>(yd);
+            pr.x_pitch = Wm; pr.y_pitch = T; pr.y_off = offset;
+            pr.y_wave = ws.allocf(wave_floats); pr.p_wave = ws.allocf(wave_floats);
+            pr.part = ws.allocf((size_t)signals * pair_nb * 3);
+            WavePair* pd = reinterpret_cast<WavePair*>(ws.allocf(64));
+            pair_host = pr;
+            VR_HIP(hipMemcpyAsync(pd, &pair_host, sizeof(WavePair), hipMemcpyHostToDevice, stream));
+            launch_istft_pair(plan, pd, pr, signals, Wm, stream);
+            launch_reduce_rows(pr.part, 3, signals * pair_nb, lossd + 1, 3, 0, 1.f, stream);
+        }
+    } else if (is_complex) {
         launch_head_complex(f3, out_w->dev, d, stream);
         launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
         launch_l1_crop_complex(od, yd, rows, T, Wm, offset, part, lossd, stream);
@@ -1466,9 +1532,9 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
         launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
         launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
     }
-    float loss_h = 0.f;
-    VR_HIP(hipMemcpyAsync(&loss_h, lossd, sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipMemcpyAsync(l4, lossd, (wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
+    const float loss_h = wave_loss ? finish_wave_loss(l4) : l4[0];
     if (loss_out) *loss_out = loss_h;
 }
 

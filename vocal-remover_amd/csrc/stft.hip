@@ -32,6 +32,10 @@ template <class SRC> constexpr bool kSongTable = std::is_same<SRC, const SongSeg
 // stream and live in rings (kernels.h); each kernel handles only what the step added to its entry's stream.
 template <class SRC> constexpr bool kStream = std::is_same<SRC, const StreamSeg>::value;
 template <class SRC> using StreamLocal = typename std::conditional<kStream<SRC>, StreamSeg, int>::type;
+// SRC = const WavePair (the wave-domain loss term): `src` is one WavePair in device memory and blockIdx.y runs over
+// its signals; the workgroup runs its frame tile twice, for the target and for the estimate (kernels.h).
+template <class SRC> constexpr bool kPair = std::is_same<SRC, const WavePair>::value;
+template <class SRC> using PairLocal = typename std::conditional<kPair<SRC>, WavePair, int>::type;
 
 // sample p of channel ch of a stream: the tail kept from earlier steps, then the step's block; zero outside [0, L)
 __device__ __forceinline__ float stream_sample(const StreamSeg& sg, int ch, long long p) {
@@ -145,6 +149,20 @@ struct WavePcmIn {                           // interleaved frames of 1 or 2 cha
     int ch;
     __device__ __forceinline__ float at(long long p) const { return pcm_decode(in.bytes, in.fmt, in.channels, p, ch); }
 };
+struct WaveGradIn {                          // the wave gradient of the SDR term over the iSTFT's envelope: (alpha y + beta p)[p] / env(p)
+    const float* yw;
+    const float* pw;
+    const float* win;
+    float alpha, beta;
+    int M;
+    __device__ __forceinline__ float at(long long p) const {
+        const int i = (int)(p & (M - 1));
+        const float w0 = win[i], w2 = win[i + M];
+        const float ws = fmaf(w0, w0, w2 * w2);      // the envelope istft_tile_kernel divides by (and its guard)
+        const float a = fmaf(alpha, yw[p], beta * pw[p]);
+        return ws > FLT_MIN ? a / ws : a;
+    }
+};
 struct WaveF32Out {                          // planar float32 [2][pitch]
     static constexpr bool kInterleaved = false;
     static __device__ __forceinline__ void put(float* w, long long pitch, int ch, long long p, int i, float v) { w[(long long)ch * pitch + p + i] = v; }
@@ -159,11 +177,14 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 // PCM (at most one type): none = `wave` / the song table's `wave` are planar float32, as documented above.  PcmIn (SRC = const float, `wave`
 // unused) = the call's interleaved sample bytes; const PcmIn* (SRC = const SongSeg) = one entry per song beside the song table, whose
 // `wave` pointers are then unused.  The stream form keeps float input.
+// WaveGrad in the same place (SRC = const float, `wave` and `spec` unused): the adjoint of the inverse transform for the wave-domain loss
+// term (kernels.h) -- blockIdx.y runs over the signals, L = hop (T-1), the source is WaveGradIn and the store epilogue writes dmask.
 template <class SRC = const float, class... PCM>
 __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
                                                          float2* __restrict__ spec, PCM... pcm) {
-    constexpr bool kPcm = sizeof...(PCM) == 1;
-    static_assert(sizeof...(PCM) <= 1 && !(kPcm && kStream<SRC>), "one PCM source at most, none for streams");
+    constexpr bool kGrad = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad>::value;
+    constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad;
+    static_assert(sizeof...(PCM) <= 1 && !(sizeof...(PCM) == 1 && kStream<SRC>), "one PCM source at most, none for streams");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -171,7 +192,8 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
     int t0 = blockIdx.x * F;
     const int ch = blockIdx.y;
-    typename std::conditional<kPcm, WavePcmIn, WaveF32In>::type in;
+    typename std::conditional<kPcm, WavePcmIn, typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type in;
+    typename std::conditional<kGrad, WaveGrad, int>::type gd{};
     StreamLocal<SRC> ss{};
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_new, T) of its stream, written into the ring
         ss = wave[blockIdx.z];
@@ -184,6 +206,12 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
         L = sg.L; T = sg.T; spec = sg.spec;
         if constexpr (kPcm) in.in = pcm_first(pcm...)[blockIdx.z];
         else in.wv = sg.wave + (long long)ch * L;
+    } else if constexpr (kGrad) {                    // alpha, beta from the batch-wide sums the pair iSTFT left in device memory
+        gd = pcm_first(pcm...);
+        const double a = (double)gd.sums[0], p = sqrt((double)gd.sums[1]), q = sqrt((double)gd.sums[2]), D = p * q + 1e-8;
+        in.yw = gd.y_wave + (long long)ch * L; in.pw = gd.p_wave + (long long)ch * L; in.win = pl.window; in.M = M;
+        in.alpha = (float)(-(double)gd.sdr_scale / D);
+        in.beta = q > 0.0 ? (float)((double)gd.sdr_scale * a * p / (q * D * D)) : 0.f;
     } else {
         if constexpr (kPcm) in.in = pcm_first(pcm...);
         else in.wv = wave + (long long)ch * L;
@@ -225,6 +253,24 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
         const int k = idx / F, f = idx - k * F;
         if constexpr (kStream<SRC>) {
             if (f < nf) ss.ring[((long long)ch * bins + k) * ss.R + (t0 + f) % ss.R] = tile[idx];
+        } else if constexpr (kGrad) {
+            if (f < nf) {
+                const long long e = ((long long)ch * bins + k) * T + t0 + f;
+                const bool edge = k == 0 || k == M;                 // irfft reads neither imaginary part: c_k = 1, no gradient there
+                const float c = (edge ? 1.f : 2.f) / (float)n;
+                float2 gv = tile[idx];
+                gv = make_float2(gv.x * c, edge ? 0.f : gv.y * c);
+                const float2 xv = gd.X[e];
+                if (gd.l1_scale != 0.f) {                           // + sgn(|p| - |y|) p / |p| / n_el, p = mask X; 0 where |p| = 0 or |p| = |y|
+                    const float2 p = cmul(gd.mask[e], xv), yv = gd.Y[e];
+                    const float ap = hypotf(p.x, p.y), ay = hypotf(yv.x, yv.y);
+                    if (ap > 0.f && ap != ay) {
+                        const float s = (ap > ay ? gd.l1_scale : -gd.l1_scale) / ap;
+                        gv.x = fmaf(s, p.x, gv.x); gv.y = fmaf(s, p.y, gv.y);
+                    }
+                }
+                gd.dmask[e] = make_float2(gv.x * xv.x + gv.y * xv.y, gv.y * xv.x - gv.x * xv.y);        // times conj(X)
+            }
         } else {
             if (f < nf) spec[((long long)ch * bins + k) * T + t0 + f] = tile[idx];
         }
@@ -276,7 +322,8 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     const int ch = blockIdx.y;
     const float2* __restrict__ spec;
     StreamLocal<SRC> ss{};
-    bool carried = false;                            // (stream) frame t0 of this workgroup comes from the carry, not from the ring
+    PairLocal<SRC> pr{};
+    bool carried = false;                           // (stream) frame t0 of this workgroup comes from the carry, not from the ring
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_out, t_done) of its stream, from its rings
         ss = src[blockIdx.z];
         if (t0 >= ss.t_done - 1 - ss.t_out) return;                 // (an entry with nothing turning final has no segment at all)
@@ -293,121 +340,166 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
         if (wgt) wgt += sg.frame0;
         wave = which ? sg.v_wave : sg.y_wave;
         out_len = (long long)M * (sg.T - 1);
+    } else if constexpr (kPair<SRC>) {
+        pr = src[0];
+        spec = nullptr;
     } else {
         spec = src;
     }
     const int nf = (T - t0) < F ? (T - t0) : F;
-    for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
-        const int k = idx / F, f = idx - k * F;
-        float2 v = make_float2(0.f, 0.f);
-        if constexpr (kStream<SRC>) {
-            if (f < nf && !(carried && f == 0)) {
+    float s_yp = 0.f, s_yy = 0.f, s_pp = 0.f;        // (pair) this thread's share of <y, p>, <y, y>, <p, p>
+    // (pair) pass 0 = the target y, pass 1 = the estimate p; a thread handles the same samples in both, so pass 1 reads back its own stores
+    for (int pass = 0; pass < (kPair<SRC> ? 2 : 1); ++pass) {
+        for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
+            const int k = idx / F, f = idx - k * F;
+            float2 v = make_float2(0.f, 0.f);
+            if constexpr (kPair<SRC>) {
+                if (f < nf) {
+                    const long long row = (long long)ch * bins + k;
+                    const int t = t0 + f;
+                    if (pass == 0) {
+                        v = pr.y[row * pr.y_pitch + pr.y_off + t];
+                    } else {
+                        v = pr.x[row * pr.x_pitch + t];
+                        if (pr.mask) v = cmul(pr.mask[row * pr.x_pitch + t], v);
+                    }
+                }
+            } else if constexpr (kStream<SRC>) {
+                if (f < nf && !(carried && f == 0)) {
+                    const long long row = (long long)ch * bins + k;
+                    const int t = t0 + f;
+                    v = spec[row * ss.R + t % ss.R];
+                    const long long ca = row * ss.RM + t % ss.RM, cb = row * ss.RM + (t + shift) % ss.RM;
+                    if constexpr (CPLX) {
+                        float2 m = reinterpret_cast<const float2*>(ma)[ca];
+                        if (mb) {
+                            const float2 b = reinterpret_cast<const float2*>(mb)[cb];
+                            m = make_float2((m.x + b.x) * 0.5f, (m.y + b.y) * 0.5f);
+                        }
+                        const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
+                        v = cmul(gm, v);
+                    } else {
+                        float m = ma[ca];
+                        if (mb) m = (m + mb[cb]) * 0.5f;
+                        const float gm = which ? 1.f - m : m;
+                        v = make_float2(gm * v.x, gm * v.y);
+                    }
+                }
+            } else if (f < nf) {
                 const long long row = (long long)ch * bins + k;
                 const int t = t0 + f;
-                v = spec[row * ss.R + t % ss.R];
-                const long long ca = row * ss.RM + t % ss.RM, cb = row * ss.RM + (t + shift) % ss.RM;
+                v = spec[row * T + t];
                 if constexpr (CPLX) {
-                    float2 m = reinterpret_cast<const float2*>(ma)[ca];
-                    if (mb) {
-                        const float2 b = reinterpret_cast<const float2*>(mb)[cb];
-                        m = make_float2((m.x + b.x) * 0.5f, (m.y + b.y) * 0.5f);
+                    if (ma) {
+                        const float2 m = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift,
+                                                    wgt, row, t);
+                        const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
+                        v = cmul(gm, v);
                     }
-                    const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
-                    v = cmul(gm, v);
-                } else {
-                    float m = ma[ca];
-                    if (mb) m = (m + mb[cb]) * 0.5f;
-                    const float gm = which ? 1.f - m : m;
+                } else if (ma) {
+                    float m = ma[row * Wa + t];
+                    if (mb) m = (m + mb[row * Wb + t + shift]) * 0.5f;
+                    if (wgt) m += wgt[t] * (1.f - m);
+                    const float gm = which ? 1.f - m : m;                // y = m X, v = (1 - m) X  (inference.py:32-38; same form as apply_mask)
                     v = make_float2(gm * v.x, gm * v.y);
                 }
             }
-        } else if (f < nf) {
-            const long long row = (long long)ch * bins + k;
-            const int t = t0 + f;
-            v = spec[row * T + t];
-            if constexpr (CPLX) {
-                if (ma) {
-                    const float2 m = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift,
-                                                wgt, row, t);
-                    const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
-                    v = cmul(gm, v);
-                }
-            } else if (ma) {
-                float m = ma[row * Wa + t];
-                if (mb) m = (m + mb[row * Wb + t + shift]) * 0.5f;
-                if (wgt) m += wgt[t] * (1.f - m);
-                const float gm = which ? 1.f - m : m;                // y = m X, v = (1 - m) X  (inference.py:32-38; same form as apply_mask)
-                v = make_float2(gm * v.x, gm * v.y);
-            }
-        }
-        tile[idx] = v;
-    }
-    __syncthreads();
-    const float invM = 1.f / (float)M;
-    for (int f0 = 0; f0 < nf; f0 += TG) {
-        const int f = f0 + g;
-        const bool live = f < nf;
-        if (live) {
-            // Z[k] = E[k] + i O[k];  loaded as conj(Z) so that a forward FFT gives conj(M * z)
-            for (int k = tid; k < M; k += 256) {
-                float2 xk = tile[k * F + f], xm = tile[(M - k) * F + f];
-                if (k == 0) { xk.y = 0.f; xm.y = 0.f; }             // numpy's irfft ignores the imaginary parts of DC and Nyquist
-                const float2 e = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y));
-                const float2 d = make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y));
-                const float2 w = pl.twiddle[k];                     // e^{-2 pi i k / N}; O = conj(w) * d
-                const float2 o = make_float2(w.x * d.x + w.y * d.y, w.x * d.y - w.y * d.x);
-                const float2 z = make_float2(e.x - o.y, e.y + o.x); // E + i O
-                zs[__brev((unsigned)k) >> (32 - logM)] = make_float2(z.x, -z.y);
-            }
-        }
-        fft_lds_sub(zs, pl.twiddle, M, logM, 1, tid, 256);
-        // in place: zs[m] = (x[2m], x[2m+1]) windowed -> the group's buffer is the windowed frame, as floats [n_fft]
-        if (live) {
-            bool from_carry = false;
-            if constexpr (kStream<SRC>) from_carry = carried && f == 0;
-            if (from_carry) {                        // only the windowed second half of that frame is used: floats [M, 2M) of the buffer
-                if constexpr (kStream<SRC>) {
-                    const float* cin = ss.carry_in + (long long)(which * 2 + ch) * M;
-                    for (int m = tid; m < M; m += 256)
-                        zs[m] = 2 * m >= M ? make_float2(cin[2 * m - M], cin[2 * m + 1 - M]) : make_float2(0.f, 0.f);
-                }
-            } else {
-                for (int m = tid; m < M; m += 256) {
-                    const float2 r = zs[m];
-                    zs[m] = make_float2(r.x * invM * pl.window[2 * m], -r.y * invM * pl.window[2 * m + 1]);
-                }
-            }
+            tile[idx] = v;
         }
         __syncthreads();
-        // segment s = t - 1 = second half of frame t-1 (previous group's buffer, or `prev` for group 0) + first half of frame t
-        if (live && f > 0) {
-            const int s = t0 + f - 1;
-            const float* cur = reinterpret_cast<const float*>(zs);
-            const float* before = g == 0 ? prev : reinterpret_cast<const float*>(zs - M) + M;
-            for (int i = tid; i < M; i += 256) {
-                const float w0 = pl.window[i], w2 = pl.window[i + M];
-                const float ws = fmaf(w0, w0, w2 * w2);
-                const float a = before[i] + cur[i];
-                if constexpr (kStream<SRC>) {
-                    // (the float store written out: through put() hipcc allocates this instantiation's registers differently)
-                    if constexpr (DST::kInterleaved) DST::put(wave, 0, ch, (long long)(s - ss.t_out) * M, i, ws > FLT_MIN ? a / ws : a);
-                    else wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
+        const float invM = 1.f / (float)M;
+        for (int f0 = 0; f0 < nf; f0 += TG) {
+            const int f = f0 + g;
+            const bool live = f < nf;
+            if (live) {
+                // Z[k] = E[k] + i O[k];  loaded as conj(Z) so that a forward FFT gives conj(M * z)
+                for (int k = tid; k < M; k += 256) {
+                    float2 xk = tile[k * F + f], xm = tile[(M - k) * F + f];
+                    if (k == 0) { xk.y = 0.f; xm.y = 0.f; }             // numpy's irfft ignores the imaginary parts of DC and Nyquist
+                    const float2 e = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y));
+                    const float2 d = make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y));
+                    const float2 w = pl.twiddle[k];                     // e^{-2 pi i k / N}; O = conj(w) * d
+                    const float2 o = make_float2(w.x * d.x + w.y * d.y, w.x * d.y - w.y * d.x);
+                    const float2 z = make_float2(e.x - o.y, e.y + o.x); // E + i O
+                    zs[__brev((unsigned)k) >> (32 - logM)] = make_float2(z.x, -z.y);
+                }
+            }
+            fft_lds_sub(zs, pl.twiddle, M, logM, 1, tid, 256);
+            // in place: zs[m] = (x[2m], x[2m+1]) windowed -> the group's buffer is the windowed frame, as floats [n_fft]
+            if (live) {
+                bool from_carry = false;
+                if constexpr (kStream<SRC>) from_carry = carried && f == 0;
+                if (from_carry) {                        // only the windowed second half of that frame is used: floats [M, 2M) of the buffer
+                    if constexpr (kStream<SRC>) {
+                        const float* cin = ss.carry_in + (long long)(which * 2 + ch) * M;
+                        for (int m = tid; m < M; m += 256)
+                            zs[m] = 2 * m >= M ? make_float2(cin[2 * m - M], cin[2 * m + 1 - M]) : make_float2(0.f, 0.f);
+                    }
                 } else {
-                    const long long p = (long long)s * M + i;
-                    if (p < out_len) DST::put(wave, out_len, ch, p, 0, ws > FLT_MIN ? a / ws : a);
+                    for (int m = tid; m < M; m += 256) {
+                        const float2 r = zs[m];
+                        zs[m] = make_float2(r.x * invM * pl.window[2 * m], -r.y * invM * pl.window[2 * m + 1]);
+                    }
                 }
             }
-        }
-        __syncthreads();
-        // carry: the last live frame of this round leaves its second half for the next round's group 0
-        {
-            const int last = (nf - f0 < TG ? nf - f0 : TG) - 1;
-            if (g == last) {
+            __syncthreads();
+            // segment s = t - 1 = second half of frame t-1 (previous group's buffer, or `prev` for group 0) + first half of frame t
+            if (live && f > 0) {
+                const int s = t0 + f - 1;
                 const float* cur = reinterpret_cast<const float*>(zs);
-                for (int i = tid; i < M; i += 256) prev[i] = cur[M + i];
+                const float* before = g == 0 ? prev : reinterpret_cast<const float*>(zs - M) + M;
+                for (int i = tid; i < M; i += 256) {
+                    const float w0 = pl.window[i], w2 = pl.window[i + M];
+                    const float ws = fmaf(w0, w0, w2 * w2);
+                    const float a = before[i] + cur[i];
+                    if constexpr (kPair<SRC>) {                       // (s <= T - 2: every sample lies inside [0, hop (T-1)))
+                        const long long p = (long long)ch * out_len + (long long)s * M + i;
+                        const float v = ws > FLT_MIN ? a / ws : a;
+                        if (pass == 0) {
+                            pr.y_wave[p] = v;
+                            s_yy = fmaf(v, v, s_yy);
+                        } else {
+                            pr.p_wave[p] = v;
+                            s_yp = fmaf(pr.y_wave[p], v, s_yp);
+                            s_pp = fmaf(v, v, s_pp);
+                        }
+                    } else if constexpr (kStream<SRC>) {
+                        // (the float store written out: through put() hipcc allocates this instantiation's registers differently)
+                        if constexpr (DST::kInterleaved) DST::put(wave, 0, ch, (long long)(s - ss.t_out) * M, i, ws > FLT_MIN ? a / ws : a);
+                        else wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
+                    } else {
+                        const long long p = (long long)s * M + i;
+                        if (p < out_len) DST::put(wave, out_len, ch, p, 0, ws > FLT_MIN ? a / ws : a);
+                    }
+                }
             }
+            __syncthreads();
+            // carry: the last live frame of this round leaves its second half for the next round's group 0
+            {
+                const int last = (nf - f0 < TG ? nf - f0 : TG) - 1;
+                if (g == last) {
+                    const float* cur = reinterpret_cast<const float*>(zs);
+                    for (int i = tid; i < M; i += 256) prev[i] = cur[M + i];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if constexpr (kPair<SRC>) {                      // the workgroup's three sums, in a fixed order: wave, then the 16 waves by index
+        float* red = reinterpret_cast<float*>(tile);                // (the tile is dead: the last round ended with a barrier)
+        float v3[3] = {s_yp, s_yy, s_pp};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v3[j] += __shfl_xor(v3[j], off, 64);
+            if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * 3 + j] = v3[j];
         }
         __syncthreads();
+        if (threadIdx.x < 3) {
+            float s = 0.f;
+            for (int w = 0; w < 16; ++w) s += red[w * 3 + threadIdx.x];
+            pr.part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = s;
+        }
     }
     if constexpr (kStream<SRC>) {                    // the workgroup that ends the step hands its last half frame to the next step
         if (t0 + nf == ss.t_done) {
@@ -464,6 +556,44 @@ void launch_istft_masked_complex(const FFTPlan& pl, const float2* spec, int hop,
                                  const float2* mask_b, int Wb, int shift, const float* wgt, int which, float* wave, hipStream_t st) {
     launch_istft_tile<true>(pl, spec, hop, T, reinterpret_cast<const float*>(mask_a), Wa, reinterpret_cast<const float*>(mask_b), Wb,
                             shift, wgt, which, wave, st);
+}
+
+bool wave_loss_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
+
+int wave_pair_blocks(const FFTPlan& pl, int T) {
+    const int S = tile_frames(pl, pl.n_fft / 2) - 1;
+    return T < 2 ? 0 : (T - 1 + S - 1) / S;
+}
+
+void launch_istft_pair(const FFTPlan& pl, const WavePair* pair_dev, const WavePair& pair, int signals, int T, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    const int nb = wave_pair_blocks(pl, T);
+    if (nb == 0) return;
+    VR_CHECK(pair.y_off >= 0 && pair.y_off + T <= pair.y_pitch && T <= pair.x_pitch && signals > 0, -2, "pair iSTFT: the frames leave their rows");
+    const int F = tile_frames(pl, M);
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const WavePair>), 160 * 1024);
+    // both spectrograms (and the mask) read once, both waves written, the target's wave read back by the thread that stored it
+    prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * (pair.mask ? 3 : 2) + 3.0 * 4.0 * (double)M * (T - 1)));
+    VR_LAUNCH((istft_tile_kernel<true, const WavePair>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, pair_dev, T, F - 1,
+              (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stft_wave_grad(const FFTPlan& pl, const WaveGrad& g, int signals, int T, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, WaveGrad>), 160 * 1024);
+    // two waves read, X (and mask, Y with the L1 part) read, dmask written
+    prof_note(0.0, (double)signals * (2.0 * 4.0 * (double)M * (T - 1) + 8.0 * (double)bins * T * (g.l1_scale != 0.f ? 4 : 2)));
+    VR_LAUNCH((stft_tile_kernel<const float, WaveGrad>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
+              (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
+    VR_HIP(hipGetLastError());
 }
 
 // irfft(spec[:, t]) * window -> frames[ch][t][0..n)

@@ -475,6 +475,7 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
     const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;
     const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
     const int Hm = max_bin;
+    const bool wave_loss = loss_kind == 1;
     // ---- plan: dry run of forward + backward sizes both arenas ----------------------------------------
     auto run_all = [&](const float* xd, const float* yd, float* maskd, float* lossd) {
         tape.clear();
@@ -492,7 +493,41 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
         float* dlogit = ws.allocf((size_t)B * CO * Hm * T);
         float* lpart = ws.allocf((size_t)head_loss_blocks(f3));
         float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
-        if (!dry) {
+        // VR_LOSS_MAG_L1_WAVE_SDR: the mask (kept even when the caller does not ask for it), both waves, dmask and the
+        // pair kernel's partial sums
+        const int signals = B * 2, pair_nb = wave_loss ? wave_pair_blocks(plan, T) : 0;
+        const size_t wave_floats = (size_t)signals * hop * (T - 1);
+        float *wl_mask = nullptr, *wl_dmask = nullptr, *wl_table = nullptr;
+        WavePair pr{};
+        if (wave_loss) {
+            wl_mask = ws.allocf(io_floats);                  // (allocated either way: the dry run, which has no maskd, sizes the same)
+            if (maskd) wl_mask = maskd;
+            wl_dmask = ws.allocf(io_floats);
+            pr.y_wave = ws.allocf(wave_floats); pr.p_wave = ws.allocf(wave_floats);
+            pr.part = ws.allocf((size_t)signals * pair_nb * 3);
+            wl_table = ws.allocf(64);
+        }
+        if (!dry && wave_loss) {
+            if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
+            const double ntot = (double)B * 2 * output_bin * T;
+            const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd);
+            launch_head_mag_l1(f3, out_w->dev, xd, yd, output_bin, wl_mask, lpart, lossd, (float)(1.0 / ntot), stream);
+            pr.x = xc; pr.mask = reinterpret_cast<const float2*>(wl_mask); pr.y = yc;
+            pr.x_pitch = pr.y_pitch = T; pr.y_off = 0;
+            pair_host = pr;
+            VR_HIP(hipMemcpyAsync(wl_table, &pair_host, sizeof(WavePair), hipMemcpyHostToDevice, stream));
+            launch_istft_pair(plan, reinterpret_cast<const WavePair*>(wl_table), pr, signals, T, stream);
+            launch_reduce_rows(pr.part, 3, signals * pair_nb, lossd + 1, 3, 0, 1.f, stream);
+            WaveGrad wg{};
+            wg.y_wave = pr.y_wave; wg.p_wave = pr.p_wave; wg.sums = lossd + 1;
+            wg.X = xc; wg.mask = pr.mask; wg.Y = yc; wg.dmask = reinterpret_cast<float2*>(wl_dmask);
+            wg.sdr_scale = (float)(sdr_weight / accumulation_steps);
+            wg.l1_scale = (float)(1.0 / (ntot * accumulation_steps));
+            launch_stft_wave_grad(plan, wg, signals, T, stream);
+            launch_head_bwd_complex(f3, out_w->dev, wl_dmask, output_bin, dlogit, stream);
+            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
+            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+        } else if (!dry) {
             if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
             const double ntot = (double)B * 2 * output_bin * T;          // (complex handle: complex elements, as torch's L1Loss counts them)
             if (is_complex)
@@ -551,10 +586,11 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
     float* lossd = ws.allocf(16);
 
     run_all(xd, yd, maskd, lossd);
-    float loss_h = 0.f;
-    VR_HIP(hipMemcpyAsync(&loss_h, lossd, sizeof(float), hipMemcpyDeviceToHost, stream));
+    float l4[4] = {0.f, 0.f, 0.f, 0.f};              // the loss; VR_LOSS_MAG_L1_WAVE_SDR: its magnitude term and the three wave sums
+    VR_HIP(hipMemcpyAsync(l4, lossd, (wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (mask_out && !mask_on_dev) VR_HIP(hipMemcpyAsync(mask_out, maskd, io_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
+    const float loss_h = wave_loss ? finish_wave_loss(l4) : l4[0];
     if (loss_out) *loss_out = loss_h;
     tape.clear();
     affine_dirty = true;

@@ -17,7 +17,9 @@ is_complex=True (lib/nets.py:82-122): inputs are complex spectrograms, masks and
 model is opt-in per handle: CascadedNet(..., is_complex=True, complex_train=True) or model.set_option('complex_train', 1) after
 .to(device); then forward under model.train(), train_step, validate_step and Trainer take complex64 tensors and the loss is
 L1Loss()(mask * X, y) on complex tensors (mean |.| of the complex difference).  Without the option -- the default -- a forward under
-model.train() and the training entry points raise NotImplementedError.
+model.train() and the training entry points raise NotImplementedError.  loss='mag_l1_wave_sdr' (or model.set_loss) makes train_step
+and validate_step of such a model compute the loss the reference keeps commented out in train.py:83-88 instead: L1 on the magnitudes
+plus sdr_weight times the negative cosine of the two waveforms; model.loss_terms() gives the two terms.
 """
 import math
 from collections import OrderedDict
@@ -151,7 +153,7 @@ class _ForwardTrain(torch.autograd.Function):
 
 class CascadedNet(object):
 
-    def __init__(self, n_fft, hop_length, nout=32, nout_lstm=128, is_complex=False, complex_train=False):
+    def __init__(self, n_fft, hop_length, nout=32, nout_lstm=128, is_complex=False, complex_train=False, loss='l1', sdr_weight=0.01):
         self.n_fft = n_fft
         self.hop_length = hop_length
         self.is_complex = bool(is_complex)
@@ -159,6 +161,8 @@ class CascadedNet(object):
             raise ValueError('complex_train belongs to a complex-mask model (is_complex=True)')
         self.complex_train = bool(complex_train)      # set on every handle .to(device) creates
         self._complex_train_on = False                # the state of the CURRENT handle's "complex_train" option
+        # the loss of train_step / validate_step (include/vr_mi355.h: vr_set_loss), kept here and set on every handle .to(device) creates
+        self.loss, self.sdr_weight = self._check_loss(loss, sdr_weight, self.is_complex and self.complex_train)
         self.nout = nout
         self.nout_lstm = nout_lstm
         self.max_bin = n_fft // 2
@@ -211,6 +215,8 @@ class CascadedNet(object):
                 self._complex_train_on = False
                 if self.complex_train:
                     self.set_option('complex_train', 1)
+                if self.loss != 'l1':
+                    self.set_loss(self.loss, self.sdr_weight)
                 native.check(native.lib().vr_set_mode(self._handle.h, int(self.training)))
                 # nn.Dropout2d(0.1) on the ASPP outputs is live in train mode (lib/layers.py:90): the library's
                 # generator is seeded from torch's seed, so torch.manual_seed() makes runs repeatable
@@ -457,6 +463,48 @@ class CascadedNet(object):
         native.check(native.lib().vr_set_option(h.h, name.encode(), int(value)))
         if name == 'complex_train':
             self._complex_train_on = bool(int(value))
+            if not self._complex_train_on:
+                self.loss, self.sdr_weight = 'l1', 0.01          # the library puts the handle's loss back to VR_LOSS_L1 with it
+
+    def _check_loss(self, kind, sdr_weight, complex_training):
+        """The refusals of vr_set_loss that need no device: -> (name, weight)."""
+        names = {v: k for k, v in native.LOSS_KINDS.items()}
+        kind = names.get(kind, kind)
+        if kind not in native.LOSS_KINDS:
+            raise ValueError('loss must be one of %s, got %r' % (sorted(native.LOSS_KINDS), kind))
+        if kind == 'l1':
+            return 'l1', 0.01
+        if not self.is_complex:
+            raise ValueError("loss 'mag_l1_wave_sdr' needs a complex-mask model (is_complex=True): the inverse STFT of its wave term takes "
+                             'a complex spectrogram, this model predicts a magnitude mask')
+        if not complex_training:
+            raise ValueError("loss 'mag_l1_wave_sdr' needs complex_train on (CascadedNet(..., complex_train=True) or "
+                             "model.set_option('complex_train', 1) after .to(device))")
+        if self.hop_length * 2 != self.n_fft:
+            raise ValueError("loss 'mag_l1_wave_sdr' needs hop_length == n_fft / 2 (the tiled signal kernels), got n_fft %d, hop_length %d"
+                             % (self.n_fft, self.hop_length))
+        sdr_weight = float(sdr_weight)
+        if not np.isfinite(sdr_weight):
+            raise ValueError('sdr_weight must be finite')
+        return kind, sdr_weight
+
+    def set_loss(self, kind, sdr_weight=0.01):
+        """The loss train_step / validate_step (hence Trainer, train_epoch, validate_epoch, fit) compute: 'l1' = L1Loss()(mask * X, y),
+        the default; 'mag_l1_wave_sdr' = L1(|y|, |mask X|) + sdr_weight * sdr_loss(to_wave(y), to_wave(mask X)), the loss the reference keeps
+        commented out in train.py:83-88 (complex-mask models with complex_train on, hop_length == n_fft / 2).  The choice stays on the
+        module: every handle .to(device) creates gets it.  Under data parallelism the sdr is per rank over that rank's batch."""
+        kind, sdr_weight = self._check_loss(kind, sdr_weight, self.is_complex and (self._complex_train_on if self._handle is not None
+                                                                                    else self.complex_train))
+        if self._handle is not None:
+            native.check(native.lib().vr_set_loss(self._handle.h, native.LOSS_KINDS[kind], sdr_weight))
+        self.loss, self.sdr_weight = kind, sdr_weight
+
+    def loss_terms(self):
+        """(mean | |y| - |mask X| |, sdr) of the last train_step / validate_step under 'mag_l1_wave_sdr', unweighted."""
+        import ctypes
+        a, b = ctypes.c_double(), ctypes.c_double()
+        native.check(native.lib().vr_loss_terms(self._need_handle().h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def set_dropout_masks(self, masks):
         """Inject Dropout2d keep-masks {'<net>.aspp': [B, 8c] tensor of 0 / (1/0.9)} (parity tests);
