@@ -128,9 +128,21 @@ int vr_set_option(vr_handle h, const char* name, int value);
  * and sdr (VR_ERR_BAD_ARGUMENT when there has been none since the loss was set).                                                    */
 #define VR_LOSS_L1               0   /* today's loss, the default */
 #define VR_LOSS_MAG_L1_WAVE_SDR  1
+/* VR_LOSS_MAG_L1_WAVE_WSDR: the same with the reference's weighted_sdr_loss (train.py:53-65) as the wave term.  With xw = to_wave(X),
+ * yw = to_wave(y), pw = to_wave(p), the residuals n = xw - yw and q = xw - pw sample by sample, eps = 1e-8, sums over the whole batch:
+ *     loss = mean | |y| - |p| |  +  sdr_weight * wsdr,     wsdr = -(alpha * y_sdr + (1 - alpha) * noise_sdr)
+ *     y_sdr = <yw, pw> / (||yw|| ||pw|| + eps),  noise_sdr = <n, q> / (||n|| ||q|| + eps),  alpha = <yw, yw> / (<yw, yw> + <n, n> + eps)
+ * In eval, vr_validate_step computes it on p = predict(X), crop_center(y) and crop_center(X).  It is accepted and refused where kind 1
+ * is, is put back to VR_LOSS_L1 by "complex_train" 0, and scales its gradient the same way.  vr_loss_terms then gives mean | |y| - |p| |
+ * and wsdr; vr_loss_terms_wsdr gives y_sdr, noise_sdr and alpha of the last step under this kind (VR_ERR_BAD_ARGUMENT when there has
+ * been none since the loss was set).
+ * The value is 3: kind 2 is not a loss of this library and stays refused with VR_ERR_BAD_ARGUMENT (callers and tests rely on
+ * vr_set_loss(h, 2, ...) failing with "kind" in vr_last_error).                                                                       */
+#define VR_LOSS_MAG_L1_WAVE_WSDR 3
 int vr_set_loss(vr_handle h, int kind, double sdr_weight);
 int vr_get_loss(vr_handle h, int* kind, double* sdr_weight);
 int vr_loss_terms(vr_handle h, double* mag_l1, double* sdr);
+int vr_loss_terms_wsdr(vr_handle h, double* y_sdr, double* noise_sdr, double* alpha);
 
 /* CascadedNet.forward (mode 0) / predict_mask (mode 1) / predict (mode 2)   lib/nets.py:82-141
  * x:   [B, 2, n_fft/2+1, T] fp32 magnitudes (a VR_CREATE_COMPLEX handle: complex64, and out complex64)

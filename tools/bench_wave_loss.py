@@ -1,5 +1,5 @@
-"""The train step of a complex-mask model under its two losses (profiles/wave_loss.md), and the same step of another
-build of the project for an A / B comparison.
+"""The train step of a complex-mask model under its losses (DESIGN.md sections 6n and 6o, profiles/wave_loss.md, profiles/wsdr_loss.md),
+and the same step of another build of the project for an A / B comparison.
 
     python tools/bench_wave_loss.py  [--rounds 3] [--steps 10] [--warmup 3] [--baseline-root DIR]
 
@@ -9,12 +9,12 @@ A step is what train_epoch runs per batch: model.train_step(X, y, 1) (it returns
 native Adam step and zero_grad, closed by a device synchronisation and timed with the host clock.
 
 Every measurement runs in a fresh child process, one at a time (a process loads one build of the library).  A child of this tree times
-loss kind 0 (VR_LOSS_L1) and kind 1 (VR_LOSS_MAG_L1_WAVE_SDR), alternating --steps timed steps of each per inner round after --warmup
-untimed ones, then profiles one step of kind 1 with the library's launch profiler and reports the new kernel forms per launch.  With
---baseline-root (another checkout of the project with its library built, e.g. the parent commit) a child of THAT tree times its kind-0
-step, and the children of the two trees alternate --rounds times.  The JSON line gives per side the median over the rounds of the
-children's medians and, as *_spread, the lowest and highest round: `kind0_over_baseline` beside the two spreads says whether the
-default loss moved."""
+loss kind 0 (VR_LOSS_L1), kind 1 (VR_LOSS_MAG_L1_WAVE_SDR) and kind 3 (VR_LOSS_MAG_L1_WAVE_WSDR), alternating --steps timed steps of each
+per inner round after --warmup untimed ones, then profiles one step of kind 1 and one of kind 3 with the library's launch profiler and
+reports the kernel forms of the loss per launch.  With --baseline-root (another checkout of the project with its library built, e.g.
+the parent commit) a child of THAT tree times the kinds it has, and the children of the two trees alternate --rounds times.  The JSON
+line gives per side the median over the rounds of the children's medians and, as *_spread, the lowest and highest round:
+`kind0_over_baseline` (and `kind1_over_baseline` where the baseline has kind 1) beside the spreads says whether those steps moved."""
 import argparse
 import json
 import os
@@ -26,7 +26,8 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BATCH, FRAMES, N_FFT = 16, 256, 2048
-NEW_FORMS = ('MagL1', 'WavePair', 'WaveGrad', 'head_bwd_kernel<true>', 'reduce_rows_kernel')
+NEW_FORMS = ('MagL1', 'WavePair', 'WaveTriple', 'WaveGrad', 'head_bwd_kernel<true>', 'reduce_rows_kernel')
+KIND_NAMES = {0: 'l1', 1: 'mag_l1_wave_sdr', 3: 'mag_l1_wave_wsdr'}
 
 
 def worker(args):
@@ -49,11 +50,12 @@ def worker(args):
     y = (X * torch.rand((BATCH, 2, bins, FRAMES), generator=g)).to(dev)
     X = X.to(dev)
     opt = vtrain.Adam(model.parameters(), lr=1e-4)
-    kinds = [0, 1] if hasattr(model, 'set_loss') else [0]
+    have = getattr(vr.native, 'LOSS_KINDS', {}) if hasattr(model, 'set_loss') else {}
+    kinds = [k for k in (0, 1, 3) if k == 0 or KIND_NAMES[k] in have]
 
     def select(kind):
         if len(kinds) > 1:
-            model.set_loss('mag_l1_wave_sdr' if kind else 'l1')
+            model.set_loss(KIND_NAMES[kind])
 
     def steps(n):
         times = []
@@ -76,9 +78,11 @@ def worker(args):
             select(kind)
             meds[kind].append(statistics.median(steps(args.steps)))
     out = {'root': root, 'step_ms': {str(k): round(statistics.median(v), 3) for k, v in meds.items()}}
-    if 1 in kinds:                                        # one profiled step of kind 1: the new forms per launch
+    for pk in (1, 3):                                     # one profiled step of each wave kind: the forms of the loss per launch
+        if pk not in kinds:
+            continue
         nat, h = vr.native, model._handle.h
-        select(1)
+        select(pk)
         nat.check(nat.lib().vr_profile_begin(h))
         try:
             model.train_step(X, y, 1)
@@ -96,8 +100,8 @@ def worker(args):
                 launches.append({'kernel': f[0].replace('vr::', ''), 'calls': calls, 'us_per_call': round(ms * 1e3 / calls, 1),
                                  'noted_MB_per_call': round(byts * 1e-6 / calls, 2),
                                  'GB_per_s': round(byts / calls / (ms * 1e-3 / calls) * 1e-9, 1) if byts and ms else None})
-        out['kind1_launches'] = launches
-        out['kind1_terms'] = model.loss_terms()
+        out['kind%d_launches' % pk] = launches
+        out['kind%d_terms' % pk] = model.loss_terms()
     print('BENCH_WAVE_LOSS ' + json.dumps(out), flush=True)
     return 0
 
@@ -140,14 +144,17 @@ def main():
         out['step_ms_' + name] = round(statistics.median(vals), 3)
         out['step_ms_%s_spread' % name] = [round(min(vals), 3), round(max(vals), 3)]
 
-    put('kind0', [m['0'] for m in mine])
-    put('kind1', [m['1'] for m in mine])
+    for k in ('0', '1', '3'):
+        put('kind' + k, [m[k] for m in mine])
     out['kind1_minus_kind0_ms'] = round(out['step_ms_kind1'] - out['step_ms_kind0'], 3)
-    if base:
-        put('baseline_kind0', [m['0'] for m in base])
-        out['kind0_over_baseline'] = round(out['step_ms_kind0'] / out['step_ms_baseline_kind0'], 4)
-    out['kind1_launches'] = last['kind1_launches']
-    out['kind1_terms'] = last['kind1_terms']
+    out['kind3_minus_kind0_ms'] = round(out['step_ms_kind3'] - out['step_ms_kind0'], 3)
+    for k in ('0', '1'):
+        if base and all(k in m for m in base):
+            put('baseline_kind' + k, [m[k] for m in base])
+            out['kind%s_over_baseline' % k] = round(out['step_ms_kind' + k] / out['step_ms_baseline_kind' + k], 4)
+    for k in ('1', '3'):
+        out['kind%s_launches' % k] = last['kind%s_launches' % k]
+        out['kind%s_terms' % k] = last['kind%s_terms' % k]
     print(json.dumps(out), flush=True)
     return 0
 

@@ -146,9 +146,20 @@ int vr_loss_terms(vr_handle h, double* mag_l1, double* sdr) {
     NEED(h);
     return guard([&] {
         VR_CHECK(h->m.loss_terms_valid, VR_ERR_BAD_ARGUMENT, "vr_loss_terms: no vr_train_step / vr_validate_step under VR_LOSS_MAG_L1_WAVE_SDR "
-                                                             "on this handle since its loss was set");
+                                                             "or VR_LOSS_MAG_L1_WAVE_WSDR on this handle since its loss was set");
         if (mag_l1) *mag_l1 = h->m.last_mag_l1;
         if (sdr) *sdr = h->m.last_sdr;
+    });
+}
+
+int vr_loss_terms_wsdr(vr_handle h, double* y_sdr, double* noise_sdr, double* alpha) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(h->m.loss_terms_valid && h->m.loss_kind == VR_LOSS_MAG_L1_WAVE_WSDR, VR_ERR_BAD_ARGUMENT,
+                 "vr_loss_terms_wsdr: no vr_train_step / vr_validate_step under VR_LOSS_MAG_L1_WAVE_WSDR on this handle since its loss was set");
+        if (y_sdr) *y_sdr = h->m.last_y_sdr;
+        if (noise_sdr) *noise_sdr = h->m.last_noise_sdr;
+        if (alpha) *alpha = h->m.last_alpha;
     });
 }
 

@@ -151,6 +151,20 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 + reduce, launch_stft_wave_grad, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
 //                 of the handle, W = the frames.  A sixth dim head_only = 1: launch_head_mag_l1 alone at any bins >= H -- only mask and
 //                 loss[0] are produced
+// wave_triple     S,T,xy_pitch,xy_off,  -                x, y [S][bins][xy_pitch] complex64, mask (same      x_wave, y_wave, p_wave [S][hop (T-1)], sums[6] = <y, p>,
+//                 p_pitch,has_mask                       shape)|null, p[S][bins][p_pitch] complex64|null     <y, y>, <p, p>, <n, q>, <n, n>, <q, q> over all signals
+//                 launch_istft_triple + the launch_reduce_rows of its partials (kernels.h: WaveTriple): the waves of
+//                 the mixture x and the target y (frame t at column xy_off + t) and of the estimate -- mask * x with a mask, else p (frame t
+//                 at column t); n = x_wave - y_wave, q = x_wave - p_wave.  Waves and partials sit between guard bands (error -3).
+// wave_grad3      S,T,l1                sdr_scale,       x_wave, y_wave, p_wave [S][hop (T-1)], sums[6],     dmask[S][bins][T] complex64
+//                                       l1_scale         X[S][bins][T] complex64, mask|null, Y|null
+//                 launch_stft_wave_grad3 (kernels.h: WaveGrad3); l1 as for wave_grad; dmask sits between guard bands (error -3)
+// head_wave_wsdr  N,C,H,W,bins          slope,sdr_scale, x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[7] =
+//                                       l1_scale                                                             (mean ||y|-|p||, the six sums), g[N,C,H,W],
+//                                                                                                            dw[4][C], dmask[N,2,bins,W] complex64
+//                 the head of a VR_LOSS_MAG_L1_WAVE_WSDR step as Model::train_fwd_bwd_api runs it: launch_head_mag_l1, launch_istft_triple
+//                 + reduce, launch_stft_wave_grad3, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
+//                 of the handle, W = the frames.  Waves, partials and dmask sit between guard bands (error -3).
 // conv_launch     nsrc,ndst,N,Cout,KS,  epi_slope,       w[Cout][Cin][KS][KS] (OIHW), bias[Cout]|null,       per destination its whole backing buffer (null where
 //                 dil_h,dil_w,flags,    slope of         epi[Cout][2]|null; per source: its backing buffer,  absent); then, with flags bit 1, stats[Cout][2] =
 //                 w_lo,w_hi,d1,d2;      source 0, 1, 2   aff0[C][2]|null, aff1[C][2]|null, post[N][C]|null;   the BatchNorm partials summed per channel
@@ -1197,6 +1211,87 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
         g.download(out[3]); dw.download(out[4]); dm.download(out[5]);
+    } else if (name == "wave_triple") {
+        need(6, 0, 4, 4);
+        const int S = (int)dims[0], T = (int)dims[1], xp = (int)dims[2], xo = (int)dims[3], pp = (int)dims[4];
+        const bool has_mask = dims[5] != 0;
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(wave_loss_available(plan, hop), -2, "wave_triple: the triple iSTFT needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(S > 0 && T >= 2 && xo >= 0 && xp >= xo + T && in[0] && in[1] && (has_mask ? in[2] != nullptr : (in[3] && pp >= T)), -2,
+                 "wave_triple: need signals > 0, T >= 2, xy_pitch >= xy_off + T, the inputs, and a mask or an estimate with p_pitch >= T");
+        const size_t rows = (size_t)S * bins, nw = (size_t)S * hop * (T - 1);
+        const int nb = wave_pair_blocks(plan, T);
+        DevBuf x(in[0], rows * xp * 2), y(in[1], rows * xp * 2), m(has_mask ? in[2] : nullptr, has_mask ? rows * xp * 2 : 0);
+        DevBuf pe(has_mask ? nullptr : in[3], has_mask ? 0 : rows * pp * 2);
+        GuardedBuf xw(nullptr, nw), yw(nullptr, nw), pw(nullptr, nw), part(nullptr, (size_t)S * nb * 6), sums(nullptr, 6);
+        DevBuf table(64);
+        WaveTriple tr{};
+        tr.x = reinterpret_cast<const float2*>(x.p); tr.y = reinterpret_cast<const float2*>(y.p);
+        tr.mask = has_mask ? reinterpret_cast<const float2*>(m.p) : nullptr; tr.p = has_mask ? nullptr : reinterpret_cast<const float2*>(pe.p);
+        tr.xy_pitch = xp; tr.xy_off = xo; tr.p_pitch = has_mask ? xp : pp;
+        tr.x_wave = xw.p(); tr.y_wave = yw.p(); tr.p_wave = pw.p(); tr.part = part.p();
+        VR_HIP(hipMemcpy(table.p, &tr, sizeof(WaveTriple), hipMemcpyHostToDevice));
+        launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(table.p), tr, S, T, st);
+        launch_reduce_rows(tr.part, 6, S * nb, sums.p(), 6, 0, 1.f, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(xw.intact() && yw.intact() && pw.intact() && part.intact() && sums.intact(), -3,
+                 "wave_triple: a store outside a wave, the partial sums or the sums");
+        xw.download(out[0]); yw.download(out[1]); pw.download(out[2]); sums.download(out[3]);
+    } else if (name == "wave_grad3") {
+        need(3, 2, 7, 1);
+        const int S = (int)dims[0], T = (int)dims[1];
+        const bool l1 = dims[2] != 0;
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(wave_loss_available(plan, hop), -2, "wave_grad3: the gradient STFT needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(S > 0 && T >= 2 && in[0] && in[1] && in[2] && in[3] && in[4] && (!l1 || (in[5] && in[6])), -2,
+                 "wave_grad3: need signals > 0, T >= 2 and the inputs");
+        const size_t ns = (size_t)S * bins * T * 2, nw = (size_t)S * hop * (T - 1);
+        DevBuf xw(in[0], nw), yw(in[1], nw), pw(in[2], nw), sums(in[3], 6), X(in[4], ns), m(l1 ? in[5] : nullptr, l1 ? ns : 0),
+            Y(l1 ? in[6] : nullptr, l1 ? ns : 0);
+        GuardedBuf dm(nullptr, ns);
+        WaveGrad3 g{};
+        g.x_wave = xw.p; g.y_wave = yw.p; g.p_wave = pw.p; g.sums = sums.p; g.X = reinterpret_cast<const float2*>(X.p);
+        g.mask = reinterpret_cast<const float2*>(m.p); g.Y = reinterpret_cast<const float2*>(Y.p);
+        g.dmask = reinterpret_cast<float2*>(dm.p()); g.sdr_scale = fp[0]; g.l1_scale = l1 ? fp[1] : 0.f;
+        launch_stft_wave_grad3(plan, g, S, T, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(dm.intact(), -3, "wave_grad3: a store outside dmask");
+        dm.download(out[0]);
+    } else if (name == "head_wave_wsdr") {
+        need(5, 3, 5, 6);
+        const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], bins = (int)dims[4];
+        VR_CHECK(wave_loss_available(plan, hop) && bins == n_fft / 2 + 1, -2, "head_wave_wsdr: bins must be n_fft / 2 + 1 of a hop == n_fft / 2 handle");
+        VR_CHECK(N > 0 && C > 0 && H > 0 && W >= 2 && bins >= H && W % 4 == 0, -2, "head_wave_wsdr: need positive sizes, bins >= H, W % 4 == 0");
+        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W, nw = (size_t)N * 2 * hop * (W - 1);
+        const int S = N * 2, nb = wave_pair_blocks(plan, W);
+        DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)4 * C), X(in[3], 2 * nx), Y(in[4], 2 * nx);
+        Tensor t = dense(x.p, N, C, H, W);
+        t.slope = fp[0];
+        if (in[1]) t.aff0 = aff.p;
+        DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), g(n), dw((size_t)4 * C);
+        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), table(64);
+        GuardedBuf loss(nullptr, 7), xw(nullptr, nw), yw(nullptr, nw), pw(nullptr, nw), pp(nullptr, (size_t)S * nb * 6), dm(nullptr, 2 * nx);
+        launch_head_mag_l1(t, w.p, X.p, Y.p, bins, mask.p, lpart.p, loss.p(), (float)(1.0 / (double)nx), st);
+        WaveTriple tr{};
+        tr.x = reinterpret_cast<const float2*>(X.p); tr.y = reinterpret_cast<const float2*>(Y.p);
+        tr.mask = reinterpret_cast<const float2*>(mask.p); tr.p = nullptr;
+        tr.xy_pitch = tr.p_pitch = W; tr.xy_off = 0;
+        tr.x_wave = xw.p(); tr.y_wave = yw.p(); tr.p_wave = pw.p(); tr.part = pp.p();
+        VR_HIP(hipMemcpy(table.p, &tr, sizeof(WaveTriple), hipMemcpyHostToDevice));
+        launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(table.p), tr, S, W, st);
+        launch_reduce_rows(tr.part, 6, S * nb, loss.p() + 1, 6, 0, 1.f, st);
+        WaveGrad3 wg{};
+        wg.x_wave = tr.x_wave; wg.y_wave = tr.y_wave; wg.p_wave = tr.p_wave; wg.sums = loss.p() + 1;
+        wg.X = tr.x; wg.mask = tr.mask; wg.Y = tr.y;
+        wg.dmask = reinterpret_cast<float2*>(dm.p()); wg.sdr_scale = fp[1]; wg.l1_scale = fp[2];
+        launch_stft_wave_grad3(plan, wg, S, W, st);
+        launch_head_bwd_complex(t, w.p, dm.p(), bins, dlogit.p, st);
+        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
+        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(loss.intact() && xw.intact() && yw.intact() && pw.intact() && pp.intact() && dm.intact(), -3,
+                 "head_wave_wsdr: a store outside the loss, a wave, the partial sums or dmask");
+        dlogit.download(out[0]); mask.download(out[1]); loss.download(out[2]); g.download(out[3]); dw.download(out[4]); dm.download(out[5]);
     } else {
         throw Error(-2, "vr_debug_kernel: unknown kernel name: " + name);
     }

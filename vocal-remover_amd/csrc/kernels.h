@@ -262,6 +262,50 @@ struct WaveGrad {
 };
 void launch_stft_wave_grad(const FFTPlan& pl, const WaveGrad& g, int signals, int T, hipStream_t st);
 
+// ---- the weighted SDR term (VR_LOSS_MAG_L1_WAVE_WSDR; the reference's weighted_sdr_loss, train.py:53-65) -------
+// The triple form of istft_tile_kernel: one workgroup runs the same frame tile three times -- the mixture x, the target y, the estimate
+// p (mask * x, the product fused into the tile load; mask null: the materialised `p`) -- stores the three waves [signals][hop (T-1)] and
+// leaves its six partial sums in part [signals * wave_pair_blocks()][6], in this order, with n = x_wave - y_wave and q = x_wave - p_wave
+// formed sample by sample:  <y, p>, <y, y>, <p, p>, <n, q>, <n, n>, <q, q>.
+struct WaveTriple {
+    const float2* x;          // [signals][bins][xy_pitch], frame t at column xy_off + t
+    const float2* y;          // the same layout
+    const float2* mask;       // the same layout, or null
+    const float2* p;          // (mask null) [signals][bins][p_pitch], frame t at column t
+    int xy_pitch, xy_off, p_pitch;
+    float* x_wave;            // [signals][hop (T-1)]
+    float* y_wave;
+    float* p_wave;
+    float* part;              // [signals * wave_pair_blocks()][6]
+};
+void launch_istft_triple(const FFTPlan& pl, const WaveTriple* triple_dev, const WaveTriple& triple, int signals, int T, hipStream_t st);
+// The three coefficients of d wsdr / d p_wave = cy y_wave + cp p_wave + cx x_wave from the six sums, in double;
+// a term whose estimate norm is 0 is 0 (torch's linalg.norm backward at a zero vector).  Host and device.
+struct WsdrCoef { double cy, cp, cx; };
+__host__ __device__ inline WsdrCoef wsdr_coefficients(double A1, double yy, double pp, double A2, double nn, double qq) {
+    const double eps = 1e-8;
+    const double P1 = sqrt(yy), Q1 = sqrt(pp), P2 = sqrt(nn), Q2 = sqrt(qq), D1 = P1 * Q1 + eps, D2 = P2 * Q2 + eps;
+    const double alpha = yy / (yy + nn + eps);
+    const double k1 = Q1 > 0.0 ? alpha * A1 * P1 / (Q1 * D1 * D1) : 0.0;
+    const double k2 = Q2 > 0.0 ? (1.0 - alpha) * A2 * P2 / (Q2 * D2 * D2) : 0.0;
+    return WsdrCoef{-alpha / D1 - (1.0 - alpha) / D2, k1 + k2, (1.0 - alpha) / D2 - k2};
+}
+// The three-wave gradient form of stft_tile_kernel: WaveGrad with the wave source (cy y_wave + cp p_wave + cx x_wave) sdr_scale / envelope,
+// the coefficients formed on the device from the six sums; the store epilogue is WaveGrad's.
+struct WaveGrad3 {
+    const float* x_wave;      // [signals][hop (T-1)]
+    const float* y_wave;
+    const float* p_wave;
+    const float* sums;        // [6], WaveTriple's order
+    const float2* X;          // [signals][bins][T]
+    const float2* mask;
+    const float2* Y;
+    float2* dmask;
+    float sdr_scale;          // sdr_weight / accumulation_steps
+    float l1_scale;           // 1 / (n_el accumulation_steps)
+};
+void launch_stft_wave_grad3(const FFTPlan& pl, const WaveGrad3& g, int signals, int T, hipStream_t st);
+
 // ---- many songs in one call (vr_separate_many / vr_separate_wave_many) ----------------------------------------------------------
 // One entry of the call's song table (built on the host, one copy to the device).  The crops of all songs, and of both TTA passes, form
 // ONE crop list (pass-major, song-major inside a pass): crop n's mask lands at column n * roi of one concatenated mask

@@ -169,8 +169,13 @@ public:
     double sdr_weight = 0.01, last_mag_l1 = 0.0, last_sdr = 0.0;
     bool loss_terms_valid = false;
     WavePair pair_host{};                                 // the pair iSTFT's table entry, staged here for its copy to the device
+    // 3 = VR_LOSS_MAG_L1_WAVE_WSDR: the wave term is the reference's weighted_sdr_loss on the target and on the
+    // residual; last_sdr is then wsdr and last_y_sdr / last_noise_sdr / last_alpha its three parts (vr_loss_terms_wsdr).
+    double last_y_sdr = 0.0, last_noise_sdr = 0.0, last_alpha = 0.0;
+    WaveTriple triple_host{};                             // the triple iSTFT's table entry, staged like pair_host
     void set_loss(int kind, double weight);
     float finish_wave_loss(const float* l4);
+    float finish_wsdr_loss(const float* l7);
     int nin = 2;
     void need_real_mask(const char* what) const;          // refuse a complex handle (training entry points)
     void need_real_mask_train(const char* what) const;    // ... only while it is in training mode

@@ -1433,7 +1433,17 @@ void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T
 // vr_set_loss: which loss vr_train_step / vr_validate_step compute on this handle.  Every refusal comes before the
 // device is touched.
 void Model::set_loss(int kind, double weight) {
-    VR_CHECK(kind == 0 || kind == 1, -2, "vr_set_loss: kind must be VR_LOSS_L1 (0) or VR_LOSS_MAG_L1_WAVE_SDR (1)");
+    VR_CHECK(kind == 0 || kind == 1 || kind == 3, -2,
+             "vr_set_loss: kind must be VR_LOSS_L1 (0), VR_LOSS_MAG_L1_WAVE_SDR (1) or VR_LOSS_MAG_L1_WAVE_WSDR (3)");
+    if (kind == 3) {
+        VR_CHECK(is_complex, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
+                                 "its wave term takes a complex spectrogram, and this handle predicts a magnitude mask");
+        VR_CHECK(complex_train, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs the option complex_train on (vr_set_option(h, \"complex_train\", 1)): "
+                                    "the training entry points refuse this complex handle without it");
+        VR_CHECK(wave_loss_available(plan, hop), -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs hop_length == n_fft / 2 (128 <= n_fft <= 4096), the "
+                                                     "tiled signal path; this handle has n_fft " + std::to_string(n_fft) + ", hop " + std::to_string(hop));
+        VR_CHECK(std::isfinite(weight), -2, "vr_set_loss: sdr_weight must be finite");
+    }
     if (kind == 1) {
         VR_CHECK(is_complex, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
                                  "its wave term takes a complex spectrogram, and this handle predicts a magnitude mask");
@@ -1444,8 +1454,8 @@ void Model::set_loss(int kind, double weight) {
         VR_CHECK(std::isfinite(weight), -2, "vr_set_loss: sdr_weight must be finite");
     }
     loss_kind = kind;
-    sdr_weight = kind == 1 ? weight : 0.01;
-    last_mag_l1 = last_sdr = 0.0;
+    sdr_weight = kind != 0 ? weight : 0.01;
+    last_mag_l1 = last_sdr = last_y_sdr = last_noise_sdr = last_alpha = 0.0;
     loss_terms_valid = false;
     graph_valid = false;
 }
@@ -1455,6 +1465,19 @@ float Model::finish_wave_loss(const float* l4) {
     const double D = std::sqrt((double)l4[2]) * std::sqrt((double)l4[3]) + 1e-8;
     last_mag_l1 = (double)l4[0];
     last_sdr = -(double)l4[1] / D;
+    loss_terms_valid = true;
+    return (float)(last_mag_l1 + sdr_weight * last_sdr);
+}
+
+// lossd [7] = (mean | |y| - |p| |, <y, p>, <y, y>, <p, p>, <n, q>, <n, n>, <q, q>) -> the terms of VR_LOSS_MAG_L1_WAVE_WSDR and the
+// loss, combined in double as the reference's weighted_sdr_loss combines them (train.py:53-65)
+float Model::finish_wsdr_loss(const float* l7) {
+    const double A1 = l7[1], yy = l7[2], pp = l7[3], A2 = l7[4], nn = l7[5], qq = l7[6], eps = 1e-8;
+    last_mag_l1 = (double)l7[0];
+    last_y_sdr = A1 / (std::sqrt(yy) * std::sqrt(pp) + eps);
+    last_noise_sdr = A2 / (std::sqrt(nn) * std::sqrt(qq) + eps);
+    last_alpha = yy / (yy + nn + eps);
+    last_sdr = -(last_alpha * last_y_sdr + (1.0 - last_alpha) * last_noise_sdr);
     loss_terms_valid = true;
     return (float)(last_mag_l1 + sdr_weight * last_sdr);
 }
@@ -1474,10 +1497,11 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     const size_t out_floats = (size_t)B * 2 * output_bin * Wm * E;
     const int nblk = l1_crop_blocks();
     // VR_LOSS_MAG_L1_WAVE_SDR: both waves of the cropped pair and the pair kernel's partial sums
-    const bool wave_loss = loss_kind == 1;
+    // VR_LOSS_MAG_L1_WAVE_WSDR: the mixture's wave too, and six partial sums per workgroup
+    const bool wsdr_loss = loss_kind == 3, wave_loss = loss_kind == 1 || wsdr_loss;
     const int signals = B * 2, pair_nb = wave_loss ? wave_pair_blocks(plan, Wm) : 0;
     const size_t wave_floats = wave_loss ? (size_t)signals * hop * (Wm > 1 ? Wm - 1 : 0) : 0;
-    const size_t loss_extra = wave_loss ? 2 * wave_floats + (size_t)signals * pair_nb * 3 + 256 : 0;
+    const size_t loss_extra = wave_loss ? (wsdr_loss ? 3 : 2) * wave_floats + (size_t)signals * pair_nb * (wsdr_loss ? 6 : 3) + 256 : 0;
     fold_eval_affines();                    // before planning, as in forward_api
     plan_and_reserve(B, T, (2 * in_floats + pack_floats + out_floats + nblk + 64 + loss_extra) * sizeof(float) + 8192);
     float* xd = ws.allocf(in_floats);
@@ -1505,8 +1529,26 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
     d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
     const long long rows = (long long)B * 2 * output_bin;
-    float l4[4] = {0.f, 0.f, 0.f, 0.f};
-    if (wave_loss) {                        // mean | |y| - |p| | and the three wave sums of the cropped pair, p = predict(X) as materialised
+    float l4[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (wsdr_loss) {                        // mean | |y| - |p| | and the six wave sums of crop_center(X), crop_center(y) and p = predict(X)
+        launch_head_complex(f3, out_w->dev, d, stream);
+        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
+        prof_memset_async(lossd, 0, 7 * sizeof(float), stream);
+        launch_mag_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
+        if (pair_nb > 0) {
+            WaveTriple tr{};
+            tr.x = reinterpret_cast<const float2*>(xd); tr.y = reinterpret_cast<const float2*>(yd); tr.mask = nullptr;
+            tr.p = reinterpret_cast<const float2*>(od);
+            tr.xy_pitch = T; tr.xy_off = offset; tr.p_pitch = Wm;
+            tr.x_wave = ws.allocf(wave_floats); tr.y_wave = ws.allocf(wave_floats); tr.p_wave = ws.allocf(wave_floats);
+            tr.part = ws.allocf((size_t)signals * pair_nb * 6);
+            WaveTriple* td = reinterpret_cast<WaveTriple*>(ws.allocf(64));
+            triple_host = tr;
+            VR_HIP(hipMemcpyAsync(td, &triple_host, sizeof(WaveTriple), hipMemcpyHostToDevice, stream));
+            launch_istft_triple(plan, td, tr, signals, Wm, stream);
+            launch_reduce_rows(tr.part, 6, signals * pair_nb, lossd + 1, 6, 0, 1.f, stream);
+        }
+    } else if (wave_loss) {                 // mean | |y| - |p| | and the three wave sums of the cropped pair, p = predict(X) as materialised
         launch_head_complex(f3, out_w->dev, d, stream);
         launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
         prof_memset_async(lossd, 0, 4 * sizeof(float), stream);
@@ -1532,9 +1574,9 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
         launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
         launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
     }
-    VR_HIP(hipMemcpyAsync(l4, lossd, (wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
+    VR_HIP(hipMemcpyAsync(l4, lossd, (wsdr_loss ? 7 : wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
-    const float loss_h = wave_loss ? finish_wave_loss(l4) : l4[0];
+    const float loss_h = wsdr_loss ? finish_wsdr_loss(l4) : wave_loss ? finish_wave_loss(l4) : l4[0];
     if (loss_out) *loss_out = loss_h;
 }
 

@@ -36,6 +36,9 @@ template <class SRC> using StreamLocal = typename std::conditional<kStream<SRC>,
 // its signals; the workgroup runs its frame tile twice, for the target and for the estimate (kernels.h).
 template <class SRC> constexpr bool kPair = std::is_same<SRC, const WavePair>::value;
 template <class SRC> using PairLocal = typename std::conditional<kPair<SRC>, WavePair, int>::type;
+// SRC = const WaveTriple (the weighted SDR term): the same with three passes -- the mixture, the target, the estimate.
+template <class SRC> constexpr bool kTriple = std::is_same<SRC, const WaveTriple>::value;
+template <class SRC> using TripleLocal = typename std::conditional<kTriple<SRC>, WaveTriple, int>::type;
 
 // sample p of channel ch of a stream: the tail kept from earlier steps, then the step's block; zero outside [0, L)
 __device__ __forceinline__ float stream_sample(const StreamSeg& sg, int ch, long long p) {
@@ -163,6 +166,21 @@ struct WaveGradIn {                          // the wave gradient of the SDR ter
         return ws > FLT_MIN ? a / ws : a;
     }
 };
+struct WaveGrad3In {                         // the same for the weighted SDR term: (cy y + cp p + cx x)[p] / env(p)
+    const float* xw;
+    const float* yw;
+    const float* pw;
+    const float* win;
+    float cy, cp, cx;
+    int M;
+    __device__ __forceinline__ float at(long long p) const {
+        const int i = (int)(p & (M - 1));
+        const float w0 = win[i], w2 = win[i + M];
+        const float ws = fmaf(w0, w0, w2 * w2);
+        const float a = fmaf(cy, yw[p], fmaf(cp, pw[p], cx * xw[p]));
+        return ws > FLT_MIN ? a / ws : a;
+    }
+};
 struct WaveF32Out {                          // planar float32 [2][pitch]
     static constexpr bool kInterleaved = false;
     static __device__ __forceinline__ void put(float* w, long long pitch, int ch, long long p, int i, float v) { w[(long long)ch * pitch + p + i] = v; }
@@ -179,10 +197,12 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 // `wave` pointers are then unused.  The stream form keeps float input.
 // WaveGrad in the same place (SRC = const float, `wave` and `spec` unused): the adjoint of the inverse transform for the wave-domain loss
 // term (kernels.h) -- blockIdx.y runs over the signals, L = hop (T-1), the source is WaveGradIn and the store epilogue writes dmask.
+// WaveGrad3: the same for the weighted SDR term, source WaveGrad3In over three waves, the same store epilogue.
 template <class SRC = const float, class... PCM>
 __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
                                                          float2* __restrict__ spec, PCM... pcm) {
-    constexpr bool kGrad = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad>::value;
+    constexpr bool kGrad3 = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad3>::value;
+    constexpr bool kGrad = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad>::value || kGrad3;
     constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad;
     static_assert(sizeof...(PCM) <= 1 && !(sizeof...(PCM) == 1 && kStream<SRC>), "one PCM source at most, none for streams");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
@@ -192,8 +212,9 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
     int t0 = blockIdx.x * F;
     const int ch = blockIdx.y;
-    typename std::conditional<kPcm, WavePcmIn, typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type in;
-    typename std::conditional<kGrad, WaveGrad, int>::type gd{};
+    typename std::conditional<kPcm, WavePcmIn, typename std::conditional<kGrad3, WaveGrad3In,
+                              typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type>::type in;
+    typename std::conditional<kGrad3, WaveGrad3, typename std::conditional<kGrad, WaveGrad, int>::type>::type gd{};
     StreamLocal<SRC> ss{};
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_new, T) of its stream, written into the ring
         ss = wave[blockIdx.z];
@@ -206,6 +227,13 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
         L = sg.L; T = sg.T; spec = sg.spec;
         if constexpr (kPcm) in.in = pcm_first(pcm...)[blockIdx.z];
         else in.wv = sg.wave + (long long)ch * L;
+    } else if constexpr (kGrad3) {                   // cy, cp, cx from the six batch-wide sums the triple iSTFT left in device memory
+        gd = pcm_first(pcm...);
+        const WsdrCoef c = wsdr_coefficients((double)gd.sums[0], (double)gd.sums[1], (double)gd.sums[2], (double)gd.sums[3],
+                                             (double)gd.sums[4], (double)gd.sums[5]);
+        in.xw = gd.x_wave + (long long)ch * L; in.yw = gd.y_wave + (long long)ch * L; in.pw = gd.p_wave + (long long)ch * L;
+        in.win = pl.window; in.M = M;
+        in.cy = (float)((double)gd.sdr_scale * c.cy); in.cp = (float)((double)gd.sdr_scale * c.cp); in.cx = (float)((double)gd.sdr_scale * c.cx);
     } else if constexpr (kGrad) {                    // alpha, beta from the batch-wide sums the pair iSTFT left in device memory
         gd = pcm_first(pcm...);
         const double a = (double)gd.sums[0], p = sqrt((double)gd.sums[1]), q = sqrt((double)gd.sums[2]), D = p * q + 1e-8;
@@ -323,6 +351,7 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     const float2* __restrict__ spec;
     StreamLocal<SRC> ss{};
     PairLocal<SRC> pr{};
+    TripleLocal<SRC> tr{};
     bool carried = false;                           // (stream) frame t0 of this workgroup comes from the carry, not from the ring
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_out, t_done) of its stream, from its rings
         ss = src[blockIdx.z];
@@ -343,13 +372,18 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     } else if constexpr (kPair<SRC>) {
         pr = src[0];
         spec = nullptr;
+    } else if constexpr (kTriple<SRC>) {
+        tr = src[0];
+        spec = nullptr;
     } else {
         spec = src;
     }
     const int nf = (T - t0) < F ? (T - t0) : F;
-    float s_yp = 0.f, s_yy = 0.f, s_pp = 0.f;        // (pair) this thread's share of <y, p>, <y, y>, <p, p>
+    float s_yp = 0.f, s_yy = 0.f, s_pp = 0.f;        // (pair, triple) this thread's share of <y, p>, <y, y>, <p, p>
+    float s_nq = 0.f, s_nn = 0.f, s_qq = 0.f;        // (triple) ... and of <n, q>, <n, n>, <q, q>, n = x - y and q = x - p sample by sample
     // (pair) pass 0 = the target y, pass 1 = the estimate p; a thread handles the same samples in both, so pass 1 reads back its own stores
-    for (int pass = 0; pass < (kPair<SRC> ? 2 : 1); ++pass) {
+    // (triple) pass 0 = the mixture x, 1 = y, 2 = p: pass 1 reads back its own x store, pass 2 its own x and y stores
+    for (int pass = 0; pass < (kTriple<SRC> ? 3 : kPair<SRC> ? 2 : 1); ++pass) {
         for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
             const int k = idx / F, f = idx - k * F;
             float2 v = make_float2(0.f, 0.f);
@@ -363,6 +397,16 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                         v = pr.x[row * pr.x_pitch + t];
                         if (pr.mask) v = cmul(pr.mask[row * pr.x_pitch + t], v);
                     }
+                }
+            } else if constexpr (kTriple<SRC>) {
+                if (f < nf) {
+                    const long long row = (long long)ch * bins + k;
+                    const int t = t0 + f;
+                    const long long e = row * tr.xy_pitch + tr.xy_off + t;
+                    if (pass == 0) v = tr.x[e];
+                    else if (pass == 1) v = tr.y[e];
+                    else if (tr.mask) v = cmul(tr.mask[e], tr.x[e]);
+                    else v = tr.p[row * tr.p_pitch + t];
                 }
             } else if constexpr (kStream<SRC>) {
                 if (f < nf && !(carried && f == 0)) {
@@ -463,6 +507,25 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                             s_yp = fmaf(pr.y_wave[p], v, s_yp);
                             s_pp = fmaf(v, v, s_pp);
                         }
+                    } else if constexpr (kTriple<SRC>) {              // (s <= T - 2, as above)
+                        const long long p = (long long)ch * out_len + (long long)s * M + i;
+                        const float v = ws > FLT_MIN ? a / ws : a;
+                        if (pass == 0) {
+                            tr.x_wave[p] = v;
+                        } else if (pass == 1) {
+                            const float nv = tr.x_wave[p] - v;
+                            tr.y_wave[p] = v;
+                            s_yy = fmaf(v, v, s_yy);
+                            s_nn = fmaf(nv, nv, s_nn);
+                        } else {
+                            const float xv = tr.x_wave[p], yv = tr.y_wave[p];
+                            const float nv = xv - yv, qv = xv - v;
+                            tr.p_wave[p] = v;
+                            s_yp = fmaf(yv, v, s_yp);
+                            s_pp = fmaf(v, v, s_pp);
+                            s_nq = fmaf(nv, qv, s_nq);
+                            s_qq = fmaf(qv, qv, s_qq);
+                        }
                     } else if constexpr (kStream<SRC>) {
                         // (the float store written out: through put() hipcc allocates this instantiation's registers differently)
                         if constexpr (DST::kInterleaved) DST::put(wave, 0, ch, (long long)(s - ss.t_out) * M, i, ws > FLT_MIN ? a / ws : a);
@@ -499,6 +562,22 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
             float s = 0.f;
             for (int w = 0; w < 16; ++w) s += red[w * 3 + threadIdx.x];
             pr.part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = s;
+        }
+    }
+    if constexpr (kTriple<SRC>) {                    // the workgroup's six sums, in the same fixed order
+        float* red = reinterpret_cast<float*>(tile);
+        float v6[6] = {s_yp, s_yy, s_pp, s_nq, s_nn, s_qq};
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v6[j] += __shfl_xor(v6[j], off, 64);
+            if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * 6 + j] = v6[j];
+        }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            float s = 0.f;
+            for (int w = 0; w < 16; ++w) s += red[w * 6 + threadIdx.x];
+            tr.part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = s;
         }
     }
     if constexpr (kStream<SRC>) {                    // the workgroup that ends the step hands its last half frame to the next step
@@ -578,6 +657,39 @@ void launch_istft_pair(const FFTPlan& pl, const WavePair* pair_dev, const WavePa
     prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * (pair.mask ? 3 : 2) + 3.0 * 4.0 * (double)M * (T - 1)));
     VR_LAUNCH((istft_tile_kernel<true, const WavePair>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, pair_dev, T, F - 1,
               (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
+    VR_HIP(hipGetLastError());
+}
+
+void launch_istft_triple(const FFTPlan& pl, const WaveTriple* triple_dev, const WaveTriple& tr, int signals, int T, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    const int nb = wave_pair_blocks(pl, T);
+    if (nb == 0) return;
+    VR_CHECK(tr.xy_off >= 0 && tr.xy_off + T <= tr.xy_pitch && (tr.mask || (tr.p && T <= tr.p_pitch)) && signals > 0, -2,
+             "triple iSTFT: the frames leave their rows");
+    const int F = tile_frames(pl, M);
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const WaveTriple>), 160 * 1024);
+    // the mixture and the target read once, the estimate once (fused: the mask and the mixture again), three waves written, the mixture's
+    // wave read back twice and the target's once by the thread that stored them
+    prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * (tr.mask ? 4 : 3) + 6.0 * 4.0 * (double)M * (T - 1)));
+    VR_LAUNCH((istft_tile_kernel<true, const WaveTriple>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, triple_dev, T, F - 1,
+              (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stft_wave_grad3(const FFTPlan& pl, const WaveGrad3& g, int signals, int T, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, WaveGrad3>), 160 * 1024);
+    // three waves read, X (and mask, Y with the L1 part) read, dmask written
+    prof_note(0.0, (double)signals * (3.0 * 4.0 * (double)M * (T - 1) + 8.0 * (double)bins * T * (g.l1_scale != 0.f ? 4 : 2)));
+    VR_LAUNCH((stft_tile_kernel<const float, WaveGrad3>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
+              (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
     VR_HIP(hipGetLastError());
 }
 

@@ -475,7 +475,7 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
     const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;
     const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
     const int Hm = max_bin;
-    const bool wave_loss = loss_kind == 1;
+    const bool wsdr_loss = loss_kind == 3, wave_loss = loss_kind == 1 || wsdr_loss;      // VR_LOSS_MAG_L1_WAVE_WSDR: DESIGN.md section 6o
     // ---- plan: dry run of forward + backward sizes both arenas ----------------------------------------
     auto run_all = [&](const float* xd, const float* yd, float* maskd, float* lossd) {
         tape.clear();
@@ -499,15 +499,39 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
         const size_t wave_floats = (size_t)signals * hop * (T - 1);
         float *wl_mask = nullptr, *wl_dmask = nullptr, *wl_table = nullptr;
         WavePair pr{};
+        float* x_wave = nullptr;                             // (kind 3) the mixture's wave; its partials are six wide
         if (wave_loss) {
             wl_mask = ws.allocf(io_floats);                  // (allocated either way: the dry run, which has no maskd, sizes the same)
             if (maskd) wl_mask = maskd;
             wl_dmask = ws.allocf(io_floats);
             pr.y_wave = ws.allocf(wave_floats); pr.p_wave = ws.allocf(wave_floats);
-            pr.part = ws.allocf((size_t)signals * pair_nb * 3);
+            if (wsdr_loss) x_wave = ws.allocf(wave_floats);
+            pr.part = ws.allocf((size_t)signals * pair_nb * (wsdr_loss ? 6 : 3));
             wl_table = ws.allocf(64);
         }
-        if (!dry && wave_loss) {
+        if (!dry && wsdr_loss) {
+            if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
+            const double ntot = (double)B * 2 * output_bin * T;
+            const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd);
+            launch_head_mag_l1(f3, out_w->dev, xd, yd, output_bin, wl_mask, lpart, lossd, (float)(1.0 / ntot), stream);
+            WaveTriple tr{};
+            tr.x = xc; tr.y = yc; tr.mask = reinterpret_cast<const float2*>(wl_mask); tr.p = nullptr;
+            tr.xy_pitch = tr.p_pitch = T; tr.xy_off = 0;
+            tr.x_wave = x_wave; tr.y_wave = pr.y_wave; tr.p_wave = pr.p_wave; tr.part = pr.part;
+            triple_host = tr;
+            VR_HIP(hipMemcpyAsync(wl_table, &triple_host, sizeof(WaveTriple), hipMemcpyHostToDevice, stream));
+            launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(wl_table), tr, signals, T, stream);
+            launch_reduce_rows(tr.part, 6, signals * pair_nb, lossd + 1, 6, 0, 1.f, stream);
+            WaveGrad3 wg{};
+            wg.x_wave = tr.x_wave; wg.y_wave = tr.y_wave; wg.p_wave = tr.p_wave; wg.sums = lossd + 1;
+            wg.X = xc; wg.mask = tr.mask; wg.Y = yc; wg.dmask = reinterpret_cast<float2*>(wl_dmask);
+            wg.sdr_scale = (float)(sdr_weight / accumulation_steps);
+            wg.l1_scale = (float)(1.0 / (ntot * accumulation_steps));
+            launch_stft_wave_grad3(plan, wg, signals, T, stream);
+            launch_head_bwd_complex(f3, out_w->dev, wl_dmask, output_bin, dlogit, stream);
+            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
+            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+        } else if (!dry && wave_loss) {
             if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
             const double ntot = (double)B * 2 * output_bin * T;
             const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd);
@@ -586,11 +610,12 @@ void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B
     float* lossd = ws.allocf(16);
 
     run_all(xd, yd, maskd, lossd);
-    float l4[4] = {0.f, 0.f, 0.f, 0.f};              // the loss; VR_LOSS_MAG_L1_WAVE_SDR: its magnitude term and the three wave sums
-    VR_HIP(hipMemcpyAsync(l4, lossd, (wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
+    // the loss; VR_LOSS_MAG_L1_WAVE_SDR: its magnitude term and the three wave sums; VR_LOSS_MAG_L1_WAVE_WSDR: the term and six sums
+    float l4[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    VR_HIP(hipMemcpyAsync(l4, lossd, (wsdr_loss ? 7 : wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (mask_out && !mask_on_dev) VR_HIP(hipMemcpyAsync(mask_out, maskd, io_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
-    const float loss_h = wave_loss ? finish_wave_loss(l4) : l4[0];
+    const float loss_h = wsdr_loss ? finish_wsdr_loss(l4) : wave_loss ? finish_wave_loss(l4) : l4[0];
     if (loss_out) *loss_out = loss_h;
     tape.clear();
     affine_dirty = true;

@@ -11,8 +11,8 @@ LIB_PATH = os.environ.get('VR_LIB_PATH') or os.path.join(_HERE, 'libvr_mi355.so'
 
 c_f32p = ctypes.c_void_p
 VR_CREATE_COMPLEX = 1         # include/vr_mi355.h
-VR_LOSS_L1, VR_LOSS_MAG_L1_WAVE_SDR = 0, 1
-LOSS_KINDS = {'l1': VR_LOSS_L1, 'mag_l1_wave_sdr': VR_LOSS_MAG_L1_WAVE_SDR}
+VR_LOSS_L1, VR_LOSS_MAG_L1_WAVE_SDR, VR_LOSS_MAG_L1_WAVE_WSDR = 0, 1, 3          # (kind 2 is not a loss: the header says why)
+LOSS_KINDS = {'l1': VR_LOSS_L1, 'mag_l1_wave_sdr': VR_LOSS_MAG_L1_WAVE_SDR, 'mag_l1_wave_wsdr': VR_LOSS_MAG_L1_WAVE_WSDR}
 VR_STREAM_TTA, VR_STREAM_MEASURE, VR_STREAM_POSTPROCESS, VR_STREAM_PCM16_OUT = 1, 2, 4, 8
 VR_PCM_S16, VR_PCM_S24, VR_PCM_S32, VR_PCM_F32 = 1, 2, 3, 4          # enum vr_pcm_format
 PCM_SAMPLE_BYTES = {VR_PCM_S16: 2, VR_PCM_S24: 3, VR_PCM_S32: 4, VR_PCM_F32: 4}
@@ -84,6 +84,8 @@ _SIGNATURES = {
     'vr_set_loss': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
     'vr_get_loss': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
     'vr_loss_terms': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    'vr_loss_terms_wsdr': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double)]),
     'vr_augment_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),

@@ -20,6 +20,8 @@ L1Loss()(mask * X, y) on complex tensors (mean |.| of the complex difference).  
 model.train() and the training entry points raise NotImplementedError.  loss='mag_l1_wave_sdr' (or model.set_loss) makes train_step
 and validate_step of such a model compute the loss the reference keeps commented out in train.py:83-88 instead: L1 on the magnitudes
 plus sdr_weight times the negative cosine of the two waveforms; model.loss_terms() gives the two terms.
+loss='mag_l1_wave_wsdr' takes the reference's weighted_sdr_loss (train.py:53-65) as the wave term, which also scores the residual
+X - y against X - mask X; model.loss_detail() gives its three parts.
 """
 import math
 from collections import OrderedDict
@@ -475,14 +477,14 @@ class CascadedNet(object):
         if kind == 'l1':
             return 'l1', 0.01
         if not self.is_complex:
-            raise ValueError("loss 'mag_l1_wave_sdr' needs a complex-mask model (is_complex=True): the inverse STFT of its wave term takes "
-                             'a complex spectrogram, this model predicts a magnitude mask')
+            raise ValueError('loss %r needs a complex-mask model (is_complex=True): the inverse STFT of its wave term takes '
+                             'a complex spectrogram, this model predicts a magnitude mask' % kind)
         if not complex_training:
-            raise ValueError("loss 'mag_l1_wave_sdr' needs complex_train on (CascadedNet(..., complex_train=True) or "
-                             "model.set_option('complex_train', 1) after .to(device))")
+            raise ValueError('loss %r needs complex_train on (CascadedNet(..., complex_train=True) or '
+                             "model.set_option('complex_train', 1) after .to(device))" % kind)
         if self.hop_length * 2 != self.n_fft:
-            raise ValueError("loss 'mag_l1_wave_sdr' needs hop_length == n_fft / 2 (the tiled signal kernels), got n_fft %d, hop_length %d"
-                             % (self.n_fft, self.hop_length))
+            raise ValueError('loss %r needs hop_length == n_fft / 2 (the tiled signal kernels), got n_fft %d, hop_length %d'
+                             % (kind, self.n_fft, self.hop_length))
         sdr_weight = float(sdr_weight)
         if not np.isfinite(sdr_weight):
             raise ValueError('sdr_weight must be finite')
@@ -491,7 +493,9 @@ class CascadedNet(object):
     def set_loss(self, kind, sdr_weight=0.01):
         """The loss train_step / validate_step (hence Trainer, train_epoch, validate_epoch, fit) compute: 'l1' = L1Loss()(mask * X, y),
         the default; 'mag_l1_wave_sdr' = L1(|y|, |mask X|) + sdr_weight * sdr_loss(to_wave(y), to_wave(mask X)), the loss the reference keeps
-        commented out in train.py:83-88 (complex-mask models with complex_train on, hop_length == n_fft / 2).  The choice stays on the
+        commented out in train.py:83-88; 'mag_l1_wave_wsdr' = the same with the reference's weighted_sdr_loss(to_wave(y), to_wave(mask X),
+        to_wave(X) - to_wave(y), to_wave(X) - to_wave(mask X)) as the wave term (train.py:53-65).  Both belong to
+        complex-mask models with complex_train on and hop_length == n_fft / 2.  The choice stays on the
         module: every handle .to(device) creates gets it.  Under data parallelism the sdr is per rank over that rank's batch."""
         kind, sdr_weight = self._check_loss(kind, sdr_weight, self.is_complex and (self._complex_train_on if self._handle is not None
                                                                                     else self.complex_train))
@@ -500,11 +504,20 @@ class CascadedNet(object):
         self.loss, self.sdr_weight = kind, sdr_weight
 
     def loss_terms(self):
-        """(mean | |y| - |mask X| |, sdr) of the last train_step / validate_step under 'mag_l1_wave_sdr', unweighted."""
+        """(mean | |y| - |mask X| |, sdr) of the last train_step / validate_step under 'mag_l1_wave_sdr', unweighted; under
+        'mag_l1_wave_wsdr' the second is the weighted sdr."""
         import ctypes
         a, b = ctypes.c_double(), ctypes.c_double()
         native.check(native.lib().vr_loss_terms(self._need_handle().h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def loss_detail(self):
+        """The parts of the weighted sdr of the last train_step / validate_step under 'mag_l1_wave_wsdr':
+        wsdr = -(alpha * y_sdr + (1 - alpha) * noise_sdr)."""
+        import ctypes
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        native.check(native.lib().vr_loss_terms_wsdr(self._need_handle().h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {'y_sdr': a.value, 'noise_sdr': b.value, 'alpha': c.value}
 
     def set_dropout_masks(self, masks):
         """Inject Dropout2d keep-masks {'<net>.aspp': [B, 8c] tensor of 0 / (1/0.9)} (parity tests);
