@@ -298,6 +298,17 @@ def test_a_steady_push_is_one_launch_per_stage(vr, small):
     assert not [n for n in seen if n.startswith('mag_pad_kernel<false, vr::StreamSeg const, false')]      # a given coef: no statistics
     one = _profiled(vr, small, lambda: sp.separate_wave(w))
     assert not [n for n in one if 'StreamSeg' in n], sorted(one)
+    # tta, batchsize 2: a steady push readies one crop per pass; the two share a device batch and ONE mask head launch, which
+    # sends each to its own pass's ring through the destination table
+    sp2 = vr.inference.Separator(small, DEV, batchsize=2, cropsize=160)
+    with sp2.stream(coef=sp2.measure_coef([w], tta=True), tta=True) as s:
+        for k in range(8):
+            s.push(w[:, k * BLOCK:(k + 1) * BLOCK])
+        out = []
+        seen = _profiled(vr, small, lambda: out.append(s.push(w[:, 8 * BLOCK:9 * BLOCK])))
+        assert out[0][0].shape[1] == BLOCK
+    print('steady tta push:', {k: v for k, v in seen.items() if 'StreamSeg' in k or 'thin_conv_kernel<2, true>' in k})
+    assert seen.get(STREAM_KERNELS[1], 0) == 1 and seen.get('thin_conv_kernel<2, true>', 0) == 1, sorted(seen)
 
 
 def test_errors(vr, small, small_complex):

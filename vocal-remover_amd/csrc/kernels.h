@@ -14,7 +14,8 @@ struct HeadDst {
     int w_lo, w_hi;           // keep input columns [w_lo, w_hi); column w lands at w - w_lo
     int pad_rows;             // replicate the last input row this many extra times (1025 - 1024)
     // optional (mask heads only): a device table with one destination per batch item, used in place of p + n * dN -- the items of a
-    // batch may then land in different buffers (vr_stream_push_many: one mask ring per stream and pass).  item_pitch[n] is then the
+    // batch may then land in different buffers (Model::stream_run, for one stream as for many: one mask ring per stream and pass,
+    // a crop's columns anywhere in it).  item_pitch[n] is then the
     // row pitch of item n's buffer, in place of dH, and rows * item_pitch[n] its plane pitch, in place of dC.
     float* const* items;
     const int* item_pitch;
@@ -344,7 +345,9 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
 // step).  The kernels take a TABLE of them: one grid dimension is the table entry, sized for the largest entry, and a workgroup past
-// its own entry's frame or segment count leaves at once (vr_stream_push has one entry, vr_stream_push_many one per stream of a round).  Samples and frames carry their ABSOLUTE index in the stream; the device keeps rings: frame t of the complex spectrogram at
+// its own entry's frame or segment count leaves at once.  One executor fills and launches the table, Model::stream_run: vr_stream_push
+// gives it one entry, vr_stream_push_many one per stream of a round; the statistics pass alone reads a single entry (seg + e).
+// Samples and frames carry their ABSOLUTE index in the stream; the device keeps rings: frame t of the complex spectrogram at
 // column t % R of ring [2][bins][R], the mask of frame t at column t % RM of mask_a [2][bins][RM] (complex64 for a complex handle) and,
 // for the TTA pass, at column (t + shift) % RM of mask_b (the offline layout: crop j of a pass at column j * roi).
 struct StreamSeg {

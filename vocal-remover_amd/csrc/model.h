@@ -122,9 +122,6 @@ struct StreamState {
     unsigned* stats = nullptr;                           // launch_mag_pad's layout: 16-byte header + 2 * bins rows of partial maxima
     float* aff = nullptr;                                // 1 / c as the crop gather reads it
     double coef[2] = {0.0, 0.0};                         // MEASURE: the normaliser, valid after flush
-    // host copies of what a push sends to the device, alive until the push has drained
-    std::deque<StreamSeg> segs_h;
-    std::deque<std::vector<int2>> crops_h;
 };
 
 // The resident training set (vr_dataset_*): every song's cached spectrogram pair copied once into two device slabs of
@@ -497,17 +494,29 @@ private:
     Tensor run_lstm(LSTMMod& M, const Tensor& h);
     SrcSpec upsampled(const Tensor& t);
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)
-    struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off;
-                          StreamSeg* seg_d; int2* crops_d; float* gather; };
-    // One step of one stream in three parts, shared by stream_push (one stream) and stream_push_many (a round of streams):
-    // stream_step_plan takes the block in, asks stream_schedule what is ready, checks the rings and fills the StreamSeg; the caller
-    // launches; stream_step_commit flips the tail / carry buffers and moves the stream's counters on.
+    // the mask head of `cropsize`-wide crops (sigmoid or complex, the handle's kind): the columns [offset, cropsize - offset) to d.p / d.items
+    void crop_mask_head(const Tensor& f3, int cropsize, HeadDst d);
+    // `count` gathered crops, dense [count][nin][max_bin][cropsize] -> the network -> crop_mask_head
+    void run_dense_crops(float* dense, int count, int cropsize, const HeadDst& d);
+    struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off; };
+    // One stream's share of a push call.  The caller fills S .. need (stream_check gives need); the rest is where stream_run stands.
+    struct StreamPart {
+        StreamState* S; const float* wave; long long n; bool flush; float *y, *v; long long capacity, need;
+        long long at; bool flush_done; float *stage_in, *stage_y, *stage_v; StreamStepIO o;
+        std::vector<unsigned long long> st;                  // MEASURE, flush: the statistics rows on their way to S->coef
+    };
+    // The one executor of vr_stream_push (one part) and vr_stream_push_many: the steps of its parts in rounds, one set of launches per
+    // round.  A step of one stream is stream_step_plan (takes the block in, asks stream_schedule what is ready, checks the rings and
+    // fills the StreamSeg), its share of the round's launches, and stream_step_commit (flips the tail / carry buffers and moves the
+    // stream's counters on).
     struct StreamStepPlan { StreamSeg seg; StreamSchedule p; int new_frames, segments; bool emit; };
     struct StreamCrop { int entry, pass; long long idx; };          // crop idx of a pass of the stream at table entry `entry`
+    long long stream_check(const StreamState& S, const std::string& who, const float* wave, long long n, bool flush, const float* y,
+                           const float* v, bool out_on_dev, long long capacity) const;     // -> samples per channel the call returns
+    void stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev);
     StreamStepPlan stream_step_plan(StreamState& S, const StreamStepIO& io_, bool final);
     void stream_step_crops(const StreamState& S, const StreamStepPlan& sp, int entry, std::vector<StreamCrop>& list) const;
     void stream_step_commit(StreamState& S, StreamStepIO& io_, const StreamStepPlan& sp);
-    void stream_step(StreamState& S, StreamStepIO& io_, bool final);
     void tap(const std::string& name, const Tensor& t);
     bool dry = false;
     const float* dropout_dev = nullptr;                  // [5][N][Cmax] keep-masks (training), or null

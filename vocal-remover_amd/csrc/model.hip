@@ -1787,6 +1787,21 @@ void Model::run_crop_chunks(int patches, int bs, const std::function<void(int, i
     }
 }
 
+void Model::crop_mask_head(const Tensor& f3, int cropsize, HeadDst d) {
+    d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
+    if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
+    else launch_head_sigmoid(f3, out_w->dev, d, stream);
+}
+
+void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst& d) {
+    ws.reset();
+    Tensor x;
+    x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
+    x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = x.C * x.sC;
+    x.slope = 1.f;
+    crop_mask_head(run_net_window(x, offset, cropsize - offset), cropsize, d);
+}
+
 void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize, float* y_spec,
                          float* v_spec, bool out_on_dev, bool io_reserved, float* y_wave_d, float* v_wave_d, bool pcm16_out) {
     DeviceGuard dev_guard(device);
@@ -1860,12 +1875,9 @@ void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int bat
             x.p = mag + (size_t)first * roi; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
             x.sN = roi; x.sC = (long long)bins * Wpad; x.sH = Wpad;
             x.slope = 1.f;
-            Tensor f3 = run_net_window(x, offset, cropsize - offset);
             HeadDst d{};
             d.p = mask[ps] + (size_t)(is_complex ? 2 : 1) * first * roi; d.dN = roi; d.dC = (long long)bins * Wm[ps]; d.dH = Wm[ps];
-            d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
-            if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
-            else launch_head_sigmoid(f3, out_w->dev, d, stream);
+            crop_mask_head(run_net_window(x, offset, cropsize - offset), cropsize, d);
         };
         run_crop_chunks(patches, bs, run_crops);
     }
@@ -2156,19 +2168,11 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     fold_eval_affines();                    // before planning, as in forward_api
     plan_and_reserve(bs, cropsize, 0);
     auto run_crops = [&](int first, int count) {
-        ws.reset();
         float* dense = gather + (size_t)(first % bs) * crop_f;          // (batches start at multiples of bs: the part's slot in its batch)
         launch_crop_gather(tab_d, crops_d + first, count, is_complex, bins, max_bin, cropsize, aff, dense, stream);
-        Tensor x;
-        x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
-        x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
-        x.slope = 1.f;
-        Tensor f3 = run_net_window(x, offset, cropsize - offset);
         HeadDst d{};
         d.p = mask + (size_t)E * first * roi; d.dN = roi; d.dC = (long long)bins * W; d.dH = W;
-        d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
-        if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
-        else launch_head_sigmoid(f3, out_w->dev, d, stream);
+        run_dense_crops(dense, count, cropsize, d);
     };
     run_crop_chunks(crops_n, bs, run_crops);
     // ---- back end
@@ -2221,7 +2225,8 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
 // frames, a mask ring per pass, one hop of overlap-add carry per stem and channel, and the normaliser (StreamState); the staging
 // arena holds one push.  A push is cut into steps of at most `chunk_frames` new frames, so the rings have a fixed size; a step is
 // one STFT of the new frames, one statistics launch (running normaliser / MEASURE), the ready crops through run_crop_chunks, and one
-// masked iSTFT per stem over the frames that became final.
+// masked iSTFT per stem over the frames that became final.  One executor runs them, stream_run: vr_stream_push gives it one stream,
+// vr_stream_push_many a round of streams.
 // =====================================================================================================
 StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed) {
     VR_CHECK(n_fft >= 2 && hop > 0 && hop * 2 == n_fft, -2, "streaming needs hop_length == n_fft / 2 (the frame-tiled STFT / iSTFT kernels exist only there)");
@@ -2401,210 +2406,41 @@ void Model::stream_step_commit(StreamState& S, StreamStepIO& o, const StreamStep
     S.frames = sp.p.frames; S.crops[0] = sp.p.crops[0]; S.crops[1] = sp.p.crops[1];
 }
 
-void Model::stream_step(StreamState& S, StreamStepIO& o, bool final) {
-    const int bins = output_bin, E = is_complex ? 2 : 1, roi = S.roi, cropsize = S.cropsize;
-    const StreamStepPlan sp = stream_step_plan(S, o, final);
-    S.segs_h.push_back(sp.seg);
-    VR_HIP(hipMemcpyAsync(o.seg_d, &S.segs_h.back(), sizeof(StreamSeg), hipMemcpyHostToDevice, stream));
-    launch_stft_stream(plan, o.seg_d, 1, sp.new_frames, (double)o.blk_n, (double)sp.new_frames, stream);
-    if (sp.new_frames > 0 && (S.measure || S.running))
-        launch_stream_stats(o.seg_d, bins, sp.new_frames, reinterpret_cast<unsigned long long*>(S.stats) + 2, stream);
-    // ---- the crops that became ready: pass 0, then pass 1, as one list in device batches of bs
-    std::vector<StreamCrop> list;
-    stream_step_crops(S, sp, 0, list);
-    if (!list.empty()) {
-        if (S.running) {
-            if (is_complex) launch_coef_complex(S.stats, 2 * bins, 0, reinterpret_cast<float2*>(S.aff), stream);
-            else launch_coef_affine(S.stats, 2 * bins, 0, S.aff, stream);
-        }
-        const int n = (int)list.size();
-        S.crops_h.emplace_back((size_t)n);
-        std::vector<int2>& cl = S.crops_h.back();
-        for (int k = 0; k < n; ++k) cl[k] = make_int2(0, (int)(list[k].idx * roi - offset - (list[k].pass ? roi / 2 : 0)));
-        VR_HIP(hipMemcpyAsync(o.crops_d, cl.data(), sizeof(int2) * n, hipMemcpyHostToDevice, stream));
-        fold_eval_affines();                    // before planning, as in forward_api
-        plan_and_reserve(S.bs, cropsize, 0);
-        const size_t crop_f = (size_t)nin * max_bin * cropsize;
-        auto run_crops = [&](int first, int count) {
-            ws.reset();
-            float* dense = o.gather + (size_t)(first % S.bs) * crop_f;
-            launch_stream_gather(o.seg_d, o.crops_d + first, count, is_complex, bins, max_bin, cropsize, dense, stream);
-            Tensor x;
-            x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
-            x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
-            x.slope = 1.f;
-            Tensor f3 = run_net_window(x, offset, cropsize - offset);
-            // one head launch per run of crops that are neighbours in one mask ring
-            for (int k = 0; k < count;) {
-                const StreamCrop c0 = list[(size_t)first + k];
-                const long long col = c0.idx * roi % S.RM;
-                int run = 1;
-                while (k + run < count && list[(size_t)first + k + run].pass == c0.pass && col + (long long)(run + 1) * roi <= S.RM) ++run;
-                Tensor part = f3;
-                part.p = f3.p + (long long)k * f3.sN; part.N = run;
-                HeadDst d{};
-                d.p = S.mask[c0.pass] + (size_t)E * col; d.dN = roi; d.dC = (long long)bins * S.RM; d.dH = S.RM;
-                d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
-                if (is_complex) launch_head_complex(part, out_w->dev, d, stream);
-                else launch_head_sigmoid(part, out_w->dev, d, stream);
-                k += run;
-            }
-        };
-        run_crop_chunks(n, S.bs, run_crops);
+// The checks of one stream's share of a push call that vr_stream_push and vr_stream_push_many have in common, `who` in front of
+// every message; nothing here touches the device or the stream.
+long long Model::stream_check(const StreamState& S, const std::string& who, const float* wave, long long n, bool flush, const float* y,
+                              const float* v, bool out_on_dev, long long capacity) const {
+    VR_CHECK(!S.broken, -2, who + "this stream failed in an earlier call: close it");
+    VR_CHECK(!S.flushed, -2, who + (flush ? "the stream is already flushed" : "push after flush"));
+    VR_CHECK(n >= 0 && (n == 0 || wave), -2, who + "null or negative input");
+    long long need = 0;
+    try {
+        const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
+        const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, flush);
+        need = S.measure ? 0 : after.samples_out - before.samples_out;
+    } catch (const Error& e) {
+        throw Error(e.code, who + e.what());
     }
-    if (sp.emit)
-        for (int which = 0; which < 2; ++which)
-            launch_istft_stream(plan, o.seg_d, 1, sp.segments, (double)sp.segments, is_complex, S.tta, which, stream, S.pcm16);
-    stream_step_commit(S, o, sp);
-}
-
-void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
-                        long long capacity, long long* n_out) {
-    // ---- arguments and the schedule of this call: nothing here touches the device
-    VR_CHECK(!S.broken, -2, "this stream failed in an earlier call: close it");
-    VR_CHECK(!S.flushed, -2, flush ? "the stream is already flushed" : "push after flush");
-    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
-    VR_CHECK(n >= 0 && (n == 0 || wave), -2, "null or negative input");
-    const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
-    const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, flush);
-    const long long need = S.measure ? 0 : after.samples_out - before.samples_out;
     if (need > 0)
-        VR_CHECK(y && v && capacity >= need, -2, "output capacity " + std::to_string(capacity) + " is too small: this call returns " +
+        VR_CHECK(y && v && capacity >= need, -2, who + "output capacity " + std::to_string(capacity) + " is too small: this call returns " +
                                                      std::to_string(need) + " samples per channel");
     if (S.pcm16 && need > 0 && out_on_dev)
-        VR_CHECK(reinterpret_cast<uintptr_t>(y) % 2 == 0 && reinterpret_cast<uintptr_t>(v) % 2 == 0, -2, "the int16 outputs are not 2-byte aligned");
-    if (n_out) *n_out = 0;
-    if (n == 0 && !flush) return;
-
-    DeviceGuard dev_guard(device);
-    const size_t crop_f = (size_t)nin * max_bin * S.cropsize;
-    float *stage_in = nullptr, *stage_y = nullptr, *stage_v = nullptr;
-    StreamStepIO o{};
-    auto carve = [&](Arena& A) {
-        o.seg_d = static_cast<StreamSeg*>(A.alloc(sizeof(StreamSeg)));
-        o.crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * 2 * (S.RM / S.roi)));
-        if (!S.measure) o.gather = A.allocf((size_t)S.bs * crop_f + 4096);
-        if (!on_dev && n > 0) stage_in = A.allocf((size_t)2 * n);
-        if (!out_on_dev && need > 0) { stage_y = A.allocf((size_t)2 * need + 4); stage_v = A.allocf((size_t)2 * need + 4); }
-    };
-    Arena dry_a;
-    dry_a.dry = true;
-    carve(dry_a);
-    ensure_io(dry_a.peak + 65536);
-    io.reset();
-    carve(io);
-    S.broken = true;                            // until the call has gone through: a failure half way leaves the rings undefined
-    if (stage_in) VR_HIP(hipMemcpyAsync(stage_in, wave, (size_t)2 * n * sizeof(float), hipMemcpyHostToDevice, stream));
-    const float* src = on_dev ? wave : stage_in;
-    o.y = out_on_dev ? y : stage_y; o.v = out_on_dev ? v : stage_v;
-    o.out_pitch = out_on_dev ? capacity : need;
-    o.blk_pitch = n;
-    const long long chunk = (long long)S.chunk_frames * hop;
-    for (long long at = 0; at < n;) {
-        long long take = std::min(chunk, n - at);
-        if (S.running)                          // the running normaliser of crop i covers exactly the frames below its window's end
-            take = std::min(take, ((S.crops[0] + 1) * S.roi + offset) * (long long)hop - S.samples);
-        o.blk = src + at; o.blk_n = take;
-        stream_step(S, o, false);
-        at += take;
-    }
-    if (flush) {
-        o.blk = src; o.blk_n = 0;
-        stream_step(S, o, true);
-        S.flushed = true;
-    }
-    VR_CHECK(S.measure || o.out_off == need, -4, "stream schedule mismatch (planning bug)");
-    std::vector<unsigned long long> st;
-    if (flush && S.measure) {
-        st.resize((size_t)2 * 2 * output_bin);
-        VR_HIP(hipMemcpyAsync(st.data(), reinterpret_cast<unsigned long long*>(S.stats) + 2, st.size() * 8, hipMemcpyDeviceToHost, stream));
-    }
-    if (!out_on_dev && need > 0 && S.pcm16) {       // interleaved int16: `need` frames of 4 bytes, one piece
-        VR_HIP(hipMemcpyAsync(y, stage_y, (size_t)need * 4, hipMemcpyDeviceToHost, stream));
-        VR_HIP(hipMemcpyAsync(v, stage_v, (size_t)need * 4, hipMemcpyDeviceToHost, stream));
-    } else if (!out_on_dev && need > 0) {
-        VR_HIP(hipMemcpy2DAsync(y, (size_t)capacity * 4, stage_y, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
-        VR_HIP(hipMemcpy2DAsync(v, (size_t)capacity * 4, stage_v, (size_t)need * 4, (size_t)need * 4, 2, hipMemcpyDeviceToHost, stream));
-    }
-    VR_HIP(hipStreamSynchronize(stream));
-    S.segs_h.clear(); S.crops_h.clear();
-    if (flush && S.measure) {
-        unsigned mxb = 0;
-        unsigned long long key = ((unsigned long long)host_ord32(0.f) << 32) | host_ord32(0.f);
-        for (int r = 0; r < 2 * output_bin; ++r) {
-            mxb = std::max(mxb, (unsigned)st[2 * r]);           // non-negative floats order like their bit patterns
-            key = std::max(key, st[2 * r + 1]);
-        }
-        if (S.tta) {
-            S.coef[0] = host_unord32((unsigned)(key >> 32)); S.coef[1] = host_unord32((unsigned)(key & 0xffffffffu));
-        } else {
-            float m;
-            memcpy(&m, &mxb, 4);
-            S.coef[0] = m; S.coef[1] = 0.0;
-        }
-    }
-    S.broken = false;
-    if (n_out) *n_out = need;
+        VR_CHECK(reinterpret_cast<uintptr_t>(y) % 2 == 0 && reinterpret_cast<uintptr_t>(v) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
+    return need;
 }
 
-// vr_stream_push_many: the steps of several streams of this handle, taken together in rounds.  Round r holds step r of every stream that
-// still has one -- the cut of stream_push, the flush step last -- so a stream's steps, and with them its crops and its numbers, are the
-// ones it would take alone; what the streams share is the launches: one StreamSeg table and one crop list per round, one STFT over the
-// table, the ready crops of all streams and both passes as ONE list through run_crop_chunks in parts of `batchsize` (one gather, one
+// The steps of the streams of one push call, taken together in rounds.  Round r holds step r of every part that still has one -- at
+// most chunk_frames new frames, the flush step last -- so a stream's steps, and with them its crops and its numbers, are the same
+// whichever streams share the call; what the parts share is the launches: one StreamSeg table and one crop list per round, one STFT
+// over the table, the ready crops of all streams and both passes as ONE list through run_crop_chunks in parts of `bs` (one gather, one
 // network pass and one head launch per part: the head scatters every item into its own stream's mask ring through a pointer table),
 // one masked iSTFT per stem over the table.  Per call: inputs in, outputs out, one drain.
-void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float* const* wave, bool on_dev, const long long* n_in, const int* flush,
-                             int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out) {
-    // ---- arguments and the schedule of this call: nothing here touches the device or a stream
-    VR_CHECK(n_streams >= 1, -2, "n_streams must be positive");
-    VR_CHECK(Sv && n_in, -2, "null table");
-    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
-    struct Part { StreamState* S; int k; bool fl; long long n, need, at; float *stage_in, *stage_y, *stage_v; StreamStepIO o; bool last_done; };
-    std::vector<Part> parts;
-    int bs = batchsize;
-    for (int k = 0; k < n_streams; ++k) {
-        const std::string who = "stream " + std::to_string(k) + ": ";
-        VR_CHECK(Sv[k], -2, who + "null stream (closed?)");
-        StreamState& S = *Sv[k];
-        for (int j = 0; j < k; ++j) VR_CHECK(Sv[j] != Sv[k], -2, who + "the same stream as stream " + std::to_string(j));
-        VR_CHECK(S.cropsize == Sv[0]->cropsize, -2, who + "cropsize " + std::to_string(S.cropsize) + " differs from stream 0's " +
-                                                        std::to_string(Sv[0]->cropsize) + ": the streams of one call share device batches");
-        VR_CHECK(!S.measure, -2, who + "a VR_STREAM_MEASURE stream is not taken by vr_stream_push_many: use vr_stream_push");
-        VR_CHECK(!S.running, -2, who + "a running-normaliser stream (coef 0) is not taken by vr_stream_push_many: its steps are cut per crop, "
-                                       "use vr_stream_push");
-        VR_CHECK(!S.broken, -2, who + "this stream failed in an earlier call: close it");
-        VR_CHECK(S.pcm16 == Sv[0]->pcm16, -2, who + "VR_STREAM_PCM16_OUT differs from stream 0's: the streams of one call share the masked iSTFT "
-                                                   "launch, which stores one sample format");
-        const bool fl = flush && flush[k];
-        VR_CHECK(!S.flushed, -2, who + (fl ? "the stream is already flushed" : "push after flush"));
-        const long long n = n_in[k];
-        VR_CHECK(n >= 0 && (n == 0 || (wave && wave[k])), -2, who + "null or negative input");
-        long long need = 0;
-        try {
-            const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
-            const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, fl);
-            need = after.samples_out - before.samples_out;
-        } catch (const Error& e) {
-            throw Error(e.code, who + e.what());
-        }
-        if (need > 0)
-            VR_CHECK(y && v && capacity && y[k] && v[k] && capacity[k] >= need, -2,
-                     who + "output capacity " + std::to_string(capacity ? capacity[k] : 0) + " is too small: this call returns " +
-                         std::to_string(need) + " samples per channel");
-        if (S.pcm16 && need > 0 && out_on_dev)
-            VR_CHECK(reinterpret_cast<uintptr_t>(y[k]) % 2 == 0 && reinterpret_cast<uintptr_t>(v[k]) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
-        if (batchsize <= 0) bs = std::max(bs, S.bs);
-        if (n == 0 && !fl) continue;                 // untouched
-        Part p{};
-        p.S = &S; p.k = k; p.fl = fl; p.n = n; p.need = need;
-        parts.push_back(p);
-    }
-    if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = 0;
-    if (parts.empty()) return;
+void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev) {
     const int np = (int)parts.size();
-    const int cropsize = Sv[0]->cropsize, roi = Sv[0]->roi, bins = output_bin, E = is_complex ? 2 : 1;
+    const int cropsize = parts[0].S->cropsize, roi = parts[0].S->roi, bins = output_bin, E = is_complex ? 2 : 1;
     size_t list_cap = 0;
-    for (const Part& p : parts) list_cap += (size_t)2 * (p.S->RM / roi);
+    bool any_crops = false;                          // (a MEASURE stream runs no crops: no gather buffer for it)
+    for (const StreamPart& p : parts) { list_cap += (size_t)2 * (p.S->RM / roi); any_crops = any_crops || !p.S->measure; }
 
     DeviceGuard dev_guard(device);
     // ---- the staging arena: carved twice, first dry for its size
@@ -2615,8 +2451,8 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
     auto carve = [&](Arena& A) {
         seg_d = static_cast<StreamSeg*>(A.alloc(sizeof(StreamSeg) * np));
         list_d = static_cast<unsigned long long*>(A.alloc(24 * list_cap));
-        gather = A.allocf((size_t)bs * crop_f + 4096);
-        for (Part& p : parts) {
+        if (any_crops) gather = A.allocf((size_t)bs * crop_f + 4096);
+        for (StreamPart& p : parts) {
             p.stage_in = (!on_dev && p.n > 0) ? A.allocf((size_t)2 * p.n) : nullptr;
             p.stage_y = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
             p.stage_v = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
@@ -2628,18 +2464,18 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
     ensure_io(dry_a.peak + 65536);
     io.reset();
     carve(io);
-    for (Part& p : parts) p.S->broken = true;       // until the call has gone through: a failure half way leaves the rings undefined
+    for (StreamPart& p : parts) p.S->broken = true;  // until the call has gone through: a failure half way leaves the rings undefined
     // host copies of what the rounds send to the device, alive until the call has drained
     std::deque<std::vector<StreamSeg>> segs_h;
     std::deque<std::vector<unsigned long long>> lists_h;
     try {
-        for (Part& p : parts) {
-            if (p.stage_in) VR_HIP(hipMemcpyAsync(p.stage_in, wave[p.k], (size_t)2 * p.n * sizeof(float), hipMemcpyHostToDevice, stream));
+        for (StreamPart& p : parts) {
+            if (p.stage_in) VR_HIP(hipMemcpyAsync(p.stage_in, p.wave, (size_t)2 * p.n * sizeof(float), hipMemcpyHostToDevice, stream));
+            p.at = 0; p.flush_done = false;
             p.o = StreamStepIO{};
-            p.o.blk = on_dev ? (p.n > 0 ? wave[p.k] : nullptr) : p.stage_in;
             p.o.blk_pitch = p.n;
-            p.o.y = out_on_dev ? (y ? y[p.k] : nullptr) : p.stage_y; p.o.v = out_on_dev ? (v ? v[p.k] : nullptr) : p.stage_v;
-            p.o.out_pitch = out_on_dev ? (capacity ? capacity[p.k] : 0) : p.need;
+            p.o.y = out_on_dev ? p.y : p.stage_y; p.o.v = out_on_dev ? p.v : p.stage_v;
+            p.o.out_pitch = out_on_dev ? p.capacity : p.need;
         }
         std::vector<int> live;                       // the parts that take a step in this round
         std::vector<StreamStepPlan> plans;
@@ -2647,20 +2483,19 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
         for (;;) {
             live.clear(); plans.clear(); list.clear();
             for (int i = 0; i < np; ++i) {
-                Part& p = parts[i];
-                if (p.at >= p.n && !(p.fl && !p.last_done)) continue;
+                StreamPart& p = parts[i];
                 StreamState& S = *p.S;
-                const float* src = p.o.blk_pitch > 0 ? (on_dev ? wave[p.k] : p.stage_in) : nullptr;
-                bool final = false;
-                if (p.at < p.n) {
-                    const long long take = std::min((long long)S.chunk_frames * hop, p.n - p.at);
-                    p.o.blk = src + p.at; p.o.blk_n = take;
-                    p.at += take;
-                } else {
-                    p.o.blk = src; p.o.blk_n = 0;
-                    final = true;
-                    p.last_done = true;
-                }
+                // the next block of this part: at most chunk_frames new frames; a running normaliser's block also ends with the
+                // window of its next crop, so that crop i's statistics cover exactly the frames below its window's end; the flush
+                // step takes no samples and comes last
+                const bool final = p.at >= p.n;
+                if (final && (!p.flush || p.flush_done)) continue;
+                long long take = std::min((long long)S.chunk_frames * hop, p.n - p.at);
+                if (S.running) take = std::min(take, ((S.crops[0] + 1) * S.roi + offset) * (long long)hop - S.samples);
+                const float* src = p.n > 0 ? (on_dev ? p.wave : p.stage_in) : nullptr;
+                p.o.blk = final ? src : src + p.at; p.o.blk_n = take;
+                p.at += take;
+                p.flush_done = final;
                 const int entry = (int)live.size();
                 plans.push_back(stream_step_plan(S, p.o, final));
                 stream_step_crops(S, plans.back(), entry, list);
@@ -2682,6 +2517,15 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
             }
             VR_HIP(hipMemcpyAsync(seg_d, segs_h.back().data(), sizeof(StreamSeg) * ne, hipMemcpyHostToDevice, stream));
             launch_stft_stream(plan, seg_d, ne, max_new, sum_blk, sum_new, stream);
+            for (int e = 0; e < ne; ++e) {           // the statistics of a MEASURE / running stream, and a running stream's 1 / c before its crops
+                const StreamState& S = *parts[live[e]].S;
+                if (plans[e].new_frames > 0 && (S.measure || S.running))
+                    launch_stream_stats(seg_d + e, bins, plans[e].new_frames, reinterpret_cast<unsigned long long*>(S.stats) + 2, stream);
+                if (S.running && plans[e].p.crops[0] > S.crops[0]) {
+                    if (is_complex) launch_coef_complex(S.stats, 2 * bins, 0, reinterpret_cast<float2*>(S.aff), stream);
+                    else launch_coef_affine(S.stats, 2 * bins, 0, S.aff, stream);
+                }
+            }
             // ---- the crops of all streams that became ready: stream-major, pass 0 then pass 1 inside a stream, in device batches of bs
             if (!list.empty()) {
                 const int nc = (int)list.size();
@@ -2700,39 +2544,34 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
                 VR_HIP(hipMemcpyAsync(list_d, lh.data(), lh.size() * 8, hipMemcpyHostToDevice, stream));
                 const int2* crops_d = reinterpret_cast<const int2*>(list_d);
                 float* const* items_d = reinterpret_cast<float* const*>(list_d + nc);
+                const int* pitch_d = reinterpret_cast<const int*>(list_d + 2 * (size_t)nc);
                 fold_eval_affines();                // before planning, as in forward_api
                 plan_and_reserve(bs, cropsize, 0);
-                const int* pitch_d = reinterpret_cast<const int*>(list_d + 2 * (size_t)nc);
                 auto run_crops = [&](int first, int count) {
-                    ws.reset();
                     float* dense = gather + (size_t)(first % bs) * crop_f;
                     launch_stream_gather(seg_d, crops_d + first, count, is_complex, bins, max_bin, cropsize, dense, stream);
-                    Tensor x;
-                    x.p = dense; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
-                    x.sH = cropsize; x.sC = (long long)max_bin * cropsize; x.sN = (long long)crop_f;
-                    x.slope = 1.f;
-                    Tensor f3 = run_net_window(x, offset, cropsize - offset);
                     HeadDst d{};
                     d.items = items_d + first; d.item_pitch = pitch_d + first;
-                    d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
-                    if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
-                    else launch_head_sigmoid(f3, out_w->dev, d, stream);
+                    run_dense_crops(dense, count, cropsize, d);
                 };
                 run_crop_chunks(nc, bs, run_crops);
             }
-            if (max_seg > 0)
-                for (int which = 0; which < 2; ++which)
-                    launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream, Sv[0]->pcm16);
+            for (int which = 0; which < 2; ++which)     // (no launch when no entry has a final segment)
+                launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream, parts[0].S->pcm16);
             for (int e = 0; e < ne; ++e) stream_step_commit(*parts[live[e]].S, parts[live[e]].o, plans[e]);
         }
-        for (Part& p : parts) {
+        for (StreamPart& p : parts) {
             VR_CHECK(p.o.out_off == p.need, -4, "stream schedule mismatch (planning bug)");
-            if (!out_on_dev && p.need > 0 && p.S->pcm16) {
-                VR_HIP(hipMemcpyAsync(y[p.k], p.stage_y, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
-                VR_HIP(hipMemcpyAsync(v[p.k], p.stage_v, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
+            if (p.flush && p.S->measure) {
+                p.st.resize((size_t)2 * 2 * bins);
+                VR_HIP(hipMemcpyAsync(p.st.data(), reinterpret_cast<unsigned long long*>(p.S->stats) + 2, p.st.size() * 8, hipMemcpyDeviceToHost, stream));
+            }
+            if (!out_on_dev && p.need > 0 && p.S->pcm16) {      // interleaved int16: `need` frames of 4 bytes, one piece
+                VR_HIP(hipMemcpyAsync(p.y, p.stage_y, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpyAsync(p.v, p.stage_v, (size_t)p.need * 4, hipMemcpyDeviceToHost, stream));
             } else if (!out_on_dev && p.need > 0) {
-                VR_HIP(hipMemcpy2DAsync(y[p.k], (size_t)capacity[p.k] * 4, p.stage_y, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
-                VR_HIP(hipMemcpy2DAsync(v[p.k], (size_t)capacity[p.k] * 4, p.stage_v, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpy2DAsync(p.y, (size_t)p.capacity * 4, p.stage_y, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpy2DAsync(p.v, (size_t)p.capacity * 4, p.stage_v, (size_t)p.need * 4, (size_t)p.need * 4, 2, hipMemcpyDeviceToHost, stream));
             }
         }
         VR_HIP(hipStreamSynchronize(stream));
@@ -2740,10 +2579,75 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
         hipStreamSynchronize(stream);               // the host copies above must outlive every copy that is still in flight
         throw;
     }
-    for (Part& p : parts) {
-        p.S->broken = false;
-        if (n_out) n_out[p.k] = p.need;
+    for (StreamPart& p : parts) {
+        StreamState& S = *p.S;
+        if (p.flush && S.measure) {
+            unsigned mxb = 0;
+            unsigned long long key = ((unsigned long long)host_ord32(0.f) << 32) | host_ord32(0.f);
+            for (int r = 0; r < 2 * bins; ++r) {
+                mxb = std::max(mxb, (unsigned)p.st[2 * r]);         // non-negative floats order like their bit patterns
+                key = std::max(key, p.st[2 * r + 1]);
+            }
+            if (S.tta) {
+                S.coef[0] = host_unord32((unsigned)(key >> 32)); S.coef[1] = host_unord32((unsigned)(key & 0xffffffffu));
+            } else {
+                float m;
+                memcpy(&m, &mxb, 4);
+                S.coef[0] = m; S.coef[1] = 0.0;
+            }
+        }
+        S.broken = false;
     }
+}
+
+void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
+                        long long capacity, long long* n_out) {
+    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    std::vector<StreamPart> parts(1);
+    StreamPart& p = parts[0];
+    p.S = &S; p.wave = wave; p.n = n; p.flush = flush; p.y = y; p.v = v; p.capacity = capacity;
+    p.need = stream_check(S, "", wave, n, flush, y, v, out_on_dev, capacity);
+    if (n_out) *n_out = 0;
+    if (n == 0 && !flush) return;
+    stream_run(parts, S.bs, on_dev, out_on_dev);
+    if (n_out) *n_out = p.need;
+}
+
+// vr_stream_push_many: stream k gets n_in[k] more samples and, flush[k], its end.  With one stream it is stream_push.
+void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float* const* wave, bool on_dev, const long long* n_in, const int* flush,
+                             int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out) {
+    // ---- arguments and the schedule of this call: nothing here touches the device or a stream
+    VR_CHECK(n_streams >= 1, -2, "n_streams must be positive");
+    VR_CHECK(Sv && n_in, -2, "null table");
+    VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    std::vector<StreamPart> parts;
+    std::vector<int> part_k;
+    int bs = batchsize;
+    for (int k = 0; k < n_streams; ++k) {
+        const std::string who = "stream " + std::to_string(k) + ": ";
+        VR_CHECK(Sv[k], -2, who + "null stream (closed?)");
+        StreamState& S = *Sv[k];
+        for (int j = 0; j < k; ++j) VR_CHECK(Sv[j] != Sv[k], -2, who + "the same stream as stream " + std::to_string(j));
+        VR_CHECK(S.cropsize == Sv[0]->cropsize, -2, who + "cropsize " + std::to_string(S.cropsize) + " differs from stream 0's " +
+                                                        std::to_string(Sv[0]->cropsize) + ": the streams of one call share device batches");
+        VR_CHECK(!S.measure, -2, who + "a VR_STREAM_MEASURE stream is not taken by vr_stream_push_many: use vr_stream_push");
+        VR_CHECK(!S.running, -2, who + "a running-normaliser stream (coef 0) is not taken by vr_stream_push_many: its steps are cut per crop, "
+                                       "use vr_stream_push");
+        VR_CHECK(S.pcm16 == Sv[0]->pcm16, -2, who + "VR_STREAM_PCM16_OUT differs from stream 0's: the streams of one call share the masked iSTFT "
+                                                   "launch, which stores one sample format");
+        StreamPart p{};
+        p.S = &S; p.wave = wave ? wave[k] : nullptr; p.n = n_in[k]; p.flush = flush && flush[k];
+        p.y = y ? y[k] : nullptr; p.v = v ? v[k] : nullptr; p.capacity = capacity ? capacity[k] : 0;
+        p.need = stream_check(S, who, p.wave, p.n, p.flush, p.y, p.v, out_on_dev, p.capacity);
+        if (batchsize <= 0) bs = std::max(bs, S.bs);
+        if (p.n == 0 && !p.flush) continue;          // untouched
+        parts.push_back(p);
+        part_k.push_back(k);
+    }
+    if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = 0;
+    if (parts.empty()) return;
+    stream_run(parts, bs, on_dev, out_on_dev);
+    if (n_out) for (size_t i = 0; i < parts.size(); ++i) n_out[part_k[i]] = parts[i].need;
 }
 
 // =====================================================================================================
