@@ -161,7 +161,11 @@ int vr_istft(vr_handle h, const float* spec, int spec_on_device, int T, float* w
 /* Separator(model, device, batchsize, cropsize).separate / separate_tta     inference.py:70-102
  * spec [2,bins,T] complex64 -> y_spec (instruments), v_spec (vocals), same shape.
  * `tta` is a flag word: bit 0 = --tta (separate_tta), bit 1 = --postprocess (spec_utils.merge_artifacts,
- * lib/spec_utils.py:60-93, inference.py:27-30).  batchsize <= 0: all crops of a pass in one device batch. */
+ * lib/spec_utils.py:60-93, inference.py:27-30).
+ * This, vr_separate_wave and vr_separate_pcm are the many-songs call below with one song (one executor).  batchsize counts crops of
+ * the song's crop list -- pass 0, then for --tta pass 1, so the two passes may share a device batch -- and is capped at the crops
+ * of the longer pass, T / roi + 1 (+ 1 with --tta), roi = cropsize - 2 * offset; batchsize <= 0 means that cap: all crops of a
+ * pass in one device batch, never more.  Errors of these three name no song. */
 int vr_separate(vr_handle h, const float* spec, int spec_on_device, int T, int tta, int batchsize,
                 int cropsize, float* y_spec, float* v_spec, int out_on_device);
 

@@ -237,9 +237,11 @@ def test_launch_count_does_not_grow_with_songs(vr, small):
     specs = [vr.spec_utils.wave_to_spectrogram(w, 256, 512) for w in waves[:3]]
     seen = _profiled(vr, small, lambda: sp.separate_many(specs))
     assert seen.get('apply_mask_kernel<false, vr::SongSeg const>', 0) == 1, sorted(seen)
-    # and the one-song entry points still run the forms they ran before
-    one = _profiled(vr, small, lambda: sp.separate_wave(waves[0]))
-    assert not [n for n in one if 'SongSeg' in n or n.startswith('coef_affine_kernel<false, true')], sorted(one)
+    # and a one-song entry point is the same executor with one song: the same launches, the table forms among them
+    sp3 = vr.inference.Separator(small, DEV, batchsize=3, cropsize=160, postprocess=True)
+    one = _profiled(vr, small, lambda: sp3.separate_wave(waves[0]))
+    assert one == _profiled(vr, small, lambda: sp3.separate_wave_many(waves[:1]))
+    assert not [n for n in TABLE_KERNELS if 'apply_mask' not in n and one.get(n, 0) < 1], sorted(one)
 
 
 def test_errors_name_the_song_and_leave_the_handle_usable(vr, small):

@@ -193,7 +193,8 @@ int vr_separate(vr_handle h, const float* spec, int spec_on_device, int T, int t
     NEED(h);
     return guard([&] {
         VR_CHECK(spec && y_spec && v_spec, VR_ERR_BAD_ARGUMENT, "null argument");
-        h->m.separate_api(spec, spec_on_device != 0, T, tta, batchsize, cropsize, y_spec, v_spec, out_on_device != 0);
+        h->m.separate_run(1, &spec, spec_on_device != 0, &T, nullptr, tta, batchsize, cropsize, &y_spec, &v_spec, out_on_device != 0, nullptr,
+                          nullptr, /*solo=*/true);
     });
 }
 
@@ -202,7 +203,9 @@ int vr_separate_wave(vr_handle h, const float* wave, int wave_on_device, int64_t
     NEED(h);
     return guard([&] {
         VR_CHECK(wave && y_wave && v_wave, VR_ERR_BAD_ARGUMENT, "null argument");
-        h->m.separate_wave_api(wave, wave_on_device != 0, L, tta, batchsize, cropsize, y_wave, v_wave, out_on_device != 0);
+        const long long len = L;
+        h->m.separate_run(1, &wave, wave_on_device != 0, nullptr, &len, tta, batchsize, cropsize, &y_wave, &v_wave, out_on_device != 0, nullptr,
+                          nullptr, /*solo=*/true);
     });
 }
 
@@ -218,8 +221,8 @@ int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int sp
     if (!many_args_ok(n_songs, specs, T, y_specs, v_specs)) return VR_ERR_BAD_ARGUMENT;
     NEED(h);
     return guard([&] {
-        h->m.separate_many_api(n_songs, specs, specs_on_device != 0, T, nullptr, tta, batchsize, cropsize, y_specs, v_specs,
-                               out_on_device != 0);
+        h->m.separate_run(n_songs, specs, specs_on_device != 0, T, nullptr, tta, batchsize, cropsize, y_specs, v_specs,
+                          out_on_device != 0);
     });
 }
 
@@ -229,8 +232,8 @@ int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, i
     NEED(h);
     return guard([&] {
         std::vector<long long> len(L, L + n_songs);
-        h->m.separate_many_api(n_songs, waves, waves_on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, y_waves, v_waves,
-                               out_on_device != 0);
+        h->m.separate_run(n_songs, waves, waves_on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, y_waves, v_waves,
+                          out_on_device != 0);
     });
 }
 
@@ -264,7 +267,11 @@ int vr_separate_pcm(vr_handle h, const void* bytes, int on_device, int64_t frame
     NEED(h);
     return guard([&] {
         VR_CHECK(bytes && y && v, VR_ERR_BAD_ARGUMENT, "null argument");
-        h->m.separate_pcm_api(bytes, on_device != 0, frames, channels, fmt, tta, batchsize, cropsize, y, v, out_on_device != 0);
+        const long long len = frames;
+        const float* in = static_cast<const float*>(bytes);
+        float *ys = reinterpret_cast<float*>(y), *vs = reinterpret_cast<float*>(v);
+        h->m.separate_run(1, &in, on_device != 0, nullptr, &len, tta, batchsize, cropsize, &ys, &vs, out_on_device != 0, &channels, &fmt,
+                          /*solo=*/true);
     });
 }
 
@@ -275,9 +282,8 @@ int vr_separate_pcm_many(vr_handle h, int n_songs, const void* const* bytes, int
     NEED(h);
     return guard([&] {
         std::vector<long long> len(frames, frames + n_songs);
-        h->m.separate_many_api(n_songs, reinterpret_cast<const float* const*>(bytes), on_device != 0, nullptr, len.data(), tta, batchsize,
-                               cropsize, reinterpret_cast<float* const*>(y), reinterpret_cast<float* const*>(v), out_on_device != 0, channels,
-                               fmt);
+        h->m.separate_run(n_songs, reinterpret_cast<const float* const*>(bytes), on_device != 0, nullptr, len.data(), tta, batchsize,
+                          cropsize, reinterpret_cast<float* const*>(y), reinterpret_cast<float* const*>(v), out_on_device != 0, channels, fmt);
     });
 }
 

@@ -212,24 +212,17 @@ public:
     // ---- signal path ----
     void stft_api(const float* wave, bool on_dev, long long L, float* spec, bool spec_on_dev);
     void istft_api(const float* spec, bool on_dev, int T, float* wave, bool wave_on_dev);
-    // spec [2,bins,T] complex64 -> y_spec, v_spec (same shape)
-    void separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize,
-                      float* y_spec, float* v_spec, bool out_on_dev, bool io_reserved = false,
-                      float* y_wave_d = nullptr, float* v_wave_d = nullptr, bool pcm16_out = false);
-    // wave [2,L] -> y_wave, v_wave [2, hop*(T-1)]: whole inference.py pipeline, device resident
-    void separate_wave_api(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                           float* y_wave, float* v_wave, bool out_on_dev);
-    // n_songs spectrograms (L null: specs [2,bins,T[s]] -> y / v spectrograms) or waves (L given: [2,L[s]] -> y / v waves) in one call
-    void separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta,
-                           int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
-                           const int* pcm_fmt = nullptr);
+    // The offline executor (vr_separate* and vr_separate*_many): n_songs spectrograms (L null: specs [2,bins,T[s]] -> y / v spectrograms)
+    // or waves (L given: [2,L[s]] -> y / v waves [2, hop*(T-1)], the whole inference.py pipeline device resident) in one call; with
+    // pcm_fmt the waves are sample bytes and the stems int16 [samples][2].  solo: a one-song entry point's call of one song.
+    void separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta, int batchsize,
+                      int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
+                      const int* pcm_fmt = nullptr, bool solo = false);
     // ---- WAV sample bytes in, PCM16 out (vr_*_pcm*; csrc/pcm.h): the sample-format forms of the frame-tiled STFT / iSTFT ----
     bool pcm_available() const;                           // the frame-tiled kernels, whose forms these are, exist on this handle
     void check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const;      // availability, format, channels, a device pointer's alignment
     void stft_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, float* spec, bool spec_on_dev);
     void istft_pcm16_api(const float* spec, bool on_dev, int T, int16_t* out, bool out_on_dev);
-    void separate_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, int tta, int batchsize, int cropsize,
-                          int16_t* y, int16_t* v, bool out_on_dev);
     void run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops);
     // ---- streaming separation (vr_stream_*) ----
     StreamState* stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im);
@@ -241,8 +234,6 @@ public:
                           int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out);
     void stream_close(StreamState* S);
     void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
-    void separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                            float* y_wave, float* v_wave, bool out_on_dev, const PcmIn* pcm = nullptr);
 
     // ---- debug / test hooks ----
     void debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,
@@ -299,7 +290,6 @@ public:
     void reset_adam_state();
     void profile_end(double* conv_ms, double* conv_flops, double* conv_bytes, int* launches);
 
-    std::chrono::steady_clock::time_point enq_t1; bool enq_have = false;   // VR_ENQ_TIMING diagnostics (model.hip: separate_wave_body)
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;          // eval mode: the high-band chain runs here
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -1730,16 +1730,6 @@ static void make_padding(int width, int cropsize, int offset, int& left, int& ri
     right = roi - (width % roi) + left;
 }
 
-// Separator.separate / separate_tta (inference.py:70-102) on device-resident spectrograms.
-// spec_d, y_d, v_d: device [2][bins][T] complex64.  scratch comes from `io` (caller reserved).
-// (planes 2 for a complex handle: its crop source has 4 channels and its mask is complex64)
-static size_t separate_scratch_floats(int bins, int T, int cropsize, int offset, int tta, int planes) {
-    int l, r, roi;
-    make_padding(T, cropsize, offset, l, r, roi);
-    const size_t Wpad2 = (size_t)T + l + r + roi;
-    return planes * 2 * (size_t)2 * bins * Wpad2 * (tta ? 2 : 1) + 2 * (size_t)T + (size_t)8 * bins + 4096;
-}
-
 // The crops [0, patches) of a separate call in device batches of `bs`; run_crops(first, count) enqueues the network and the mask
 // head for one contiguous part on the current streams.  A batch is split over the lanes unless profiling / serial_exec.
 void Model::run_crop_chunks(int patches, int bs, const std::function<void(int, int)>& run_crops) {
@@ -1802,234 +1792,20 @@ void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst
     crop_mask_head(run_net_window(x, offset, cropsize - offset), cropsize, d);
 }
 
-void Model::separate_api(const float* spec, bool on_dev, int T, int tta, int batchsize, int cropsize, float* y_spec,
-                         float* v_spec, bool out_on_dev, bool io_reserved, float* y_wave_d, float* v_wave_d, bool pcm16_out) {
-    DeviceGuard dev_guard(device);
-    const bool post = (tta & 2) != 0;       // flags: bit 0 = --tta, bit 1 = --postprocess
-    tta &= 1;
-    VR_CHECK(T > 0, -2, "empty spectrogram");
-    VR_CHECK(!training, -2, "separate() runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
-    check_T(cropsize, offset, 1);
-    VR_CHECK(cropsize - 2 * offset > 0, -6, "cropsize must exceed 2*offset");
-    const int bins = output_bin;
-    const size_t spec_f = (size_t)2 * bins * T * 2;
-    int pad_l, pad_r, roi;
-    make_padding(T, cropsize, offset, pad_l, pad_r, roi);
-    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta, is_complex ? 2 : 1);
-    if (!io_reserved) {
-        // direct call (host or device pointers): size and rewind the staging arena here; only the wave-level entry
-        // point, which has already carved its own buffers out of `io`, passes io_reserved
-        ensure_io((3 * spec_f + scratch) * sizeof(float) + 65536);
-        io.reset();
-    }
-    const float* sd = spec;
-    if (!on_dev) {
-        float* tmp = io.allocf(spec_f);
-        VR_HIP(hipMemcpyAsync(tmp, spec, spec_f * sizeof(float), hipMemcpyHostToDevice, stream));
-        sd = tmp;
-    }
-    float* yd = out_on_dev ? y_spec : io.allocf(spec_f);
-    float* vd = out_on_dev ? v_spec : io.allocf(spec_f);
-    unsigned* stats = static_cast<unsigned*>(io.alloc(16 + (size_t)2 * bins * 16));
-    float* in_aff = io.allocf(16);
-    const int npass = tta ? 2 : 1;
-    float* mask[2] = {nullptr, nullptr};
-    int Wm[2] = {0, 0};
-    int max_patches = 0;
-    for (int ps = 0; ps < npass; ++ps) {
-        const int Wpad = T + pad_l + pad_r + (ps ? roi : 0);
-        max_patches = std::max(max_patches, (Wpad - 2 * offset) / roi);
-    }
-    const int bs = (batchsize <= 0) ? max_patches : std::min(batchsize, max_patches);
-    fold_eval_affines();                    // before planning, as in forward_api
-    plan_and_reserve(bs, cropsize, 0);
-    for (int ps = 0; ps < npass; ++ps) {
-        const int pl = pad_l + (ps ? roi / 2 : 0), pr = pad_r + (ps ? roi / 2 : 0);
-        const int Wpad = T + pl + pr;
-        const int patches = (Wpad - 2 * offset) / roi;
-        float* mag = io.allocf((size_t)nin * bins * Wpad);
-        Wm[ps] = patches * roi;
-        mask[ps] = io.allocf((size_t)(is_complex ? 4 : 2) * bins * Wm[ps]);
-        if (is_complex) {
-            // X_pad / c as [re L, re R, im L, im R] planes, zero padding included.  The stats pass is the magnitude path's: it
-            // also stores |X| into the first two planes, which the pack then overwrites.  c is real (max |X|, inference.py:74) or
-            // numpy's lexicographic complex maximum (inference.py:87,94), applied as a complex product with 1/c.
-            launch_mag_pad(reinterpret_cast<const float2*>(sd), bins, T, mag, Wpad, pl, stats, stream);
-            launch_coef_complex(stats, 2 * bins, tta ? 1 : 0, reinterpret_cast<float2*>(in_aff), stream);
-            launch_pack_complex(reinterpret_cast<const float2*>(sd), 1, bins, T, mag, Wpad, pl, reinterpret_cast<const float2*>(in_aff),
-                                stream);
-        } else {
-            prof_memset_async(mag, 0, (size_t)2 * bins * Wpad * sizeof(float), stream);
-            launch_mag_pad(reinterpret_cast<const float2*>(sd), bins, T, mag, Wpad, pl, stats, stream);
-            launch_coef_affine(stats, 2 * bins, tta ? 1 : 0, in_aff, stream);
-            // X_mag / coef once, so that the first conv of every BaseNet reads a plain tensor (LDS-DMA path)
-            Tensor m;
-            m.p = mag; m.N = 1; m.C = 2; m.H = bins; m.W = Wpad;
-            m.sH = Wpad; m.sC = (long long)bins * Wpad; m.sN = 2 * m.sC;
-            m.aff0 = in_aff; m.slope = 1.f;
-            launch_materialize(m, mag, stream);          // element-wise, in place
-        }
-        auto run_crops = [&](int first, int count) {
-            ws.reset();
-            Tensor x;
-            x.p = mag + (size_t)first * roi; x.N = count; x.C = nin; x.H = max_bin; x.W = cropsize;
-            x.sN = roi; x.sC = (long long)bins * Wpad; x.sH = Wpad;
-            x.slope = 1.f;
-            HeadDst d{};
-            d.p = mask[ps] + (size_t)(is_complex ? 2 : 1) * first * roi; d.dN = roi; d.dC = (long long)bins * Wm[ps]; d.dH = Wm[ps];
-            crop_mask_head(run_net_window(x, offset, cropsize - offset), cropsize, d);
-        };
-        run_crop_chunks(patches, bs, run_crops);
-    }
-    const float* wgt = nullptr;
-    if (post) {
-        // spec_utils.merge_artifacts (lib/spec_utils.py:60-93): frames whose mask minimum exceeds the
-        // threshold for more than min_range frames are pulled towards 1 with linear fades.  The per-frame
-        // minimum is reduced on the GPU, the O(T) run logic runs on the host, the blend in apply_mask.
-        float* fmin_d = io.allocf((size_t)T);
-        float* wgt_d = io.allocf((size_t)T);
-        if (is_complex)      // (the minimum of |mask|, inference.py:28-29)
-            launch_frame_min_complex(bins, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
-                                     tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, fmin_d, stream);
-        else
-            launch_frame_min(bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2, fmin_d, stream);
-        std::vector<float> fmin((size_t)T), w;
-        VR_HIP(hipMemcpyAsync(fmin.data(), fmin_d, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream));
-        VR_HIP(hipStreamSynchronize(stream));
-        merge_artifacts_weight(fmin, w, 0.05f, 64, 32);
-        VR_HIP(hipMemcpyAsync(wgt_d, w.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice, stream));
-        VR_HIP(hipStreamSynchronize(stream));
-        wgt = wgt_d;
-    }
-    if (y_wave_d && v_wave_d) {
-        // wave-level caller: mask application, inverse FFT, window and overlap-add in one pass per stem -- the y / v
-        // spectrograms (inference.py:32-38) are never materialised
-        for (int which = 0; which < 2; ++which) {
-            if (pcm16_out)       // (y_wave_d / v_wave_d are int16 [samples][2]: the encode is the kernel's store)
-                launch_istft_masked_pcm16(plan, reinterpret_cast<const float2*>(sd), hop, T, is_complex, mask[0], Wm[0], tta ? mask[1] : nullptr,
-                                          Wm[1], roi / 2, wgt, which, reinterpret_cast<int16_t*>(which ? v_wave_d : y_wave_d), stream);
-            else if (is_complex)
-                launch_istft_masked_complex(plan, reinterpret_cast<const float2*>(sd), hop, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
-                                            tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, wgt, which,
-                                            which ? v_wave_d : y_wave_d, stream);
-            else
-                launch_istft_masked(plan, reinterpret_cast<const float2*>(sd), hop, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1],
-                                    roi / 2, wgt, which, which ? v_wave_d : y_wave_d, stream);
-        }
-        enq_t1 = std::chrono::steady_clock::now(); enq_have = true;       // (VR_ENQ_TIMING: everything is enqueued at this point)
-        VR_HIP(hipStreamSynchronize(stream));
-        return;
-    }
-    if (is_complex)
-        launch_apply_mask_complex(reinterpret_cast<const float2*>(sd), bins, T, reinterpret_cast<const float2*>(mask[0]), Wm[0],
-                                  tta ? reinterpret_cast<const float2*>(mask[1]) : nullptr, Wm[1], roi / 2, wgt,
-                                  reinterpret_cast<float2*>(yd), reinterpret_cast<float2*>(vd), stream);
-    else
-        launch_apply_mask(reinterpret_cast<const float2*>(sd), bins, T, mask[0], Wm[0], tta ? mask[1] : nullptr, Wm[1], roi / 2,
-                          wgt, reinterpret_cast<float2*>(yd), reinterpret_cast<float2*>(vd), stream);
-    if (!out_on_dev) {
-        VR_HIP(hipMemcpyAsync(y_spec, yd, spec_f * sizeof(float), hipMemcpyDeviceToHost, stream));
-        VR_HIP(hipMemcpyAsync(v_spec, vd, spec_f * sizeof(float), hipMemcpyDeviceToHost, stream));
-    }
-    VR_HIP(hipStreamSynchronize(stream));
-}
-
-void Model::separate_wave_api(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                              float* y_wave, float* v_wave, bool out_on_dev) {
-    DeviceGuard dev_guard(device);
-    VR_CHECK(L >= hop, -2, "wave shorter than one hop");
-    separate_wave_body(wave, on_dev, L, tta, batchsize, cropsize, y_wave, v_wave, out_on_dev);
-}
-
-void Model::separate_pcm_api(const void* bytes, bool on_dev, long long L, int channels, int fmt, int tta, int batchsize, int cropsize,
-                             int16_t* y, int16_t* v, bool out_on_dev) {
-    check_pcm(on_dev ? bytes : nullptr, channels, fmt, "");
-    if (out_on_dev)
-        VR_CHECK(reinterpret_cast<uintptr_t>(y) % 2 == 0 && reinterpret_cast<uintptr_t>(v) % 2 == 0, -2, "the int16 outputs are not 2-byte aligned");
-    DeviceGuard dev_guard(device);
-    VR_CHECK(L >= hop, -2, "wave shorter than one hop");
-    VR_CHECK(L / hop < (1LL << 30), -2, "wave too long");
-    const PcmIn in{static_cast<const uint8_t*>(bytes), channels, fmt};
-    separate_wave_body(nullptr, on_dev, L, tta, batchsize, cropsize, reinterpret_cast<float*>(y), reinterpret_cast<float*>(v), out_on_dev, &in);
-}
-
-// pcm: the input is pcm->bytes (interleaved sample bytes, `wave` unused) and y_wave / v_wave are int16 [samples][2]
-void Model::separate_wave_body(const float* wave, bool on_dev, long long L, int tta, int batchsize, int cropsize,
-                               float* y_wave, float* v_wave, bool out_on_dev, const PcmIn* pcm) {
-    // VR_ENQ_TIMING=1 (diagnostics): host time to ENQUEUE the whole call vs the time until the device has drained it
+// Separator.separate[_tta] / the inference.py:147-176 pipeline for n_songs inputs in ONE call: the executor of every offline entry
+// point (vr_separate*, vr_separate*_many).  Each song keeps its own normaliser, padding and merge_artifacts runs; what the songs share
+// is the device batches.  All crops of the call -- pass 0 of every song, then for tta pass 1 of every song -- form one list; a gather
+// kernel writes the crops of a batch part as one dense tensor [n][nin][max_bin][cropsize] straight from the complex spectrograms
+// (normalised, zero outside the song), and crop n's mask lands at column n * roi of one concatenated mask [2][bins][W].  Front end
+// and back end are one launch each for all songs (song = a grid dimension, kernels.h SongSeg), so the launch count does not depend
+// on n_songs.  solo: the call of a one-song entry point (api.cpp) -- its errors name no song, and its device batch holds at most the
+// crops of its longer pass, which is what batchsize <= 0 means there.
+void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta, int batchsize,
+                         int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels, const int* pcm_fmt,
+                         bool solo) {
+    // VR_ENQ_TIMING=1 (diagnostics, wave-level calls): host time to ENQUEUE the whole call vs the time until the device has drained it
     static const bool enq_timing = getenv("VR_ENQ_TIMING") != nullptr;
     const auto enq_t0 = std::chrono::steady_clock::now();
-    struct EnqReport {
-        Model* m; bool on; std::chrono::steady_clock::time_point t0;
-        ~EnqReport() {
-            if (!on || !m->enq_have) return;
-            const auto t2 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[vr-enq] enqueue %.3f ms, total %.3f ms\n", std::chrono::duration<double, std::milli>(m->enq_t1 - t0).count(),
-                    std::chrono::duration<double, std::milli>(t2 - t0).count());
-            m->enq_have = false;
-        }
-    } enq_report{this, enq_timing, enq_t0};
-    const int T = 1 + (int)(L / hop);
-    const int bins = output_bin;
-    const size_t spec_f = (size_t)2 * bins * T * 2;
-    const size_t out_f = (size_t)2 * hop * (T - 1);
-    const size_t frames_f = (size_t)2 * T * n_fft;
-    const size_t scratch = separate_scratch_floats(bins, T, cropsize, offset, tta, is_complex ? 2 : 1);
-    // (pcm: the staged input holds the file's sample bytes, the staged stems int16 -- half the floats)
-    const size_t in_b = pcm ? (size_t)L * pcm->channels * pcm_sample_bytes(pcm->fmt) : (size_t)2 * L * sizeof(float);
-    const size_t in_f = pcm ? in_b / 4 + 1 : (size_t)2 * L, stage_f = pcm ? out_f / 2 : out_f;
-    ensure_io((in_f + 3 * spec_f + 2 * out_f + frames_f + scratch) * sizeof(float) + 65536);
-    io.reset();
-    float* stage_in = io.allocf(in_f);
-    const void* src = pcm ? static_cast<const void*>(pcm->bytes) : wave;
-    const float* wd = wave;
-    if (!on_dev) {
-        VR_HIP(hipMemcpyAsync(stage_in, src, in_b, hipMemcpyHostToDevice, stream));
-        wd = stage_in;
-        src = stage_in;
-    }
-    float* spec = io.allocf(spec_f);
-    float* ys = io.allocf(spec_f);
-    float* vs = io.allocf(spec_f);
-    float* frames = io.allocf(frames_f);
-    float* stage_y = io.allocf(stage_f + 4);
-    float* stage_v = io.allocf(stage_f + 4);
-    float* yw = out_on_dev ? y_wave : stage_y;
-    float* vw = out_on_dev ? v_wave : stage_v;
-    if (pcm) {                                  // (check_pcm: the tiled kernels exist; L >= hop: out_f > 0)
-        launch_stft_pcm(plan, PcmIn{static_cast<const uint8_t*>(src), pcm->channels, pcm->fmt}, L, T, reinterpret_cast<float2*>(spec), stream);
-        separate_api(spec, true, T, tta, batchsize, cropsize, ys, vs, true, /*io_reserved=*/true, yw, vw, /*pcm16_out=*/true);
-        if (!out_on_dev) {
-            VR_HIP(hipMemcpyAsync(y_wave, yw, out_f * 2, hipMemcpyDeviceToHost, stream));
-            VR_HIP(hipMemcpyAsync(v_wave, vw, out_f * 2, hipMemcpyDeviceToHost, stream));
-        }
-        VR_HIP(hipStreamSynchronize(stream));
-        return;
-    }
-    launch_stft(plan, wd, L, hop, T, reinterpret_cast<float2*>(spec), stream);
-    if (istft_masked_available(plan, hop) && out_f) {
-        separate_api(spec, true, T, tta, batchsize, cropsize, ys, vs, true, /*io_reserved=*/true, yw, vw);
-    } else {
-        separate_api(spec, true, T, tta, batchsize, cropsize, ys, vs, true, /*io_reserved=*/true);
-        launch_istft(plan, reinterpret_cast<const float2*>(ys), hop, T, frames, yw, stream);
-        launch_istft(plan, reinterpret_cast<const float2*>(vs), hop, T, frames, vw, stream);
-    }
-    if (!out_on_dev && out_f) {
-        VR_HIP(hipMemcpyAsync(y_wave, yw, out_f * sizeof(float), hipMemcpyDeviceToHost, stream));
-        VR_HIP(hipMemcpyAsync(v_wave, vw, out_f * sizeof(float), hipMemcpyDeviceToHost, stream));
-    }
-    VR_HIP(hipStreamSynchronize(stream));
-}
-
-// Separator.separate[_tta] / the inference.py:147-176 pipeline for n_songs inputs in ONE call (vr_separate_many /
-// vr_separate_wave_many).  Each song keeps its own normaliser, padding and merge_artifacts runs; what the songs share is the device
-// batches.  All crops of the call -- pass 0 of every song, then for tta pass 1 of every song -- form one list; a gather kernel writes
-// the crops of a batch part as one dense tensor [n][nin][max_bin][cropsize] straight from the complex spectrograms (normalised,
-// zero outside the song), and crop n's mask lands at column n * roi of one concatenated mask [2][bins][W].  Front end and back end
-// are one launch each for all songs (song = a grid dimension, kernels.h SongSeg), so the launch count does not depend on n_songs.
-void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta,
-                              int batchsize, int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels,
-                              const int* pcm_fmt) {
     const bool post = (tta & 2) != 0;       // flags: bit 0 = --tta, bit 1 = --postprocess
     tta &= 1;
     const bool waves = L != nullptr;
@@ -2046,8 +1822,9 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     std::vector<Song> sg((size_t)n_songs);
     int roi = 0, max_T = 0;
     long long n_crops[2] = {0, 0}, sum_T = 0, sum_L = 0;
+    auto song = [&](int s) { return solo ? std::string() : "song " + std::to_string(s) + ": "; };      // what an error starts with
     for (int s = 0; s < n_songs; ++s) {
-        const std::string who = "song " + std::to_string(s) + ": ";
+        const std::string who = song(s);
         VR_CHECK(in[s] && y[s] && v[s], -2, who + "null pointer");
         if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
         else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
@@ -2073,7 +1850,8 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
     const long long total_crops = n_crops[0] + n_crops[1];
     VR_CHECK(total_crops * roi < (1LL << 31) && sum_T < (1LL << 31), -2, "too many frames for one call: split the songs over several calls");
     const int crops_n = (int)total_crops, W = crops_n * roi;
-    const int bs = (batchsize <= 0) ? crops_n : std::min(batchsize, crops_n);
+    const int most = solo ? std::max(sg[0].patches[0], sg[0].patches[1]) : crops_n;
+    const int bs = (batchsize <= 0) ? most : std::min(batchsize, most);
     const bool tiled = many_tiled_available(plan, hop);
 
     DeviceGuard dev_guard(device);
@@ -2190,7 +1968,7 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
             try {
                 merge_artifacts_weight(f1, w1, 0.05f, 64, 32);
             } catch (const Error& e) {
-                throw Error(e.code, "song " + std::to_string(s) + ": " + e.what());
+                throw Error(e.code, song(s) + e.what());
             }
             std::copy(w1.begin(), w1.end(), wgt_h.begin() + tab[s].frame0);
         }
@@ -2215,7 +1993,11 @@ void Model::separate_many_api(int n_songs, const float* const* in, bool in_on_de
             VR_HIP(hipMemcpyAsync(y[s], stage_y[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
             VR_HIP(hipMemcpyAsync(v[s], stage_v[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
         }
+    const auto enq_t1 = std::chrono::steady_clock::now();     // everything is enqueued at this point
     VR_HIP(hipStreamSynchronize(stream));
+    if (enq_timing && waves)
+        fprintf(stderr, "[vr-enq] enqueue %.3f ms, total %.3f ms\n", std::chrono::duration<double, std::milli>(enq_t1 - enq_t0).count(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - enq_t0).count());
 }
 
 // =====================================================================================================
