@@ -8,6 +8,8 @@
 // (tests/test_gpu_dgrad_launch.py), and ONE launch_materialize, launch_upsample2x or launch_avgpool_h on a pending, strided tensor
 // (tests/test_gpu_tensor_pass.py), and the derived weight forms those launches read -- one form of given weights through its single-layer and
 // its batched launcher, and what a live handle holds for a layer (tests/test_gpu_weight_forms.py).
+// The head_loss* and head_wave_* hooks run the train step's own head function (run_train_head, train.hip) on their buffers, and the
+// wave_pair / wave_triple hooks the wave-term launcher it and vr_validate_step run (launch_wave_term, stft.hip): no copy of either here.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -108,9 +110,9 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
 // head_loss_complex N,C,H,W,bins        slope,gscale     x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[1],
 //                                                        (complex64)                                         g[N,C,H,W], dw[4][C]
-//                 launch_head_loss_complex (loss = mean |m X - y| over the N*2*bins*W complex elements), then the CO = 4 thin data and
-//                 weight gradients of that dlogit (launch_thin_dgrad storing, launch_thin_wgrad storing), as Model::train_fwd_bwd_api
-//                 runs them on a complex handle
+//                 run_train_head, the function Model::train_fwd_bwd_api runs, in its complex L1 form (loss = mean |m X - y| over the
+//                 N*2*bins*W complex elements; then the CO = 4 thin weight and data gradients of that dlogit, both storing); head_loss
+//                 is its real form without the thin gradients
 // head            N,C,H,W,w_lo,w_hi,pad_rows,cplx,hsplit,use_items,pitch_extra
 //                                       slope            x[N,C,H,W], aff0[C][2]|null, aff1[C][2]|null,       the destination(s), whole: dense [N][2][H+pad_rows][Wm +
 //                                                        w[CO][C] (CO = 2; cplx: 4)                          pitch_extra], or with use_items one buffer per item n,
@@ -121,7 +123,7 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 launch_squeeze_conv; nblk = what its dry run returns
 // head_bwd        N,H,W,bins            -                dmask[N,2,bins,W], mask[N,2,bins,W]                 dlogit[N,2,H,W]
 // crop            rows,T,Wm,off,cplx    -                m[rows][Wm], x[rows][T], y[rows][T]|null            m * x[.., off + w] [rows][Wm], mean |that - y[.., off + w]|
-//                 launch_mul_crop, launch_l1_crop (real only); cplx: m and x complex64, the complex product     [1]|null
+//                 launch_mul_crop, launch_l1_crop (its real form only); cplx: m and x complex64, the complex product     [1]|null
 // rows            N,R,W                 -                x[N,R,W], aff[R][2], d[N,R,W]                       relu(x*a+b), channel sums of d [R]
 // adam            n                     lr,b1,b2,eps,gscale,step   p, g, m, v                                p, m, v
 // wire            n                     -                x[n]                                                bf16_to_f32(f32_to_bf16(x)) [n]
@@ -137,7 +139,7 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
 // wave_pair       S,T,x_pitch,y_pitch,  -                x[S][bins][x_pitch] complex64, mask (same shape)    y_wave, p_wave [S][hop (T-1)], sums[3] = <y, p>,
 //                 y_off,has_mask                         |null, y[S][bins][y_pitch] complex64                <y, y>, <p, p> over all signals
-//                 launch_istft_pair + the launch_reduce_rows of its partials: the waves of the target y (frame t at column y_off + t) and
+//                 launch_wave_term on a WavePair (launch_istft_pair + the launch_reduce_rows of its partials): the waves of the target y (frame t at column y_off + t) and
 //                 of the estimate p = mask * x (no mask: x itself); bins = n_fft / 2 + 1 of the handle (hop == n_fft / 2 only).  Waves
 //                 and partials sit between guard bands (error -3).
 // wave_grad       S,T,l1                sdr_scale,       y_wave, p_wave [S][hop (T-1)], sums[3], X[S][bins]  dmask[S][bins][T] complex64
@@ -147,13 +149,13 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 // head_wave_loss  N,C,H,W,bins[,       slope,sdr_scale, x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[4] =
 //                 head_only]            l1_scale                                                             (mean ||y|-|p||, <y,p>, <y,y>, <p,p>), g[N,C,H,W],
 //                                                                                                            dw[4][C], dmask[N,2,bins,W] complex64
-//                 the head of a VR_LOSS_MAG_L1_WAVE_SDR step as Model::train_fwd_bwd_api runs it: launch_head_mag_l1, launch_istft_pair
-//                 + reduce, launch_stft_wave_grad, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
-//                 of the handle, W = the frames.  A sixth dim head_only = 1: launch_head_mag_l1 alone at any bins >= H -- only mask and
-//                 loss[0] are produced
+//                 run_train_head in its VR_LOSS_MAG_L1_WAVE_SDR form, the call Model::train_fwd_bwd_api makes: launch_head_mag_l1, the pair
+//                 wave term, launch_stft_wave_grad, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
+//                 of the handle, W = the frames.  A sixth dim head_only = 1: the same call without gradient destinations, which stops
+//                 after launch_head_mag_l1, at any bins >= H -- only mask and loss[0] are produced
 // wave_triple     S,T,xy_pitch,xy_off,  -                x, y [S][bins][xy_pitch] complex64, mask (same      x_wave, y_wave, p_wave [S][hop (T-1)], sums[6] = <y, p>,
 //                 p_pitch,has_mask                       shape)|null, p[S][bins][p_pitch] complex64|null     <y, y>, <p, p>, <n, q>, <n, n>, <q, q> over all signals
-//                 launch_istft_triple + the launch_reduce_rows of its partials (kernels.h: WaveTriple): the waves of
+//                 launch_wave_term on a WaveTriple (launch_istft_triple + the launch_reduce_rows of its partials; kernels.h: WaveTriple): the waves of
 //                 the mixture x and the target y (frame t at column xy_off + t) and of the estimate -- mask * x with a mask, else p (frame t
 //                 at column t); n = x_wave - y_wave, q = x_wave - p_wave.  Waves and partials sit between guard bands (error -3).
 // wave_grad3      S,T,l1                sdr_scale,       x_wave, y_wave, p_wave [S][hop (T-1)], sums[6],     dmask[S][bins][T] complex64
@@ -162,8 +164,8 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 // head_wave_wsdr  N,C,H,W,bins          slope,sdr_scale, x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[7] =
 //                                       l1_scale                                                             (mean ||y|-|p||, the six sums), g[N,C,H,W],
 //                                                                                                            dw[4][C], dmask[N,2,bins,W] complex64
-//                 the head of a VR_LOSS_MAG_L1_WAVE_WSDR step as Model::train_fwd_bwd_api runs it: launch_head_mag_l1, launch_istft_triple
-//                 + reduce, launch_stft_wave_grad3, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
+//                 run_train_head in its VR_LOSS_MAG_L1_WAVE_WSDR form, the call Model::train_fwd_bwd_api makes: launch_head_mag_l1, the triple
+//                 wave term, launch_stft_wave_grad3, launch_head_bwd_complex, then the CO = 4 thin gradients (storing); bins = n_fft / 2 + 1
 //                 of the handle, W = the frames.  Waves, partials and dmask sit between guard bands (error -3).
 // conv_launch     nsrc,ndst,N,Cout,KS,  epi_slope,       w[Cout][Cin][KS][KS] (OIHW), bias[Cout]|null,       per destination its whole backing buffer (null where
 //                 dil_h,dil_w,flags,    slope of         epi[Cout][2]|null; per source: its backing buffer,  absent); then, with flags bit 1, stats[Cout][2] =
@@ -938,7 +940,10 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         t.slope = fp[0];
         if (in[1]) t.aff0 = aff.p;
         DevBuf dlogit((size_t)N * 2 * H * W), mask(nx), lpart((size_t)head_loss_blocks(t)), loss(4);
-        launch_head_loss(t, w.p, X.p, Y.p, bins, fp[1], dlogit.p, mask.p, lpart.p, loss.p, (float)(1.0 / (double)nx), st);
+        HeadScratch hs{};
+        hs.dlogit = dlogit.p; hs.lpart = lpart.p;
+        run_train_head(plan, t, TrainHead{0, false, w.p, X.p, Y.p, bins, mask.p, loss.p, (float)(1.0 / (double)nx), fp[1], 0.f, nullptr, 0, nullptr, 0},
+                       hs, nullptr, st);
         VR_HIP(hipStreamSynchronize(st));
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, sizeof(float), hipMemcpyDeviceToHost));
@@ -953,9 +958,10 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         if (in[1]) t.aff0 = aff.p;
         DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), loss(4), g(n), dw((size_t)4 * C);
         DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C);
-        launch_head_loss_complex(t, w.p, X.p, Y.p, bins, fp[1], dlogit.p, mask.p, lpart.p, loss.p, (float)(1.0 / (double)nx), st);
-        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
-        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
+        HeadScratch hs{};
+        hs.dlogit = dlogit.p; hs.lpart = lpart.p; hs.wpart = part.p;
+        run_train_head(plan, t, TrainHead{0, true, w.p, X.p, Y.p, bins, mask.p, loss.p, (float)(1.0 / (double)nx), fp[1], 0.f, g.p, 0, dw.p, 0},
+                       hs, nullptr, st);
         VR_HIP(hipStreamSynchronize(st));
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, sizeof(float), hipMemcpyDeviceToHost));
@@ -1041,7 +1047,7 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         DevBuf m(in[0], (size_t)rows * Wm * E), x(in[1], (size_t)rows * T * E), y(loss ? in[2] : nullptr, loss ? (size_t)rows * T : 0);
         DevBuf part((size_t)l1_crop_blocks()), lossd(4);
         launch_mul_crop(x.p, m.p, cplx, rows, T, Wm, off, st);
-        if (loss) launch_l1_crop(m.p, y.p, rows, T, Wm, off, part.p, lossd.p, st);
+        if (loss) launch_l1_crop(L1_CROP_REAL, m.p, y.p, rows, T, Wm, off, part.p, lossd.p, st);
         VR_HIP(hipStreamSynchronize(st));
         m.download(out[0]);
         if (loss) VR_HIP(hipMemcpy(out[1], lossd.p, sizeof(float), hipMemcpyDeviceToHost));
@@ -1138,17 +1144,15 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_CHECK(S > 0 && T >= 2 && xp >= T && yo >= 0 && yp >= yo + T && in[0] && in[2] && (!has_mask || in[1]), -2,
                  "wave_pair: need signals > 0, T >= 2, x_pitch >= T, y_pitch >= y_off + T and the inputs");
         const size_t rows = (size_t)S * bins, nw = (size_t)S * hop * (T - 1);
-        const int nb = wave_pair_blocks(plan, T);
+        const WaveTermFloats wf = wave_term_floats(plan, hop, 1, S, T);
         DevBuf x(in[0], rows * xp * 2), m(has_mask ? in[1] : nullptr, has_mask ? rows * xp * 2 : 0), y(in[2], rows * yp * 2);
-        GuardedBuf yw(nullptr, nw), pw(nullptr, nw), part(nullptr, (size_t)S * nb * 3);
-        DevBuf sums(4), table(64);
+        GuardedBuf yw(nullptr, nw), pw(nullptr, nw), part(nullptr, wf.part);
+        DevBuf sums(4), table(wf.table);
         WavePair pr{};
         pr.x = reinterpret_cast<const float2*>(x.p); pr.mask = has_mask ? reinterpret_cast<const float2*>(m.p) : nullptr;
         pr.y = reinterpret_cast<const float2*>(y.p); pr.x_pitch = xp; pr.y_pitch = yp; pr.y_off = yo;
         pr.y_wave = yw.p(); pr.p_wave = pw.p(); pr.part = part.p();
-        VR_HIP(hipMemcpy(table.p, &pr, sizeof(WavePair), hipMemcpyHostToDevice));
-        launch_istft_pair(plan, reinterpret_cast<const WavePair*>(table.p), pr, S, T, st);
-        launch_reduce_rows(pr.part, 3, S * nb, sums.p, 3, 0, 1.f, st);
+        launch_wave_term(plan, pr, table.p, nullptr, S, T, sums.p, st);
         VR_HIP(hipStreamSynchronize(st));
         VR_CHECK(yw.intact() && pw.intact() && part.intact(), -3, "wave_pair: a store outside a wave or the partial sums");
         yw.download(out[0]); pw.download(out[1]);
@@ -1178,36 +1182,23 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_CHECK(head_only || (wave_loss_available(plan, hop) && bins == n_fft / 2 + 1), -2,
                  "head_wave_loss: bins must be n_fft / 2 + 1 of a hop == n_fft / 2 handle (or head_only)");
         VR_CHECK(N > 0 && C > 0 && H > 0 && W >= 2 && bins >= H && W % 4 == 0, -2, "head_wave_loss: need positive sizes, bins >= H, W % 4 == 0");
-        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W, nw = head_only ? 0 : (size_t)N * 2 * hop * (W - 1);
-        const int S = N * 2, nb = head_only ? 0 : wave_pair_blocks(plan, W);
+        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W;
+        const WaveTermFloats wf = head_only ? WaveTermFloats{} : wave_term_floats(plan, hop, 1, N * 2, W);
         DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)4 * C), X(in[3], 2 * nx), Y(in[4], 2 * nx);
         Tensor t = dense(x.p, N, C, H, W);
         t.slope = fp[0];
         if (in[1]) t.aff0 = aff.p;
         DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), loss(4), g(n), dw((size_t)4 * C);
-        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), yw(nw), pw(nw), pp((size_t)S * nb * 3), dm(2 * nx), table(64);
-        launch_head_mag_l1(t, w.p, X.p, Y.p, bins, mask.p, lpart.p, loss.p, (float)(1.0 / (double)nx), st);
+        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), yw(wf.wave), pw(wf.wave), pp(wf.part), dm(2 * nx), table(64);
+        const HeadScratch hs{dlogit.p, lpart.p, part.p, nullptr, dm.p, {yw.p, pw.p, nullptr}, pp.p, table.p};
+        run_train_head(plan, t, TrainHead{1, true, w.p, X.p, Y.p, bins, mask.p, loss.p, (float)(1.0 / (double)nx), fp[2], fp[1], head_only ? nullptr : g.p, 0,
+                                          head_only ? nullptr : dw.p, 0}, hs, nullptr, st);
+        VR_HIP(hipStreamSynchronize(st));
         if (head_only) {
-            VR_HIP(hipStreamSynchronize(st));
             mask.download(out[1]);
             VR_HIP(hipMemcpy(out[2], loss.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
             return;
         }
-        WavePair pr{};
-        pr.x = reinterpret_cast<const float2*>(X.p); pr.mask = reinterpret_cast<const float2*>(mask.p);
-        pr.y = reinterpret_cast<const float2*>(Y.p); pr.x_pitch = pr.y_pitch = W; pr.y_off = 0;
-        pr.y_wave = yw.p; pr.p_wave = pw.p; pr.part = pp.p;
-        VR_HIP(hipMemcpy(table.p, &pr, sizeof(WavePair), hipMemcpyHostToDevice));
-        launch_istft_pair(plan, reinterpret_cast<const WavePair*>(table.p), pr, S, W, st);
-        launch_reduce_rows(pr.part, 3, S * nb, loss.p + 1, 3, 0, 1.f, st);
-        WaveGrad wg{};
-        wg.y_wave = yw.p; wg.p_wave = pw.p; wg.sums = loss.p + 1; wg.X = pr.x; wg.mask = pr.mask; wg.Y = pr.y;
-        wg.dmask = reinterpret_cast<float2*>(dm.p); wg.sdr_scale = fp[1]; wg.l1_scale = fp[2];
-        launch_stft_wave_grad(plan, wg, S, W, st);
-        launch_head_bwd_complex(t, w.p, dm.p, bins, dlogit.p, st);
-        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
-        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
-        VR_HIP(hipStreamSynchronize(st));
         dlogit.download(out[0]); mask.download(out[1]);
         VR_HIP(hipMemcpy(out[2], loss.p, 4 * sizeof(float), hipMemcpyDeviceToHost));
         g.download(out[3]); dw.download(out[4]); dm.download(out[5]);
@@ -1220,19 +1211,17 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_CHECK(S > 0 && T >= 2 && xo >= 0 && xp >= xo + T && in[0] && in[1] && (has_mask ? in[2] != nullptr : (in[3] && pp >= T)), -2,
                  "wave_triple: need signals > 0, T >= 2, xy_pitch >= xy_off + T, the inputs, and a mask or an estimate with p_pitch >= T");
         const size_t rows = (size_t)S * bins, nw = (size_t)S * hop * (T - 1);
-        const int nb = wave_pair_blocks(plan, T);
+        const WaveTermFloats wf = wave_term_floats(plan, hop, 3, S, T);
         DevBuf x(in[0], rows * xp * 2), y(in[1], rows * xp * 2), m(has_mask ? in[2] : nullptr, has_mask ? rows * xp * 2 : 0);
         DevBuf pe(has_mask ? nullptr : in[3], has_mask ? 0 : rows * pp * 2);
-        GuardedBuf xw(nullptr, nw), yw(nullptr, nw), pw(nullptr, nw), part(nullptr, (size_t)S * nb * 6), sums(nullptr, 6);
-        DevBuf table(64);
+        GuardedBuf xw(nullptr, nw), yw(nullptr, nw), pw(nullptr, nw), part(nullptr, wf.part), sums(nullptr, 6);
+        DevBuf table(wf.table);
         WaveTriple tr{};
         tr.x = reinterpret_cast<const float2*>(x.p); tr.y = reinterpret_cast<const float2*>(y.p);
         tr.mask = has_mask ? reinterpret_cast<const float2*>(m.p) : nullptr; tr.p = has_mask ? nullptr : reinterpret_cast<const float2*>(pe.p);
         tr.xy_pitch = xp; tr.xy_off = xo; tr.p_pitch = has_mask ? xp : pp;
         tr.x_wave = xw.p(); tr.y_wave = yw.p(); tr.p_wave = pw.p(); tr.part = part.p();
-        VR_HIP(hipMemcpy(table.p, &tr, sizeof(WaveTriple), hipMemcpyHostToDevice));
-        launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(table.p), tr, S, T, st);
-        launch_reduce_rows(tr.part, 6, S * nb, sums.p(), 6, 0, 1.f, st);
+        launch_wave_term(plan, tr, table.p, nullptr, S, T, sums.p(), st);
         VR_HIP(hipStreamSynchronize(st));
         VR_CHECK(xw.intact() && yw.intact() && pw.intact() && part.intact() && sums.intact(), -3,
                  "wave_triple: a store outside a wave, the partial sums or the sums");
@@ -1262,32 +1251,18 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         const int N = (int)dims[0], C = (int)dims[1], H = (int)dims[2], W = (int)dims[3], bins = (int)dims[4];
         VR_CHECK(wave_loss_available(plan, hop) && bins == n_fft / 2 + 1, -2, "head_wave_wsdr: bins must be n_fft / 2 + 1 of a hop == n_fft / 2 handle");
         VR_CHECK(N > 0 && C > 0 && H > 0 && W >= 2 && bins >= H && W % 4 == 0, -2, "head_wave_wsdr: need positive sizes, bins >= H, W % 4 == 0");
-        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W, nw = (size_t)N * 2 * hop * (W - 1);
-        const int S = N * 2, nb = wave_pair_blocks(plan, W);
+        const size_t n = (size_t)N * C * H * W, nx = (size_t)N * 2 * bins * W;
+        const WaveTermFloats wf = wave_term_floats(plan, hop, 3, N * 2, W);
         DevBuf x(in[0], n), aff(in[1], in[1] ? (size_t)C * 2 : 0), w(in[2], (size_t)4 * C), X(in[3], 2 * nx), Y(in[4], 2 * nx);
         Tensor t = dense(x.p, N, C, H, W);
         t.slope = fp[0];
         if (in[1]) t.aff0 = aff.p;
         DevBuf dlogit((size_t)N * 4 * H * W), mask(2 * nx), lpart((size_t)head_loss_blocks(t)), g(n), dw((size_t)4 * C);
-        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), table(64);
-        GuardedBuf loss(nullptr, 7), xw(nullptr, nw), yw(nullptr, nw), pw(nullptr, nw), pp(nullptr, (size_t)S * nb * 6), dm(nullptr, 2 * nx);
-        launch_head_mag_l1(t, w.p, X.p, Y.p, bins, mask.p, lpart.p, loss.p(), (float)(1.0 / (double)nx), st);
-        WaveTriple tr{};
-        tr.x = reinterpret_cast<const float2*>(X.p); tr.y = reinterpret_cast<const float2*>(Y.p);
-        tr.mask = reinterpret_cast<const float2*>(mask.p); tr.p = nullptr;
-        tr.xy_pitch = tr.p_pitch = W; tr.xy_off = 0;
-        tr.x_wave = xw.p(); tr.y_wave = yw.p(); tr.p_wave = pw.p(); tr.part = pp.p();
-        VR_HIP(hipMemcpy(table.p, &tr, sizeof(WaveTriple), hipMemcpyHostToDevice));
-        launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(table.p), tr, S, W, st);
-        launch_reduce_rows(tr.part, 6, S * nb, loss.p() + 1, 6, 0, 1.f, st);
-        WaveGrad3 wg{};
-        wg.x_wave = tr.x_wave; wg.y_wave = tr.y_wave; wg.p_wave = tr.p_wave; wg.sums = loss.p() + 1;
-        wg.X = tr.x; wg.mask = tr.mask; wg.Y = tr.y;
-        wg.dmask = reinterpret_cast<float2*>(dm.p()); wg.sdr_scale = fp[1]; wg.l1_scale = fp[2];
-        launch_stft_wave_grad3(plan, wg, S, W, st);
-        launch_head_bwd_complex(t, w.p, dm.p(), bins, dlogit.p, st);
-        launch_thin_dgrad(t, 4, w.p, dlogit.p, g.p, 0, st);
-        launch_thin_wgrad(t, 4, dlogit.p, part.p, dw.p, 0, st);
+        DevBuf part((size_t)thin_wgrad_blocks(t) * 4 * C), table(wf.table);
+        GuardedBuf loss(nullptr, 7), xw(nullptr, wf.wave), yw(nullptr, wf.wave), pw(nullptr, wf.wave), pp(nullptr, wf.part), dm(nullptr, 2 * nx);
+        const HeadScratch hs{dlogit.p, lpart.p, part.p, nullptr, dm.p(), {yw.p(), pw.p(), xw.p()}, pp.p(), table.p};
+        run_train_head(plan, t, TrainHead{3, true, w.p, X.p, Y.p, bins, mask.p, loss.p(), (float)(1.0 / (double)nx), fp[2], fp[1], g.p, 0, dw.p, 0}, hs,
+                       nullptr, st);
         VR_HIP(hipStreamSynchronize(st));
         VR_CHECK(loss.intact() && xw.intact() && yw.intact() && pw.intact() && pp.intact() && dm.intact(), -3,
                  "head_wave_wsdr: a store outside the loss, a wave, the partial sums or dmask");

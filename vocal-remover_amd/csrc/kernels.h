@@ -178,12 +178,12 @@ void launch_bf16_to_f32(const unsigned short* x, float* y, long long n, hipStrea
 // m [rows][Wm] *= x [rows][T] at columns off .. off + Wm; cplx: both complex64, the complex product
 void launch_mul_crop(const float* x, float* m, bool cplx, long long rows, int T, int Wm, int off, hipStream_t st);
 // loss[0] = mean |pred [rows][Wm] - y [rows][T] at columns off .. off + Wm|; part: scratch of l1_crop_blocks() floats
+// form L1_CROP_COMPLEX: complex64 pred and y, mean |pred - y| over complex elements (rows and columns count complex elements);
+// L1_CROP_MAG: the same on their magnitudes, mean | |pred| - |y| |
 int l1_crop_blocks();
-void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
-// the same on complex64 pred and y: mean |pred - y| over complex elements (rows and columns count complex elements)
-void launch_l1_crop_complex(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
-// the same on their magnitudes: mean | |pred| - |y| |
-void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st);
+enum L1CropForm { L1_CROP_REAL = 0, L1_CROP_COMPLEX = 1, L1_CROP_MAG = 2 };
+void launch_l1_crop(L1CropForm form, const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss,
+                    hipStream_t st);
 
 // ---- stft.hip -----------------------------------------------------------------------------------
 struct FFTPlan { int n_fft; int log2n; float2* twiddle; float* window; };
@@ -306,6 +306,20 @@ struct WaveGrad3 {
     float l1_scale;           // 1 / (n_el accumulation_steps)
 };
 void launch_stft_wave_grad3(const FFTPlan& pl, const WaveGrad3& g, int signals, int T, hipStream_t st);
+
+// ---- the wave term of either kind, as every caller runs it (validate step, train-form head, the wave_pair / wave_triple hooks) --------
+// The caller states sources, pitches, offset, waves and partials in the kernel's own table entry (WavePair: kind 1, WaveTriple: kind 3).
+// launch_wave_term copies the entry to table_dev (64 floats) -- through `staging`, which must outlive the copy, on the stream; staging
+// null: synchronously -- launches the pair or triple form of istft_tile_kernel over `signals` spectrograms of T >= 2 frames and sums the
+// partials into sums [3] or [6].
+union WaveTable { WavePair pair; WaveTriple triple; };
+void launch_wave_term(const FFTPlan& pl, const WavePair& pair, float* table_dev, WaveTable* staging, int signals, int T, float* sums,
+                      hipStream_t st);
+void launch_wave_term(const FFTPlan& pl, const WaveTriple& triple, float* table_dev, WaveTable* staging, int signals, int T, float* sums,
+                      hipStream_t st);
+// what a wave term of loss kind 1 / 3 needs, in floats: `waves` waves of `wave` each, the partial sums, the table entry's slot
+struct WaveTermFloats { int waves; size_t wave, part, table; };
+WaveTermFloats wave_term_floats(const FFTPlan& pl, int hop, int kind, int signals, int T);
 
 // ---- many songs in one call (vr_separate_many / vr_separate_wave_many) ----------------------------------------------------------
 // One entry of the call's song table (built on the host, one copy to the device).  The crops of all songs, and of both TTA passes, form

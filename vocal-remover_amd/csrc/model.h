@@ -146,6 +146,43 @@ private:
     void upload(float2* dst, const float* src, size_t n_bytes);
 };
 
+// ---- the train-form head (train.hip): mask head -> loss -> dmask -> dlogit -> thin weight and data gradients of one feature tensor f3
+// [N][C][H][W], in its four forms: real L1, complex L1 (kind 0), VR_LOSS_MAG_L1_WAVE_SDR (1) and VR_LOSS_MAG_L1_WAVE_WSDR (3), the last
+// two on complex heads.  The fused train step, the split step's backward and the head_* hooks of debug.hip all run this one function.
+struct HeadScratch {
+    float *dlogit, *lpart, *wpart;                       // [N][CO][H][W], head_loss_blocks(f3), thin_wgrad_blocks(f3) * CO * C
+    float *mask, *dmask, *wave[3], *part, *table;        // kinds 1 / 3: complex64 [N][2][bins][W] each, the y, p (kind 3: and x) waves,
+};                                                       // the wave term's partials and table slot (wave_term_floats)
+struct TrainHead {
+    int kind; bool cplx;
+    const float *w, *X, *Y; int bins;                    // the head weights [CO][C]; X, Y [N][2][bins][W] (cplx: complex64)
+    float* mask;                                         // null: kind 0 writes no mask, kinds 1 / 3 keep it in the scratch
+    float* loss;                                         // [1], [4] or [7]: the loss or its magnitude term, then the three or six wave sums
+    float loss_scale, grad_scale, sdr_scale;             // 1 / ntot, 1 / (ntot accumulation_steps), sdr_weight / accumulation_steps
+    float* g; int g_acc; float* dw; int dw_acc;          // dL/df3 and dL/dw, stored (0) or added (1); dw null: the head kernel alone
+};                                                       // (mask, loss[0] and, kind 0, dlogit)
+// the scratch from `allocf` (floats -> pointer), in one fixed order: a dry run and the real run size alike
+template <class ALLOC>
+HeadScratch head_scratch(ALLOC&& allocf, const FFTPlan& pl, int hop, const Tensor& f3, int kind, bool cplx, int bins) {
+    const int CO = cplx ? 4 : 2;
+    HeadScratch s{};
+    s.dlogit = allocf((size_t)f3.N * CO * f3.H * f3.W);
+    s.lpart = allocf((size_t)head_loss_blocks(f3));
+    s.wpart = allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
+    if (kind == 0) return s;
+    const WaveTermFloats wf = wave_term_floats(pl, hop, kind, f3.N * 2, f3.W);
+    s.mask = allocf((size_t)f3.N * 2 * bins * f3.W * 2);
+    s.dmask = allocf((size_t)f3.N * 2 * bins * f3.W * 2);
+    for (int i = 0; i < wf.waves; ++i) s.wave[i] = allocf(wf.wave);
+    s.part = allocf(wf.part);
+    s.table = allocf(wf.table);
+    return s;
+}
+void run_train_head(const FFTPlan& pl, const Tensor& f3, const TrainHead& h, const HeadScratch& s, WaveTable* staging, hipStream_t st);
+// its tail, for a caller that has dlogit already: the thin weight and data gradients
+void launch_head_grads(const Tensor& f3, int CO, const float* w, const float* dlogit, float* wpart, float* g, int g_acc, float* dw,
+                       int dw_acc, hipStream_t st);
+
 class Model {
 public:
     Model(int device, int n_fft, int hop, int nout, int nout_lstm, bool is_complex = false);
@@ -165,11 +202,10 @@ public:
     int loss_kind = 0;
     double sdr_weight = 0.01, last_mag_l1 = 0.0, last_sdr = 0.0;
     bool loss_terms_valid = false;
-    WavePair pair_host{};                                 // the pair iSTFT's table entry, staged here for its copy to the device
+    WaveTable wave_host{};                                // the wave term's table entry, staged here for its copy to the device
     // 3 = VR_LOSS_MAG_L1_WAVE_WSDR: the wave term is the reference's weighted_sdr_loss on the target and on the
     // residual; last_sdr is then wsdr and last_y_sdr / last_noise_sdr / last_alpha its three parts (vr_loss_terms_wsdr).
     double last_y_sdr = 0.0, last_noise_sdr = 0.0, last_alpha = 0.0;
-    WaveTriple triple_host{};                             // the triple iSTFT's table entry, staged like pair_host
     void set_loss(int kind, double weight);
     float finish_wave_loss(const float* l4);
     float finish_wsdr_loss(const float* l7);
@@ -191,7 +227,6 @@ public:
     // x: [B,2,output_bin,T] fp32 magnitudes (complex handle: complex64, and out complex64 too).  mode 0: forward (full
     // width), 1: predict_mask (offset crop), 2: predict (x*mask, offset crop).  out sized accordingly.
     void forward_api(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device);
-    void forward_complex(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device);
 
     // train.validate_epoch body for one batch (train.py:117-127): predict + crop_center(y) + L1, on the device
     void validate_api(const float* X, const float* Y, bool on_dev, int B, int T, float* loss_out);
@@ -422,6 +457,9 @@ public:
                         float* dw_out);
 private:
     void ensure_train_state();
+    void refresh_train_weights();
+    template <class F> void plan_train_arenas(F&& dry_run, size_t extra_ws, bool clear_beside);
+    void wait_gs_clear();                                // the main stream waits for a gs clear still running on lanes[0].main
     void backward();
     void bwd_conv(TapeRec& r);
     // which launches the data gradient of a conv record took (bwd_conv_dgrad's return value)
@@ -484,7 +522,12 @@ private:
     Tensor run_lstm(LSTMMod& M, const Tensor& h);
     SrcSpec upsampled(const Tensor& t);
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)
-    // the mask head of `cropsize`-wide crops (sigmoid or complex, the handle's kind): the columns [offset, cropsize - offset) to d.p / d.items
+    // the network's input from X: an optional workspace copy (*copy: from where), a complex handle's pack, the strided tensor; dry: sizes only
+    Tensor net_input(const float* X, const hipMemcpyKind* copy, int B, int T, const float** xd = nullptr);
+    // the mask head of the handle's kind (sigmoid or complex) over the columns [w_lo, w_hi): to d.p / d.items, or dense to `out`
+    void mask_head(const Tensor& f3, int w_lo, int w_hi, HeadDst d);
+    void mask_head(const Tensor& f3, int w_lo, int w_hi, float* out);
+    // ... of `cropsize`-wide crops: the columns [offset, cropsize - offset)
     void crop_mask_head(const Tensor& f3, int cropsize, HeadDst d);
     // `count` gathered crops, dense [count][nin][max_bin][cropsize] -> the network -> crop_mask_head
     void run_dense_crops(float* dense, int count, int cropsize, const HeadDst& d);

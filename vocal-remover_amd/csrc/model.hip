@@ -1305,71 +1305,60 @@ void launch_mul_crop(const float* x, float* m, bool cplx, long long rows, int T,
     VR_HIP(hipGetLastError());
 }
 
-// forward_api of a complex handle: x [B][2][bins][T] complex64 -> planar [B][4][bins][T] (the reference's cat([x.real, x.imag])),
-// out [B][2][bins][Wm] complex64
-void Model::forward_complex(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
-    need_real_mask_train("vr_forward");
-    const size_t in_floats = (size_t)B * 2 * output_bin * T * 2;
-    const size_t pack_floats = (size_t)B * 4 * output_bin * T;
-    const int Wm = mode == 0 ? T : T - 2 * offset;
-    const size_t out_floats = (size_t)B * 2 * output_bin * Wm * 2;
-    // train mode ("complex_train"): batch statistics and their running update, live Dropout2d, no tape -- as forward_api
-    struct FwdOnly { Model* m; ~FwdOnly() { m->fwd_only = false; m->dropout_dev = nullptr; } } fwd_scope{this};
-    fwd_only = training;
-    if (training) refresh_wino(false);
-    if (!training) fold_eval_affines();
-    plan_and_reserve(B, T, (in_floats + pack_floats + out_floats) * sizeof(float) + 2048);
-    if (training) prepare_dropout(B);
-    float* xd = ws.allocf(in_floats);
-    float* xp = ws.allocf(pack_floats);
-    float* od = out_on_device ? out : ws.allocf(out_floats);
-    VR_HIP(hipMemcpyAsync(xd, x, in_floats * sizeof(float), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-    launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
+// The network's input from X [B][2][bins][T] (complex handle: complex64).  copy given: X (on the host or the device, as *copy says) goes
+// into a workspace copy first; *xd (if asked) is where X then lies on the device.  A complex handle's input is packed into the planar
+// [B][4][bins][T] (re L, re R, im L, im R: the reference's cat([x.real, x.imag])), unscaled.  dry: sizes only.
+Tensor Model::net_input(const float* X, const hipMemcpyKind* copy, int B, int T, const float** xd) {
+    const size_t planes = (size_t)B * 2 * output_bin * T;
+    if (copy) {
+        float* c = ws.allocf(planes * (is_complex ? 2 : 1));
+        VR_HIP(hipMemcpyAsync(c, X, planes * (is_complex ? 2 : 1) * sizeof(float), *copy, stream));
+        X = c;
+    }
+    if (xd) *xd = X;
     Tensor xt;
-    xt.p = xp; xt.N = B; xt.C = 4; xt.H = max_bin; xt.W = T;
-    xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 4 * xt.sC; xt.slope = 1.f;
-    if (record_taps) taps.clear();
-    Tensor f3 = run_net_window(xt, mode == 0 ? 0 : offset, mode == 0 ? 0 : T - offset);
+    xt.p = const_cast<float*>(X); xt.N = B; xt.C = nin; xt.H = max_bin; xt.W = T;
+    xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = nin * xt.sC; xt.slope = 1.f;
+    if (is_complex) {
+        xt.p = ws.allocf(2 * planes);
+        if (!dry) launch_pack_complex(reinterpret_cast<const float2*>(X), B, output_bin, T, xt.p, T, 0, nullptr, stream);
+    }
+    return xt;
+}
+
+// the mask head of this handle's kind (sigmoid or complex) over the columns [w_lo, w_hi) of f3, dense [B][2][bins][w_hi - w_lo] at `out`
+void Model::mask_head(const Tensor& f3, int w_lo, int w_hi, float* out) {
     HeadDst d{};
-    d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;       // (complex elements)
-    d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
-    launch_head_complex(f3, out_w->dev, d, stream);
-    if (mode == 2) launch_mul_crop(xd, od, true, (long long)B * 2 * output_bin, T, Wm, offset, stream);
-    if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
-    VR_HIP(hipStreamSynchronize(stream));
-    if (training) affine_dirty = true;
+    d.p = out; d.dH = w_hi - w_lo; d.dC = (long long)output_bin * d.dH; d.dN = 2 * d.dC;       // (complex handle: complex elements)
+    mask_head(f3, w_lo, w_hi, d);
 }
 
 void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode, float* out, bool out_on_device) {
     DeviceGuard dev_guard(device);
     VR_CHECK(B > 0, -2, "batch must be positive");
     check_T(T, offset, mode);
-    if (is_complex) { forward_complex(x, x_on_device, B, T, mode, out, out_on_device); return; }
-    const size_t in_floats = (size_t)B * 2 * output_bin * T;
+    if (is_complex) need_real_mask_train("vr_forward");
+    const size_t E = is_complex ? 2 : 1;             // floats per element: a complex handle takes and gives complex64
+    const size_t in_floats = (size_t)B * 2 * output_bin * T * E;
+    const size_t pack_floats = is_complex ? (size_t)B * 4 * output_bin * T : 0;
     const int Wm = mode == 0 ? T : T - 2 * offset;
-    const size_t out_floats = (size_t)B * 2 * output_bin * Wm;
+    const size_t out_floats = (size_t)B * 2 * output_bin * Wm * E;
     // Train mode (the reference's `model(X)` under model.train(), train.py:81 without the backward): BatchNorm uses
     // and updates batch statistics, Dropout2d is live, but no tape and no gradient buffers are kept.
     struct FwdOnly { Model* m; ~FwdOnly() { m->fwd_only = false; m->dropout_dev = nullptr; } } fwd_scope{this};
     fwd_only = training;
     if (training) refresh_wino(false);      // before planning: the kernel choice (and its partial-statistics layout) depends on them
     if (!training) fold_eval_affines();     // (eval: the bf16-plane weight tables decide conv_x3 vs the materialised-upsample plan)
-    plan_and_reserve(B, T, (in_floats + out_floats) * sizeof(float) + 1024);
+    plan_and_reserve(B, T, (in_floats + pack_floats + out_floats) * sizeof(float) + 1024 * E);
     if (training) prepare_dropout(B);
-    float* xd = ws.allocf(in_floats);
+    const hipMemcpyKind kind = x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const float* xd = nullptr;
+    const Tensor xt = net_input(x, &kind, B, T, &xd);
     float* od = out_on_device ? out : ws.allocf(out_floats);
-    if (x_on_device) VR_HIP(hipMemcpyAsync(xd, x, in_floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    else VR_HIP(hipMemcpyAsync(xd, x, in_floats * sizeof(float), hipMemcpyHostToDevice, stream));
-    Tensor xt;
-    xt.p = xd; xt.N = B; xt.C = 2; xt.H = max_bin; xt.W = T;
-    xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
     if (record_taps) taps.clear();
     Tensor f3 = run_net_window(xt, mode == 0 ? 0 : offset, mode == 0 ? 0 : T - offset);
-    HeadDst d{};
-    d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
-    d.w_lo = mode == 0 ? 0 : offset; d.w_hi = mode == 0 ? T : T - offset; d.pad_rows = output_bin - max_bin;
-    launch_head_sigmoid(f3, out_w->dev, d, stream);
-    if (mode == 2) launch_mul_crop(xd, od, false, (long long)B * 2 * output_bin, T, Wm, offset, stream);
+    mask_head(f3, mode == 0 ? 0 : offset, mode == 0 ? T : T - offset, od);
+    if (mode == 2) launch_mul_crop(xd, od, is_complex, (long long)B * 2 * output_bin, T, Wm, offset, stream);
     if (!out_on_device) VR_HIP(hipMemcpyAsync(out, od, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
     if (training) affine_dirty = true;
@@ -1406,26 +1395,13 @@ __global__ __launch_bounds__(256) void l1_crop_kernel(const float* __restrict__ 
 
 int l1_crop_blocks() { return 1024; }
 
-void launch_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
+void launch_l1_crop(L1CropForm form, const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss,
+                    hipStream_t st) {
     const long long total = rows * Wm;
     const int nblk = l1_crop_blocks();
-    VR_LAUNCH((l1_crop_kernel<false>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
-    VR_HIP(hipGetLastError());
-    launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
-}
-
-void launch_l1_crop_complex(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
-    const long long total = rows * Wm;
-    const int nblk = l1_crop_blocks();
-    VR_LAUNCH((l1_crop_kernel<true>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
-    VR_HIP(hipGetLastError());
-    launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
-}
-
-void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T, int Wm, int off, float* part, float* loss, hipStream_t st) {
-    const long long total = rows * Wm;
-    const int nblk = l1_crop_blocks();
-    VR_LAUNCH((l1_crop_kernel<true, MagL1>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    if (form == L1_CROP_REAL) VR_LAUNCH((l1_crop_kernel<false>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    else if (form == L1_CROP_COMPLEX) VR_LAUNCH((l1_crop_kernel<true>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
+    else VR_LAUNCH((l1_crop_kernel<true, MagL1>), dim3(nblk), dim3(256), 0, st, pred, y, T, Wm, off, total, part);
     VR_HIP(hipGetLastError());
     launch_reduce_rows(part, 1, nblk, loss, 1, 0, (float)(1.0 / (double)total), st);
 }
@@ -1435,21 +1411,13 @@ void launch_mag_l1_crop(const float* pred, const float* y, long long rows, int T
 void Model::set_loss(int kind, double weight) {
     VR_CHECK(kind == 0 || kind == 1 || kind == 3, -2,
              "vr_set_loss: kind must be VR_LOSS_L1 (0), VR_LOSS_MAG_L1_WAVE_SDR (1) or VR_LOSS_MAG_L1_WAVE_WSDR (3)");
-    if (kind == 3) {
-        VR_CHECK(is_complex, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
+    if (kind != 0) {
+        const std::string name = kind == 3 ? "VR_LOSS_MAG_L1_WAVE_WSDR" : "VR_LOSS_MAG_L1_WAVE_SDR";
+        VR_CHECK(is_complex, -2, "vr_set_loss: " + name + " needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
                                  "its wave term takes a complex spectrogram, and this handle predicts a magnitude mask");
-        VR_CHECK(complex_train, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs the option complex_train on (vr_set_option(h, \"complex_train\", 1)): "
+        VR_CHECK(complex_train, -2, "vr_set_loss: " + name + " needs the option complex_train on (vr_set_option(h, \"complex_train\", 1)): "
                                     "the training entry points refuse this complex handle without it");
-        VR_CHECK(wave_loss_available(plan, hop), -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_WSDR needs hop_length == n_fft / 2 (128 <= n_fft <= 4096), the "
-                                                     "tiled signal path; this handle has n_fft " + std::to_string(n_fft) + ", hop " + std::to_string(hop));
-        VR_CHECK(std::isfinite(weight), -2, "vr_set_loss: sdr_weight must be finite");
-    }
-    if (kind == 1) {
-        VR_CHECK(is_complex, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs a complex-mask handle (VR_CREATE_COMPLEX): the inverse STFT of "
-                                 "its wave term takes a complex spectrogram, and this handle predicts a magnitude mask");
-        VR_CHECK(complex_train, -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs the option complex_train on (vr_set_option(h, \"complex_train\", 1)): "
-                                    "the training entry points refuse this complex handle without it");
-        VR_CHECK(wave_loss_available(plan, hop), -2, "vr_set_loss: VR_LOSS_MAG_L1_WAVE_SDR needs hop_length == n_fft / 2 (128 <= n_fft <= 4096), the "
+        VR_CHECK(wave_loss_available(plan, hop), -2, "vr_set_loss: " + name + " needs hop_length == n_fft / 2 (128 <= n_fft <= 4096), the "
                                                      "tiled signal path; this handle has n_fft " + std::to_string(n_fft) + ", hop " + std::to_string(hop));
         VR_CHECK(std::isfinite(weight), -2, "vr_set_loss: sdr_weight must be finite");
     }
@@ -1489,7 +1457,7 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     need_real_mask("vr_validate_step (its L1 loss is defined on magnitudes)");
     VR_CHECK(!training, -2, "validate step runs in eval mode (train.py:109 model.eval()); call vr_set_mode(h, 0) first");
     VR_CHECK(B > 0, -2, "batch must be positive");
-    check_T(T, offset, 2);
+    check_T(T, offset, 2);                           // T % 16 == 0 and T > 2 * offset: the cropped width Wm is at least 16 frames
     const size_t E = is_complex ? 2 : 1;             // floats per element: a complex handle takes and predicts complex64
     const size_t in_floats = (size_t)B * 2 * output_bin * T * E;
     const size_t pack_floats = is_complex ? (size_t)B * 4 * output_bin * T : 0;
@@ -1499,15 +1467,14 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     // VR_LOSS_MAG_L1_WAVE_SDR: both waves of the cropped pair and the pair kernel's partial sums
     // VR_LOSS_MAG_L1_WAVE_WSDR: the mixture's wave too, and six partial sums per workgroup
     const bool wsdr_loss = loss_kind == 3, wave_loss = loss_kind == 1 || wsdr_loss;
-    const int signals = B * 2, pair_nb = wave_loss ? wave_pair_blocks(plan, Wm) : 0;
-    const size_t wave_floats = wave_loss ? (size_t)signals * hop * (Wm > 1 ? Wm - 1 : 0) : 0;
-    const size_t loss_extra = wave_loss ? (wsdr_loss ? 3 : 2) * wave_floats + (size_t)signals * pair_nb * (wsdr_loss ? 6 : 3) + 256 : 0;
+    const int signals = B * 2;
+    const WaveTermFloats wf = wave_loss ? wave_term_floats(plan, hop, loss_kind, signals, Wm) : WaveTermFloats{};
+    const size_t loss_extra = wave_loss ? wf.waves * wf.wave + wf.part + 256 : 0;
     fold_eval_affines();                    // before planning, as in forward_api
     plan_and_reserve(B, T, (2 * in_floats + pack_floats + out_floats + nblk + 64 + loss_extra) * sizeof(float) + 8192);
-    float* xd = ws.allocf(in_floats);
-    const float* yd = Y;
     const hipMemcpyKind kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    VR_HIP(hipMemcpyAsync(xd, X, in_floats * sizeof(float), kind, stream));
+    const float *xd = nullptr, *yd = Y;
+    const Tensor xt = net_input(X, &kind, B, T, &xd);
     if (!on_dev) {
         float* ty = ws.allocf(in_floats);
         VR_HIP(hipMemcpyAsync(ty, Y, in_floats * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -1516,63 +1483,22 @@ void Model::validate_api(const float* X, const float* Y, bool on_dev, int B, int
     float* od = ws.allocf(out_floats);
     float* part = ws.allocf(nblk);
     float* lossd = ws.allocf(16);
-    Tensor xt;
-    xt.p = xd; xt.N = B; xt.C = 2; xt.H = max_bin; xt.W = T;
-    xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
-    if (is_complex) {                       // the planar [re L, re R, im L, im R] input of forward_complex
-        float* xp = ws.allocf(pack_floats);
-        launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
-        xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
-    }
     Tensor f3 = run_net_window(xt, offset, T - offset);
-    HeadDst d{};
-    d.p = od; d.dH = Wm; d.dC = (long long)output_bin * Wm; d.dN = 2 * d.dC;
-    d.w_lo = offset; d.w_hi = T - offset; d.pad_rows = output_bin - max_bin;
     const long long rows = (long long)B * 2 * output_bin;
     float l4[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (wsdr_loss) {                        // mean | |y| - |p| | and the six wave sums of crop_center(X), crop_center(y) and p = predict(X)
-        launch_head_complex(f3, out_w->dev, d, stream);
-        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
-        prof_memset_async(lossd, 0, 7 * sizeof(float), stream);
-        launch_mag_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
-        if (pair_nb > 0) {
-            WaveTriple tr{};
-            tr.x = reinterpret_cast<const float2*>(xd); tr.y = reinterpret_cast<const float2*>(yd); tr.mask = nullptr;
-            tr.p = reinterpret_cast<const float2*>(od);
-            tr.xy_pitch = T; tr.xy_off = offset; tr.p_pitch = Wm;
-            tr.x_wave = ws.allocf(wave_floats); tr.y_wave = ws.allocf(wave_floats); tr.p_wave = ws.allocf(wave_floats);
-            tr.part = ws.allocf((size_t)signals * pair_nb * 6);
-            WaveTriple* td = reinterpret_cast<WaveTriple*>(ws.allocf(64));
-            triple_host = tr;
-            VR_HIP(hipMemcpyAsync(td, &triple_host, sizeof(WaveTriple), hipMemcpyHostToDevice, stream));
-            launch_istft_triple(plan, td, tr, signals, Wm, stream);
-            launch_reduce_rows(tr.part, 6, signals * pair_nb, lossd + 1, 6, 0, 1.f, stream);
-        }
-    } else if (wave_loss) {                 // mean | |y| - |p| | and the three wave sums of the cropped pair, p = predict(X) as materialised
-        launch_head_complex(f3, out_w->dev, d, stream);
-        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
-        prof_memset_async(lossd, 0, 4 * sizeof(float), stream);
-        launch_mag_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
-        if (pair_nb > 0) {
-            WavePair pr{};
-            pr.x = reinterpret_cast<const float2*>(od); pr.mask = nullptr; pr.y = reinterpret_cast<const float2*>(yd);
-            pr.x_pitch = Wm; pr.y_pitch = T; pr.y_off = offset;
-            pr.y_wave = ws.allocf(wave_floats); pr.p_wave = ws.allocf(wave_floats);
-            pr.part = ws.allocf((size_t)signals * pair_nb * 3);
-            WavePair* pd = reinterpret_cast<WavePair*>(ws.allocf(64));
-            pair_host = pr;
-            VR_HIP(hipMemcpyAsync(pd, &pair_host, sizeof(WavePair), hipMemcpyHostToDevice, stream));
-            launch_istft_pair(plan, pd, pr, signals, Wm, stream);
-            launch_reduce_rows(pr.part, 3, signals * pair_nb, lossd + 1, 3, 0, 1.f, stream);
-        }
-    } else if (is_complex) {
-        launch_head_complex(f3, out_w->dev, d, stream);
-        launch_mul_crop(xd, od, true, rows, T, Wm, offset, stream);
-        launch_l1_crop_complex(od, yd, rows, T, Wm, offset, part, lossd, stream);
-    } else {
-        launch_head_sigmoid(f3, out_w->dev, d, stream);
-        launch_mul_crop(xd, od, false, rows, T, Wm, offset, stream);
-        launch_l1_crop(od, yd, rows, T, Wm, offset, part, lossd, stream);
+    // p = predict(X) as materialised, then the loss of the handle's kind on p and crop_center(y)
+    mask_head(f3, offset, T - offset, od);
+    launch_mul_crop(xd, od, is_complex, rows, T, Wm, offset, stream);
+    if (wave_loss) prof_memset_async(lossd, 0, (wsdr_loss ? 7 : 4) * sizeof(float), stream);
+    launch_l1_crop(wave_loss ? L1_CROP_MAG : is_complex ? L1_CROP_COMPLEX : L1_CROP_REAL, od, yd, rows, T, Wm, offset, part, lossd, stream);
+    if (wave_loss) {                        // the three (kind 3: six) wave sums of crop_center(y), p (and crop_center(X))
+        const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd), *pc = reinterpret_cast<const float2*>(od);
+        float* w[3];
+        for (int i = 0; i < wf.waves; ++i) w[i] = ws.allocf(wf.wave);
+        float* wpart = ws.allocf(wf.part);
+        float* table = ws.allocf(wf.table);
+        if (wsdr_loss) launch_wave_term(plan, WaveTriple{xc, yc, nullptr, pc, T, offset, Wm, w[0], w[1], w[2], wpart}, table, &wave_host, signals, Wm, lossd + 1, stream);
+        else launch_wave_term(plan, WavePair{pc, nullptr, yc, Wm, T, offset, w[0], w[1], wpart}, table, &wave_host, signals, Wm, lossd + 1, stream);
     }
     VR_HIP(hipMemcpyAsync(l4, lossd, (wsdr_loss ? 7 : wave_loss ? 4 : 1) * sizeof(float), hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
@@ -1777,11 +1703,13 @@ void Model::run_crop_chunks(int patches, int bs, const std::function<void(int, i
     }
 }
 
-void Model::crop_mask_head(const Tensor& f3, int cropsize, HeadDst d) {
-    d.w_lo = offset; d.w_hi = cropsize - offset; d.pad_rows = output_bin - max_bin;
+void Model::mask_head(const Tensor& f3, int w_lo, int w_hi, HeadDst d) {
+    d.w_lo = w_lo; d.w_hi = w_hi; d.pad_rows = output_bin - max_bin;
     if (is_complex) launch_head_complex(f3, out_w->dev, d, stream);
     else launch_head_sigmoid(f3, out_w->dev, d, stream);
 }
+
+void Model::crop_mask_head(const Tensor& f3, int cropsize, HeadDst d) { mask_head(f3, offset, cropsize - offset, d); }
 
 void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst& d) {
     ws.reset();

@@ -17,6 +17,7 @@
 
 #include <cfloat>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace vr {
@@ -644,69 +645,96 @@ int wave_pair_blocks(const FFTPlan& pl, int T) {
     return T < 2 ? 0 : (T - 1 + S - 1) / S;
 }
 
-void launch_istft_pair(const FFTPlan& pl, const WavePair* pair_dev, const WavePair& pair, int signals, int T, hipStream_t st) {
+// The pair and the triple form of istft_tile_kernel: one body, the table entry's type picks the kernel instance
+template <class TABLE>
+static void launch_istft_table(const FFTPlan& pl, const TABLE* table_dev, const TABLE& t, int signals, int T, hipStream_t st) {
+    constexpr bool kTriple = std::is_same<TABLE, WaveTriple>::value;
     const int M = pl.n_fft / 2, bins = M + 1;
     const int nb = wave_pair_blocks(pl, T);
     if (nb == 0) return;
-    VR_CHECK(pair.y_off >= 0 && pair.y_off + T <= pair.y_pitch && T <= pair.x_pitch && signals > 0, -2, "pair iSTFT: the frames leave their rows");
+    if constexpr (kTriple)
+        VR_CHECK(t.xy_off >= 0 && t.xy_off + T <= t.xy_pitch && (t.mask || (t.p && T <= t.p_pitch)) && signals > 0, -2,
+                 "triple iSTFT: the frames leave their rows");
+    else
+        VR_CHECK(t.y_off >= 0 && t.y_off + T <= t.y_pitch && T <= t.x_pitch && signals > 0, -2, "pair iSTFT: the frames leave their rows");
     const int F = tile_frames(pl, M);
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const WavePair>), 160 * 1024);
-    // both spectrograms (and the mask) read once, both waves written, the target's wave read back by the thread that stored it
-    prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * (pair.mask ? 3 : 2) + 3.0 * 4.0 * (double)M * (T - 1)));
-    VR_LAUNCH((istft_tile_kernel<true, const WavePair>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, pair_dev, T, F - 1,
-              (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const TABLE>), 160 * 1024);
+    // every spectrogram read once (pair: target and estimate; triple: the mixture too; fused: the mask and the mixture again), the waves
+    // written, the target's wave (triple: the mixture's twice as well) read back by the thread that stored it
+    prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * ((kTriple ? 3 : 2) + (t.mask ? 1 : 0)) + (kTriple ? 6.0 : 3.0) * 4.0 * (double)M * (T - 1)));
+    if constexpr (kTriple)
+        VR_LAUNCH((istft_tile_kernel<true, const WaveTriple>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, table_dev, T, F - 1,
+                  (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
+    else
+        VR_LAUNCH((istft_tile_kernel<true, const WavePair>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, table_dev, T, F - 1,
+                  (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
     VR_HIP(hipGetLastError());
+}
+
+void launch_istft_pair(const FFTPlan& pl, const WavePair* pair_dev, const WavePair& pair, int signals, int T, hipStream_t st) {
+    launch_istft_table(pl, pair_dev, pair, signals, T, st);
 }
 
 void launch_istft_triple(const FFTPlan& pl, const WaveTriple* triple_dev, const WaveTriple& tr, int signals, int T, hipStream_t st) {
-    const int M = pl.n_fft / 2, bins = M + 1;
-    const int nb = wave_pair_blocks(pl, T);
-    if (nb == 0) return;
-    VR_CHECK(tr.xy_off >= 0 && tr.xy_off + T <= tr.xy_pitch && (tr.mask || (tr.p && T <= tr.p_pitch)) && signals > 0, -2,
-             "triple iSTFT: the frames leave their rows");
-    const int F = tile_frames(pl, M);
-    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
-    static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const WaveTriple>), 160 * 1024);
-    // the mixture and the target read once, the estimate once (fused: the mask and the mixture again), three waves written, the mixture's
-    // wave read back twice and the target's once by the thread that stored them
-    prof_note(0.0, (double)signals * ((double)bins * T * 8.0 * (tr.mask ? 4 : 3) + 6.0 * 4.0 * (double)M * (T - 1)));
-    VR_LAUNCH((istft_tile_kernel<true, const WaveTriple>), dim3((unsigned)nb, (unsigned)signals), dim3(1024), lds, st, pl, triple_dev, T, F - 1,
-              (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, (float*)nullptr, (long long)M * (T - 1));
-    VR_HIP(hipGetLastError());
+    launch_istft_table(pl, triple_dev, tr, signals, T, st);
 }
 
-void launch_stft_wave_grad3(const FFTPlan& pl, const WaveGrad3& g, int signals, int T, hipStream_t st) {
+// the table entry on its way to the device: through the caller's staging slot on the stream, or (no slot) synchronously
+template <class TABLE>
+static const TABLE* send_wave_table(const TABLE& t, float* table_dev, WaveTable* staging, hipStream_t st) {
+    if (staging) {
+        memcpy(staging, &t, sizeof(TABLE));
+        VR_HIP(hipMemcpyAsync(table_dev, staging, sizeof(TABLE), hipMemcpyHostToDevice, st));
+    } else {
+        VR_HIP(hipMemcpy(table_dev, &t, sizeof(TABLE), hipMemcpyHostToDevice));
+    }
+    return reinterpret_cast<const TABLE*>(table_dev);
+}
+
+void launch_wave_term(const FFTPlan& pl, const WavePair& pair, float* table_dev, WaveTable* staging, int signals, int T, float* sums,
+                      hipStream_t st) {
+    launch_istft_pair(pl, send_wave_table(pair, table_dev, staging, st), pair, signals, T, st);
+    launch_reduce_rows(pair.part, 3, signals * wave_pair_blocks(pl, T), sums, 3, 0, 1.f, st);
+}
+
+void launch_wave_term(const FFTPlan& pl, const WaveTriple& tr, float* table_dev, WaveTable* staging, int signals, int T, float* sums,
+                      hipStream_t st) {
+    launch_istft_triple(pl, send_wave_table(tr, table_dev, staging, st), tr, signals, T, st);
+    launch_reduce_rows(tr.part, 6, signals * wave_pair_blocks(pl, T), sums, 6, 0, 1.f, st);
+}
+
+WaveTermFloats wave_term_floats(const FFTPlan& pl, int hop, int kind, int signals, int T) {
+    const int waves = kind == 3 ? 3 : 2;
+    return WaveTermFloats{waves, (size_t)signals * hop * (T - 1), (size_t)signals * wave_pair_blocks(pl, T) * (waves == 3 ? 6 : 3), 64};
+}
+
+// The two- and the three-wave gradient form of stft_tile_kernel: one body, the argument struct's type picks the kernel instance
+template <class GRAD>
+static void launch_wave_grad(const FFTPlan& pl, const GRAD& g, int signals, int T, hipStream_t st) {
+    constexpr bool kThree = std::is_same<GRAD, WaveGrad3>::value;
     const int M = pl.n_fft / 2, bins = M + 1;
     int F = tile_frames(pl, 0);
     if (F > 16) F = 16;
     F = F / TG * TG;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
     static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, WaveGrad3>), 160 * 1024);
-    // three waves read, X (and mask, Y with the L1 part) read, dmask written
-    prof_note(0.0, (double)signals * (3.0 * 4.0 * (double)M * (T - 1) + 8.0 * (double)bins * T * (g.l1_scale != 0.f ? 4 : 2)));
-    VR_LAUNCH((stft_tile_kernel<const float, WaveGrad3>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
-              (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, GRAD>), 160 * 1024);
+    // two or three waves read, X (and mask, Y with the L1 part) read, dmask written
+    prof_note(0.0, (double)signals * ((kThree ? 3.0 : 2.0) * 4.0 * (double)M * (T - 1) + 8.0 * (double)bins * T * (g.l1_scale != 0.f ? 4 : 2)));
+    if constexpr (kThree)
+        VR_LAUNCH((stft_tile_kernel<const float, WaveGrad3>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
+                  (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
+    else
+        VR_LAUNCH((stft_tile_kernel<const float, WaveGrad>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
+                  (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
     VR_HIP(hipGetLastError());
 }
 
-void launch_stft_wave_grad(const FFTPlan& pl, const WaveGrad& g, int signals, int T, hipStream_t st) {
-    const int M = pl.n_fft / 2, bins = M + 1;
-    int F = tile_frames(pl, 0);
-    if (F > 16) F = 16;
-    F = F / TG * TG;
-    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
-    static std::atomic<unsigned long long> attr_done{0};
-    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, WaveGrad>), 160 * 1024);
-    // two waves read, X (and mask, Y with the L1 part) read, dmask written
-    prof_note(0.0, (double)signals * (2.0 * 4.0 * (double)M * (T - 1) + 8.0 * (double)bins * T * (g.l1_scale != 0.f ? 4 : 2)));
-    VR_LAUNCH((stft_tile_kernel<const float, WaveGrad>), dim3((unsigned)((T + F - 1) / F), (unsigned)signals), dim3(1024), lds, st, pl,
-              (const float*)nullptr, (long long)M * (T - 1), T, F, (float2*)nullptr, g);
-    VR_HIP(hipGetLastError());
-}
+void launch_stft_wave_grad3(const FFTPlan& pl, const WaveGrad3& g, int signals, int T, hipStream_t st) { launch_wave_grad(pl, g, signals, T, st); }
+
+void launch_stft_wave_grad(const FFTPlan& pl, const WaveGrad& g, int signals, int T, hipStream_t st) { launch_wave_grad(pl, g, signals, T, st); }
 
 // irfft(spec[:, t]) * window -> frames[ch][t][0..n)
 __global__ __launch_bounds__(256) void istft_frame_kernel(FFTPlan pl, const float2* __restrict__ spec, int T,

@@ -457,144 +457,121 @@ void Model::flush_wgrad_sums() {
     wred_host.clear();
 }
 
+// ---- the train-form head: the one path from the feature tensor f3 to the loss and to the gradients of f3 and of the head weights, for
+// the fused step, the split step's backward (launch_head_grads, its "dlogit is given" tail) and the head_* hooks of debug.hip ------------
+void launch_head_grads(const Tensor& f3, int CO, const float* w, const float* dlogit, float* wpart, float* g, int g_acc, float* dw,
+                       int dw_acc, hipStream_t st) {
+    launch_thin_wgrad(f3, CO, dlogit, wpart, dw, dw_acc, st);
+    launch_thin_dgrad(f3, CO, w, dlogit, g, g_acc, st);
+}
+
+void run_train_head(const FFTPlan& pl, const Tensor& f3, const TrainHead& h, const HeadScratch& s, WaveTable* staging, hipStream_t st) {
+    const int CO = h.cplx ? 4 : 2;
+    if (h.kind == 0) {
+        if (h.cplx) launch_head_loss_complex(f3, h.w, h.X, h.Y, h.bins, h.grad_scale, s.dlogit, h.mask, s.lpart, h.loss, h.loss_scale, st);
+        else launch_head_loss(f3, h.w, h.X, h.Y, h.bins, h.grad_scale, s.dlogit, h.mask, s.lpart, h.loss, h.loss_scale, st);
+        if (!h.dw) return;
+    } else {
+        // VR_LOSS_MAG_L1_WAVE_SDR / _WSDR (DESIGN.md sections 6n, 6o): the mask and the magnitude term, the waves and their three or six
+        // sums behind it in `loss`, dmask from the sums, dlogit from dmask
+        float* mask = h.mask ? h.mask : s.mask;
+        launch_head_mag_l1(f3, h.w, h.X, h.Y, h.bins, mask, s.lpart, h.loss, h.loss_scale, st);
+        if (!h.dw) return;
+        const int signals = f3.N * 2, T = f3.W;
+        const float2 *xc = reinterpret_cast<const float2*>(h.X), *yc = reinterpret_cast<const float2*>(h.Y), *mc = reinterpret_cast<const float2*>(mask);
+        float2* dm = reinterpret_cast<float2*>(s.dmask);
+        if (h.kind == 3) {
+            launch_wave_term(pl, WaveTriple{xc, yc, mc, nullptr, T, 0, T, s.wave[2], s.wave[0], s.wave[1], s.part}, s.table, staging, signals, T, h.loss + 1, st);
+            launch_stft_wave_grad3(pl, WaveGrad3{s.wave[2], s.wave[0], s.wave[1], h.loss + 1, xc, mc, yc, dm, h.sdr_scale, h.grad_scale}, signals, T, st);
+        } else {
+            launch_wave_term(pl, WavePair{xc, mc, yc, T, T, 0, s.wave[0], s.wave[1], s.part}, s.table, staging, signals, T, h.loss + 1, st);
+            launch_stft_wave_grad(pl, WaveGrad{s.wave[0], s.wave[1], h.loss + 1, xc, mc, yc, dm, h.sdr_scale, h.grad_scale}, signals, T, st);
+        }
+        launch_head_bwd_complex(f3, h.w, s.dmask, h.bins, s.dlogit, st);
+    }
+    launch_head_grads(f3, CO, h.w, s.dlogit, s.wpart, h.g, h.g_acc, h.dw, h.dw_acc, st);
+}
+
+// The planning block of the two training entry points: `dry_run` (forward + backward on measuring arenas) sizes ws and gs, both grow to
+// it (ws by extra_ws bytes more), and the zero ranges of gs (gs_zero_plan; the real pass allocates in the same order) are cleared --
+// beside the forward on lanes[0].main (the fused step: gs is only touched from the loss kernels on) or on the main stream.
+template <class F>
+void Model::plan_train_arenas(F&& dry_run, size_t extra_ws, bool clear_beside) {
+    Arena sws = ws, sgs = gs;
+    ws.dry = gs.dry = true; ws.base = gs.base = nullptr; ws.off = gs.off = 0; ws.peak = gs.peak = 0;
+    dry = true;
+    try { dry_run(); }
+    catch (...) { dry = false; ws = sws; gs = sgs; tape.clear(); throw; }
+    dry = false;
+    gs_zero_plan = gs_zero;
+    const size_t need_ws = ws.peak + extra_ws, need_gs = gs.peak + 4096;
+    ws = sws; gs = sgs;
+    ensure_ws(need_ws);
+    if (need_gs > gs.cap) {
+        VR_HIP(hipStreamSynchronize(stream));
+        if (gs.base) VR_HIP(hipFree(gs.base));
+        gs.base = nullptr; gs.cap = 0;
+        VR_HIP(hipMalloc(reinterpret_cast<void**>(&gs.base), need_gs + (need_gs >> 4)));
+        gs.cap = need_gs + (need_gs >> 4);
+    }
+    ws.reset(); gs.reset();
+    if (clear_beside && !lanes.empty()) {
+        VR_HIP(hipEventRecord(lanes[0].fork, stream));            // (previous step's consumers of gs are done)
+        VR_HIP(hipStreamWaitEvent(lanes[0].main, lanes[0].fork, 0));
+        clear_gs_zero_ranges(lanes[0].main);
+        VR_HIP(hipEventRecord(lanes[0].join, lanes[0].main));
+        gs_clear_pending = true;
+    } else {
+        wait_gs_clear();
+        clear_gs_zero_ranges(stream);
+    }
+}
+
+void Model::wait_gs_clear() {
+    if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
+}
+
+// what both train-mode entry points do after their checks: the flipped / transposed weights for the data gradients and the Winograd-domain
+// copies of both, once per step (before the planning dry run: the kernel choice, hence the partial-statistics layout, depends on them)
+void Model::refresh_train_weights() {
+    ensure_train_state();
+    launch_flip_transpose(d_flip, n_flip, stream);
+    launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
+    refresh_wino(true);
+}
+
 void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B, int T, int accumulation_steps,
                               float* loss_out, float* mask_out, bool mask_on_dev) {
     DeviceGuard dev_guard(device);
     VR_CHECK(training, -2, "train step needs train mode: call vr_set_mode(h, 1) (model.train(), train.py:69)");
     graph_valid = false;
     VR_CHECK(B > 0 && accumulation_steps > 0, -2, "batch and accumulation_steps must be positive");
+    // (so T >= 16: the wave terms of kinds 1 / 3 always have samples)
     VR_CHECK(T > 0 && T % 16 == 0, -5, "h1_shape[3] must be greater than h2_shape[3] (frames must be a multiple of 16)");
-    ensure_train_state();
-    // flipped/transposed weights for the data gradients + Winograd-domain copies of both, once per step
-    // (before the planning dry run: the kernel choice, hence the partial-statistics layout, depends on them)
-    launch_flip_transpose(d_flip, n_flip, stream);
-    launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
-    refresh_wino(true);
+    refresh_train_weights();
     // a complex handle ("complex_train"): X, y, mask are interleaved complex64, the network reads four planar channels, the head has four
-    // outputs -- every buffer below that holds complex or four-channel data doubles (cplx), in the dry run and the real one alike
-    const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;
-    const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
-    const int Hm = max_bin;
+    // outputs -- every buffer below that holds complex or four-channel data doubles, in the dry run and the real one alike
+    const size_t io_floats = (size_t)B * 2 * output_bin * T * (is_complex ? 2 : 1);
     const bool wsdr_loss = loss_kind == 3, wave_loss = loss_kind == 1 || wsdr_loss;      // VR_LOSS_MAG_L1_WAVE_WSDR: DESIGN.md section 6o
-    // ---- plan: dry run of forward + backward sizes both arenas ----------------------------------------
+    const double ntot = (double)B * 2 * output_bin * T;          // (complex handle: complex elements, as torch's L1Loss counts them)
     auto run_all = [&](const float* xd, const float* yd, float* maskd, float* lossd) {
         tape.clear();
         g_fresh.clear(); gs_zero.clear();
-        Tensor xt;
-        xt.p = const_cast<float*>(xd); xt.N = B; xt.C = 2; xt.H = Hm; xt.W = T;
-        xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
-        if (is_complex) {                            // [B][2][bins][T] complex64 -> planar [B][4][bins][T] (re L, re R, im L, im R), unscaled
-            float* xp = ws.allocf((size_t)B * 4 * output_bin * T);
-            if (!dry) launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
-            xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
-        }
-        Tensor f3 = run_net(xt);
-        // head + loss (train.py:81,89) and its backward into f3.g / out.weight
-        float* dlogit = ws.allocf((size_t)B * CO * Hm * T);
-        float* lpart = ws.allocf((size_t)head_loss_blocks(f3));
-        float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
-        // VR_LOSS_MAG_L1_WAVE_SDR: the mask (kept even when the caller does not ask for it), both waves, dmask and the
-        // pair kernel's partial sums
-        const int signals = B * 2, pair_nb = wave_loss ? wave_pair_blocks(plan, T) : 0;
-        const size_t wave_floats = (size_t)signals * hop * (T - 1);
-        float *wl_mask = nullptr, *wl_dmask = nullptr, *wl_table = nullptr;
-        WavePair pr{};
-        float* x_wave = nullptr;                             // (kind 3) the mixture's wave; its partials are six wide
-        if (wave_loss) {
-            wl_mask = ws.allocf(io_floats);                  // (allocated either way: the dry run, which has no maskd, sizes the same)
-            if (maskd) wl_mask = maskd;
-            wl_dmask = ws.allocf(io_floats);
-            pr.y_wave = ws.allocf(wave_floats); pr.p_wave = ws.allocf(wave_floats);
-            if (wsdr_loss) x_wave = ws.allocf(wave_floats);
-            pr.part = ws.allocf((size_t)signals * pair_nb * (wsdr_loss ? 6 : 3));
-            wl_table = ws.allocf(64);
-        }
-        if (!dry && wsdr_loss) {
-            if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
-            const double ntot = (double)B * 2 * output_bin * T;
-            const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd);
-            launch_head_mag_l1(f3, out_w->dev, xd, yd, output_bin, wl_mask, lpart, lossd, (float)(1.0 / ntot), stream);
-            WaveTriple tr{};
-            tr.x = xc; tr.y = yc; tr.mask = reinterpret_cast<const float2*>(wl_mask); tr.p = nullptr;
-            tr.xy_pitch = tr.p_pitch = T; tr.xy_off = 0;
-            tr.x_wave = x_wave; tr.y_wave = pr.y_wave; tr.p_wave = pr.p_wave; tr.part = pr.part;
-            triple_host = tr;
-            VR_HIP(hipMemcpyAsync(wl_table, &triple_host, sizeof(WaveTriple), hipMemcpyHostToDevice, stream));
-            launch_istft_triple(plan, reinterpret_cast<const WaveTriple*>(wl_table), tr, signals, T, stream);
-            launch_reduce_rows(tr.part, 6, signals * pair_nb, lossd + 1, 6, 0, 1.f, stream);
-            WaveGrad3 wg{};
-            wg.x_wave = tr.x_wave; wg.y_wave = tr.y_wave; wg.p_wave = tr.p_wave; wg.sums = lossd + 1;
-            wg.X = xc; wg.mask = tr.mask; wg.Y = yc; wg.dmask = reinterpret_cast<float2*>(wl_dmask);
-            wg.sdr_scale = (float)(sdr_weight / accumulation_steps);
-            wg.l1_scale = (float)(1.0 / (ntot * accumulation_steps));
-            launch_stft_wave_grad3(plan, wg, signals, T, stream);
-            launch_head_bwd_complex(f3, out_w->dev, wl_dmask, output_bin, dlogit, stream);
-            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
-            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
-        } else if (!dry && wave_loss) {
-            if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
-            const double ntot = (double)B * 2 * output_bin * T;
-            const float2 *xc = reinterpret_cast<const float2*>(xd), *yc = reinterpret_cast<const float2*>(yd);
-            launch_head_mag_l1(f3, out_w->dev, xd, yd, output_bin, wl_mask, lpart, lossd, (float)(1.0 / ntot), stream);
-            pr.x = xc; pr.mask = reinterpret_cast<const float2*>(wl_mask); pr.y = yc;
-            pr.x_pitch = pr.y_pitch = T; pr.y_off = 0;
-            pair_host = pr;
-            VR_HIP(hipMemcpyAsync(wl_table, &pair_host, sizeof(WavePair), hipMemcpyHostToDevice, stream));
-            launch_istft_pair(plan, reinterpret_cast<const WavePair*>(wl_table), pr, signals, T, stream);
-            launch_reduce_rows(pr.part, 3, signals * pair_nb, lossd + 1, 3, 0, 1.f, stream);
-            WaveGrad wg{};
-            wg.y_wave = pr.y_wave; wg.p_wave = pr.p_wave; wg.sums = lossd + 1;
-            wg.X = xc; wg.mask = pr.mask; wg.Y = yc; wg.dmask = reinterpret_cast<float2*>(wl_dmask);
-            wg.sdr_scale = (float)(sdr_weight / accumulation_steps);
-            wg.l1_scale = (float)(1.0 / (ntot * accumulation_steps));
-            launch_stft_wave_grad(plan, wg, signals, T, stream);
-            launch_head_bwd_complex(f3, out_w->dev, wl_dmask, output_bin, dlogit, stream);
-            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
-            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
-        } else if (!dry) {
-            if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
-            const double ntot = (double)B * 2 * output_bin * T;          // (complex handle: complex elements, as torch's L1Loss counts them)
-            if (is_complex)
-                launch_head_loss_complex(f3, out_w->dev, xd, yd, output_bin, (float)(1.0 / (ntot * accumulation_steps)), dlogit, maskd,
-                                         lpart, lossd, (float)(1.0 / ntot), stream);
-            else
-                launch_head_loss(f3, out_w->dev, xd, yd, output_bin, (float)(1.0 / (ntot * accumulation_steps)), dlogit, maskd,
-                                 lpart, lossd, (float)(1.0 / ntot), stream);
-            launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
-            launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+        Tensor f3 = run_net(net_input(xd, nullptr, B, T));
+        // head + loss (train.py:81,89) and its backward into f3.g / out.weight; kinds 1 / 3 keep the mask even when the caller does not ask
+        // for it (scratch: the dry run, which has no maskd, sizes the same)
+        const HeadScratch hs = head_scratch([&](size_t n) { return ws.allocf(n); }, plan, hop, f3, loss_kind, is_complex, output_bin);
+        if (!dry) {
+            wait_gs_clear();
+            const TrainHead h{loss_kind, is_complex, out_w->dev, xd, yd, output_bin, maskd, lossd, (float)(1.0 / ntot),
+                              (float)(1.0 / (ntot * accumulation_steps)), (float)(sdr_weight / accumulation_steps),
+                              f3.g, g_first(f3.g) ? 0 : 1, grad_of(out_w), 1};
+            run_train_head(plan, f3, h, hs, &wave_host, stream);
         }
         backward();
     };
-    {
-        Arena sws = ws, sgs = gs;
-        ws.dry = gs.dry = true; ws.base = gs.base = nullptr; ws.off = gs.off = 0; ws.peak = gs.peak = 0;
-        dry = true;
-        try { run_all(reinterpret_cast<float*>(uintptr_t(256)), nullptr, nullptr, nullptr); }
-        catch (...) { dry = false; ws = sws; gs = sgs; tape.clear(); throw; }
-        dry = false;
-        gs_zero_plan = gs_zero;                      // which buffers of gs need a zero fill (the real pass allocates in the same order)
-        const size_t need_ws = ws.peak + (3 * io_floats + 64) * sizeof(float) + 8192, need_gs = gs.peak + 4096;
-        ws = sws; gs = sgs;
-        ensure_ws(need_ws);
-        if (need_gs > gs.cap) {
-            VR_HIP(hipStreamSynchronize(stream));
-            if (gs.base) VR_HIP(hipFree(gs.base));
-            gs.base = nullptr; gs.cap = 0;
-            VR_HIP(hipMalloc(reinterpret_cast<void**>(&gs.base), need_gs + (need_gs >> 4)));
-            gs.cap = need_gs + (need_gs >> 4);
-        }
-        ws.reset(); gs.reset();
-        // the activation-gradient arena is only touched from the loss kernels on: clear it beside the forward pass
-        if (!lanes.empty()) {
-            VR_HIP(hipEventRecord(lanes[0].fork, stream));            // (previous step's consumers of gs are done)
-            VR_HIP(hipStreamWaitEvent(lanes[0].main, lanes[0].fork, 0));
-            clear_gs_zero_ranges(lanes[0].main);
-            VR_HIP(hipEventRecord(lanes[0].join, lanes[0].main));
-            gs_clear_pending = true;
-        } else {
-            clear_gs_zero_ranges(stream);
-        }
-    }
+    plan_train_arenas([&] { run_all(reinterpret_cast<float*>(uintptr_t(256)), nullptr, nullptr, nullptr); },
+                  (3 * io_floats + 64) * sizeof(float) + 8192, true);
     prepare_dropout(B);
     // ---- inputs ---------------------------------------------------------------------------------------------------
     const float *xd = X, *yd = Y;
@@ -632,67 +609,26 @@ void Model::forward_train_api(const float* X, bool on_dev, int B, int T, float* 
     VR_CHECK(T > 0 && T % 16 == 0, -5, "h1_shape[3] must be greater than h2_shape[3] (frames must be a multiple of 16)");
     VR_CHECK(mask_out != nullptr, -2, "null argument");
     graph_valid = false;
-    ensure_train_state();
-    launch_flip_transpose(d_flip, n_flip, stream);
-    launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
-    refresh_wino(true);
-    const int cplx = is_complex ? 2 : 1, CO = 2 * cplx;          // as in train_fwd_bwd_api
-    const size_t io_floats = (size_t)B * 2 * output_bin * T * cplx;
-    const int Hm = max_bin;
-    auto fwd = [&](const float* xd) {
+    refresh_train_weights();
+    const int CO = is_complex ? 4 : 2;
+    const size_t io_floats = (size_t)B * 2 * output_bin * T * (is_complex ? 2 : 1);
+    auto fwd = [&](const float* x, const hipMemcpyKind* copy) {
         tape.clear();
         g_fresh.clear(); gs_zero.clear();
-        Tensor xt;
-        xt.p = const_cast<float*>(xd); xt.N = B; xt.C = 2; xt.H = Hm; xt.W = T;
-        xt.sH = T; xt.sC = (long long)output_bin * T; xt.sN = 2 * xt.sC; xt.slope = 1.f;
-        if (is_complex) {
-            float* xp = ws.allocf((size_t)B * 4 * output_bin * T);
-            if (!dry) launch_pack_complex(reinterpret_cast<const float2*>(xd), B, output_bin, T, xp, T, 0, nullptr, stream);
-            xt.p = xp; xt.C = 4; xt.sN = 4 * xt.sC;
-        }
-        return run_net(xt);
+        return run_net(net_input(x, copy, B, T));
     };
-    auto bwd_scratch = [&](const Tensor& f3) {       // the allocations backward_api makes, in its order
-        ws.allocf((size_t)B * CO * Hm * T);
+    plan_train_arenas([&] {
+        ws.allocf(3 * io_floats + 64);               // the real run's input copy, graph_mask and 64 floats to spare
+        Tensor f3 = fwd(reinterpret_cast<float*>(uintptr_t(256)), nullptr);
+        ws.allocf((size_t)B * CO * max_bin * T);     // the allocations backward_api makes, in its order
         ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
-    };
-    {   // plan: dry run of forward + backward sizes both arenas
-        Arena sws = ws, sgs = gs;
-        ws.dry = gs.dry = true; ws.base = gs.base = nullptr; ws.off = gs.off = 0; ws.peak = gs.peak = 0;
-        dry = true;
-        try {
-            ws.allocf(3 * io_floats + 64);
-            Tensor f3 = fwd(reinterpret_cast<float*>(uintptr_t(256)));
-            bwd_scratch(f3);
-            backward();
-        } catch (...) { dry = false; ws = sws; gs = sgs; tape.clear(); throw; }
-        dry = false;
-        gs_zero_plan = gs_zero;
-        const size_t need_ws = ws.peak + 8192, need_gs = gs.peak + 4096;
-        ws = sws; gs = sgs;
-        ensure_ws(need_ws);
-        if (need_gs > gs.cap) {
-            VR_HIP(hipStreamSynchronize(stream));
-            if (gs.base) VR_HIP(hipFree(gs.base));
-            gs.base = nullptr; gs.cap = 0;
-            VR_HIP(hipMalloc(reinterpret_cast<void**>(&gs.base), need_gs + (need_gs >> 4)));
-            gs.cap = need_gs + (need_gs >> 4);
-        }
-        ws.reset(); gs.reset();
-        if (gs_clear_pending) { VR_HIP(hipStreamWaitEvent(stream, lanes[0].join, 0)); gs_clear_pending = false; }
-        clear_gs_zero_ranges(stream);
-    }
+        backward();
+    }, 8192, false);
     prepare_dropout(B);
-    float* xd = ws.allocf(io_floats);
     graph_mask = ws.allocf(io_floats);
-    ws.allocf(io_floats + 64);                                     // (keeps the dry run's offsets)
-    VR_HIP(hipMemcpyAsync(xd, X, io_floats * sizeof(float), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-    graph_f3 = fwd(xd);
-    HeadDst d{};
-    d.p = graph_mask; d.dH = T; d.dC = (long long)output_bin * T; d.dN = 2 * d.dC;
-    d.w_lo = 0; d.w_hi = T; d.pad_rows = output_bin - max_bin;
-    if (is_complex) launch_head_complex(graph_f3, out_w->dev, d, stream);       // (d's strides count complex elements)
-    else launch_head_sigmoid(graph_f3, out_w->dev, d, stream);
+    const hipMemcpyKind kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    graph_f3 = fwd(X, &kind);
+    mask_head(graph_f3, 0, T, graph_mask);
     VR_HIP(hipMemcpyAsync(mask_out, graph_mask, io_floats * sizeof(float), mask_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
     VR_HIP(hipStreamSynchronize(stream));
     graph_valid = true; graph_B = B; graph_T = T; ++graph_gen;
@@ -720,8 +656,7 @@ void Model::backward_api(const float* dmask, bool on_dev) {
     float* wpart = ws.allocf((size_t)thin_wgrad_blocks(f3) * CO * f3.C);
     if (is_complex) launch_head_bwd_complex(f3, out_w->dev, dm, output_bin, dlogit, stream);
     else launch_head_bwd(dm, graph_mask, B, Hm, T, output_bin, dlogit, stream);
-    launch_thin_wgrad(f3, CO, dlogit, wpart, grad_of(out_w), 1, stream);
-    launch_thin_dgrad(f3, CO, out_w->dev, dlogit, f3.g, g_first(f3.g) ? 0 : 1, stream);
+    launch_head_grads(f3, CO, out_w->dev, dlogit, wpart, f3.g, g_first(f3.g) ? 0 : 1, grad_of(out_w), 1, stream);
     backward();
     VR_HIP(hipStreamSynchronize(stream));
     tape.clear();
