@@ -229,6 +229,32 @@ int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int sp
 int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
                           int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device);
 
+/* ---- score a separation against the true stems: windowed SDR sums on the device -----------------
+ * vr_separate_wave_many that also measures each song.  mix[s], inst[s]: float32 [2, L[s]], the mixture and its true instruments (both
+ * on the host or both on the device, `on_device`).  With samples = hop * (L / hop), the stems y, v of vr_separate_wave and the true stems
+ * r_y = inst[:, :samples], r_v = (mix - inst)[:, :samples], window w covers samples [w * window, min((w + 1) * window, samples)) of both
+ * channels, n_windows = ceil(samples / window), and
+ *     sums[s][w] = { sum r_y^2, sum (r_y - y)^2, sum r_v^2, sum (r_v - v)^2 }            (HOST doubles, [n_windows][4])
+ * Every term is formed and added in double from the float32 samples; the estimate is the very float the stem holds (or would hold).
+ * The library returns sums, not decibels, and hides no epsilon: sdr = 10 log10(sums[.][0] / sums[.][1]) per window, from the column
+ * sums for the whole song (spec_utils.sdr_from_sums).  Two identical calls give bit-identical sums: no atomics, a fixed order.
+ * y_waves / v_waves: the stems as vr_separate_wave_many returns them, or BOTH tables null: sums only -- no stem is then allocated,
+ * stored or copied.  window >= hop_length (44100 = one second of the reference's audio).  tta (flag word) / batchsize / cropsize as
+ * vr_separate_wave_many.  Magnitude and VR_CREATE_COMPLEX handles; float waves only (no sample bytes, no PCM16 stems, no streams), and
+ * only where hop_length == n_fft / 2 -- the sums are formed in the frame-tiled masked iSTFT kernel, which exists only there.
+ * Errors (VR_ERR_BAD_ARGUMENT, the device untouched): n_songs <= 0, a null table, one stem table null and the other not (these before
+ * the handle is looked at); a null entry, L[s] < hop_length, window < hop_length, another hop, training mode.  Errors of a many-call
+ * start with "song <s>: " where they concern one song.
+ *   vr_evaluate_wave     the many-call of one song (`solo` as for vr_separate_wave: batchsize <= 0 = the crops of its longer pass);
+ *                        y_wave and v_wave both null: sums only
+ *   vr_evaluate_plan     no handle, no device: samples and n_windows of a song of L samples (L < hop or window < hop: VR_ERR_BAD_ARGUMENT) */
+int vr_evaluate_wave_many(vr_handle h, int n_songs, const float* const* mix, const float* const* inst, int on_device, const int64_t* L, int tta,
+                          int batchsize, int cropsize, int64_t window, double* const* sums, float* const* y_waves, float* const* v_waves,
+                          int out_on_device);
+int vr_evaluate_wave(vr_handle h, const float* mix, const float* inst, int on_device, int64_t L, int tta, int batchsize, int cropsize,
+                     int64_t window, double* sums, float* y_wave, float* v_wave, int out_on_device);
+int vr_evaluate_plan(int hop, int64_t L, int64_t window, int64_t* samples, int64_t* n_windows);
+
 /* ---- streaming separation: push audio in blocks, get the stems back with bounded state -----------------------------------
  * The offline call's crops sit at multiples of roi = cropsize - 2 * offset whatever the song's length (make_padding: pad_l = offset),
  * the --tta pass is the same list shifted by roi / 2, and with hop == n_fft / 2 frame t needs the samples below (t + 1) * hop.  The
@@ -512,7 +538,7 @@ int vr_debug_merge_artifacts_weight(const float* frame_min, int T, float thres, 
                                     float* weight_out);
 /* One kernel of the training path or of the signal front end in isolation, host pointers in and out (csrc/debug.hip lists
  * the names, their dims / float parameters / inputs / outputs): bn_backward, lstm, upsample, pool, thin, head_loss, rows,
- * adam, wire, signal_norm, signal_mask.                                                                             */
+ * adam, wire, signal_norm, signal_mask, wave_eval.                                                                  */
 int vr_debug_kernel(vr_handle h, const char* name, const int64_t* dims, int ndims, const float* fparams, int nfparams,
                     const float* const* inputs, int ninputs, float* const* outputs, int noutputs);
 /* Record intermediate activations of the next vr_forward and read them back (post-activation). */

@@ -237,6 +237,55 @@ int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, i
     });
 }
 
+// ---- evaluation against the true stems -------------------------------------------------------------------
+// What can be judged without the handle is: the tables, the counts, a stem table without its partner, a window or a length below one
+// sample.  window < hop and L < hop need the handle's hop: Model::separate_run refuses them before it touches the device.
+static bool evaluate_args_ok(int n_songs, const void* mix, const void* inst, const int64_t* L, int64_t window, const void* sums, const void* y,
+                             const void* v) {
+    if (n_songs <= 0) { g_err = "n_songs must be positive"; return false; }
+    if (!mix || !inst || !L || !sums) { g_err = "null table"; return false; }
+    if ((y == nullptr) != (v == nullptr)) { g_err = "one stem table is null and the other is not: give both, or neither for sums only"; return false; }
+    if (window < 1) { g_err = "window shorter than one hop"; return false; }
+    return true;
+}
+
+int vr_evaluate_wave_many(vr_handle h, int n_songs, const float* const* mix, const float* const* inst, int on_device, const int64_t* L, int tta,
+                          int batchsize, int cropsize, int64_t window, double* const* sums, float* const* y_waves, float* const* v_waves,
+                          int out_on_device) {
+    if (!evaluate_args_ok(n_songs, mix, inst, L, window, sums, y_waves, v_waves)) return VR_ERR_BAD_ARGUMENT;
+    for (int s = 0; s < n_songs; ++s)
+        if (L[s] < 1) { g_err = "song " + std::to_string(s) + ": wave shorter than one hop"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n_songs);
+        const vr::EvalArgs ev{inst, (long long)window, sums, y_waves != nullptr};
+        h->m.separate_run(n_songs, mix, on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, y_waves, v_waves, out_on_device != 0, nullptr,
+                          nullptr, /*solo=*/false, &ev);
+    });
+}
+
+int vr_evaluate_wave(vr_handle h, const float* mix, const float* inst, int on_device, int64_t L, int tta, int batchsize, int cropsize,
+                     int64_t window, double* sums, float* y_wave, float* v_wave, int out_on_device) {
+    if (!mix || !inst || !sums) { g_err = "null argument"; return VR_ERR_BAD_ARGUMENT; }
+    if (!evaluate_args_ok(1, &mix, &inst, &L, window, &sums, y_wave, v_wave)) return VR_ERR_BAD_ARGUMENT;
+    if (L < 1) { g_err = "wave shorter than one hop"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        const long long len = L;
+        const vr::EvalArgs ev{&inst, (long long)window, &sums, y_wave != nullptr};
+        h->m.separate_run(1, &mix, on_device != 0, nullptr, &len, tta, batchsize, cropsize, &y_wave, &v_wave, out_on_device != 0, nullptr, nullptr,
+                          /*solo=*/true, &ev);
+    });
+}
+
+int vr_evaluate_plan(int hop, int64_t L, int64_t window, int64_t* samples, int64_t* n_windows) {
+    return guard([&] {
+        const vr::EvalPlan p = vr::evaluate_plan(hop, L, window);
+        if (samples) *samples = p.samples;
+        if (n_windows) *n_windows = p.windows;
+    });
+}
+
 // ---- WAV sample bytes in, PCM16 out (csrc/pcm.h; the host converters are pcm_host.cpp) ------------------------------------------
 int vr_pcm_available(vr_handle h, int* available) {
     NEED(h);

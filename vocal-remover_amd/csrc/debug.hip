@@ -137,6 +137,14 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                                                        mask_b[2 bins][Wb]|null, wgt[T]|null                y_wave, v_wave [2][hop (T-1)] (fused masked
 //                                                        (cplx: complex64 masks)                             iSTFT; hop == n_fft / 2 handles only)
 //                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
+// wave_eval       T,Wa,Wb,shift,has_b,  -                spec, mask_a, mask_b|null, wgt|null as signal_mask,  y_wave, v_wave [2][hop (T-1)] (store 0: left as they were
+//                 has_wgt,cplx,window,                   mix[2][L], inst[2][L]                               allocated, zero), sums[windows][4] float64 (in a float32
+//                 store,L                                                                                    buffer of twice the count), info[2] = (S, windows)
+//                 One launch pair (which 0 and 1) of the evaluation form of istft_tile_kernel on a song table of one song, then
+//                 launch_eval_sums (kernels.h: WaveEval): the stems signal_mask's fused masked iSTFT gives, and per
+//                 window sum r_y^2, sum (r_y - y)^2, sum r_v^2, sum (r_v - v)^2 with r_y = inst, r_v = mix - inst.  window >= hop,
+//                 L >= hop (T-1), T >= 2; S = the tile step (segments per workgroup).  Stems, partials and sums sit between guard bands
+//                 (error -3).
 // wave_pair       S,T,x_pitch,y_pitch,  -                x[S][bins][x_pitch] complex64, mask (same shape)    y_wave, p_wave [S][hop (T-1)], sums[3] = <y, p>,
 //                 y_off,has_mask                         |null, y[S][bins][y_pitch] complex64                <y, y>, <p, p> over all signals
 //                 launch_wave_term on a WavePair (launch_istft_pair + the launch_reduce_rows of its partials): the waves of the target y (frame t at column y_off + t) and
@@ -1135,6 +1143,39 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_HIP(hipStreamSynchronize(st));
         fmin.download(out[0]); y.download(out[1]); v.download(out[2]);
         if (waves) { yw.download(out[3]); vw.download(out[4]); }
+    } else if (name == "wave_eval") {
+        need(10, 0, 6, 4);
+        const int T = (int)dims[0], Wa = (int)dims[1], Wb = (int)dims[2], shift = (int)dims[3];
+        const bool has_b = dims[4] != 0, has_wgt = dims[5] != 0, cplx = dims[6] != 0, store = dims[8] != 0;
+        const long long window = dims[7], L = dims[9];
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(many_tiled_available(plan, hop), -2, "wave_eval: the evaluation form needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(T >= 2 && Wa >= T && (!has_b || (shift >= 0 && Wb >= T + shift)), -2, "wave_eval: need T >= 2 and masks that cover T (+ shift) frames");
+        VR_CHECK(window >= hop && L >= (long long)hop * (T - 1), -2, "wave_eval: need window >= hop and L >= hop (T-1)");
+        VR_CHECK(in[0] && in[1] && (!has_b || in[2]) && (!has_wgt || in[3]) && in[4] && in[5], -2, "wave_eval: missing input");
+        const size_t rows = (size_t)2 * bins, mc = cplx ? 2 : 1, nspec = rows * T * 2, nwave = (size_t)2 * hop * (T - 1);
+        const long long samples = (long long)hop * (T - 1), windows = (samples + window - 1) / window;
+        DevBuf spec(in[0], nspec), ma(in[1], rows * Wa * mc), mb(has_b ? in[2] : nullptr, has_b ? rows * Wb * mc : 0);
+        DevBuf wgt(has_wgt ? in[3] : nullptr, has_wgt ? (size_t)T : 0), mix(in[4], (size_t)2 * L), inst(in[5], (size_t)2 * L);
+        GuardedBuf yw(nullptr, nwave), vw(nullptr, nwave), part(nullptr, 2 * eval_part_doubles(T)), sums(nullptr, (size_t)windows * 8);
+        DevBuf table((sizeof(SongSeg) + 3) / 4), entry((sizeof(WaveEval) + 3) / 4);
+        SongSeg sg{};
+        sg.wave = mix.p; sg.L = L; sg.spec = reinterpret_cast<float2*>(spec.p); sg.y_wave = yw.p(); sg.v_wave = vw.p(); sg.T = T;
+        WaveEval ev{};
+        ev.inst = inst.p; ev.part = reinterpret_cast<double*>(part.p()); ev.sums = reinterpret_cast<double*>(sums.p());
+        ev.window = window; ev.store = store ? 1 : 0;
+        VR_HIP(hipMemcpy(table.p, &sg, sizeof(SongSeg), hipMemcpyHostToDevice));
+        VR_HIP(hipMemcpy(entry.p, &ev, sizeof(WaveEval), hipMemcpyHostToDevice));
+        const SongSeg* tab = reinterpret_cast<const SongSeg*>(table.p);
+        const WaveEval* evd = reinterpret_cast<const WaveEval*>(entry.p);
+        for (int which = 0; which < 2; ++which)
+            launch_istft_eval_many(plan, tab, evd, 1, T, (double)T, ma.p, Wa, has_b ? mb.p : nullptr, Wb, shift, cplx, has_wgt ? wgt.p : nullptr, which,
+                                   store, st);
+        launch_eval_sums(plan, tab, evd, 1, windows, (double)T, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(yw.intact() && vw.intact() && part.intact() && sums.intact(), -3, "wave_eval: a store outside a stem, the partial sums or the sums");
+        yw.download(out[0]); vw.download(out[1]); sums.download(out[2]);
+        if (out[3]) { out[3][0] = (float)eval_tile_step(plan); out[3][1] = (float)windows; }
     } else if (name == "wave_pair") {
         need(6, 0, 3, 3);
         const int S = (int)dims[0], T = (int)dims[1], xp = (int)dims[2], yp = (int)dims[3], yo = (int)dims[4];

@@ -356,6 +356,28 @@ void launch_apply_mask_many(const SongSeg* songs, int n_songs, int max_T, int bi
 void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_songs, int max_T, double sum_T, const float* mask, int W, int tta,
                               bool cplx, const float* wgt, int which, hipStream_t st, bool pcm16 = false);   // pcm16: y_wave / v_wave are int16 [samples][2]
 
+// ---- evaluation against the true stems (vr_evaluate_wave*; hop == n_fft / 2) -------------------------------------
+// One entry per song beside the song table (device memory): the evaluation form of istft_tile_kernel takes the table entry's mixture
+// (`wave`, `L`) and this song's true instruments, and leaves per segment of hop samples the double sums of the reference squares and of the
+// error squares of the segment's lower and upper window (window >= hop: at most two).  `which` 0 measures the instruments against
+// inst, 1 the vocals against mix - inst.  The estimate is the float the plain form stores; `store` 0: it is not stored at all (y_wave /
+// v_wave of the table may then be null).
+struct WaveEval {
+    const float* inst;        // [2][L], L of the table entry
+    double* part;             // [stem 2][channel 2][segment T-1][wave 4][4] = (reference lower, error lower, reference upper, error upper)
+    double* sums;             // [n_windows][4] = sum r_y^2, sum (r_y - y)^2, sum r_v^2, sum (r_v - v)^2   (launch_eval_sums)
+    long long window;         // samples per window, >= hop
+    int store;
+};
+size_t eval_part_doubles(int T);                             // doubles of `part` for a song of T frames
+int eval_tile_step(const FFTPlan& pl);                       // segments per workgroup of the tile kernel (the hook reports it)
+// mask_a / mask_b / shift as istft_tile_kernel documents them for the song table (the executor: mask_b = mask_a or null, Wb = Wa, shift 0);
+// stored: whether any entry stores its stems (the profiler's note)
+void launch_istft_eval_many(const FFTPlan& pl, const SongSeg* songs, const WaveEval* evs, int n_songs, int max_T, double sum_T, const float* mask_a,
+                            int Wa, const float* mask_b, int Wb, int shift, bool cplx, const float* wgt, int which, bool stored, hipStream_t st);
+// sums[w][q] of every song = its partials of window w added over (segment, channel, wave) in a fixed order; max_windows: the largest count
+void launch_eval_sums(const FFTPlan& pl, const SongSeg* songs, const WaveEval* evs, int n_songs, long long max_windows, double sum_T, hipStream_t st);
+
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
 // step).  The kernels take a TABLE of them: one grid dimension is the table entry, sized for the largest entry, and a workgroup past

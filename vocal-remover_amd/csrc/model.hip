@@ -1728,9 +1728,12 @@ void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst
 // and back end are one launch each for all songs (song = a grid dimension, kernels.h SongSeg), so the launch count does not depend
 // on n_songs.  solo: the call of a one-song entry point (api.cpp) -- its errors name no song, and its device batch holds at most the
 // crops of its longer pass, which is what batchsize <= 0 means there.
+// eval (vr_evaluate_wave*): a wave-level float call that also scores each song against its true instruments --
+// the inst waves are staged like the mixtures, the back end is the evaluation form of the masked iSTFT plus one launch that adds its
+// partials per window, and the sums go back to the host.  Without eval->stems no stem is allocated, stored or copied (y, v unused).
 void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta, int batchsize,
                          int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels, const int* pcm_fmt,
-                         bool solo) {
+                         bool solo, const EvalArgs* eval) {
     // VR_ENQ_TIMING=1 (diagnostics, wave-level calls): host time to ENQUEUE the whole call vs the time until the device has drained it
     static const bool enq_timing = getenv("VR_ENQ_TIMING") != nullptr;
     const auto enq_t0 = std::chrono::steady_clock::now();
@@ -1741,19 +1744,26 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     const bool pcm = pcm_fmt != nullptr;
     // ---- arguments and the host-side plan: nothing here touches the device
     VR_CHECK(n_songs > 0, -2, "n_songs must be positive");
-    VR_CHECK(in && y && v && (waves || T_in), -2, "null table");
+    const bool stems = !eval || eval->stems;
+    VR_CHECK(in && (!stems || (y && v)) && (waves || T_in), -2, "null table");
+    if (eval) {
+        VR_CHECK(waves && !pcm && eval->inst && eval->sums, -2, "evaluation takes float waves and their true instruments");
+        VR_CHECK(many_tiled_available(plan, hop), -2,
+                 "evaluation needs hop_length == n_fft / 2 (the frame-tiled iSTFT kernel that forms the sums exists only there)");
+        VR_CHECK(eval->window >= hop, -2, "window shorter than one hop");
+    }
     VR_CHECK(!training, -2, "separate() runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
     check_T(cropsize, offset, 1);
     VR_CHECK(cropsize - 2 * offset > 0, -6, "cropsize must exceed 2*offset");
     const int bins = output_bin, E = is_complex ? 2 : 1;
-    struct Song { int T, pad_l, patches[2], crop0[2]; size_t spec_f, out_f; };
+    struct Song { int T, pad_l, patches[2], crop0[2]; size_t spec_f, out_f; long long windows; };
     std::vector<Song> sg((size_t)n_songs);
     int roi = 0, max_T = 0;
-    long long n_crops[2] = {0, 0}, sum_T = 0, sum_L = 0;
+    long long n_crops[2] = {0, 0}, sum_T = 0, sum_L = 0, max_windows = 0;
     auto song = [&](int s) { return solo ? std::string() : "song " + std::to_string(s) + ": "; };      // what an error starts with
     for (int s = 0; s < n_songs; ++s) {
         const std::string who = song(s);
-        VR_CHECK(in[s] && y[s] && v[s], -2, who + "null pointer");
+        VR_CHECK(in[s] && (!stems || (y[s] && v[s])) && (!eval || (eval->inst[s] && eval->sums[s])), -2, who + "null pointer");
         if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
         else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
         if (waves) VR_CHECK(L[s] / hop < (1LL << 30), -2, who + "wave too long");
@@ -1769,6 +1779,8 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         g.patches[1] = tta ? (g.T + g.pad_l + pad_r + roi - 2 * offset) / roi : 0;
         g.spec_f = (size_t)2 * bins * g.T * 2;
         g.out_f = (size_t)2 * hop * (g.T - 1);
+        g.windows = eval ? evaluate_plan(hop, L[s], eval->window).windows : 0;
+        max_windows = std::max(max_windows, g.windows);
         max_T = std::max(max_T, g.T);
         sum_T += g.T;
         if (waves) sum_L += L[s];
@@ -1789,6 +1801,9 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     SongSeg* tab_d = nullptr; int2* crops_d = nullptr;
     std::vector<PcmIn> pin(pcm ? (size_t)n_songs : 0);
     PcmIn* pin_d = nullptr;
+    std::vector<WaveEval> evt(eval ? (size_t)n_songs : 0);
+    std::vector<float*> stage_inst(eval ? (size_t)n_songs : 0);
+    WaveEval* evt_d = nullptr;
     double pcm_bytes = 0.0;
     auto in_bytes = [&](int s) {
         return pcm ? (size_t)L[s] * pcm_channels[s] * pcm_sample_bytes(pcm_fmt[s]) : (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float);
@@ -1800,6 +1815,7 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         tab_d = static_cast<SongSeg*>(A.alloc(sizeof(SongSeg) * n_songs));
         crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * crops_n));
         if (pcm) pin_d = static_cast<PcmIn*>(A.alloc(sizeof(PcmIn) * n_songs));
+        if (eval) evt_d = static_cast<WaveEval*>(A.alloc(sizeof(WaveEval) * n_songs));
         part = static_cast<unsigned long long*>(A.alloc((size_t)n_songs * 2 * bins * 16));
         aff = A.allocf((size_t)n_songs * 4);
         mask = A.allocf((size_t)E * 2 * bins * W);
@@ -1822,9 +1838,20 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
                     pin[s] = PcmIn{reinterpret_cast<const uint8_t*>(src), pcm_channels[s], pcm_fmt[s]};
                 }
                 t.spec = reinterpret_cast<float2*>(A.allocf(g.spec_f));
-                stage_y[s] = out_on_dev ? y[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
-                stage_v[s] = out_on_dev ? v[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
+                if (stems) {
+                    stage_y[s] = out_on_dev ? y[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
+                    stage_v[s] = out_on_dev ? v[s] : A.allocf((pcm ? g.out_f / 2 : g.out_f) + 4);
+                }
                 t.y_wave = stage_y[s]; t.v_wave = stage_v[s];
+                if (eval) {                           // the true instruments beside the mixture; the partials and the sums of this song
+                    stage_inst[s] = in_on_dev ? nullptr : A.allocf((size_t)2 * L[s]);
+                    WaveEval& e = evt[s];
+                    e.inst = in_on_dev ? eval->inst[s] : stage_inst[s];
+                    e.part = static_cast<double*>(A.alloc(eval_part_doubles(g.T) * sizeof(double)));
+                    e.sums = static_cast<double*>(A.alloc((size_t)g.windows * 4 * sizeof(double)));
+                    e.window = eval->window;
+                    e.store = stems ? 1 : 0;
+                }
                 if (!tiled) {                         // general hop: masked spectrograms, then the per-frame inverse per song
                     t.y = reinterpret_cast<float2*>(A.allocf(g.spec_f));
                     t.v = reinterpret_cast<float2*>(A.allocf(g.spec_f));
@@ -1862,6 +1889,12 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     if (!in_on_dev)
         for (int s = 0; s < n_songs; ++s)
             VR_HIP(hipMemcpyAsync(stage_in[s], in[s], in_bytes(s), hipMemcpyHostToDevice, stream));
+    if (eval) {
+        VR_HIP(hipMemcpyAsync(evt_d, evt.data(), sizeof(WaveEval) * n_songs, hipMemcpyHostToDevice, stream));
+        if (!in_on_dev)
+            for (int s = 0; s < n_songs; ++s)
+                VR_HIP(hipMemcpyAsync(stage_inst[s], eval->inst[s], in_bytes(s), hipMemcpyHostToDevice, stream));
+    }
     // ---- front end
     if (waves) {
         if (pcm) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream, pin_d, pcm_bytes);   // (check_pcm: tiled)
@@ -1903,7 +1936,15 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         VR_HIP(hipMemcpyAsync(wgt_d, wgt_h.data(), (size_t)sum_T * sizeof(float), hipMemcpyHostToDevice, stream));
         wgt = wgt_d;
     }
-    if (waves && tiled) {
+    if (eval) {                             // (tiled, checked above)
+        for (int which = 0; which < 2; ++which)
+            launch_istft_eval_many(plan, tab_d, evt_d, n_songs, max_T, (double)sum_T, mask, W, tta ? mask : nullptr, W, 0, is_complex, wgt, which,
+                                   stems, stream);
+        launch_eval_sums(plan, tab_d, evt_d, n_songs, max_windows, (double)sum_T, stream);
+        for (int s = 0; s < n_songs; ++s)
+            if (sg[s].windows)
+                VR_HIP(hipMemcpyAsync(eval->sums[s], evt[s].sums, (size_t)sg[s].windows * 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    } else if (waves && tiled) {
         for (int which = 0; which < 2; ++which)
             launch_istft_masked_many(plan, tab_d, n_songs, max_T, (double)sum_T, mask, W, tta, is_complex, wgt, which, stream, pcm);
     } else {
@@ -1914,7 +1955,7 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
                 launch_istft(plan, tab[s].v, hop, sg[s].T, frames, tab[s].v_wave, stream);
             }
     }
-    if (!out_on_dev)
+    if (!out_on_dev && stems)
         for (int s = 0; s < n_songs; ++s) {
             const size_t nf = waves ? sg[s].out_f : sg[s].spec_f;
             if (!nf) continue;
@@ -1926,6 +1967,16 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     if (enq_timing && waves)
         fprintf(stderr, "[vr-enq] enqueue %.3f ms, total %.3f ms\n", std::chrono::duration<double, std::milli>(enq_t1 - enq_t0).count(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - enq_t0).count());
+}
+
+EvalPlan evaluate_plan(int hop, long long L, long long window) {
+    VR_CHECK(hop > 0, -2, "hop must be positive");
+    VR_CHECK(L >= hop, -2, "wave shorter than one hop");
+    VR_CHECK(window >= hop, -2, "window shorter than one hop");
+    EvalPlan p{};
+    p.samples = (long long)hop * (L / hop);
+    p.windows = p.samples / window + (p.samples % window ? 1 : 0);
+    return p;
 }
 
 // =====================================================================================================

@@ -329,18 +329,64 @@ __device__ __forceinline__ float2 final_mask(const float2* __restrict__ ma, int 
     return m;
 }
 
+// (evaluation form) what the workgroup keeps of its song, and a thread's share of a segment's sums; empty in every other form, so
+// that those keep their code as it was
+struct EvalSong { WaveEval e; const float* mix; long long L; };         // the song's entry, its mixture [2][L]
+struct EvalSeg { double q[4]; long long bound; };                       // reference and error squares of the lower, then of the upper window
+struct EvalNone {};
+template <bool EVAL> using EvalLocal = typename std::conditional<EVAL, EvalSong, EvalNone>::type;
+template <bool EVAL> using EvalSums = typename std::conditional<EVAL, EvalSeg, EvalNone>::type;
+struct WindowSums {};                                                   // behind const WaveEval* in the pack: the evaluation's second launch
+template <class X, class... T> constexpr bool kHasType = (std::is_same<X, T>::value || ...);
+
+// The second launch of an evaluation, blockIdx = (window, song), 256 threads: one wave (64 lanes) per quantity q = 2 * stem + (0: reference
+// square, 1: error square).  The window's items are (segment, channel, wave of the segment's group), in that order; lane l adds items l,
+// l + 64, ... and the xor butterfly adds the lanes: a fixed order, so two calls give the same bits.  The window's first segment may begin in
+// the window before: its upper slots are taken.
+__device__ __forceinline__ void eval_window_sums(int M, const SongSeg& sg, const WaveEval& ev) {
+    const long long samples = (long long)M * (sg.T - 1), lo = (long long)blockIdx.x * ev.window;
+    if (lo >= samples) return;
+    const long long hi = lo + ev.window < samples ? lo + ev.window : samples;
+    const long long s0 = lo / M, s1 = (hi - 1) / M, items = (s1 - s0 + 1) * 8;
+    const int q = threadIdx.x >> 6, lane = threadIdx.x & 63, stem = q >> 1, k = q & 1;
+    double acc = 0.0;
+    for (long long it = lane; it < items; it += 64) {
+        const long long s = s0 + (it >> 3);
+        const int ch = (int)(it >> 2) & 1, wv = (int)it & 3;
+        const int slot = s * M >= lo ? 0 : 2;
+        acc += ev.part[((((long long)stem * 2 + ch) * (sg.T - 1) + s) * 4 + wv) * 4 + slot + k];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) ev.sums[(long long)blockIdx.x * 4 + q] = acc;
+}
+
 // which: 0 = plain spectrogram (mask_a null) / instruments y = m X, 1 = vocals v = (1 - m) X
 // CPLX: the mask is complex64 (is_complex handles), y = m X and v = (1 - m) X as complex products
 // OUT (at most one type): where the samples go -- none = WaveF32Out (planar float32, as documented); WavePcm16Out: `wave` / the table's
 // y_wave, v_wave then point to interleaved int16 [samples][2] (streams: [capacity][2], segment s at sample (s - t_out) * M); the carry
-// and `prev` stay float.
+// and `prev` stay float.  const WaveEval* (SRC = const SongSeg only): the evaluation form -- one WaveEval per song beside
+// the song table, behind the kernel's `wave` pointer (which the table forms do not read).  Where the plain form stores sample p of channel
+// ch, this form takes the same float, the true stem's sample from the song's `inst` wave (which 1: the table's mixture minus it, formed in
+// double) and adds the reference square and the error square, in double, to the segment's lower or upper window (window >= hop: a segment
+// of hop samples meets at most two).  A segment belongs to one group of 256 threads, so its sums are reduced by wave shuffles alone and
+// lane 0 of each of the group's four waves writes that wave's four partials.  With WindowSums behind it in the pack the kernel is the
+// evaluation's second launch instead (eval_window_sums above: grid (window, song), 256 threads, no LDS), which adds them per window in a
+// fixed order -- under this kernel's name, like every form of this file, so that the launch profiler's report keeps one name per stage.
 template <bool CPLX, class SRC = const float2, class... OUT>
 __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __restrict__ src, int T, int S,
                                                           const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb,
                                                           int shift, const float* __restrict__ wgt, int which,
                                                           float* __restrict__ wave, long long out_len) {
-    static_assert(sizeof...(OUT) <= 1, "one destination type at most");
-    using DST = typename FirstOr<WaveF32Out, OUT...>::type;
+    constexpr bool kSums = kHasType<WindowSums, OUT...>;
+    static_assert(sizeof...(OUT) <= (kSums ? 2 : 1), "one destination type at most");
+    constexpr bool kEval = std::is_same<typename FirstOr<void, OUT...>::type, const WaveEval*>::value;
+    static_assert((!kEval || kSongTable<SRC>) && (!kSums || kEval), "the evaluation forms are song-table forms");
+    if constexpr (kSums) {
+        eval_window_sums(pl.n_fft >> 1, src[blockIdx.y], reinterpret_cast<const WaveEval*>(wave)[blockIdx.y]);
+        return;
+    }
+    using DST = typename std::conditional<kEval, WaveF32Out, typename FirstOr<WaveF32Out, OUT...>::type>::type;
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, logM = pl.log2n - 1, F = S + 1;
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -353,6 +399,7 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
     StreamLocal<SRC> ss{};
     PairLocal<SRC> pr{};
     TripleLocal<SRC> tr{};
+    EvalLocal<kEval> ev{};
     bool carried = false;                           // (stream) frame t0 of this workgroup comes from the carry, not from the ring
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_out, t_done) of its stream, from its rings
         ss = src[blockIdx.z];
@@ -368,6 +415,7 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
         ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
         if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
         if (wgt) wgt += sg.frame0;
+        if constexpr (kEval) { ev.e = reinterpret_cast<const WaveEval*>(wave)[blockIdx.z]; ev.mix = sg.wave; ev.L = sg.L; }
         wave = which ? sg.v_wave : sg.y_wave;
         out_len = (long long)M * (sg.T - 1);
     } else if constexpr (kPair<SRC>) {
@@ -493,6 +541,16 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                 const int s = t0 + f - 1;
                 const float* cur = reinterpret_cast<const float*>(zs);
                 const float* before = g == 0 ? prev : reinterpret_cast<const float*>(zs - M) + M;
+                // (evaluation) `bound` = the first sample of the segment's upper window (the quotient in double: exact below 2^53, then
+                // corrected by one)
+                EvalSums<kEval> es{};
+                if constexpr (kEval) {
+                    const long long p0 = (long long)s * M;
+                    long long w = (long long)((double)p0 / (double)ev.e.window);
+                    if (w * ev.e.window > p0) --w;
+                    else if ((w + 1) * ev.e.window <= p0) ++w;
+                    es.bound = (w + 1) * ev.e.window;
+                }
                 for (int i = tid; i < M; i += 256) {
                     const float w0 = pl.window[i], w2 = pl.window[i + M];
                     const float ws = fmaf(w0, w0, w2 * w2);
@@ -531,9 +589,30 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                         // (the float store written out: through put() hipcc allocates this instantiation's registers differently)
                         if constexpr (DST::kInterleaved) DST::put(wave, 0, ch, (long long)(s - ss.t_out) * M, i, ws > FLT_MIN ? a / ws : a);
                         else wave[(long long)ch * ss.out_pitch + (long long)(s - ss.t_out) * M + i] = ws > FLT_MIN ? a / ws : a;
+                    } else if constexpr (kEval) {                     // (s <= T - 2: every sample lies inside [0, hop (T-1)), and hop (T-1) <= L)
+                        const long long p = (long long)s * M + i;
+                        const float v = ws > FLT_MIN ? a / ws : a;
+                        if (ev.e.store) wave[(long long)ch * out_len + p] = v;
+                        double r = (double)ev.e.inst[(long long)ch * ev.L + p];
+                        if (which) r = (double)ev.mix[(long long)ch * ev.L + p] - r;
+                        const double d = r - (double)v;
+                        if (p < es.bound) { es.q[0] = fma(r, r, es.q[0]); es.q[1] = fma(d, d, es.q[1]); }
+                        else { es.q[2] = fma(r, r, es.q[2]); es.q[3] = fma(d, d, es.q[3]); }
                     } else {
                         const long long p = (long long)s * M + i;
                         if (p < out_len) DST::put(wave, out_len, ch, p, 0, ws > FLT_MIN ? a / ws : a);
+                    }
+                }
+                if constexpr (kEval) {                               // the wave's four sums by the xor butterfly: the same order every time
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                        for (int off = 32; off >= 1; off >>= 1) es.q[j] += __shfl_xor(es.q[j], off, 64);
+                    }
+                    if ((tid & 63) == 0) {
+                        double* dst = ev.e.part + ((((long long)which * 2 + ch) * (T - 1) + s) * 4 + (tid >> 6)) * 4;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) dst[j] = es.q[j];
                     }
                 }
             }
@@ -1246,6 +1325,45 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg>), 160 * 1024);
         VR_LAUNCH((istft_tile_kernel<false, const SongSeg>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
     }
+    VR_HIP(hipGetLastError());
+}
+
+// ---- evaluation (vr_evaluate_wave*) ---------------------------------------------------------------------------
+size_t eval_part_doubles(int T) { return T < 2 ? 0 : (size_t)2 * 2 * (T - 1) * 4 * 4; }
+
+int eval_tile_step(const FFTPlan& pl) { return tile_frames(pl, pl.n_fft / 2) - 1; }
+
+void launch_istft_eval_many(const FFTPlan& pl, const SongSeg* songs, const WaveEval* evs, int n_songs, int max_T, double sum_T, const float* mask_a,
+                            int Wa, const float* mask_b, int Wb, int shift, bool cplx, const float* wgt, int which, bool stored, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    if (max_T < 2) return;
+    const int F = tile_frames(pl, M);
+    const int S = F - 1;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8 + (size_t)M * 4;
+    const dim3 grid((unsigned)((max_T - 1 + S - 1) / S), 2, n_songs);
+    // the plain form's traffic with the stem written only if stored; the true stem (which 1: and the mixture) read, the partials written
+    prof_note(0.0, 2.0 * ((double)bins * sum_T * (8.0 + (cplx ? 8.0 : 4.0) * (mask_b ? 2 : 1)) + ((stored ? 4.0 : 0.0) + (which ? 8.0 : 4.0)) * (double)M * sum_T
+                          + 128.0 * sum_T));
+    float* ev = reinterpret_cast<float*>(const_cast<WaveEval*>(evs));       // (the table forms do not read `wave`: the entries ride there)
+    if (cplx) {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<true, const SongSeg, const WaveEval*>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<true, const SongSeg, const WaveEval*>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask_a, Wa, mask_b, Wb, shift, wgt, which, ev, 0LL);
+    } else {
+        static std::atomic<unsigned long long> attr_done{0};
+        ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg, const WaveEval*>), 160 * 1024);
+        VR_LAUNCH((istft_tile_kernel<false, const SongSeg, const WaveEval*>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask_a, Wa, mask_b, Wb, shift, wgt, which, ev, 0LL);
+    }
+    VR_HIP(hipGetLastError());
+}
+
+void launch_eval_sums(const FFTPlan& pl, const SongSeg* songs, const WaveEval* evs, int n_songs, long long max_windows, double sum_T, hipStream_t st) {
+    if (max_windows <= 0) return;
+    VR_CHECK(max_windows < (1LL << 31), -2, "too many windows for one call");
+    prof_note(0.0, 512.0 * sum_T + 32.0 * (double)max_windows * n_songs);
+    float* ev = reinterpret_cast<float*>(const_cast<WaveEval*>(evs));
+    VR_LAUNCH((istft_tile_kernel<false, const SongSeg, const WaveEval*, WindowSums>), dim3((unsigned)max_windows, n_songs), dim3(256), 0, st, pl, songs, 0, 0,
+              (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, ev, 0LL);
     VR_HIP(hipGetLastError());
 }
 

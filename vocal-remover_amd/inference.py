@@ -4,7 +4,7 @@ numpy-in / numpy-out contract; the crop loop, stitching and mask application run
 _postprocess (inference.py:26-40): complex TTA average, merge_artifacts on |mask| with the phase kept, complex products."""
 import numpy as np
 
-from . import native
+from . import native, spec_utils
 
 
 class Separator(object):
@@ -132,6 +132,114 @@ class Separator(object):
         native.check(native.lib().vr_separate_wave_many(h.h, len(waves), addr(waves), 1 if on_dev else 0, L, self._flags(tta),
                                                         int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0))
         return list(zip(ys, vs))
+
+    def evaluate_wave_many(self, mixes, insts, tta=False, window=44100, stems=False):
+        """separate_wave_many that also scores every song against its true instruments, in ONE library call (vr_evaluate_wave_many).
+        mixes[s], insts[s]: [2, L_s] float32, numpy arrays or cuda tensors (all of one kind).  Per song a dict: 'sums' [n_windows, 4]
+        float64 (sum r_y^2, sum (r_y - y)^2, sum r_v^2, sum (r_v - v)^2 per window of `window` samples, r_v = mix - inst),
+        'instruments' / 'vocals' = spec_utils.sdr_from_sums of them, and with stems=True 'stems' = (y, v) as separate_wave_many gives
+        them.  Without stems the device stores and returns no sample.  Needs hop_length == n_fft / 2."""
+        h = self.model._need_handle()
+        hop = self.model.hop_length
+        mixes, insts = list(mixes), list(insts)
+        if not mixes or len(mixes) != len(insts):
+            raise ValueError('evaluate_wave_many needs at least one song and as many true stems as mixtures')
+        self.model.eval()
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        both = mixes + insts
+        on_dev = torch is not None and all(torch.is_tensor(w) and w.is_cuda for w in both)
+        if on_dev:
+            mixes = [w.detach().to(torch.float32).contiguous() for w in mixes]
+            insts = [w.detach().to(torch.float32).contiguous() for w in insts]
+        else:
+            if torch is not None and any(torch.is_tensor(w) and w.is_cuda for w in both):
+                raise ValueError('evaluate_wave_many: either every wave is a cuda tensor or none is')
+            mixes = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w in mixes]
+            insts = [np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w in insts]
+        for m, r in zip(mixes, insts):
+            if m.ndim != 2 or m.shape[0] != 2 or tuple(r.shape) != tuple(m.shape):
+                raise ValueError('every mixture must be [2, L] and its true stem of the same shape')
+        lens = [int(w.shape[1]) for w in mixes]
+        window = int(window)
+        if window < hop:
+            raise ValueError('window shorter than one hop')
+        for s, n in enumerate(lens):
+            if n < hop:
+                raise ValueError('song %d: wave shorter than one hop' % s)
+        L = (native.ctypes.c_int64 * len(mixes))(*lens)
+        sums = [np.zeros((native.evaluate_plan(hop, n, window)[1], 4), dtype=np.float64) for n in lens]
+        sums_tab = native.ptr_table([a.ctypes.data if a.size else np.zeros(4).ctypes.data for a in sums])
+        if on_dev:
+            torch.cuda.current_stream(mixes[0].device).synchronize()
+            addr = lambda seq: native.ptr_table([a.data_ptr() for a in seq])
+        else:
+            addr = lambda seq: native.ptr_table([a.ctypes.data for a in seq])
+        ys = vs = None
+        if stems:
+            if on_dev:
+                ys = [torch.empty((2, hop * (n // hop)), dtype=torch.float32, device=w.device) for w, n in zip(mixes, lens)]
+                vs = [torch.empty_like(a) for a in ys]
+            else:
+                ys = [np.empty((2, hop * (n // hop)), dtype=np.float32) for n in lens]
+                vs = [np.empty_like(a) for a in ys]
+        native.check(native.lib().vr_evaluate_wave_many(
+            h.h, len(mixes), addr(mixes), addr(insts), 1 if on_dev else 0, L, self._flags(tta), int(self.batchsize), int(self.cropsize),
+            window, sums_tab, addr(ys) if stems else None, addr(vs) if stems else None, 1 if on_dev else 0))
+        return [self._scored(a, (ys[s], vs[s]) if stems else None) for s, a in enumerate(sums)]
+
+    @staticmethod
+    def _scored(sums, stems):
+        out = {'sums': sums}
+        out.update(spec_utils.sdr_from_sums(sums))
+        if stems is not None:
+            out['stems'] = stems
+        return out
+
+    def evaluate_wave(self, mix, inst, tta=False, window=44100, stems=False):
+        """evaluate_wave_many for one song through the one-song entry point (vr_evaluate_wave), which batches as separate_wave does."""
+        h = self.model._need_handle()
+        hop = self.model.hop_length
+        self.model.eval()
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        on_dev = torch is not None and torch.is_tensor(mix) and mix.is_cuda and torch.is_tensor(inst) and inst.is_cuda
+        if on_dev:
+            mix, inst = (w.detach().to(torch.float32).contiguous() for w in (mix, inst))
+        else:
+            if torch is not None and any(torch.is_tensor(w) and w.is_cuda for w in (mix, inst)):
+                raise ValueError('evaluate_wave: either both waves are cuda tensors or neither is')
+            mix, inst = (np.ascontiguousarray(np.asarray(w, dtype=np.float32)) for w in (mix, inst))
+        if mix.ndim != 2 or mix.shape[0] != 2 or tuple(inst.shape) != tuple(mix.shape):
+            raise ValueError('the mixture must be [2, L] and the true stem of the same shape')
+        n, window = int(mix.shape[1]), int(window)
+        if window < hop:
+            raise ValueError('window shorter than one hop')
+        if n < hop:
+            raise ValueError('wave shorter than one hop')
+        sums = np.zeros((native.evaluate_plan(hop, n, window)[1], 4), dtype=np.float64)
+        spare = np.zeros(4)                     # (a song shorter than two hops has no sample and no window; the library still wants a pointer)
+        y = v = None
+        if on_dev:
+            torch.cuda.current_stream(mix.device).synchronize()
+            ptr = lambda a: a.data_ptr()
+            if stems:
+                y = torch.empty((2, hop * (n // hop)), dtype=torch.float32, device=mix.device)
+                v = torch.empty_like(y)
+        else:
+            ptr = lambda a: a.ctypes.data
+            if stems:
+                y = np.empty((2, hop * (n // hop)), dtype=np.float32)
+                v = np.empty_like(y)
+        native.check(native.lib().vr_evaluate_wave(
+            h.h, ptr(mix), ptr(inst), 1 if on_dev else 0, n, self._flags(tta), int(self.batchsize), int(self.cropsize), window,
+            sums.ctypes.data if sums.size else spare.ctypes.data, (ptr(y) or None) if stems else None, (ptr(v) or None) if stems else None,
+            1 if on_dev else 0))
+        return self._scored(sums, (y, v) if stems else None)
 
     def separate_pcm(self, raw, tta=False):
         """separate_wave with the file's bytes at both ends: raw = audio.RawPcm (audio.read_wav_raw: PCM16 / 24 / 32 or float32 frames of
@@ -518,16 +626,9 @@ def expand_inputs(path, songs_per_call):
     return [files[i:i + songs_per_call] for i in range(0, len(files), songs_per_call)]
 
 
-def main(argv=None):
-    """inference.py main() (inference.py:107-185) with the same flags; decoding / resampling / WAV writing come from
-    vocal_remover_amd.audio (no librosa / soundfile), everything numeric from the library.  --output_image is the only
-    flag not carried over (cv2 image dump, SURVEY section 2: out of scope)."""
+def build_parser():
+    """The command line of main()."""
     import argparse
-    import os
-
-    import torch
-
-    from . import audio, nets
     p = argparse.ArgumentParser()
     p.add_argument('--gpu', '-g', type=int, default=0)
     p.add_argument('--pretrained_model', '-P', type=str, required=True)
@@ -545,7 +646,23 @@ def main(argv=None):
     p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call (--stream: files streamed together)
     p.add_argument('--stream', action='store_true')                  # read, separate and write block by block (Separator.stream)
     p.add_argument('--block_seconds', type=float, default=1.0)
-    args = p.parse_args(argv)
+    p.add_argument('--reference', type=str, default=None)            # the true instruments of --input (one file): also print the stems' SDR as one JSON line
+    p.add_argument('--eval_window_seconds', type=float, default=1.0)  # the window of the median SDR
+    return p
+
+
+def main(argv=None):
+    """inference.py main() (inference.py:107-185) with the same flags; decoding / resampling / WAV writing come from
+    vocal_remover_amd.audio (no librosa / soundfile), everything numeric from the library.  --output_image is the only
+    flag not carried over (cv2 image dump, SURVEY section 2: out of scope)."""
+    import os
+
+    import torch
+
+    from . import audio, nets
+    args = build_parser().parse_args(argv)
+    if args.reference is not None and (args.stream or os.path.isdir(args.input)):
+        raise SystemExit('--reference scores one file separated offline: not with --stream, not with a directory')
 
     if args.output_image:
         print('--output_image: not written by this entry point (spectrogram_to_image + cv2 are outside the MI355X path); run the '
@@ -595,6 +712,18 @@ def main(argv=None):
         basename = os.path.splitext(os.path.basename(args.input))[0]
         stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
                     args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled)
+        return 0
+    if args.reference is not None:
+        import json
+        X, sr = load(args.input)
+        ref, _ = load(args.reference)
+        if ref.shape[1] < X.shape[1]:
+            raise SystemExit('--reference is shorter than --input')
+        window = max(int(round(args.eval_window_seconds * sr)), args.hop_length)
+        res = sp.evaluate_wave(X, ref[:, :X.shape[1]], tta=args.tta, window=window, stems=True)
+        write(args.input, res['stems'][0], res['stems'][1], sr)
+        print(json.dumps({'window': window, 'instruments': {'sdr': res['instruments']['sdr'], 'sdr_median': res['instruments']['sdr_median']},
+                          'vocals': {'sdr': res['vocals']['sdr'], 'sdr_median': res['vocals']['sdr_median']}}))
         return 0
     if not os.path.isdir(args.input):
         raw = load_raw(args.input)

@@ -44,6 +44,13 @@ _SIGNATURES = {
     'vr_separate_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_evaluate_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.c_int, c_i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_evaluate_wave': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int]),
+    'vr_evaluate_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_i64p, c_i64p]),
     'vr_pcm_available': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     'vr_stft_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int]),
     'vr_istft_pcm16': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
@@ -216,6 +223,13 @@ def stream_plan(n_fft, hop, cropsize, offset, tta, samples_in, flushed):
     check(lib().vr_stream_plan(int(n_fft), int(hop), int(cropsize), int(offset), 1 if tta else 0, int(samples_in), 1 if flushed else 0,
                                ctypes.byref(fr), crops, ctypes.byref(out)))
     return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
+
+
+def evaluate_plan(hop, L, window):
+    """vr_evaluate_plan (host only): -> (samples, n_windows) of a song of L samples scored in windows of `window` samples."""
+    samples, windows = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().vr_evaluate_plan(int(hop), int(L), int(window), ctypes.byref(samples), ctypes.byref(windows)))
+    return int(samples.value), int(windows.value)
 
 
 def resampler_plan(sr_in, sr_out, samples_in, flushed):

@@ -118,6 +118,32 @@ def spectrogram_to_pcm16(spec, hop_length=1024):
     return out
 
 
+def _sdr_db(num, den):
+    """10 log10(num / den) with no epsilon: num == 0 -> nan (nothing to measure), den == 0 with num > 0 -> +inf."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    out = np.full(num.shape, np.nan)
+    exact = (num > 0) & (den == 0)
+    ok = (num > 0) & (den > 0)
+    out[exact] = np.inf
+    out[ok] = 10.0 * np.log10(num[ok] / den[ok])
+    return out
+
+
+def sdr_from_sums(sums):
+    """The signal-to-distortion ratios of one song from what Separator.evaluate_wave returns: sums [n_windows, 4] float64 =
+    (sum r_y^2, sum (r_y - y)^2, sum r_v^2, sum (r_v - v)^2) per window (tests/evaluate_ref.py states the definition).
+    -> {'instruments': {'sdr': whole song, from the column sums; 'sdr_windows': [n_windows]; 'sdr_median': nanmedian of those},
+    'vocals': {...}}, in dB.  A window whose true stem is silent is nan and left out of the median; a song of silent windows only
+    (or of no window) has a nan median."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 4)
+    out = {}
+    for name, c in (('instruments', 0), ('vocals', 2)):
+        windows = _sdr_db(sums[:, c], sums[:, c + 1])
+        median = float(np.median(windows[~np.isnan(windows)])) if np.any(~np.isnan(windows)) else float('nan')
+        out[name] = {'sdr': float(_sdr_db(sums[:, c].sum(), sums[:, c + 1].sum())), 'sdr_windows': windows, 'sdr_median': median}
+    return out
+
+
 def _head_lag(a, b, sr, seconds=4):
     """Lag (samples, positive = `a` starts late) at which the first `seconds` of the two stereo waves, summed to mono with the
     mean removed, correlate best -- argmax of the full cross-correlation, evaluated on the GPU (vr_xcorr_argmax)."""

@@ -206,6 +206,37 @@ def validate_epoch(dataloader, model, device):
     return sum_loss / len(dataloader.dataset)
 
 
+def evaluate_songs(sp, pairs, songs_per_call=8, tta=False, window=44100, sr=44100):
+    """What validate_epoch does not say: how good the separation of whole songs is.  sp: an inference.Separator; pairs: (mixture
+    path, instruments path) per song, loaded and aligned the way the spectrogram cache does (audio.load, then
+    spec_utils.align_wave_head_and_tail).  The songs go through Separator.evaluate_wave_many in groups of songs_per_call, sums only:
+    the cost is the separation itself.  -> (per-song results as evaluate_wave_many gives them, {'instruments': mean over the songs of
+    the median window SDR, 'vocals': the same}); a song whose median is nan (silent throughout) is left out of the mean."""
+    import numpy as np
+
+    from . import audio, spec_utils
+    if songs_per_call < 1:
+        raise ValueError('songs_per_call must be at least 1')
+    pairs = list(pairs)
+    results = []
+    for i in range(0, len(pairs), songs_per_call):
+        mixes, insts = [], []
+        for mix_path, inst_path in pairs[i:i + songs_per_call]:
+            waves = []
+            for path in (mix_path, inst_path):
+                w = audio.load(path, sr=sr, mono=False, dtype=np.float32, res_type='kaiser_fast')[0]
+                waves.append(np.asarray([w, w]) if w.ndim == 1 else w)
+            m, r = spec_utils.align_wave_head_and_tail(waves[0], waves[1], sr)
+            mixes.append(np.ascontiguousarray(m))
+            insts.append(np.ascontiguousarray(r))
+        results.extend(sp.evaluate_wave_many(mixes, insts, tta=tta, window=window, stems=False))
+    mean = {}
+    for stem in ('instruments', 'vocals'):
+        medians = [r[stem]['sdr_median'] for r in results if not np.isnan(r[stem]['sdr_median'])]
+        mean[stem] = float(np.mean(medians)) if medians else float('nan')
+    return results, mean
+
+
 # ---- the epoch loop of train.py main() (train.py:272-294) + what the reference lacks: a resumable checkpoint ----------
 def save_checkpoint(path, model, optimizer, scheduler=None, epoch=0, best_loss=None, log=None):
     """Model state_dict (the reference's 689 keys) + Adam moments / step + scheduler state + loop position."""
