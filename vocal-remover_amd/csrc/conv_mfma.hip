@@ -405,6 +405,13 @@ double launch_conv(const ConvArgs& a_in, const ConvShape& s, hipStream_t st) {
         VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && a.w_lo >= 0 && a.w_lo < a.w_hi && !a.part && x3_pick(a, s, &x3t), -2,
                  "conv column window: only conv_x3h (mfma_mode 3, eval) takes one");
     }
+    if (a.tail) {
+        // a second stage in the epilogue is conv_x3h.hip's alone (x3h_tail_ok): the launch must take it, nothing drops the stage
+        X3Tile x3t;
+        int th;
+        VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && !thin16_pick(a, s, &th) && x3_pick(a, s, &x3t), -2,
+                 "conv with a second stage in its epilogue: only conv_x3h (mfma_mode 3, eval) takes one");
+    }
     for (int i = 0; i < a.nsrc && i < 3; ++i) {
         // the loaders interpolate an upsampled source from ONE affine (aff0): no kernel splits its rows between two BatchNorms, and the
         // network never asks for it (the band-stacked aux tensors are consumed at their own resolution) -- refuse it, do not compute it wrong

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "conv_epilogue.h"
+#include "conv_x3h_tail.h"
 #include "conv_stage.h"
 #include "kernels.h"
 #include "lds_dma.h"
@@ -36,7 +37,8 @@ namespace vr {
 
 // UP: the launch has upsampled sources (only then the low-resolution staging tile takes LDS: without it three 64 x 8 workgroups fit a CU
 // with room to spare -- 146 KB -- where 3 x 53.3 KB = 159.8 KB sat on the edge of the 160 KB, allocation granularity unknown)
-template <int MT, int TH, bool UP = true>
+// TAIL: the launch runs a second 1x1 stage in its epilogue (ConvArgs::tail) and parks that stage's constants behind the wave maxima
+template <int MT, int TH, bool UP = true, int TAIL = 0>
 struct X3hCfg {
     static constexpr int TW = 32, CK = 8, KK = 9;
     static constexpr int TH_in = TH + 2, PW = TW + 2;           // halo tile, pixels
@@ -57,7 +59,10 @@ struct X3hCfg {
     static constexpr int L_BYTES = UP ? CK * LSLOT * 4 : 0;
     static constexpr int E_OFF = L_OFF + L_BYTES;               // epilogue constants of the cout tile: bias, scale, shift, 1 / weight scale [4][MT] fp32
     static constexpr int M_OFF = E_OFF + 4 * MT * 4;            // the four wave maxima of the chunk being split (uint bits of |x|)
-    static constexpr int LDS_BYTES = M_OFF + 16;
+    // second stage (TAIL 1: w2 [32 couts of this stage][16] + its affine [16][2]; TAIL 2: w2 [MT] + its affine [2]), fp32
+    static constexpr int T_OFF = M_OFF + 16;
+    static constexpr int T_BYTES = TAIL == 1 ? (32 * 16 + 32) * 4 : (TAIL == 2 ? (MT + 4) * 4 : 0);
+    static constexpr int LDS_BYTES = T_OFF + T_BYTES;
     // workgroups per CU the register budget must allow (64 x 8 would fit three by LDS, 53 KB, but needs 175 registers: 36 bytes of
     // scratch under a 168-register cap, and a spilled in-flight pixel register would be silently wrong)
     static constexpr int OCC = (MT == 32 && TH == 8) ? 3 : 2;
@@ -83,9 +88,11 @@ void x3h_trace_clear() {
 // UP: some source arrives through the fused bilinear x2 (eval); the plain instantiation sheds that path's registers and code
 // TRACE: the diagnostic build of the same kernel (phase stamps; never launched unless VR_CONV_DBG has bit 64)
 // HI: one more workgroup per CU than the register budget of the UP form allows (plain form only: 153 / 113 registers)
-template <int MT, int TH, bool UP, bool HI, bool TRACE = false>
+// TAIL: 0, or ConvArgs::tail of the launch: a second 1x1 stage on the accumulators (conv_x3h_tail.h; one cout tile, eval).  TAIL 0 is the
+// kernel as it always was: everything of the second stage sits behind `if constexpr`.
+template <int MT, int TH, bool UP, bool HI, bool TRACE = false, int TAIL = 0>
 __global__ __launch_bounds__(256, (X3hCfg<MT, TH>::OCC + (HI ? 1 : 0))) void conv_x3h_kernel(const ConvArgs a) {
-    using Cfg = X3hCfg<MT, TH, UP>;
+    using Cfg = X3hCfg<MT, TH, UP, TAIL>;
     constexpr int TW = Cfg::TW, KK = Cfg::KK, PW = Cfg::PW, NSLOT = Cfg::NSLOT, NPASS = Cfg::NPASS, WM = Cfg::WM, WN = Cfg::WN,
                   PLANE = Cfg::PLANE, NWP = Cfg::NWP, NWPASS = Cfg::NWPASS;
     extern __shared__ __attribute__((aligned(16))) char smem_x3h[];
@@ -364,6 +371,25 @@ __global__ __launch_bounds__(256, (X3hCfg<MT, TH>::OCC + (HI ? 1 : 0))) void con
         ecv[2] = x3h_load(re, ecc * 8 + 4);
         ecv[3] = x3h_load(rw, ec * 4);                                             // (padded couts included: [CoutPad])
     }
+    // second stage: its weights and folded affine take the same road (anything out of range reads 0 through the descriptor)
+    float tcv[3] = {0.f, 0.f, 0.f};
+    if constexpr (TAIL != 0) {
+        i32x4 r2 = make_rsrc(a.t_w, 0x7FFFFFF0u), r3 = make_rsrc(a.t_epi, 0x7FFFFFF0u);
+        settle_rsrc(r2);
+        settle_rsrc(r3);
+        constexpr int OOB = (int)0x80000000u;
+        if constexpr (TAIL == 1) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {                                          // T[c][j], c < 32, j < 16
+                const int c = (tid + 256 * q) >> 4, j = tid & 15;
+                tcv[q] = x3h_load(r2, (c < a.Cout && j < a.t_Cout) ? (c * a.t_CoutPad + j) * 4 : OOB);
+            }
+            tcv[2] = x3h_load(r3, tid < 2 * a.t_Cout ? tid * 4 : OOB);
+        } else {
+            tcv[0] = x3h_load(r2, tid < a.Cout ? tid * 4 : OOB);
+            tcv[1] = x3h_load(r3, tid < 2 ? tid * 4 : OOB);
+        }
+    }
     // the shift follows the chunk maxima (header): `e` = biased exponent of the largest |x| of the chunk about to be split
     auto follow = [&](int e, bool first) {
         const int need = 140 - (e < 14 ? 14 : e);                                  // chunk maximum -> [2^13, 2^14)
@@ -406,6 +432,18 @@ __global__ __launch_bounds__(256, (X3hCfg<MT, TH>::OCC + (HI ? 1 : 0))) void con
         E[MT + tid] = a.epi ? ecv[1] : 1.f;
         E[2 * MT + tid] = a.epi ? ecv[2] : 0.f;
         E[3 * MT + tid] = ecv[3];
+    }
+    if constexpr (TAIL != 0) {
+        asm volatile("; landed %0 %1 %2" : "+v"(tcv[0]), "+v"(tcv[1]), "+v"(tcv[2]));
+        float* T = reinterpret_cast<float*>(smem_x3h + Cfg::T_OFF);
+        if constexpr (TAIL == 1) {
+            T[tid] = tcv[0];
+            T[256 + tid] = tcv[1];
+            if (tid < 32) T[512 + tid] = tcv[2];
+        } else {
+            if (tid < MT) T[tid] = tcv[0];
+            if (tid < 2) T[MT + tid] = tcv[1];
+        }
     }
     post_max(P0{});
     if (any_up) stage_lowres(P0{});
@@ -522,12 +560,18 @@ __global__ __launch_bounds__(256, (X3hCfg<MT, TH>::OCC + (HI ? 1 : 0))) void con
                     for (int j = 0; j < 4; ++j) acc[mi][ni][rq * 4 + j] = (acc[mi][ni][rq * 4 + j] * fo) * wi[j];
             }
     }
-    {
+    if constexpr (TAIL != 1) {
         int hon[WN], won[WN];
 #pragma unroll
         for (int ni = 0; ni < WN; ++ni) { hon[ni] = h0 + wave * WN + ni; won[ni] = w0 + l31; }
         epi_store<MT, WM, WN>(VR_EPI_ARGS(a), acc, reinterpret_cast<const float*>(smem_x3h + Cfg::E_OFF), n, co0, khalf,
                               h0 + TH <= a.Hout && w0 + TW <= a.Wout, hon, won);
+    }
+    if constexpr (TAIL != 0) {
+        x3h_second_stage<MT, WM, WN, TAIL>(acc, reinterpret_cast<const float*>(smem_x3h + Cfg::E_OFF), reinterpret_cast<const float*>(smem_x3h + Cfg::T_OFF),
+                                   a.epi ? a.epi_slope : 1.f, a.t_slope, a.t_Cout, a.t_p, a.t_sN, a.t_sC, a.t_sH, n, h0 + wave * WN, w0 + l31,
+                                   a.Hout, a.Wout, khalf, lane);
+        return;
     }
     // ---------------- BatchNorm partial statistics (training) -------------------------------------------------
     if (a.part) {
@@ -665,8 +709,41 @@ static void x3h_launch(const ConvArgs& a, hipStream_t st) {
     else x3h_launch_up<MT, TH, false, false>(a, st);
 }
 
+// HI: the plain TH = 8 forms are built for one more workgroup per CU, which their registers already allow (115 / 155: the same code and
+// occupancy as without), so that the two symbols tests/test_asm_audit.py addresses by prefix stay the only ones with that prefix
+template <int MT, int TH, bool UP, int TAIL>
+static void x3h_launch_tail(const ConvArgs& a, hipStream_t st) {
+    using Cfg = X3hCfg<MT, TH, UP, TAIL>;
+    auto kern = conv_x3h_kernel<MT, TH, UP, (TH == 8 && !UP), false, TAIL>;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES);
+    VR_LAUNCH(kern, dim3((a.npt + 7) / 8 * 8), dim3(256), Cfg::LDS_BYTES, st, a);
+    VR_HIP(hipGetLastError());
+}
+
+// A launch with a second stage (ConvArgs::tail) exists for the tilings the network's sites run at, and only with every channel of a
+// pixel in one workgroup: tail 1 (stage tail) <32, 16> with upsampled sources; tail 2 (LSTM squeeze) <32, 8> plain, <64, 8> plain and
+// upsampled.  `a` is tiled (x3_fill_tiling).  The executor asks first; what it is refused runs as two launches.
+bool x3h_tail_ok(const ConvArgs& a, const X3Tile& t) {
+    if (a.tail != 1 && a.tail != 2) return false;
+    if (a.bf16 != 3 || a.nct != 1 || a.Cout > t.MT || a.part || a.w_hi != 0 || !a.t_w || !a.t_epi || !a.t_p) return false;
+    const bool up = (a.src[0].up | (a.nsrc > 1 ? a.src[1].up : 0) | (a.nsrc > 2 ? a.src[2].up : 0)) != 0;
+    if (a.tail == 1) return t.MT == 32 && t.TH == 16 && up && a.t_Cout >= 1 && a.t_Cout <= 16 && a.t_CoutPad >= a.t_Cout;
+    if (a.d1 < a.Cout || !a.dst[0].p || a.dst[0].accumulate || a.dst[0].wshift) return false;             // (the squeeze stores the first stage as one plain destination)
+    return t.TH == 8 && (t.MT == 64 || (t.MT == 32 && !up));
+}
+
 // same tile choice as conv_x3.hip (x3_pick / x3_fill_tiling); taken when ConvArgs::bf16 == 3
 void x3h_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st) {
+    if (a.tail) {
+        VR_CHECK(x3h_tail_ok(a, t), -2, "conv_x3h: no kernel for this launch with a second stage (x3h_tail_ok)");
+        const bool up = (a.src[0].up | a.src[1].up | a.src[2].up) != 0;
+        if (a.tail == 1) x3h_launch_tail<32, 16, true, 1>(a, st);
+        else if (t.MT == 32) x3h_launch_tail<32, 8, false, 2>(a, st);
+        else if (up) x3h_launch_tail<64, 8, true, 2>(a, st);
+        else x3h_launch_tail<64, 8, false, 2>(a, st);
+        return;
+    }
     if (t.MT == 64) x3h_launch<64, 8>(a, st);
     else if (t.TH == 16) x3h_launch<32, 16>(a, st);
     else x3h_launch<32, 8>(a, st);

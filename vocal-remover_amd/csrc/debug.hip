@@ -543,6 +543,117 @@ void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, i
     }
 }
 
+// conv_tail       nsrc,N,Cout,kind,     slope of the     w1[Cout][Cin][3][3] (OIHW), epi1[Cout][2],          y's backing buffer, whole, as the device left it;
+//                 Cout2,MT,TH,          3x3 stage, of    w2[Cout2][Cout], epi2[Cout2][2], y's backing        the 3x3 stage's output [N][Cout][H][W] (null: not
+//                 y floats,off,sN,sC,   the 1x1 stage    buffer uploaded AS GIVEN; per source its            wanted; kind 1 fused: never written, returned as
+//                 sH; per source C,H,W,                  backing buffer                                      the zeros it was allocated with)
+//                 up,floats,off,sN,sC,sH
+//                 A 3x3 conv + folded BatchNorm + activation on conv_x3h.hip in the tiling <MT, TH> (mfma_mode 3), and the 1x1 stage that
+//                 reads its output: kind 1 a Conv2DBNActiv Cout -> Cout2 into the view (off, sN, sC, sH) of y (the stage tails of the
+//                 low-band nets), kind 2 the LSTM squeeze Cout -> 1 + BatchNorm + ReLU into y [N][H][W].  With the handle's option
+//                 fuse_tail on: ONE launch (ConvArgs::tail; refused, -2, where x3h_tail_ok refuses); off: the two launches of the
+//                 executor (launch_conv's 1x1 / launch_squeeze_conv behind the same conv_x3h launch).  y sits between guard bands (-3).
+void Model::debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                            int nout) {
+    const std::string who = "vr_debug_kernel(conv_tail): ";
+    VR_CHECK(ndims >= 12 && nfp >= 2 && nout >= 2, -2, who + "too few arguments");
+    const int nsrc = (int)dims[0], N = (int)dims[1], Cout = (int)dims[2], kind = (int)dims[3], Cout2 = (int)dims[4];
+    const X3Tile tile{(int)dims[5], (int)dims[6]};
+    VR_CHECK(nsrc >= 1 && nsrc <= 3 && N >= 1 && Cout >= 1 && (kind == 1 || kind == 2) && Cout2 >= 1 && (kind == 1 || Cout2 == 1), -2,
+             who + "1..3 sources, kind 1 or 2");
+    VR_CHECK((tile.MT == 32 || tile.MT == 64) && (tile.TH == 8 || (tile.TH == 16 && tile.MT == 32)), -2, who + "tilings: <32,8>, <32,16>, <64,8>");
+    VR_CHECK(mfma_mode == 3, -2, who + "conv_x3h runs in mfma_mode 3");
+    VR_CHECK(ndims >= 12 + 9 * nsrc && nin >= 5 + nsrc && in[0] && in[1] && in[2] && in[3] && in[4] && out[0], -2, who + "too few arguments");
+    ConvArgs a{};
+    a.nsrc = nsrc; a.N = N; a.Cout = Cout; a.CoutPad = (Cout + 31) / 32 * 32;
+    VR_CHECK(a.CoutPad % tile.MT == 0, -2, who + "the cout tile does not divide the padded couts");
+    a.d1 = a.d2 = 1 << 30;
+    a.bf16 = 3;
+    a.pad_h = a.pad_w = 1;
+    std::vector<std::unique_ptr<DevBuf>> keep;
+    auto upload = [&](const float* host, size_t n) { keep.emplace_back(new DevBuf(host, n)); return keep.back()->p; };
+    int Cin = 0;
+    const ConvSrc* ups = nullptr;
+    for (int i = 0; i < nsrc; ++i) {
+        const int64_t* d = dims + 12 + 9 * i;
+        Tensor t;
+        t.N = N; t.C = (int)d[0]; t.H = (int)d[1]; t.W = (int)d[2];
+        const bool up = d[3] != 0;
+        const size_t floats = (size_t)d[4];
+        t.sN = d[6]; t.sC = d[7]; t.sH = d[8];
+        VR_CHECK(in[5 + i] && view_fits(d[5], t.sN, t.sC, t.sH, N, t.C, t.H, t.W, floats), -2, who + "a source view leaves its buffer");
+        t.p = upload(in[5 + i], floats) + d[5];
+        t.slope = 1.f;
+        a.src[i] = make_src(t, up, 0);
+        const int vh = up ? 2 * t.H : t.H, vw = up ? 2 * t.W : t.W;
+        if (i == 0) { a.Hin = vh; a.Win = vw; }
+        VR_CHECK(vh == a.Hin && vw == a.Win, -2, who + "the sources must share the input size");
+        if (up && ups) VR_CHECK(ups->H == t.H && ups->W == t.W && ups->sH == t.sH, -2, who + "upsampled sources must share H, W and row stride");
+        if (up) ups = &a.src[i];
+        Cin += t.C;
+        if (i == 0) a.c1 = Cin;
+        if (i <= 1) a.c2 = Cin;
+    }
+    a.Cin = Cin;
+    a.Hout = a.Hin; a.Wout = a.Win;
+    const int H = a.Hout, W = a.Wout;
+    std::vector<float> wk((size_t)Cin * 9 * a.CoutPad, 0.f);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int k = 0; k < 9; ++k) wk[((size_t)ci * 9 + k) * a.CoutPad + co] = in[0][((size_t)co * Cin + ci) * 9 + k];
+    DevBuf dwk(wk.data(), wk.size());
+    a.w = dwk.p;
+    a.epi = upload(in[1], (size_t)Cout * 2); a.epi_slope = fp[0];
+    DebugWeightForms wf;
+    debug_weight_forms(dwk.p, Cin, 3, 1, 1, 1, a.CoutPad, a.Win, true, a, wf);
+    {
+        X3Tile any;
+        VR_CHECK(a.x3w && x3_pick(a, ConvShape{3, 1, 1, 1}, &any), -2, who + "conv_x3h does not take this launch");
+    }
+    // the second stage: K-major weights [Cout][CoutPad2] (kind 1) or [Cout] (kind 2)
+    const int CoutPad2 = (Cout2 + 31) / 32 * 32;
+    std::vector<float> w2((size_t)Cout * (kind == 1 ? CoutPad2 : 1), 0.f);
+    for (int j = 0; j < Cout2; ++j)
+        for (int c = 0; c < Cout; ++c) w2[kind == 1 ? (size_t)c * CoutPad2 + j : (size_t)c] = in[2][(size_t)j * Cout + c];
+    DevBuf dw2(w2.data(), w2.size());
+    const float* epi2 = upload(in[3], (size_t)Cout2 * 2);
+    const size_t yfloats = (size_t)dims[7];
+    const long long yoff = kind == 1 ? dims[8] : 0, ysN = kind == 1 ? dims[9] : (long long)H * W, ysC = kind == 1 ? dims[10] : 0,
+                    ysH = kind == 1 ? dims[11] : W;
+    VR_CHECK(view_fits(yoff, ysN, kind == 1 ? ysC : 1, ysH, N, kind == 1 ? Cout2 : 1, H, W, yfloats), -2, who + "the view of y leaves its buffer");
+    GuardedBuf y(in[4], yfloats);
+    DevBuf prod((size_t)N * Cout * H * W);
+    a.dst[0] = ConvDst{prod.p, (long long)Cout * H * W, (long long)H * W, W, 0, 0};
+    x3_fill_tiling(a, tile);
+    if (fuse_tail) {
+        a.tail = kind; a.t_Cout = Cout2; a.t_CoutPad = kind == 1 ? CoutPad2 : 1; a.t_w = dw2.p; a.t_epi = epi2; a.t_slope = fp[1];
+        a.t_p = y.p() + yoff; a.t_sN = ysN; a.t_sC = ysC; a.t_sH = ysH;
+        VR_CHECK(x3h_tail_ok(a, tile), -2, who + "conv_x3h has no kernel for this launch with a second stage (x3h_tail_ok)");
+        x3h_launch_conv(a, tile, stream);
+    } else {
+        x3h_launch_conv(a, tile, stream);
+        const Tensor pt = dense(prod.p, N, Cout, H, W);
+        if (kind == 1) {
+            ConvArgs b{};
+            b.nsrc = 1; b.N = N; b.Cin = Cout; b.c1 = b.c2 = Cout; b.Cout = Cout2; b.CoutPad = CoutPad2;
+            b.d1 = b.d2 = 1 << 30;
+            b.bf16 = 3;
+            b.src[0] = make_src(pt, false, 0);
+            b.Hin = b.Hout = H; b.Win = b.Wout = W;
+            b.w = dw2.p;
+            b.epi = epi2; b.epi_slope = fp[1];
+            b.dst[0] = ConvDst{y.p() + yoff, ysN, ysC, ysH, 0, 0};
+            launch_conv(b, ConvShape{1, 1, 1, 1}, stream);
+        } else {
+            launch_squeeze_conv(pt, dw2.p, y.p(), nullptr, false, stream, epi2);
+        }
+    }
+    VR_HIP(hipStreamSynchronize(stream));
+    VR_CHECK(y.intact(), -3, who + "a launch stored outside y's buffer");
+    y.download(out[0]);
+    prod.download(out[1]);
+}
+
 void Model::debug_wgrad_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                                int nout) {
     const std::string who = "vr_debug_kernel(wgrad_launch): ";
@@ -809,6 +920,7 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         return;
     }
     if (name == "conv_launch") { debug_conv_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
+    if (name == "conv_tail") { debug_conv_tail(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "wgrad_launch") { debug_wgrad_launch(dims, ndims, fp, nfp, in, nin, out, nout); return; }
     if (name == "wgrad_reduce") { debug_wgrad_reduce(dims, ndims, in, nin, out, nout); return; }
     if (name == "dgrad_launch") { debug_dgrad_launch(dims, ndims, in, nin, out, nout); return; }

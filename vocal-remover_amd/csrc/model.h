@@ -244,6 +244,8 @@ public:
 
     void debug_conv_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                            int nout);                     // its "conv_launch" entry
+    void debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
+                         int nout);                       // "conv_tail": a conv_x3h launch and the 1x1 stage behind it, fused or as two launches
     void debug_wgrad_launch(const int64_t* dims, int ndims, const float* fp, int nfp, const float* const* in, int nin, float* const* out,
                             int nout);                    // "wgrad_launch": one launch_wgrad in its general form
     void debug_wgrad_reduce(const int64_t* dims, int ndims, const float* const* in, int nin, float* const* out, int nout);   // "wgrad_reduce"
@@ -329,6 +331,9 @@ public:
     // the mask (predict_mask's offset crop, lib/nets.py:124-128) has the stage-3 dec1 conv compute only the 32-column tiles meeting
     // them (ConvArgs::w_lo / w_hi) and the head read only those; 0 = every column, as before
     bool crop_window = true;
+    // vr_set_option("fuse_tail") (default 1): eval, mfma_mode 3, no taps -- the 1x1 stage tails of the low-band nets and the LSTM squeeze
+    // run in the epilogue of the conv_x3h launch whose output they alone read (FusedTail); 0 = two launches each, as before
+    bool fuse_tail = true;
     int net_w_lo = 0, net_w_hi = 0;                      // run_net: the columns of the mask the caller keeps (0, 0: all)
     void set_option(const std::string& name, int value);
     void reset_adam_state();
@@ -522,13 +527,18 @@ public:
     void* wire_buf = nullptr;                            // bf16 copy of the gradient bucket (wire_dtype 1)
 private:
     void build_fwd_args(Conv& L, const std::vector<SrcSpec>& srcs, int N, bool batch_as_h, ConvArgs& a);
+    // A 1x1 stage that only reads what ONE conv stores, offered to that conv's run_conv: the stage tail behind a low-band dec1 (kind 1:
+    // `L` into the view `out`; dec1's own output is then not written) or the LSTM squeeze behind dec2 (kind 2: `M` into out.p [N][H][W]).
+    // run_conv takes it into the launch's epilogue (ConvArgs::tail) when option "fuse_tail" is on, in eval, mfma_mode 3, with no taps
+    // recorded, and conv_x3h has the kernel for the launch's tiling (x3h_tail_ok); `done` says so, otherwise the caller launches it.
+    struct FusedTail { int kind = 0; Conv* L = nullptr; LSTMMod* M = nullptr; Tensor out; bool done = false; };
     Tensor run_conv(Conv& L, const std::vector<SrcSpec>& srcs, int N, const Tensor* out_view, const float* bias,
-                    bool batch_as_h);
+                    bool batch_as_h, FusedTail* tail = nullptr);
     template <class F> void for_each_conv(F&& f);
     std::vector<Conv*> conv_layers();                    // every conv in for_each_conv's order (train.hip)
-    Tensor run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view);
+    Tensor run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view, FusedTail* tail = nullptr);
     Tensor run_net_window(const Tensor& x, int w_lo, int w_hi);
-    Tensor run_lstm(LSTMMod& M, const Tensor& h);
+    Tensor run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed);   // z: [N][h.H][h.W]; squeezed: dec2's launch has filled it
     SrcSpec upsampled(const Tensor& t);
     Tensor run_net(const Tensor& x);                     // -> stg3 dec1 output (raw + affine)
     // the network's input from X: an optional workspace copy (*copy: from where), a complex handle's pack, the strided tensor; dry: sizes only

@@ -376,6 +376,7 @@ void Model::set_option(const std::string& name, int value) {
         x3s_mode = value < 0 ? x3s_default() : value;
     }
     else if (name == "crop_window") crop_window = value != 0;
+    else if (name == "fuse_tail") fuse_tail = value != 0;
     else if (name == "complex_train") {                      // a complex handle under the training entry points (off by default: they refuse it)
         if (!is_complex) throw Error(-2, "complex_train: this handle predicts a magnitude mask; the option belongs to complex-mask handles (VR_CREATE_COMPLEX)");
         complex_train = value != 0;
@@ -772,7 +773,7 @@ void Model::build_fwd_args(Conv& L, const std::vector<SrcSpec>& srcs, int N, boo
 }
 
 Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, const Tensor* out_view, const float* bias,
-                       bool batch_as_h) {
+                       bool batch_as_h, FusedTail* tail) {
     // Training: give the conv plain inputs (one element-wise / upsample pass per source) -- the forward conv
     // then takes the LDS-DMA kernel and the weight gradient re-reads the same buffers without arithmetic.
     std::vector<SrcSpec> srcs = srcs_in;
@@ -870,6 +871,43 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         npt = conv_part_count(a, shp);
         a.part = ws.allocf(npt * L.Cout * 2);
     }
+    // The 1x1 stage that only reads this conv's output goes into the launch's epilogue where conv_x3h has the kernel for it (model.h:
+    // FusedTail).  The workspace is laid out as without it (the dry run and every mode plan one sequence); a stage tail's producer
+    // buffer is then simply not written.
+    const char* fused_tag = "";
+    if (tail && !dry && fuse_tail && !training && mfma_mode == 3 && !record_taps && !conv_sink && !batch_as_h && fuse_epi && a.w_hi == 0) {
+        X3Tile xt;
+        int tth;
+        if (!thin16_pick(a, shp, &tth) && x3_pick(a, shp, &xt)) {           // (the launch takes conv_x3h: launch_conv's order)
+            ConvArgs b = a;
+            x3_fill_tiling(b, xt);
+            b.tail = tail->kind;
+            b.t_p = tail->out.p;
+            if (tail->kind == 1) {
+                const Conv& L2 = *tail->L;
+                VR_CHECK(L2.KS == 1 && L2.Cin == L.Cout && L2.bn && tail->out.C == L2.Cout && tail->out.H == a.Hout && tail->out.W == a.Wout, -3,
+                         "fused stage tail: " + L2.name + " does not follow " + L.name);
+                b.t_Cout = L2.Cout; b.t_CoutPad = L2.CoutPad; b.t_w = L2.w->dev; b.t_epi = L2.bn->affine; b.t_slope = L2.slope;
+                b.t_sN = tail->out.sN; b.t_sC = tail->out.sC; b.t_sH = tail->out.sH;
+            } else {
+                const LSTMMod& M = *tail->M;
+                VR_CHECK(M.squeeze.Cin == L.Cout, -3, "fused LSTM squeeze: " + M.squeeze.name + " does not follow " + L.name);
+                b.t_Cout = 1; b.t_CoutPad = 1; b.t_w = M.squeeze.w->dev; b.t_epi = M.squeeze.bn->affine; b.t_slope = 0.f;
+                b.t_sN = (long long)a.Hout * a.Wout; b.t_sC = 0; b.t_sH = a.Wout;
+            }
+            // Rule (profiles/fused_tail_ab.md): a site is fused where the one launch beats producer + consumer by at least half the consumer's
+            // time at the 11-, 6- and 5-crop grids.  The squeeze behind the 64-cout dec2 with upsampled sources (stage 3) missed it at 6 crops
+            // (13.6 us saved against a bar of 16.1; 23.9 / 22.9 at 11): it stays two launches.
+            const bool any_up = a.src[0].up || (a.nsrc > 1 && a.src[1].up) || (a.nsrc > 2 && a.src[2].up);
+            const bool by_rule = !(tail->kind == 2 && xt.MT == 64 && any_up);
+            if (by_rule && x3h_tail_ok(b, xt)) {
+                a.tail = b.tail; a.t_p = b.t_p; a.t_Cout = b.t_Cout; a.t_CoutPad = b.t_CoutPad; a.t_w = b.t_w; a.t_epi = b.t_epi;
+                a.t_slope = b.t_slope; a.t_sN = b.t_sN; a.t_sC = b.t_sC; a.t_sH = b.t_sH;
+                tail->done = true;
+                fused_tag = tail->kind == 1 ? "+tail" : "+squeeze";
+            }
+        }
+    }
     if (!dry && conv_sink) {
         // the caller launches this conv together with its siblings (ASPP branches: one conv_x3d launch for the four) and, in training,
         // finalises the BatchNorm statistics behind it
@@ -893,7 +931,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         if (profiling) {
             // algorithmic HBM bytes of the launch: the virtual input, the 3x3/1x1 weights and the output, once each
             char tag[160];
-            snprintf(tag, sizeof tag, "%s k%d s%d d%d ci%d co%d %dx%dx%d", L.name.c_str(), L.KS, L.stride, L.dh, L.Cin,
+            snprintf(tag, sizeof tag, "%s%s k%d s%d d%d ci%d co%d %dx%dx%d", L.name.c_str(), fused_tag, L.KS, L.stride, L.dh, L.Cin,
                      L.Cout, a.N, a.Hout, a.Wout);
             double bytes = conv_alg_bytes(L, a, N, batch_as_h);
             if (wcols < a.Wout) {                            // column window: the output and the full-resolution input over those columns (+ halo)
@@ -927,14 +965,13 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
 }
 
 // layers.LSTMModule.forward (lib/layers.py:124-133)
-Tensor Model::run_lstm(LSTMMod& M, const Tensor& h) {
+Tensor Model::run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed) {
     const int N = h.N, nb = h.H, nf = h.W;
     VR_CHECK(nb == M.nin, -2, "LSTM input size does not match the number of bins at dec2");
-    // 1x1 conv 2c -> 1 (+BN+ReLU): raw z [N][nb][nf]
-    float* z = ws.allocf((size_t)N * nb * nf);
+    // 1x1 conv 2c -> 1 (+BN+ReLU): raw z [N][nb][nf] (the caller's buffer: dec2's launch may have filled it already, FusedTail)
     const int nblk = launch_squeeze_conv(h, M.squeeze.w->dev, z, nullptr, true, stream);
     float* part = training ? ws.allocf((size_t)nblk * 2) : nullptr;
-    if (!dry) {
+    if (!dry && !squeezed) {
         // eval: BatchNorm (running statistics, folded) + ReLU in the kernel's store, so the LSTM input projection reads a plain tensor
         launch_squeeze_conv(h, M.squeeze.w->dev, z, part, false, stream, training ? nullptr : M.squeeze.bn->affine);
         if (training) {
@@ -1022,7 +1059,7 @@ Model::SrcSpec Model::upsampled(const Tensor& t) {
 }
 
 // nets.BaseNet.__call__ (lib/nets.py:26-41)
-Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view) {
+Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view, FusedTail* tail) {
     const std::string& p = B.prefix;
     Tensor e[5];
     e[0] = run_conv(B.enc1, in, N, nullptr, nullptr, false);
@@ -1140,9 +1177,13 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
     }
     tap(p + ".aspp", h);
     // decoders (lib/layers.py:51-64): upsample x2 + skip concat + conv, all inside the conv's loader
+    // (the LSTM squeeze reads only dec2's output: its buffer exists before dec2 runs, so that dec2's launch can fill it, FusedTail)
+    FusedTail sq;
+    sq.kind = 2; sq.M = &B.lstm;
     for (int i = 0; i < 3; ++i) {
         SrcSpec up = upsampled(h);
-        h = run_conv(B.dec[i], {up, SrcSpec{e[3 - i]}}, N, nullptr, nullptr, false);
+        if (i == 2) sq.out.p = ws.allocf((size_t)N * e[1].H * e[1].W);
+        h = run_conv(B.dec[i], {up, SrcSpec{e[3 - i]}}, N, nullptr, nullptr, false, i == 2 ? &sq : nullptr);
         tap(p + ".dec" + std::to_string(4 - i), h);
     }
     // Eval, stage 3 (the side stream is idle there): the x2 upsample of h (HBM-bound) runs beside the LSTM branch
@@ -1162,7 +1203,7 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
         VR_HIP(hipEventRecord(lstm_join, side_stream));
         stream = ms;
     }
-    Tensor l = run_lstm(B.lstm, h);
+    Tensor l = run_lstm(B.lstm, h, sq.out.p, sq.done);
     tap(p + ".lstm", l);
     if (fk) VR_HIP(hipStreamWaitEvent(stream, lstm_join, 0));
     else uh = upsampled(h);
@@ -1171,7 +1212,7 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
     const bool win = &B == &nets_[4] && net_w_hi > 0;
     if (win) { conv_w_lo = net_w_lo; conv_w_hi = net_w_hi; }
     Tensor o;
-    try { o = run_conv(B.dec[3], {uh, ul, SrcSpec{e[0]}}, N, out_view, nullptr, false); } catch (...) { conv_w_lo = conv_w_hi = 0; throw; }
+    try { o = run_conv(B.dec[3], {uh, ul, SrcSpec{e[0]}}, N, out_view, nullptr, false, tail); } catch (...) { conv_w_lo = conv_w_hi = 0; throw; }
     conv_w_lo = conv_w_hi = 0;
     tap(p + ".dec1", o);
     return o;
@@ -1213,12 +1254,23 @@ Tensor Model::run_net(const Tensor& x) {
         VR_HIP(hipStreamWaitEvent(side_stream, ef, 0));
         band_fork_active = true;                 // until the join: the side stream belongs to the high-band chain
     }
-    Tensor l1r = run_basenet(nets_[0], {SrcSpec{xl}}, B, nullptr);
+    // the low-band nets end in a 1x1 Conv2DBNActiv that is dec1's only reader: offered to dec1's launch (FusedTail); what that launch
+    // has stored is the tail's output -- the tensor run_conv(tail) returns in eval: final activations, no pending affine
+    auto low_band = [&](BaseNetL& net, Conv& tl, const std::vector<SrcSpec>& in, const Tensor& view) {
+        FusedTail ft;
+        ft.kind = 1; ft.L = &tl; ft.out = view; ft.out.C = tl.Cout;
+        Tensor r = run_basenet(net, in, B, nullptr, &ft);
+        if (!ft.done) return run_conv(tl, {SrcSpec{r}}, B, &view, nullptr, false);
+        Tensor o;
+        o.N = B; o.C = tl.Cout; o.H = view.H; o.W = view.W;
+        o.p = view.p; o.g = view.g; o.sN = view.sN; o.sC = view.sC; o.sH = view.sH;
+        o.aff0 = nullptr; o.slope = 1.f;
+        return o;
+    };
     v = half(aux1, 0);
-    Tensor l1 = run_conv(tail1, {SrcSpec{l1r}}, B, &v, nullptr, false);
-    Tensor l2r = run_basenet(nets_[2], {SrcSpec{xl}, SrcSpec{l1}}, B, nullptr);
+    Tensor l1 = low_band(nets_[0], tail1, {SrcSpec{xl}}, v);
     v = half(aux2, 0);
-    Tensor l2 = run_conv(tail2, {SrcSpec{l2r}}, B, &v, nullptr, false);
+    Tensor l2 = low_band(nets_[2], tail2, {SrcSpec{xl}, SrcSpec{l1}}, v);
     if (fork) stream = side_stream;
     const size_t tape_hi0 = tape.size();
     v = half(aux1, 1);

@@ -171,6 +171,18 @@ struct ConvArgs {
                                // [w_lo, w_hi) run; the input geometry stays full width (halo columns are real data) and the columns
                                // outside those tiles are not written.  Eval: the consumer keeps only the window (predict_mask's crop)
     int wt0;                   // first 32-column tile of the window (x3_fill_tiling); tiles_w counts the window's tiles
+    // A second, 1x1 stage in the epilogue (conv_x3h.hip only, eval, one cout tile: x3h_tail_ok).  The first stage's bias, folded
+    // BatchNorm and activation are applied to the accumulators in registers, then
+    //   tail 1: y[j] = act(t_slope)(s2[j] * sum_c w2[c][j] a[c] + b2[j]), j < t_Cout <= 16, stored through the view t_p / t_sN / t_sC /
+    //           t_sH; the first stage's own output is NOT stored (dst is ignored)
+    //   tail 2: the first stage's output is stored as usual, and z = relu(s2 * sum_c w2[c] a[c] + b2) goes to t_p [N][Hout][Wout]
+    int tail;                  // 0: none
+    int t_Cout, t_CoutPad;     // tail 1: the 1x1 layer's couts and the row pitch of t_w
+    const float* t_w;          // tail 1: [Cout][t_CoutPad] (the 1x1 layer's K-major weights); tail 2: [Cout]
+    const float* t_epi;        // folded BatchNorm of the second stage: tail 1 [t_Cout][2], tail 2 [2]
+    float t_slope;             // tail 1: activation slope of the second stage
+    float* t_p;
+    long long t_sN, t_sC, t_sH;
 };
 
 struct ConvShape {             // static description used by the launcher
