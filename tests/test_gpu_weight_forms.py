@@ -28,13 +28,16 @@ just below one, 2^20 among 2^-20, negative maxima, subnormals only, the largest 
 
 Part two, vr_debug_kernel 'layer_forms': what a live handle CascadedNet(512, 256, 8, 32) (B 2, 160 frames; its first conv has Cin 2) holds
 for each of its 107 convs, downloaded after a call and recomputed from the weights downloaded with it: bit equality for the plane, flip and
-class forms, the bound above for U.  Only the forms the call's launches read are checked (Model::refresh_wino, train.hip): eval -- wino of
+class forms, the bound above for U.  Only the forms the call's launches read are checked (Model::refresh_forms, csrc/weight_forms.h): eval -- wino of
 the 3x3 stride-1 layers, their x3w as bf16 x 3 in mfma_mode 2, as fp16 x 2 + tails in mode 3 together with the ASPP branch convs and the
 stride-2 convs; train_step -- those plus wt of every conv, s2w of the stride-2 ones, winot, x3t (modes 2, 3), x3dt (mode 3).  Steps: a
 fresh handle with seed A; load_state_dict(seed B) on the same handle (every layer's weights are B's, no x3w image equals A's); mfma_mode
 3 -> 2 -> 0 -> 3 (the one arena holds the form of the mode); train_step under train_winograd 1, 0, 1; Trainer.step (Adam) then
 train_step; eval; the flat parameter scaled by 1.01 on the device + params_dirty.  Without the hook: after eval and after the last
 step a FRESH handle given the used handle's state_dict() predicts bit for bit the same mask (after the last step in modes 3, 2, 0).
+
+Part three, the library's launch profiler: how many launches of the six batched refresh kernels a call makes -- once after a change, none
+when nothing changed (test_a_call_refreshes_once_and_only_after_a_change, which says where its expected counts come from).
 
 One finding, fixed here: the bf16 split of a finite weight above 2^128 - 2^119 (the largest finite float of the value table) rounds its
 first plane to infinity, and the planes that follow are then -Inf and NaN.  Before: the three plane words of every such weight differed from
@@ -60,7 +63,9 @@ Scratch mutants the file was tried against on the device (never committed; each 
   * the early return of x3_weights_elem taken one element early -- the four x3 cases fail (three plane words left unwritten).  The early
     return REMOVED was not run: it stores past the destination by construction, further than the hook's guard bands reach.
 """
+import ctypes
 import functools
+import re
 
 import numpy as np
 import pytest
@@ -403,3 +408,72 @@ def test_a_live_handle_refreshes_the_forms_its_launches_read(vr):
     assert not torch.equal(scaled['stg1_low_band_net.0.enc1.conv.0.weight'], moved['stg1_low_band_net.0.enc1.conv.0.weight'])
     check_handle(vr.native, model, 3, False, 'step 7, the arena scaled by 1.01', prior_x3w=x3w_5, state=scaled)
     fresh_handle_agrees(vr, model, x, (3, 2, 0), 'step 7')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# how often a call refreshes
+# ---------------------------------------------------------------------------------------------------------------------------------
+REFRESH_KERNELS = ('wino_weights_batched_kernel', 'x3_weights_batched_kernel', 'x3h_wscale_batched_kernel', 'x3h_weights_batched_kernel',
+                   'flip_transpose_kernel', 's2_class_weights_kernel')
+REFRESH_CALLS = ('predict_mask after params_dirty', 'predict_mask again', 'train_step', 'predict_mask after the step')
+# {mfma_mode: per call of REFRESH_CALLS the launches of each of REFRESH_KERNELS}
+REFRESH_LAUNCHES = {
+    3: ((1, 0, 1, 1, 0, 0), (0, 0, 0, 0, 0, 0), (2, 0, 2, 2, 1, 1), (1, 0, 1, 1, 0, 0)),
+    2: ((1, 1, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0), (2, 2, 0, 0, 1, 1), (1, 1, 0, 0, 0, 0)),
+    0: ((1, 0, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0), (2, 0, 0, 0, 1, 1), (1, 0, 0, 0, 0, 0)),
+}
+
+
+def _profiled(vr, model, fn):
+    """{kernel name: launches} of fn() under the library's launch profiler"""
+    nat, h = vr.native, model._handle.h
+    nat.check(nat.lib().vr_profile_begin(h))
+    try:
+        fn()
+    finally:
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
+        nat.check(nat.lib().vr_profile_end(h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+    need = nat.lib().vr_profile_report(h, None, 0)
+    buf = ctypes.create_string_buffer(int(need) + 1)
+    nat.lib().vr_profile_report(h, buf, need)
+    calls = {}
+    for ln in buf.value.decode().splitlines():
+        f = ln.split('\t')
+        calls[f[0].strip()] = calls.get(f[0].strip(), 0) + int(f[1])
+    return calls
+
+
+def test_a_call_refreshes_once_and_only_after_a_change(vr):
+    """Launches of the six refresh kernels per call, in mfma_mode 3, 2 and 0: a predict_mask after params_dirty, the same call again
+    (nothing changed: none), one train_step, a predict_mask after it.  The expected counts are NOT derived from the code under test:
+    they are what the commit before the weight forms moved into one record per conv (WeightForms) launched, measured with this test
+    body on an MI355X.  A refresh that ran twice, or ran with nothing changed, computes the same forms and costs time on every step."""
+    sd = weights.make_state_dict(21, n_fft=N_FFT, nout=NOUT, nout_lstm=NOUT_LSTM)
+    x = torch.rand(2, 2, N_FFT // 2 + 1, FRAMES, generator=torch.Generator().manual_seed(0)).to(DEV)
+    X, y = (t.to(DEV) for t in train_step.synth_batch(2, T=FRAMES, n_fft=N_FFT, seed=5))
+    model = vr.nets.CascadedNet(N_FFT, N_FFT // 2, NOUT, NOUT_LSTM)
+    model.load_state_dict(sd)
+    model.to(torch.device(DEV))
+
+    def count(fn):
+        calls = _profiled(vr, model, fn)
+        return tuple(sum(n for k, n in calls.items() if re.search(r'\b%s\b' % name, k)) for name in REFRESH_KERNELS)
+
+    got = {}
+    for mode in REFRESH_LAUNCHES:
+        model.eval()
+        model.set_option('mfma_mode', mode)
+        model.set_option('params_dirty', 1)
+        dirty = count(lambda: model.predict_mask(x))
+        again = count(lambda: model.predict_mask(x))
+        model.train()
+        step = count(lambda: model.train_step(X, y, 1))
+        model.eval()
+        got[mode] = (dirty, again, step, count(lambda: model.predict_mask(x)))
+    print('REFRESH_KERNELS = %s' % ', '.join(REFRESH_KERNELS))
+    for mode, rows in got.items():
+        print('    %d: (%s),' % (mode, ', '.join(str(r) for r in rows)))
+    for mode, rows in got.items():
+        assert rows[1] == (0,) * len(REFRESH_KERNELS), 'mfma_mode %d, %s: %s' % (mode, REFRESH_CALLS[1], rows[1])
+        for what, r, want in zip(REFRESH_CALLS, rows, REFRESH_LAUNCHES[mode]):
+            assert r == want, 'mfma_mode %d, %s: launches %s, expected %s (%s)' % (mode, what, r, want, ', '.join(REFRESH_KERNELS))

@@ -244,7 +244,7 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 layers, from their K-major copies [Cin][KK][CoutPad] with zeroed padded couts, on the handle's stream: once per
 //                 descriptor through launch_wino_weights / launch_wino_weights6 / launch_x3_weights / launch_x3h_weights (flip and
 //                 s2_class exist only in batched form: a table of one descriptor), and once for all descriptors in ONE launch of the
-//                 batched launcher, its grid sized as Model::run_wino_batch / run_x3_batch / ensure_train_state size it.  Every buffer has
+//                 batched launcher, its grid sized as Model::fill_form sizes it.  Every buffer has
 //                 the size the library gives it (x3_weights_bytes, wino_weights6_bytes, Cin 16 CoutPad, Cout KK CinPad, 4 Cout 9
 //                 CinPad), is filled with the NaN canary 0x7FC12345 and sits between guard bands.  Error -3: a store found in a guard band.
 // layer_forms     i[,capacity]           -                -                                                   i = -1: out[0] = the layer count, then per conv in
@@ -252,10 +252,12 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                                                                                                            mask (`capacity` floats); else the K-major weights
 //                                                                                                            [Cin][KK][CoutPad], then the buffers of the mask
 //                 What the handle holds for conv i, read-only, after the handle's stream has drained.  Mask bits and outputs 1..9 in this
-//                 order: L.wino [Cin][16][CoutPad], L.wino6, L.x3w (x3_weights_bytes(Cin, KK, CoutPad)), wt_of [Cout][KK][CinPad], winot_of
-//                 [Cout][16][CinPad], winot6_of, x3t_of and x3dt_of (x3_weights_bytes(Cout, KK, CinPad)), s2w_of [4][Cout][9][CinPad].  A
+//                 order: wino [Cin][16][CoutPad], wino6, x3w (x3_weights_bytes of Cin, KK, CoutPad), wt [Cout][KK][CinPad], winot
+//                 [Cout][16][CinPad], winot6, x3t and x3dt (x3_weights_bytes of Cout, KK, CinPad), s2w [4][Cout][9][CinPad].  A
 //                 null output is skipped; an output for a buffer the handle does not hold is error -2.  A set bit says that the buffer
-//                 exists, not that the current mfma_mode fills it.
+//                 exists, not that the current mfma_mode fills it.  The buffers are the slots of the conv's record (Conv::forms,
+//                 weight_forms.h) and their sizes come from form_spec, the rule the handle allocates by: a new form is added there.
+//                 The record has ONE slot for the planes of wt; it is reported as x3t for a plain 3x3, as x3dt for a conv_x3d layer.
 namespace {
 
 constexpr uint32_t FORM_CANARY = 0x7fc12345u;
@@ -363,10 +365,10 @@ void Model::debug_layer_forms(const int64_t* dims, int ndims, float* const* out,
     VR_CHECK(ndims >= 1 && nout >= 1 && out[0], -2, who + "too few arguments");
     VR_HIP(hipStreamSynchronize(stream));
     const std::vector<Conv*> convs = conv_layers();
+    static const FormId form_of[9] = {F_WINO, F_WINO6, F_X3W, F_WT, F_WINOT, F_WINOT6, F_X3T, F_X3T, F_S2W};
     auto held = [&](const Conv& L, void* b[9]) {
-        auto at = [&](auto& map) { auto it = map.find(L.w); return it == map.end() ? nullptr : (void*)it->second; };
-        b[0] = L.wino; b[1] = L.wino6; b[2] = L.x3w; b[3] = at(wt_of); b[4] = at(winot_of); b[5] = at(winot6_of); b[6] = at(x3t_of);
-        b[7] = at(x3dt_of); b[8] = at(s2w_of);
+        for (int j = 0; j < 9; ++j) b[j] = L.forms.p[form_of[j]];
+        b[L.cls == FC_X3D ? 6 : 7] = nullptr;
     };
     const long long i = dims[0];
     if (i < 0) {
@@ -385,17 +387,13 @@ void Model::debug_layer_forms(const int64_t* dims, int ndims, float* const* out,
     }
     VR_CHECK(i < (long long)convs.size() && nout >= 10, -2, who + "no such conv, or fewer than ten outputs");
     const Conv& L = *convs[(size_t)i];
-    const int KK = L.KS * L.KS, CinPad = round32(L.Cin);
     void* b[9];
     held(L, b);
-    const size_t words[9] = {(size_t)L.Cin * 16 * L.CoutPad, wino_weights6_bytes(L.Cin, L.CoutPad) / 4, x3_weights_bytes(L.Cin, KK, L.CoutPad) / 4,
-                             (size_t)L.Cout * KK * CinPad, (size_t)L.Cout * 16 * CinPad, wino_weights6_bytes(L.Cout, CinPad) / 4,
-                             x3_weights_bytes(L.Cout, KK, CinPad) / 4, x3_weights_bytes(L.Cout, KK, CinPad) / 4, (size_t)4 * L.Cout * 9 * CinPad};
-    VR_HIP(hipMemcpy(out[0], L.w->dev, (size_t)L.Cin * KK * L.CoutPad * 4, hipMemcpyDeviceToHost));
+    VR_HIP(hipMemcpy(out[0], L.w->dev, (size_t)L.Cin * L.KS * L.KS * L.CoutPad * 4, hipMemcpyDeviceToHost));
     for (int j = 0; j < 9; ++j) {
         if (!out[1 + j]) continue;
         VR_CHECK(b[j], -2, who + "the handle holds no such buffer for this conv");
-        VR_HIP(hipMemcpy(out[1 + j], b[j], words[j] * 4, hipMemcpyDeviceToHost));
+        VR_HIP(hipMemcpy(out[1 + j], b[j], form_spec(form_of[j], L, mfma_mode, W6_PAD64).bytes, hipMemcpyDeviceToHost));
     }
 }
 
@@ -504,7 +502,7 @@ void Model::debug_conv_launch(const int64_t* dims, int ndims, const float* fp, i
     a.w = dwk.p;
     if (in[1]) a.bias = upload(in[1], (size_t)Cout);
     if (in[2]) { a.epi = upload(in[2], (size_t)Cout * 2); a.epi_slope = fp[0]; }
-    DebugWeightForms wf;
+    LocalConv wf;
     debug_weight_forms(dwk.p, Cin, KS, 1, dh, dw, a.CoutPad, a.Win, transformed, a, wf);
     // destinations
     std::vector<std::unique_ptr<GuardedBuf>> dst(3);
@@ -604,7 +602,7 @@ void Model::debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int
     DevBuf dwk(wk.data(), wk.size());
     a.w = dwk.p;
     a.epi = upload(in[1], (size_t)Cout * 2); a.epi_slope = fp[0];
-    DebugWeightForms wf;
+    LocalConv wf;
     debug_weight_forms(dwk.p, Cin, 3, 1, 1, 1, a.CoutPad, a.Win, true, a, wf);
     {
         X3Tile any;
@@ -776,7 +774,9 @@ void Model::debug_dgrad_launch(const int64_t* dims, int ndims, const float* cons
     VR_CHECK(stride == 1 || (KS == 3 && dh == 1 && dw == 1), -2, who + "stride 2 needs a 3x3 kernel without dilation");
     VR_CHECK(ndims >= 13 + 11 * nsrc && nin >= 2 + nsrc && nout >= nsrc + 1, -2, who + "too few arguments");
     VR_CHECK(in[0] && in[1] && out[nsrc], -2, who + "missing weights, dz or the info output");
-    Conv L;
+    LocalConv lc;
+    Conv& L = lc.L;
+    Param& P = lc.P;
     L.name = "debug"; L.KS = KS; L.stride = stride; L.dh = dh; L.dw = dw;
     L.pad_h = KS == 1 ? 0 : dh; L.pad_w = KS == 1 ? 0 : dw; L.bn = nullptr; L.slope = 1.f;
     TapeRec r;
@@ -814,9 +814,7 @@ void Model::debug_dgrad_launch(const int64_t* dims, int ndims, const float* cons
     }
     L.Cin = Cin; L.Cout = Cout; L.CoutPad = (Cout + 31) / 32 * 32;
     const int KK = KS * KS;
-    Param P;
     P.kind = PK_CONV; P.Cin = Cin; P.Cout = Cout; P.KK = KK; P.CoutPad = L.CoutPad;
-    L.w = &P;
     std::vector<float> wk((size_t)Cin * KK * L.CoutPad, 0.f);
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci)
@@ -833,8 +831,7 @@ void Model::debug_dgrad_launch(const int64_t* dims, int ndims, const float* cons
     r.out.sN = dims[10]; r.out.sC = dims[11]; r.out.sH = dims[12]; r.out.slope = 1.f;
     ConvArgs f;
     build_fwd_args(L, r.srcs, N, batch_as_h, f);          // (refuses a batch-as-rows record that is no 1x1 conv on H = 1)
-    DebugDgradForms forms;
-    debug_dgrad_weight_forms(P, KS, stride, dh, dw, forms);
+    debug_dgrad_weight_forms(lc);
     // the workspace: sized by a dry pass, then a guarded slab of exactly that size in place of the handle's arena
     struct WsRestore {
         Model* m; Arena saved;

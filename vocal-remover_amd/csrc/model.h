@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "weight_forms.h"
 
 namespace vr {
 
@@ -63,10 +64,12 @@ struct Conv {
     Param* w = nullptr;
     BN* bn = nullptr;
     float slope = 0.f;              // activation after the BatchNorm
-    float* wino = nullptr;          // eval: Winograd-transformed weights [Cin][16][CoutPad] (3x3 stride-1 layers)
-    void* wino6 = nullptr;          // mfma_mode 2: the same as three bf16 planes (conv_wino.hip: wino_weights6_kernel)
-    void* x3w = nullptr;            // mfma_mode 2: the direct weights as three bf16 planes (conv_x3.hip: x3_weights_kernel)
+    FormClass cls = FC_NONE;        // which derived weight forms the layer's shape asks for (weight_forms.h)
+    WeightForms forms;              // ... and the ones it holds
 };
+inline FormSpec form_spec(FormId f, const Conv& L, int mfma_mode, Wino6Want w6) {
+    return form_spec(f, L.cls, L.Cin, L.Cout, L.KS * L.KS, L.CoutPad, mfma_mode, w6);
+}
 
 struct LSTMMod {
     Conv squeeze;                   // 1x1 conv 2c -> 1 (+BN+ReLU), run by the thin-conv kernel
@@ -285,19 +288,21 @@ public:
     void debug_conv(const float* x, int N, int Cin, int H, int W, const float* w_oihw, int Cout, int KS, int stride,
                     int dh, int dw, int up, const float* aff, float slope, const float* bias, float* out,
                     float* stats_out);
-    // The device forms of one layer's weights that `mfma_mode` multiplies with, made from the K-major copy dw_kmajor [Cin][KS*KS][CoutPad]
-    // and set in `a` (wino / wino6 / x3w); shared by debug_conv and the conv_launch hook of debug.hip.  Freed with the object.
-    struct DebugWeightForms {
-        float* wino = nullptr;
-        void* wino6 = nullptr;
-        void* x3w = nullptr;
-        DebugWeightForms() = default;
-        ~DebugWeightForms() { (void)hipFree(wino); (void)hipFree(wino6); (void)hipFree(x3w); }
-        DebugWeightForms(const DebugWeightForms&) = delete;
-        DebugWeightForms& operator=(const DebugWeightForms&) = delete;
+    // A hook's local conv and the weight forms made for it, by the handle's own rule, allocator and selection; frees them, also when a
+    // launch throws.
+    struct LocalConv {
+        Conv L;
+        Param P;
+        FormStore store;
+        LocalConv() { L.w = &P; }
+        ~LocalConv() { store.release(); }
+        LocalConv(const LocalConv&) = delete;
+        LocalConv& operator=(const LocalConv&) = delete;
     };
+    // The device forms of one layer's weights that `mfma_mode` multiplies with, made from the K-major copy dw_kmajor [Cin][KS*KS][CoutPad]
+    // through the single-layer launchers and set in `a` (wino / wino6 / x3w); shared by debug_conv and the conv_launch / conv_tail hooks.
     void debug_weight_forms(const float* dw_kmajor, int Cin, int KS, int stride, int dh, int dw, int CoutPad, int Win, bool transformed,
-                            ConvArgs& a, DebugWeightForms& f);
+                            ConvArgs& a, LocalConv& lc);
     bool record_taps = false;
     std::map<std::string, Tensor> taps;
     int64_t get_tap(const std::string& name, float* host, int64_t cap_floats, int64_t* shape4);
@@ -364,43 +369,30 @@ private:
 
     std::deque<BN> bns;
     std::vector<BN*> bn_list;
-    std::vector<Conv*> wino_list;                        // 3x3 stride-1 layers (conv_wino.hip)
     struct PendingConv { ConvArgs a; ConvShape shp; double flops, bytes; bool stats; BNFinalizeArgs fin; BN* bn; };
     std::vector<PendingConv>* conv_sink = nullptr;       // set: run_conv hands the launch to its caller instead of launching (ASPP branch group)
     int x3d_mode = 2;                                    // option "conv_x3d": 0 off, 1 single launches, 2 + the ASPP branch group
     int conv_w_lo = 0, conv_w_hi = 0;                    // set: the next run_conv stores only these output columns if conv_x3h takes it
-    std::vector<Conv*> x3d_list;                         // the ASPP branch convs conv_x3d.hip takes in mfma_mode 3: dilated 3x3, conv2 (1x1)
     int x3s_mode = x3s_default();                        // option "conv_x3s": the 3x3 stride-2 layers on the fp16 pipe in eval (conv_x3s.hip, mfma_mode 3); 0: conv_dma.hip
     static int x3s_default() { const char* e = getenv("VR_CONV_X3S"); return (e && atoi(e) == 0) ? 0 : 1; }
-    std::vector<Conv*> x3s_list;                         // the 3x3 stride-2 convs (enc2..enc5.conv1): fp16 planes, filled in mfma_mode 3
-    float* wino_arena = nullptr;
-    float* winot_arena = nullptr;                        // training: Winograd copies of the flipped/transposed weights
-    std::map<const Param*, float*> winot_of;
-    char* wino6_arena = nullptr;                         // mfma_mode 2: bf16-plane copies of both
-    char* winot6_arena = nullptr;
-    std::map<const Param*, void*> winot6_of;
-    char* x3_arena = nullptr;                            // mfma_mode 2: bf16-plane copies of the direct 3x3 stride-1 weights (conv_x3.hip)
-    char* x3t_arena = nullptr;                           //              and of their flipped / transposed forms (data gradient)
-    std::map<const Param*, void*> x3t_of;
-    std::map<const Param*, void*> x3dt_of;                // the same for x3d_list (fp16 planes, valid in mfma_mode 3 only)
+    // The derived weight forms (weight_forms.h): every conv's record points into form_store's one allocation per form, made when a
+    // refresh first fills the form -- an eval-only handle never holds the data-gradient forms, the bf16 planes of U exist only under
+    // mfma_mode 2 with VR_CONV_X3=0.  hold_form / fill_form serve the hooks' local convs too (`single`: the single-layer launchers).
+    FormStore form_store;
+    void hold_form(FormId f, const std::vector<Conv*>& convs, Wino6Want w6, FormStore& s);
+    void fill_form(FormId f, const std::vector<Conv*>& convs, Wino6Want w6, FormStore& s, bool single);
+    FormSelect form_select() const { return FormSelect{mfma_mode, training, train_wino, x3d_mode, x3s_mode, dry}; }
     // deferred weight-gradient slab sums of one backward pass (launch_wgrad_reduce_batched, round 6)
     std::vector<WgReduceDesc> wred_host, wred_sent;
     WgReduceDesc* wred_dev = nullptr;
     size_t wred_cap = 0;
     void flush_wgrad_sums();
-    struct X3Batch { std::vector<X3WDesc> host; X3WDesc* dev = nullptr; long long max_elems = 0; };
-    X3Batch xb_fwd, xb_bwd;
-    void run_x3_batch(X3Batch& b, std::vector<X3WDesc>& descs);
     // the grid sizes of the batched refresh launches, from their descriptor tables (shared with the weight_forms hook of debug.hip)
     static long long x3_batch_max_elems(const std::vector<X3WDesc>& descs);
     static int x3_batch_max_cout_pad(const std::vector<X3WDesc>& descs);
     static long long wino_batch_max_elems(const std::vector<WinoWDesc>& descs, bool split6);
     static long long s2w_batch_max_elems(const std::vector<S2WDesc>& descs);
-    void refresh_wino(bool with_dgrad);
-    // batched refresh: descriptor tables (host copy + device copy, re-uploaded only when a pointer changed)
-    struct WinoBatch { std::vector<WinoWDesc> host; WinoWDesc* dev = nullptr; long long max_elems = 0; };
-    WinoBatch wb_fwd, wb_bwd, wb_fwd6, wb_bwd6;
-    void run_wino_batch(WinoBatch& b, std::vector<WinoWDesc>& descs, bool split6);
+    void refresh_forms(bool with_dgrad);
     BNFoldDesc* d_fold = nullptr;
     bool affine_dirty = true;
     void fold_eval_affines();
@@ -455,14 +447,6 @@ private:
     void clear_gs_zero_ranges(hipStream_t st);
     float* g_arena = nullptr;                            // gradients of parameters (mirrors p_arena)
     float* m_arena = nullptr; float* v_arena = nullptr;  // Adam moments
-    float* wt_arena = nullptr; size_t wt_floats = 0;     // flipped/transposed conv weights for dgrad
-    FlipDesc* d_flip = nullptr; int n_flip = 0;
-    std::map<const Param*, float*> wt_of;
-    float* s2w_arena = nullptr;                          // parity-class weights of the stride-2 convs' data gradients
-    std::map<const Param*, float*> s2w_of;
-    std::vector<Conv*> s2_list;
-    S2WDesc* d_s2w = nullptr;                            // descriptor table of launch_s2_class_weights (one launch for all of them)
-    long long s2w_max = 0;
     long long adam_step = 0;
     float* grad_of(const Param* p) { return p->grad_override ? p->grad_override : g_arena + (p->dev - p_arena); }
 public:
@@ -479,21 +463,10 @@ private:
     // which launches the data gradient of a conv record took (bwd_conv_dgrad's return value)
     enum DgradPath { DG_NONE = 0, DG_STRIDE1 = 1, DG_S2_FUSED = 2, DG_S2_CLASSES = 3, DG_S2_ZINS = 4 };
     int bwd_conv_dgrad(TapeRec& r, const ConvArgs& f);   // step 4 of bwd_conv; f = the record's forward launch (build_fwd_args)
-    // The device forms of ONE layer's weights that its data gradient multiplies with, made from the K-major copy P.dev
-    // [Cin][KS*KS][CoutPad]: flipped / transposed, their Winograd, x3 / x3h and x3d forms in the handle's mfma_mode, the four parity-class
-    // arrays of a stride-2 3x3 -- registered under &P in wt_of / winot_of / x3t_of / x3dt_of / s2w_of as a train step registers a layer's.
-    // Shared by debug_conv_bwd and the dgrad_launch hook of debug.hip.  The object unregisters and frees them, also when a launch throws.
-    struct DebugDgradForms {
-        Model* m = nullptr;
-        const Param* P = nullptr;
-        float *wt = nullptr, *winot = nullptr, *s2w = nullptr;
-        void *x3t = nullptr, *flip_desc = nullptr, *s2_desc = nullptr;
-        DebugDgradForms() = default;
-        ~DebugDgradForms();
-        DebugDgradForms(const DebugDgradForms&) = delete;
-        DebugDgradForms& operator=(const DebugDgradForms&) = delete;
-    };
-    void debug_dgrad_weight_forms(const Param& P, int KS, int stride, int dh, int dw, DebugDgradForms& f);
+    // The device forms of ONE layer's weights that its data gradient multiplies with, made from the K-major copy lc.P.dev
+    // [Cin][KS*KS][CoutPad] of the local conv lc.L (dims set by the caller): flipped / transposed, their Winograd and plane forms in the
+    // handle's mfma_mode, the four parity-class arrays of a stride-2 3x3.  Shared by debug_conv_bwd and the dgrad_launch hook of debug.hip.
+    void debug_dgrad_weight_forms(LocalConv& lc);
     void bwd_bn_of(const Tensor& out, Conv& L);
     std::vector<float> dropout_host;                     // injected keep-masks [5][N][8*nout] or empty
     int dropout_mode = 1;                                // 0 off, 1 native RNG (default: nn.Dropout2d is active in train mode), 2 injected
@@ -535,7 +508,8 @@ private:
     Tensor run_conv(Conv& L, const std::vector<SrcSpec>& srcs, int N, const Tensor* out_view, const float* bias,
                     bool batch_as_h, FusedTail* tail = nullptr);
     template <class F> void for_each_conv(F&& f);
-    std::vector<Conv*> conv_layers();                    // every conv in for_each_conv's order (train.hip)
+    std::vector<Conv*> convs_;
+    const std::vector<Conv*>& conv_layers();             // every conv in for_each_conv's order (train.hip)
     Tensor run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, const Tensor* out_view, FusedTail* tail = nullptr);
     Tensor run_net_window(const Tensor& x, int w_lo, int w_hi);
     Tensor run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed);   // z: [N][h.H][h.W]; squeezed: dec2's launch has filled it

@@ -60,9 +60,7 @@ void Model::build_cba(Conv& L, const std::string& prefix, int nin, int nout_, in
     L.KS = ks; L.stride = stride; L.pad_h = pad_h; L.pad_w = pad_w; L.dh = dh; L.dw = dw; L.slope = slope;
     L.w = add_param(prefix + ".conv.0.weight", {nout_, nin, ks, ks}, PK_CONV, true);
     L.bn = add_bn(prefix + ".conv.1", nout_, 0);
-    if (ks == 3 && stride == 1 && dh == 1 && dw == 1) wino_list.push_back(&L);
-    if (ks == 3 && stride == 1 && dh > 1) x3d_list.push_back(&L);         // the dilated ASPP branches (conv_x3d.hip)
-    if (ks == 3 && stride == 2 && dh == 1 && dw == 1) x3s_list.push_back(&L);   // the encoder's stride-2 convs (conv_x3s.hip)
+    L.cls = form_class(ks, stride, dh, dw, false);
 }
 
 // nets.BaseNet (lib/nets.py:10-24)
@@ -79,7 +77,7 @@ void Model::build_basenet(BaseNetL& B, const std::string& p, int nin, int c, int
     const int C8 = 8 * c;
     build_cba(B.aspp_pool, p + ".aspp.conv1.1", C8, C8, 1, 1, 0, 0, 1, 1, RELU);
     build_cba(B.aspp_c2, p + ".aspp.conv2", C8, C8, 1, 1, 0, 0, 1, 1, RELU);
-    x3d_list.push_back(&B.aspp_c2);                                        // (runs beside the dilated branches in their launch)
+    B.aspp_c2.cls = form_class(1, 1, 1, 1, true);                          // (runs beside the dilated branches in their launch)
     const int dil[3][2] = {{4, 2}, {8, 4}, {12, 6}};
     for (int i = 0; i < 3; ++i)
         build_cba(B.aspp_d[i], p + ".aspp.conv" + std::to_string(i + 3), C8, C8, 3, 1, dil[i][0], dil[i][1], dil[i][0],
@@ -249,9 +247,9 @@ Model::~Model() {
     hipFree(wire_buf);
     if (stream) hipStreamSynchronize(stream);
     hipFree(p_arena); hipFree(b_arena); hipFree(d_fold);
-    hipFree(ws.base); hipFree(io.base); hipFree(gs.base); hipFree(wino_arena); hipFree(winot_arena); hipFree(wino6_arena); hipFree(winot6_arena); hipFree(x3_arena); hipFree(x3t_arena); hipFree(xb_fwd.dev); hipFree(xb_bwd.dev); hipFree(wb_fwd.dev); hipFree(wb_bwd.dev); hipFree(wb_fwd6.dev); hipFree(wb_bwd6.dev); hipFree(aug_buf); hipFree(wred_dev); hipFree(d_s2w);
+    hipFree(ws.base); hipFree(io.base); hipFree(gs.base); form_store.release(); hipFree(aug_buf); hipFree(wred_dev);
     for (BaseNetL& B : nets_) hipFree(B.lstm.bias_sum);
-    hipFree(g_arena); hipFree(m_arena); hipFree(v_arena); hipFree(wt_arena); hipFree(d_flip); hipFree(dropout_buf);
+    hipFree(g_arena); hipFree(m_arena); hipFree(v_arena); hipFree(dropout_buf);
     hipFree(plan.twiddle); hipFree(plan.window);
     for (Lane& l : lanes) {
         hipStreamSynchronize(l.main); hipStreamSynchronize(l.side);
@@ -346,7 +344,7 @@ void Model::fold_eval_affines() {
     int maxC = 1;
     for (BN* b : bn_list) maxC = std::max(maxC, std::max(b->C, b->bcast));
     launch_bn_fold_eval(d_fold, (int)bn_list.size(), maxC, 1e-5f, stream);
-    refresh_wino(false);        // the weights may have changed too (set_param / Adam)
+    refresh_forms(false);       // the weights may have changed too (set_param / Adam)
     for (BaseNetL& B : nets_) {  // LSTM gate biases b_ih + b_hh, once per parameter change instead of two launches per LSTM and forward
         LSTMMod& M = B.lstm;
         const int G = 4 * M.hid;
@@ -396,115 +394,80 @@ void Model::set_option(const std::string& name, int value) {
     else throw Error(-2, "unknown option: " + name);
 }
 
-// Winograd-domain copies (G g G^T) of every 3x3 stride-1 weight; with_dgrad: also of the flipped/transposed
-// weights the data gradient convolves with (train.hip keeps those in wt_of, refreshed once per step).
-void Model::refresh_wino(bool with_dgrad) {
-    if (!wino_arena) {
-        size_t total = 0;
-        for (Conv* L : wino_list) total += (size_t)L->Cin * 16 * L->CoutPad;
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&wino_arena), total * sizeof(float)));
-        size_t off = 0;
-        for (Conv* L : wino_list) { L->wino = wino_arena + off; off += (size_t)L->Cin * 16 * L->CoutPad; }
+// One allocation for form `f` of `convs`: total -> hipMalloc -> offsets into the layers' records.  Once per store and form; wt is zero
+// filled here and never again (the flip kernel does not write its ci >= Cin padding).
+void Model::hold_form(FormId f, const std::vector<Conv*>& convs, Wino6Want w6, FormStore& s) {
+    if (s.arena[f]) return;
+    auto room = [&](const Conv* L) {
+        const FormSpec sp = form_spec(f, *L, mfma_mode, w6);
+        return sp.held ? (sp.bytes + 255) & ~size_t(255) : size_t(0);
+    };
+    size_t total = 0;
+    for (const Conv* L : convs) total += room(L);
+    VR_HIP(hipMalloc(reinterpret_cast<void**>(&s.arena[f]), total ? total : 16));
+    if (f == F_WT) {
+        VR_HIP(hipMemset(s.arena[f], 0, total));
+        VR_HIP(hipStreamSynchronize(nullptr));                // (the fill runs on the NULL stream, the transforms on the handle's)
     }
-    {
-        std::vector<WinoWDesc> d;
-        for (Conv* L : wino_list) d.push_back(WinoWDesc{L->w->dev, L->wino, L->Cin, L->CoutPad});
-        run_wino_batch(wb_fwd, d, false);
+    size_t off = 0;
+    for (Conv* L : convs)
+        if (room(L)) { L->forms.p[f] = s.arena[f] + off; off += room(L); }
+}
+
+// Form `f` of every conv that holds it and whose image mfma_mode reads: one batched launch from the form's descriptor table, or
+// (`single`, the hooks) one single-layer launch per conv where such a launcher exists.  The table is made when the mode changes: the
+// pointers and dims of a held form never do.
+void Model::fill_form(FormId f, const std::vector<Conv*>& convs, Wino6Want w6, FormStore& s, bool single) {
+    FormStore::Tables& t = s.tbl[f];
+    const bool split6 = f == F_WINO6 || f == F_WINOT6, planes = f == F_X3W || f == F_X3T;
+    if (t.mode != mfma_mode) {
+        std::vector<WinoWDesc> wd;
+        std::vector<X3WDesc> xd;
+        std::vector<FlipDesc> fd;
+        std::vector<S2WDesc> sd;
+        for (Conv* L : convs) {
+            const FormSpec sp = form_spec(f, *L, mfma_mode, w6);
+            if (!sp.held || !sp.live) continue;
+            const float* src = sp.from_wt ? L->forms.f32(F_WT) : L->w->dev;
+            void* dst = L->forms.p[f];
+            if (f == F_WT) fd.push_back(FlipDesc{src, static_cast<float*>(dst), L->Cin, L->Cout, sp.KK, sp.pad, L->CoutPad});
+            else if (f == F_S2W) sd.push_back(S2WDesc{src, static_cast<float*>(dst), L->Cin, L->Cout, L->CoutPad, sp.pad});
+            else if (!single) { if (planes) xd.push_back(X3WDesc{src, dst, sp.rows, sp.KK, sp.pad}); else wd.push_back(WinoWDesc{src, dst, sp.rows, sp.pad}); }
+            else if (planes && mfma_mode == 3) launch_x3h_weights(src, dst, sp.rows, sp.KK, sp.pad, stream);
+            else if (planes) launch_x3_weights(src, dst, sp.rows, sp.KK, sp.pad, stream);
+            else if (split6) launch_wino_weights6(src, dst, sp.rows, sp.pad, stream);
+            else launch_wino_weights(src, static_cast<float*>(dst), sp.rows, sp.pad, stream);
+        }
+        t.n = (int)(fd.size() + sd.size() + wd.size() + xd.size());
+        if (!fd.empty()) t.flip.upload(fd, stream);
+        if (!sd.empty()) { t.s2.upload(sd, stream); t.max_elems = s2w_batch_max_elems(sd); }
+        if (!wd.empty()) { t.wino.upload(wd, stream); t.max_elems = wino_batch_max_elems(wd, split6); }
+        if (!xd.empty()) { t.x3.upload(xd, stream); t.max_elems = x3_batch_max_elems(xd); t.max_cout_pad = x3_batch_max_cout_pad(xd); }
+        t.mode = mfma_mode;
     }
-    auto cin_pad = [](const Conv* L) { return (L->Cin + 31) / 32 * 32; };
+    if (!t.n) return;
+    if (f == F_WT) launch_flip_transpose(t.flip.dev, t.n, stream);
+    else if (f == F_S2W) launch_s2_class_weights(t.s2.dev, t.n, t.max_elems, stream);
+    else if (!planes) launch_wino_weights_batched(t.wino.dev, t.n, t.max_elems, split6, stream);
+    else if (mfma_mode == 3) launch_x3h_weights_batched(t.x3.dev, t.n, t.max_elems, t.max_cout_pad, stream);
+    else launch_x3_weights_batched(t.x3.dev, t.n, t.max_elems, stream);
+}
+
+// The handle's refresh: the forward forms of the current mfma_mode; with_dgrad (once per train step): first wt and the parity classes,
+// then the forms made from wt.  A form is allocated when a refresh first fills it.
+void Model::refresh_forms(bool with_dgrad) {
     static const bool x3_on = !(getenv("VR_CONV_X3") && atoi(getenv("VR_CONV_X3")) == 0);
-    if (x3_mode() && x3_on) {
-        // split-bf16 (mode 2) / split-fp16 (mode 3) copies of the DIRECT weights (conv_x3.hip takes every 3x3 stride-1 launch wide enough for its tiles)
-        // (x3d_list: the dilated 3x3 and 1x1 branch convs of the ASPP modules, conv_x3d.hip -- fp16 planes only, filled in mode 3)
-        if (!x3_arena) {
-            size_t total = 0;
-            for (Conv* L : wino_list) total += x3_weights_bytes(L->Cin, 9, L->CoutPad);
-            for (Conv* L : x3d_list) total += x3_weights_bytes(L->Cin, L->KS * L->KS, L->CoutPad);
-            for (Conv* L : x3s_list) total += x3_weights_bytes(L->Cin, 9, L->CoutPad);
-            VR_HIP(hipMalloc(reinterpret_cast<void**>(&x3_arena), total ? total : 16));
-            size_t off = 0;
-            for (Conv* L : wino_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, 9, L->CoutPad); }
-            for (Conv* L : x3d_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, L->KS * L->KS, L->CoutPad); }
-            for (Conv* L : x3s_list) { L->x3w = x3_arena + off; off += x3_weights_bytes(L->Cin, 9, L->CoutPad); }
-        }
-        {
-            std::vector<X3WDesc> d;
-            for (Conv* L : wino_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, 9, L->CoutPad});
-            if (mfma_mode == 3) {
-                for (Conv* L : x3d_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, L->KS * L->KS, L->CoutPad});
-                for (Conv* L : x3s_list) d.push_back(X3WDesc{L->w->dev, L->x3w, L->Cin, 9, L->CoutPad});
-            }
-            run_x3_batch(xb_fwd, d);
-        }
-        if (with_dgrad) {
-            if (!x3t_arena) {
-                size_t total = 0;
-                for (Conv* L : wino_list) total += x3_weights_bytes(L->Cout, 9, cin_pad(L));
-                for (Conv* L : x3d_list) total += x3_weights_bytes(L->Cout, L->KS * L->KS, cin_pad(L));
-                VR_HIP(hipMalloc(reinterpret_cast<void**>(&x3t_arena), total ? total : 16));
-                size_t off = 0;
-                for (Conv* L : wino_list) { x3t_of[L->w] = x3t_arena + off; off += x3_weights_bytes(L->Cout, 9, cin_pad(L)); }
-                for (Conv* L : x3d_list) { x3dt_of[L->w] = x3t_arena + off; off += x3_weights_bytes(L->Cout, L->KS * L->KS, cin_pad(L)); }
-            }
-            std::vector<X3WDesc> d;
-            for (Conv* L : wino_list) {
-                auto it = wt_of.find(L->w);
-                if (it != wt_of.end()) d.push_back(X3WDesc{it->second, x3t_of[L->w], L->Cout, 9, cin_pad(L)});
-            }
-            if (mfma_mode == 3)
-                for (Conv* L : x3d_list) {
-                    auto it = wt_of.find(L->w);
-                    if (it != wt_of.end()) d.push_back(X3WDesc{it->second, x3dt_of[L->w], L->Cout, L->KS * L->KS, cin_pad(L)});
-                }
-            run_x3_batch(xb_bwd, d);
-        }
+    // split-bf16 (mode 2) / split-fp16 (mode 3) planes of the direct weights; VR_CONV_X3=0 in mode 2: bf16 planes of U instead, for the
+    // launches that can take the split kernel -- the 64-cout Winograd variant only (conv_wino.hip)
+    const bool x3 = x3_mode() && x3_on, six = mfma_mode == 2 && !x3_on;
+    bool fill[F_COUNT] = {};
+    fill[F_WINO] = true; fill[F_WINO6] = six; fill[F_X3W] = x3;
+    fill[F_WT] = fill[F_S2W] = fill[F_WINOT] = with_dgrad; fill[F_WINOT6] = with_dgrad && six; fill[F_X3T] = with_dgrad && x3;
+    for (FormId f : {F_WT, F_S2W, F_WINO, F_WINO6, F_X3W, F_WINOT, F_WINOT6, F_X3T}) {
+        if (!fill[f]) continue;
+        hold_form(f, conv_layers(), W6_PAD64, form_store);
+        fill_form(f, conv_layers(), W6_PAD64, form_store, false);
     }
-    if (mfma_mode == 2 && !x3_on) {
-        // bf16-plane copies for the launches that can take the split kernel: the 64-cout Winograd variant only (conv_wino.hip)
-        auto fwd6 = [](const Conv* L) { return L->CoutPad % 64 == 0; };
-        auto bwd6 = [&](const Conv* L) { return cin_pad(L) % 64 == 0; };
-        if (!wino6_arena) {
-            size_t total = 0;
-            for (Conv* L : wino_list) if (fwd6(L)) total += wino_weights6_bytes(L->Cin, L->CoutPad);
-            VR_HIP(hipMalloc(reinterpret_cast<void**>(&wino6_arena), total ? total : 16));
-            size_t off = 0;
-            for (Conv* L : wino_list) if (fwd6(L)) { L->wino6 = wino6_arena + off; off += wino_weights6_bytes(L->Cin, L->CoutPad); }
-        }
-        {
-            std::vector<WinoWDesc> d;
-            for (Conv* L : wino_list) if (fwd6(L)) d.push_back(WinoWDesc{L->w->dev, L->wino6, L->Cin, L->CoutPad});
-            run_wino_batch(wb_fwd6, d, true);
-        }
-        if (with_dgrad) {
-            if (!winot6_arena) {
-                size_t total = 0;
-                for (Conv* L : wino_list) if (bwd6(L)) total += wino_weights6_bytes(L->Cout, cin_pad(L));
-                VR_HIP(hipMalloc(reinterpret_cast<void**>(&winot6_arena), total ? total : 16));
-                size_t off = 0;
-                for (Conv* L : wino_list) if (bwd6(L)) { winot6_of[L->w] = winot6_arena + off; off += wino_weights6_bytes(L->Cout, cin_pad(L)); }
-            }
-            std::vector<WinoWDesc> d;
-            for (Conv* L : wino_list) {
-                auto it = wt_of.find(L->w);
-                if (bwd6(L) && it != wt_of.end()) d.push_back(WinoWDesc{it->second, winot6_of[L->w], L->Cout, cin_pad(L)});
-            }
-            run_wino_batch(wb_bwd6, d, true);
-        }
-    }
-    if (!with_dgrad) return;
-    if (!winot_arena) {
-        size_t total = 0;
-        for (Conv* L : wino_list) total += (size_t)L->Cout * 16 * cin_pad(L);
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&winot_arena), total * sizeof(float)));
-        size_t off = 0;
-        for (Conv* L : wino_list) { winot_of[L->w] = winot_arena + off; off += (size_t)L->Cout * 16 * cin_pad(L); }
-    }
-    std::vector<WinoWDesc> d;
-    for (Conv* L : wino_list) {
-        auto it = wt_of.find(L->w);
-        if (it != wt_of.end()) d.push_back(WinoWDesc{it->second, winot_of[L->w], L->Cout, cin_pad(L)});
-    }
-    run_wino_batch(wb_bwd, d, false);
 }
 
 long long Model::x3_batch_max_elems(const std::vector<X3WDesc>& descs) {
@@ -529,43 +492,6 @@ long long Model::s2w_batch_max_elems(const std::vector<S2WDesc>& descs) {
     long long m = 0;
     for (const S2WDesc& e : descs) m = std::max(m, (long long)4 * e.Cout * 9 * e.CinPad);
     return m;
-}
-
-void Model::run_x3_batch(X3Batch& b, std::vector<X3WDesc>& descs) {
-    if (descs.empty()) return;
-    bool same = b.dev && b.host.size() == descs.size();
-    for (size_t i = 0; same && i < descs.size(); ++i)
-        same = b.host[i].w == descs[i].w && b.host[i].o == descs[i].o && b.host[i].Cin == descs[i].Cin && b.host[i].CoutPad == descs[i].CoutPad;
-    if (!same) {
-        VR_HIP(hipStreamSynchronize(stream));
-        if (b.dev) VR_HIP(hipFree(b.dev));
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&b.dev), descs.size() * sizeof(X3WDesc)));
-        VR_HIP(hipMemcpy(b.dev, descs.data(), descs.size() * sizeof(X3WDesc), hipMemcpyHostToDevice));
-        b.host = descs;
-        b.max_elems = x3_batch_max_elems(descs);
-    }
-    if (mfma_mode == 3) {
-        launch_x3h_weights_batched(b.dev, (int)descs.size(), b.max_elems, x3_batch_max_cout_pad(descs), stream);
-    } else {
-        launch_x3_weights_batched(b.dev, (int)descs.size(), b.max_elems, stream);
-    }
-}
-
-// One launch for a whole descriptor table; the device copy is re-uploaded only when the table changed.
-void Model::run_wino_batch(WinoBatch& b, std::vector<WinoWDesc>& descs, bool split6) {
-    if (descs.empty()) return;
-    bool same = b.dev && b.host.size() == descs.size();
-    for (size_t i = 0; same && i < descs.size(); ++i)
-        same = b.host[i].w == descs[i].w && b.host[i].u == descs[i].u && b.host[i].Cin == descs[i].Cin && b.host[i].CoutPad == descs[i].CoutPad;
-    if (!same) {
-        VR_HIP(hipStreamSynchronize(stream));                       // (a launch may still read the old table)
-        if (b.dev) VR_HIP(hipFree(b.dev));
-        VR_HIP(hipMalloc(reinterpret_cast<void**>(&b.dev), descs.size() * sizeof(WinoWDesc)));
-        VR_HIP(hipMemcpy(b.dev, descs.data(), descs.size() * sizeof(WinoWDesc), hipMemcpyHostToDevice));
-        b.host = descs;
-        b.max_elems = wino_batch_max_elems(descs, split6);
-    }
-    launch_wino_weights_batched(b.dev, (int)descs.size(), b.max_elems, split6, stream);
 }
 
 // =====================================================================================================
@@ -803,7 +729,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         for (const SrcSpec& sp : srcs) any_up = any_up || sp.up;
         if (any_up) {
             ConvArgs probe = a;
-            probe.x3w = x3_mode() ? L.x3w : nullptr;
+            select_fwd_forms(probe, L.forms, form_select(), probe.Win, L.stride);
             probe.bf16 = mfma_mode;
             X3Tile xt;
             if (!x3_pick(probe, ConvShape{L.KS, L.stride, L.dh, L.dw}, &xt)) {
@@ -827,11 +753,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
     // the raw tensor + pending affine: the batch statistics only exist after the whole conv has run.
     const bool fuse_epi = !training && L.bn != nullptr;
     if (fuse_epi) { a.epi = L.bn->affine; a.epi_slope = L.slope; }
-    a.wino = (training && !train_wino) ? nullptr : L.wino;   // (null until the first refresh_wino())
-    a.wino6 = (a.wino && mfma_mode == 2) ? L.wino6 : nullptr;
-    a.x3w = (x3_mode() && !(training && !train_wino)) ? L.x3w : nullptr;
-    if (!x3d_mode && a.Win == 16) a.x3w = nullptr;          // (16-column layers: only conv_x3d.hip reads the planes)
-    if (L.stride == 2 && (training || !x3s_mode)) a.x3w = nullptr;   // (stride-2 layers: conv_x3s.hip is eval only; option conv_x3s 0: conv_dma.hip)
+    select_fwd_forms(a, L.forms, form_select(), a.Win, L.stride);
     a.bf16 = mfma_mode;
     int wcols = a.Wout;                                      // output columns the launch computes
     if (conv_w_hi > 0 && !training && mfma_mode == 3 && !batch_as_h && !conv_sink) {
@@ -1399,7 +1321,7 @@ void Model::forward_api(const float* x, bool x_on_device, int B, int T, int mode
     // and updates batch statistics, Dropout2d is live, but no tape and no gradient buffers are kept.
     struct FwdOnly { Model* m; ~FwdOnly() { m->fwd_only = false; m->dropout_dev = nullptr; } } fwd_scope{this};
     fwd_only = training;
-    if (training) refresh_wino(false);      // before planning: the kernel choice (and its partial-statistics layout) depends on them
+    if (training) refresh_forms(false);     // before planning: the kernel choice (and its partial-statistics layout) depends on them
     if (!training) fold_eval_affines();     // (eval: the bf16-plane weight tables decide conv_x3 vs the materialised-upsample plan)
     plan_and_reserve(B, T, (in_floats + pack_floats + out_floats) * sizeof(float) + 1024 * E);
     if (training) prepare_dropout(B);
@@ -2467,40 +2389,28 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
 // unit-test hooks: the weight forms of a single conv launch
 // =====================================================================================================
 void Model::debug_weight_forms(const float* dw_, int Cin, int KS, int stride, int dh, int dw, int CoutPad, int Win, bool want_wino,
-                               ConvArgs& a, DebugWeightForms& f) {
-    const int KK = KS * KS;
-    if (mfma_mode == 3 && KS == 3 && stride == 2 && dh == 1 && dw == 1) {
-        // conv_x3s.hip's layers (3x3 stride 2): fp16-plane weights, with or without the flag -- no other weight form exists for them
-        if (x3s_mode) {
-            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
-            launch_x3h_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
-            a.x3w = f.x3w;
-        }
-    } else if (want_wino && mfma_mode == 3 && stride == 1 && (KS == 1 || dh > 1)) {
-        // conv_x3d.hip's layers (dilated 3x3, 1x1 at 16 columns): fp16-plane weights only
-        VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, KK, CoutPad)));
-        launch_x3h_weights(dw_, f.x3w, Cin, KK, CoutPad, stream);
-        a.x3w = f.x3w;
-    } else if (want_wino) {
-        VR_CHECK(KS == 3 && stride == 1 && dh == 1 && dw == 1, -2, "Winograd weights exist for 3x3 stride-1 convs only");
-        VR_HIP(hipMalloc(&f.wino, (size_t)Cin * 16 * CoutPad * 4));
-        launch_wino_weights(dw_, f.wino, Cin, CoutPad, stream);
-        a.wino = f.wino;
-        if (mfma_mode == 2) {
-            VR_HIP(hipMalloc(&f.wino6, wino_weights6_bytes(Cin, CoutPad)));
-            launch_wino_weights6(dw_, f.wino6, Cin, CoutPad, stream);
-            a.wino6 = f.wino6;
-            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
-            launch_x3_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
-            a.x3w = f.x3w;
-        }
-        if (mfma_mode == 3) {
-            VR_HIP(hipMalloc(&f.x3w, x3_weights_bytes(Cin, 9, CoutPad)));
-            launch_x3h_weights(dw_, f.x3w, Cin, 9, CoutPad, stream);
-            a.x3w = f.x3w;
-        }
+                               ConvArgs& a, LocalConv& lc) {
+    Conv& L = lc.L;
+    L.name = "debug"; L.Cin = Cin; L.Cout = L.CoutPad = CoutPad; L.KS = KS;    // (no forward form depends on Cout)
+    L.stride = stride; L.dh = dh; L.dw = dw;
+    L.cls = form_class(KS, stride, dh, dw, true);            // (the hook takes any 1x1 stride-1 conv for a conv_x3d layer)
+    lc.P.dev = const_cast<float*>(dw_);
+    // Where the hook differs from the handle: a stride-2 layer gets its planes under option conv_x3s only (and with or without the
+    // flag -- no other form exists for it), every other layer its forms only when asked; the bf16 planes of U exist for every plain
+    // layer in mfma_mode 2.
+    const bool x3dl = mfma_mode == 3 && (L.cls == FC_X3D || L.cls == FC_S2);
+    if (want_wino && !x3dl) VR_CHECK(L.cls == FC_PLAIN3, -2, "Winograd weights exist for 3x3 stride-1 convs only");
+    const bool made = L.cls == FC_S2 ? x3s_mode != 0 : want_wino;
+    const std::vector<Conv*> one{&L};
+    for (FormId f : {F_WINO, F_WINO6, F_X3W}) {
+        const FormSpec sp = form_spec(f, L, mfma_mode, W6_ALL);
+        if (!(made && sp.held && sp.live)) continue;
+        hold_form(f, one, W6_ALL, lc.store);
+        fill_form(f, one, W6_ALL, lc.store, true);
     }
-    if (!x3d_mode && Win == 16) a.x3w = nullptr;            // option conv_x3d 0: the fp32-pipe kernels for the 16-column layers
+    FormSelect sel = form_select();
+    sel.training = false;                                    // (the hook's launch reads what was made for it, as an eval launch does)
+    select_fwd_forms(a, L.forms, sel, Win, stride);
 }
 
 // =====================================================================================================
@@ -2539,7 +2449,7 @@ void Model::debug_conv(const float* x, int N, int Cin, int H, int W, const float
     a.w = dw_; a.bias = dbias; a.Cout = Cout; a.CoutPad = CoutPad;
     if (epi && daff) { a.epi = daff; a.epi_slope = slope; }
     a.bf16 = mfma_mode;
-    DebugWeightForms wf;
+    LocalConv wf;
     debug_weight_forms(dw_, Cin, KS, stride, dh, dw, CoutPad, Win, want_wino, a, wf);
     a.dst[0] = ConvDst{dout, (long long)Hout * Wout * Cout, (long long)Hout * Wout, (long long)Wout, 0};
     a.d1 = a.d2 = 1 << 30;

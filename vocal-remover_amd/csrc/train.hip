@@ -26,10 +26,9 @@ void Model::for_each_conv(F&& f) {
     f(tail1); f(tail2);
 }
 
-std::vector<Conv*> Model::conv_layers() {
-    std::vector<Conv*> v;
-    for_each_conv([&](Conv& L) { v.push_back(&L); });
-    return v;
+const std::vector<Conv*>& Model::conv_layers() {
+    if (convs_.empty()) for_each_conv([&](Conv& L) { convs_.push_back(&L); });
+    return convs_;
 }
 
 void Model::ensure_train_state() {
@@ -40,45 +39,10 @@ void Model::ensure_train_state() {
     VR_HIP(hipMemset(g_arena, 0, p_floats * sizeof(float)));
     VR_HIP(hipMemset(m_arena, 0, p_floats * sizeof(float)));
     VR_HIP(hipMemset(v_arena, 0, p_floats * sizeof(float)));
-    // flipped + transposed copies of the conv weights for the data-gradient launches
-    size_t off = 0;
-    std::vector<std::pair<Conv*, size_t>> slots;
-    for_each_conv([&](Conv& L) {
-        const size_t n = (size_t)L.Cout * L.KS * L.KS * round_up32(L.Cin);
-        slots.push_back({&L, off});
-        off += (n + 63) & ~size_t(63);
-    });
-    wt_floats = off;
-    VR_HIP(hipMalloc(&wt_arena, wt_floats * sizeof(float)));
-    VR_HIP(hipMemset(wt_arena, 0, wt_floats * sizeof(float)));
-    std::vector<FlipDesc> descs;
-    for (auto& sl : slots) {
-        Conv& L = *sl.first;
-        wt_of[L.w] = wt_arena + sl.second;
-        descs.push_back(FlipDesc{L.w->dev, wt_arena + sl.second, L.Cin, L.Cout, L.KS * L.KS, round_up32(L.Cin), L.CoutPad});
-    }
-    {   // stride-2 3x3 convs: four parity-class weight tensors each (refreshed per step next to the flip)
-        size_t tot = 0;
-        for_each_conv([&](Conv& L) {
-            if (L.KS == 3 && L.stride == 2 && L.dh == 1 && L.dw == 1) { s2_list.push_back(&L); tot += (size_t)4 * L.Cout * 9 * round_up32(L.Cin); }
-        });
-        if (tot) {
-            VR_HIP(hipMalloc(&s2w_arena, tot * sizeof(float)));
-            size_t o = 0;
-            std::vector<S2WDesc> sd;
-            for (Conv* L : s2_list) {
-                s2w_of[L->w] = s2w_arena + o;
-                sd.push_back(S2WDesc{L->w->dev, s2w_arena + o, L->Cin, L->Cout, L->CoutPad, round_up32(L->Cin)});
-                o += (size_t)4 * L->Cout * 9 * round_up32(L->Cin);
-            }
-            s2w_max = s2w_batch_max_elems(sd);
-            VR_HIP(hipMalloc(reinterpret_cast<void**>(&d_s2w), sd.size() * sizeof(S2WDesc)));
-            VR_HIP(hipMemcpy(d_s2w, sd.data(), sd.size() * sizeof(S2WDesc), hipMemcpyHostToDevice));
-        }
-    }
-    n_flip = (int)descs.size();
-    VR_HIP(hipMalloc(&d_flip, descs.size() * sizeof(FlipDesc)));
-    VR_HIP(hipMemcpy(d_flip, descs.data(), descs.size() * sizeof(FlipDesc), hipMemcpyHostToDevice));
+    // flipped + transposed copies of the conv weights for the data-gradient launches, and the four parity-class weight tensors of each
+    // stride-2 3x3 conv (both refreshed once per step)
+    hold_form(F_WT, conv_layers(), W6_PAD64, form_store);
+    hold_form(F_S2W, conv_layers(), W6_PAD64, form_store);
 }
 
 void Model::zero_grad_api() {
@@ -223,20 +187,7 @@ int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
     if (r.batch_as_h) { d.src[0].sH = d.src[0].sN; d.src[0].sN = 0; d.src[0].H = N; }
     d.src[0].zins = (L.stride == 2) ? 1 : 0;
     d.c1 = d.c2 = L.Cout; d.Cin = L.Cout;
-    d.w = dry ? nullptr : wt_of[L.w];
-    {
-        auto it = winot_of.find(L.w);
-        d.wino = (!dry && train_wino && it != winot_of.end()) ? it->second : nullptr;
-        auto it6 = winot6_of.find(L.w);
-        d.wino6 = (d.wino && mfma_mode == 2 && it6 != winot6_of.end()) ? it6->second : nullptr;
-    }
-    {
-        auto itx = x3t_of.find(L.w);
-        d.x3w = (!dry && train_wino && x3_mode() && itx != x3t_of.end()) ? itx->second : nullptr;
-        auto itd = x3dt_of.find(L.w);                     // dilated 3x3 / 1x1 ASPP branches (conv_x3d.hip)
-        if (!dry && train_wino && mfma_mode == 3 && itd != x3dt_of.end()) d.x3w = itd->second;
-        if (!x3d_mode && f.Win == 16) d.x3w = nullptr;
-    }
+    select_dgrad_forms(d, L.forms, L.cls, form_select(), f.Win);
     d.bias = nullptr;
     d.bf16 = mfma_mode;
     d.Cout = L.Cin; d.CoutPad = round_up32(L.Cin);
@@ -273,8 +224,8 @@ int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
     // zero-inserted gradient (36), when the LDS-DMA kernel covers the shape.
     {
         static const bool s2_classes = !getenv("VR_NO_S2_CLASSES");
-        auto it = s2w_of.find(L.w);
-        bool ok = s2_classes && L.stride == 2 && L.KS == 3 && it != s2w_of.end() && posts.empty() && !r.batch_as_h;
+        const float* s2w = L.forms.f32(F_S2W);
+        bool ok = s2_classes && L.stride == 2 && L.KS == 3 && s2w && posts.empty() && !r.batch_as_h;
         if (ok) {
             ConvArgs c = d;
             c.src[0].zins = 0;
@@ -285,7 +236,7 @@ int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
             {
                 ConvArgs k = c;
                 k.Hout = (f.Hin + 1) / 2; k.Wout = (f.Win + 1) / 2;
-                k.w = it->second; k.wino = nullptr; k.wino6 = nullptr; k.x3w = nullptr;
+                k.w = s2w; k.wino = nullptr; k.wino6 = nullptr; k.x3w = nullptr;
                 k.s2_cls_stride = (long long)cls_stride; k.s2_H = f.Hin; k.s2_W = f.Win;
                 if (s2d_fused_eligible(k)) {
                     record_begin(0, 2.0 * N * (double)f.Hout * f.Wout * (double)L.Cout * L.Cin * L.KS * L.KS);
@@ -305,7 +256,7 @@ int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
                 ConvArgs& k = cls_args[cls];
                 k = c;
                 k.Hout = (f.Hin - ph + 1) / 2; k.Wout = (f.Win - pw + 1) / 2;
-                k.w = it->second + cls * cls_stride;
+                k.w = s2w + cls * cls_stride;
                 k.wino = nullptr; k.wino6 = nullptr; k.x3w = nullptr;
                 int tm = 0;
                 for (int th = 0; th < 3; ++th)
@@ -535,9 +486,7 @@ void Model::wait_gs_clear() {
 // copies of both, once per step (before the planning dry run: the kernel choice, hence the partial-statistics layout, depends on them)
 void Model::refresh_train_weights() {
     ensure_train_state();
-    launch_flip_transpose(d_flip, n_flip, stream);
-    launch_s2_class_weights(d_s2w, (int)s2_list.size(), s2w_max, stream);
-    refresh_wino(true);
+    refresh_forms(true);
 }
 
 void Model::train_fwd_bwd_api(const float* X, const float* Y, bool on_dev, int B, int T, int accumulation_steps,
@@ -909,52 +858,17 @@ void Model::get_grad(const std::string& key, float* host, int64_t cap_bytes) {
 // =====================================================================================================
 namespace vr {
 
-Model::DebugDgradForms::~DebugDgradForms() {
-    if (m && P) {
-        m->wt_of.erase(P); m->s2w_of.erase(P); m->winot_of.erase(P); m->x3t_of.erase(P); m->x3dt_of.erase(P);
-    }
-    (void)hipFree(wt); (void)hipFree(winot); (void)hipFree(s2w); (void)hipFree(x3t); (void)hipFree(flip_desc); (void)hipFree(s2_desc);
-}
-
-void Model::debug_dgrad_weight_forms(const Param& P, int KS, int stride, int dh, int dw, DebugDgradForms& f) {
-    const int Cin = P.Cin, Cout = P.Cout, KK = KS * KS, CoutPad = P.CoutPad, CinPad = round_up32(Cin);
-    f.m = this; f.P = &P;
-    VR_HIP(hipMalloc(&f.wt, (size_t)Cout * KK * CinPad * 4));
-    VR_HIP(hipMemset(f.wt, 0, (size_t)Cout * KK * CinPad * 4));
-    VR_HIP(hipStreamSynchronize(nullptr));                    // (the fill runs on the NULL stream, the transforms below on the handle's)
-    wt_of[&P] = f.wt;
-    const FlipDesc fd{P.dev, f.wt, Cin, Cout, KK, CinPad, CoutPad};
-    VR_HIP(hipMalloc(&f.flip_desc, sizeof(FlipDesc)));
-    VR_HIP(hipMemcpy(f.flip_desc, &fd, sizeof(FlipDesc), hipMemcpyHostToDevice));
-    launch_flip_transpose(static_cast<const FlipDesc*>(f.flip_desc), 1, stream);
-    // 3x3 stride-1: the data gradient takes the same kernels as in a train step (Winograd / split-bf16 direct over the flipped weights)
-    if (KS == 3 && stride == 1 && dh == 1 && dw == 1 && train_wino) {
-        VR_HIP(hipMalloc(&f.winot, (size_t)Cout * 16 * CinPad * sizeof(float)));
-        launch_wino_weights(f.wt, f.winot, Cout, CinPad, stream);
-        winot_of[&P] = f.winot;
-        if (mfma_mode == 2) {
-            VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, 9, CinPad)));
-            launch_x3_weights(f.wt, f.x3t, Cout, 9, CinPad, stream);
-            x3t_of[&P] = f.x3t;
-        }
-        if (mfma_mode == 3) {
-            VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, 9, CinPad)));
-            launch_x3h_weights(f.wt, f.x3t, Cout, 9, CinPad, stream);
-            x3t_of[&P] = f.x3t;
-        }
-    }
-    if (stride == 1 && (KS == 1 || dh > 1) && train_wino && mfma_mode == 3) {      // conv_x3d.hip's layers (16-column images)
-        VR_HIP(hipMalloc(&f.x3t, x3_weights_bytes(Cout, KK, CinPad)));
-        launch_x3h_weights(f.wt, f.x3t, Cout, KK, CinPad, stream);
-        x3dt_of[&P] = f.x3t;
-    }
-    if (KS == 3 && stride == 2 && dh == 1 && dw == 1) {       // stride-2 3x3: also exercise the parity-class data gradient
-        VR_HIP(hipMalloc(&f.s2w, (size_t)4 * Cout * 9 * CinPad * sizeof(float)));
-        const S2WDesc sd{P.dev, f.s2w, Cin, Cout, CoutPad, CinPad};
-        VR_HIP(hipMalloc(&f.s2_desc, sizeof(S2WDesc)));
-        VR_HIP(hipMemcpy(f.s2_desc, &sd, sizeof(S2WDesc), hipMemcpyHostToDevice));
-        launch_s2_class_weights(static_cast<const S2WDesc*>(f.s2_desc), 1, 4LL * Cout * 9 * CinPad, stream);
-        s2w_of[&P] = f.s2w;
+void Model::debug_dgrad_weight_forms(LocalConv& lc) {
+    Conv& L = lc.L;
+    L.cls = form_class(L.KS, L.stride, L.dh, L.dw, true);    // (the hook takes any 1x1 stride-1 conv for a conv_x3d layer)
+    // Where the hook differs from the handle: the Winograd and plane forms of wt are made only under option train_winograd (the handle
+    // makes them always and masks them at the launch), the bf16 planes of its U never.
+    const std::vector<Conv*> one{&L};
+    for (FormId f : {F_WT, F_S2W, F_WINOT, F_WINOT6, F_X3T}) {
+        const FormSpec sp = form_spec(f, L, mfma_mode, W6_NONE);
+        if (!(sp.held && sp.live && (f == F_WT || f == F_S2W || train_wino))) continue;
+        hold_form(f, one, W6_NONE, lc.store);
+        fill_form(f, one, W6_NONE, lc.store, true);
     }
 }
 
@@ -964,12 +878,12 @@ void Model::debug_conv_bwd(const float* x, int N, int Cin, int H, int W, const f
     DeviceGuard dev_guard(device);
     ensure_train_state();
     const int KK = KS * KS, CoutPad = (Cout + 31) / 32 * 32;
-    Conv L;
+    LocalConv lc;
+    Conv& L = lc.L;
+    Param& P = lc.P;
     L.name = "debug"; L.Cin = Cin; L.Cout = Cout; L.CoutPad = CoutPad; L.KS = KS; L.stride = stride; L.dh = dh; L.dw = dw;
     L.pad_h = KS == 1 ? 0 : dh; L.pad_w = KS == 1 ? 0 : dw; L.bn = nullptr; L.slope = 1.f;
-    Param P;
     P.kind = PK_CONV; P.Cin = Cin; P.Cout = Cout; P.KK = KK; P.CoutPad = CoutPad;
-    L.w = &P;
     const int Hin = up ? 2 * H : H, Win = up ? 2 * W : W;
     const int Hout = (Hin + 2 * L.pad_h - dh * (KS - 1) - 1) / stride + 1, Wout = (Win + 2 * L.pad_w - dw * (KS - 1) - 1) / stride + 1;
     std::vector<float> wk((size_t)Cin * KK * CoutPad, 0.f);
@@ -986,8 +900,7 @@ void Model::debug_conv_bwd(const float* x, int N, int Cin, int H, int W, const f
     VR_HIP(hipMemcpy(dzd, dz, xout * 4, hipMemcpyHostToDevice));
     if (aff) { VR_HIP(hipMalloc(&daff, (size_t)Cin * 8)); VR_HIP(hipMemcpy(daff, aff, (size_t)Cin * 8, hipMemcpyHostToDevice)); }
     P.dev = dwk; P.grad_override = dgw;
-    DebugDgradForms forms;
-    debug_dgrad_weight_forms(P, KS, stride, dh, dw, forms);
+    debug_dgrad_weight_forms(lc);
     Tensor t;
     t.p = dx; t.g = dgx; t.N = N; t.C = Cin; t.H = H; t.W = W; t.sH = W; t.sC = (long long)H * W; t.sN = t.sC * Cin;
     t.aff0 = daff; t.slope = slope;
