@@ -108,6 +108,11 @@ int vr_set_mode(vr_handle h, int training);
  * "conv_x3s" ("mfma_mode" 3 only, eval): the encoders' 3x3 stride-2 convs (Encoder.conv1, lib/layers.py:33) with at least 32 output
  *   columns and more than 16 input channels on the fp16 matrix pipe: 1 (default, also -1; VR_CONV_X3S=0 makes 0 the default),
  *   0 the fp32-pipe kernel for them.
+ * "aspp_pool_fused" (eval, default 1): where the four ASPP branch convs of a module go out as one launch ("conv_x3d" 2), the module's
+ *   pooled branch (the mean over frequency and its 1x1 Conv2DBNActiv, lib/layers.py:72-73) is a fifth part of that launch; 0 = its two
+ *   launches of before.
+ * "lstm_gemm" (eval, default 1, every "mfma_mode"): the LSTM input projection and the Linear behind the LSTM (lib/layers.py:117-121) as
+ *   rows_gemm launches (fp32 matrix instructions); 0 = the one-row 1x1 conv launches of before.
  * "complex_train" (default 0; VR_CREATE_COMPLEX handles only, VR_ERR_BAD_ARGUMENT on a magnitude handle): 1 = the training entry points
  *   take this complex-mask handle (see vr_create_ex); 0 = they refuse it again.  Eval-mode calls are the same either way.   */
 int vr_set_option(vr_handle h, const char* name, int value);

@@ -13,7 +13,8 @@
 //     (TH + 2 DH) x 16 real slots (rows outside the image: zeros again) and the matrix phase reads every tap at a compile-time offset,
 //     no bounds arithmetic at all;
 //   * the ASPP launch runs the module's FOUR branch convolutions side by side (blockIdx.y = branch: each branch its own ConvArgs and its
-//     own instantiation of the tile body): every branch alone fills 44 - 352 of the 512 workgroup slots of the chip.
+//     own instantiation of the tile body): every branch alone fills 44 - 352 of the 512 workgroup slots of the chip.  In eval a fifth
+//     blockIdx.y carries the module's pooled branch (x3d_pool_tile: plain fp32, no matrix instructions).
 // Everything else is conv_x3h.hip's schedule: pixel registers two chunks ahead with hand-placed waits, weights by LDS-DMA
 // (double-buffered; x3h format, launch_x3h_weights with KK = 9 or 1), the running power-of-two shift, conv_epilogue.h, BatchNorm
 // partial sums.
@@ -420,13 +421,81 @@ __global__ __launch_bounds__(256, 2) void conv_x3d_kernel(const ConvArgs a) {
     x3d_tile<KK, DH, DW, MT, 16>(a, pt, ct, smem_x3d);
 }
 
-// the four branch convs of one ASPP module: c[0] the 1x1 (conv2), c[1..3] the dilated 3x3 (conv3..conv5); same N, H, Cout, tiling
-struct X3dAsppArgs { ConvArgs c[4]; };
+// The module's pooled branch (layers.py:72-73, 94: AdaptiveAvgPool2d((1, None)) + 1x1 Conv2DBNActiv), eval: f1[n][co][w] =
+// act(scale[co] * sum_ci W[ci][co] * mean_h x5[n][ci][h][w] + shift[co]) for the MT couts of one cout tile of one sample.  0.02 GFLOP
+// in all, so plain fp32 FMAs: the column means of the sample (rows added in ascending h, divided once, as avgpool_h_kernel does) go to
+// LDS, then every thread forms MT / 16 couts of one column in ascending input-channel order.  Every cout tile of a sample forms the
+// sample's means again (C8 x H x 16 floats from L2) -- cheaper than a launch of its own, which is what it replaces.
+template <int MT>
+__device__ __forceinline__ void x3d_pool_tile(const X3dPoolArgs& q, const int n, const int ct, char* const smem) {
+    float* const pooled = reinterpret_cast<float*>(smem);          // [C8][16]
+    const int tid = threadIdx.x;
+    const float* const xn = q.x + (long long)n * q.xN;
+    const float rows = (float)q.H;
+    // four columns per thread (a row of x5 is 64 bytes), eight rows in flight: the adds stay in ascending h
+    for (int i = tid; i < q.C8 * 4; i += 256) {
+        const float* xc = xn + (long long)(i >> 2) * q.xC + (i & 3) * 4;
+        vr_f32x4h s = {0.f, 0.f, 0.f, 0.f};
+        int h = 0;
+        for (; h + 8 <= q.H; h += 8) {
+            vr_f32x4h v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const vr_f32x4h*>(xc + (long long)(h + j) * q.xH);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[j];
+        }
+        for (; h < q.H; ++h) s += *reinterpret_cast<const vr_f32x4h*>(xc + (long long)h * q.xH);
+        *reinterpret_cast<vr_f32x4h*>(pooled + i * 4) = s / rows;
+    }
+    __syncthreads();
+    constexpr int CPT = MT / 16;                                   // couts per thread
+    const int w = tid & 15;
+    const int co = ct * MT + (tid >> 4) * CPT;                     // (CoutPad is a multiple of MT: the row is read whole, padding included)
+    const float* wp = q.w + co;
+    float acc[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) acc[j] = 0.f;
+#pragma unroll 16
+    for (int ci = 0; ci < q.C8; ++ci) {
+        const float p = pooled[ci * 16 + w];
+        float wv[CPT];
+        if (CPT == 4) {
+            const vr_f32x4h v = *reinterpret_cast<const vr_f32x4h*>(wp + (long long)ci * q.CoutPad);
+#pragma unroll
+            for (int j = 0; j < CPT; ++j) wv[j] = v[j];
+        } else {
+            const vr_f32x2 v = *reinterpret_cast<const vr_f32x2*>(wp + (long long)ci * q.CoutPad);
+#pragma unroll
+            for (int j = 0; j < CPT; ++j) wv[j] = v[j];
+        }
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) acc[j] = fmaf(wv[j], p, acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+        const int c = co + j;
+        if (c < q.Cout) {
+            float v = acc[j];
+            if (q.epi) v = act_apply(fmaf(v, q.epi[2 * c], q.epi[2 * c + 1]), q.slope);
+            q.out[((long long)n * q.Cout + c) * 16 + w] = v;
+        }
+    }
+}
+
+// the four branch convs of one ASPP module: c[0] the 1x1 (conv2), c[1..3] the dilated 3x3 (conv3..conv5); same N, H, Cout, tiling;
+// pool.x set: a fifth blockIdx.y, dispatched last, forms the pooled branch -- only the workgroups of pixel-tile row 0 work, one per
+// (sample, cout tile), in the shadow of the dilated branches
+struct X3dAsppArgs { ConvArgs c[4]; X3dPoolArgs pool; };
 template <int MT>
 __global__ __launch_bounds__(256, 2) void conv_x3d_aspp_kernel(const X3dAsppArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem_x3d[];
     int pt, ct;
     if (!x3d_block(g.c[1], pt, ct)) return;
+    if (blockIdx.y == 4) {
+        const int n = pt / g.c[1].tiles_h;
+        if (pt - n * g.c[1].tiles_h == 0) x3d_pool_tile<MT>(g.pool, n, ct, smem_x3d);
+        return;
+    }
     // the longest branch first in dispatch order (blockIdx.y = 0: dilation 12)
     if (blockIdx.y == 0) x3d_tile<9, 12, 6, MT, 16>(g.c[3], pt, ct, smem_x3d);
     else if (blockIdx.y == 1) x3d_tile<9, 8, 4, MT, 16>(g.c[2], pt, ct, smem_x3d);
@@ -498,7 +567,7 @@ static void x3d_launch_aspp_mt(const X3dAsppArgs& g, hipStream_t st) {
     static std::atomic<unsigned long long> attr_done{0};
     ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), lds);
     const ConvArgs& a = g.c[1];
-    VR_LAUNCH(kern, dim3((unsigned)((a.npt + 7) / 8 * 8 * a.nct), 4u), dim3(256), lds, st, g);
+    VR_LAUNCH(kern, dim3((unsigned)((a.npt + 7) / 8 * 8 * a.nct), g.pool.x ? 5u : 4u), dim3(256), lds, st, g);
     VR_HIP(hipGetLastError());
 }
 bool x3d_aspp_eligible(const ConvArgs* c, const ConvShape* s) {
@@ -511,8 +580,21 @@ bool x3d_aspp_eligible(const ConvArgs* c, const ConvShape* s) {
     }
     return s[0].KS == 1 && s[1].KS == 3 && s[1].dil_h == 4 && s[2].KS == 3 && s[2].dil_h == 8 && s[3].KS == 3 && s[3].dil_h == 12;
 }
-void x3d_launch_aspp(const ConvArgs* c, hipStream_t st) {
+bool x3d_pool_eligible(const X3dPoolArgs& q, const ConvArgs* c) {
+    if (!q.x || !q.w || !q.out || q.C8 < 1 || q.H < 1 || q.Cout < 1) return false;
+    // one cout tile of the pooled part per cout tile of the branches; the means of a sample fit the smaller tiling's LDS
+    if (q.CoutPad != c[1].CoutPad || q.CoutPad % 32 != 0 || q.Cout > q.CoutPad || q.H != c[1].Hin || c[1].Win != 16) return false;
+    // (the means are formed from 16-byte loads of x5's rows)
+    if (((size_t)q.x & 15) || (q.xN & 3) || (q.xC & 3) || (q.xH & 3)) return false;
+    return (long long)q.C8 * 16 * 4 <= X3dCfg<9, 12, 6, 32, 16>::LDS_BYTES;
+}
+void x3d_launch_aspp(const ConvArgs* c, hipStream_t st, const X3dPoolArgs* pool) {
     X3dAsppArgs g;
+    g.pool = X3dPoolArgs{};
+    if (pool) {
+        VR_CHECK(x3d_pool_eligible(*pool, c), -3, "conv_x3d: the ASPP group launch cannot carry this pooled branch");
+        g.pool = *pool;
+    }
     // one cout tile for the four: the dilated branches decide (the launch is four times one branch's grid)
     int MT = (c[1].CoutPad % 64 == 0) ? 64 : 32;
     if (MT == 64 && (long long)c[1].N * ((c[1].Hout + 15) / 16) * (c[1].CoutPad / 64) * 4 < 512) MT = 32;

@@ -1177,6 +1177,110 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         launch_channel_sum(d.p, N, R, W, sums.p, 0, st);
         VR_HIP(hipStreamSynchronize(st));
         o.download(out[0]); sums.download(out[1]);
+    } else if (name == "rows_gemm") {
+        // dims: N, T, K, Cout, CoutPad, flags[, tile: 0 = the host's choice, 11 / 21 / 22].  in: x [N][K][T], w [K][CoutPad] (K-major, as stored), bias [Cout] or null, epi [Cout][2] or
+        // null; fp[0]: activation slope behind epi.  out[0]: [N][Cout][T] of ONE launch_rows_gemm, between guard bands (-3); flags & 1:
+        // out[1] = the same product as Model::run_lstm states it for run_conv (a 1x1 conv on the batch-as-rows view, launch_conv)
+        need(6, 1, 2, 1);
+        const int N = (int)dims[0], T = (int)dims[1], K = (int)dims[2], Cout = (int)dims[3], CoutPad = (int)dims[4];
+        const bool conv_too = dims[5] & 1;
+        VR_CHECK(N >= 1 && T >= 1 && K >= 1 && Cout >= 1 && CoutPad >= 1 && in[0] && in[1] && out[0], -2, "rows_gemm: sizes must be positive");
+        VR_CHECK(!conv_too || (nout >= 2 && out[1] && CoutPad % 32 == 0 && CoutPad >= Cout), -2, "rows_gemm: the conv launch needs couts padded to 32 and out[1]");
+        const size_t no = (size_t)N * Cout * T;
+        DevBuf x(in[0], (size_t)N * K * T), w(in[1], (size_t)K * CoutPad);
+        DevBuf bias(nin >= 3 ? in[2] : nullptr, nin >= 3 && in[2] ? (size_t)Cout : 0), epi(nin >= 4 ? in[3] : nullptr, nin >= 4 && in[3] ? (size_t)Cout * 2 : 0);
+        const bool has_bias = nin >= 3 && in[2], has_epi = nin >= 4 && in[3];
+        GuardedBuf o(out[0], no);                                 // (the caller's fill stays where the launch does not store)
+        RowsGemmArgs g{};
+        g.x = x.p; g.xN = (long long)K * T; g.w = w.p; g.bias = has_bias ? bias.p : nullptr; g.epi = has_epi ? epi.p : nullptr; g.slope = fp[0];
+        g.out = o.p(); g.N = N; g.T = T; g.K = K; g.Cout = Cout; g.CoutPad = CoutPad;
+        launch_rows_gemm(g, st, ndims >= 7 ? (int)dims[6] : 0);   // (refuses, -2, what rows_gemm_ok refuses and a tile it does not have)
+        DevBuf oc(conv_too ? no : 0);
+        if (conv_too) {
+            ConvArgs a{};
+            a.nsrc = 1; a.N = 1; a.Cin = K; a.c1 = a.c2 = K; a.Cout = Cout; a.CoutPad = CoutPad;
+            a.d1 = a.d2 = 1 << 30;
+            a.bf16 = mfma_mode;
+            Tensor xt = dense(x.p, N, K, 1, T);
+            a.src[0] = make_src(xt, false, 0);
+            a.src[0].sH = a.src[0].sN; a.src[0].sN = 0; a.src[0].H = N;
+            a.Hin = a.Hout = N; a.Win = a.Wout = T;
+            a.w = w.p; a.bias = g.bias;
+            if (has_epi) { a.epi = epi.p; a.epi_slope = fp[0]; }
+            a.dst[0] = ConvDst{oc.p, 0, (long long)T, (long long)Cout * T, 0, 0};
+            launch_conv(a, ConvShape{1, 1, 1, 1}, st);
+        }
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(o.intact(), -3, "rows_gemm: a store outside the output buffer");
+        o.download(out[0]);
+        if (conv_too) oc.download(out[1]);
+    } else if (name == "aspp_pool") {
+        // dims: N, C8, H (W = 16).  in: x5 [N][C8][H][16], the pooled branch's 1x1 weights [C8][C8] and folded BatchNorm [C8][2], the four
+        // branch convs' weights (1x1 [C8][C8], then three 3x3 [C8][C8][3][3] for dilation (4,2), (8,4), (12,6)) and their folded
+        // BatchNorms [4][C8][2]; fp[0]: the pooled branch's activation slope.  An ASPP module's eval launches in mfma_mode 3, twice:
+        //   out[0], out[1]: ONE group launch with the pooled branch as its fifth part -> f1 [N][C8][16] (between guard bands, over the
+        //                   caller's fill) and the four branch outputs [N][4 C8][H][16]
+        //   out[2], out[3]: launch_avgpool_h + the 1x1 conv as Model::run_conv states it (batch-as-rows, launch_conv) -> f1, and the group
+        //                   launch without the fifth part -> the branch outputs
+        need(3, 1, 8, 4);
+        const int N = (int)dims[0], C8 = (int)dims[1], H = (int)dims[2], W = 16, CoutPad = (C8 + 31) / 32 * 32;
+        VR_CHECK(N >= 1 && C8 >= 1 && H >= 1, -2, "aspp_pool: sizes must be positive");
+        VR_CHECK(mfma_mode == 3, -2, "aspp_pool: the group launch runs in mfma_mode 3");
+        for (int i = 0; i < 8; ++i) VR_CHECK(in[i] != nullptr, -2, "aspp_pool: missing input");
+        const size_t nx = (size_t)N * C8 * H * W, nf = (size_t)N * C8 * W;
+        DevBuf x(in[0], nx), epi1(in[2], (size_t)C8 * 2), epib(in[7], (size_t)4 * C8 * 2), cat_a(4 * nx), cat_b(4 * nx), pooled(nf), f1b(nf);
+        GuardedBuf f1a(out[0], nf);
+        const Tensor xt = dense(x.p, N, C8, H, W);
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        auto kmajor = [&](const float* oihw, int KK) {
+            std::vector<float> wk((size_t)C8 * KK * CoutPad, 0.f);
+            for (int co = 0; co < C8; ++co)
+                for (int ci = 0; ci < C8; ++ci)
+                    for (int k = 0; k < KK; ++k) wk[((size_t)ci * KK + k) * CoutPad + co] = oihw[((size_t)co * C8 + ci) * KK + k];
+            keep.emplace_back(new DevBuf(wk.data(), wk.size()));
+            return keep.back()->p;
+        };
+        ConvArgs c4[4];
+        ConvShape s4[4];
+        LocalConv wf[4];
+        for (int j = 0; j < 4; ++j) {
+            const int KS = j ? 3 : 1, dh = j ? 4 * j : 1, dw = j ? 2 * j : 1;
+            ConvArgs& a = c4[j];
+            a = ConvArgs{};
+            a.nsrc = 1; a.src[0] = make_src(xt, false, 0); a.c1 = a.c2 = a.Cin = C8;
+            a.w = kmajor(in[3 + j], KS * KS); a.Cout = C8; a.CoutPad = CoutPad;
+            a.epi = epib.p + (size_t)j * C8 * 2; a.epi_slope = 0.f;
+            a.bf16 = 3; a.d1 = a.d2 = 1 << 30;
+            a.N = N; a.Hin = a.Hout = H; a.Win = a.Wout = W; a.pad_h = j ? dh : 0; a.pad_w = j ? dw : 0;
+            debug_weight_forms(a.w, C8, KS, 1, dh, dw, CoutPad, W, true, a, wf[j]);
+            a.dst[0] = ConvDst{cat_a.p + (size_t)j * C8 * H * W, (long long)4 * C8 * H * W, (long long)H * W, W, 0, 0};
+            s4[j] = ConvShape{KS, 1, dh, dw};
+        }
+        VR_CHECK(x3d_aspp_eligible(c4, s4), -2, "aspp_pool: conv_x3d does not take these four branch convs as one launch");
+        X3dPoolArgs q{};
+        q.x = x.p; q.xN = xt.sN; q.xC = xt.sC; q.xH = xt.sH;
+        q.w = kmajor(in[1], 1); q.epi = epi1.p; q.slope = fp[0]; q.out = f1a.p();
+        q.C8 = C8; q.H = H; q.Cout = C8; q.CoutPad = CoutPad;
+        VR_CHECK(x3d_pool_eligible(q, c4), -2, "aspp_pool: the group launch cannot carry this pooled branch (x3d_pool_eligible)");
+        x3d_launch_aspp(c4, st, &q);
+        for (int j = 0; j < 4; ++j) c4[j].dst[0].p = cat_b.p + (size_t)j * C8 * H * W;
+        launch_avgpool_h(xt, pooled.p, st);
+        {
+            ConvArgs b{};
+            b.nsrc = 1; b.N = 1; b.Cin = C8; b.c1 = b.c2 = C8; b.Cout = C8; b.CoutPad = CoutPad;
+            b.d1 = b.d2 = 1 << 30;
+            b.bf16 = 3;
+            b.src[0] = make_src(dense(pooled.p, N, C8, 1, W), false, 0);
+            b.src[0].sH = b.src[0].sN; b.src[0].sN = 0; b.src[0].H = N;
+            b.Hin = b.Hout = N; b.Win = b.Wout = W;
+            b.w = q.w; b.epi = epi1.p; b.epi_slope = fp[0];
+            b.dst[0] = ConvDst{f1b.p, 0, (long long)W, (long long)C8 * W, 0, 0};
+            launch_conv(b, ConvShape{1, 1, 1, 1}, st);
+        }
+        x3d_launch_aspp(c4, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(f1a.intact(), -3, "aspp_pool: a store outside f1's buffer");
+        f1a.download(out[0]); cat_a.download(out[1]); f1b.download(out[2]); cat_b.download(out[3]);
     } else if (name == "adam") {
         need(1, 6, 4, 3);
         const size_t n = (size_t)dims[0];

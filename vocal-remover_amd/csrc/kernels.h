@@ -99,7 +99,18 @@ bool x3d_pick(const ConvArgs& a, const ConvShape& s, int* MT);
 void x3d_fill_tiling(ConvArgs& a, int MT);
 void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, hipStream_t st);
 bool x3d_aspp_eligible(const ConvArgs* c4, const ConvShape* s4);   // c4 / s4 in concat order: 1x1, dilation (4,2), (8,4), (12,6)
-void x3d_launch_aspp(const ConvArgs* c4, hipStream_t st);          // the four branch convs of an ASPP module in ONE launch
+// The module's pooled branch in eval, f1 = act(BN(conv1x1(mean over H of x5))), as a fifth part of that launch (option "aspp_pool_fused")
+struct X3dPoolArgs {
+    const float* x;            // x5 [N][C8][H][16], plain; null: no pooled part
+    long long xN, xC, xH;
+    const float* w;            // the 1x1 layer's K-major weights [C8][CoutPad]
+    const float* epi;          // its folded BatchNorm [Cout][2], or null: no affine and no activation
+    float slope;
+    float* out;                // f1 [N][Cout][16] dense
+    int C8, H, Cout, CoutPad;
+};
+bool x3d_pool_eligible(const X3dPoolArgs& q, const ConvArgs* c4);  // the group launch of c4 can carry q
+void x3d_launch_aspp(const ConvArgs* c4, hipStream_t st, const X3dPoolArgs* pool = nullptr);   // the four branch convs of an ASPP module in ONE launch
 // conv_x3s.hip: conv_x3h's arithmetic for the 3x3 STRIDE-2 layers with >= 32 output columns (eval, one plain source), the stride taken in the
 // loader; weights in x3h format (KK = 9); mfma_mode 3 only
 bool x3s_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t);
@@ -123,6 +134,23 @@ void launch_bilstm_bwd(const float* dh, const float* save, const float* whh_f, c
 size_t lstm_whh_grad_scratch_floats(int N, int H);      // floats of `part` below (one slab per sample slice and direction)
 void launch_lstm_whh_grad(const float* dgx, const float* hout, float* dwhh_f, float* dwhh_r, int N, int T, int H,
                           int accumulate, float* part, hipStream_t st);
+
+// ---- rows_gemm.hip ------------------------------------------------------------------------------
+// out[n][co][t] = act((sum_k w[k][co] x[n][k][t] + bias[co]) * epi[co][0] + epi[co][1]): the LSTM input projection and the Linear behind
+// the LSTM in eval, on v_mfma_f32_16x16x4_f32
+struct RowsGemmArgs {
+    const float* x;            // [N][K][T], samples xN floats apart
+    long long xN;
+    const float* w;            // [K][CoutPad] (a 1x1 conv's K-major weights)
+    const float* bias;         // [Cout] or null
+    const float* epi;          // folded BatchNorm [Cout][2] (scale, shift), or null: no affine and no activation
+    float slope;               // activation slope behind the affine
+    float* out;                // [N][Cout][T] dense
+    int N, T, K, Cout, CoutPad;
+};
+bool rows_gemm_ok(const RowsGemmArgs& a);                        // the kernel takes this shape
+int rows_gemm_tile(const RowsGemmArgs& a);                       // 22 / 21 / 11: (16 MC) couts x (16 NP) positions per workgroup, as MC NP
+void launch_rows_gemm(const RowsGemmArgs& a, hipStream_t st, int tile = 0);   // tile 0: rows_gemm_tile's; the values do not depend on it
 
 // ---- backward.hip -------------------------------------------------------------------------------
 struct BnBwdArgs {

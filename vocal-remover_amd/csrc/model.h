@@ -339,6 +339,12 @@ public:
     // vr_set_option("fuse_tail") (default 1): eval, mfma_mode 3, no taps -- the 1x1 stage tails of the low-band nets and the LSTM squeeze
     // run in the epilogue of the conv_x3h launch whose output they alone read (FusedTail); 0 = two launches each, as before
     bool fuse_tail = true;
+    // vr_set_option("lstm_gemm") (default 1): eval -- the LSTM input projection and the Linear behind the LSTM run as rows_gemm.hip launches
+    // (16 x 16 output tiles, K split over a workgroup's four waves); 0 = run_conv's one-row 1x1 convs, as before
+    bool lstm_gemm = true;
+    // vr_set_option("aspp_pool_fused") (default 1): eval, where the four ASPP branch convs go out as one conv_x3d launch -- the pooled
+    // branch (mean over H + conv1.1) is a fifth part of that launch; 0 = avgpool_h + a 1x1 conv launch in front of it, as before
+    bool aspp_pool_fused = true;
     int net_w_lo = 0, net_w_hi = 0;                      // run_net: the columns of the mask the caller keeps (0, 0: all)
     void set_option(const std::string& name, int value);
     void reset_adam_state();

@@ -375,6 +375,8 @@ void Model::set_option(const std::string& name, int value) {
     }
     else if (name == "crop_window") crop_window = value != 0;
     else if (name == "fuse_tail") fuse_tail = value != 0;
+    else if (name == "lstm_gemm") lstm_gemm = value != 0;
+    else if (name == "aspp_pool_fused") aspp_pool_fused = value != 0;
     else if (name == "complex_train") {                      // a complex handle under the training entry points (off by default: they refuse it)
         if (!is_complex) throw Error(-2, "complex_train: this handle predicts a magnitude mask; the option belongs to complex-mask handles (VR_CREATE_COMPLEX)");
         complex_train = value != 0;
@@ -928,7 +930,30 @@ Tensor Model::run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed) {
         launch_add(M.b_ih_f->dev, M.b_hh_f->dev, bias, G, stream);
         launch_add(M.b_ih_r->dev, M.b_hh_r->dev, bias + G, G, stream);
     }
-    Tensor gx = run_conv(M.proj, {SrcSpec{zt}}, N, nullptr, bias, true);       // [N][8H][nf]
+    // Eval (option "lstm_gemm", default 1): both matrix products of the module as rows_gemm.hip launches -- fp32 arithmetic, so in every
+    // mfma_mode.  The workspace is laid out as run_conv lays it out (one buffer per product).
+    const bool gemm = lstm_gemm && !training && !taping() && !conv_sink;
+    auto rows_gemm = [&](Conv& L, const Tensor& x, const float* b) {
+        Tensor o;
+        o.N = N; o.C = L.Cout; o.H = 1; o.W = nf;
+        o.p = ws.allocf((size_t)N * L.Cout * nf); o.sN = (long long)L.Cout * nf; o.sC = nf; o.sH = nf; o.slope = 1.f;
+        if (dry) return o;
+        RowsGemmArgs g{};
+        g.x = x.p; g.xN = x.sN; g.w = L.w->dev; g.bias = b; g.out = o.p;
+        if (L.bn) { g.epi = L.bn->affine; g.slope = L.slope; }
+        g.N = N; g.T = nf; g.K = L.Cin; g.Cout = L.Cout; g.CoutPad = L.CoutPad;
+        VR_CHECK(L.KS == 1 && x.C == L.Cin && x.sC == nf && rows_gemm_ok(g), -3, "rows_gemm: " + L.name + " is not a matrix product it takes");
+        record_begin(0, 2.0 * N * (double)nf * L.Cout * L.Cin);
+        if (profiling) {
+            char tag[160];
+            snprintf(tag, sizeof tag, "%s gemm ci%d co%d 1x%dx%d", L.name.c_str(), L.Cin, L.Cout, N, nf);
+            record_note(4.0 * ((double)N * L.Cin * nf + (double)N * L.Cout * nf + (double)L.Cin * L.Cout), tag);
+        }
+        launch_rows_gemm(g, stream);
+        record_end();
+        return o;
+    };
+    Tensor gx = gemm ? rows_gemm(M.proj, zt, bias) : run_conv(M.proj, {SrcSpec{zt}}, N, nullptr, bias, true);       // [N][8H][nf]
     float* hc = ws.allocf((size_t)N * 2 * M.hid * nf);                          // [N][2H][nf]
     float* save = taping() ? ws.allocf((size_t)N * 2 * nf * 5 * M.hid) : nullptr;
     if (!dry) launch_bilstm_train(gx.p, M.whh_f->dev, M.whh_r->dev, hc, save, N, nf, M.hid, stream);
@@ -941,7 +966,7 @@ Tensor Model::run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed) {
         r.kind = TK_LSTM; r.M = &M; r.N = N; r.out = ht; r.aux = gx; r.save = save;
         tape.push_back(std::move(r));
     }
-    Tensor lin = run_conv(M.dense, {SrcSpec{ht}}, N, nullptr, M.dense_b->dev, true);   // [N][nb][nf] raw
+    Tensor lin = gemm ? rows_gemm(M.dense, ht, M.dense_b->dev) : run_conv(M.dense, {SrcSpec{ht}}, N, nullptr, M.dense_b->dev, true);   // [N][nb][nf] raw (eval: activated)
     if (taping()) tape.back().bias_param = M.dense_b;
     // BatchNorm1d + ReLU (lib/layers.py:120-121).  Eval: in place.  Train: the raw values are what the
     // BatchNorm backward needs, so the activated copy goes to its own buffer and shares lin's gradient.
@@ -995,7 +1020,13 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
     const Tensor& x5 = e[4];
     const int C8 = 8 * B.c;
     float* pooled = ws.allocf((size_t)N * C8 * x5.W);
-    if (!dry) launch_avgpool_h(x5, pooled, stream);
+    // Eval, mfma_mode 3 (round 6): the four branch convs go out as ONE launch on the fp16 matrix pipe (conv_x3d.hip: blockIdx.y = branch).
+    // They are collected first; if any of them does not qualify (another mode, VR_ASPP_FUSED=0) each is launched on its own as before.
+    const bool group = !dry && mfma_mode == 3 && x3d_mode == 2 && !(training && !train_wino);
+    // Eval (option "aspp_pool_fused", default 1): the pooled branch -- the mean over H and conv1.1 -- waits for that launch too and rides in
+    // it as a fifth part (X3dPoolArgs) where the launch can carry it; where not, its two launches go out in front of the group's.
+    const bool pool_wait = group && !training && aspp_pool_fused;
+    if (!dry && !pool_wait) launch_avgpool_h(x5, pooled, stream);
     Tensor pt;
     pt.p = pooled; pt.N = N; pt.C = C8; pt.H = 1; pt.W = x5.W;
     pt.sN = (long long)C8 * x5.W; pt.sC = x5.W; pt.sH = x5.W; pt.slope = 1.f;
@@ -1005,7 +1036,11 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
         r.kind = TK_AVGPOOL; r.srcs = {SrcSpec{x5}}; r.out = pt; r.N = N;
         tape.push_back(std::move(r));
     }
-    Tensor f1 = run_conv(B.aspp_pool, {SrcSpec{pt}}, N, nullptr, nullptr, true);
+    std::vector<PendingConv> pend_pool;
+    if (pool_wait) conv_sink = &pend_pool;
+    Tensor f1;
+    try { f1 = run_conv(B.aspp_pool, {SrcSpec{pt}}, N, nullptr, nullptr, true); } catch (...) { conv_sink = nullptr; throw; }
+    conv_sink = nullptr;
     // conv2..conv5 write channel slices of one [N, 4*C8, H, W] buffer (the concat is never built)
     Tensor cat4;
     cat4.N = N; cat4.C = 4 * C8; cat4.H = x5.H; cat4.W = x5.W;
@@ -1029,10 +1064,7 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
     // Eval, stage 3: the four branch convs are independent and each fills < 256 CUs at 1/16 resolution --
     // two of them go to the idle side stream.
     static const bool aspp_fork = !getenv("VR_NO_ASPP_FORK");
-    // Eval, mfma_mode 3 (round 6): the four branch convs go out as ONE launch on the fp16 matrix pipe (conv_x3d.hip: blockIdx.y = branch).
-    // They are collected first; if any of them does not qualify (another mode, VR_ASPP_FUSED=0) each is launched on its own as before.
     std::vector<PendingConv> pend;
-    const bool group = !dry && mfma_mode == 3 && x3d_mode == 2 && !(training && !train_wino);
     const bool afk = aspp_fork && !serial && !training && !dry && !profiling && side_stream != nullptr && !band_fork_active && !group;
     hipStream_t aspp_main = stream;
     // (Round 5, measured and removed: every branch on its own stream -- three auxiliary streams per lane, in every stage -- made the
@@ -1059,15 +1091,38 @@ Tensor Model::run_basenet(BaseNetL& B, const std::vector<SrcSpec>& in, int N, co
         ConvShape s4[4];
         double flops = 0.0, bytes = 0.0;
         for (int j = 0; j < 4; ++j) { c4[j] = pend[j].a; s4[j] = pend[j].shp; flops += pend[j].flops; bytes += pend[j].bytes; }
-        if (x3d_aspp_eligible(c4, s4)) {
-            record_begin(0, flops);
+        const bool grouped = x3d_aspp_eligible(c4, s4);
+        X3dPoolArgs q{};
+        if (pool_wait) {
+            VR_CHECK(pend_pool.size() == 1, -3, "ASPP: the pooled branch's conv expected");
+            const ConvArgs& pa = pend_pool[0].a;
+            const ConvSrc& xs = c4[0].src[0];                    // x5 as the branch convs read it (x3d_pick: one plain source)
+            q.x = xs.p; q.xN = xs.sN; q.xC = xs.sC; q.xH = xs.sH;
+            q.w = pa.w; q.epi = pa.epi; q.slope = pa.epi ? pa.epi_slope : 1.f; q.out = f1.p;
+            q.C8 = C8; q.H = x5.H; q.Cout = pa.Cout; q.CoutPad = pa.CoutPad;
+        }
+        const bool pool_in = pool_wait && grouped && c4[0].nsrc == 1 && !pend_pool[0].a.bias && f1.sN == (long long)q.Cout * 16 && f1.sC == 16 &&
+                             x3d_pool_eligible(q, c4);
+        if (pool_wait && !pool_in) {
+            launch_avgpool_h(x5, pooled, stream);
+            record_begin(0, pend_pool[0].flops);
+            if (profiling) record_note(pend_pool[0].bytes, B.aspp_pool.name.c_str());
+            launch_conv(pend_pool[0].a, pend_pool[0].shp, stream);
+            record_end();
+        }
+        if (grouped) {
+            // the pooled part's own work: the mean reads x5 (counted with the branches) and 1x1 weights, and writes f1
+            const double pflops = pool_in ? (double)N * C8 * x5.H * x5.W + pend_pool[0].flops : 0.0;
+            const double pbytes = pool_in ? 4.0 * ((double)C8 * C8 + (double)N * C8 * x5.W) : 0.0;
+            record_begin(0, flops + pflops);
             if (profiling) {
                 char tag[160];
-                snprintf(tag, sizeof tag, "%s.aspp.conv2-5 k1+3x(k3 d4/8/12) ci%d co%d %dx%dx%d", p.c_str(), C8, C8, N, x5.H, x5.W);
+                snprintf(tag, sizeof tag, "%s.aspp.conv2-5%s k1+3x(k3 d4/8/12) ci%d co%d %dx%dx%d", p.c_str(), pool_in ? "+pool+conv1" : "", C8, C8, N,
+                         x5.H, x5.W);
                 // (the four read the same input: counted once)
-                record_note(bytes - 3.0 * 4.0 * (double)N * C8 * x5.H * x5.W, tag);
+                record_note(bytes - 3.0 * 4.0 * (double)N * C8 * x5.H * x5.W + pbytes, tag);
             }
-            x3d_launch_aspp(c4, stream);
+            x3d_launch_aspp(c4, stream, pool_in ? &q : nullptr);
             record_end();
         } else {
             for (int j = 0; j < 4; ++j) {
