@@ -24,8 +24,6 @@
 
 namespace vr {
 
-struct DmaTile { int MT, TH, TW; };
-
 template <int KS, int S, int DH, int DW, int MT, int TH, int TW, int CK>
 struct DmaCfg {
     static constexpr int KK = KS * KS;
@@ -390,10 +388,6 @@ static void dma_launch(const ConvArgs& a, hipStream_t st) {
     VR_HIP(hipGetLastError());
 }
 
-static bool src_plain(const ConvSrc& s) {
-    return !s.aff0 && !s.aff1 && !s.post && !s.up && !s.zins && s.slope == 1.f;
-}
-
 // -------------------------------------------------------------------------------------------------------
 // Data gradient of a stride-2 3x3 conv, all four output-parity classes in ONE launch (train.hip: run_conv_backward).
 //   dx[2i+ph][2j+pw] = sum over the class's live taps of  w_cls[tap] * dz[i + th - 1][j + tw - 1],   th in {1} (ph = 0) or {1,2} (ph = 1)
@@ -641,7 +635,7 @@ bool s2d_fused_eligible(const ConvArgs& a) {
     static const int min_w = getenv("VR_S2D_MIN_W") ? atoi(getenv("VR_S2D_MIN_W")) : 16;
     if (!enabled || a.nsrc != 1 || (a.Cin & 3) || a.Wout < min_w || (a.Win & 3)) return false;
     const ConvSrc& c = a.src[0];
-    if (!src_plain(c) || c.W != a.Win) return false;
+    if (!conv_src_plain(c) || c.up || c.W != a.Win) return false;
     if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
     if ((3 * a.s2_cls_stride + (long long)a.Cin * 9 * a.CoutPad) * 4 >= 0x7FFFFFF0LL) return false;
     return true;
@@ -663,8 +657,8 @@ void launch_s2d_fused(const ConvArgs& a_in, hipStream_t st) {
 }
 
 
-// True when the launch can take the LDS-DMA kernel; fills the tile choice (MT, TH, TW).
-bool dma_pick(const ConvArgs& a, const ConvShape& s, DmaTile* t) {
+// True when the launch can take the LDS-DMA kernel; fills the plan.
+bool dma_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* t) {
     static const int enabled = getenv("VR_CONV_DMA") ? atoi(getenv("VR_CONV_DMA")) : 1;
     if (!enabled) return false;
     const bool dil = s.dil_h != 1 || s.dil_w != 1;
@@ -679,7 +673,7 @@ bool dma_pick(const ConvArgs& a, const ConvShape& s, DmaTile* t) {
     if (a.Wout < 16 || (a.Win & 3)) return false;
     for (int i = 0; i < a.nsrc; ++i) {
         const ConvSrc& c = a.src[i];
-        if (!src_plain(c) || c.W != a.Win) return false;
+        if (!conv_src_plain(c) || c.up || c.W != a.Win) return false;
         if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
     }
     if ((long long)a.Cin * s.KS * s.KS * a.CoutPad * 4 >= 0x7FFFFFF0LL) return false;
@@ -687,7 +681,7 @@ bool dma_pick(const ConvArgs& a, const ConvShape& s, DmaTile* t) {
     if (a.Wout < 32 || dil) {
         // 1/16-resolution layers: 16x16 pixel tiles, 32 couts per workgroup (the grids are small); 8x16 tiles when even
         // that leaves most of the 256 CUs without a second workgroup
-        t->TW = 16; t->TH = 16; t->MT = 32;
+        *t = ConvPlan{CK_DMA, 32, 16, 16, nullptr};
         static const int min16 = getenv("VR_DMA_MIN16") ? atoi(getenv("VR_DMA_MIN16")) : 800;     // (measured: conv time of the step -2.8 %)
         const long long wgs = (long long)a.N * ((a.Hout + 15) / 16) * ((a.Wout + 15) / 16) * (a.CoutPad / 32);
         if (wgs < min16) t->TH = 8;
@@ -703,23 +697,11 @@ bool dma_pick(const ConvArgs& a, const ConvShape& s, DmaTile* t) {
         const long long tiles16 = (long long)a.N * ((a.Hout + 15) / 16) * ((a.Wout + 31) / 32);
         if (tiles16 * (a.CoutPad / 32) >= 1024) TH = 16;
     }
-    t->MT = MT; t->TH = TH; t->TW = 32;
+    *t = ConvPlan{CK_DMA, MT, TH, 32, nullptr};
     return true;
 }
 
-bool conv_dma_eligible(const ConvArgs& a, const ConvShape& s) {
-    DmaTile t;
-    return dma_pick(a, s, &t);
-}
-
-void dma_fill_tiling(ConvArgs& a, const DmaTile& t) {
-    a.tiles_w = (a.Wout + t.TW - 1) / t.TW;
-    a.tiles_h = (a.Hout + t.TH - 1) / t.TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / t.MT;
-}
-
-void dma_launch_conv(const ConvArgs& a, const ConvShape& s, const DmaTile& t, hipStream_t st) {
+void dma_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& t, hipStream_t st) {
     const int MT = t.MT, TH = t.TH;
     if (t.TW == 16 && TH == 8) {
         if (s.KS == 1) dma_launch<1, 1, 1, 1, 32, 8, 16, 32>(a, st);

@@ -1,8 +1,8 @@
 // Conv dispatcher (launch_conv) + the fused-LOADER convolution for the CascadedNet blocks
 // (lib/layers.py:8-64, 67-105) on gfx950.
 //
-// launch_conv picks, in this order:  conv_wino.hip (Winograd F(2x2,3x3), plain inputs, 3x3 stride 1)  ->
-// conv_dma.hip (direct implicit GEMM, plain inputs by LDS-DMA)  ->  conv_ws.hip / the kernel below (inputs that
+// conv_plan (below) states which family a launch takes: the plain-input kernels first (conv_thin, conv_x3 / conv_x3h, conv_x3d,
+// conv_x3s, conv_wino, conv_dma), then conv_ws.hip / the kernel below (inputs that
 // still carry a pending BatchNorm affine / activation / dropout / x2 upsample / zero insertion).  Eval mode and
 // the materialised training path only produce plain inputs, so the kernel in this file is what remains for
 // non-materialised training (VR_NO_TRAIN_MAT), 16-wide stride-2 data gradients and the unit-test hook.
@@ -299,12 +299,10 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// Launcher: pick the instantiation from the layer shape.
+// Launcher: one plan per launch (conv_plan), then the tiling and the family's launcher from it.
 // -------------------------------------------------------------------------------------------------
-struct TileChoice { int MT, TH, TW; };
-
-static TileChoice pick_tile(const ConvArgs& a, const ConvShape& s) {
-    TileChoice t;
+static ConvPlan pick_tile(const ConvArgs& a, const ConvShape& s) {
+    ConvPlan t{CK_MFMA, 0, 0, 0, nullptr};
     const bool dilated = (s.dil_h != 1 || s.dil_w != 1);
     t.TW = (a.Wout >= 32 && !dilated) ? 32 : 16;
     t.TH = (t.TW == 32) ? 8 : 16;
@@ -323,47 +321,6 @@ static TileChoice pick_tile(const ConvArgs& a, const ConvShape& s) {
     return t;
 }
 
-bool ws_pick(const ConvArgs& a, const ConvShape& s, int* MT_out, int* TH_out);
-bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH);
-void thin16_fill_tiling(ConvArgs& a, int TH);
-void thin16_launch_conv(const ConvArgs& a, const ConvShape& s, int TH, hipStream_t st);
-bool wino_pick(const ConvArgs& a, const ConvShape& s, int* MT_out);
-void wino_fill_tiling(ConvArgs& a, int MT);
-void wino_launch_conv(const ConvArgs& a, int MT, hipStream_t st);
-struct DmaTile { int MT, TH, TW; };
-bool dma_pick(const ConvArgs& a, const ConvShape& s, DmaTile* t);
-void dma_fill_tiling(ConvArgs& a, const DmaTile& t);
-void dma_launch_conv(const ConvArgs& a, const ConvShape& s, const DmaTile& t, hipStream_t st);
-void ws_fill_tiling(ConvArgs& a, int MT, int TH);
-void ws_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, int TH, hipStream_t st);
-
-void conv_fill_tiling(ConvArgs& a, const ConvShape& s) {
-    int wmt, wth;
-    int wino_mt, thin_th;
-    if (a.w_hi == 0 && thin16_pick(a, s, &thin_th)) { thin16_fill_tiling(a, thin_th); return; }
-    X3Tile x3t;
-    if (x3_pick(a, s, &x3t)) { x3_fill_tiling(a, x3t); return; }
-    int x3d_mt;
-    if (x3d_pick(a, s, &x3d_mt)) { x3d_fill_tiling(a, x3d_mt); return; }
-    X3Tile x3st;
-    if (x3s_pick(a, s, &x3st)) { x3s_fill_tiling(a, x3st); return; }
-    if (wino_pick(a, s, &wino_mt)) { wino_fill_tiling(a, wino_mt); return; }
-    DmaTile dt;
-    if (dma_pick(a, s, &dt)) { dma_fill_tiling(a, dt); return; }
-    if (ws_pick(a, s, &wmt, &wth)) { ws_fill_tiling(a, wmt, wth); return; }
-    TileChoice t = pick_tile(a, s);
-    a.tiles_w = (a.Wout + t.TW - 1) / t.TW;
-    a.tiles_h = (a.Hout + t.TH - 1) / t.TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / t.MT;
-}
-
-size_t conv_part_count(const ConvArgs& a, const ConvShape& s) {
-    ConvArgs b = a;
-    conv_fill_tiling(b, s);
-    return (size_t)b.npt;
-}
-
 template <int KS, int S, int DH, int DW, int MT, int TH, int TW, int CK, int WAVES_M>
 static void launch_inst(const ConvArgs& a, hipStream_t st) {
     using Cfg = ConvCfg<KS, S, DH, DW, MT, TH, TW, CK, WAVES_M>;
@@ -377,7 +334,7 @@ static void launch_inst(const ConvArgs& a, hipStream_t st) {
 }
 
 template <int KS, int S, int DH, int DW, int CK>
-static void launch_by_tile(const ConvArgs& a, const TileChoice& t, hipStream_t st) {
+static void launch_by_tile(const ConvArgs& a, const ConvPlan& t, hipStream_t st) {
     if (t.TW == 32) {
         if constexpr (DH == 1 && DW == 1) {
             if (t.MT == 64) launch_inst<KS, S, DH, DW, 64, 8, 32, CK, 1>(a, st);
@@ -395,96 +352,95 @@ static void launch_by_tile(const ConvArgs& a, const TileChoice& t, hipStream_t s
     }
 }
 
+// The kernels of this file by (kernel size, stride, dilation); 0: none (the last arm of conv_plan refuses the launch).
+typedef void (*MfmaLauncher)(const ConvArgs&, const ConvPlan&, hipStream_t);
+static MfmaLauncher mfma_launcher(const ConvShape& s) {
+    if (s.KS == 1) return (s.stride == 1 && s.dil_h == 1 && s.dil_w == 1) ? launch_by_tile<1, 1, 1, 1, 32> : nullptr;
+    if (s.KS != 3) return nullptr;
+    if (s.stride == 1 && s.dil_h == 1 && s.dil_w == 1) return launch_by_tile<3, 1, 1, 1, 8>;
+    if (s.stride == 2 && s.dil_h == 1 && s.dil_w == 1) return launch_by_tile<3, 2, 1, 1, 4>;
+    if (s.stride == 1 && s.dil_h == 4 && s.dil_w == 2) return launch_by_tile<3, 1, 4, 2, 4>;
+    if (s.stride == 1 && s.dil_h == 8 && s.dil_w == 4) return launch_by_tile<3, 1, 8, 4, 4>;
+    if (s.stride == 1 && s.dil_h == 12 && s.dil_w == 6) return launch_by_tile<3, 1, 12, 6, 4>;
+    return nullptr;
+}
+
+// THE order the families are tried in, with every guard that is not a family's own rule.  Each *_pick states its family's rule (shape,
+// plain sources, thresholds, VR_* knobs) and fills the plan; nothing else in the library repeats a pick to learn what a launch takes.
+ConvPlan conv_plan(const ConvArgs& a, const ConvShape& s) {
+    auto refuse = [](const char* why) { return ConvPlan{CK_MFMA, 0, 0, 0, why}; };
+    // (in front of the picks: they walk src[0 .. nsrc))
+    if (a.nsrc < 1 || a.nsrc > 3) return refuse("conv takes 1..3 sources");
+    ConvPlan p{CK_MFMA, 0, 0, 0, nullptr};
+    if (a.w_hi == 0 && thin16_pick(a, s, &p)) return p;     // (a column window is conv_x3h's: the 16-cout kernel does not take one)
+    if (x3_pick(a, s, &p)) return p;
+    if (x3d_pick(a, s, &p)) return p;
+    if (x3s_pick(a, s, &p)) return p;
+    if (wino_pick(a, s, &p)) return p;
+    if (dma_pick(a, s, &p)) return p;
+    if (a.tapmask != 0) return refuse("a tap-masked conv needs the LDS-DMA kernel (conv_plan: CK_DMA)");
+    if (ws_pick(a, s, &p)) return p;
+    p = pick_tile(a, s);
+    if (a.CoutPad % p.MT != 0 || a.CoutPad % 32 != 0) return refuse("CoutPad must be a multiple of the cout tile");
+    if (s.KS == 1 && !mfma_launcher(s)) return refuse("1x1 conv: stride/dilation must be 1");
+    if (!mfma_launcher(s)) return refuse("unsupported conv shape (kernel/stride/dilation)");
+    return p;
+}
+
+void conv_fill_tiling(ConvArgs& a, const ConvPlan& p) {
+    a.tiles_w = (a.Wout + p.TW - 1) / p.TW;
+    a.wt0 = 0;
+    if (p.k == CK_X3 && a.w_hi > 0) {                       // column window (conv_x3h.hip): the tiles that meet [w_lo, w_hi)
+        const int hi = a.w_hi < a.Wout ? a.w_hi : a.Wout;
+        a.wt0 = a.w_lo / p.TW;
+        a.tiles_w = (hi + p.TW - 1) / p.TW - a.wt0;
+    }
+    a.tiles_h = (a.Hout + p.TH - 1) / p.TH;
+    a.npt = a.N * a.tiles_h * a.tiles_w;
+    a.nct = a.CoutPad / p.MT;
+}
+
+size_t conv_part_count(const ConvArgs& a, const ConvShape& s) {
+    static float wanted;                                    // never written: a pick only asks whether partials are wanted (x3s_pick)
+    ConvArgs b = a;
+    if (!b.part) b.part = &wanted;
+    const ConvPlan p = conv_plan(b, s);
+    VR_CHECK(!p.refused, -2, p.refused);
+    conv_fill_tiling(b, p);
+    return (size_t)b.npt;
+}
+
 double launch_conv(const ConvArgs& a_in, const ConvShape& s, hipStream_t st) {
     ConvArgs a = a_in;
     static const int dbg = getenv("VR_CONV_DBG") ? atoi(getenv("VR_CONV_DBG")) : 0;
     a.dbg = dbg;
-    if (a.w_hi > 0) {
-        // a column window is honoured by conv_x3h.hip alone: the launch must take it (mfma_mode 3, x3_pick), nothing falls back to full width
-        X3Tile x3t;
-        VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && a.w_lo >= 0 && a.w_lo < a.w_hi && !a.part && x3_pick(a, s, &x3t), -2,
-                 "conv column window: only conv_x3h (mfma_mode 3, eval) takes one");
-    }
-    if (a.tail) {
-        // a second stage in the epilogue is conv_x3h.hip's alone (x3h_tail_ok): the launch must take it, nothing drops the stage
-        X3Tile x3t;
-        int th;
-        VR_CHECK(a.bf16 == 3 && a.nsrc >= 1 && a.nsrc <= 3 && !thin16_pick(a, s, &th) && x3_pick(a, s, &x3t), -2,
-                 "conv with a second stage in its epilogue: only conv_x3h (mfma_mode 3, eval) takes one");
-    }
+    const ConvPlan p = conv_plan(a, s);
+    const bool x3h = !p.refused && p.k == CK_X3 && a.bf16 == 3;
+    // a column window is honoured by conv_x3h.hip alone: the launch must take it (mfma_mode 3), nothing falls back to full width
+    VR_CHECK(a.w_hi <= 0 || (x3h && a.w_lo >= 0 && a.w_lo < a.w_hi && !a.part), -2,
+             "conv column window: only conv_x3h (mfma_mode 3, eval) takes one");
+    // a second stage in the epilogue is conv_x3h.hip's alone (x3h_tail_ok): the launch must take it, nothing drops the stage
+    VR_CHECK(!a.tail || x3h, -2, "conv with a second stage in its epilogue: only conv_x3h (mfma_mode 3, eval) takes one");
     for (int i = 0; i < a.nsrc && i < 3; ++i) {
         // the loaders interpolate an upsampled source from ONE affine (aff0): no kernel splits its rows between two BatchNorms, and the
         // network never asks for it (the band-stacked aux tensors are consumed at their own resolution) -- refuse it, do not compute it wrong
         const ConvSrc& c = a.src[i];
         VR_CHECK(!(c.up && c.aff1 && c.aff1 != c.aff0 && c.hsplit < c.H), -2, "conv: an upsampled source cannot carry a row-split affine (hsplit)");
     }
-    {
-        int wmt, wth;
-        int wino_mt, thin_th;
-        if (a.w_hi == 0 && a.nsrc >= 1 && a.nsrc <= 3 && thin16_pick(a, s, &thin_th)) {
-            thin16_fill_tiling(a, thin_th);
-            thin16_launch_conv(a, s, thin_th, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        X3Tile x3t;
-        if (a.nsrc >= 1 && a.nsrc <= 3 && x3_pick(a, s, &x3t)) {
-            x3_fill_tiling(a, x3t);
-            x3_launch_conv(a, x3t, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        int x3d_mt;
-        if (a.nsrc >= 1 && a.nsrc <= 3 && x3d_pick(a, s, &x3d_mt)) {
-            x3d_fill_tiling(a, x3d_mt);
-            x3d_launch_conv(a, s, x3d_mt, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        X3Tile x3st;
-        if (x3s_pick(a, s, &x3st)) {                              // 3x3 stride 2 on the fp16 pipe (conv_x3s.hip: eval, one plain source)
-            x3s_fill_tiling(a, x3st);
-            x3s_launch_conv(a, x3st, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        if (a.nsrc >= 1 && a.nsrc <= 3 && wino_pick(a, s, &wino_mt)) {
-            wino_fill_tiling(a, wino_mt);
-            wino_launch_conv(a, wino_mt, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        DmaTile dt;
-        if (dma_pick(a, s, &dt)) {
-            VR_CHECK(a.nsrc >= 1 && a.nsrc <= 3, -2, "conv takes 1..3 sources");
-            dma_fill_tiling(a, dt);
-            dma_launch_conv(a, s, dt, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-        VR_CHECK(a.tapmask == 0, -2, "a tap-masked conv needs the LDS-DMA kernel (conv_dma_eligible)");
-        if (ws_pick(a, s, &wmt, &wth)) {
-            VR_CHECK(a.nsrc >= 1 && a.nsrc <= 3, -2, "conv takes 1..3 sources");
-            ws_fill_tiling(a, wmt, wth);
-            ws_launch_conv(a, s, wmt, wth, st);
-            return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
-        }
-    }
-    conv_fill_tiling(a, s);
-    TileChoice t = pick_tile(a, s);
-    VR_CHECK(a.CoutPad % t.MT == 0 && a.CoutPad % 32 == 0, -2, "CoutPad must be a multiple of the cout tile");
-    VR_CHECK(a.nsrc >= 1 && a.nsrc <= 3, -2, "conv takes 1..3 sources");
-    if (s.KS == 1) {
-        VR_CHECK(s.stride == 1 && s.dil_h == 1 && s.dil_w == 1, -2, "1x1 conv: stride/dilation must be 1");
-        launch_by_tile<1, 1, 1, 1, 32>(a, t, st);
-    } else if (s.KS == 3 && s.stride == 1 && s.dil_h == 1 && s.dil_w == 1) {
-        launch_by_tile<3, 1, 1, 1, 8>(a, t, st);
-    } else if (s.KS == 3 && s.stride == 2 && s.dil_h == 1 && s.dil_w == 1) {
-        launch_by_tile<3, 2, 1, 1, 4>(a, t, st);
-    } else if (s.KS == 3 && s.stride == 1 && s.dil_h == 4 && s.dil_w == 2) {
-        launch_by_tile<3, 1, 4, 2, 4>(a, t, st);
-    } else if (s.KS == 3 && s.stride == 1 && s.dil_h == 8 && s.dil_w == 4) {
-        launch_by_tile<3, 1, 8, 4, 4>(a, t, st);
-    } else if (s.KS == 3 && s.stride == 1 && s.dil_h == 12 && s.dil_w == 6) {
-        launch_by_tile<3, 1, 12, 6, 4>(a, t, st);
-    } else {
-        throw Error(-2, "unsupported conv shape (kernel/stride/dilation)");
+    VR_CHECK(!p.refused, -2, p.refused);
+    conv_fill_tiling(a, p);
+    switch (p.k) {
+    case CK_THIN16: thin16_launch_conv(a, p, st); break;
+    case CK_X3: x3_launch_conv(a, p, st); break;
+    case CK_X3D: x3d_launch_conv(a, s, p, st); break;
+    case CK_X3S: x3s_launch_conv(a, p, st); break;             // 3x3 stride 2 on the fp16 pipe (eval, one plain source)
+    case CK_WINO: wino_launch_conv(a, p, st); break;
+    case CK_DMA: dma_launch_conv(a, s, p, st); break;
+    case CK_WS: ws_launch_conv(a, s, p, st); break;
+    case CK_MFMA: mfma_launcher(s)(a, p, st); break;
     }
     return 2.0 * a.N * (double)a.Hout * a.Wout * (double)a.Cout * a.Cin * s.KS * s.KS;
 }
 
 }  // namespace vr
+

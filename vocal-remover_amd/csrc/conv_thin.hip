@@ -230,10 +230,8 @@ __global__ __launch_bounds__(256, 4) void conv_thin_kernel(const ConvArgs a) {
     }
 }
 
-static bool thin_src_plain(const ConvSrc& s) { return !s.aff0 && !s.aff1 && !s.post && !s.up && !s.zins && s.slope == 1.f; }
-
-// The launch can take the 16-cout kernel; fills TH (16, or 8 when the 16-row grid would be small).
-bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH_out) {
+// The launch can take the 16-cout kernel; fills the plan: every cout in one tile, TH 16, or 8 when the 16-row grid would be small.
+bool thin16_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     static const int enabled = getenv("VR_CONV_THIN16") ? atoi(getenv("VR_CONV_THIN16")) : 1;
     if (!enabled || a.Cout > 16 || a.tapmask || a.bf16 == 1) return false;
     // measured per layer: 3x3 with >= 8 input channels 1.35-1.6x faster than the 32-row kernels; the 1x1 tails and the 2-channel
@@ -242,21 +240,14 @@ bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH_out) {
     if (a.pad_h != (s.KS - 1) / 2 || a.pad_w != (s.KS - 1) / 2 || a.Wout < 32 || (a.Win & 3)) return false;
     for (int i = 0; i < a.nsrc; ++i) {
         const ConvSrc& c = a.src[i];
-        if (!thin_src_plain(c) || c.W != a.Win) return false;
+        if (!conv_src_plain(c) || c.up || c.W != a.Win) return false;
         if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
         if (i < 3 && a.dst[i].wshift) return false;
     }
     if ((long long)a.Cin * s.KS * s.KS * a.CoutPad * 4 >= 0x7FFFFFF0LL) return false;
     const long long tiles16 = (long long)a.N * ((a.Hout + 15) / 16) * ((a.Wout + 31) / 32);
-    *TH_out = tiles16 >= 1024 ? 16 : 8;
+    *p = ConvPlan{CK_THIN16, a.CoutPad, tiles16 >= 1024 ? 16 : 8, 32, nullptr};
     return true;
-}
-
-void thin16_fill_tiling(ConvArgs& a, int TH) {
-    a.tiles_w = (a.Wout + 31) / 32;
-    a.tiles_h = (a.Hout + TH - 1) / TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = 1;
 }
 
 template <int KS, int TH, int CK>
@@ -270,9 +261,8 @@ static void thin_launch(const ConvArgs& a, hipStream_t st) {
     VR_HIP(hipGetLastError());
 }
 
-void thin16_launch_conv(const ConvArgs& a, const ConvShape& s, int TH, hipStream_t st) {
-    (void)s;
-    if (TH == 16) thin_launch<3, 16, 4>(a, st); else thin_launch<3, 8, 4>(a, st);
+void thin16_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    if (p.TH == 16) thin_launch<3, 16, 4>(a, st); else thin_launch<3, 8, 4>(a, st);
 }
 
 }  // namespace vr

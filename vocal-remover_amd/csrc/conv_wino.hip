@@ -491,14 +491,14 @@ static void wino_launch(const ConvArgs& a, hipStream_t st) {
 
 // True when the launch can take the Winograd kernel (3x3 stride-1 forward or data gradient, plain inputs,
 // transformed weights available).
-bool wino_pick(const ConvArgs& a, const ConvShape& s, int* MT_out) {
+bool wino_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     static const int enabled = getenv("VR_CONV_WINO") ? atoi(getenv("VR_CONV_WINO")) : 1;
     if (!enabled || !a.wino || a.tapmask) return false;
     if (!(s.KS == 3 && s.stride == 1 && s.dil_h == 1 && s.dil_w == 1)) return false;
     if (a.pad_h != 1 || a.pad_w != 1 || a.Wout < 32 || (a.Win & 3)) return false;
     for (int i = 0; i < a.nsrc; ++i) {
         const ConvSrc& c = a.src[i];
-        if (c.aff0 || c.aff1 || c.post || c.up || c.zins || c.slope != 1.f || c.W != a.Win) return false;
+        if (!conv_src_plain(c) || c.up || c.W != a.Win) return false;
         if (i < 3 && a.dst[i].wshift) return false;
         if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
     }
@@ -514,18 +514,12 @@ bool wino_pick(const ConvArgs& a, const ConvShape& s, int* MT_out) {
     // chunks of 8, no partial-chunk shortcut here) the direct LDS-DMA kernel is the faster one (measured)
     static const int min_cin = getenv("VR_WINO_MINCIN") ? atoi(getenv("VR_WINO_MINCIN")) : 24;
     if (MT == 32 && a.Cin < min_cin) return false;
-    *MT_out = MT;
+    *p = ConvPlan{CK_WINO, MT, 8, 32, nullptr};
     return true;
 }
 
-void wino_fill_tiling(ConvArgs& a, int MT) {
-    a.tiles_w = (a.Wout + 31) / 32;
-    a.tiles_h = (a.Hout + 7) / 8;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / MT;
-}
-
-void wino_launch_conv(const ConvArgs& a, int MT, hipStream_t st) {
+void wino_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    const int MT = p.MT;
     // mode 2 on the 64-cout variant only: the 32-cout one would lose its second workgroup per CU to the bf16 planes (93 KB
     // of LDS) and measured 1.35x SLOWER than its fp32 self (VR_X6_MIN_MT=32 runs it)
     static const int x6_min_mt = getenv("VR_X6_MIN_MT") ? atoi(getenv("VR_X6_MIN_MT")) : 64;

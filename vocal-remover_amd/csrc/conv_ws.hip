@@ -294,7 +294,7 @@ static void ws_launch(const ConvArgs& a, hipStream_t st) {
 }
 
 // Returns false when the shape is not covered (caller falls back to conv_mfma.hip).
-bool ws_pick(const ConvArgs& a, const ConvShape& s, int* MT_out, int* TH_out) {
+bool ws_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     static const int enabled = getenv("VR_CONV_WS") ? atoi(getenv("VR_CONV_WS")) : 1;
     if (!enabled) return false;
     if (s.dil_h != 1 || s.dil_w != 1) return false;
@@ -313,19 +313,12 @@ bool ws_pick(const ConvArgs& a, const ConvShape& s, int* MT_out, int* TH_out) {
         const long long tiles16 = (long long)a.N * ((a.Hout + 15) / 16) * ((a.Wout + 31) / 32);
         if (tiles16 * (a.CoutPad / 32) >= 1024) TH = 16;
     }
-    *MT_out = MT;
-    *TH_out = TH;
+    *p = ConvPlan{CK_WS, MT, TH, 32, nullptr};
     return true;
 }
 
-void ws_fill_tiling(ConvArgs& a, int MT, int TH) {
-    a.tiles_w = (a.Wout + 31) / 32;
-    a.tiles_h = (a.Hout + TH - 1) / TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / MT;
-}
-
-void ws_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, int TH, hipStream_t st) {
+void ws_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& p, hipStream_t st) {
+    const int MT = p.MT, TH = p.TH;
     if (s.KS == 3 && s.stride == 1) {
         static const int npw12 = getenv("VR_WS_NPW") ? atoi(getenv("VR_WS_NPW")) : 12;
         if (npw12 == 12) {

@@ -482,8 +482,8 @@ static void x3_launch(const ConvArgs& a, hipStream_t st) {
     VR_HIP(hipGetLastError());
 }
 
-// True when the launch can take this kernel (3x3 stride-1, plain inputs, split weights available); fills the tile choice.
-bool x3_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
+// True when the launch can take this kernel (3x3 stride-1, plain inputs, split weights available); fills the plan.
+bool x3_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     static const int enabled = getenv("VR_CONV_X3") ? atoi(getenv("VR_CONV_X3")) : 1;
     if (!enabled || !a.x3w || a.tapmask) return false;
     if (!(s.KS == 3 && s.stride == 1 && s.dil_h == 1 && s.dil_w == 1)) return false;
@@ -491,7 +491,7 @@ bool x3_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
     const ConvSrc* u = nullptr;
     for (int i = 0; i < a.nsrc; ++i) {
         const ConvSrc& c = a.src[i];
-        if (c.aff0 || c.aff1 || c.post || c.zins || c.slope != 1.f || (c.up ? 2 * c.W : c.W) != a.Win) return false;
+        if (!conv_src_plain(c) || (c.up ? 2 * c.W : c.W) != a.Win) return false;
         if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
         if (c.up) {                                          // fused bilinear x2: one interpolation geometry per launch
             if (u && (u->H != c.H || u->W != c.W)) return false;
@@ -511,27 +511,14 @@ bool x3_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
     if (force_mt == 32 || force_mt == 64) MT = (a.CoutPad % force_mt == 0) ? force_mt : MT;
     if (force_th == 8 || force_th == 16) TH = force_th;
     if (MT == 64) TH = 8;
-    t->MT = MT; t->TH = TH;
+    *p = ConvPlan{CK_X3, MT, TH, 32, nullptr};
     return true;
 }
 
-void x3_fill_tiling(ConvArgs& a, const X3Tile& t) {
-    a.tiles_w = (a.Wout + 31) / 32;
-    a.wt0 = 0;
-    if (a.w_hi > 0) {                                                    // column window (conv_x3h.hip): the tiles that meet [w_lo, w_hi)
-        const int hi = a.w_hi < a.Wout ? a.w_hi : a.Wout;
-        a.wt0 = a.w_lo / 32;
-        a.tiles_w = (hi + 31) / 32 - a.wt0;
-    }
-    a.tiles_h = (a.Hout + t.TH - 1) / t.TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / t.MT;
-}
-
-void x3_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st) {
-    if (a.bf16 == 3) { x3h_launch_conv(a, t, st); return; }          // mfma_mode 3: three fp16 products (conv_x3h.hip)
-    if (t.MT == 64) x3_launch<64, 8>(a, st);
-    else if (t.TH == 16) x3_launch<32, 16>(a, st);
+void x3_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    if (a.bf16 == 3) { x3h_launch_conv(a, p, st); return; }          // mfma_mode 3: three fp16 products (conv_x3h.hip)
+    if (p.MT == 64) x3_launch<64, 8>(a, st);
+    else if (p.TH == 16) x3_launch<32, 16>(a, st);
     else x3_launch<32, 8>(a, st);
 }
 

@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3d_aspp_kernel(const X3dAsppArgs
 
 // True when conv_x3d takes the launch: 16-column image, 3x3 stride 1 with padding = dilation in {1, (4,2), (8,4), (12,6)} or 1x1,
 // plain sources (eval: final activations; training: materialised), fp16-plane weights present.
-bool x3d_pick(const ConvArgs& a, const ConvShape& s, int* MT_out) {
+bool x3d_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     static const int enabled = getenv("VR_CONV_X3D") ? atoi(getenv("VR_CONV_X3D")) : 1;
     if (!enabled || a.bf16 != 3 || !a.x3w || a.tapmask) return false;
     if (s.stride != 1 || a.Win != 16 || a.Wout != 16 || a.Hin != a.Hout) return false;
@@ -518,7 +518,7 @@ bool x3d_pick(const ConvArgs& a, const ConvShape& s, int* MT_out) {
     } else return false;
     for (int i = 0; i < a.nsrc; ++i) {
         const ConvSrc& c = a.src[i];
-        if (c.aff0 || c.aff1 || c.post || c.zins || c.up || c.slope != 1.f || c.W != 16 || c.H != a.Hin) return false;
+        if (!conv_src_plain(c) || c.up || c.W != 16 || c.H != a.Hin) return false;
         if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
     }
     static const int force_mt = getenv("VR_X3D_MT") ? atoi(getenv("VR_X3D_MT")) : 0;
@@ -526,14 +526,8 @@ bool x3d_pick(const ConvArgs& a, const ConvShape& s, int* MT_out) {
     // fewer than one workgroup per CU with 64 couts: halve the cout tile
     if (MT == 64 && (long long)a.N * ((a.Hout + 15) / 16) * (a.CoutPad / 64) < 256) MT = 32;
     if ((force_mt == 32 || force_mt == 64) && a.CoutPad % force_mt == 0) MT = force_mt;
-    *MT_out = MT;
+    *p = ConvPlan{CK_X3D, MT, 16, 16, nullptr};
     return true;
-}
-void x3d_fill_tiling(ConvArgs& a, int MT) {
-    a.tiles_w = 1;
-    a.tiles_h = (a.Hout + 15) / 16;
-    a.npt = a.N * a.tiles_h;
-    a.nct = a.CoutPad / MT;
 }
 
 template <int KK, int DH, int DW, int MT>
@@ -553,12 +547,12 @@ static void x3d_launch_mt(const ConvArgs& a, const ConvShape& s, hipStream_t st)
     else if (s.dil_h == 8) x3d_launch<9, 8, 4, MT>(a, st);
     else x3d_launch<9, 12, 6, MT>(a, st);
 }
-void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, hipStream_t st) {
-    if (MT == 64) x3d_launch_mt<64>(a, s, st);
+void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& p, hipStream_t st) {
+    if (p.MT == 64) x3d_launch_mt<64>(a, s, st);
     else x3d_launch_mt<32>(a, s, st);
 }
 
-// The four branches of an ASPP module in one launch; c[] in concat order (1x1, d = 4, 8, 12), tiling already filled (x3d_fill_tiling, one MT).
+// The four branches of an ASPP module in one launch; c[] in concat order (1x1, d = 4, 8, 12), tiling already filled (conv_fill_tiling, one MT).
 template <int MT>
 static void x3d_launch_aspp_mt(const X3dAsppArgs& g, hipStream_t st) {
     auto kern = conv_x3d_aspp_kernel<MT>;
@@ -573,9 +567,9 @@ static void x3d_launch_aspp_mt(const X3dAsppArgs& g, hipStream_t st) {
 bool x3d_aspp_eligible(const ConvArgs* c, const ConvShape* s) {
     static const bool on = !(getenv("VR_ASPP_FUSED") && atoi(getenv("VR_ASPP_FUSED")) == 0);
     if (!on) return false;
-    int mt[4];
+    ConvPlan p;
     for (int j = 0; j < 4; ++j) {
-        if (!x3d_pick(c[j], s[j], &mt[j])) return false;
+        if (!x3d_pick(c[j], s[j], &p)) return false;
         if (c[j].N != c[0].N || c[j].Hout != c[0].Hout || c[j].CoutPad != c[0].CoutPad) return false;
     }
     return s[0].KS == 1 && s[1].KS == 3 && s[1].dil_h == 4 && s[2].KS == 3 && s[2].dil_h == 8 && s[3].KS == 3 && s[3].dil_h == 12;
@@ -600,7 +594,7 @@ void x3d_launch_aspp(const ConvArgs* c, hipStream_t st, const X3dPoolArgs* pool)
     if (MT == 64 && (long long)c[1].N * ((c[1].Hout + 15) / 16) * (c[1].CoutPad / 64) * 4 < 512) MT = 32;
     static const int force_mt = getenv("VR_X3D_MT") ? atoi(getenv("VR_X3D_MT")) : 0;
     if ((force_mt == 32 || force_mt == 64) && c[1].CoutPad % force_mt == 0) MT = force_mt;
-    for (int j = 0; j < 4; ++j) { g.c[j] = c[j]; x3d_fill_tiling(g.c[j], MT); }
+    for (int j = 0; j < 4; ++j) { g.c[j] = c[j]; conv_fill_tiling(g.c[j], ConvPlan{CK_X3D, MT, 16, 16, nullptr}); }
     if (MT == 64) x3d_launch_aspp_mt<64>(g, st);
     else x3d_launch_aspp_mt<32>(g, st);
 }

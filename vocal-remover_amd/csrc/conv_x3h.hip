@@ -723,18 +723,18 @@ static void x3h_launch_tail(const ConvArgs& a, hipStream_t st) {
 
 // A launch with a second stage (ConvArgs::tail) exists for the tilings the network's sites run at, and only with every channel of a
 // pixel in one workgroup: tail 1 (stage tail) <32, 16> with upsampled sources; tail 2 (LSTM squeeze) <32, 8> plain, <64, 8> plain and
-// upsampled.  `a` is tiled (x3_fill_tiling).  The executor asks first; what it is refused runs as two launches.
-bool x3h_tail_ok(const ConvArgs& a, const X3Tile& t) {
+// upsampled.  `a` need not be tiled yet.  The executor asks first; what it is refused runs as two launches.
+bool x3h_tail_ok(const ConvArgs& a, const ConvPlan& t) {
     if (a.tail != 1 && a.tail != 2) return false;
-    if (a.bf16 != 3 || a.nct != 1 || a.Cout > t.MT || a.part || a.w_hi != 0 || !a.t_w || !a.t_epi || !a.t_p) return false;
+    if (a.bf16 != 3 || a.CoutPad != t.MT || a.Cout > t.MT || a.part || a.w_hi != 0 || !a.t_w || !a.t_epi || !a.t_p) return false;
     const bool up = (a.src[0].up | (a.nsrc > 1 ? a.src[1].up : 0) | (a.nsrc > 2 ? a.src[2].up : 0)) != 0;
     if (a.tail == 1) return t.MT == 32 && t.TH == 16 && up && a.t_Cout >= 1 && a.t_Cout <= 16 && a.t_CoutPad >= a.t_Cout;
     if (a.d1 < a.Cout || !a.dst[0].p || a.dst[0].accumulate || a.dst[0].wshift) return false;             // (the squeeze stores the first stage as one plain destination)
     return t.TH == 8 && (t.MT == 64 || (t.MT == 32 && !up));
 }
 
-// same tile choice as conv_x3.hip (x3_pick / x3_fill_tiling); taken when ConvArgs::bf16 == 3
-void x3h_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st) {
+// same tile choice as conv_x3.hip (x3_pick); taken when ConvArgs::bf16 == 3
+void x3h_launch_conv(const ConvArgs& a, const ConvPlan& t, hipStream_t st) {
     if (a.tail) {
         VR_CHECK(x3h_tail_ok(a, t), -2, "conv_x3h: no kernel for this launch with a second stage (x3h_tail_ok)");
         const bool up = (a.src[0].up | a.src[1].up | a.src[2].up) != 0;

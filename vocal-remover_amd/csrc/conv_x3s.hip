@@ -402,12 +402,12 @@ static void x3s_launch(const ConvArgs& a, hipStream_t st) {
 
 // True when the launch can take this kernel: mfma_mode 3, eval, 3x3 stride 2 pad 1, one plain source whose column pairs are whole
 // and 8-byte aligned, at least 32 output columns.  The tile choice depends on the launch's shape alone.
-bool x3s_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
+bool x3s_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p) {
     if (a.bf16 != 3 || !a.x3w || a.tapmask || a.part || a.w_hi != 0 || a.nsrc != 1) return false;
     if (!(s.KS == 3 && s.stride == 2 && s.dil_h == 1 && s.dil_w == 1) || a.pad_h != 1 || a.pad_w != 1) return false;
     if (a.Hin < 1 || a.Hout != (a.Hin - 1) / 2 + 1 || a.Wout != (a.Win - 1) / 2 + 1 || a.Wout < 32) return false;
     const ConvSrc& c = a.src[0];
-    if (c.aff0 || c.aff1 || c.post || c.zins || c.up || c.slope != 1.f || c.W != a.Win || c.H != a.Hin) return false;
+    if (!conv_src_plain(c) || c.up || c.W != a.Win || c.H != a.Hin) return false;
     // dwordx2 loads of (even, odd) column pairs: no pair may straddle the right edge, every pair 8-byte aligned
     if ((a.Win & 1) || (c.sH & 1) || (c.sC & 1) || (c.sN & 1) || (reinterpret_cast<unsigned long long>(c.p) & 7)) return false;
     if ((long long)c.H * (c.sH > 0 ? c.sH : 1) * 4 >= 0x7FFFFFF0LL) return false;
@@ -419,20 +419,12 @@ bool x3s_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t) {
     int MT = (a.CoutPad % 64 == 0) ? 64 : 32;
     const long long tiles8 = (long long)a.N * ((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
     if (MT == 64 && tiles8 * (a.CoutPad / 64) < 512) MT = 32;            // fewer than two workgroups per CU: halve the cout tile
-    t->MT = MT; t->TH = 8;
+    *p = ConvPlan{CK_X3S, MT, 8, 32, nullptr};
     return true;
 }
 
-void x3s_fill_tiling(ConvArgs& a, const X3Tile& t) {
-    a.tiles_w = (a.Wout + 31) / 32;
-    a.wt0 = 0;
-    a.tiles_h = (a.Hout + t.TH - 1) / t.TH;
-    a.npt = a.N * a.tiles_h * a.tiles_w;
-    a.nct = a.CoutPad / t.MT;
-}
-
-void x3s_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st) {
-    if (t.MT == 64) x3s_launch<64, 8>(a, st);
+void x3s_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    if (p.MT == 64) x3s_launch<64, 8>(a, st);
     else x3s_launch<32, 8>(a, st);
 }
 

@@ -556,7 +556,7 @@ void Model::debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int
     const std::string who = "vr_debug_kernel(conv_tail): ";
     VR_CHECK(ndims >= 12 && nfp >= 2 && nout >= 2, -2, who + "too few arguments");
     const int nsrc = (int)dims[0], N = (int)dims[1], Cout = (int)dims[2], kind = (int)dims[3], Cout2 = (int)dims[4];
-    const X3Tile tile{(int)dims[5], (int)dims[6]};
+    const ConvPlan tile{CK_X3, (int)dims[5], (int)dims[6], 32, nullptr};       // the tiling is the test's, not conv_plan's
     VR_CHECK(nsrc >= 1 && nsrc <= 3 && N >= 1 && Cout >= 1 && (kind == 1 || kind == 2) && Cout2 >= 1 && (kind == 1 || Cout2 == 1), -2,
              who + "1..3 sources, kind 1 or 2");
     VR_CHECK((tile.MT == 32 || tile.MT == 64) && (tile.TH == 8 || (tile.TH == 16 && tile.MT == 32)), -2, who + "tilings: <32,8>, <32,16>, <64,8>");
@@ -604,10 +604,7 @@ void Model::debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int
     a.epi = upload(in[1], (size_t)Cout * 2); a.epi_slope = fp[0];
     LocalConv wf;
     debug_weight_forms(dwk.p, Cin, 3, 1, 1, 1, a.CoutPad, a.Win, true, a, wf);
-    {
-        X3Tile any;
-        VR_CHECK(a.x3w && x3_pick(a, ConvShape{3, 1, 1, 1}, &any), -2, who + "conv_x3h does not take this launch");
-    }
+    VR_CHECK(a.x3w && conv_plan(a, ConvShape{3, 1, 1, 1}).k == CK_X3, -2, who + "conv_x3h does not take this launch");
     // the second stage: K-major weights [Cout][CoutPad2] (kind 1) or [Cout] (kind 2)
     const int CoutPad2 = (Cout2 + 31) / 32 * 32;
     std::vector<float> w2((size_t)Cout * (kind == 1 ? CoutPad2 : 1), 0.f);
@@ -622,7 +619,7 @@ void Model::debug_conv_tail(const int64_t* dims, int ndims, const float* fp, int
     GuardedBuf y(in[4], yfloats);
     DevBuf prod((size_t)N * Cout * H * W);
     a.dst[0] = ConvDst{prod.p, (long long)Cout * H * W, (long long)H * W, W, 0, 0};
-    x3_fill_tiling(a, tile);
+    conv_fill_tiling(a, tile);
     if (fuse_tail) {
         a.tail = kind; a.t_Cout = Cout2; a.t_CoutPad = kind == 1 ? CoutPad2 : 1; a.t_w = dw2.p; a.t_epi = epi2; a.t_slope = fp[1];
         a.t_p = y.p() + yoff; a.t_sN = ysN; a.t_sC = ysC; a.t_sH = ysH;

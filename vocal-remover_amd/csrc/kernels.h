@@ -64,9 +64,16 @@ void launch_augment(const float2* X, const float2* Y, const float2* Xi, const fl
 struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
                              float* Ymag, bool out_complex, hipStream_t st);
-bool thin16_pick(const ConvArgs& a, const ConvShape& s, int* TH);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32
-void thin16_fill_tiling(ConvArgs& a, int TH);
-void thin16_launch_conv(const ConvArgs& a, const ConvShape& s, int TH, hipStream_t st);
+// The conv families behind launch_conv.  A *_pick says whether its family takes the launch and fills the plan (kernel, MT, TH, TW);
+// conv_plan (conv_mfma.hip) alone calls them, in its order.  A *_launch_conv takes tiled args (conv_fill_tiling) and the plan.
+bool thin16_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32
+void thin16_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+bool wino_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);    // conv_wino.hip: Winograd F(2x2,3x3), 3x3 stride 1
+void wino_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+bool dma_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);     // conv_dma.hip: direct implicit GEMM, plain inputs by LDS-DMA
+void dma_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& p, hipStream_t st);
+bool ws_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);      // conv_ws.hip: inputs with pending arithmetic, >= 32 columns
+void ws_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& p, hipStream_t st);
 bool s2d_fused_eligible(const ConvArgs& a);                       // conv_dma.hip: stride-2 data gradient, four parity classes in one launch
 void launch_s2d_fused(const ConvArgs& a, hipStream_t st);
 struct S2WDesc { const float* w; float* wc; int Cin, Cout, CoutPad, CinPad; };          // one stride-2 layer; max_elems = max over layers of 4 * Cout * 9 * CinPad
@@ -77,27 +84,24 @@ void launch_wino_weights_batched(const WinoWDesc* d_descs, int n, long long max_
 size_t wino_weights6_bytes(int Cin, int CoutPad);                                           // U as three bf16 planes (mfma_mode 2)
 void launch_wino_weights6(const float* w, void* u6, int Cin, int CoutPad, hipStream_t st);
 // conv_x3.hip: direct 3x3 stride-1 conv, fp32 products from six bf16 products (mfma_mode 2)
-struct X3Tile { int MT, TH; };
 struct X3WDesc { const float* w; void* o; int Cin, KK, CoutPad; };                            // one layer of a batched weight split
-bool x3_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t);
-void x3_fill_tiling(ConvArgs& a, const X3Tile& t);
-void x3_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st);
+bool x3_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);
+void x3_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);   // ConvArgs::bf16 == 3: x3h_launch_conv
 size_t x3_weights_bytes(int Cin, int KK, int CoutPad);
 void launch_x3_weights(const float* w, void* o, int Cin, int KK, int CoutPad, hipStream_t st);
 void launch_x3_weights_batched(const X3WDesc* d_descs, int n, long long max_elems, hipStream_t st);
 // conv_x3h.hip: the same convs with fp32-grade products from three fp16 products (mfma_mode 3); weights in the SAME buffers
 // (x3_weights_bytes), format [chunk][tap][2][CoutPad][8] fp16 + per-cout scale tails
-void x3h_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st);
-bool x3h_tail_ok(const ConvArgs& a, const X3Tile& t);  // a tiled launch with ConvArgs::tail set: a kernel with that second stage exists
+void x3h_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
+bool x3h_tail_ok(const ConvArgs& a, const ConvPlan& p);  // a launch of plan p (CK_X3) with ConvArgs::tail set: a kernel with that second stage exists
 void x3h_trace_read(long long* host, int n);          // diagnostics: phase stamps of the TRACE build (VR_CONV_DBG bit 64)
 void x3h_trace_clear();
 void launch_x3h_weights(const float* w, void* o, int Cin, int KK, int CoutPad, hipStream_t st);
 void launch_x3h_weights_batched(const X3WDesc* d_descs, int n, long long max_elems, int max_cout_pad, hipStream_t st);
 // conv_x3d.hip (round 6): conv_x3h's arithmetic for the 16-column layers -- dilated 3x3 (ASPP), 3x3 dilation 1 (enc5.conv2), 1x1 (ASPP conv2);
 // weights in x3h format (launch_x3h_weights with KK = 9 / 1); mfma_mode 3 only
-bool x3d_pick(const ConvArgs& a, const ConvShape& s, int* MT);
-void x3d_fill_tiling(ConvArgs& a, int MT);
-void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, int MT, hipStream_t st);
+bool x3d_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);
+void x3d_launch_conv(const ConvArgs& a, const ConvShape& s, const ConvPlan& p, hipStream_t st);
 bool x3d_aspp_eligible(const ConvArgs* c4, const ConvShape* s4);   // c4 / s4 in concat order: 1x1, dilation (4,2), (8,4), (12,6)
 // The module's pooled branch in eval, f1 = act(BN(conv1x1(mean over H of x5))), as a fifth part of that launch (option "aspp_pool_fused")
 struct X3dPoolArgs {
@@ -113,9 +117,8 @@ bool x3d_pool_eligible(const X3dPoolArgs& q, const ConvArgs* c4);  // the group 
 void x3d_launch_aspp(const ConvArgs* c4, hipStream_t st, const X3dPoolArgs* pool = nullptr);   // the four branch convs of an ASPP module in ONE launch
 // conv_x3s.hip: conv_x3h's arithmetic for the 3x3 STRIDE-2 layers with >= 32 output columns (eval, one plain source), the stride taken in the
 // loader; weights in x3h format (KK = 9); mfma_mode 3 only
-bool x3s_pick(const ConvArgs& a, const ConvShape& s, X3Tile* t);
-void x3s_fill_tiling(ConvArgs& a, const X3Tile& t);
-void x3s_launch_conv(const ConvArgs& a, const X3Tile& t, hipStream_t st);
+bool x3s_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);
+void x3s_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);
 void launch_upsample2x(const Tensor& x, float* out, hipStream_t st);   // dense [N][C][2H][2W], activated
 
 // ---- lstm.hip -----------------------------------------------------------------------------------

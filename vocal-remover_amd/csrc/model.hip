@@ -700,6 +700,16 @@ void Model::build_fwd_args(Conv& L, const std::vector<SrcSpec>& srcs, int N, boo
     a.pad_h = L.pad_h; a.pad_w = L.pad_w;
 }
 
+// The batch statistics of a BatchNorm from the partial sums its producer left: `nparts` rows of `pstride` floats, `count` elements per channel.
+static BNFinalizeArgs bn_finalize_args(const BN& b, const float* part, int nparts, int pstride, double count) {
+    BNFinalizeArgs f{};
+    f.part = part; f.nparts = nparts; f.pstride = pstride; f.count = count;
+    f.w = b.w->dev; f.b = b.b->dev; f.rm = b.rm->dev; f.rv = b.rv->dev;
+    f.affine = b.affine; f.save_mean = b.save_mean; f.save_invstd = b.save_invstd;
+    f.C = b.C; f.eps = 1e-5f; f.momentum = 0.1f; f.broadcast = b.bcast;
+    return f;
+}
+
 Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, const Tensor* out_view, const float* bias,
                        bool batch_as_h, FusedTail* tail) {
     // Training: give the conv plain inputs (one element-wise / upsample pass per source) -- the forward conv
@@ -725,6 +735,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
     }
     ConvArgs a;
     build_fwd_args(L, srcs, N, batch_as_h, a);
+    const ConvShape shp{L.KS, L.stride, L.dh, L.dw};
     if (!training) {
         // fused-upsample sources are for conv_x3.hip only: anything else gets the materialised tensor after all
         bool any_up = false;
@@ -733,8 +744,8 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
             ConvArgs probe = a;
             select_fwd_forms(probe, L.forms, form_select(), probe.Win, L.stride);
             probe.bf16 = mfma_mode;
-            X3Tile xt;
-            if (!x3_pick(probe, ConvShape{L.KS, L.stride, L.dh, L.dw}, &xt)) {
+            // ("the plan is conv_x3" is "x3_pick takes it" here: the 16-cout kernel ahead of it refuses any upsampled source)
+            if (conv_plan(probe, shp).k != CK_X3) {
                 for (SrcSpec& sp : srcs) {
                     if (!sp.up) continue;
                     const Tensor& t = sp.t;
@@ -758,14 +769,9 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
     select_fwd_forms(a, L.forms, form_select(), a.Win, L.stride);
     a.bf16 = mfma_mode;
     int wcols = a.Wout;                                      // output columns the launch computes
-    if (conv_w_hi > 0 && !training && mfma_mode == 3 && !batch_as_h && !conv_sink) {
-        X3Tile xt;
-        int tth;
-        const ConvShape cs{L.KS, L.stride, L.dh, L.dw};
-        if (!thin16_pick(a, cs, &tth) && x3_pick(a, cs, &xt)) {             // (the launch takes conv_x3h: launch_conv's order)
-            a.w_lo = conv_w_lo; a.w_hi = conv_w_hi;
-            wcols = std::min(a.Wout, (conv_w_hi + 31) / 32 * 32) - conv_w_lo / 32 * 32;
-        }
+    if (conv_w_hi > 0 && !training && mfma_mode == 3 && !batch_as_h && !conv_sink && conv_plan(a, shp).k == CK_X3) {
+        a.w_lo = conv_w_lo; a.w_hi = conv_w_hi;                             // (the launch takes conv_x3h)
+        wcols = std::min(a.Wout, (conv_w_hi + 31) / 32 * 32) - conv_w_lo / 32 * 32;
     }
     Tensor o;
     if (batch_as_h) {
@@ -788,23 +794,21 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         }
         a.dst[0] = ConvDst{o.p, o.sN, o.sC, o.sH, 0};
     }
-    const ConvShape shp{L.KS, L.stride, L.dh, L.dw};
     const bool stats = training && L.bn;
-    size_t npt = 0;
+    BNFinalizeArgs fin{};
     if (stats) {
-        npt = conv_part_count(a, shp);
+        const size_t npt = conv_part_count(a, shp);
         a.part = ws.allocf(npt * L.Cout * 2);
+        fin = bn_finalize_args(*L.bn, a.part, (int)npt, L.Cout * 2, (double)N * (batch_as_h ? 1 : a.Hout) * a.Wout);
     }
     // The 1x1 stage that only reads this conv's output goes into the launch's epilogue where conv_x3h has the kernel for it (model.h:
     // FusedTail).  The workspace is laid out as without it (the dry run and every mode plan one sequence); a stage tail's producer
     // buffer is then simply not written.
     const char* fused_tag = "";
     if (tail && !dry && fuse_tail && !training && mfma_mode == 3 && !record_taps && !conv_sink && !batch_as_h && fuse_epi && a.w_hi == 0) {
-        X3Tile xt;
-        int tth;
-        if (!thin16_pick(a, shp, &tth) && x3_pick(a, shp, &xt)) {           // (the launch takes conv_x3h: launch_conv's order)
+        const ConvPlan plan = conv_plan(a, shp);
+        if (plan.k == CK_X3) {                                             // (the launch takes conv_x3h)
             ConvArgs b = a;
-            x3_fill_tiling(b, xt);
             b.tail = tail->kind;
             b.t_p = tail->out.p;
             if (tail->kind == 1) {
@@ -823,10 +827,9 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
             // time at the 11-, 6- and 5-crop grids.  The squeeze behind the 64-cout dec2 with upsampled sources (stage 3) missed it at 6 crops
             // (13.6 us saved against a bar of 16.1; 23.9 / 22.9 at 11): it stays two launches.
             const bool any_up = a.src[0].up || (a.nsrc > 1 && a.src[1].up) || (a.nsrc > 2 && a.src[2].up);
-            const bool by_rule = !(tail->kind == 2 && xt.MT == 64 && any_up);
-            if (by_rule && x3h_tail_ok(b, xt)) {
-                a.tail = b.tail; a.t_p = b.t_p; a.t_Cout = b.t_Cout; a.t_CoutPad = b.t_CoutPad; a.t_w = b.t_w; a.t_epi = b.t_epi;
-                a.t_slope = b.t_slope; a.t_sN = b.t_sN; a.t_sC = b.t_sC; a.t_sH = b.t_sH;
+            const bool by_rule = !(tail->kind == 2 && plan.MT == 64 && any_up);
+            if (by_rule && x3h_tail_ok(b, plan)) {
+                a = b;
                 tail->done = true;
                 fused_tag = tail->kind == 1 ? "+tail" : "+squeeze";
             }
@@ -839,15 +842,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         pc.a = a; pc.shp = shp;
         pc.flops = 2.0 * N * (double)a.Hout * a.Wout * (double)L.Cout * L.Cin * L.KS * L.KS;
         pc.bytes = conv_alg_bytes(L, a, N, batch_as_h);
-        pc.stats = stats; pc.bn = L.bn;
-        if (stats) {
-            BNFinalizeArgs& f = pc.fin;
-            f.part = a.part; f.nparts = (int)npt; f.pstride = L.Cout * 2;
-            f.count = (double)N * a.Hout * a.Wout;
-            f.w = L.bn->w->dev; f.b = L.bn->b->dev; f.rm = L.bn->rm->dev; f.rv = L.bn->rv->dev;
-            f.affine = L.bn->affine; f.save_mean = L.bn->save_mean; f.save_invstd = L.bn->save_invstd;
-            f.C = L.Cout; f.eps = 1e-5f; f.momentum = 0.1f; f.broadcast = 0;
-        }
+        pc.stats = stats; pc.fin = fin; pc.bn = L.bn;
         conv_sink->push_back(pc);
     } else if (!dry) {
         const double flops = 2.0 * N * (double)(batch_as_h ? 1 : a.Hout) * wcols * (double)L.Cout * L.Cin * L.KS * L.KS;
@@ -869,13 +864,7 @@ Tensor Model::run_conv(Conv& L, const std::vector<SrcSpec>& srcs_in, int N, cons
         launch_conv(a, shp, stream);
         record_end();
         if (stats) {
-            BNFinalizeArgs f{};
-            f.part = a.part; f.nparts = (int)npt; f.pstride = L.Cout * 2;
-            f.count = (double)N * (batch_as_h ? 1 : a.Hout) * a.Wout;
-            f.w = L.bn->w->dev; f.b = L.bn->b->dev; f.rm = L.bn->rm->dev; f.rv = L.bn->rv->dev;
-            f.affine = L.bn->affine; f.save_mean = L.bn->save_mean; f.save_invstd = L.bn->save_invstd;
-            f.C = L.Cout; f.eps = 1e-5f; f.momentum = 0.1f; f.broadcast = 0;
-            launch_bn_finalize(f, stream);
+            launch_bn_finalize(fin, stream);
             L.bn->nbt->nbt += 1;
         }
     }
@@ -900,12 +889,7 @@ Tensor Model::run_lstm(LSTMMod& M, const Tensor& h, float* z, bool squeezed) {
         launch_squeeze_conv(h, M.squeeze.w->dev, z, part, false, stream, training ? nullptr : M.squeeze.bn->affine);
         if (training) {
             BN* b = M.squeeze.bn;
-            BNFinalizeArgs f{};
-            f.part = part; f.nparts = nblk; f.pstride = 2; f.count = (double)N * nb * nf;
-            f.w = b->w->dev; f.b = b->b->dev; f.rm = b->rm->dev; f.rv = b->rv->dev;
-            f.affine = b->affine; f.save_mean = b->save_mean; f.save_invstd = b->save_invstd;
-            f.C = 1; f.eps = 1e-5f; f.momentum = 0.1f; f.broadcast = b->bcast;
-            launch_bn_finalize(f, stream);
+            launch_bn_finalize(bn_finalize_args(*b, part, nblk, 2, (double)N * nb * nf), stream);
             b->nbt->nbt += 1;
         }
     }

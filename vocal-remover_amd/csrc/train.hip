@@ -269,7 +269,7 @@ int Model::bwd_conv_dgrad(TapeRec& r, const ConvArgs& f) {
                     k.dst[i].sH *= 2;
                     k.dst[i].wshift = 1;
                 }
-                if (k.Hout < 1 || k.Wout < 1 || !conv_dma_eligible(k, cshp)) ok = false;
+                if (k.Hout < 1 || k.Wout < 1 || conv_plan(k, cshp).k != CK_DMA) ok = false;
             }
             if (ok) {
                 record_begin(0, 2.0 * N * (double)f.Hout * f.Wout * (double)L.Cout * L.Cin * L.KS * L.KS);

@@ -170,7 +170,7 @@ struct ConvArgs {
     int w_lo, w_hi;            // output-column window (conv_x3h.hip only; w_hi == 0: every column).  Only the 32-column tiles that meet
                                // [w_lo, w_hi) run; the input geometry stays full width (halo columns are real data) and the columns
                                // outside those tiles are not written.  Eval: the consumer keeps only the window (predict_mask's crop)
-    int wt0;                   // first 32-column tile of the window (x3_fill_tiling); tiles_w counts the window's tiles
+    int wt0;                   // first 32-column tile of the window (conv_fill_tiling); tiles_w counts the window's tiles
     // A second, 1x1 stage in the epilogue (conv_x3h.hip only, eval, one cout tile: x3h_tail_ok).  The first stage's bias, folded
     // BatchNorm and activation are applied to the accumulators in registers, then
     //   tail 1: y[j] = act(t_slope)(s2[j] * sum_c w2[c][j] a[c] + b2[j]), j < t_Cout <= 16, stored through the view t_p / t_sN / t_sC /
@@ -215,10 +215,24 @@ size_t wgrad_scratch_floats(const WgradArgs& a, const ConvShape& s);
 // out[i] (+)= the sum over the P slabs part[p * stride + i], i < n: the immediate form of the slab sum (wgrad_reduce_kernel)
 void launch_wgrad_reduce(const float* part, long long stride, int P, float* out, long long n, int accumulate, hipStream_t st);
 
+// A source the loaders read with no arithmetic: no pending affine, activation or dropout mask, no zero insertion.  (`up` is asked
+// separately: conv_x3 / conv_x3h interpolate an upsampled plain source in their loader, no other plain-input kernel does.)
+inline bool conv_src_plain(const ConvSrc& c) { return !c.aff0 && !c.aff1 && !c.post && !c.zins && c.slope == 1.f; }
+
+// Which kernel a conv launch takes and in which tiling: decided ONCE, by conv_plan, and read by everything that depends on it -- the
+// launch itself, the size of the BatchNorm partials (conv_part_count), and every caller that may ask for something only one family
+// has (a column window, a second stage in the epilogue, a fused-upsample source: conv_x3h; a tap mask: conv_dma).
+enum ConvKernel { CK_THIN16, CK_X3, CK_X3D, CK_X3S, CK_WINO, CK_DMA, CK_WS, CK_MFMA };   // the order conv_plan tries them in
+struct ConvPlan {
+    ConvKernel k;              // CK_X3: conv_x3.hip, or conv_x3h.hip when ConvArgs::bf16 == 3
+    int MT, TH, TW;            // couts x rows x columns of one workgroup's tile
+    const char* refused;       // set: no kernel takes the launch (launch_conv and conv_part_count raise it, -2); k is then CK_MFMA
+};
+ConvPlan conv_plan(const ConvArgs& a, const ConvShape& s);     // THE statement of the order and of its guards; never throws
+void conv_fill_tiling(ConvArgs& a, const ConvPlan& p);         // tiles_w / tiles_h / npt / nct (+ wt0 and conv_x3h's column window)
 // Returns the algorithmic FLOPs of the launch (2*MACs) for roofline accounting.
 double launch_conv(const ConvArgs& a, const ConvShape& s, hipStream_t st);
-size_t conv_part_count(const ConvArgs& a, const ConvShape& s);   // #partials rows (npt)
-void conv_fill_tiling(ConvArgs& a, const ConvShape& s);
-bool conv_dma_eligible(const ConvArgs& a, const ConvShape& s);    // the LDS-DMA kernel covers this launch
+// #partials rows (npt) of the plan the launch takes once ConvArgs::part is set (callers size the buffer first: a.part may still be null)
+size_t conv_part_count(const ConvArgs& a, const ConvShape& s);
 
 }  // namespace vr
