@@ -260,6 +260,36 @@ int vr_evaluate_wave(vr_handle h, const float* mix, const float* inst, int on_de
                      int64_t window, double* sums, float* y_wave, float* v_wave, int out_on_device);
 int vr_evaluate_plan(int hop, int64_t L, int64_t window, int64_t* samples, int64_t* n_windows);
 
+/* ---- pseudo-instrument labels (the reference's pseudo.py:40-74), many pairs in one call ------------------------------------------------
+ * For pair s of a mixture X_s and its imperfect instrumental y_s, both complex64 [2][bins][T_s]:
+ *     D_s = X_s - y_s                                   (one float32 subtraction per component, as numpy's complex64 difference)
+ *     a_s = instruments stem of vr_separate of D_s      (flag word `tta` as vr_separate: bit 0 --tta, bit 1 --postprocess)
+ *     P_s = y_s + a_s                                   (one float32 addition per component, never contracted with the product before it)
+ * out[s] receives P_s, T_s frames of complex64, as [2][bins][T] (VR_PSEUDO_SPEC, what pseudo.py saves) or as [T][2][bins]
+ * (VR_PSEUDO_ROWS, the rows of the training cache: vr_dataset_add takes them as they are).  Nothing else is stored or copied: no vocal
+ * stem, no wave, and at wave level not X either.  Each pair comes out as it would alone -- the normaliser is that of D_s (max|D|, or for tta
+ * the lexicographic complex maximum), padding and merge_artifacts runs are its own -- while the crops of all pairs and of both passes share
+ * device batches exactly as in vr_separate_many.  A pair with X == y everywhere has D = 0 and gives what vr_separate_many gives for a zero
+ * spectrogram (the reference divides 0 by 0 there: NaN); it is not treated specially.  pseudo.py always runs tta; the flag is honoured.
+ *   vr_pseudo_many        mix_specs[s], inst_specs[s]: [2][bins][T[s]] complex64 (both tables on the host or both on the device); any hop_length
+ *   vr_pseudo_wave_many   mix_waves[s], inst_waves[s]: float32 [2][L[s]], already aligned, the same length; T = 1 + L / hop as for vr_stft.  One
+ *                         launch transforms both waves of all pairs (the pair form of the frame-tiled STFT), so it exists only where
+ *                         hop_length == n_fft / 2; elsewhere VR_ERR_BAD_ARGUMENT with the reason
+ *   vr_pseudo, vr_pseudo_wave   the many-call of one pair (`solo` as for vr_separate: batchsize <= 0 = the crops of its longer pass)
+ * Magnitude and VR_CREATE_COMPLEX handles.  Errors as for vr_separate_many: n_songs <= 0, a null table or an unknown layout before the
+ * handle is looked at; a null entry, T[s] <= 0, L[s] < hop_length or training mode before the device is touched; errors of a many-call
+ * that concern one pair start with "song <s>: ", a solo call's name no song; a --postprocess IndexError of one pair fails the call with
+ * VR_ERR_INDEX and leaves the handle usable.                                                                                        */
+enum vr_pseudo_layout { VR_PSEUDO_SPEC = 0 /* [2][bins][T], pseudo.py's .npy */, VR_PSEUDO_ROWS = 1 /* [T][2][bins], the cache's */ };
+int vr_pseudo_many(vr_handle h, int n_songs, const float* const* mix_specs, const float* const* inst_specs, int on_device, const int* T, int tta,
+                   int batchsize, int cropsize, int layout, float* const* out, int out_on_device);
+int vr_pseudo_wave_many(vr_handle h, int n_songs, const float* const* mix_waves, const float* const* inst_waves, int on_device, const int64_t* L,
+                        int tta, int batchsize, int cropsize, int layout, float* const* out, int out_on_device);
+int vr_pseudo(vr_handle h, const float* mix_spec, const float* inst_spec, int on_device, int T, int tta, int batchsize, int cropsize, int layout,
+              float* out, int out_on_device);
+int vr_pseudo_wave(vr_handle h, const float* mix_wave, const float* inst_wave, int on_device, int64_t L, int tta, int batchsize, int cropsize,
+                   int layout, float* out, int out_on_device);
+
 /* ---- streaming separation: push audio in blocks, get the stems back with bounded state -----------------------------------
  * The offline call's crops sit at multiples of roi = cropsize - 2 * offset whatever the song's length (make_padding: pad_l = offset),
  * the --tta pass is the same list shifted by roi / 2, and with hop == n_fft / 2 frame t needs the samples below (t + 1) * hop.  The

@@ -286,6 +286,64 @@ int vr_evaluate_plan(int hop, int64_t L, int64_t window, int64_t* samples, int64
     });
 }
 
+// ---- pseudo-instrument labels ---------------------------------------------------------------------------------
+// What can be judged without the handle: the count, the tables, the layout.  Everything per song (a null entry, T <= 0, L < hop) and
+// training mode need the handle: Model::separate_run refuses them before it touches the device.
+static bool pseudo_args_ok(int n_songs, const void* mix, const void* inst, const void* len, const void* out, int layout) {
+    if (n_songs <= 0) { g_err = "n_songs must be positive"; return false; }
+    if (!mix || !inst || !len || !out) { g_err = "null table"; return false; }
+    if (layout != VR_PSEUDO_SPEC && layout != VR_PSEUDO_ROWS) { g_err = "unknown layout (VR_PSEUDO_SPEC or VR_PSEUDO_ROWS)"; return false; }
+    return true;
+}
+
+int vr_pseudo_many(vr_handle h, int n_songs, const float* const* mix_specs, const float* const* inst_specs, int on_device, const int* T, int tta,
+                   int batchsize, int cropsize, int layout, float* const* out, int out_on_device) {
+    if (!pseudo_args_ok(n_songs, mix_specs, inst_specs, T, out, layout)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        const vr::PseudoArgs ps{inst_specs, layout};
+        h->m.separate_run(n_songs, mix_specs, on_device != 0, T, nullptr, tta, batchsize, cropsize, out, nullptr, out_on_device != 0, nullptr, nullptr,
+                          /*solo=*/false, nullptr, &ps);
+    });
+}
+
+int vr_pseudo_wave_many(vr_handle h, int n_songs, const float* const* mix_waves, const float* const* inst_waves, int on_device, const int64_t* L,
+                        int tta, int batchsize, int cropsize, int layout, float* const* out, int out_on_device) {
+    if (!pseudo_args_ok(n_songs, mix_waves, inst_waves, L, out, layout)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n_songs);
+        const vr::PseudoArgs ps{inst_waves, layout};
+        h->m.separate_run(n_songs, mix_waves, on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, out, nullptr, out_on_device != 0, nullptr,
+                          nullptr, /*solo=*/false, nullptr, &ps);
+    });
+}
+
+int vr_pseudo(vr_handle h, const float* mix_spec, const float* inst_spec, int on_device, int T, int tta, int batchsize, int cropsize, int layout,
+              float* out, int out_on_device) {
+    if (!mix_spec || !inst_spec || !out) { g_err = "null argument"; return VR_ERR_BAD_ARGUMENT; }
+    if (!pseudo_args_ok(1, &mix_spec, &inst_spec, &T, &out, layout)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        const vr::PseudoArgs ps{&inst_spec, layout};
+        h->m.separate_run(1, &mix_spec, on_device != 0, &T, nullptr, tta, batchsize, cropsize, &out, nullptr, out_on_device != 0, nullptr, nullptr,
+                          /*solo=*/true, nullptr, &ps);
+    });
+}
+
+int vr_pseudo_wave(vr_handle h, const float* mix_wave, const float* inst_wave, int on_device, int64_t L, int tta, int batchsize, int cropsize,
+                   int layout, float* out, int out_on_device) {
+    if (!mix_wave || !inst_wave || !out) { g_err = "null argument"; return VR_ERR_BAD_ARGUMENT; }
+    if (!pseudo_args_ok(1, &mix_wave, &inst_wave, &L, &out, layout)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        const long long len = L;
+        const vr::PseudoArgs ps{&inst_wave, layout};
+        h->m.separate_run(1, &mix_wave, on_device != 0, nullptr, &len, tta, batchsize, cropsize, &out, nullptr, out_on_device != 0, nullptr, nullptr,
+                          /*solo=*/true, nullptr, &ps);
+    });
+}
+
 // ---- WAV sample bytes in, PCM16 out (csrc/pcm.h; the host converters are pcm_host.cpp) ------------------------------------------
 int vr_pcm_available(vr_handle h, int* available) {
     NEED(h);

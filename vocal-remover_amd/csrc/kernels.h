@@ -410,6 +410,25 @@ void launch_istft_eval_many(const FFTPlan& pl, const SongSeg* songs, const WaveE
 // sums[w][q] of every song = its partials of window w added over (segment, channel, wave) in a fixed order; max_windows: the largest count
 void launch_eval_sums(const FFTPlan& pl, const SongSeg* songs, const WaveEval* evs, int n_songs, long long max_windows, double sum_T, hipStream_t st);
 
+// ---- pseudo-instrument labels (vr_pseudo*) ------------------------------------------------------------------------
+// One entry per song beside the song table (device memory), as WaveEval rides beside it: the plain table forms keep their entry and
+// their code.  The pair takes the place of the one input: the table's `spec` is D = X - Y (what the network separates), written by the
+// pair front end; the back end stores P = Y + instruments stem of D and nothing else.
+struct PseudoSeg {
+    const float* inst_wave;   // [2][L] the imperfect instrumental, L of the table entry (wave-level calls)
+    const float2* mix;        // [2][bins][T] X (spectrogram-level calls; a wave-level call never writes X)
+    float2* inst;             // [2][bins][T] Y (read; written by the pair STFT of a wave-level call)
+    float2* out;              // P: [2][bins][T] (VR_PSEUDO_SPEC) or [T][2][bins] (VR_PSEUDO_ROWS)
+};
+// the pair form of stft_tile_kernel: mixture tile and instrumental tile of the same frames in one workgroup; stores Y and D = X - Y
+void launch_stft_pseudo_many(const FFTPlan& pl, const SongSeg* songs, const PseudoSeg* ps, int n_songs, int max_T, double sum_L, double sum_T,
+                             hipStream_t st);
+// D = X - Y over the song table, one workgroup per (row, song)
+void launch_pseudo_diff_many(const SongSeg* songs, const PseudoSeg* ps, int n_songs, int bins, double sum_T, hipStream_t st);
+// the pseudo form of apply_mask_kernel: out = Y + instruments stem; rows: out is [T][2][bins], written through an LDS tile
+void launch_apply_mask_pseudo_many(const SongSeg* songs, const PseudoSeg* ps, int n_songs, int max_T, int bins, const float* mask, int W, int tta,
+                                   bool cplx, const float* wgt, bool rows, double sum_T, hipStream_t st);
+
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
 // step).  The kernels take a TABLE of them: one grid dimension is the table entry, sized for the largest entry, and a workgroup past

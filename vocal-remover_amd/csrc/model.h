@@ -113,6 +113,10 @@ StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int
 // inst[s]: song s's true instruments [2][L[s]], where the mixtures are (host or device); sums[s]: HOST [windows][4] doubles;
 // stems false: the call returns sums only (y, v of separate_run unused).
 struct EvalArgs { const float* const* inst; long long window; double* const* sums; bool stems; };
+// Pseudo-instrument labels (vr_pseudo*): the input of song s is the pair (in[s], inst[s]) -- two spectrograms or two
+// waves of the same size, where the mixtures are (host or device); the network separates D = in - inst, and y[s] receives
+// P = inst + instruments stem of D, T complex64 frames in `layout` (enum vr_pseudo_layout).  v of separate_run is unused.
+struct PseudoArgs { const float* const* inst; int layout; };
 // the stems' length and the window count of a song of L samples: samples = hop (L / hop), windows = ceil(samples / window); host only
 struct EvalPlan { long long samples, windows; };
 EvalPlan evaluate_plan(int hop, long long L, long long window);
@@ -263,10 +267,11 @@ public:
     // The offline executor (vr_separate* and vr_separate*_many): n_songs spectrograms (L null: specs [2,bins,T[s]] -> y / v spectrograms)
     // or waves (L given: [2,L[s]] -> y / v waves [2, hop*(T-1)], the whole inference.py pipeline device resident) in one call; with
     // pcm_fmt the waves are sample bytes and the stems int16 [samples][2].  solo: a one-song entry point's call of one song.
-    // eval: the evaluation mode of a float wave-level call (EvalArgs above).
+    // eval: the evaluation mode of a float wave-level call (EvalArgs above).  pseudo: the pair call (PseudoArgs above), float inputs.
     void separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta, int batchsize,
                       int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
-                      const int* pcm_fmt = nullptr, bool solo = false, const EvalArgs* eval = nullptr);
+                      const int* pcm_fmt = nullptr, bool solo = false, const EvalArgs* eval = nullptr,
+                      const PseudoArgs* pseudo = nullptr);
     // ---- WAV sample bytes in, PCM16 out (vr_*_pcm*; csrc/pcm.h): the sample-format forms of the frame-tiled STFT / iSTFT ----
     bool pcm_available() const;                           // the frame-tiled kernels, whose forms these are, exist on this handle
     void check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const;      // availability, format, channels, a device pointer's alignment

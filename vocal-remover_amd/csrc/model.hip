@@ -1744,9 +1744,13 @@ void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst
 // eval (vr_evaluate_wave*): a wave-level float call that also scores each song against its true instruments --
 // the inst waves are staged like the mixtures, the back end is the evaluation form of the masked iSTFT plus one launch that adds its
 // partials per window, and the sums go back to the host.  Without eval->stems no stem is allocated, stored or copied (y, v unused).
+// pseudo (vr_pseudo*): the input of a song is a pair (X, Y) and the call returns P = Y + instruments stem of X - Y.  The
+// front end stores Y and D = X - Y (wave level: the pair form of the tiled STFT; spectrogram level: one elementwise launch), the table's
+// `spec` is D, so everything between the normaliser and the per-frame minima runs as for any song; the back end is the pseudo form
+// of apply_mask, which stores P once, in the caller's layout.  No vocal stem and no wave is allocated, stored or copied (v unused).
 void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta, int batchsize,
                          int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels, const int* pcm_fmt,
-                         bool solo, const EvalArgs* eval) {
+                         bool solo, const EvalArgs* eval, const PseudoArgs* pseudo) {
     // VR_ENQ_TIMING=1 (diagnostics, wave-level calls): host time to ENQUEUE the whole call vs the time until the device has drained it
     static const bool enq_timing = getenv("VR_ENQ_TIMING") != nullptr;
     const auto enq_t0 = std::chrono::steady_clock::now();
@@ -1758,7 +1762,13 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     // ---- arguments and the host-side plan: nothing here touches the device
     VR_CHECK(n_songs > 0, -2, "n_songs must be positive");
     const bool stems = !eval || eval->stems;
-    VR_CHECK(in && (!stems || (y && v)) && (waves || T_in), -2, "null table");
+    VR_CHECK(in && (!stems || (y && (v || pseudo))) && (waves || T_in), -2, "null table");
+    if (pseudo) {
+        VR_CHECK(!pcm && !eval && pseudo->inst, -2, "a pseudo-label call takes float pairs");
+        VR_CHECK(pseudo->layout == 0 || pseudo->layout == 1, -2, "unknown layout");
+        VR_CHECK(!waves || many_tiled_available(plan, hop), -2,
+                 "the wave-level pseudo-label call needs hop_length == n_fft / 2 (the frame-tiled STFT kernel whose pair form it is exists only there)");
+    }
     if (eval) {
         VR_CHECK(waves && !pcm && eval->inst && eval->sums, -2, "evaluation takes float waves and their true instruments");
         VR_CHECK(many_tiled_available(plan, hop), -2,
@@ -1776,7 +1786,8 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     auto song = [&](int s) { return solo ? std::string() : "song " + std::to_string(s) + ": "; };      // what an error starts with
     for (int s = 0; s < n_songs; ++s) {
         const std::string who = song(s);
-        VR_CHECK(in[s] && (!stems || (y[s] && v[s])) && (!eval || (eval->inst[s] && eval->sums[s])), -2, who + "null pointer");
+        VR_CHECK(in[s] && (!stems || (y[s] && (pseudo || v[s]))) && (!eval || (eval->inst[s] && eval->sums[s])) && (!pseudo || pseudo->inst[s]), -2,
+                 who + "null pointer");
         if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
         else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
         if (waves) VR_CHECK(L[s] / hop < (1LL << 30), -2, who + "wave too long");
@@ -1817,6 +1828,9 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     std::vector<WaveEval> evt(eval ? (size_t)n_songs : 0);
     std::vector<float*> stage_inst(eval ? (size_t)n_songs : 0);
     WaveEval* evt_d = nullptr;
+    std::vector<PseudoSeg> pst(pseudo ? (size_t)n_songs : 0);
+    std::vector<float*> stage_pinst(pseudo ? (size_t)n_songs : 0);
+    PseudoSeg* pst_d = nullptr;
     double pcm_bytes = 0.0;
     auto in_bytes = [&](int s) {
         return pcm ? (size_t)L[s] * pcm_channels[s] * pcm_sample_bytes(pcm_fmt[s]) : (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float);
@@ -1829,6 +1843,7 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         crops_d = static_cast<int2*>(A.alloc(sizeof(int2) * crops_n));
         if (pcm) pin_d = static_cast<PcmIn*>(A.alloc(sizeof(PcmIn) * n_songs));
         if (eval) evt_d = static_cast<WaveEval*>(A.alloc(sizeof(WaveEval) * n_songs));
+        if (pseudo) pst_d = static_cast<PseudoSeg*>(A.alloc(sizeof(PseudoSeg) * n_songs));
         part = static_cast<unsigned long long*>(A.alloc((size_t)n_songs * 2 * bins * 16));
         aff = A.allocf((size_t)n_songs * 4);
         mask = A.allocf((size_t)E * 2 * bins * W);
@@ -1844,7 +1859,23 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
             t.mcol_b = tta ? g.crop0[1] * roi + roi / 2 : 0;
             stage_in[s] = in_on_dev ? nullptr : A.allocf(in_bytes(s) / 4 + (pcm ? 1 : 0));
             const float* src = in_on_dev ? in[s] : stage_in[s];
-            if (waves) {
+            if (pseudo) {                             // the pair beside the table entry: `spec` is D, P goes out once, no other stem exists
+                stage_pinst[s] = in_on_dev ? nullptr : A.allocf(in_bytes(s) / 4);
+                const float* isrc = in_on_dev ? pseudo->inst[s] : stage_pinst[s];
+                PseudoSeg& q = pst[s];
+                q = PseudoSeg{};
+                t.spec = reinterpret_cast<float2*>(A.allocf(g.spec_f));
+                if (waves) {
+                    t.wave = src; t.L = L[s];
+                    q.inst_wave = isrc;
+                    q.inst = reinterpret_cast<float2*>(A.allocf(g.spec_f));
+                } else {
+                    q.mix = reinterpret_cast<const float2*>(src);
+                    q.inst = reinterpret_cast<float2*>(const_cast<float*>(isrc));
+                }
+                stage_y[s] = out_on_dev ? y[s] : A.allocf(g.spec_f);
+                q.out = reinterpret_cast<float2*>(stage_y[s]);
+            } else if (waves) {
                 t.wave = src; t.L = L[s];
                 if (pcm) {                            // the STFT reads the bytes through the PcmIn table; the stems are int16
                     t.wave = nullptr;
@@ -1908,8 +1939,17 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
             for (int s = 0; s < n_songs; ++s)
                 VR_HIP(hipMemcpyAsync(stage_inst[s], eval->inst[s], in_bytes(s), hipMemcpyHostToDevice, stream));
     }
+    if (pseudo) {
+        VR_HIP(hipMemcpyAsync(pst_d, pst.data(), sizeof(PseudoSeg) * n_songs, hipMemcpyHostToDevice, stream));
+        if (!in_on_dev)
+            for (int s = 0; s < n_songs; ++s)
+                VR_HIP(hipMemcpyAsync(stage_pinst[s], pseudo->inst[s], in_bytes(s), hipMemcpyHostToDevice, stream));
+    }
     // ---- front end
-    if (waves) {
+    if (pseudo) {                           // Y and D = X - Y; X itself is never written (waves: tiled, checked above)
+        if (waves) launch_stft_pseudo_many(plan, tab_d, pst_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
+        else launch_pseudo_diff_many(tab_d, pst_d, n_songs, bins, (double)sum_T, stream);
+    } else if (waves) {
         if (pcm) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream, pin_d, pcm_bytes);   // (check_pcm: tiled)
         else if (tiled) launch_stft_many(plan, tab_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
         else for (int s = 0; s < n_songs; ++s) launch_stft(plan, tab[s].wave, L[s], hop, sg[s].T, tab[s].spec, stream);
@@ -1949,7 +1989,9 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         VR_HIP(hipMemcpyAsync(wgt_d, wgt_h.data(), (size_t)sum_T * sizeof(float), hipMemcpyHostToDevice, stream));
         wgt = wgt_d;
     }
-    if (eval) {                             // (tiled, checked above)
+    if (pseudo) {
+        launch_apply_mask_pseudo_many(tab_d, pst_d, n_songs, max_T, bins, mask, W, tta, is_complex, wgt, pseudo->layout == 1, (double)sum_T, stream);
+    } else if (eval) {                      // (tiled, checked above)
         for (int which = 0; which < 2; ++which)
             launch_istft_eval_many(plan, tab_d, evt_d, n_songs, max_T, (double)sum_T, mask, W, tta ? mask : nullptr, W, 0, is_complex, wgt, which,
                                    stems, stream);
@@ -1970,9 +2012,10 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     }
     if (!out_on_dev && stems)
         for (int s = 0; s < n_songs; ++s) {
-            const size_t nf = waves ? sg[s].out_f : sg[s].spec_f;
+            const size_t nf = (waves && !pseudo) ? sg[s].out_f : sg[s].spec_f;
             if (!nf) continue;
             VR_HIP(hipMemcpyAsync(y[s], stage_y[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
+            if (pseudo) continue;
             VR_HIP(hipMemcpyAsync(v[s], stage_v[s], nf * (pcm ? 2 : sizeof(float)), hipMemcpyDeviceToHost, stream));
         }
     const auto enq_t1 = std::chrono::steady_clock::now();     // everything is enqueued at this point

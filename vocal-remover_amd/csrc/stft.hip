@@ -51,6 +51,17 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// a - b and a + b per component, each one float32 operation of its own: never contracted with a product on either side, so that the
+// result is numpy's complex64 difference / sum of the two rounded values (the pseudo-label forms)
+__device__ __forceinline__ float2 sub_rounded(float2 a, float2 b) {
+#pragma clang fp contract(off)
+    return make_float2(a.x - b.x, a.y - b.y);
+}
+__device__ __forceinline__ float2 add_rounded(float2 a, float2 b) {
+#pragma clang fp contract(off)
+    return make_float2(a.x + b.x, a.y + b.y);
+}
+
 // In-place radix-2 DIT FFT on x[0..n) (already in bit-reversed order). tw[k] = exp(-2*pi*i*k/n).
 __device__ __forceinline__ void fft_lds(float2* x, const float2* __restrict__ tw, int n, int log2n) {
     const int half_n = n >> 1;
@@ -199,12 +210,17 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 // WaveGrad in the same place (SRC = const float, `wave` and `spec` unused): the adjoint of the inverse transform for the wave-domain loss
 // term (kernels.h) -- blockIdx.y runs over the signals, L = hop (T-1), the source is WaveGradIn and the store epilogue writes dmask.
 // WaveGrad3: the same for the weighted SDR term, source WaveGrad3In over three waves, the same store epilogue.
+// const PseudoSeg* (SRC = const SongSeg): the pair form -- one PseudoSeg per song beside the song table.  The workgroup
+// runs its frame tile twice with the same arithmetic: first the song's instrumental (`inst_wave`), stored to `inst` as vr_stft stores it,
+// then the table's mixture, of which only D = X - Y goes to the table's `spec`; X itself is never written.
 template <class SRC = const float, class... PCM>
 __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
                                                          float2* __restrict__ spec, PCM... pcm) {
     constexpr bool kGrad3 = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad3>::value;
     constexpr bool kGrad = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad>::value || kGrad3;
-    constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad;
+    constexpr bool kPseudo = std::is_same<typename FirstOr<void, PCM...>::type, const PseudoSeg*>::value;
+    constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad && !kPseudo;
+    static_assert(!kPseudo || kSongTable<SRC>, "the pair form is a song-table form");
     static_assert(sizeof...(PCM) <= 1 && !(sizeof...(PCM) == 1 && kStream<SRC>), "one PCM source at most, none for streams");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
@@ -217,6 +233,8 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
                               typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type>::type in;
     typename std::conditional<kGrad3, WaveGrad3, typename std::conditional<kGrad, WaveGrad, int>::type>::type gd{};
     StreamLocal<SRC> ss{};
+    typename std::conditional<kPseudo, PseudoSeg, int>::type ps{};
+    const float* mix_wv = nullptr;                   // (pseudo) the mixture's row, for pass 1
     if constexpr (kStream<SRC>) {                    // blockIdx.z = table entry; the frames [t_new, T) of its stream, written into the ring
         ss = wave[blockIdx.z];
         if (blockIdx.x > 0 && t0 >= ss.T - ss.t_new) return;        // (workgroup 0 always runs: it moves the input tail on)
@@ -228,6 +246,11 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
         L = sg.L; T = sg.T; spec = sg.spec;
         if constexpr (kPcm) in.in = pcm_first(pcm...)[blockIdx.z];
         else in.wv = sg.wave + (long long)ch * L;
+        if constexpr (kPseudo) {
+            ps = pcm_first(pcm...)[blockIdx.z];
+            mix_wv = in.wv;
+            in.wv = ps.inst_wave + (long long)ch * L;
+        }
     } else if constexpr (kGrad3) {                   // cy, cp, cx from the six batch-wide sums the triple iSTFT left in device memory
         gd = pcm_first(pcm...);
         const WsdrCoef c = wsdr_coefficients((double)gd.sums[0], (double)gd.sums[1], (double)gd.sums[2], (double)gd.sums[3],
@@ -247,6 +270,11 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     }
     if constexpr (kPcm) in.ch = ch < in.in.channels ? ch : in.in.channels - 1;
     const int nf = (T - t0) < F ? (T - t0) : F;
+    // (pseudo) pass 0 = the instrumental Y, stored as it is; pass 1 = the mixture X, of which only D = X - Y is stored: a thread unpacks the
+    // same (bin, frame) elements in both passes, so pass 1 reads back its own tile entries.  (A jump back, not a loop around the body:
+    // every other form then has no loop in its source and keeps the code it had.)
+    int pass = 0;
+second_pass:
     for (int f0 = 0; f0 < nf; f0 += TG) {
         const int f = f0 + g;
         const bool live = f < nf;
@@ -273,7 +301,12 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
                 const float2 b = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
                 const float2 w = k < M ? pl.twiddle[k] : make_float2(-1.f, 0.f);
                 const float2 wb = cmul(w, b);                              // X = E - i * w * B
-                tile[k * F + f] = make_float2(e.x + wb.y, e.y - wb.x);
+                if constexpr (kPseudo) {
+                    const float2 xv = make_float2(e.x + wb.y, e.y - wb.x);
+                    tile[k * F + f] = pass == 1 ? sub_rounded(xv, tile[k * F + f]) : xv;
+                } else {
+                    tile[k * F + f] = make_float2(e.x + wb.y, e.y - wb.x);
+                }
             }
         }
         __syncthreads();
@@ -300,8 +333,18 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
                 }
                 gd.dmask[e] = make_float2(gv.x * xv.x + gv.y * xv.y, gv.y * xv.x - gv.x * xv.y);        // times conj(X)
             }
+        } else if constexpr (kPseudo) {
+            if (f < nf) (pass == 0 ? ps.inst : spec)[((long long)ch * bins + k) * T + t0 + f] = tile[idx];
         } else {
             if (f < nf) spec[((long long)ch * bins + k) * T + t0 + f] = tile[idx];
+        }
+    }
+    if constexpr (kPseudo) {
+        if (pass == 0) {
+            pass = 1;
+            in.wv = mix_wv;
+            __syncthreads();                         // the Y tile is read out before pass 1 writes D over it
+            goto second_pass;
         }
     }
     if constexpr (kStream<SRC>) {                    // the samples the next step's first frames reach back to
@@ -1162,11 +1205,105 @@ void launch_frame_min(int bins, int T, const float* mask_a, int Wa, const float*
     VR_HIP(hipGetLastError());
 }
 
+// ---- the pseudo-label back end (vr_pseudo*) ---------------------------------------------------------------------
+// the instruments stem of apply_mask_kernel at (row, t) for the spectrogram value z: the same expressions in the same order
+template <bool CPLX>
+__device__ __forceinline__ float2 instruments_stem(const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb, int shift,
+                                                   const float* __restrict__ wgt, long long row, int t, float2 z) {
+    if constexpr (CPLX) {
+        const float2 mc = final_mask(reinterpret_cast<const float2*>(ma), Wa, reinterpret_cast<const float2*>(mb), Wb, shift, wgt, row, t);
+        return cmul(mc, z);
+    } else {
+        float m = ma[row * Wa + t];
+        if (mb) m = (m + mb[row * Wb + t + shift]) * 0.5f;
+        if (wgt) m += wgt[t] * (1.f - m);            // merge_artifacts: y_mask += weight * (1 - y_mask)
+        return make_float2(m * z.x, m * z.y);
+    }
+}
+
+// What rides behind apply_mask_kernel's arguments in its pseudo forms: the PseudoSeg table; the type is the layout of `out`.
+struct PseudoSpec { const PseudoSeg* ps; };          // VR_PSEUDO_SPEC [2][bins][T]: today's mapping, consecutive lanes along t
+struct PseudoRows { const PseudoSeg* ps; };          // VR_PSEUDO_ROWS [T][2][bins]: through an LDS tile
+struct PseudoDiff { const PseudoSeg* ps; };          // not a back end: D = X - Y of a spectrogram-level call (pseudo_diff below)
+constexpr int PT = 64;                               // the rows form's tile: PT frames x PT bins of one channel
+// Row pitch of the tile in float2: lanes along t write a row (kk fixed, consecutive 8-byte addresses: no conflict at any pitch); lanes along
+// the bin read a column, lane l at dword 2 * (l * pitch + tt) -- ds_read_b64 banks are (a / 4) % 64 per 32-lane half, so the 32 lanes of a half
+// must hit 32 distinct even banks: 2 * l * pitch mod 64 distinct for l < 32, which holds exactly for an odd pitch.  64 would be 32-way.
+constexpr int PT_PITCH = PT + 1;
+
+// out = Y + instruments stem of D and nothing else.  SPEC: grid (elements / 256, song) as the plain table form.  ROWS: grid (frame tiles,
+// bin tiles x channel, song), 256 threads; the tile is read along t (mask, D, Y rows coalesced), written along the bin (out rows coalesced).
+// Edge tiles are masked: no read or write outside [0, T) x [0, bins).
+template <bool CPLX, bool ROWS>
+__device__ __forceinline__ void pseudo_apply(const SongSeg* __restrict__ songs, const PseudoSeg* __restrict__ pst, int bins,
+                                             const float* __restrict__ ma, int Wa, const float* __restrict__ mb, int Wb, int shift,
+                                             const float* __restrict__ wgt) {
+    const SongSeg sg = songs[ROWS ? blockIdx.z : blockIdx.y];
+    const PseudoSeg ps = pst[ROWS ? blockIdx.z : blockIdx.y];
+    const int T = sg.T;
+    ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
+    if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
+    if (wgt) wgt += sg.frame0;
+    if constexpr (!ROWS) {
+        const long long total = 2LL * bins * T;
+        const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (gid >= total) return;
+        const int t = (int)(gid % T);
+        const long long row = gid / T;
+        ps.out[gid] = add_rounded(ps.inst[gid], instruments_stem<CPLX>(ma, Wa, mb, Wb, shift, wgt, row, t, sg.spec[gid]));
+    } else {
+        __shared__ float2 tl[PT * PT_PITCH];
+        const int t0 = blockIdx.x * PT;
+        if (t0 >= T) return;                         // (the grid is sized for the longest song; uniform per workgroup)
+        const int ch = blockIdx.y & 1, k0 = (blockIdx.y >> 1) * PT;
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        {
+            const int t = t0 + lane;
+            for (int kk = w; kk < PT; kk += 4) {
+                const int k = k0 + kk;
+                if (k < bins && t < T) {
+                    const long long row = (long long)ch * bins + k;
+                    const long long e = row * T + t;
+                    tl[kk * PT_PITCH + lane] = add_rounded(ps.inst[e], instruments_stem<CPLX>(ma, Wa, mb, Wb, shift, wgt, row, t, sg.spec[e]));
+                }
+            }
+        }
+        __syncthreads();
+        const int k = k0 + lane;
+        for (int tt = w; tt < PT; tt += 4) {
+            const int t = t0 + tt;
+            if (k < bins && t < T) ps.out[((long long)t * 2 + ch) * bins + k] = tl[lane * PT_PITCH + tt];
+        }
+    }
+}
+
+// D = X - Y over the song table (the pair front end of a spectrogram-level call): blockIdx = (row of [2][bins], song), 256 threads; the
+// row's 64-bit offset is formed once, the lanes stream it; no atomics
+__device__ __forceinline__ void pseudo_diff(const SongSeg* __restrict__ songs, const PseudoSeg* __restrict__ pst) {
+    const SongSeg sg = songs[blockIdx.y];
+    const PseudoSeg ps = pst[blockIdx.y];
+    const long long base = (long long)blockIdx.x * sg.T;
+    const float2* __restrict__ x = ps.mix + base;
+    const float2* __restrict__ y = ps.inst + base;
+    float2* __restrict__ d = sg.spec + base;
+    for (int t = threadIdx.x; t < sg.T; t += 256) d[t] = sub_rounded(x[t], y[t]);
+}
+
 // CPLX: complex64 masks, complex products (final_mask: TTA average and merge_artifacts blend of a complex mask)
-template <bool CPLX, class SRC = const float2>
+// PS (at most one type, SRC = const SongSeg): PseudoSpec / PseudoRows = the pseudo back ends above, PseudoDiff = the elementwise pair front
+// end -- under this kernel's name, like every form of this file, so that the launch profiler's report keeps one name per stage
+template <bool CPLX, class SRC = const float2, class... PS>
 __global__ void apply_mask_kernel(SRC* __restrict__ src, int bins, int T, const float* __restrict__ ma,
                                   int Wa, const float* __restrict__ mb, int Wb, int shift, const float* __restrict__ wgt,
-                                  float2* __restrict__ y, float2* __restrict__ v) {
+                                  float2* __restrict__ y, float2* __restrict__ v, PS... ps) {
+    static_assert(sizeof...(PS) <= 1 && (sizeof...(PS) == 0 || kSongTable<SRC>), "the pseudo forms are song-table forms");
+    if constexpr (kHasType<PseudoDiff, PS...>) {
+        pseudo_diff(src, pcm_first(ps...).ps);
+        return;
+    } else if constexpr (sizeof...(PS) == 1) {
+        pseudo_apply<CPLX, kHasType<PseudoRows, PS...>>(src, pcm_first(ps...).ps, bins, ma, Wa, mb, Wb, shift, wgt);
+        return;
+    }
     const float2* __restrict__ spec;
     if constexpr (kSongTable<SRC>) {                 // blockIdx.y = song, its own y / v
         const SongSeg sg = src[blockIdx.y];
@@ -1324,6 +1461,48 @@ void launch_istft_masked_many(const FFTPlan& pl, const SongSeg* songs, int n_son
         static std::atomic<unsigned long long> attr_done{0};
         ensure_lds_attr(attr_done, reinterpret_cast<const void*>(istft_tile_kernel<false, const SongSeg>), 160 * 1024);
         VR_LAUNCH((istft_tile_kernel<false, const SongSeg>), grid, dim3(1024), lds, st, pl, songs, 0, S, mask, W, mb, W, 0, wgt, which, nullptr, 0LL);
+    }
+    VR_HIP(hipGetLastError());
+}
+
+// ---- pseudo-instrument labels (vr_pseudo*) -----------------------------------------------------------------------
+void launch_stft_pseudo_many(const FFTPlan& pl, const SongSeg* songs, const PseudoSeg* ps, int n_songs, int max_T, double sum_L, double sum_T,
+                             hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const SongSeg, const PseudoSeg*>), 160 * 1024);
+    prof_note(0.0, 2.0 * 2.0 * (4.0 * sum_L + 8.0 * (double)bins * sum_T));         // two waves read, Y and D written
+    VR_LAUNCH((stft_tile_kernel<const SongSeg, const PseudoSeg*>), dim3((unsigned)((max_T + F - 1) / F), 2, n_songs), dim3(1024), lds, st, pl, songs, 0LL,
+              0, F, (float2*)nullptr, ps);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_pseudo_diff_many(const SongSeg* songs, const PseudoSeg* ps, int n_songs, int bins, double sum_T, hipStream_t st) {
+    prof_note(0.0, 2.0 * (double)bins * 24.0 * sum_T);
+    VR_LAUNCH((apply_mask_kernel<false, const SongSeg, PseudoDiff>), dim3(2 * bins, n_songs), dim3(256), 0, st, songs, bins, 0, (const float*)nullptr, 0,
+              (const float*)nullptr, 0, 0, (const float*)nullptr, (float2*)nullptr, (float2*)nullptr, PseudoDiff{ps});
+    VR_HIP(hipGetLastError());
+}
+
+void launch_apply_mask_pseudo_many(const SongSeg* songs, const PseudoSeg* ps, int n_songs, int max_T, int bins, const float* mask, int W, int tta,
+                                   bool cplx, const float* wgt, bool rows, double sum_T, hipStream_t st) {
+    const float* mb = tta ? mask : nullptr;
+    prof_note(0.0, 2.0 * (double)bins * sum_T * (24.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1)));          // D, Y read, P written, the mask(s)
+    if (rows) {
+        const dim3 grid((max_T + PT - 1) / PT, 2 * ((bins + PT - 1) / PT), n_songs);
+        const PseudoRows a{ps};
+        if (cplx) VR_LAUNCH((apply_mask_kernel<true, const SongSeg, PseudoRows>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr, a);
+        else VR_LAUNCH((apply_mask_kernel<false, const SongSeg, PseudoRows>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr, a);
+    } else {
+        const long long total = 2LL * bins * max_T;
+        const dim3 grid((unsigned)((total + 255) / 256), n_songs);
+        const PseudoSpec a{ps};
+        if (cplx) VR_LAUNCH((apply_mask_kernel<true, const SongSeg, PseudoSpec>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr, a);
+        else VR_LAUNCH((apply_mask_kernel<false, const SongSeg, PseudoSpec>), grid, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, nullptr, nullptr, a);
     }
     VR_HIP(hipGetLastError());
 }

@@ -484,6 +484,49 @@ def make_training_set(filelist, sr, hop_length, n_fft):
     return rows
 
 
+def load_aligned_pair(mix_path, inst_path, sr):
+    """The two waves of a pair as SpectrogramCache.pair decodes and aligns them: -> mixture, instrumental [2, L] float32."""
+    from . import audio
+    from .spec_utils import align_wave_head_and_tail
+    waves = [audio.load(p, sr=sr, mono=False, dtype=np.float32, res_type='kaiser_fast')[0] for p in (mix_path, inst_path)]
+    waves = [np.asarray([w, w]) if w.ndim == 1 else w for w in waves]
+    return align_wave_head_and_tail(waves[0], waves[1], sr)
+
+
+def pseudo_cache_path(cache, inst_path):
+    """<instrumental's cache dir>/<instrumental's basename>_PseudoInstruments.npy"""
+    return cache.npy_path(inst_path)[:-len('.npy')] + '_PseudoInstruments.npy'
+
+
+def make_pseudo_training_set(sp, filelist, sr, hop_length, n_fft, songs_per_call=8, tta=True):
+    """make_training_set with the instrumental of every pair replaced by its pseudo-instrument label (the reference's pseudo.py:40-74):
+    the pairs go through sp.pseudo_instruments_wave_many(layout='rows') in groups of `songs_per_call`, and the rows [T, 2, bins] are
+    saved as the device wrote them -- the cache's layout, no host transpose -- as <inst cache dir>/<inst basename>_PseudoInstruments.npy;
+    the mixture's cache is written as SpectrogramCache.pair writes it.  -> [[mixture cache path, label cache path, peak], ...], the list
+    VocalRemoverTrainingSet / ResidentTrainingSet take, peak = max(|X|.max(), |P|.max()) formed on the host as in make_training_set."""
+    from .spec_utils import SpectrogramCache, wave_to_spectrogram
+    cache = SpectrogramCache(sr, hop_length, n_fft)
+    filelist = list(filelist)
+    step = max(int(songs_per_call), 1)
+    rows = []
+    for g in range(0, len(filelist), step):
+        group = filelist[g:g + step]
+        pairs = [load_aligned_pair(m, i, sr) for m, i in group]
+        labels = sp.pseudo_instruments_wave_many([X for X, _ in pairs], [y for _, y in pairs], tta=tta, layout='rows')
+        for (mix_path, inst_path), (Xw, _), P in zip(group, pairs, labels):
+            P = P if isinstance(P, np.ndarray) else P.cpu().numpy()
+            mix_npy, out_npy = cache.npy_path(mix_path), pseudo_cache_path(cache, inst_path)
+            if os.path.exists(mix_npy):
+                x_peak = np.abs(np.load(mix_npy, mmap_mode='r')).max()
+            else:
+                X = wave_to_spectrogram(Xw, hop_length, n_fft)
+                np.save(mix_npy, X.transpose(2, 0, 1))
+                x_peak = np.abs(X).max()
+            np.save(out_npy, P)
+            rows.append([mix_npy, out_npy, np.max([x_peak, np.abs(P).max()])])
+    return rows
+
+
 def make_validation_set(filelist, cropsize, sr, hop_length, n_fft, offset):
     """Cuts every validation song into ceil(T / roi) windows of `cropsize` frames, `roi` apart, of the peak-normalised,
     make_padding-padded spectrogram pair and stores each once as cs{}_sr{}_hl{}_nf{}_of{}/<song>_p<j>.npz; returns the paths."""

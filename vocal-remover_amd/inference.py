@@ -241,6 +241,89 @@ class Separator(object):
             1 if on_dev else 0))
         return self._scored(sums, (y, v) if stems else None)
 
+    def pseudo_instruments(self, X_spec, y_spec, tta=True, layout='spec'):
+        """The reference's pseudo.py:67-70 for one pair, on the device: y_spec + separate[_tta](X_spec - y_spec)[0] (vr_pseudo).
+        X_spec, y_spec: complex64 [2, bins, T], numpy arrays or cuda tensors (a cuda result for cuda inputs).  layout 'spec' gives
+        [2, bins, T] (what pseudo.py saves), 'rows' gives [T, 2, bins] (the training cache's rows).  Honours self.postprocess."""
+        return self._pseudo([X_spec], [y_spec], tta, layout, waves=False, one=True)[0]
+
+    def pseudo_instruments_many(self, X_specs, y_specs, tta=True, layout='spec'):
+        """pseudo_instruments for a list of pairs in ONE library call (vr_pseudo_many): each result is what the pair gives alone; the
+        crops of all pairs and of both TTA passes share device batches of `self.batchsize` crops, as in separate_many."""
+        return self._pseudo(X_specs, y_specs, tta, layout, waves=False, one=False)
+
+    def pseudo_instruments_wave(self, mix, inst, tta=True, layout='spec'):
+        """pseudo_instruments of the spectrograms of two aligned waves [2, L] of the same length (vr_pseudo_wave): both transforms run
+        in one launch and the mixture's spectrogram is never stored.  T = 1 + L // hop frames.  Needs hop_length == n_fft / 2."""
+        return self._pseudo([mix], [inst], tta, layout, waves=True, one=True)[0]
+
+    def pseudo_instruments_wave_many(self, mixes, insts, tta=True, layout='spec'):
+        """pseudo_instruments_wave for a list of pairs in ONE library call (vr_pseudo_wave_many)."""
+        return self._pseudo(mixes, insts, tta, layout, waves=True, one=False)
+
+    def _pseudo(self, mixes, insts, tta, layout, waves, one):
+        h = self.model._need_handle()
+        hop, bins = self.model.hop_length, self.model.output_bin
+        if layout not in native.PSEUDO_LAYOUTS:
+            raise ValueError("layout must be 'spec' or 'rows'")
+        mixes, insts = list(mixes), list(insts)
+        if not mixes or len(mixes) != len(insts):
+            raise ValueError('pseudo_instruments needs at least one pair and as many instrumentals as mixtures')
+        self.model.eval()
+        try:
+            import torch
+        except ImportError:              # pragma: no cover
+            torch = None
+        both = mixes + insts
+        on_dev = torch is not None and all(torch.is_tensor(a) and a.is_cuda for a in both)
+        if on_dev:
+            dt = torch.float32 if waves else torch.complex64
+            mixes = [a.detach().to(dt).contiguous() for a in mixes]
+            insts = [a.detach().to(dt).contiguous() for a in insts]
+        else:
+            if torch is not None and any(torch.is_tensor(a) and a.is_cuda for a in both):
+                raise ValueError('pseudo_instruments: either every input is a cuda tensor or none is')
+            dt = np.float32 if waves else np.complex64
+            mixes = [np.ascontiguousarray(np.asarray(a).astype(dt)) for a in mixes]
+            insts = [np.ascontiguousarray(np.asarray(a).astype(dt)) for a in insts]
+        N = len(mixes)
+        who = (lambda s: '') if one else (lambda s: 'song %d: ' % s)
+        for s, (X, y) in enumerate(zip(mixes, insts)):
+            if tuple(X.shape) != tuple(y.shape):
+                raise ValueError('%sthe mixture is %s and its instrumental %s' % (who(s), tuple(X.shape), tuple(y.shape)))
+            if waves and (X.ndim != 2 or X.shape[0] != 2):
+                raise ValueError('%severy wave must be [2, L]' % who(s))
+            if not waves and (X.ndim != 3 or X.shape[0] != 2 or X.shape[1] != bins):
+                raise ValueError('%severy spectrogram must be [2, %d, T]' % (who(s), bins))
+        lens = [int(X.shape[-1]) for X in mixes]
+        # (an empty input has no usable pointer; the library reports it before it reads any: its message is raised here already)
+        for s, n in enumerate(lens):
+            if waves and n < hop:
+                raise ValueError('%swave shorter than one hop' % who(s))
+            if not waves and n <= 0:
+                raise ValueError('%sempty spectrogram' % who(s))
+        Ts = [1 + n // hop for n in lens] if waves else lens
+        shape = (lambda T: (T, 2, bins)) if layout == 'rows' else (lambda T: (2, bins, T))
+        if on_dev:
+            outs = [torch.empty(shape(T), dtype=torch.complex64, device=mixes[0].device) for T in Ts]
+            torch.cuda.current_stream(mixes[0].device).synchronize()
+            addr = lambda a: a.data_ptr()
+        else:
+            outs = [np.empty(shape(T), dtype=np.complex64) for T in Ts]
+            addr = lambda a: a.ctypes.data
+        ct, L, dev = native.ctypes, native.lib(), 1 if on_dev else 0
+        args = (self._flags(tta), int(self.batchsize), int(self.cropsize), native.PSEUDO_LAYOUTS[layout])
+        if one:
+            fn = L.vr_pseudo_wave if waves else L.vr_pseudo
+            native.check(fn(h.h, addr(mixes[0]), addr(insts[0]), dev, lens[0], *args, addr(outs[0]), dev))
+        else:
+            table = lambda seq: native.ptr_table([addr(a) for a in seq])
+            if waves:
+                native.check(L.vr_pseudo_wave_many(h.h, N, table(mixes), table(insts), dev, (ct.c_int64 * N)(*lens), *args, table(outs), dev))
+            else:
+                native.check(L.vr_pseudo_many(h.h, N, table(mixes), table(insts), dev, (ct.c_int * N)(*lens), *args, table(outs), dev))
+        return outs
+
     def separate_pcm(self, raw, tta=False):
         """separate_wave with the file's bytes at both ends: raw = audio.RawPcm (audio.read_wav_raw: PCM16 / 24 / 32 or float32 frames of
         1 or 2 channels) -> (instruments, vocals) as int16 [hop*(frames//hop), 2], ready for audio.write_pcm16 -- exactly

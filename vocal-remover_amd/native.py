@@ -15,6 +15,8 @@ VR_LOSS_L1, VR_LOSS_MAG_L1_WAVE_SDR, VR_LOSS_MAG_L1_WAVE_WSDR = 0, 1, 3         
 LOSS_KINDS = {'l1': VR_LOSS_L1, 'mag_l1_wave_sdr': VR_LOSS_MAG_L1_WAVE_SDR, 'mag_l1_wave_wsdr': VR_LOSS_MAG_L1_WAVE_WSDR}
 VR_STREAM_TTA, VR_STREAM_MEASURE, VR_STREAM_POSTPROCESS, VR_STREAM_PCM16_OUT = 1, 2, 4, 8
 VR_PCM_S16, VR_PCM_S24, VR_PCM_S32, VR_PCM_F32 = 1, 2, 3, 4          # enum vr_pcm_format
+VR_PSEUDO_SPEC, VR_PSEUDO_ROWS = 0, 1          # enum vr_pseudo_layout
+PSEUDO_LAYOUTS = {'spec': VR_PSEUDO_SPEC, 'rows': VR_PSEUDO_ROWS}
 PCM_SAMPLE_BYTES = {VR_PCM_S16: 2, VR_PCM_S24: 3, VR_PCM_S32: 4, VR_PCM_F32: 4}
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 
@@ -51,6 +53,16 @@ _SIGNATURES = {
     'vr_evaluate_wave': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int]),
     'vr_evaluate_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, c_i64p, c_i64p]),
+    'vr_pseudo_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_pseudo_wave_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.c_int, c_i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_pseudo': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_int, c_f32p, ctypes.c_int]),
+    'vr_pseudo_wave': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, c_f32p, ctypes.c_int]),
     'vr_pcm_available': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     'vr_stft_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int]),
     'vr_istft_pcm16': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
