@@ -290,6 +290,39 @@ int vr_pseudo(vr_handle h, const float* mix_spec, const float* inst_spec, int on
 int vr_pseudo_wave(vr_handle h, const float* mix_wave, const float* inst_wave, int on_device, int64_t L, int tta, int batchsize, int cropsize,
                    int layout, float* out, int out_on_device);
 
+/* ---- pitch-shifted waves and training pairs (the reference's augment.py), many per call ---------------------------------------------------
+ * The shift of one signal y of L samples is librosa.effects.pitch_shift's, not SoundTouch's (DESIGN.md section 6r says why), with
+ * rate = 2 ** (-n_steps / bins_per_octave) and ratio = sr / (float(sr) / rate), both formed by the caller in double:
+ *     D  = stft(y, n_fft, hop)                         periodic Hann, centre zero pad, T = 1 + L / hop
+ *     D' = phase_vocoder(D, rate, hop)                 T_stretch = ceil(T / rate) frames; the phase is accumulated in double
+ *     ys = istft(D', hop, length = round(L / rate))    n_stretch samples
+ *     z  = fix_length(resample(ys, ratio), L)          'kaiser_fast': int(n_stretch * ratio) samples computed, n_resampled =
+ *                                                      ceil(n_stretch * ratio) with the zero tail, then cut or zero-padded to L
+ *   vr_pitch_plan        no handle, no device: the four lengths, from the expressions the launches use (L < n_fft: VR_ERR_BAD_ARGUMENT)
+ *   vr_phase_vocoder     spec [signals][bins][T] complex64 -> out [signals][bins][ceil(T / rate)], bins and hop the handle's
+ *   vr_istft_length      vr_istft with librosa's length=: wave [2][length] = the overlap-add behind the n_fft / 2 in front, cut or
+ *                        followed by zeros; always the per-frame kernels, whatever the hop
+ *   vr_resample_ratio    vr_resample for a ratio that is no quotient of two integer rates (vr_resample is this at (double)sr_out / sr_in)
+ *   vr_pitch_shift_many  waves[i] [channels][L[i]] -> out[i] of the same shape, shifted at the handle's n_fft / hop_length
+ *   vr_pitch_pair_many   mix[i], inst[i] float32 [2][L[i]], aligned: y' = shift(inst), v' = shift(mix - inst) (one float32 subtraction per
+ *                        sample), X' = y' + v' (one float32 addition), the shifts at shift_n_fft / shift_hop; X_out[i] / y_out[i] = the
+ *                        STFTs of X' / y' at the handle's n_fft / hop_length, T = 1 + L[i] / hop_length frames, as [2][bins][T]
+ *                        (VR_PSEUDO_SPEC) or [T][2][bins] (VR_PSEUDO_ROWS: hop_length == n_fft / 2 only).  The pair's peak
+ *                        max(max|X'|, max|y'|) is not an output: the caller takes it from the stored values, as for every cache
+ * The items of a call run one after the other through one workspace, sized for the largest item: its spectrogram at the shift's hop, the
+ * stretched one and the inverse transform's frames, about 210 bytes per sample of a pair at 2048 / 512 and rate near 1 (1.7 GB for 180 s at 44.1 kHz).  It is checked against max_bytes
+ * (<= 0: nine tenths of the free device memory) before anything is allocated: VR_ERR_OOM, and vr_last_error() names both sizes.  Nothing
+ * is accumulated with atomics: two identical calls agree bit for bit.                                                                */
+int vr_pitch_plan(int64_t L, int n_fft, int hop, double rate, double ratio, int* T, int* T_stretch, int64_t* n_stretch, int64_t* n_resampled);
+int vr_phase_vocoder(vr_handle h, const float* spec, int on_device, int signals, int T, double rate, float* out, int out_on_device);
+int vr_istft_length(vr_handle h, const float* spec, int spec_on_device, int T, int64_t length, float* wave, int wave_on_device);
+int vr_resample_ratio(int device, const float* x, int channels, int64_t n_in, double ratio, float* y, int64_t n_out);
+int vr_pitch_shift_many(vr_handle h, int n, const float* const* waves, int on_device, int channels, const int64_t* L, double rate, double ratio,
+                        int64_t max_bytes, float* const* out, int out_on_device);
+int vr_pitch_pair_many(vr_handle h, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L, int shift_n_fft,
+                       int shift_hop, double rate, double ratio, int layout, int64_t max_bytes, float* const* X_out, float* const* y_out,
+                       int out_on_device);
+
 /* ---- streaming separation: push audio in blocks, get the stems back with bounded state -----------------------------------
  * The offline call's crops sit at multiples of roi = cropsize - 2 * offset whatever the song's length (make_padding: pad_l = offset),
  * the --tta pass is the same list shifted by roi / 2, and with hop == n_fft / 2 frame t needs the samples below (t + 1) * hop.  The

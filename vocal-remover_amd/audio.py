@@ -265,6 +265,179 @@ def resample(y, orig_sr, target_sr, res_type='kaiser_fast'):
     return out[0] if mono else out
 
 
+def _on_device(x):
+    torch = _torch()
+    return torch is not None and torch.is_tensor(x) and x.is_cuda
+
+
+def _float_in(x):
+    """-> (contiguous float32 numpy array or cuda tensor, its address, on the device)"""
+    if _on_device(x):
+        torch = _torch()
+        x = x.detach().to(torch.float32).contiguous()
+        torch.cuda.current_stream(x.device).synchronize()
+        return x, x.data_ptr(), True
+    torch = _torch()
+    x = np.ascontiguousarray(np.asarray(x.detach().cpu().numpy() if torch is not None and torch.is_tensor(x) else x, dtype=np.float32))
+    return x, x.ctypes.data, False
+
+
+def _like_out(shape, like, on_dev, dtype=np.float32):
+    """an output buffer beside `like`: -> (array or cuda tensor, its address)"""
+    if on_dev:
+        torch = _torch()
+        y = torch.empty(shape, dtype=torch.complex64 if dtype == np.complex64 else torch.float32, device=like.device)
+        torch.cuda.current_stream(like.device).synchronize()
+        return y, y.data_ptr()
+    y = np.empty(shape, dtype=dtype)
+    return y, y.ctypes.data
+
+
+def resample_by(y, ratio):
+    """The 'kaiser_fast' resampler for any ratio (librosa.effects.pitch_shift resamples by sr / (sr / rate), no quotient of two integer
+    rates): [..., n] -> [..., ceil(n * ratio)] float32, int(n * ratio) samples computed and zeros behind them.  resample(y, a, b) is this
+    at float(b) / a.  numpy in, numpy out; a torch cuda tensor in, a cuda tensor out (the samples cross the host: vr_resample_ratio, like
+    vr_resample, takes host memory)."""
+    on_dev = _on_device(y)
+    x, _, _ = _float_in(y.cpu() if on_dev else y)
+    ratio = float(ratio)
+    if not ratio > 0:
+        raise ValueError('ratio must be positive')
+    rows = np.ascontiguousarray(x.reshape(-1, x.shape[-1]))
+    n_out = int(np.ceil(rows.shape[1] * ratio))
+    out = np.empty((rows.shape[0], n_out), dtype=np.float32)
+    native.check(native.lib().vr_resample_ratio(_device(), native.np_ptr(rows), rows.shape[0], rows.shape[1], ratio, native.np_ptr(out), n_out))
+    out = out.reshape(x.shape[:-1] + (n_out,))
+    return _torch().from_numpy(out).to(y.device) if on_dev else out
+
+
+def fix_length(y, size):
+    """librosa.util.fix_length along the last axis: cut, or zeros behind"""
+    n = int(y.shape[-1])
+    if n >= size:
+        return y[..., :size]
+    if _on_device(y):
+        return _torch().nn.functional.pad(y, (0, size - n))
+    return np.concatenate([y, np.zeros(y.shape[:-1] + (size - n,), y.dtype)], axis=-1)
+
+
+def _stereo(y):
+    """[L] or [2, L] -> ([2, L], was 1-D)"""
+    if y.ndim == 1:
+        return (_torch().stack([y, y]) if _on_device(y) else np.asarray([y, y])), True
+    if y.ndim != 2 or y.shape[0] != 2:
+        raise ValueError('wave must be [L] or [2, L]')
+    return y, False
+
+
+def time_stretch(y, rate, n_fft=2048, hop_length=None):
+    """librosa.effects.time_stretch(y, rate=rate, n_fft=n_fft, hop_length=hop_length): [L] or [2, L] -> int(round(L / rate)) samples,
+    stft -> phase_vocoder -> istft(length) through the public calls of spec_utils."""
+    from . import spec_utils
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    y, flat = _stereo(y if _on_device(y) else np.asarray(y, dtype=np.float32))
+    L = int(y.shape[-1])
+    if L < n_fft:
+        raise ValueError('time_stretch: the wave has %d samples, fewer than n_fft = %d' % (L, n_fft))
+    D = spec_utils.phase_vocoder(spec_utils.wave_to_spectrogram(y, hop, n_fft), rate, hop)
+    out = spec_utils.spectrogram_to_wave(D, hop, length=int(round(L / float(rate))))
+    return out[0] if flat else out
+
+
+def pitch_rate_and_ratio(sr, n_steps, bins_per_octave=12):
+    """-> (rate, ratio) of librosa.effects.pitch_shift, each evaluated once, in its order, in double"""
+    rate = 2.0 ** (-float(n_steps) / bins_per_octave)
+    return rate, sr / (float(sr) / rate)
+
+
+def pitch_shift_many(waves, sr, n_steps, bins_per_octave=12, n_fft=2048, hop_length=None, max_bytes=None):
+    """pitch_shift of every wave in ONE library call (vr_pitch_shift_many): waves[i] [L_i] or [channels, L_i], any lengths >= n_fft, one
+    channel count; -> the shifted waves, same shapes.  Either every wave is a numpy array (numpy out) or every wave is a cuda tensor
+    (cuda out).  max_bytes: the device workspace the call may take (the largest wave's spectrograms; MemoryError names the need)."""
+    from . import spec_utils
+    ct = native.ctypes
+    waves = list(waves)
+    if not waves:
+        return []
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    rate, ratio = pitch_rate_and_ratio(sr, n_steps, bins_per_octave)
+    ins = [_float_in(w) for w in waves]
+    if any(on for _, _, on in ins) and not all(on for _, _, on in ins):
+        raise ValueError('pitch_shift_many: either every wave is a cuda tensor or none is')
+    on_dev = ins[0][2]
+    rows = [x.reshape(1, -1) if x.ndim == 1 else x for x, _, _ in ins]
+    if any(r.ndim != 2 or r.shape[0] != rows[0].shape[0] for r in rows):
+        raise ValueError('pitch_shift_many: waves must be [L] or [channels, L] with one channel count')
+    for r in rows:
+        if r.shape[1] < n_fft:
+            raise ValueError('pitch_shift: the wave has %d samples, fewer than n_fft = %d' % (r.shape[1], n_fft))
+    outs = [_like_out(tuple(x.shape), x, on_dev) for x, _, _ in ins]
+    N = len(rows)
+    rc = native.lib().vr_pitch_shift_many(
+        spec_utils._signal_handle(n_fft, hop).h, N, (ct.c_void_p * N)(*[p for _, p, _ in ins]), 1 if on_dev else 0, int(rows[0].shape[0]),
+        (ct.c_int64 * N)(*[int(r.shape[1]) for r in rows]), rate, ratio, int(max_bytes or 0), (ct.c_void_p * N)(*[p for _, p in outs]),
+        1 if on_dev else 0)
+    _check_workspace(rc)
+    return [y for y, _ in outs]
+
+
+def _check_workspace(rc):
+    if rc == -4:
+        raise MemoryError(native.lib().vr_last_error().decode('utf-8', 'replace'))
+    native.check(rc)
+
+
+def pitch_shift(y, sr, n_steps, bins_per_octave=12, n_fft=2048, hop_length=None):
+    """librosa.effects.pitch_shift(y, sr=sr, n_steps=n_steps, bins_per_octave=..., res_type='kaiser_fast', n_fft=..., hop_length=...):
+    time_stretch by rate = 2 ** (-n_steps / bins_per_octave), resample_by(sr / (sr / rate)), fix_length to the input's length -- as one
+    device pipeline.  n_steps = 0 runs all of it.  [L] or [channels, L], numpy or cuda, L >= n_fft."""
+    return pitch_shift_many([y], sr, n_steps, bins_per_octave, n_fft, hop_length)[0]
+
+
+def pitch_pair_many(mixes, insts, sr, n_steps, hop_length, n_fft, bins_per_octave=12, shift_n_fft=2048, shift_hop_length=None, layout='rows',
+                    max_bytes=None):
+    """The pitch-shifted copies of (mixture, instrumental) pairs of aligned waves [2, L_i], many per call (vr_pitch_pair_many; the
+    reference's augment.py:54-73): y' = pitch_shift(y), v' = pitch_shift(X - y), X' = y' + v', each in float32.  -> (X specs, y specs,
+    peaks): the STFTs of X' and y' at n_fft / hop_length as [T, 2, bins] (layout 'rows', the training cache's) or [2, bins, T] ('spec')
+    complex64, and peak_i = max(|X'|.max(), |y'|.max()), taken on the host with numpy.  numpy in, numpy out; cuda tensors in, cuda tensors out."""
+    from . import spec_utils
+    ct = native.ctypes
+    mixes, insts = list(mixes), list(insts)
+    if len(mixes) != len(insts):
+        raise ValueError('pitch_pair_many: %d mixtures but %d instrumentals' % (len(mixes), len(insts)))
+    if not mixes:
+        return [], [], []
+    if layout not in native.PSEUDO_LAYOUTS:
+        raise ValueError("layout must be 'rows' or 'spec'")
+    shift_hop = shift_n_fft // 4 if shift_hop_length is None else int(shift_hop_length)
+    rate, ratio = pitch_rate_and_ratio(sr, n_steps, bins_per_octave)
+    xs, ys = [_float_in(w) for w in mixes], [_float_in(w) for w in insts]
+    flags = [on for _, _, on in xs + ys]
+    if any(flags) and not all(flags):
+        raise ValueError('pitch_pair_many: either every wave is a cuda tensor or none is')
+    on_dev = flags[0]
+    for (x, _, _), (y, _, _) in zip(xs, ys):
+        if x.ndim != 2 or x.shape[0] != 2 or tuple(x.shape) != tuple(y.shape):
+            raise ValueError('pitch_pair_many: a pair is two waves [2, L] of one length')
+        if x.shape[1] < shift_n_fft:
+            raise ValueError('pitch_shift: the wave has %d samples, fewer than n_fft = %d' % (x.shape[1], shift_n_fft))
+    bins = n_fft // 2 + 1
+    shapes = [((1 + int(x.shape[1]) // hop_length, 2, bins) if layout == 'rows' else (2, bins, 1 + int(x.shape[1]) // hop_length)) for x, _, _ in xs]
+    Xo = [_like_out(sh, x, on_dev, np.complex64) for sh, (x, _, _) in zip(shapes, xs)]
+    yo = [_like_out(sh, x, on_dev, np.complex64) for sh, (x, _, _) in zip(shapes, xs)]
+    N = len(xs)
+    rc = native.lib().vr_pitch_pair_many(
+        spec_utils._signal_handle(n_fft, hop_length).h, N, (ct.c_void_p * N)(*[p for _, p, _ in xs]), (ct.c_void_p * N)(*[p for _, p, _ in ys]),
+        1 if on_dev else 0, (ct.c_int64 * N)(*[int(x.shape[1]) for x, _, _ in xs]), int(shift_n_fft), shift_hop, rate, ratio,
+        native.PSEUDO_LAYOUTS[layout], int(max_bytes or 0), (ct.c_void_p * N)(*[p for _, p in Xo]), (ct.c_void_p * N)(*[p for _, p in yo]),
+        1 if on_dev else 0)
+    _check_workspace(rc)
+    # the peak on the host with numpy, as make_training_set and make_pseudo_training_set form it: the library returns none
+    host = (lambda a: a.cpu().numpy()) if on_dev else (lambda a: a)
+    peaks = [np.max([np.abs(host(X)).max(), np.abs(host(y)).max()]) for (X, _), (y, _) in zip(Xo, yo)]
+    return [a for a, _ in Xo], [a for a, _ in yo], peaks
+
+
 class StreamResampler(object):
     """resample() on blocks with bounded state (vr_resampler_*): push(x [channels, n]) -> every output sample that has become final
     (possibly none), flush() -> the rest; the concatenation IS resample(whole input, orig_sr, target_sr), bit for bit, however the input

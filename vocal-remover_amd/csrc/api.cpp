@@ -8,6 +8,7 @@
 
 namespace vr {
 void resample_api(int device, const float* x, int channels, long long n_in, int sr_in, int sr_out, float* y, long long n_out);
+void resample_ratio_api(int device, const float* x, int channels, long long n_in, double ratio, float* y, long long n_out);
 void xcorr_argmax_api(int device, const float* a, long long na, const float* b, long long nb, long long* argmax_out);
 struct Resampler;
 long long resampler_plan(int sr_in, int sr_out, long long samples_in, bool flushed);
@@ -761,6 +762,64 @@ int vr_resample(int device, const float* x, int channels, int64_t n_in, int sr_i
         VR_CHECK(x && y, VR_ERR_BAD_ARGUMENT, "null argument");
         need_device(device);
         vr::resample_api(device, x, channels, n_in, sr_in, sr_out, y, n_out);
+    });
+}
+
+int vr_resample_ratio(int device, const float* x, int channels, int64_t n_in, double ratio, float* y, int64_t n_out) {
+    return guard([&] {
+        VR_CHECK(x && y, VR_ERR_BAD_ARGUMENT, "null argument");
+        need_device(device);
+        vr::resample_ratio_api(device, x, channels, n_in, ratio, y, n_out);
+    });
+}
+
+// ---- pitch-shifted waves and training pairs (csrc/pitch.hip) --------------------------------------------------------------------
+int vr_pitch_plan(int64_t L, int n_fft, int hop, double rate, double ratio, int* T, int* T_stretch, int64_t* n_stretch, int64_t* n_resampled) {
+    return guard([&] {
+        const vr::PitchPlan p = vr::pitch_plan(L, n_fft, hop, rate, ratio);
+        if (T) *T = p.T;
+        if (T_stretch) *T_stretch = p.T_stretch;
+        if (n_stretch) *n_stretch = p.n_stretch;
+        if (n_resampled) *n_resampled = p.n_resampled;
+    });
+}
+
+int vr_phase_vocoder(vr_handle h, const float* spec, int on_device, int signals, int T, double rate, float* out, int out_on_device) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(spec && out, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.phase_vocoder_api(spec, on_device != 0, signals, T, rate, out, out_on_device != 0);
+    });
+}
+
+int vr_istft_length(vr_handle h, const float* spec, int spec_on_device, int T, int64_t length, float* wave, int wave_on_device) {
+    NEED(h);
+    return guard([&] {
+        VR_CHECK(spec && wave, VR_ERR_BAD_ARGUMENT, "null argument");
+        h->m.istft_length_api(spec, spec_on_device != 0, T, length, wave, wave_on_device != 0);
+    });
+}
+
+int vr_pitch_shift_many(vr_handle h, int n, const float* const* waves, int on_device, int channels, const int64_t* L, double rate, double ratio,
+                        int64_t max_bytes, float* const* out, int out_on_device) {
+    if (n <= 0 || !waves || !L || !out) { g_err = "pitch shift: no item or a null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n);
+        h->m.pitch_run(n, waves, nullptr, on_device != 0, channels, len.data(), h->m.n_fft, h->m.hop, rate, ratio, max_bytes, out, nullptr, nullptr,
+                       0, out_on_device != 0);
+    });
+}
+
+int vr_pitch_pair_many(vr_handle h, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L, int shift_n_fft,
+                       int shift_hop, double rate, double ratio, int layout, int64_t max_bytes, float* const* X_out, float* const* y_out,
+                       int out_on_device) {
+    if (n <= 0 || !mix || !inst || !L || !X_out || !y_out) { g_err = "pitch pair: no item or a null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n);
+        h->m.pitch_run(n, mix, inst, on_device != 0, 2, len.data(), shift_n_fft, shift_hop, rate, ratio, max_bytes, nullptr, X_out, y_out, layout,
+                       out_on_device != 0);
     });
 }
 

@@ -42,7 +42,44 @@ struct ResampleSeg {
     int nwin, precision;
 };
 
-// y[c][t] = sum over both filter wings (resampy.interpn._resample_loop), fp32 accumulator like the float32 output array.
+// One output sample: the sum over both filter wings (resampy.interpn._resample_loop), fp32 accumulator like the float32 output array.
+// xc is the channel's window, whose first sample has the global index g0; n_in is the right-hand clamp.
+__device__ __forceinline__ float resample_sample(const float* __restrict__ xc, long long g0, long long n_in, long long t,
+                                                 const double* __restrict__ win, const double* __restrict__ delta, int nwin, int precision,
+                                                 double sample_ratio) {
+    const double scale = sample_ratio < 1.0 ? sample_ratio : 1.0;
+    const double time_increment = 1.0 / sample_ratio;
+    const int index_step = (int)(scale * precision);
+    const double time_register = (double)t * time_increment;
+    const long long n = (long long)time_register;
+    const long long nw = n - g0;                        // n inside the window
+    double frac = scale * (time_register - (double)n);
+    double index_frac = frac * precision;
+    int offset = (int)index_frac;
+    double eta = index_frac - offset;
+    float acc = 0.f;
+    long long i_max = (nwin - offset) / index_step;
+    if (i_max > n + 1) i_max = n + 1;
+    for (long long i = 0; i < i_max; ++i) {
+        const int k = offset + (int)i * index_step;
+        const double w = win[k] + eta * delta[k];
+        acc = (float)((double)acc + w * (double)xc[nw - i]);
+    }
+    frac = scale - frac;
+    index_frac = frac * precision;
+    offset = (int)index_frac;
+    eta = index_frac - offset;
+    long long k_max = (nwin - offset) / index_step;
+    if (k_max > n_in - n - 1) k_max = n_in - n - 1;
+    for (long long k2 = 0; k2 < k_max; ++k2) {
+        const int k = offset + (int)k2 * index_step;
+        const double w = win[k] + eta * delta[k];
+        acc = (float)((double)acc + w * (double)xc[nw + k2 + 1]);
+    }
+    return acc;
+}
+
+// y[c][t] = resample_sample of channel c.
 // resample_kernel<false> is the offline kernel of vr_resample, argument for argument.  resample_kernel<true> takes a table of ResampleSeg
 // in place of the first pointer (the other arguments are unused) and computes the same taps from global positions: output sample t
 // depends on t alone, so a sample whose right wing lies inside the samples received is already the offline call's sample.
@@ -77,36 +114,38 @@ __global__ void resample_kernel(std::conditional_t<kStream, const ResampleSeg*, 
         xc = x + (long long)c * n_in;
         yo = y + (long long)c * n_out + t;
     }
-    const double scale = sample_ratio < 1.0 ? sample_ratio : 1.0;
-    const double time_increment = 1.0 / sample_ratio;
-    const int index_step = (int)(scale * precision);
-    const double time_register = (double)t * time_increment;
-    const long long n = (long long)time_register;
-    const long long nw = n - g0;                        // n inside the window
-    double frac = scale * (time_register - (double)n);
-    double index_frac = frac * precision;
-    int offset = (int)index_frac;
-    double eta = index_frac - offset;
-    float acc = 0.f;
-    long long i_max = (nwin - offset) / index_step;
-    if (i_max > n + 1) i_max = n + 1;
-    for (long long i = 0; i < i_max; ++i) {
-        const int k = offset + (int)i * index_step;
-        const double w = win[k] + eta * delta[k];
-        acc = (float)((double)acc + w * (double)xc[nw - i]);
+    *yo = resample_sample(xc, g0, n_in, t, win, delta, nwin, precision, sample_ratio);
+}
+
+// The pitch form (librosa.effects.pitch_shift's resample + fix_length): channel c of x [rows][n_in] -> y [c][n_out],
+// samples [0, n_core) computed (n_core = min(int(n_in * ratio), n_out)), zeros behind them.  `sum` (the pair entry): x holds 2 * gridDim.y
+// rows, the instrumental's then the vocals'; sum[c][t] = y[c][t] + the vocals' sample, one float32 addition -- the rebuilt mixture
+// X' = y' + v' costs no pass of its own.
+struct ResampleFix {
+    const float* x;
+    long long n_in, n_core, n_out;
+    float* y;
+    float* sum;               // or null
+    const double* win;
+    const double* delta;
+    int nwin, precision;
+    double ratio;
+};
+
+template <class FORM>
+__global__ void resample_kernel(FORM f) {
+    static_assert(std::is_same<FORM, ResampleFix>::value, "resample_kernel: unknown form");
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (t >= f.n_out) return;
+    const long long o = (long long)c * f.n_out + t;
+    float a = 0.f, b = 0.f;
+    if (t < f.n_core) {
+        a = resample_sample(f.x + (long long)c * f.n_in, 0, f.n_in, t, f.win, f.delta, f.nwin, f.precision, f.ratio);
+        if (f.sum) b = resample_sample(f.x + (long long)(c + gridDim.y) * f.n_in, 0, f.n_in, t, f.win, f.delta, f.nwin, f.precision, f.ratio);
     }
-    frac = scale - frac;
-    index_frac = frac * precision;
-    offset = (int)index_frac;
-    eta = index_frac - offset;
-    long long k_max = (nwin - offset) / index_step;
-    if (k_max > n_in - n - 1) k_max = n_in - n - 1;
-    for (long long k2 = 0; k2 < k_max; ++k2) {
-        const int k = offset + (int)k2 * index_step;
-        const double w = win[k] + eta * delta[k];
-        acc = (float)((double)acc + w * (double)xc[nw + k2 + 1]);
-    }
-    *yo = acc;
+    f.y[o] = a;
+    if (f.sum) f.sum[o] = a + b;
 }
 
 // resampy.filters.sinc_window(num_zeros, precision, kaiser(beta), rolloff): the right half of the windowed sinc
@@ -125,17 +164,24 @@ static void kaiser_sinc_table(int num_zeros, int precision_bits, double rolloff,
     }
 }
 
-void resample_api(int device, const float* x, int channels, long long n_in, int sr_in, int sr_out, float* y, long long n_out) {
-    VR_CHECK(channels > 0 && n_in > 0 && sr_in > 0 && sr_out > 0 && n_out > 0, -2, "resample: bad argument");
-    DeviceGuard dev_guard(device);
-    const double ratio = (double)sr_out / (double)sr_in;
-    VR_CHECK(n_out <= (long long)std::ceil((double)n_in * ratio) + 1, -2, "resample: n_out larger than ceil(n_in * ratio)");
-    std::vector<double> win, delta;
-    kaiser_sinc_table(16, 9, 0.85, 8.555504641634386, win);                           // 'kaiser_fast'
+// the 'kaiser_fast' table as the kernels read it for one ratio: scaled by the ratio when it decimates, and its first differences
+static void kaiser_fast_table(double ratio, std::vector<double>& win, std::vector<double>& delta) {
+    kaiser_sinc_table(16, 9, 0.85, 8.555504641634386, win);
     if (ratio < 1.0) for (double& v : win) v *= ratio;
     delta.resize(win.size());
     for (size_t i = 0; i + 1 < win.size(); ++i) delta[i] = win[i + 1] - win[i];
     delta.back() = 0.0;
+}
+
+// vr_resample_ratio: the resampler for a ratio that is no quotient of two integer rates (librosa.effects.pitch_shift resamples by
+// sr / (sr / rate)); vr_resample is this with ratio = (double)sr_out / sr_in
+void resample_ratio_api(int device, const float* x, int channels, long long n_in, double ratio, float* y, long long n_out) {
+    VR_CHECK(channels > 0 && n_in > 0 && ratio > 0.0 && n_out > 0, -2, "resample: bad argument");
+    VR_CHECK((int)((ratio < 1.0 ? ratio : 1.0) * (1 << 9)) >= 1, -2, "resample: the ratio is below the filter table's resolution (1 / 512)");
+    DeviceGuard dev_guard(device);
+    VR_CHECK(n_out <= (long long)std::ceil((double)n_in * ratio) + 1, -2, "resample: n_out larger than ceil(n_in * ratio)");
+    std::vector<double> win, delta;
+    kaiser_fast_table(ratio, win, delta);
     float *dx = nullptr, *dy = nullptr;
     double *dw = nullptr, *dd = nullptr;
     struct Free { void* p[4]; ~Free() { for (void* q : p) hipFree(q); } } fr{{nullptr, nullptr, nullptr, nullptr}};
@@ -163,6 +209,37 @@ void resample_api(int device, const float* x, int channels, long long n_in, int 
         for (int c = 0; c < channels; ++c)
             VR_HIP(hipMemset(dy + (size_t)c * n_out + n_run, 0, (size_t)(n_out - n_run) * sizeof(float)));
     VR_HIP(hipMemcpy(y, dy, (size_t)channels * n_out * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void resample_api(int device, const float* x, int channels, long long n_in, int sr_in, int sr_out, float* y, long long n_out) {
+    VR_CHECK(sr_in > 0 && sr_out > 0, -2, "resample: bad argument");
+    resample_ratio_api(device, x, channels, n_in, (double)sr_out / (double)sr_in, y, n_out);
+}
+
+// ---- the pitch form: the filter table of one call on the device, and the launch (csrc/pitch.hip) ------------------------------------
+void resample_table_create(double ratio, double** win, double** delta, int* nwin) {
+    VR_CHECK(ratio > 0.0 && (int)((ratio < 1.0 ? ratio : 1.0) * (1 << 9)) >= 1, -2,
+             "pitch: the resampling ratio is below the filter table's resolution (1 / 512)");
+    std::vector<double> w, d;
+    kaiser_fast_table(ratio, w, d);
+    *win = *delta = nullptr;
+    VR_HIP(hipMalloc(win, w.size() * sizeof(double)));
+    VR_HIP(hipMalloc(delta, w.size() * sizeof(double)));
+    VR_HIP(hipMemcpy(*win, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    VR_HIP(hipMemcpy(*delta, d.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    *nwin = (int)w.size();
+}
+
+// x [rows][n_in] -> y [channels][n_out] = fix_length(resample(x, ratio), n_out); sum (or null): x has 2 * channels rows, sum = y + the
+// resampled rows [channels, 2 channels)
+void launch_resample_fix(const float* x, long long n_in, int channels, double ratio, const double* win, const double* delta, int nwin, float* y,
+                         float* sum, long long n_out, hipStream_t st) {
+    long long n_core = (long long)((double)n_in * ratio);
+    if (n_core > n_out) n_core = n_out;
+    prof_note(0.0, 4.0 * ((sum ? 2.0 : 1.0) * channels * (double)n_in + (sum ? 2.0 : 1.0) * channels * (double)n_out));
+    VR_LAUNCH(resample_kernel<ResampleFix>, dim3((unsigned)((n_out + 255) / 256), (unsigned)channels), dim3(256), 0, st,
+              ResampleFix{x, n_in, n_core, n_out, y, sum, win, delta, nwin, 1 << 9, ratio});
+    VR_HIP(hipGetLastError());
 }
 
 // ---- the streamed resampler (vr_resampler_*) -------------------------------------------------------------------------------------
@@ -240,11 +317,7 @@ Resampler* resampler_open(int device, int channels, int sr_in, int sr_out) {
         r->g = resample_geom(sr_in, sr_out);
         VR_HIP(hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking));
         std::vector<double> win, delta;
-        kaiser_sinc_table(16, 9, 0.85, 8.555504641634386, win);                       // 'kaiser_fast', as resample_api builds it
-        if (r->g.ratio < 1.0) for (double& v : win) v *= r->g.ratio;
-        delta.resize(win.size());
-        for (size_t i = 0; i + 1 < win.size(); ++i) delta[i] = win[i + 1] - win[i];
-        delta.back() = 0.0;
+        kaiser_fast_table(r->g.ratio, win, delta);                                    // as resample_api builds it
         r->nwin = (int)win.size();
         VR_HIP(hipMalloc(&r->d_win, win.size() * sizeof(double)));
         VR_HIP(hipMalloc(&r->d_delta, win.size() * sizeof(double)));

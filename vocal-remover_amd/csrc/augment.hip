@@ -106,6 +106,85 @@ __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kReside
     }
 }
 
+// ---- pitch-shifted training pairs (vr_pitch_*): the offline augmentation of the reference's augment.py --------
+// Two more forms under the family's name, selected by the argument struct the kernel is instantiated with (kernels.h).
+//
+// PitchDiff: v = mix - inst over n samples, one float32 subtraction each (the vocals wave the pair entry shifts beside the instrumental).
+//
+// PitchVocoder: librosa.phase_vocoder on `signals` spectrograms [bins][T] -> [bins][Tout], Tout = ceil(T / rate).  Output frame t reads
+// the input at s = t * rate (double): i = int(s), a = s - i, mag = (1 - a) |D[i]| + a |D[i + 1]|, and its phase is
+//     acc[t] = angle(D[0]) + sum over u < t of (phi + wrap(angle(D[i_u + 1]) - angle(D[i_u]) - phi)),   phi = pi hop k / (bins - 1),
+// an exclusive prefix sum along time.  Everything up to the store is fp64 (a float32 phase is off by 1e-2 of the wave's peak after a
+// few hundred frames): angles by atan2 of the complex64 parts, the sum, the magnitude, sincos; the product mag * (cos, sin) is rounded
+// to float once.  A wave owns one (signal, bin) row; its lanes run along t, 64 frames per step: a shuffle scan inside the wave, the
+// total carried to the next step in a double.  No LDS, no barrier, no atomics: the order of the additions is fixed, so two calls agree
+// bit for bit.  Columns at and past T read as zero, as the two zero columns librosa appends.
+// grid (ceil(bins / 4), signals), block 256 = four rows.
+template <class FORM>
+__global__ __launch_bounds__(256) void augment_kernel(FORM a) {
+    if constexpr (std::is_same<FORM, PitchDiff>::value) {
+        const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (i < a.n) a.v[i] = a.mix[i] - a.inst[i];
+    } else {
+        static_assert(std::is_same<FORM, PitchVocoder>::value, "augment_kernel: unknown form");
+        const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (k >= a.bins) return;                                    // (a whole wave leaves: nothing below is workgroup-wide)
+        const long long r = (long long)blockIdx.y * a.bins + k;
+        const float2* __restrict__ row = a.D + r * a.T;
+        float2* __restrict__ orow = a.out + r * a.Tout;
+        const double PI = 3.14159265358979323846, TWO_PI = 2.0 * PI;
+        // np.linspace(0, pi * hop, bins)[k]: k * step, the last one the end point itself
+        const double phi = k == a.bins - 1 ? PI * (double)a.hop : (double)k * ((PI * (double)a.hop) / (double)(a.bins - 1));
+        const float2 first = row[0];
+        double carry = atan2((double)first.y, (double)first.x);
+        for (int t0 = 0; t0 < a.Tout; t0 += 64) {
+            const int t = t0 + lane;
+            double inc = 0.0, mag = 0.0;
+            if (t < a.Tout) {
+                const double s = (double)t * a.rate;
+                const int i = (int)s;
+                const double al = s - (double)i;
+                const float2 c0 = i < a.T ? row[i] : make_float2(0.f, 0.f);
+                const float2 c1 = i + 1 < a.T ? row[i + 1] : make_float2(0.f, 0.f);
+                const double x0 = c0.x, y0 = c0.y, x1 = c1.x, y1 = c1.y;
+                mag = (1.0 - al) * sqrt(x0 * x0 + y0 * y0) + al * sqrt(x1 * x1 + y1 * y1);
+                double d = atan2(y1, x1) - atan2(y0, x0) - phi;
+                d = d - TWO_PI * rint(d / TWO_PI);
+                inc = phi + d;
+            }
+            double incl = inc;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const double up = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += up;
+            }
+            double excl = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 0.0;
+            const double acc = carry + excl;
+            carry += __shfl(incl, 63, 64);
+            if (t < a.Tout) {
+                double sn, cs;
+                sincos(acc, &sn, &cs);
+                orow[t] = make_float2((float)(mag * cs), (float)(mag * sn));
+            }
+        }
+    }
+}
+
+void launch_pitch_diff(const float* mix, const float* inst, float* v, long long n, hipStream_t st) {
+    if (n <= 0) return;
+    prof_note(0.0, 12.0 * (double)n);
+    VR_LAUNCH(augment_kernel<PitchDiff>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, PitchDiff{mix, inst, v, n});
+    VR_HIP(hipGetLastError());
+}
+
+void launch_phase_vocoder(const float2* D, float2* out, int signals, int bins, int T, int Tout, int hop, double rate, hipStream_t st) {
+    prof_note(0.0, 8.0 * (double)signals * bins * ((double)T + (double)Tout));      // each spectrogram read once, the stretched one written
+    VR_LAUNCH(augment_kernel<PitchVocoder>, dim3((unsigned)((bins + 3) / 4), (unsigned)signals), dim3(256), 0, st,
+              PitchVocoder{D, out, bins, T, Tout, hop, rate});
+    VR_HIP(hipGetLastError());
+}
+
 void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDesc* desc, const float* rw,
                     int B, int T, int bins, float* Xmag, float* Ymag, bool out_complex, hipStream_t st) {
     const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);

@@ -64,6 +64,19 @@ void launch_augment(const float2* X, const float2* Y, const float2* Xi, const fl
 struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
                              float* Ymag, bool out_complex, hipStream_t st);
+// the pitch forms of the same kernel family: the argument struct selects the body
+struct PitchDiff { const float* mix; const float* inst; float* v; long long n; };          // v = mix - inst
+struct PitchVocoder {                                                                       // librosa.phase_vocoder, fp64 phase
+    const float2* D;          // [signals][bins][T]
+    float2* out;              // [signals][bins][Tout], Tout = ceil(T / rate)
+    int bins, T, Tout, hop;
+    double rate;
+};
+// the four lengths of one shift (vr_pitch_plan; csrc/pitch.hip): STFT frames, stretched frames, stretched samples, resampled samples
+struct PitchPlan { int T, T_stretch; long long n_stretch, n_resampled; };
+PitchPlan pitch_plan(long long L, int n_fft, int hop, double rate, double ratio);
+void launch_pitch_diff(const float* mix, const float* inst, float* v, long long n, hipStream_t st);
+void launch_phase_vocoder(const float2* D, float2* out, int signals, int bins, int T, int Tout, int hop, double rate, hipStream_t st);
 // The conv families behind launch_conv.  A *_pick says whether its family takes the launch and fills the plan (kernel, MT, TH, TW);
 // conv_plan (conv_mfma.hip) alone calls them, in its order.  A *_launch_conv takes tiled args (conv_fill_tiling) and the plan.
 bool thin16_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32
@@ -223,6 +236,16 @@ struct FFTPlan { int n_fft; int log2n; float2* twiddle; float* window; };
 void launch_stft(const FFTPlan& pl, const float* wave, long long L, int hop, int T, float2* spec, hipStream_t st);
 // spec [2][bins][T] -> frames scratch [2][T][n_fft] -> wave [2][hop*(T-1)]
 void launch_istft(const FFTPlan& pl, const float2* spec, int hop, int T, float* frames, float* wave, hipStream_t st);
+// The per-frame kernels on any number of signals in one grid, whatever the hop (the pitch shifter's transforms):
+// wave [signals][L] -> spec [signals][bins][T];  spec [signals][bins][T] -> frames scratch [signals][T][n_fft] -> wave [signals][length],
+// length samples of the overlap-add behind the n_fft / 2 in front (librosa.istft(length=)): cut, or zeros past the last frame
+void launch_stft_signals(const FFTPlan& pl, const float* wave, long long L, int hop, int T, int signals, float2* spec, hipStream_t st);
+void launch_istft_length(const FFTPlan& pl, const float2* spec, int hop, int T, int signals, float* frames, float* wave, long long length,
+                         hipStream_t st);
+// the rows form of the frame-tiled STFT (hop == n_fft / 2): wave [2][L] -> rows [T][2][bins], the training cache's layout, the values
+// launch_stft's
+struct SpecRows {};
+void launch_stft_rows(const FFTPlan& pl, const float* wave, long long L, int T, float2* rows, hipStream_t st);
 // Fused form for hop == n_fft/2: wave = istft(m * spec) (which 0) or istft(spec - m * spec) (which 1); mask_a null = plain
 // istft.  No frame buffer, no materialised y / v spectrograms (inference.py:26-40 + lib/spec_utils.py:157-165 in one pass).
 bool istft_masked_available(const FFTPlan& pl, int hop);

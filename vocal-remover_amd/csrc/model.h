@@ -198,6 +198,8 @@ void run_train_head(const FFTPlan& pl, const Tensor& f3, const TrainHead& h, con
 void launch_head_grads(const Tensor& f3, int CO, const float* w, const float* dlogit, float* wpart, float* g, int g_acc, float* dw,
                        int dw_acc, hipStream_t st);
 
+void fft_plan_create(FFTPlan& plan, int n_fft);           // twiddles and the periodic Hann window of one n_fft, on the current device
+
 class Model {
 public:
     Model(int device, int n_fft, int hop, int nout, int nout_lstm, bool is_complex = false);
@@ -272,6 +274,17 @@ public:
                       int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
                       const int* pcm_fmt = nullptr, bool solo = false, const EvalArgs* eval = nullptr,
                       const PseudoArgs* pseudo = nullptr);
+    // ---- pitch-shifted waves and training pairs (vr_pitch_*, csrc/pitch.hip) ----
+    // spec [signals][bins][T] -> out [signals][bins][ceil(T / rate)], the handle's bins and hop
+    void phase_vocoder_api(const float* spec, bool on_dev, int signals, int T, double rate, float* out, bool out_on_dev);
+    // vr_istft with librosa's length=: the per-frame kernels whatever the hop, wave [2][length]
+    void istft_length_api(const float* spec, bool on_dev, int T, long long length, float* wave, bool wave_on_dev);
+    // n items through stft -> phase vocoder -> istft(length) -> resample -> fix_length at shift_n_fft / shift_hop, one after the other in one
+    // workspace.  inst null: waves[i] [channels][L[i]] -> out[i] of the same shape.  inst given (channels 2): y' = shift(inst), v' =
+    // shift(waves - inst), X' = y' + v'; X_out[i] / y_out[i] = their STFTs at the handle's n_fft / hop in `layout`.
+    void pitch_run(int n, const float* const* waves, const float* const* inst, bool on_dev, int channels, const long long* L, int shift_n_fft,
+                   int shift_hop, double rate, double ratio, long long max_bytes, float* const* out, float* const* X_out, float* const* y_out,
+                   int layout, bool out_on_dev);
     // ---- WAV sample bytes in, PCM16 out (vr_*_pcm*; csrc/pcm.h): the sample-format forms of the frame-tiled STFT / iSTFT ----
     bool pcm_available() const;                           // the frame-tiled kernels, whose forms these are, exist on this handle
     void check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const;      // availability, format, channels, a device pointer's alignment
@@ -413,6 +426,7 @@ private:
     Param *out_w = nullptr, *aux_out_w = nullptr;
 
     FFTPlan plan{};
+    FFTPlan shift_plan{};                                // the pitch shifter's transform when it is not the handle's own (pitch.hip)
 
     // builders
     Param* add_param(const std::string& key, std::vector<int64_t> shape, ParamKind kind, bool trainable);

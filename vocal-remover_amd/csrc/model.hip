@@ -163,10 +163,14 @@ Model::Model(int device_, int n_fft_, int hop_, int nout_, int nout_lstm_, bool 
     aux_out_w = add_param("aux_out.weight", {nin, 3 * nout / 4, 1, 1}, PK_PLAIN, true);   // never used (nets.py:80)
     finalize_layout();
 
-    // FFT plan: twiddles and periodic Hann window computed in double on the host
-    plan.n_fft = n_fft;
-    plan.log2n = 0;
-    while ((1 << plan.log2n) < n_fft) ++plan.log2n;
+    fft_plan_create(plan, n_fft);
+}
+
+// FFT plan: twiddles and periodic Hann window computed in double on the host
+void fft_plan_create(FFTPlan& plan, int n_fft) {
+    FFTPlan p{};
+    p.n_fft = n_fft;
+    while ((1 << p.log2n) < n_fft) ++p.log2n;
     std::vector<float2> tw(n_fft / 2);
     std::vector<float> win(n_fft);
     const double PI = 3.14159265358979323846;
@@ -175,10 +179,16 @@ Model::Model(int device_, int n_fft_, int hop_, int nout_, int nout_lstm_, bool 
         tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
     for (int i = 0; i < n_fft; ++i) win[i] = (float)(0.5 - 0.5 * std::cos(2.0 * PI * i / n_fft));
-    VR_HIP(hipMalloc(&plan.twiddle, tw.size() * sizeof(float2)));
-    VR_HIP(hipMalloc(&plan.window, win.size() * sizeof(float)));
-    VR_HIP(hipMemcpy(plan.twiddle, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-    VR_HIP(hipMemcpy(plan.window, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+    try {
+        VR_HIP(hipMalloc(&p.twiddle, tw.size() * sizeof(float2)));
+        VR_HIP(hipMalloc(&p.window, win.size() * sizeof(float)));
+        VR_HIP(hipMemcpy(p.twiddle, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+        VR_HIP(hipMemcpy(p.window, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+    } catch (...) {                                      // `plan` is left as it was: never an n_fft without its tables
+        hipFree(p.twiddle); hipFree(p.window);
+        throw;
+    }
+    plan = p;
 }
 
 void Model::finalize_layout() {
@@ -251,6 +261,7 @@ Model::~Model() {
     for (BaseNetL& B : nets_) hipFree(B.lstm.bias_sum);
     hipFree(g_arena); hipFree(m_arena); hipFree(v_arena); hipFree(dropout_buf);
     hipFree(plan.twiddle); hipFree(plan.window);
+    hipFree(shift_plan.twiddle); hipFree(shift_plan.window);
     for (Lane& l : lanes) {
         hipStreamSynchronize(l.main); hipStreamSynchronize(l.side);
         hipStreamDestroy(l.main); hipStreamDestroy(l.side);

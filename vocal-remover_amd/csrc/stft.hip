@@ -210,6 +210,7 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 // WaveGrad in the same place (SRC = const float, `wave` and `spec` unused): the adjoint of the inverse transform for the wave-domain loss
 // term (kernels.h) -- blockIdx.y runs over the signals, L = hop (T-1), the source is WaveGradIn and the store epilogue writes dmask.
 // WaveGrad3: the same for the weighted SDR term, source WaveGrad3In over three waves, the same store epilogue.
+// SpecRows (SRC = const float): the same spectrogram stored as rows [T][2][bins], the training cache's layout.
 // const PseudoSeg* (SRC = const SongSeg): the pair form -- one PseudoSeg per song beside the song table.  The workgroup
 // runs its frame tile twice with the same arithmetic: first the song's instrumental (`inst_wave`), stored to `inst` as vr_stft stores it,
 // then the table's mixture, of which only D = X - Y goes to the table's `spec`; X itself is never written.
@@ -219,8 +220,10 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     constexpr bool kGrad3 = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad3>::value;
     constexpr bool kGrad = std::is_same<typename FirstOr<void, PCM...>::type, WaveGrad>::value || kGrad3;
     constexpr bool kPseudo = std::is_same<typename FirstOr<void, PCM...>::type, const PseudoSeg*>::value;
-    constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad && !kPseudo;
+    constexpr bool kRows = std::is_same<typename FirstOr<void, PCM...>::type, SpecRows>::value;
+    constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad && !kPseudo && !kRows;
     static_assert(!kPseudo || kSongTable<SRC>, "the pair form is a song-table form");
+    static_assert(!kRows || std::is_same<SRC, const float>::value, "the rows form is a one-song form");
     static_assert(sizeof...(PCM) <= 1 && !(sizeof...(PCM) == 1 && kStream<SRC>), "one PCM source at most, none for streams");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
@@ -311,7 +314,14 @@ second_pass:
         }
         __syncthreads();
     }
-    for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
+    if constexpr (kRows) {                           // [T][2][bins]: a frame's bins lie together, so consecutive lanes run along k
+        // (the tile is [bins][F], so these LDS reads stride F values and conflict on banks; lanes along f would read it conflict-free
+        // and scatter the global stores over F rows instead.  Coalesced stores were preferred: profiles/pitch.md has the kernel's share)
+        for (int idx = threadIdx.x; idx < bins * nf; idx += 1024) {
+            const int f = idx / bins, k = idx - f * bins;
+            spec[((long long)(t0 + f) * 2 + ch) * bins + k] = tile[k * F + f];
+        }
+    } else for (int idx = threadIdx.x; idx < bins * F; idx += 1024) {
         const int k = idx / F, f = idx - k * F;
         if constexpr (kStream<SRC>) {
             if (f < nf) ss.ring[((long long)ch * bins + k) * ss.R + (t0 + f) % ss.R] = tile[idx];
@@ -933,6 +943,38 @@ void launch_stft_pcm(const FFTPlan& pl, const PcmIn& in, long long L, int T, flo
     VR_LAUNCH((stft_tile_kernel<const float, PcmIn>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, (const float*)nullptr, L, T, F,
               spec, in);
     VR_HIP(hipGetLastError());
+}
+
+void launch_stft_rows(const FFTPlan& pl, const float* wave, long long L, int T, float2* rows, hipStream_t st) {
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const float, SpecRows>), 160 * 1024);
+    prof_note(0.0, 2.0 * (4.0 * (double)L + 8.0 * (double)bins * T));
+    VR_LAUNCH((stft_tile_kernel<const float, SpecRows>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, wave, L, T, F, rows,
+              SpecRows{});
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stft_signals(const FFTPlan& pl, const float* wave, long long L, int hop, int T, int signals, float2* spec, hipStream_t st) {
+    prof_note(0.0, (double)signals * (4.0 * (double)L + 8.0 * (double)(pl.n_fft / 2 + 1) * T));
+    VR_LAUNCH(stft_kernel, dim3(T, signals), dim3(256), pl.n_fft * sizeof(float2), st, pl, wave, L, hop, T, spec);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_istft_length(const FFTPlan& pl, const float2* spec, int hop, int T, int signals, float* frames, float* wave, long long length,
+                         hipStream_t st) {
+    prof_note(0.0, (double)signals * T * (8.0 * (double)(pl.n_fft / 2 + 1) + 4.0 * (double)pl.n_fft));
+    VR_LAUNCH(istft_frame_kernel, dim3(T, signals), dim3(256), pl.n_fft * sizeof(float2), st, pl, spec, T, frames);
+    VR_HIP(hipGetLastError());
+    if (length > 0) {
+        prof_note(0.0, (double)signals * (4.0 * (double)T * pl.n_fft + 4.0 * (double)length));
+        VR_LAUNCH(istft_ola_kernel, dim3((unsigned)((length + 255) / 256), signals), dim3(256), 0, st, pl, frames, hop, T, length, wave);
+        VR_HIP(hipGetLastError());
+    }
 }
 
 bool istft_masked_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }

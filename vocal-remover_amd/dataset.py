@@ -527,6 +527,41 @@ def make_pseudo_training_set(sp, filelist, sr, hop_length, n_fft, songs_per_call
     return rows
 
 
+def pitch_cache_paths(cache, mix_path, inst_path, pitch):
+    """<cache dir>/<basename>_pitch{pitch}.npy of the mixture and of the instrumental: the reference's names (augment.py:30-44)"""
+    suffix = '_pitch{}.npy'.format(pitch)
+    return cache.npy_path(mix_path)[:-len('.npy')] + suffix, cache.npy_path(inst_path)[:-len('.npy')] + suffix
+
+
+def make_pitch_training_set(filelist, sr, hop_length, n_fft, pitch, songs_per_call=4):
+    """make_training_set for the copies of every pair shifted by `pitch` semitones (the reference's augment.py): the pairs are loaded and
+    aligned as make_pseudo_training_set does, go through audio.pitch_pair_many(layout='rows') in groups of `songs_per_call`, and the rows
+    [T, 2, bins] are saved as the device wrote them -- the cache's layout -- under the reference's names, <cache dir>/<basename>_pitch{n}.npy.
+    A pair whose two files exist is skipped (its peak is read back from them).  -> [[X path, y path, peak], ...], the rows
+    VocalRemoverTrainingSet / ResidentTrainingSet take: train on make_training_set(...) + make_pitch_training_set(..., pitch=-1) + ..."""
+    from . import audio
+    from .spec_utils import SpectrogramCache
+    cache = SpectrogramCache(sr, hop_length, n_fft)
+    filelist = list(filelist)
+    paths = [pitch_cache_paths(cache, m, i, pitch) for m, i in filelist]
+    todo = [k for k, (xp, yp) in enumerate(paths) if not (os.path.exists(xp) and os.path.exists(yp))]
+    step = max(int(songs_per_call), 1)
+    peaks = {}
+    for g in range(0, len(todo), step):
+        group = todo[g:g + step]
+        pairs = [load_aligned_pair(*filelist[k], sr) for k in group]
+        Xs, ys, pk = audio.pitch_pair_many([X for X, _ in pairs], [y for _, y in pairs], sr, pitch, hop_length, n_fft, layout='rows')
+        for k, X, y, p in zip(group, Xs, ys, pk):
+            np.save(paths[k][0], X)
+            np.save(paths[k][1], y)
+            peaks[k] = p
+    rows = []
+    for k, (xp, yp) in enumerate(paths):
+        peak = peaks[k] if k in peaks else _song_peak(np.load(xp, mmap_mode='r'), np.load(yp, mmap_mode='r'))
+        rows.append([xp, yp, peak])
+    return rows
+
+
 def make_validation_set(filelist, cropsize, sr, hop_length, n_fft, offset):
     """Cuts every validation song into ceil(T / roi) windows of `cropsize` frames, `roi` apart, of the peak-normalised,
     make_padding-padded spectrogram pair and stores each once as cs{}_sr{}_hl{}_nf{}_of{}/<song>_p<j>.npz; returns the paths."""

@@ -132,6 +132,17 @@ _SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     'vr_resample': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int64]),
     'vr_xcorr_argmax': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64, c_i64p]),
+    'vr_resample_ratio': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, c_f32p, ctypes.c_int64]),
+    'vr_pitch_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int), c_i64p, c_i64p]),
+    'vr_phase_vocoder': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_f32p, ctypes.c_int]),
+    'vr_istft_length': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int]),
+    'vr_pitch_shift_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, c_i64p,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    'vr_pitch_pair_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                          ctypes.c_int, c_i64p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                          ctypes.c_int]),
     'vr_resampler_open': (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_void_p)]),
     'vr_resampler_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
     'vr_resampler_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
@@ -249,6 +260,15 @@ def resampler_plan(sr_in, sr_out, samples_in, flushed):
     out = ctypes.c_int64()
     check(lib().vr_resampler_plan(int(sr_in), int(sr_out), int(samples_in), 1 if flushed else 0, ctypes.byref(out)))
     return int(out.value)
+
+
+def pitch_plan(L, n_fft, hop, rate, ratio):
+    """vr_pitch_plan (host only): -> (T, T_stretch, n_stretch, n_resampled) of one shift of a signal of L samples."""
+    T, Ts = ctypes.c_int(), ctypes.c_int()
+    ns, nr = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().vr_pitch_plan(int(L), int(n_fft), int(hop), float(rate), float(ratio), ctypes.byref(T), ctypes.byref(Ts), ctypes.byref(ns),
+                              ctypes.byref(nr)))
+    return int(T.value), int(Ts.value), int(ns.value), int(nr.value)
 
 
 class Crop(ctypes.Structure):               # include/vr_mi355.h: vr_crop

@@ -46,8 +46,38 @@ def merge_artifacts(y_mask, thres=0.05, min_range=64, fade_size=32):
     return y_mask
 
 
+def _cuda(x):
+    """x is a torch cuda tensor"""
+    torch = audio._torch()
+    return torch is not None and torch.is_tensor(x) and x.is_cuda
+
+
+def _cuda_in(x, dtype):
+    """a cuda tensor as the library reads it: contiguous, of `dtype`, every pending write of torch's stream done"""
+    import torch
+    x = x.detach().to(dtype).contiguous()
+    torch.cuda.current_stream(x.device).synchronize()
+    return x
+
+
+def _cuda_out(shape, dtype, device):
+    import torch
+    y = torch.empty(shape, dtype=dtype, device=device)
+    torch.cuda.current_stream(device).synchronize()
+    return y
+
+
 def wave_to_spectrogram(wave, hop_length, n_fft):
-    """lib/spec_utils.py:26-31: [2, L] float32 -> [2, n_fft/2+1, 1 + L//hop] complex64."""
+    """lib/spec_utils.py:26-31: [2, L] float32 -> [2, n_fft/2+1, 1 + L//hop] complex64 (a torch cuda tensor gives a cuda tensor)."""
+    if _cuda(wave):
+        import torch
+        wave = _cuda_in(wave, torch.float32)
+        if wave.ndim != 2 or wave.shape[0] != 2:
+            raise ValueError('wave must be [2, L]')
+        L = int(wave.shape[1])
+        spec = _cuda_out((2, n_fft // 2 + 1, 1 + L // hop_length), torch.complex64, wave.device)
+        native.check(native.lib().vr_stft(_signal_handle(n_fft, hop_length).h, wave.data_ptr(), 1, L, spec.data_ptr(), 1))
+        return spec
     wave = np.ascontiguousarray(np.asarray(wave, dtype=np.float32))
     if wave.ndim != 2 or wave.shape[0] != 2:
         raise ValueError('wave must be [2, L]')
@@ -59,8 +89,12 @@ def wave_to_spectrogram(wave, hop_length, n_fft):
     return spec
 
 
-def spectrogram_to_wave(spec, hop_length=1024):
-    """lib/spec_utils.py:157-165: [2, bins, T] (or [bins, T]) complex64 -> float32 wave."""
+def spectrogram_to_wave(spec, hop_length=1024, length=None):
+    """lib/spec_utils.py:157-165: [2, bins, T] (or [bins, T]) complex64 -> float32 wave of hop * (T - 1) samples.  length (librosa.istft's
+    length=): that many samples of the overlap-add behind the n_fft / 2 in front -- cut, or followed by zeros; a torch cuda tensor
+    gives a cuda tensor (with length only)."""
+    if length is not None:
+        return _spectrogram_to_wave_length(spec, hop_length, int(length))
     spec = np.asarray(spec)
     mono = spec.ndim == 2
     if mono:
@@ -72,6 +106,61 @@ def spectrogram_to_wave(spec, hop_length=1024):
     h = _signal_handle(n_fft, hop_length)
     native.check(native.lib().vr_istft(h.h, native.np_ptr(spec), 0, T, native.np_ptr(wave), 0))
     return wave[0] if mono else wave
+
+
+def _spectrogram_to_wave_length(spec, hop_length, length):
+    on_dev = _cuda(spec)
+    if on_dev:
+        import torch
+        mono = spec.ndim == 2
+        spec = _cuda_in(torch.stack([spec, spec]) if mono else spec, torch.complex64)
+    else:
+        spec = np.asarray(spec)
+        mono = spec.ndim == 2
+        spec = np.ascontiguousarray((np.asarray([spec, spec]) if mono else spec).astype(np.complex64))
+    if spec.ndim != 3 or spec.shape[0] != 2:
+        raise ValueError('spec must be [2, bins, T] or [bins, T]')
+    bins, T = int(spec.shape[1]), int(spec.shape[2])
+    h = _signal_handle(2 * (bins - 1), hop_length)
+    if on_dev:
+        wave = _cuda_out((2, length), torch.float32, spec.device)
+        native.check(native.lib().vr_istft_length(h.h, spec.data_ptr(), 1, T, length, wave.data_ptr(), 1))
+    else:
+        wave = np.empty((2, length), dtype=np.float32)
+        native.check(native.lib().vr_istft_length(h.h, native.np_ptr(spec), 0, T, length, native.np_ptr(wave), 0))
+    return wave[0] if mono else wave
+
+
+def phase_vocoder(D, rate, hop_length=None):
+    """librosa.phase_vocoder(D, rate=rate, hop_length=hop_length): [..., bins, T] complex64 -> [..., bins, ceil(T / rate)] complex64, the
+    phase accumulated in double on the device (vr_phase_vocoder).  hop_length None: n_fft / 4.  numpy in, numpy out; a torch cuda
+    tensor in, a cuda tensor out."""
+    on_dev = _cuda(D)
+    if on_dev:
+        import torch
+        D = _cuda_in(D, torch.complex64)
+    else:
+        D = np.ascontiguousarray(np.asarray(D).astype(np.complex64))
+    if D.ndim < 2:
+        raise ValueError('D must be [..., bins, T]')
+    bins, T = int(D.shape[-2]), int(D.shape[-1])
+    n_fft = 2 * (bins - 1)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    signals = 1
+    for d in D.shape[:-2]:
+        signals *= int(d)
+    if not rate > 0:
+        raise ValueError('rate must be positive')
+    Tout = int(np.ceil(T / float(rate)))
+    shape = tuple(D.shape[:-1]) + (Tout,)
+    h = _signal_handle(n_fft, hop)
+    if on_dev:
+        out = _cuda_out(shape, torch.complex64, D.device)
+        native.check(native.lib().vr_phase_vocoder(h.h, D.data_ptr(), 1, signals, T, float(rate), out.data_ptr(), 1))
+    else:
+        out = np.empty(shape, dtype=np.complex64)
+        native.check(native.lib().vr_phase_vocoder(h.h, native.np_ptr(D), 0, signals, T, float(rate), native.np_ptr(out), 0))
+    return out
 
 
 def _pcm_bytes(raw):
