@@ -472,6 +472,30 @@ int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_a
 int vr_dataset_batch_complex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
                              float* X_out, float* y_out, int out_on_device);
 
+/* The peak of one resident song, taken on the device from its rows: *peak = np.max([np.abs(X).max(), np.abs(y).max()]) of the song's two
+ * arrays, bit for bit (lib/dataset.py:214, the coef of a training row and the normaliser of a validation song).  np.abs of a complex64
+ * is, in numpy 1.25 and later on a CPU with fused multiply-add, larger * sqrt(fma(r, r, 1)) with r = smaller / larger in float32 -- not
+ * hypotf; the device computes exactly that per element, finds the element of largest value -- ties to the lowest (slab, index), so two
+ * calls agree in every output -- and the host forms the float from that one element by the same operations.  at[2] (re, im of that
+ * element), *slab (0 = X, 1 = y) and *index (its flat complex index in the slab, (row * 2 + channel) * bins + bin) may each be NULL.
+ * A NaN in either array (beside no infinite part of the same element) makes *peak NaN, as np.max does; at, slab and index then
+ * describe the largest element that is not NaN.  Runs on the store's own stream and returns when the result is on the host.
+ * Errors, VR_ERR_BAD_ARGUMENT before anything is launched: a null d or peak, a song index out of range. */
+int vr_dataset_peak(vr_dataset d, int song, float* peak, float* at, int* slab, int64_t* index);
+
+/* Windows of resident songs, the validation patches of lib/dataset.py:220-248 without the patch files: sample b is rows
+ * [start, start + T) of song w[b].song.  start may be negative and the window may end past the song, or lie wholly outside it: a row
+ * outside [0, rows) reads as zero (np.pad).  Every value read is multiplied by w[b].scale, real and imaginary part each, one float32
+ * product -- pass 1 / peak as a float32, which is what numpy's complex64 / float32 computes.  Outputs as vr_dataset_batch: X_mag, y_mag
+ * [B][2][bins][T] fp32 hypotf of the scaled values; the _complex entry stores the scaled complex64 values themselves.  Runs on the
+ * handle's stream and returns when the outputs are complete.
+ * Errors, all VR_ERR_BAD_ARGUMENT and all before anything is launched: B <= 0 or a null table (reported before the handle and the store
+ * are looked at); a handle on another device than the store; T <= 0; and, with vr_last_error() naming the sample: a song index out of
+ * range, start + T overflowing an int64, a scale that is not finite. */
+typedef struct vr_window { int song; int reserved; int64_t start; float scale; } vr_window;
+int vr_dataset_windows(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_mag, float* y_mag, int out_on_device);
+int vr_dataset_windows_complex(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_out, float* y_out, int out_on_device);
+
 /* torch.optim.Adam(lr, betas=(b1,b2), eps, weight_decay=0).step()   train.py:215-218,95
  * grad_scale multiplies every gradient first (1/world_size after a SUM all-reduce).  Hyper-parameters are doubles
  * like torch's python floats: 1 - beta, the bias corrections and lr / bias_correction1 are formed in double and only

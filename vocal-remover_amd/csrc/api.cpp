@@ -1,6 +1,7 @@
 // extern "C" surface of libvr_mi355.so (include/vr_mi355.h).  Exceptions stop here.
 #include "../../include/vr_mi355.h"
 
+#include <cstddef>
 #include <cstring>
 #include <new>
 
@@ -621,6 +622,16 @@ int vr_dataset_rows(vr_dataset d, int song, int64_t* rows) {
     });
 }
 
+int vr_dataset_peak(vr_dataset d, int song, float* peak, float* at, int* slab, int64_t* index) {
+    NEED_DATASET(d);
+    if (!peak) { g_err = "null argument"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        long long idx = 0;
+        *peak = d->set.peak(song, at, slab, &idx);
+        if (index) *index = idx;
+    });
+}
+
 int vr_augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
                      const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
                      int out_on_device) {
@@ -656,6 +667,28 @@ int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_a
 int vr_dataset_batch_complex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
                              float* X_out, float* y_out, int out_on_device) {
     return dataset_batch(h, d, crops, desc, reduction_weight, B, T, X_out, y_out, out_on_device, true);
+}
+
+// (argument errors first, as dataset_batch)
+static int dataset_windows(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_out, float* y_out, int out_on_device,
+                           bool out_complex) {
+    if (B <= 0) { g_err = "B must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!w || !X_out || !y_out) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    NEED_DATASET(d);
+    static_assert(sizeof(vr_window) == sizeof(vr::ResidentWindow) && offsetof(vr_window, scale) == offsetof(vr::ResidentWindow, scale),
+                  "C ABI struct and its model.h twin");
+    return guard([&] {
+        h->m.dataset_windows_api(d->set, reinterpret_cast<const vr::ResidentWindow*>(w), B, T, X_out, y_out, out_on_device != 0, out_complex);
+    });
+}
+
+int vr_dataset_windows(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_mag, float* y_mag, int out_on_device) {
+    return dataset_windows(h, d, w, B, T, X_mag, y_mag, out_on_device, false);
+}
+
+int vr_dataset_windows_complex(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_out, float* y_out, int out_on_device) {
+    return dataset_windows(h, d, w, B, T, X_out, y_out, out_on_device, true);
 }
 
 int vr_adam_step(vr_handle h, double lr, double b1, double b2, double eps, double grad_scale) {

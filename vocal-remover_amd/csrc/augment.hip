@@ -171,6 +171,161 @@ __global__ __launch_bounds__(256) void augment_kernel(FORM a) {
     }
 }
 
+// ---- the resident song store's own forms (vr_dataset_windows, vr_dataset_peak) ----------------------------------
+// A third template under the family's name, again selected by the argument struct; the six instantiations above are not touched.
+//
+// SongWindows (kFlag: complex64 output): the resident form of the first kernel -- same grid, same 32 x 32 tile through LDS rows of 33
+// words -- without augmentation and with the window free to leave its song: the per-sample entry carries the song's rows and a signed
+// start, a row outside [0, rows) reads as zero, and every value read is multiplied by the entry's scale (one float32 product per part:
+// 1 / peak of the song, numpy's complex64 / float32).
+//
+// SongPeak (kFlag: the second of its two launches): the element of largest np.abs of one song's two slabs.  The key is np.abs itself,
+// the float32 numpy computes for a complex64 (numpy_cabsf, kernels.h: five IEEE operations, so the device's value is numpy's), and the
+// candidate is the key and its position in the [X | y] sequence of complex elements; a larger key wins, an equal key at a lower
+// position wins, so the result does not depend on the grid.  A NaN key sets a flag carried beside the candidate.  First launch:
+// workgroup g takes float4 1024 g + 256 k + lane of the sequence (k < 4: four independent 16-byte loads a lane, two complex64 each),
+// strides by the grid, reduces across the wave by shuffles and across its four waves through LDS, and stores one partial.  Second
+// launch: one workgroup over the partials; it reads the winning element back and stores candidate and element for the host.  No atomics.
+__device__ __forceinline__ void peak_take(float& k, unsigned long long& p, float ok, unsigned long long op) {
+    if (ok > k || (ok == k && op < p)) { k = ok; p = op; }
+}
+
+__device__ __forceinline__ void peak_element(float re, float im, unsigned long long pos, float& k, unsigned long long& p, unsigned& bad) {
+    const float key = numpy_cabsf(re, im);
+    bad |= key != key ? 1u : 0u;
+    if (key > k) { k = key; p = pos; }               // (a lane meets its positions in rising order: the first of equals stays)
+}
+
+// -> thread 0 of the workgroup holds the workgroup's candidate and flag
+__device__ __forceinline__ void peak_reduce(float& k, unsigned long long& p, unsigned& bad) {
+    __shared__ float sk[4];
+    __shared__ unsigned long long sp[4];
+    __shared__ unsigned sb[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ok = __shfl_down(k, off, 64);
+        const unsigned long long op = __shfl_down(p, off, 64);
+        bad |= __shfl_down(bad, off, 64);
+        peak_take(k, p, ok, op);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sk[wave] = k; sp[wave] = p; sb[wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) { peak_take(k, p, sk[w], sp[w]); bad |= sb[w]; }
+}
+
+template <class FORM, bool kFlag>
+__global__ __launch_bounds__(256) void augment_kernel(FORM a) {
+    if constexpr (std::is_same<FORM, SongWindows>::value) {
+        constexpr int NT = kFlag ? 2 : 1;
+        __shared__ float tx[NT][32][33], ty[NT][32][33];
+        const int b = blockIdx.z >> 1, c = blockIdx.z & 1;
+        const int t0 = blockIdx.x * 32, bin0 = blockIdx.y * 32;
+        const int T = a.T, bins = a.bins;
+        const SongWindow s = a.table[b];                   // (b is uniform over the block: scalar loads)
+        const int bin = bin0 + threadIdx.x;
+        for (int r = threadIdx.y; r < 32; r += 8) {
+            const int t = t0 + r;
+            float2 x = make_float2(0.f, 0.f), y = make_float2(0.f, 0.f);
+            if (t < T && bin < bins) {
+                const long long row = s.start + t;         // (start + T does not overflow: checked by the host)
+                if (row >= 0 && row < s.rows) {
+                    const long long i = (row * 2 + c) * bins + bin;
+                    const float2 xv = s.X[i], yv = s.y[i];
+                    x = make_float2(xv.x * s.scale, xv.y * s.scale);
+                    y = make_float2(yv.x * s.scale, yv.y * s.scale);
+                }
+            }
+            if constexpr (kFlag) {
+                tx[0][r][threadIdx.x] = x.x; tx[1][r][threadIdx.x] = x.y;
+                ty[0][r][threadIdx.x] = y.x; ty[1][r][threadIdx.x] = y.y;
+            } else {
+                tx[0][r][threadIdx.x] = hypotf(x.x, x.y);
+                ty[0][r][threadIdx.x] = hypotf(y.x, y.y);
+            }
+        }
+        __syncthreads();
+        const int t = t0 + threadIdx.x;
+        for (int r = threadIdx.y; r < 32; r += 8) {
+            const int bo = bin0 + r;
+            if (t < T && bo < bins) {
+                const long long o = (((long long)b * 2 + c) * bins + bo) * T + t;
+                if constexpr (kFlag) {
+                    reinterpret_cast<float2*>(a.X_out)[o] = make_float2(tx[0][threadIdx.x][r], tx[1][threadIdx.x][r]);
+                    reinterpret_cast<float2*>(a.y_out)[o] = make_float2(ty[0][threadIdx.x][r], ty[1][threadIdx.x][r]);
+                } else {
+                    a.X_out[o] = tx[0][threadIdx.x][r];
+                    a.y_out[o] = ty[0][threadIdx.x][r];
+                }
+            }
+        }
+    } else {
+        static_assert(std::is_same<FORM, SongPeak>::value, "augment_kernel: unknown form");
+        float k = -1.f;
+        unsigned long long p = ~0ull;
+        unsigned bad = 0;
+        if constexpr (!kFlag) {
+            const long long half = a.n >> 1, total = 2 * half;        // float4s of one slab, of both
+            const float4* __restrict__ X4 = reinterpret_cast<const float4*>(a.X);
+            const float4* __restrict__ Y4 = reinterpret_cast<const float4*>(a.y);
+            for (long long base = (long long)blockIdx.x * 1024; base < total; base += (long long)gridDim.x * 1024) {
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const long long q = base + u * 256 + threadIdx.x;
+                    v[u] = q >= total ? make_float4(0.f, 0.f, 0.f, 0.f) : q < half ? X4[q] : Y4[q - half];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const long long q = base + u * 256 + threadIdx.x;
+                    if (q < total) {
+                        peak_element(v[u].x, v[u].y, 2ull * (unsigned long long)q, k, p, bad);
+                        peak_element(v[u].z, v[u].w, 2ull * (unsigned long long)q + 1, k, p, bad);
+                    }
+                }
+            }
+            peak_reduce(k, p, bad);
+            if (threadIdx.x == 0) a.part[blockIdx.x] = PeakCand{p, k, bad, 0.f, 0.f};
+        } else {
+            for (int i = threadIdx.x; i < a.parts; i += 256) {
+                const PeakCand c = a.part[i];
+                peak_take(k, p, c.key, c.pos);
+                bad |= c.bad;
+            }
+            peak_reduce(k, p, bad);
+            if (threadIdx.x == 0) {
+                float2 e = make_float2(0.f, 0.f);                    // (every element NaN: no candidate, the flag says so)
+                if (p < 2ull * (unsigned long long)a.n) e = p < (unsigned long long)a.n ? a.X[p] : a.y[p - (unsigned long long)a.n];
+                a.part[a.parts] = PeakCand{p, k, bad, e.x, e.y};
+            }
+        }
+    }
+}
+
+int song_peak_parts(long long n) {
+    const long long groups = (n + 1023) / 1024;         // n complex64 of each slab = n float4 in all, 1024 a workgroup and step
+    return (int)(groups < kPeakParts ? groups : kPeakParts);
+}
+
+void launch_song_peak(const float2* X, const float2* y, long long n, PeakCand* ws, hipStream_t st) {
+    const int parts = song_peak_parts(n);
+    const SongPeak a{X, y, n, ws, parts};
+    prof_note(0.0, 16.0 * (double)n);
+    VR_LAUNCH((augment_kernel<SongPeak, false>), dim3((unsigned)parts), dim3(256), 0, st, a);
+    VR_HIP(hipGetLastError());
+    VR_LAUNCH((augment_kernel<SongPeak, true>), dim3(1), dim3(256), 0, st, a);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_song_windows(const SongWindow* table, int B, int T, int bins, float* X_out, float* y_out, bool out_complex, hipStream_t st) {
+    const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
+    const SongWindows a{table, T, bins, X_out, y_out};
+    if (out_complex) VR_LAUNCH((augment_kernel<SongWindows, true>), grid, block, 0, st, a);
+    else VR_LAUNCH((augment_kernel<SongWindows, false>), grid, block, 0, st, a);
+    VR_HIP(hipGetLastError());
+}
+
 void launch_pitch_diff(const float* mix, const float* inst, float* v, long long n, hipStream_t st) {
     if (n <= 0) return;
     prof_note(0.0, 12.0 * (double)n);

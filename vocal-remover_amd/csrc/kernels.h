@@ -64,6 +64,30 @@ void launch_augment(const float2* X, const float2* Y, const float2* Xi, const fl
 struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
                              float* Ymag, bool out_complex, hipStream_t st);
+// windows of resident songs (vr_dataset_windows): one entry per sample, the pointers at row 0 of the song's slabs;
+// sample b is rows [start, start + T) of them, a row outside [0, rows) zero, every value read times `scale`
+struct SongWindow { const float2 *X, *y; long long rows, start; float scale; int reserved; };
+struct SongWindows { const SongWindow* table; int T, bins; float *X_out, *y_out; };      // outputs [B][2][bins][T], fp32 or complex64
+void launch_song_windows(const SongWindow* table, int B, int T, int bins, float* X_out, float* y_out, bool out_complex, hipStream_t st);
+// np.abs of one complex64 as numpy computes it (its loop for complex absolute, numpy 1.25 and later on a CPU with fused multiply-add):
+// larger * sqrt(fma(ratio, ratio, 1)), ratio = smaller / larger, all float32 -- NOT hypotf, from which it differs in the last bit of
+// about a third of all values, and not monotone in the exact magnitude.  Five correctly rounded IEEE operations: host and device agree.
+__host__ __device__ inline float numpy_cabsf(float re, float im) {
+    re = fabsf(re); im = fabsf(im);
+    if (re == INFINITY || im == INFINITY) return INFINITY; // inf beside NaN is inf
+    if (re != re || im != im) return NAN;
+    const float larger = fmaxf(re, im), smaller = fminf(re, im);
+    const float ratio = larger == 0.f ? 0.f : smaller / larger;
+    return sqrtf(fmaf(ratio, ratio, 1.f)) * larger;
+}
+// the element of largest np.abs of one resident song (vr_dataset_peak): X, y slabs of n complex64 each (n even).  ws holds
+// kPeakParts + 1 candidates: one per workgroup of the first launch, and at [song_peak_parts(n)] the result -- pos = the element's index
+// in the sequence [X | y], key = its numpy_cabsf, bad = a NaN key was met, re, im = the element.
+struct PeakCand { unsigned long long pos; float key; unsigned bad; float re, im; };
+struct SongPeak { const float2 *X, *y; long long n; PeakCand* part; int parts; };
+constexpr int kPeakParts = 2048;                          // 256 CUs x 8 workgroups; a shorter song launches fewer (song_peak_parts)
+int song_peak_parts(long long n);
+void launch_song_peak(const float2* X, const float2* y, long long n, PeakCand* ws, hipStream_t st);
 // the pitch forms of the same kernel family: the argument struct selects the body
 struct PitchDiff { const float* mix; const float* inst; float* v; long long n; };          // v = mix - inst
 struct PitchVocoder {                                                                       // librosa.phase_vocoder, fp64 phase

@@ -143,6 +143,8 @@ struct StreamState {
 // [rows][2][bins] complex64, the on-disk layout of spec_utils.SpectrogramCache.  The store owns its allocations and nothing of any
 // handle: it may outlive handles, and every handle on its device may cut batches from it (Model::dataset_batch_api).
 struct ResidentCrop { int song, mix_song; long long start, mix_start; };        // layout-compatible with vr_crop
+struct ResidentWindow { int song, reserved; long long start; float scale; };    // layout-compatible with vr_window
+struct PeakCand;
 struct ResidentSet {
     struct Song { float2* X; float2* y; long long rows; };
     int device, bins;
@@ -153,7 +155,10 @@ struct ResidentSet {
     ResidentSet(const ResidentSet&) = delete;
     ResidentSet& operator=(const ResidentSet&) = delete;
     int add(const float* X, const float* y, long long rows);                    // -> song index
+    // vr_dataset_peak: np.max([np.abs(X).max(), np.abs(y).max()]) of one song, on the store's own stream; returns with the result
+    float peak(int song, float* at, int* slab, long long* index);
 private:
+    PeakCand* peak_ws = nullptr;                                                // kPeakParts + 1 candidates (kernels.h), made at the first peak
     static constexpr size_t kPiece = size_t(8) << 20;                           // upload staging: two pinned pieces, never a whole song
     hipStream_t up = nullptr;
     char* stage[2] = {nullptr, nullptr};
@@ -334,6 +339,8 @@ public:
                      int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
     void dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
                            float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
+    void dataset_windows_api(const ResidentSet& set, const ResidentWindow* w, int B, int T, float* Xmag, float* ymag, bool out_on_dev,
+                             bool out_complex = false);
     char* aug_buf = nullptr; size_t aug_cap = 0;         // staging of the training input pipeline
     void aug_reserve(size_t need);
     bool train_wino = true;                              // vr_set_option("train_winograd"): Winograd kernels in train mode

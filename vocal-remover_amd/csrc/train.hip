@@ -2,6 +2,7 @@
 // (train.py:81-96: loss = L1(mask*X, y); (loss/accumulation_steps).backward(); optimizer.step()).
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 #include "model.h"
 
@@ -671,6 +672,7 @@ ResidentSet::~ResidentSet() {
     (void)hipSetDevice(device);
     if (up) (void)hipStreamSynchronize(up);
     for (Song& s : songs) { (void)hipFree(s.X); (void)hipFree(s.y); }
+    if (peak_ws) (void)hipFree(peak_ws);
     for (int i = 0; i < 2; ++i) {
         if (stage[i]) (void)hipHostFree(stage[i]);
         if (drained[i]) (void)hipEventDestroy(drained[i]);
@@ -724,6 +726,73 @@ int ResidentSet::add(const float* X, const float* y, long long rows) {
     songs.push_back(Song{dev[0], dev[1], rows});
     bytes += 2 * (long long)slab;
     return (int)songs.size() - 1;
+}
+
+// The peak of one song from its resident rows: two launches on the store's stream (augment.hip, SongPeak), one candidate back.  The
+// float is formed here, from the one element the device reports, by the operations numpy's np.abs performs on a complex64.
+float ResidentSet::peak(int song, float* at, int* slab, long long* index) {
+    VR_CHECK(song >= 0 && song < (int)songs.size(), -2, "vr_dataset_peak: song " + std::to_string(song) + " out of range (the dataset holds " +
+                                                            std::to_string(songs.size()) + ")");
+    DeviceGuard dev_guard(device);
+    const Song& s = songs[song];
+    const long long n = s.rows * 2 * bins;
+    const int parts = song_peak_parts(n);
+    VR_CHECK(parts >= 1 && parts <= kPeakParts, -1, "vr_dataset_peak: " + std::to_string(parts) + " partials for a workspace of " +
+                                                        std::to_string(kPeakParts));
+    if (!peak_ws) {
+        const size_t ws_bytes = (size_t)(kPeakParts + 1) * sizeof(PeakCand);
+        if (hipMalloc(reinterpret_cast<void**>(&peak_ws), ws_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            peak_ws = nullptr;
+            throw Error(-4, "vr_dataset_peak: hipMalloc of " + std::to_string(ws_bytes) + " bytes failed (the store holds " +
+                                std::to_string(bytes) + " bytes in " + std::to_string(songs.size()) + " songs)");
+        }
+    }
+    launch_song_peak(s.X, s.y, n, peak_ws, up);
+    PeakCand r;
+    VR_HIP(hipMemcpyAsync(&r, peak_ws + parts, sizeof(PeakCand), hipMemcpyDeviceToHost, up));
+    VR_HIP(hipStreamSynchronize(up));
+    if (at) { at[0] = r.re; at[1] = r.im; }
+    if (slab) *slab = r.pos >= (unsigned long long)n ? 1 : 0;
+    if (index) *index = (long long)(r.pos >= (unsigned long long)n ? r.pos - (unsigned long long)n : r.pos);
+    return r.bad ? std::numeric_limits<float>::quiet_NaN() : numpy_cabsf(r.re, r.im);
+}
+
+// Windows of resident songs (vr_dataset_windows): every entry is checked on the host, the table goes to the handle's aug_buf in one copy
+// and the SongWindows form of augment_kernel reads the rows where they lie.  A window may leave its song on either side (those rows are
+// zero), so the checks are the song index, start + T as an int64, and a finite scale.
+void Model::dataset_windows_api(const ResidentSet& set, const ResidentWindow* w, int B, int T, float* Xmag, float* ymag, bool out_on_dev,
+                                bool out_complex) {
+    VR_CHECK(set.device == device, -2, "vr_dataset_windows: the handle is on device " + std::to_string(device) + ", the dataset on device " +
+                                           std::to_string(set.device));
+    VR_CHECK(T > 0, -2, "vr_dataset_windows: T must be positive");
+    const int bins = set.bins, n_songs = (int)set.songs.size();
+    auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t tab_b = (size_t)B * sizeof(SongWindow), head = up256(tab_b);
+    const size_t out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
+    std::vector<SongWindow> tab((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const std::string who = "vr_dataset_windows: sample " + std::to_string(b) + ": ";
+        VR_CHECK(w[b].song >= 0 && w[b].song < n_songs, -2, who + "song " + std::to_string(w[b].song) + " out of range (the dataset holds " +
+                                                               std::to_string(n_songs) + ")");
+        VR_CHECK(w[b].start <= std::numeric_limits<long long>::max() - T, -2, who + "start " + std::to_string(w[b].start) + " + T " +
+                                                                                 std::to_string(T) + " overflows");
+        VR_CHECK(std::isfinite(w[b].scale), -2, who + "scale " + std::to_string(w[b].scale) + " is not finite");
+        const ResidentSet::Song& s = set.songs[w[b].song];
+        tab[b] = SongWindow{s.X, s.y, s.rows, w[b].start, w[b].scale, 0};
+    }
+    DeviceGuard dev_guard(device);
+    aug_reserve(head + (out_on_dev ? 0 : 2 * up256(out_b)));
+    VR_HIP(hipMemcpyAsync(aug_buf, tab.data(), tab_b, hipMemcpyHostToDevice, stream));
+    float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(aug_buf + head);
+    float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(aug_buf + head + up256(out_b));
+    prof_note(0.0, (out_complex ? 32.0 : 24.0) * (double)B * 2 * bins * T);
+    launch_song_windows(reinterpret_cast<const SongWindow*>(aug_buf), B, T, bins, ox, oy, out_complex, stream);
+    if (!out_on_dev) {
+        VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
+        VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));
+    }
+    VR_HIP(hipStreamSynchronize(stream));
 }
 
 // One batch cut from the store: the host checks every crop against its song (the kernel is never given a row it cannot read), then

@@ -98,17 +98,26 @@ class VocalRemoverTrainingSet(object):
             flags |= 4
         return flags
 
+    def _coef(self, row):
+        if row[2] is None:
+            raise ValueError('%s: the peak of this row is None (make_training_set(peaks=False)).  VocalRemoverTrainingSet reads crops '
+                             'from the files and has no whole song to take a peak from: build the rows with peaks=True, or use '
+                             'ResidentTrainingSet, which takes the peak on the device at upload' % (row[0],))
+        return float(row[2])
+
     def plan(self, idx):
-        X_path, y_path, coef = self.training_set[idx]
+        X_path, y_path = self.training_set[idx][:2]
+        coef = self._coef(self.training_set[idx])
         n_rows = self.read_npy_shape(X_path)[0]
-        p = {'paths': (X_path, y_path), 'coef': float(coef), 'start': int(np.random.randint(0, n_rows - self.cropsize))}
+        p = {'paths': (X_path, y_path), 'coef': coef, 'start': int(np.random.randint(0, n_rows - self.cropsize))}
         p['flags'] = self._draw_aug()
         p['mix'] = None
         if np.random.uniform() < self.mixup_rate:
             j = int(np.random.randint(0, len(self)))
-            Xj, yj, coef_j = self.training_set[j]
+            Xj, yj = self.training_set[j][:2]
+            coef_j = self._coef(self.training_set[j])
             nj = self.read_npy_shape(Xj)[0]
-            m = {'paths': (Xj, yj), 'coef': float(coef_j), 'start': int(np.random.randint(0, nj - self.cropsize))}
+            m = {'paths': (Xj, yj), 'coef': coef_j, 'start': int(np.random.randint(0, nj - self.cropsize))}
             m['flags'] = self._draw_aug()
             m['lam'] = float(np.random.beta(self.mixup_alpha, self.mixup_alpha))
             p['mix'] = m
@@ -260,11 +269,13 @@ class ResidentTrainingSet(_Resident):
     (MemoryError at construction when the distinct songs of the list need more); same numpy draws in the same order, so from one
     numpy seed `batch(indices)` returns what VocalRemoverTrainingSet.batch returns, bit for bit, and leaves numpy's generator
     where that leaves it.  The first batch uploads every distinct (X, y) pair of the list once, through a memory map of the .npy
-    files; `model` may be swapped for another model on the same device at any time (the store belongs to the set, not to a handle)."""
+    files; `model` may be swapped for another model on the same device at any time (the store belongs to the set, not to a handle).
+    A row's peak may be None (make_training_set(peaks=False)): the upload takes it on the device from the resident rows
+    (native.Dataset.peak, the same float32) and keeps it in the set's own copy of the list -- the caller's rows are not written."""
 
     def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None,
                  complex_output=False):
-        self.training_set = training_set
+        self.training_set = [list(row) for row in training_set]      # (a copy: peaks that are None are filled in here at upload)
         self.complex_output = bool(complex_output)
         self.cropsize = cropsize
         self.reduction_rate = reduction_rate
@@ -290,6 +301,7 @@ class ResidentTrainingSet(_Resident):
 
     __len__ = VocalRemoverTrainingSet.__len__
     _draw_aug = VocalRemoverTrainingSet._draw_aug
+    _coef = VocalRemoverTrainingSet._coef
     plan = VocalRemoverTrainingSet.plan          # the draws themselves: one statement of them for both classes
 
     def read_npy_shape(self, path):
@@ -310,6 +322,9 @@ class ResidentTrainingSet(_Resident):
                     raise ValueError('%s, %s: %d and %d rows, a resident pair has as many of both'
                                      % (X_path, y_path, pair[0].shape[0], pair[1].shape[0]))
                 assert store.add(pair[0], pair[1]) == song
+            for row in self.training_set:
+                if row[2] is None:
+                    row[2] = store.peak(self._song[(row[0], row[1])])
         except Exception:
             store.close()
             raise
@@ -400,6 +415,94 @@ class ResidentValidationSet(_Resident):
         return self._batch(h, crops, desc, None, self._T)
 
 
+def validation_windows(frames, cropsize, offset):
+    """The signed start rows of the windows make_validation_set cuts from a song of `frames` frames: window j of the make_padding-padded
+    song is columns [j * roi, j * roi + cropsize) of it, which are rows [j * roi - left, j * roi - left + cropsize) of the song itself,
+    j < ceil(frames / roi).  The first starts before row 0 by `left`, the last may end past the song: those rows are the padding."""
+    left, _, roi = make_padding(frames, cropsize, offset)
+    return [j * roi - left for j in range(-(-frames // roi))]
+
+
+class ResidentSongValidationSet(_Resident):
+    """The validation set cut from the song caches alone, without patch files: `song_rows` is what make_training_set returns for the
+    validation pairs ([[X npy, y npy, peak or None], ...]), every distinct pair is uploaded once as the rows it is cached as, and item k
+    is window j of song i in make_validation_set's order (song-major, window-minor): rows validation_windows(...)[j] onwards, zero
+    outside the song, times the float32 1 / peak -- what `np.pad(X / peak)` holds.  A batch is one vr_dataset_windows call and equals,
+    bit for bit, the batch of ResidentValidationSet(make_validation_set(...)) for the same songs, cropsize and offset.  A peak that is
+    None is taken on the device at upload.  A peak of 0 or NaN raises ValueError naming the song (make_validation_set would write
+    patches of NaN)."""
+
+    def __init__(self, song_rows, cropsize, offset, model=None, max_bytes=None, complex_output=False):
+        self.song_rows = [list(row) for row in song_rows]
+        self.cropsize, self.offset = int(cropsize), int(offset)
+        self.model = model
+        self.complex_output = bool(complex_output)
+        self.max_bytes = max_bytes
+        self._song = {}                        # (X path, y path) -> index in the store, in first-seen order
+        self._items = []                       # (row of song_rows, start row of the window)
+        self._bins = None
+        self._scale = None                     # per row of song_rows: float32 1 / peak, known after the upload
+        need = 0
+        for i, (X_path, y_path, _) in enumerate(self.song_rows):
+            shape, dtype, _ = _npy_header(X_path)
+            if len(shape) != 3 or shape[1] != 2 or dtype != np.complex64:
+                raise ValueError('%s: expected complex64 rows of shape [T, 2, bins], found %s %s' % (X_path, dtype, shape))
+            if self._bins is None:
+                self._bins = int(shape[2])
+            if (X_path, y_path) not in self._song:
+                self._song[(X_path, y_path)] = len(self._song)
+                need += 2 * int(np.prod(shape)) * dtype.itemsize
+            self._items.extend((i, start) for start in validation_windows(int(shape[0]), self.cropsize, self.offset))
+        self._need = need
+        _check_capacity('ResidentSongValidationSet: %d songs' % len(self._song), need, max_bytes)
+
+    def __len__(self):
+        return len(self._items)
+
+    def _upload(self, device):
+        store = native.Dataset(device, self._bins)
+        try:
+            for (X_path, y_path), song in self._song.items():
+                pair = []
+                for path in (X_path, y_path):
+                    a = np.load(path, mmap_mode='r')
+                    if a.dtype != np.complex64 or tuple(a.shape[1:]) != (2, self._bins):
+                        raise ValueError('%s: expected complex64 rows of shape %s, found %s %s' % (path, (2, self._bins), a.dtype, a.shape[1:]))
+                    pair.append(a)
+                if pair[0].shape[0] != pair[1].shape[0]:
+                    raise ValueError('%s, %s: %d and %d rows, a resident pair has as many of both'
+                                     % (X_path, y_path, pair[0].shape[0], pair[1].shape[0]))
+                assert store.add(pair[0], pair[1]) == song
+            scale = []
+            for row in self.song_rows:
+                if row[2] is None:
+                    row[2] = store.peak(self._song[(row[0], row[1])])
+                peak = np.float32(row[2])
+                if not peak > 0:
+                    raise ValueError('%s: the peak of the pair is %r, the song cannot be normalised' % (row[0], float(peak)))
+                scale.append(np.float32(1) / peak)
+        except Exception:
+            store.close()
+            raise
+        self._store, self._scale = store, scale
+
+    def batch(self, indices):
+        h = self._handle()
+        if self._store is None:
+            self._upload(h.device)
+        B, T = len(indices), self.cropsize
+        table = (native.Window * B)()
+        for b, k in enumerate(indices):
+            i, start = self._items[k]
+            row = self.song_rows[i]
+            table[b] = native.Window(self._song[(row[0], row[1])], 0, start, self._scale[i])
+        dev = torch.device('cuda', h.device)
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, self._bins, T), dev, 'vr_dataset_windows')
+        native.check(call(h.h, self._store.d, ctypes.cast(table, ctypes.c_void_p), B, T,
+                          ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
+        return X_mag, y_mag
+
+
 class DeviceLoader(object):
     """Iterable stand-in for torch.utils.data.DataLoader(dataset, batch_size, shuffle) (train.py:242-247):
     yields (X_batch, y_batch) device tensors produced by one vr_augment_batch call per batch."""
@@ -473,14 +576,19 @@ def _song_peak(X, y):
     return np.max([np.abs(X).max(), np.abs(y).max()])
 
 
-def make_training_set(filelist, sr, hop_length, n_fft):
-    """One [mixture cache path, instrumental cache path, peak magnitude of the pair] row per song (VocalRemoverTrainingSet input)."""
+def make_training_set(filelist, sr, hop_length, n_fft, peaks=True):
+    """One [mixture cache path, instrumental cache path, peak magnitude of the pair] row per song (VocalRemoverTrainingSet input).
+    peaks=False: every peak is None and a cached pair is not read beyond its two headers -- for the resident sets, which take the
+    peak on the device from the rows they upload (ResidentTrainingSet, ResidentSongValidationSet)."""
     from .spec_utils import SpectrogramCache
     cache = SpectrogramCache(sr, hop_length, n_fft)
     rows = []
     for mix_path, inst_path in filelist:
-        X, y, mix_npy, inst_npy = cache.pair(mix_path, inst_path)
-        rows.append([mix_npy, inst_npy, _song_peak(X, y)])
+        if peaks:
+            X, y, mix_npy, inst_npy = cache.pair(mix_path, inst_path)
+            rows.append([mix_npy, inst_npy, _song_peak(X, y)])
+        else:
+            rows.append(list(cache.pair_paths(mix_path, inst_path)) + [None])
     return rows
 
 

@@ -120,6 +120,12 @@ _SIGNATURES = {
                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'vr_dataset_batch_complex': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    'vr_dataset_peak': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                       ctypes.POINTER(ctypes.c_int), c_i64p]),
+    'vr_dataset_windows': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int]),
+    'vr_dataset_windows_complex': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'vr_validate_step': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_float)]),
     'vr_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
@@ -275,6 +281,10 @@ class Crop(ctypes.Structure):               # include/vr_mi355.h: vr_crop
     _fields_ = [('song', ctypes.c_int), ('mix_song', ctypes.c_int), ('start', ctypes.c_int64), ('mix_start', ctypes.c_int64)]
 
 
+class Window(ctypes.Structure):             # include/vr_mi355.h: vr_window
+    _fields_ = [('song', ctypes.c_int), ('reserved', ctypes.c_int), ('start', ctypes.c_int64), ('scale', ctypes.c_float)]
+
+
 class Dataset:
     """Owns one vr_dataset: songs resident on one GPU, independent of any Handle."""
 
@@ -315,6 +325,15 @@ class Dataset:
         r = ctypes.c_int64()
         check(lib().vr_dataset_rows(self.d, int(song), ctypes.byref(r)))
         return int(r.value)
+
+    def peak(self, song, where=False):
+        """np.max([np.abs(X).max(), np.abs(y).max()]) of one song, taken on the device from its resident rows -> np.float32.
+        where=True: -> (peak, complex64 element that attains it, slab (0 = X, 1 = y), flat complex index in the slab)."""
+        p, at = ctypes.c_float(), (ctypes.c_float * 2)()
+        slab, index = ctypes.c_int(), ctypes.c_int64()
+        check(lib().vr_dataset_peak(self.d, int(song), ctypes.byref(p), at, ctypes.byref(slab), ctypes.byref(index)))
+        peak = np.float32(p.value)
+        return (peak, np.complex64(complex(at[0], at[1])), int(slab.value), int(index.value)) if where else peak
 
 
 class Handle:

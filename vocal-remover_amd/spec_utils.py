@@ -289,6 +289,21 @@ class SpectrogramCache(object):
         assert specs[0].shape == specs[1].shape
         return specs[0], specs[1], paths[0], paths[1]
 
+    def pair_paths(self, mix_path, inst_path):
+        """-> the two .npy paths of `pair`, without its arrays: on a cache hit only the two headers are read (the shapes must agree, as
+        `pair` asserts); a miss builds the cache as `pair` does."""
+        paths = [self.npy_path(mix_path), self.npy_path(inst_path)]
+        if not all(os.path.exists(p) for p in paths):
+            return self.pair(mix_path, inst_path)[2:]
+        shapes = []
+        for p in paths:
+            with open(p, 'rb') as f:
+                version = np.lib.format.read_magic(f)
+                read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+                shapes.append(read(f)[0])
+        assert shapes[0] == shapes[1]
+        return paths[0], paths[1]
+
 
 def cache_or_load(mix_path, inst_path, sr, hop_length, n_fft):
     """The reference's entry point to the cache (lib/spec_utils.py:122): X, y, X_cache_path, y_cache_path."""
