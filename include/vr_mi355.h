@@ -36,7 +36,8 @@ enum vr_status {
     VR_ERR_CROP_CENTER = -5,    /* reference ValueError of spec_utils.crop_center (spec_utils.py:15) */
     VR_ERR_EMPTY_MASK = -6,     /* reference `assert mask.size()[3] > 0` (nets.py:129,139)         */
     VR_ERR_INDEX = -7,          /* reference IndexError in merge_artifacts (spec_utils.py:65, empty idx) */
-    VR_ERR_COMM = -8            /* RCCL could not be loaded, or a collective failed                        */
+    VR_ERR_COMM = -8,           /* RCCL could not be loaded, or a collective failed                        */
+    VR_ERR_UNSUPPORTED = -9     /* the handle has no kernel for this request (vr_pair_rows_many: hop_length != n_fft / 2); the caller's other route applies */
 };
 
 const char* vr_last_error(void);
@@ -322,6 +323,44 @@ int vr_pitch_shift_many(vr_handle h, int n, const float* const* waves, int on_de
 int vr_pitch_pair_many(vr_handle h, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L, int shift_n_fft,
                        int shift_hop, double rate, double ratio, int layout, int64_t max_bytes, float* const* X_out, float* const* y_out,
                        int out_on_device);
+
+/* ---- plain training pairs on the device: trim, align, STFT rows and peak, many pairs per call (csrc/prepare.hip) ----
+ * What the reference's spec_utils.cache_or_load does to a decoded (mixture, instrumental) pair, in two steps; the window of step 1
+ * sizes the outputs of step 2, so it comes back to the host between them (64 bytes per pair).  Waves are float32 [2][L], host or device.
+ *   vr_pair_window_plan  no device: the window arithmetic, the one statement every layer uses.  lag > 0 moves a_off = a_start + lag, otherwise
+ *                        b_off = b_start - lag; n = min(a_end - a_off, b_end - b_off); n <= 0 is VR_ERR_BAD_ARGUMENT.
+ *   vr_align_pair_many   no handle.  Per wave librosa.effects.trim(top_db 60, frame_length 2048, hop_length 512): centre zero padding of
+ *                        1024 samples, 1 + L / 512 frames, per frame and channel the mean square summed in double and rms =
+ *                        float32(sqrt(.)), ref = the largest rms of both channels, a frame is signal where on any channel
+ *                        20 log10(max(1e-5, rms)) - 20 log10(max(1e-5, ref)) > -60; start = first * 512, end = min(L, (last + 1) * 512)
+ *                        (an all-zero wave keeps everything).  Heads: the first min(4 * sr, end - start) trimmed samples, the two channels
+ *                        added (one float32 addition), the mean (summed in double) removed.  lag = argmax_first(correlate(a, b, 'full')) -
+ *                        (na - 1), correlation and argmax on the device; the contract of the lag search is the lag of a well-conditioned
+ *                        pair, not the bits of the correlation (vr_xcorr_argmax keeps its own arithmetic).  Every stage but the
+ *                        correlation is one launch over the call's table; one wait and one copy of n windows back per call.  An empty
+ *                        window is VR_ERR_BAD_ARGUMENT and vr_last_error() names the pair.  inst[i] NULL: the mixture is trimmed alone
+ *                        (b_start, b_end repeat a_start, a_end; no correlation, lag 0).
+ *   vr_pair_rows_many    the STFT rows [T][2][bins] complex64 (the training cache's layout, T = 1 + n / hop_length) of
+ *                        mix[i][:, a_off : a_off + n] and inst[i][:, b_off : b_off + n] at the handle's n_fft / hop_length, the values those of
+ *                        vr_stft on the sliced waves, and peaks[i] = max(max|X|, max|y|) as numpy forms it in float32, taken on the device
+ *                        from the rows just written.  The windows are the caller's: however they were found.  hop_length != n_fft / 2:
+ *                        VR_ERR_UNSUPPORTED (the rows are a form of the frame-tiled STFT).  The pairs run one after the other through one
+ *                        workspace sized for the largest (its two windows, and the rows when the outputs are host memory), checked against
+ *                        max_bytes (<= 0: nine tenths of the free device memory) before anything is allocated: VR_ERR_OOM, and
+ *                        vr_last_error() names both sizes.
+ * Nothing is accumulated with atomics: two identical calls agree bit for bit.                                                         */
+typedef struct vr_pair_window {
+    int64_t a_start, a_end;     /* the mixture's trimmed range */
+    int64_t b_start, b_end;     /* the instrumental's */
+    int64_t lag;                /* > 0: the mixture starts late by lag samples */
+    int64_t a_off, b_off, n;    /* the common window: n samples from a_off of the mixture, from b_off of the instrumental */
+} vr_pair_window;
+int vr_pair_window_plan(int64_t a_start, int64_t a_end, int64_t b_start, int64_t b_end, int64_t lag, vr_pair_window* out);
+int vr_align_pair_many(int device, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L_mix,
+                       const int64_t* L_inst, int sr, vr_pair_window* out);
+int vr_pair_rows_many(vr_handle h, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L_mix,
+                      const int64_t* L_inst, const vr_pair_window* w, int64_t max_bytes, float* const* X_out, float* const* y_out,
+                      int out_on_device, float* peaks);
 
 /* ---- streaming separation: push audio in blocks, get the stems back with bounded state -----------------------------------
  * The offline call's crops sit at multiples of roi = cropsize - 2 * offset whatever the song's length (make_padding: pad_l = offset),

@@ -630,3 +630,49 @@ def trim(y, top_db=60, frame_length=2048, hop_length=512):
     else:
         start, end = 0, 0
     return y[..., start:end], np.asarray([start, end])
+
+
+def _stereo_waves(waves, who):
+    """-> ([(wave [2, L] float32 contiguous, address)], on the device): either every wave is a numpy array or every wave is a cuda tensor"""
+    ins = []
+    for w in waves:
+        if not _on_device(w):
+            w = np.asarray(w, dtype=np.float32)
+        ins.append(_float_in(_stereo(w)[0]))
+    flags = [on for _, _, on in ins]
+    if any(flags) and not all(flags):
+        raise ValueError('%s: either every wave is a cuda tensor or none is' % who)
+    if any(x.shape[1] == 0 for x, _, _ in ins):
+        raise ValueError('%s: empty wave' % who)
+    return [(x, p) for x, p, _ in ins], bool(flags and flags[0])
+
+
+def align_windows(mixes, insts, sr):
+    """One vr_align_pair_many call -> [native.PairWindow]: per pair the two trimmed ranges, the lag and the common window.  insts[i]
+    None: the mixture is trimmed alone.  Waves [L] or [2, L], numpy or cuda."""
+    ct = native.ctypes
+    mixes, insts = list(mixes), list(insts)
+    if len(mixes) != len(insts):
+        raise ValueError('align: %d mixtures but %d instrumentals' % (len(mixes), len(insts)))
+    N = len(mixes)
+    if not N:
+        return []
+    given = [k for k, w in enumerate(insts) if w is not None]
+    ins, on_dev = _stereo_waves(mixes + [insts[k] for k in given], 'align')
+    xs, ys = ins[:N], dict(zip(given, ins[N:]))
+    out = (native.PairWindow * N)()
+    dev = xs[0][0].device.index if on_dev else _device()
+    native.check(native.lib().vr_align_pair_many(
+        int(dev), N, (ct.c_void_p * N)(*[p for _, p in xs]), (ct.c_void_p * N)(*[ys[k][1] if k in ys else None for k in range(N)]),
+        1 if on_dev else 0, (ct.c_int64 * N)(*[int(x.shape[1]) for x, _ in xs]),
+        (ct.c_int64 * N)(*[int(ys[k][0].shape[1]) if k in ys else 0 for k in range(N)]), int(sr), out))
+    return list(out)
+
+
+def trim_many(waves, top_db=60, frame_length=2048, hop_length=512):
+    """The (start, end) of trim() for every wave in ONE library call, the frames measured on the device (vr_align_pair_many with no second
+    wave): waves[i] [L_i] or [2, L_i], numpy or cuda -> [(start, end)].  Only trim's defaults are built."""
+    if (top_db, frame_length, hop_length) != (60, 2048, 512):
+        raise NotImplementedError('trim_many: only top_db 60, frame_length 2048, hop_length 512 (the defaults the reference uses)')
+    waves = list(waves)
+    return [(int(w.a_start), int(w.a_end)) for w in align_windows(waves, [None] * len(waves), 1)]

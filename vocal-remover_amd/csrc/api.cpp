@@ -11,6 +11,10 @@ namespace vr {
 void resample_api(int device, const float* x, int channels, long long n_in, int sr_in, int sr_out, float* y, long long n_out);
 void resample_ratio_api(int device, const float* x, int channels, long long n_in, double ratio, float* y, long long n_out);
 void xcorr_argmax_api(int device, const float* a, long long na, const float* b, long long nb, long long* argmax_out);
+void align_pair_check(int n, const float* const* mix, const float* const* inst, const long long* L_mix, const long long* L_inst, int sr,
+                      const void* out);
+void align_pair_many_api(int device, int n, const float* const* mix, const float* const* inst, bool on_dev, const long long* L_mix,
+                         const long long* L_inst, int sr, PairWindow* out);
 struct Resampler;
 long long resampler_plan(int sr_in, int sr_out, long long samples_in, bool flushed);
 Resampler* resampler_open(int device, int channels, int sr_in, int sr_out);
@@ -853,6 +857,48 @@ int vr_pitch_pair_many(vr_handle h, int n, const float* const* mix, const float*
         std::vector<long long> len(L, L + n);
         h->m.pitch_run(n, mix, inst, on_device != 0, 2, len.data(), shift_n_fft, shift_hop, rate, ratio, max_bytes, nullptr, X_out, y_out, layout,
                        out_on_device != 0);
+    });
+}
+
+// ---- plain training pairs: trim, align, STFT rows and peak (csrc/prepare.hip) ------------------------------------------------------
+static_assert(sizeof(vr_pair_window) == sizeof(vr::PairWindow) && offsetof(vr_pair_window, n) == offsetof(vr::PairWindow, n),
+              "vr_pair_window and vr::PairWindow must agree");
+
+int vr_pair_window_plan(int64_t a_start, int64_t a_end, int64_t b_start, int64_t b_end, int64_t lag, vr_pair_window* out) {
+    return guard([&] {
+        VR_CHECK(out, VR_ERR_BAD_ARGUMENT, "null argument");
+        VR_CHECK(a_start >= 0 && a_start <= a_end && b_start >= 0 && b_start <= b_end, VR_ERR_BAD_ARGUMENT,
+                 "pair window: a trimmed range must be 0 <= start <= end");
+        vr::PairWindow w{a_start, a_end, b_start, b_end, lag, 0, 0, 0};
+        const bool ok = vr::pair_window_plan(w);
+        std::memcpy(out, &w, sizeof(w));
+        VR_CHECK(ok, VR_ERR_BAD_ARGUMENT, "pair window: the common window is empty (n = " + std::to_string(w.n) + ")");
+    });
+}
+
+int vr_align_pair_many(int device, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L_mix,
+                       const int64_t* L_inst, int sr, vr_pair_window* out) {
+    if (n <= 0 || !mix || !inst || !L_mix || !L_inst || !out) { g_err = "align pair: no pair or a null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        std::vector<long long> la(L_mix, L_mix + n), lb(L_inst, L_inst + n);
+        vr::align_pair_check(n, mix, inst, la.data(), lb.data(), sr, out);
+        need_device(device);
+        vr::align_pair_many_api(device, n, mix, inst, on_device != 0, la.data(), lb.data(), sr, reinterpret_cast<vr::PairWindow*>(out));
+    });
+}
+
+int vr_pair_rows_many(vr_handle h, int n, const float* const* mix, const float* const* inst, int on_device, const int64_t* L_mix,
+                      const int64_t* L_inst, const vr_pair_window* w, int64_t max_bytes, float* const* X_out, float* const* y_out,
+                      int out_on_device, float* peaks) {
+    if (n <= 0 || !mix || !inst || !L_mix || !L_inst || !w || !X_out || !y_out || !peaks) {
+        g_err = "pair rows: no pair or a null table";
+        return VR_ERR_BAD_ARGUMENT;
+    }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> la(L_mix, L_mix + n), lb(L_inst, L_inst + n);
+        h->m.pair_rows_run(n, mix, inst, on_device != 0, la.data(), lb.data(), reinterpret_cast<const vr::PairWindow*>(w), max_bytes, X_out, y_out,
+                           out_on_device != 0, peaks);
     });
 }
 

@@ -101,6 +101,55 @@ struct PitchPlan { int T, T_stretch; long long n_stretch, n_resampled; };
 PitchPlan pitch_plan(long long L, int n_fft, int hop, double rate, double ratio);
 void launch_pitch_diff(const float* mix, const float* inst, float* v, long long n, hipStream_t st);
 void launch_phase_vocoder(const float2* D, float2* out, int signals, int bins, int T, int Tout, int hop, double rate, hipStream_t st);
+// ---- plain training pairs (prepare.hip; vr_align_pair_many / vr_pair_rows_many) -----------------------------------
+// Layout-compatible with vr_pair_window (include/vr_mi355.h): the trimmed ranges of the two waves, the lag of the mixture's head behind
+// the instrumental's, and the common window -- n samples from a_off of the mixture and from b_off of the instrumental.
+struct PairWindow { long long a_start, a_end, b_start, b_end, lag, a_off, b_off, n; };
+// THE statement of the window arithmetic (vr_pair_window_plan; spec_utils.align_wave_head_and_tail's slicing): fills a_off, b_off, n from
+// the other five; false when the window is empty (n <= 0)
+inline bool pair_window_plan(PairWindow& w) {
+    w.a_off = w.a_start;
+    w.b_off = w.b_start;
+    if (w.lag > 0) w.a_off += w.lag;
+    else w.b_off -= w.lag;
+    const long long na = w.a_end - w.a_off, nb = w.b_end - w.b_off;
+    w.n = na < nb ? na : nb;
+    return w.n > 0;
+}
+constexpr int kTrimFrame = 2048, kTrimHop = 512;     // librosa.effects.trim's defaults, top_db 60 (audio.trim)
+// what the device keeps of one wave between the launches of a call: the trimmed range, the head's length and its mean
+struct PrepState { long long start, end, nh; float mean, ref; };
+// one wave of a call (2 per pair: the mixture 2 i, the instrumental 2 i + 1); a grid dimension picks the entry
+struct PrepWave {
+    const float* w;           // [2][L]
+    long long L;
+    long long head_cap;       // 4 * sr: the head is the first min(head_cap, end - start) trimmed samples
+    int frames;               // 1 + L / kTrimHop
+    float* rms;               // [2][frames]
+    float* head;              // [min(head_cap, L)]
+    PrepState* st;
+};
+struct LagCand { float v; int k; };                   // a correlation and its index in the 'full' sequence
+constexpr int kLagParts = 64;                         // workgroups (and partial candidates) per pair of the argmax's first launch
+struct PrepPair {
+    const PrepState *sa, *sb;  // the two waves' states
+    const float *a, *b;        // their heads
+    float* full;               // [na + nb - 1] at most: np.correlate(a, b, 'full')
+    LagCand* part;             // [kLagParts]
+    PairWindow* out;           // the pair's window: the five measured fields
+    int solo;                  // the pair has no second wave (trim only): sb = sa, no correlation, lag 0
+};
+// The forms of xcorr_full_kernel<FORM> (prepare.hip), one launch each over the call's table unless noted:
+struct PrepRms { const PrepWave* tab; };              // rms[c][f] of every trim frame: one wave per (frame, channel), the squares summed in double
+struct PrepTrim { const PrepWave* tab; };             // ref, first and last signal frame -> start, end; the head's sum in double -> its mean
+struct PrepHeads { const PrepWave* tab; };            // head[j] = (w[0][start + j] + w[1][start + j]) - mean
+struct XcorrTile { PrepPair p; };                     // ONE pair per launch: a block of kLagTile lags per workgroup, both heads through LDS
+struct LagPart { const PrepPair* tab; };              // first maximum of `full`, per workgroup
+struct LagPick { const PrepPair* tab; };              // ... of the partials; writes the pair's window
+constexpr int kLagR = 8, kLagTile = 64 * kLagR, kLagChunk = 1024;
+void launch_prep_trim(const PrepWave* tab_dev, int n_waves, int max_frames, long long max_head, hipStream_t st);
+void launch_xcorr_tile(const PrepPair& p, long long nf_max, hipStream_t st);
+void launch_lag_argmax(const PrepPair* tab_dev, int n_pairs, hipStream_t st);
 // The conv families behind launch_conv.  A *_pick says whether its family takes the launch and fills the plan (kernel, MT, TH, TW);
 // conv_plan (conv_mfma.hip) alone calls them, in its order.  A *_launch_conv takes tiled args (conv_fill_tiling) and the plan.
 bool thin16_pick(const ConvArgs& a, const ConvShape& s, ConvPlan* p);  // conv_thin.hip: <= 16 couts on v_mfma_f32_16x16x4_f32

@@ -290,6 +290,11 @@ public:
     void pitch_run(int n, const float* const* waves, const float* const* inst, bool on_dev, int channels, const long long* L, int shift_n_fft,
                    int shift_hop, double rate, double ratio, long long max_bytes, float* const* out, float* const* X_out, float* const* y_out,
                    int layout, bool out_on_dev);
+    // ---- plain training pairs (vr_pair_rows_many, csrc/prepare.hip) ----
+    // rows [T][2][bins] of mix[i][:, a_off : a_off + n] and inst[i][:, b_off : b_off + n] at the handle's n_fft / hop (hop == n_fft / 2 only:
+    // -9 elsewhere), T = 1 + n / hop, and peaks[i] = max(|X|.max(), |y|.max()) from the rows just written
+    void pair_rows_run(int n, const float* const* mix, const float* const* inst, bool on_dev, const long long* L_mix, const long long* L_inst,
+                       const PairWindow* w, long long max_bytes, float* const* X_out, float* const* y_out, bool out_on_dev, float* peaks);
     // ---- WAV sample bytes in, PCM16 out (vr_*_pcm*; csrc/pcm.h): the sample-format forms of the frame-tiled STFT / iSTFT ----
     bool pcm_available() const;                           // the frame-tiled kernels, whose forms these are, exist on this handle
     void check_pcm(const void* bytes, int channels, int fmt, const std::string& who) const;      // availability, format, channels, a device pointer's alignment

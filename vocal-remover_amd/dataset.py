@@ -576,15 +576,23 @@ def _song_peak(X, y):
     return np.max([np.abs(X).max(), np.abs(y).max()])
 
 
-def make_training_set(filelist, sr, hop_length, n_fft, peaks=True):
+def make_training_set(filelist, sr, hop_length, n_fft, peaks=True, pairs_per_call=None):
     """One [mixture cache path, instrumental cache path, peak magnitude of the pair] row per song (VocalRemoverTrainingSet input).
     peaks=False: every peak is None and a cached pair is not read beyond its two headers -- for the resident sets, which take the
-    peak on the device from the rows they upload (ResidentTrainingSet, ResidentSongValidationSet)."""
+    peak on the device from the rows they upload (ResidentTrainingSet, ResidentSongValidationSet).
+    pairs_per_call (None: off): the pairs that have no cache yet are trimmed, aligned, transformed and measured on the device, that many
+    per library call (SpectrogramCache.pairs): the same files and the same peaks, the peak from the call instead of a host pass."""
     from .spec_utils import SpectrogramCache
     cache = SpectrogramCache(sr, hop_length, n_fft)
     rows = []
-    for mix_path, inst_path in filelist:
-        if peaks:
+    filelist = list(filelist)
+    made = {}
+    if pairs_per_call is not None:
+        made = {k: p for k, (_, _, p) in enumerate(cache.pairs(filelist, pairs_per_call)) if p is not None}
+    for k, (mix_path, inst_path) in enumerate(filelist):
+        if k in made:
+            rows.append([cache.npy_path(mix_path), cache.npy_path(inst_path), made[k] if peaks else None])
+        elif peaks:
             X, y, mix_npy, inst_npy = cache.pair(mix_path, inst_path)
             rows.append([mix_npy, inst_npy, _song_peak(X, y)])
         else:

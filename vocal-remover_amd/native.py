@@ -149,6 +149,12 @@ _SIGNATURES = {
                                           ctypes.c_int, c_i64p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                           ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                           ctypes.c_int]),
+    'vr_pair_window_plan': (ctypes.c_int, [ctypes.c_int64] * 5 + [ctypes.c_void_p]),
+    'vr_align_pair_many': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                          ctypes.c_int, c_i64p, c_i64p, ctypes.c_int, ctypes.c_void_p]),
+    'vr_pair_rows_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                         ctypes.c_int, c_i64p, c_i64p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p),
+                                         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     'vr_resampler_open': (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_void_p)]),
     'vr_resampler_push': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
     'vr_resampler_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
@@ -204,6 +210,11 @@ class VRArgumentError(VRError, ValueError):
     raises for it, and a VRError like every other refusal of the library."""
 
 
+class VRUnsupported(VRError):
+    """VR_ERR_UNSUPPORTED: the handle has no kernel for the request (vr_pair_rows_many at hop_length != n_fft / 2); the caller's other
+    route applies."""
+
+
 def check(rc, arg_error=ValueError):
     """Map vr_status to the exception the reference would raise at the same spot.  arg_error: what VR_ERR_BAD_ARGUMENT raises (the
     sample-format entry points pass VRArgumentError)."""
@@ -220,6 +231,8 @@ def check(rc, arg_error=ValueError):
         raise arg_error(msg)
     if rc == -8:
         raise VRError('libvr_mi355 RCCL error: %s' % msg)
+    if rc == -9:
+        raise VRUnsupported(msg)
     raise VRError('libvr_mi355 error %d: %s' % (rc, msg))
 
 
@@ -275,6 +288,21 @@ def pitch_plan(L, n_fft, hop, rate, ratio):
     check(lib().vr_pitch_plan(int(L), int(n_fft), int(hop), float(rate), float(ratio), ctypes.byref(T), ctypes.byref(Ts), ctypes.byref(ns),
                               ctypes.byref(nr)))
     return int(T.value), int(Ts.value), int(ns.value), int(nr.value)
+
+
+class PairWindow(ctypes.Structure):         # include/vr_mi355.h: vr_pair_window
+    _fields_ = [(k, ctypes.c_int64) for k in ('a_start', 'a_end', 'b_start', 'b_end', 'lag', 'a_off', 'b_off', 'n')]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def pair_window_plan(a_start, a_end, b_start, b_end, lag):
+    """vr_pair_window_plan (host only): the common window of a pair from its two trimmed ranges and the lag -> PairWindow; ValueError
+    when it is empty."""
+    w = PairWindow()
+    check(lib().vr_pair_window_plan(int(a_start), int(a_end), int(b_start), int(b_end), int(lag), ctypes.byref(w)))
+    return w
 
 
 class Crop(ctypes.Structure):               # include/vr_mi355.h: vr_crop

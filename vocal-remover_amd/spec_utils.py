@@ -262,6 +262,43 @@ def align_wave_head_and_tail(a, b, sr):
     return a[:, :n], b[:, :n]
 
 
+def align_pair_many(mixes, insts, sr):
+    """align_wave_head_and_tail's decisions for many pairs in ONE library call (vr_align_pair_many): trim, the two heads and the lag search
+    run on the device.  mixes[i], insts[i] [2, L] (the two lengths of a pair may differ), numpy or cuda -> [native.PairWindow]: the pair
+    is mixes[i][:, a_off:a_off + n] and insts[i][:, b_off:b_off + n]."""
+    return audio.align_windows(mixes, insts, sr)
+
+
+def prepare_pair_many(mixes, insts, sr, hop_length, n_fft, max_bytes=None):
+    """What SpectrogramCache.pair does to decoded waves, many pairs per call, on the device: align_pair_many, then the STFT rows of the two
+    windows and the pair's peak (vr_pair_rows_many).  -> (X rows, y rows, peaks, windows): rows [T, 2, bins] complex64, the training
+    cache's layout, the values wave_to_spectrogram's of the sliced waves; peaks np.float32 = max(|X|.max(), |y|.max()).  numpy in, numpy
+    out; cuda tensors in, cuda tensors out.  hop_length != n_fft / 2: native.VRUnsupported (the host route applies); a workspace above
+    max_bytes: MemoryError."""
+    ct = native.ctypes
+    mixes, insts = list(mixes), list(insts)
+    if len(mixes) != len(insts):
+        raise ValueError('prepare_pair_many: %d mixtures but %d instrumentals' % (len(mixes), len(insts)))
+    N = len(mixes)
+    if not N:
+        return [], [], [], []
+    ins, on_dev = audio._stereo_waves(mixes + insts, 'prepare_pair_many')
+    xs, ys = ins[:N], ins[N:]
+    windows = audio.align_windows([x for x, _ in xs], [y for y, _ in ys], sr)
+    bins = n_fft // 2 + 1
+    shapes = [(1 + int(w.n) // hop_length, 2, bins) for w in windows]
+    Xo = [audio._like_out(sh, x, on_dev, np.complex64) for sh, (x, _) in zip(shapes, xs)]
+    yo = [audio._like_out(sh, x, on_dev, np.complex64) for sh, (x, _) in zip(shapes, xs)]
+    peaks = (ct.c_float * N)()
+    rc = native.lib().vr_pair_rows_many(
+        _signal_handle(n_fft, hop_length).h, N, (ct.c_void_p * N)(*[p for _, p in xs]), (ct.c_void_p * N)(*[p for _, p in ys]),
+        1 if on_dev else 0, (ct.c_int64 * N)(*[int(x.shape[1]) for x, _ in xs]), (ct.c_int64 * N)(*[int(y.shape[1]) for y, _ in ys]),
+        (native.PairWindow * N)(*windows), int(max_bytes or 0), (ct.c_void_p * N)(*[p for _, p in Xo]), (ct.c_void_p * N)(*[p for _, p in yo]),
+        1 if on_dev else 0, peaks)
+    audio._check_workspace(rc)
+    return [a for a, _ in Xo], [a for a, _ in yo], [np.float32(p) for p in peaks], windows
+
+
 class SpectrogramCache(object):
     """The reference's spectrogram cache (lib/spec_utils.py:122-154) as an on-disk contract: the STFT of <dir>/<song>.<ext>
     lives in <dir>/sr{sr}_hl{hop}_nf{n_fft}/<song>.npy as [T, 2, bins] complex64 (time-major, so that the training set can
@@ -288,6 +325,32 @@ class SpectrogramCache(object):
                 np.save(p, spec.transpose(2, 0, 1))
         assert specs[0].shape == specs[1].shape
         return specs[0], specs[1], paths[0], paths[1]
+
+    def pairs(self, filelist, pairs_per_call):
+        """The cache of every (mixture path, instrumental path) of filelist -> [(mixture .npy, instrumental .npy, peak or None)].  A pair
+        whose two files exist is left as it is (peak None: the caller reads what it needs, as after `pair` / `pair_paths`).  The others are
+        decoded by audio.load as in `pair` and go through prepare_pair_many in groups of pairs_per_call: the rows [T, 2, bins] are saved
+        as the device wrote them -- the bytes `pair` writes -- and the peak is the call's.  Where the device route does not apply
+        (hop_length != n_fft / 2) the group takes `pair`'s."""
+        filelist = [tuple(f) for f in filelist]
+        paths = [(self.npy_path(m), self.npy_path(i)) for m, i in filelist]
+        out = [(xp, yp, None) for xp, yp in paths]
+        todo = [k for k, p in enumerate(paths) if not all(os.path.exists(q) for q in p)]
+        step = max(int(pairs_per_call), 1)
+        for g in range(0, len(todo), step):
+            group = todo[g:g + step]
+            waves = [[audio.load(p, sr=self.sr, mono=False, dtype=np.float32, res_type='kaiser_fast')[0] for p in filelist[k]] for k in group]
+            try:
+                Xs, ys, peaks, _ = prepare_pair_many([w[0] for w in waves], [w[1] for w in waves], self.sr, self.hop_length, self.n_fft)
+            except native.VRUnsupported:
+                for k in group:
+                    self.pair(*filelist[k])
+                continue
+            for k, X, y, peak in zip(group, Xs, ys, peaks):
+                np.save(paths[k][0], X)
+                np.save(paths[k][1], y)
+                out[k] = (paths[k][0], paths[k][1], peak)
+        return out
 
     def pair_paths(self, mix_path, inst_path):
         """-> the two .npy paths of `pair`, without its arrays: on a cache hit only the two headers are read (the shapes must agree, as
