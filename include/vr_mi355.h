@@ -423,6 +423,24 @@ int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t 
  * leaves them so. */
 int vr_stream_push_many(int n_streams, const vr_stream* s, const float* const* wave, int on_device, const int64_t* n, const int* flush,
                         int batchsize, float* const* y, float* const* v, int out_on_device, const int64_t* capacity, int64_t* n_out);
+/* The file's sample bytes into a stream: vr_stream_push / vr_stream_push_many with `bytes` = `frames` interleaved frames of `channels`
+ * (1 or 2; one channel is up-mixed) samples in format `fmt` (vr_pcm_format) in place of the planar float wave.  The stream STFT reads the
+ * bytes (a form of the frame-tiled kernel, csrc/pcm.h's arithmetic); no decode pass, no extra launch, and the upload carries the file's
+ * sample size.  CONTRACT: each call returns exactly what the float entry point returns for vr_pcm_convert_host of the same bytes, mono
+ * up-mixed -- the samples, n_out and the state left behind, bit for bit, since the first kernel sees the same floats (the input tail a
+ * step keeps is stored decoded, as float32: vr_stream_info's state_bytes is unchanged).  A stream may mix float and PCM pushes freely;
+ * vr_stream_flush serves both.  Every kind of stream is taken by vr_stream_push_pcm: plain, VR_STREAM_TTA, VR_STREAM_MEASURE, the running
+ * normaliser, VR_STREAM_PCM16_OUT, VR_CREATE_COMPLEX handles.  vr_stream_push_many_pcm: format and channel count per stream; it refuses
+ * what vr_stream_push_many refuses.  A push worked through in several steps advances through the bytes frame by frame, so a step of a
+ * VR_PCM_S24 block may begin at any byte.  Host bytes are staged as bytes in the handle's staging arena, rounded up to whole 32-bit words.
+ * VR_ERR_BAD_ARGUMENT, before the device or any stream is touched (vr_stream_push_many_pcm: vr_last_error() starts "stream <k>: "): an
+ * unknown fmt, channels not 1 or 2, frames < 0, bytes NULL with frames > 0, a DEVICE buffer of VR_PCM_S16 / S32 / F32 off its natural
+ * alignment (VR_PCM_S24 may start at any byte; host buffers may lie anywhere), and everything the float forms refuse. */
+int vr_stream_push_pcm(vr_stream s, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* y, float* v,
+                       int out_on_device, int64_t capacity, int64_t* n_out);
+int vr_stream_push_many_pcm(int n_streams, const vr_stream* s, const void* const* bytes, int on_device, const int64_t* frames,
+                            const int* channels, const int* fmt, const int* flush, int batchsize, float* const* y, float* const* v,
+                            int out_on_device, const int64_t* capacity, int64_t* n_out);
 int vr_stream_coef(vr_stream s, double* coef_re_im /*[2]*/);
 int vr_stream_info(vr_stream s, int64_t* lookahead_samples, int64_t* block_samples, int64_t* state_bytes);
 int vr_stream_close(vr_stream s);
@@ -627,6 +645,24 @@ int vr_resampler_push(vr_resampler r, const float* x, int x_on_device, int64_t n
 int vr_resampler_flush(vr_resampler r, float* y, int y_on_device, int64_t capacity, int64_t* n_out);
 int vr_resampler_push_many(int n, const vr_resampler* r, const float* const* x, int on_device, const int64_t* n_in, const int* flush,
                            float* const* y, int y_on_device, const int64_t* capacity, int64_t* n_out);
+/* The file's sample bytes into a session: vr_resampler_push / vr_resampler_push_many with `bytes` = `frames` interleaved frames in format
+ * `fmt` (vr_pcm_format) in place of the planar float block.  A block's frames hold the session's channel count, or 1: every session
+ * channel then reads the one sample (the up-mix of a mono file).  The resampling kernel reads the float history of the session's window
+ * and, behind it, the bytes; the samples the session carries on reach its other window buffer decoded -- the float part by a device
+ * copy, the rest stored by the launch itself, which therefore also happens for a push that returns nothing.  Pass-through sessions
+ * (sr_in == sr_out) take bytes too and return the decoded samples on the usual schedule.  CONTRACT: each call returns exactly what the
+ * float entry point returns for vr_pcm_convert_host of the same bytes (mono repeated per channel) -- samples, n_out and the state left
+ * behind, bit for bit; a session may mix float and PCM pushes freely, vr_resampler_flush serves both, vr_resampler_info reports the
+ * same state_bytes.  One launch still serves all sessions of vr_resampler_push_many_pcm: rate pair, format and channel count per entry.
+ * Host bytes are staged as bytes in a per-session buffer, rounded up to whole 32-bit words.
+ * VR_ERR_BAD_ARGUMENT, before the device or any session is touched (many: vr_last_error() starts "resampler <k>: "): an unknown fmt,
+ * channels neither 1 nor the session's, frames < 0, bytes NULL with frames > 0, a DEVICE buffer of VR_PCM_S16 / S32 / F32 off its
+ * natural alignment, and everything the float forms refuse. */
+int vr_resampler_push_pcm(vr_resampler r, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* y, int y_on_device,
+                          int64_t capacity, int64_t* n_out);
+int vr_resampler_push_many_pcm(int n, const vr_resampler* r, const void* const* bytes, int on_device, const int64_t* frames,
+                               const int* channels, const int* fmt, const int* flush, float* const* y, int y_on_device,
+                               const int64_t* capacity, int64_t* n_out);
 int vr_resampler_info(vr_resampler r, int64_t* lookahead_samples, int64_t* state_bytes);
 int vr_resampler_close(vr_resampler r);
 int vr_resampler_plan(int sr_in, int sr_out, int64_t samples_in, int flushed, int64_t* samples_out);

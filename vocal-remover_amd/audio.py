@@ -519,6 +519,13 @@ class StreamResampler(object):
     def flush(self):
         return self._call(None, True)
 
+    def push_pcm(self, raw):
+        """push() of the decoded block without the host decode (vr_resampler_push_pcm): raw = RawPcm whose frames hold the session's
+        channel count or 1 (every session channel then reads the one sample); the kernel reads the bytes.  Returns exactly what
+        push(decoded) returns and leaves the same state; push and push_pcm may be mixed.  numpy bytes give a numpy array, a cuda uint8
+        tensor a cuda tensor.  Refusals (format, channel count, a misaligned cuda buffer) are native.VRArgumentError."""
+        return resample_push_many_pcm([self], [raw], one=True)[0]
+
     def close(self):
         if getattr(self, '_r', None) is not None and self._r.value:
             native.lib().vr_resampler_close(self._r)
@@ -586,6 +593,58 @@ def resample_push_many(resamplers, blocks, flush=False):
             r._dev_out = on_dev
             if x is not None:
                 r._flat = flat
+        y = y[:, :int(g)]
+        res.append(y[0] if getattr(r, '_flat', False) else y)
+    return res
+
+
+def resample_push_many_pcm(resamplers, raws, flush=False, one=False):
+    """resample_push_many with sample bytes in (vr_resampler_push_many_pcm; one launch for all sessions): resamplers[k] receives
+    raws[k] -- a RawPcm whose frames hold the session's channel count or 1, or None for nothing -- and, where flush says so, its input
+    ends there.  Formats and channel counts may differ per session.  Returns what resample_push_many returns for the decoded blocks, bit
+    for bit.  Either every raw.bytes is a numpy array (numpy out) or every one is a cuda uint8 tensor (cuda out)."""
+    from .spec_utils import _pcm_bytes
+    ct = native.ctypes
+    rs, raws = list(resamplers), list(raws)
+    N = len(rs)
+    if not N:
+        raise ValueError('resample_push_many_pcm needs at least one resampler')
+    if len(raws) != N:
+        raise ValueError('resample_push_many_pcm: %d resamplers but %d blocks' % (N, len(raws)))
+    fl = [bool(flush)] * N if isinstance(flush, (bool, np.bool_)) else [bool(f) for f in flush]
+    if len(fl) != N:
+        raise ValueError('resample_push_many_pcm: %d resamplers but %d flush flags' % (N, len(fl)))
+    prepared = [None if raw is None else _pcm_bytes(raw) for raw in raws]
+    given = [p[2] for p in prepared if p is not None]
+    if any(given) and not all(given):
+        raise ValueError('resample_push_many_pcm: either every block is a cuda tensor or none is')
+    on_dev = all(given) if given else bool(rs[0]._dev_out)
+    for k, (r, p) in enumerate(zip(rs, prepared)):
+        if on_dev and p is not None and p[0].device.index != r.device:
+            raise ValueError('resampler %d: block is on %s, the resampler on cuda:%d' % (k, p[0].device, r.device))
+    lens = [0 if raw is None else int(raw.frames) for raw in raws]
+    chans = [r.channels if raw is None else int(raw.channels) for r, raw in zip(rs, raws)]
+    fmts = [native.VR_PCM_S16 if raw is None else int(raw.fmt) for raw in raws]
+    handles = [r._handle().value for r in rs]
+    caps = [max(r._need(n, f), 1) for r, n, f in zip(rs, lens, fl)]
+    outs = [r._out(c, on_dev) for r, c in zip(rs, caps)]
+    got = (ct.c_int64 * N)()
+    dev = 1 if on_dev else 0
+    if one:
+        native.check(native.lib().vr_resampler_push_pcm(handles[0], prepared[0][1] if lens[0] else None, dev, lens[0], chans[0], fmts[0],
+                                                        outs[0][1], dev, caps[0], got), native.VRArgumentError)
+    else:
+        native.check(native.lib().vr_resampler_push_many_pcm(
+            N, (ct.c_void_p * N)(*handles), (ct.c_void_p * N)(*[p[1] if p is not None and n else None for p, n in zip(prepared, lens)]), dev,
+            (ct.c_int64 * N)(*lens), (ct.c_int * N)(*chans), (ct.c_int * N)(*fmts), (ct.c_int * N)(*[1 if f else 0 for f in fl]),
+            (ct.c_void_p * N)(*[p for _, p in outs]), dev, (ct.c_int64 * N)(*caps), got), native.VRArgumentError)
+    res = []
+    for r, raw, n, f, (y, _), g in zip(rs, raws, lens, fl, outs, got):
+        if n or f:
+            r._samples += n
+            r._dev_out = on_dev
+            if raw is not None:
+                r._flat = False
         y = y[:, :int(g)]
         res.append(y[0] if getattr(r, '_flat', False) else y)
     return res

@@ -21,7 +21,8 @@ Resampler* resampler_open(int device, int channels, int sr_in, int sr_out);
 void resampler_close(Resampler* r);
 void resampler_info(const Resampler* r, long long* lookahead, long long* state_bytes);
 void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool x_on_dev, const long long* n, const int* flush,
-                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many);
+                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many,
+                         const void* const* bytes = nullptr, const int* pcm_channels = nullptr, const int* pcm_fmt = nullptr);
 }  // namespace vr
 
 struct vr_model {
@@ -467,6 +468,53 @@ int vr_stream_push_many(int n_streams, const vr_stream* s, const float* const* w
         }
         s[0]->h->m.stream_push_many(n_streams, st.data(), wave, on_device != 0, len.data(), flush, batchsize, y, v, out_on_device != 0,
                                     capacity ? cap.data() : nullptr, got.data());
+        if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = got[k];
+    });
+}
+
+// The argument checks of the *_push_pcm entry points that need neither a device nor the stream or session: format, channel count (streams:
+// 1 or 2; sessions: positive here, the session's or 1 once it is known), frame count, a null buffer.  `who` in front of the message.
+static void check_pcm_args(const std::string& who, const void* bytes, int64_t frames, int channels, int fmt, bool stream) {
+    VR_CHECK(fmt == VR_PCM_S16 || fmt == VR_PCM_S24 || fmt == VR_PCM_S32 || fmt == VR_PCM_F32, VR_ERR_BAD_ARGUMENT,
+             who + "unknown sample format " + std::to_string(fmt) + " (VR_PCM_S16 / S24 / S32 / F32)");
+    if (stream) VR_CHECK(channels == 1 || channels == 2, VR_ERR_BAD_ARGUMENT, who + "1 or 2 channels, not " + std::to_string(channels));
+    else VR_CHECK(channels >= 1, VR_ERR_BAD_ARGUMENT, who + "frames of " + std::to_string(channels) + " channels: a block holds the session's or 1");
+    VR_CHECK(frames >= 0, VR_ERR_BAD_ARGUMENT, who + "negative frame count");
+    VR_CHECK(frames == 0 || bytes, VR_ERR_BAD_ARGUMENT, who + "null input");
+}
+
+int vr_stream_push_pcm(vr_stream s, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* y, float* v,
+                       int out_on_device, int64_t capacity, int64_t* n_out) {
+    const int rc = guard([&] { check_pcm_args("", bytes, frames, channels, fmt, true); });
+    if (rc != VR_OK) return rc;
+    NEED_STREAM(s);
+    return guard([&] {
+        long long got = 0;
+        s->h->m.stream_push(*s->st, static_cast<const float*>(bytes), on_device != 0, frames, false, y, v, out_on_device != 0, capacity, &got,
+                            channels, fmt);
+        if (n_out) *n_out = got;
+    });
+}
+
+int vr_stream_push_many_pcm(int n_streams, const vr_stream* s, const void* const* bytes, int on_device, const int64_t* frames,
+                            const int* channels, const int* fmt, const int* flush, int batchsize, float* const* y, float* const* v,
+                            int out_on_device, const int64_t* capacity, int64_t* n_out) {
+    if (n_streams <= 0) { g_err = "n_streams must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!s || !frames || !channels || !fmt) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        for (int k = 0; k < n_streams; ++k)
+            check_pcm_args("stream " + std::to_string(k) + ": ", bytes ? bytes[k] : nullptr, frames[k], channels[k], fmt[k], true);
+        std::vector<vr::StreamState*> st((size_t)n_streams);
+        std::vector<long long> len(frames, frames + n_streams), cap, got((size_t)n_streams, 0);
+        if (capacity) cap.assign(capacity, capacity + n_streams);
+        for (int k = 0; k < n_streams; ++k) {
+            const std::string who = "stream " + std::to_string(k) + ": ";
+            VR_CHECK(s[k] && s[k]->st, VR_ERR_BAD_ARGUMENT, who + "null stream (closed?)");
+            VR_CHECK(s[k]->h == s[0]->h, VR_ERR_BAD_ARGUMENT, who + "belongs to another handle than stream 0: the streams of one call share a handle");
+            st[k] = s[k]->st;
+        }
+        s[0]->h->m.stream_push_many(n_streams, st.data(), reinterpret_cast<const float* const*>(bytes), on_device != 0, len.data(), flush, batchsize,
+                                    y, v, out_on_device != 0, capacity ? cap.data() : nullptr, got.data(), channels, fmt);
         if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = got[k];
     });
 }
@@ -962,6 +1010,36 @@ int vr_resampler_push_many(int n, const vr_resampler* r, const float* const* x, 
         for (int k = 0; k < n; ++k) rs[k] = r[k] ? r[k]->r : nullptr;
         vr::resampler_push_many(n, rs.data(), x, on_device != 0, len.data(), flush, y, y_on_device != 0, capacity ? cap.data() : nullptr,
                                 got.data(), true);
+        if (n_out) for (int k = 0; k < n; ++k) n_out[k] = got[k];
+    });
+}
+
+int vr_resampler_push_pcm(vr_resampler r, const void* bytes, int on_device, int64_t frames, int channels, int fmt, float* y, int y_on_device,
+                          int64_t capacity, int64_t* n_out) {
+    const int rc = guard([&] { check_pcm_args("resampler: ", bytes, frames, channels, fmt, false); });
+    if (rc != VR_OK) return rc;
+    NEED_RESAMPLER(r);
+    return guard([&] {
+        long long len = frames, cap = capacity, got = 0;
+        const int no_flush = 0;
+        vr::resampler_push_many(1, &r->r, nullptr, on_device != 0, &len, &no_flush, &y, y_on_device != 0, &cap, &got, false, &bytes, &channels, &fmt);
+        if (n_out) *n_out = got;
+    });
+}
+
+int vr_resampler_push_many_pcm(int n, const vr_resampler* r, const void* const* bytes, int on_device, const int64_t* frames, const int* channels,
+                               const int* fmt, const int* flush, float* const* y, int y_on_device, const int64_t* capacity, int64_t* n_out) {
+    if (n <= 0) { g_err = "n must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (!r || !frames || !channels || !fmt) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        for (int k = 0; k < n; ++k)
+            check_pcm_args("resampler " + std::to_string(k) + ": ", bytes ? bytes[k] : nullptr, frames[k], channels[k], fmt[k], false);
+        std::vector<vr::Resampler*> rs((size_t)n);
+        std::vector<long long> len(frames, frames + n), cap, got((size_t)n, 0);
+        if (capacity) cap.assign(capacity, capacity + n);
+        for (int k = 0; k < n; ++k) rs[k] = r[k] ? r[k]->r : nullptr;
+        vr::resampler_push_many(n, rs.data(), nullptr, on_device != 0, len.data(), flush, y, y_on_device != 0, capacity ? cap.data() : nullptr,
+                                got.data(), true, bytes, channels, fmt);
         if (n_out) for (int k = 0; k < n; ++k) n_out[k] = got[k];
     });
 }

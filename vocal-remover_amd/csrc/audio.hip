@@ -20,8 +20,11 @@
 #include <vector>
 
 #include "kernels.h"
+#include "pcm.h"
 
 namespace vr {
+
+template <class A> __device__ __forceinline__ A resample_first(A a) { return a; }
 
 // One session's share of a streamed launch (resample_kernel<true>, blockIdx.z selects the entry).  Every position is a global one: input
 // sample g of the session lies at x[c * x_pitch + (g - g0)], output sample t0 + j goes to y[c * y_pitch + j].
@@ -42,9 +45,30 @@ struct ResampleSeg {
     int nwin, precision;
 };
 
+// The PCM form's entry beside a ResampleSeg (resample_kernel<true, const ResamplePcm*>): the session's window is the float
+// history x[0, blk_w) followed by the push's block as interleaved sample bytes, and the launch itself moves the decoded part of the carry on.
+struct ResamplePcm {
+    const uint8_t* bytes;    // the block: frames of `channels` samples (1: every session channel reads the one sample) in format `fmt`
+    long long blk_w;         // window index of the block's first frame (= the float history held)
+    float* carry;            // where window samples [carry_w, carry_w + carry_n) go, channel pitch x_pitch: the other window buffer
+    long long carry_w, carry_n;
+    int channels, fmt;
+    int same;                // pass-through session: output sample t IS input sample t
+};
+// a channel's window of the PCM form, indexed like the float window
+struct ResamplePcmWin {
+    const float* x;
+    const uint8_t* bytes;
+    long long blk_w;
+    int channels, fmt, ch;
+    __device__ __forceinline__ float operator[](long long i) const { return i < blk_w ? x[i] : pcm_decode(bytes, fmt, channels, i - blk_w, ch); }
+};
+
 // One output sample: the sum over both filter wings (resampy.interpn._resample_loop), fp32 accumulator like the float32 output array.
-// xc is the channel's window, whose first sample has the global index g0; n_in is the right-hand clamp.
-__device__ __forceinline__ float resample_sample(const float* __restrict__ xc, long long g0, long long n_in, long long t,
+// xc is the channel's window (a float pointer, or the PCM form's ResamplePcmWin), whose first sample has the global index g0; n_in is the
+// right-hand clamp.
+template <class WIN>
+__device__ __forceinline__ float resample_sample(WIN xc, long long g0, long long n_in, long long t,
                                                  const double* __restrict__ win, const double* __restrict__ delta, int nwin, int precision,
                                                  double sample_ratio) {
     const double scale = sample_ratio < 1.0 ? sample_ratio : 1.0;
@@ -83,12 +107,30 @@ __device__ __forceinline__ float resample_sample(const float* __restrict__ xc, l
 // resample_kernel<false> is the offline kernel of vr_resample, argument for argument.  resample_kernel<true> takes a table of ResampleSeg
 // in place of the first pointer (the other arguments are unused) and computes the same taps from global positions: output sample t
 // depends on t alone, so a sample whose right wing lies inside the samples received is already the offline call's sample.
-template <bool kStream>
+// PCM (at most one type, a trailing pack so that the two forms above keep their signatures and names): const ResamplePcm* (kStream only) = one
+// entry per session beside the table.  Thread j < carry_n first stores window sample carry_w + j, decoded, into the other window buffer
+// (the part of the carry that lies in the block; the float part is a device copy), then the output sample as above with the window read
+// through ResamplePcmWin.  The grid covers max(count, carry_n), so the launch also happens for a push that returns no sample.
+template <bool kStream, class... PCM>
 __global__ void resample_kernel(std::conditional_t<kStream, const ResampleSeg*, const float*> __restrict__ x, long long n_in,
                                 float* __restrict__ y, long long n_out, const double* __restrict__ win, const double* __restrict__ delta,
-                                int nwin, int precision, double sample_ratio) {
+                                int nwin, int precision, double sample_ratio, PCM... pcm) {
+    static_assert(sizeof...(PCM) == 0 || (sizeof...(PCM) == 1 && kStream), "one PCM table at most, for the streamed form");
     long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int c = blockIdx.y;
+    if constexpr (sizeof...(PCM) == 1) {
+        const ResampleSeg& s = x[blockIdx.z];
+        const ResamplePcm& q = resample_first(pcm...)[blockIdx.z];
+        const ResamplePcmWin w{s.x + (long long)c * s.x_pitch, q.bytes, q.blk_w, q.channels, q.fmt, c < q.channels ? c : q.channels - 1};
+        if (t < q.carry_n) q.carry[(long long)c * s.x_pitch + t] = w[q.carry_w + t];
+        if (t >= s.count) return;
+        float* yo = s.y + (long long)c * s.y_pitch + t;
+        t += s.t0;
+        if (t >= s.t_core) *yo = 0.f;
+        else if (q.same) *yo = w[t - s.g0];
+        else *yo = resample_sample(w, s.g0, s.n_in, t, s.win, s.delta, s.nwin, s.precision, s.ratio);
+        return;
+    }
     const float* xc;
     float* yo;
     long long g0 = 0;
@@ -301,10 +343,15 @@ struct Resampler {
     long long out_cap = 0;
     ResampleSeg *d_tab = nullptr, *h_tab = nullptr;
     int tab_cap = 0;
+    uint8_t* d_pcm = nullptr;                    // (PCM pushes from the host) the block's bytes, staged as bytes
+    size_t pcm_cap = 0;
+    ResamplePcm *d_ptab = nullptr, *h_ptab = nullptr;
+    int ptab_cap = 0;
     long long history_cap() const { return 2LL * g.K + 2; }
     ~Resampler() {
-        hipFree(d_win); hipFree(d_delta); hipFree(buf[0]); hipFree(buf[1]); hipFree(d_out); hipFree(d_tab);
+        hipFree(d_win); hipFree(d_delta); hipFree(buf[0]); hipFree(buf[1]); hipFree(d_out); hipFree(d_tab); hipFree(d_pcm); hipFree(d_ptab);
         if (h_tab) hipHostFree(h_tab);
+        if (h_ptab) hipHostFree(h_ptab);
         if (st) hipStreamDestroy(st);
     }
 };
@@ -354,9 +401,16 @@ static void copy_rows(void* dst, long long dpitch, const void* src, long long sp
 // Session k receives n[k] >= 0 samples and, where flush[k], its input ends.  Everything is checked first; then the copies of all sessions,
 // ONE launch with one table entry per session, the copies out and the carry run on session 0's stream, and the call waits for it (every
 // session's memory is idle between calls, so no other stream has to be waited for).
+// pcm_fmt given (vr_resampler_push*_pcm; x is then unused): session k's block is bytes[k], n[k] interleaved frames of pcm_channels[k] samples
+// in format pcm_fmt[k].  The window keeps only the float history: host bytes are staged as bytes in the session's own buffer, the PCM form of
+// the kernel reads history and block, returns a pass-through session's samples too, and stores the decoded part of the carry itself -- so
+// the launch also happens for a push that returns nothing.  What is left behind is the float state a float push leaves.
 void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool x_on_dev, const long long* n, const int* flush,
-                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many) {
+                         float* const* y, bool y_on_dev, const long long* capacity, long long* n_out, bool many, const void* const* bytes,
+                         const int* pcm_channels, const int* pcm_fmt) {
     VR_CHECK(N <= 65535, -2, "resampler: at most 65535 sessions in one call (one grid plane each)");
+    const bool pcm = pcm_fmt != nullptr;
+    VR_CHECK(!pcm || pcm_channels, -2, "resampler: null table");
     std::vector<long long> need((size_t)N, 0), total((size_t)N, 0);
     for (int k = 0; k < N; ++k) {
         const std::string who = many ? "resampler " + std::to_string(k) + ": " : std::string("resampler: ");
@@ -368,7 +422,18 @@ void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool
         VR_CHECK(!r[k]->flushed, -2, who + (fl && n[k] == 0 ? "already flushed" : "push after flush"));
         VR_CHECK(!r[k]->broken, -2, who + "an earlier call failed half way: close the session");
         VR_CHECK(n[k] >= 0, -2, who + "negative sample count");
-        VR_CHECK(n[k] == 0 || (x && x[k]), -2, who + "null input");
+        if (pcm) {
+            VR_CHECK(pcm_fmt_ok(pcm_fmt[k]), -2, who + "unknown sample format " + std::to_string(pcm_fmt[k]) + " (VR_PCM_S16 / S24 / S32 / F32)");
+            VR_CHECK(pcm_channels[k] == 1 || pcm_channels[k] == r[k]->channels, -2,
+                     who + "frames of " + std::to_string(pcm_channels[k]) + " channels: a block holds the session's " + std::to_string(r[k]->channels) +
+                         " or 1 (every session channel then reads the one sample)");
+            VR_CHECK(n[k] == 0 || (bytes && bytes[k]), -2, who + "null input");
+            if (x_on_dev && n[k] > 0 && pcm_fmt[k] != VR_PCM_S24)
+                VR_CHECK(reinterpret_cast<uintptr_t>(bytes[k]) % (uintptr_t)pcm_sample_bytes(pcm_fmt[k]) == 0, -2,
+                         who + "the sample buffer is not aligned to its " + std::to_string(pcm_sample_bytes(pcm_fmt[k])) +
+                             "-byte samples (only VR_PCM_S24 may start at any byte)");
+        } else
+            VR_CHECK(n[k] == 0 || (x && x[k]), -2, who + "null input");
         total[k] = r[k]->n_recv + n[k];
         VR_CHECK(!fl || total[k] > 0, -2, who + "flush with no sample received");
         need[k] = resample_ready(r[k]->g, total[k], fl) - r[k]->n_emit;
@@ -389,11 +454,65 @@ void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool
         VR_HIP(hipHostMalloc(&lead->h_tab, (size_t)N * sizeof(ResampleSeg)));
         lead->tab_cap = N;
     }
+    if (pcm && lead->ptab_cap < N) {
+        hipFree(lead->d_ptab);
+        if (lead->h_ptab) hipHostFree(lead->h_ptab);
+        lead->d_ptab = nullptr; lead->h_ptab = nullptr; lead->ptab_cap = 0;
+        VR_HIP(hipMalloc(&lead->d_ptab, (size_t)N * sizeof(ResamplePcm)));
+        VR_HIP(hipHostMalloc(&lead->h_ptab, (size_t)N * sizeof(ResamplePcm)));
+        lead->ptab_cap = N;
+    }
     const hipMemcpyKind in_kind = x_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const hipMemcpyKind out_kind = y_on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     long long max_count = 0;
+    std::vector<long long> keep_at((size_t)N, 0);       // (PCM) the first global sample the session carries on
     for (int k = 0; k < N; ++k) {
         Resampler& s = *r[k];
+        const bool fl = flush && flush[k];
+        const bool same = s.sr_in == s.sr_out;               // pass-through: the schedule is the filter's, the samples are the input's
+        if (pcm) {
+            ResamplePcm& q = lead->h_ptab[k];
+            q = ResamplePcm{};
+            q.bytes = n[k] ? static_cast<const uint8_t*>(bytes[k]) : nullptr;
+            if (!x_on_dev && n[k] > 0) {                    // staged as bytes; rounded so that pcm_load24's aligned word reads stay inside
+                const size_t nb = (size_t)n[k] * pcm_channels[k] * pcm_sample_bytes(pcm_fmt[k]);
+                if (s.pcm_cap < nb) {
+                    hipFree(s.d_pcm); s.d_pcm = nullptr; s.pcm_cap = 0;
+                    VR_HIP(hipMalloc(&s.d_pcm, ((nb + 3) & ~size_t(3)) + 4));
+                    s.pcm_cap = nb;
+                }
+                VR_HIP(hipMemcpyAsync(s.d_pcm, bytes[k], nb, hipMemcpyHostToDevice, st));
+                q.bytes = s.d_pcm;
+            }
+            q.blk_w = s.hist; q.channels = pcm_channels[k]; q.fmt = pcm_fmt[k]; q.same = same ? 1 : 0;
+            ResampleSeg& e = lead->h_tab[k];
+            e.x = s.buf[s.cur]; e.x_pitch = s.pitch; e.g0 = s.g0; e.n_in = total[k];
+            e.t0 = s.n_emit; e.count = need[k];
+            e.t_core = fl ? (long long)((double)total[k] * s.g.ratio) : LLONG_MAX;
+            VR_CHECK(s.n_emit <= e.t_core, -3, "resampler: the schedule ran past int(n_in * ratio)");
+            e.win = s.d_win; e.delta = s.d_delta; e.ratio = s.g.ratio; e.nwin = s.nwin; e.precision = 1 << 9;
+            if (y_on_dev) { e.y = y[k]; e.y_pitch = capacity ? capacity[k] : 0; }
+            else {
+                if (s.out_cap < need[k]) {
+                    hipFree(s.d_out); s.d_out = nullptr; s.out_cap = 0;
+                    VR_HIP(hipMalloc(&s.d_out, (size_t)C * need[k] * sizeof(float)));
+                    s.out_cap = need[k];
+                }
+                e.y = s.d_out; e.y_pitch = need[k];
+            }
+            VR_CHECK(e.count == 0 || s.g0 <= std::max(0LL, (long long)((double)e.t0 * s.g.inc) - s.g.K + 1), -3, "resampler: window lost its history");
+            if (!fl && n[k] > 0) {
+                // the carry (the rule below): its float part [keep, n_recv) is a device copy, the launch stores the decoded rest [d0, total)
+                long long keep = std::max(s.g0, std::max(0LL, (long long)((double)(s.n_emit + need[k]) * s.g.inc) - s.g.K));
+                keep = std::min(keep, total[k]);
+                VR_CHECK(total[k] - keep <= s.pitch, -3, "resampler: the carry outgrew the window");
+                keep_at[k] = keep;
+                const long long d0 = std::max(keep, s.n_recv);
+                q.carry = s.buf[1 - s.cur] + (d0 - keep); q.carry_w = d0 - s.g0; q.carry_n = total[k] - d0;
+            }
+            max_count = std::max(max_count, std::max(e.count, q.carry_n));
+            continue;
+        }
         if (s.hist + n[k] > s.pitch) {                      // a larger push than any before: both windows grow, the history moves over
             const long long pitch = s.history_cap() + n[k];
             struct Pair { float* p[2]; ~Pair() { hipFree(p[0]); hipFree(p[1]); } } nb{{nullptr, nullptr}};      // freed unless taken over
@@ -405,8 +524,6 @@ void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool
             s.cur = 0; s.pitch = pitch;
         }
         copy_rows(s.buf[s.cur] + s.hist, s.pitch, n[k] ? x[k] : nullptr, n[k], n[k], C, in_kind, st);
-        const bool fl = flush && flush[k];
-        const bool same = s.sr_in == s.sr_out;               // pass-through: the schedule is the filter's, the samples are the input's
         ResampleSeg& e = lead->h_tab[k];
         e.x = s.buf[s.cur]; e.x_pitch = s.pitch; e.g0 = s.g0; e.n_in = total[k];
         e.t0 = s.n_emit; e.count = same ? 0 : need[k];
@@ -426,7 +543,16 @@ void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool
         VR_CHECK(e.count == 0 || s.g0 <= std::max(0LL, (long long)((double)e.t0 * s.g.inc) - s.g.K + 1), -3, "resampler: window lost its history");
         max_count = std::max(max_count, e.count);
     }
-    if (max_count > 0) {
+    if (max_count > 0 && pcm) {
+        VR_HIP(hipMemcpyAsync(lead->d_tab, lead->h_tab, (size_t)N * sizeof(ResampleSeg), hipMemcpyHostToDevice, st));
+        VR_HIP(hipMemcpyAsync(lead->d_ptab, lead->h_ptab, (size_t)N * sizeof(ResamplePcm), hipMemcpyHostToDevice, st));
+        float* const unused_out = nullptr;
+        const double* const unused_tab = nullptr;
+        const ResamplePcm* ptab = lead->d_ptab;
+        VR_LAUNCH((resample_kernel<true, const ResamplePcm*>), dim3((unsigned)((max_count + 255) / 256), C, N), dim3(256), 0, st, lead->d_tab, 0LL,
+                  unused_out, 0LL, unused_tab, unused_tab, 0, 0, 0.0, ptab);
+        VR_HIP(hipGetLastError());
+    } else if (max_count > 0) {
         VR_HIP(hipMemcpyAsync(lead->d_tab, lead->h_tab, (size_t)N * sizeof(ResampleSeg), hipMemcpyHostToDevice, st));
         float* const unused_out = nullptr;
         const double* const unused_tab = nullptr;
@@ -438,6 +564,16 @@ void resampler_push_many(int N, Resampler* const* r, const float* const* x, bool
         Resampler& s = *r[k];
         const ResampleSeg& e = lead->h_tab[k];
         const long long cap = capacity ? capacity[k] : 0;
+        if (pcm) {
+            if (!y_on_dev) copy_rows(y ? y[k] : nullptr, cap, s.d_out, e.y_pitch, need[k], C, hipMemcpyDeviceToHost, st);
+            if (!(flush && flush[k]) && n[k] > 0) {
+                const long long keep = keep_at[k];
+                copy_rows(s.buf[1 - s.cur], s.pitch, s.buf[s.cur] + (keep - s.g0), s.pitch, std::min(total[k], s.n_recv) - keep, C,
+                          hipMemcpyDeviceToDevice, st);
+                s.cur = 1 - s.cur; s.g0 = keep; s.hist = total[k] - keep;
+            }
+            continue;
+        }
         if (s.sr_in == s.sr_out) copy_rows(y ? y[k] : nullptr, cap, s.buf[s.cur] + (s.n_emit - s.g0), s.pitch, need[k], C, out_kind, st);
         else if (!y_on_dev) copy_rows(y ? y[k] : nullptr, cap, s.d_out, e.y_pitch, need[k], C, hipMemcpyDeviceToHost, st);
         const bool fl = flush && flush[k];

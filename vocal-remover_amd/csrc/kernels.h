@@ -564,7 +564,10 @@ struct StreamSeg {
 };
 bool stream_tiled_available(const FFTPlan& pl, int hop);
 // seg: a device table of n_seg entries; new_frames = the largest count of new frames among them, new_samples / sum_* only size the profiler's note
-void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st);
+// pcm (device, one per entry): the blocks of this round are sample bytes, read in place of the entries' `blk` from the block's first frame on
+// (pcm_bytes: the profiler's note)
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st,
+                        const PcmIn* pcm = nullptr, double pcm_bytes = 0.0);
 // part: per-row partial maxima as launch_mag_pad leaves them (stats + 16 bytes); the new frames are reduced INTO them
 void launch_stream_stats(const StreamSeg* seg, int bins, int new_frames, unsigned long long* part, hipStream_t st);
 // crops[n] = (table entry, first frame; may be negative): as launch_crop_gather, from the entry's ring, times the entry's 1 / c

@@ -304,11 +304,13 @@ public:
     // ---- streaming separation (vr_stream_*) ----
     StreamState* stream_open(int cropsize, int batchsize, int flags, double coef_re, double coef_im);
     // n samples more (flush: none, the end of the input); y / v [2][capacity] receive *n_out final samples per channel
+    // fmt != 0 (vr_stream_push_pcm): `wave` is n interleaved frames of `channels` samples in that format, read by the stream STFT itself
     void stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
-                     long long capacity, long long* n_out);
+                     long long capacity, long long* n_out, int channels = 0, int fmt = 0);
     // vr_stream_push_many: stream k gets n[k] more samples and, flush[k], its end; the crops of all streams share device batches
     void stream_push_many(int n_streams, StreamState* const* S, const float* const* wave, bool on_dev, const long long* n, const int* flush,
-                          int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out);
+                          int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out,
+                          const int* channels = nullptr, const int* fmt = nullptr);      // fmt given (vr_stream_push_many_pcm): wave[k] is bytes
     void stream_close(StreamState* S);
     void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
 
@@ -561,11 +563,12 @@ private:
     void crop_mask_head(const Tensor& f3, int cropsize, HeadDst d);
     // `count` gathered crops, dense [count][nin][max_bin][cropsize] -> the network -> crop_mask_head
     void run_dense_crops(float* dense, int count, int cropsize, const HeadDst& d);
-    struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off; };
+    struct StreamStepIO { const float* blk; long long blk_n, blk_pitch; float *y, *v; long long out_pitch, out_off; PcmIn pcm; };
     // One stream's share of a push call.  The caller fills S .. need (stream_check gives need); the rest is where stream_run stands.
     struct StreamPart {
         StreamState* S; const float* wave; long long n; bool flush; float *y, *v; long long capacity, need;
         long long at; bool flush_done; float *stage_in, *stage_y, *stage_v; StreamStepIO o;
+        int channels, fmt;                                   // (PCM pushes) `wave` is bytes: frames of `channels` samples in format `fmt`
         std::vector<unsigned long long> st;                  // MEASURE, flush: the statistics rows on their way to S->coef
     };
     // The one executor of vr_stream_push (one part) and vr_stream_push_many: the steps of its parts in rounds, one set of launches per
@@ -576,7 +579,7 @@ private:
     struct StreamCrop { int entry, pass; long long idx; };          // crop idx of a pass of the stream at table entry `entry`
     long long stream_check(const StreamState& S, const std::string& who, const float* wave, long long n, bool flush, const float* y,
                            const float* v, bool out_on_dev, long long capacity) const;     // -> samples per channel the call returns
-    void stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev);
+    void stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev, bool pcm = false);
     StreamStepPlan stream_step_plan(StreamState& S, const StreamStepIO& io_, bool final);
     void stream_step_crops(const StreamState& S, const StreamStepPlan& sp, int entry, std::vector<StreamCrop>& list) const;
     void stream_step_commit(StreamState& S, StreamStepIO& io_, const StreamStepPlan& sp);

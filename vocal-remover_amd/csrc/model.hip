@@ -2263,7 +2263,9 @@ long long Model::stream_check(const StreamState& S, const std::string& who, cons
 // over the table, the ready crops of all streams and both passes as ONE list through run_crop_chunks in parts of `bs` (one gather, one
 // network pass and one head launch per part: the head scatters every item into its own stream's mask ring through a pointer table),
 // one masked iSTFT per stem over the table.  Per call: inputs in, outputs out, one drain.
-void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev) {
+// pcm: the parts' `wave` are sample bytes (channels, fmt per part).  They are staged as bytes, a PcmIn table rides beside the StreamSeg table
+// of every round, and the PCM form of the stream STFT reads the block through it; everything behind the STFT is the same.
+void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool out_on_dev, bool pcm) {
     const int np = (int)parts.size();
     const int cropsize = parts[0].S->cropsize, roi = parts[0].S->roi, bins = output_bin, E = is_complex ? 2 : 1;
     size_t list_cap = 0;
@@ -2274,14 +2276,19 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
     // ---- the staging arena: carved twice, first dry for its size
     const size_t crop_f = (size_t)nin * max_bin * cropsize;
     StreamSeg* seg_d = nullptr;
+    PcmIn* pin_d = nullptr;
+    auto frame_bytes = [](const StreamPart& p) { return (size_t)p.channels * pcm_sample_bytes(p.fmt); };
     unsigned long long* list_d = nullptr;            // per round: the crop list (int2 per crop), one mask destination per crop, its row pitch
     float* gather = nullptr;
     auto carve = [&](Arena& A) {
         seg_d = static_cast<StreamSeg*>(A.alloc(sizeof(StreamSeg) * np));
+        if (pcm) pin_d = static_cast<PcmIn*>(A.alloc(sizeof(PcmIn) * np));
         list_d = static_cast<unsigned long long*>(A.alloc(24 * list_cap));
         if (any_crops) gather = A.allocf((size_t)bs * crop_f + 4096);
         for (StreamPart& p : parts) {
-            p.stage_in = (!on_dev && p.n > 0) ? A.allocf((size_t)2 * p.n) : nullptr;
+            // (bytes are staged as bytes, rounded up so that pcm_load24's aligned word reads stay inside the allocation)
+            if (pcm) p.stage_in = (!on_dev && p.n > 0) ? A.allocf(((size_t)p.n * frame_bytes(p) + 3) / 4 + 1) : nullptr;
+            else p.stage_in = (!on_dev && p.n > 0) ? A.allocf((size_t)2 * p.n) : nullptr;
             p.stage_y = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
             p.stage_v = (!out_on_dev && p.need > 0) ? A.allocf((size_t)2 * p.need + 4) : nullptr;
         }
@@ -2295,10 +2302,12 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
     for (StreamPart& p : parts) p.S->broken = true;  // until the call has gone through: a failure half way leaves the rings undefined
     // host copies of what the rounds send to the device, alive until the call has drained
     std::deque<std::vector<StreamSeg>> segs_h;
+    std::deque<std::vector<PcmIn>> pins_h;
     std::deque<std::vector<unsigned long long>> lists_h;
     try {
         for (StreamPart& p : parts) {
-            if (p.stage_in) VR_HIP(hipMemcpyAsync(p.stage_in, p.wave, (size_t)2 * p.n * sizeof(float), hipMemcpyHostToDevice, stream));
+            if (p.stage_in)
+                VR_HIP(hipMemcpyAsync(p.stage_in, p.wave, pcm ? (size_t)p.n * frame_bytes(p) : (size_t)2 * p.n * sizeof(float), hipMemcpyHostToDevice, stream));
             p.at = 0; p.flush_done = false;
             p.o = StreamStepIO{};
             p.o.blk_pitch = p.n;
@@ -2322,6 +2331,10 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
                 if (S.running) take = std::min(take, ((S.crops[0] + 1) * S.roi + offset) * (long long)hop - S.samples);
                 const float* src = p.n > 0 ? (on_dev ? p.wave : p.stage_in) : nullptr;
                 p.o.blk = final ? src : src + p.at; p.o.blk_n = take;
+                if (pcm) {                            // the step's bytes begin at frame p.at: any byte address for PCM24
+                    p.o.pcm = PcmIn{(final || !src) ? nullptr : reinterpret_cast<const uint8_t*>(src) + (size_t)p.at * frame_bytes(p), p.channels, p.fmt};
+                    p.o.blk = nullptr;
+                }
                 p.at += take;
                 p.flush_done = final;
                 const int entry = (int)live.size();
@@ -2344,7 +2357,17 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
                 any_tta = any_tta || parts[live[e]].S->tta;
             }
             VR_HIP(hipMemcpyAsync(seg_d, segs_h.back().data(), sizeof(StreamSeg) * ne, hipMemcpyHostToDevice, stream));
-            launch_stft_stream(plan, seg_d, ne, max_new, sum_blk, sum_new, stream);
+            if (pcm) {
+                pins_h.emplace_back((size_t)ne);
+                double blk_bytes = 0;
+                for (int e = 0; e < ne; ++e) {
+                    pins_h.back()[e] = parts[live[e]].o.pcm;
+                    blk_bytes += (double)parts[live[e]].o.blk_n * (double)frame_bytes(parts[live[e]]);
+                }
+                VR_HIP(hipMemcpyAsync(pin_d, pins_h.back().data(), sizeof(PcmIn) * ne, hipMemcpyHostToDevice, stream));
+                launch_stft_stream(plan, seg_d, ne, max_new, sum_blk, sum_new, stream, pin_d, blk_bytes);
+            } else
+                launch_stft_stream(plan, seg_d, ne, max_new, sum_blk, sum_new, stream);
             for (int e = 0; e < ne; ++e) {           // the statistics of a MEASURE / running stream, and a running stream's 1 / c before its crops
                 const StreamState& S = *parts[live[e]].S;
                 if (plans[e].new_frames > 0 && (S.measure || S.running))
@@ -2429,24 +2452,29 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
 }
 
 void Model::stream_push(StreamState& S, const float* wave, bool on_dev, long long n, bool flush, float* y, float* v, bool out_on_dev,
-                        long long capacity, long long* n_out) {
+                        long long capacity, long long* n_out, int channels, int fmt) {
     VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
+    if (fmt) {
+        VR_CHECK(n >= 0 && (n == 0 || wave), -2, "null or negative input");
+        check_pcm(on_dev && n > 0 ? wave : nullptr, channels, fmt, "");
+    }
     std::vector<StreamPart> parts(1);
     StreamPart& p = parts[0];
-    p.S = &S; p.wave = wave; p.n = n; p.flush = flush; p.y = y; p.v = v; p.capacity = capacity;
+    p.S = &S; p.wave = wave; p.n = n; p.flush = flush; p.y = y; p.v = v; p.capacity = capacity; p.channels = channels; p.fmt = fmt;
     p.need = stream_check(S, "", wave, n, flush, y, v, out_on_dev, capacity);
     if (n_out) *n_out = 0;
     if (n == 0 && !flush) return;
-    stream_run(parts, S.bs, on_dev, out_on_dev);
+    stream_run(parts, S.bs, on_dev, out_on_dev, fmt != 0);
     if (n_out) *n_out = p.need;
 }
 
 // vr_stream_push_many: stream k gets n_in[k] more samples and, flush[k], its end.  With one stream it is stream_push.
 void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float* const* wave, bool on_dev, const long long* n_in, const int* flush,
-                             int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out) {
+                             int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out,
+                             const int* channels, const int* fmt) {
     // ---- arguments and the schedule of this call: nothing here touches the device or a stream
     VR_CHECK(n_streams >= 1, -2, "n_streams must be positive");
-    VR_CHECK(Sv && n_in, -2, "null table");
+    VR_CHECK(Sv && n_in && (!fmt || channels), -2, "null table");
     VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
     std::vector<StreamPart> parts;
     std::vector<int> part_k;
@@ -2466,6 +2494,11 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
         StreamPart p{};
         p.S = &S; p.wave = wave ? wave[k] : nullptr; p.n = n_in[k]; p.flush = flush && flush[k];
         p.y = y ? y[k] : nullptr; p.v = v ? v[k] : nullptr; p.capacity = capacity ? capacity[k] : 0;
+        if (fmt) {
+            VR_CHECK(p.n >= 0 && (p.n == 0 || p.wave), -2, who + "null or negative input");
+            check_pcm(on_dev && p.n > 0 ? p.wave : nullptr, channels[k], fmt[k], who);
+            p.channels = channels[k]; p.fmt = fmt[k];
+        }
         p.need = stream_check(S, who, p.wave, p.n, p.flush, p.y, p.v, out_on_dev, p.capacity);
         if (batchsize <= 0) bs = std::max(bs, S.bs);
         if (p.n == 0 && !p.flush) continue;          // untouched
@@ -2474,7 +2507,7 @@ void Model::stream_push_many(int n_streams, StreamState* const* Sv, const float*
     }
     if (n_out) for (int k = 0; k < n_streams; ++k) n_out[k] = 0;
     if (parts.empty()) return;
-    stream_run(parts, bs, on_dev, out_on_dev);
+    stream_run(parts, bs, on_dev, out_on_dev, fmt != nullptr);
     if (n_out) for (size_t i = 0; i < parts.size(); ++i) n_out[part_k[i]] = parts[i].need;
 }
 

@@ -46,6 +46,13 @@ __device__ __forceinline__ float stream_sample(const StreamSeg& sg, int ch, long
     if (p < 0 || p >= sg.L) return 0.f;
     return p < sg.blk_base ? sg.tail[(long long)ch * sg.tail_pitch + (p - sg.tail_base)] : sg.blk[(long long)ch * sg.blk_pitch + (p - sg.blk_base)];
 }
+// the same where the step's block is sample bytes (`in`: the entry's PcmIn, whose bytes begin at the block's first frame): the tail is
+// float, kept per network channel `ch`; the block is read through pcm_decode at the file's channel in.ch
+template <class IN>
+__device__ __forceinline__ float stream_sample_pcm(const StreamSeg& sg, const IN& in, int ch, long long p) {
+    if (p < 0 || p >= sg.L) return 0.f;
+    return p < sg.blk_base ? sg.tail[(long long)ch * sg.tail_pitch + (p - sg.tail_base)] : in.at(p - sg.blk_base);
+}
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -206,7 +213,10 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 
 // PCM (at most one type): none = `wave` / the song table's `wave` are planar float32, as documented above.  PcmIn (SRC = const float, `wave`
 // unused) = the call's interleaved sample bytes; const PcmIn* (SRC = const SongSeg) = one entry per song beside the song table, whose
-// `wave` pointers are then unused.  The stream form keeps float input.
+// `wave` pointers are then unused; const PcmIn* (SRC = const StreamSeg) = one entry per table entry beside the stream
+// table: the step's block (`blk`, then unused) is that entry's interleaved sample bytes from the block's first frame on, format and channel
+// count per entry.  The input tail stays float32: `tail_out` receives the decoded samples, so the next step, float or PCM, reads the floats
+// a float push would have left.
 // WaveGrad in the same place (SRC = const float, `wave` and `spec` unused): the adjoint of the inverse transform for the wave-domain loss
 // term (kernels.h) -- blockIdx.y runs over the signals, L = hop (T-1), the source is WaveGradIn and the store epilogue writes dmask.
 // WaveGrad3: the same for the weighted SDR term, source WaveGrad3In over three waves, the same store epilogue.
@@ -224,7 +234,9 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad && !kPseudo && !kRows;
     static_assert(!kPseudo || kSongTable<SRC>, "the pair form is a song-table form");
     static_assert(!kRows || std::is_same<SRC, const float>::value, "the rows form is a one-song form");
-    static_assert(sizeof...(PCM) <= 1 && !(sizeof...(PCM) == 1 && kStream<SRC>), "one PCM source at most, none for streams");
+    static_assert(sizeof...(PCM) <= 1, "one PCM source at most");
+    static_assert(!kStream<SRC> || sizeof...(PCM) == 0 || std::is_same<typename FirstOr<void, PCM...>::type, const PcmIn*>::value,
+                  "a stream's PCM source is a table of PcmIn beside the stream table");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int n = pl.n_fft, M = n >> 1, bins = M + 1, hop = M, logM = pl.log2n - 1;
     const int g = threadIdx.x >> 8, tid = threadIdx.x & 255;
@@ -242,7 +254,8 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
         ss = wave[blockIdx.z];
         if (blockIdx.x > 0 && t0 >= ss.T - ss.t_new) return;        // (workgroup 0 always runs: it moves the input tail on)
         t0 += ss.t_new; T = ss.T;
-        in.wv = nullptr;
+        if constexpr (kPcm) in.in = pcm_first(pcm...)[blockIdx.z];
+        else in.wv = nullptr;
     } else if constexpr (kSongTable<SRC>) {          // blockIdx.z = song; the grid is sized for the longest one
         const SongSeg sg = wave[blockIdx.z];
         if (t0 >= sg.T) return;
@@ -286,7 +299,10 @@ second_pass:
             for (int m = tid; m < M; m += 256) {
                 const long long p = start + 2 * m;
                 float v0, v1;
-                if constexpr (kStream<SRC>) {
+                if constexpr (kStream<SRC> && kPcm) {
+                    v0 = stream_sample_pcm(ss, in, ch, p) * pl.window[2 * m];
+                    v1 = stream_sample_pcm(ss, in, ch, p + 1) * pl.window[2 * m + 1];
+                } else if constexpr (kStream<SRC>) {
                     v0 = stream_sample(ss, ch, p) * pl.window[2 * m];
                     v1 = stream_sample(ss, ch, p + 1) * pl.window[2 * m + 1];
                 } else {
@@ -360,8 +376,10 @@ second_pass:
     if constexpr (kStream<SRC>) {                    // the samples the next step's first frames reach back to
         if (blockIdx.x == 0) {
             const int keep = (int)(ss.L - ss.tail_out_base);
-            for (int i = threadIdx.x; i < keep; i += 1024)
-                ss.tail_out[(long long)ch * ss.tail_pitch + i] = stream_sample(ss, ch, ss.tail_out_base + i);
+            for (int i = threadIdx.x; i < keep; i += 1024) {
+                if constexpr (kPcm) ss.tail_out[(long long)ch * ss.tail_pitch + i] = stream_sample_pcm(ss, in, ch, ss.tail_out_base + i);
+                else ss.tail_out[(long long)ch * ss.tail_pitch + i] = stream_sample(ss, ch, ss.tail_out_base + i);
+            }
         }
     }
 }
@@ -1592,12 +1610,23 @@ void launch_eval_sums(const FFTPlan& pl, const SongSeg* songs, const WaveEval* e
 // Every launch covers what one step of the stream added: new frames, newly ready crops, newly final output segments.
 bool stream_tiled_available(const FFTPlan& pl, int hop) { return tiled_signal_path(pl, hop); }
 
-void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st) {
+void launch_stft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int new_frames, double new_samples, double sum_frames, hipStream_t st,
+                        const PcmIn* pcm, double pcm_bytes) {
     const int M = pl.n_fft / 2, bins = M + 1;
     int F = tile_frames(pl, 0);
     if (F > 16) F = 16;
     F = F / TG * TG;
     const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    if (pcm) {                                           // the blocks of the entries are sample bytes (one PcmIn per entry)
+        static std::atomic<unsigned long long> attr_pcm{0};
+        ensure_lds_attr(attr_pcm, reinterpret_cast<const void*>(stft_tile_kernel<const StreamSeg, const PcmIn*>), 160 * 1024);
+        prof_note(0.0, pcm_bytes + 2.0 * 8.0 * (double)bins * sum_frames);
+        const int blocks = new_frames > 0 ? (new_frames + F - 1) / F : 1;
+        VR_LAUNCH((stft_tile_kernel<const StreamSeg, const PcmIn*>), dim3((unsigned)blocks, 2, (unsigned)n_seg), dim3(1024), lds, st, pl, seg, 0LL, 0, F,
+                  nullptr, pcm);
+        VR_HIP(hipGetLastError());
+        return;
+    }
     static std::atomic<unsigned long long> attr_done{0};
     ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const StreamSeg>), 160 * 1024);
     prof_note(0.0, 2.0 * (4.0 * new_samples + 8.0 * (double)bins * sum_frames));

@@ -449,17 +449,77 @@ class Separator(object):
                 st._device = dev if on_dev else st._device
         return [(a[:int(g)], b[:int(g)]) if q else (a[:, :int(g)], b[:, :int(g)]) for a, b, g, q in zip(ys, vs, got, pcm)]
 
+    def push_many_pcm(self, streams, raws, flush=False, batchsize=None):
+        """push_many with the sample bytes in (vr_stream_push_many_pcm): streams[k] receives raws[k] -- an audio.RawPcm of PCM16 / 24 / 32 or
+        float32 frames of 1 or 2 channels, or None for nothing -- and, where flush says so, its input ends there.  Formats and channel
+        counts may differ per stream; the stream STFT decodes (a mono block is up-mixed).  Returns what push_many returns for the decoded
+        blocks.  Either every raw.bytes is a numpy array (numpy out) or every one is a cuda uint8 tensor (cuda out)."""
+        from .spec_utils import _pcm_bytes
+        ct = native.ctypes
+        streams, raws = list(streams), list(raws)
+        N = len(streams)
+        if not N:
+            raise ValueError('push_many_pcm needs at least one stream')
+        if len(raws) != N:
+            raise ValueError('push_many_pcm: %d streams but %d blocks' % (N, len(raws)))
+        fl = [bool(flush)] * N if isinstance(flush, (bool, np.bool_)) else [bool(f) for f in flush]
+        if len(fl) != N:
+            raise ValueError('push_many_pcm: %d streams but %d flush flags' % (N, len(fl)))
+        prepared = [None if r is None else _pcm_bytes(r) for r in raws]
+        cuda = [p[2] for p in prepared if p is not None]
+        if any(cuda) and not all(cuda):
+            raise ValueError('push_many_pcm: either every block is a cuda tensor or none is')
+        on_dev = all(cuda) if cuda else bool(streams[0]._dev_out)
+        if on_dev:
+            import torch
+            devs = set(p[0].device for p in prepared if p is not None)
+            if len(devs) > 1:
+                raise ValueError('push_many_pcm: the blocks are on different devices')
+            dev = devs.pop() if devs else next(st._device for st in streams if st._device is not None)
+        lens = [0 if r is None else int(r.frames) for r in raws]
+        caps = [max(st._need(n, f), 1) for st, n, f in zip(streams, lens, fl)]       # (a flush below one hop of input raises here)
+        pcm = [st.pcm16 for st in streams]
+        if on_dev:
+            ys = [torch.empty((c, 2) if q else (2, c), dtype=torch.int16 if q else torch.float32, device=dev) for c, q in zip(caps, pcm)]
+            vs = [torch.empty_like(a) for a in ys]
+            torch.cuda.current_stream(dev).synchronize()
+            addr = lambda a: a.data_ptr()
+        else:
+            ys = [np.empty((c, 2) if q else (2, c), dtype=np.int16 if q else np.float32) for c, q in zip(caps, pcm)]
+            vs = [np.empty_like(a) for a in ys]
+            addr = lambda a: a.ctypes.data
+        table = lambda seq: (ct.c_void_p * N)(*[addr(a) for a in seq])
+        got = (ct.c_int64 * N)()
+        self.model.eval()
+        native.check(native.lib().vr_stream_push_many_pcm(
+            N, (ct.c_void_p * N)(*[st._s.value for st in streams]),
+            (ct.c_void_p * N)(*[p[1] if p is not None and n else None for p, n in zip(prepared, lens)]), 1 if on_dev else 0,
+            (ct.c_int64 * N)(*lens), (ct.c_int * N)(*[2 if r is None else int(r.channels) for r in raws]),
+            (ct.c_int * N)(*[native.VR_PCM_S16 if r is None else int(r.fmt) for r in raws]), (ct.c_int * N)(*[1 if f else 0 for f in fl]),
+            int(self.batchsize if batchsize is None else batchsize), table(ys), table(vs), 1 if on_dev else 0, (ct.c_int64 * N)(*caps), got),
+            native.VRArgumentError)
+        for st, n, f in zip(streams, lens, fl):
+            if n or f:
+                st._samples += n
+                st._dev_out = on_dev
+                st._device = dev if on_dev else st._device
+        return [(a[:int(g)], b[:int(g)]) if q else (a[:, :int(g)], b[:, :int(g)]) for a, b, g, q in zip(ys, vs, got, pcm)]
+
     def flush_many(self, streams):
         """Stream.flush for every stream of the list in one call."""
         streams = list(streams)
         return self.push_many(streams, [None] * len(streams), flush=True)
 
     def measure_coef(self, blocks, tta=False):
-        """The normaliser separate_wave(tta=tta) would use for the concatenation of `blocks` (an iterable of waves [2, n]), without
-        running the network or holding the input."""
+        """The normaliser separate_wave(tta=tta) would use for the concatenation of `blocks` (an iterable of waves [2, n], or of
+        audio.RawPcm blocks, which go in as bytes: Stream.push_pcm), without running the network or holding the input."""
+        from .audio import RawPcm
         with Stream(self, None, tta, measure=True) as s:
             for b in blocks:
-                s.push(b)
+                if isinstance(b, RawPcm):
+                    s.push_pcm(b)
+                else:
+                    s.push(b)
             s.flush()
             return s.coef()
 
@@ -544,6 +604,37 @@ class Stream(object):
     def push(self, wave):
         return self._call(wave, False)
 
+    def push_pcm(self, raw):
+        """push() of the decoded block without the host decode (vr_stream_push_pcm): raw = audio.RawPcm of PCM16 / 24 / 32 or float32
+        frames of 1 or 2 channels (mono is up-mixed); the stream STFT reads the bytes.  Returns exactly what push(decoded) returns and
+        leaves the same state, so push and push_pcm may be mixed.  numpy bytes give numpy arrays, a cuda uint8 tensor cuda tensors.
+        Refusals (format, channels, a misaligned PCM16 / PCM32 / float32 cuda buffer) are native.VRArgumentError."""
+        from .spec_utils import _pcm_bytes
+        if not self._s.value:
+            raise native.VRError('stream is closed')
+        b, addr, on_dev = _pcm_bytes(raw)
+        n = int(raw.frames)
+        self._dev_out = on_dev
+        cap = max(self._need(n, False), 1)
+        got = native.ctypes.c_int64()
+        if on_dev:
+            import torch
+            self._device = dev = b.device
+            y = torch.empty((cap, 2) if self.pcm16 else (2, cap), dtype=torch.int16 if self.pcm16 else torch.float32, device=dev)
+            v = torch.empty_like(y)
+            torch.cuda.current_stream(dev).synchronize()
+            yp, vp = y.data_ptr(), v.data_ptr()
+        else:
+            y = np.empty((cap, 2) if self.pcm16 else (2, cap), dtype=np.int16 if self.pcm16 else np.float32)
+            v = np.empty_like(y)
+            yp, vp = native.np_ptr(y), native.np_ptr(v)
+        native.check(native.lib().vr_stream_push_pcm(self._s, addr if n else None, 1 if on_dev else 0, n, int(raw.channels), int(raw.fmt), yp, vp,
+                                                     1 if on_dev else 0, cap, native.ctypes.byref(got)), native.VRArgumentError)
+        self._samples += n
+        if self.pcm16:
+            return y[:int(got.value)], v[:int(got.value)]
+        return y[:, :int(got.value)], v[:, :int(got.value)]
+
     def flush(self):
         return self._call(None, True)
 
@@ -586,12 +677,17 @@ class _StreamSource(object):
     whole file is audio.load(path, sr)'s, so the blocks vary in length by a sample and the last one carries the resampler's flush.
     A mono file is up-mixed BEFORE the resampler (the channels are independent, so the bits are those of resampling it mono): every
     session has two channels, and the sessions of a group fit one resample_push_many call.  on_device: the blocks are uploaded once, as
-    cuda tensors, so that the resampler's output goes into Stream.push where it lies (set for a source that resamples)."""
+    cuda tensors, so that the resampler's output goes into Stream.push where it lies (set for a source that resamples).
+    pcm_in: where the reader gives the file's bytes (WavBlockReader.raw_blocks: PCM16 / 24 / 32 / float32 of 1 or 2 channels) the blocks are
+    audio.RawPcm -- no _decode and no _stereo on the host: at the file's own rate they go into Stream.push_pcm, otherwise into the
+    resampler's push_pcm, whose output is the same float block as before.  `self.pcm_in` is the choice made; 8-bit and float64 files
+    keep the decoded route."""
 
-    def __init__(self, path, sr, block_seconds, resample=False, device=None):
+    def __init__(self, path, sr, block_seconds, resample=False, device=None, pcm_in=True):
         from . import audio
         self.device = device
         self.rd = rd = audio.WavBlockReader(path)
+        self.pcm_in = bool(pcm_in) and rd.raw_blocks(1) is not None
         if rd.sr != sr and not resample:
             raise ValueError('%s has sample rate %d, not --sr %d: the resampler is not streamed, run without --stream '
                              '(or pass resample=True to stream_file / stream_files)' % (path, rd.sr, sr))
@@ -599,11 +695,18 @@ class _StreamSource(object):
         self.on_device = self.resamples
         self.n = max(1, int(round(block_seconds * rd.sr)))
 
-    def raw(self):
-        """the file's own blocks, stereo [2, n], at its own rate"""
+    def raw(self, decoded=False):
+        """the file's own blocks at its own rate: stereo [2, n], or (pcm_in, unless `decoded`) audio.RawPcm of the file's frames"""
+        from . import audio
         if self.on_device:
             import torch
             dev = torch.device('cuda', int(self.device or 0))
+        if self.pcm_in and not decoded:
+            for r in self.rd.raw_blocks(self.n):
+                if self.on_device:
+                    r = audio.RawPcm(torch.from_numpy(np.array(r.bytes)).to(dev), r.fmt, r.channels, r.sr, r.frames)
+                yield r
+            return
         for b in self.rd.blocks(self.n):
             b = _stereo(b)
             yield torch.from_numpy(b).to(dev) if self.on_device else b
@@ -619,15 +722,20 @@ class _StreamSource(object):
             return
         with self.resampler() as rs:
             for b in self.raw():
-                y = rs.push(b)
+                y = rs.push_pcm(b) if self.pcm_in else rs.push(b)
                 if y.shape[1]:
                     yield y
             yield rs.flush()
 
 
-def _stream_reader(path, sr, block_seconds, resample=False, device=None):
-    """-> blocks(): a fresh iterator over the WAV at `path` as stereo blocks [2, n] at `sr` (see _StreamSource)."""
-    return _StreamSource(path, sr, block_seconds, resample, device).blocks
+def _stream_reader(path, sr, block_seconds, resample=False, device=None, pcm_in=True):
+    """-> blocks(): a fresh iterator over the WAV at `path` as blocks at `sr`: stereo [2, n], or audio.RawPcm (see _StreamSource)."""
+    return _StreamSource(path, sr, block_seconds, resample, device, pcm_in).blocks
+
+
+def _push_block(s, b):
+    from .audio import RawPcm
+    return s.push_pcm(b) if isinstance(b, RawPcm) else s.push(b)
 
 
 def _rows(a, pcm16):
@@ -636,19 +744,20 @@ def _rows(a, pcm16):
     return a if pcm16 else a.T
 
 
-def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False):
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True):
     """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
     written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed -- unless
     resample=True, which reads both passes at the file's own rate through an audio.StreamResampler (bounded state; the blocks stay on
     the device from the upload to the stems); the stems are written at `sr`, as the offline path writes them.  pcm16: the stream
-    returns the stems as the file's int16 samples (Separator.stream(pcm16=True)); the files are byte for byte the same."""
+    returns the stems as the file's int16 samples (Separator.stream(pcm16=True)); the files are byte for byte the same.
+    pcm_in: both passes push the file's own bytes where the device decodes them (_StreamSource); the stems are the same bits."""
     from . import audio
-    blocks = _stream_reader(path, sr, block_seconds, resample, sp.model._need_handle().device)
+    blocks = _stream_reader(path, sr, block_seconds, resample, sp.model._need_handle().device, pcm_in)
     coef = sp.measure_coef(blocks(), tta=tta)
     with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, \
             sp.stream(coef=coef, tta=tta, pcm16=pcm16) as s:
         for b in blocks():
-            y, v = s.push(b)
+            y, v = _push_block(s, b)
             wy.append(_rows(y, pcm16))
             wv.append(_rows(v, pcm16))
         y, v = s.flush()
@@ -656,7 +765,7 @@ def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resamp
         wv.append(_rows(v, pcm16))
 
 
-def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False):
+def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True):
     """--stream on a directory: stream_file for a group of WAVs at once.  Every file's normaliser is measured first; then the files
     advance together, one block each per Separator.push_many call, so their crops share device batches; a file that ends is flushed
     in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k].
@@ -664,13 +773,17 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
     them in ONE audio.resample_push_many launch in front of push_many.  The files may have different rates: the launch table carries
     each session's ratio and filter, so they are not grouped by rate.  Mono files are up-mixed first, so every session has two
     channels.  When any file of the group resamples, the blocks of all its files are uploaded as cuda tensors (push_many takes one
-    kind), and nothing comes back to the host before the stems."""
+    kind), and nothing comes back to the host before the stems.
+    pcm_in: the measuring pass of every file, and every resampler, take the file's bytes where the device decodes them.  The separating
+    pass takes one kind of block per push_many call: bytes (push_many_pcm) when no file of the group resamples and every file's encoding
+    is one the device decodes; otherwise the files at `sr` are decoded on the host as before, beside the resamplers' float output."""
     import contextlib
 
     from . import audio
-    sources = [_StreamSource(p, sr, block_seconds, resample, sp.model._need_handle().device) for p in paths]
+    sources = [_StreamSource(p, sr, block_seconds, resample, sp.model._need_handle().device, pcm_in) for p in paths]
     coefs = [sp.measure_coef(src.blocks(), tta=tta) for src in sources]
     on_device = any(src.resamples for src in sources)
+    bytes_in = not on_device and all(src.pcm_in for src in sources)        # the streams themselves take bytes
     for src in sources:
         src.on_device = on_device
     with contextlib.ExitStack() as stack:
@@ -678,7 +791,7 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
         wv = [stack.enter_context(audio.WavAppendWriter(ov, sr, 2)) for _, ov in outs]
         streams = [stack.enter_context(sp.stream(coef=c, tta=tta, pcm16=pcm16)) for c in coefs]
         rs = [stack.enter_context(src.resampler()) if src.resamples else None for src in sources]
-        its = [src.raw() for src in sources]
+        its = [src.raw(decoded=not (bytes_in or src.resamples)) for src in sources]
         ahead = [next(it, None) for it in its]
         live = list(range(len(paths)))                  # the files still streaming; a flushed stream takes no further part
         while live:
@@ -686,12 +799,13 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
             for k in live:
                 ahead[k] = next(its[k], None) if ahead[k] is not None else None
             ends = [ahead[k] is None for k in live]
-            sel = [i for i, k in enumerate(live) if rs[k] is not None]
-            if sel:                                     # one resampling launch for the round, whatever the files' rates
-                done = audio.resample_push_many([rs[live[i]] for i in sel], [cur[i] for i in sel], [ends[i] for i in sel])
-                for i, y in zip(sel, done):
-                    cur[i] = y
-            for k, (y, v) in zip(live, sp.push_many([streams[k] for k in live], cur, ends)):
+            for pcm, push in ((False, audio.resample_push_many), (True, audio.resample_push_many_pcm)):
+                sel = [i for i, k in enumerate(live) if rs[k] is not None and sources[k].pcm_in == pcm]
+                if sel:                                 # one resampling launch for the round, whatever the files' rates (and one per kind of block)
+                    done = push([rs[live[i]] for i in sel], [cur[i] for i in sel], [ends[i] for i in sel])
+                    for i, y in zip(sel, done):
+                        cur[i] = y
+            for k, (y, v) in zip(live, (sp.push_many_pcm if bytes_in else sp.push_many)([streams[k] for k in live], cur, ends)):
                 wy[k].append(_rows(y, pcm16))
                 wv[k].append(_rows(v, pcm16))
             live = [k for k, end in zip(live, ends) if not end]

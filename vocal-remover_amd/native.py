@@ -81,6 +81,12 @@ _SIGNATURES = {
     'vr_stream_push_many': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
                                            ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p, c_i64p]),
+    'vr_stream_push_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p,
+                                          ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_stream_push_many_pcm': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                               ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                               c_i64p, c_i64p]),
     'vr_stream_coef': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     'vr_stream_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i64p]),
     'vr_stream_close': (ctypes.c_int, [ctypes.c_void_p]),
@@ -160,6 +166,11 @@ _SIGNATURES = {
     'vr_resampler_flush': (ctypes.c_int, [ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int64, c_i64p]),
     'vr_resampler_push_many': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p,
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p, c_i64p]),
+    'vr_resampler_push_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p,
+                                             ctypes.c_int, ctypes.c_int64, c_i64p]),
+    'vr_resampler_push_many_pcm': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                                  c_i64p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_i64p, c_i64p]),
     'vr_resampler_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p]),
     'vr_resampler_close': (ctypes.c_int, [ctypes.c_void_p]),
     'vr_resampler_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_i64p]),
