@@ -235,6 +235,33 @@ int vr_separate_many(vr_handle h, int n_songs, const float* const* specs, int sp
 int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
                           int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device);
 
+/* ---- spectrogram images: lib/spec_utils.py:34-57 on the device ------------------------------------
+ * spectrogram_to_image in float32 as numpy evaluates it: y = log10(|z|^2 + 1e-8) (VR_IMAGE_MAGNITUDE; a float input: s^2) or angle(z)
+ * (VR_IMAGE_PHASE; a float input: s), lo = min y, r = max (y - lo), pixel = uint8((y - lo) * (255 / r)), truncated.
+ * vr_spec_image_many: specs[i] [channels][bins][T[i]] complex64 (is_complex) or float32 -> imgs[i]: channels == 2 gives
+ * [bins][T[i]][3] bytes = (max(L, R), L, R), channels == 1 gives [bins][T[i]]; no vertical flip, the input is not modified.  ranges
+ * (HOST, may be null) [n][2] = (lo, r) of every picture.  One range launch and one write launch cover all n pictures; no handle.
+ * A constant input (r == 0; the reference casts NaN to uint8 there) gives a picture of zeros.  NaN or Inf in the input: the picture is
+ * unspecified, nothing outside it is touched.  Device inputs need their natural alignment (8 / 4 bytes); pictures may lie anywhere.
+ * vr_separate_wave_many_img / vr_separate_pcm_many_img: the call without the suffix, which also returns for every song the magnitude
+ * pictures y_img[s], v_img[s] [bins][1 + L[s] / hop][3] of the instruments and vocals spectrograms -- of the very values
+ * vr_separate_many would have stored, formed from the resident spectrogram and mask: no stem spectrogram is stored for them.  The
+ * pictures lie where the stems lie (out_on_device).  ranges (HOST, may be null) [n_songs][2 stems][2].  The stems are bit for bit
+ * those of the call without the suffix; BOTH stem tables null: pictures only, no stem is formed.
+ * Errors (VR_ERR_BAD_ARGUMENT, the device untouched): n <= 0, a null table or entry, channels not 1 or 2, bins or T[i] <= 0, more
+ * than 2^31 - 1 pixels in a picture, an unknown mode, one picture table or one stem table null and the other not, training mode.   */
+enum vr_image_mode { VR_IMAGE_MAGNITUDE = 0, VR_IMAGE_PHASE = 1 };
+int vr_spec_image_many(int device, int n, const void* const* specs, int on_device, int channels, int bins, const int* T, int is_complex,
+                       int mode, uint8_t* const* imgs, int out_on_device, float* ranges /* [n][2] or null */);
+int vr_spec_image(int device, const void* spec, int on_device, int channels, int bins, int T, int is_complex, int mode, uint8_t* img,
+                  int out_on_device, float* range /* [2] or null */);
+int vr_separate_wave_many_img(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
+                              int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device,
+                              uint8_t* const* y_img, uint8_t* const* v_img, float* ranges /* [n_songs][2 stems][2] or null */);
+int vr_separate_pcm_many_img(vr_handle h, int n_songs, const void* const* bytes, int on_device, const int64_t* frames, const int* channels,
+                             const int* fmt, int tta, int batchsize, int cropsize, int16_t* const* y, int16_t* const* v, int out_on_device,
+                             uint8_t* const* y_img, uint8_t* const* v_img, float* ranges /* [n_songs][2 stems][2] or null */);
+
 /* ---- score a separation against the true stems: windowed SDR sums on the device -----------------
  * vr_separate_wave_many that also measures each song.  mix[s], inst[s]: float32 [2, L[s]], the mixture and its true instruments (both
  * on the host or both on the device, `on_device`).  With samples = hop * (L / hop), the stems y, v of vr_separate_wave and the true stems

@@ -244,6 +244,74 @@ int vr_separate_wave_many(vr_handle h, int n_songs, const float* const* waves, i
     });
 }
 
+// ---- spectrogram images ---------------------------------------------------------------------------------------
+// What can be judged without the handle: the count, the tables, a stem table or a picture table without its partner.
+static bool image_args_ok(int n_songs, const void* in, const void* len, const void* y, const void* v, const void* y_img, const void* v_img) {
+    if (n_songs <= 0) { g_err = "n_songs must be positive"; return false; }
+    if (!in || !len) { g_err = "null table"; return false; }
+    if ((y == nullptr) != (v == nullptr)) { g_err = "one stem table is null and the other is not: give both, or neither for pictures only"; return false; }
+    if ((y_img == nullptr) != (v_img == nullptr)) { g_err = "one picture table is null and the other is not"; return false; }
+    if (!y_img) { g_err = "null table"; return false; }
+    return true;
+}
+
+int vr_separate_wave_many_img(vr_handle h, int n_songs, const float* const* waves, int waves_on_device, const int64_t* L, int tta,
+                              int batchsize, int cropsize, float* const* y_waves, float* const* v_waves, int out_on_device,
+                              uint8_t* const* y_img, uint8_t* const* v_img, float* ranges) {
+    if (!image_args_ok(n_songs, waves, L, y_waves, v_waves, y_img, v_img)) return VR_ERR_BAD_ARGUMENT;
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(L, L + n_songs);
+        const vr::ImageArgs im{y_img, v_img, ranges, y_waves != nullptr};
+        h->m.separate_run(n_songs, waves, waves_on_device != 0, nullptr, len.data(), tta, batchsize, cropsize, y_waves, v_waves,
+                          out_on_device != 0, nullptr, nullptr, /*solo=*/false, nullptr, nullptr, &im);
+    });
+}
+
+int vr_separate_pcm_many_img(vr_handle h, int n_songs, const void* const* bytes, int on_device, const int64_t* frames, const int* channels,
+                             const int* fmt, int tta, int batchsize, int cropsize, int16_t* const* y, int16_t* const* v, int out_on_device,
+                             uint8_t* const* y_img, uint8_t* const* v_img, float* ranges) {
+    if (!image_args_ok(n_songs, bytes, frames, y, v, y_img, v_img)) return VR_ERR_BAD_ARGUMENT;
+    if (!channels || !fmt) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
+    NEED(h);
+    return guard([&] {
+        std::vector<long long> len(frames, frames + n_songs);
+        const vr::ImageArgs im{y_img, v_img, ranges, y != nullptr};
+        h->m.separate_run(n_songs, reinterpret_cast<const float* const*>(bytes), on_device != 0, nullptr, len.data(), tta, batchsize,
+                          cropsize, reinterpret_cast<float* const*>(y), reinterpret_cast<float* const*>(v), out_on_device != 0, channels, fmt,
+                          /*solo=*/false, nullptr, nullptr, &im);
+    });
+}
+
+static void need_device(int device);
+
+int vr_spec_image_many(int device, int n, const void* const* specs, int on_device, int channels, int bins, const int* T, int is_complex,
+                       int mode, uint8_t* const* imgs, int out_on_device, float* ranges) {
+    if (n <= 0 || !specs || !T || !imgs) { g_err = "spec image: no picture or a null table"; return VR_ERR_BAD_ARGUMENT; }
+    return guard([&] {
+        VR_CHECK(channels == 1 || channels == 2, VR_ERR_BAD_ARGUMENT, "spec image: channels must be 1 or 2");
+        VR_CHECK(bins > 0, VR_ERR_BAD_ARGUMENT, "spec image: bins must be positive");
+        VR_CHECK(mode == VR_IMAGE_MAGNITUDE || mode == VR_IMAGE_PHASE, VR_ERR_BAD_ARGUMENT, "spec image: unknown mode (VR_IMAGE_MAGNITUDE or VR_IMAGE_PHASE)");
+        for (int i = 0; i < n; ++i) {
+            const std::string who = "spec image: picture " + std::to_string(i) + ": ";
+            VR_CHECK(specs[i] && imgs[i], VR_ERR_BAD_ARGUMENT, who + "null pointer");
+            VR_CHECK(T[i] > 0, VR_ERR_BAD_ARGUMENT, who + "T must be positive");
+            VR_CHECK((long long)bins * T[i] < (1LL << 31), VR_ERR_BAD_ARGUMENT, who + "more than 2^31 - 1 pixels");
+            if (on_device)
+                VR_CHECK((reinterpret_cast<uintptr_t>(specs[i]) & (is_complex ? 7 : 3)) == 0, VR_ERR_BAD_ARGUMENT,
+                         who + "a device spectrogram needs its natural alignment");
+        }
+        need_device(device);
+        vr::spec_image_many_api(device, n, specs, on_device != 0, channels, bins, T, is_complex != 0, mode, imgs, out_on_device != 0, ranges);
+    });
+}
+
+int vr_spec_image(int device, const void* spec, int on_device, int channels, int bins, int T, int is_complex, int mode, uint8_t* img,
+                  int out_on_device, float* range) {
+    if (!spec || !img) { g_err = "spec image: null argument"; return VR_ERR_BAD_ARGUMENT; }
+    return vr_spec_image_many(device, 1, &spec, on_device, channels, bins, &T, is_complex, mode, &img, out_on_device, range);
+}
+
 // ---- evaluation against the true stems -------------------------------------------------------------------
 // What can be judged without the handle is: the tables, the counts, a stem table without its partner, a window or a length below one
 // sample.  window < hop and L < hop need the handle's hop: Model::separate_run refuses them before it touches the device.

@@ -525,6 +525,31 @@ void launch_pseudo_diff_many(const SongSeg* songs, const PseudoSeg* ps, int n_so
 void launch_apply_mask_pseudo_many(const SongSeg* songs, const PseudoSeg* ps, int n_songs, int max_T, int bins, const float* mask, int W, int tta,
                                    bool cplx, const float* wgt, bool rows, double sum_T, hipStream_t st);
 
+// ---- spectrogram images (vr_spec_image*, vr_separate_*_img) ---------------------------------------------------------
+// One entry per image job of a call (device memory).  A job is one min / max range and the pictures scaled by it: a stored spectrogram
+// gives one picture (img[0]); a song of a separation call gives two, instruments and vocals, each with a range of its own, and rides
+// beside the song table as PseudoSeg does.  A picture of a two-channel source is [bins][T][3] bytes (max(L, R), L, R), of a one-channel
+// source [bins][T].  The range pass leaves per workgroup (min y, max y) of either stem in part[workgroup]; the write pass reduces them
+// again in every workgroup and leaves (lo, max - lo) per stem in `range`.
+constexpr int kImgChunk = 1024;       // pixels per workgroup step of either pass
+constexpr int kImgParts = 512;        // most workgroups of a job's range pass
+constexpr int kImgWriteChunks = 4;    // chunks per workgroup of the write pass
+struct ImgSeg {
+    const void* src;          // [channels][bins][T] complex64 or float32 (stored spectrograms; unused beside a song table)
+    uint8_t* img[2];
+    float4* part;             // [kImgParts] (min, max) of stem 0, (min, max) of stem 1
+    float* range;             // [stems][2]
+    int T;
+};
+// n stored spectrograms: one range launch and one write launch for all of them; max_T, sum_T: the longest job, all jobs (profiler's note)
+void launch_spec_image_many(const ImgSeg* jobs, int n, int channels, int bins, int max_T, double sum_T, bool cplx, int mode, hipStream_t st);
+// the two stems of every song of a separation call, from the song's spectrogram and the call's mask as apply_mask_kernel reads them
+void launch_stem_image_many(const SongSeg* songs, const ImgSeg* jobs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                            const float* wgt, double sum_T, hipStream_t st);
+// vr_spec_image_many behind its argument checks: staging, the two launches, the copies back
+void spec_image_many_api(int device, int n, const void* const* specs, bool on_dev, int channels, int bins, const int* T, bool cplx, int mode,
+                         uint8_t* const* imgs, bool out_on_dev, float* ranges);
+
 // ---- streaming separation (vr_stream_*) ------------------------------------------------------------------------------------------
 // The state of one step of a stream, as the StreamSeg instantiations of the spectrogram-side kernels read it (one copy to the device per
 // step).  The kernels take a TABLE of them: one grid dimension is the table entry, sized for the largest entry, and a workgroup past

@@ -117,6 +117,10 @@ struct EvalArgs { const float* const* inst; long long window; double* const* sum
 // waves of the same size, where the mixtures are (host or device); the network separates D = in - inst, and y[s] receives
 // P = inst + instruments stem of D, T complex64 frames in `layout` (enum vr_pseudo_layout).  v of separate_run is unused.
 struct PseudoArgs { const float* const* inst; int layout; };
+// Spectrogram images of the stems (vr_separate_*_img): y_img[s] / v_img[s] receive song s's pictures [bins][T][3]
+// bytes, where the stems go (host or device); ranges (HOST, may be null) [song][stem][2] = (lo, max - lo) of each picture.  stems false:
+// pictures only (y, v of separate_run unused).
+struct ImageArgs { uint8_t* const* y_img; uint8_t* const* v_img; float* ranges; bool stems; };
 // the stems' length and the window count of a song of L samples: samples = hop (L / hop), windows = ceil(samples / window); host only
 struct EvalPlan { long long samples, windows; };
 EvalPlan evaluate_plan(int hop, long long L, long long window);
@@ -278,7 +282,7 @@ public:
     void separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T, const long long* L, int tta, int batchsize,
                       int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels = nullptr,
                       const int* pcm_fmt = nullptr, bool solo = false, const EvalArgs* eval = nullptr,
-                      const PseudoArgs* pseudo = nullptr);
+                      const PseudoArgs* pseudo = nullptr, const ImageArgs* image = nullptr);
     // ---- pitch-shifted waves and training pairs (vr_pitch_*, csrc/pitch.hip) ----
     // spec [signals][bins][T] -> out [signals][bins][ceil(T / rate)], the handle's bins and hop
     void phase_vocoder_api(const float* spec, bool on_dev, int signals, int T, double rate, float* out, bool out_on_dev);

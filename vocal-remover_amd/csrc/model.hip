@@ -1759,9 +1759,12 @@ void Model::run_dense_crops(float* dense, int count, int cropsize, const HeadDst
 // front end stores Y and D = X - Y (wave level: the pair form of the tiled STFT; spectrogram level: one elementwise launch), the table's
 // `spec` is D, so everything between the normaliser and the per-frame minima runs as for any song; the back end is the pseudo form
 // of apply_mask, which stores P once, in the caller's layout.  No vocal stem and no wave is allocated, stored or copied (v unused).
+// image (vr_separate_*_img): the call also returns the two spectrogram pictures of every song.  Nothing before the back
+// end changes and no launch of it is replaced: two more launches (the range and the write form of mag_pad / apply_mask) read the song's
+// spectrogram and the call's mask once more, and the pictures go out beside the stems.  Without image->stems no stem is formed at all.
 void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, const int* T_in, const long long* L, int tta, int batchsize,
                          int cropsize, float* const* y, float* const* v, bool out_on_dev, const int* pcm_channels, const int* pcm_fmt,
-                         bool solo, const EvalArgs* eval, const PseudoArgs* pseudo) {
+                         bool solo, const EvalArgs* eval, const PseudoArgs* pseudo, const ImageArgs* image) {
     // VR_ENQ_TIMING=1 (diagnostics, wave-level calls): host time to ENQUEUE the whole call vs the time until the device has drained it
     static const bool enq_timing = getenv("VR_ENQ_TIMING") != nullptr;
     const auto enq_t0 = std::chrono::steady_clock::now();
@@ -1772,7 +1775,8 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     const bool pcm = pcm_fmt != nullptr;
     // ---- arguments and the host-side plan: nothing here touches the device
     VR_CHECK(n_songs > 0, -2, "n_songs must be positive");
-    const bool stems = !eval || eval->stems;
+    const bool stems = (!eval || eval->stems) && (!image || image->stems);
+    if (image) VR_CHECK(!eval && !pseudo && image->y_img && image->v_img && (stems || waves), -2, "an image call takes songs and both picture tables");
     VR_CHECK(in && (!stems || (y && (v || pseudo))) && (waves || T_in), -2, "null table");
     if (pseudo) {
         VR_CHECK(!pcm && !eval && pseudo->inst, -2, "a pseudo-label call takes float pairs");
@@ -1799,12 +1803,13 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         const std::string who = song(s);
         VR_CHECK(in[s] && (!stems || (y[s] && (pseudo || v[s]))) && (!eval || (eval->inst[s] && eval->sums[s])) && (!pseudo || pseudo->inst[s]), -2,
                  who + "null pointer");
+        if (image) VR_CHECK(image->y_img[s] && image->v_img[s], -2, who + "null pointer");
         if (waves) VR_CHECK(L[s] >= hop, -2, who + "wave shorter than one hop");
         else VR_CHECK(T_in[s] > 0, -2, who + "empty spectrogram");
         if (waves) VR_CHECK(L[s] / hop < (1LL << 30), -2, who + "wave too long");
         if (pcm) {
             check_pcm(in_on_dev ? in[s] : nullptr, pcm_channels[s], pcm_fmt[s], who);
-            if (out_on_dev) VR_CHECK(reinterpret_cast<uintptr_t>(y[s]) % 2 == 0 && reinterpret_cast<uintptr_t>(v[s]) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
+            if (out_on_dev && stems) VR_CHECK(reinterpret_cast<uintptr_t>(y[s]) % 2 == 0 && reinterpret_cast<uintptr_t>(v[s]) % 2 == 0, -2, who + "the int16 outputs are not 2-byte aligned");
         }
         Song& g = sg[s];
         g.T = waves ? 1 + (int)(L[s] / hop) : T_in[s];
@@ -1842,6 +1847,9 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
     std::vector<PseudoSeg> pst(pseudo ? (size_t)n_songs : 0);
     std::vector<float*> stage_pinst(pseudo ? (size_t)n_songs : 0);
     PseudoSeg* pst_d = nullptr;
+    std::vector<ImgSeg> imt(image ? (size_t)n_songs : 0);
+    ImgSeg* imt_d = nullptr;
+    float* img_range = nullptr;
     double pcm_bytes = 0.0;
     auto in_bytes = [&](int s) {
         return pcm ? (size_t)L[s] * pcm_channels[s] * pcm_sample_bytes(pcm_fmt[s]) : (waves ? (size_t)2 * L[s] : sg[s].spec_f) * sizeof(float);
@@ -1855,6 +1863,20 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
         if (pcm) pin_d = static_cast<PcmIn*>(A.alloc(sizeof(PcmIn) * n_songs));
         if (eval) evt_d = static_cast<WaveEval*>(A.alloc(sizeof(WaveEval) * n_songs));
         if (pseudo) pst_d = static_cast<PseudoSeg*>(A.alloc(sizeof(PseudoSeg) * n_songs));
+        if (image) {                                  // one job per song beside the table: two pictures, their partials and ranges
+            imt_d = static_cast<ImgSeg*>(A.alloc(sizeof(ImgSeg) * n_songs));
+            img_range = A.allocf((size_t)n_songs * 4);
+            for (int s = 0; s < n_songs; ++s) {
+                const size_t bytes = (size_t)3 * bins * sg[s].T;
+                ImgSeg& e = imt[s];
+                e = ImgSeg{};
+                e.T = sg[s].T;
+                e.img[0] = out_on_dev ? image->y_img[s] : static_cast<uint8_t*>(A.alloc(bytes));
+                e.img[1] = out_on_dev ? image->v_img[s] : static_cast<uint8_t*>(A.alloc(bytes));
+                e.part = static_cast<float4*>(A.alloc(sizeof(float4) * kImgParts));
+                e.range = img_range + 4 * s;
+            }
+        }
         part = static_cast<unsigned long long*>(A.alloc((size_t)n_songs * 2 * bins * 16));
         aff = A.allocf((size_t)n_songs * 4);
         mask = A.allocf((size_t)E * 2 * bins * W);
@@ -1956,6 +1978,7 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
             for (int s = 0; s < n_songs; ++s)
                 VR_HIP(hipMemcpyAsync(stage_pinst[s], pseudo->inst[s], in_bytes(s), hipMemcpyHostToDevice, stream));
     }
+    if (image) VR_HIP(hipMemcpyAsync(imt_d, imt.data(), sizeof(ImgSeg) * n_songs, hipMemcpyHostToDevice, stream));
     // ---- front end
     if (pseudo) {                           // Y and D = X - Y; X itself is never written (waves: tiled, checked above)
         if (waves) launch_stft_pseudo_many(plan, tab_d, pst_d, n_songs, max_T, (double)sum_L, (double)sum_T, stream);
@@ -2011,15 +2034,24 @@ void Model::separate_run(int n_songs, const float* const* in, bool in_on_dev, co
             if (sg[s].windows)
                 VR_HIP(hipMemcpyAsync(eval->sums[s], evt[s].sums, (size_t)sg[s].windows * 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
     } else if (waves && tiled) {
-        for (int which = 0; which < 2; ++which)
+        for (int which = 0; which < 2 && stems; ++which)
             launch_istft_masked_many(plan, tab_d, n_songs, max_T, (double)sum_T, mask, W, tta, is_complex, wgt, which, stream, pcm);
-    } else {
+    } else if (stems) {
         launch_apply_mask_many(tab_d, n_songs, max_T, bins, mask, W, tta, is_complex, wgt, stream);
         if (waves)
             for (int s = 0; s < n_songs; ++s) {
                 launch_istft(plan, tab[s].y, hop, sg[s].T, frames, tab[s].y_wave, stream);
                 launch_istft(plan, tab[s].v, hop, sg[s].T, frames, tab[s].v_wave, stream);
             }
+    }
+    if (image) {                            // the pictures of the very stems, from the resident spectrogram and mask: no stem is stored for them
+        launch_stem_image_many(tab_d, imt_d, n_songs, max_T, bins, mask, W, tta, is_complex, wgt, (double)sum_T, stream);
+        if (!out_on_dev)
+            for (int s = 0; s < n_songs; ++s) {
+                VR_HIP(hipMemcpyAsync(image->y_img[s], imt[s].img[0], (size_t)3 * bins * sg[s].T, hipMemcpyDeviceToHost, stream));
+                VR_HIP(hipMemcpyAsync(image->v_img[s], imt[s].img[1], (size_t)3 * bins * sg[s].T, hipMemcpyDeviceToHost, stream));
+            }
+        if (image->ranges) VR_HIP(hipMemcpyAsync(image->ranges, img_range, (size_t)n_songs * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
     if (!out_on_dev && stems)
         for (int s = 0; s < n_songs; ++s) {

@@ -1023,6 +1023,221 @@ __device__ __forceinline__ float unord32(unsigned o) {
 }
 
 
+// ---- spectrogram images (vr_spec_image*, vr_separate_*_img) ---------------------------------------------------------
+// lib/spec_utils.py:34-57 in float32 as numpy evaluates it: y = log10(|z|^2 + 1e-8) or angle(z) (a float input: s for |z|, s for the
+// angle), lo = min y, r = max (y - lo) = max y - lo (the float32 difference is monotone in y), pixel = uint8((y - lo) * (255 / r)),
+// truncated.  Every step is one float32 operation of its own: nothing here is contracted into a fused multiply-add.
+template <bool PHASE>
+__device__ __forceinline__ float img_y(float2 z) {
+#pragma clang fp contract(off)
+    if constexpr (PHASE) return atan2f(z.y, z.x);
+    const float a = hypotf(z.x, z.y);               // np.abs of a complex64
+    const float q = a * a;
+    return log10f(q + 1e-8f);
+}
+template <bool PHASE>
+__device__ __forceinline__ float img_y(float s) {
+#pragma clang fp contract(off)
+    if constexpr (PHASE) return s;
+    const float q = s * s;
+    return log10f(q + 1e-8f);
+}
+// r == 0 (a constant input; the reference casts NaN there): zero.  The clamps only keep a NaN or Inf input inside a byte.
+__device__ __forceinline__ unsigned img_pixel(float y, float lo, float scale, bool flat) {
+#pragma clang fp contract(off)
+    const float d = y - lo;
+    const float s = d * scale;
+    return flat ? 0u : (unsigned)fminf(fmaxf(s, 0.f), 255.f);
+}
+
+// What rides behind the arguments of the image forms of mag_pad_kernel (the range pass) and apply_mask_kernel (the write pass).
+struct SpecImage { int channels, mode, nparts; };            // SRC = const ImgSeg: stored spectrograms, `src` is the job table
+struct StemImage { const ImgSeg* jobs; int nparts; };        // SRC = const SongSeg: the two stems of every song, one job per song
+
+// The two sources.  load(p, y): y[stem][channel] of pixel p = bin * T + frame; consecutive lanes take consecutive p, so every row of
+// either channel is read along t.
+template <bool CPLX>
+struct SpecSource {                                          // complex64 (CPLX) or float32 planes [C][bins * T]
+    static constexpr int NS = 1;
+    const void* src; long long plane;
+    template <bool PHASE, int C>
+    __device__ __forceinline__ void load(int p, float (&y)[2][2]) const {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if constexpr (CPLX) y[0][c] = img_y<PHASE>(static_cast<const float2*>(src)[c * plane + p]);
+            else y[0][c] = img_y<PHASE>(static_cast<const float*>(src)[c * plane + p]);
+        }
+    }
+};
+template <bool CPLX>
+struct StemSource {                                          // the float2 apply_mask_kernel would store: the same expressions in the same order
+    static constexpr int NS = 2;
+    const float2* spec; const float* ma; const float* mb; const float* wgt; int W, T, bins;
+    template <bool PHASE, int C>
+    __device__ __forceinline__ void load(int p, float (&y)[2][2]) const {
+        const int k = p / T, t = p - k * T;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const long long row = (long long)c * bins + k;
+            const float2 z = spec[row * T + t];
+            float2 ys, vs;
+            if constexpr (CPLX) {
+                const float2 mc = final_mask(reinterpret_cast<const float2*>(ma), W, reinterpret_cast<const float2*>(mb), W, 0, wgt, row, t);
+                ys = cmul(mc, z);
+                vs = cmul(make_float2(1.f - mc.x, -mc.y), z);
+            } else {
+                float m = ma[row * W + t];
+                if (mb) m = (m + mb[row * W + t]) * 0.5f;
+                if (wgt) m += wgt[t] * (1.f - m);
+                ys = make_float2(m * z.x, m * z.y);
+                const float im = 1.f - m;
+                vs = make_float2(im * z.x, im * z.y);
+            }
+            y[0][c] = img_y<PHASE>(ys);
+            y[1][c] = img_y<PHASE>(vs);
+        }
+    }
+};
+
+// (min, max) of four values over the workgroup's 256 threads: the xor butterfly per wave, then the four waves through LDS.  Minimum and
+// maximum do not depend on the order, so two calls give the same bits; no atomics.
+__device__ __forceinline__ float4 img_reduce(float4 v, float4* red) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        v.x = fminf(v.x, __shfl_xor(v.x, off, 64)); v.y = fmaxf(v.y, __shfl_xor(v.y, off, 64));
+        v.z = fminf(v.z, __shfl_xor(v.z, off, 64)); v.w = fmaxf(v.w, __shfl_xor(v.w, off, 64));
+    }
+    __syncthreads();                                 // (red may still be read from an earlier call)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float4 a = red[0], b = red[1], c = red[2], d = red[3];
+    return make_float4(fminf(fminf(a.x, b.x), fminf(c.x, d.x)), fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y)),
+                       fminf(fminf(a.z, b.z), fminf(c.z, d.z)), fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w)));
+}
+
+// The range pass, grid (parts, job), 256 threads: workgroup b takes the chunks b, b + parts, ... of kImgChunk pixels and leaves its
+// (min, max) per stem in part[b]; a workgroup past its job's last chunk leaves (+inf, -inf).
+template <bool PHASE, int C, class F>
+__device__ __forceinline__ void img_range_pass(const F& f, long long pixels, float4* __restrict__ part) {
+    __shared__ float4 red[4];
+    float4 m = make_float4(INFINITY, -INFINITY, INFINITY, -INFINITY);
+    for (long long base = (long long)blockIdx.x * kImgChunk; base < pixels; base += (long long)gridDim.x * kImgChunk) {
+#pragma unroll
+        for (int i = 0; i < kImgChunk / 256; ++i) {
+            const long long p = base + i * 256 + threadIdx.x;
+            if (p < pixels) {
+                float y[2][2];
+                f.template load<PHASE, C>((int)p, y);
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    m.x = fminf(m.x, y[0][c]); m.y = fmaxf(m.y, y[0][c]);
+                    if constexpr (F::NS == 2) { m.z = fminf(m.z, y[1][c]); m.w = fmaxf(m.w, y[1][c]); }
+                }
+            }
+        }
+    }
+    m = img_reduce(m, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+
+// The write pass, grid (pixels of the longest job / (kImgWriteChunks * kImgChunk), job), 256 threads.  Every workgroup reduces the
+// job's `nparts` partials again (a few KB from L2), so that no third launch stands between the passes; the first one leaves (lo, r) per
+// stem in `range`.  A chunk's pixels are computed with the lanes along t, laid out as bytes in LDS and stored as dwords: a chunk begins
+// at a multiple of 4 bytes of the picture whatever T is, so only a picture whose own address is no multiple of 4, and the last bytes
+// of the last chunk, go out as bytes.
+template <bool PHASE, int C, class F>
+__device__ __forceinline__ void img_write_pass(const F& f, long long pixels, const float4* __restrict__ part, int nparts, float* __restrict__ range,
+                                               uint8_t* const (&img)[2]) {
+    constexpr int NS = F::NS, PB = C == 2 ? 3 : 1;
+    __shared__ float4 red[4];
+    __shared__ unsigned tile[NS][kImgChunk * PB / 4];
+    float4 m = make_float4(INFINITY, -INFINITY, INFINITY, -INFINITY);
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        const float4 q = part[i];
+        m = make_float4(fminf(m.x, q.x), fmaxf(m.y, q.y), fminf(m.z, q.z), fmaxf(m.w, q.w));
+    }
+    m = img_reduce(m, red);
+    float lo[2], r[2], scale[2];
+    {
+#pragma clang fp contract(off)
+        lo[0] = m.x; r[0] = m.y - m.x;
+        lo[1] = m.z; r[1] = m.w - m.z;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        scale[s] = (float)(255.0 / (double)r[s]);   // the float32 quotient: a double quotient rounds to it exactly (53 >= 2 * 24 + 2)
+        if (blockIdx.x == 0 && threadIdx.x == 0) { range[2 * s] = lo[s]; range[2 * s + 1] = r[s]; }
+    }
+    for (int cc = 0; cc < kImgWriteChunks; ++cc) {
+        const long long base = ((long long)blockIdx.x * kImgWriteChunks + cc) * kImgChunk;
+        if (base >= pixels) break;                   // (uniform per workgroup)
+#pragma unroll
+        for (int i = 0; i < kImgChunk / 256; ++i) {
+            const int e = i * 256 + threadIdx.x;
+            if (base + e < pixels) {
+                float y[2][2];
+                f.template load<PHASE, C>((int)(base + e), y);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    uint8_t* tb = reinterpret_cast<uint8_t*>(tile[s]);
+                    const unsigned l = img_pixel(y[s][0], lo[s], scale[s], !(r[s] > 0.f));
+                    if constexpr (C == 2) {
+                        const unsigned rr = img_pixel(y[s][1], lo[s], scale[s], !(r[s] > 0.f));
+                        tb[3 * e] = (uint8_t)(l > rr ? l : rr); tb[3 * e + 1] = (uint8_t)l; tb[3 * e + 2] = (uint8_t)rr;
+                    } else {
+                        tb[e] = (uint8_t)l;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        const long long left = pixels - base;
+        const int nbytes = (int)(left < kImgChunk ? left : kImgChunk) * PB;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            uint8_t* out = img[s] + base * PB;
+            const uint8_t* tb = reinterpret_cast<const uint8_t*>(tile[s]);
+            if ((reinterpret_cast<uintptr_t>(out) & 3) == 0) {
+                for (int d = threadIdx.x; d < nbytes / 4; d += 256) reinterpret_cast<unsigned*>(out)[d] = tile[s][d];
+                for (int b = (nbytes & ~3) + threadIdx.x; b < nbytes; b += 256) out[b] = tb[b];
+            } else {
+                for (int b = threadIdx.x; b < nbytes; b += 256) out[b] = tb[b];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Either pass of either source: the job (blockIdx.y), its source, then the pass.  A job of a separation call is a magnitude picture.
+template <bool CPLX, bool WRITE>
+__device__ __forceinline__ void spec_image_pass(const ImgSeg* __restrict__ jobs, int bins, const SpecImage a) {
+    const ImgSeg jb = jobs[blockIdx.y];
+    const long long pixels = (long long)bins * jb.T;
+    const SpecSource<CPLX> f{jb.src, pixels};
+    uint8_t* const img[2] = {jb.img[0], jb.img[1]};
+    auto run = [&](auto phase, auto ch) {
+        if constexpr (WRITE) img_write_pass<decltype(phase)::value, decltype(ch)::value>(f, pixels, jb.part, a.nparts, jb.range, img);
+        else img_range_pass<decltype(phase)::value, decltype(ch)::value>(f, pixels, jb.part);
+    };
+    using std::integral_constant;
+    if (a.mode) { if (a.channels == 2) run(integral_constant<bool, true>{}, integral_constant<int, 2>{}); else run(integral_constant<bool, true>{}, integral_constant<int, 1>{}); }
+    else { if (a.channels == 2) run(integral_constant<bool, false>{}, integral_constant<int, 2>{}); else run(integral_constant<bool, false>{}, integral_constant<int, 1>{}); }
+}
+template <bool CPLX, bool WRITE>
+__device__ __forceinline__ void stem_image_pass(const SongSeg* __restrict__ songs, int bins, const float* __restrict__ ma, int W, const float* __restrict__ mb,
+                                                const float* __restrict__ wgt, const StemImage a) {
+    const SongSeg sg = songs[blockIdx.y];
+    const ImgSeg jb = a.jobs[blockIdx.y];
+    ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
+    if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
+    if (wgt) wgt += sg.frame0;
+    const StemSource<CPLX> f{sg.spec, ma, mb, wgt, W, sg.T, bins};
+    const long long pixels = (long long)bins * sg.T;
+    uint8_t* const img[2] = {jb.img[0], jb.img[1]};
+    if constexpr (WRITE) img_write_pass<false, 2>(f, pixels, jb.part, a.nparts, jb.range, img);
+    else img_range_pass<false, 2>(f, pixels, jb.part);
+}
+
 // One workgroup per (channel, bin) row: |X| into the padded crop source (row-contiguous loads and stores, no 64-bit
 // division per element) and the row's two maxima into part[row] -- no atomics; coef_affine_kernel reduces the 2 x bins
 // partials.  (Round 1: 16 k same-address atomics and a flat 64-bit index made this 190 us for 34 MB.)
@@ -1035,11 +1250,22 @@ __device__ __forceinline__ float unord32(unsigned o) {
 // item n of the dense network input mag_pad [n][nin][max_bin][cropsize] -- |X| / c (PACK false) or the planes [re L, re R, im L, im R]
 // of X / c (PACK true), zero outside [0, T_song).  It stands for memset + mag_pad + materialize (+ pack) of the one-song path and for
 // its strided crop view, so that a device batch can hold crops of several songs and of both TTA passes.
-template <bool PACK, class SRC = const float2, bool GATHER = false>
+// IM (at most one type): the range pass of the spectrogram images -- min and max of y per job, grid (parts, job).
+// SpecImage (SRC = const ImgSeg, PACK = complex64 input): `spec` is the job table.  StemImage (SRC = const SongSeg, PACK = complex
+// mask): the two stems of every song; mag_pad / Wpad / pad_l / scale carry the call's mask, its row pitch, whether the TTA pass is
+// averaged in, and the merge_artifacts weights, as apply_mask_kernel takes them.
+template <bool PACK, class SRC = const float2, bool GATHER = false, class... IM>
 __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, int T, float* __restrict__ mag_pad,
                                                       int Wpad, int pad_l, unsigned long long* __restrict__ part, int bins,
-                                                      const float2* __restrict__ scale) {
-    if constexpr (GATHER) {
+                                                      const float2* __restrict__ scale, IM... im) {
+    static_assert(sizeof...(IM) <= 1 && !(sizeof...(IM) && GATHER), "the image forms are forms of their own");
+    if constexpr (kHasType<SpecImage, IM...>) {
+        spec_image_pass<PACK, false>(spec, bins, pcm_first(im...));
+        return;
+    } else if constexpr (kHasType<StemImage, IM...>) {
+        stem_image_pass<PACK, false>(spec, bins, mag_pad, Wpad, pad_l ? mag_pad : nullptr, reinterpret_cast<const float*>(scale), pcm_first(im...));
+        return;
+    } else if constexpr (GATHER) {
         const int max_bin = Wpad, cropsize = T;
         const int c = blockIdx.x / max_bin, k = blockIdx.x - c * max_bin, n = blockIdx.y;
         const int2 cr = reinterpret_cast<const int2*>(part)[n];
@@ -1095,7 +1321,7 @@ __global__ __launch_bounds__(256) void mag_pad_kernel(SRC* __restrict__ spec, in
         T = sg.T;
         sp = sg.spec + (long long)row * T;
         row += blockIdx.y * 2 * bins;
-    } else {
+    } else if constexpr (sizeof...(IM) == 0) {
         sp = spec + (long long)row * T;
         dst = mag_pad + (long long)row * Wpad + pad_l;
     }
@@ -1351,13 +1577,20 @@ __device__ __forceinline__ void pseudo_diff(const SongSeg* __restrict__ songs, c
 
 // CPLX: complex64 masks, complex products (final_mask: TTA average and merge_artifacts blend of a complex mask)
 // PS (at most one type, SRC = const SongSeg): PseudoSpec / PseudoRows = the pseudo back ends above, PseudoDiff = the elementwise pair front
-// end -- under this kernel's name, like every form of this file, so that the launch profiler's report keeps one name per stage
+// end -- under this kernel's name, like every form of this file, so that the launch profiler's report keeps one name per stage;
+// SpecImage (SRC = const ImgSeg) / StemImage = the write pass of the spectrogram images
 template <bool CPLX, class SRC = const float2, class... PS>
 __global__ void apply_mask_kernel(SRC* __restrict__ src, int bins, int T, const float* __restrict__ ma,
                                   int Wa, const float* __restrict__ mb, int Wb, int shift, const float* __restrict__ wgt,
                                   float2* __restrict__ y, float2* __restrict__ v, PS... ps) {
-    static_assert(sizeof...(PS) <= 1 && (sizeof...(PS) == 0 || kSongTable<SRC>), "the pseudo forms are song-table forms");
-    if constexpr (kHasType<PseudoDiff, PS...>) {
+    static_assert(sizeof...(PS) <= 1 && (sizeof...(PS) == 0 || kSongTable<SRC> || kHasType<SpecImage, PS...>), "the pseudo forms are song-table forms");
+    if constexpr (kHasType<SpecImage, PS...>) {      // the write pass of the spectrogram images (CPLX: complex64 input), src = the job table
+        spec_image_pass<CPLX, true>(src, bins, pcm_first(ps...));
+        return;
+    } else if constexpr (kHasType<StemImage, PS...>) {
+        stem_image_pass<CPLX, true>(src, bins, ma, Wa, mb, wgt, pcm_first(ps...));
+        return;
+    } else if constexpr (kHasType<PseudoDiff, PS...>) {
         pseudo_diff(src, pcm_first(ps...).ps);
         return;
     } else if constexpr (sizeof...(PS) == 1) {
@@ -1371,7 +1604,7 @@ __global__ void apply_mask_kernel(SRC* __restrict__ src, int bins, int T, const 
         ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
         if (mb) mb += (long long)(CPLX ? 2 : 1) * sg.mcol_b;
         if (wgt) wgt += sg.frame0;
-    } else {
+    } else if constexpr (sizeof...(PS) == 0) {
         spec = src;
     }
     const long long total = 2LL * bins * T;
@@ -1604,6 +1837,102 @@ void launch_eval_sums(const FFTPlan& pl, const SongSeg* songs, const WaveEval* e
     VR_LAUNCH((istft_tile_kernel<false, const SongSeg, const WaveEval*, WindowSums>), dim3((unsigned)max_windows, n_songs), dim3(256), 0, st, pl, songs, 0, 0,
               (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, ev, 0LL);
     VR_HIP(hipGetLastError());
+}
+
+// ---- spectrogram images: the launches -------------------------------------------------------------------------------
+static int image_parts(long long max_pixels) {
+    const long long chunks = (max_pixels + kImgChunk - 1) / kImgChunk;
+    return (int)(chunks < kImgParts ? chunks : kImgParts);
+}
+static unsigned image_write_blocks(long long max_pixels) {
+    const long long per = (long long)kImgChunk * kImgWriteChunks;
+    return (unsigned)((max_pixels + per - 1) / per);
+}
+
+void launch_spec_image_many(const ImgSeg* jobs, int n, int channels, int bins, int max_T, double sum_T, bool cplx, int mode, hipStream_t st) {
+    const long long max_pixels = (long long)bins * max_T;
+    const SpecImage a{channels, mode, image_parts(max_pixels)};
+    const double in_bytes = (double)channels * bins * sum_T * (cplx ? 8.0 : 4.0);
+    const dim3 rg(a.nparts, n), wg(image_write_blocks(max_pixels), n);
+    prof_note(0.0, in_bytes);
+    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const ImgSeg, false, SpecImage>), rg, dim3(256), 0, st, jobs, 0, (float*)nullptr, 0, 0, (unsigned long long*)nullptr, bins, (const float2*)nullptr, a);
+    else VR_LAUNCH((mag_pad_kernel<false, const ImgSeg, false, SpecImage>), rg, dim3(256), 0, st, jobs, 0, (float*)nullptr, 0, 0, (unsigned long long*)nullptr, bins, (const float2*)nullptr, a);
+    VR_HIP(hipGetLastError());
+    prof_note(0.0, in_bytes + (channels == 2 ? 3.0 : 1.0) * bins * sum_T);
+    if (cplx) VR_LAUNCH((apply_mask_kernel<true, const ImgSeg, SpecImage>), wg, dim3(256), 0, st, jobs, bins, 0, (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, (float2*)nullptr, (float2*)nullptr, a);
+    else VR_LAUNCH((apply_mask_kernel<false, const ImgSeg, SpecImage>), wg, dim3(256), 0, st, jobs, bins, 0, (const float*)nullptr, 0, (const float*)nullptr, 0, 0, (const float*)nullptr, (float2*)nullptr, (float2*)nullptr, a);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_stem_image_many(const SongSeg* songs, const ImgSeg* jobs, int n_songs, int max_T, int bins, const float* mask, int W, int tta, bool cplx,
+                            const float* wgt, double sum_T, hipStream_t st) {
+    const long long max_pixels = (long long)bins * max_T;
+    const StemImage a{jobs, image_parts(max_pixels)};
+    // per pixel and channel: the spectrogram value and the mask (both passes of a TTA call); the write pass adds two 3-byte pixels
+    const double in_bytes = 2.0 * bins * sum_T * (8.0 + (cplx ? 8.0 : 4.0) * (tta ? 2 : 1));
+    const dim3 rg(a.nparts, n_songs), wg(image_write_blocks(max_pixels), n_songs);
+    const float* mb = tta ? mask : nullptr;
+    float* m = const_cast<float*>(mask);             // (mag_pad_kernel's slot is its output in the other forms; this one only reads it)
+    const float2* w2 = reinterpret_cast<const float2*>(wgt);
+    prof_note(0.0, in_bytes);
+    if (cplx) VR_LAUNCH((mag_pad_kernel<true, const SongSeg, false, StemImage>), rg, dim3(256), 0, st, songs, 0, m, W, tta, (unsigned long long*)nullptr, bins, w2, a);
+    else VR_LAUNCH((mag_pad_kernel<false, const SongSeg, false, StemImage>), rg, dim3(256), 0, st, songs, 0, m, W, tta, (unsigned long long*)nullptr, bins, w2, a);
+    VR_HIP(hipGetLastError());
+    prof_note(0.0, in_bytes + 6.0 * bins * sum_T);
+    if (cplx) VR_LAUNCH((apply_mask_kernel<true, const SongSeg, StemImage>), wg, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, (float2*)nullptr, (float2*)nullptr, a);
+    else VR_LAUNCH((apply_mask_kernel<false, const SongSeg, StemImage>), wg, dim3(256), 0, st, songs, bins, 0, mask, W, mb, W, 0, wgt, (float2*)nullptr, (float2*)nullptr, a);
+    VR_HIP(hipGetLastError());
+}
+
+// vr_spec_image_many: n stored spectrograms -> n pictures.  No handle: one workspace for the call, the null stream.
+void spec_image_many_api(int device, int n, const void* const* specs, bool on_dev, int channels, int bins, const int* T, bool cplx, int mode,
+                         uint8_t* const* imgs, bool out_on_dev, float* ranges) {
+    struct Buf { char* p = nullptr; ~Buf() { hipFree(p); } } buf;
+    DeviceGuard dev_guard(device);
+    const size_t el = cplx ? 8 : 4, pb = channels == 2 ? 3 : 1;
+    std::vector<ImgSeg> tab((size_t)n);
+    std::vector<char*> stage_in((size_t)n, nullptr), stage_out((size_t)n, nullptr);
+    ImgSeg* tab_d = nullptr;
+    float* range_d = nullptr;
+    int max_T = 0;
+    double sum_T = 0;
+    for (int pass = 0; pass < 2; ++pass) {           // the same carve twice: once for the total, once for the pointers
+        size_t off = 0;
+        auto carve = [&](size_t bytes) { const size_t a = (off + 255) & ~size_t(255); off = a + bytes; return buf.p ? buf.p + a : nullptr; };
+        tab_d = reinterpret_cast<ImgSeg*>(carve(sizeof(ImgSeg) * n));
+        range_d = reinterpret_cast<float*>(carve(sizeof(float) * 2 * n));
+        for (int i = 0; i < n; ++i) {
+            const size_t pixels = (size_t)bins * T[i];
+            ImgSeg& e = tab[i];
+            e = ImgSeg{};
+            e.T = T[i];
+            stage_in[i] = on_dev ? nullptr : carve(pixels * channels * el);
+            stage_out[i] = out_on_dev ? nullptr : carve(pixels * pb);
+            e.src = on_dev ? specs[i] : stage_in[i];
+            e.img[0] = out_on_dev ? imgs[i] : reinterpret_cast<uint8_t*>(stage_out[i]);
+            e.part = reinterpret_cast<float4*>(carve(sizeof(float4) * kImgParts));
+            e.range = range_d + 2 * i;
+            if (!pass) { max_T = std::max(max_T, T[i]); sum_T += T[i]; }
+        }
+        if (pass) break;
+        const size_t need = off + 256;
+        if (hipMalloc(reinterpret_cast<void**>(&buf.p), need) != hipSuccess) {
+            (void)hipGetLastError();
+            buf.p = nullptr;
+            throw Error(-4, "spec image: hipMalloc of " + std::to_string(need) + " bytes of workspace failed");
+        }
+    }
+    hipStream_t st = nullptr;
+    if (!on_dev)
+        for (int i = 0; i < n; ++i)
+            VR_HIP(hipMemcpyAsync(stage_in[i], specs[i], (size_t)bins * T[i] * channels * el, hipMemcpyHostToDevice, st));
+    VR_HIP(hipMemcpyAsync(tab_d, tab.data(), sizeof(ImgSeg) * n, hipMemcpyHostToDevice, st));
+    launch_spec_image_many(tab_d, n, channels, bins, max_T, sum_T, cplx, mode, st);
+    if (!out_on_dev)
+        for (int i = 0; i < n; ++i)
+            VR_HIP(hipMemcpyAsync(imgs[i], stage_out[i], (size_t)bins * T[i] * pb, hipMemcpyDeviceToHost, st));
+    if (ranges) VR_HIP(hipMemcpyAsync(ranges, range_d, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipStreamSynchronize(st));
 }
 
 // ---- streaming separation (vr_stream_*): the STREAM instantiations -----------------------------------------------------------------

@@ -41,12 +41,14 @@ class Separator(object):
         """inference.py:83-102 (incl. the complex lexicographic-max normaliser of :87,94)."""
         return self._run(X_spec, True)
 
-    def separate_wave(self, wave, tta=False):
+    def separate_wave(self, wave, tta=False, images=False):
         """Whole inference.py:147-176 pipeline in one device-resident call.
 
         wave: numpy [2, L] float32 (host) or a torch cuda tensor [2, L]; returns two arrays / tensors
-        [2, hop*(L//hop)] (instruments, vocals) on the same side.
+        [2, hop*(L//hop)] (instruments, vocals) on the same side.  images=True: (y, v, y_img, v_img) -- see separate_wave_many.
         """
+        if images:
+            return self.separate_wave_many([wave], tta=tta, images=True)[0]
         h = self.model._need_handle()
         hop = self.model.hop_length
         self.model.eval()
@@ -94,9 +96,12 @@ class Separator(object):
             int(self.cropsize), native.ptr_table([a.ctypes.data for a in ys]), native.ptr_table([a.ctypes.data for a in vs]), 0))
         return list(zip(ys, vs))
 
-    def separate_wave_many(self, waves, tta=False):
+    def separate_wave_many(self, waves, tta=False, images=False):
         """separate_wave for a list of waves [2, L_s] in ONE library call: returns [(y_wave, v_wave), ...].  A list of numpy arrays
-        gives numpy arrays; a list of torch cuda tensors (all on the model's GPU) stays on the device, as in separate_wave."""
+        gives numpy arrays; a list of torch cuda tensors (all on the model's GPU) stays on the device, as in separate_wave.
+        images=True (vr_separate_wave_many_img): [(y_wave, v_wave, y_img, v_img), ...] -- the same stems, and per song what
+        image.spectrogram_to_image gives for the instruments and the vocals spectrogram of separate_many, uint8 [bins, T, 3], formed
+        on the device from the resident spectrogram and mask (no stem spectrogram is stored or copied for them)."""
         h = self.model._need_handle()
         hop = self.model.hop_length
         waves = list(waves)
@@ -129,9 +134,25 @@ class Separator(object):
             vs = [np.empty_like(a) for a in ys]
             addr = lambda seq: native.ptr_table([a.ctypes.data for a in seq])
         # (an empty torch tensor has a null data_ptr; the library reports waves shorter than one hop before it reads any pointer table entry)
+        if images:
+            yi, vi = self._image_pairs([1 + n // hop for n in lens], waves[0].device if on_dev else None)
+            native.check(native.lib().vr_separate_wave_many_img(h.h, len(waves), addr(waves), 1 if on_dev else 0, L, self._flags(tta),
+                                                                int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0,
+                                                                addr(yi), addr(vi), None))
+            return list(zip(ys, vs, yi, vi))
         native.check(native.lib().vr_separate_wave_many(h.h, len(waves), addr(waves), 1 if on_dev else 0, L, self._flags(tta),
                                                         int(self.batchsize), int(self.cropsize), addr(ys), addr(vs), 1 if on_dev else 0))
         return list(zip(ys, vs))
+
+    def _image_pairs(self, Ts, device):
+        """the pictures of an images=True call: per song two uint8 [bins, T, 3], cuda tensors on `device` or numpy arrays (device None)"""
+        bins = self.model.output_bin
+        if device is not None:
+            import torch
+            yi = [torch.empty((bins, T, 3), dtype=torch.uint8, device=device) for T in Ts]
+            return yi, [torch.empty_like(a) for a in yi]
+        yi = [np.empty((bins, T, 3), dtype=np.uint8) for T in Ts]
+        return yi, [np.empty_like(a) for a in yi]
 
     def evaluate_wave_many(self, mixes, insts, tta=False, window=44100, stems=False):
         """separate_wave_many that also scores every song against its true instruments, in ONE library call (vr_evaluate_wave_many).
@@ -324,17 +345,19 @@ class Separator(object):
                 native.check(L.vr_pseudo_many(h.h, N, table(mixes), table(insts), dev, (ct.c_int * N)(*lens), *args, table(outs), dev))
         return outs
 
-    def separate_pcm(self, raw, tta=False):
+    def separate_pcm(self, raw, tta=False, images=False):
         """separate_wave with the file's bytes at both ends: raw = audio.RawPcm (audio.read_wav_raw: PCM16 / 24 / 32 or float32 frames of
         1 or 2 channels) -> (instruments, vocals) as int16 [hop*(frames//hop), 2], ready for audio.write_pcm16 -- exactly
         clip(rint(separate_wave(decoded).T * 32767)).  The STFT kernel decodes, the masked iSTFT encodes; no host pass over the
-        samples.  numpy bytes give numpy arrays; a cuda uint8 tensor gives cuda int16 tensors.  Needs pcm_available()."""
-        return self._separate_pcm([raw], tta, one=True)[0]
+        samples.  numpy bytes give numpy arrays; a cuda uint8 tensor gives cuda int16 tensors.  Needs pcm_available().
+        images=True: (y, v, y_img, v_img), the pictures as separate_wave_many(images=True) gives them for the decoded samples."""
+        return self._separate_pcm([raw], tta, one=not images, images=images)[0]
 
-    def separate_pcm_many(self, raws, tta=False):
+    def separate_pcm_many(self, raws, tta=False, images=False):
         """separate_pcm for a list of RawPcm in ONE library call (vr_separate_pcm_many): formats and channel counts may differ per song;
-        each result is what separate_pcm returns for that song alone up to the batching bar of separate_wave_many."""
-        return self._separate_pcm(raws, tta, one=False)
+        each result is what separate_pcm returns for that song alone up to the batching bar of separate_wave_many.
+        images=True (vr_separate_pcm_many_img): [(y, v, y_img, v_img), ...]."""
+        return self._separate_pcm(raws, tta, one=False, images=images)
 
     def pcm_available(self):
         """Whether this model's handle has the sample-format kernels (vr_pcm_available): they are forms of the frame-tiled STFT / iSTFT,
@@ -344,7 +367,7 @@ class Separator(object):
         native.check(native.lib().vr_pcm_available(self.model._need_handle().h, native.ctypes.byref(ok)))
         return bool(ok.value)
 
-    def _separate_pcm(self, raws, tta, one):
+    def _separate_pcm(self, raws, tta, one, images=False):
         from .spec_utils import _pcm_bytes
         h = self.model._need_handle()
         hop = self.model.hop_length
@@ -369,6 +392,14 @@ class Separator(object):
             vs = [np.empty_like(a) for a in ys]
             addr = lambda a: a.ctypes.data
         ct, N = native.ctypes, len(raws)
+        if images:
+            yi, vi = self._image_pairs([1 + n // hop for n in lens], dev if on_dev else None)
+            native.check(native.lib().vr_separate_pcm_many_img(
+                h.h, N, native.ptr_table([p[1] for p in prepared]), 1 if on_dev else 0, (ct.c_int64 * N)(*lens),
+                (ct.c_int * N)(*[r.channels for r in raws]), (ct.c_int * N)(*[r.fmt for r in raws]), self._flags(tta), int(self.batchsize),
+                int(self.cropsize), native.ptr_table([addr(a) for a in ys]), native.ptr_table([addr(a) for a in vs]), 1 if on_dev else 0,
+                native.ptr_table([addr(a) for a in yi]), native.ptr_table([addr(a) for a in vi]), None), native.VRArgumentError)
+            return list(zip(ys, vs, yi, vi))
         if one:
             native.check(native.lib().vr_separate_pcm(h.h, prepared[0][1], 1 if on_dev else 0, lens[0], raws[0].channels, raws[0].fmt,
                                                       self._flags(tta), int(self.batchsize), int(self.cropsize), addr(ys[0]), addr(vs[0]),
@@ -838,7 +869,7 @@ def build_parser():
     p.add_argument('--tta', '-t', action='store_true')
     p.add_argument('--postprocess', '-p', action='store_true')
     p.add_argument('--is_complex', action='store_true')              # a checkpoint of CascadedNet(..., is_complex=True)
-    p.add_argument('--output_image', '-I', action='store_true')      # accepted for command-line compatibility; no image is written
+    p.add_argument('--output_image', '-I', action='store_true')      # also write {base}_Instruments.jpg / _Vocals.jpg (.png without Pillow); not with --stream
     p.add_argument('--output_dir', '-o', type=str, default="")
     p.add_argument('--songs_per_call', type=int, default=8)          # --input naming a directory: songs per separate_wave_many call (--stream: files streamed together)
     p.add_argument('--stream', action='store_true')                  # read, separate and write block by block (Separator.stream)
@@ -850,20 +881,27 @@ def build_parser():
 
 def main(argv=None):
     """inference.py main() (inference.py:107-185) with the same flags; decoding / resampling / WAV writing come from
-    vocal_remover_amd.audio (no librosa / soundfile), everything numeric from the library.  --output_image is the only
-    flag not carried over (cv2 image dump, SURVEY section 2: out of scope)."""
+    vocal_remover_amd.audio (no librosa / soundfile), everything numeric from the library.  --output_image writes the two
+    spectrogram pictures of inference.py:180-185 from the separation call itself (Separator.*(images=True), image.imwrite: no cv2); only
+    --stream does not write them -- the pictures' minimum and maximum are those of the whole song, which no block knows."""
     import os
 
     import torch
 
-    from . import audio, nets
+    from . import audio, image, nets
     args = build_parser().parse_args(argv)
     if args.reference is not None and (args.stream or os.path.isdir(args.input)):
         raise SystemExit('--reference scores one file separated offline: not with --stream, not with a directory')
 
-    if args.output_image:
-        print('--output_image: not written by this entry point (spectrogram_to_image + cv2 are outside the MI355X path); run the '
-              "reference's inference.py through vocal-remover_amd/run.py to get the image dumps")
+    images = args.output_image and not args.stream and args.reference is None
+    if args.output_image and not images:
+        print('--output_image: no picture is written with --stream or --reference (a picture is scaled by the minimum and maximum of '
+              'the whole song, which a stream does not know block by block); separate the file offline to get the pictures')
+    want = {'images': True} if images else {}           # (asked for only where wanted: the calls without -I are the calls they were)
+    image_ext = '.jpg'
+    if images and not image.have_jpeg():
+        image_ext = '.png'
+        print('--output_image: Pillow is not installed, so the pictures are written as .png')
     device = torch.device('cuda:{}'.format(max(args.gpu, 0)))
     model = nets.CascadedNet(args.n_fft, args.hop_length, 32, 128, is_complex=args.is_complex)
     model.load_state_dict(torch.load(args.pretrained_model, map_location='cpu'))
@@ -899,6 +937,11 @@ def main(argv=None):
         audio.write_pcm16('{}{}_Instruments.wav'.format(output_dir, basename), _host(y_pcm), sr)
         audio.write_pcm16('{}{}_Vocals.wav'.format(output_dir, basename), _host(v_pcm), sr)
 
+    def write_images(path, y_img, v_img):
+        basename = os.path.splitext(os.path.basename(path))[0]
+        image.imwrite('{}{}_Instruments{}'.format(output_dir, basename, image_ext), _host(y_img))
+        image.imwrite('{}{}_Vocals{}'.format(output_dir, basename, image_ext), _host(v_img))
+
     if args.stream and os.path.isdir(args.input):
         for group in expand_inputs(args.input, args.songs_per_call):      # the group's files advance together, block by block
             names = [os.path.splitext(os.path.basename(path))[0] for path in group]
@@ -925,26 +968,34 @@ def main(argv=None):
     if not os.path.isdir(args.input):
         raw = load_raw(args.input)
         if raw is not None:
-            y_pcm, v_pcm = sp.separate_pcm(raw, tta=args.tta)
-            write_pcm(args.input, y_pcm, v_pcm, raw.sr)
+            res = sp.separate_pcm(raw, tta=args.tta, **want)
+            write_pcm(args.input, res[0], res[1], raw.sr)
+            if images:
+                write_images(args.input, res[2], res[3])
             return 0
         X, sr = load(args.input)
-        y_wave, v_wave = sp.separate_wave(X, tta=args.tta)  # STFT -> separate -> iSTFT x2 in one device-resident call
-        write(args.input, y_wave, v_wave, sr)
+        res = sp.separate_wave(X, tta=args.tta, **want)  # STFT -> separate -> iSTFT x2 (-> the pictures) in one device-resident call
+        write(args.input, res[0], res[1], sr)
+        if images:
+            write_images(args.input, res[2], res[3])
         return 0
     for group in expand_inputs(args.input, args.songs_per_call):
         raws = [(path, load_raw(path)) for path in group]
         fresh = [(path, raw) for path, raw in raws if raw is not None]
         if fresh:                                # the group's files the device decodes share one call; the others the old one
-            for (path, raw), (y_pcm, v_pcm) in zip(fresh, sp.separate_pcm_many([raw for _, raw in fresh], tta=args.tta)):
-                write_pcm(path, y_pcm, v_pcm, raw.sr)
+            for (path, raw), res in zip(fresh, sp.separate_pcm_many([raw for _, raw in fresh], tta=args.tta, **want)):
+                write_pcm(path, res[0], res[1], raw.sr)
+                if images:
+                    write_images(path, res[2], res[3])
         group = [path for path, raw in raws if raw is None]
         if not group:
             continue
         loaded = [load(path) for path in group]
-        stems = sp.separate_wave_many([X for X, _ in loaded], tta=args.tta)      # the crops of the group's songs share device batches
-        for path, (_, sr), (y_wave, v_wave) in zip(group, loaded, stems):
-            write(path, y_wave, v_wave, sr)
+        stems = sp.separate_wave_many([X for X, _ in loaded], tta=args.tta, **want)      # the crops of the group's songs share device batches
+        for path, (_, sr), res in zip(group, loaded, stems):
+            write(path, res[0], res[1], sr)
+            if images:
+                write_images(path, res[2], res[3])
     return 0
 
 
