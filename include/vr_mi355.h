@@ -410,20 +410,28 @@ int vr_pair_rows_many(vr_handle h, int n, const float* const* mix, const float* 
  * and returns every output sample that is final: *n_out per channel, possibly 0, at y / v [2][capacity] (channel pitch = capacity).
  * A capacity below what the call returns is VR_ERR_BAD_ARGUMENT, reported before anything is consumed; vr_last_error() names the size
  * needed (vr_stream_plan computes it: samples_out after minus before).  wave: planar [2][n].
- * vr_stream_info: lookahead_samples = (roi + offset) * hop, the samples that must have arrived before the first output sample;
+ * vr_stream_info: lookahead_samples = (roi + offset) * hop (VR_STREAM_POSTPROCESS: (roi + offset + 161) * hop), the samples that must have arrived before the first output sample;
  * block_samples = roi * hop, the step in which crops become ready; state_bytes = the device memory the stream holds: an input tail,
  * a ring of spectrogram frames, a mask ring per pass, one hop of overlap-add carry per stem and channel, the normaliser.  It depends
  * on (n_fft, cropsize, batchsize, flags) and not on how much audio has passed; the handle's staging arena holds one push (see
  * vr_arena_bytes).  A push larger than batchsize * roi frames is worked through in steps of that size.
+ * VR_STREAM_POSTPROCESS: the stream applies spec_utils.merge_artifacts (thres 0.05, min_range 64, fade_size 32, as vr_separate_wave's
+ * postprocess) to its mask.  The blend weight of frame t is final once the mask minima of the frames below t + 161 are known (161 =
+ * 3 * fade_size + min_range + 1), so such a stream returns its samples 161 frames later -- lookahead_samples = (roi + offset + 161) * hop --
+ * keeps that many more frames and mask columns plus a ring of minima, a ring of weights and five ints, and a steady push adds two small
+ * launches (the minima, the walk over them); at flush everything left is final.  The concatenated stems are what vr_separate_wave with
+ * postprocess returns, at the same bar.  One deviation: a song with no frame above the threshold is an error offline (the reference's
+ * IndexError); a stream has returned samples before that could be known, never raises for it, and blends nothing.  With a given
+ * normaliser it combines with every other flag and entry point; VR_STREAM_MEASURE (no samples) and the running normaliser refuse it.
  * Errors (VR_ERR_BAD_ARGUMENT, before the device is touched): training mode (at open and at every push), hop_length != n_fft / 2,
- * VR_STREAM_POSTPROCESS (merge_artifacts needs whole-song runs), an unknown flag, push or flush after flush, fewer than hop_length
+ * VR_STREAM_POSTPROCESS with VR_STREAM_MEASURE or coef 0, an unknown flag, push or flush after flush, fewer than hop_length
  * samples in all at flush ("wave shorter than one hop", as vr_separate_wave).  Other calls on the handle between two pushes are
  * allowed (the stream keeps nothing in the handle's arenas); a stream must be closed before its handle is destroyed.  A push that
  * fails half way (a HIP error) leaves the stream unusable: close it. */
 typedef struct vr_stream_s* vr_stream;
 #define VR_STREAM_TTA         1   /* second pass shifted by roi/2, masks averaged (separate_tta)                  */
 #define VR_STREAM_MEASURE     2   /* no network, no output: only accumulate the normaliser                        */
-#define VR_STREAM_POSTPROCESS 4   /* refused: see above                                                           */
+#define VR_STREAM_POSTPROCESS 4   /* merge_artifacts with 161 frames of look-ahead: see above                     */
 /* y / v of vr_stream_push, vr_stream_flush and vr_stream_push_many are int16 [capacity][2] interleaved (pass them cast to float*):
  * the encoding of vr_separate_pcm of the very floats the stream would have returned.  capacity and n_out still count samples per
  * channel; the input stays planar float.  All streams of one vr_stream_push_many call must agree on it (VR_ERR_BAD_ARGUMENT).   */
@@ -441,7 +449,8 @@ int vr_stream_flush(vr_stream s, float* y, float* v, int out_on_device, int64_t 
  * on the handle may come between.  What the streams share is the launches: the call goes in rounds, round r = step r of every stream
  * that still has input; per round one STFT over all streams, the ready crops of all streams and both passes in shared device batches
  * of `batchsize` (independent of the batchsize a stream was opened with, which sizes its rings and its step; <= 0: the largest among
- * the streams), one masked iSTFT per stem; per call one drain.  Plain and VR_STREAM_TTA streams may be mixed; VR_CREATE_COMPLEX
+ * the streams), one masked iSTFT per stem; per call one drain.  Plain, VR_STREAM_TTA and VR_STREAM_POSTPROCESS streams may be mixed
+ * (the two postprocess launches of a round serve all its streams); VR_CREATE_COMPLEX
  * handles are supported.  VR_STREAM_MEASURE streams and running-normaliser streams (coef 0) are REFUSED here: the running normaliser
  * cuts its steps per crop, which stays on vr_stream_push.
  * Checked before the device is touched, every stream left as it was (VR_ERR_BAD_ARGUMENT, vr_last_error() starts "stream <k>: "):
@@ -478,6 +487,11 @@ int vr_stream_close(vr_stream s);
  * VR_ERR_BAD_ARGUMENT: hop * 2 != n_fft, cropsize <= 2 * offset, samples_in < 0, flushed with samples_in < hop. */
 int vr_stream_plan(int n_fft, int hop, int cropsize, int offset, int tta, int64_t samples_in, int flushed, int64_t* frames_ready,
                    int64_t* crops_ready /*[2]*/, int64_t* samples_out);
+/* The same with the flags of vr_stream_open in place of `tta` (VR_STREAM_TTA and VR_STREAM_POSTPROCESS matter; an unknown flag is
+ * VR_ERR_BAD_ARGUMENT).  With VR_STREAM_POSTPROCESS and before the flush, samples_out counts the frames 161 below the final masks:
+ * it lags vr_stream_plan's by 161 * hop once positive; flushed, both give hop * (samples_in / hop). */
+int vr_stream_plan_ex(int n_fft, int hop, int cropsize, int offset, int flags, int64_t samples_in, int flushed, int64_t* frames_ready,
+                      int64_t* crops_ready /*[2]*/, int64_t* samples_out);
 /* Device bytes the handle holds for staging (inputs, outputs, masks of one call) and for the network's workspace. */
 int vr_arena_bytes(vr_handle h, int64_t* staging_bytes, int64_t* workspace_bytes);
 
@@ -730,9 +744,16 @@ int vr_debug_conv2d_backward(vr_handle h, const float* x, int N, int Cin, int H,
  * weight [T] (lib/spec_utils.py:64-87), incl. the reference's IndexError / ValueError cases.        */
 int vr_debug_merge_artifacts_weight(const float* frame_min, int T, float thres, int min_range, int fade_size,
                                     float* weight_out);
+/* The same weights from the incremental form a VR_STREAM_POSTPROCESS stream runs (csrc/stream_post.h, the code the device walk runs; the
+ * constants are fixed: 0.05 / 64 / 32), no GPU involved.  The minima are taken in steps: step k ends in front of frame cuts[k]
+ * (0 < cuts[0] <= cuts[1] <= ... <= T), one more step takes the rest, then the flush.  The weights live in a ring of 161 + (the largest
+ * step) entries; a frame is copied to weight_out at the moment it is declared final: after a step that ends in front of frame h the
+ * frames below h - 161, at the flush all.  final_after_out [n_cuts + 1] (may be NULL): the frames declared final after each of the
+ * n_cuts steps, then T.  All minima at or below the threshold give zeros, no error. */
+int vr_debug_stream_post_weight(const float* frame_min, int T, const int* cuts, int n_cuts, float* weight_out, int* final_after_out);
 /* One kernel of the training path or of the signal front end in isolation, host pointers in and out (csrc/debug.hip lists
  * the names, their dims / float parameters / inputs / outputs): bn_backward, lstm, upsample, pool, thin, head_loss, rows,
- * adam, wire, signal_norm, signal_mask, wave_eval.                                                                  */
+ * adam, wire, signal_norm, signal_mask, wave_eval, stream_post.                                                        */
 int vr_debug_kernel(vr_handle h, const char* name, const int64_t* dims, int ndims, const float* fparams, int nfparams,
                     const float* const* inputs, int ninputs, float* const* outputs, int noutputs);
 /* Record intermediate activations of the next vr_forward and read them back (post-activation). */

@@ -491,6 +491,18 @@ int vr_stream_plan(int n_fft, int hop, int cropsize, int offset, int tta, int64_
     });
 }
 
+int vr_stream_plan_ex(int n_fft, int hop, int cropsize, int offset, int flags, int64_t samples_in, int flushed, int64_t* frames_ready,
+                      int64_t* crops_ready, int64_t* samples_out) {
+    return guard([&] {
+        VR_CHECK(!(flags & ~15), VR_ERR_BAD_ARGUMENT, "unknown vr_stream_open flag");
+        const vr::StreamSchedule p = vr::stream_schedule(n_fft, hop, cropsize, offset, (flags & VR_STREAM_TTA) != 0, samples_in, flushed != 0,
+                                                         (flags & VR_STREAM_POSTPROCESS) != 0);
+        if (frames_ready) *frames_ready = p.frames;
+        if (crops_ready) { crops_ready[0] = p.crops[0]; crops_ready[1] = p.crops[1]; }
+        if (samples_out) *samples_out = p.samples_out;
+    });
+}
+
 int vr_stream_open(vr_handle h, int cropsize, int batchsize, int flags, double coef_re, double coef_im, vr_stream* out) {
     if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
     *out = nullptr;
@@ -601,7 +613,7 @@ int vr_stream_info(vr_stream s, int64_t* lookahead_samples, int64_t* block_sampl
     NEED_STREAM(s);
     return guard([&] {
         const vr::Model& m = s->h->m;
-        if (lookahead_samples) *lookahead_samples = (int64_t)(s->st->roi + m.offset) * m.hop;
+        if (lookahead_samples) *lookahead_samples = (int64_t)(s->st->roi + m.offset + (s->st->post ? vr::kStreamPostDelay : 0)) * m.hop;
         if (block_samples) *block_samples = (int64_t)s->st->roi * m.hop;
         if (state_bytes) *state_bytes = (int64_t)s->st->state_bytes;
     });
@@ -1188,6 +1200,35 @@ int vr_debug_merge_artifacts_weight(const float* frame_min, int T, float thres, 
         std::vector<float> f(frame_min, frame_min + T), w;
         vr::merge_artifacts_weight(f, w, thres, min_range, fade_size);
         std::memcpy(weight_out, w.data(), (size_t)T * sizeof(float));
+    });
+}
+
+int vr_debug_stream_post_weight(const float* frame_min, int T, const int* cuts, int n_cuts, float* weight_out, int* final_after_out) {
+    return guard([&] {
+        VR_CHECK(frame_min && weight_out && T > 0 && n_cuts >= 0 && (cuts || n_cuts == 0), VR_ERR_BAD_ARGUMENT, "null argument");
+        int step = 0;
+        for (int k = 0, at = 0; k <= n_cuts; ++k) {
+            const int to = k < n_cuts ? cuts[k] : T;
+            VR_CHECK(to >= at && to <= T && to > 0, VR_ERR_BAD_ARGUMENT, "cuts must ascend inside (0, T]");
+            step = std::max(step, to - at);
+            at = to;
+        }
+        const int RW = vr::kStreamPostDelay + step;
+        std::vector<float> ring((size_t)RW, 0.f);
+        vr::StreamPostState st{};
+        int final_n = 0;
+        auto declare = [&](int n) { for (; final_n < n; ++final_n) weight_out[final_n] = ring[(size_t)(final_n % RW)]; };
+        for (int k = 0; k <= n_cuts; ++k) {
+            const int to = k < n_cuts ? cuts[k] : T;
+            vr::stream_post_advance(st, frame_min + st.h, to - st.h, ring.data(), RW);
+            if (k < n_cuts) {
+                declare(std::max(0, to - vr::kStreamPostDelay));
+                if (final_after_out) final_after_out[k] = final_n;
+            }
+        }
+        vr::stream_post_finish(st, ring.data(), RW);
+        declare(T);
+        if (final_after_out) final_after_out[n_cuts] = final_n;
     });
 }
 

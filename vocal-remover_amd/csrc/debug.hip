@@ -137,6 +137,14 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                                                        mask_b[2 bins][Wb]|null, wgt[T]|null                y_wave, v_wave [2][hop (T-1)] (fused masked
 //                                                        (cplx: complex64 masks)                             iSTFT; hop == n_fft / 2 handles only)
 //                 bins = n_fft / 2 + 1 of the handle; frame_min (no wgt), apply_mask and the masked iSTFT with `which` 0 and 1
+// stream_post     T,RW,cut...           -                fmin[T]                                             weight[T], final_after[cuts + 1] (counts as floats),
+//                                                                                                            ring[RW] as the last step left it
+//                 The walk a VR_STREAM_POSTPROCESS stream runs (the rows == 0 form of frame_min_kernel's stream instantiation, stream_post.h's
+//                 code on the device) on given minima, in steps: step k ends in front of frame cut[k] (ascending, in
+//                 (0, T]), one more takes the rest and flushes.  Per step the minima are placed in a ring of RW entries (RW 0: 161 + the
+//                 largest step, the least that works), a StreamSeg table of one entry is sent and the walk launched; a frame's weight is
+//                 read back from the weight ring when it is declared final (below cut - 161; at the flush all), as
+//                 vr_debug_stream_post_weight does on the host.  Both rings sit between guard bands (error -3).
 // wave_eval       T,Wa,Wb,shift,has_b,  -                spec, mask_a, mask_b|null, wgt|null as signal_mask,  y_wave, v_wave [2][hop (T-1)] (store 0: left as they were
 //                 has_wgt,cplx,window,                   mix[2][L], inst[2][L]                               allocated, zero), sums[windows][4] float64 (in a float32
 //                 store,L                                                                                    buffer of twice the count), info[2] = (S, windows)
@@ -1292,6 +1300,50 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         launch_adam(p.p, g.p, m.p, v.p, (long long)n, dp[0], dp[1], dp[2], dp[3], (long long)dp[5], dp[4], st);
         VR_HIP(hipStreamSynchronize(st));
         p.download(out[0]); m.download(out[1]); v.download(out[2]);
+    } else if (name == "stream_post") {
+        need(2, 0, 1, 2);
+        const int T = (int)dims[0], n_cuts = ndims - 2;
+        VR_CHECK(T > 0 && in[0] && out[0] && out[1], -2, "stream_post: need T > 0, the minima and two outputs");
+        int step = 0;
+        for (int k = 0, at = 0; k <= n_cuts; ++k) {
+            const int to = k < n_cuts ? (int)dims[2 + k] : T;
+            VR_CHECK(to >= at && to <= T && to > 0, -2, "stream_post: cuts must ascend inside (0, T]");
+            step = std::max(step, to - at);
+            at = to;
+        }
+        const int RW = dims[1] ? (int)dims[1] : kStreamPostDelay + step;
+        VR_CHECK(RW >= kStreamPostDelay + step, -2, "stream_post: the ring must hold 161 + the largest step");
+        GuardedBuf fring(nullptr, (size_t)RW), wring(nullptr, (size_t)RW);
+        DevBuf state(8), table((sizeof(StreamSeg) + 3) / 4);
+        VR_HIP(hipMemset(fring.p(), 0, (size_t)RW * 4));
+        VR_HIP(hipMemset(wring.p(), 0, (size_t)RW * 4));
+        VR_HIP(hipDeviceSynchronize());
+        std::vector<float> host_ring((size_t)RW, 0.f);
+        int final_n = 0;
+        auto declare = [&](int n) {
+            if (n <= final_n) return;
+            VR_HIP(hipMemcpy(host_ring.data(), wring.p(), (size_t)RW * 4, hipMemcpyDeviceToHost));
+            for (; final_n < n; ++final_n) out[0][final_n] = host_ring[(size_t)(final_n % RW)];
+        };
+        for (int k = 0, at = 0; k <= n_cuts; ++k) {
+            const int to = k < n_cuts ? (int)dims[2 + k] : T;
+            for (int t = at; t < to; ++t) VR_HIP(hipMemcpy(fring.p() + t % RW, in[0] + t, 4, hipMemcpyHostToDevice));
+            StreamSeg g{};
+            g.fmin_ring = fring.p(); g.wgt_ring = wring.p(); g.post = reinterpret_cast<StreamPostState*>(state.p); g.RW = RW;
+            g.fm_lo = at; g.fm_hi = to; g.post_flush = k == n_cuts;
+            VR_HIP(hipMemcpy(table.p, &g, sizeof g, hipMemcpyHostToDevice));
+            launch_stream_post(reinterpret_cast<const StreamSeg*>(table.p), 1, 0, (double)(to - at), true, false, false, n_fft / 2 + 1, st);
+            VR_HIP(hipStreamSynchronize(st));
+            if (k < n_cuts) {
+                declare(std::max(0, to - kStreamPostDelay));
+                out[1][k] = (float)final_n;
+            }
+            at = to;
+        }
+        declare(T);
+        out[1][n_cuts] = (float)final_n;
+        VR_CHECK(fring.intact() && wring.intact(), -3, "stream_post: a store outside a ring");
+        if (nout >= 3 && out[2]) wring.download(out[2]);
     } else if (name == "wire") {
         need(1, 0, 1, 1);
         const size_t n = (size_t)dims[0];

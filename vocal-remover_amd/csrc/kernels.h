@@ -1,5 +1,6 @@
 // Launch wrappers for the non-MFMA kernels of libvr_mi355.so (definitions in *.hip).
 #pragma once
+#include "stream_post.h"
 #include "vr_common.h"
 
 namespace vr {
@@ -586,6 +587,14 @@ struct StreamSeg {
     float* y_wave;
     float* v_wave;
     long long out_pitch;
+    // --postprocess (fmin_ring null: not a postprocess stream, and the masked iSTFT blends nothing): the minima of the
+    // frames [fm_lo, fm_hi), whose masks became final in this step, go to fmin_ring[t % RW]; the walk (stream_post.h) takes them from
+    // there, moves `post` on and writes the merge_artifacts weight of frame t at wgt_ring[t % RW]; post_flush: the stream ends with frame
+    // fm_hi - 1.  The masked iSTFT reads wgt_ring for its frames, which lie kStreamPostDelay below fm_hi (or, flushed, anywhere below it).
+    float* fmin_ring;
+    float* wgt_ring;
+    StreamPostState* post;
+    int RW, fm_lo, fm_hi, post_flush;
 };
 bool stream_tiled_available(const FFTPlan& pl, int hop);
 // seg: a device table of n_seg entries; new_frames = the largest count of new frames among them, new_samples / sum_* only size the profiler's note
@@ -601,5 +610,10 @@ void launch_stream_gather(const StreamSeg* seg, const int2* crops, int count, bo
 // segments = the largest count of output segments among the n_seg entries (an entry with none is skipped); sum_segments, tta: profiler's note
 void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int segments, double sum_segments, bool cplx, bool tta, int which,
                          hipStream_t st, bool pcm16 = false);         // pcm16: y_wave / v_wave are int16 [capacity][2]
+// the postprocess entries of the table (the others are skipped): the minima of their frames [fm_lo, fm_hi) -- post_frames = the largest
+// count among them, sum_frames: profiler's note; no launch when 0 -- then the walk, one workgroup per entry (walk false: no entry has
+// new minima or a flush).  Both are forms of frame_min_kernel.
+void launch_stream_post(const StreamSeg* seg, int n_seg, int post_frames, double sum_frames, bool walk, bool cplx, bool tta, int bins,
+                        hipStream_t st);
 
 }  // namespace vr

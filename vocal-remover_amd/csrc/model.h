@@ -105,9 +105,11 @@ void merge_artifacts_weight(const std::vector<float>& fmin, std::vector<float>& 
 // when the frame count becomes the offline 1 + L / hop.  Crop i of pass 0 covers the frames [i roi - offset, (i+1) roi + offset) and
 // gives the mask of [i roi, (i+1) roi); pass 1 (tta) is the same list shifted by -roi/2.  A crop runs once every frame of its window
 // is ready, at flush the offline count of make_padding.  Frame t is final when the crops of both passes that hold its mask have run;
-// with `done` final frames, hop * (done - 1) output samples are final.
-struct StreamSchedule { long long frames, crops[2], done, samples_out; };
-StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed);
+// with `out_done` frames out, hop * (out_done - 1) output samples are final.  out_done = done, or for a --postprocess stream (DESIGN.md
+// section 6w) the frames whose merge_artifacts weight is final too: every frame once flushed, else done - kStreamPostDelay (0 below 2: a
+// lone first frame gives no sample).
+struct StreamSchedule { long long frames, crops[2], done, samples_out, out_done; };
+StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed, int postprocess = 0);
 
 // Evaluation against the true stems (vr_evaluate_wave*): what Model::separate_run needs beyond a wave-level call.
 // inst[s]: song s's true instruments [2][L[s]], where the mixtures are (host or device); sums[s]: HOST [windows][4] doubles;
@@ -126,13 +128,14 @@ struct EvalPlan { long long samples, windows; };
 EvalPlan evaluate_plan(int hop, long long L, long long window);
 
 // One streaming session of a handle (vr_stream_*): everything that outlives a push.  Device state is one slab whose size depends on
-// (n_fft, cropsize, batchsize, tta) only.
+// (n_fft, cropsize, batchsize, tta, postprocess) only.
 struct StreamState {
     int cropsize = 0, bs = 0, roi = 0, R = 0, RM = 0, chunk_frames = 0;
-    bool tta = false, measure = false, running = false, pcm16 = false;
+    bool tta = false, measure = false, running = false, pcm16 = false, post = false;
     bool flushed = false, broken = false;
     long long samples = 0, tail_base = 0;
-    long long frames = 0, crops[2] = {0, 0}, done = 0;
+    long long frames = 0, crops[2] = {0, 0}, done = 0;   // done: frames whose mask is final
+    long long out_done = 0;                              // frames given out (= done unless post)
     char* slab = nullptr; size_t state_bytes = 0;
     float* tail[2] = {nullptr, nullptr}; int tail_cur = 0;
     float2* ring = nullptr;
@@ -140,6 +143,11 @@ struct StreamState {
     float* carry[2] = {nullptr, nullptr}; int carry_cur = 0;
     unsigned* stats = nullptr;                           // launch_mag_pad's layout: 16-byte header + 2 * bins rows of partial maxima
     float* aff = nullptr;                                // 1 / c as the crop gather reads it
+    // post: per-frame mask minima and merge_artifacts weights, frame t at [t % RW], and the state of the walk (stream_post.h)
+    int RW = 0;
+    float* fmin_ring = nullptr;
+    float* wgt_ring = nullptr;
+    StreamPostState* post_state = nullptr;
     double coef[2] = {0.0, 0.0};                         // MEASURE: the normaliser, valid after flush
 };
 
@@ -579,7 +587,7 @@ private:
     // round.  A step of one stream is stream_step_plan (takes the block in, asks stream_schedule what is ready, checks the rings and
     // fills the StreamSeg), its share of the round's launches, and stream_step_commit (flips the tail / carry buffers and moves the
     // stream's counters on).
-    struct StreamStepPlan { StreamSeg seg; StreamSchedule p; int new_frames, segments; bool emit; };
+    struct StreamStepPlan { StreamSeg seg; StreamSchedule p; int new_frames, segments, post_frames; bool emit, post_walk; };
     struct StreamCrop { int entry, pass; long long idx; };          // crop idx of a pass of the stream at table entry `entry`
     long long stream_check(const StreamState& S, const std::string& who, const float* wave, long long n, bool flush, const float* y,
                            const float* v, bool out_on_dev, long long capacity) const;     // -> samples per channel the call returns

@@ -2086,9 +2086,11 @@ EvalPlan evaluate_plan(int hop, long long L, long long window) {
 // arena holds one push.  A push is cut into steps of at most `chunk_frames` new frames, so the rings have a fixed size; a step is
 // one STFT of the new frames, one statistics launch (running normaliser / MEASURE), the ready crops through run_crop_chunks, and one
 // masked iSTFT per stem over the frames that became final.  One executor runs them, stream_run: vr_stream_push gives it one stream,
-// vr_stream_push_many a round of streams.
+// vr_stream_push_many a round of streams.  A --postprocess stream gives its frames out kStreamPostDelay behind
+// their masks (`out_done` behind `done`): in front of the iSTFT a step takes the minima of the mask columns that became final and walks
+// them into merge_artifacts weights (stream_post.h), both in rings beside the others.
 // =====================================================================================================
-StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed) {
+StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int tta, long long samples_in, int flushed, int postprocess) {
     VR_CHECK(n_fft >= 2 && hop > 0 && hop * 2 == n_fft, -2, "streaming needs hop_length == n_fft / 2 (the frame-tiled STFT / iSTFT kernels exist only there)");
     VR_CHECK(offset >= 0 && cropsize - 2 * offset > 0, -2, "cropsize must exceed 2*offset");
     VR_CHECK(samples_in >= 0, -2, "negative sample count");
@@ -2105,7 +2107,9 @@ StreamSchedule stream_schedule(int n_fft, int hop, int cropsize, int offset, int
         p.crops[1] = (tta && p.frames + half >= offset) ? (p.frames - offset + half) / roi : 0;
         p.done = tta ? std::max(0LL, std::min(p.crops[0] * roi, p.crops[1] * roi - half)) : p.crops[0] * roi;
     }
-    p.samples_out = (long long)hop * std::max(0LL, p.done - 1);
+    p.out_done = p.done;
+    if (postprocess && !flushed) p.out_done = p.done - kStreamPostDelay >= 2 ? p.done - kStreamPostDelay : 0;
+    p.samples_out = (long long)hop * std::max(0LL, p.out_done - 1);
     return p;
 }
 
@@ -2125,7 +2129,7 @@ StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double c
     // ---- arguments: nothing here touches the device
     VR_CHECK(!(flags & ~15), -2, "unknown vr_stream_open flag");
     VR_CHECK(!((flags & 8) && (flags & 2)), -2, "VR_STREAM_PCM16_OUT on a VR_STREAM_MEASURE stream: it returns no samples");
-    VR_CHECK(!(flags & 4), -2, "a stream cannot run --postprocess: merge_artifacts looks at runs of frames over the whole song; use vr_separate_wave");
+    VR_CHECK(!((flags & 4) && (flags & 2)), -2, "VR_STREAM_POSTPROCESS on a VR_STREAM_MEASURE stream: it returns no samples to post-process");
     VR_CHECK(!training, -2, "a stream runs in eval mode (inference.py:52); call vr_set_mode(h, 0) first");
     VR_CHECK(hop * 2 == n_fft && stream_tiled_available(plan, hop), -2,
              "streaming needs hop_length == n_fft / 2 (the frame-tiled STFT / iSTFT kernels exist only there)");
@@ -2134,18 +2138,24 @@ StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double c
     const bool tta = flags & 1, measure = (flags & 2) != 0;
     const bool running = !measure && coef_re == 0.0 && coef_im == 0.0;
     VR_CHECK(!(running && tta), -2, "a tta stream needs the normaliser (coef): the running normaliser exists for plain streams only");
+    VR_CHECK(!(running && (flags & 4)), -2, "a postprocess stream needs the normaliser (coef): with the running normaliser a step ends with "
+                                           "every crop window, and the look-ahead of merge_artifacts is not worked out for it");
     VR_CHECK(measure || (std::isfinite(coef_re) && std::isfinite(coef_im)), -2, "coef must be finite");
     std::unique_ptr<StreamState> S(new StreamState);
     S->cropsize = cropsize; S->tta = tta; S->measure = measure; S->running = running;
     S->pcm16 = (flags & 8) != 0;                // y / v are int16 [capacity][2]: the last kernel's store encodes
+    S->post = (flags & 4) != 0;                 // merge_artifacts with kStreamPostDelay frames of look-ahead
     S->bs = batchsize > 0 ? batchsize : 8;               // (a stream never sees "all crops": <= 0 means 8)
     const int roi = cropsize - 2 * offset, bins = output_bin, E = is_complex ? 2 : 1;
     S->roi = roi;
     S->chunk_frames = S->bs * roi;
     // frames still needed before a step reach back less than cropsize + roi / 2, a step adds at most chunk_frames (+ 1 at flush)
-    S->R = cropsize + roi / 2 + S->chunk_frames + 4;
+    // (post: frames leave kStreamPostDelay behind their masks, so both rings keep that many more)
+    S->R = cropsize + roi / 2 + S->chunk_frames + 4 + (S->post ? kStreamPostDelay : 0);
     // mask columns not yet final before a step: at most roi / 2; a step adds at most bs + 1 crops per pass, the flush offset / roi + 3
-    S->RM = roi * (std::max(S->bs + 1, offset / roi + 3) + 2);
+    S->RM = roi * (std::max(S->bs + 1, offset / roi + 3) + 2 + (S->post ? (kStreamPostDelay + roi - 1) / roi : 0));
+    // minima and weights: from the oldest frame not yet out to the newest final mask, which is what the frame ring spans
+    S->RW = S->post ? S->R : 0;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t a = (off + 255) & ~size_t(255); off = a + bytes; return a; };
     const size_t tail_b = (size_t)2 * 2 * hop * 4, ring_b = (size_t)2 * bins * S->R * 8, mask_b = (size_t)E * 2 * bins * S->RM * 4;
@@ -2158,6 +2168,8 @@ StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double c
         if (tta) o_mask[1] = take(mask_b);
         o_carry[0] = take(carry_b); o_carry[1] = take(carry_b);
     }
+    size_t o_fmin = 0, o_wgt = 0, o_post = 0;
+    if (S->post) { o_fmin = take((size_t)S->RW * 4); o_wgt = take((size_t)S->RW * 4); o_post = take(sizeof(StreamPostState)); }
     S->state_bytes = off;
 
     DeviceGuard dev_guard(device);
@@ -2171,6 +2183,10 @@ StreamState* Model::stream_open(int cropsize, int batchsize, int flags, double c
             S->mask[0] = reinterpret_cast<float*>(b + o_mask[0]);
             S->mask[1] = tta ? reinterpret_cast<float*>(b + o_mask[1]) : nullptr;
             S->carry[0] = reinterpret_cast<float*>(b + o_carry[0]); S->carry[1] = reinterpret_cast<float*>(b + o_carry[1]);
+        }
+        if (S->post) {                          // (the zeroed slab is the walk's state before frame 0)
+            S->fmin_ring = reinterpret_cast<float*>(b + o_fmin); S->wgt_ring = reinterpret_cast<float*>(b + o_wgt);
+            S->post_state = reinterpret_cast<StreamPostState*>(b + o_post);
         }
         VR_HIP(hipMemsetAsync(S->slab, 0, off, stream));
         // the statistics rows as an empty reduction leaves them (the zero padding is part of the reduced array); a given normaliser
@@ -2216,17 +2232,18 @@ Model::StreamStepPlan Model::stream_step_plan(StreamState& S, const StreamStepIO
     const long long prev_frames = S.frames;
     S.samples += o.blk_n;
     StreamStepPlan sp{};
-    const StreamSchedule p = stream_schedule(n_fft, hop, cropsize, offset, S.tta, S.samples, final);
+    const StreamSchedule p = stream_schedule(n_fft, hop, cropsize, offset, S.tta, S.samples, final, S.post);
     sp.p = p;
     VR_CHECK(p.frames < (1LL << 31) - 2 * cropsize, -2, "stream too long");
     // what the rings must still hold: the oldest frame a coming crop or the iSTFT reads, the oldest mask column not yet final
-    long long oldest = std::min(S.done, S.crops[0] * roi - offset);
+    long long oldest = std::min(S.out_done, S.crops[0] * roi - offset);
     if (S.tta) oldest = std::min(oldest, S.crops[1] * roi - offset - roi / 2);
     if (S.measure) oldest = prev_frames;        // (only the statistics pass reads the new frames)
     VR_CHECK(p.frames - std::max(0LL, oldest) <= S.R, -4, "stream frame ring overflow (planning bug)");
     if (!S.measure) {
-        VR_CHECK(p.crops[0] * roi - S.done / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
-        if (S.tta) VR_CHECK(p.crops[1] * roi - (S.done + roi / 2) / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+        VR_CHECK(p.crops[0] * roi - S.out_done / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+        if (S.tta) VR_CHECK(p.crops[1] * roi - (S.out_done + roi / 2) / roi * roi <= S.RM, -4, "stream mask ring overflow (planning bug)");
+        if (S.post) VR_CHECK(p.done - S.out_done <= S.RW, -4, "stream weight ring overflow (planning bug)");
         VR_CHECK((p.crops[0] - S.crops[0]) + (p.crops[1] - S.crops[1]) <= 2 * (S.RM / roi), -4, "stream crop list overflow (planning bug)");
     }
     StreamSeg& g = sp.seg;
@@ -2238,13 +2255,19 @@ Model::StreamStepPlan Model::stream_step_plan(StreamState& S, const StreamStepIO
     g.ring = S.ring; g.R = S.R; g.t_new = (int)prev_frames; g.T = (int)p.frames;
     g.mask_a = S.mask[0]; g.mask_b = S.tta ? S.mask[1] : nullptr; g.RM = S.RM; g.shift = roi / 2;
     g.aff = S.aff;
-    sp.emit = !S.measure && p.done > S.done;
-    g.carried = S.done > 0;
-    g.t_out = S.done > 0 ? (int)S.done - 1 : 0; g.t_done = (int)p.done;
+    sp.emit = !S.measure && p.out_done > S.out_done;
+    g.carried = S.out_done > 0;
+    g.t_out = S.out_done > 0 ? (int)S.out_done - 1 : 0; g.t_done = (int)p.out_done;
     g.carry_in = S.carry[S.carry_cur]; g.carry_out = S.carry[S.carry_cur ^ 1];
     g.y_wave = o.y ? o.y + o.out_off : nullptr; g.v_wave = o.v ? o.v + o.out_off : nullptr; g.out_pitch = o.out_pitch;
     sp.new_frames = (int)(p.frames - prev_frames);
     sp.segments = sp.emit ? g.t_done - 1 - g.t_out : 0;
+    if (S.post) {
+        g.fmin_ring = S.fmin_ring; g.wgt_ring = S.wgt_ring; g.post = S.post_state; g.RW = S.RW;
+        g.fm_lo = (int)S.done; g.fm_hi = (int)p.done; g.post_flush = final;
+        sp.post_frames = (int)(p.done - S.done);
+        sp.post_walk = sp.post_frames > 0 || final;
+    }
     return sp;
 }
 
@@ -2259,8 +2282,9 @@ void Model::stream_step_commit(StreamState& S, StreamStepIO& o, const StreamStep
     if (sp.emit) {
         S.carry_cur ^= 1;
         o.out_off += (long long)hop * sp.segments;
-        S.done = sp.p.done;
+        S.out_done = sp.p.out_done;
     }
+    if (!S.measure) S.done = sp.p.done;
     S.tail_cur ^= 1;
     S.tail_base = sp.seg.tail_out_base;
     S.frames = sp.p.frames; S.crops[0] = sp.p.crops[0]; S.crops[1] = sp.p.crops[1];
@@ -2275,8 +2299,8 @@ long long Model::stream_check(const StreamState& S, const std::string& who, cons
     VR_CHECK(n >= 0 && (n == 0 || wave), -2, who + "null or negative input");
     long long need = 0;
     try {
-        const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0);
-        const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, flush);
+        const StreamSchedule before = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples, 0, S.post);
+        const StreamSchedule after = stream_schedule(n_fft, hop, S.cropsize, offset, S.tta, S.samples + n, flush, S.post);
         need = S.measure ? 0 : after.samples_out - before.samples_out;
     } catch (const Error& e) {
         throw Error(e.code, who + e.what());
@@ -2378,13 +2402,15 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
             if (live.empty()) break;
             const int ne = (int)live.size();
             segs_h.emplace_back((size_t)ne);
-            int max_new = 0, max_seg = 0;
-            double sum_new = 0, sum_seg = 0, sum_blk = 0;
-            bool any_tta = false;
+            int max_new = 0, max_seg = 0, max_post = 0;
+            double sum_new = 0, sum_seg = 0, sum_blk = 0, sum_post = 0;
+            bool any_tta = false, post_walk = false;
             for (int e = 0; e < ne; ++e) {
                 segs_h.back()[e] = plans[e].seg;
                 max_new = std::max(max_new, plans[e].new_frames); sum_new += plans[e].new_frames;
                 max_seg = std::max(max_seg, plans[e].segments); sum_seg += plans[e].segments;
+                max_post = std::max(max_post, plans[e].post_frames); sum_post += plans[e].post_frames;
+                post_walk = post_walk || plans[e].post_walk;
                 sum_blk += (double)parts[live[e]].o.blk_n;
                 any_tta = any_tta || parts[live[e]].S->tta;
             }
@@ -2439,6 +2465,8 @@ void Model::stream_run(std::vector<StreamPart>& parts, int bs, bool on_dev, bool
                 };
                 run_crop_chunks(nc, bs, run_crops);
             }
+            // --postprocess streams: the minima of the masks that became final, then the walk that turns them into blend weights
+            if (max_post > 0 || post_walk) launch_stream_post(seg_d, ne, max_post, sum_post, post_walk, is_complex, any_tta, bins, stream);
             for (int which = 0; which < 2; ++which)     // (no launch when no entry has a final segment)
                 launch_istft_stream(plan, seg_d, ne, max_seg, sum_seg, is_complex, any_tta, which, stream, parts[0].S->pcm16);
             for (int e = 0; e < ne; ++e) stream_step_commit(*parts[live[e]].S, parts[live[e]].o, plans[e]);

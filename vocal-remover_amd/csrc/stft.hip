@@ -540,11 +540,17 @@ __global__ __launch_bounds__(1024) void istft_tile_kernel(FFTPlan pl, SRC* __res
                             const float2 b = reinterpret_cast<const float2*>(mb)[cb];
                             m = make_float2((m.x + b.x) * 0.5f, (m.y + b.y) * 0.5f);
                         }
+                        if (ss.fmin_ring) {             // (--postprocess stream: final_mask's blend, the weight from the stream's ring)
+                            const float mag = hypotf(m.x, m.y), w = ss.wgt_ring[t % ss.RW];
+                            const float nm = mag + w * (1.f - mag);
+                            m = mag > 0.f ? make_float2(nm * (m.x / mag), nm * (m.y / mag)) : make_float2(nm, 0.f);
+                        }
                         const float2 gm = which ? make_float2(1.f - m.x, -m.y) : m;
                         v = cmul(gm, v);
                     } else {
                         float m = ma[ca];
                         if (mb) m = (m + mb[cb]) * 0.5f;
+                        if (ss.fmin_ring) m += ss.wgt_ring[t % ss.RW] * (1.f - m);
                         const float gm = which ? 1.f - m : m;
                         v = make_float2(gm * v.x, gm * v.y);
                     }
@@ -1449,13 +1455,71 @@ void launch_pack_complex(const float2* spec, int N, int bins, int T, float* dst,
 // (lib/spec_utils.py:64).  One workgroup per 64 frames; lanes along time (coalesced rows).
 // CPLX: complex64 masks, the minimum of |mask| (inference.py:28-29)
 // DST = const SongSeg: `dst` is the song table, blockIdx.y = song, the minima go to that song's own fmin
+constexpr int kStreamMinFrames = 8;       // frames per workgroup of the stream form's minima
 template <bool CPLX, class DST = float>
 __global__ __launch_bounds__(256) void frame_min_kernel(int rows, int T, const float* __restrict__ ma, int Wa,
                                                         const float* __restrict__ mb, int Wb, int shift,
                                                         DST* __restrict__ dst) {
     __shared__ float red[4][64];
     float* __restrict__ fmin;
-    if constexpr (kSongTable<DST>) {
+    if constexpr (kStream<DST>) {
+        // DST = const StreamSeg (--postprocess streams): blockIdx.y = table entry; an entry without the rings is skipped.
+        // rows > 0: the minima of the entry's frames [fm_lo, fm_hi) from its mask rings (pass 0 at column t % RM, the TTA pass at
+        // (t + shift) % RM, averaged as the masked iSTFT averages them) into fmin_ring[t % RW]; T, ma .. shift are unused.
+        // rows == 0: the walk -- one workgroup per entry takes those minima through stream_post_advance (stream_post.h): the wave
+        // brings them into LDS, lane 0 walks the state and stores the weights; no atomics, nothing comes back to the host.
+        const StreamSeg sg = dst[blockIdx.y];
+        if (!sg.fmin_ring) return;
+        if (rows == 0) {
+            __shared__ float fm[1024];
+            if (blockIdx.x) return;
+            StreamPostState ps = *sg.post;
+            for (int base = ps.h; base < sg.fm_hi; base += 1024) {
+                const int n = sg.fm_hi - base < 1024 ? sg.fm_hi - base : 1024;
+                for (int i = threadIdx.x; i < n; i += 256) fm[i] = sg.fmin_ring[(base + i) % sg.RW];
+                __syncthreads();
+                if (threadIdx.x == 0) stream_post_advance(ps, fm, n, sg.wgt_ring, sg.RW);
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) {
+                if (sg.post_flush) stream_post_finish(ps, sg.wgt_ring, sg.RW);
+                *sg.post = ps;
+            }
+            return;
+        }
+        // (a step brings few frames -- one crop's roi in a steady push -- so a workgroup takes kStreamMinFrames of them and splits the rows
+        // 256 / kStreamMinFrames ways: 64 frames per workgroup, as offline, would leave a steady push to two workgroups)
+        constexpr int FW = kStreamMinFrames, PARTS = 256 / FW;
+        if ((int)blockIdx.x * FW >= sg.fm_hi - sg.fm_lo) return;
+        const int fl = threadIdx.x % FW, part = threadIdx.x / FW;
+        const int t = sg.fm_lo + blockIdx.x * FW + fl;
+        const int ca = t % sg.RM, cb = (t + sg.shift) % sg.RM;
+        float* redf = &red[0][0];                           // [PARTS][FW]
+        float m = 3.4e38f;
+        if (t < sg.fm_hi) {
+            for (int r = part; r < rows; r += PARTS) {
+                if constexpr (CPLX) {
+                    float2 v = reinterpret_cast<const float2*>(sg.mask_a)[(long long)r * sg.RM + ca];
+                    if (sg.mask_b) {
+                        const float2 b = reinterpret_cast<const float2*>(sg.mask_b)[(long long)r * sg.RM + cb];
+                        v = make_float2((v.x + b.x) * 0.5f, (v.y + b.y) * 0.5f);
+                    }
+                    m = fminf(m, hypotf(v.x, v.y));
+                } else {
+                    float v = sg.mask_a[(long long)r * sg.RM + ca];
+                    if (sg.mask_b) v = (v + sg.mask_b[(long long)r * sg.RM + cb]) * 0.5f;
+                    m = fminf(m, v);
+                }
+            }
+        }
+        redf[threadIdx.x] = m;
+        __syncthreads();
+        if (part == 0 && t < sg.fm_hi) {
+            for (int q = 1; q < PARTS; ++q) m = fminf(m, redf[q * FW + fl]);
+            sg.fmin_ring[t % sg.RW] = m;
+        }
+        return;
+    } else if constexpr (kSongTable<DST>) {
         const SongSeg sg = dst[blockIdx.y];
         T = sg.T;
         ma += (long long)(CPLX ? 2 : 1) * sg.mcol_a;
@@ -2012,6 +2076,23 @@ void launch_istft_stream(const FFTPlan& pl, const StreamSeg* seg, int n_seg, int
         VR_LAUNCH((istft_tile_kernel<false, const StreamSeg>), grid, dim3(1024), lds, st, pl, seg, 0, S, nullptr, 0, nullptr, 0, 0, nullptr, which, nullptr, 0LL);
     }
     VR_HIP(hipGetLastError());
+}
+
+void launch_stream_post(const StreamSeg* seg, int n_seg, int post_frames, double sum_frames, bool walk, bool cplx, bool tta, int bins,
+                        hipStream_t st) {
+    if (post_frames > 0) {
+        const dim3 grid((unsigned)((post_frames + kStreamMinFrames - 1) / kStreamMinFrames), (unsigned)n_seg);
+        prof_note(0.0, 2.0 * (double)bins * sum_frames * (cplx ? 8.0 : 4.0) * (tta ? 2 : 1));
+        if (cplx) VR_LAUNCH((frame_min_kernel<true, const StreamSeg>), grid, dim3(256), 0, st, 2 * bins, 0, nullptr, 0, nullptr, 0, 0, seg);
+        else VR_LAUNCH((frame_min_kernel<false, const StreamSeg>), grid, dim3(256), 0, st, 2 * bins, 0, nullptr, 0, nullptr, 0, 0, seg);
+        VR_HIP(hipGetLastError());
+    }
+    if (walk) {
+        prof_note(0.0, 8.0 * sum_frames);
+        if (cplx) VR_LAUNCH((frame_min_kernel<true, const StreamSeg>), dim3(1, (unsigned)n_seg), dim3(256), 0, st, 0, 0, nullptr, 0, nullptr, 0, 0, seg);
+        else VR_LAUNCH((frame_min_kernel<false, const StreamSeg>), dim3(1, (unsigned)n_seg), dim3(256), 0, st, 0, 0, nullptr, 0, nullptr, 0, 0, seg);
+        VR_HIP(hipGetLastError());
+    }
 }
 
 }  // namespace vr

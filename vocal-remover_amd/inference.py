@@ -412,11 +412,21 @@ class Separator(object):
                 native.VRArgumentError)
         return list(zip(ys, vs))
 
-    def stream(self, coef=None, tta=False, pcm16=False):
+    def stream(self, coef=None, tta=False, pcm16=False, postprocess=False):
         """A streaming session on this model: see Stream.  coef: the normaliser of the whole input (measure_coef); None (plain only)
         = a running normaliser over the audio received so far, which is NOT the offline result.  pcm16: the stems come back as int16
-        [n_out, 2], encoded by the last kernel as audio.write encodes them (VR_STREAM_PCM16_OUT); the input stays float."""
-        return Stream(self, coef, tta, pcm16=pcm16)
+        [n_out, 2], encoded by the last kernel as audio.write encodes them (VR_STREAM_PCM16_OUT); the input stays float.
+        postprocess: the stream applies merge_artifacts as separate_wave of a Separator(postprocess=True) does, exactly, at the price
+        of 161 more frames of delay (Stream.lookahead_samples says how much).  It is asked for HERE: a Separator built with
+        postprocess=True does not switch it on by itself -- stream() without the keyword raises ValueError on such a Separator --
+        so that a stream's latency never changes behind the caller's back.  Needs a given coef.  Unlike the offline call, a stream
+        never raises for input whose mask stays below the threshold everywhere: nothing is blended then."""
+        if self.postprocess and not postprocess:
+            raise ValueError('this Separator was built with postprocess=True, which a stream does not take over by itself: pass '
+                             'stream(..., postprocess=True) to run merge_artifacts in the stream (the stems then come %d frames = %d '
+                             'samples later), or stream from a Separator without postprocess'
+                             % (native.STREAM_POST_DELAY, native.STREAM_POST_DELAY * self.model.hop_length))
+        return Stream(self, coef, tta, pcm16=pcm16, postprocess=postprocess)
 
     def push_many(self, streams, waves, flush=False, batchsize=None):
         """One vr_stream_push_many call: streams[k] (opened by self.stream) receives waves[k] ([2, n], or None for nothing) and, where
@@ -560,15 +570,16 @@ class Stream(object):
     0), flush() -> the rest; the concatenation is what separate_wave returns for the whole input when `coef` is that call's normaliser
     (Separator.measure_coef).  numpy in, numpy out; a torch cuda tensor in, cuda tensors out.  Use as a context manager or close()."""
 
-    def __init__(self, sep, coef, tta, measure=False, pcm16=False):
+    def __init__(self, sep, coef, tta, measure=False, pcm16=False, postprocess=False):
         m = sep.model
         self.pcm16 = bool(pcm16)                 # push / flush return int16 [n_out, 2] instead of float32 [2, n_out]
         self._handle = m._need_handle()
-        self._geom = (m.n_fft, m.hop_length, int(sep.cropsize), m.offset, bool(tta))
+        self.postprocess = bool(postprocess)     # merge_artifacts in the stream: the keyword alone decides (Separator.stream)
         self.measure = measure
         m.eval()
         flags = (native.VR_STREAM_TTA if tta else 0) | (native.VR_STREAM_MEASURE if measure else 0)
-        flags |= native.VR_STREAM_POSTPROCESS if sep.postprocess else 0          # (the library refuses it with its reason)
+        flags |= native.VR_STREAM_POSTPROCESS if self.postprocess else 0
+        self._geom = (m.n_fft, m.hop_length, int(sep.cropsize), m.offset, flags & (native.VR_STREAM_TTA | native.VR_STREAM_POSTPROCESS))
         flags |= native.VR_STREAM_PCM16_OUT if self.pcm16 else 0
         c = complex(coef) if coef is not None else 0j
         self._s = native.ctypes.c_void_p()
@@ -582,8 +593,8 @@ class Stream(object):
         self.lookahead_samples, self.block_samples, self.state_bytes = [int(i.value) for i in info]
 
     def _need(self, n, flushed):
-        before = native.stream_plan(*self._geom, self._samples, False)[2]
-        return 0 if self.measure else native.stream_plan(*self._geom, self._samples + n, flushed)[2] - before
+        before = native.stream_plan_ex(*self._geom, self._samples, False)[2]
+        return 0 if self.measure else native.stream_plan_ex(*self._geom, self._samples + n, flushed)[2] - before
 
     def _call(self, wave, flush):
         if not self._s.value:
@@ -673,7 +684,7 @@ class Stream(object):
         """After the flush of a measuring stream: max|X| (plain) or numpy's lexicographic complex maximum (tta) of the whole input."""
         c = (native.ctypes.c_double * 2)()
         native.check(native.lib().vr_stream_coef(self._s, c))
-        return complex(c[0], c[1]) if self._geom[4] else float(c[0])
+        return complex(c[0], c[1]) if self._geom[4] & native.VR_STREAM_TTA else float(c[0])
 
     def close(self):
         if getattr(self, '_s', None) is not None and self._s.value:
@@ -775,18 +786,19 @@ def _rows(a, pcm16):
     return a if pcm16 else a.T
 
 
-def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True):
+def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True, postprocess=False):
     """--stream: the WAV at `path` is read in blocks twice -- pass 1 measures the normaliser, pass 2 separates -- and the two stems are
     written as they arrive; the song is never held whole.  The file's rate must be `sr`: the resampler is not streamed -- unless
     resample=True, which reads both passes at the file's own rate through an audio.StreamResampler (bounded state; the blocks stay on
     the device from the upload to the stems); the stems are written at `sr`, as the offline path writes them.  pcm16: the stream
     returns the stems as the file's int16 samples (Separator.stream(pcm16=True)); the files are byte for byte the same.
-    pcm_in: both passes push the file's own bytes where the device decodes them (_StreamSource); the stems are the same bits."""
+    pcm_in: both passes push the file's own bytes where the device decodes them (_StreamSource); the stems are the same bits.
+    postprocess: merge_artifacts in the stream (Separator.stream(postprocess=True)): the offline --postprocess stems, 161 frames later."""
     from . import audio
     blocks = _stream_reader(path, sr, block_seconds, resample, sp.model._need_handle().device, pcm_in)
     coef = sp.measure_coef(blocks(), tta=tta)
     with audio.WavAppendWriter(out_y, sr, 2) as wy, audio.WavAppendWriter(out_v, sr, 2) as wv, \
-            sp.stream(coef=coef, tta=tta, pcm16=pcm16) as s:
+            sp.stream(coef=coef, tta=tta, pcm16=pcm16, postprocess=postprocess) as s:
         for b in blocks():
             y, v = _push_block(s, b)
             wy.append(_rows(y, pcm16))
@@ -796,7 +808,7 @@ def stream_file(sp, path, out_y, out_v, sr, tta=False, block_seconds=1.0, resamp
         wv.append(_rows(v, pcm16))
 
 
-def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True):
+def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=False, pcm16=False, pcm_in=True, postprocess=False):
     """--stream on a directory: stream_file for a group of WAVs at once.  Every file's normaliser is measured first; then the files
     advance together, one block each per Separator.push_many call, so their crops share device batches; a file that ends is flushed
     in the call that carries its last block while the others go on.  outs[k] = (instruments path, vocals path) of paths[k].
@@ -807,7 +819,8 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
     kind), and nothing comes back to the host before the stems.
     pcm_in: the measuring pass of every file, and every resampler, take the file's bytes where the device decodes them.  The separating
     pass takes one kind of block per push_many call: bytes (push_many_pcm) when no file of the group resamples and every file's encoding
-    is one the device decodes; otherwise the files at `sr` are decoded on the host as before, beside the resamplers' float output."""
+    is one the device decodes; otherwise the files at `sr` are decoded on the host as before, beside the resamplers' float output.
+    postprocess: every stream of the group runs merge_artifacts (Separator.stream(postprocess=True))."""
     import contextlib
 
     from . import audio
@@ -820,7 +833,7 @@ def stream_files(sp, paths, outs, sr, tta=False, block_seconds=1.0, resample=Fal
     with contextlib.ExitStack() as stack:
         wy = [stack.enter_context(audio.WavAppendWriter(oy, sr, 2)) for oy, _ in outs]
         wv = [stack.enter_context(audio.WavAppendWriter(ov, sr, 2)) for _, ov in outs]
-        streams = [stack.enter_context(sp.stream(coef=c, tta=tta, pcm16=pcm16)) for c in coefs]
+        streams = [stack.enter_context(sp.stream(coef=c, tta=tta, pcm16=pcm16, postprocess=postprocess)) for c in coefs]
         rs = [stack.enter_context(src.resampler()) if src.resamples else None for src in sources]
         its = [src.raw(decoded=not (bytes_in or src.resamples)) for src in sources]
         ahead = [next(it, None) for it in its]
@@ -946,12 +959,12 @@ def main(argv=None):
         for group in expand_inputs(args.input, args.songs_per_call):      # the group's files advance together, block by block
             names = [os.path.splitext(os.path.basename(path))[0] for path in group]
             stream_files(sp, group, [('{}{}_Instruments.wav'.format(output_dir, b), '{}{}_Vocals.wav'.format(output_dir, b)) for b in names],
-                         args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled)
+                         args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled, postprocess=args.postprocess)
         return 0
     if args.stream:
         basename = os.path.splitext(os.path.basename(args.input))[0]
         stream_file(sp, args.input, '{}{}_Instruments.wav'.format(output_dir, basename), '{}{}_Vocals.wav'.format(output_dir, basename),
-                    args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled)
+                    args.sr, tta=args.tta, block_seconds=args.block_seconds, resample=True, pcm16=tiled, postprocess=args.postprocess)
         return 0
     if args.reference is not None:
         import json

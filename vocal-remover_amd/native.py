@@ -104,6 +104,9 @@ _SIGNATURES = {
     'vr_stream_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i64p]),
     'vr_stream_close': (ctypes.c_int, [ctypes.c_void_p]),
     'vr_stream_plan': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_int64, ctypes.c_int, c_i64p, c_i64p, c_i64p]),
+    'vr_stream_plan_ex': (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.c_int64, ctypes.c_int, c_i64p, c_i64p, c_i64p]),
+    'vr_debug_stream_post_weight': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, c_f32p,
+                                                   ctypes.POINTER(ctypes.c_int)]),
     'vr_arena_bytes': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p]),
     'vr_train_step': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.POINTER(ctypes.c_float), c_f32p, ctypes.c_int]),
@@ -289,6 +292,31 @@ def stream_plan(n_fft, hop, cropsize, offset, tta, samples_in, flushed):
     check(lib().vr_stream_plan(int(n_fft), int(hop), int(cropsize), int(offset), 1 if tta else 0, int(samples_in), 1 if flushed else 0,
                                ctypes.byref(fr), crops, ctypes.byref(out)))
     return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
+
+
+def stream_plan_ex(n_fft, hop, cropsize, offset, flags, samples_in, flushed):
+    """vr_stream_plan_ex (host only): stream_plan with the flags of vr_stream_open (VR_STREAM_TTA, VR_STREAM_POSTPROCESS) in place of tta."""
+    fr, out = ctypes.c_int64(), ctypes.c_int64()
+    crops = (ctypes.c_int64 * 2)()
+    check(lib().vr_stream_plan_ex(int(n_fft), int(hop), int(cropsize), int(offset), int(flags), int(samples_in), 1 if flushed else 0,
+                                  ctypes.byref(fr), crops, ctypes.byref(out)))
+    return int(fr.value), (int(crops[0]), int(crops[1])), int(out.value)
+
+
+def stream_post_weight(frame_min, cuts=()):
+    """vr_debug_stream_post_weight (host only): the merge_artifacts weights of the per-frame mask minima `frame_min` from the incremental
+    form a postprocess stream runs, taken in steps that end in front of the frames `cuts`.  -> (weight [T], frames final after each
+    step and after the flush [len(cuts) + 1])."""
+    import numpy as np
+    f = np.ascontiguousarray(frame_min, dtype=np.float32)
+    c = (ctypes.c_int * max(len(cuts), 1))(*[int(x) for x in cuts])
+    w = np.empty(f.size, np.float32)
+    fin = (ctypes.c_int * (len(cuts) + 1))()
+    check(lib().vr_debug_stream_post_weight(np_ptr(f), int(f.size), c, len(cuts), np_ptr(w), fin))
+    return w, np.array(list(fin), dtype=np.int64)
+
+
+STREAM_POST_DELAY = 161      # frames a postprocess stream's output lags its masks: 3 * fade_size + min_range + 1
 
 
 def evaluate_plan(hop, L, window):
