@@ -494,6 +494,12 @@ int vr_stream_plan_ex(int n_fft, int hop, int cropsize, int offset, int flags, i
                       int64_t* crops_ready /*[2]*/, int64_t* samples_out);
 /* Device bytes the handle holds for staging (inputs, outputs, masks of one call) and for the network's workspace. */
 int vr_arena_bytes(vr_handle h, int64_t* staging_bytes, int64_t* workspace_bytes);
+/* Device bytes the handle holds for the training input pipeline, a buffer of its own that vr_arena_bytes does not count: the tables and
+ * host-side outputs of vr_augment_batch / vr_dataset_batch / vr_dataset_windows and, over a wave store, the STFT rows of one batch
+ * (4 * B * T * 2 * bins * 8 bytes plus one eighth: about 300 MB at B 16, T 256, 1025 bins).  It grows to the largest call made and is kept
+ * until the handle is destroyed, or until release != 0 here: *bytes (may be NULL) receives what was held before the call, the buffer is
+ * freed after the handle's stream has drained, and the next call that needs it allocates it again. */
+int vr_pipeline_buffer(vr_handle h, int64_t* bytes, int release);
 
 /* ---- training: the body of train.train_epoch (train.py:77-96) ------------------------------------ */
 /* mask = model(X); loss = L1Loss()(mask * X, y); (loss / accumulation_steps).backward()
@@ -593,6 +599,37 @@ int vr_dataset_peak(vr_dataset d, int song, float* peak, float* at, int* slab, i
 typedef struct vr_window { int song; int reserved; int64_t start; float scale; } vr_window;
 int vr_dataset_windows(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_mag, float* y_mag, int out_on_device);
 int vr_dataset_windows_complex(vr_handle h, vr_dataset d, const vr_window* w, int B, int T, float* X_out, float* y_out, int out_on_device);
+
+/* The WAVE store, a second kind of vr_dataset: a song is kept as its two ALIGNED WAVES instead of their STFT rows --
+ * half the device bytes as float32 (hop * 4 bytes against bins * 8 per hop and channel), a quarter as the file's PCM16 frames, and no cache
+ * file to write or read -- and every entry point above forms the rows it needs on the device: rows [start, start + T) of a song's
+ * spectrogram depend on its samples alone, and the crop-table form of the frame-tiled STFT writes them bit for bit as vr_pair_rows_many
+ * writes them for the whole wave (row 0 reaches n_fft / 2 zeros in front of the wave, the last rows reach past its end).  The kind of a
+ * store is fixed at creation: vr_dataset_add on a wave store and the two calls below on a rows store are VR_ERR_BAD_ARGUMENT.
+ *   vr_dataset_create_waves   an empty wave store with its own FFT plan (window and twiddles as every handle builds them); bins =
+ *                       n_fft / 2 + 1.  hop_length != n_fft / 2, or an n_fft the frame-tiled kernels do not take (a power of two from 128
+ *                       up to what the tile holds in LDS): VR_ERR_UNSUPPORTED, judged on the host before the device is touched.
+ *   vr_dataset_add_waves      one song: mix, inst float32 [2][n], already aligned, both on the host or both on the device; each is copied
+ *                       once into one device slab (host memory through the store's bounded pinned staging).  vr_dataset_rows reports
+ *                       1 + n / hop_length.  OOM as vr_dataset_add.
+ *   vr_dataset_add_pcm        the same song as `frames` interleaved frames of 1 or 2 channels (one channel is up-mixed) in a vr_pcm_format,
+ *                       channel count and format per wave.  The bytes are stored as they are and decoded where the STFT reads them
+ *                       (csrc/pcm.h): every batch, window and peak equals, bit for bit, that of the song added as its decoded floats
+ *                       (vr_pcm_convert_host).  The buffers may lie at any byte, host or device.
+ *   vr_dataset_info counts the bytes of the slabs (sample bytes rounded up to whole 32-bit words).
+ * vr_dataset_batch[_complex], vr_dataset_windows[_complex] and vr_dataset_peak keep their signatures, checks and results: on a wave store
+ * a batch is two launches -- the crop STFT of B * (2..4) signals of T rows into scratch of the calling handle (its input-pipeline buffer,
+ * reserved for 4 * B signals whatever the flags, so its size follows from B and T alone: 4 * B * T * 2 * bins * 8 bytes plus one
+ * eighth, grown once and kept -- vr_pipeline_buffer reports and releases it; two handles never share it), then the augmentation kernel of the rows store
+ * reading that scratch; windows transform only the rows inside the song (a row outside is zero, not the transform of padded samples); the
+ * peak passes the song's rows through scratch of the store's own, 1024 rows at a time, and merges the chunk candidates by the kernel's
+ * rule, so peak, at, slab and index are those of a rows store holding the vr_pair_rows_many rows of the same waves, NaN cases included.
+ * One more check, before anything is launched: the handle's n_fft and hop_length must be the store's, else VR_ERR_BAD_ARGUMENT naming
+ * both; and B <= 16383.  No float atomics: two identical calls agree bit for bit. */
+int vr_dataset_create_waves(int device, int n_fft, int hop_length, vr_dataset* out);
+int vr_dataset_add_waves(vr_dataset d, const float* mix, const float* inst, int on_device, int64_t n, int* song_out);
+int vr_dataset_add_pcm(vr_dataset d, const void* mix_bytes, const void* inst_bytes, int on_device, int64_t frames, int mix_channels,
+                       int inst_channels, int mix_fmt, int inst_fmt, int* song_out);
 
 /* torch.optim.Adam(lr, betas=(b1,b2), eps, weight_decay=0).step()   train.py:215-218,95
  * grad_scale multiplies every gradient first (1/world_size after a SUM all-reduce).  Hyper-parameters are doubles

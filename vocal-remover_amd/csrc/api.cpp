@@ -637,6 +637,14 @@ int vr_arena_bytes(vr_handle h, int64_t* staging_bytes, int64_t* workspace_bytes
     });
 }
 
+int vr_pipeline_buffer(vr_handle h, int64_t* bytes, int release) {
+    NEED(h);
+    return guard([&] {
+        const long long held = h->m.pipeline_buffer(release != 0);
+        if (bytes) *bytes = held;
+    });
+}
+
 int vr_train_step(vr_handle h, const float* X, const float* y, int on_device, int B, int T, int accumulation_steps,
                   float* loss_out, float* mask_out, int mask_on_device) {
     NEED(h);
@@ -705,6 +713,7 @@ static void need_device(int device);
 struct vr_dataset_s {
     vr::ResidentSet set;
     vr_dataset_s(int device, int bins) : set(device, bins) {}
+    vr_dataset_s(int device, int n_fft, int hop) : set(device, n_fft, hop) {}
 };
 
 #define NEED_DATASET(d)                                          \
@@ -720,6 +729,43 @@ int vr_dataset_create(int device, int bins, vr_dataset* out) {
     return guard([&] {
         need_device(device);
         *out = new vr_dataset_s(device, bins);
+    });
+}
+
+// The wave store: the sizes are judged on the host alone (stft_crops_supported), so an unsupported pair is refused without a device.
+int vr_dataset_create_waves(int device, int n_fft, int hop_length, vr_dataset* out) {
+    if (!out) { g_err = "null out pointer"; return VR_ERR_BAD_ARGUMENT; }
+    *out = nullptr;
+    if (n_fft <= 0 || hop_length <= 0) { g_err = "vr_dataset_create_waves: n_fft and hop_length must be positive"; return VR_ERR_BAD_ARGUMENT; }
+    if (hop_length * 2 != n_fft || !vr::stft_crops_supported(n_fft, hop_length)) {
+        g_err = "vr_dataset_create_waves: n_fft " + std::to_string(n_fft) + ", hop_length " + std::to_string(hop_length) +
+                ": the wave store forms its rows with the frame-tiled STFT, which needs hop_length == n_fft / 2 and a power-of-two n_fft "
+                "from 128 up to what its tile holds in LDS; keep such a set as cached rows (vr_dataset_create)";
+        return VR_ERR_UNSUPPORTED;
+    }
+    return guard([&] {
+        need_device(device);
+        *out = new vr_dataset_s(device, n_fft, hop_length);
+    });
+}
+
+int vr_dataset_add_waves(vr_dataset d, const float* mix, const float* inst, int on_device, int64_t n, int* song_out) {
+    NEED_DATASET(d);
+    return guard([&] {
+        VR_CHECK(mix && inst, VR_ERR_BAD_ARGUMENT, "null argument");
+        const int song = d->set.add_waves(mix, inst, on_device != 0, n);
+        if (song_out) *song_out = song;
+    });
+}
+
+int vr_dataset_add_pcm(vr_dataset d, const void* mix_bytes, const void* inst_bytes, int on_device, int64_t frames, int mix_channels,
+                       int inst_channels, int mix_fmt, int inst_fmt, int* song_out) {
+    NEED_DATASET(d);
+    return guard([&] {
+        VR_CHECK(mix_bytes && inst_bytes, VR_ERR_BAD_ARGUMENT, "null argument");
+        const int channels[2] = {mix_channels, inst_channels}, fmt[2] = {mix_fmt, inst_fmt};
+        const int song = d->set.add_pcm(mix_bytes, inst_bytes, on_device != 0, frames, channels, fmt);
+        if (song_out) *song_out = song;
     });
 }
 

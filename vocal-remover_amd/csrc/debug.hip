@@ -10,6 +10,7 @@
 // its batched launcher, and what a live handle holds for a layer (tests/test_gpu_weight_forms.py).
 // The head_loss* and head_wave_* hooks run the train step's own head function (run_train_head, train.hip) on their buffers, and the
 // wave_pair / wave_triple hooks the wave-term launcher it and vr_validate_step run (launch_wave_term, stft.hip): no copy of either here.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -107,6 +108,13 @@ int wgrad_choose(WgradArgs& a, const ConvShape& s, int* CB, int* MT);      // wg
 //                 contents, canaries) between guard bands and returned whole in its output; accumulate 0 stores, 1 adds.  Without them:
 //                 dense, accumulated onto zeros
 // thin            N,C,H,W,CO            slope            x, aff[C][2]|null, w[CO][C], dz[N,CO,H,W]           g[N,C,H,W], dw[CO][C], z[N,H,W] (CO=1: forward)
+// stft_crops      W,E,max_T,            -                wave w: float32 [2][n_w] (fmt 0) or its                rows [E][max_T][2][bins] complex64: entry e's
+//                 W x (n,fmt,channels), interleaved sample bytes (padded to whole floats)     T_e rows at [e][0 .. T_e), zeros behind them
+//                 E x (wave,start,T)
+//                 launch 1 of a wave store's batch alone (launch_stft_crops, stft.hip): entry e = rows [start, start + T) of the STFT of
+//                 wave `wave` at the handle's n_fft (hop == n_fft / 2), the scratch between guard bands (error -3).  fmt: 0 or a
+//                 vr_pcm_format with its channel count; start >= 0, start + T <= 1 + n / hop and T <= max_T are checked here, as the
+//                 entry points check them
 // head_loss       N,C,H,W,bins          slope,gscale     x, aff|null, w[2][C], X[N,2,bins,W], Y              dlogit[N,2,H,W], mask[N,2,bins,W], loss[1]
 // head_loss_complex N,C,H,W,bins        slope,gscale     x, aff|null, w[4][C], X[N,2,bins,W] complex64, Y    dlogit[N,4,H,W], mask[N,2,bins,W] complex64, loss[1],
 //                                                        (complex64)                                         g[N,C,H,W], dw[4][C]
@@ -1570,6 +1578,44 @@ void Model::debug_kernel(const std::string& name, const int64_t* dims, int ndims
         VR_CHECK(loss.intact() && xw.intact() && yw.intact() && pw.intact() && pp.intact() && dm.intact(), -3,
                  "head_wave_wsdr: a store outside the loss, a wave, the partial sums or dmask");
         dlogit.download(out[0]); mask.download(out[1]); loss.download(out[2]); g.download(out[3]); dw.download(out[4]); dm.download(out[5]);
+    } else if (name == "stft_crops") {
+        need(3, 0, 1, 1);
+        const int W = (int)dims[0], E = (int)dims[1], max_T = (int)dims[2];
+        const int bins = n_fft / 2 + 1;
+        VR_CHECK(many_tiled_available(plan, hop), -2, "stft_crops: the crop form needs hop == n_fft / 2 (128 <= n_fft <= 4096)");
+        VR_CHECK(W > 0 && E > 0 && E <= 65535 && max_T > 0 && ndims >= 3 + 3 * W + 3 * E && nin >= W, -2,
+                 "stft_crops: need waves, entries and max_T > 0 and three dims for every wave and every entry");
+        std::vector<std::unique_ptr<DevBuf>> wv;
+        for (int w = 0; w < W; ++w) {
+            const long long n = dims[3 + 3 * w], fmt = dims[4 + 3 * w], chn = dims[5 + 3 * w];
+            VR_CHECK(n > 0 && in[w] && (fmt == 0 || (fmt >= 1 && fmt <= 4 && (chn == 1 || chn == 2))), -2,
+                     "stft_crops: wave " + std::to_string(w) + ": need n > 0, the samples, and fmt 0 or a vr_pcm_format with 1 or 2 channels");
+            const size_t bytes = fmt == 0 ? (size_t)2 * n * 4 : (size_t)n * chn * (fmt == 1 ? 2 : fmt == 2 ? 3 : 4);
+            wv.emplace_back(new DevBuf(in[w], (bytes + 3) / 4));
+        }
+        const size_t rows_f = (size_t)max_T * 2 * bins * 2;
+        GuardedBuf rows(nullptr, (size_t)E * rows_f);
+        std::vector<CropSeg> segs((size_t)E);
+        int longest = 0;
+        double rows_total = 0.0;
+        for (int e = 0; e < E; ++e) {
+            const int64_t* d = dims + 3 + 3 * W + 3 * e;
+            VR_CHECK(d[0] >= 0 && d[0] < W, -2, "stft_crops: entry " + std::to_string(e) + ": wave index out of range");
+            const long long n = dims[3 + 3 * d[0]], song_rows = 1 + n / hop;
+            VR_CHECK(d[2] > 0 && d[2] <= max_T && d[1] >= 0 && d[1] <= song_rows - d[2], -2,
+                     "stft_crops: entry " + std::to_string(e) + ": rows [" + std::to_string(d[1]) + ", " + std::to_string(d[1] + d[2]) +
+                         ") must lie inside the " + std::to_string(song_rows) + " rows of its wave and T inside max_T");
+            segs[e] = CropSeg{wv[d[0]]->p, n, d[1], reinterpret_cast<float2*>(rows.p() + (size_t)e * rows_f), (int)d[2], (int)dims[4 + 3 * d[0]],
+                              (int)dims[5 + 3 * d[0]], 0};
+            longest = std::max(longest, (int)d[2]);
+            rows_total += (double)d[2];
+        }
+        DevBuf table(((size_t)E * sizeof(CropSeg) + 3) / 4);
+        VR_HIP(hipMemcpy(table.p, segs.data(), (size_t)E * sizeof(CropSeg), hipMemcpyHostToDevice));
+        launch_stft_crops(plan, reinterpret_cast<const CropSeg*>(table.p), E, longest, rows_total, st);
+        VR_HIP(hipStreamSynchronize(st));
+        VR_CHECK(rows.intact(), -3, "stft_crops: a store outside the scratch rows");
+        rows.download(out[0]);
     } else {
         throw Error(-2, "vr_debug_kernel: unknown kernel name: " + name);
     }

@@ -329,6 +329,14 @@ void launch_istft_masked(const FFTPlan& pl, const float2* spec, int hop, int T, 
 // masked iSTFT (mask_a null: plain) writes interleaved int16 [hop * (T-1)][2] = pcm16_from_float of the float it would have stored.
 struct PcmIn { const uint8_t* bytes; int channels; int fmt; };   // frames of `channels` (1: up-mixed) samples, fmt = vr_pcm_format
 void launch_stft_pcm(const FFTPlan& pl, const PcmIn& in, long long L, int T, float2* spec, hipStream_t st);
+// the crop-table form of the frame-tiled STFT (the wave store of vr_dataset_*): one entry per signal, grid (frame
+// tile, channel, entry).  Entry e writes rows [start, start + T) of the STFT of its wave -- n samples per channel, the zero padding at the
+// wave's own ends -- to dst as [T][2][bins] complex64, the values launch_stft_rows gives for the whole wave.  fmt 0: `wave` is planar
+// float32 [2][n]; otherwise interleaved frames of `channels` (1: up-mixed) samples in that vr_pcm_format, read through WavePcmIn.  The
+// host keeps 0 <= start and start + T <= 1 + n / hop: the kernel checks samples against n, never rows against the song.
+struct CropSeg { const void* wave; long long n; long long start; float2* dst; int T; int fmt; int channels; int reserved; };
+bool stft_crops_supported(int n_fft, int hop);           // no device: the frame-tiled path takes this n_fft at hop == n_fft / 2
+void launch_stft_crops(const FFTPlan& pl, const CropSeg* table_dev, int entries, int max_T, double rows_total, hipStream_t st);
 void launch_istft_masked_pcm16(const FFTPlan& pl, const float2* spec, int hop, int T, bool cplx, const float* mask_a, int Wa,
                                const float* mask_b, int Wb, int shift, const float* wgt, int which, int16_t* out, hipStream_t st);
 // mag_pad [2][bins][Wpad] (pre-zeroed) <- |spec| at column pad_l + t; maxima into stats:

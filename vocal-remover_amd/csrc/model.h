@@ -157,12 +157,28 @@ struct StreamState {
 struct ResidentCrop { int song, mix_song; long long start, mix_start; };        // layout-compatible with vr_crop
 struct ResidentWindow { int song, reserved; long long start; float scale; };    // layout-compatible with vr_window
 struct PeakCand;
+// A second kind, fixed at creation, the WAVE store: a song is its two aligned waves -- planar float32 [2][n], or
+// the file's interleaved sample bytes as they are -- in one slab each (X, y then point to those), rows = 1 + n / hop, and every entry
+// point forms the rows it needs with the crop-table form of the frame-tiled STFT (launch_stft_crops) from the store's own FFT plan.
 struct ResidentSet {
-    struct Song { float2* X; float2* y; long long rows; };
+    struct Song {
+        float2* X; float2* y; long long rows;
+        long long n = 0;                                                        // (wave store) samples per channel
+        int fmt[2] = {0, 0}, channels[2] = {2, 2};                              // (wave store) per slab: 0 = planar float32, else vr_pcm_format
+    };
     int device, bins;
     std::vector<Song> songs;
     long long bytes = 0;
+    bool waves = false;                                                         // the store kind
+    int n_fft = 0, hop = 0;                                                     // (wave store)
+    FFTPlan plan{};                                                             // (wave store) window and twiddles from fft_plan_create
     ResidentSet(int device, int bins);
+    ResidentSet(int device, int n_fft, int hop);                                // the wave store
+    // (wave store) one song from two float waves [2][n], host or device / from two blocks of interleaved sample bytes -> song index
+    int add_waves(const float* mix, const float* inst, bool on_dev, long long n);
+    int add_pcm(const void* mix, const void* inst, bool on_dev, long long frames, const int* channels, const int* fmt);
+    // one CropSeg for rows [start, start + T) of slab `which` (0 = mixture, 1 = instrumental) of a song of the wave store
+    CropSeg crop_seg(int song, int which, long long start, int T, float2* dst) const;
     ~ResidentSet();
     ResidentSet(const ResidentSet&) = delete;
     ResidentSet& operator=(const ResidentSet&) = delete;
@@ -176,6 +192,11 @@ private:
     char* stage[2] = {nullptr, nullptr};
     hipEvent_t drained[2] = {nullptr, nullptr};
     void upload(float2* dst, const float* src, size_t n_bytes);
+    int add_slabs(const void* const src[2], const size_t slab[2], bool on_dev, const Song& proto, const char* who);
+    // (wave store) vr_dataset_peak's bounded scratch: kPeakChunkRows rows of both slabs and a table of two entries, made at the first peak
+    static constexpr int kPeakChunkRows = 1024;
+    char* peak_rows = nullptr;
+    float peak_waves(int song, float* at, int* slab, long long* index);
 };
 
 // ---- the train-form head (train.hip): mask head -> loss -> dmask -> dlogit -> thin weight and data gradients of one feature tensor f3
@@ -324,6 +345,7 @@ public:
                           int batchsize, float* const* y, float* const* v, bool out_on_dev, const long long* capacity, long long* n_out,
                           const int* channels = nullptr, const int* fmt = nullptr);      // fmt given (vr_stream_push_many_pcm): wave[k] is bytes
     void stream_close(StreamState* S);
+    long long pipeline_buffer(bool release);             // bytes of aug_buf held before the call; release: free it
     void arena_bytes(long long* staging, long long* workspace) const { *staging = (long long)io.cap; *workspace = (long long)ws.cap; }
 
     // ---- debug / test hooks ----
@@ -356,6 +378,7 @@ public:
     void profile_begin();
     void augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
                      int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
+    void wave_store_check(const ResidentSet& set, const char* who, int B) const;
     void dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
                            float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
     void dataset_windows_api(const ResidentSet& set, const ResidentWindow* w, int B, int T, float* Xmag, float* ymag, bool out_on_dev,

@@ -40,6 +40,10 @@ template <class SRC> using PairLocal = typename std::conditional<kPair<SRC>, Wav
 // SRC = const WaveTriple (the weighted SDR term): the same with three passes -- the mixture, the target, the estimate.
 template <class SRC> constexpr bool kTriple = std::is_same<SRC, const WaveTriple>::value;
 template <class SRC> using TripleLocal = typename std::conditional<kTriple<SRC>, WaveTriple, int>::type;
+// SRC = const CropSeg (the wave store of vr_dataset_*): `src` is a table with one entry per signal and blockIdx.z picks
+// the entry; the workgroup computes frames of that entry's own wave, counted from the entry's first row, and stores them as rows.
+template <class SRC> constexpr bool kCrops = std::is_same<SRC, const CropSeg>::value;
+template <class SRC> using CropLocal = typename std::conditional<kCrops<SRC>, CropSeg, int>::type;
 
 // sample p of channel ch of a stream: the tail kept from earlier steps, then the step's block; zero outside [0, L)
 __device__ __forceinline__ float stream_sample(const StreamSeg& sg, int ch, long long p) {
@@ -171,6 +175,12 @@ struct WavePcmIn {                           // interleaved frames of 1 or 2 cha
     int ch;
     __device__ __forceinline__ float at(long long p) const { return pcm_decode(in.bytes, in.fmt, in.channels, p, ch); }
 };
+struct WaveCropIn {                          // a crop-table entry's wave: planar float32 (fmt 0) or the file's sample bytes
+    WaveF32In f;
+    WavePcmIn p;
+    int fmt;
+    __device__ __forceinline__ float at(long long i) const { return fmt ? p.at(i) : f.at(i); }
+};
 struct WaveGradIn {                          // the wave gradient of the SDR term over the iSTFT's envelope: (alpha y + beta p)[p] / env(p)
     const float* yw;
     const float* pw;
@@ -224,6 +234,9 @@ struct WavePcm16Out {                        // interleaved int16 [samples][2] b
 // const PseudoSeg* (SRC = const SongSeg): the pair form -- one PseudoSeg per song beside the song table.  The workgroup
 // runs its frame tile twice with the same arithmetic: first the song's instrumental (`inst_wave`), stored to `inst` as vr_stft stores it,
 // then the table's mixture, of which only D = X - Y goes to the table's `spec`; X itself is never written.
+// SRC = const CropSeg (no PCM type): the crop-table form -- blockIdx.z picks the entry, frame f of the grid is row
+// start + f of the entry's wave (the samples are checked against the wave's own n, so row 0 and the last rows meet the zero padding they
+// meet in the whole song's transform), the entry's fmt picks the reader, and the rows go to the entry's dst as the SpecRows form stores them.
 template <class SRC = const float, class... PCM>
 __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __restrict__ wave, long long L, int T, int F,
                                                          float2* __restrict__ spec, PCM... pcm) {
@@ -234,6 +247,7 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     constexpr bool kPcm = sizeof...(PCM) == 1 && !kGrad && !kPseudo && !kRows;
     static_assert(!kPseudo || kSongTable<SRC>, "the pair form is a song-table form");
     static_assert(!kRows || std::is_same<SRC, const float>::value, "the rows form is a one-song form");
+    static_assert(!kCrops<SRC> || sizeof...(PCM) == 0, "a crop entry names its own sample format");
     static_assert(sizeof...(PCM) <= 1, "one PCM source at most");
     static_assert(!kStream<SRC> || sizeof...(PCM) == 0 || std::is_same<typename FirstOr<void, PCM...>::type, const PcmIn*>::value,
                   "a stream's PCM source is a table of PcmIn beside the stream table");
@@ -244,8 +258,9 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
     float2* tile = lds2 + (size_t)TG * M;    // [bins][F]
     int t0 = blockIdx.x * F;
     const int ch = blockIdx.y;
-    typename std::conditional<kPcm, WavePcmIn, typename std::conditional<kGrad3, WaveGrad3In,
-                              typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type>::type in;
+    typename std::conditional<kCrops<SRC>, WaveCropIn, typename std::conditional<kPcm, WavePcmIn, typename std::conditional<kGrad3, WaveGrad3In,
+                              typename std::conditional<kGrad, WaveGradIn, WaveF32In>::type>::type>::type>::type in;
+    CropLocal<SRC> cs{};
     typename std::conditional<kGrad3, WaveGrad3, typename std::conditional<kGrad, WaveGrad, int>::type>::type gd{};
     StreamLocal<SRC> ss{};
     typename std::conditional<kPseudo, PseudoSeg, int>::type ps{};
@@ -267,6 +282,14 @@ __global__ __launch_bounds__(1024) void stft_tile_kernel(FFTPlan pl, SRC* __rest
             mix_wv = in.wv;
             in.wv = ps.inst_wave + (long long)ch * L;
         }
+    } else if constexpr (kCrops<SRC>) {              // blockIdx.z = entry; the grid is sized for the longest crop
+        cs = wave[blockIdx.z];
+        if (t0 >= cs.T) return;
+        L = cs.n; T = cs.T; spec = cs.dst;
+        in.fmt = cs.fmt;
+        in.f.wv = static_cast<const float*>(cs.wave) + (long long)ch * L;
+        in.p.in = PcmIn{static_cast<const uint8_t*>(cs.wave), cs.channels, cs.fmt};
+        in.p.ch = ch < cs.channels ? ch : cs.channels - 1;
     } else if constexpr (kGrad3) {                   // cy, cp, cx from the six batch-wide sums the triple iSTFT left in device memory
         gd = pcm_first(pcm...);
         const WsdrCoef c = wsdr_coefficients((double)gd.sums[0], (double)gd.sums[1], (double)gd.sums[2], (double)gd.sums[3],
@@ -295,7 +318,8 @@ second_pass:
         const int f = f0 + g;
         const bool live = f < nf;
         if (live) {
-            const long long start = (long long)(t0 + f) * hop - M;      // centre = True: n_fft/2 zeros in front
+            long long start = (long long)(t0 + f) * hop - M;            // centre = True: n_fft/2 zeros in front
+            if constexpr (kCrops<SRC>) start += cs.start * hop;         // (frame f of a crop is row start + f of its song)
             for (int m = tid; m < M; m += 256) {
                 const long long p = start + 2 * m;
                 float v0, v1;
@@ -330,7 +354,7 @@ second_pass:
         }
         __syncthreads();
     }
-    if constexpr (kRows) {                           // [T][2][bins]: a frame's bins lie together, so consecutive lanes run along k
+    if constexpr (kRows || kCrops<SRC>) {            // [T][2][bins]: a frame's bins lie together, so consecutive lanes run along k
         // (the tile is [bins][F], so these LDS reads stride F values and conflict on banks; lanes along f would read it conflict-free
         // and scatter the global stores over F rows instead.  Coalesced stores were preferred: profiles/pitch.md has the kernel's share)
         for (int idx = threadIdx.x; idx < bins * nf; idx += 1024) {
@@ -980,6 +1004,27 @@ void launch_stft_rows(const FFTPlan& pl, const float* wave, long long L, int T, 
     prof_note(0.0, 2.0 * (4.0 * (double)L + 8.0 * (double)bins * T));
     VR_LAUNCH((stft_tile_kernel<const float, SpecRows>), dim3((unsigned)((T + F - 1) / F), 2), dim3(1024), lds, st, pl, wave, L, T, F, rows,
               SpecRows{});
+    VR_HIP(hipGetLastError());
+}
+
+bool stft_crops_supported(int n_fft, int hop) {
+    if (n_fft <= 0 || (n_fft & (n_fft - 1))) return false;
+    return tiled_signal_path(FFTPlan{n_fft, 0, nullptr, nullptr}, hop);
+}
+
+// rows_total: the rows the call writes, both channels of every entry counted once (the profiler's byte note)
+void launch_stft_crops(const FFTPlan& pl, const CropSeg* table_dev, int entries, int max_T, double rows_total, hipStream_t st) {
+    if (entries <= 0 || max_T <= 0) return;
+    const int M = pl.n_fft / 2, bins = M + 1;
+    int F = tile_frames(pl, 0);
+    if (F > 16) F = 16;
+    F = F / TG * TG;
+    const size_t lds = (size_t)TG * M * 8 + (size_t)bins * F * 8;
+    static std::atomic<unsigned long long> attr_done{0};
+    ensure_lds_attr(attr_done, reinterpret_cast<const void*>(stft_tile_kernel<const CropSeg>), 160 * 1024);
+    prof_note(0.0, rows_total * 2.0 * (4.0 * (double)M + 8.0 * (double)bins));      // a row reads one hop of new samples a channel
+    VR_LAUNCH((stft_tile_kernel<const CropSeg>), dim3((unsigned)((max_T + F - 1) / F), 2, (unsigned)entries), dim3(1024), lds, st, pl, table_dev,
+              0LL, 0, F, (float2*)nullptr);
     VR_HIP(hipGetLastError());
 }
 

@@ -1,10 +1,12 @@
 // Training executor: forward in train mode (model.hip) records a tape; this file walks it backwards
 // (train.py:81-96: loss = L1(mask*X, y); (loss/accumulation_steps).backward(); optimizer.step()).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
 
 #include "model.h"
+#include "pcm.h"
 
 namespace vr {
 
@@ -622,6 +624,19 @@ void Model::aug_reserve(size_t need) {
     aug_cap = need + (need >> 3);
 }
 
+// vr_pipeline_buffer: what the handle holds for the input pipeline (tables, host outputs and, over a wave store, the rows of a batch), and
+// its release; the next call that needs it allocates it again
+long long Model::pipeline_buffer(bool release) {
+    const long long held = (long long)aug_cap;
+    if (release && aug_buf) {
+        DeviceGuard dev_guard(device);
+        VR_HIP(hipStreamSynchronize(stream));
+        VR_HIP(hipFree(aug_buf));
+        aug_buf = nullptr; aug_cap = 0;
+    }
+    return held;
+}
+
 // Training input pipeline (lib/dataset.py:105-120 after the random draws and the file reads), see augment.hip.
 void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
                         int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex) {
@@ -666,6 +681,15 @@ ResidentSet::ResidentSet(int device_, int bins_) : device(device_), bins(bins_) 
     VR_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
 }
 
+ResidentSet::ResidentSet(int device_, int n_fft_, int hop_) : device(device_), bins(n_fft_ / 2 + 1), waves(true), n_fft(n_fft_), hop(hop_) {
+    DeviceGuard dev_guard(device);
+    fft_plan_create(plan, n_fft);
+    if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) {
+        (void)hipFree(plan.twiddle); (void)hipFree(plan.window);
+        throw Error(-1, "vr_dataset_create_waves: hipStreamCreateWithFlags failed");
+    }
+}
+
 ResidentSet::~ResidentSet() {
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
@@ -673,6 +697,9 @@ ResidentSet::~ResidentSet() {
     if (up) (void)hipStreamSynchronize(up);
     for (Song& s : songs) { (void)hipFree(s.X); (void)hipFree(s.y); }
     if (peak_ws) (void)hipFree(peak_ws);
+    if (peak_rows) (void)hipFree(peak_rows);
+    if (plan.twiddle) (void)hipFree(plan.twiddle);
+    if (plan.window) (void)hipFree(plan.window);
     for (int i = 0; i < 2; ++i) {
         if (stage[i]) (void)hipHostFree(stage[i]);
         if (drained[i]) (void)hipEventDestroy(drained[i]);
@@ -703,6 +730,7 @@ void ResidentSet::upload(float2* dst, const float* src, size_t n_bytes) {
 }
 
 int ResidentSet::add(const float* X, const float* y, long long rows) {
+    VR_CHECK(!waves, -2, "vr_dataset_add: this store holds waves (vr_dataset_create_waves): add songs with vr_dataset_add_waves or vr_dataset_add_pcm");
     DeviceGuard dev_guard(device);
     VR_CHECK(rows > 0, -2, "vr_dataset_add: rows must be positive");
     const size_t slab = (size_t)rows * 2 * bins * sizeof(float2);
@@ -728,11 +756,142 @@ int ResidentSet::add(const float* X, const float* y, long long rows) {
     return (int)songs.size() - 1;
 }
 
+// ---- the wave store (vr_dataset_create_waves) --------------------------------------------------------------------
+// Two slabs of one song, allocated and filled as ResidentSet::add does: host memory in bounded pieces through the pinned staging, device
+// memory in one copy on the store's stream.  A slab of sample bytes is rounded up to whole 32-bit words (pcm.h reads aligned words).
+int ResidentSet::add_slabs(const void* const src[2], const size_t slab[2], bool on_dev, const Song& proto, const char* who) {
+    char* dev[2] = {nullptr, nullptr};
+    const size_t alloc[2] = {(slab[0] + 3) & ~size_t(3), (slab[1] + 3) & ~size_t(3)};
+    for (int i = 0; i < 2; ++i) {
+        if (hipMalloc(reinterpret_cast<void**>(&dev[i]), alloc[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            if (dev[0]) (void)hipFree(dev[0]);
+            throw Error(-4, std::string(who) + ": hipMalloc of " + std::to_string(slab[i]) + " bytes failed (song of " + std::to_string(proto.n) +
+                                " samples needs " + std::to_string(slab[0]) + " + " + std::to_string(slab[1]) + "; the store already holds " +
+                                std::to_string(bytes) + " bytes in " + std::to_string(songs.size()) + " songs)");
+        }
+    }
+    try {
+        for (int i = 0; i < 2; ++i) {
+            if (!on_dev) { upload(reinterpret_cast<float2*>(dev[i]), static_cast<const float*>(src[i]), slab[i]); continue; }
+            VR_HIP(hipMemcpyAsync(dev[i], src[i], slab[i], hipMemcpyDeviceToDevice, up));
+            VR_HIP(hipStreamSynchronize(up));
+        }
+    } catch (...) {
+        (void)hipFree(dev[0]); (void)hipFree(dev[1]);
+        throw;
+    }
+    Song s = proto;
+    s.X = reinterpret_cast<float2*>(dev[0]);
+    s.y = reinterpret_cast<float2*>(dev[1]);
+    songs.push_back(s);
+    bytes += (long long)(alloc[0] + alloc[1]);
+    return (int)songs.size() - 1;
+}
+
+int ResidentSet::add_waves(const float* mix, const float* inst, bool on_dev, long long n) {
+    VR_CHECK(waves, -2, "vr_dataset_add_waves: this store holds spectrogram rows (vr_dataset_create): add songs with vr_dataset_add");
+    VR_CHECK(n > 0 && n / hop < (1LL << 28), -2, "vr_dataset_add_waves: n must be positive (and below 2^28 hops)");
+    VR_CHECK(!on_dev || ((reinterpret_cast<uintptr_t>(mix) | reinterpret_cast<uintptr_t>(inst)) & 3) == 0, -2,
+             "vr_dataset_add_waves: a device wave must be 4-byte aligned");
+    DeviceGuard dev_guard(device);
+    Song proto{nullptr, nullptr, 1 + n / hop};
+    proto.n = n;
+    const void* const src[2] = {mix, inst};
+    const size_t slab[2] = {(size_t)2 * n * sizeof(float), (size_t)2 * n * sizeof(float)};
+    return add_slabs(src, slab, on_dev, proto, "vr_dataset_add_waves");
+}
+
+int ResidentSet::add_pcm(const void* mix, const void* inst, bool on_dev, long long frames, const int* channels, const int* fmt) {
+    VR_CHECK(waves, -2, "vr_dataset_add_pcm: this store holds spectrogram rows (vr_dataset_create): add songs with vr_dataset_add");
+    VR_CHECK(frames > 0 && frames / hop < (1LL << 28), -2, "vr_dataset_add_pcm: frames must be positive (and below 2^28 hops)");
+    Song proto{nullptr, nullptr, 1 + frames / hop};
+    proto.n = frames;
+    const void* const src[2] = {mix, inst};
+    size_t slab[2];
+    for (int i = 0; i < 2; ++i) {
+        const std::string who = std::string("vr_dataset_add_pcm: ") + (i ? "instrumental: " : "mixture: ");
+        VR_CHECK(pcm_fmt_ok(fmt[i]), -2, who + "unknown sample format " + std::to_string(fmt[i]));
+        VR_CHECK(channels[i] == 1 || channels[i] == 2, -2, who + "channels must be 1 or 2, got " + std::to_string(channels[i]));
+        proto.fmt[i] = fmt[i];
+        proto.channels[i] = channels[i];
+        slab[i] = (size_t)frames * channels[i] * pcm_sample_bytes(fmt[i]);
+    }
+    DeviceGuard dev_guard(device);
+    // (the device copy starts at the slab's aligned first byte, so a source buffer may lie anywhere, host or device)
+    return add_slabs(src, slab, on_dev, proto, "vr_dataset_add_pcm");
+}
+
+CropSeg ResidentSet::crop_seg(int song, int which, long long start, int T, float2* dst) const {
+    const Song& s = songs[song];
+    return CropSeg{which ? static_cast<const void*>(s.y) : static_cast<const void*>(s.X), s.n, start, dst, T, s.fmt[which], s.channels[which], 0};
+}
+
+// vr_dataset_peak of a wave store: the song's rows pass through the store's own scratch kPeakChunkRows at a time -- one crop launch for
+// both slabs, then the two launches of launch_song_peak on that chunk -- and the chunk candidates are merged here by the kernel's rule: the
+// larger key, ties to the lowest (slab, index).  Every chunk's candidate is copied to its own host slot; one wait at the end.
+float ResidentSet::peak_waves(int song, float* at, int* slab, long long* index) {
+    DeviceGuard dev_guard(device);
+    const Song& s = songs[song];
+    auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t chunk_b = up256((size_t)kPeakChunkRows * 2 * bins * sizeof(float2)), tab_b = up256(2 * sizeof(CropSeg));
+    const size_t cand_b = up256((size_t)(kPeakParts + 1) * sizeof(PeakCand));
+    if (!peak_rows) {
+        const size_t ws_bytes = 2 * chunk_b + tab_b + cand_b;
+        if (hipMalloc(reinterpret_cast<void**>(&peak_rows), ws_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            peak_rows = nullptr;
+            throw Error(-4, "vr_dataset_peak: hipMalloc of " + std::to_string(ws_bytes) + " bytes of scratch failed (the store holds " +
+                                std::to_string(bytes) + " bytes in " + std::to_string(songs.size()) + " songs)");
+        }
+    }
+    float2* rx = reinterpret_cast<float2*>(peak_rows);
+    float2* ry = reinterpret_cast<float2*>(peak_rows + chunk_b);
+    CropSeg* tab = reinterpret_cast<CropSeg*>(peak_rows + 2 * chunk_b);
+    PeakCand* cand_dev = reinterpret_cast<PeakCand*>(peak_rows + 2 * chunk_b + tab_b);
+    const int chunks = (int)((s.rows + kPeakChunkRows - 1) / kPeakChunkRows);
+    std::vector<PeakCand> cand((size_t)chunks);
+    std::vector<CropSeg> segs((size_t)chunks * 2);
+    for (int c = 0; c < chunks; ++c) {
+        const long long r0 = (long long)c * kPeakChunkRows;
+        const int T = (int)std::min<long long>(kPeakChunkRows, s.rows - r0);
+        segs[2 * c] = crop_seg(song, 0, r0, T, rx);
+        segs[2 * c + 1] = crop_seg(song, 1, r0, T, ry);
+        VR_HIP(hipMemcpyAsync(tab, &segs[2 * c], 2 * sizeof(CropSeg), hipMemcpyHostToDevice, up));
+        launch_stft_crops(plan, tab, 2, T, 2.0 * T, up);
+        const long long n = (long long)T * 2 * bins;
+        launch_song_peak(rx, ry, n, cand_dev, up);
+        VR_HIP(hipMemcpyAsync(&cand[c], cand_dev + song_peak_parts(n), sizeof(PeakCand), hipMemcpyDeviceToHost, up));
+    }
+    VR_HIP(hipStreamSynchronize(up));
+    bool bad = false, have = false;
+    float key = -1.f, re = 0.f, im = 0.f;
+    // (no candidate at all -- every element NaN: slab and index as the rows store derives them from the kernel's empty position ~0)
+    int best_slab = 1;
+    long long best_index = -1 - s.rows * 2 * bins;
+    for (int c = 0; c < chunks; ++c) {
+        const long long r0 = (long long)c * kPeakChunkRows;
+        const long long n = std::min<long long>(kPeakChunkRows, s.rows - r0) * 2 * bins;
+        const PeakCand& r = cand[c];
+        bad = bad || r.bad;
+        if (r.pos >= 2ull * (unsigned long long)n) continue;                     // (every element of the chunk NaN: no candidate)
+        const int sl = r.pos >= (unsigned long long)n ? 1 : 0;
+        const long long idx = r0 * 2 * bins + (long long)(sl ? r.pos - (unsigned long long)n : r.pos);
+        const bool wins = !have || r.key > key || (r.key == key && (sl < best_slab || (sl == best_slab && idx < best_index)));
+        if (wins) { have = true; key = r.key; re = r.re; im = r.im; best_slab = sl; best_index = idx; }
+    }
+    if (at) { at[0] = re; at[1] = im; }
+    if (slab) *slab = best_slab;
+    if (index) *index = best_index;
+    return bad ? std::numeric_limits<float>::quiet_NaN() : numpy_cabsf(re, im);
+}
+
 // The peak of one song from its resident rows: two launches on the store's stream (augment.hip, SongPeak), one candidate back.  The
 // float is formed here, from the one element the device reports, by the operations numpy's np.abs performs on a complex64.
 float ResidentSet::peak(int song, float* at, int* slab, long long* index) {
     VR_CHECK(song >= 0 && song < (int)songs.size(), -2, "vr_dataset_peak: song " + std::to_string(song) + " out of range (the dataset holds " +
                                                             std::to_string(songs.size()) + ")");
+    if (waves) return peak_waves(song, at, slab, index);
     DeviceGuard dev_guard(device);
     const Song& s = songs[song];
     const long long n = s.rows * 2 * bins;
@@ -758,6 +917,14 @@ float ResidentSet::peak(int song, float* at, int* slab, long long* index) {
     return r.bad ? std::numeric_limits<float>::quiet_NaN() : numpy_cabsf(r.re, r.im);
 }
 
+// (wave store) what a handle must share with the store before it may cut anything from it: the transform's two sizes
+void Model::wave_store_check(const ResidentSet& set, const char* who, int B) const {
+    VR_CHECK(n_fft == set.n_fft && hop == set.hop, -2,
+             std::string(who) + ": the handle transforms at n_fft " + std::to_string(n_fft) + ", hop_length " + std::to_string(hop) +
+                 ", the wave store was created for n_fft " + std::to_string(set.n_fft) + ", hop_length " + std::to_string(set.hop));
+    VR_CHECK(B <= 16383, -2, std::string(who) + ": at most 16383 samples per call on a wave store (four table entries each)");
+}
+
 // Windows of resident songs (vr_dataset_windows): every entry is checked on the host, the table goes to the handle's aug_buf in one copy
 // and the SongWindows form of augment_kernel reads the rows where they lie.  A window may leave its song on either side (those rows are
 // zero), so the checks are the song index, start + T as an int64, and a finite scale.
@@ -766,11 +933,14 @@ void Model::dataset_windows_api(const ResidentSet& set, const ResidentWindow* w,
     VR_CHECK(set.device == device, -2, "vr_dataset_windows: the handle is on device " + std::to_string(device) + ", the dataset on device " +
                                            std::to_string(set.device));
     VR_CHECK(T > 0, -2, "vr_dataset_windows: T must be positive");
+    if (set.waves) wave_store_check(set, "vr_dataset_windows", B);
     const int bins = set.bins, n_songs = (int)set.songs.size();
     auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t tab_b = (size_t)B * sizeof(SongWindow), head = up256(tab_b);
     const size_t out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
     std::vector<SongWindow> tab((size_t)B);
+    std::vector<CropSeg> segs;                           // (wave store) two entries per window that meets its song
+    std::vector<int> seg_of;                             // ... and the sample each pair belongs to
     for (int b = 0; b < B; ++b) {
         const std::string who = "vr_dataset_windows: sample " + std::to_string(b) + ": ";
         VR_CHECK(w[b].song >= 0 && w[b].song < n_songs, -2, who + "song " + std::to_string(w[b].song) + " out of range (the dataset holds " +
@@ -780,9 +950,38 @@ void Model::dataset_windows_api(const ResidentSet& set, const ResidentWindow* w,
         VR_CHECK(std::isfinite(w[b].scale), -2, who + "scale " + std::to_string(w[b].scale) + " is not finite");
         const ResidentSet::Song& s = set.songs[w[b].song];
         tab[b] = SongWindow{s.X, s.y, s.rows, w[b].start, w[b].scale, 0};
+        if (set.waves) {
+            // the rows of the window that lie inside the song, [lo, hi), are formed in scratch; the entry then describes a song of hi - lo
+            // rows that the window meets at start - lo, so the rows outside stay the kernel's zeros
+            const long long lo = std::max<long long>(w[b].start, 0), hi = std::min<long long>(w[b].start + T, s.rows);
+            tab[b] = SongWindow{nullptr, nullptr, std::max<long long>(hi - lo, 0), w[b].start - lo, w[b].scale, 0};
+            if (hi > lo) {
+                seg_of.push_back(b);
+                segs.push_back(set.crop_seg(w[b].song, 0, lo, (int)(hi - lo), nullptr));
+                segs.push_back(set.crop_seg(w[b].song, 1, lo, (int)(hi - lo), nullptr));
+            }
+        }
     }
     DeviceGuard dev_guard(device);
-    aug_reserve(head + (out_on_dev ? 0 : 2 * up256(out_b)));
+    const size_t out_all = out_on_dev ? 0 : 2 * up256(out_b);
+    const size_t seg_b = up256(segs.size() * sizeof(CropSeg)), rows_b = up256((size_t)T * 2 * bins * sizeof(float2));
+    // (wave store) reserved for the most the call's B and T can need -- both slabs of every window -- so that the buffer's size follows
+    // from B and T alone and a later call of the same shape never grows it
+    aug_reserve(head + out_all + (set.waves ? up256((size_t)2 * B * sizeof(CropSeg)) + (size_t)2 * B * rows_b : 0));
+    if (!segs.empty()) {
+        char* scratch = aug_buf + head + out_all + seg_b;
+        int max_T = 0;
+        double rows_total = 0.0;
+        for (size_t e = 0; e < segs.size(); ++e) {
+            segs[e].dst = reinterpret_cast<float2*>(scratch + e * rows_b);
+            max_T = std::max(max_T, segs[e].T);
+            rows_total += segs[e].T;
+            if (e & 1) { tab[seg_of[e >> 1]].X = segs[e - 1].dst; tab[seg_of[e >> 1]].y = segs[e].dst; }
+        }
+        CropSeg* dseg = reinterpret_cast<CropSeg*>(aug_buf + head + out_all);
+        VR_HIP(hipMemcpyAsync(dseg, segs.data(), segs.size() * sizeof(CropSeg), hipMemcpyHostToDevice, stream));
+        launch_stft_crops(set.plan, dseg, (int)segs.size(), max_T, rows_total, stream);
+    }
     VR_HIP(hipMemcpyAsync(aug_buf, tab.data(), tab_b, hipMemcpyHostToDevice, stream));
     float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(aug_buf + head);
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(aug_buf + head + up256(out_b));
@@ -803,6 +1002,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
     VR_CHECK(set.device == device, -2, "vr_dataset_batch: the handle is on device " + std::to_string(device) + ", the dataset on device " +
                                            std::to_string(set.device));
     VR_CHECK(T > 0, -2, "vr_dataset_batch: T must be positive");
+    if (set.waves) wave_store_check(set, "vr_dataset_batch", B);
     const AugDesc* dh = static_cast<const AugDesc*>(desc);
     const int bins = set.bins, n_songs = (int)set.songs.size();
     std::vector<char> host;
@@ -812,6 +1012,8 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
     const size_t head = up256(tab_b) + up256(desc_b) + (rw ? up256(rw_b) : 0);
     host.resize(head);
     AugCrops* tab = reinterpret_cast<AugCrops*>(host.data());
+    std::vector<CropSeg> segs;                           // (wave store) launch 1's table: X, y and, with bit 3, the partners of every sample
+    std::vector<int> first((size_t)(set.waves ? B : 0)); // ... and each sample's first entry in it
     auto rows_at = [&](int b, const char* which, int song, long long start) -> size_t {
         const std::string who = "vr_dataset_batch: sample " + std::to_string(b) + ": " + which;
         VR_CHECK(song >= 0 && song < n_songs, -2, who + "song " + std::to_string(song) + " out of range (the dataset holds " +
@@ -829,6 +1031,11 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
         const size_t o = rows_at(b, "", crops[b].song, crops[b].start);
         const ResidentSet::Song& s = set.songs[crops[b].song];
         tab[b] = AugCrops{s.X + o, s.y + o, s.X + o, s.y + o};
+        if (set.waves) {                                 // (the pointers are set below, once the scratch is reserved)
+            first[b] = (int)segs.size();
+            segs.push_back(set.crop_seg(crops[b].song, 0, crops[b].start, T, nullptr));
+            segs.push_back(set.crop_seg(crops[b].song, 1, crops[b].start, T, nullptr));
+        }
         if (flags & 8) {
             VR_CHECK(crops[b].mix_song >= 0, -2, "vr_dataset_batch: sample " + std::to_string(b) + ": mixup flagged but mix_song is " +
                                                      std::to_string(crops[b].mix_song));
@@ -836,13 +1043,35 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
             const ResidentSet::Song& m = set.songs[crops[b].mix_song];
             tab[b].X_mix = m.X + om;
             tab[b].y_mix = m.y + om;
+            if (set.waves) {
+                segs.push_back(set.crop_seg(crops[b].mix_song, 0, crops[b].mix_start, T, nullptr));
+                segs.push_back(set.crop_seg(crops[b].mix_song, 1, crops[b].mix_start, T, nullptr));
+            }
         }
     }
     std::memcpy(host.data() + up256(tab_b), dh, desc_b);
     if (rw) std::memcpy(host.data() + up256(tab_b) + up256(desc_b), rw, rw_b);
 
     DeviceGuard dev_guard(device);
-    aug_reserve(head + (out_on_dev ? 0 : 2 * up256(out_b)));
+    const size_t out_all = out_on_dev ? 0 : 2 * up256(out_b);
+    const size_t seg_b = up256(segs.size() * sizeof(CropSeg)), rows_b = up256((size_t)T * 2 * bins * sizeof(float2));
+    // (wave store) reserved for the most the call's B and T can need -- four signals a sample and the reduction weight, whatever the flags
+    // of this batch -- so that the buffer's size follows from B and T alone and a later batch with more partners never grows it
+    aug_reserve(set.waves ? up256(tab_b) + up256(desc_b) + up256(rw_b) + out_all + up256((size_t)4 * B * sizeof(CropSeg)) + (size_t)4 * B * rows_b
+                          : head + out_all);
+    if (set.waves) {
+        // launch 1: the crop-table STFT writes every signal's T rows into the handle's scratch; launch 2 below reads them through the
+        // AugCrops table exactly as it reads the slabs of a rows store
+        char* scratch = aug_buf + head + out_all + seg_b;
+        for (size_t e = 0; e < segs.size(); ++e) segs[e].dst = reinterpret_cast<float2*>(scratch + e * rows_b);
+        for (int b = 0; b < B; ++b) {
+            const int e = first[b], em = (dh[b].flags & 8) ? e + 2 : e;
+            tab[b] = AugCrops{segs[e].dst, segs[e + 1].dst, segs[em].dst, segs[em + 1].dst};
+        }
+        CropSeg* dseg = reinterpret_cast<CropSeg*>(aug_buf + head + out_all);
+        VR_HIP(hipMemcpyAsync(dseg, segs.data(), segs.size() * sizeof(CropSeg), hipMemcpyHostToDevice, stream));
+        launch_stft_crops(set.plan, dseg, (int)segs.size(), T, (double)segs.size() * T, stream);
+    }
     VR_HIP(hipMemcpyAsync(aug_buf, host.data(), head, hipMemcpyHostToDevice, stream));
     const AugCrops* dtab = reinterpret_cast<const AugCrops*>(aug_buf);
     const AugDesc* dd = reinterpret_cast<const AugDesc*>(aug_buf + up256(tab_b));

@@ -236,6 +236,26 @@ class _Resident(object):
             ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
         return X_mag, y_mag
 
+    def _training_batch(self, h, indices):
+        """The draws of `indices` (self.plan) packed as crops and descriptors and cut from the store; self._song_of(paths) names the
+        song of a plan's pair in it.  One statement of the packing for the rows set and the wave set."""
+        plans = [self.plan(i) for i in indices]
+        B = len(plans)
+        crops, desc = (native.Crop * B)(), (_Aug * B)()
+        need_rw = False
+        for b, p in enumerate(plans):
+            flags, coef_mix, lam, mix_song, mix_start = p['flags'], 1.0, 1.0, -1, 0
+            if p['mix'] is not None:
+                m = p['mix']
+                flags |= 8 | (m['flags'] << 4)
+                coef_mix, lam, mix_song, mix_start = m['coef'], m['lam'], self._song_of(m['paths']), m['start']
+            need_rw = need_rw or bool(flags & (1 | 16))
+            crops[b] = native.Crop(self._song_of(p['paths']), mix_song, p['start'], mix_start)
+            desc[b] = _Aug(p['coef'], coef_mix, lam, flags)
+        if need_rw and self.reduction_weight is None:
+            raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
+        return self._batch(h, crops, desc, self.reduction_weight, self.cropsize)
+
     @property
     def nbytes(self):
         """Bytes of the set on the device: what the upload will take before the first batch, what the store holds after it."""
@@ -334,22 +354,10 @@ class ResidentTrainingSet(_Resident):
         h = self._handle()
         if self._store is None:
             self._upload(h.device)
-        plans = [self.plan(i) for i in indices]
-        B = len(plans)
-        crops, desc = (native.Crop * B)(), (_Aug * B)()
-        need_rw = False
-        for b, p in enumerate(plans):
-            flags, coef_mix, lam, mix_song, mix_start = p['flags'], 1.0, 1.0, -1, 0
-            if p['mix'] is not None:
-                m = p['mix']
-                flags |= 8 | (m['flags'] << 4)
-                coef_mix, lam, mix_song, mix_start = m['coef'], m['lam'], self._song[m['paths']], m['start']
-            need_rw = need_rw or bool(flags & (1 | 16))
-            crops[b] = native.Crop(self._song[p['paths']], mix_song, p['start'], mix_start)
-            desc[b] = _Aug(p['coef'], coef_mix, lam, flags)
-        if need_rw and self.reduction_weight is None:
-            raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
-        return self._batch(h, crops, desc, self.reduction_weight, self.cropsize)
+        return self._training_batch(h, indices)
+
+    def _song_of(self, paths):
+        return self._song[paths]
 
 
 def _npz_member_shape(path, key):
@@ -503,6 +511,177 @@ class ResidentSongValidationSet(_Resident):
         return X_mag, y_mag
 
 
+# ---- the resident sets cut from the songs' WAVES ------------------------------------------------------------------------------------------
+# At hop == n_fft / 2 the cached rows are twice the bytes of the float32 samples they came from, four times the file's PCM16 frames, and
+# the rows of a crop depend on the song's samples alone.  These two sets keep every song as its aligned pair of waves in a wave store
+# (native.Dataset.waves) and let each batch form the rows of its crops on the device: no cache files, half or a quarter of the device
+# bytes, the same batches bit for bit.
+def _wave_len(w):
+    """samples per channel of one wave of a wave row: a float32 [2, n] array or cuda tensor, or an audio.RawPcm"""
+    return int(w.frames) if hasattr(w, 'frames') else int(w.shape[1])
+
+
+def _wave_nbytes(w):
+    """device bytes of one wave's slab: planar float32, or the sample bytes rounded up to whole 32-bit words"""
+    if hasattr(w, 'frames'):
+        return (int(w.frames) * w.channels * native.PCM_SAMPLE_BYTES[w.fmt] + 3) // 4 * 4
+    return 2 * int(w.shape[1]) * 4
+
+
+class _ResidentWaves(_Resident):
+    """What the two wave sets share: the songs of `rows` ([[mix, inst, peak or None], ...]) by the identity of their two objects, the
+    bytes they need, the model's transform sizes, the upload and the peaks taken at upload."""
+
+    def _index(self, rows, what, max_bytes):
+        self._song = {}                        # (id(mix), id(inst)) -> index in the store, in first-seen order
+        self._waves = []                       # the pair of every song, in that order (kept alive: the ids stay theirs)
+        need = 0
+        for mix, inst, _ in rows:
+            if _wave_len(mix) != _wave_len(inst):
+                raise ValueError('%s: a pair of %d and %d samples; the two waves of a row are aligned and equally long'
+                                 % (what, _wave_len(mix), _wave_len(inst)))
+            if hasattr(mix, 'frames') != hasattr(inst, 'frames'):
+                raise ValueError('%s: a pair is two float waves or two audio.RawPcm' % what)
+            key = (id(mix), id(inst))
+            if key in self._song:
+                continue
+            self._song[key] = len(self._waves)
+            self._waves.append((mix, inst))
+            need += _wave_nbytes(mix) + _wave_nbytes(inst)
+        self._need = need
+        _check_capacity('%s: %d songs' % (what, len(self._waves)), need, max_bytes)
+
+    def _fft(self):
+        if self.model is None:
+            raise RuntimeError('%s needs the model (its n_fft and hop_length size the rows, its device holds the set); no CPU fallback'
+                               % type(self).__name__)
+        return int(self.model.n_fft), int(self.model.hop_length)
+
+    def _song_of(self, row):
+        return self._song[(id(row[0]), id(row[1]))]
+
+    def _upload_waves(self, device, rows):
+        n_fft, hop = self._fft()
+        store = native.Dataset.waves(device, n_fft, hop)
+        try:
+            for song, (mix, inst) in enumerate(self._waves):
+                got = store.add_pcm(mix, inst) if hasattr(mix, 'frames') else store.add_waves(mix, inst)
+                assert got == song
+            for row in rows:
+                if row[2] is None:
+                    row[2] = store.peak(self._song_of(row))
+        except Exception:
+            store.close()
+            raise
+        return store
+
+
+class ResidentWaveTrainingSet(_ResidentWaves):
+    """ResidentTrainingSet without the cache: `wave_rows` is [[mix, inst, peak or None], ...] (load_wave_rows), mix and inst the ALIGNED
+    waves of a pair -- float32 [2, n] numpy arrays or cuda tensors of one n, or two audio.RawPcm of equal frames (the files' own sample
+    bytes).  A song is identified by the identity of its two objects, so a list of rows * patches uploads each song once.  The numpy draws
+    are VocalRemoverTrainingSet.plan's, with 1 + n // hop_length rows for a song of n samples, so from one numpy seed `batch(indices)`
+    returns what ResidentTrainingSet.batch returns over caches of the same waves, bit for bit, and leaves the generator where that
+    leaves it.  A peak that is None is taken on the device at upload.  nbytes / max_bytes as ResidentTrainingSet: 2 * 2 * n * 4 bytes a
+    float song, the sample bytes a PCM song."""
+
+    def __init__(self, wave_rows, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None,
+                 complex_output=False):
+        self.training_set = [list(row) for row in wave_rows]
+        self.complex_output = bool(complex_output)
+        self.cropsize = cropsize
+        self.reduction_rate = reduction_rate
+        self.reduction_weight = None if reduction_weight is None else \
+            np.ascontiguousarray(np.asarray(reduction_weight, np.float32).reshape(-1))
+        self.mixup_rate = mixup_rate
+        self.mixup_alpha = mixup_alpha
+        self.model = model
+        self.max_bytes = max_bytes
+        self._index(self.training_set, 'ResidentWaveTrainingSet', max_bytes)
+
+    __len__ = VocalRemoverTrainingSet.__len__
+    _draw_aug = VocalRemoverTrainingSet._draw_aug
+    plan = VocalRemoverTrainingSet.plan          # the draws themselves: one statement of them for every training class
+
+    def _coef(self, row):
+        """VocalRemoverTrainingSet._coef with a message for a wave row: the row's first entry is a whole wave, not a path to print"""
+        if row[2] is None:
+            raise ValueError('wave row %d (%d samples): its peak is None and is taken on the device when the set is uploaded, at the first '
+                             'batch(); plan() before that needs rows with peaks' % (self._song_of(row), _wave_len(row[0])))
+        return float(row[2])
+
+    def read_npy_shape(self, wave):
+        """the shape the cache of this wave would have: plan() draws its start rows from it"""
+        n_fft, hop = self._fft()
+        return (1 + _wave_len(wave) // hop, 2, n_fft // 2 + 1)
+
+    def _ensure_store(self):
+        if self._store is None:
+            self._store = self._upload_waves(self._handle().device, self.training_set)
+
+    def batch(self, indices):
+        h = self._handle()
+        self._ensure_store()
+        return self._training_batch(h, indices)
+
+
+class ResidentWaveValidationSet(_ResidentWaves):
+    """ResidentSongValidationSet without the cache: `wave_rows` as for ResidentWaveTrainingSet, item k is window j of song i in
+    make_validation_set's order (validation_windows of 1 + n // hop_length rows), zero outside the song, times the float32 1 / peak.  A
+    batch is one vr_dataset_windows call on the wave store and equals ResidentSongValidationSet.batch over caches of the same waves, bit
+    for bit.  A peak that is None is taken on the device at upload; a peak of 0 or NaN raises ValueError naming the song."""
+
+    def __init__(self, wave_rows, cropsize, offset, model=None, max_bytes=None, complex_output=False):
+        self.song_rows = [list(row) for row in wave_rows]
+        self.cropsize, self.offset = int(cropsize), int(offset)
+        self.model = model
+        self.complex_output = bool(complex_output)
+        self.max_bytes = max_bytes
+        self._scale = None                     # per row of song_rows: float32 1 / peak, known after the upload
+        self._item_list = None                 # (row of song_rows, start row of the window), known once the model gives the hop
+        self._index(self.song_rows, 'ResidentWaveValidationSet', max_bytes)
+
+    @property
+    def _items(self):
+        if self._item_list is None:
+            _, hop = self._fft()
+            self._item_list = [(i, start) for i, row in enumerate(self.song_rows)
+                               for start in validation_windows(1 + _wave_len(row[0]) // hop, self.cropsize, self.offset)]
+        return self._item_list
+
+    def __len__(self):
+        return len(self._items)
+
+    def _upload(self, device):
+        store = self._upload_waves(device, self.song_rows)
+        try:
+            scale = []
+            for i, row in enumerate(self.song_rows):
+                peak = np.float32(row[2])
+                if not peak > 0:
+                    raise ValueError('wave row %d: the peak of the pair is %r, the song cannot be normalised' % (i, float(peak)))
+                scale.append(np.float32(1) / peak)
+        except Exception:
+            store.close()
+            raise
+        self._store, self._scale = store, scale
+
+    def batch(self, indices):
+        h = self._handle()
+        if self._store is None:
+            self._upload(h.device)
+        B, T = len(indices), self.cropsize
+        table = (native.Window * B)()
+        for b, k in enumerate(indices):
+            i, start = self._items[k]
+            table[b] = native.Window(self._song_of(self.song_rows[i]), 0, start, self._scale[i])
+        dev = torch.device('cuda', h.device)
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, self._store.bins, T), dev, 'vr_dataset_windows')
+        native.check(call(h.h, self._store.d, ctypes.cast(table, ctypes.c_void_p), B, T,
+                          ctypes.c_void_p(X_mag.data_ptr()), ctypes.c_void_p(y_mag.data_ptr()), 1))
+        return X_mag, y_mag
+
+
 class DeviceLoader(object):
     """Iterable stand-in for torch.utils.data.DataLoader(dataset, batch_size, shuffle) (train.py:242-247):
     yields (X_batch, y_batch) device tensors produced by one vr_augment_batch call per batch."""
@@ -607,6 +786,59 @@ def load_aligned_pair(mix_path, inst_path, sr):
     waves = [audio.load(p, sr=sr, mono=False, dtype=np.float32, res_type='kaiser_fast')[0] for p in (mix_path, inst_path)]
     waves = [np.asarray([w, w]) if w.ndim == 1 else w for w in waves]
     return align_wave_head_and_tail(waves[0], waves[1], sr)
+
+
+def _host_pair_window(a, b, sr):
+    """align_wave_head_and_tail's decisions as a window: -> (a_off, b_off, n), the pair being a[:, a_off:a_off + n], b[:, b_off:b_off + n]"""
+    from . import audio
+    from .spec_utils import _head_lag
+    (ta, (a0, a1)), (tb, (b0, b1)) = audio.trim(a), audio.trim(b)
+    w = native.pair_window_plan(a0, a1, b0, b1, _head_lag(ta, tb, sr))
+    return int(w.a_off), int(w.b_off), int(w.n)
+
+
+def _pcm_window(raw, off, n):
+    """frames [off, off + n) of a RawPcm, the bytes as they are"""
+    from . import audio
+    align = raw.channels * native.PCM_SAMPLE_BYTES[raw.fmt]
+    return audio.RawPcm(np.ascontiguousarray(raw.bytes[off * align:(off + n) * align]), raw.fmt, raw.channels, raw.sr, n)
+
+
+def load_wave_rows(filelist, sr, pairs_per_call=None, pcm=False):
+    """The rows ResidentWaveTrainingSet / ResidentWaveValidationSet take, [[mixture, instrumental, None], ...]: every pair of filelist
+    decoded and aligned as SpectrogramCache.pair does it -- load_aligned_pair, or, with pairs_per_call, spec_utils.align_pair_many on
+    that many pairs per library call -- and kept as float32 [2, n] waves; no cache is read or written, the peak is left to the upload.
+    pcm=True: a pair whose two files are RIFF/WAVE at `sr` in a format the device decodes keeps the files' own sample bytes, sliced to
+    the aligned window (audio.RawPcm; a quarter of the rows' bytes for PCM16) -- the decoded waves then serve the alignment only; any
+    other pair stays float."""
+    from . import audio
+    from .spec_utils import align_pair_many
+    filelist = [tuple(f) for f in filelist]
+    step = len(filelist) if pairs_per_call is None else max(int(pairs_per_call), 1)
+    rows = []
+    for g in range(0, len(filelist), max(step, 1)):
+        group = filelist[g:g + step]
+        waves = []
+        for pair in group:
+            ws = [audio.load(p, sr=sr, mono=False, dtype=np.float32, res_type='kaiser_fast')[0] for p in pair]
+            waves.append([np.asarray([w, w]) if w.ndim == 1 else w for w in ws])
+        if pairs_per_call is None:
+            windows = [_host_pair_window(a, b, sr) if pcm else None for a, b in waves]
+        else:
+            windows = [(int(w.a_off), int(w.b_off), int(w.n)) for w in align_pair_many([a for a, _ in waves], [b for _, b in waves], sr)]
+        for pair, (a, b), w in zip(group, waves, windows):
+            if w is None:                        # the reference's own statement sequence on the host
+                from .spec_utils import align_wave_head_and_tail
+                a, b = align_wave_head_and_tail(a, b, sr)
+                rows.append([np.ascontiguousarray(a), np.ascontiguousarray(b), None])
+                continue
+            a_off, b_off, n = w
+            raws = [audio.read_wav_raw(p) for p in pair] if pcm else [None, None]
+            if all(r is not None and r.sr == sr for r in raws):
+                rows.append([_pcm_window(raws[0], a_off, n), _pcm_window(raws[1], b_off, n), None])
+            else:
+                rows.append([np.ascontiguousarray(a[:, a_off:a_off + n]), np.ascontiguousarray(b[:, b_off:b_off + n]), None])
+    return rows
 
 
 def pseudo_cache_path(cache, inst_path):

@@ -134,7 +134,13 @@ _SIGNATURES = {
                                                 ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'vr_dataset_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_dataset_create_waves': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    'vr_dataset_add_waves': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int)]),
+    'vr_dataset_add_pcm': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     'vr_dataset_destroy': (ctypes.c_int, [ctypes.c_void_p]),
+    'vr_pipeline_buffer': (ctypes.c_int, [ctypes.c_void_p, c_i64p, ctypes.c_int]),
     'vr_dataset_add': (ctypes.c_int, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]),
     'vr_dataset_info': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), c_i64p]),
     'vr_dataset_rows': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64p]),
@@ -365,6 +371,24 @@ class Window(ctypes.Structure):             # include/vr_mi355.h: vr_window
     _fields_ = [('song', ctypes.c_int), ('reserved', ctypes.c_int), ('start', ctypes.c_int64), ('scale', ctypes.c_float)]
 
 
+def _wave_pair(mix, inst):
+    """-> (pointer, pointer, n, on_device) of two aligned float32 [2, n] waves, numpy or cuda"""
+    if tuple(mix.shape) != tuple(inst.shape) or len(mix.shape) != 2 or mix.shape[0] != 2:
+        raise ValueError('a pair of aligned waves is two [2, n] arrays of one n, found %s and %s' % (tuple(mix.shape), tuple(inst.shape)))
+    if isinstance(mix, np.ndarray) != isinstance(inst, np.ndarray):
+        raise ValueError('both waves on the host or both on the device')
+    if isinstance(mix, np.ndarray):
+        for w in (mix, inst):
+            if w.dtype != np.float32 or not w.flags['C_CONTIGUOUS']:
+                raise ValueError('a host wave must be a C-contiguous float32 array')
+        return np_ptr(mix), np_ptr(inst), int(mix.shape[1]), 0
+    import torch
+    for w in (mix, inst):
+        if not w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError('a device wave must be a contiguous float32 cuda tensor')
+    return ctypes.c_void_p(mix.data_ptr()), ctypes.c_void_p(inst.data_ptr()), int(mix.shape[1]), 1
+
+
 class Dataset:
     """Owns one vr_dataset: songs resident on one GPU, independent of any Handle."""
 
@@ -372,6 +396,19 @@ class Dataset:
         self._d = ctypes.c_void_p()
         check(lib().vr_dataset_create(int(device), int(bins), ctypes.byref(self._d)))
         self.device, self.bins = int(device), int(bins)
+        self.n_fft = self.hop_length = None
+
+    @classmethod
+    def waves(cls, device, n_fft, hop_length):
+        """A WAVE store (vr_dataset_create_waves): songs are kept as their two aligned waves, and batches, windows and peaks form the
+        STFT rows they need on the device.  hop_length != n_fft / 2 or an n_fft the frame-tiled STFT does not take: VRUnsupported,
+        raised without a device."""
+        self = cls.__new__(cls)
+        self._d = ctypes.c_void_p()
+        check(lib().vr_dataset_create_waves(int(device), int(n_fft), int(hop_length), ctypes.byref(self._d)))
+        self.device, self.bins = int(device), int(n_fft) // 2 + 1
+        self.n_fft, self.hop_length = int(n_fft), int(hop_length)
+        return self
 
     def close(self):
         if getattr(self, '_d', None) and self._d.value:
@@ -394,6 +431,41 @@ class Dataset:
         """One song: X, y complex64 [rows, 2, bins], C-contiguous (a np.memmap of the cache file will do) -> its index."""
         song = ctypes.c_int()
         check(lib().vr_dataset_add(self.d, np_ptr(X), np_ptr(y), int(X.shape[0]), ctypes.byref(song)))
+        return int(song.value)
+
+    def add_waves(self, mix, inst):
+        """One song of a wave store: mix, inst aligned float32 [2, n], both C-contiguous numpy arrays or both cuda tensors -> its index."""
+        pm, pi, n, on_dev = _wave_pair(mix, inst)
+        song = ctypes.c_int()
+        check(lib().vr_dataset_add_waves(self.d, pm, pi, on_dev, n, ctypes.byref(song)))
+        return int(song.value)
+
+    def add_pcm(self, mix, inst):
+        """One song of a wave store as the files' sample bytes: mix, inst audio.RawPcm of equal frames (`bytes` a uint8 numpy array or
+        cuda tensor, both on the same side); the bytes are stored as they are -> its index."""
+        if int(mix.frames) != int(inst.frames):
+            raise ValueError('add_pcm: %d and %d frames, a pair has as many of both' % (mix.frames, inst.frames))
+        ptrs, sides = [], []
+        for r in (mix, inst):
+            if r.fmt not in PCM_SAMPLE_BYTES:
+                raise ValueError('add_pcm: unknown sample format %d' % r.fmt)
+            need = r.frames * r.channels * PCM_SAMPLE_BYTES[r.fmt]
+            b = r.bytes
+            if isinstance(b, np.ndarray):
+                if b.dtype != np.uint8 or not b.flags['C_CONTIGUOUS'] or b.size < need:
+                    raise ValueError('add_pcm: bytes must be a C-contiguous uint8 array of at least %d bytes' % need)
+                ptrs.append(ctypes.c_void_p(b.ctypes.data))
+                sides.append(0)
+            else:
+                if not b.is_cuda or not b.is_contiguous() or b.element_size() != 1 or b.numel() < need:
+                    raise ValueError('add_pcm: bytes must be a contiguous uint8 cuda tensor of at least %d bytes' % need)
+                ptrs.append(ctypes.c_void_p(b.data_ptr()))
+                sides.append(1)
+        if sides[0] != sides[1]:
+            raise ValueError('add_pcm: both waves on the host or both on the device')
+        song = ctypes.c_int()
+        check(lib().vr_dataset_add_pcm(self.d, ptrs[0], ptrs[1], sides[0], int(mix.frames), mix.channels, inst.channels, mix.fmt, inst.fmt,
+                                       ctypes.byref(song)))
         return int(song.value)
 
     def info(self):
@@ -445,6 +517,13 @@ class Handle:
         if not self._h.value:
             raise VRError('handle is closed')
         return self._h
+
+    def pipeline_buffer_bytes(self, release=False):
+        """vr_pipeline_buffer: device bytes this handle holds for the training input pipeline (over a wave store: the rows of one batch),
+        which vr_arena_bytes does not count; release=True frees them (the next batch allocates again)."""
+        b = ctypes.c_int64()
+        check(lib().vr_pipeline_buffer(self.h, ctypes.byref(b), 1 if release else 0))
+        return int(b.value)
 
     def param_infos(self):
         out = []
