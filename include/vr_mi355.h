@@ -545,6 +545,30 @@ int vr_augment_batch_complex(vr_handle h, const float* X, const float* y, const 
                              const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_out, float* y_out,
                              int out_on_device);
 
+/* The extended descriptor and its entry points: two augmentations beyond lib/dataset.py's four.  vr_aug stays 16
+ * bytes; vr_aug_ex is its four fields, with the same meaning, and two gains (24 bytes).  Flag bits beyond 0-6:
+ *   bit 7  VR_AUG_REMIX     the partner (X_mix, y_mix of the sample; mix_song, mix_start of its vr_crop) is a REMIX partner: after
+ *                           /coef_mix and the partner's swap (bit 5, its place for a mixup partner) v = X_j - y_j is the partner's
+ *                           vocals, and the sample becomes y = gain_y * y, X = y + gain_v * v -- whatever inst-only made of X.  The
+ *                           sample's own bits 0-2 and 8 apply first.  lam is ignored.
+ *   bit 8  VR_AUG_MONO      lib/dataset.py:81-83 (commented out there), after inst-only: both channels of X and of y become
+ *                           0.5f * (L + R); the two channels of the output hold the same bits.
+ *   bit 9  VR_AUG_MIX_MONO  bit 8 for a mixup partner (bit 3).
+ * One float32 rounding per operation written above.  The _ex entry points take what their namesakes take, check what they check and,
+ * over a table in which no sample has a bit above 6, launch what they launch: the same bytes.  A remix reads the four crops a mixup
+ * reads; over a wave store the scratch is what it was (vr_pipeline_buffer).  More refusals, all VR_ERR_BAD_ARGUMENT before anything is
+ * launched, vr_last_error() naming the sample: bits 3 and 7 both set; bit 7 with bit 4 or 6 (a remix partner is not reduced and not
+ * inst-only); bit 7 with a gain that is not finite; and, for bit 7 as for bit 3, no partner crops (vr_augment_batch_ex), mix_song < 0 or
+ * the partner's rows outside its song (vr_dataset_batch_ex). */
+typedef struct vr_aug_ex { float coef; float coef_mix; float lam; int flags; float gain_y; float gain_v; } vr_aug_ex;
+enum { VR_AUG_MIXUP = 8, VR_AUG_REMIX = 128, VR_AUG_MONO = 256, VR_AUG_MIX_MONO = 512 };
+int vr_augment_batch_ex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug_ex* desc,
+                        const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
+                        int out_on_device);
+int vr_augment_batch_complex_ex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug_ex* desc,
+                                const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_out, float* y_out,
+                                int out_on_device);
+
 /* The training set resident in HBM: load every song's cached spectrogram pair once, then each batch is one vr_dataset_batch -- the
  * kernel of vr_augment_batch reading the crops where they lie, no file read and no host-to-device copy of spectrogram rows.
  *   vr_dataset_create   an empty store on `device` for spectrograms of `bins` bins.  It owns its own device allocations and nothing
@@ -575,6 +599,11 @@ int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_a
 /* vr_dataset_batch with the outputs of vr_augment_batch_complex: X_out, y_out [B][2][bins][T] complex64; same checks, same errors. */
 int vr_dataset_batch_complex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
                              float* X_out, float* y_out, int out_on_device);
+/* The two with vr_aug_ex descriptors (above): a remix partner sits in mix_song / mix_start and is checked as a mixup partner is. */
+int vr_dataset_batch_ex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug_ex* desc, const float* reduction_weight, int B, int T,
+                        float* X_mag, float* y_mag, int out_on_device);
+int vr_dataset_batch_complex_ex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug_ex* desc, const float* reduction_weight, int B,
+                                int T, float* X_out, float* y_out, int out_on_device);
 
 /* The peak of one resident song, taken on the device from its rows: *peak = np.max([np.abs(X).max(), np.abs(y).max()]) of the song's two
  * arrays, bit for bit (lib/dataset.py:214, the coef of a training row and the normaliser of a validation song).  np.abs of a complex64

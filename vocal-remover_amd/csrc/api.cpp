@@ -689,21 +689,28 @@ int vr_param_arena(vr_handle h, float** device_ptr, int64_t* numel) {
     });
 }
 
-static int augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug* desc,
+// ex: desc is a table of vr_aug_ex, the _ex entry points (a remix partner's crops lie where a mixup partner's do)
+static int augment_batch(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const void* desc,
                          const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
-                         int out_on_device, bool out_complex) {
+                         int out_on_device, bool out_complex, bool ex = false) {
+    static_assert(sizeof(vr_aug_ex) == sizeof(vr::AugDescEx) && offsetof(vr_aug_ex, gain_y) == offsetof(vr::AugDescEx, gain_y) &&
+                      offsetof(vr_aug_ex, gain_v) == offsetof(vr::AugDescEx, gain_v) && sizeof(vr_aug_ex) == 24,
+                  "C ABI struct and its kernels.h twin");
+    static_assert(VR_AUG_REMIX == vr::kAugRemix && VR_AUG_MONO == vr::kAugMono && VR_AUG_MIX_MONO == vr::kAugMixMono && VR_AUG_MIXUP == vr::kAugMix,
+                  "flag bits of the header and of kernels.h");
     NEED(h);
     return guard([&] {
         VR_CHECK(X && y && desc && X_mag && y_mag, VR_ERR_BAD_ARGUMENT, "null argument");
         bool mix = false, red = false;
         for (int b = 0; b < B; ++b) {
-            mix = mix || (desc[b].flags & 8);
-            red = red || (desc[b].flags & (1 | 16));
+            const int flags = ex ? static_cast<const vr_aug_ex*>(desc)[b].flags : static_cast<const vr_aug*>(desc)[b].flags;
+            mix = mix || (flags & (ex ? 8 | VR_AUG_REMIX : 8));
+            red = red || (flags & (1 | 16));
         }
-        VR_CHECK(!mix || (X_mix && y_mix), VR_ERR_BAD_ARGUMENT, "mixup flagged but no partner crops given");
+        VR_CHECK(!mix || (X_mix && y_mix), VR_ERR_BAD_ARGUMENT, ex ? "mixup or remix flagged but no partner crops given" : "mixup flagged but no partner crops given");
         VR_CHECK(!red || reduction_weight, VR_ERR_BAD_ARGUMENT, "vocal reduction flagged but no reduction_weight given");
         h->m.augment_api(X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device != 0, X_mag, y_mag,
-                         out_on_device != 0, out_complex);
+                         out_on_device != 0, out_complex, ex);
     });
 }
 
@@ -822,10 +829,22 @@ int vr_augment_batch_complex(vr_handle h, const float* X, const float* y, const 
     return augment_batch(h, X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device, X_out, y_out, out_on_device, true);
 }
 
+int vr_augment_batch_ex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug_ex* desc,
+                        const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_mag, float* y_mag,
+                        int out_on_device) {
+    return augment_batch(h, X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device, X_mag, y_mag, out_on_device, false, true);
+}
+
+int vr_augment_batch_complex_ex(vr_handle h, const float* X, const float* y, const float* X_mix, const float* y_mix, const vr_aug_ex* desc,
+                                const float* reduction_weight, int B, int T, int bins, int in_on_device, float* X_out, float* y_out,
+                                int out_on_device) {
+    return augment_batch(h, X, y, X_mix, y_mix, desc, reduction_weight, B, T, bins, in_on_device, X_out, y_out, out_on_device, true, true);
+}
+
 // The tables and the batch size are checked before the handle and the store, so that a caller's argument error is reported without a
 // device (as vr_separate_many does).
-static int dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,
-                         float* X_mag, float* y_mag, int out_on_device, bool out_complex) {
+static int dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const void* desc, const float* reduction_weight, int B, int T,
+                         float* X_mag, float* y_mag, int out_on_device, bool out_complex, bool ex = false) {
     if (B <= 0) { g_err = "B must be positive"; return VR_ERR_BAD_ARGUMENT; }
     if (!crops || !desc || !X_mag || !y_mag) { g_err = "null table"; return VR_ERR_BAD_ARGUMENT; }
     NEED(h);
@@ -833,8 +852,18 @@ static int dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const 
     static_assert(sizeof(vr_crop) == sizeof(vr::ResidentCrop) && sizeof(vr_aug) == sizeof(vr::AugDesc), "C ABI structs and their kernels.h twins");
     return guard([&] {
         h->m.dataset_batch_api(d->set, reinterpret_cast<const vr::ResidentCrop*>(crops), desc, reduction_weight, B, T, X_mag, y_mag,
-                               out_on_device != 0, out_complex);
+                               out_on_device != 0, out_complex, ex);
     });
+}
+
+int vr_dataset_batch_ex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug_ex* desc, const float* reduction_weight, int B, int T,
+                        float* X_mag, float* y_mag, int out_on_device) {
+    return dataset_batch(h, d, crops, desc, reduction_weight, B, T, X_mag, y_mag, out_on_device, false, true);
+}
+
+int vr_dataset_batch_complex_ex(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug_ex* desc, const float* reduction_weight, int B,
+                                int T, float* X_out, float* y_out, int out_on_device) {
+    return dataset_batch(h, d, crops, desc, reduction_weight, B, T, X_out, y_out, out_on_device, true, true);
 }
 
 int vr_dataset_batch(vr_handle h, vr_dataset d, const vr_crop* crops, const vr_aug* desc, const float* reduction_weight, int B, int T,

@@ -36,6 +36,11 @@ __device__ __forceinline__ void aug_element(const float2* __restrict__ X, const 
     yo = y;
 }
 
+// a = 0.5f * (a + o): the mono augmentation of one element from its two channels (lib/dataset.py:81-83, X.mean(axis=0))
+__device__ __forceinline__ void aug_mono(float2& a, float2 o) {
+    a = make_float2(__fmul_rn(0.5f, __fadd_rn(a.x, o.x)), __fmul_rn(0.5f, __fadd_rn(a.y, o.y)));
+}
+
 // grid: (ceil(T/32), ceil(bins/32), B*2); block (32, 8).  32x32 tile transposed through LDS so that both the
 // reads (bin-contiguous) and the writes (frame-contiguous) are coalesced.
 // Two forms, which differ only in where the four crops of sample b lie.  Dense (vr_augment_batch): X, Y, Xi, Yi are staged batches,
@@ -45,17 +50,25 @@ __device__ __forceinline__ void aug_element(const float2* __restrict__ X, const 
 // kComplex (training a complex-mask model): everything before the final np.abs is the same; the augmented x, y themselves are stored,
 // complex64 [B][2][bins][T].  The real and imaginary parts cross the transpose in tiles of their own (four float tiles of 33-word rows,
 // the bank-conflict-free layout of the magnitude form; a float2 tile would put a 64-bit read at a 66-word stride).
-template <bool kResident, bool kComplex>
+// DESC = AugDescEx (the _ex entry points): three more branches, each behind `if constexpr (kEx)`, so the AugDesc
+// instantiations compile from the statements they always had.  d.flags is uniform over the block: none of them diverges.
+//   mono    the element of the other channel is read as well and both blocks of the sample store 0.5f * (L + R); L + R is R + L in
+//           IEEE arithmetic, so the two channels of the output hold the same bits.  Only a sample (or partner) with the bit reads twice.
+//   remix   the partner's crop with its own coef and swap bit, no reduce and no inst-only: v = X_j - y_j, y = g_y y, X = y + g_v v.
+//           One rounding per operation, spelled with the _rn intrinsics, so no instantiation may contract them differently.
+template <bool kResident, bool kComplex, class DESC = AugDesc>
 __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kResident, const AugCrops*, const float2*> __restrict__ X,
                                                       const float2* __restrict__ Y, const float2* __restrict__ Xi,
-                                                      const float2* __restrict__ Yi, const AugDesc* __restrict__ desc,
+                                                      const float2* __restrict__ Yi, const DESC* __restrict__ desc,
                                                       const float* __restrict__ rw, int T, int bins, float* __restrict__ Xmag,
                                                       float* __restrict__ Ymag) {
     constexpr int NT = kComplex ? 2 : 1;
     __shared__ float tx[NT][32][33], ty[NT][32][33];
     const int b = blockIdx.z >> 1, c = blockIdx.z & 1;
     const int t0 = blockIdx.x * 32, bin0 = blockIdx.y * 32;
-    const AugDesc d = desc[b];
+    constexpr bool kEx = std::is_same<DESC, AugDescEx>::value;
+    static_assert(kEx || std::is_same<DESC, AugDesc>::value, "augment_kernel: unknown descriptor");
+    const DESC d = desc[b];
     const float2* __restrict__ Xc;
     long long base;
     if constexpr (kResident) {
@@ -73,9 +86,32 @@ __global__ __launch_bounds__(256) void augment_kernel(std::conditional_t<kReside
         if (t < T && bin < bins) {
             const float w = rw ? rw[bin] : 0.f;
             aug_element(Xc, Y, base, bins, t, c, bin, d.coef, d.flags & 1, d.flags & 2, d.flags & 4, w, x, y);
+            if constexpr (kEx) {
+                if (d.flags & kAugMono) {
+                    float2 xo, yo;
+                    aug_element(Xc, Y, base, bins, t, 1 - c, bin, d.coef, d.flags & 1, d.flags & 2, d.flags & 4, w, xo, yo);
+                    aug_mono(x, xo);
+                    aug_mono(y, yo);
+                }
+                if (d.flags & kAugRemix) {
+                    float2 xj, yj;
+                    aug_element(Xi, Yi, base, bins, t, c, bin, d.coef_mix, 0, d.flags & 32, 0, w, xj, yj);
+                    y = make_float2(__fmul_rn(d.gain_y, y.x), __fmul_rn(d.gain_y, y.y));
+                    x = make_float2(__fadd_rn(y.x, __fmul_rn(d.gain_v, __fsub_rn(xj.x, yj.x))),
+                                    __fadd_rn(y.y, __fmul_rn(d.gain_v, __fsub_rn(xj.y, yj.y))));
+                }
+            }
             if (d.flags & 8) {
                 float2 xi, yi;
                 aug_element(Xi, Yi, base, bins, t, c, bin, d.coef_mix, d.flags & 16, d.flags & 32, d.flags & 64, w, xi, yi);
+                if constexpr (kEx) {
+                    if (d.flags & kAugMixMono) {
+                        float2 xo, yo;
+                        aug_element(Xi, Yi, base, bins, t, 1 - c, bin, d.coef_mix, d.flags & 16, d.flags & 32, d.flags & 64, w, xo, yo);
+                        aug_mono(xi, xo);
+                        aug_mono(yi, yo);
+                    }
+                }
                 const float l = d.lam, m = 1.f - d.lam;
                 x = make_float2(l * x.x + m * xi.x, l * x.y + m * xi.y);
                 y = make_float2(l * y.x + m * yi.x, l * y.y + m * yi.y);
@@ -354,6 +390,23 @@ void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const f
     const float2* const unused = nullptr;
     if (out_complex) VR_LAUNCH((augment_kernel<true, true>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
     else VR_LAUNCH((augment_kernel<true, false>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDescEx* desc, const float* rw,
+                    int B, int T, int bins, float* Xmag, float* Ymag, bool out_complex, hipStream_t st) {
+    const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
+    if (out_complex) VR_LAUNCH((augment_kernel<false, true, AugDescEx>), grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    else VR_LAUNCH((augment_kernel<false, false, AugDescEx>), grid, block, 0, st, X, Y, Xi, Yi, desc, rw, T, bins, Xmag, Ymag);
+    VR_HIP(hipGetLastError());
+}
+
+void launch_augment_resident(const AugCrops* table, const AugDescEx* desc, const float* rw, int B, int T, int bins, float* Xmag,
+                             float* Ymag, bool out_complex, hipStream_t st) {
+    const dim3 grid((T + 31) / 32, (bins + 31) / 32, B * 2), block(32, 8);
+    const float2* const unused = nullptr;
+    if (out_complex) VR_LAUNCH((augment_kernel<true, true, AugDescEx>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
+    else VR_LAUNCH((augment_kernel<true, false, AugDescEx>), grid, block, 0, st, table, unused, unused, unused, desc, rw, T, bins, Xmag, Ymag);
     VR_HIP(hipGetLastError());
 }
 

@@ -65,6 +65,16 @@ void launch_augment(const float2* X, const float2* Y, const float2* Xi, const fl
 struct AugCrops { const float2 *X, *y, *X_mix, *y_mix; };
 void launch_augment_resident(const AugCrops* table, const AugDesc* desc, const float* rw, int B, int T, int bins, float* Xmag,
                              float* Ymag, bool out_complex, hipStream_t st);
+// the extended descriptor (vr_aug_ex): AugDesc's four fields and the two gains of a remix.  Flag bits beyond
+// AugDesc's 0-6: kAugRemix (the partner is a remix partner: X = g_y y + g_v (X_j - y_j), y = g_y y), kAugMono (both channels become
+// 0.5f * (L + R)) and kAugMixMono (the same for a mixup partner).  The two launchers above instantiated with it: same grid, same tile,
+// same four crops a sample.
+struct AugDescEx { float coef, coef_mix, lam; int flags; float gain_y, gain_v; };
+constexpr int kAugMix = 8, kAugRemix = 128, kAugMono = 256, kAugMixMono = 512, kAugExBits = kAugRemix | kAugMono | kAugMixMono;
+void launch_augment(const float2* X, const float2* Y, const float2* Xi, const float2* Yi, const AugDescEx* desc, const float* rw,
+                    int B, int T, int bins, float* Xmag, float* Ymag, bool out_complex, hipStream_t st);
+void launch_augment_resident(const AugCrops* table, const AugDescEx* desc, const float* rw, int B, int T, int bins, float* Xmag,
+                             float* Ymag, bool out_complex, hipStream_t st);
 // windows of resident songs (vr_dataset_windows): one entry per sample, the pointers at row 0 of the song's slabs;
 // sample b is rows [start, start + T) of them, a row outside [0, rows) zero, every value read times `scale`
 struct SongWindow { const float2 *X, *y; long long rows, start; float scale; int reserved; };

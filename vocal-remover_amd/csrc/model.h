@@ -377,10 +377,11 @@ public:
     std::string profile_report;                          // per-kernel-name totals of the last profiled step (vr_profile_report)
     void profile_begin();
     void augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
-                     int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
+                     int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false,
+                     bool ex = false);                 // (ex: desc is a table of AugDescEx, the _ex entry points)
     void wave_store_check(const ResidentSet& set, const char* who, int B) const;
     void dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
-                           float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false);
+                           float* Xmag, float* ymag, bool out_on_dev, bool out_complex = false, bool ex = false);
     void dataset_windows_api(const ResidentSet& set, const ResidentWindow* w, int B, int T, float* Xmag, float* ymag, bool out_on_dev,
                              bool out_complex = false);
     char* aug_buf = nullptr; size_t aug_cap = 0;         // staging of the training input pipeline

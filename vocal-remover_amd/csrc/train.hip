@@ -637,13 +637,40 @@ long long Model::pipeline_buffer(bool release) {
     return held;
 }
 
+// What the _ex entry points refuse in a descriptor table, before anything is launched (the rows of a remix partner are checked where
+// a mixup partner's are).  -> true when no sample carries a new bit; `plain` then holds the table as AugDesc, and the caller goes the
+// way of the old entry point: the same instantiation, so the same bytes.
+static bool aug_ex_check(const AugDescEx* d, int B, const char* who, std::vector<AugDesc>& plain) {
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const int flags = d[b].flags;
+        const std::string at = std::string(who) + ": sample " + std::to_string(b) + ": ";
+        any = any || (flags & kAugExBits);
+        if (!(flags & kAugRemix)) continue;
+        VR_CHECK(!(flags & kAugMix), -2, at + "remix and mixup are both flagged; a sample has one partner");
+        VR_CHECK(!(flags & (16 | 64)), -2, at + "remix flagged with the partner's " + ((flags & 16) ? "reduce" : "inst-only") +
+                                               " bit; a remix partner takes its swap bit only");
+        VR_CHECK(std::isfinite(d[b].gain_y), -2, at + "gain_y is not finite");
+        VR_CHECK(std::isfinite(d[b].gain_v), -2, at + "gain_v is not finite");
+    }
+    if (any) return false;
+    plain.resize((size_t)B);
+    for (int b = 0; b < B; ++b) plain[b] = AugDesc{d[b].coef, d[b].coef_mix, d[b].lam, d[b].flags};
+    return true;
+}
+
 // Training input pipeline (lib/dataset.py:105-120 after the random draws and the file reads), see augment.hip.
 void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const float* yi, const void* desc, const float* rw,
-                        int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex) {
+                        int B, int T, int bins, bool in_on_dev, float* Xmag, float* ymag, bool out_on_dev, bool out_complex, bool ex) {
     DeviceGuard dev_guard(device);
     VR_CHECK(B > 0 && T > 0 && bins > 0, -2, "augment: empty batch");
+    std::vector<AugDesc> plain;
+    if (ex && aug_ex_check(static_cast<const AugDescEx*>(desc), B, "vr_augment_batch_ex", plain)) {       // no new bit: today's launch
+        desc = plain.data();
+        ex = false;
+    }
     const size_t crop_b = (size_t)B * T * 2 * bins * sizeof(float2), out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
-    const size_t desc_b = (size_t)B * sizeof(AugDesc), rw_b = (size_t)bins * sizeof(float);
+    const size_t desc_b = (size_t)B * (ex ? sizeof(AugDescEx) : sizeof(AugDesc)), rw_b = (size_t)bins * sizeof(float);
     auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
     size_t need = up256(desc_b) + up256(rw_b);
     if (!in_on_dev) need += 4 * up256(crop_b);
@@ -651,7 +678,7 @@ void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const
     aug_reserve(need);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = aug_buf + off; off += up256(bytes); return p; };
-    AugDesc* dd = reinterpret_cast<AugDesc*>(take(desc_b));
+    char* dd = take(desc_b);
     float* drw = reinterpret_cast<float*>(take(rw_b));
     VR_HIP(hipMemcpyAsync(dd, desc, desc_b, hipMemcpyHostToDevice, stream));
     if (rw) VR_HIP(hipMemcpyAsync(drw, rw, rw_b, hipMemcpyHostToDevice, stream));
@@ -666,8 +693,12 @@ void Model::augment_api(const float* Xc, const float* yc, const float* Xi, const
     }
     float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(take(out_b));
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(take(out_b));
-    launch_augment(dev[0], dev[1], dev[2] ? dev[2] : dev[0], dev[3] ? dev[3] : dev[1], dd, rw ? drw : nullptr, B, T, bins, ox, oy,
-                   out_complex, stream);
+    if (ex)
+        launch_augment(dev[0], dev[1], dev[2] ? dev[2] : dev[0], dev[3] ? dev[3] : dev[1], reinterpret_cast<const AugDescEx*>(dd),
+                       rw ? drw : nullptr, B, T, bins, ox, oy, out_complex, stream);
+    else
+        launch_augment(dev[0], dev[1], dev[2] ? dev[2] : dev[0], dev[3] ? dev[3] : dev[1], reinterpret_cast<const AugDesc*>(dd),
+                       rw ? drw : nullptr, B, T, bins, ox, oy, out_complex, stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));
@@ -998,16 +1029,24 @@ void Model::dataset_windows_api(const ResidentSet& set, const ResidentWindow* w,
 // pointer table, descriptors and reduction weight go to the handle's aug_buf in ONE copy and augment_kernel<true> reads the crops
 // where they lie.
 void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops, const void* desc, const float* rw, int B, int T,
-                              float* Xmag, float* ymag, bool out_on_dev, bool out_complex) {
+                              float* Xmag, float* ymag, bool out_on_dev, bool out_complex, bool ex) {
     VR_CHECK(set.device == device, -2, "vr_dataset_batch: the handle is on device " + std::to_string(device) + ", the dataset on device " +
                                            std::to_string(set.device));
     VR_CHECK(T > 0, -2, "vr_dataset_batch: T must be positive");
     if (set.waves) wave_store_check(set, "vr_dataset_batch", B);
-    const AugDesc* dh = static_cast<const AugDesc*>(desc);
+    std::vector<AugDesc> plain;
+    if (ex && aug_ex_check(static_cast<const AugDescEx*>(desc), B, "vr_dataset_batch_ex", plain)) {       // no new bit: today's launch
+        desc = plain.data();
+        ex = false;
+    }
+    // (ex) the table is read through its stride; a partner is a mixup partner or a remix partner
+    const size_t desc_sz = ex ? sizeof(AugDescEx) : sizeof(AugDesc);
+    const int partner = ex ? (kAugMix | kAugRemix) : kAugMix;
+    auto flags_of = [&](int b) { return reinterpret_cast<const AugDesc*>(static_cast<const char*>(desc) + (size_t)b * desc_sz)->flags; };
     const int bins = set.bins, n_songs = (int)set.songs.size();
     std::vector<char> host;
     auto up256 = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t tab_b = (size_t)B * sizeof(AugCrops), desc_b = (size_t)B * sizeof(AugDesc), rw_b = (size_t)bins * sizeof(float);
+    const size_t tab_b = (size_t)B * sizeof(AugCrops), desc_b = (size_t)B * desc_sz, rw_b = (size_t)bins * sizeof(float);
     const size_t out_b = (size_t)B * 2 * bins * T * (out_complex ? sizeof(float2) : sizeof(float));
     const size_t head = up256(tab_b) + up256(desc_b) + (rw ? up256(rw_b) : 0);
     host.resize(head);
@@ -1025,7 +1064,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
         return (size_t)start * 2 * bins;
     };
     for (int b = 0; b < B; ++b) {
-        const int flags = dh[b].flags;
+        const int flags = flags_of(b);
         VR_CHECK(!(flags & (1 | 16)) || rw, -2, "vr_dataset_batch: sample " + std::to_string(b) +
                                                    ": vocal reduction flagged but no reduction_weight given");
         const size_t o = rows_at(b, "", crops[b].song, crops[b].start);
@@ -1036,10 +1075,11 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
             segs.push_back(set.crop_seg(crops[b].song, 0, crops[b].start, T, nullptr));
             segs.push_back(set.crop_seg(crops[b].song, 1, crops[b].start, T, nullptr));
         }
-        if (flags & 8) {
-            VR_CHECK(crops[b].mix_song >= 0, -2, "vr_dataset_batch: sample " + std::to_string(b) + ": mixup flagged but mix_song is " +
-                                                     std::to_string(crops[b].mix_song));
-            const size_t om = rows_at(b, "mixup partner: ", crops[b].mix_song, crops[b].mix_start);
+        if (flags & partner) {
+            const bool remix = ex && (flags & kAugRemix);
+            VR_CHECK(crops[b].mix_song >= 0, -2, "vr_dataset_batch: sample " + std::to_string(b) + (remix ? ": remix" : ": mixup") +
+                                                     " flagged but mix_song is " + std::to_string(crops[b].mix_song));
+            const size_t om = rows_at(b, remix ? "remix partner: " : "mixup partner: ", crops[b].mix_song, crops[b].mix_start);
             const ResidentSet::Song& m = set.songs[crops[b].mix_song];
             tab[b].X_mix = m.X + om;
             tab[b].y_mix = m.y + om;
@@ -1049,7 +1089,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
             }
         }
     }
-    std::memcpy(host.data() + up256(tab_b), dh, desc_b);
+    std::memcpy(host.data() + up256(tab_b), desc, desc_b);
     if (rw) std::memcpy(host.data() + up256(tab_b) + up256(desc_b), rw, rw_b);
 
     DeviceGuard dev_guard(device);
@@ -1065,7 +1105,7 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
         char* scratch = aug_buf + head + out_all + seg_b;
         for (size_t e = 0; e < segs.size(); ++e) segs[e].dst = reinterpret_cast<float2*>(scratch + e * rows_b);
         for (int b = 0; b < B; ++b) {
-            const int e = first[b], em = (dh[b].flags & 8) ? e + 2 : e;
+            const int e = first[b], em = (flags_of(b) & partner) ? e + 2 : e;
             tab[b] = AugCrops{segs[e].dst, segs[e + 1].dst, segs[em].dst, segs[em + 1].dst};
         }
         CropSeg* dseg = reinterpret_cast<CropSeg*>(aug_buf + head + out_all);
@@ -1074,11 +1114,12 @@ void Model::dataset_batch_api(const ResidentSet& set, const ResidentCrop* crops,
     }
     VR_HIP(hipMemcpyAsync(aug_buf, host.data(), head, hipMemcpyHostToDevice, stream));
     const AugCrops* dtab = reinterpret_cast<const AugCrops*>(aug_buf);
-    const AugDesc* dd = reinterpret_cast<const AugDesc*>(aug_buf + up256(tab_b));
+    const char* dd = aug_buf + up256(tab_b);
     const float* drw = rw ? reinterpret_cast<const float*>(aug_buf + up256(tab_b) + up256(desc_b)) : nullptr;
     float* ox = out_on_dev ? Xmag : reinterpret_cast<float*>(aug_buf + head);
     float* oy = out_on_dev ? ymag : reinterpret_cast<float*>(aug_buf + head + up256(out_b));
-    launch_augment_resident(dtab, dd, drw, B, T, bins, ox, oy, out_complex, stream);
+    if (ex) launch_augment_resident(dtab, reinterpret_cast<const AugDescEx*>(dd), drw, B, T, bins, ox, oy, out_complex, stream);
+    else launch_augment_resident(dtab, reinterpret_cast<const AugDesc*>(dd), drw, B, T, bins, ox, oy, out_complex, stream);
     if (!out_on_dev) {
         VR_HIP(hipMemcpyAsync(Xmag, ox, out_b, hipMemcpyDeviceToHost, stream));
         VR_HIP(hipMemcpyAsync(ymag, oy, out_b, hipMemcpyDeviceToHost, stream));

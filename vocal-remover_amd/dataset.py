@@ -33,6 +33,35 @@ class _Aug(ctypes.Structure):               # include/vr_mi355.h: vr_aug
     _fields_ = [('coef', ctypes.c_float), ('coef_mix', ctypes.c_float), ('lam', ctypes.c_float), ('flags', ctypes.c_int)]
 
 
+class _AugEx(ctypes.Structure):             # include/vr_mi355.h: vr_aug_ex (the _ex entry points: remix and mono)
+    _fields_ = _Aug._fields_ + [('gain_y', ctypes.c_float), ('gain_v', ctypes.c_float)]
+
+
+AUG_MIXUP, AUG_REMIX, AUG_MONO, AUG_MIX_MONO = 8, 128, 256, 512          # include/vr_mi355.h: VR_AUG_*
+
+
+def _remix_args(remix_rate, remix_gain, mono_rate):
+    """The three keywords every training class takes beyond the reference's, checked at construction."""
+    try:
+        lo, hi = (float(g) for g in remix_gain)
+    except (TypeError, ValueError):
+        raise ValueError('remix_gain is a pair (lo, hi) of gains, found %r' % (remix_gain,))
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError('remix_gain needs finite 0 < lo <= hi, found %r' % (remix_gain,))
+    return float(remix_rate), (lo, hi), float(mono_rate)
+
+
+def _pack(p):
+    """One plan as the fields of its descriptor -> (partner plan or None, flags, coef_mix, lam, gain_y, gain_v).  The partner of a
+    mixup carries its own three bits at 4-6 and its mono bit at AUG_MIX_MONO; the partner of a remix its swap bit only."""
+    flags, r, m = p['flags'], p.get('remix'), p['mix']
+    if r is not None:
+        return r, flags | AUG_REMIX | (32 if r['swap'] else 0), r['coef'], 1.0, r['gain_y'], r['gain_v']
+    if m is not None:
+        return m, flags | AUG_MIXUP | ((m['flags'] & 7) << 4) | (AUG_MIX_MONO if m['flags'] & AUG_MONO else 0), m['coef'], m['lam'], 1.0, 1.0
+    return None, flags, 1.0, 1.0, 1.0, 1.0
+
+
 def _npy_header(path):
     with open(path, 'rb') as f:
         np.lib.format.read_magic(f)
@@ -55,22 +84,33 @@ def _read_rows(path, start_row, n_rows, out):
         raise ValueError('%s: short read (%d of %d bytes)' % (path, got, n_rows * row_bytes))
 
 
-def _outputs(complex_output, shape, dev, entry):
+def _outputs(complex_output, shape, dev, entry, ex=False):
     """The two output tensors of a batch and the entry point that fills them: float32 magnitudes, or with complex_output the
-    augmented crops themselves as complex64 (the `_complex` variant of the entry point)."""
+    augmented crops themselves as complex64 (the `_complex` variant of the entry point); ex: its `_ex` variant (_AugEx descriptors)."""
     dtype = torch.complex64 if complex_output else torch.float32
-    call = getattr(native.lib(), entry + '_complex' if complex_output else entry)
+    call = getattr(native.lib(), entry + ('_complex' if complex_output else '') + ('_ex' if ex else ''))
     return torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=dtype, device=dev), call
+
+
+def _needs_ex(ds, packed):
+    """The _ex entry points are called only when a new rate is on or a plan of the batch carries a new bit; else today's calls go out."""
+    return ds.remix_rate > 0 or ds.mono_rate > 0 or any(k[1] & (AUG_REMIX | AUG_MONO | AUG_MIX_MONO) for k in packed)
 
 
 class VocalRemoverTrainingSet(object):
     """lib/dataset.py:15-120 with the numeric part on the GPU.  `model` is the vocal_remover_amd CascadedNet
     whose device (and HIP stream) the batches are produced on.  complex_output=True (all four set classes): the batches are the
     augmented complex crops (complex64), what a complex-mask model trains on -- lib/dataset.py:120, the commented `return X, y`;
-    the random draws are the same."""
+    the random draws are the same.
+    Beyond the reference (all three training classes): remix_rate, the chance that a sample becomes a REMIX --
+    g_y * its own instrumental + g_v * the vocals X_j - y_j of a random song's crop, both gains uniform in remix_gain -- instead of
+    taking the mixup draw; mono_rate, the chance of the mono augmentation the reference keeps commented out (lib/dataset.py:81-83).
+    With both at 0 the generator is consumed, and every batch is made, as without them."""
+    remix_rate, remix_gain, mono_rate = 0.0, (0.5, 1.0), 0.0
 
     def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None,
-                 complex_output=False):
+                 complex_output=False, remix_rate=0.0, remix_gain=(0.5, 1.0), mono_rate=0.0):
+        self.remix_rate, self.remix_gain, self.mono_rate = _remix_args(remix_rate, remix_gain, mono_rate)
         self.training_set = training_set
         self.complex_output = bool(complex_output)      # complex64 batches for a complex-mask model: no final np.abs
         self.cropsize = cropsize
@@ -96,6 +136,8 @@ class VocalRemoverTrainingSet(object):
             flags |= 2
         if np.random.uniform() < 0.01:
             flags |= 4
+        if self.mono_rate > 0 and np.random.uniform() < self.mono_rate:          # lib/dataset.py:81-83, where the reference has it
+            flags |= AUG_MONO
         return flags
 
     def _coef(self, row):
@@ -112,6 +154,16 @@ class VocalRemoverTrainingSet(object):
         p = {'paths': (X_path, y_path), 'coef': coef, 'start': int(np.random.randint(0, n_rows - self.cropsize))}
         p['flags'] = self._draw_aug()
         p['mix'] = None
+        if self.remix_rate > 0 and np.random.uniform() < self.remix_rate:       # a remixed sample takes no mixup draw at all
+            j = int(np.random.randint(0, len(self)))
+            Xj, yj = self.training_set[j][:2]
+            r = {'paths': (Xj, yj), 'coef': self._coef(self.training_set[j]),
+                 'start': int(np.random.randint(0, self.read_npy_shape(Xj)[0] - self.cropsize))}
+            r['swap'] = bool(np.random.uniform() < 0.5)
+            r['gain_y'] = float(np.random.uniform(*self.remix_gain))
+            r['gain_v'] = float(np.random.uniform(*self.remix_gain))
+            p['remix'] = r
+            return p
         if np.random.uniform() < self.mixup_rate:
             j = int(np.random.randint(0, len(self)))
             Xj, yj = self.training_set[j][:2]
@@ -133,27 +185,25 @@ class VocalRemoverTrainingSet(object):
         bins = int(self.read_npy_shape(plans[0]['paths'][0])[2])
         X = np.empty((B, T, 2, bins), np.complex64)
         y = np.empty((B, T, 2, bins), np.complex64)
-        any_mix = any(p['mix'] is not None for p in plans)
+        packed = [_pack(p) for p in plans]
+        any_mix = any(k[0] is not None for k in packed)         # (a remix partner's rows are staged where a mixup partner's are)
         Xm = np.zeros((B, T, 2, bins), np.complex64) if any_mix else None
         ym = np.zeros((B, T, 2, bins), np.complex64) if any_mix else None
-        desc = (_Aug * B)()
+        ex = _needs_ex(self, packed)
+        desc = ((_AugEx if ex else _Aug) * B)()
         need_rw = False
-        for b, p in enumerate(plans):
+        for b, (p, (m, flags, coef_mix, lam, gain_y, gain_v)) in enumerate(zip(plans, packed)):
             _read_rows(p['paths'][0], p['start'], T, X[b])
             _read_rows(p['paths'][1], p['start'], T, y[b])
-            flags, coef_mix, lam = p['flags'], 1.0, 1.0
-            if p['mix'] is not None:
-                m = p['mix']
+            if m is not None:
                 _read_rows(m['paths'][0], m['start'], T, Xm[b])
                 _read_rows(m['paths'][1], m['start'], T, ym[b])
-                flags |= 8 | (m['flags'] << 4)
-                coef_mix, lam = m['coef'], m['lam']
             need_rw = need_rw or bool(flags & (1 | 16))
-            desc[b] = _Aug(p['coef'], coef_mix, lam, flags)
+            desc[b] = _AugEx(p['coef'], coef_mix, lam, flags, gain_y, gain_v) if ex else _Aug(p['coef'], coef_mix, lam, flags)
         if need_rw and self.reduction_weight is None:
             raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
         dev = torch.device('cuda', h.device)
-        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, bins, T), dev, 'vr_augment_batch')
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, bins, T), dev, 'vr_augment_batch', ex)
         rw = self.reduction_weight
         native.check(call(
             h.h, native.np_ptr(X), native.np_ptr(y), native.np_ptr(Xm) if any_mix else None,
@@ -218,6 +268,7 @@ class _Resident(object):
     model = None
     complex_output = False
     _store = None
+    remix_rate, remix_gain, mono_rate = 0.0, (0.5, 1.0), 0.0
 
     def _handle(self):
         if self.model is None:
@@ -225,11 +276,11 @@ class _Resident(object):
                                % type(self).__name__)
         return self.model._need_handle()
 
-    def _batch(self, h, crops, desc, rw, T):
+    def _batch(self, h, crops, desc, rw, T, ex=False):
         store = self._store
         B = len(desc)
         dev = torch.device('cuda', h.device)
-        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, store.bins, T), dev, 'vr_dataset_batch')
+        X_mag, y_mag, call = _outputs(self.complex_output, (B, 2, store.bins, T), dev, 'vr_dataset_batch', ex)
         native.check(call(
             h.h, store.d, ctypes.cast(crops, ctypes.c_void_p), ctypes.cast(desc, ctypes.c_void_p),
             native.np_ptr(rw) if rw is not None else None, B, T,
@@ -241,20 +292,18 @@ class _Resident(object):
         song of a plan's pair in it.  One statement of the packing for the rows set and the wave set."""
         plans = [self.plan(i) for i in indices]
         B = len(plans)
-        crops, desc = (native.Crop * B)(), (_Aug * B)()
+        packed = [_pack(p) for p in plans]
+        ex = _needs_ex(self, packed)
+        crops, desc = (native.Crop * B)(), ((_AugEx if ex else _Aug) * B)()
         need_rw = False
-        for b, p in enumerate(plans):
-            flags, coef_mix, lam, mix_song, mix_start = p['flags'], 1.0, 1.0, -1, 0
-            if p['mix'] is not None:
-                m = p['mix']
-                flags |= 8 | (m['flags'] << 4)
-                coef_mix, lam, mix_song, mix_start = m['coef'], m['lam'], self._song_of(m['paths']), m['start']
+        for b, (p, (m, flags, coef_mix, lam, gain_y, gain_v)) in enumerate(zip(plans, packed)):
+            mix_song, mix_start = (-1, 0) if m is None else (self._song_of(m['paths']), m['start'])     # (a mixup or a remix partner)
             need_rw = need_rw or bool(flags & (1 | 16))
             crops[b] = native.Crop(self._song_of(p['paths']), mix_song, p['start'], mix_start)
-            desc[b] = _Aug(p['coef'], coef_mix, lam, flags)
+            desc[b] = _AugEx(p['coef'], coef_mix, lam, flags, gain_y, gain_v) if ex else _Aug(p['coef'], coef_mix, lam, flags)
         if need_rw and self.reduction_weight is None:
             raise ValueError('reduction_rate > 0 needs reduction_weight (train.py:197-205)')
-        return self._batch(h, crops, desc, self.reduction_weight, self.cropsize)
+        return self._batch(h, crops, desc, self.reduction_weight, self.cropsize, ex)
 
     @property
     def nbytes(self):
@@ -294,7 +343,8 @@ class ResidentTrainingSet(_Resident):
     (native.Dataset.peak, the same float32) and keeps it in the set's own copy of the list -- the caller's rows are not written."""
 
     def __init__(self, training_set, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None,
-                 complex_output=False):
+                 complex_output=False, remix_rate=0.0, remix_gain=(0.5, 1.0), mono_rate=0.0):
+        self.remix_rate, self.remix_gain, self.mono_rate = _remix_args(remix_rate, remix_gain, mono_rate)
         self.training_set = [list(row) for row in training_set]      # (a copy: peaks that are None are filled in here at upload)
         self.complex_output = bool(complex_output)
         self.cropsize = cropsize
@@ -586,7 +636,8 @@ class ResidentWaveTrainingSet(_ResidentWaves):
     float song, the sample bytes a PCM song."""
 
     def __init__(self, wave_rows, cropsize, reduction_rate, reduction_weight, mixup_rate, mixup_alpha, model=None, max_bytes=None,
-                 complex_output=False):
+                 complex_output=False, remix_rate=0.0, remix_gain=(0.5, 1.0), mono_rate=0.0):
+        self.remix_rate, self.remix_gain, self.mono_rate = _remix_args(remix_rate, remix_gain, mono_rate)
         self.training_set = [list(row) for row in wave_rows]
         self.complex_output = bool(complex_output)
         self.cropsize = cropsize
